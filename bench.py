@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """bench.py - MU-Diff reverse-diffusion sampling throughput on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--total-slices M] [--sweep 1,2,4,8]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--total-slices M] [--full] [--dump-outputs DIR]
+    python bench.py --sweep 1,2,4,8 [--total-slices M]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, runs W warm-up steps and K timed steps, writes the last timed step's sampled slices if
+--dump-outputs is given, and prints the headline line (ms_per_step = one timed step).  Inputs (weights, condition
+slices, x_init, the device noise of every step) are seeded: the same arguments give the same inputs in every run.
 
 A "step" is one pass of the hot path over one batch of synthetic slices: the complete 4-step
 dual-generator reverse sampling (4 x [G1 -> G2 -> posterior]) of B 256x256 slices per GPU (BASELINE
@@ -24,7 +29,7 @@ strong - a step is one pass over M slices sharded contiguously over the ranks (m
 SURVEY.md section 8(d) item 4, M = 512 there).  `--sweep 1,2,4,8`: runs the strong-scaling bench at every listed GPU
 count that fits the visible devices and prints ONE line {n: slices/s} with the CPU baseline beside it.
 
-One JSON line on rank 0, with
+One JSON line on rank 0.  With --full (and in a --sweep, on its first run) it also holds
   roofline        the dominant kernel (3x3 implicit-GEMM conv on split-precision MFMA, both arithmetic plans): algorithmic FLOPs /
                   per-launch HIP-event time, measured in an instrumented pass of the same workload;
   cpu_baseline    the CPU oracle (port of the reference's PyTorch-CPU path) timed on this host's cores on
@@ -68,12 +73,23 @@ def parse(argv=None):
     ap.add_argument('--total-slices', type=int, default=0, help='strong scaling: a step is one pass over this many slices sharded over the ranks')
     ap.add_argument('--sweep', default='', help='comma-separated GPU counts, e.g. 1,2,4,8: strong-scaling curve + CPU baseline in one line')
     ap.add_argument('--no-graph', action='store_true', help='eager launches instead of hipGraph replay')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the legs beyond the headline: roofline pass, pcie / batch1 / batch16 / batch32 / parity legs, CPU baseline '
+                         '(each can still be switched off with its --no-* flag)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default='',
+                    help='after the timed steps, write the slices sampled in the last step as DIR/samples.npy (float32; '
+                         'DIR/samples.rank<r>.npy per rank when --gpus > 1)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-baseline-full', action='store_true',
-                    help='BASELINE.md section 3 in full: adds the 1-thread figure and B=8 to the default (all cores, B=1, 2 warm-up + 3 timed slices); ~10 min')
+                    help='with --full: BASELINE.md section 3 in full: adds the 1-thread figure and B=8 to the default (all cores, B=1, 2 warm-up + 3 timed slices); ~10 min')
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--no-extras', action='store_true', help='skip the parity / batch1 / batch32 / pcie legs')
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    if a.sweep and a.dump_outputs:
+        ap.error('--dump-outputs applies to one run, not to a --sweep')
+    return a
 
 
 def log(*a):
@@ -175,7 +191,8 @@ def run_sweep(a, argv):
         if n > have:
             skipped.append(n)
             continue
-        args = clean + ['--gpus', str(n), '--total-slices', str(total), '--no-extras']
+        # --full: the CPU baseline and the roofline ride on the first run, as they always did in a sweep
+        args = clean + ['--gpus', str(n), '--total-slices', str(total), '--no-extras'] + ([] if '--full' in clean else ['--full'])
         if have_extras or a.no_cpu_baseline:
             args.append('--no-cpu-baseline')
         if have_extras:
@@ -516,6 +533,25 @@ def parity_wide_cfg3(cfg, dev, g1, g2):
             'ok': bool(max(per_step) <= 1e-3 and np.abs(dps).max() <= 0.05 and np.abs(dss).max() <= 0.001)}
 
 
+DUMP_BYTES = 64_000_000          # --dump-outputs: at most this much in all, over all ranks
+
+
+def dump_outputs(d, x, rank, world):
+    """--dump-outputs: the slices this rank sampled in the last timed step ([n, 1, H, W] fp32) -> d/samples.npy (per rank:
+    d/samples.rank<r>.npy).  Above its share of DUMP_BYTES a fixed seeded sample of whole slices, in their order, is written."""
+    import numpy as np
+    x = x.detach().float().cpu()
+    cap = max(1, DUMP_BYTES // world // (x[0].numel() * 4))
+    if x.shape[0] > cap:
+        keep = torch.randperm(x.shape[0], generator=torch.Generator().manual_seed(0))[:cap].sort().values
+        log(f'dump: {x.shape[0]} slices exceed the {DUMP_BYTES // world} byte share: writing a seeded sample of {cap}')
+        x = x[keep]
+    os.makedirs(d, exist_ok=True)
+    fn = os.path.join(d, 'samples.npy' if world == 1 else f'samples.rank{rank}.npy')
+    np.save(fn, np.ascontiguousarray(x.numpy(), dtype=np.float32))
+    log(f'dump: {fn} {tuple(x.shape)} float32')
+
+
 def timed_batches(sampler_fn, n_iter):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -626,10 +662,7 @@ def worker(a):
             return sampler.sample(cs[0], cs[1], cs[2], x_init, cfg.num_timesteps)
 
     def one_step():
-        out = None
-        for cs in batches:
-            out = one_batch(cs)
-        return out
+        return [one_batch(cs) for cs in batches]       # every batch's result is a fresh tensor: holding them adds no GPU work
 
     def barrier():
         if world > 1:
@@ -648,7 +681,9 @@ def worker(a):
         out = one_step()
     barrier()
     dt_local = dt = time.perf_counter() - t0
-    assert out is None or torch.isfinite(out).all()
+    assert all(bool(torch.isfinite(o).all()) for o in out)
+    if a.dump_outputs and out:
+        dump_outputs(a.dump_outputs, torch.cat(out, 0)[:n_local], rank, world)
     dt = max_over_ranks(dt, dev)
     per_rank = per_rank_rates(n_local * K, dt_local, dev, world) if world > 1 else None
 
@@ -672,7 +707,8 @@ def worker(a):
     }
     flop_per_slice = FLOP_PER_SLICE
 
-    if rank == 0 and not a.no_roofline:
+    # --full: the legs beyond the headline, each with runs of its own after the timed region
+    if rank == 0 and a.full and not a.no_roofline:
         # instrumented eager pass of the same workload: HIP events around every launch of the dominant kernel
         ops.PROFILE.enable()
         S.sample_from_model(coef, g1, c1, g2, c2, c3, cfg.num_timesteps, x_init, None, cfg)
@@ -702,13 +738,14 @@ def worker(a):
             line['kernel_time_ms_per_batch'] = {n: round(v['ms'], 3) for n, v in sorted(prof.items(), key=lambda kv: -kv[1]['ms'])}
             # FLOPs the path actually issues per slice (the loop cache skips what depends on the condition images alone)
             flop_per_slice = sum(v['flops'] for v in prof.values()) / B
-    per_gpu = value / world
-    line['end_to_end'] = {'flop_per_slice_issued': round(flop_per_slice / 1e9, 1), 'flop_per_slice_reference_graph': round(FLOP_PER_SLICE / 1e9, 1),
-                          'fp32_flop_frac': round(per_gpu * flop_per_slice / 1e12 / PEAK_FP32_TFLOPS, 4),
-                          'x3_issued_frac': round(3 * per_gpu * flop_per_slice / 1e12 / PEAK_BF16_TFLOPS, 4),
-                          'fused_hbm_frac': round(per_gpu * FUSED_BYTES_PER_SLICE / 1e9 / PEAK_HBM_GBS, 4)}
+    if a.full:
+        per_gpu = value / world
+        line['end_to_end'] = {'flop_per_slice_issued': round(flop_per_slice / 1e9, 1), 'flop_per_slice_reference_graph': round(FLOP_PER_SLICE / 1e9, 1),
+                              'fp32_flop_frac': round(per_gpu * flop_per_slice / 1e12 / PEAK_FP32_TFLOPS, 4),
+                              'x3_issued_frac': round(3 * per_gpu * flop_per_slice / 1e12 / PEAK_BF16_TFLOPS, 4),
+                              'fused_hbm_frac': round(per_gpu * FUSED_BYTES_PER_SLICE / 1e9 / PEAK_HBM_GBS, 4)}
 
-    extras = rank == 0 and world == 1 and not a.no_extras and not a.no_graph
+    extras = rank == 0 and world == 1 and a.full and not a.no_extras and not a.no_graph
     if extras:
         # PCIe-inclusive rate (SURVEY.md section 8(d) "Metric"): H2D of the three condition batches + sampling + D2H of the result
         hc = [c.cpu().pin_memory() for c in (c1, c2, c3)]
@@ -736,7 +773,7 @@ def worker(a):
             del sb, cs, xb
         log('parity leg: config 2 and wide config 3 fixtures through the captured sampler ...')
         line['parity'] = parity_leg(cfg, dev)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         log('timing the CPU oracle (2 warm-up + 3 timed slices, all cores' + (', then B=8 and 1 thread' if a.cpu_baseline_full else '') + ') ...')
         line['cpu_baseline'] = cpu_baseline(cfg, full=a.cpu_baseline_full)
     if rank == 0:

@@ -100,6 +100,7 @@ def test_sweep_whose_first_count_does_not_fit_still_carries_the_extras():
     assert rc == 0 and d['skipped_gpu_counts'] == [8] and [c[0] for c in calls] == [4, 2]
     assert '--no-cpu-baseline' not in calls[0][1] and '--no-roofline' not in calls[0][1]
     assert '--no-cpu-baseline' in calls[1][1] and '--no-roofline' in calls[1][1]
+    assert all(c[1].count('--full') == 1 for c in calls)          # the extras of a sweep run only under --full
     assert d['cpu_baseline'] == {'value': 0.1} and d['roofline'] == {'frac': 0.1} and d['efficiency_vs_1gpu'] is None
 
 
@@ -111,6 +112,37 @@ def test_launcher_helpers():
     assert len(bench.csrc_digest()) == 16
     a = bench.parse(['--gpus', '4', '--total-slices', '512'])
     assert a.gpus == 4 and a.total_slices == 512 and a.batch == 32      # default batch = BASELINE config 3
+
+
+def test_plain_run_options():
+    """A plain run is lean: the legs beyond the headline need --full; --steps is the number of timed steps."""
+    sys.path.insert(0, REPO)
+    import bench
+    a = bench.parse(['--gpus', '1', '--steps', '3', '--warmup', '1'])
+    assert a.steps == 3 and a.warmup == 1 and not a.full and a.dump_outputs == ''
+    assert bench.parse(['--full', '--dump-outputs', 'd']).full
+    for bad in (['--steps', '0'], ['--warmup', '-1'], ['--sweep', '1,2', '--dump-outputs', 'd']):
+        with pytest.raises(SystemExit):
+            bench.parse(bad)
+
+
+def test_dump_outputs_float32_within_the_size_cap(tmp_path, monkeypatch):
+    sys.path.insert(0, REPO)
+    import numpy as np
+    import torch
+    import bench
+    x = torch.randn(7, 1, 8, 8, generator=torch.Generator().manual_seed(1))
+    bench.dump_outputs(str(tmp_path / 'all'), x, 0, 1)
+    got = np.load(tmp_path / 'all' / 'samples.npy')
+    assert got.dtype == np.float32 and np.array_equal(got, x.numpy())
+    # above the cap: a fixed seeded sample of whole slices, in their order; per rank, each rank's share of the cap
+    monkeypatch.setattr(bench, 'DUMP_BYTES', 2 * 3 * 64 * 4)
+    for d in ('s1', 's2'):
+        bench.dump_outputs(str(tmp_path / d), x, 1, 2)
+    s1, s2 = (np.load(tmp_path / d / 'samples.rank1.npy') for d in ('s1', 's2'))
+    assert s1.shape == (3, 1, 8, 8) and np.array_equal(s1, s2)
+    rows = [next(i for i in range(7) if np.array_equal(s, x[i].numpy())) for s in s1]
+    assert rows == sorted(set(rows))
 
 
 @pytest.mark.parametrize('which', ['g1', 'g2'])
@@ -145,3 +177,25 @@ def test_two_real_ranks_on_the_gpu_box():
         # the generators' parameters: 20,472,065 (G1) + 21,399,681 (G2) fp32 values in two flattened messages
         assert d['param_broadcast']['bytes'] == 4 * (20472065 + 21399681) and d['param_broadcast']['messages'] == 2
         assert len(d['per_rank']['slices_per_s']) == 2 and 0 < d['per_rank']['min'] <= d['per_rank']['max']
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """bench.py without --full: the headline fields only, no leg of --full; --dump-outputs writes the slices of the last timed
+    step, and a second run with the same arguments samples from the same inputs (same outputs up to the parity tolerance)."""
+    e = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT', 'MUDIFF_BENCH_DRYRUN')}
+    import numpy as np
+    outs = []
+    for run in ('a', 'b'):
+        d = tmp_path / run
+        p = subprocess.run([sys.executable, BENCH, '--gpus', '1', '--batch', '2', '--steps', '2', '--warmup', '1', '--dump-outputs', str(d)],
+                           env=e, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        line = _line(p)
+        assert {'metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'} <= set(line)
+        assert line['steps'] == 2 and line['warmup'] == 1 and line['value'] > 0 and line['ms_per_step'] > 0
+        assert not {'roofline', 'cpu_baseline', 'parity', 'pcie_inclusive', 'batch1', 'end_to_end'} & set(line)
+        x = np.load(d / 'samples.npy')
+        assert x.dtype == np.float32 and x.shape == (2, 1, 256, 256) and np.isfinite(x).all()
+        outs.append(x)
+    assert float(np.abs(outs[0] - outs[1]).max()) <= 1e-3

@@ -33,8 +33,13 @@ def test_schedules_bit_exact(tag, kw):
     for f in ('betas', 'alphas_cumprod', 'posterior_variance', 'posterior_mean_coef1', 'posterior_mean_coef2',
               'posterior_log_variance_clipped'):
         close(getattr(p, f), g[f'{tag}.{f}'], f)
-    for f in ('sigmas', 'a_s', 'a_s_cum', 'sigmas_cum', 'a_s_prev'):
+    for f in ('sigmas', 'a_s', 'a_s_cum', 'a_s_prev'):
         close(getattr(d, f), g[f'{tag}.{f}'], f)
+    # sigmas_cum = sqrt(1 - a_s_cum^2) multiplies a relative move of a_s_cum by a_s_cum^2 / sigmas_cum^2 (x46 at T4geo's
+    # second entry): the same rtol, carried through that condition number (exact where sigmas_cum is 0)
+    a, s = g[f'{tag}.a_s_cum'], g[f'{tag}.sigmas_cum']
+    amp = torch.where(s > 0, a * a / (s * s).clamp_min(1e-30), torch.zeros_like(s))
+    assert ((d.sigmas_cum - s).abs() <= 3e-7 * (1 + amp) * s).all(), ('sigmas_cum', d.sigmas_cum, s)
     close(O.get_time_schedule(cfg), g[f'{tag}.T'], 'T')
 
 
@@ -101,10 +106,15 @@ def test_small_models_every_step(tag):
     g = load_golden('small_models.npz')
     cfg = O.default_config(**SMALL_CFGS[tag])
     sd1, sd2 = O.make_state_dict(cfg, 'g1', 1234), O.make_state_dict(cfg, 'g2', 1234)
-    conds = small_conds(cfg)
     x_init, zs, noises = sampler_inputs(cfg, 2)
-    assert torch.equal(x_init, g[f'{tag}.x_init']) and torch.equal(conds[1], g[f'{tag}.c2'])
-    assert torch.equal(zs[1], g[f'{tag}.z1']) and torch.equal(noises[0], g[f'{tag}.noise0'])
+    assert torch.equal(x_init, g[f'{tag}.x_init'])
+    assert all(torch.equal(z, g[f'{tag}.z{k}']) for k, z in enumerate(zs))
+    assert all(torch.equal(n, g[f'{tag}.noise{k}']) for k, n in enumerate(noises))
+    # the condition images are tanh of seeded draws, and the host CPU's tanh may round them 1 ulp apart from the host that
+    # made the fixture: the oracle runs on the fixture's own images (the ones the reference consumed)
+    conds = [g[f'{tag}.c{i + 1}'] for i in range(3)]
+    for c, ref in zip(small_conds(cfg), conds):
+        assert int((c.view(torch.int32).long() - ref.view(torch.int32).long()).abs().max()) <= 1
     _, steps = O.sample_from_model(O.PosteriorCoefficients(cfg), sd1, sd2, cfg, *conds, x_init, zs, noises, return_steps=True)
     for k, st in enumerate(steps):
         for nm, v in zip(('x01', 'x02', 'xnew'), st):
