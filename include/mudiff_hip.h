@@ -192,6 +192,28 @@ int mud_conv2d_mfma_prec_supported(const mud_conv_args* a, int prec);
 /* Bytes of split-K workspace mud_conv2d_mfma would use for this call (0: the launch is not split). */
 int64_t mud_conv2d_mfma_splitk_bytes(const mud_conv_args* a);
 
+/* ---- e4m3 range census of a convolution input (the precision guard of MUD_PREC_FP8X: mudiff_hip.precision).
+ * MUD_PREC_FP8X converts every prologued activation a (and its fp16 remainder a - fp16(a)) to e4m3 at CONSTANT power-of-two
+ * pre-scales; the cross terms are only right while |a| stays inside about [5e-4, 112].  This call mirrors the staging of
+ * mud_conv2d_mfma (conv_mfma.hip, cm_stage4: fmaf(x, scale, shift), then the same fast SiLU, fp16 pieces saturating at +-65504)
+ * on every element of the view and ACCUMULATES into `out` (a device struct; zero it once, every launch adds to it):
+ *   n            elements seen
+ *   n_over       |a|*2^CM_X_SA > 448  or  |a - fp16(a)|*2^CM_X_SAL > 448       (an e4m3 image saturates)
+ *   n_under      0 < |a|*2^CM_X_SA < 2^-9                                      (below e4m3's smallest subnormal: flushes)
+ *   n_fp16_over  |a| > 65504                                                   (the fp16 hi piece saturates, both plans)
+ *   amax_bits    bit pattern of max |a| (fp32, zero-extended; merged with an integer max)
+ * Integer counts merged with one atomic per counter per workgroup: the result does not depend on the order of arrival.
+ * x: 16-byte aligned, C % 4 == 0, ldx % 4 == 0, ldx >= C, B*H*W*C/4 < 2^31.  pro_mode: MUD_PRO_NONE, MUD_PRO_AFFINE or
+ * MUD_PRO_AFFINE_SILU; with an affine mode pro_scale / pro_shift are [B, pro_ld] rows (16-byte aligned, pro_ld % 4 == 0, >= C). */
+typedef struct mud_census_args {
+  const float* x; int B, H, W, C, ldx;
+  const float* pro_scale; const float* pro_shift; int pro_ld; int pro_mode;
+} mud_census_args;
+typedef struct mud_census_out {
+  uint64_t n, n_over, n_under, n_fp16_over, amax_bits;
+} mud_census_out;
+int mud_e4m3_census(const mud_census_args* a, mud_census_out* out, void* stream);
+
 /* ---- FIR resampling (utils/op/upfirdn2d.cpp:20-31 + upfirdn2d_kernel.cu:109-209; python front
  *      ends backbones/up_or_down_sampling.py:149-262).
  * Plane form = the reference's pybind op: input [planes, H, W] (its [major, in_h, in_w, minor=1]),

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from mudiff_hip import ops
+from mudiff_hip import ops, precision
 from mudiff_hip.ops import (ACT_NONE, ACT_SILU, INV_SQRT2, PRO_AFFINE, PRO_AFFINE_SILU, View)
 
 from . import dense_layer, layers, up_or_down_sampling
@@ -49,6 +49,22 @@ def _apply_affine(x: View, sc, sh):
     return ops.fir_nhwc(x, [[1.0]], 1, 1, (0, 0), pro=(sc, sh, PRO_AFFINE))[0]
 
 
+class PlanScope:
+    """Per-generator arithmetic-plan state, held by the generator (mudiff_hip.precision): `overrides` = names of the layers
+    (state_dict prefixes) that run fp16 x 3 whatever MUD_PREC_PLAN picks.  The ConvParams of the generator's blocks are bound to
+    it by name every time their prepared-weight cache is (re)built, so an override outlives any rebuild of that cache."""
+
+    def __init__(self):
+        self.overrides = set()
+
+
+def bind_plan_scope(root: nn.Module, scope: PlanScope):
+    """Give every _Prepared module under `root` (itself included) the scope and its state_dict prefix."""
+    for name, m in root.named_modules():
+        if isinstance(m, _Prepared):
+            m.__dict__['_plan_bound'] = (scope, name + '.' if name else '')
+
+
 class _Prepared:
     """Caches device-side re-packed weights; rebuilt when a parameter is replaced or modified."""
 
@@ -61,26 +77,54 @@ class _Prepared:
         if cache is None or cache[0] != key:
             with torch.no_grad():
                 cache = (key, self._prepare())
+            self._name_convs(cache[1])
             self.__dict__['_prep_cache'] = cache
         return cache[1]
+
+    def _name_convs(self, prep):
+        """Bind the ConvParams of a freshly prepared cache to the generator's PlanScope, under their state_dict names."""
+        bound = self.__dict__.get('_plan_bound')
+        if bound is None:
+            return
+        scope, prefix = bound
+        names = {id(m): n for n, m in self.named_modules()}
+        todo = list(prep.values()) if isinstance(prep, dict) else [prep]
+        while todo:
+            v = todo.pop()
+            if isinstance(v, dict):
+                todo += list(v.values())
+            elif isinstance(v, (list, tuple)):
+                todo += list(v)
+            elif isinstance(v, ConvParam):
+                n = v.name if v.src is None else names.get(id(v.src))
+                if n is not None:
+                    v.name, v.scope = prefix + n, scope
 
 
 class ConvParam:
     """A conv weight prepared for one of the two kernels."""
 
-    def __init__(self, conv: nn.Conv2d = None, weight=None, bias=None):
-        """conv: an nn.Conv2d; or weight [O,I,k,k] (+ bias) of a stride-1 'same' convolution (several convs merged into one)."""
+    @staticmethod
+    def uses_mfma(cout, cin, ks, stride=(1, 1), padding=(1, 1)):
+        """Matrix-core kernel (True) or the exact direct kernels (False) for a conv of this shape."""
+        # C_out <= 4 3x3 convs (the image-space output / pyramid convs) have a dedicated exact kernel on the direct path
+        tail = ks == 3 and cout <= 4 and cin % 16 == 0 and tuple(stride) == (1, 1) and tuple(padding) == (1, 1)
+        return use_mfma(cin, cout) and ks in (1, 3) and not tail
+
+    def __init__(self, conv: nn.Conv2d = None, weight=None, bias=None, name=None):
+        """conv: an nn.Conv2d; or weight [O,I,k,k] (+ bias) of a stride-1 'same' convolution (several convs merged into one).
+        name: the layer name of a merged conv (an nn.Conv2d is named after its module when its owner binds it: PlanScope)."""
+        self.src = conv if isinstance(conv, nn.Module) else None
         if conv is None:
             from types import SimpleNamespace
             conv = SimpleNamespace(weight=weight, bias=bias, stride=(1, 1), padding=(weight.shape[2] // 2,) * 2)
         w = conv.weight.detach()
         self.cout, self.cin, self.ks = w.shape[0], w.shape[1], w.shape[2]
-        # C_out <= 4 3x3 convs (the image-space output / pyramid convs) have a dedicated exact kernel on the direct path
-        tail = self.ks == 3 and self.cout <= 4 and self.cin % 16 == 0 and tuple(conv.stride) == (1, 1) and tuple(conv.padding) == (1, 1)
-        self.mfma = use_mfma(self.cin, self.cout) and self.ks in (1, 3) and not tail
+        self.mfma = ConvParam.uses_mfma(self.cout, self.cin, self.ks, conv.stride, conv.padding)
         self.w = ops.pack_conv_weight(w) if self.mfma else ops.direct_weight(w)
         self.bias = conv.bias.detach().contiguous() if conv.bias is not None else None
         self._w32, self._w8, self.w_exp = w, None, 0       # the fp32 weight stays referenced: other arithmetic plans are packed on first use
+        self.name, self.scope = name, None                  # layer name and the generator's PlanScope, once bound
 
     def fp8x(self):
         """The operand packed for MUD_PREC_FP8X (fp16 hi planes + e4m3 images at this layer's own exponent), made on first use."""
@@ -90,13 +134,17 @@ class ConvParam:
         return self._w8
 
     def plan(self, x, pro=None, skip=None, sub2=False):
-        """The arithmetic plan this launch would run with (ops.choose_prec)."""
+        """The arithmetic plan this launch would run with (ops.choose_prec; fp16 x 3 for a layer its generator overrides)."""
         if not self.mfma or self.ks != 3:
+            return ops.PREC_16X3
+        if self.scope is not None and self.name in self.scope.overrides:
             return ops.PREC_16X3
         return ops.choose_prec(x, self.cout, pro[2] if pro is not None else ops.PRO_NONE, skip=skip is not None, sub2=sub2)
 
     def __call__(self, x, **kw):
         if self.plan(x, kw.get('pro'), kw.get('skip'), kw.get('sub2', False)) == ops.PREC_FP8X:
+            if precision.CENSUS:          # inside precision.census(): the e4m3 range census of this input first (eager only)
+                precision.record(self, x, kw.get('pro'))
             return ops.conv(x, self.fp8x(), self.ks, self.cout, mfma=True, bias=self.bias, prec=ops.PREC_FP8X, w_exp=self.w_exp, **kw)
         return ops.conv(x, self.w, self.ks, self.cout, mfma=self.mfma, bias=self.bias, **kw)
 

@@ -40,6 +40,7 @@ conv3x3 = layerspp.conv3x3
 conv1x1 = layerspp.conv1x1
 default_initializer = layers.default_init
 dense = dense_layer.dense
+GATES_NAME = 'feat_att'       # layer name of G2's merged sigmoid-gate conv (every feat_att1_* / feat_att2_* in one launch)
 
 
 class PixelNorm(nn.Module):
@@ -201,6 +202,9 @@ class _NCSNppBase(nn.Module, layerspp._Prepared):
             mapping_layers.append(dense(z_emb_dim, z_emb_dim))
             mapping_layers.append(self.act)
         self.z_transform = nn.Sequential(*mapping_layers)
+        # per-layer arithmetic-plan overrides by layer name (mudiff_hip.precision), shared by every block's prepared convs
+        self._plan_scope = layerspp.PlanScope()
+        layerspp.bind_plan_scope(self, self._plan_scope)
 
     # ------------------------------------------------------------------------------------------
     def begin_loop_cache(self):
@@ -242,7 +246,7 @@ class _NCSNppBase(nn.Module, layerspp._Prepared):
             # the att2 gates - so the concatenated condition features are staged once
             gates = [getattr(self, 'feat_att1_' + pair) for pair in self._pairs] + [getattr(self, 'feat_att2_' + pair) for pair in self._pairs]
             wg = torch.cat([g.weight for g in gates], 0).contiguous()              # [2*n_pairs*nf, n_cond*nf, 3, 3]
-            p['gates'] = layerspp.ConvParam(weight=wg, bias=torch.cat([g.bias for g in gates], 0).contiguous())
+            p['gates'] = layerspp.ConvParam(weight=wg, bias=torch.cat([g.bias for g in gates], 0).contiguous(), name=GATES_NAME)
             p['fw'] = [layerspp.ConvParam(getattr(self, f'feat_weight_c{j + 1}')) for j in range(len(self._pairs))]
             ada = [mods[e['idx']] for e in self._plan if e['kind'] == 'ada']
             p['ada_w'] = torch.cat([m.group_norm.style.weight for m in ada], 0).contiguous()

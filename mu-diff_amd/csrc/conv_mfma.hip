@@ -48,8 +48,7 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 //                  weight step  [f16 hi 2 KiB][e4m3 w*2^w_exp 1 KiB][e4m3 w_lo*2^(w_exp+11) 1 KiB]  (w_exp: per layer, chosen at pack time).
 typedef mud_h16x4 h16x4;
 typedef mud_h16x8 h16x8;
-#define CM_X_SA 2                // constant power-of-two pre-scales of the e4m3 activation images (undone by the MFMA's E8M0 scale operands):
-#define CM_X_SAL 13              // a*2^2 covers |a| in [5e-4, 112]; a_lo <= 2^-11 |a| -> a_lo*2^13 <= 448 as well.  Out-of-range values only lose their cross term
+// CM_X_SA / CM_X_SAL: the constant pre-scales of the e4m3 activation images (mud_common.h, shared with the range census: census.hip)
 __device__ __forceinline__ int cm_e4m3x4(f32x4 v, float scale) {    // 4 floats * scale -> 4 packed OCP e4m3 bytes (hardware converter)
   // v_cvt_pk_fp8_f32 does NOT saturate: |x| >= 480 comes out as NaN (scripts/mfma_f8_layout.hip), so out-of-range values are clamped to +-448 first
   v = v * scale;
@@ -148,11 +147,6 @@ __device__ __forceinline__ void cm_gn_to_lds(const mud_conv_args& a, int b, int 
     sc_lds[c] = sc;
     sh_lds[c] = be - meanf * sc;
   }
-}
-
-__device__ __forceinline__ float cm_fast_silu(float v) {
-  // v * sigmoid(v) with the hardware exp2 / rcp (each ~1 ulp): the result is rounded to fp16 hi+lo (2^-22) anyway
-  return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.44269504088896340736f));
 }
 
 // One float4 of raw activations -> its LDS pieces (prologue, hi / lo split, e4m3 images).  SCALAR f32 arithmetic on purpose: beside

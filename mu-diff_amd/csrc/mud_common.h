@@ -90,6 +90,15 @@ __device__ __forceinline__ float mud_fast_silu(float v) {
   return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.44269504088896340736f));
 }
 
+// ---- shared by the 3x3 convolution's staging (conv_mfma.hip: cm_stage4) and the e4m3 range census (census.hip), so that the
+// census measures exactly what the MUD_PREC_FP8X plan converts
+#define CM_X_SA 2                // constant power-of-two pre-scales of the e4m3 activation images (undone by the MFMA's E8M0 scale operands):
+#define CM_X_SAL 13              // a*2^2 covers |a| in [5e-4, 112]; a_lo <= 2^-11 |a| -> a_lo*2^13 <= 448 as well.  Out-of-range values only lose their cross term
+__device__ __forceinline__ float cm_fast_silu(float v) {
+  // v * sigmoid(v) with the hardware exp2 / rcp (each ~1 ulp): the result is rounded to fp16 hi+lo (2^-22) anyway
+  return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.44269504088896340736f));
+}
+
 __device__ __forceinline__ float mud_prologue(float v, float sc, float sh, int mode) {
   if (mode == MUD_PRO_NONE) return v;
   if (mode == MUD_PRO_LRELU) return v > 0.f ? v : 0.2f * v;

@@ -65,6 +65,19 @@ class MlpArgs(C.Structure):
     ]
 
 
+class CensusArgs(C.Structure):
+    """struct mud_census_args (include/mudiff_hip.h)."""
+    _fields_ = [
+        ('x', C.c_void_p), ('B', C.c_int), ('H', C.c_int), ('W', C.c_int), ('C', C.c_int), ('ldx', C.c_int),
+        ('pro_scale', C.c_void_p), ('pro_shift', C.c_void_p), ('pro_ld', C.c_int), ('pro_mode', C.c_int),
+    ]
+
+
+class CensusOut(C.Structure):
+    """struct mud_census_out (include/mudiff_hip.h): accumulated on the device, read back as 5 x int64."""
+    _fields_ = [('n', C.c_uint64), ('n_over', C.c_uint64), ('n_under', C.c_uint64), ('n_fp16_over', C.c_uint64), ('amax_bits', C.c_uint64)]
+
+
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
 _SIGNATURES = {
     'mud_version': (C.c_int, []),
@@ -100,6 +113,7 @@ _SIGNATURES = {
     'mud_fourier_embedding': (_I, [_P, _P, _P, _I, _I, _P]),
     'mud_resize_bilinear': (_I, [_P, _L, _I, _I, _I, _I, _P, _P]),
     'mud_affine_clamp': (_I, [_P, _L, _F, _F, _F, _F, _P, _P]),
+    'mud_e4m3_census': (_I, [C.POINTER(CensusArgs), _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -129,6 +129,39 @@ def export_and_score(pred_slices, gt_slices, save_dir=None):
 
 
 # ---------------------------------------------------------------------------------------------------
+def pad_batch(t, n, batch_size):
+    """Last partial batch: repeat the last slice up to the fixed graph shape (trimmed after sampling)."""
+    return t if t.shape[0] == batch_size else torch.cat([t, t[-1:].expand(batch_size - n, *t.shape[1:])], 0)
+
+
+def calibrate_first_batch(args, gen1, gen2, source, batch_size, device, rank=0, world=1, group=None):
+    """precision.calibrate_plan on this rank's FIRST batch, padded as sample_slices pads it (plan eligibility depends on the
+    batch and image size the captured sampler runs at); installs the overrides on gen1 / gen2.  A rank without slices of its
+    own calibrates on the first batch of the set.  -> Calibration, or None for an empty source."""
+    from . import precision
+    from . import sampling as S
+    from .distributed import shard_range
+    lo, hi = shard_range(len(source), rank, world)
+    if hi == lo:
+        lo, hi = 0, len(source)
+    if hi == lo:
+        return None
+    c1, c2, c3, _ = source.batch(lo, min(lo + batch_size, hi))
+    n = c1.shape[0]
+    c1, c2, c3 = (pad_batch(c, n, batch_size).to(device) for c in (c1, c2, c3))
+    return precision.calibrate_plan(S.Posterior_Coefficients(args, device), gen1, c1, gen2, c2, c3, args.num_timesteps, args,
+                                    threshold=args.calibrate_threshold, group=group)
+
+
+def write_calibration(cal, output_path):
+    import json
+    os.makedirs(output_path, exist_ok=True)
+    path = os.path.join(output_path, 'prec_calibration.json')
+    with open(path, 'w') as f:
+        json.dump(cal.to_dict(), f, indent=1)
+    return path
+
+
 def sample_slices(args, gen1, gen2, source, batch_size, device, rank=0, world=1, seed=42, progress=None, draws=None):
     """Sample this rank's contiguous shard of `source` in batches of `batch_size` through one captured reverse step.
     -> (lo, predictions [n,H,W] float32 numpy, targets [n,H,W]).
@@ -144,9 +177,7 @@ def sample_slices(args, gen1, gen2, source, batch_size, device, rank=0, world=1,
     preds, gts = [], []
     sampler = None
     gen = torch.Generator(device=device).manual_seed(seed + rank)
-
-    def pad(t, n):      # last partial batch: repeat the last slice up to the fixed graph shape, trimmed afterwards
-        return t if t.shape[0] == batch_size else torch.cat([t, t[-1:].expand(batch_size - n, *t.shape[1:])], 0)
+    pad = lambda t, n: pad_batch(t, n, batch_size)      # noqa: E731
 
     for b0 in range(lo, hi, batch_size):
         c1, c2, c3, y = source.batch(b0, min(b0 + batch_size, hi))
@@ -205,7 +236,16 @@ def build_parser():
     p.add_argument('--batch_size', type=int, default=16, help='slices per GPU per captured reverse step')
     p.add_argument('--target_modality', default='T1CE')
     p.add_argument('--no_png', action='store_true')
+    add_calibration_flags(p)
     return p
+
+
+def add_calibration_flags(p):
+    p.add_argument('--calibrate', action='store_true',
+                   help='before capturing the sampler, check the default fp8 cross-term plan on the first batch and switch the layers '
+                        'it cannot carry back to fp16x3 (mudiff_hip.precision; result in <output>/prec_calibration.json)')
+    from .precision import DEFAULT_THRESHOLD
+    p.add_argument('--calibrate_threshold', type=float, default=DEFAULT_THRESHOLD, help='max-abs deviation from the fp16x3 plan --calibrate accepts')
 
 
 def main(argv=None):
@@ -228,6 +268,12 @@ def main(argv=None):
     broadcast_parameters(g2)
     g1.eval(); g2.eval()
     source = SliceSource('test', args.input_path, args.target_modality)
+    if args.calibrate:
+        cal = calibrate_first_batch(args, g1, g2, source, args.batch_size, device, rank, world, group=dist.group.WORLD if world > 1 else None)
+        if cal is not None:
+            logging.info('rank %d: %s', rank, cal.summary())
+            if rank == 0:
+                write_calibration(cal, args.output_path)
     lo, preds, gts = sample_slices(args, g1, g2, source, args.batch_size, device, rank, world,
                                    progress=lambda d, n: logging.info('rank %d: %d/%d slices', rank, d, n) if d % (args.batch_size * 8) == 0 else None)
     if world > 1:                                                # gather the shards on rank 0 (256 KB per slice)

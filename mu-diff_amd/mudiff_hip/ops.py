@@ -462,6 +462,29 @@ def fp8x_pays(B, H, W, cin, cout):
     return True
 
 
+PREC_PLANS = ('off', 'auto', 'all')
+
+
+class prec_plan:
+    """Context: PREC_PLAN = `name` ('off' | 'auto' | 'all') for the launches planned inside (eager calls; a graph captured inside
+    keeps the plans it was captured with), restored on exit."""
+
+    def __init__(self, name):
+        if name not in PREC_PLANS:
+            raise ValueError(f'prec_plan: unknown plan {name!r} (one of {PREC_PLANS})')
+        self.name, self._saved = name, None
+
+    def __enter__(self):
+        global PREC_PLAN
+        self._saved, PREC_PLAN = PREC_PLAN, self.name
+        return self
+
+    def __exit__(self, *exc):
+        global PREC_PLAN
+        PREC_PLAN = self._saved
+        return False
+
+
 def conv_prec_supported(x: View, cout, pro_mode, prec, skip=False, sub2=False):
     a = ConvArgs()
     a.x, a.B, a.H, a.W, a.Cin, a.ldx, a.ks, a.stride, a.pad = x.ptr, x.B, x.H, x.W, x.C, x.ld, 3, 1, 1
@@ -557,6 +580,36 @@ def conv(x: View, w, ks, Cout, *, mfma, stride=1, pad=None, pro=None, bias=None,
     flops = 2.0 * x.B * Ho * Wo * Cout * x.C * ks * ks + skip_flops     # algorithmic (sub2 issues 4x this)
     nbytes = 4.0 * (x.npix * x.C + out.npix * Cout * ((2 if res is not None else 1) + (1 if skip is not None else 0))) + (w.numel() * w.element_size() if w_bstride == 0 else x.B * w_bstride)
     _launch(name, x.device, fn, C.byref(a), STREAM, flops=flops, nbytes=nbytes)
+    return out
+
+
+CENSUS_FIELDS = ('n', 'n_over', 'n_under', 'n_fp16_over', 'amax_bits')     # struct mud_census_out, in order
+
+
+def new_census_slot(device):
+    """Zeroed device accumulator of e4m3_census: int64 [5] laid out as struct mud_census_out (CENSUS_FIELDS)."""
+    return torch.zeros(len(CENSUS_FIELDS), device=device, dtype=torch.int64)
+
+
+def e4m3_census(x: View, pro, out):
+    """Accumulate the e4m3 range census of a MUD_PREC_FP8X convolution input into `out` (new_census_slot): `x` after the
+    prologue `pro` = None | (scale, shift, mode) | (LazyGN, None, mode) - the same prologue the conv is given.  A LazyGN is
+    finalised here through LazyGN.tensors() (the arithmetic the conv's folded prologue repeats); the conv itself still takes
+    the lazy form, so its launch and outputs do not change."""
+    from . import CensusArgs
+    require_gpu(x.base, out)
+    assert out.dtype == torch.int64 and out.numel() == len(CENSUS_FIELDS) and out.is_contiguous()
+    a = CensusArgs()
+    a.x, a.B, a.H, a.W, a.C, a.ldx = x.ptr, x.B, x.H, x.W, x.C, x.ld
+    if pro is None:
+        a.pro_mode = PRO_NONE
+    else:
+        sc, sh, mode = resolve_pro(pro)
+        a.pro_mode = mode
+        if mode != PRO_NONE:
+            assert sc.shape == (x.B, x.C) and sc.stride(1) == 1 and sh.stride() == sc.stride(), (tuple(sc.shape), sc.stride(), sh.stride())
+            a.pro_scale, a.pro_shift, a.pro_ld = ptr(sc), ptr(sh), sc.stride(0)
+    _launch('e4m3_census', x.device, load().mud_e4m3_census, C.byref(a), ptr(out), STREAM, nbytes=4.0 * x.npix * x.C)
     return out
 
 

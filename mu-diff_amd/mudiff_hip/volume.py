@@ -180,6 +180,33 @@ def load_checkpoint(template, net, name, device):
 # ---------------------------------------------------------------------------------------------------
 # batched sampling of a stack of slices
 # ---------------------------------------------------------------------------------------------------
+def upload_conds(cond_stacks, size, device):
+    """Three [n,X,Y] condition stacks -> [n,1,size,size] device tensors: one upload + one resize launch per contrast (reference:
+    per slice, on the CPU)."""
+    from . import ops
+    conds = []
+    for st in cond_stacks:
+        t = torch.from_numpy(np.ascontiguousarray(st, dtype=np.float32)).to(device)[:, None]
+        if tuple(t.shape[-2:]) != (size, size):
+            t = ops.resize_bilinear(t, (size, size))
+        conds.append(t.contiguous())
+    return conds
+
+
+def calibrate_volume(args, gen1, gen2, cond_stacks, device, batch_size=32):
+    """precision.calibrate_plan on the first batch predict_slices will sample (min(batch_size, n) slices: never padded), at the
+    model's image size; installs the overrides on gen1 / gen2.  -> Calibration, or None for an empty volume."""
+    from . import precision
+    from . import sampling as S
+    n = int(cond_stacks[0].shape[0])
+    if n == 0:
+        return None
+    bs = min(int(batch_size), n)
+    c1, c2, c3 = upload_conds([st[:bs] for st in cond_stacks], int(args.image_size), device)
+    return precision.calibrate_plan(S.Posterior_Coefficients(args, device), gen1, c1, gen2, c2, c3, int(args.num_timesteps), args,
+                                    threshold=args.calibrate_threshold)
+
+
 def predict_slices(args, gen1, gen2, cond_stacks, device, batch_size=32, x_inits=None, zs=None, noises=None, seed=None,
                    use_graph=True, progress=None, sampler=None):
     """cond_stacks: three float arrays [n,X,Y] in [-1,1] (the condition contrasts, already normalised and sliced).
@@ -196,12 +223,7 @@ def predict_slices(args, gen1, gen2, cond_stacks, device, batch_size=32, x_inits
     size = int(args.image_size)
     if n == 0:
         return np.zeros((0, size, size), np.float32)
-    conds = []
-    for st in cond_stacks:      # one upload + one resize launch per contrast (reference: per slice, on the CPU)
-        t = torch.from_numpy(np.ascontiguousarray(st, dtype=np.float32)).to(device)[:, None]
-        if tuple(t.shape[-2:]) != (size, size):
-            t = ops.resize_bilinear(t, (size, size))
-        conds.append(t.contiguous())
+    conds = upload_conds(cond_stacks, size, device)
     coef = S.Posterior_Coefficients(args, device)
     gen = None
     if seed is not None:
@@ -279,6 +301,12 @@ def predict_volume(args):
         # written into an [X,Y] plane); --resize_back is this build's opt-in extension
         raise ValueError(f'in-plane size {tuple(shp[:2])} differs from --image_size {args.image_size}: the prediction cannot be '
                          'written back into the volume (pass --resize_back to resample it bilinearly)')
+    if getattr(args, 'calibrate', False):
+        cal = calibrate_volume(args, gen1, gen2, stacks, device, batch_size=args.batch_size)
+        if cal is not None:
+            from .driver import write_calibration
+            print(f'[calibrate] {cal.summary()}')
+            print(f'[calibrate] wrote {write_calibration(cal, args.output_dir)}')
     pred = predict_slices(args, gen1, gen2, stacks, device, batch_size=args.batch_size, seed=args.seed,
                           progress=lambda d, n: print(f'[infer] processed {d}/{n} slices'))
     if tuple(shp[:2]) != tuple(pred.shape[1:]):
@@ -294,7 +322,8 @@ def predict_volume(args):
 
 def build_argparser(argv=None):
     """Flags and defaults of the reference parser (:302-357; like it, returns the PARSED namespace), plus --centered (which
-    the generators read and the reference parser forgot), --batch_size and --resize_back."""
+    the generators read and the reference parser forgot), --batch_size, --resize_back and --calibrate / --calibrate_threshold
+    (mudiff_hip.precision; the record goes to <output_dir>/prec_calibration.json)."""
     p = argparse.ArgumentParser('MU-Diff volume prediction (MI355X)')
     for m in ('t1ce', 't1', 't2', 'flair'):
         p.add_argument(f'--input_{m}', type=str, help=f'Path to {m.upper()} NIfTI')
@@ -336,6 +365,8 @@ def build_argparser(argv=None):
     p.add_argument('--gpu_chose', type=int, default=0)
     p.add_argument('--batch_size', type=int, default=32, help='slices per captured reverse step (MI355X build)')
     p.add_argument('--resize_back', action='store_true', help='resample the prediction to the in-plane size of the inputs')
+    from .driver import add_calibration_flags
+    add_calibration_flags(p)
     return p.parse_args(argv)
 
 
