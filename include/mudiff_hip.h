@@ -259,6 +259,27 @@ int mud_fourier_embedding(const float* t, const float* W, float* out, int B, int
 int mud_resize_bilinear(const float* in, int64_t planes, int H, int W, int Ho, int Wo, float* out, void* stream);
 int mud_affine_clamp(const float* x, int64_t n, float scale, float shift, float lo, float hi, float* out, void* stream);
 
+/* ---- on-device evaluation metrics (mudiff_hip.metrics; the driver's --device_metrics).  They replace the host end of an
+ *      evaluation: the global intensity range and 8-bit quantisation of engine/test.py:371-387 and the PSNR / SSIM / MAE of
+ *      tools/metric_calc.py:28-53 (skimage defaults: 7x7 uniform window, sample covariance, K1 = 0.01, K2 = 0.03, data_range 1).
+ *
+ * out[0] = min, out[1] = max over a[0..na) and b[0..nb) (fp32), in one launch sequence; NaN in both if any input is NaN (np.min);
+ * +inf / -inf for empty inputs.  ws: mud_value_range_ws_bytes() bytes, 4-byte aligned. */
+int64_t mud_value_range_ws_bytes(void);
+int mud_value_range(const float* a, int64_t na, const float* b, int64_t nb, float* out, void* ws, void* stream);
+/* out[i] = (uint8) clip((x[i] - lo) / range * 255.0f, 0, 255), every step IEEE fp32 rounded once, truncation toward zero: bit-identical
+ * to numpy's clip((s - gmin) / (gmax - gmin) * 255.0, 0, 255).astype(uint8) on fp32 s (engine/test.py:386-387) when the caller
+ * passes lo = (float)gmin and range = (float)(gmax - gmin) with the difference taken in double.  range must be finite and > 0. */
+int mud_quantize_u8(const float* x, int64_t n, float lo, float range, uint8_t* out, void* stream);
+/* Per-slice sums of uint8 images pred, gt [n, H, W] (H, W >= 7):  sse[i] = sum (g-p)^2,  sae[i] = sum |g-p| (exact, int64), and
+ * ssim_sum[i] = the fp64 sum of the per-pixel SSIM of (g/255, p/255) over the (H-6) x (W-6) interior (tools/metric_calc.py:44-48;
+ * PSNR = 10 log10(255^2 H W / sse), SSIM = ssim_sum / ((H-6)(W-6)), MAE = sae / (255 H W)).  Window sums are exact integers;
+ * the per-slice sum has a fixed order, so results are bit-identical run to run and independent of n.
+ * ws: mud_slice_metrics_ws_bytes(n, H, W) bytes (-1 for bad sizes), 8-byte aligned. */
+int64_t mud_slice_metrics_ws_bytes(int n, int H, int W);
+int mud_slice_metrics_u8(const uint8_t* pred, const uint8_t* gt, int n, int H, int W, int64_t* sse, int64_t* sae, double* ssim_sum,
+                         void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

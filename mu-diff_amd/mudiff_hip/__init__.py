@@ -114,6 +114,11 @@ _SIGNATURES = {
     'mud_resize_bilinear': (_I, [_P, _L, _I, _I, _I, _I, _P, _P]),
     'mud_affine_clamp': (_I, [_P, _L, _F, _F, _F, _F, _P, _P]),
     'mud_e4m3_census': (_I, [C.POINTER(CensusArgs), _P, _P]),
+    'mud_value_range_ws_bytes': (_L, []),
+    'mud_value_range': (_I, [_P, _L, _P, _L, _P, _P, _P]),
+    'mud_quantize_u8': (_I, [_P, _L, _F, _F, _P, _P]),
+    'mud_slice_metrics_ws_bytes': (_L, [_I, _I, _I]),
+    'mud_slice_metrics_u8': (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _L, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

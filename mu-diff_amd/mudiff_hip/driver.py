@@ -9,6 +9,9 @@ per GPU and shards the slice list over ranks (the reference runs batch_size = 1 
            --image_size 256 --num_channels 1 --num_channels_dae 64 --ch_mult 1 2 4 --batch_size 16
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m mudiff_hip.driver ...   # 8 GPUs
 
+--device_metrics moves the end of the run to the GPUs (mudiff_hip.metrics): every rank keeps its slices in HBM, quantises,
+exports and scores its own shard, and rank 0 gathers per-slice sums only; PNGs and metrics are those of the default host path.
+
 LPIPS (needs downloaded AlexNet weights) is out of scope.  skimage is not installed here, so PSNR / SSIM are
 restated from the published definitions with skimage's defaults ("parity unpinned")."""
 from __future__ import annotations
@@ -162,9 +165,10 @@ def write_calibration(cal, output_path):
     return path
 
 
-def sample_slices(args, gen1, gen2, source, batch_size, device, rank=0, world=1, seed=42, progress=None, draws=None):
+def sample_slices(args, gen1, gen2, source, batch_size, device, rank=0, world=1, seed=42, progress=None, draws=None, keep_on_device=False):
     """Sample this rank's contiguous shard of `source` in batches of `batch_size` through one captured reverse step.
-    -> (lo, predictions [n,H,W] float32 numpy, targets [n,H,W]).
+    -> (lo, predictions [n,H,W] float32 numpy, targets [n,H,W]); with `keep_on_device` both are fp32 tensors on `device` instead
+    (--device_metrics: 512 KB of HBM per slice, nothing copied to the host).
     Draws: x_init, z and the posterior noise come from ONE device generator seeded with `seed + rank` (so a run is
     reproducible from `seed`, and ranks do not repeat each other's streams).  `draws(lo, n) -> (x_init [n,1,H,W],
     zs [T][n,nz], noises [T][n,1,H,W])` (host tensors, indexed by GLOBAL slice number) injects them instead - parity runs
@@ -192,10 +196,17 @@ def sample_slices(args, gen1, gen2, source, batch_size, device, rank=0, world=1,
         else:
             x_init = torch.randn(batch_size, 1, c1.shape[2], c1.shape[3], device=device, generator=gen)
             out = sampler.sample(c1.to(device), c2.to(device), c3.to(device), x_init, args.num_timesteps, generator=gen)
-        preds.append(out[:n, 0].cpu().numpy())
-        gts.append(y[:, 0].numpy())
+        if keep_on_device:
+            preds.append(out[:n, 0].clone())                 # the graph's output buffer is overwritten by the next replay
+            gts.append(y[:, 0].to(device))
+        else:
+            preds.append(out[:n, 0].cpu().numpy())
+            gts.append(y[:, 0].numpy())
         if progress:
             progress(min(b0 + batch_size, hi) - lo, hi - lo)
+    if keep_on_device:
+        tcat = (lambda xs: torch.cat(xs, 0) if xs else torch.zeros((0, 1, 1), dtype=torch.float32, device=device))
+        return lo, tcat(preds), tcat(gts)
     cat = (lambda xs: np.concatenate(xs, 0) if xs else np.zeros((0, 1, 1), np.float32))
     return lo, cat(preds), cat(gts)
 
@@ -236,6 +247,9 @@ def build_parser():
     p.add_argument('--batch_size', type=int, default=16, help='slices per GPU per captured reverse step')
     p.add_argument('--target_modality', default='T1CE')
     p.add_argument('--no_png', action='store_true')
+    p.add_argument('--device_metrics', action='store_true',
+                   help='quantise, export and score on the GPUs (mudiff_hip.metrics): every rank keeps its slices in HBM and scores its '
+                        'own shard; rank 0 gathers only per-slice sums.  Same PNGs and metrics as the default host path')
     add_calibration_flags(p)
     return p
 
@@ -275,15 +289,21 @@ def main(argv=None):
             if rank == 0:
                 write_calibration(cal, args.output_path)
     lo, preds, gts = sample_slices(args, g1, g2, source, args.batch_size, device, rank, world,
-                                   progress=lambda d, n: logging.info('rank %d: %d/%d slices', rank, d, n) if d % (args.batch_size * 8) == 0 else None)
-    if world > 1:                                                # gather the shards on rank 0 (256 KB per slice)
-        parts = [None] * world
-        dist.gather_object((lo, preds, gts), parts if rank == 0 else None, dst=0)
-        if rank == 0:
-            parts.sort(key=lambda t: t[0])
-            preds, gts = np.concatenate([p[1] for p in parts], 0), np.concatenate([p[2] for p in parts], 0)
+                                   progress=lambda d, n: logging.info('rank %d: %d/%d slices', rank, d, n) if d % (args.batch_size * 8) == 0 else None,
+                                   keep_on_device=args.device_metrics)
+    png_dir = None if args.no_png else os.path.join(args.output_path, 'generated_samples')
+    if args.device_metrics:                                      # every rank scores its shard; rank 0 gathers per-slice sums only
+        from . import metrics
+        res = metrics.score_distributed(lo, preds, gts, png_dir)
+    else:
+        if world > 1:                                            # gather the shards on rank 0 (256 KB per slice)
+            parts = [None] * world
+            dist.gather_object((lo, preds, gts), parts if rank == 0 else None, dst=0)
+            if rank == 0:
+                parts.sort(key=lambda t: t[0])
+                preds, gts = np.concatenate([p[1] for p in parts], 0), np.concatenate([p[2] for p in parts], 0)
+        res = export_and_score(list(preds), list(gts), png_dir) if rank == 0 else None
     if rank == 0:
-        res = export_and_score(list(preds), list(gts), None if args.no_png else os.path.join(args.output_path, 'generated_samples'))
         logging.info('Average PSNR: %.4f dB  SSIM: %.4f  MAE: %.6f over %d slices (global range [%.4f, %.4f])', res['psnr'], res['ssim'],
                      res['mae'], res['count'], res['global_min'], res['global_max'])
     if world > 1:

@@ -6,6 +6,7 @@ import ctypes as C
 import math
 import os
 
+import numpy as np
 import torch
 
 from . import (ACT_LRELU, ACT_NONE, ACT_SIGMOID, ACT_SILU, ACT_TANH, PREC_16X3, PREC_FP8X, PRO_AFFINE, PRO_AFFINE_SILU, PRO_LRELU, PRO_NONE,  # noqa: F401
@@ -710,6 +711,58 @@ def affine_clamp(x, scale, shift, lo, hi):
     out = torch.empty_like(xin)
     _launch('affine_clamp', x.device, load().mud_affine_clamp, ptr(xin), xin.numel(), float(scale), float(shift), float(lo), float(hi), ptr(out), STREAM)
     return out
+
+
+def value_range(a, b=None):
+    """min and max over every element of the fp32 tensors `a` and `b` (driver: all predictions and all targets of a rank) ->
+    fp32 device tensor [min, max]; NaN in both if any input is NaN, +inf / -inf if both are empty.  No synchronisation."""
+    require_gpu(a, b)
+    ain = _f32(a.contiguous())
+    bin_ = None if b is None else _f32(b.contiguous())
+    out = torch.empty(2, device=a.device, dtype=torch.float32)
+    ws = torch.empty(load().mud_value_range_ws_bytes(), device=a.device, dtype=torch.uint8)
+    _launch('value_range', a.device, load().mud_value_range, ptr(ain), ain.numel(), ptr(bin_), 0 if bin_ is None else bin_.numel(),
+            ptr(out), ptr(ws), STREAM)
+    return out
+
+
+def quantize_u8(x, gmin, gmax):
+    """uint8 image of fp32 `x` with the global range [gmin, gmax] (python floats): bit-identical to
+    driver.to_uint8 = clip((x - gmin) / (gmax - gmin) * 255.0, 0, 255).astype(uint8) (reference engine/test.py:386-387).
+    As there, gmax <= gmin is NOT remapped here: the caller applies the (0, 1) fallback."""
+    require_gpu(x)
+    gmin, gmax = float(gmin), float(gmax)
+    if not gmax > gmin:
+        raise ValueError(f'quantize_u8: empty range [{gmin}, {gmax}] (use the (0, 1) fallback of the driver)')
+    xin = _f32(x.contiguous())
+    out = torch.empty(xin.shape, device=x.device, dtype=torch.uint8)
+    # numpy 2 evaluates the expression in fp32 with weak python scalars: fp32(gmin), and fp32 of the difference taken in double
+    _launch('quantize_u8', x.device, load().mud_quantize_u8, ptr(xin), xin.numel(), float(np.float32(gmin)), float(np.float32(gmax - gmin)),
+            ptr(out), STREAM)
+    return out
+
+
+def slice_metrics_u8(pred, gt):
+    """Per-slice sums of uint8 images [n, H, W] (H, W >= 7) -> (sse int64 [n], sae int64 [n], ssim_sum fp64 [n]) device tensors:
+    sum (g-p)^2, sum |g-p| and the sum of the per-pixel SSIM (7x7 window, skimage defaults) over the (H-6)(W-6) interior."""
+    require_gpu(pred, gt)
+    if pred.dtype != torch.uint8 or gt.dtype != torch.uint8 or pred.dim() != 3 or pred.shape != gt.shape:
+        raise MudiffHipError(f'slice_metrics_u8: need two uint8 [n, H, W] tensors of one shape (got {pred.dtype} {tuple(pred.shape)}, '
+                             f'{gt.dtype} {tuple(gt.shape)})')
+    n, H, W = pred.shape
+    if H < 7 or W < 7:
+        raise MudiffHipError(f'slice_metrics_u8: slices must be at least 7x7 (the SSIM window), got {H}x{W}')
+    pin, gin = pred.contiguous(), gt.contiguous()
+    sse = torch.empty(n, device=pred.device, dtype=torch.int64)
+    sae = torch.empty(n, device=pred.device, dtype=torch.int64)
+    ssim_sum = torch.empty(n, device=pred.device, dtype=torch.float64)
+    if n == 0:
+        return sse, sae, ssim_sum
+    nbytes = load().mud_slice_metrics_ws_bytes(n, H, W)
+    ws = torch.empty(nbytes, device=pred.device, dtype=torch.uint8)
+    _launch('slice_metrics_u8', pred.device, load().mud_slice_metrics_u8, ptr(pin), ptr(gin), n, H, W, ptr(sse), ptr(sae), ptr(ssim_sum),
+            ptr(ws), nbytes, STREAM)
+    return sse, sae, ssim_sum
 
 
 def to_range_0_1(x):
