@@ -280,6 +280,19 @@ int64_t mud_slice_metrics_ws_bytes(int n, int H, int W);
 int mud_slice_metrics_u8(const uint8_t* pred, const uint8_t* gt, int n, int H, int W, int64_t* sse, int64_t* sae, double* ssim_sum,
                          void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- LPIPS, AlexNet backbone (lpips v0.1, net='alex', eval; tools/metric_calc.py:50-51) of uint8 grayscale pairs (mudiff_hip.lpips_net).
+ * Weights are packed once into the kernels' layout: mud_lpips_packed_bytes() bytes, 16-byte aligned, written by mud_lpips_pack from
+ * device fp32 tensors in torch layout: table[768] = the scaled input of level v in channel c at [c*256 + v] (fp32, built on the host),
+ * conv_w[l] [Cout][Cin][k][k] and conv_b[l] [Cout] of torchvision AlexNet features.{0,3,6,8,10}, lin_w[l] [C] of lin{l}.model.1.
+ * mud_lpips_u8: out[i*5 + l] = d_l of pair (pred[i], gt[i]) [n, H, W], H, W >= 31, in fp64; LPIPS = sum over l.  Convolutions in exact
+ * fp32 (fp32-input MFMA), the head in fp64; fixed-order sums, so results are bit-identical run to run and independent of n.
+ * ws: mud_lpips_ws_bytes(n, H, W) bytes (-1 for bad sizes), 16-byte aligned; out 8-byte aligned. */
+int64_t mud_lpips_packed_bytes(void);
+int mud_lpips_pack(const float* table, void* const* conv_w, void* const* conv_b, void* const* lin_w, void* packed, void* stream);
+int64_t mud_lpips_ws_bytes(int n, int H, int W);
+int mud_lpips_u8(const uint8_t* pred, const uint8_t* gt, int n, int H, int W, const void* packed, double* out, void* ws,
+                 int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

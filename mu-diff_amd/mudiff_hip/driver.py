@@ -11,8 +11,8 @@ per GPU and shards the slice list over ranks (the reference runs batch_size = 1 
 
 --device_metrics moves the end of the run to the GPUs (mudiff_hip.metrics): every rank keeps its slices in HBM, quantises,
 exports and scores its own shard, and rank 0 gathers per-slice sums only; PNGs and metrics are those of the default host path.
-
-LPIPS (needs downloaded AlexNet weights) is out of scope.  skimage is not installed here, so PSNR / SSIM are
+With --lpips_weights [--lpips_lin] (device metrics only) every rank loads the LPIPS-alex weights itself and scores its shard's
+LPIPS too (mudiff_hip.lpips_net); the host path has no LPIPS.  skimage is not installed here, so PSNR / SSIM are
 restated from the published definitions with skimage's defaults ("parity unpinned")."""
 from __future__ import annotations
 
@@ -250,8 +250,21 @@ def build_parser():
     p.add_argument('--device_metrics', action='store_true',
                    help='quantise, export and score on the GPUs (mudiff_hip.metrics): every rank keeps its slices in HBM and scores its '
                         'own shard; rank 0 gathers only per-slice sums.  Same PNGs and metrics as the default host path')
+    from .metrics import add_lpips_flags
+    add_lpips_flags(p)
     add_calibration_flags(p)
     return p
+
+
+def parse_args(argv=None):
+    """build_parser().parse_args plus the flag rules: the LPIPS flags need --device_metrics."""
+    from .metrics import check_lpips_flags
+    p = build_parser()
+    args = p.parse_args(argv)
+    check_lpips_flags(p, args)
+    if args.lpips_weights is not None and not args.device_metrics:
+        p.error('--lpips_weights needs --device_metrics (the host path scores PSNR / SSIM / MAE only)')
+    return args
 
 
 def add_calibration_flags(p):
@@ -266,7 +279,7 @@ def main(argv=None):
     import torch.distributed as dist
     from backbones.ncsnpp_generator_adagn_feat import NCSNpp, NCSNpp_adaptive
     from .distributed import broadcast_parameters
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     logging.basicConfig(level=logging.INFO, format='%(asctime)s | %(levelname)s | %(message)s')
     rank, world, local = (int(os.environ.get(k, d)) for k, d in (('RANK', 0), ('WORLD_SIZE', 1), ('LOCAL_RANK', 0)))
     torch.cuda.set_device(local)
@@ -294,7 +307,8 @@ def main(argv=None):
     png_dir = None if args.no_png else os.path.join(args.output_path, 'generated_samples')
     if args.device_metrics:                                      # every rank scores its shard; rank 0 gathers per-slice sums only
         from . import metrics
-        res = metrics.score_distributed(lo, preds, gts, png_dir)
+        lp = metrics.load_lpips(args)                            # every rank reads the (~10 MB) weights itself
+        res = metrics.score_distributed(lo, preds, gts, png_dir, lpips=lp)
     else:
         if world > 1:                                            # gather the shards on rank 0 (256 KB per slice)
             parts = [None] * world
@@ -304,8 +318,9 @@ def main(argv=None):
                 preds, gts = np.concatenate([p[1] for p in parts], 0), np.concatenate([p[2] for p in parts], 0)
         res = export_and_score(list(preds), list(gts), png_dir) if rank == 0 else None
     if rank == 0:
-        logging.info('Average PSNR: %.4f dB  SSIM: %.4f  MAE: %.6f over %d slices (global range [%.4f, %.4f])', res['psnr'], res['ssim'],
-                     res['mae'], res['count'], res['global_min'], res['global_max'])
+        logging.info('Average PSNR: %.4f dB  SSIM: %.4f  MAE: %.6f over %d slices (global range [%.4f, %.4f])%s', res['psnr'], res['ssim'],
+                     res['mae'], res['count'], res['global_min'], res['global_max'],
+                     '  LPIPS: %.6f' % res['lpips'] if 'lpips' in res else '')
     if world > 1:
         dist.destroy_process_group()
 

@@ -765,6 +765,50 @@ def slice_metrics_u8(pred, gt):
     return sse, sae, ssim_sum
 
 
+LPIPS_WS_CAP = 512 << 20      # bytes of workspace per lpips_u8 launch sequence: larger n is split into chunks
+
+
+def lpips_pack(table, conv_w, conv_b, lin_w):
+    """Packed LPIPS-alex weights (mud_lpips_pack) from device fp32 tensors in torch layout: the input table [768], the 5 AlexNet conv
+    weights [Cout, Cin, k, k] and biases [Cout], the 5 lin weights [C] -> device uint8 tensor of mud_lpips_packed_bytes()."""
+    require_gpu(table, *conv_w, *conv_b, *lin_w)
+    table = _f32(table.contiguous())
+    conv_w, conv_b, lin_w = ([_f32(t.contiguous()) for t in ts] for ts in (conv_w, conv_b, lin_w))
+    packed = torch.empty(load().mud_lpips_packed_bytes(), device=table.device, dtype=torch.uint8)
+    arr = lambda ts: (C.c_void_p * 5)(*[ptr(t) for t in ts])       # noqa: E731
+    _launch('lpips_pack', table.device, load().mud_lpips_pack, ptr(table), arr(conv_w), arr(conv_b), arr(lin_w), ptr(packed), STREAM)
+    return packed
+
+
+def lpips_u8(pred_u8, gt_u8, net, max_ws_bytes=LPIPS_WS_CAP):
+    """LPIPS-alex per tap of uint8 image pairs [n, H, W] (H, W >= 31) with the packed weights of `net` (mudiff_hip.lpips_net.LpipsAlex
+    on the images' device) -> device fp64 [n, 5]; LPIPS = the row sum.  Slices go through in chunks whose workspace stays within
+    `max_ws_bytes`; a slice's result does not depend on the chunking (or on the other slices of its launch)."""
+    require_gpu(pred_u8, gt_u8)
+    if pred_u8.dtype != torch.uint8 or gt_u8.dtype != torch.uint8 or pred_u8.dim() != 3 or pred_u8.shape != gt_u8.shape:
+        raise MudiffHipError(f'lpips_u8: need two uint8 [n, H, W] tensors of one shape (got {pred_u8.dtype} {tuple(pred_u8.shape)}, '
+                             f'{gt_u8.dtype} {tuple(gt_u8.shape)})')
+    n, H, W = pred_u8.shape
+    if H < 31 or W < 31:
+        raise MudiffHipError(f'lpips_u8: slices must be at least 31x31 (AlexNet\'s two pools), got {H}x{W}')
+    packed = getattr(net, 'packed', None)
+    if packed is None or packed.device != pred_u8.device:
+        raise MudiffHipError(f'lpips_u8: the LPIPS weights are not packed on {pred_u8.device} (call net.to(device) first)')
+    out = torch.empty(n, 5, device=pred_u8.device, dtype=torch.float64)
+    if n == 0:
+        return out
+    lib = load()
+    chunk = max(1, min(n, int(max_ws_bytes) // max(lib.mud_lpips_ws_bytes(1, H, W), 1)))
+    nbytes = lib.mud_lpips_ws_bytes(chunk, H, W)
+    ws = torch.empty(nbytes, device=pred_u8.device, dtype=torch.uint8)
+    pin, gin = pred_u8.contiguous(), gt_u8.contiguous()
+    for c0 in range(0, n, chunk):
+        m = min(chunk, n - c0)
+        _launch('lpips_u8', pred_u8.device, lib.mud_lpips_u8, ptr(pin[c0:c0 + m]), ptr(gin[c0:c0 + m]), m, H, W, ptr(packed),
+                ptr(out[c0:c0 + m]), ptr(ws), nbytes, STREAM, flops=3.47e9 * m * (H * W / 65536.0))
+    return out
+
+
 def to_range_0_1(x):
     """[-1,1] -> [0,1] with clipping: ((x + 1) / 2).clamp(0, 1) (reference engine/test_volume.py:281)."""
     return affine_clamp(x, 0.5, 0.5, 0.0, 1.0)
