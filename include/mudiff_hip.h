@@ -293,6 +293,20 @@ int64_t mud_lpips_ws_bytes(int n, int H, int W);
 int mud_lpips_u8(const uint8_t* pred, const uint8_t* gt, int n, int H, int W, const void* packed, double* out, void* ws,
                  int64_t ws_bytes, void* stream);
 
+/* ---- N-sample ensemble inference (mudiff_hip.ensemble; the drivers' --num_samples).  Every Gaussian of an ensemble is a pure function
+ *      of (seed, slice, sample, step, kind, element), so results do not depend on batch size, chunking or rank count.
+ * mud_randn_keyed: out[r*row_len + e] for row r with keys[2r..2r+1] = (slice s >= 0, sample j in [0, 2^31)) (device int64 [rows][2]):
+ * Philox4x64-10 (numpy.random.Philox's algorithm and word order) with key (seed, 0x4D55444946460001) and counter
+ * (e/4, s, (j << 32) | (step << 8) | kind, 0); lane l = e % 4 takes the word pair (w[2(l/2)], w[2(l/2)+1]) = (wa, wb),
+ * u1 = ((wa >> 11) + 1) 2^-53, u2 = (wb >> 11) 2^-53, r = sqrt(-2 log u1), theta = 2 pi u2: r cos theta (even l), r sin theta (odd l),
+ * in fp64, rounded once to fp32.  kind: 0 x_init, 1 z, 2 posterior noise; step in [0, 2^24); row_len > 0.
+ * mud_ensemble_stats: samples [n][N][hw] -> mean, std [n][hw] (N >= 2, hw > 0): y = clamp(x*scale + shift, lo, hi) in fp32 (each step
+ * rounded once, NaN kept), m = (sum_j y_j) / N and v = sum_j (y_j - m)^2 / (N - 1) in fp64 in sample order j = 0..N-1,
+ * mean = (float)m, std = (float)sqrt(v); a NaN sample gives NaN in both.  No atomics: a fixed function of the samples. */
+int mud_randn_keyed(float* out, int rows, int64_t row_len, const int64_t* keys, uint64_t seed, int step, int kind, void* stream);
+int mud_ensemble_stats(const float* samples, int n, int N, int64_t hw, float scale, float shift, float lo, float hi, float* mean,
+                       float* std, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

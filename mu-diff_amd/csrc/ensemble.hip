@@ -1,0 +1,218 @@
+// N-sample ensemble inference (include/mudiff_hip.h: mud_randn_keyed, mud_ensemble_stats).
+//
+// The sampler is stochastic: x_init, every step's latent z and every step's posterior noise are Gaussian draws.  Sampling a slice N
+// times and reporting the per-pixel mean and spread shows where a synthesis is unsure of itself.  Two kernels serve it:
+//  - keyed draws: every Gaussian is a pure function of (seed, slice, sample, step, kind, element) through counter-based
+//    Philox4x64-10 (Random123; the algorithm and word order of numpy.random.Philox), so an ensemble does not depend on batch size,
+//    chunking or rank count, and nothing is pre-drawn;
+//  - statistics: per pixel, the fp64 mean and unbiased standard deviation over the N samples, summed in sample order with no
+//    atomics and no contraction: a fixed function of the samples.
+// DESIGN.md section 5.7 has the definitions and the order arguments.
+#include "mud_common.h"
+
+#define ES_THREADS 256
+#define ES_KEY_HI 0x4D55444946460001ull
+
+// ---- Philox4x64-10 ----------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void es_philox_round(uint64_t& c0, uint64_t& c1, uint64_t& c2, uint64_t& c3, uint64_t k0, uint64_t k1) {
+  const uint64_t lo0 = 0xD2E7470EE14C6C93ull * c0, hi0 = __umul64hi(0xD2E7470EE14C6C93ull, c0);
+  const uint64_t lo1 = 0xCA5A826395121157ull * c2, hi1 = __umul64hi(0xCA5A826395121157ull, c2);
+  const uint64_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
+  c0 = n0;
+  c1 = lo1;
+  c2 = n2;
+  c3 = lo0;
+}
+
+__device__ __forceinline__ void es_philox(uint64_t& c0, uint64_t& c1, uint64_t& c2, uint64_t& c3, uint64_t k0, uint64_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    if (r) {
+      k0 += 0x9E3779B97F4A7C15ull;
+      k1 += 0xBB67AE8584CAA73Bull;
+    }
+    es_philox_round(c0, c1, c2, c3, k0, k1);
+  }
+}
+
+// Box-Muller on one word pair, all in fp64: u1 in (0, 1], u2 in [0, 1)
+__device__ __forceinline__ void es_box_muller(uint64_t wa, uint64_t wb, float& a, float& b) {
+  const double u1 = (double)((wa >> 11) + 1) * 0x1.0p-53;
+  const double u2 = (double)(wb >> 11) * 0x1.0p-53;
+  const double r = sqrt(-2.0 * log(u1));
+  double s, c;
+  sincos(6.283185307179586 * u2, &s, &c);
+  a = (float)(r * c);
+  b = (float)(r * s);
+}
+
+// one thread = one Philox block = 4 consecutive elements of one row
+__global__ __launch_bounds__(ES_THREADS) void k_randn_keyed(float* __restrict__ out, int rows, int64_t row_len, int64_t blocks_per_row,
+                                                            const int64_t* __restrict__ keys, uint64_t seed, uint64_t word2, int vec) {
+  const int64_t t = (int64_t)blockIdx.x * ES_THREADS + threadIdx.x;
+  if (t >= (int64_t)rows * blocks_per_row) return;
+  const int64_t r = t / blocks_per_row, b = t - r * blocks_per_row;
+  const uint64_t slice = (uint64_t)keys[2 * r], sample = (uint64_t)keys[2 * r + 1];
+  uint64_t c0 = (uint64_t)b, c1 = slice, c2 = (sample << 32) | word2, c3 = 0;
+  es_philox(c0, c1, c2, c3, seed, ES_KEY_HI);
+  f32x4 v;
+  float a, bb;
+  es_box_muller(c0, c1, a, bb);
+  v[0] = a;
+  v[1] = bb;
+  es_box_muller(c2, c3, a, bb);
+  v[2] = a;
+  v[3] = bb;
+  float* dst = out + r * row_len + 4 * b;
+  if (vec) {                       // row_len % 4 == 0 and out 16-byte aligned: every block is whole and aligned
+    *reinterpret_cast<f32x4*>(dst) = v;
+  } else {
+    const int64_t n = row_len - 4 * b < 4 ? row_len - 4 * b : 4;
+    for (int e = 0; e < n; ++e) dst[e] = v[e];
+  }
+}
+
+extern "C" int mud_randn_keyed(float* out, int rows, int64_t row_len, const int64_t* keys, uint64_t seed, int step, int kind, void* stream) {
+  MUD_REQUIRE(rows >= 0 && row_len > 0, "mud_randn_keyed: bad sizes (rows %d, row_len %lld)", rows, (long long)row_len);
+  MUD_REQUIRE(kind >= 0 && kind <= 2, "mud_randn_keyed: kind must be 0 (x_init), 1 (z) or 2 (posterior noise), got %d", kind);
+  MUD_REQUIRE(step >= 0 && step < (1 << 24), "mud_randn_keyed: step must be in [0, 2^24), got %d", step);
+  MUD_REQUIRE(out && keys, "mud_randn_keyed: null pointer");
+  if (rows == 0) return MUD_OK;
+  const int64_t bpr = mud_cdiv(row_len, 4);
+  const int64_t threads = (int64_t)rows * bpr;
+  MUD_REQUIRE(mud_cdiv(threads, ES_THREADS) <= 0x7fffffff, "mud_randn_keyed: too many elements");
+  const int vec = (row_len % 4 == 0) && mud_aligned16(out);
+  const uint64_t word2 = ((uint64_t)step << 8) | (uint64_t)kind;
+  hipLaunchKernelGGL(k_randn_keyed, dim3((unsigned)mud_cdiv(threads, ES_THREADS)), dim3(ES_THREADS), 0, (hipStream_t)stream, out, rows,
+                     row_len, bpr, keys, seed, word2, vec);
+  MUD_CHECK_LAUNCH("mud_randn_keyed");
+  return MUD_OK;
+}
+
+// ---- per-pixel ensemble statistics --------------------------------------------------------------------------------------------------
+// y = clamp(x*scale + shift, lo, hi) with the fp32 steps of mud_affine_clamp, each rounded once (no contraction); unlike fminf / fmaxf
+// alone, a NaN stays NaN (np.clip semantics) so that it reaches both outputs
+__device__ __forceinline__ float es_premap(float x, float scale, float shift, float lo, float hi) {
+#pragma clang fp contract(off)
+  const float t = x * scale + shift;
+  return t != t ? t : fminf(fmaxf(t, lo), hi);
+}
+
+// m = (sum_j y_j) / N and v = sum_j (y_j - m)^2 / (N - 1), fp64 in sample order j = 0..N-1.  Up to ES_CAP samples stay in registers
+// (one read of the samples); more are read a second time for the deviations.
+#define ES_CAP 16
+template <int W>
+__device__ __forceinline__ void es_load(const float* __restrict__ p, float (&x)[W]) {
+  if constexpr (W == 4) {           // 16-byte aligned (k_ensemble_stats4): one dwordx4 load
+    const f32x4 v = *reinterpret_cast<const f32x4*>(p);
+#pragma unroll
+    for (int w = 0; w < 4; ++w) x[w] = v[w];
+  } else {
+#pragma unroll
+    for (int w = 0; w < W; ++w) x[w] = p[w];
+  }
+}
+
+template <int W>
+__device__ __forceinline__ void es_stats(const float* __restrict__ src, int N, int64_t hw, float scale, float shift, float lo, float hi,
+                                         double (&m)[W], double (&v)[W]) {
+#pragma clang fp contract(off)
+  float y[ES_CAP][W];
+  double s[W];
+#pragma unroll
+  for (int w = 0; w < W; ++w) s[w] = 0.0;
+#pragma unroll
+  for (int j = 0; j < ES_CAP; ++j) {
+    if (j < N) {
+      float x[W];
+      es_load<W>(src + (int64_t)j * hw, x);
+#pragma unroll
+      for (int w = 0; w < W; ++w) {
+        y[j][w] = es_premap(x[w], scale, shift, lo, hi);
+        s[w] += (double)y[j][w];
+      }
+    }
+  }
+  for (int j = ES_CAP; j < N; ++j) {
+    float x[W];
+    es_load<W>(src + (int64_t)j * hw, x);
+#pragma unroll
+    for (int w = 0; w < W; ++w) s[w] += (double)es_premap(x[w], scale, shift, lo, hi);
+  }
+#pragma unroll
+  for (int w = 0; w < W; ++w) {
+    m[w] = s[w] / (double)N;
+    v[w] = 0.0;
+  }
+#pragma unroll
+  for (int j = 0; j < ES_CAP; ++j) {
+    if (j < N) {
+#pragma unroll
+      for (int w = 0; w < W; ++w) {
+        const double d = (double)y[j][w] - m[w];
+        v[w] += d * d;
+      }
+    }
+  }
+  for (int j = ES_CAP; j < N; ++j) {
+    float x[W];
+    es_load<W>(src + (int64_t)j * hw, x);
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+      const double d = (double)es_premap(x[w], scale, shift, lo, hi) - m[w];
+      v[w] += d * d;
+    }
+  }
+#pragma unroll
+  for (int w = 0; w < W; ++w) v[w] = v[w] / (double)(N - 1);
+}
+
+// one thread = 4 consecutive pixels of one slice (vec: hw % 4 == 0 and every pointer 16-byte aligned), else one pixel
+__global__ __launch_bounds__(ES_THREADS) void k_ensemble_stats4(const float* __restrict__ x, int n, int N, int64_t hw, float scale, float shift,
+                                                                float lo, float hi, float* __restrict__ mean, float* __restrict__ std) {
+  const int64_t q = hw / 4;
+  const int64_t t = (int64_t)blockIdx.x * ES_THREADS + threadIdx.x;
+  if (t >= (int64_t)n * q) return;
+  const int64_t i = t / q, p = 4 * (t - i * q);
+  const float* src = x + (int64_t)i * N * hw + p;
+  double m[4], v[4];
+  es_stats<4>(src, N, hw, scale, shift, lo, hi, m, v);
+  f32x4 om, os;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    om[w] = (float)m[w];
+    os[w] = (float)sqrt(v[w]);
+  }
+  *reinterpret_cast<f32x4*>(mean + i * hw + p) = om;
+  *reinterpret_cast<f32x4*>(std + i * hw + p) = os;
+}
+
+__global__ __launch_bounds__(ES_THREADS) void k_ensemble_stats1(const float* __restrict__ x, int n, int N, int64_t hw, float scale, float shift,
+                                                                float lo, float hi, float* __restrict__ mean, float* __restrict__ std) {
+  const int64_t t = (int64_t)blockIdx.x * ES_THREADS + threadIdx.x;
+  if (t >= (int64_t)n * hw) return;
+  const int64_t i = t / hw, p = t - i * hw;
+  double m[1], v[1];
+  es_stats<1>(x + (int64_t)i * N * hw + p, N, hw, scale, shift, lo, hi, m, v);
+  mean[i * hw + p] = (float)m[0];
+  std[i * hw + p] = (float)sqrt(v[0]);
+}
+
+extern "C" int mud_ensemble_stats(const float* samples, int n, int N, int64_t hw, float scale, float shift, float lo, float hi, float* mean,
+                                  float* std, void* stream) {
+  MUD_REQUIRE(n >= 0 && hw > 0, "mud_ensemble_stats: bad sizes (n %d, hw %lld)", n, (long long)hw);
+  MUD_REQUIRE(N >= 2, "mud_ensemble_stats: N must be >= 2 (the spread needs two samples), got %d", N);
+  MUD_REQUIRE(samples && mean && std, "mud_ensemble_stats: null pointer");
+  if (n == 0) return MUD_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const bool vec = hw % 4 == 0 && mud_aligned16(samples) && mud_aligned16(mean) && mud_aligned16(std);
+  const int64_t threads = vec ? (int64_t)n * (hw / 4) : (int64_t)n * hw;
+  MUD_REQUIRE(mud_cdiv(threads, ES_THREADS) <= 0x7fffffff, "mud_ensemble_stats: too many pixels");
+  const dim3 grid((unsigned)mud_cdiv(threads, ES_THREADS));
+  if (vec)
+    hipLaunchKernelGGL(k_ensemble_stats4, grid, dim3(ES_THREADS), 0, s, samples, n, N, hw, scale, shift, lo, hi, mean, std);
+  else
+    hipLaunchKernelGGL(k_ensemble_stats1, grid, dim3(ES_THREADS), 0, s, samples, n, N, hw, scale, shift, lo, hi, mean, std);
+  MUD_CHECK_LAUNCH("mud_ensemble_stats");
+  return MUD_OK;
+}

@@ -123,6 +123,8 @@ _SIGNATURES = {
     'mud_lpips_pack': (_I, [_P, _P, _P, _P, _P, _P]),
     'mud_lpips_ws_bytes': (_L, [_I, _I, _I]),
     'mud_lpips_u8': (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _L, _P]),
+    'mud_randn_keyed': (_I, [_P, _I, _L, _P, C.c_uint64, _I, _I, _P]),
+    'mud_ensemble_stats': (_I, [_P, _I, _I, _L, _F, _F, _F, _F, _P, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -211,6 +211,51 @@ def sample_slices(args, gen1, gen2, source, batch_size, device, rank=0, world=1,
     return lo, cat(preds), cat(gts)
 
 
+def sample_slices_ensemble(args, gen1, gen2, source, batch_size, device, rank=0, world=1, progress=None):
+    """--num_samples: this rank's contiguous shard of `source`, every slice sampled args.num_samples times with draws keyed by
+    (args.ensemble_seed, GLOBAL slice number, sample) (mudiff_hip.ensemble), in groups of ensemble.default_chunk slices through one
+    captured sampler.  -> (lo, ensemble means [n,H,W], targets [n,H,W], stds [n,H,W]), fp32 tensors on `device`.  The means and stds
+    are of the raw [-1,1] samples, so the means go through the global-range 8-bit export like single draws."""
+    from . import ensemble
+    from . import sampling as S
+    from .distributed import shard_range
+    lo, hi = shard_range(len(source), rank, world)
+    device = torch.device(device)
+    N, size = int(args.num_samples), int(args.image_size)
+    means, stds, gts = [], [], []
+    sampler = None
+    group = ensemble.default_chunk(N, size, hi - lo)
+    for g0 in range(lo, hi, group):
+        c1, c2, c3, y = source.batch(g0, min(g0 + group, hi))
+        if sampler is None:
+            sampler = S.GraphSampler(S.Posterior_Coefficients(args, device), gen1, gen2, args, batch_size, c1.shape[2], c1.shape[3], device)
+        m, sd = ensemble.sample_ensemble(args, gen1, gen2, [c.to(device) for c in (c1, c2, c3)], N, args.ensemble_seed, slice_offset=g0,
+                                         sampler=sampler)
+        means.append(m)
+        stds.append(sd)
+        gts.append(y[:, 0].to(device))
+        if progress:
+            progress(min(g0 + group, hi) - lo, hi - lo)
+    tcat = (lambda xs: torch.cat(xs, 0) if xs else torch.zeros((0, 1, 1), dtype=torch.float32, device=device))
+    return lo, tcat(means), tcat(gts), tcat(stds)
+
+
+def ensemble_summary(stds, lo, png_dir, device):
+    """Std maps of this rank's shard -> generated_samples/std/std_{global:05d}.png, quantised with the 8-bit export over
+    [0, max std over all ranks] ([0, 1] when that max is 0); -> the mean std over every pixel of every rank (python float)."""
+    from . import ops
+    from .distributed import max_over_ranks, sum_over_ranks
+    smax = max_over_ranks(float(stds.max()) if stds.numel() else 0.0, device)
+    total, count = sum_over_ranks([float(stds.double().sum()) if stds.numel() else 0.0, float(stds.numel())], device)
+    if png_dir is not None and stds.shape[0]:
+        from PIL import Image
+        q = ops.quantize_u8(stds.contiguous(), 0.0, smax if smax > 0 else 1.0).cpu().numpy()
+        os.makedirs(os.path.join(png_dir, 'std'), exist_ok=True)
+        for i, s in enumerate(q):
+            Image.fromarray(s).save(os.path.join(png_dir, 'std', f'std_{lo + i:05d}.png'))
+    return total / max(count, 1.0)
+
+
 def build_parser():
     p = argparse.ArgumentParser('mudiff MI355X batched test driver (flags as in the reference engine/test.py:400-484)')
     p.add_argument('--centered', action='store_false', default=True)
@@ -253,17 +298,28 @@ def build_parser():
     from .metrics import add_lpips_flags
     add_lpips_flags(p)
     add_calibration_flags(p)
+    p.add_argument('--num_samples', type=int, default=None,
+                   help='sample every slice N >= 2 times with keyed draws (mudiff_hip.ensemble): the ensemble mean is scored and exported '
+                        'in place of the single draw, and per-pixel std maps go to generated_samples/std (needs --device_metrics)')
+    p.add_argument('--ensemble_seed', type=int, default=1024, help='seed of the keyed draws of --num_samples')
     return p
 
 
 def parse_args(argv=None):
-    """build_parser().parse_args plus the flag rules: the LPIPS flags need --device_metrics."""
+    """build_parser().parse_args plus the flag rules: the LPIPS flags and --num_samples need --device_metrics, --num_samples >= 2."""
     from .metrics import check_lpips_flags
     p = build_parser()
     args = p.parse_args(argv)
     check_lpips_flags(p, args)
     if args.lpips_weights is not None and not args.device_metrics:
         p.error('--lpips_weights needs --device_metrics (the host path scores PSNR / SSIM / MAE only)')
+    if args.num_samples is not None:
+        if args.num_samples < 2:
+            p.error(f'--num_samples must be >= 2 (got {args.num_samples}): the spread needs two samples per slice')
+        if not args.device_metrics:
+            p.error('--num_samples needs --device_metrics (the ensemble statistics stay on the GPUs)')
+        if not 0 <= args.ensemble_seed < 1 << 64:
+            p.error('--ensemble_seed must lie in [0, 2^64)')
     return args
 
 
@@ -301,14 +357,21 @@ def main(argv=None):
             logging.info('rank %d: %s', rank, cal.summary())
             if rank == 0:
                 write_calibration(cal, args.output_path)
-    lo, preds, gts = sample_slices(args, g1, g2, source, args.batch_size, device, rank, world,
-                                   progress=lambda d, n: logging.info('rank %d: %d/%d slices', rank, d, n) if d % (args.batch_size * 8) == 0 else None,
-                                   keep_on_device=args.device_metrics)
     png_dir = None if args.no_png else os.path.join(args.output_path, 'generated_samples')
+    ens = None
+    if args.num_samples is not None:                             # the ensemble mean stands in for the single draw
+        lo, preds, gts, stds = sample_slices_ensemble(args, g1, g2, source, args.batch_size, device, rank, world,
+                                                      progress=lambda d, n: logging.info('rank %d: %d/%d slices', rank, d, n))
+    else:
+        lo, preds, gts = sample_slices(args, g1, g2, source, args.batch_size, device, rank, world,
+                                       progress=lambda d, n: logging.info('rank %d: %d/%d slices', rank, d, n) if d % (args.batch_size * 8) == 0 else None,
+                                       keep_on_device=args.device_metrics)
     if args.device_metrics:                                      # every rank scores its shard; rank 0 gathers per-slice sums only
         from . import metrics
         lp = metrics.load_lpips(args)                            # every rank reads the (~10 MB) weights itself
         res = metrics.score_distributed(lo, preds, gts, png_dir, lpips=lp)
+        if args.num_samples is not None:                         # after the scoring, which refuses NaN on every rank alike
+            ens = ensemble_summary(stds, lo, png_dir, device)
     else:
         if world > 1:                                            # gather the shards on rank 0 (256 KB per slice)
             parts = [None] * world
@@ -320,7 +383,8 @@ def main(argv=None):
     if rank == 0:
         logging.info('Average PSNR: %.4f dB  SSIM: %.4f  MAE: %.6f over %d slices (global range [%.4f, %.4f])%s', res['psnr'], res['ssim'],
                      res['mae'], res['count'], res['global_min'], res['global_max'],
-                     '  LPIPS: %.6f' % res['lpips'] if 'lpips' in res else '')
+                     ('  LPIPS: %.6f' % res['lpips'] if 'lpips' in res else '') +
+                     ('' if ens is None else '  ensemble: %d samples, mean std %.6f' % (args.num_samples, ens)))
     if world > 1:
         dist.destroy_process_group()
 

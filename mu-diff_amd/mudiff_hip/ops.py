@@ -815,3 +815,79 @@ def to_range_0_1(x):
 
 
 INV_SQRT2 = 1.0 / math.sqrt(2.0)
+
+
+# ---------------------------------------------------------------------------------------------------
+# N-sample ensembles (csrc/ensemble.hip, mudiff_hip.ensemble)
+KIND_X_INIT, KIND_Z, KIND_NOISE = 0, 1, 2
+_MAX_SAMPLE = 1 << 31
+
+
+def check_keys(keys):
+    """(slice, sample) row keys -> an int64 [rows, 2] tensor on the host, refused unless slice >= 0 and 0 <= sample < 2^31.  A device
+    tensor is copied to the host for the check (one synchronisation)."""
+    k = torch.as_tensor(keys).detach().to('cpu', torch.int64)
+    if k.dim() != 2 or k.shape[1] != 2:
+        raise MudiffHipError(f'randn_keyed: keys must be [rows, 2] = (slice, sample), got {tuple(k.shape)}')
+    if k.numel() and int(k[:, 0].min()) < 0:
+        raise MudiffHipError('randn_keyed: slice indices must be >= 0')
+    if k.numel() and (int(k[:, 1].min()) < 0 or int(k[:, 1].max()) >= _MAX_SAMPLE):
+        raise MudiffHipError('randn_keyed: sample indices must lie in [0, 2^31)')
+    return k.contiguous()
+
+
+def _seed64(seed):
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise MudiffHipError(f'randn_keyed: seed must lie in [0, 2^64), got {seed}')
+    return seed
+
+
+def randn_keyed_into(out, keys_dev, seed, step, kind):
+    """Unchecked launch of ops.randn_keyed into `out` (fp32, contiguous, [rows, ...]) with keys already through check_keys and on
+    out's device (GraphSampler.sample_keyed checks its keys once per batch, not once per draw)."""
+    rows = keys_dev.shape[0]
+    _launch('randn_keyed', out.device, load().mud_randn_keyed, ptr(out), rows, out.numel() // max(rows, 1), ptr(keys_dev), C.c_uint64(seed),
+            int(step), int(kind), STREAM)
+    return out
+
+
+def randn_keyed(rows_keys, row_len, seed, step, kind, out=None):
+    """Keyed standard normals: row r of the fp32 result [rows, row_len] is a pure function of (seed, slice, sample, step, kind) with
+    rows_keys[r] = (slice, sample) (int64 [rows, 2], host or device): Philox4x64-10 + Box-Muller in fp64 (mud_randn_keyed).  `out`:
+    a contiguous fp32 device tensor of rows * row_len elements to fill (any shape); without it the result lands on rows_keys's device
+    (or the current one for host keys).  kind: KIND_X_INIT, KIND_Z or KIND_NOISE."""
+    k = check_keys(rows_keys)
+    seed = _seed64(seed)
+    rows, row_len = k.shape[0], int(row_len)
+    if out is None:
+        dev = rows_keys.device if isinstance(rows_keys, torch.Tensor) and rows_keys.is_cuda else torch.device('cuda', torch.cuda.current_device())
+        out = torch.empty(rows, row_len, device=dev, dtype=torch.float32)
+    require_gpu(out)
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != rows * row_len:
+        raise MudiffHipError(f'randn_keyed: out must be a contiguous fp32 tensor of {rows} x {row_len} elements, got {out.dtype} '
+                             f'{tuple(out.shape)}')
+    _launch('randn_keyed', out.device, load().mud_randn_keyed, ptr(out), rows, row_len, ptr(k.to(out.device)), C.c_uint64(seed), int(step),
+            int(kind), STREAM)
+    return out
+
+
+def ensemble_stats(samples, scale=1.0, shift=0.0, lo=-math.inf, hi=math.inf):
+    """Per-pixel mean and standard deviation (N - 1) over the samples of each slice: samples [n, N, ...] (N >= 2, fp32) -> (mean, std),
+    fp32 [n, ...], of y = clamp(samples*scale + shift, lo, hi); fp64 sums in sample order, so a fixed function of the samples
+    (mud_ensemble_stats).  scale = shift = 0.5, [0, 1] is the pre-map of ops.to_range_0_1."""
+    require_gpu(samples)
+    if samples.dim() < 3:
+        raise MudiffHipError(f'ensemble_stats: samples must be [n, N, ...], got {tuple(samples.shape)}')
+    n, N = samples.shape[0], samples.shape[1]
+    if N < 2:
+        raise MudiffHipError(f'ensemble_stats: need N >= 2 samples per slice, got {N}')
+    x = _f32(samples.contiguous())
+    hw = x[0, 0].numel()
+    mean = torch.empty(n, *x.shape[2:], device=x.device, dtype=torch.float32)
+    std = torch.empty_like(mean)
+    if n == 0 or hw == 0:
+        return mean, std
+    _launch('ensemble_stats', x.device, load().mud_ensemble_stats, ptr(x), n, N, hw, float(scale), float(shift), float(lo), float(hi),
+            ptr(mean), ptr(std), STREAM, nbytes=4.0 * n * hw * (N + 2))
+    return mean, std

@@ -245,3 +245,27 @@ class GraphSampler:
             self.x.copy_(x_new)
         out = self.x.clone()
         return (out, steps) if return_steps else out
+
+    def sample_keyed(self, cond1, cond2, cond3, keys, seed, n_time):
+        """sample() with keyed draws (DESIGN.md section 5.7): row r of the batch is sample keys[r] = (slice, sample) of an ensemble;
+        x_init (kind 0, step 0) and every executed step k's z (kind 1) and posterior noise (kind 2) are drawn with ops.randn_keyed
+        on this device's current stream, so each row's result depends on (seed, its key) alone.  keys: int64 [B, 2] (host or device)."""
+        k = ops.check_keys(keys)
+        if k.shape[0] != self.B:
+            raise ValueError(f'GraphSampler.sample_keyed: {k.shape[0]} keys for a batch of {self.B}')
+        seed = ops._seed64(seed)
+        kd = k.to(self.x.device)
+        self.c1.copy_(cond1); self.c2.copy_(cond2); self.c3.copy_(cond3)
+        ops.randn_keyed_into(self.x, kd, seed, 0, ops.KIND_X_INIT)
+        for k_, i in enumerate(reversed(range(n_time))):
+            self.t.fill_(i)
+            ops.randn_keyed_into(self.z, kd, seed, k_, ops.KIND_Z)
+            ops.randn_keyed_into(self.noise, kd, seed, k_, ops.KIND_NOISE)
+            if k_ == 0:
+                self.graph.replay()
+                x_new = self._first_out[2]
+            else:
+                self.graph_rest.replay()
+                x_new = self._rest_out[2]
+            self.x.copy_(x_new)
+        return self.x.clone()

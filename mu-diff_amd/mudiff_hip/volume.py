@@ -270,7 +270,8 @@ def predict_slices(args, gen1, gen2, cond_stacks, device, batch_size=32, x_inits
 
 
 def predict_volume(args):
-    """Reference :209-300, same flags, same output file `predicted_<target>.nii.gz`."""
+    """Reference :209-300, same flags, same output file `predicted_<target>.nii.gz`.  With --num_samples the ensemble's mean goes
+    there and its std next to it; the return value is then the pair of paths."""
     from backbones.ncsnpp_generator_adagn_feat import NCSNpp, NCSNpp_adaptive
     torch.manual_seed(args.seed)
     torch.cuda.set_device(args.gpu_chose)
@@ -307,6 +308,9 @@ def predict_volume(args):
             from .driver import write_calibration
             print(f'[calibrate] {cal.summary()}')
             print(f'[calibrate] wrote {write_calibration(cal, args.output_dir)}')
+    num_samples = getattr(args, 'num_samples', None)
+    if num_samples is not None:
+        return _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref)
     pred = predict_slices(args, gen1, gen2, stacks, device, batch_size=args.batch_size, seed=args.seed,
                           progress=lambda d, n: print(f'[infer] processed {d}/{n} slices'))
     if tuple(shp[:2]) != tuple(pred.shape[1:]):
@@ -320,10 +324,33 @@ def predict_volume(args):
     return out_path
 
 
+def _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref):
+    """--num_samples: every slice sampled N times with draws keyed by (--seed, slice, sample) (mudiff_hip.ensemble); the mean and
+    the std of the [0,1]-mapped samples, resized back and re-assembled like the single prediction, go to predicted_<t>.nii.gz and
+    predicted_<t>_std.nii.gz.  -> (mean path, std path)."""
+    from . import ensemble, ops
+    shp, aff, hdr, s0, s1 = ref
+    size = int(args.image_size)
+    conds = upload_conds(stacks, size, device)
+    print(f'[infer] {conds[0].shape[0]} slices x {args.num_samples} samples')
+    mean, std = ensemble.sample_ensemble(args, gen1, gen2, conds, args.num_samples, args.seed, batch_size=args.batch_size, map_0_1=True)
+    os.makedirs(args.output_dir, exist_ok=True)
+    paths = []
+    for suffix, t in (('', mean), ('_std', std)):
+        if tuple(shp[:2]) != tuple(t.shape[1:]):
+            t = ops.resize_bilinear(t, shp[:2])
+        vol = reconstruct_volume_from_slices(list(t.cpu().numpy()), shp, s0, s1)
+        path = os.path.join(args.output_dir, f'predicted_{args.target_modality.lower()}{suffix}.nii.gz')
+        write_nifti(path, vol, aff, hdr)
+        paths.append(path)
+    print(f'[done] saved: {paths[0]} and {paths[1]} | shape={tuple(shp)} | slices={s0}..{s1} | {args.num_samples} samples per slice')
+    return tuple(paths)
+
+
 def build_argparser(argv=None):
     """Flags and defaults of the reference parser (:302-357; like it, returns the PARSED namespace), plus --centered (which
-    the generators read and the reference parser forgot), --batch_size, --resize_back and --calibrate / --calibrate_threshold
-    (mudiff_hip.precision; the record goes to <output_dir>/prec_calibration.json)."""
+    the generators read and the reference parser forgot), --batch_size, --resize_back, --calibrate / --calibrate_threshold
+    (mudiff_hip.precision; the record goes to <output_dir>/prec_calibration.json) and --num_samples (ensembles)."""
     p = argparse.ArgumentParser('MU-Diff volume prediction (MI355X)')
     for m in ('t1ce', 't1', 't2', 'flair'):
         p.add_argument(f'--input_{m}', type=str, help=f'Path to {m.upper()} NIfTI')
@@ -365,9 +392,17 @@ def build_argparser(argv=None):
     p.add_argument('--gpu_chose', type=int, default=0)
     p.add_argument('--batch_size', type=int, default=32, help='slices per captured reverse step (MI355X build)')
     p.add_argument('--resize_back', action='store_true', help='resample the prediction to the in-plane size of the inputs')
+    p.add_argument('--num_samples', type=int, default=None,
+                   help='sample every slice N >= 2 times with draws keyed by --seed (mudiff_hip.ensemble): predicted_<t>.nii.gz is then '
+                        'the mean of the [0,1]-mapped samples, and predicted_<t>_std.nii.gz their per-voxel standard deviation')
     from .driver import add_calibration_flags
     add_calibration_flags(p)
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.num_samples is not None and args.num_samples < 2:
+        p.error(f'--num_samples must be >= 2 (got {args.num_samples})')
+    if args.num_samples is not None and not 0 <= args.seed < 1 << 64:
+        p.error('--num_samples needs a --seed in [0, 2^64)')
+    return args
 
 
 if __name__ == '__main__':
