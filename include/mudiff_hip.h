@@ -46,6 +46,9 @@ extern "C" {
 #define MUD_PREC_16X3 0        /* every product as hi*hi + hi*lo + lo*hi on the 16-bit MFMA (fp16 pieces): ~2^-22 per product */
 #define MUD_PREC_FP8X 1        /* hi*hi on the fp16 MFMA + both cross terms on the block-scaled e4m3 MFMA: ~2^-15 per product, */
                                /* 0.78x the matrix cycles; 3x3 launches that fill the chip (mud_conv2d_mfma_prec_supported)     */
+#define MUD_PREC_16X1 2        /* ONE pass: fp16(a) * fp16(w) on the fp16 MFMA, fp32 accumulate: ~2^-11 per product, 1/3 of the */
+                               /* 16x3 matrix cycles, hi-only weights at half the bytes.  Every 3x3 launch (no 1x1 form); the    */
+                               /* accuracy class of autocast, NOT the parity plan (~1-2e-2 per sampling step from the reference)  */
 
 int mud_version(void);
 const char* mud_last_error(void);
@@ -186,6 +189,10 @@ int mud_pack_weights(const float* src, int64_t s_tap, int64_t s_ci, int64_t s_co
  * (w * 2^w_exp, (w - fp16(w)) * 2^(w_exp + 11)) in place of the lo planes; same size. */
 int mud_pack_weights_prec(const float* src, int64_t s_tap, int64_t s_ci, int64_t s_co, int64_t src_bstride,
                           int ks, int Cin, int Cout, int nbatch, int prec, int w_exp, void* dst, void* stream);
+/* Bytes of one packed operand for plan `prec`: MUD_PREC_16X3 / MUD_PREC_FP8X = mud_packed_weight_bytes; MUD_PREC_16X1 (ks == 3 only,
+ * fp16 hi planes alone: mud_pack_weights_prec writes them) ceil(Cout/64) * ceil(Cin/16) * 9 * 2048 + 4096, half the steps' bytes.
+ * -1 for a plan / ks pair that has no packed form. */
+int64_t mud_packed_weight_bytes_prec(int ks, int Cin, int Cout, int prec);
 int mud_conv2d_mfma(const mud_conv_args* a, void* stream);
 /* 1 when mud_conv2d_mfma has plan `prec` for this launch (sizes, prologue mode, skip_w, sub2 are looked at), else 0. */
 int mud_conv2d_mfma_prec_supported(const mud_conv_args* a, int prec);

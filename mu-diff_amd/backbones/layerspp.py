@@ -59,10 +59,19 @@ class PlanScope:
 
 
 def bind_plan_scope(root: nn.Module, scope: PlanScope):
-    """Give every _Prepared module under `root` (itself included) the scope and its state_dict prefix."""
+    """Give every _Prepared module under `root` (itself included) the scope and its state_dict prefix, and every module that
+    launches a conv of its own weights (the input pyramid's Downsample, FIR Conv2d) its state_dict name for launch records."""
     for name, m in root.named_modules():
         if isinstance(m, _Prepared):
             m.__dict__['_plan_bound'] = (scope, name + '.' if name else '')
+        if isinstance(m, (Downsample, up_or_down_sampling.Conv2d)):
+            m.__dict__['_layer_name'] = name
+
+
+def _child_name(m, child):
+    """State_dict name of `m`'s submodule `child` (bind_plan_scope), or `child` alone for a module no generator has bound."""
+    base = m.__dict__.get('_layer_name')
+    return child if base is None else (base + '.' + child if base else child)
 
 
 class _Prepared:
@@ -123,7 +132,7 @@ class ConvParam:
         self.mfma = ConvParam.uses_mfma(self.cout, self.cin, self.ks, conv.stride, conv.padding)
         self.w = ops.pack_conv_weight(w) if self.mfma else ops.direct_weight(w)
         self.bias = conv.bias.detach().contiguous() if conv.bias is not None else None
-        self._w32, self._w8, self.w_exp = w, None, 0       # the fp32 weight stays referenced: other arithmetic plans are packed on first use
+        self._w32, self._w8, self._w16, self.w_exp = w, None, None, 0   # the fp32 weight stays referenced: other plans are packed on first use
         self.name, self.scope = name, None                  # layer name and the generator's PlanScope, once bound
 
     def fp8x(self):
@@ -133,20 +142,32 @@ class ConvParam:
             self._w8 = ops.pack_conv_weight(self._w32, prec=ops.PREC_FP8X, w_exp=self.w_exp)
         return self._w8
 
+    def fp16(self):
+        """The operand packed for MUD_PREC_16X1 (fp16 hi planes alone, half the bytes), made on first use."""
+        if self._w16 is None:
+            self._w16 = ops.pack_conv_weight(self._w32, prec=ops.PREC_16X1)
+        return self._w16
+
     def plan(self, x, pro=None, skip=None, sub2=False):
-        """The arithmetic plan this launch would run with (ops.choose_prec; fp16 x 3 for a layer its generator overrides)."""
+        """The arithmetic plan this launch would run with (ops.choose_prec; fp16 x 3 for a layer its generator overrides).  The
+        single-pass plan ('fp16') is for the generators' layers only: a conv no generator has bound (the critic's) stays fp16 x 3."""
         if not self.mfma or self.ks != 3:
             return ops.PREC_16X3
         if self.scope is not None and self.name in self.scope.overrides:
             return ops.PREC_16X3
+        if ops.PREC_PLAN == 'fp16' and self.scope is None:
+            return ops.PREC_16X3
         return ops.choose_prec(x, self.cout, pro[2] if pro is not None else ops.PRO_NONE, skip=skip is not None, sub2=sub2)
 
     def __call__(self, x, **kw):
-        if self.plan(x, kw.get('pro'), kw.get('skip'), kw.get('sub2', False)) == ops.PREC_FP8X:
+        plan = self.plan(x, kw.get('pro'), kw.get('skip'), kw.get('sub2', False))
+        if plan == ops.PREC_FP8X:
             if precision.CENSUS:          # inside precision.census(): the e4m3 range census of this input first (eager only)
                 precision.record(self, x, kw.get('pro'))
-            return ops.conv(x, self.fp8x(), self.ks, self.cout, mfma=True, bias=self.bias, prec=ops.PREC_FP8X, w_exp=self.w_exp, **kw)
-        return ops.conv(x, self.w, self.ks, self.cout, mfma=self.mfma, bias=self.bias, **kw)
+            return ops.conv(x, self.fp8x(), self.ks, self.cout, mfma=True, bias=self.bias, prec=ops.PREC_FP8X, w_exp=self.w_exp, layer=self.name, **kw)
+        if plan == ops.PREC_16X1:
+            return ops.conv(x, self.fp16(), self.ks, self.cout, mfma=True, bias=self.bias, prec=ops.PREC_16X1, layer=self.name, **kw)
+        return ops.conv(x, self.w, self.ks, self.cout, mfma=self.mfma, bias=self.bias, layer=self.name, **kw)
 
 
 class AdaptiveGroupNorm(nn.Module):
@@ -281,12 +302,12 @@ class Downsample(nn.Module):
         self.fir, self.fir_kernel, self.with_conv, self.out_ch = fir, fir_kernel, with_conv, out_ch
         self._prep = None
 
-    def _naive_weights(self, mfma):
+    def _naive_weights(self, mfma, prec=ops.PREC_16X3):
         w = self.Conv_0.weight
-        key = (w._version, w.data_ptr(), mfma)
+        key = (w._version, w.data_ptr(), mfma, prec)
         if self._prep is None or self._prep[0] != key:
             with torch.no_grad():
-                self._prep = (key, ops.pack_conv_weight(w) if mfma else ops.direct_weight(w))
+                self._prep = (key, ops.pack_conv_weight(w, prec=prec) if mfma else ops.direct_weight(w))
         return self._prep[1]
 
     def run(self, x: View, res: View = None, out_scale=1.0, out: View = None):
@@ -294,7 +315,8 @@ class Downsample(nn.Module):
             return self.Conv2d_0.run(x, res=res, out_scale=out_scale, out=out)
         if self.with_conv:      # F.pad(x, (0,1,0,1)) + conv3x3(stride 2, padding 0): an identity "FIR" that only pads
             return up_or_down_sampling.padded_strided_conv(x, np.ones((1, 1), np.float32), (0, 1), self._naive_weights, 3,
-                                                           self.Conv_0.weight.shape[0], self.Conv_0.bias.detach(), res, out_scale, out)
+                                                           self.Conv_0.weight.shape[0], self.Conv_0.bias.detach(), res, out_scale, out,
+                                                           layer=_child_name(self, 'Conv_0'))
         assert res is None and out is None
         return up_or_down_sampling.resample_view(x, 'down', self.fir, self.fir_kernel)
 

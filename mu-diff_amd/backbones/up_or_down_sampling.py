@@ -97,14 +97,17 @@ def resample_view(x: View, direction, fir, fir_kernel):
     return View.from_nchw(r)
 
 
-def padded_strided_conv(x: View, kk, pad, weights, ks, cout, bias, res, out_scale, out):
+def padded_strided_conv(x: View, kk, pad, weights, ks, cout, bias, res, out_scale, out, layer=None):
     """FIR `kk` with padding `pad` (an identity tap = pure zero padding), then a stride-2 pad-0 ks x ks conv whose
-    epilogue adds bias / residual and rescales.  `weights(mfma)` returns the packed or direct-layout weights."""
+    epilogue adds bias / residual and rescales.  `weights(mfma, prec)` returns the packed (for plan `prec`) or direct-layout
+    weights; `layer`: the launch's name in a launch record."""
     if x.C % 4 == 0 and x.C >= 8 and ks == 3 and x.H % 2 == 0 and x.W % 2 == 0:
         # matrix-core path: the stride-2 pad-0 conv of the padded (H+1)x(W+1) image is the odd-position subset
         # of the stride-1 pad-1 conv (4x the MFMA work, still ~5x faster than the direct kernel)
         xf, _ = ops.fir_nhwc(x, kk, 1, 1, pad)
-        return ops.conv(xf, weights(True), 3, cout, mfma=True, bias=bias, res=res, out_scale=out_scale, out=out, sub2=True)
+        prec = ops.choose_prec(xf, cout, ops.PRO_NONE, sub2=True)       # (only the single-pass plan has a sub2 form)
+        return ops.conv(xf, weights(True, prec), 3, cout, mfma=True, bias=bias, res=res, out_scale=out_scale, out=out, sub2=True, prec=prec,
+                        layer=layer)
     if x.C % 4 == 0:
         xf, _ = ops.fir_nhwc(x, kk, 1, 1, pad)
     else:   # image pyramid with few channels: planes kernel
@@ -131,11 +134,11 @@ class Conv2d(nn.Module):
         self.up, self.down, self.resample_kernel, self.kernel, self.use_bias = up, down, resample_kernel, kernel, use_bias
         self._prep = None
 
-    def _weights(self, mfma=False):
-        key = (self.weight._version, self.weight.data_ptr(), mfma)
+    def _weights(self, mfma=False, prec=ops.PREC_16X3):
+        key = (self.weight._version, self.weight.data_ptr(), mfma, prec)
         if self._prep is None or self._prep[0] != key:
             with torch.no_grad():
-                self._prep = (key, ops.pack_conv_weight(self.weight) if mfma else ops.direct_weight(self.weight))
+                self._prep = (key, ops.pack_conv_weight(self.weight, prec=prec) if mfma else ops.direct_weight(self.weight))
         return self._prep[1]
 
     def run(self, x: View, res: View = None, out_scale=1.0, out: View = None):
@@ -146,7 +149,8 @@ class Conv2d(nn.Module):
         if not self.down:
             return ops.conv(x, self._weights(), self.kernel, self.weight.shape[0], mfma=False, bias=bias, res=res, out_scale=out_scale, out=out)
         kk, up, down, pad = fir_params('conv_down', self.resample_kernel, conv_k=self.kernel)
-        return padded_strided_conv(x, kk, pad, self._weights, self.kernel, self.weight.shape[0], bias, res, out_scale, out)
+        return padded_strided_conv(x, kk, pad, self._weights, self.kernel, self.weight.shape[0], bias, res, out_scale, out,
+                                   layer=self.__dict__.get('_layer_name', 'Conv2d_0'))    # (its state_dict name: layerspp.bind_plan_scope)
 
     def forward(self, x):
         return self.run(View.from_nchw(x)).to_nchw()

@@ -64,7 +64,7 @@ __device__ __forceinline__ int cm_e4m3x4(f32x4 v, float scale) {    // 4 floats 
 #define CM_GN_MAXC 1024         // most channels the folded GroupNorm finalisation takes (scale | shift arrays in LDS: up to 8 KiB)
 #define CM_GN_BYTES (2 * CM_GN_MAXC * 4)
 
-template <int KS, int MT, int WM, int WN, bool DUAL = false>
+template <int KS, int MT, int WM, int WN, bool DUAL = false, int PREC = MUD_PREC_16X3>
 struct CmGeo {
   static constexpr int NT = 64 * WM * WN;               // threads per workgroup
   static constexpr int TAPS = KS * KS;
@@ -73,7 +73,13 @@ struct CmGeo {
   static constexpr int ROWS = WM * MT;
   static constexpr int PW = 32 + KS - 1;
   static constexpr int P = (KS == 3) ? (ROWS + 2) * PW : 32 * WM * MT;
-  static constexpr int PLANE = P * CM_PIX;              // P pixel records [hi 32 B | lo 32 B | pad 16 B]
+  // MUD_PREC_16X1 (one pass, fp16(a) * fp16(w), fp32 accumulate; opt-in, not the parity plan): hi-only operands.  Pixel record
+  // [hi 32 B | pad 16 B]: the 48-B stride keeps the ds_read_b128 A reads conflict-free (3 r mod 16 is a permutation of a 16-lane
+  // read group, as 5 r mod 16 is for 80 B) and shrinks the A image to 0.6x; weight step [hi 2 KiB], half the bytes of a 16x3 step.
+  static constexpr bool H1 = PREC == MUD_PREC_16X1;
+  static constexpr int PIX = H1 ? 48 : CM_PIX;          // LDS bytes per pixel record of the A tile
+  static constexpr int BSTEP = H1 ? CM_BPLANE : CM_BSTEP;   // packed bytes of one (k16 chunk, tap) weight step
+  static constexpr int PLANE = P * PIX;                 // P pixel records [hi 32 B | lo 32 B | pad 16 B] (16X1: [hi 32 B | pad 16 B])
   static constexpr int BUF = CH * PLANE;                // [k16 s]
   static constexpr int Q = 4 * CH;                      // float4 per pixel per chunk
   static constexpr int ITEMS = P * Q;
@@ -81,7 +87,7 @@ struct CmGeo {
   static constexpr int STEPS = TAPS * CH;               // MFMA steps (tap, s) per chunk
   static constexpr int GS = (KS == 3) ? 3 : 2;          // steps per B group (one DMA batch, one barrier)
   static constexpr int NG = STEPS / GS;                 // B groups per chunk
-  static constexpr int GB1 = GS * CM_BSTEP;             // bytes per B group of ONE 64-channel tile (contiguous in the packed weights)
+  static constexpr int GB1 = GS * BSTEP;                // bytes per B group of ONE 64-channel tile (contiguous in the packed weights)
   static constexpr int GB = WN * GB1;                   // bytes per B group of the workgroup (WN tiles)
   // DMA pieces of a group (1 KiB = 64 lanes x 16 B each): N4 per wave, and the first REM waves one more (12 KiB over 8 waves: 2 | 1.
   // Measured against equal counts with 256-byte pieces for the remainder - 1 KiB + 2 x 256 B per wave - the fewer instructions win by 2 %
@@ -159,7 +165,8 @@ __device__ __forceinline__ void cm_gn_to_lds(const mud_conv_args& a, int b, int 
 // touches only instructions that PRODUCE fp16 / fp8 values, and the kernels have no others.
 __device__ __forceinline__ void cm_saturating_converters() { asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 1"); }
 
-template <int PRO, bool X8>
+// H1 (MUD_PREC_16X1): the prologue in fp32 as always, then ONE rounding to fp16 (RNE, saturating at +-65504): no lo piece, no e4m3 image.
+template <int PRO, bool X8, bool H1 = false>
 __device__ __forceinline__ void cm_stage4(const f32x4& rw, const f32x4& sc, const f32x4& sh, float keep, h16x4& hi, h16x4& lo, int& a8, int& al8) {
   f32x4 v, l;
 #pragma unroll
@@ -174,6 +181,7 @@ __device__ __forceinline__ void cm_stage4(const f32x4& rw, const f32x4& sc, cons
     v[e] = x * keep;                           // zero padding stays zero (the fp16 pieces saturate in the converter: cm_saturating_converters)
   }
   hi = __builtin_convertvector(v, h16x4);      // (2 x v_cvt_pk_f16_f32: a conversion, not packed arithmetic)
+  if constexpr (H1) return;
 #pragma unroll
   for (int e = 0; e < 4; ++e) l[e] = v[e] - (float)hi[e];
   if constexpr (X8) {
@@ -214,9 +222,11 @@ struct CmFin {
 template <int KS, int MT, int WM, int WN, int PRO, bool DUAL = false, int PREC = MUD_PREC_16X3>
 __global__ __launch_bounds__(64 * WM * WN, (MT == 1 && WM * WN == 8) ? 4 : 2) void k_conv_mfma(mud_conv_args a, int tiles_x, int tiles_per_img, int ntiles, int k16s,
                                                                 unsigned nblocks, int nsplit, int64_t split_stride, CmFin fin) {
-  using G = CmGeo<KS, MT, WM, WN, DUAL>;
+  using G = CmGeo<KS, MT, WM, WN, DUAL, PREC>;
   constexpr bool X8 = PREC == MUD_PREC_FP8X;           // fp16 hi.hi + e4m3 cross terms (3x3 only)
+  constexpr bool H1 = G::H1;                            // one pass: fp16 hi.hi only (3x3 only)
   static_assert(!X8 || KS == 3, "the fp8 cross-term plan is built for the 3x3 kernel");
+  static_assert(!H1 || KS == 3, "the single-pass fp16 plan is built for the 3x3 kernel");
   using HV4 = h16x4;
   using HV8 = h16x8;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -247,7 +257,7 @@ __global__ __launch_bounds__(64 * WM * WN, (MT == 1 && WM * WN == 8) ? 4 : 2) vo
     flat0 = (int64_t)tile * G::P;
   }
   const float* xb = a.x + (int64_t)b * HW * a.ldx;
-  const int64_t tile_bytes = (int64_t)k16s * (G::TAPS * CM_BSTEP);          // packed bytes of one 64-channel tile
+  const int64_t tile_bytes = (int64_t)k16s * (G::TAPS * G::BSTEP);          // packed bytes of one 64-channel tile
   const char* wb = (const char*)a.w + (int64_t)b * a.w_bstride + (int64_t)nt * WN * tile_bytes;
   const float* psc = a.pro_scale + (int64_t)b * a.pro_ld;
   const float* psh = a.pro_shift + (int64_t)b * a.pro_ld;
@@ -287,7 +297,7 @@ __global__ __launch_bounds__(64 * WM * WN, (MT == 1 && WM * WN == 8) ? 4 : 2) vo
     }
     goff[j] = valid ? (int)g : 0;
     vmask |= (valid ? 1u : 0u) << j;
-    loff[j] = (q >> 2) * G::PLANE + p * CM_PIX + (q & 3) * 8;
+    loff[j] = (q >> 2) * G::PLANE + p * G::PIX + (q & 3) * 8;
   }
 
   f32x4 raw[G::NLOAD];
@@ -341,12 +351,12 @@ __global__ __launch_bounds__(64 * WM * WN, (MT == 1 && WM * WN == 8) ? 4 : 2) vo
       const float keep = (cvalid && ((vmask >> j) & 1u)) ? 1.0f : 0.0f;   // zero padding stays zero
       HV4 hi, lo;
       int a8 = 0, al8 = 0;
-      cm_stage4<PRO, X8>(raw[j], psc_r, psh_r, keep, hi, lo, a8, al8);
+      cm_stage4<PRO, X8, H1>(raw[j], psc_r, psh_r, keep, hi, lo, a8, al8);
       *(HV4*)(buf + loff[j]) = hi;
       if constexpr (X8) {                       // (loff holds record + 8 q)
         *(int*)(buf + loff[j] + 32 - q * 4) = a8;          // record + 32 + 4 q
         *(int*)(buf + loff[j] + 48 - q * 4) = al8;         // record + 48 + 4 q
-      } else {
+      } else if constexpr (!H1) {
         *(HV4*)(buf + loff[j] + 32) = lo;
       }
       if (DUAL) {                               // the RAW value of the tile's centre pixels: A operand of the 1x1 skip conv (always 16-bit x 3)
@@ -400,7 +410,7 @@ __global__ __launch_bounds__(64 * WM * WN, (MT == 1 && WM * WN == 8) ? 4 : 2) vo
     }
   };
 
-  const int lane_a = ((KS == 3) ? (wm * MT * G::PW + r) : (wm * MT * 32 + r)) * CM_PIX + hh * 16;
+  const int lane_a = ((KS == 3) ? (wm * MT * G::PW + r) : (wm * MT * 32 + r)) * G::PIX + hh * 16;
   // fp8 cross terms: K = 64 = (tap 0, tap 1 | tap 2, zero) x 16 channels of a 3-tap group; lane half hh owns K [32 hh, 32 hh + 32)
   // (operand map checked by scripts/mfma_f8_layout.hip).  Every address is a per-lane base with the lane-half dependence folded in
   // + a compile-time offset, like the rest of the loop's LDS reads.
@@ -534,16 +544,16 @@ __global__ __launch_bounds__(64 * WM * WN, (MT == 1 && WM * WN == 8) ? 4 : 2) vo
           HV8 bh[2], bl[2];
 #pragma unroll
           for (int n = 0; n < 2; ++n) {
-            bh[n] = *(const HV8*)(bcur + sg * CM_BSTEP + n * 1024 + lane_b);
-            if constexpr (!X8) bl[n] = *(const HV8*)(bcur + sg * CM_BSTEP + CM_BPLANE + n * 1024 + lane_b);
+            bh[n] = *(const HV8*)(bcur + sg * G::BSTEP + n * 1024 + lane_b);
+            if constexpr (!X8 && !H1) bl[n] = *(const HV8*)(bcur + sg * G::BSTEP + CM_BPLANE + n * 1024 + lane_b);
           }
 #pragma unroll
           for (int m = 0; m < MT; ++m) {
             // lane base (wave row, column r, k half hh) + compile-time (m, tap, s) offset
-            const int off = s * G::PLANE + ((KS == 3) ? ((m + dy) * G::PW + dx) : (m * 32)) * CM_PIX;
+            const int off = s * G::PLANE + ((KS == 3) ? ((m + dy) * G::PW + dx) : (m * 32)) * G::PIX;
             const HV8 ah = *(const HV8*)(cur + lane_a + off);
-            if constexpr (X8) {
-              // hi.hi in fp16; the cross terms follow the group's last tap
+            if constexpr (X8 || H1) {
+              // hi.hi in fp16; under X8 the cross terms follow the group's last tap, under H1 that is all
               acc[m][0] = mud_mfma16(ah, bh[0], acc[m][0]);
               acc[m][1] = mud_mfma16(ah, bh[1], acc[m][1]);
             } else {
@@ -606,7 +616,12 @@ __global__ __launch_bounds__(64 * WM * WN, (MT == 1 && WM * WN == 8) ? 4 : 2) vo
         // chunk k+1's LDS image is written slot by slot behind the MFMAs of steps GS.. (its raw loads had group 0 to land),
         // so the conversion VALU work interleaves with matrix work instead of forming one long MFMA-free stretch
         if (more && G::NG > 1 && st >= G::GS) {
-          if (st == G::GS) {                    // (CNT) only this group's DMA is younger: N4 pieces, one more in the first REM waves
+          // (CNT) only this group's DMA is younger: N4 pieces, one more in the first REM waves.  The counts follow the group size:
+          // 16x3 / fp8x 24 KiB groups on 8 waves (8X2) 3 | 0, 12 KiB on 8 waves (16X1, 8X1R) 1 | 4, on 4 waves (MT2, MT1) 3 | 0;
+          // 16X1's hi-only groups are half that: 12 KiB on 8 waves 1 | 4, 6 KiB on 8 waves 0 | 6 (waves 6, 7 move nothing and
+          // wait for vmcnt(0)), 6 KiB on 4 waves 1 | 2.  The assertion ties N4 | REM to the group that dma_b moves.
+          static_assert(G::N4 * WM * WN + G::REM == G::GB / 1024 && G::REM < WM * WN, "DMA pieces per wave and group");
+          if (st == G::GS) {
             if constexpr (G::REM > 0) {
               if (__builtin_amdgcn_readfirstlane(wave) < G::REM) CM_RAW_WAIT(G::N4 + 1);
               else CM_RAW_WAIT(G::N4);
@@ -1217,9 +1232,16 @@ __global__ __launch_bounds__(256) void k_pack_weights(const float* __restrict__ 
       if (j < 4) v0[j] = v;
       else v1[j - 4] = v;
     }
-    char* step = dst + (int64_t)b * dst_bstride + (((int64_t)nt * k16s + kc) * taps + tap) * CM_BSTEP;
+    const int64_t bstep = prec == MUD_PREC_16X1 ? CM_BPLANE : CM_BSTEP;     // 16X1: hi-only steps
+    char* step = dst + (int64_t)b * dst_bstride + (((int64_t)nt * k16s + kc) * taps + tap) * bstep;
     char* base = step + co_l * 32 + ((h2 ^ ((co_l >> 3) & 1)) << 4);   // 16-B halves swapped on rows with bit 3 set: the image is copied verbatim to LDS
-    if (prec == MUD_PREC_FP8X) {
+    if (prec == MUD_PREC_16X1) {
+      h16x4 h0, h1, l0, l1;
+      mud_split4(v0, h0, l0);                  // (hi = the saturating RNE fp16 of w; lo unused)
+      mud_split4(v1, h1, l1);
+      *(h16x4*)base = h0;
+      *(h16x4*)(base + 8) = h1;
+    } else if (prec == MUD_PREC_FP8X) {
       h16x4 h0, h1, l0, l1;
       mud_split4(v0, h0, l0);
       mud_split4(v1, h1, l1);
@@ -1249,19 +1271,26 @@ extern "C" int64_t mud_packed_weight_bytes(int ks, int Cin, int Cout) {
   return mud_cdiv(Cout, CM_BN) * mud_cdiv(Cin, 16) * (int64_t)ks * ks * CM_BSTEP + 2 * CM_BSTEP;   // + slack: the last DMA group of a 1x1 operand with an odd number of 16-channel chunks reads one step past the end
 }
 
+extern "C" int64_t mud_packed_weight_bytes_prec(int ks, int Cin, int Cout, int prec) {
+  if (prec == MUD_PREC_16X3 || (prec == MUD_PREC_FP8X && ks == 3)) return mud_packed_weight_bytes(ks, Cin, Cout);
+  if (prec != MUD_PREC_16X1 || ks != 3 || Cin <= 0 || Cout <= 0) return -1;
+  return mud_cdiv(Cout, CM_BN) * mud_cdiv(Cin, 16) * (int64_t)9 * CM_BPLANE + 2 * CM_BPLANE;      // hi-only steps (+ the same two steps of slack)
+}
+
 extern "C" int mud_pack_weights_prec(const float* src, int64_t s_tap, int64_t s_ci, int64_t s_co, int64_t src_bstride, int ks,
                                      int Cin, int Cout, int nbatch, int prec, int w_exp, void* dst, void* stream) {
   MUD_REQUIRE(src && dst, "mud_pack_weights: null pointer");
   MUD_REQUIRE((ks == 1 || ks == 3) && Cin > 0 && Cout > 0 && nbatch >= 1 && nbatch <= 65535, "mud_pack_weights: bad sizes");
   MUD_REQUIRE(mud_aligned16(dst), "mud_pack_weights: dst must be 16-byte aligned");
-  MUD_REQUIRE(prec == MUD_PREC_16X3 || (prec == MUD_PREC_FP8X && ks == 3 && w_exp >= -100 && w_exp <= 100),
-              "mud_pack_weights: prec must be MUD_PREC_16X3, or MUD_PREC_FP8X with ks == 3 and |w_exp| <= 100 (got prec=%d ks=%d w_exp=%d)", prec, ks, w_exp);
+  MUD_REQUIRE(prec == MUD_PREC_16X3 || (prec == MUD_PREC_FP8X && ks == 3 && w_exp >= -100 && w_exp <= 100) || (prec == MUD_PREC_16X1 && ks == 3),
+              "mud_pack_weights: prec must be MUD_PREC_16X3, MUD_PREC_FP8X with ks == 3 and |w_exp| <= 100, or MUD_PREC_16X1 with ks == 3 "
+              "(got prec=%d ks=%d w_exp=%d)", prec, ks, w_exp);
   const int k16s = (int)mud_cdiv(Cin, 16), ntiles = (int)mud_cdiv(Cout, CM_BN), taps = ks * ks;
   const int64_t units = (int64_t)ntiles * k16s * taps * 128;
   int64_t blocks = mud_cdiv(units, 256);
   if (blocks > 256 * 16) blocks = 256 * 16;
   hipLaunchKernelGGL(k_pack_weights, dim3((int)blocks, nbatch), dim3(256), 0, (hipStream_t)stream, src, s_tap, s_ci, s_co,
-                     src_bstride, taps, Cin, Cout, k16s, units, (char*)dst, mud_packed_weight_bytes(ks, Cin, Cout), prec, w_exp);
+                     src_bstride, taps, Cin, Cout, k16s, units, (char*)dst, mud_packed_weight_bytes_prec(ks, Cin, Cout, prec), prec, w_exp);
   MUD_CHECK_LAUNCH("mud_pack_weights");
   return MUD_OK;
 }
@@ -1359,7 +1388,7 @@ static int cm_splits(int64_t blocks, int nchunks) {
 
 template <int KS, int MT, int WM, int WN, int PRO, bool DUAL = false, int PREC = MUD_PREC_16X3>
 static int cm_launch_pro(const mud_conv_args& a, hipStream_t s) {
-  using G = typename std::conditional<KS == 3, CmGeo<KS, MT, WM, WN, DUAL>, CmGeoRegB<KS, MT>>::type;
+  using G = typename std::conditional<KS == 3, CmGeo<KS, MT, WM, WN, DUAL, PREC>, CmGeoRegB<KS, MT>>::type;
   const void* kfn;
   if constexpr (KS == 3) kfn = (const void*)k_conv_mfma<KS, MT, WM, WN, PRO, DUAL, PREC>;      // only the variant that is launched is instantiated
   else kfn = (const void*)k_conv_mfma_regb<KS, MT, PRO>;
@@ -1429,13 +1458,13 @@ static int cm_launch_pro(const mud_conv_args& a, hipStream_t s) {
   return MUD_OK;
 }
 
-template <int KS, int MT, int WM = 4, int WN = 1>
+template <int KS, int MT, int WM = 4, int WN = 1, int PREC = MUD_PREC_16X3>
 static int cm_launch(const mud_conv_args& a, hipStream_t s) {
   switch (a.pro_mode) {
-    case MUD_PRO_NONE: return cm_launch_pro<KS, MT, WM, WN, MUD_PRO_NONE>(a, s);
-    case MUD_PRO_AFFINE: return cm_launch_pro<KS, MT, WM, WN, MUD_PRO_AFFINE>(a, s);
-    case MUD_PRO_LRELU: return cm_launch_pro<KS, MT, WM, WN, MUD_PRO_LRELU>(a, s);
-    default: return cm_launch_pro<KS, MT, WM, WN, MUD_PRO_AFFINE_SILU>(a, s);
+    case MUD_PRO_NONE: return cm_launch_pro<KS, MT, WM, WN, MUD_PRO_NONE, false, PREC>(a, s);
+    case MUD_PRO_AFFINE: return cm_launch_pro<KS, MT, WM, WN, MUD_PRO_AFFINE, false, PREC>(a, s);
+    case MUD_PRO_LRELU: return cm_launch_pro<KS, MT, WM, WN, MUD_PRO_LRELU, false, PREC>(a, s);
+    default: return cm_launch_pro<KS, MT, WM, WN, MUD_PRO_AFFINE_SILU, false, PREC>(a, s);
   }
 }
 
@@ -1499,9 +1528,13 @@ static bool cm_fp8x_built(const mud_conv_args& a) {
   const int v = cm_variant3(a, nullptr);
   return v == CMV_8X2 || v == CMV_16X1 || v == CMV_8X1R;
 }
+// MUD_PREC_16X1 is built for every 3x3 launch: every tile, every prologue, the fused skip conv (AdaGN + SiLU prologue, as always),
+// split-K and sub2.  No 1x1 form.
 extern "C" int mud_conv2d_mfma_prec_supported(const mud_conv_args* ap, int prec) {
   if (!ap || ap->B <= 0 || ap->H <= 0 || ap->W <= 0 || ap->Cin <= 0 || ap->Cout <= 0) return 0;
   if (prec == MUD_PREC_16X3) return ap->ks == 1 || ap->ks == 3;
+  if (prec == MUD_PREC_16X1)
+    return ap->ks == 3 && ap->pro_mode >= MUD_PRO_NONE && ap->pro_mode <= MUD_PRO_LRELU && (!ap->skip_w || ap->pro_mode == MUD_PRO_AFFINE_SILU);
   mud_conv_args a = *ap;
   a.prec = prec;                                 // (the tile choice looks at it)
   return prec == MUD_PREC_FP8X && cm_fp8x_built(a);
@@ -1545,7 +1578,8 @@ extern "C" int mud_conv2d_mfma(const mud_conv_args* ap, void* stream) {
                 mud_aligned16(a.skip_w) && mud_aligned16(a.skip_out) && mud_aligned16(a.out),
                 "mud_conv2d_mfma: fused skip conv needs Cin <= 512, Cout %% 4 == 0 and aligned float4 output rows (Cin=%d Cout=%d)", a.Cin, a.Cout);
   }
-  MUD_REQUIRE(a.prec == MUD_PREC_16X3 || a.prec == MUD_PREC_FP8X, "mud_conv2d_mfma: unknown arithmetic plan prec=%d", a.prec);
+  MUD_REQUIRE(a.prec == MUD_PREC_16X3 || a.prec == MUD_PREC_FP8X || a.prec == MUD_PREC_16X1, "mud_conv2d_mfma: unknown arithmetic plan prec=%d", a.prec);
+  MUD_REQUIRE(a.prec != MUD_PREC_16X1 || a.ks == 3, "mud_conv2d_mfma: MUD_PREC_16X1 is built for ks == 3 only (got ks=%d)", a.ks);
   MUD_REQUIRE(a.prec != MUD_PREC_FP8X || (cm_fp8x_built(a) && a.w_exp >= -100 && a.w_exp <= 100),
               "mud_conv2d_mfma: MUD_PREC_FP8X is not built for this launch (ask mud_conv2d_mfma_prec_supported first; the weights were packed for it and cannot be read by another plan)");
   if (a.B == 0) return MUD_OK;
@@ -1560,6 +1594,24 @@ extern "C" int mud_conv2d_mfma(const mud_conv_args* ap, void* stream) {
     if (a.skip_w) return x2 ? cm_launch_pro<3, 2, 4, 2, MUD_PRO_AFFINE_SILU, true, MUD_PREC_FP8X>(a, s) : cm_launch_pro<3, 2, 8, 1, MUD_PRO_AFFINE_SILU, true, MUD_PREC_FP8X>(a, s);
     if (a.pro_mode == MUD_PRO_NONE) return x2 ? cm_launch_pro<3, 2, 4, 2, MUD_PRO_NONE, false, MUD_PREC_FP8X>(a, s) : cm_launch_pro<3, 2, 8, 1, MUD_PRO_NONE, false, MUD_PREC_FP8X>(a, s);
     return x2 ? cm_launch_pro<3, 2, 4, 2, MUD_PRO_AFFINE_SILU, false, MUD_PREC_FP8X>(a, s) : cm_launch_pro<3, 2, 8, 1, MUD_PRO_AFFINE_SILU, false, MUD_PREC_FP8X>(a, s);
+  }
+  if (a.prec == MUD_PREC_16X1) {
+    // the single-pass plan on the same tile choice as 16x3 (cm_variant3; the fused skip conv: its three tiles)
+    constexpr int P1 = MUD_PREC_16X1;
+    if (a.skip_w) {
+      switch (cm_variant3(a, nullptr)) {
+        case CMV_8X2: return cm_launch_pro<3, 2, 4, 2, MUD_PRO_AFFINE_SILU, true, P1>(a, s);
+        case CMV_16X1: return cm_launch_pro<3, 2, 8, 1, MUD_PRO_AFFINE_SILU, true, P1>(a, s);
+        default: return cm_launch_pro<3, 1, 4, 1, MUD_PRO_AFFINE_SILU, true, P1>(a, s);
+      }
+    }
+    switch (cm_variant3(a, nullptr)) {
+      case CMV_8X2: return cm_launch<3, 2, 4, 2, P1>(a, s);
+      case CMV_16X1: return cm_launch<3, 2, 8, 1, P1>(a, s);
+      case CMV_MT2: return cm_launch<3, 2, 4, 1, P1>(a, s);
+      case CMV_8X1R: return cm_launch<3, 1, 8, 1, P1>(a, s);
+      default: return cm_launch<3, 1, 4, 1, P1>(a, s);
+    }
   }
   // tile height by problem size: big tiles (more MFMA work per weight byte) once they still fill the 256 CUs
   const int64_t ntiles = mud_cdiv(a.Cout, CM_BN);

@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _SHIPPED = os.path.join(_HERE, 'libmudiff_hip.so')
 _LIB_PATH = os.environ.get('MUDIFF_HIP_LIB', _SHIPPED)   # override: kernel experiments; refused unless MUDIFF_ALLOW_VARIANT=1 (see load())
 _lib = None
-PREC_16X3, PREC_FP8X = 0, 1
+PREC_16X3, PREC_FP8X, PREC_16X1 = 0, 1, 2
 
 ACT_NONE, ACT_SIGMOID, ACT_TANH, ACT_SILU, ACT_LRELU = 0, 1, 2, 3, 4
 PRO_NONE, PRO_AFFINE, PRO_AFFINE_SILU, PRO_LRELU = 0, 1, 2, 3
@@ -98,6 +98,7 @@ _SIGNATURES = {
     'mud_packed_weight_bytes': (_L, [_I, _I, _I]),
     'mud_pack_weights': (_I, [_P, _L, _L, _L, _L, _I, _I, _I, _I, _P, _P]),
     'mud_pack_weights_prec': (_I, [_P, _L, _L, _L, _L, _I, _I, _I, _I, _I, _I, _P, _P]),
+    'mud_packed_weight_bytes_prec': (_L, [_I, _I, _I, _I]),
     'mud_conv2d_mfma': (_I, [C.POINTER(ConvArgs), _P]),
     'mud_conv2d_mfma_prec_supported': (_I, [C.POINTER(ConvArgs), _I]),
     'mud_conv2d_mfma_splitk_bytes': (_L, [C.POINTER(ConvArgs)]),

@@ -311,6 +311,7 @@ def parse_args(argv=None):
     p = build_parser()
     args = p.parse_args(argv)
     check_lpips_flags(p, args)
+    check_prec_plan_flags(p, args)
     if args.lpips_weights is not None and not args.device_metrics:
         p.error('--lpips_weights needs --device_metrics (the host path scores PSNR / SSIM / MAE only)')
     if args.num_samples is not None:
@@ -329,13 +330,38 @@ def add_calibration_flags(p):
                         'it cannot carry back to fp16x3 (mudiff_hip.precision; result in <output>/prec_calibration.json)')
     from .precision import DEFAULT_THRESHOLD
     p.add_argument('--calibrate_threshold', type=float, default=DEFAULT_THRESHOLD, help='max-abs deviation from the fp16x3 plan --calibrate accepts')
+    from .ops import PREC_PLANS
+    p.add_argument('--prec_plan', choices=PREC_PLANS, default=None,
+                   help='arithmetic plan of the 3x3 convolutions while the sampler is captured (default: whatever MUD_PREC_PLAN says, '
+                        "normally 'auto').  'fp16' = one fp16 pass with fp32 accumulation, the arithmetic of the reference's autocast: "
+                        'faster, ~1-2e-2 per step from the fp32 reference - not for parity work (INTEGRATION.md)')
+
+
+def effective_prec_plan(args):
+    """--prec_plan if given, else the plan MUD_PREC_PLAN selected (ops.PREC_PLAN)."""
+    from . import ops
+    plan = getattr(args, 'prec_plan', None)
+    return ops.PREC_PLAN if plan is None else plan
+
+
+def check_prec_plan_flags(p, args):
+    if getattr(args, 'calibrate', False) and effective_prec_plan(args) == 'fp16':
+        p.error("--calibrate measures the fp8 cross-term plan against fp16x3 and means nothing under the 'fp16' plan "
+                '(from --prec_plan or MUD_PREC_PLAN)')
 
 
 def main(argv=None):
+    from . import ops
+    args = parse_args(argv)
+    plan = effective_prec_plan(args)
+    with ops.prec_plan(plan):                                    # active while the samplers are captured (ensembles included)
+        _main(args, plan)
+
+
+def _main(args, plan):
     import torch.distributed as dist
     from backbones.ncsnpp_generator_adagn_feat import NCSNpp, NCSNpp_adaptive
     from .distributed import broadcast_parameters
-    args = parse_args(argv)
     logging.basicConfig(level=logging.INFO, format='%(asctime)s | %(levelname)s | %(message)s')
     rank, world, local = (int(os.environ.get(k, d)) for k, d in (('RANK', 0), ('WORLD_SIZE', 1), ('LOCAL_RANK', 0)))
     torch.cuda.set_device(local)
@@ -384,7 +410,8 @@ def main(argv=None):
         logging.info('Average PSNR: %.4f dB  SSIM: %.4f  MAE: %.6f over %d slices (global range [%.4f, %.4f])%s', res['psnr'], res['ssim'],
                      res['mae'], res['count'], res['global_min'], res['global_max'],
                      ('  LPIPS: %.6f' % res['lpips'] if 'lpips' in res else '') +
-                     ('' if ens is None else '  ensemble: %d samples, mean std %.6f' % (args.num_samples, ens)))
+                     ('' if ens is None else '  ensemble: %d samples, mean std %.6f' % (args.num_samples, ens)) +
+                     ('' if plan == 'auto' else '  prec_plan: ' + plan))      # (the default plan leaves the line as it was)
     if world > 1:
         dist.destroy_process_group()
 

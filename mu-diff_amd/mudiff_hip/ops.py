@@ -2,6 +2,7 @@
 current stream.  Everything here is GPU-only (see mudiff_hip.__init__)."""
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import math
 import os
@@ -9,8 +10,8 @@ import os
 import numpy as np
 import torch
 
-from . import (ACT_LRELU, ACT_NONE, ACT_SIGMOID, ACT_SILU, ACT_TANH, PREC_16X3, PREC_FP8X, PRO_AFFINE, PRO_AFFINE_SILU, PRO_LRELU, PRO_NONE,  # noqa: F401
-               ConvArgs, MudiffHipError, check, load, ptr, require_gpu)
+from . import (ACT_LRELU, ACT_NONE, ACT_SIGMOID, ACT_SILU, ACT_TANH, PREC_16X1, PREC_16X3, PREC_FP8X, PRO_AFFINE, PRO_AFFINE_SILU, PRO_LRELU,  # noqa: F401
+               PRO_NONE, ConvArgs, MudiffHipError, check, load, ptr, require_gpu)
 
 
 # MUD_DETERMINISTIC=1: bit-stable outputs run to run.  The only order-dependent arithmetic of the path is the fp64 atomic
@@ -415,7 +416,9 @@ def pack_weights(src, s_tap, s_ci, s_co, ks, Cin, Cout, nbatch=1, src_bstride=0,
     """-> uint8 tensor [nbatch, packed bytes] in the MFMA kernel's B-operand layout (for the arithmetic plan `prec`)."""
     lib = load()
     require_gpu(src)
-    nbytes = lib.mud_packed_weight_bytes(ks, Cin, Cout)
+    nbytes = lib.mud_packed_weight_bytes_prec(ks, Cin, Cout, prec)
+    if nbytes < 0:
+        raise MudiffHipError(f'pack_weights: plan {prec} has no packed form for ks={ks}')
     dst = torch.empty(nbatch, nbytes, device=src.device, dtype=torch.uint8)
     _launch('pack_weights', src.device, lib.mud_pack_weights_prec, C.c_void_p(src.data_ptr() + 4 * src_offset), s_tap, s_ci, s_co, src_bstride, ks, Cin, Cout,
             nbatch, prec, w_exp, ptr(dst), STREAM)
@@ -451,7 +454,9 @@ def direct_weight(w_oihw):
 
 # ---- arithmetic plan per 3x3 launch (mud_conv_args.prec).  MUD_PREC_PLAN: 'auto' (default) = the fp16 + e4m3-cross-term plan
 # (MUD_PREC_FP8X) for every launch the library has it for (fp8x_pays), fp16 x 3 elsewhere (small grids, 1x1, the exact head / tail
-# kernels); 'off' = every launch fp16 x 3; 'all' = wherever the library has the plan, whatever fp8x_pays says.
+# kernels); 'off' = every launch fp16 x 3; 'all' = wherever the library has the plan, whatever fp8x_pays says; 'fp16' = the
+# single-pass plan (MUD_PREC_16X1: fp16 operands, fp32 accumulation - autocast's arithmetic, NOT the parity plan) on every 3x3
+# launch of the generators, fp16 x 3 elsewhere (1x1 GEMMs, attention, the critic, the exact direct kernels).
 PREC_PLAN = os.environ.get('MUD_PREC_PLAN', 'auto')
 
 
@@ -463,12 +468,12 @@ def fp8x_pays(B, H, W, cin, cout):
     return True
 
 
-PREC_PLANS = ('off', 'auto', 'all')
+PREC_PLANS = ('off', 'auto', 'all', 'fp16')
 
 
 class prec_plan:
-    """Context: PREC_PLAN = `name` ('off' | 'auto' | 'all') for the launches planned inside (eager calls; a graph captured inside
-    keeps the plans it was captured with), restored on exit."""
+    """Context: PREC_PLAN = `name` ('off' | 'auto' | 'all' | 'fp16') for the launches planned inside (eager calls; a graph captured
+    inside keeps the plans it was captured with), restored on exit."""
 
     def __init__(self, name):
         if name not in PREC_PLANS:
@@ -499,17 +504,33 @@ def choose_prec(x: View, cout, pro_mode, *, skip=False, sub2=False, w_bstride=0)
     """The plan a 3x3 mud_conv2d_mfma launch of this shape runs with."""
     if PREC_PLAN == 'off' or w_bstride or x.C % 4:
         return PREC_16X3
+    if PREC_PLAN == 'fp16':
+        return PREC_16X1 if conv_prec_supported(x, cout, pro_mode, PREC_16X1, skip=skip, sub2=sub2) else PREC_16X3
     if PREC_PLAN != 'all' and not fp8x_pays(x.B, x.H, x.W, x.C, cout):
         return PREC_16X3
     return PREC_FP8X if conv_prec_supported(x, cout, pro_mode, PREC_FP8X, skip=skip, sub2=sub2) else PREC_16X3
 
 
+# One entry of a launch record (precision.launch_record): layer name (None where no ConvParam names the launch), kernel size,
+# matrix-core kernel or not, arithmetic plan, (B, H, W, Cin, Cout), sub2 form, fused skip conv, prologue mode.
+Launch = collections.namedtuple('Launch', 'layer ks mfma prec shape sub2 skip pro')
+
+
+RECORD = None         # the active precision.launch_record() list, or None: every ops.conv call appends a Launch to it
+
+
 def conv(x: View, w, ks, Cout, *, mfma, stride=1, pad=None, pro=None, bias=None, bias2=None, res: View = None,
          out_scale=1.0, act=ACT_NONE, out: View = None, w_bstride=0, arena=None, sub2=False, emul: View = None, gate=None, emul_cout=0,
-         skip=None, prec=PREC_16X3, w_exp=0):
+         skip=None, prec=PREC_16X3, w_exp=0, layer=None):
     """One fused convolution launch.  pro = (scale [B,Cin], shift [B,Cin], mode).
     skip = (packed 1x1 weights, bias or None, out View): the same launch also writes the 1x1 convolution of the RAW input
-    (the residual block's Conv_2) - see fused_skip_ok().  prec / w_exp: the arithmetic plan `w` was packed for."""
+    (the residual block's Conv_2) - see fused_skip_ok().  prec / w_exp: the arithmetic plan `w` was packed for.
+    layer: the launch's layer name in a launch record (precision.launch_record)."""
+    if RECORD is not None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('precision.launch_record() is eager only: the launch is being captured into a graph')
+        RECORD.append(Launch(layer, ks, bool(mfma), prec, (x.B, x.H, x.W, x.C, Cout), bool(sub2), skip is not None,
+                             PRO_NONE if pro is None else pro[2]))
     lib = load()
     pad = ks // 2 if pad is None else pad
     Ho = (x.H + 2 * pad - ks) // stride + 1
@@ -577,7 +598,7 @@ def conv(x: View, w, ks, Cout, *, mfma, stride=1, pad=None, pro=None, bias=None,
             keep = (keep, torch.empty(nws, device=x.device, dtype=torch.uint8))
             a.splitk_ws, a.splitk_ws_bytes = ptr(keep[1]), nws
     fn = lib.mud_conv2d_mfma if mfma else lib.mud_conv2d_direct
-    name = (f'conv_mfma_k{ks}' if mfma else f'conv_direct_k{ks}') + ('_fp8x' if prec == PREC_FP8X else '')
+    name = (f'conv_mfma_k{ks}' if mfma else f'conv_direct_k{ks}') + {PREC_FP8X: '_fp8x', PREC_16X1: '_fp16'}.get(prec, '')
     flops = 2.0 * x.B * Ho * Wo * Cout * x.C * ks * ks + skip_flops     # algorithmic (sub2 issues 4x this)
     nbytes = 4.0 * (x.npix * x.C + out.npix * Cout * ((2 if res is not None else 1) + (1 if skip is not None else 0))) + (w.numel() * w.element_size() if w_bstride == 0 else x.B * w_bstride)
     _launch(name, x.device, fn, C.byref(a), STREAM, flops=flops, nbytes=nbytes)

@@ -95,6 +95,27 @@ def record(conv, x, pro):
     CENSUS.add(conv, x, pro)
 
 
+class launch_record:
+    """Context: collects one ops.Launch (layer name, plan, kernel size, kernel, shape, ...) per convolution launch issued inside
+    (`.launches`; `.plans()` = [(layer, plan)]).  Eager only, like census(): refuses to start under graph capture, and a launch
+    captured while it is active raises."""
+
+    def __enter__(self):
+        if _capturing():
+            raise RuntimeError('precision.launch_record() is eager only (the current stream is capturing a graph)')
+        if ops.RECORD is not None:
+            raise RuntimeError('precision.launch_record() does not nest')
+        self.launches = ops.RECORD = []
+        return self
+
+    def __exit__(self, *exc):
+        ops.RECORD = None
+        return False
+
+    def plans(self):
+        return [(r.layer, r.prec) for r in self.launches]
+
+
 # ---------------------------------------------------------------------------------------------------
 def conv_layer_names(g):
     """Names of the layers of generator `g` that can run MUD_PREC_FP8X (3x3 convs on the matrix-core kernel), from module
@@ -219,6 +240,9 @@ def calibrate_plan(coefficients, g1, cond1, g2, cond2, cond3, n_time, opt, x_ini
     its B, H, W - and, unless apply=False, install its per-layer overrides on g1 / g2.  Draws not injected (x_init [B,1,H,W],
     zs / noises per step) come from a private torch.Generator seeded with `seed`.  `group` (torch.distributed, > 1 rank): every
     rank calibrates its own batch; deviations and census counters are MAX-reduced, so every rank installs the same overrides."""
+    if ops.PREC_PLAN == 'fp16':
+        raise ValueError("calibrate_plan: the guard measures the fp8 cross-term plan against fp16 x 3 and means nothing under the "
+                         "single-pass 'fp16' plan (MUD_PREC_PLAN / ops.prec_plan)")
     from . import sampling as S
     t0 = time.perf_counter()
     B, _, H, W = cond1.shape

@@ -271,7 +271,15 @@ def predict_slices(args, gen1, gen2, cond_stacks, device, batch_size=32, x_inits
 
 def predict_volume(args):
     """Reference :209-300, same flags, same output file `predicted_<target>.nii.gz`.  With --num_samples the ensemble's mean goes
-    there and its std next to it; the return value is then the pair of paths."""
+    there and its std next to it; the return value is then the pair of paths.  --prec_plan holds for the whole prediction."""
+    from . import ops
+    from .driver import effective_prec_plan
+    plan = effective_prec_plan(args)
+    with ops.prec_plan(plan):
+        return _predict_volume(args, plan)
+
+
+def _predict_volume(args, plan):
     from backbones.ncsnpp_generator_adagn_feat import NCSNpp, NCSNpp_adaptive
     torch.manual_seed(args.seed)
     torch.cuda.set_device(args.gpu_chose)
@@ -320,7 +328,7 @@ def predict_volume(args):
     os.makedirs(args.output_dir, exist_ok=True)
     out_path = os.path.join(args.output_dir, f'predicted_{args.target_modality.lower()}.nii.gz')
     write_nifti(out_path, vol_pred, aff, hdr)
-    print(f'[done] saved: {out_path} | shape={tuple(vol_pred.shape)} | slices={s0}..{s1}')
+    print(f'[done] saved: {out_path} | shape={tuple(vol_pred.shape)} | slices={s0}..{s1}' + ('' if plan == 'auto' else f' | prec_plan={plan}'))
     return out_path
 
 
@@ -329,6 +337,7 @@ def _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref):
     the std of the [0,1]-mapped samples, resized back and re-assembled like the single prediction, go to predicted_<t>.nii.gz and
     predicted_<t>_std.nii.gz.  -> (mean path, std path)."""
     from . import ensemble, ops
+    from .driver import effective_prec_plan
     shp, aff, hdr, s0, s1 = ref
     size = int(args.image_size)
     conds = upload_conds(stacks, size, device)
@@ -343,7 +352,8 @@ def _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref):
         path = os.path.join(args.output_dir, f'predicted_{args.target_modality.lower()}{suffix}.nii.gz')
         write_nifti(path, vol, aff, hdr)
         paths.append(path)
-    print(f'[done] saved: {paths[0]} and {paths[1]} | shape={tuple(shp)} | slices={s0}..{s1} | {args.num_samples} samples per slice')
+    print(f'[done] saved: {paths[0]} and {paths[1]} | shape={tuple(shp)} | slices={s0}..{s1} | {args.num_samples} samples per slice' +
+          ('' if effective_prec_plan(args) == 'auto' else f' | prec_plan={effective_prec_plan(args)}'))      # (the default plan: the line as it was)
     return tuple(paths)
 
 
@@ -395,9 +405,10 @@ def build_argparser(argv=None):
     p.add_argument('--num_samples', type=int, default=None,
                    help='sample every slice N >= 2 times with draws keyed by --seed (mudiff_hip.ensemble): predicted_<t>.nii.gz is then '
                         'the mean of the [0,1]-mapped samples, and predicted_<t>_std.nii.gz their per-voxel standard deviation')
-    from .driver import add_calibration_flags
-    add_calibration_flags(p)
+    from .driver import add_calibration_flags, check_prec_plan_flags
+    add_calibration_flags(p)                # (also --prec_plan)
     args = p.parse_args(argv)
+    check_prec_plan_flags(p, args)
     if args.num_samples is not None and args.num_samples < 2:
         p.error(f'--num_samples must be >= 2 (got {args.num_samples})')
     if args.num_samples is not None and not 0 <= args.seed < 1 << 64:
