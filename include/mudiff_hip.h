@@ -287,6 +287,33 @@ int64_t mud_slice_metrics_ws_bytes(int n, int H, int W);
 int mud_slice_metrics_u8(const uint8_t* pred, const uint8_t* gt, int n, int H, int W, int64_t* sse, int64_t* sae, double* ssim_sum,
                          void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- whole-volume scoring (mudiff_hip.volume_metrics; the volume pipeline's --gt_volume).  It extends the definitions of
+ *      tools/metric_calc.py:40-47 (PSNR, SSIM with skimage defaults, MAE) to fp32 volumes in [0, 1]: a 7x7x7 uniform window, sample
+ *      covariance (343/342), K1 = 0.01, K2 = 0.03, data_range 1, masked means over regions.
+ *
+ * pred, gt (fp32), region (uint8) and the optional std (fp32, may be NULL) are [Z, X, Y] with planes contiguous, Z, X, Y >= 7.  Voxel v
+ * belongs to region k (0 <= k < nreg <= MUD_VM_MAX_REGIONS) when bit k of region[v] is set.  sums[(z * nreg + k) * MUD_VM_NQ + q] are
+ * fp64 sums over the voxels of plane z in region k, with d = pred - gt and e = |d| taken in fp64:
+ *   MUD_VM_N       the voxel count             MUD_VM_SSE  sum d^2        MUD_VM_SAE      sum e
+ *   MUD_VM_N_INT   the interior voxel count    MUD_VM_SSIM sum of SSIM over the interior voxels (whole window inside the volume)
+ *   MUD_VM_SS      sum std                     MUD_VM_SS2  sum std^2      MUD_VM_SSE_STD  sum std * e      (zero without std)
+ * Window sums are fp64 in a fixed order per voxel and the per-plane sums have a fixed order: bit-identical run to run; the SSIM
+ * expression is not contracted, so pred == gt gives SSIM exactly 1.  ws: mud_volume_metrics_ws_bytes(Z, X, Y, nreg) bytes (-1 for bad
+ * sizes), 8-byte aligned. */
+#define MUD_VM_MAX_REGIONS 8
+#define MUD_VM_NQ 8
+#define MUD_VM_N 0
+#define MUD_VM_SSE 1
+#define MUD_VM_SAE 2
+#define MUD_VM_N_INT 3
+#define MUD_VM_SSIM 4
+#define MUD_VM_SS 5
+#define MUD_VM_SS2 6
+#define MUD_VM_SSE_STD 7
+int64_t mud_volume_metrics_ws_bytes(int Z, int X, int Y, int nreg);
+int mud_volume_metrics(const float* pred, const float* gt, const uint8_t* region, const float* std, int Z, int X, int Y, int nreg,
+                       double* sums, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- LPIPS, AlexNet backbone (lpips v0.1, net='alex', eval; tools/metric_calc.py:50-51) of uint8 grayscale pairs (mudiff_hip.lpips_net).
  * Weights are packed once into the kernels' layout: mud_lpips_packed_bytes() bytes, 16-byte aligned, written by mud_lpips_pack from
  * device fp32 tensors in torch layout: table[768] = the scaled input of level v in channel c at [c*256 + v] (fp32, built on the host),

@@ -120,6 +120,8 @@ _SIGNATURES = {
     'mud_quantize_u8': (_I, [_P, _L, _F, _F, _P, _P]),
     'mud_slice_metrics_ws_bytes': (_L, [_I, _I, _I]),
     'mud_slice_metrics_u8': (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _L, _P]),
+    'mud_volume_metrics_ws_bytes': (_L, [_I, _I, _I, _I]),
+    'mud_volume_metrics': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _L, _P]),
     'mud_lpips_packed_bytes': (_L, []),
     'mud_lpips_pack': (_I, [_P, _P, _P, _P, _P, _P]),
     'mud_lpips_ws_bytes': (_L, [_I, _I, _I]),

@@ -786,6 +786,39 @@ def slice_metrics_u8(pred, gt):
     return sse, sae, ssim_sum
 
 
+# columns of volume_metrics' sums (include/mudiff_hip.h: MUD_VM_*)
+VM_N, VM_SSE, VM_SAE, VM_N_INT, VM_SSIM, VM_SS, VM_SS2, VM_SSE_STD = range(8)
+VM_NQ, VM_MAX_REGIONS = 8, 8
+
+
+def volume_metrics(pred, gt, region, std=None, nreg=VM_MAX_REGIONS):
+    """Per-plane, per-region sums of a [Z, X, Y] volume pair (Z, X, Y >= 7; planes contiguous): pred, gt (and std) fp32, region uint8
+    (voxel v is in region k < nreg when bit k of region[v] is set) -> device fp64 [Z, nreg, VM_NQ]: voxel count, sum d^2, sum |d|,
+    interior voxel count, sum of the 7x7x7 SSIM over the interior (skimage defaults, data_range 1), and with `std` sum s, sum s^2,
+    sum s*|d| (zeros without), d = pred - gt in fp64.  Bit-identical run to run.  No synchronisation."""
+    require_gpu(pred, gt, region, std)
+    ts = [pred, gt] + ([] if std is None else [std])
+    if any(t.dtype != torch.float32 for t in ts) or region.dtype != torch.uint8:
+        raise MudiffHipError(f'volume_metrics: need fp32 pred / gt{" / std" if std is not None else ""} and a uint8 region '
+                             f'(got {", ".join(str(t.dtype) for t in ts)}, {region.dtype})')
+    if pred.dim() != 3 or any(t.shape != pred.shape for t in ts + [region]):
+        raise MudiffHipError(f'volume_metrics: need [Z, X, Y] tensors of one shape (got {", ".join(str(tuple(t.shape)) for t in ts + [region])})')
+    Z, X, Y = pred.shape
+    if Z < 7 or X < 7 or Y < 7:
+        raise MudiffHipError(f'volume_metrics: volumes must be at least 7x7x7 (the SSIM window), got {Z}x{X}x{Y}')
+    if not 1 <= int(nreg) <= VM_MAX_REGIONS:
+        raise MudiffHipError(f'volume_metrics: nreg must be in [1, {VM_MAX_REGIONS}] (got {nreg})')
+    nreg = int(nreg)
+    pin, gin, rin = pred.contiguous(), gt.contiguous(), region.contiguous()
+    sin = None if std is None else std.contiguous()
+    sums = torch.empty(Z, nreg, VM_NQ, device=pred.device, dtype=torch.float64)
+    nbytes = load().mud_volume_metrics_ws_bytes(Z, X, Y, nreg)
+    ws = torch.empty(nbytes, device=pred.device, dtype=torch.uint8)
+    _launch('volume_metrics', pred.device, load().mud_volume_metrics, ptr(pin), ptr(gin), ptr(rin), ptr(sin), Z, X, Y, nreg, ptr(sums),
+            ptr(ws), nbytes, STREAM, nbytes=float(pin.numel()) * (9 + (0 if sin is None else 4)))
+    return sums
+
+
 LPIPS_WS_CAP = 512 << 20      # bytes of workspace per lpips_u8 launch sequence: larger n is split into chunks
 
 

@@ -271,15 +271,65 @@ def predict_slices(args, gen1, gen2, cond_stacks, device, batch_size=32, x_inits
 
 def predict_volume(args):
     """Reference :209-300, same flags, same output file `predicted_<target>.nii.gz`.  With --num_samples the ensemble's mean goes
-    there and its std next to it; the return value is then the pair of paths.  --prec_plan holds for the whole prediction."""
+    there and its std next to it; the return value is then the pair of paths.  --prec_plan holds for the whole prediction.
+    With --gt_volume (and --eval_mask) the written prediction is scored afterwards (mudiff_hip.volume_metrics): the lines are printed
+    after the [done] line and metrics_<target>.json goes next to the prediction.  Those inputs are checked first, before any GPU or
+    checkpoint work."""
+    evaluation = load_eval_inputs(args)
     from . import ops
     from .driver import effective_prec_plan
     plan = effective_prec_plan(args)
     with ops.prec_plan(plan):
-        return _predict_volume(args, plan)
+        return _predict_volume(args, plan, evaluation)
 
 
-def _predict_volume(args, plan):
+def _needed_inputs(args):
+    """[(modality, path)] of the target's three condition contrasts, in MODALITY_ORDERS order."""
+    if args.target_modality not in MODALITY_ORDERS:
+        raise ValueError(f'Unsupported target modality: {args.target_modality}')
+    needed = MODALITY_ORDERS[args.target_modality]
+    provided = {'T1CE': args.input_t1ce, 'T1': args.input_t1, 'T2': args.input_t2, 'FLAIR': args.input_flair}
+    for m in needed:
+        if not provided.get(m):
+            raise ValueError(f'Missing required input for {m}. Provide --input_{m.lower()}')
+    return [(m, provided[m]) for m in needed]
+
+
+def load_eval_inputs(args):
+    """--gt_volume / --eval_mask -> None, or (raw GT volume, label volume or None) once the files have been read and their shapes
+    checked against the first input volume and the slab (volume_metrics.check_shapes).  A bad evaluation input raises ValueError
+    here, so that it cannot cost a sampling run."""
+    gt_path, mask_path = getattr(args, 'gt_volume', None), getattr(args, 'eval_mask', None)
+    if gt_path is None:
+        if mask_path is not None:
+            raise ValueError('--eval_mask needs --gt_volume')
+        return None
+    from .volume_metrics import check_shapes, warn_affine
+    _, first = _needed_inputs(args)[0]
+    inp, inp_aff, _ = read_nifti(first)
+    gt, gt_aff, _ = read_nifti(gt_path)
+    label = None if mask_path is None else read_nifti(mask_path)[0]
+    try:
+        check_shapes(inp.shape, gt.shape, None if label is None else label.shape, args.slice_half_range)
+    except ValueError as e:
+        raise ValueError(f'--gt_volume / --eval_mask: {e} (the prediction has the shape of {first})') from None
+    warn_affine(inp_aff, gt_aff, first, gt_path)
+    return gt, label
+
+
+def _score_prediction(args, evaluation, vol, std_vol, device):
+    """Scores of the prediction exactly as written -> printed lines and <output_dir>/metrics_<target>.json (its path)."""
+    from . import volume_metrics as VM
+    gt, label = evaluation
+    rep = VM.score_arrays(vol, gt, label, std_vol, args.slice_half_range, device)
+    for ln in VM.format_lines(rep):
+        print(ln)
+    path = VM.write_json(rep, os.path.join(args.output_dir, f'metrics_{args.target_modality.lower()}.json'))
+    print(f'[metrics] wrote {path}')
+    return path
+
+
+def _predict_volume(args, plan, evaluation=None):
     from backbones.ncsnpp_generator_adagn_feat import NCSNpp, NCSNpp_adaptive
     torch.manual_seed(args.seed)
     torch.cuda.set_device(args.gpu_chose)
@@ -289,16 +339,9 @@ def _predict_volume(args, plan):
     load_checkpoint(tmpl, gen1, 'gen_diffusive_1', device)
     load_checkpoint(tmpl, gen2, 'gen_diffusive_2', device)
 
-    if args.target_modality not in MODALITY_ORDERS:
-        raise ValueError(f'Unsupported target modality: {args.target_modality}')
-    needed = MODALITY_ORDERS[args.target_modality]
-    provided = {'T1CE': args.input_t1ce, 'T1': args.input_t1, 'T2': args.input_t2, 'FLAIR': args.input_flair}
-    for m in needed:
-        if not provided.get(m):
-            raise ValueError(f'Missing required input for {m}. Provide --input_{m.lower()}')
     stacks, ref = [], None
-    for m in needed:
-        slices, shp, aff, hdr, s0, s1 = load_and_preprocess_volume(provided[m], args.slice_half_range)
+    for m, path in _needed_inputs(args):
+        slices, shp, aff, hdr, s0, s1 = load_and_preprocess_volume(path, args.slice_half_range)
         if ref is None:
             ref = (shp, aff, hdr, s0, s1)
         elif shp != ref[0]:
@@ -318,7 +361,7 @@ def _predict_volume(args, plan):
             print(f'[calibrate] wrote {write_calibration(cal, args.output_dir)}')
     num_samples = getattr(args, 'num_samples', None)
     if num_samples is not None:
-        return _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref)
+        return _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref, evaluation)
     pred = predict_slices(args, gen1, gen2, stacks, device, batch_size=args.batch_size, seed=args.seed,
                           progress=lambda d, n: print(f'[infer] processed {d}/{n} slices'))
     if tuple(shp[:2]) != tuple(pred.shape[1:]):
@@ -329,13 +372,15 @@ def _predict_volume(args, plan):
     out_path = os.path.join(args.output_dir, f'predicted_{args.target_modality.lower()}.nii.gz')
     write_nifti(out_path, vol_pred, aff, hdr)
     print(f'[done] saved: {out_path} | shape={tuple(vol_pred.shape)} | slices={s0}..{s1}' + ('' if plan == 'auto' else f' | prec_plan={plan}'))
+    if evaluation is not None:
+        _score_prediction(args, evaluation, vol_pred, None, device)
     return out_path
 
 
-def _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref):
+def _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref, evaluation=None):
     """--num_samples: every slice sampled N times with draws keyed by (--seed, slice, sample) (mudiff_hip.ensemble); the mean and
     the std of the [0,1]-mapped samples, resized back and re-assembled like the single prediction, go to predicted_<t>.nii.gz and
-    predicted_<t>_std.nii.gz.  -> (mean path, std path)."""
+    predicted_<t>_std.nii.gz.  With `evaluation` the mean is scored, the std feeding the uncertainty block.  -> (mean path, std path)."""
     from . import ensemble, ops
     from .driver import effective_prec_plan
     shp, aff, hdr, s0, s1 = ref
@@ -344,7 +389,7 @@ def _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref):
     print(f'[infer] {conds[0].shape[0]} slices x {args.num_samples} samples')
     mean, std = ensemble.sample_ensemble(args, gen1, gen2, conds, args.num_samples, args.seed, batch_size=args.batch_size, map_0_1=True)
     os.makedirs(args.output_dir, exist_ok=True)
-    paths = []
+    paths, vols = [], []
     for suffix, t in (('', mean), ('_std', std)):
         if tuple(shp[:2]) != tuple(t.shape[1:]):
             t = ops.resize_bilinear(t, shp[:2])
@@ -352,15 +397,19 @@ def _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref):
         path = os.path.join(args.output_dir, f'predicted_{args.target_modality.lower()}{suffix}.nii.gz')
         write_nifti(path, vol, aff, hdr)
         paths.append(path)
+        vols.append(vol)
     print(f'[done] saved: {paths[0]} and {paths[1]} | shape={tuple(shp)} | slices={s0}..{s1} | {args.num_samples} samples per slice' +
           ('' if effective_prec_plan(args) == 'auto' else f' | prec_plan={effective_prec_plan(args)}'))      # (the default plan: the line as it was)
+    if evaluation is not None:
+        _score_prediction(args, evaluation, vols[0], vols[1], device)
     return tuple(paths)
 
 
 def build_argparser(argv=None):
     """Flags and defaults of the reference parser (:302-357; like it, returns the PARSED namespace), plus --centered (which
     the generators read and the reference parser forgot), --batch_size, --resize_back, --calibrate / --calibrate_threshold
-    (mudiff_hip.precision; the record goes to <output_dir>/prec_calibration.json) and --num_samples (ensembles)."""
+    (mudiff_hip.precision; the record goes to <output_dir>/prec_calibration.json), --num_samples (ensembles) and --gt_volume /
+    --eval_mask (scoring of the written prediction, mudiff_hip.volume_metrics)."""
     p = argparse.ArgumentParser('MU-Diff volume prediction (MI355X)')
     for m in ('t1ce', 't1', 't2', 'flair'):
         p.add_argument(f'--input_{m}', type=str, help=f'Path to {m.upper()} NIfTI')
@@ -405,6 +454,11 @@ def build_argparser(argv=None):
     p.add_argument('--num_samples', type=int, default=None,
                    help='sample every slice N >= 2 times with draws keyed by --seed (mudiff_hip.ensemble): predicted_<t>.nii.gz is then '
                         'the mean of the [0,1]-mapped samples, and predicted_<t>_std.nii.gz their per-voxel standard deviation')
+    p.add_argument('--gt_volume', type=str, default=None,
+                   help='ground-truth NIfTI of the target contrast: score the written prediction on the GPU (PSNR / SSIM3D / MAE per '
+                        'region, mudiff_hip.volume_metrics) and write metrics_<t>.json next to it')
+    p.add_argument('--eval_mask', type=str, default=None,
+                   help='label NIfTI (e.g. a BraTS segmentation; needs --gt_volume): adds the tumor (label != 0) and healthy regions')
     from .driver import add_calibration_flags, check_prec_plan_flags
     add_calibration_flags(p)                # (also --prec_plan)
     args = p.parse_args(argv)
