@@ -341,6 +341,45 @@ int mud_randn_keyed(float* out, int rows, int64_t row_len, const int64_t* keys, 
 int mud_ensemble_stats(const float* samples, int n, int N, int64_t hw, float scale, float shift, float lo, float hi, float* mean,
                        float* std, void* stream);
 
+/* ---- on-device NIfTI intake and re-assembly of the volume pipeline (mudiff_hip.volume_intake; --device_intake, mudiff_hip.cohort).
+ * A volume is passed exactly as the file stores it: X x Y x Z voxels, x fastest ([Z][Y][X] in C terms), 16-byte aligned, X*Y*Z < 2^31,
+ * in the NIfTI datatype MUD_NIFTI_* (little-endian), with the header's scl_slope / scl_inter.  A voxel's value is
+ * float32(double(raw) * slope + inter), product and sum rounded separately, when scaling applies (slope finite and not 0, and not
+ * slope 1 with inter 0: volume.read_nifti's rule), else float32(raw).  Voxels with value != 0 are `selected` (a NaN is).
+ *
+ * mud_volume_census: the order statistics of the selected values, as one device record (8-byte aligned):
+ *   n, n_nonfinite (selected NaN / inf), min and max (0 when n is 0), and for each fraction q[i] in [0, 1] (i < nq <= MUD_VI_MAX_RANKS; a
+ *   host array) the exact sorted values at the ranks first_rank[i] .. first_rank[i] + count[i] - 1 = [r - 8, r + 7] clipped to [0, n),
+ *   r = floor((n - 1) * q[i]) in fp64 on the device: window[i][0 .. count[i]).  A radix select (8-bit digits, four histogram passes
+ *   over the volume and one gathering pass): exact for any tie structure, no host round trip, no sort of the volume.  NaN sorts last.
+ *   ws: mud_volume_census_ws_bytes() bytes, 8-byte aligned.
+ * mud_volume_slab_normalise: out[i][x][y] (fp32 [s1 - s0 + 1][X][Y]) = clip((v - lo) / den, 0, 1) * 2 - 1 of the voxel (x, y, s0 + i),
+ *   every step in fp32 and rounded once, the division correctly rounded; NaN stays NaN.  den is hi - lo as the host forms it (fp32).
+ *   With `degenerate` != 0 (no selected voxels, or a flat volume) the slab is zeros.  Needs 0 <= s0 <= s1 < Z.
+ * mud_volume_assemble: planes [s1 - s0 + 1][X][Y] (fp32) -> vol [Z][Y][X] (file order): zeros, except the planes s0..s1.  planes2 / vol2:
+ *   an optional second stack (an ensemble's std) assembled the same way; both NULL or both given. */
+#define MUD_NIFTI_U1 2
+#define MUD_NIFTI_I2 4
+#define MUD_NIFTI_I4 8
+#define MUD_NIFTI_F4 16
+#define MUD_NIFTI_U2 512
+#define MUD_VI_MAX_RANKS 4
+#define MUD_VI_WINDOW 16
+typedef struct mud_volume_census_record {
+  uint64_t n, n_nonfinite;
+  float min, max;
+  int32_t count[MUD_VI_MAX_RANKS];
+  int64_t first_rank[MUD_VI_MAX_RANKS];
+  float window[MUD_VI_MAX_RANKS][MUD_VI_WINDOW];
+} mud_volume_census_record;
+int64_t mud_volume_census_ws_bytes(void);
+int mud_volume_census(const void* vol, int datatype, int X, int Y, int Z, float slope, float inter, const double* q, int nq,
+                      mud_volume_census_record* record, void* ws, int64_t ws_bytes, void* stream);
+int mud_volume_slab_normalise(const void* vol, int datatype, int X, int Y, int Z, float slope, float inter, float lo, float den,
+                              int degenerate, int s0, int s1, float* out, void* stream);
+int mud_volume_assemble(const float* planes, const float* planes2, int X, int Y, int Z, int s0, int s1, float* vol, float* vol2,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

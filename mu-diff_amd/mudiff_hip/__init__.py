@@ -78,6 +78,17 @@ class CensusOut(C.Structure):
     _fields_ = [('n', C.c_uint64), ('n_over', C.c_uint64), ('n_under', C.c_uint64), ('n_fp16_over', C.c_uint64), ('amax_bits', C.c_uint64)]
 
 
+VI_MAX_RANKS, VI_WINDOW = 4, 16
+NIFTI_U1, NIFTI_I2, NIFTI_I4, NIFTI_F4, NIFTI_U2 = 2, 4, 8, 16, 512
+
+
+class VolumeCensusRecord(C.Structure):
+    """struct mud_volume_census_record (include/mudiff_hip.h)."""
+    _fields_ = [('n', C.c_uint64), ('n_nonfinite', C.c_uint64), ('min', C.c_float), ('max', C.c_float),
+                ('count', C.c_int32 * VI_MAX_RANKS), ('first_rank', C.c_int64 * VI_MAX_RANKS),
+                ('window', (C.c_float * VI_WINDOW) * VI_MAX_RANKS)]
+
+
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
 _SIGNATURES = {
     'mud_version': (C.c_int, []),
@@ -128,6 +139,10 @@ _SIGNATURES = {
     'mud_lpips_u8': (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _L, _P]),
     'mud_randn_keyed': (_I, [_P, _I, _L, _P, C.c_uint64, _I, _I, _P]),
     'mud_ensemble_stats': (_I, [_P, _I, _I, _L, _F, _F, _F, _F, _P, _P, _P]),
+    'mud_volume_census_ws_bytes': (_L, []),
+    'mud_volume_census': (_I, [_P, _I, _I, _I, _I, _F, _F, C.POINTER(C.c_double), _I, _P, _P, _L, _P]),
+    'mud_volume_slab_normalise': (_I, [_P, _I, _I, _I, _I, _F, _F, _F, _F, _I, _I, _I, _P, _P]),
+    'mud_volume_assemble': (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

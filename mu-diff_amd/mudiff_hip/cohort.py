@@ -1,0 +1,293 @@
+"""Cohort volume prediction: a whole test split in one process (the volume pipeline of mudiff_hip.volume, once per subject).
+
+    python -m mudiff_hip.cohort --manifest cohort.tsv --target_modality T1CE --exp <exp> --output_dir out [--score] [volume.py's flags]
+    python -m mudiff_hip.cohort --brats_root DIR --subjects test.list --target_modality T1CE --exp <exp> --output_dir out --score
+
+What one process buys: the checkpoints are loaded, the weights packed and the sampler's hipGraphs captured once (one GraphSampler per
+(batch, image_size), reused for every subject); a small host thread pool reads and gunzips subject i+1 while the GPU samples subject i
+and compresses and writes subject i-1; intake and re-assembly run on the device (mudiff_hip.volume_intake).  All GPU work stays on one
+stream in this process.
+
+Every subject is sampled with --seed exactly as a separate `python -m mudiff_hip.volume` run would sample it, so each written volume
+is that run's file, bit for bit.  (--calibrate is the exception it has to be: it runs once, on the first subject.)
+
+A bad subject - a missing or unreadable file, volumes of different shapes, an in-plane size the flags cannot write back - is reported
+and skipped; the run goes on and exits non-zero at the end.  A GPU error is not caught: it ends the run.
+
+Outputs: <output_dir>/<id>/predicted_<t>.nii.gz (plus _std and metrics_<t>.json when applicable) and <output_dir>/cohort_<t>.json: the
+per-subject rows, per region and metric the mean, the population standard deviation (ddof = 0) and the subject count, and the seconds
+of every stage summed over the cohort.
+"""
+from __future__ import annotations
+
+import collections
+import concurrent.futures as cf
+import copy
+import csv
+import json
+import math
+import os
+import sys
+import struct
+import time
+import zlib
+
+METRICS = ('psnr', 'ssim3d', 'mae')
+MODALITIES = ('t1', 't1ce', 't2', 'flair')
+QUEUE_DEPTH = 2                    # subjects read ahead, and written volumes in flight: memory stays flat whatever the cohort's size
+Subject = collections.namedtuple('Subject', 'id inputs gt mask')       # inputs: {'T1': path, ...}; gt / mask: path or None
+
+
+# ---------------------------------------------------------------------------------------------------
+# which subjects
+# ---------------------------------------------------------------------------------------------------
+def read_manifest(path):
+    """TSV with a header row: id, t1, t1ce, t2, flair and optionally gt, mask (an empty cell is `not given`).  Relative paths are
+    relative to the manifest."""
+    base = os.path.dirname(os.path.abspath(path))
+    with open(path, newline='') as f:
+        rows = list(csv.DictReader(f, delimiter='\t'))
+    if not rows:
+        raise ValueError(f'{path}: no subjects')
+    missing = [c for c in ('id',) + MODALITIES if c not in rows[0]]
+    if missing:
+        raise ValueError(f'{path}: the header lacks the column(s) {", ".join(missing)}')
+    where = lambda v: (v if os.path.isabs(v) else os.path.join(base, v)) if v else None      # noqa: E731
+    out = []
+    for r in rows:
+        sid = (r['id'] or '').strip()
+        if not sid:
+            raise ValueError(f'{path}: a row without an id')
+        out.append(Subject(sid, {m.upper(): where((r[m] or '').strip()) for m in MODALITIES}, where((r.get('gt') or '').strip()),
+                           where((r.get('mask') or '').strip())))
+    if len({s.id for s in out}) != len(out):
+        raise ValueError(f'{path}: subject ids must be unique')
+    return out
+
+
+def brats_subjects(root, list_path, target):
+    """The BraTS layout: <root>/<id>/<id>_{t1,t1ce,t2,flair,seg}.nii.gz for every id in the list file (one per line; blank lines and
+    # comments are skipped).  The target contrast's own file is the ground truth, seg the mask."""
+    with open(list_path) as f:
+        ids = [ln.strip() for ln in f if ln.strip() and not ln.lstrip().startswith('#')]
+    if not ids:
+        raise ValueError(f'{list_path}: no subjects')
+    p = lambda sid, what: os.path.join(root, sid, f'{sid}_{what}.nii.gz')                      # noqa: E731
+    return [Subject(sid, {m.upper(): p(sid, m) for m in MODALITIES}, p(sid, target.lower()), p(sid, 'seg')) for sid in ids]
+
+
+# ---------------------------------------------------------------------------------------------------
+# the cohort's table
+# ---------------------------------------------------------------------------------------------------
+def subject_row(sid, report):
+    """One row of the table from a metrics_<t>.json report: {id, metrics: {region: {psnr, ssim3d, mae, voxels}}}."""
+    return dict(id=sid, metrics={name: {k: report['metrics'][name][k] for k in METRICS + ('voxels',)} for name in report['regions']})
+
+
+def aggregate(rows):
+    """Per region and metric over the subjects that have a finite value: mean, std (population, ddof = 0) and count, summed in fp64 in
+    row order.  A region no subject has (or only with null / infinite scores) reports null."""
+    regions = []
+    for r in rows:
+        regions += [name for name in r['metrics'] if name not in regions]
+    out = {}
+    for name in regions:
+        out[name] = {}
+        for k in METRICS:
+            vals = [r['metrics'][name][k] for r in rows if name in r['metrics']]
+            vals = [float(v) for v in vals if v is not None and math.isfinite(v)]
+            if not vals:
+                out[name][k] = dict(mean=None, std=None, count=0)
+                continue
+            mean = math.fsum(vals) / len(vals)
+            out[name][k] = dict(mean=mean, std=math.sqrt(math.fsum((v - mean) ** 2 for v in vals) / len(vals)), count=len(vals))
+    return out
+
+
+def format_lines(agg):
+    """One line per region, in the style of volume_metrics.format_lines."""
+    f = lambda d, spec: 'n/a' if d['mean'] is None else f"{format(d['mean'], spec)} +- {format(d['std'], spec)}"      # noqa: E731
+    return [f"[cohort] {name}: PSNR {f(m['psnr'], '.4f')} dB | SSIM3D {f(m['ssim3d'], '.6f')} | MAE {f(m['mae'], '.6f')} | "
+            f"subjects {m['psnr']['count']}" for name, m in agg.items()]
+
+
+# ---------------------------------------------------------------------------------------------------
+# one subject
+# ---------------------------------------------------------------------------------------------------
+def _read_subject(subject, needed, score):
+    """(prefetch thread) The subject's three condition volumes as stored (volume_intake.read_nifti_raw) and, with `score`, the
+    evaluation inputs of volume.load_eval_inputs.  -> (raws, evaluation inputs or None, seconds)."""
+    from . import volume as V
+    from . import volume_intake as VI
+    t0 = time.perf_counter()
+    for m in needed:
+        if not subject.inputs.get(m):
+            raise ValueError(f'no {m} volume given')
+    raws = [VI.read_nifti_raw(subject.inputs[m]) for m in needed]
+    ev = None
+    if score:
+        if not subject.gt:
+            raise ValueError('--score needs a ground-truth volume (the manifest\'s gt column)')
+        gt, gt_aff, _ = V.read_nifti(subject.gt)
+        label = V.read_nifti(subject.mask)[0] if subject.mask else None
+        ev = (gt, label, gt_aff)
+    return raws, ev, time.perf_counter() - t0
+
+
+def _timed_write(path, vol, affine, header):
+    from .volume import write_nifti
+    t0 = time.perf_counter()
+    write_nifti(path, vol, affine, header)
+    return time.perf_counter() - t0
+
+
+def run(args, subjects, predict=None):
+    """The cohort loop -> (report dict, failures [(id, message)]).  `predict(args, plan, evaluation, conds, ref, write, calibrate,
+    timing)` replaces the sampling of one subject (tests stub it); by default it is volume.predict_from_conditions on the loaded model."""
+    import torch
+    from . import ops
+    from . import volume as V
+    from . import volume_intake as VI
+    from . import volume_metrics as VM
+    from .driver import effective_prec_plan
+    target = args.target_modality
+    needed = V.MODALITY_ORDERS[target]
+    plan = effective_prec_plan(args)
+    timing = dict(read=0.0, intake=0.0, sample=0.0, assemble=0.0, write=0.0, write_wait=0.0, score=0.0)
+    rows, failures, pending = [], [], collections.deque()
+    t_wall = time.perf_counter()
+    device = None
+    if predict is None:
+        torch.cuda.set_device(args.gpu_chose)
+        device = torch.device(f'cuda:{args.gpu_chose}')
+        gen1, gen2 = V.load_generators(args, device)
+        samplers = {}
+
+        def predict(sargs, plan, evaluation, conds, ref, write, calibrate, timing):
+            return V.predict_from_conditions(sargs, plan, evaluation, gen1, gen2, device, conds, ref, on_device=True, samplers=samplers,
+                                             write=write, calibrate=calibrate, timing=timing)
+
+    def drain(keep):
+        while len(pending) > keep:
+            timing['write'] += pending.popleft().result()
+
+    pool = cf.ThreadPoolExecutor(max_workers=max(1, int(args.io_threads)))
+    try:
+        reads = collections.deque()
+        todo = iter(subjects)
+
+        def prefetch():
+            while len(reads) < QUEUE_DEPTH:
+                s = next(todo, None)
+                if s is None:
+                    return
+                reads.append((s, pool.submit(_read_subject, s, needed, args.score)))
+
+        prefetch()
+        calibrated = False
+        with ops.prec_plan(plan):
+            while reads:
+                subject, fut = reads.popleft()
+                prefetch()                                         # subject i+1 is read while subject i runs
+                try:
+                    raws, ev, t_read = fut.result()
+                    timing['read'] += t_read
+                    sargs = copy.copy(args)
+                    sargs.output_dir = os.path.join(args.output_dir, subject.id)
+                    evaluation = None
+                    if ev is not None:
+                        gt, label, gt_aff = ev
+                        try:
+                            VM.check_shapes(raws[0].shape, gt.shape, None if label is None else label.shape, args.slice_half_range)
+                        except ValueError as e:
+                            raise ValueError(f'ground truth / mask: {e}') from None
+                        VM.warn_affine(raws[0].affine, gt_aff, subject.inputs[needed[0]], subject.gt)
+                        evaluation = (gt, label)
+                    torch.manual_seed(args.seed)
+                    t0 = time.perf_counter()
+                    if device is None:
+                        conds, ref = raws, (raws[0].shape, raws[0].affine, raws[0].header) + VI.slab_range(raws[0].shape[2], args.slice_half_range)
+                        for r, m in zip(raws, needed):
+                            if r.shape != raws[0].shape:
+                                raise ValueError(f'All input volumes must share shape. Got {r.shape} vs {raws[0].shape} for {m}')
+                    else:
+                        conds, *ref = VI.load_conditions([subject.inputs[m] for m in needed], args.slice_half_range, args.image_size,
+                                                         device, raws=raws)
+                        torch.cuda.synchronize(device)
+                    timing['intake'] += time.perf_counter() - t0
+
+                    def write(path, vol, affine, header):
+                        drain(QUEUE_DEPTH - 1)                     # subject i-1 is compressed and written while subject i runs
+                        pending.append(pool.submit(_timed_write, path, vol, affine, header))
+
+                    t0 = time.perf_counter()
+                    stage = {}
+                    predict(sargs, plan, evaluation, conds, tuple(ref), write, not calibrated, stage)
+                    calibrated = True
+                    for k in ('sample', 'assemble'):
+                        timing[k] += stage.get(k, 0.0)
+                    timing['write_wait'] += stage.get('write', 0.0)      # the main thread waiting for an earlier subject's write
+                    timing['score'] += max(0.0, time.perf_counter() - t0 - sum(stage.values()))
+                    row = dict(id=subject.id, metrics={})
+                    if evaluation is not None:
+                        with open(os.path.join(sargs.output_dir, f'metrics_{target.lower()}.json')) as f:
+                            row = subject_row(subject.id, json.load(f))
+                    rows.append(row)
+                except (OSError, ValueError, EOFError, zlib.error, struct.error) as e:       # (what reading a damaged file raises)
+                    failures.append((subject.id, f'{type(e).__name__}: {e}'))
+                    print(f'[cohort] skipped {subject.id}: {e}', file=sys.stderr)
+        drain(0)
+    finally:
+        pool.shutdown(wait=True, cancel_futures=True)
+    timing['wall'] = time.perf_counter() - t_wall
+    agg = aggregate(rows)
+    report = dict(target=target, subjects=rows, failed=[dict(id=i, error=e) for i, e in failures], aggregate=agg,
+                  std_definition='population standard deviation over subjects (ddof = 0)', timing=timing)
+    os.makedirs(args.output_dir, exist_ok=True)
+    path = os.path.join(args.output_dir, f'cohort_{target.lower()}.json')
+    with open(path, 'w') as f:
+        json.dump(report, f, indent=1)
+    for ln in format_lines(agg):
+        print(ln)
+    print(f'[cohort] {len(rows)} of {len(subjects)} subjects in {timing["wall"]:.1f} s; wrote {path}')
+    return report, failures
+
+
+def build_argparser(argv=None):
+    """volume.py's parser (shared, not copied) plus the cohort's own flags."""
+    from . import volume as V
+    p = V.make_parser('MU-Diff cohort volume prediction (MI355X)')
+    p.add_argument('--manifest', type=str, default=None, help='TSV with a header row: id, t1, t1ce, t2, flair and optionally gt, mask')
+    p.add_argument('--brats_root', type=str, default=None, help='BraTS layout: <root>/<id>/<id>_{t1,t1ce,t2,flair,seg}.nii.gz')
+    p.add_argument('--subjects', type=str, default=None, help='with --brats_root: a file with one subject id per line')
+    p.add_argument('--score', action='store_true',
+                   help='score every prediction (mudiff_hip.volume_metrics) against the subject\'s gt / mask and aggregate the cohort')
+    p.add_argument('--io_threads', type=int, default=4, help='host threads that read / gunzip ahead and compress / write behind')
+    args = V.finish_args(p, p.parse_args(argv))
+    if (args.manifest is None) == (args.brats_root is None):
+        p.error('give --manifest FILE, or --brats_root DIR with --subjects LIST')
+    if args.brats_root is not None and args.subjects is None:
+        p.error('--brats_root needs --subjects LIST')
+    if args.io_threads < 1:
+        p.error('--io_threads must be >= 1')
+    for flag in ('gt_volume', 'eval_mask') + tuple(f'input_{m}' for m in MODALITIES):
+        if getattr(args, flag) is not None:
+            p.error(f'--{flag} names one subject\'s file: a cohort takes its files from the manifest or the BraTS layout')
+    return args
+
+
+def main(argv=None):
+    args = build_argparser(argv)
+    try:
+        subjects = read_manifest(args.manifest) if args.manifest else brats_subjects(args.brats_root, args.subjects, args.target_modality)
+    except (OSError, ValueError) as e:
+        print(f'error: {e}', file=sys.stderr)
+        return 2
+    _, failures = run(args, subjects)
+    for sid, msg in failures:
+        print(f'[cohort] FAILED {sid}: {msg}', file=sys.stderr)
+    return 1 if failures else 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

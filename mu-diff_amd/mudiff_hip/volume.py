@@ -182,11 +182,14 @@ def load_checkpoint(template, net, name, device):
 # ---------------------------------------------------------------------------------------------------
 def upload_conds(cond_stacks, size, device):
     """Three [n,X,Y] condition stacks -> [n,1,size,size] device tensors: one upload + one resize launch per contrast (reference:
-    per slice, on the CPU)."""
+    per slice, on the CPU).  A stack that is a device tensor already ([n,1,X,Y], mudiff_hip.volume_intake) is only resized."""
     from . import ops
     conds = []
     for st in cond_stacks:
-        t = torch.from_numpy(np.ascontiguousarray(st, dtype=np.float32)).to(device)[:, None]
+        if torch.is_tensor(st):
+            t = st.to(device)
+        else:
+            t = torch.from_numpy(np.ascontiguousarray(st, dtype=np.float32)).to(device)[:, None]
         if tuple(t.shape[-2:]) != (size, size):
             t = ops.resize_bilinear(t, (size, size))
         conds.append(t.contiguous())
@@ -208,9 +211,10 @@ def calibrate_volume(args, gen1, gen2, cond_stacks, device, batch_size=32):
 
 
 def predict_slices(args, gen1, gen2, cond_stacks, device, batch_size=32, x_inits=None, zs=None, noises=None, seed=None,
-                   use_graph=True, progress=None, sampler=None):
-    """cond_stacks: three float arrays [n,X,Y] in [-1,1] (the condition contrasts, already normalised and sliced).
-    -> [n,S,S] float32 numpy in [0,1], S = args.image_size.
+                   use_graph=True, progress=None, sampler=None, return_device=False):
+    """cond_stacks: three float arrays [n,X,Y] in [-1,1] (the condition contrasts, already normalised and sliced), or three device
+    tensors [n,1,X,Y] (volume_intake.load_conditions).  -> [n,S,S] float32 numpy in [0,1], S = args.image_size; with `return_device`
+    the device tensor instead (no copy to the host).
 
     `sampler`: a sampling.GraphSampler built for these generators (any batch size, image_size x image_size) to reuse across
     volumes - warm-up and the two hipGraph captures are then paid once per process instead of once per volume.
@@ -222,7 +226,7 @@ def predict_slices(args, gen1, gen2, cond_stacks, device, batch_size=32, x_inits
     n = int(cond_stacks[0].shape[0])
     size = int(args.image_size)
     if n == 0:
-        return np.zeros((0, size, size), np.float32)
+        return torch.zeros(0, size, size, device=device) if return_device else np.zeros((0, size, size), np.float32)
     conds = upload_conds(cond_stacks, size, device)
     coef = S.Posterior_Coefficients(args, device)
     gen = None
@@ -266,7 +270,7 @@ def predict_slices(args, gen1, gen2, cond_stacks, device, batch_size=32, x_inits
         out[lo:hi] = ops.to_range_0_1(fake)[:hi - lo, 0]
         if progress:
             progress(hi, n)
-    return out.cpu().numpy()
+    return out if return_device else out.cpu().numpy()
 
 
 def predict_volume(args):
@@ -329,16 +333,26 @@ def _score_prediction(args, evaluation, vol, std_vol, device):
     return path
 
 
-def _predict_volume(args, plan, evaluation=None):
+def load_generators(args, device):
+    """The two generators of --exp on `device`, checkpoints loaded (reference :193-203)."""
     from backbones.ncsnpp_generator_adagn_feat import NCSNpp, NCSNpp_adaptive
-    torch.manual_seed(args.seed)
-    torch.cuda.set_device(args.gpu_chose)
-    device = torch.device(f'cuda:{args.gpu_chose}')
     gen1, gen2 = NCSNpp(args).to(device), NCSNpp_adaptive(args).to(device)
     tmpl = os.path.join(args.output_path, args.exp, '{}.pth')
     load_checkpoint(tmpl, gen1, 'gen_diffusive_1', device)
     load_checkpoint(tmpl, gen2, 'gen_diffusive_2', device)
+    return gen1, gen2
 
+
+def _predict_volume(args, plan, evaluation=None):
+    torch.manual_seed(args.seed)
+    torch.cuda.set_device(args.gpu_chose)
+    device = torch.device(f'cuda:{args.gpu_chose}')
+    gen1, gen2 = load_generators(args, device)
+
+    if getattr(args, 'device_intake', False):
+        from . import volume_intake as VI
+        stacks, *ref = VI.load_conditions([path for _, path in _needed_inputs(args)], args.slice_half_range, args.image_size, device)
+        return predict_from_conditions(args, plan, evaluation, gen1, gen2, device, stacks, tuple(ref), on_device=True)
     stacks, ref = [], None
     for m, path in _needed_inputs(args):
         slices, shp, aff, hdr, s0, s1 = load_and_preprocess_volume(path, args.slice_half_range)
@@ -347,13 +361,44 @@ def _predict_volume(args, plan, evaluation=None):
         elif shp != ref[0]:
             raise ValueError(f'All input volumes must share shape. Got {shp} vs {ref[0]} for {m}')
         stacks.append(np.stack(slices, 0))
+    return predict_from_conditions(args, plan, evaluation, gen1, gen2, device, stacks, ref)
+
+
+class _Stages:
+    """Per-stage seconds of predict_from_conditions for a caller that asks (mudiff_hip.cohort): each stage ends in a device
+    synchronise.  Without a dict nothing is timed and nothing is synchronised."""
+
+    def __init__(self, timing, device):
+        self.timing, self.device = timing, device
+
+    def run(self, name, fn):
+        if self.timing is None:
+            return fn()
+        import time
+        torch.cuda.synchronize(self.device)
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize(self.device)
+        self.timing[name] = self.timing.get(name, 0.0) + time.perf_counter() - t0
+        return out
+
+
+def predict_from_conditions(args, plan, evaluation, gen1, gen2, device, stacks, ref, on_device=False, samplers=None, write=None,
+                            calibrate=True, timing=None):
+    """Everything after the intake: `stacks` are the three condition stacks (host [n,X,Y], or device [n,1,S,S] with `on_device`, which
+    also keeps the prediction on the device until volume_intake.assemble has put it in file order), `ref` = (shape, affine, header, s0,
+    s1).  `samplers`: a dict that keeps the captured GraphSamplers by (batch, image_size) across calls; `write`: replaces write_nifti
+    (same arguments; a cohort defers it to a thread); `calibrate=False` skips --calibrate (done on an earlier subject); `timing`: a
+    dict that receives the seconds of the stages sample / assemble / write."""
     shp, aff, hdr, s0, s1 = ref
+    write = write or write_nifti
+    stages = _Stages(timing, device)
     if tuple(shp[:2]) != (args.image_size, args.image_size) and not args.resize_back:
         # the reference fails here too, later and less clearly (numpy broadcast error at :179 when the [S,S] prediction is
         # written into an [X,Y] plane); --resize_back is this build's opt-in extension
         raise ValueError(f'in-plane size {tuple(shp[:2])} differs from --image_size {args.image_size}: the prediction cannot be '
                          'written back into the volume (pass --resize_back to resample it bilinearly)')
-    if getattr(args, 'calibrate', False):
+    if getattr(args, 'calibrate', False) and calibrate:
         cal = calibrate_volume(args, gen1, gen2, stacks, device, batch_size=args.batch_size)
         if cal is not None:
             from .driver import write_calibration
@@ -361,23 +406,48 @@ def _predict_volume(args, plan, evaluation=None):
             print(f'[calibrate] wrote {write_calibration(cal, args.output_dir)}')
     num_samples = getattr(args, 'num_samples', None)
     if num_samples is not None:
-        return _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref, evaluation)
-    pred = predict_slices(args, gen1, gen2, stacks, device, batch_size=args.batch_size, seed=args.seed,
-                          progress=lambda d, n: print(f'[infer] processed {d}/{n} slices'))
-    if tuple(shp[:2]) != tuple(pred.shape[1:]):
-        from . import ops
-        pred = ops.resize_bilinear(torch.from_numpy(pred).to(device), shp[:2]).cpu().numpy()
-    vol_pred = reconstruct_volume_from_slices(list(pred), shp, s0, s1)
+        return _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref, evaluation, on_device, samplers, write, stages)
+    n = int(stacks[0].shape[0])
+    sampler = _cached_sampler(args, gen1, gen2, device, samplers, min(int(args.batch_size), n)) if n else None
+    pred = stages.run('sample', lambda: predict_slices(args, gen1, gen2, stacks, device, batch_size=args.batch_size, seed=args.seed,
+                                                       progress=lambda d, n: print(f'[infer] processed {d}/{n} slices'), sampler=sampler,
+                                                       return_device=on_device))
+    if on_device:
+        def put_together():
+            from . import ops
+            from . import volume_intake as VI
+            p = pred if tuple(shp[:2]) == tuple(pred.shape[1:]) else ops.resize_bilinear(pred, shp[:2])
+            return VI.to_host_volume(VI.assemble(p, shp, s0, s1))
+        vol_pred = stages.run('assemble', put_together)
+    else:
+        if tuple(shp[:2]) != tuple(pred.shape[1:]):
+            from . import ops
+            pred = ops.resize_bilinear(torch.from_numpy(pred).to(device), shp[:2]).cpu().numpy()
+        vol_pred = reconstruct_volume_from_slices(list(pred), shp, s0, s1)
     os.makedirs(args.output_dir, exist_ok=True)
     out_path = os.path.join(args.output_dir, f'predicted_{args.target_modality.lower()}.nii.gz')
-    write_nifti(out_path, vol_pred, aff, hdr)
+    stages.run('write', lambda: write(out_path, vol_pred, aff, hdr))
     print(f'[done] saved: {out_path} | shape={tuple(vol_pred.shape)} | slices={s0}..{s1}' + ('' if plan == 'auto' else f' | prec_plan={plan}'))
     if evaluation is not None:
         _score_prediction(args, evaluation, vol_pred, None, device)
     return out_path
 
 
-def _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref, evaluation=None):
+def _cached_sampler(args, gen1, gen2, device, samplers, batch):
+    """None without a cache (the callee captures its own sampler, as ever); else the cache's GraphSampler for (batch, image_size),
+    captured on first use."""
+    if samplers is None:
+        return None
+    from . import sampling as S
+    size = int(args.image_size)
+    key = (int(batch), size)
+    if key not in samplers:
+        samplers[key] = S.GraphSampler(S.Posterior_Coefficients(args, device), gen1, gen2, args, int(batch), size, size, device)
+    return samplers[key]
+
+
+def _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref, evaluation=None, on_device=False, samplers=None, write=None,
+                             stages=None):
     """--num_samples: every slice sampled N times with draws keyed by (--seed, slice, sample) (mudiff_hip.ensemble); the mean and
     the std of the [0,1]-mapped samples, resized back and re-assembled like the single prediction, go to predicted_<t>.nii.gz and
     predicted_<t>_std.nii.gz.  With `evaluation` the mean is scored, the std feeding the uncertainty block.  -> (mean path, std path)."""
@@ -387,17 +457,24 @@ def _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref, evaluation=N
     size = int(args.image_size)
     conds = upload_conds(stacks, size, device)
     print(f'[infer] {conds[0].shape[0]} slices x {args.num_samples} samples')
-    mean, std = ensemble.sample_ensemble(args, gen1, gen2, conds, args.num_samples, args.seed, batch_size=args.batch_size, map_0_1=True)
+    write = write or write_nifti
+    stages = stages or _Stages(None, device)
+    sampler = _cached_sampler(args, gen1, gen2, device, samplers, args.batch_size)
+    mean, std = stages.run('sample', lambda: ensemble.sample_ensemble(args, gen1, gen2, conds, args.num_samples, args.seed,
+                                                                      batch_size=args.batch_size, map_0_1=True, sampler=sampler))
     os.makedirs(args.output_dir, exist_ok=True)
-    paths, vols = [], []
-    for suffix, t in (('', mean), ('_std', std)):
-        if tuple(shp[:2]) != tuple(t.shape[1:]):
-            t = ops.resize_bilinear(t, shp[:2])
-        vol = reconstruct_volume_from_slices(list(t.cpu().numpy()), shp, s0, s1)
+    if tuple(shp[:2]) != tuple(mean.shape[1:]):
+        mean, std = (stages.run('assemble', lambda t=t: ops.resize_bilinear(t, shp[:2])) for t in (mean, std))
+    if on_device:
+        from . import volume_intake as VI
+        vols = stages.run('assemble', lambda: [VI.to_host_volume(v) for v in VI.assemble(mean, shp, s0, s1, std)])
+    else:
+        vols = [reconstruct_volume_from_slices(list(t.cpu().numpy()), shp, s0, s1) for t in (mean, std)]
+    paths = []
+    for suffix, vol in (('', vols[0]), ('_std', vols[1])):
         path = os.path.join(args.output_dir, f'predicted_{args.target_modality.lower()}{suffix}.nii.gz')
-        write_nifti(path, vol, aff, hdr)
+        stages.run('write', lambda: write(path, vol, aff, hdr))
         paths.append(path)
-        vols.append(vol)
     print(f'[done] saved: {paths[0]} and {paths[1]} | shape={tuple(shp)} | slices={s0}..{s1} | {args.num_samples} samples per slice' +
           ('' if effective_prec_plan(args) == 'auto' else f' | prec_plan={effective_prec_plan(args)}'))      # (the default plan: the line as it was)
     if evaluation is not None:
@@ -405,12 +482,9 @@ def _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref, evaluation=N
     return tuple(paths)
 
 
-def build_argparser(argv=None):
-    """Flags and defaults of the reference parser (:302-357; like it, returns the PARSED namespace), plus --centered (which
-    the generators read and the reference parser forgot), --batch_size, --resize_back, --calibrate / --calibrate_threshold
-    (mudiff_hip.precision; the record goes to <output_dir>/prec_calibration.json), --num_samples (ensembles) and --gt_volume /
-    --eval_mask (scoring of the written prediction, mudiff_hip.volume_metrics)."""
-    p = argparse.ArgumentParser('MU-Diff volume prediction (MI355X)')
+def make_parser(prog='MU-Diff volume prediction (MI355X)'):
+    """The volume pipeline's parser, unparsed (mudiff_hip.cohort adds its own flags to it; finish_args checks the result)."""
+    p = argparse.ArgumentParser(prog)
     for m in ('t1ce', 't1', 't2', 'flair'):
         p.add_argument(f'--input_{m}', type=str, help=f'Path to {m.upper()} NIfTI')
     p.add_argument('--target_modality', type=str, required=True, choices=['T1CE', 'FLAIR', 'T2', 'T1'])
@@ -459,9 +533,17 @@ def build_argparser(argv=None):
                         'region, mudiff_hip.volume_metrics) and write metrics_<t>.json next to it')
     p.add_argument('--eval_mask', type=str, default=None,
                    help='label NIfTI (e.g. a BraTS segmentation; needs --gt_volume): adds the tumor (label != 0) and healthy regions')
-    from .driver import add_calibration_flags, check_prec_plan_flags
+    p.add_argument('--device_intake', action='store_true',
+                   help='normalise, slice and re-assemble the volumes on the GPU (mudiff_hip.volume_intake): the same files, bit for '
+                        'bit, without the numpy passes over each volume')
+    from .driver import add_calibration_flags
     add_calibration_flags(p)                # (also --prec_plan)
-    args = p.parse_args(argv)
+    return p
+
+
+def finish_args(p, args):
+    """The checks that follow parsing (p.error on a bad combination) -> args."""
+    from .driver import check_prec_plan_flags
     check_prec_plan_flags(p, args)
     if args.num_samples is not None and args.num_samples < 2:
         p.error(f'--num_samples must be >= 2 (got {args.num_samples})')
@@ -470,5 +552,16 @@ def build_argparser(argv=None):
     return args
 
 
+def build_argparser(argv=None):
+    """Flags and defaults of the reference parser (:302-357; like it, returns the PARSED namespace), plus --centered (which
+    the generators read and the reference parser forgot), --batch_size, --resize_back, --calibrate / --calibrate_threshold
+    (mudiff_hip.precision; the record goes to <output_dir>/prec_calibration.json), --num_samples (ensembles), --gt_volume /
+    --eval_mask (scoring of the written prediction, mudiff_hip.volume_metrics) and --device_intake (mudiff_hip.volume_intake)."""
+    p = make_parser()
+    return finish_args(p, p.parse_args(argv))
+
+
 if __name__ == '__main__':
-    predict_volume(build_argparser())
+    # run the package's copy of this module: volume_intake imports it by name, and NiftiHeader must be one class for both
+    from mudiff_hip import volume as _volume
+    _volume.predict_volume(_volume.build_argparser())
