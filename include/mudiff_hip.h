@@ -356,6 +356,10 @@ int mud_ensemble_stats(const float* samples, int n, int N, int64_t hw, float sca
  * mud_volume_slab_normalise: out[i][x][y] (fp32 [s1 - s0 + 1][X][Y]) = clip((v - lo) / den, 0, 1) * 2 - 1 of the voxel (x, y, s0 + i),
  *   every step in fp32 and rounded once, the division correctly rounded; NaN stays NaN.  den is hi - lo as the host forms it (fp32).
  *   With `degenerate` != 0 (no selected voxels, or a flat volume) the slab is zeros.  Needs 0 <= s0 <= s1 < Z.
+ * mud_volume_slab_zscore: the same slab under the training normalisation (--norm zscore): out[i][x][y] = clamp((v - mean) / std, -3, 3) / 3,
+ *   every step in fp32 and rounded once, both divisions correctly rounded (the last one is a division by 3, not a product with 1 / 3);
+ *   NaN stays NaN.  mean / std: the fp32 moments of the selected voxels as the host forms them (volume_intake.zscore_moments; 0 / 1 for
+ *   no selected voxels, std 1 for a flat volume); std must not be 0.  Needs 0 <= s0 <= s1 < Z.
  * mud_volume_assemble: planes [s1 - s0 + 1][X][Y] (fp32) -> vol [Z][Y][X] (file order): zeros, except the planes s0..s1.  planes2 / vol2:
  *   an optional second stack (an ensemble's std) assembled the same way; both NULL or both given. */
 #define MUD_NIFTI_U1 2
@@ -377,6 +381,8 @@ int mud_volume_census(const void* vol, int datatype, int X, int Y, int Z, float 
                       mud_volume_census_record* record, void* ws, int64_t ws_bytes, void* stream);
 int mud_volume_slab_normalise(const void* vol, int datatype, int X, int Y, int Z, float slope, float inter, float lo, float den,
                               int degenerate, int s0, int s1, float* out, void* stream);
+int mud_volume_slab_zscore(const void* vol, int datatype, int X, int Y, int Z, float slope, float inter, float mean, float std, int s0,
+                           int s1, float* out, void* stream);
 int mud_volume_assemble(const float* planes, const float* planes2, int X, int Y, int Z, int s0, int s1, float* vol, float* vol2,
                         void* stream);
 

@@ -1,5 +1,5 @@
 // On-device NIfTI intake and re-assembly of the volume pipeline (include/mudiff_hip.h: mud_volume_census, mud_volume_slab_normalise,
-// mud_volume_assemble; mudiff_hip.volume_intake).
+// mud_volume_slab_zscore, mud_volume_assemble; mudiff_hip.volume_intake).
 //
 // A volume arrives exactly as the file stores it: x fastest ([Z][Y][X] in C terms), in the file's datatype, with scl_slope / scl_inter
 // still to be applied.  Three things happen to it on the device:
@@ -8,7 +8,8 @@
 //    four histogram passes (LDS-privatised, one read of the volume per pass serving every target rank), then one gathering pass for
 //    the few keys strictly between a window's end keys.  Counts are integers: the result does not depend on the order of the atomics.
 //  - slab normalise: clip((v - lo) / den, 0, 1) * 2 - 1 of the planes s0..s1 in fp32, each step rounded once, written as [n][X][Y]
-//    (the transposed plane the sampler takes) through an LDS tile so that reads and writes are both coalesced;
+//    (the transposed plane the sampler takes) through an LDS tile so that reads and writes are both coalesced; slab z-score
+//    (--norm zscore) is the same tile with clamp((v - mean) / std, -3, 3) / 3, the moments coming from the host;
 //  - assemble: the inverse transpose of predicted [n][X][Y] planes into a zero-filled volume in file order.
 // DESIGN.md section 5.10 has the definitions and why they equal the host's results bit for bit.
 #include "mud_common.h"
@@ -352,16 +353,18 @@ __device__ __forceinline__ float vi_normalise(float v, float lo, float den) {
   return t - 1.0f;
 }
 
-template <typename T>
-__global__ __launch_bounds__(VI_THREADS) void k_vi_slab(const T* __restrict__ vol, int X, int Y, int s0, int scaled, double slope, double inter,
-                                                        float lo, float den, int degenerate, float* __restrict__ out) {
+// the tile both slab kernels share: f(value) of the 64 x 64 voxels at (x0, y0) of stored plane s0 + i goes through LDS, so that the
+// reads run along x and the writes of out[i][x][y] along y (row stride 65 words: a column read touches 64 different banks)
+template <typename T, typename F>
+__device__ __forceinline__ void vi_slab_tile(const T* __restrict__ vol, int X, int Y, int s0, int scaled, double slope, double inter,
+                                             float* __restrict__ out, F f) {
   __shared__ float tile[VI_TILE][VI_TILE + 1];
   const int x0 = blockIdx.x * VI_TILE, y0 = blockIdx.y * VI_TILE, i = blockIdx.z;
   const int lx = threadIdx.x & (VI_TILE - 1), r0 = threadIdx.x / VI_TILE;
   const T* __restrict__ src = vol + (int64_t)(s0 + i) * X * Y;
   for (int r = r0; r < VI_TILE; r += VI_THREADS / VI_TILE) {                 // row r of the tile: y = y0 + r, lanes along x
     const int x = x0 + lx, y = y0 + r;
-    if (x < X && y < Y) tile[r][lx] = degenerate ? 0.0f : vi_normalise(vi_value<T>(src[(int64_t)y * X + x], scaled, slope, inter), lo, den);
+    if (x < X && y < Y) tile[r][lx] = f(vi_value<T>(src[(int64_t)y * X + x], scaled, slope, inter));
   }
   __syncthreads();
   float* __restrict__ dst = out + (int64_t)i * X * Y;
@@ -369,6 +372,12 @@ __global__ __launch_bounds__(VI_THREADS) void k_vi_slab(const T* __restrict__ vo
     const int x = x0 + r, y = y0 + lx;
     if (x < X && y < Y) dst[(int64_t)x * Y + y] = tile[lx][r];
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(VI_THREADS) void k_vi_slab(const T* __restrict__ vol, int X, int Y, int s0, int scaled, double slope, double inter,
+                                                        float lo, float den, int degenerate, float* __restrict__ out) {
+  vi_slab_tile<T>(vol, X, Y, s0, scaled, slope, inter, out, [=](float v) { return degenerate ? 0.0f : vi_normalise(v, lo, den); });
 }
 
 extern "C" int mud_volume_slab_normalise(const void* vol, int datatype, int X, int Y, int Z, float slope, float inter, float lo, float den,
@@ -383,6 +392,36 @@ extern "C" int mud_volume_slab_normalise(const void* vol, int datatype, int X, i
   VI_DISPATCH(datatype, hipLaunchKernelGGL(k_vi_slab<T>, grid, dim3(VI_THREADS), 0, (hipStream_t)stream, (const T*)vol, X, Y, s0, scaled,
                                            (double)slope, (double)inter, lo, den, degenerate, out));
   MUD_CHECK_LAUNCH("mud_volume_slab_normalise");
+  return MUD_OK;
+}
+
+// ---- slab z-score: the training normalisation, clamp((v - mean) / std, -3, 3) / 3 ------------------------------------------------------
+__device__ __forceinline__ float vi_zscore(float v, float mean, float std) {
+#pragma clang fp contract(off)
+  float t = v - mean;
+  t = t / std;                                     // correctly rounded fp32 division
+  t = t != t ? t : fminf(fmaxf(t, -3.0f), 3.0f);   // torch.clamp keeps a NaN
+  return t / 3.0f;                                 // a division, like torch on the CPU: x * (1 / 3) rounds differently
+}
+
+template <typename T>
+__global__ __launch_bounds__(VI_THREADS) void k_vi_slab_zscore(const T* __restrict__ vol, int X, int Y, int s0, int scaled, double slope,
+                                                               double inter, float mean, float std, float* __restrict__ out) {
+  vi_slab_tile<T>(vol, X, Y, s0, scaled, slope, inter, out, [=](float v) { return vi_zscore(v, mean, std); });
+}
+
+extern "C" int mud_volume_slab_zscore(const void* vol, int datatype, int X, int Y, int Z, float slope, float inter, float mean, float std,
+                                      int s0, int s1, float* out, void* stream) {
+  if (int e = vi_check_volume("mud_volume_slab_zscore", vol, datatype, X, Y, Z)) return e;
+  MUD_REQUIRE(s0 >= 0 && s1 >= s0 && s1 < Z, "mud_volume_slab_zscore: the slab %d..%d is not inside the %d planes", s0, s1, Z);
+  MUD_REQUIRE(out != nullptr, "mud_volume_slab_zscore: null pointer");
+  MUD_REQUIRE(std != 0.0f, "mud_volume_slab_zscore: std must not be 0 (a flat volume passes 1)");
+  const dim3 grid((unsigned)mud_cdiv(X, VI_TILE), (unsigned)mud_cdiv(Y, VI_TILE), (unsigned)(s1 - s0 + 1));
+  MUD_REQUIRE(grid.y <= 65535 && grid.z <= 65535, "mud_volume_slab_zscore: the volume is too large");
+  const int scaled = vi_scaled(slope, inter);
+  VI_DISPATCH(datatype, hipLaunchKernelGGL(k_vi_slab_zscore<T>, grid, dim3(VI_THREADS), 0, (hipStream_t)stream, (const T*)vol, X, Y, s0, scaled,
+                                           (double)slope, (double)inter, mean, std, out));
+  MUD_CHECK_LAUNCH("mud_volume_slab_zscore");
   return MUD_OK;
 }
 

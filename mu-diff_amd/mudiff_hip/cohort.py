@@ -16,7 +16,8 @@ and skipped; the run goes on and exits non-zero at the end.  A GPU error is not 
 
 Outputs: <output_dir>/<id>/predicted_<t>.nii.gz (plus _std and metrics_<t>.json when applicable) and <output_dir>/cohort_<t>.json: the
 per-subject rows, per region and metric the mean, the population standard deviation (ddof = 0) and the subject count, and the seconds
-of every stage summed over the cohort.
+of every stage summed over the cohort.  With --norm zscore the moments of every volume are computed on the
+prefetch thread, the [done] lines end in ` | norm=zscore`, and the reports carry "norm": "zscore" (a default run's are unchanged).
 """
 from __future__ import annotations
 
@@ -114,9 +115,10 @@ def format_lines(agg):
 # ---------------------------------------------------------------------------------------------------
 # one subject
 # ---------------------------------------------------------------------------------------------------
-def _read_subject(subject, needed, score):
+def _read_subject(subject, needed, score, norm='percentile'):
     """(prefetch thread) The subject's three condition volumes as stored (volume_intake.read_nifti_raw) and, with `score`, the
-    evaluation inputs of volume.load_eval_inputs.  -> (raws, evaluation inputs or None, seconds)."""
+    evaluation inputs of volume.load_eval_inputs.  With norm='zscore' every volume's moments are computed here too, next to the read
+    (RawVolume.moments; their seconds in RawVolume.moments_s).  -> (raws, evaluation inputs or None, seconds)."""
     from . import volume as V
     from . import volume_intake as VI
     t0 = time.perf_counter()
@@ -124,6 +126,11 @@ def _read_subject(subject, needed, score):
         if not subject.inputs.get(m):
             raise ValueError(f'no {m} volume given')
     raws = [VI.read_nifti_raw(subject.inputs[m]) for m in needed]
+    if norm == 'zscore':
+        for r in raws:
+            t1 = time.perf_counter()
+            r.moments = VI.zscore_moments(r)
+            r.moments_s = time.perf_counter() - t1
     ev = None
     if score:
         if not subject.gt:
@@ -153,7 +160,10 @@ def run(args, subjects, predict=None):
     target = args.target_modality
     needed = V.MODALITY_ORDERS[target]
     plan = effective_prec_plan(args)
+    norm = getattr(args, 'norm', 'percentile')
     timing = dict(read=0.0, intake=0.0, sample=0.0, assemble=0.0, write=0.0, write_wait=0.0, score=0.0)
+    if norm != 'percentile':                 # (a default run's report keeps the keys it had)
+        timing.update(moments=0.0, read_wait=0.0)
     rows, failures, pending = [], [], collections.deque()
     t_wall = time.perf_counter()
     device = None
@@ -181,7 +191,7 @@ def run(args, subjects, predict=None):
                 s = next(todo, None)
                 if s is None:
                     return
-                reads.append((s, pool.submit(_read_subject, s, needed, args.score)))
+                reads.append((s, pool.submit(_read_subject, s, needed, args.score, norm)))
 
         prefetch()
         calibrated = False
@@ -190,8 +200,12 @@ def run(args, subjects, predict=None):
                 subject, fut = reads.popleft()
                 prefetch()                                         # subject i+1 is read while subject i runs
                 try:
+                    t0 = time.perf_counter()
                     raws, ev, t_read = fut.result()
                     timing['read'] += t_read
+                    if norm != 'percentile':
+                        timing['read_wait'] += time.perf_counter() - t0      # the main thread waiting for the read and the moments
+                        timing['moments'] += sum(getattr(r, 'moments_s', 0.0) for r in raws)
                     sargs = copy.copy(args)
                     sargs.output_dir = os.path.join(args.output_dir, subject.id)
                     evaluation = None
@@ -212,7 +226,7 @@ def run(args, subjects, predict=None):
                                 raise ValueError(f'All input volumes must share shape. Got {r.shape} vs {raws[0].shape} for {m}')
                     else:
                         conds, *ref = VI.load_conditions([subject.inputs[m] for m in needed], args.slice_half_range, args.image_size,
-                                                         device, raws=raws)
+                                                         device, raws=raws, norm=norm)
                         torch.cuda.synchronize(device)
                     timing['intake'] += time.perf_counter() - t0
 
@@ -241,7 +255,7 @@ def run(args, subjects, predict=None):
         pool.shutdown(wait=True, cancel_futures=True)
     timing['wall'] = time.perf_counter() - t_wall
     agg = aggregate(rows)
-    report = dict(target=target, subjects=rows, failed=[dict(id=i, error=e) for i, e in failures], aggregate=agg,
+    report = dict(target=target, **({} if norm == 'percentile' else dict(norm=norm)), subjects=rows, failed=[dict(id=i, error=e) for i, e in failures], aggregate=agg,
                   std_definition='population standard deviation over subjects (ddof = 0)', timing=timing)
     os.makedirs(args.output_dir, exist_ok=True)
     path = os.path.join(args.output_dir, f'cohort_{target.lower()}.json')

@@ -51,6 +51,41 @@ def robust_minmax_to_minus1_1(vol, mask=None, pmin=1.0, pmax=99.0):
     return np.clip((data - lo) / (hi - lo), 0.0, 1.0) * 2.0 - 1.0
 
 
+NORMS = ('percentile', 'zscore')      # --norm: 'percentile' is the reference's volume entry point, 'zscore' what its training sees
+
+
+def zscore_moments_f32(data):
+    """(mean, std) as np.float32 of the non-zero voxels of an fp32 [X,Y,Z] array: the reference's tools/pre_process.py:53-61 with
+    numpy's own fp32 reductions over data[data != 0] (C order).  No such voxels -> (0, 1); a flat volume -> std 1."""
+    vals = data[data != 0]
+    if vals.size == 0:
+        return np.float32(0.0), np.float32(1.0)
+    mean, s = vals.mean(), vals.std()
+    return np.float32(mean), np.float32(s if s != 0 else 1.0)
+
+
+def zscore_to_minus1_1(vol):
+    """The training normalisation: the reference's tools/pre_process.py:46-67 (z-score over the non-zero
+    voxels of the whole volume) followed by dataset/dataset_brats.py:83 (clamp to +-3 sigma, divided by 3), all in fp32.  A NaN voxel
+    makes both moments, and with them the whole volume, NaN."""
+    data = np.asarray(vol).astype(np.float32, copy=False)
+    mean, std = zscore_moments_f32(data)
+    z = (data - mean) / std
+    return np.clip(z, -3.0, 3.0) / np.float32(3.0)
+
+
+def normalise_volume(vol, norm='percentile'):
+    """--norm: robust_minmax_to_minus1_1 ('percentile', the default) or zscore_to_minus1_1 ('zscore')."""
+    if norm not in NORMS:
+        raise ValueError(f'norm must be one of {NORMS}, got {norm!r}')
+    return zscore_to_minus1_1(vol) if norm == 'zscore' else robust_minmax_to_minus1_1(vol)
+
+
+def norm_suffix(norm):
+    """What a log line gains under a non-default --norm (nothing by default: the lines as they were)."""
+    return '' if norm == 'percentile' else f' | norm={norm}'
+
+
 def extract_center_slices(volume, half_range):
     """Reference :159-168 -> (list of [X,Y] slices, first index, last index)."""
     z = volume.shape[2]
@@ -161,10 +196,10 @@ def write_nifti(path, vol, affine, header=None):
         f.write(payload)
 
 
-def load_and_preprocess_volume(file_path, slice_half_range):
-    """Reference :183-191 -> (slices, shape, affine, header, first, last)."""
+def load_and_preprocess_volume(file_path, slice_half_range, norm='percentile'):
+    """Reference :183-191 -> (slices, shape, affine, header, first, last).  `norm`: --norm."""
     vol, affine, header = read_nifti(file_path)
-    slices, s0, s1 = extract_center_slices(robust_minmax_to_minus1_1(vol), slice_half_range)
+    slices, s0, s1 = extract_center_slices(normalise_volume(vol, norm), slice_half_range)
     return slices, vol.shape, affine, header, s0, s1
 
 
@@ -325,7 +360,7 @@ def _score_prediction(args, evaluation, vol, std_vol, device):
     """Scores of the prediction exactly as written -> printed lines and <output_dir>/metrics_<target>.json (its path)."""
     from . import volume_metrics as VM
     gt, label = evaluation
-    rep = VM.score_arrays(vol, gt, label, std_vol, args.slice_half_range, device)
+    rep = VM.score_arrays(vol, gt, label, std_vol, args.slice_half_range, device, norm=getattr(args, 'norm', 'percentile'))
     for ln in VM.format_lines(rep):
         print(ln)
     path = VM.write_json(rep, os.path.join(args.output_dir, f'metrics_{args.target_modality.lower()}.json'))
@@ -348,14 +383,16 @@ def _predict_volume(args, plan, evaluation=None):
     torch.cuda.set_device(args.gpu_chose)
     device = torch.device(f'cuda:{args.gpu_chose}')
     gen1, gen2 = load_generators(args, device)
+    norm = getattr(args, 'norm', 'percentile')
 
     if getattr(args, 'device_intake', False):
         from . import volume_intake as VI
-        stacks, *ref = VI.load_conditions([path for _, path in _needed_inputs(args)], args.slice_half_range, args.image_size, device)
+        stacks, *ref = VI.load_conditions([path for _, path in _needed_inputs(args)], args.slice_half_range, args.image_size, device,
+                                          norm=norm)
         return predict_from_conditions(args, plan, evaluation, gen1, gen2, device, stacks, tuple(ref), on_device=True)
     stacks, ref = [], None
     for m, path in _needed_inputs(args):
-        slices, shp, aff, hdr, s0, s1 = load_and_preprocess_volume(path, args.slice_half_range)
+        slices, shp, aff, hdr, s0, s1 = load_and_preprocess_volume(path, args.slice_half_range, norm)
         if ref is None:
             ref = (shp, aff, hdr, s0, s1)
         elif shp != ref[0]:
@@ -427,7 +464,8 @@ def predict_from_conditions(args, plan, evaluation, gen1, gen2, device, stacks, 
     os.makedirs(args.output_dir, exist_ok=True)
     out_path = os.path.join(args.output_dir, f'predicted_{args.target_modality.lower()}.nii.gz')
     stages.run('write', lambda: write(out_path, vol_pred, aff, hdr))
-    print(f'[done] saved: {out_path} | shape={tuple(vol_pred.shape)} | slices={s0}..{s1}' + ('' if plan == 'auto' else f' | prec_plan={plan}'))
+    print(f'[done] saved: {out_path} | shape={tuple(vol_pred.shape)} | slices={s0}..{s1}' + ('' if plan == 'auto' else f' | prec_plan={plan}') +
+          norm_suffix(getattr(args, 'norm', 'percentile')))
     if evaluation is not None:
         _score_prediction(args, evaluation, vol_pred, None, device)
     return out_path
@@ -476,7 +514,8 @@ def _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref, evaluation=N
         stages.run('write', lambda: write(path, vol, aff, hdr))
         paths.append(path)
     print(f'[done] saved: {paths[0]} and {paths[1]} | shape={tuple(shp)} | slices={s0}..{s1} | {args.num_samples} samples per slice' +
-          ('' if effective_prec_plan(args) == 'auto' else f' | prec_plan={effective_prec_plan(args)}'))      # (the default plan: the line as it was)
+          ('' if effective_prec_plan(args) == 'auto' else f' | prec_plan={effective_prec_plan(args)}') +      # (the default plan: the line as it was)
+          norm_suffix(getattr(args, 'norm', 'percentile')))
     if evaluation is not None:
         _score_prediction(args, evaluation, vols[0], vols[1], device)
     return tuple(paths)
@@ -536,6 +575,10 @@ def make_parser(prog='MU-Diff volume prediction (MI355X)'):
     p.add_argument('--device_intake', action='store_true',
                    help='normalise, slice and re-assemble the volumes on the GPU (mudiff_hip.volume_intake): the same files, bit for '
                         'bit, without the numpy passes over each volume')
+    p.add_argument('--norm', type=str, default='percentile', choices=list(NORMS),
+                   help="how the input volumes (and --gt_volume) are mapped to [-1, 1]: 'percentile' = 1st / 99th percentile min-max "
+                        "(the reference's volume entry point); 'zscore' = z-score over the non-zero voxels, clamped to +-3 sigma and "
+                        "divided by 3 (what the reference's training and 2D test data see: use it with such a checkpoint)")
     from .driver import add_calibration_flags
     add_calibration_flags(p)                # (also --prec_plan)
     return p
@@ -556,7 +599,8 @@ def build_argparser(argv=None):
     """Flags and defaults of the reference parser (:302-357; like it, returns the PARSED namespace), plus --centered (which
     the generators read and the reference parser forgot), --batch_size, --resize_back, --calibrate / --calibrate_threshold
     (mudiff_hip.precision; the record goes to <output_dir>/prec_calibration.json), --num_samples (ensembles), --gt_volume /
-    --eval_mask (scoring of the written prediction, mudiff_hip.volume_metrics) and --device_intake (mudiff_hip.volume_intake)."""
+    --eval_mask (scoring of the written prediction, mudiff_hip.volume_metrics), --device_intake (mudiff_hip.volume_intake) and --norm
+    (the training normalisation)."""
     p = make_parser()
     return finish_args(p, p.parse_args(argv))
 

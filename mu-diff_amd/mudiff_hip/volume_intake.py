@@ -13,6 +13,9 @@ an F-contiguous [X,Y,Z] array (volume.write_nifti's tobytes(order='F') is then a
 
 Every result equals the host path's bit for bit: the census values are order statistics, the thresholds are np.percentile's own
 output, and the normalisation rounds each fp32 step once like numpy.  A volume that holds NaN or inf takes the host path (with a warning).
+
+With norm='zscore' (--norm zscore) there is no census: the two moments come from numpy on the host
+(zscore_moments, the reference's own calls on the stored array) and slab_zscore does the rest on the device, non-finite voxels included.
 """
 from __future__ import annotations
 
@@ -41,6 +44,7 @@ class RawVolume:
         self.data, self.code, self.endian = data, int(code), endian
         self.slope, self.inter = float(slope), float(inter)
         self.shape, self.affine, self.header = tuple(int(v) for v in shape), affine, header
+        self.moments = None                  # zscore_moments(self), when a prefetch thread has computed them already
 
     @property
     def scaled(self):
@@ -196,6 +200,32 @@ def slab_normalise(dev_raw, code, shape, slope, inter, lo, den, degenerate, s0, 
     return out
 
 
+def zscore_moments(raw):
+    """(mean, std) as np.float32 of a RawVolume's non-zero voxels: volume.zscore_moments_f32 (numpy's fp32 reductions, the calls the
+    reference makes) on the fp32 values the host path sees, read_nifti(...).astype(float32).  Host work, about 0.1 s for
+    240 x 240 x 155 int16 voxels; a cohort does it on the prefetch thread."""
+    from .volume import zscore_moments_f32
+    stored = np.ascontiguousarray(np.asarray(raw.data).reshape(raw.shape, order='F'))      # C order first, in the small stored dtype:
+    if raw.scaled:                                                                         # the gather below then reads memory in order
+        data = (stored.astype(np.float64) * raw.slope + raw.inter).astype(np.float32)
+    else:
+        data = stored.astype(np.float32)          # = float32(float64(stored)): one rounding either way
+    return zscore_moments_f32(data)
+
+
+def slab_zscore(dev_raw, code, shape, slope, inter, mean, std, s0, s1):
+    """mud_volume_slab_zscore -> device fp32 [s1 - s0 + 1, 1, X, Y]: clamp((v - mean) / std, -3, 3) / 3 of the planes s0..s1."""
+    require_gpu(dev_raw)
+    X, Y, Z = (int(v) for v in shape)
+    if not 0 <= s0 <= s1 < Z:
+        raise MudiffHipError(f'slab_zscore: the slab {s0}..{s1} is not inside the {Z} planes')
+    out = torch.empty(s1 - s0 + 1, 1, X, Y, device=dev_raw.device, dtype=torch.float32)
+    from . import ops
+    ops._launch('volume_slab_zscore', dev_raw.device, load().mud_volume_slab_zscore, ptr(dev_raw), int(code), X, Y, Z, float(slope),
+                float(inter), float(mean), float(std), int(s0), int(s1), ptr(out), ops.STREAM)
+    return out
+
+
 def assemble(planes, shape, s0, s1, planes2=None):
     """Device fp32 planes [n, X, Y] (n = s1 - s0 + 1; optionally a second stack) -> device fp32 volume(s) [Z, Y, X]: zeros with the
     planes at s0..s1 (volume.reconstruct_volume_from_slices, in file order).  -> tensor, or a pair with `planes2`."""
@@ -245,14 +275,20 @@ def _host_condition(raw, s0, s1, device):
     return torch.from_numpy(planes).to(device)[:, None]
 
 
-def condition_from_raw(raw, half_range, image_size, device, pmin=1.0, pmax=99.0, name='volume'):
-    """One RawVolume -> its condition tensor [n, 1, S, S] on the device: upload, census, thresholds, slab normalise, resize."""
-    from . import ops
+def condition_from_raw(raw, half_range, image_size, device, pmin=1.0, pmax=99.0, name='volume', norm='percentile'):
+    """One RawVolume -> its condition tensor [n, 1, S, S] on the device: upload, census, thresholds, slab normalise, resize; with
+    norm='zscore': upload, slab z-score with the host's moments (raw.moments when set, else computed here), resize."""
+    from .volume import NORMS
+    if norm not in NORMS:
+        raise ValueError(f'norm must be one of {NORMS}, got {norm!r}')
     if len(raw.shape) != 3:
         raise ValueError(f'{name}: expected a 3D volume, got shape {raw.shape}')
     s0, s1 = slab_range(raw.shape[2], half_range)
     dev_raw = upload(raw, device)
     slope, inter = (raw.slope, raw.inter) if raw.scaled else (1.0, 0.0)
+    if norm == 'zscore':
+        mean, std = raw.moments if raw.moments is not None else zscore_moments(raw)
+        return _resized(slab_zscore(dev_raw, raw.code, raw.shape, slope, inter, mean, std, s0, s1), image_size)
     rec_dev = census(dev_raw, raw.code, raw.shape, slope, inter, (pmin / 100.0, pmax / 100.0))
     rec = CensusRecord.from_bytes(rec_dev.cpu().numpy().tobytes(), 2)
     try:
@@ -261,15 +297,20 @@ def condition_from_raw(raw, half_range, image_size, device, pmin=1.0, pmax=99.0,
     except ValueError as e:
         print(f'[intake] warning: {name}: {e}; normalised on the host')
         t = _host_condition(raw, s0, s1, device)
+    return _resized(t, image_size)
+
+
+def _resized(t, image_size):
+    from . import ops
     size = int(image_size)
     if tuple(t.shape[-2:]) != (size, size):
         t = ops.resize_bilinear(t, (size, size))
     return t.contiguous()
 
 
-def load_conditions(paths, half_range, image_size, device, raws=None):
+def load_conditions(paths, half_range, image_size, device, raws=None, norm='percentile'):
     """The condition volumes of one subject (paths in MODALITY_ORDERS order; `raws`: the RawVolumes when a prefetch thread has read them
-    already) -> ([three device tensors [n,1,S,S]], shape, affine, header, s0, s1) with the geometry of the first volume.  ValueError when
+    already; `norm`: --norm) -> ([three device tensors [n,1,S,S]], shape, affine, header, s0, s1) with the geometry of the first volume.  ValueError when
     the volumes differ in shape."""
     conds, ref = [], None
     for i, path in enumerate(paths):
@@ -278,6 +319,6 @@ def load_conditions(paths, half_range, image_size, device, raws=None):
             ref = raw
         elif raw.shape != ref.shape:
             raise ValueError(f'All input volumes must share shape. Got {raw.shape} vs {ref.shape} for {path}')
-        conds.append(condition_from_raw(raw, half_range, image_size, device, name=path))
+        conds.append(condition_from_raw(raw, half_range, image_size, device, name=path, norm=norm))
     s0, s1 = slab_range(ref.shape[2], half_range)
     return conds, ref.shape, ref.affine, ref.header, s0, s1

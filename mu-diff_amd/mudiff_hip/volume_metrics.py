@@ -4,6 +4,7 @@
 Definitions (every score is taken on the slab: the planes s0..s1 that volume.extract_center_slices(z, slice_half_range) selects):
 - prediction: the fp32 values in [0, 1] as written to predicted_<t>.nii.gz;
 - ground truth: robust_minmax_to_minus1_1 of the raw GT volume (whole-volume percentiles, like the inputs), then ops.to_range_0_1;
+  with norm='zscore' (--norm zscore) volume.zscore_to_minus1_1 instead, like the inputs of that mode; the report then has "norm": "zscore";
 - regions (bit k of a uint8 per voxel): slab = every voxel, brain = raw GT != 0, and with a label volume tumor = label != 0 and
   healthy = brain and not tumor;
 - SSIM3D: skimage's structural_similarity carried to three axes (uniform 7x7x7 window, sample covariance 343/342, K1 = 0.01,
@@ -207,24 +208,26 @@ def score_volume(pred, gt, region, std=None, names=REGIONS, first_plane=0):
     return rep
 
 
-def score_arrays(pred_vol, gt_raw, label=None, std_vol=None, slice_half_range=80, device='cuda'):
+def score_arrays(pred_vol, gt_raw, label=None, std_vol=None, slice_half_range=80, device='cuda', norm='percentile'):
     """Scores of a prediction as written (host [X, Y, Z] array in [0, 1]) against the raw GT volume, with an optional label volume
-    (regions tumor / healthy) and std volume.  -> score_volume's report plus shape and slab [s0, s1]."""
+    (regions tumor / healthy) and std volume.  `norm`: how the GT is mapped to [-1, 1] (volume.NORMS; the mode the prediction's inputs
+    were normalised with).  -> score_volume's report plus shape and slab [s0, s1], and the key norm when it is not the default."""
     from . import ops
-    from .volume import robust_minmax_to_minus1_1
+    from .volume import normalise_volume
     s0, s1 = check_shapes(np.shape(pred_vol), np.shape(gt_raw), None if label is None else np.shape(label), slice_half_range,
                           None if std_vol is None else np.shape(std_vol))
     device = torch.device(device)
-    gt_norm = robust_minmax_to_minus1_1(gt_raw)
+    gt_norm = normalise_volume(gt_raw, norm)
     gt = ops.to_range_0_1(torch.from_numpy(slab_planes(gt_norm, s0, s1)).to(device))
     pred = torch.from_numpy(slab_planes(pred_vol, s0, s1)).to(device)
     std = None if std_vol is None else torch.from_numpy(slab_planes(std_vol, s0, s1)).to(device)
     m, names = region_mask(slab_planes(gt_raw, s0, s1, np.float64), None if label is None else slab_planes(label, s0, s1, np.float64))
     rep = score_volume(pred, gt, torch.from_numpy(m).to(device), std, names, first_plane=s0)
-    return dict(shape=[int(v) for v in np.shape(gt_raw)], slab=[s0, s1], **rep)
+    extra = {} if norm == 'percentile' else dict(norm=norm)
+    return dict(shape=[int(v) for v in np.shape(gt_raw)], slab=[s0, s1], **extra, **rep)
 
 
-def score_files(pred_path, gt_path, mask_path=None, std_path=None, slice_half_range=80, device='cuda'):
+def score_files(pred_path, gt_path, mask_path=None, std_path=None, slice_half_range=80, device='cuda', norm='percentile'):
     """score_arrays on NIfTI files (volume.read_nifti): the prediction, the raw GT, an optional label volume (--eval_mask, e.g. a
     BraTS segmentation) and an optional std volume.  Warns when the prediction's affine differs from the GT's."""
     from .volume import read_nifti
@@ -233,7 +236,8 @@ def score_files(pred_path, gt_path, mask_path=None, std_path=None, slice_half_ra
     label = None if mask_path is None else read_nifti(mask_path)[0]
     std = None if std_path is None else read_nifti(std_path)[0]
     warn_affine(pa, ga, pred_path, gt_path)
-    return score_arrays(pred.astype(np.float32), gt, label, None if std is None else std.astype(np.float32), slice_half_range, device)
+    return score_arrays(pred.astype(np.float32), gt, label, None if std is None else std.astype(np.float32), slice_half_range, device,
+                        norm=norm)
 
 
 def warn_affine(pred_affine, gt_affine, pred_name='the prediction', gt_name='the ground truth'):
@@ -250,6 +254,8 @@ def build_parser():
     p.add_argument('--mask', type=str, default=None, help='label volume (NIfTI, e.g. a BraTS segmentation): label != 0 is the tumor region')
     p.add_argument('--std', type=str, default=None, help="an ensemble's std volume (predicted_<t>_std.nii.gz): adds the uncertainty block")
     p.add_argument('--slice_half_range', type=int, default=80, help='the slab: the centre +- this many planes (as the volume pipeline)')
+    p.add_argument('--norm', type=str, default='percentile', choices=['percentile', 'zscore'],
+                   help="how the ground truth is mapped to [-1, 1]: the --norm the prediction was made with (mudiff_hip.volume)")
     p.add_argument('--json', type=str, default=None, help='write the full report (per-plane curves included) to this file')
     return p
 
@@ -257,7 +263,7 @@ def build_parser():
 def main(argv=None):
     args = build_parser().parse_args(argv)
     try:
-        rep = score_files(args.pred, args.gt, args.mask, args.std, args.slice_half_range)
+        rep = score_files(args.pred, args.gt, args.mask, args.std, args.slice_half_range, norm=args.norm)
     except ValueError as e:
         print(f'error: {e}', file=sys.stderr)
         return 2

@@ -9,7 +9,10 @@ integer intensities; BASELINE config 3's model (256 x 256, nf = 64, batches of 3
 profiles/cohort_bench.json (or --out): subjects/s, per-stage seconds and the GPU-busy share (sampling seconds / wall) of both, and
 whether the files of (A) and (B) are identical.  One pass each, no repetitions: the numbers are what one run of each costs.
 
-    python scripts/bench_cohort.py [--subjects 8] [--out profiles/cohort_bench.json]"""
+--norm is passed through to both (mudiff_hip.volume's flag): with `zscore` (B)'s stage table gains the prefetch
+threads' moments seconds and read_wait, the main thread's seconds waiting for a read (moments included).
+
+    python scripts/bench_cohort.py [--subjects 8] [--norm percentile] [--out profiles/cohort_bench.json]"""
 import argparse
 import gzip
 import json
@@ -107,6 +110,7 @@ class Timed:
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--subjects', type=int, default=8)
+    ap.add_argument('--norm', type=str, default='percentile', choices=list(V.NORMS))
     ap.add_argument('--out', type=str, default=os.path.join(REPO, 'profiles', 'cohort_bench.json'))
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'bench_cohort.py measures on a GPU'
@@ -114,7 +118,7 @@ def main():
         manifest, fill = make_cohort(root, a.subjects)
         make_checkpoints(root)
         model = ['--target_modality', 'T1CE', '--exp', 'bench', '--output_path', os.path.join(root, 'results'), '--num_channels_dae', '64',
-                 '--image_size', '256', '--batch_size', '32', '--resize_back']
+                 '--image_size', '256', '--batch_size', '32', '--resize_back'] + ([] if a.norm == 'percentile' else ['--norm', a.norm])
         subjects = Co.read_manifest(manifest)
 
         # (A) the parent's way
@@ -142,7 +146,7 @@ def main():
     n = len(subjects)
     out = dict(what='scripts/bench_cohort.py: per-subject volume prediction, (A) predict_volume per subject with host intake and a fresh '
                     'model and sampler each time, (B) mudiff_hip.cohort with device intake; one process, one pass each',
-               device=torch.cuda.get_device_name(0), subjects=n, shape=list(SHAPE), nonzero_fraction=fill, slices_per_subject=SHAPE[2],
+               device=torch.cuda.get_device_name(0), norm=a.norm, subjects=n, shape=list(SHAPE), nonzero_fraction=fill, slices_per_subject=SHAPE[2],
                A=dict(subjects_per_s=n / wall_a, seconds_per_subject=wall_a / n, stages_s=stages_a, gpu_busy_share=stages_a['sample'] / wall_a,
                       note='sample includes the per-subject warm-up and hipGraph capture'),
                B=dict(subjects_per_s=n / stages_b['wall'], seconds_per_subject=stages_b['wall'] / n, stages_s=stages_b,
