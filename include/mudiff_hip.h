@@ -361,7 +361,17 @@ int mud_ensemble_stats(const float* samples, int n, int N, int64_t hw, float sca
  *   NaN stays NaN.  mean / std: the fp32 moments of the selected voxels as the host forms them (volume_intake.zscore_moments; 0 / 1 for
  *   no selected voxels, std 1 for a flat volume); std must not be 0.  Needs 0 <= s0 <= s1 < Z.
  * mud_volume_assemble: planes [s1 - s0 + 1][X][Y] (fp32) -> vol [Z][Y][X] (file order): zeros, except the planes s0..s1.  planes2 / vol2:
- *   an optional second stack (an ensemble's std) assembled the same way; both NULL or both given. */
+ *   an optional second stack (an ensemble's std) assembled the same way; both NULL or both given.
+ * mud_volume_regrid (--regrid): a volume src of SX x SY x SZ stored voxels that lies on another voxel grid -> out, fp32 [Z][Y][X] in file
+ *   order on the reference grid (the first input's), ready for the entry points above as MUD_NIFTI_F4 with slope 1, inter 0.  It lifts
+ *   the reference's check that all inputs share one shape (engine/test_volume.py:262-263) for volumes whose world coordinates agree; it
+ *   does not register.  m: 12 doubles on the host, the row-major 3 x 4 matrix inv(source affine) * (reference affine) that takes a
+ *   reference voxel index (i, j, k) to a source voxel coordinate p = m * (i, j, k, 1), evaluated in fp64.
+ *   mode 0, trilinear: f = floor(p), w = p - f; out = float32 of the fp64 sum over the 8 neighbours f + {0, 1}^3 of value * weight (x
+ *   fastest), the weight being the product of w or 1 - w per axis.  A neighbour outside the source counts as 0 (zero padding: continuous
+ *   at the border); one whose weight is exactly 0 is not read, so identities and integer shifts are bit-exact, next to a NaN too.
+ *   mode 1, nearest (label volumes): the value at floor(p + 0.5) per axis, 0 outside the source.
+ *   Both sizes obey X*Y*Z < 2^31; m must be finite. */
 #define MUD_NIFTI_U1 2
 #define MUD_NIFTI_I2 4
 #define MUD_NIFTI_I4 8
@@ -385,6 +395,8 @@ int mud_volume_slab_zscore(const void* vol, int datatype, int X, int Y, int Z, f
                            int s1, float* out, void* stream);
 int mud_volume_assemble(const float* planes, const float* planes2, int X, int Y, int Z, int s0, int s1, float* vol, float* vol2,
                         void* stream);
+int mud_volume_regrid(const void* src, int datatype, int SX, int SY, int SZ, float slope, float inter, const double* m, int mode, int X,
+                      int Y, int Z, float* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,5 @@
 // On-device NIfTI intake and re-assembly of the volume pipeline (include/mudiff_hip.h: mud_volume_census, mud_volume_slab_normalise,
-// mud_volume_slab_zscore, mud_volume_assemble; mudiff_hip.volume_intake).
+// mud_volume_slab_zscore, mud_volume_assemble, mud_volume_regrid; mudiff_hip.volume_intake, mudiff_hip.volume_regrid).
 //
 // A volume arrives exactly as the file stores it: x fastest ([Z][Y][X] in C terms), in the file's datatype, with scl_slope / scl_inter
 // still to be applied.  Three things happen to it on the device:
@@ -11,6 +11,8 @@
 //    (the transposed plane the sampler takes) through an LDS tile so that reads and writes are both coalesced; slab z-score
 //    (--norm zscore) is the same tile with clamp((v - mean) / std, -3, 3) / 3, the moments coming from the host;
 //  - assemble: the inverse transpose of predicted [n][X][Y] planes into a zero-filled volume in file order.
+// In front of all that, mud_volume_regrid (--regrid) resamples a volume that lies on another voxel grid onto
+// the grid of the first input: a gather through the affines, trilinear or nearest.
 // DESIGN.md section 5.10 has the definitions and why they equal the host's results bit for bit.
 #include "mud_common.h"
 
@@ -461,5 +463,72 @@ extern "C" int mud_volume_assemble(const float* planes, const float* planes2, in
     hipLaunchKernelGGL(k_vi_assemble, grid, dim3(VI_THREADS), 0, (hipStream_t)stream, planes2, X, Y, s0, s1, vol2);
     MUD_CHECK_LAUNCH("mud_volume_assemble (second stack)");
   }
+  return MUD_OK;
+}
+
+// ---- regrid: a volume on another voxel grid -> fp32 [Z][Y][X] on the reference grid ---------------------------------------------------
+// m maps a reference voxel index (i, j, k) to a source voxel coordinate p; everything about p is fp64, so that an identity, an integer
+// shift, a flip or a dyadic scale reproduce stored values exactly and an oblique matrix places a 240-voxel axis to ~1e-13 voxels.
+struct vi_mat {
+  double m[12];
+};
+
+// one axis of p: is any neighbour inside [0, S)?  With p in (-1, S) floor(p) fits an int; a NaN or an infinite p fails the test
+__device__ __forceinline__ bool vi_axis_near(double p, int S) { return p > -1.0 && p < (double)S; }
+
+template <typename T>
+__global__ __launch_bounds__(VI_THREADS) void k_vi_regrid(const T* __restrict__ src, int SX, int SY, int SZ, int scaled, double slope,
+                                                          double inter, vi_mat M, int mode, int X, int Y, int64_t n,
+                                                          float* __restrict__ out) {
+  for (int64_t i = (int64_t)blockIdx.x * VI_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * VI_THREADS) {
+    const uint32_t l = (uint32_t)i;                          // n < 2^31 (the entry point checks it): 32-bit divisions
+    const uint32_t row = l / (uint32_t)X;
+    const double x = (double)(l - row * (uint32_t)X), y = (double)(row % (uint32_t)Y), z = (double)(row / (uint32_t)Y);
+    double p[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) p[a] = fma(M.m[4 * a], x, fma(M.m[4 * a + 1], y, fma(M.m[4 * a + 2], z, M.m[4 * a + 3])));
+    float r = 0.0f;
+    if (mode == 1) {                                         // nearest: floor(p + 0.5) per axis, 0 outside
+      const double qx = floor(p[0] + 0.5), qy = floor(p[1] + 0.5), qz = floor(p[2] + 0.5);
+      if (qx >= 0.0 && qx < (double)SX && qy >= 0.0 && qy < (double)SY && qz >= 0.0 && qz < (double)SZ)
+        r = vi_value<T>(src[((int64_t)(int)qz * SY + (int)qy) * SX + (int)qx], scaled, slope, inter);
+    } else if (vi_axis_near(p[0], SX) && vi_axis_near(p[1], SY) && vi_axis_near(p[2], SZ)) {
+      const double fx = floor(p[0]), fy = floor(p[1]), fz = floor(p[2]);
+      const double wx[2] = {1.0 - (p[0] - fx), p[0] - fx}, wy[2] = {1.0 - (p[1] - fy), p[1] - fy}, wz[2] = {1.0 - (p[2] - fz), p[2] - fz};
+      const int x0 = (int)fx, y0 = (int)fy, z0 = (int)fz;
+      double acc = 0.0;
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {                          // neighbours in file order: x fastest
+        const int dx = c & 1, dy = (c >> 1) & 1, dz = c >> 2;
+        const int xx = x0 + dx, yy = y0 + dy, zz = z0 + dz;
+        const double w = wx[dx] * wy[dy] * wz[dz];
+        // a neighbour of weight 0 is not read (an identity next to a NaN stays exact); one outside the grid counts as 0
+        if (w != 0.0 && xx >= 0 && xx < SX && yy >= 0 && yy < SY && zz >= 0 && zz < SZ)
+          acc = fma((double)vi_value<T>(src[((int64_t)zz * SY + yy) * SX + xx], scaled, slope, inter), w, acc);
+      }
+      r = (float)acc;
+    }
+    out[i] = r;
+  }
+}
+
+extern "C" int mud_volume_regrid(const void* src, int datatype, int SX, int SY, int SZ, float slope, float inter, const double* m, int mode,
+                                 int X, int Y, int Z, float* out, void* stream) {
+  if (int e = vi_check_volume("mud_volume_regrid", src, datatype, SX, SY, SZ)) return e;
+  MUD_REQUIRE(X > 0 && Y > 0 && Z > 0 && (int64_t)X * Y * Z < ((int64_t)1 << 31), "mud_volume_regrid: bad output size %d x %d x %d", X, Y, Z);
+  MUD_REQUIRE(out != nullptr && m != nullptr, "mud_volume_regrid: null pointer");
+  MUD_REQUIRE(mode == 0 || mode == 1, "mud_volume_regrid: mode %d is neither 0 (trilinear) nor 1 (nearest)", mode);
+  vi_mat M;
+  for (int i = 0; i < 12; ++i) {
+    MUD_REQUIRE(m[i] - m[i] == 0.0, "mud_volume_regrid: m[%d] = %g is not finite", i, m[i]);
+    M.m[i] = m[i];
+  }
+  const int64_t n = (int64_t)X * Y * Z;
+  int64_t blocks = mud_cdiv(n, VI_THREADS);
+  blocks = blocks > VI_MAX_BLOCKS ? VI_MAX_BLOCKS : blocks;
+  const int scaled = vi_scaled(slope, inter);
+  VI_DISPATCH(datatype, hipLaunchKernelGGL(k_vi_regrid<T>, dim3((unsigned)blocks), dim3(VI_THREADS), 0, (hipStream_t)stream, (const T*)src, SX,
+                                           SY, SZ, scaled, (double)slope, (double)inter, M, mode, X, Y, n, out));
+  MUD_CHECK_LAUNCH("mud_volume_regrid");
   return MUD_OK;
 }

@@ -144,6 +144,7 @@ _SIGNATURES = {
     'mud_volume_slab_normalise': (_I, [_P, _I, _I, _I, _I, _F, _F, _F, _F, _I, _I, _I, _P, _P]),
     'mud_volume_slab_zscore': (_I, [_P, _I, _I, _I, _I, _F, _F, _F, _F, _I, _I, _P, _P]),
     'mud_volume_assemble': (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    'mud_volume_regrid': (_I, [_P, _I, _I, _I, _I, _F, _F, C.POINTER(C.c_double), _I, _I, _I, _I, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

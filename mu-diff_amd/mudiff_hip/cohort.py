@@ -18,6 +18,8 @@ Outputs: <output_dir>/<id>/predicted_<t>.nii.gz (plus _std and metrics_<t>.json 
 per-subject rows, per region and metric the mean, the population standard deviation (ddof = 0) and the subject count, and the seconds
 of every stage summed over the cohort.  With --norm zscore the moments of every volume are computed on the
 prefetch thread, the [done] lines end in ` | norm=zscore`, and the reports carry "norm": "zscore" (a default run's are unchanged).
+With --regrid a subject's volumes, ground truth and mask included, need not share one voxel grid: what is not
+on the first input's grid is resampled onto it on the device, and the subject's [done] line names it (` | regrid=T2,gt_volume`).
 """
 from __future__ import annotations
 
@@ -115,10 +117,11 @@ def format_lines(agg):
 # ---------------------------------------------------------------------------------------------------
 # one subject
 # ---------------------------------------------------------------------------------------------------
-def _read_subject(subject, needed, score, norm='percentile'):
+def _read_subject(subject, needed, score, norm='percentile', regrid=False):
     """(prefetch thread) The subject's three condition volumes as stored (volume_intake.read_nifti_raw) and, with `score`, the
     evaluation inputs of volume.load_eval_inputs.  With norm='zscore' every volume's moments are computed here too, next to the read
-    (RawVolume.moments; their seconds in RawVolume.moments_s).  -> (raws, evaluation inputs or None, seconds)."""
+    (RawVolume.moments; their seconds in RawVolume.moments_s).  With `regrid` (--regrid) the evaluation inputs stay as stored, geometry
+    included: the main thread puts them on the first input's grid.  -> (raws, evaluation inputs or None, seconds)."""
     from . import volume as V
     from . import volume_intake as VI
     t0 = time.perf_counter()
@@ -135,9 +138,12 @@ def _read_subject(subject, needed, score, norm='percentile'):
     if score:
         if not subject.gt:
             raise ValueError('--score needs a ground-truth volume (the manifest\'s gt column)')
-        gt, gt_aff, _ = V.read_nifti(subject.gt)
-        label = V.read_nifti(subject.mask)[0] if subject.mask else None
-        ev = (gt, label, gt_aff)
+        if regrid:
+            ev = (VI.read_nifti_raw(subject.gt), VI.read_nifti_raw(subject.mask) if subject.mask else None, None)
+        else:
+            gt, gt_aff, _ = V.read_nifti(subject.gt)
+            label = V.read_nifti(subject.mask)[0] if subject.mask else None
+            ev = (gt, label, gt_aff)
     return raws, ev, time.perf_counter() - t0
 
 
@@ -161,6 +167,7 @@ def run(args, subjects, predict=None):
     needed = V.MODALITY_ORDERS[target]
     plan = effective_prec_plan(args)
     norm = getattr(args, 'norm', 'percentile')
+    regrid = getattr(args, 'regrid', False)
     timing = dict(read=0.0, intake=0.0, sample=0.0, assemble=0.0, write=0.0, write_wait=0.0, score=0.0)
     if norm != 'percentile':                 # (a default run's report keeps the keys it had)
         timing.update(moments=0.0, read_wait=0.0)
@@ -191,7 +198,7 @@ def run(args, subjects, predict=None):
                 s = next(todo, None)
                 if s is None:
                     return
-                reads.append((s, pool.submit(_read_subject, s, needed, args.score, norm)))
+                reads.append((s, pool.submit(_read_subject, s, needed, args.score, norm, regrid)))
 
         prefetch()
         calibrated = False
@@ -209,8 +216,15 @@ def run(args, subjects, predict=None):
                     sargs = copy.copy(args)
                     sargs.output_dir = os.path.join(args.output_dir, subject.id)
                     evaluation = None
+                    regridded = []
                     if ev is not None:
                         gt, label, gt_aff = ev
+                        if regrid:                                 # the evaluation inputs onto the first input's grid
+                            from . import volume_regrid as VR
+                            gt_aff = gt.affine
+                            gt, label, regridded = VR.eval_onto_grid(raws[0].shape, VR.world_affine_of(raws[0].affine, raws[0].header), gt,
+                                                                     label, device or torch.device(f'cuda:{args.gpu_chose}'))
+                            gt_aff = raws[0].affine if 'gt_volume' in regridded else gt_aff
                         try:
                             VM.check_shapes(raws[0].shape, gt.shape, None if label is None else label.shape, args.slice_half_range)
                         except ValueError as e:
@@ -225,9 +239,13 @@ def run(args, subjects, predict=None):
                             if r.shape != raws[0].shape:
                                 raise ValueError(f'All input volumes must share shape. Got {r.shape} vs {raws[0].shape} for {m}')
                     else:
+                        resampled = []
                         conds, *ref = VI.load_conditions([subject.inputs[m] for m in needed], args.slice_half_range, args.image_size,
-                                                         device, raws=raws, norm=norm)
+                                                         device, raws=raws, norm=norm, regrid=regrid, resampled=resampled)
+                        regridded = [needed[i] for i in resampled] + regridded
                         torch.cuda.synchronize(device)
+                    if regridded:
+                        sargs.regridded = regridded                # (the [done] line names them)
                     timing['intake'] += time.perf_counter() - t0
 
                     def write(path, vol, affine, header):

@@ -17,6 +17,7 @@ handles single-file NIfTI-1 (.nii / .nii.gz, little- or big-endian, scl_slope/in
 from __future__ import annotations
 
 import argparse
+import copy
 import gzip
 import os
 import struct
@@ -86,6 +87,12 @@ def norm_suffix(norm):
     return '' if norm == 'percentile' else f' | norm={norm}'
 
 
+def regrid_suffix(names):
+    """What a [done] line gains when --regrid resampled inputs (nothing otherwise: the lines as they were)."""
+    names = list(names or ())
+    return f" | regrid={','.join(names)}" if names else ''
+
+
 def extract_center_slices(volume, half_range):
     """Reference :159-168 -> (list of [X,Y] slices, first index, last index)."""
     z = volume.shape[2]
@@ -132,6 +139,25 @@ class NiftiHeader:
             return np.array(rows + [(0., 0., 0., 1.)], dtype=np.float64)
         pix = self._get('8f', 76)
         return np.diag([pix[1], pix[2], pix[3], 1.0]).astype(np.float64)
+
+    @property
+    def world_affine(self):
+        """Voxel index -> world coordinate by NIfTI-1's own precedence: sform if sform_code > 0, else qform if qform_code > 0 (the
+        quaternion's rotation, columns scaled by pixdim[1..3], the third also by qfac = pixdim[0], 0 read as +1), else the pixdim
+        diagonal.  --regrid places volumes by this matrix (mudiff_hip.volume_regrid); `affine` stays what it was."""
+        if self._get('h', 254)[0] > 0 or self._get('h', 252)[0] <= 0:
+            return self.affine
+        pix = self._get('8f', 76)
+        b, c, d = (float(v) for v in self._get('3f', 256))
+        a = float(np.sqrt(max(0.0, 1.0 - b * b - c * c - d * d)))
+        rot = np.array([[a * a + b * b - c * c - d * d, 2 * (b * c - a * d), 2 * (b * d + a * c)],
+                        [2 * (b * c + a * d), a * a + c * c - b * b - d * d, 2 * (c * d - a * b)],
+                        [2 * (b * d - a * c), 2 * (c * d + a * b), a * a + d * d - b * b - c * c]], dtype=np.float64)
+        qfac = float(pix[0]) if pix[0] != 0 else 1.0
+        out = np.eye(4, dtype=np.float64)
+        out[:3, :3] = rot * np.array([pix[1], pix[2], pix[3] * qfac], dtype=np.float64)
+        out[:3, 3] = self._get('3f', 268)
+        return out
 
 
 def read_nifti(path):
@@ -314,7 +340,10 @@ def predict_volume(args):
     With --gt_volume (and --eval_mask) the written prediction is scored afterwards (mudiff_hip.volume_metrics): the lines are printed
     after the [done] line and metrics_<target>.json goes next to the prediction.  Those inputs are checked first, before any GPU or
     checkpoint work."""
-    evaluation = load_eval_inputs(args)
+    evaluation, resampled = _load_eval_inputs(args)
+    if resampled:
+        args = copy.copy(args)
+        args.regridded = list(resampled)
     from . import ops
     from .driver import effective_prec_plan
     plan = effective_prec_plan(args)
@@ -337,23 +366,43 @@ def _needed_inputs(args):
 def load_eval_inputs(args):
     """--gt_volume / --eval_mask -> None, or (raw GT volume, label volume or None) once the files have been read and their shapes
     checked against the first input volume and the slab (volume_metrics.check_shapes).  A bad evaluation input raises ValueError
-    here, so that it cannot cost a sampling run."""
+    here, so that it cannot cost a sampling run.  With --regrid a ground truth or a label volume on another grid is first resampled
+    onto the first input's (mudiff_hip.volume_regrid: trilinear / nearest neighbour)."""
+    return _load_eval_inputs(args)[0]
+
+
+def _load_eval_inputs(args):
+    """load_eval_inputs -> (its result, the names of the evaluation inputs --regrid resampled)."""
     gt_path, mask_path = getattr(args, 'gt_volume', None), getattr(args, 'eval_mask', None)
     if gt_path is None:
         if mask_path is not None:
             raise ValueError('--eval_mask needs --gt_volume')
-        return None
+        return None, []
     from .volume_metrics import check_shapes, warn_affine
     _, first = _needed_inputs(args)[0]
-    inp, inp_aff, _ = read_nifti(first)
-    gt, gt_aff, _ = read_nifti(gt_path)
-    label = None if mask_path is None else read_nifti(mask_path)[0]
+    resampled = []
+    if getattr(args, 'regrid', False):
+        from . import volume_intake as VI
+        from . import volume_regrid as VR
+        ref = VI.read_nifti_raw(first)
+        inp_shape, inp_aff = ref.shape, ref.affine
+        gt_raw = VI.read_nifti_raw(gt_path)
+        gt_aff = gt_raw.affine
+        gt, label, resampled = VR.eval_onto_grid(ref.shape, VR.world_affine_of(ref.affine, ref.header), gt_raw,
+                                                 None if mask_path is None else VI.read_nifti_raw(mask_path),
+                                                 torch.device(f'cuda:{args.gpu_chose}'))
+    else:
+        inp, inp_aff, _ = read_nifti(first)
+        inp_shape = inp.shape
+        gt, gt_aff, _ = read_nifti(gt_path)
+        label = None if mask_path is None else read_nifti(mask_path)[0]
     try:
-        check_shapes(inp.shape, gt.shape, None if label is None else label.shape, args.slice_half_range)
+        check_shapes(inp_shape, gt.shape, None if label is None else label.shape, args.slice_half_range)
     except ValueError as e:
         raise ValueError(f'--gt_volume / --eval_mask: {e} (the prediction has the shape of {first})') from None
-    warn_affine(inp_aff, gt_aff, first, gt_path)
-    return gt, label
+    if 'gt_volume' not in resampled:
+        warn_affine(inp_aff, gt_aff, first, gt_path)
+    return (gt, label), resampled
 
 
 def _score_prediction(args, evaluation, vol, std_vol, device):
@@ -385,13 +434,20 @@ def _predict_volume(args, plan, evaluation=None):
     gen1, gen2 = load_generators(args, device)
     norm = getattr(args, 'norm', 'percentile')
 
+    regrid = getattr(args, 'regrid', False)
+    needed = _needed_inputs(args)
     if getattr(args, 'device_intake', False):
         from . import volume_intake as VI
-        stacks, *ref = VI.load_conditions([path for _, path in _needed_inputs(args)], args.slice_half_range, args.image_size, device,
-                                          norm=norm)
+        resampled = []
+        stacks, *ref = VI.load_conditions([path for _, path in needed], args.slice_half_range, args.image_size, device, norm=norm,
+                                          regrid=regrid, resampled=resampled)
+        args = _with_regridded(args, [needed[i][0] for i in resampled])
         return predict_from_conditions(args, plan, evaluation, gen1, gen2, device, stacks, tuple(ref), on_device=True)
+    if regrid:
+        stacks, ref, resampled = _load_regridded(needed, args.slice_half_range, norm, device)
+        return predict_from_conditions(_with_regridded(args, resampled), plan, evaluation, gen1, gen2, device, stacks, ref)
     stacks, ref = [], None
-    for m, path in _needed_inputs(args):
+    for m, path in needed:
         slices, shp, aff, hdr, s0, s1 = load_and_preprocess_volume(path, args.slice_half_range, norm)
         if ref is None:
             ref = (shp, aff, hdr, s0, s1)
@@ -399,6 +455,38 @@ def _predict_volume(args, plan, evaluation=None):
             raise ValueError(f'All input volumes must share shape. Got {shp} vs {ref[0]} for {m}')
         stacks.append(np.stack(slices, 0))
     return predict_from_conditions(args, plan, evaluation, gen1, gen2, device, stacks, ref)
+
+
+def _with_regridded(args, names):
+    """args, or a copy whose `regridded` (the names the [done] line reports) has `names` in front of the evaluation inputs'."""
+    if not names:
+        return args
+    args = copy.copy(args)
+    args.regridded = list(names) + list(getattr(args, 'regridded', ()))
+    return args
+
+
+def _load_regridded(needed, half_range, norm, device):
+    """The host path under --regrid: every input that is not on the first one's grid is uploaded as the fp32 values the pipeline sees,
+    resampled on the device (mudiff_hip.volume_regrid) and downloaded; the numpy normalisation is the one of every run.
+    -> (stacks, ref, names of the resampled inputs)."""
+    from . import volume_intake as VI
+    from . import volume_regrid as VR
+    stacks, ref, ref_world, resampled = [], None, None, []
+    for m, path in needed:
+        raw = VI.read_nifti_raw(path)
+        if ref is None:
+            s0, s1 = VI.slab_range(raw.shape[2], half_range) if len(raw.shape) == 3 else (0, 0)
+            ref, ref_world = (raw.shape, raw.affine, raw.header, s0, s1), VR.world_affine_of(raw.affine, raw.header)
+        on_grid = VR.regrid_to(raw, ref[0], ref_world, device, header=ref[2])
+        if on_grid is raw:
+            vol = raw.values_float64()
+        else:
+            vol = on_grid.values_float32()
+            resampled.append(m)
+        slices, _, _ = extract_center_slices(normalise_volume(vol, norm), half_range)
+        stacks.append(np.stack(slices, 0))
+    return stacks, ref, resampled
 
 
 class _Stages:
@@ -465,7 +553,7 @@ def predict_from_conditions(args, plan, evaluation, gen1, gen2, device, stacks, 
     out_path = os.path.join(args.output_dir, f'predicted_{args.target_modality.lower()}.nii.gz')
     stages.run('write', lambda: write(out_path, vol_pred, aff, hdr))
     print(f'[done] saved: {out_path} | shape={tuple(vol_pred.shape)} | slices={s0}..{s1}' + ('' if plan == 'auto' else f' | prec_plan={plan}') +
-          norm_suffix(getattr(args, 'norm', 'percentile')))
+          norm_suffix(getattr(args, 'norm', 'percentile')) + regrid_suffix(getattr(args, 'regridded', ())))
     if evaluation is not None:
         _score_prediction(args, evaluation, vol_pred, None, device)
     return out_path
@@ -515,7 +603,7 @@ def _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref, evaluation=N
         paths.append(path)
     print(f'[done] saved: {paths[0]} and {paths[1]} | shape={tuple(shp)} | slices={s0}..{s1} | {args.num_samples} samples per slice' +
           ('' if effective_prec_plan(args) == 'auto' else f' | prec_plan={effective_prec_plan(args)}') +      # (the default plan: the line as it was)
-          norm_suffix(getattr(args, 'norm', 'percentile')))
+          norm_suffix(getattr(args, 'norm', 'percentile')) + regrid_suffix(getattr(args, 'regridded', ())))
     if evaluation is not None:
         _score_prediction(args, evaluation, vols[0], vols[1], device)
     return tuple(paths)
@@ -579,6 +667,11 @@ def make_parser(prog='MU-Diff volume prediction (MI355X)'):
                    help="how the input volumes (and --gt_volume) are mapped to [-1, 1]: 'percentile' = 1st / 99th percentile min-max "
                         "(the reference's volume entry point); 'zscore' = z-score over the non-zero voxels, clamped to +-3 sigma and "
                         "divided by 3 (what the reference's training and 2D test data see: use it with such a checkpoint)")
+    p.add_argument('--regrid', action='store_true',
+                   help='accept inputs (and --gt_volume / --eval_mask) on other voxel grids: each volume that is not on the first '
+                        "input's grid (shape and affine) is resampled onto it on the GPU through the affines before normalisation, "
+                        'trilinearly (the label volume: nearest neighbour).  Resampling only: the volumes must already share one '
+                        'world space (mudiff_hip.volume_regrid)')
     from .driver import add_calibration_flags
     add_calibration_flags(p)                # (also --prec_plan)
     return p
@@ -599,8 +692,8 @@ def build_argparser(argv=None):
     """Flags and defaults of the reference parser (:302-357; like it, returns the PARSED namespace), plus --centered (which
     the generators read and the reference parser forgot), --batch_size, --resize_back, --calibrate / --calibrate_threshold
     (mudiff_hip.precision; the record goes to <output_dir>/prec_calibration.json), --num_samples (ensembles), --gt_volume /
-    --eval_mask (scoring of the written prediction, mudiff_hip.volume_metrics), --device_intake (mudiff_hip.volume_intake) and --norm
-    (the training normalisation)."""
+    --eval_mask (scoring of the written prediction, mudiff_hip.volume_metrics), --device_intake (mudiff_hip.volume_intake), --norm
+    (the training normalisation) and --regrid (inputs on other voxel grids)."""
     p = make_parser()
     return finish_args(p, p.parse_args(argv))
 

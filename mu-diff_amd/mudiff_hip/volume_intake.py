@@ -254,7 +254,11 @@ def to_host_volume(vol_zyx):
 # the intake of a subject's condition volumes
 # ---------------------------------------------------------------------------------------------------
 def upload(raw, device):
-    """RawVolume -> flat device tensor of the stored voxels (uint16 travels as int16 bits: the kernels reinterpret by datatype code)."""
+    """RawVolume -> flat device tensor of the stored voxels (uint16 travels as int16 bits: the kernels reinterpret by datatype code).
+    A volume that --regrid resampled is on the device already (volume_regrid.RegriddedVolume.dev)."""
+    dev = getattr(raw, 'dev', None)
+    if dev is not None:
+        return dev.reshape(-1).to(device)
     a = np.asarray(raw.data)
     if a.dtype == np.dtype('<u2'):
         a = a.view(np.int16)
@@ -308,15 +312,22 @@ def _resized(t, image_size):
     return t.contiguous()
 
 
-def load_conditions(paths, half_range, image_size, device, raws=None, norm='percentile'):
+def load_conditions(paths, half_range, image_size, device, raws=None, norm='percentile', regrid=False, resampled=None):
     """The condition volumes of one subject (paths in MODALITY_ORDERS order; `raws`: the RawVolumes when a prefetch thread has read them
     already; `norm`: --norm) -> ([three device tensors [n,1,S,S]], shape, affine, header, s0, s1) with the geometry of the first volume.  ValueError when
-    the volumes differ in shape."""
+    the volumes differ in shape.  With `regrid` (--regrid) a volume that is not on the first one's grid is resampled onto it on the device
+    instead (mudiff_hip.volume_regrid), before it is normalised; its index in `paths` is appended to the list `resampled`."""
     conds, ref = [], None
     for i, path in enumerate(paths):
         raw = read_nifti_raw(path) if raws is None else raws[i]
         if ref is None:
             ref = raw
+        elif regrid:
+            from . import volume_regrid as VR
+            on_grid = VR.regrid_to(raw, ref.shape, VR.world_affine_of(ref.affine, ref.header), device, header=ref.header)
+            if on_grid is not raw and resampled is not None:
+                resampled.append(i)
+            raw = on_grid
         elif raw.shape != ref.shape:
             raise ValueError(f'All input volumes must share shape. Got {raw.shape} vs {ref.shape} for {path}')
         conds.append(condition_from_raw(raw, half_range, image_size, device, name=path, norm=norm))

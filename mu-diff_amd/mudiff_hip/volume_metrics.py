@@ -227,15 +227,31 @@ def score_arrays(pred_vol, gt_raw, label=None, std_vol=None, slice_half_range=80
     return dict(shape=[int(v) for v in np.shape(gt_raw)], slab=[s0, s1], **extra, **rep)
 
 
-def score_files(pred_path, gt_path, mask_path=None, std_path=None, slice_half_range=80, device='cuda', norm='percentile'):
+def score_files(pred_path, gt_path, mask_path=None, std_path=None, slice_half_range=80, device='cuda', norm='percentile', regrid=False,
+                resampled=None):
     """score_arrays on NIfTI files (volume.read_nifti): the prediction, the raw GT, an optional label volume (--eval_mask, e.g. a
-    BraTS segmentation) and an optional std volume.  Warns when the prediction's affine differs from the GT's."""
+    BraTS segmentation) and an optional std volume.  Warns when the prediction's affine differs from the GT's.  With `regrid`
+    (--regrid) a GT or a label volume that is not on the prediction's grid is first resampled onto it (mudiff_hip.volume_regrid:
+    trilinear / nearest neighbour); the list `resampled` receives their names."""
     from .volume import read_nifti
-    pred, pa, _ = read_nifti(pred_path)
-    gt, ga, _ = read_nifti(gt_path)
-    label = None if mask_path is None else read_nifti(mask_path)[0]
+    pred, pa, ph = read_nifti(pred_path)
     std = None if std_path is None else read_nifti(std_path)[0]
-    warn_affine(pa, ga, pred_path, gt_path)
+    done = []
+    if regrid:
+        from . import volume_intake as VI
+        from . import volume_regrid as VR
+        gt_raw = VI.read_nifti_raw(gt_path)
+        ga = gt_raw.affine
+        gt, label, done = VR.eval_onto_grid(pred.shape, VR.world_affine_of(pa, ph), gt_raw,
+                                            None if mask_path is None else VI.read_nifti_raw(mask_path), torch.device(device),
+                                            names=('gt', 'mask'))
+        if resampled is not None:
+            resampled.extend(done)
+    else:
+        gt, ga, _ = read_nifti(gt_path)
+        label = None if mask_path is None else read_nifti(mask_path)[0]
+    if 'gt' not in done:
+        warn_affine(pa, ga, pred_path, gt_path)
     return score_arrays(pred.astype(np.float32), gt, label, None if std is None else std.astype(np.float32), slice_half_range, device,
                         norm=norm)
 
@@ -256,6 +272,9 @@ def build_parser():
     p.add_argument('--slice_half_range', type=int, default=80, help='the slab: the centre +- this many planes (as the volume pipeline)')
     p.add_argument('--norm', type=str, default='percentile', choices=['percentile', 'zscore'],
                    help="how the ground truth is mapped to [-1, 1]: the --norm the prediction was made with (mudiff_hip.volume)")
+    p.add_argument('--regrid', action='store_true',
+                   help="resample a --gt (trilinearly) or a --mask (nearest neighbour) that is not on the prediction's voxel grid onto "
+                        'it through the affines before scoring (mudiff_hip.volume_regrid; resampling, not registration)')
     p.add_argument('--json', type=str, default=None, help='write the full report (per-plane curves included) to this file')
     return p
 
@@ -263,10 +282,14 @@ def build_parser():
 def main(argv=None):
     args = build_parser().parse_args(argv)
     try:
-        rep = score_files(args.pred, args.gt, args.mask, args.std, args.slice_half_range, norm=args.norm)
+        resampled = []
+        rep = score_files(args.pred, args.gt, args.mask, args.std, args.slice_half_range, norm=args.norm, regrid=args.regrid,
+                          resampled=resampled)
     except ValueError as e:
         print(f'error: {e}', file=sys.stderr)
         return 2
+    if resampled:
+        print(f"[metrics] regrid={','.join(resampled)}")
     for ln in format_lines(rep):
         print(ln)
     if args.json:
