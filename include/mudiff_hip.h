@@ -371,7 +371,16 @@ int mud_ensemble_stats(const float* samples, int n, int N, int64_t hw, float sca
  *   fastest), the weight being the product of w or 1 - w per axis.  A neighbour outside the source counts as 0 (zero padding: continuous
  *   at the border); one whose weight is exactly 0 is not read, so identities and integer shifts are bit-exact, next to a NaN too.
  *   mode 1, nearest (label volumes): the value at floor(p + 0.5) per axis, 0 outside the source.
- *   Both sizes obey X*Y*Z < 2^31; m must be finite. */
+ *   Both sizes obey X*Y*Z < 2^31; m must be finite.
+ * mud_volume_joint_hist (--coregister): the joint histogram a rigid registration search evaluates, between a
+ *   fixed volume (X x Y x Z stored voxels) and a moving one (SX x SY x SZ) seen through m, the matrix of mud_volume_regrid (fixed voxel
+ *   index -> moving voxel coordinate, 12 doubles on the host).  Sample points: the fixed voxels (i, j, k) whose indices are all multiples
+ *   of `stride`.  A sample is counted iff 0 <= p_a <= S_a - 1 on every axis (the overlap only: no zero padding enters) and both values
+ *   are finite.  The fixed value is the stored voxel's; the moving value is mode 0 of mud_volume_regrid at p, so the histogram is that of
+ *   (fixed, mud_volume_regrid(moving, m)) over the counted samples.  bin = clamp((int)floor((double(v) - lo) * scale), 0, bins - 1), the
+ *   subtraction and the product rounded separately; hist[bin_fix][bin_mov] += 1.  hist: device, uint32 [bins][bins], cleared first
+ *   (stream-ordered).  Counts are integers (LDS atomics per workgroup, one global atomic per non-empty bin): the result does not depend
+ *   on the order of arrival and is the same bits on every run.  bins: 2 to 64; stride > 0; m, lo and scale finite. */
 #define MUD_NIFTI_U1 2
 #define MUD_NIFTI_I2 4
 #define MUD_NIFTI_I4 8
@@ -397,6 +406,9 @@ int mud_volume_assemble(const float* planes, const float* planes2, int X, int Y,
                         void* stream);
 int mud_volume_regrid(const void* src, int datatype, int SX, int SY, int SZ, float slope, float inter, const double* m, int mode, int X,
                       int Y, int Z, float* out, void* stream);
+int mud_volume_joint_hist(const void* fix, int fix_dt, int X, int Y, int Z, float fix_slope, float fix_inter, const void* mov, int mov_dt,
+                          int SX, int SY, int SZ, float mov_slope, float mov_inter, const double* m, int stride, double fix_lo,
+                          double fix_scale, double mov_lo, double mov_scale, int bins, uint32_t* hist, void* stream);
 
 #ifdef __cplusplus
 }

@@ -14,29 +14,13 @@
 // In front of all that, mud_volume_regrid (--regrid) resamples a volume that lies on another voxel grid onto
 // the grid of the first input: a gather through the affines, trilinear or nearest.
 // DESIGN.md section 5.10 has the definitions and why they equal the host's results bit for bit.
-#include "mud_common.h"
+#include "volume_common.h"      // vi_value, vi_trilinear, VI_DISPATCH, vi_check_volume: shared with volume_coreg.hip
 
 typedef uint32_t vi_u32x4 __attribute__((ext_vector_type(4)));
 
-#define VI_THREADS 256
-#define VI_MAX_BLOCKS 2048
 #define VI_TILE 64
 #define VI_NT (2 + 2 * MUD_VI_MAX_RANKS)      // select targets: min, max, and the two ends of every window
 #define VI_BETWEEN 16                         // capacity per window of the keys strictly between its end keys (at most 14 exist)
-
-// ---- the value of a stored voxel ------------------------------------------------------------------------------------------------------
-// float32(double(raw) * slope + inter), the product and the sum rounded separately (numpy: data.astype(float64) * slope + inter, then
-// astype(float32)); without scaling float32(double(raw)) = float32(raw)
-template <typename T>
-__device__ __forceinline__ float vi_value(T raw, int scaled, double slope, double inter) {
-#pragma clang fp contract(off)
-  double d = (double)raw;
-  if (scaled) {
-    d = d * slope;
-    d = d + inter;
-  }
-  return (float)d;
-}
 
 // order-preserving uint32 image of a float; every NaN sorts last (np.sort puts them there)
 __device__ __forceinline__ uint32_t vi_key(float v) {
@@ -268,38 +252,6 @@ __global__ __launch_bounds__(64) void k_vi_finish(vi_state* __restrict__ st, int
   for (int j = 0; j < MUD_VI_WINDOW; ++j) rec->window[i][j] = w[j];
 }
 
-static bool vi_scaled(float slope, float inter) {      // volume.read_nifti's condition
-  return slope != 0.0f && slope - slope == 0.0f && (slope != 1.0f || inter != 0.0f);
-}
-
-static int vi_esize(int datatype) {
-  switch (datatype) {
-    case MUD_NIFTI_U1: return 1;
-    case MUD_NIFTI_I2:
-    case MUD_NIFTI_U2: return 2;
-    case MUD_NIFTI_I4:
-    case MUD_NIFTI_F4: return 4;
-    default: return 0;
-  }
-}
-
-static int vi_check_volume(const char* who, const void* vol, int datatype, int X, int Y, int Z) {
-  MUD_REQUIRE(vi_esize(datatype) != 0, "%s: unsupported NIfTI datatype code %d (u1 2, i2 4, i4 8, f4 16, u2 512)", who, datatype);
-  MUD_REQUIRE(X > 0 && Y > 0 && Z > 0 && (int64_t)X * Y * Z < ((int64_t)1 << 31), "%s: bad volume size %d x %d x %d", who, X, Y, Z);
-  MUD_REQUIRE(vol != nullptr, "%s: null pointer", who);
-  MUD_REQUIRE(mud_aligned16(vol), "%s: the volume must be 16-byte aligned", who);
-  return MUD_OK;
-}
-
-#define VI_DISPATCH(datatype, CALL)                           \
-  switch (datatype) {                                         \
-    case MUD_NIFTI_U1: { typedef uint8_t T; CALL; } break;    \
-    case MUD_NIFTI_I2: { typedef int16_t T; CALL; } break;    \
-    case MUD_NIFTI_U2: { typedef uint16_t T; CALL; } break;   \
-    case MUD_NIFTI_I4: { typedef int32_t T; CALL; } break;    \
-    default: { typedef float T; CALL; } break;                \
-  }
-
 extern "C" int64_t mud_volume_census_ws_bytes(void) { return (int64_t)((sizeof(vi_state) + 255) / 256 * 256); }
 
 extern "C" int mud_volume_census(const void* vol, int datatype, int X, int Y, int Z, float slope, float inter, const double* q, int nq,
@@ -467,15 +419,7 @@ extern "C" int mud_volume_assemble(const float* planes, const float* planes2, in
 }
 
 // ---- regrid: a volume on another voxel grid -> fp32 [Z][Y][X] on the reference grid ---------------------------------------------------
-// m maps a reference voxel index (i, j, k) to a source voxel coordinate p; everything about p is fp64, so that an identity, an integer
-// shift, a flip or a dyadic scale reproduce stored values exactly and an oblique matrix places a 240-voxel axis to ~1e-13 voxels.
-struct vi_mat {
-  double m[12];
-};
-
-// one axis of p: is any neighbour inside [0, S)?  With p in (-1, S) floor(p) fits an int; a NaN or an infinite p fails the test
-__device__ __forceinline__ bool vi_axis_near(double p, int S) { return p > -1.0 && p < (double)S; }
-
+// (vi_mat, vi_coordinate, vi_axis_near and vi_trilinear: volume_common.h)
 template <typename T>
 __global__ __launch_bounds__(VI_THREADS) void k_vi_regrid(const T* __restrict__ src, int SX, int SY, int SZ, int scaled, double slope,
                                                           double inter, vi_mat M, int mode, int X, int Y, int64_t n,
@@ -485,28 +429,14 @@ __global__ __launch_bounds__(VI_THREADS) void k_vi_regrid(const T* __restrict__ 
     const uint32_t row = l / (uint32_t)X;
     const double x = (double)(l - row * (uint32_t)X), y = (double)(row % (uint32_t)Y), z = (double)(row / (uint32_t)Y);
     double p[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) p[a] = fma(M.m[4 * a], x, fma(M.m[4 * a + 1], y, fma(M.m[4 * a + 2], z, M.m[4 * a + 3])));
+    vi_coordinate(M, x, y, z, p);
     float r = 0.0f;
     if (mode == 1) {                                         // nearest: floor(p + 0.5) per axis, 0 outside
       const double qx = floor(p[0] + 0.5), qy = floor(p[1] + 0.5), qz = floor(p[2] + 0.5);
       if (qx >= 0.0 && qx < (double)SX && qy >= 0.0 && qy < (double)SY && qz >= 0.0 && qz < (double)SZ)
         r = vi_value<T>(src[((int64_t)(int)qz * SY + (int)qy) * SX + (int)qx], scaled, slope, inter);
     } else if (vi_axis_near(p[0], SX) && vi_axis_near(p[1], SY) && vi_axis_near(p[2], SZ)) {
-      const double fx = floor(p[0]), fy = floor(p[1]), fz = floor(p[2]);
-      const double wx[2] = {1.0 - (p[0] - fx), p[0] - fx}, wy[2] = {1.0 - (p[1] - fy), p[1] - fy}, wz[2] = {1.0 - (p[2] - fz), p[2] - fz};
-      const int x0 = (int)fx, y0 = (int)fy, z0 = (int)fz;
-      double acc = 0.0;
-#pragma unroll
-      for (int c = 0; c < 8; ++c) {                          // neighbours in file order: x fastest
-        const int dx = c & 1, dy = (c >> 1) & 1, dz = c >> 2;
-        const int xx = x0 + dx, yy = y0 + dy, zz = z0 + dz;
-        const double w = wx[dx] * wy[dy] * wz[dz];
-        // a neighbour of weight 0 is not read (an identity next to a NaN stays exact); one outside the grid counts as 0
-        if (w != 0.0 && xx >= 0 && xx < SX && yy >= 0 && yy < SY && zz >= 0 && zz < SZ)
-          acc = fma((double)vi_value<T>(src[((int64_t)zz * SY + yy) * SX + xx], scaled, slope, inter), w, acc);
-      }
-      r = (float)acc;
+      r = vi_trilinear<T>(src, SX, SY, SZ, scaled, slope, inter, p);
     }
     out[i] = r;
   }

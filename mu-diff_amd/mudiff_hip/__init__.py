@@ -89,7 +89,7 @@ class VolumeCensusRecord(C.Structure):
                 ('window', (C.c_float * VI_WINDOW) * VI_MAX_RANKS)]
 
 
-_P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
+_P, _I, _L, _F, _D = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 _SIGNATURES = {
     'mud_version': (C.c_int, []),
     'mud_last_error': (C.c_char_p, []),
@@ -145,6 +145,7 @@ _SIGNATURES = {
     'mud_volume_slab_zscore': (_I, [_P, _I, _I, _I, _I, _F, _F, _F, _F, _I, _I, _P, _P]),
     'mud_volume_assemble': (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     'mud_volume_regrid': (_I, [_P, _I, _I, _I, _I, _F, _F, C.POINTER(C.c_double), _I, _I, _I, _I, _P, _P]),
+    'mud_volume_joint_hist': (_I, [_P, _I, _I, _I, _I, _F, _F, _P, _I, _I, _I, _I, _F, _F, C.POINTER(C.c_double), _I, _D, _D, _D, _D, _I, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -20,6 +20,8 @@ of every stage summed over the cohort.  With --norm zscore (DESIGN.md section 5.
 prefetch thread, the [done] lines end in ` | norm=zscore`, and the reports carry "norm": "zscore" (a default run's are unchanged).
 With --regrid a subject's volumes, ground truth and mask included, need not share one voxel grid: what is not
 on the first input's grid is resampled onto it on the device, and the subject's [done] line names it (` | regrid=T2,gt_volume`).
+With --coregister every input other than the first is first aligned to the first one rigidly; the search runs
+on the main thread between the upload and the intake, and coreg_<t>.json goes next to each subject's prediction.
 """
 from __future__ import annotations
 
@@ -168,6 +170,10 @@ def run(args, subjects, predict=None):
     plan = effective_prec_plan(args)
     norm = getattr(args, 'norm', 'percentile')
     regrid = getattr(args, 'regrid', False)
+    coreg = None
+    if getattr(args, 'coregister', False):
+        from . import volume_coreg as VC
+        coreg = VC.options(args)
     timing = dict(read=0.0, intake=0.0, sample=0.0, assemble=0.0, write=0.0, write_wait=0.0, score=0.0)
     if norm != 'percentile':                 # (a default run's report keeps the keys it had)
         timing.update(moments=0.0, read_wait=0.0)
@@ -239,10 +245,13 @@ def run(args, subjects, predict=None):
                             if r.shape != raws[0].shape:
                                 raise ValueError(f'All input volumes must share shape. Got {r.shape} vs {raws[0].shape} for {m}')
                     else:
-                        resampled = []
+                        resampled, reports = [], []                # (--coregister searches here, on the main thread: it needs the GPU)
                         conds, *ref = VI.load_conditions([subject.inputs[m] for m in needed], args.slice_half_range, args.image_size,
-                                                         device, raws=raws, norm=norm, regrid=regrid, resampled=resampled)
+                                                         device, raws=raws, norm=norm, regrid=regrid, resampled=resampled,
+                                                         coregister=coreg, coreg_reports=reports)
                         regridded = [needed[i] for i in resampled] + regridded
+                        if reports:
+                            sargs.coreg_reports = [(needed[i], r) for i, r in reports]
                         torch.cuda.synchronize(device)
                     if regridded:
                         sargs.regridded = regridded                # (the [done] line names them)

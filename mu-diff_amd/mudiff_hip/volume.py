@@ -436,16 +436,22 @@ def _predict_volume(args, plan, evaluation=None):
 
     regrid = getattr(args, 'regrid', False)
     needed = _needed_inputs(args)
+    coreg = None
+    if getattr(args, 'coregister', False):                 # (--coregister, DESIGN.md section 5.13: implies the --regrid machinery)
+        from . import volume_coreg as VC
+        coreg = VC.options(args)
     if getattr(args, 'device_intake', False):
         from . import volume_intake as VI
-        resampled = []
+        resampled, reports = [], []
         stacks, *ref = VI.load_conditions([path for _, path in needed], args.slice_half_range, args.image_size, device, norm=norm,
-                                          regrid=regrid, resampled=resampled)
-        args = _with_regridded(args, [needed[i][0] for i in resampled])
+                                          regrid=regrid, resampled=resampled, coregister=coreg, coreg_reports=reports)
+        args = _with_coregistered(_with_regridded(args, [needed[i][0] for i in resampled]), [(needed[i][0], r) for i, r in reports])
         return predict_from_conditions(args, plan, evaluation, gen1, gen2, device, stacks, tuple(ref), on_device=True)
-    if regrid:
-        stacks, ref, resampled = _load_regridded(needed, args.slice_half_range, norm, device)
-        return predict_from_conditions(_with_regridded(args, resampled), plan, evaluation, gen1, gen2, device, stacks, ref)
+    if regrid or coreg is not None:
+        reports = []
+        stacks, ref, resampled = _load_regridded(needed, args.slice_half_range, norm, device, coreg, reports)
+        args = _with_coregistered(_with_regridded(args, resampled), reports)
+        return predict_from_conditions(args, plan, evaluation, gen1, gen2, device, stacks, ref)
     stacks, ref = [], None
     for m, path in needed:
         slices, shp, aff, hdr, s0, s1 = load_and_preprocess_volume(path, args.slice_half_range, norm)
@@ -466,19 +472,44 @@ def _with_regridded(args, names):
     return args
 
 
-def _load_regridded(needed, half_range, norm, device):
+def _with_coregistered(args, reports):
+    """args, or a copy whose `coreg_reports` ([(input name, report)]: the [done] line and coreg_<t>.json) is `reports`."""
+    if not reports:
+        return args
+    args = copy.copy(args)
+    args.coreg_reports = list(reports)
+    return args
+
+
+def _coreg_done(args):
+    """Under --coregister: writes coreg_<t>.json next to the prediction -> what the [done] line gains ('' otherwise)."""
+    reports = getattr(args, 'coreg_reports', None)
+    if not reports:
+        return ''
+    from . import volume_coreg as VC
+    VC.write_reports(reports, args.output_dir, args.target_modality)
+    return VC.coreg_suffix(reports)
+
+
+def _load_regridded(needed, half_range, norm, device, coreg=None, reports=None):
     """The host path under --regrid: every input that is not on the first one's grid is uploaded as the fp32 values the pipeline sees,
-    resampled on the device (mudiff_hip.volume_regrid) and downloaded; the numpy normalisation is the one of every run.
+    resampled on the device (mudiff_hip.volume_regrid) and downloaded; the numpy normalisation is the one of every run.  With `coreg`
+    (--coregister: volume_coreg.options) each such input is first aligned to the first one (its (name, report) goes to `reports`).
     -> (stacks, ref, names of the resampled inputs)."""
     from . import volume_intake as VI
     from . import volume_regrid as VR
-    stacks, ref, ref_world, resampled = [], None, None, []
+    stacks, ref, ref_world, resampled, first = [], None, None, [], None
     for m, path in needed:
         raw = VI.read_nifti_raw(path)
+        world = None
         if ref is None:
             s0, s1 = VI.slab_range(raw.shape[2], half_range) if len(raw.shape) == 3 else (0, 0)
-            ref, ref_world = (raw.shape, raw.affine, raw.header, s0, s1), VR.world_affine_of(raw.affine, raw.header)
-        on_grid = VR.regrid_to(raw, ref[0], ref_world, device, header=ref[2])
+            ref, ref_world, first = (raw.shape, raw.affine, raw.header, s0, s1), VR.world_affine_of(raw.affine, raw.header), raw
+        elif coreg is not None:
+            from . import volume_coreg as VC
+            world, report = VC.coregister(first, raw, device, **coreg)
+            reports.append((m, report))
+        on_grid = VR.regrid_to(raw, ref[0], ref_world, device, header=ref[2], world=world)
         if on_grid is raw:
             vol = raw.values_float64()
         else:
@@ -553,7 +584,7 @@ def predict_from_conditions(args, plan, evaluation, gen1, gen2, device, stacks, 
     out_path = os.path.join(args.output_dir, f'predicted_{args.target_modality.lower()}.nii.gz')
     stages.run('write', lambda: write(out_path, vol_pred, aff, hdr))
     print(f'[done] saved: {out_path} | shape={tuple(vol_pred.shape)} | slices={s0}..{s1}' + ('' if plan == 'auto' else f' | prec_plan={plan}') +
-          norm_suffix(getattr(args, 'norm', 'percentile')) + regrid_suffix(getattr(args, 'regridded', ())))
+          norm_suffix(getattr(args, 'norm', 'percentile')) + regrid_suffix(getattr(args, 'regridded', ())) + _coreg_done(args))
     if evaluation is not None:
         _score_prediction(args, evaluation, vol_pred, None, device)
     return out_path
@@ -603,7 +634,7 @@ def _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref, evaluation=N
         paths.append(path)
     print(f'[done] saved: {paths[0]} and {paths[1]} | shape={tuple(shp)} | slices={s0}..{s1} | {args.num_samples} samples per slice' +
           ('' if effective_prec_plan(args) == 'auto' else f' | prec_plan={effective_prec_plan(args)}') +      # (the default plan: the line as it was)
-          norm_suffix(getattr(args, 'norm', 'percentile')) + regrid_suffix(getattr(args, 'regridded', ())))
+          norm_suffix(getattr(args, 'norm', 'percentile')) + regrid_suffix(getattr(args, 'regridded', ())) + _coreg_done(args))
     if evaluation is not None:
         _score_prediction(args, evaluation, vols[0], vols[1], device)
     return tuple(paths)
@@ -672,6 +703,15 @@ def make_parser(prog='MU-Diff volume prediction (MI355X)'):
                         "input's grid (shape and affine) is resampled onto it on the GPU through the affines before normalisation, "
                         'trilinearly (the label volume: nearest neighbour).  Resampling only: the volumes must already share one '
                         'world space (mudiff_hip.volume_regrid)')
+    p.add_argument('--coregister', action='store_true',
+                   help='rigidly align every input other than the first to the first input (six parameters, normalised mutual '
+                        'information, histogram on the GPU: mudiff_hip.volume_coreg), then resample it onto the first input\'s grid '
+                        'as --regrid does; coreg_<t>.json next to the prediction holds what was found.  --gt_volume / --eval_mask are '
+                        'not registered')
+    p.add_argument('--coregister_strides', nargs='+', type=int, default=[4, 2, 1],
+                   help='sampling strides of the coarse-to-fine search levels')
+    p.add_argument('--coregister_max_mm', type=float, default=20.0, help='largest translation per axis the search may propose')
+    p.add_argument('--coregister_max_deg', type=float, default=15.0, help='largest rotation per axis the search may propose')
     from .driver import add_calibration_flags
     add_calibration_flags(p)                # (also --prec_plan)
     return p
@@ -685,6 +725,8 @@ def finish_args(p, args):
         p.error(f'--num_samples must be >= 2 (got {args.num_samples})')
     if args.num_samples is not None and not 0 <= args.seed < 1 << 64:
         p.error('--num_samples needs a --seed in [0, 2^64)')
+    if min(args.coregister_strides) < 1 or args.coregister_max_mm < 0 or args.coregister_max_deg < 0:
+        p.error('--coregister_strides must be positive, --coregister_max_mm / --coregister_max_deg not negative')
     return args
 
 
@@ -693,7 +735,8 @@ def build_argparser(argv=None):
     the generators read and the reference parser forgot), --batch_size, --resize_back, --calibrate / --calibrate_threshold
     (mudiff_hip.precision; the record goes to <output_dir>/prec_calibration.json), --num_samples (ensembles), --gt_volume /
     --eval_mask (scoring of the written prediction, mudiff_hip.volume_metrics), --device_intake (mudiff_hip.volume_intake), --norm
-    (the training normalisation) and --regrid (inputs on other voxel grids)."""
+    (the training normalisation), --regrid (inputs on other voxel grids) and
+    --coregister (rigid alignment of the inputs to the first one)."""
     p = make_parser()
     return finish_args(p, p.parse_args(argv))
 

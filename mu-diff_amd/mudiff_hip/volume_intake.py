@@ -312,19 +312,28 @@ def _resized(t, image_size):
     return t.contiguous()
 
 
-def load_conditions(paths, half_range, image_size, device, raws=None, norm='percentile', regrid=False, resampled=None):
+def load_conditions(paths, half_range, image_size, device, raws=None, norm='percentile', regrid=False, resampled=None, coregister=None,
+                    coreg_reports=None):
     """The condition volumes of one subject (paths in MODALITY_ORDERS order; `raws`: the RawVolumes when a prefetch thread has read them
     already; `norm`: --norm) -> ([three device tensors [n,1,S,S]], shape, affine, header, s0, s1) with the geometry of the first volume.  ValueError when
     the volumes differ in shape.  With `regrid` (--regrid) a volume that is not on the first one's grid is resampled onto it on the device
-    instead (mudiff_hip.volume_regrid), before it is normalised; its index in `paths` is appended to the list `resampled`."""
+    instead (mudiff_hip.volume_regrid), before it is normalised; its index in `paths` is appended to the list `resampled`.
+    `coregister` (--coregister: the keyword arguments of volume_coreg.coregister, or None) first aligns each such volume to the first one
+    rigidly and resamples it through the transform found; (index, report) goes to the list `coreg_reports`."""
     conds, ref = [], None
     for i, path in enumerate(paths):
         raw = read_nifti_raw(path) if raws is None else raws[i]
         if ref is None:
             ref = raw
-        elif regrid:
+        elif regrid or coregister is not None:
             from . import volume_regrid as VR
-            on_grid = VR.regrid_to(raw, ref.shape, VR.world_affine_of(ref.affine, ref.header), device, header=ref.header)
+            world = None
+            if coregister is not None:
+                from . import volume_coreg as VC
+                world, report = VC.coregister(ref, raw, device, **coregister)
+                if coreg_reports is not None:
+                    coreg_reports.append((i, report))
+            on_grid = VR.regrid_to(raw, ref.shape, VR.world_affine_of(ref.affine, ref.header), device, header=ref.header, world=world)
             if on_grid is not raw and resampled is not None:
                 resampled.append(i)
             raw = on_grid

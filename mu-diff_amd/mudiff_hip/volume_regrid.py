@@ -110,16 +110,19 @@ class RegriddedVolume(RawVolume):
         return self.data.reshape(self.shape, order='F')
 
 
-def regrid_to(raw, ref_shape, ref_affine, device, mode='linear', header=None):
+def regrid_to(raw, ref_shape, ref_affine, device, mode='linear', header=None, world=None):
     """A RawVolume -> the same volume on the grid (ref_shape, ref_affine): a RegriddedVolume (fp32, NIFTI_F4, slope 1, inter 0, that
     geometry; `header`: the reference's) ready for volume_intake.condition_from_raw.  A volume already on that grid is returned
-    untouched.  The source's place in the world is world_affine_of(raw.affine, raw.header)."""
+    untouched.  The source's place in the world is world_affine_of(raw.affine, raw.header).  `world` (--coregister,
+    mudiff_hip.volume_coreg): a 4 x 4 matrix W that takes a world point of the reference to the source's world, so that the sampling
+    matrix is inv(source affine) @ W @ reference affine; with a W that is not the identity the volume is resampled even on its own grid."""
     if len(raw.shape) != 3 or len(ref_shape) != 3:
         raise ValueError(f'regrid: expected 3D volumes, got shapes {tuple(raw.shape)} and {tuple(ref_shape)}')
     src_affine = world_affine_of(raw.affine, raw.header)
-    if same_grid(raw.shape, src_affine, ref_shape, ref_affine):
+    moved = world is not None and not np.array_equal(np.asarray(world, np.float64), np.eye(4))
+    if not moved and same_grid(raw.shape, src_affine, ref_shape, ref_affine):
         return raw
-    M = grid_matrix(src_affine, ref_affine)
+    M = grid_matrix(src_affine, _affine44(world, 'world transform') @ _affine44(ref_affine, 'reference affine') if moved else ref_affine)
     slope, inter = (raw.slope, raw.inter) if raw.scaled else (1.0, 0.0)
     dev = regrid(upload(raw, device), raw.code, raw.shape, slope, inter, M, ref_shape, mode)
     return RegriddedVolume(dev, ref_shape, np.asarray(ref_affine, np.float64), header)
