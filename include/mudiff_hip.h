@@ -380,7 +380,30 @@ int mud_ensemble_stats(const float* samples, int n, int N, int64_t hw, float sca
  *   (fixed, mud_volume_regrid(moving, m)) over the counted samples.  bin = clamp((int)floor((double(v) - lo) * scale), 0, bins - 1), the
  *   subtraction and the product rounded separately; hist[bin_fix][bin_mov] += 1.  hist: device, uint32 [bins][bins], cleared first
  *   (stream-ordered).  Counts are integers (LDS atomics per workgroup, one global atomic per non-empty bin): the result does not depend
- *   on the order of arrival and is the same bits on every run.  bins: 2 to 64; stride > 0; m, lo and scale finite. */
+ *   on the order of arrival and is the same bits on every run.  bins: 2 to 64; stride > 0; m, lo and scale finite.
+ * mud_volume_bias_* (--bias_correct): the device's share of an N4-style bias-field correction; the loop around
+ *   them is mudiff_hip.volume_bias.loop.  Sample points: the voxels whose indices are all multiples of `shrink`, nx x ny x nz of them (nx =
+ *   ceil(X / shrink), ...), flat with x fastest.  The field F is a sum of uniform cubic B-spline lattices: level l = 0 .. levels - 1 (at
+ *   most 5) has n = 2^l spans per axis and (n + 3)^3 fp64 control points [cz][cy][cx]; `lattices` holds the levels one after the other
+ *   (device, 8-byte aligned).  On an axis of size S voxel i sits at x = (double(i) + 0.5) * double(n) / double(S), span = floor(x), t = x -
+ *   span, with weights b0 = (1 - t)^3 / 6, b1 = (3 t^3 - 6 t^2 + 4) / 6, b2 = (3 t^2 - 3 t^3 + 3 t + 1) / 6, b3 = t^3 / 6 on the control
+ *   points span .. span + 3; F = sum over levels, then over the 4 x 4 x 4 support (x fastest) of (bx * by) * bz * L.  Every fp64
+ *   expression is evaluated uncontracted in the order of tests/volume_bias_ref.py.
+ *   _log: u[sample] = logf(value of the stored voxel) where that value is finite and > 0 (the mask), NaN elsewhere.
+ *   _corrected: c_new = float32(double(u) - F), NaN where u is; stats (device, 3 x uint64, cleared first): [0] the bits of the largest
+ *     |double(c_new) - double(c_old)| that is a number (0 without any), [1] / [2] the order-preserving keys (an fp32's bits with the sign
+ *     bit set for a positive value, all bits flipped for a negative one) of the largest / smallest finite c_new; [2] stays all ones without a
+ *     finite sample.  c_new must not be u or c_old.
+ *   _hist: hist[clamp((int)floor((double(c) - lo) * scale), 0, bins - 1)] += 1 over the finite c (mud_volume_joint_hist's formula);
+ *     hist: device uint32 [bins], cleared first.  bins: 2 to 1024.
+ *   _fit: one level's multilevel-B-spline sums of the residual r = double(c) - table(c) over the finite c; table: device fp64 [bins], the
+ *     value at each bin centre, interpolated linearly in p = (double(c) - lo) * scale - 0.5 and clamped at the ends.  With w = (bx * by) * bz
+ *     and S2 = (sum bx^2)(sum by^2)(sum bz^2) each control point of the support receives llrint(((w * w) * w) * r / S2 * 2^k) into
+ *     sums[0][cp] (delta) and llrint((w * w) * 2^k) into sums[1][cp] (omega); sums: device int64 [2][(n + 3)^3], cleared first.  The caller
+ *     picks k (0 .. 62) so that no sum can overflow (volume_bias.choose_k).  level: 0 .. 4 (a lattice of more than 16 spans does not fit in LDS).
+ *   _apply: out (fp32 [Z][Y][X], 16-byte aligned, not vol) = float32(double(v) / exp(F)) at every voxel; a zero stays zero and a
+ *     non-finite voxel is passed through.  With field != 0 out is float32(exp(F)) instead.
+ *   Integer atomics only: every result is the same bits on every run. */
 #define MUD_NIFTI_U1 2
 #define MUD_NIFTI_I2 4
 #define MUD_NIFTI_I4 8
@@ -409,6 +432,14 @@ int mud_volume_regrid(const void* src, int datatype, int SX, int SY, int SZ, flo
 int mud_volume_joint_hist(const void* fix, int fix_dt, int X, int Y, int Z, float fix_slope, float fix_inter, const void* mov, int mov_dt,
                           int SX, int SY, int SZ, float mov_slope, float mov_inter, const double* m, int stride, double fix_lo,
                           double fix_scale, double mov_lo, double mov_scale, int bins, uint32_t* hist, void* stream);
+int mud_volume_bias_log(const void* vol, int datatype, int X, int Y, int Z, float slope, float inter, int shrink, float* u, void* stream);
+int mud_volume_bias_corrected(const float* u, const float* c_old, float* c_new, const double* lattices, int levels, int X, int Y, int Z,
+                              int shrink, uint64_t* stats, void* stream);
+int mud_volume_bias_hist(const float* c, int64_t n, double lo, double scale, int bins, uint32_t* hist, void* stream);
+int mud_volume_bias_fit(const float* c, const double* table, int bins, double lo, double scale, int level, int X, int Y, int Z, int shrink,
+                        int k, int64_t* sums, void* stream);
+int mud_volume_bias_apply(const void* vol, int datatype, int X, int Y, int Z, float slope, float inter, const double* lattices, int levels,
+                          int field, float* out, void* stream);
 
 #ifdef __cplusplus
 }

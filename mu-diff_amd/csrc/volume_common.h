@@ -1,4 +1,4 @@
-// What the kernels of the volume pipeline share (volume_intake.hip, volume_coreg.hip): the value of a stored voxel, the trilinear value
+// What the kernels of the volume pipeline share (volume_intake.hip, volume_coreg.hip, volume_bias.hip): the value of a stored voxel, the trilinear value
 // at a source coordinate, the datatype dispatch and the argument checks of a stored volume.  One definition each, so that a histogram
 // sample of mud_volume_joint_hist is the voxel mud_volume_regrid writes, bit for bit.
 #pragma once
@@ -54,6 +54,32 @@ __device__ __forceinline__ float vi_trilinear(const T* __restrict__ src, int SX,
   }
   return (float)acc;
 }
+
+// ---- shared by the histograms of volume_coreg.hip and volume_bias.hip: the bin of a value, a stored voxel by datatype code, finiteness
+// clamp((int)floor((double(v) - lo) * scale), 0, bins - 1), the subtraction and the product rounded separately (numpy's two steps);
+// clamped before the conversion, so that no product is too large for an int
+__device__ __forceinline__ int vc_bin(float v, double lo, double scale, int bins) {
+#pragma clang fp contract(off)
+  double d = (double)v - lo;
+  d = d * scale;
+  d = floor(d);
+  const double top = (double)(bins - 1);
+  d = d > 0.0 ? d : 0.0;
+  d = d < top ? d : top;
+  return (int)d;
+}
+
+__device__ __forceinline__ float vc_stored_value(const void* __restrict__ p, int datatype, int64_t i, int scaled, double slope, double inter) {
+  switch (datatype) {                          // uniform over the launch
+    case MUD_NIFTI_U1: return vi_value<uint8_t>(((const uint8_t*)p)[i], scaled, slope, inter);
+    case MUD_NIFTI_I2: return vi_value<int16_t>(((const int16_t*)p)[i], scaled, slope, inter);
+    case MUD_NIFTI_U2: return vi_value<uint16_t>(((const uint16_t*)p)[i], scaled, slope, inter);
+    case MUD_NIFTI_I4: return vi_value<int32_t>(((const int32_t*)p)[i], scaled, slope, inter);
+    default: return vi_value<float>(((const float*)p)[i], scaled, slope, inter);
+  }
+}
+
+__device__ __forceinline__ bool vc_finite(float v) { return fabsf(v) <= 3.402823466e38f; }
 
 static inline bool vi_scaled(float slope, float inter) {      // volume.read_nifti's condition
   return slope != 0.0f && slope - slope == 0.0f && (slope != 1.0f || inter != 0.0f);

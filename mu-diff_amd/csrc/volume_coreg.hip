@@ -13,31 +13,6 @@
 #define VC_MAX_BINS 64
 #define VC_MAX_BLOCKS 1024                     // 4 workgroups per CU: each merges up to bins^2 counts, so fewer, longer-lived groups
 
-// clamp((int)floor((double(v) - lo) * scale), 0, bins - 1), the subtraction and the product rounded separately (numpy's two steps);
-// clamped before the conversion, so that no product is too large for an int
-__device__ __forceinline__ int vc_bin(float v, double lo, double scale, int bins) {
-#pragma clang fp contract(off)
-  double d = (double)v - lo;
-  d = d * scale;
-  d = floor(d);
-  const double top = (double)(bins - 1);
-  d = d > 0.0 ? d : 0.0;
-  d = d < top ? d : top;
-  return (int)d;
-}
-
-__device__ __forceinline__ float vc_stored_value(const void* __restrict__ p, int datatype, int64_t i, int scaled, double slope, double inter) {
-  switch (datatype) {                          // uniform over the launch
-    case MUD_NIFTI_U1: return vi_value<uint8_t>(((const uint8_t*)p)[i], scaled, slope, inter);
-    case MUD_NIFTI_I2: return vi_value<int16_t>(((const int16_t*)p)[i], scaled, slope, inter);
-    case MUD_NIFTI_U2: return vi_value<uint16_t>(((const uint16_t*)p)[i], scaled, slope, inter);
-    case MUD_NIFTI_I4: return vi_value<int32_t>(((const int32_t*)p)[i], scaled, slope, inter);
-    default: return vi_value<float>(((const float*)p)[i], scaled, slope, inter);
-  }
-}
-
-__device__ __forceinline__ bool vc_finite(float v) { return fabsf(v) <= 3.402823466e38f; }
-
 struct vc_side {                               // one volume: stored voxels, how to read them, how to bin them
   const void* vol;
   int datatype, scaled;

@@ -22,6 +22,8 @@ With --regrid a subject's volumes, ground truth and mas
 on the first input's grid is resampled onto it on the device, and the subject's [done] line names it (` | regrid=T2,gt_volume`).
 With --coregister every input other than the first is first aligned to the first one rigidly; the search runs
 on the main thread between the upload and the intake, and coreg_<t>.json goes next to each subject's prediction.
+With --bias_correct every input is divided by its estimated bias field, also on the main thread between the
+upload and the intake; bias_<t>.json goes next to each subject's prediction and the [done] line names the inputs (` | bias=...`).
 """
 from __future__ import annotations
 
@@ -174,6 +176,10 @@ def run(args, subjects, predict=None):
     if getattr(args, 'coregister', False):
         from . import volume_coreg as VC
         coreg = VC.options(args)
+    bias = None
+    if getattr(args, 'bias_correct', False):
+        from . import volume_bias as VB
+        bias = VB.options(args)
     timing = dict(read=0.0, intake=0.0, sample=0.0, assemble=0.0, write=0.0, write_wait=0.0, score=0.0)
     if norm != 'percentile':                 # (a default run's report keeps the keys it had)
         timing.update(moments=0.0, read_wait=0.0)
@@ -245,13 +251,15 @@ def run(args, subjects, predict=None):
                             if r.shape != raws[0].shape:
                                 raise ValueError(f'All input volumes must share shape. Got {r.shape} vs {raws[0].shape} for {m}')
                     else:
-                        resampled, reports = [], []                # (--coregister searches here, on the main thread: it needs the GPU)
-                        conds, *ref = VI.load_conditions([subject.inputs[m] for m in needed], args.slice_half_range, args.image_size,
+                        resampled, reports, bias_reports = [], [], []      # (--coregister searches and --bias_correct estimates here,
+                        conds, *ref = VI.load_conditions([subject.inputs[m] for m in needed], args.slice_half_range, args.image_size,   # on the main thread: they need the GPU)
                                                          device, raws=raws, norm=norm, regrid=regrid, resampled=resampled,
-                                                         coregister=coreg, coreg_reports=reports)
+                                                         coregister=coreg, coreg_reports=reports, bias=bias, bias_reports=bias_reports)
                         regridded = [needed[i] for i in resampled] + regridded
                         if reports:
                             sargs.coreg_reports = [(needed[i], r) for i, r in reports]
+                        if bias_reports:
+                            sargs.bias_reports = [(needed[r[0]],) + tuple(r[1:]) for r in bias_reports]
                         torch.cuda.synchronize(device)
                     if regridded:
                         sargs.regridded = regridded                # (the [done] line names them)

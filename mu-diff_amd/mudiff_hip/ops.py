@@ -945,3 +945,97 @@ def ensemble_stats(samples, scale=1.0, shift=0.0, lo=-math.inf, hi=math.inf):
     _launch('ensemble_stats', x.device, load().mud_ensemble_stats, ptr(x), n, N, hw, float(scale), float(shift), float(lo), float(hi),
             ptr(mean), ptr(std), STREAM, nbytes=4.0 * n * hw * (N + 2))
     return mean, std
+
+
+# ---------------------------------------------------------------------------------------------------
+# --bias_correct (csrc/volume_bias.hip; the loop around these is mudiff_hip.volume_bias)
+# ---------------------------------------------------------------------------------------------------
+def _bias_samples(shape, shrink):
+    s = max(int(shrink), 1)
+    return tuple(-(-int(v) // s) for v in shape)
+
+
+def _bias_volume(what, dev_raw, code, shape):
+    from .volume_intake import DEVICE_DTYPES
+    import numpy as np
+    require_gpu(dev_raw)
+    X, Y, Z = (int(v) for v in shape)
+    if int(code) not in DEVICE_DTYPES:
+        raise MudiffHipError(f'{what}: unsupported NIfTI datatype code {code}')
+    if dev_raw.numel() != X * Y * Z or dev_raw.element_size() != np.dtype(DEVICE_DTYPES[int(code)]).itemsize or not dev_raw.is_contiguous():
+        raise MudiffHipError(f'{what}: {dev_raw.numel()} voxels of {dev_raw.element_size()} bytes do not hold a {X} x {Y} x {Z} volume of '
+                             f'datatype {code}')
+    return X, Y, Z
+
+
+def _bias_image(what, shape, shrink, *images):
+    nx, ny, nz = _bias_samples(shape, shrink)
+    for t in images:
+        if t.dtype != torch.float32 or t.numel() != nx * ny * nz or not t.is_contiguous():
+            raise MudiffHipError(f'{what}: need contiguous fp32 log images of {nx} x {ny} x {nz} samples, got {t.dtype} {tuple(t.shape)}')
+
+
+def volume_bias_log(dev_raw, code, shape, slope, inter, shrink):
+    """mud_volume_bias_log: the flat device array of a volume's stored voxels -> u, device fp32 [nz, ny, nx]: logf of every shrink-th
+    voxel per axis, NaN where it is not finite or not > 0."""
+    X, Y, Z = _bias_volume('volume_bias_log', dev_raw, code, shape)
+    nx, ny, nz = _bias_samples(shape, shrink)
+    u = torch.empty(nz, ny, nx, device=dev_raw.device, dtype=torch.float32)
+    _launch('volume_bias_log', dev_raw.device, load().mud_volume_bias_log, ptr(dev_raw), int(code), X, Y, Z, float(slope), float(inter),
+            int(shrink), ptr(u), STREAM, nbytes=float(u.numel() * (dev_raw.element_size() + 4)))
+    return u
+
+
+def _bias_lattices(what, lattices, levels):
+    need = sum(((1 << l) + 3) ** 3 for l in range(max(int(levels), 0)))
+    if lattices.dtype != torch.float64 or lattices.numel() != need or not lattices.is_contiguous():
+        raise MudiffHipError(f'{what}: {levels} levels need {need} contiguous fp64 control points, got {lattices.dtype} {tuple(lattices.shape)}')
+
+
+def volume_bias_corrected(u, c_old, c_new, lattices, levels, shape, shrink):
+    """mud_volume_bias_corrected: c_new = float32(double(u) - F) -> device int64 [3]: the bits of the largest |c_new - c_old| and the
+    order-preserving keys of the largest and the smallest finite c_new (the smallest all ones without any)."""
+    require_gpu(u, c_old, c_new, lattices)
+    _bias_image('volume_bias_corrected', shape, shrink, u, c_old, c_new)
+    _bias_lattices('volume_bias_corrected', lattices, levels)
+    X, Y, Z = (int(v) for v in shape)
+    stats = torch.empty(3, device=u.device, dtype=torch.int64)
+    _launch('volume_bias_corrected', u.device, load().mud_volume_bias_corrected, ptr(u), ptr(c_old), ptr(c_new), ptr(lattices), int(levels), X, Y,
+            Z, int(shrink), ptr(stats), STREAM, nbytes=12.0 * u.numel())
+    return stats
+
+
+def volume_bias_hist(c, lo, scale, bins):
+    """mud_volume_bias_hist -> device int32 [bins] (uint32 counts) of the finite values of c."""
+    require_gpu(c)
+    if c.dtype != torch.float32 or not c.is_contiguous():
+        raise MudiffHipError(f'volume_bias_hist: need a contiguous fp32 log image, got {c.dtype}')
+    hist = torch.empty(max(int(bins), 1), device=c.device, dtype=torch.int32)
+    _launch('volume_bias_hist', c.device, load().mud_volume_bias_hist, ptr(c), int(c.numel()), float(lo), float(scale), int(bins), ptr(hist),
+            STREAM, nbytes=4.0 * c.numel())
+    return hist
+
+
+def volume_bias_fit(c, table, lo, scale, level, shape, shrink, k):
+    """mud_volume_bias_fit -> device int64 [2, m, m, m], m = 2^level + 3: delta and omega of one level's fit of c - table(c)."""
+    require_gpu(c, table)
+    _bias_image('volume_bias_fit', shape, shrink, c)
+    if table.dtype != torch.float64 or not table.is_contiguous():
+        raise MudiffHipError(f'volume_bias_fit: need a contiguous fp64 table, got {table.dtype}')
+    X, Y, Z = (int(v) for v in shape)
+    m = (1 << min(max(int(level), 0), 8)) + 3
+    sums = torch.empty(2, m, m, m, device=c.device, dtype=torch.int64)
+    _launch('volume_bias_fit', c.device, load().mud_volume_bias_fit, ptr(c), ptr(table), int(table.numel()), float(lo), float(scale), int(level),
+            X, Y, Z, int(shrink), int(k), ptr(sums), STREAM, nbytes=4.0 * c.numel())
+    return sums
+
+
+def volume_bias_apply(dev_raw, code, shape, slope, inter, lattices, levels, field=False):
+    """mud_volume_bias_apply -> device fp32 [Z, Y, X]: every voxel / exp(F) (with `field`: exp(F) itself)."""
+    X, Y, Z = _bias_volume('volume_bias_apply', dev_raw, code, shape)
+    require_gpu(dev_raw, lattices)
+    _bias_lattices('volume_bias_apply', lattices, levels)
+    out = torch.empty(Z, Y, X, device=dev_raw.device, dtype=torch.float32)
+    _launch('volume_bias_apply', dev_raw.device, load().mud_volume_bias_apply, ptr(dev_raw), int(code), X, Y, Z, float(slope), float(inter),
+            ptr(lattices), int(levels), int(bool(field)), ptr(out), STREAM, nbytes=float(out.numel() * (dev_raw.element_size() + 4)))
+    return out

@@ -440,17 +440,24 @@ def _predict_volume(args, plan, evaluation=None):
     if getattr(args, 'coregister', False):                 # (--coregister, DESIGN.md section 5.13: implies the --regrid machinery)
         from . import volume_coreg as VC
         coreg = VC.options(args)
+    bias = None
+    if getattr(args, 'bias_correct', False):               # (--bias_correct)
+        from . import volume_bias as VB
+        bias = VB.options(args)
     if getattr(args, 'device_intake', False):
         from . import volume_intake as VI
-        resampled, reports = [], []
+        resampled, reports, bias_reports = [], [], []
         stacks, *ref = VI.load_conditions([path for _, path in needed], args.slice_half_range, args.image_size, device, norm=norm,
-                                          regrid=regrid, resampled=resampled, coregister=coreg, coreg_reports=reports)
+                                          regrid=regrid, resampled=resampled, coregister=coreg, coreg_reports=reports,
+                                          bias=bias, bias_reports=bias_reports)
         args = _with_coregistered(_with_regridded(args, [needed[i][0] for i in resampled]), [(needed[i][0], r) for i, r in reports])
+        args = _with_bias(args, [(needed[r[0]][0],) + tuple(r[1:]) for r in bias_reports])
         return predict_from_conditions(args, plan, evaluation, gen1, gen2, device, stacks, tuple(ref), on_device=True)
-    if regrid or coreg is not None:
-        reports = []
-        stacks, ref, resampled = _load_regridded(needed, args.slice_half_range, norm, device, coreg, reports)
-        args = _with_coregistered(_with_regridded(args, resampled), reports)
+    if regrid or coreg is not None or bias is not None:
+        reports, bias_reports = [], []
+        stacks, ref, resampled = _load_regridded(needed, args.slice_half_range, norm, device, coreg, reports, regrid or coreg is not None,
+                                                 bias, bias_reports)
+        args = _with_bias(_with_coregistered(_with_regridded(args, resampled), reports), bias_reports)
         return predict_from_conditions(args, plan, evaluation, gen1, gen2, device, stacks, ref)
     stacks, ref = [], None
     for m, path in needed:
@@ -481,6 +488,25 @@ def _with_coregistered(args, reports):
     return args
 
 
+def _with_bias(args, reports):
+    """args, or a copy whose `bias_reports` ([(input name, report, field or None)]: the [done] line and bias_<t>.json) is `reports`."""
+    if not reports:
+        return args
+    args = copy.copy(args)
+    args.bias_reports = list(reports)
+    return args
+
+
+def _bias_done(args, affine, header):
+    """Under --bias_correct: writes bias_<t>.json (and the fields) next to the prediction -> what the [done] line gains ('' otherwise)."""
+    reports = getattr(args, 'bias_reports', None)
+    if not reports:
+        return ''
+    from . import volume_bias as VB
+    VB.write_reports(reports, args.output_dir, args.target_modality, affine, header)
+    return VB.bias_suffix(reports)
+
+
 def _coreg_done(args):
     """Under --coregister: writes coreg_<t>.json next to the prediction -> what the [done] line gains ('' otherwise)."""
     reports = getattr(args, 'coreg_reports', None)
@@ -491,10 +517,12 @@ def _coreg_done(args):
     return VC.coreg_suffix(reports)
 
 
-def _load_regridded(needed, half_range, norm, device, coreg=None, reports=None):
+def _load_regridded(needed, half_range, norm, device, coreg=None, reports=None, regrid=True, bias=None, bias_reports=None):
     """The host path under --regrid: every input that is not on the first one's grid is uploaded as the fp32 values the pipeline sees,
     resampled on the device (mudiff_hip.volume_regrid) and downloaded; the numpy normalisation is the one of every run.  With `coreg`
     (--coregister: volume_coreg.options) each such input is first aligned to the first one (its (name, report) goes to `reports`).
+    With `bias` (--bias_correct: volume_bias.options) every input, once on the grid, is divided by its estimated bias field on the device
+    and downloaded ((name, report, field) goes to `bias_reports`); without `regrid` the inputs must share one shape, as ever.
     -> (stacks, ref, names of the resampled inputs)."""
     from . import volume_intake as VI
     from . import volume_regrid as VR
@@ -509,12 +537,18 @@ def _load_regridded(needed, half_range, norm, device, coreg=None, reports=None):
             from . import volume_coreg as VC
             world, report = VC.coregister(first, raw, device, **coreg)
             reports.append((m, report))
-        on_grid = VR.regrid_to(raw, ref[0], ref_world, device, header=ref[2], world=world)
-        if on_grid is raw:
-            vol = raw.values_float64()
+        if regrid:
+            on_grid = VR.regrid_to(raw, ref[0], ref_world, device, header=ref[2], world=world)
+        elif raw.shape != ref[0]:
+            raise ValueError(f'All input volumes must share shape. Got {raw.shape} vs {ref[0]} for {m}')
         else:
-            vol = on_grid.values_float32()
+            on_grid = raw
+        if on_grid is not raw:
             resampled.append(m)
+        if bias is not None:
+            from . import volume_bias as VB
+            on_grid = VB.corrected_input(on_grid, device, bias, m, bias_reports)
+        vol = raw.values_float64() if on_grid is raw else on_grid.values_float32()
         slices, _, _ = extract_center_slices(normalise_volume(vol, norm), half_range)
         stacks.append(np.stack(slices, 0))
     return stacks, ref, resampled
@@ -584,7 +618,7 @@ def predict_from_conditions(args, plan, evaluation, gen1, gen2, device, stacks, 
     out_path = os.path.join(args.output_dir, f'predicted_{args.target_modality.lower()}.nii.gz')
     stages.run('write', lambda: write(out_path, vol_pred, aff, hdr))
     print(f'[done] saved: {out_path} | shape={tuple(vol_pred.shape)} | slices={s0}..{s1}' + ('' if plan == 'auto' else f' | prec_plan={plan}') +
-          norm_suffix(getattr(args, 'norm', 'percentile')) + regrid_suffix(getattr(args, 'regridded', ())) + _coreg_done(args))
+          norm_suffix(getattr(args, 'norm', 'percentile')) + regrid_suffix(getattr(args, 'regridded', ())) + _coreg_done(args) + _bias_done(args, aff, hdr))
     if evaluation is not None:
         _score_prediction(args, evaluation, vol_pred, None, device)
     return out_path
@@ -634,7 +668,7 @@ def _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref, evaluation=N
         paths.append(path)
     print(f'[done] saved: {paths[0]} and {paths[1]} | shape={tuple(shp)} | slices={s0}..{s1} | {args.num_samples} samples per slice' +
           ('' if effective_prec_plan(args) == 'auto' else f' | prec_plan={effective_prec_plan(args)}') +      # (the default plan: the line as it was)
-          norm_suffix(getattr(args, 'norm', 'percentile')) + regrid_suffix(getattr(args, 'regridded', ())) + _coreg_done(args))
+          norm_suffix(getattr(args, 'norm', 'percentile')) + regrid_suffix(getattr(args, 'regridded', ())) + _coreg_done(args) + _bias_done(args, aff, hdr))
     if evaluation is not None:
         _score_prediction(args, evaluation, vols[0], vols[1], device)
     return tuple(paths)
@@ -712,6 +746,20 @@ def make_parser(prog='MU-Diff volume prediction (MI355X)'):
                    help='sampling strides of the coarse-to-fine search levels')
     p.add_argument('--coregister_max_mm', type=float, default=20.0, help='largest translation per axis the search may propose')
     p.add_argument('--coregister_max_deg', type=float, default=15.0, help='largest rotation per axis the search may propose')
+    p.add_argument('--bias_correct', action='store_true',
+                   help='divide every input by an estimate of its coil-shading (bias) field before it is normalised: an N4-style '
+                        'correction on the GPU (histogram sharpening + multilevel B-spline fit of the log image: '
+                        'mudiff_hip.volume_bias), after --regrid / --coregister; bias_<t>.json next to the prediction holds what was '
+                        'found.  --gt_volume / --eval_mask are not corrected')
+    p.add_argument('--bias_shrink', type=int, default=4, help='the field is estimated from every N-th voxel per axis')
+    p.add_argument('--bias_levels', type=int, default=4, help='B-spline levels: level l has 2^l spans per axis (1 to 5)')
+    p.add_argument('--bias_iters', type=int, default=50, help='most iterations per level')
+    p.add_argument('--bias_tol', type=float, default=1e-3, help='a level ends when no sample of the corrected log image moved by more')
+    p.add_argument('--bias_bins', type=int, default=200, help='bins of the log-intensity histogram (2 to 1024)')
+    p.add_argument('--bias_fwhm', type=float, default=0.15, help='FWHM, in log units, of the Gaussian the histogram is deconvolved by')
+    p.add_argument('--bias_wiener', type=float, default=0.01, help='noise term of the Wiener deconvolution filter')
+    p.add_argument('--bias_field_out', action='store_true',
+                   help='with --bias_correct: also write bias_field_<name>_<t>.nii.gz, exp(field) of each input on the output grid')
     from .driver import add_calibration_flags
     add_calibration_flags(p)                # (also --prec_plan)
     return p
@@ -727,6 +775,13 @@ def finish_args(p, args):
         p.error('--num_samples needs a --seed in [0, 2^64)')
     if min(args.coregister_strides) < 1 or args.coregister_max_mm < 0 or args.coregister_max_deg < 0:
         p.error('--coregister_strides must be positive, --coregister_max_mm / --coregister_max_deg not negative')
+    from .volume_bias import check_options
+    try:
+        check_options(args.bias_shrink, args.bias_levels, args.bias_iters, args.bias_tol, args.bias_bins, args.bias_fwhm, args.bias_wiener)
+    except ValueError as e:
+        p.error(str(e))
+    if args.bias_field_out and not args.bias_correct:
+        p.error('--bias_field_out needs --bias_correct')
     return args
 
 
@@ -735,8 +790,9 @@ def build_argparser(argv=None):
     the generators read and the reference parser forgot), --batch_size, --resize_back, --calibrate / --calibrate_threshold
     (mudiff_hip.precision; the record goes to <output_dir>/prec_calibration.json), --num_samples (ensembles), --gt_volume /
     --eval_mask (scoring of the written prediction, mudiff_hip.volume_metrics), --device_intake (mudiff_hip.volume_intake), --norm
-    (the training normalisation), --regrid (inputs on other voxel grids) and
-    --coregister (rigid alignment of the inputs to the first one)."""
+    (the training normalisation), --regrid (inputs on other voxel grids),
+    --coregister (rigid alignment of the inputs to the first one) and --bias_correct (removal of the coil
+    shading of every input)."""
     p = make_parser()
     return finish_args(p, p.parse_args(argv))
 

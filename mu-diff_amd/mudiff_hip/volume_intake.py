@@ -313,13 +313,15 @@ def _resized(t, image_size):
 
 
 def load_conditions(paths, half_range, image_size, device, raws=None, norm='percentile', regrid=False, resampled=None, coregister=None,
-                    coreg_reports=None):
+                    coreg_reports=None, bias=None, bias_reports=None):
     """The condition volumes of one subject (paths in MODALITY_ORDERS order; `raws`: the RawVolumes when a prefetch thread has read them
     already; `norm`: --norm) -> ([three device tensors [n,1,S,S]], shape, affine, header, s0, s1) with the geometry of the first volume.  ValueError when
     the volumes differ in shape.  With `regrid` (--regrid) a volume that is not on the first one's grid is resampled onto it on the device
     instead (mudiff_hip.volume_regrid), before it is normalised; its index in `paths` is appended to the list `resampled`.
     `coregister` (--coregister: the keyword arguments of volume_coreg.coregister, or None) first aligns each such volume to the first one
-    rigidly and resamples it through the transform found; (index, report) goes to the list `coreg_reports`."""
+    rigidly and resamples it through the transform found; (index, report) goes to the list `coreg_reports`.  `bias` (--bias_correct: the
+    keyword arguments of volume_bias.correct, or None) divides every volume, once on the grid, by its estimated bias field before it is
+    normalised; (index, report, field or None) goes to the list `bias_reports`."""
     conds, ref = [], None
     for i, path in enumerate(paths):
         raw = read_nifti_raw(path) if raws is None else raws[i]
@@ -339,6 +341,9 @@ def load_conditions(paths, half_range, image_size, device, raws=None, norm='perc
             raw = on_grid
         elif raw.shape != ref.shape:
             raise ValueError(f'All input volumes must share shape. Got {raw.shape} vs {ref.shape} for {path}')
+        if bias is not None:
+            from . import volume_bias as VB
+            raw = VB.corrected_input(raw, device, bias, i, bias_reports if bias_reports is not None else [])
         conds.append(condition_from_raw(raw, half_range, image_size, device, name=path, norm=norm))
     s0, s1 = slab_range(ref.shape[2], half_range)
     return conds, ref.shape, ref.affine, ref.header, s0, s1
