@@ -5,7 +5,8 @@
 
 What one process buys: the checkpoints are loaded, the weights packed and the sampler's hipGraphs captured once (one GraphSampler per
 (batch, image_size), reused for every subject); a small host thread pool reads and gunzips subject i+1 while the GPU samples subject i
-and compresses and writes subject i-1; intake and re-assembly run on the device (mudiff_hip.volume_intake).  All GPU work stays on one
+and compresses and writes subject i-1; the inputs go through volume_prepare.prepare_inputs like a single run's, and intake and
+re-assembly run on the device (mudiff_hip.volume_intake).  All GPU work stays on one
 stream in this process.
 
 Every subject is sampled with --seed exactly as a separate `python -m mudiff_hip.volume` run would sample it, so each written volume
@@ -125,7 +126,7 @@ def _read_subject(subject, needed, score, norm='percentile', regrid=False):
     """(prefetch thread) The subject's three condition volumes as stored (volume_intake.read_nifti_raw) and, with `score`, the
     evaluation inputs of volume.load_eval_inputs.  With norm='zscore' every volume's moments are computed here too, next to the read
     (RawVolume.moments; their seconds in RawVolume.moments_s).  With `regrid` (--regrid) the evaluation inputs stay as stored, geometry
-    included: the main thread puts them on the first input's grid.  -> (raws, evaluation inputs or None, seconds)."""
+    included: the main thread puts them on the first input's grid.  -> (raws, (gt, label or None, the gt's affine) or None, seconds)."""
     from . import volume as V
     from . import volume_intake as VI
     t0 = time.perf_counter()
@@ -143,7 +144,8 @@ def _read_subject(subject, needed, score, norm='percentile', regrid=False):
         if not subject.gt:
             raise ValueError('--score needs a ground-truth volume (the manifest\'s gt column)')
         if regrid:
-            ev = (VI.read_nifti_raw(subject.gt), VI.read_nifti_raw(subject.mask) if subject.mask else None, None)
+            gt = VI.read_nifti_raw(subject.gt)
+            ev = (gt, VI.read_nifti_raw(subject.mask) if subject.mask else None, gt.affine)
         else:
             gt, gt_aff, _ = V.read_nifti(subject.gt)
             label = V.read_nifti(subject.mask)[0] if subject.mask else None
@@ -167,19 +169,12 @@ def run(args, subjects, predict=None):
     from . import volume_intake as VI
     from . import volume_metrics as VM
     from .driver import effective_prec_plan
+    from .volume_prepare import IntakeOptions, prepare_inputs
     target = args.target_modality
     needed = V.MODALITY_ORDERS[target]
     plan = effective_prec_plan(args)
-    norm = getattr(args, 'norm', 'percentile')
-    regrid = getattr(args, 'regrid', False)
-    coreg = None
-    if getattr(args, 'coregister', False):
-        from . import volume_coreg as VC
-        coreg = VC.options(args)
-    bias = None
-    if getattr(args, 'bias_correct', False):
-        from . import volume_bias as VB
-        bias = VB.options(args)
+    options = IntakeOptions.from_args(args)
+    norm = options.norm
     timing = dict(read=0.0, intake=0.0, sample=0.0, assemble=0.0, write=0.0, write_wait=0.0, score=0.0)
     if norm != 'percentile':                 # (a default run's report keeps the keys it had)
         timing.update(moments=0.0, read_wait=0.0)
@@ -210,7 +205,7 @@ def run(args, subjects, predict=None):
                 s = next(todo, None)
                 if s is None:
                     return
-                reads.append((s, pool.submit(_read_subject, s, needed, args.score, norm, regrid)))
+                reads.append((s, pool.submit(_read_subject, s, needed, args.score, norm, options.regrid)))
 
         prefetch()
         calibrated = False
@@ -224,45 +219,25 @@ def run(args, subjects, predict=None):
                     timing['read'] += t_read
                     if norm != 'percentile':
                         timing['read_wait'] += time.perf_counter() - t0      # the main thread waiting for the read and the moments
-                        timing['moments'] += sum(getattr(r, 'moments_s', 0.0) for r in raws)
+                        timing['moments'] += sum(r.moments_s for r in raws)
                     sargs = copy.copy(args)
                     sargs.output_dir = os.path.join(args.output_dir, subject.id)
-                    evaluation = None
-                    regridded = []
-                    if ev is not None:
-                        gt, label, gt_aff = ev
-                        if regrid:                                 # the evaluation inputs onto the first input's grid
-                            from . import volume_regrid as VR
-                            gt_aff = gt.affine
-                            gt, label, regridded = VR.eval_onto_grid(raws[0].shape, VR.world_affine_of(raws[0].affine, raws[0].header), gt,
-                                                                     label, device or torch.device(f'cuda:{args.gpu_chose}'))
-                            gt_aff = raws[0].affine if 'gt_volume' in regridded else gt_aff
-                        try:
-                            VM.check_shapes(raws[0].shape, gt.shape, None if label is None else label.shape, args.slice_half_range)
-                        except ValueError as e:
-                            raise ValueError(f'ground truth / mask: {e}') from None
-                        VM.warn_affine(raws[0].affine, gt_aff, subject.inputs[needed[0]], subject.gt)
-                        evaluation = (gt, label)
+                    gpu = device or torch.device(f'cuda:{args.gpu_chose}')
+                    evaluation, resampled = None, []
+                    if ev is not None:                             # the evaluation inputs onto the first input's grid, checked
+                        evaluation, resampled = VM.eval_inputs_on_grid((raws[0].shape, raws[0].affine, raws[0].header), *ev, options.regrid,
+                                                                       options.half_range, gpu, names=(subject.inputs[needed[0]], subject.gt),
+                                                                       wording=lambda e: f'ground truth / mask: {e}')
                     torch.manual_seed(args.seed)
                     t0 = time.perf_counter()
-                    if device is None:
-                        conds, ref = raws, (raws[0].shape, raws[0].affine, raws[0].header) + VI.slab_range(raws[0].shape[2], args.slice_half_range)
-                        for r, m in zip(raws, needed):
-                            if r.shape != raws[0].shape:
-                                raise ValueError(f'All input volumes must share shape. Got {r.shape} vs {raws[0].shape} for {m}')
-                    else:
-                        resampled, reports, bias_reports = [], [], []      # (--coregister searches and --bias_correct estimates here,
-                        conds, *ref = VI.load_conditions([subject.inputs[m] for m in needed], args.slice_half_range, args.image_size,   # on the main thread: they need the GPU)
-                                                         device, raws=raws, norm=norm, regrid=regrid, resampled=resampled,
-                                                         coregister=coreg, coreg_reports=reports, bias=bias, bias_reports=bias_reports)
-                        regridded = [needed[i] for i in resampled] + regridded
-                        if reports:
-                            sargs.coreg_reports = [(needed[i], r) for i, r in reports]
-                        if bias_reports:
-                            sargs.bias_reports = [(needed[r[0]],) + tuple(r[1:]) for r in bias_reports]
+                    conds, ref, report = prepare_inputs(list(zip(needed, raws)), options, gpu,      # (--coregister and --bias_correct work
+                                                        labels=None if device is None else subject.inputs)      # here: they need the GPU)
+                    if device is not None:
+                        conds = [VI.condition_from_raw(vol, options.half_range, args.image_size, device, name=subject.inputs[m], norm=norm)
+                                 for m, vol in zip(needed, conds)]
                         torch.cuda.synchronize(device)
-                    if regridded:
-                        sargs.regridded = regridded                # (the [done] line names them)
+                    report.regridded += resampled
+                    sargs.intake_report = report                   # (the [done] line names what it lists)
                     timing['intake'] += time.perf_counter() - t0
 
                     def write(path, vol, affine, header):
@@ -271,7 +246,7 @@ def run(args, subjects, predict=None):
 
                     t0 = time.perf_counter()
                     stage = {}
-                    predict(sargs, plan, evaluation, conds, tuple(ref), write, not calibrated, stage)
+                    predict(sargs, plan, evaluation, conds, ref, write, not calibrated, stage)
                     calibrated = True
                     for k in ('sample', 'assemble'):
                         timing[k] += stage.get(k, 0.0)

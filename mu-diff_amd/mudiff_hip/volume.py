@@ -11,6 +11,10 @@ kernel, and sampled in batches of `--batch_size` through one captured hipGraph p
 Slices are independent, so the only observable difference is the order in which Gaussian draws are consumed; parity runs
 inject the draws per slice (`predict_slices(..., x_inits, zs, noises)`).
 
+Intake: every path reads the three condition files as stored (volume_intake.read_nifti_raw) and hands them to the one preparation
+stage, volume_prepare.prepare_inputs (the first input's grid; --coregister, --regrid, --bias_correct); host_stacks then normalises
+with numpy, --device_intake with volume_intake.condition_from_raw.  What the stage did travels as args.intake_report to the [done] line.
+
 NIfTI I/O: nibabel is used when importable (it is not in this image); otherwise a minimal built-in reader/writer
 handles single-file NIfTI-1 (.nii / .nii.gz, little- or big-endian, scl_slope/inter applied like get_fdata()).
 """
@@ -160,14 +164,9 @@ class NiftiHeader:
         return out
 
 
-def read_nifti(path):
-    """-> (float64 array scaled like nibabel's get_fdata(), affine [4,4], header)."""
-    try:
-        import nibabel as nib                      # noqa: F401  (preferred when present)
-        img = nib.load(path)
-        return img.get_fdata(), img.affine, img.header
-    except ImportError:
-        pass
+def open_nifti1(path):
+    """The built-in reader's first half (read_nifti, and volume_intake.read_nifti_raw): -> (the file's bytes, its NiftiHeader, its datatype
+    code).  ValueError for what is not a single-file NIfTI-1 image of a known datatype."""
     opener = gzip.open if path.endswith('.gz') else open
     with opener(path, 'rb') as f:
         buf = f.read()
@@ -180,11 +179,23 @@ def read_nifti(path):
     code = hdr._get('h', 70)[0]
     if code not in _NIFTI_DTYPES:
         raise ValueError(f'{path}: unsupported NIfTI datatype code {code}')
+    return buf, hdr, code
+
+
+def read_nifti(path):
+    """-> (float64 array scaled like nibabel's get_fdata(), affine [4,4], header)."""
+    try:
+        import nibabel as nib                      # noqa: F401  (preferred when present)
+        img = nib.load(path)
+        return img.get_fdata(), img.affine, img.header
+    except ImportError:
+        pass
+    buf, hdr, code = open_nifti1(path)
     offset = int(hdr._get('f', 108)[0])
     slope, inter = hdr._get('2f', 112)
     shape = hdr.shape
     n = int(np.prod(shape))
-    data = np.frombuffer(buf, dtype=np.dtype(endian + _NIFTI_DTYPES[code]), count=n, offset=offset).reshape(shape, order='F')
+    data = np.frombuffer(buf, dtype=np.dtype(hdr.endian + _NIFTI_DTYPES[code]), count=n, offset=offset).reshape(shape, order='F')
     data = data.astype(np.float64)
     if slope not in (0.0,) and np.isfinite(slope) and (slope != 1.0 or inter != 0.0):
         data = data * slope + inter
@@ -274,7 +285,7 @@ def calibrate_volume(args, gen1, gen2, cond_stacks, device, batch_size=32):
 def predict_slices(args, gen1, gen2, cond_stacks, device, batch_size=32, x_inits=None, zs=None, noises=None, seed=None,
                    use_graph=True, progress=None, sampler=None, return_device=False):
     """cond_stacks: three float arrays [n,X,Y] in [-1,1] (the condition contrasts, already normalised and sliced), or three device
-    tensors [n,1,X,Y] (volume_intake.load_conditions).  -> [n,S,S] float32 numpy in [0,1], S = args.image_size; with `return_device`
+    tensors [n,1,S,S] (volume_intake.condition_from_raw).  -> [n,S,S] float32 numpy in [0,1], S = args.image_size; with `return_device`
     the device tensor instead (no copy to the host).
 
     `sampler`: a sampling.GraphSampler built for these generators (any batch size, image_size x image_size) to reuse across
@@ -339,11 +350,12 @@ def predict_volume(args):
     there and its std next to it; the return value is then the pair of paths.  --prec_plan holds for the whole prediction.
     With --gt_volume (and --eval_mask) the written prediction is scored afterwards (mudiff_hip.volume_metrics): the lines are printed
     after the [done] line and metrics_<target>.json goes next to the prediction.  Those inputs are checked first, before any GPU or
-    checkpoint work."""
+    checkpoint work.  --coregister and --bias_correct add coreg_<target>.json and bias_<target>.json (and, with --bias_field_out, the
+    field volumes) next to the prediction (volume_prepare.IntakeReport.write)."""
+    from .volume_prepare import IntakeReport
     evaluation, resampled = _load_eval_inputs(args)
-    if resampled:
-        args = copy.copy(args)
-        args.regridded = list(resampled)
+    args = copy.copy(args)                               # the run's own copy: it carries the record of what the intake did
+    args.intake_report = IntakeReport(resampled)
     from . import ops
     from .driver import effective_prec_plan
     plan = effective_prec_plan(args)
@@ -373,43 +385,34 @@ def load_eval_inputs(args):
 
 def _load_eval_inputs(args):
     """load_eval_inputs -> (its result, the names of the evaluation inputs --regrid resampled)."""
-    gt_path, mask_path = getattr(args, 'gt_volume', None), getattr(args, 'eval_mask', None)
-    if gt_path is None:
-        if mask_path is not None:
+    if args.gt_volume is None:
+        if args.eval_mask is not None:
             raise ValueError('--eval_mask needs --gt_volume')
         return None, []
-    from .volume_metrics import check_shapes, warn_affine
+    from . import volume_intake as VI
+    from .volume_metrics import eval_inputs_on_grid
     _, first = _needed_inputs(args)[0]
-    resampled = []
-    if getattr(args, 'regrid', False):
-        from . import volume_intake as VI
-        from . import volume_regrid as VR
-        ref = VI.read_nifti_raw(first)
-        inp_shape, inp_aff = ref.shape, ref.affine
-        gt_raw = VI.read_nifti_raw(gt_path)
-        gt_aff = gt_raw.affine
-        gt, label, resampled = VR.eval_onto_grid(ref.shape, VR.world_affine_of(ref.affine, ref.header), gt_raw,
-                                                 None if mask_path is None else VI.read_nifti_raw(mask_path),
-                                                 torch.device(f'cuda:{args.gpu_chose}'))
+    if args.regrid:
+        inp = VI.read_nifti_raw(first)
+        ref = (inp.shape, inp.affine, inp.header)
+        gt = VI.read_nifti_raw(args.gt_volume)
+        gt_aff = gt.affine
+        label = None if args.eval_mask is None else VI.read_nifti_raw(args.eval_mask)
     else:
-        inp, inp_aff, _ = read_nifti(first)
-        inp_shape = inp.shape
-        gt, gt_aff, _ = read_nifti(gt_path)
-        label = None if mask_path is None else read_nifti(mask_path)[0]
-    try:
-        check_shapes(inp_shape, gt.shape, None if label is None else label.shape, args.slice_half_range)
-    except ValueError as e:
-        raise ValueError(f'--gt_volume / --eval_mask: {e} (the prediction has the shape of {first})') from None
-    if 'gt_volume' not in resampled:
-        warn_affine(inp_aff, gt_aff, first, gt_path)
-    return (gt, label), resampled
+        inp, inp_aff, inp_hdr = read_nifti(first)
+        ref = (inp.shape, inp_aff, inp_hdr)
+        gt, gt_aff, _ = read_nifti(args.gt_volume)
+        label = None if args.eval_mask is None else read_nifti(args.eval_mask)[0]
+    return eval_inputs_on_grid(ref, gt, label, gt_aff, args.regrid, args.slice_half_range, torch.device(f'cuda:{args.gpu_chose}'),
+                               names=(first, args.gt_volume),
+                               wording=lambda e: f'--gt_volume / --eval_mask: {e} (the prediction has the shape of {first})')
 
 
 def _score_prediction(args, evaluation, vol, std_vol, device):
     """Scores of the prediction exactly as written -> printed lines and <output_dir>/metrics_<target>.json (its path)."""
     from . import volume_metrics as VM
     gt, label = evaluation
-    rep = VM.score_arrays(vol, gt, label, std_vol, args.slice_half_range, device, norm=getattr(args, 'norm', 'percentile'))
+    rep = VM.score_arrays(vol, gt, label, std_vol, args.slice_half_range, device, norm=args.norm)
     for ln in VM.format_lines(rep):
         print(ln)
     path = VM.write_json(rep, os.path.join(args.output_dir, f'metrics_{args.target_modality.lower()}.json'))
@@ -432,126 +435,42 @@ def _predict_volume(args, plan, evaluation=None):
     torch.cuda.set_device(args.gpu_chose)
     device = torch.device(f'cuda:{args.gpu_chose}')
     gen1, gen2 = load_generators(args, device)
-    norm = getattr(args, 'norm', 'percentile')
-
-    regrid = getattr(args, 'regrid', False)
-    needed = _needed_inputs(args)
-    coreg = None
-    if getattr(args, 'coregister', False):                 # (--coregister, DESIGN.md section 5.13: implies the --regrid machinery)
-        from . import volume_coreg as VC
-        coreg = VC.options(args)
-    bias = None
-    if getattr(args, 'bias_correct', False):               # (--bias_correct)
-        from . import volume_bias as VB
-        bias = VB.options(args)
-    if getattr(args, 'device_intake', False):
-        from . import volume_intake as VI
-        resampled, reports, bias_reports = [], [], []
-        stacks, *ref = VI.load_conditions([path for _, path in needed], args.slice_half_range, args.image_size, device, norm=norm,
-                                          regrid=regrid, resampled=resampled, coregister=coreg, coreg_reports=reports,
-                                          bias=bias, bias_reports=bias_reports)
-        args = _with_coregistered(_with_regridded(args, [needed[i][0] for i in resampled]), [(needed[i][0], r) for i, r in reports])
-        args = _with_bias(args, [(needed[r[0]][0],) + tuple(r[1:]) for r in bias_reports])
-        return predict_from_conditions(args, plan, evaluation, gen1, gen2, device, stacks, tuple(ref), on_device=True)
-    if regrid or coreg is not None or bias is not None:
-        reports, bias_reports = [], []
-        stacks, ref, resampled = _load_regridded(needed, args.slice_half_range, norm, device, coreg, reports, regrid or coreg is not None,
-                                                 bias, bias_reports)
-        args = _with_bias(_with_coregistered(_with_regridded(args, resampled), reports), bias_reports)
-        return predict_from_conditions(args, plan, evaluation, gen1, gen2, device, stacks, ref)
-    stacks, ref = [], None
-    for m, path in needed:
-        slices, shp, aff, hdr, s0, s1 = load_and_preprocess_volume(path, args.slice_half_range, norm)
-        if ref is None:
-            ref = (shp, aff, hdr, s0, s1)
-        elif shp != ref[0]:
-            raise ValueError(f'All input volumes must share shape. Got {shp} vs {ref[0]} for {m}')
-        stacks.append(np.stack(slices, 0))
-    return predict_from_conditions(args, plan, evaluation, gen1, gen2, device, stacks, ref)
-
-
-def _with_regridded(args, names):
-    """args, or a copy whose `regridded` (the names the [done] line reports) has `names` in front of the evaluation inputs'."""
-    if not names:
-        return args
-    args = copy.copy(args)
-    args.regridded = list(names) + list(getattr(args, 'regridded', ()))
-    return args
-
-
-def _with_coregistered(args, reports):
-    """args, or a copy whose `coreg_reports` ([(input name, report)]: the [done] line and coreg_<t>.json) is `reports`."""
-    if not reports:
-        return args
-    args = copy.copy(args)
-    args.coreg_reports = list(reports)
-    return args
-
-
-def _with_bias(args, reports):
-    """args, or a copy whose `bias_reports` ([(input name, report, field or None)]: the [done] line and bias_<t>.json) is `reports`."""
-    if not reports:
-        return args
-    args = copy.copy(args)
-    args.bias_reports = list(reports)
-    return args
-
-
-def _bias_done(args, affine, header):
-    """Under --bias_correct: writes bias_<t>.json (and the fields) next to the prediction -> what the [done] line gains ('' otherwise)."""
-    reports = getattr(args, 'bias_reports', None)
-    if not reports:
-        return ''
-    from . import volume_bias as VB
-    VB.write_reports(reports, args.output_dir, args.target_modality, affine, header)
-    return VB.bias_suffix(reports)
-
-
-def _coreg_done(args):
-    """Under --coregister: writes coreg_<t>.json next to the prediction -> what the [done] line gains ('' otherwise)."""
-    reports = getattr(args, 'coreg_reports', None)
-    if not reports:
-        return ''
-    from . import volume_coreg as VC
-    VC.write_reports(reports, args.output_dir, args.target_modality)
-    return VC.coreg_suffix(reports)
-
-
-def _load_regridded(needed, half_range, norm, device, coreg=None, reports=None, regrid=True, bias=None, bias_reports=None):
-    """The host path under --regrid: every input that is not on the first one's grid is uploaded as the fp32 values the pipeline sees,
-    resampled on the device (mudiff_hip.volume_regrid) and downloaded; the numpy normalisation is the one of every run.  With `coreg`
-    (--coregister: volume_coreg.options) each such input is first aligned to the first one (its (name, report) goes to `reports`).
-    With `bias` (--bias_correct: volume_bias.options) every input, once on the grid, is divided by its estimated bias field on the device
-    and downloaded ((name, report, field) goes to `bias_reports`); without `regrid` the inputs must share one shape, as ever.
-    -> (stacks, ref, names of the resampled inputs)."""
     from . import volume_intake as VI
-    from . import volume_regrid as VR
-    stacks, ref, ref_world, resampled, first = [], None, None, [], None
-    for m, path in needed:
-        raw = VI.read_nifti_raw(path)
-        world = None
-        if ref is None:
-            s0, s1 = VI.slab_range(raw.shape[2], half_range) if len(raw.shape) == 3 else (0, 0)
-            ref, ref_world, first = (raw.shape, raw.affine, raw.header, s0, s1), VR.world_affine_of(raw.affine, raw.header), raw
-        elif coreg is not None:
-            from . import volume_coreg as VC
-            world, report = VC.coregister(first, raw, device, **coreg)
-            reports.append((m, report))
-        if regrid:
-            on_grid = VR.regrid_to(raw, ref[0], ref_world, device, header=ref[2], world=world)
-        elif raw.shape != ref[0]:
-            raise ValueError(f'All input volumes must share shape. Got {raw.shape} vs {ref[0]} for {m}')
-        else:
-            on_grid = raw
-        if on_grid is not raw:
-            resampled.append(m)
-        if bias is not None:
-            from . import volume_bias as VB
-            on_grid = VB.corrected_input(on_grid, device, bias, m, bias_reports)
-        vol = raw.values_float64() if on_grid is raw else on_grid.values_float32()
-        slices, _, _ = extract_center_slices(normalise_volume(vol, norm), half_range)
-        stacks.append(np.stack(slices, 0))
-    return stacks, ref, resampled
+    from .volume_prepare import IntakeOptions, prepare_inputs
+    options = IntakeOptions.from_args(args)
+    needed = _needed_inputs(args)
+    prepared, ref, report = prepare_inputs([(m, VI.read_nifti_raw(path)) for m, path in needed], options, device,
+                                           labels=dict(needed) if args.device_intake else None)      # (the device path names the file)
+    report.regridded += _intake_report(args).regridded       # the inputs first, then the evaluation inputs predict_volume resampled
+    args.intake_report = report
+    if args.device_intake:
+        stacks = [VI.condition_from_raw(vol, options.half_range, args.image_size, device, name=path, norm=options.norm)
+                  for vol, (_, path) in zip(prepared, needed)]
+    else:
+        stacks = host_stacks(prepared, options)
+    return predict_from_conditions(args, plan, evaluation, gen1, gen2, device, stacks, ref, on_device=args.device_intake)
+
+
+def host_stacks(prepared, options):
+    """The host's normalisation of volume_prepare.prepare_inputs' volumes -> one [n,X,Y] condition stack each.  An untouched file gives
+    the float64 array read_nifti returns; a volume --regrid or --bias_correct made on the device is downloaded as the fp32 it is."""
+    from .volume_regrid import RegriddedVolume
+    stacks = []
+    for vol in prepared:
+        values = vol.values_float32() if isinstance(vol, RegriddedVolume) else vol.values_float64()
+        stacks.append(np.stack(extract_center_slices(normalise_volume(values, options.norm), options.half_range)[0], 0))
+    return stacks
+
+
+def _intake_report(args):
+    """The run's volume_prepare.IntakeReport (args.intake_report; absent means empty)."""
+    from .volume_prepare import IntakeReport
+    return getattr(args, 'intake_report', None) or IntakeReport()
+
+
+def _done_tail(args, plan):
+    """What a [done] line ends in: the arithmetic plan, --norm and what the intake did, each only when it is not the default."""
+    return ('' if plan == 'auto' else f' | prec_plan={plan}') + norm_suffix(args.norm) + _intake_report(args).suffix()
 
 
 class _Stages:
@@ -588,14 +507,13 @@ def predict_from_conditions(args, plan, evaluation, gen1, gen2, device, stacks, 
         # written into an [X,Y] plane); --resize_back is this build's opt-in extension
         raise ValueError(f'in-plane size {tuple(shp[:2])} differs from --image_size {args.image_size}: the prediction cannot be '
                          'written back into the volume (pass --resize_back to resample it bilinearly)')
-    if getattr(args, 'calibrate', False) and calibrate:
+    if args.calibrate and calibrate:
         cal = calibrate_volume(args, gen1, gen2, stacks, device, batch_size=args.batch_size)
         if cal is not None:
             from .driver import write_calibration
             print(f'[calibrate] {cal.summary()}')
             print(f'[calibrate] wrote {write_calibration(cal, args.output_dir)}')
-    num_samples = getattr(args, 'num_samples', None)
-    if num_samples is not None:
+    if args.num_samples is not None:
         return _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref, evaluation, on_device, samplers, write, stages)
     n = int(stacks[0].shape[0])
     sampler = _cached_sampler(args, gen1, gen2, device, samplers, min(int(args.batch_size), n)) if n else None
@@ -617,8 +535,8 @@ def predict_from_conditions(args, plan, evaluation, gen1, gen2, device, stacks, 
     os.makedirs(args.output_dir, exist_ok=True)
     out_path = os.path.join(args.output_dir, f'predicted_{args.target_modality.lower()}.nii.gz')
     stages.run('write', lambda: write(out_path, vol_pred, aff, hdr))
-    print(f'[done] saved: {out_path} | shape={tuple(vol_pred.shape)} | slices={s0}..{s1}' + ('' if plan == 'auto' else f' | prec_plan={plan}') +
-          norm_suffix(getattr(args, 'norm', 'percentile')) + regrid_suffix(getattr(args, 'regridded', ())) + _coreg_done(args) + _bias_done(args, aff, hdr))
+    _intake_report(args).write(args.output_dir, args.target_modality, aff, hdr)
+    print(f'[done] saved: {out_path} | shape={tuple(vol_pred.shape)} | slices={s0}..{s1}' + _done_tail(args, plan))
     if evaluation is not None:
         _score_prediction(args, evaluation, vol_pred, None, device)
     return out_path
@@ -666,9 +584,9 @@ def _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref, evaluation=N
         path = os.path.join(args.output_dir, f'predicted_{args.target_modality.lower()}{suffix}.nii.gz')
         stages.run('write', lambda: write(path, vol, aff, hdr))
         paths.append(path)
+    _intake_report(args).write(args.output_dir, args.target_modality, aff, hdr)
     print(f'[done] saved: {paths[0]} and {paths[1]} | shape={tuple(shp)} | slices={s0}..{s1} | {args.num_samples} samples per slice' +
-          ('' if effective_prec_plan(args) == 'auto' else f' | prec_plan={effective_prec_plan(args)}') +      # (the default plan: the line as it was)
-          norm_suffix(getattr(args, 'norm', 'percentile')) + regrid_suffix(getattr(args, 'regridded', ())) + _coreg_done(args) + _bias_done(args, aff, hdr))
+          _done_tail(args, effective_prec_plan(args)))
     if evaluation is not None:
         _score_prediction(args, evaluation, vols[0], vols[1], device)
     return tuple(paths)

@@ -194,8 +194,7 @@ def correct(raw, device, shrink=4, levels=4, iters=50, tol=1e-3, bins=200, fwhm=
     if len(raw.shape) != 3:
         raise ValueError(f'bias correction: expected a 3D volume, got shape {tuple(raw.shape)}')
     check_options(shrink, levels, iters, tol, bins, fwhm, wiener)
-    slope, inter = (raw.slope, raw.inter) if raw.scaled else (1.0, 0.0)
-    eng = DeviceEngine(upload(raw, device), (raw.code, raw.shape, slope, inter), shrink)
+    eng = DeviceEngine(upload(raw, device), (raw.code, raw.shape) + raw.scaling, shrink)
     lattices, iterations, dmax = loop(eng, levels, iters, tol, bins, fwhm, wiener)
     eng.corrected(lattices)
     u, c = eng.u.cpu().numpy().astype(np.float64), eng.c[0].cpu().numpy().astype(np.float64)
@@ -214,23 +213,6 @@ def correct(raw, device, shrink=4, levels=4, iters=50, tol=1e-3, bins=200, fwhm=
 # ---------------------------------------------------------------------------------------------------
 # the pipeline's side
 # ---------------------------------------------------------------------------------------------------
-def options(args):
-    """None without --bias_correct, else the keyword arguments of correct() the flags ask for."""
-    if not getattr(args, 'bias_correct', False):
-        return None
-    return dict(shrink=int(getattr(args, 'bias_shrink', 4)), levels=int(getattr(args, 'bias_levels', 4)),
-                iters=int(getattr(args, 'bias_iters', 50)), tol=float(getattr(args, 'bias_tol', 1e-3)),
-                bins=int(getattr(args, 'bias_bins', 200)), fwhm=float(getattr(args, 'bias_fwhm', 0.15)),
-                wiener=float(getattr(args, 'bias_wiener', 0.01)), field=bool(getattr(args, 'bias_field_out', False)))
-
-
-def corrected_input(raw, device, bias, name, reports):
-    """One input through correct() for the pipeline: (name, report) - and the field, when asked for - goes to `reports`."""
-    out, report = correct(raw, device, **bias)
-    reports.append((name, report, getattr(out, 'field', None)))
-    return out
-
-
 def bias_suffix(reports):
     """What a [done] line gains under --bias_correct (nothing otherwise): ` | bias=<name>,<name>,...`."""
     if not reports:

@@ -283,7 +283,7 @@ def coregister(fixed_raw, moving_raw, device, strides=(4, 2, 1), bins=32, max_mm
     a_fix, a_mov = world_affine_of(fixed_raw.affine, fixed_raw.header), world_affine_of(moving_raw.affine, moving_raw.header)
     centre = grid_centre(fixed_raw.shape, a_fix)
     ranges = bin_ranges(fixed_raw, moving_raw, bins)
-    metas = [(r.code, r.shape) + ((r.slope, r.inter) if r.scaled else (1.0, 0.0)) for r in (fixed_raw, moving_raw)]
+    metas = [(r.code, r.shape) + r.scaling for r in (fixed_raw, moving_raw)]
     fix_dev, mov_dev = upload(fixed_raw, device), upload(moving_raw, device)
 
     def cost_at(params, stride):
@@ -311,14 +311,6 @@ def finish(cost_at, centre, strides, bins, max_mm, max_deg):
 # ---------------------------------------------------------------------------------------------------
 # the pipeline's side
 # ---------------------------------------------------------------------------------------------------
-def options(args):
-    """None without --coregister, else the keyword arguments of coregister() the flags ask for."""
-    if not getattr(args, 'coregister', False):
-        return None
-    return dict(strides=tuple(int(s) for s in getattr(args, 'coregister_strides', None) or (4, 2, 1)),
-                max_mm=float(getattr(args, 'coregister_max_mm', 20.0)), max_deg=float(getattr(args, 'coregister_max_deg', 15.0)))
-
-
 def coreg_suffix(reports):
     """What a [done] line gains under --coregister (nothing otherwise): ` | coreg=<name>:<mm>mm/<deg>deg,...`, the lengths of the
     translation and of the rotation vector of each registered input."""

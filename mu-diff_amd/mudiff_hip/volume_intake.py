@@ -14,14 +14,15 @@ an F-contiguous [X,Y,Z] array (volume.write_nifti's tobytes(order='F') is then a
 Every result equals the host path's bit for bit: the census values are order statistics, the thresholds are np.percentile's own
 output, and the normalisation rounds each fp32 step once like numpy.  A volume that holds NaN or inf takes the host path (with a warning).
 
+condition_from_raw is that chain for one volume; which volumes it sees - as stored, resampled (--regrid, --coregister) or bias-corrected -
+is volume_prepare.prepare_inputs' business, the same for the host path.
+
 With norm='zscore' (--norm zscore) there is no census: the two moments come from numpy on the host
 (zscore_moments, the reference's own calls on the stored array) and slab_zscore does the rest on the device, non-finite voxels included.
 """
 from __future__ import annotations
 
 import ctypes as C
-import gzip
-import struct
 import warnings
 
 import numpy as np
@@ -51,6 +52,11 @@ class RawVolume:
         """volume.read_nifti's rule for applying scl_slope / scl_inter."""
         return self.slope != 0.0 and np.isfinite(self.slope) and (self.slope != 1.0 or self.inter != 0.0)
 
+    @property
+    def scaling(self):
+        """(slope, inter) as the kernels take them: the file's where read_nifti applies them, else (1, 0)."""
+        return (self.slope, self.inter) if self.scaled else (1.0, 0.0)
+
     def values_float64(self):
         """The [X,Y,Z] float64 array volume.read_nifti returns for this file (the reference conversion)."""
         data = np.asarray(self.data).reshape(self.shape, order='F').astype(np.float64)
@@ -71,32 +77,21 @@ def read_nifti_raw(path):
     """volume.read_nifti's built-in reader without the float64 conversion -> RawVolume (stored array untouched, datatype code,
     endianness, slope, inter, shape, affine, header).  Big-endian files, datatypes the kernels do not read, non-3D images and
     nibabel-loaded images go through volume.read_nifti and come back as float32 (its values, rounded as the pipeline rounds them)."""
-    from .volume import _NIFTI_DTYPES, NiftiHeader
+    from .volume import open_nifti1
     try:
         import nibabel  # noqa: F401
         return _via_read_nifti(path)
     except ImportError:
         pass
-    opener = gzip.open if path.endswith('.gz') else open
-    with opener(path, 'rb') as f:
-        buf = f.read()
-    if len(buf) < 352:
-        raise ValueError(f'{path}: too short for a NIfTI-1 file')
-    endian = '<' if struct.unpack_from('<i', buf, 0)[0] == 348 else '>'
-    if struct.unpack_from(endian + 'i', buf, 0)[0] != 348 or buf[344:347] != b'n+1':
-        raise ValueError(f'{path}: not a single-file NIfTI-1 image (sizeof_hdr / magic mismatch)')
-    hdr = NiftiHeader(buf[:348], endian)
-    code = hdr._get('h', 70)[0]
-    if code not in _NIFTI_DTYPES:
-        raise ValueError(f'{path}: unsupported NIfTI datatype code {code}')
+    buf, hdr, code = open_nifti1(path)
     shape = hdr.shape
-    if endian != '<' or code not in DEVICE_DTYPES or len(shape) != 3:
+    if hdr.endian != '<' or code not in DEVICE_DTYPES or len(shape) != 3:
         return _via_read_nifti(path)
     offset = int(hdr._get('f', 108)[0])
     slope, inter = hdr._get('2f', 112)
     n = int(np.prod(shape))
     data = np.frombuffer(buf, dtype=np.dtype('<' + DEVICE_DTYPES[code]), count=n, offset=offset)
-    return RawVolume(data, code, endian, slope, inter, shape, hdr.affine, hdr)
+    return RawVolume(data, code, hdr.endian, slope, inter, shape, hdr.affine, hdr)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -251,7 +246,7 @@ def to_host_volume(vol_zyx):
 
 
 # ---------------------------------------------------------------------------------------------------
-# the intake of a subject's condition volumes
+# the intake of one condition volume (a subject's three: volume_prepare.prepare_inputs, then condition_from_raw on each)
 # ---------------------------------------------------------------------------------------------------
 def upload(raw, device):
     """RawVolume -> flat device tensor of the stored voxels (uint16 travels as int16 bits: the kernels reinterpret by datatype code).
@@ -289,7 +284,7 @@ def condition_from_raw(raw, half_range, image_size, device, pmin=1.0, pmax=99.0,
         raise ValueError(f'{name}: expected a 3D volume, got shape {raw.shape}')
     s0, s1 = slab_range(raw.shape[2], half_range)
     dev_raw = upload(raw, device)
-    slope, inter = (raw.slope, raw.inter) if raw.scaled else (1.0, 0.0)
+    slope, inter = raw.scaling
     if norm == 'zscore':
         mean, std = raw.moments if raw.moments is not None else zscore_moments(raw)
         return _resized(slab_zscore(dev_raw, raw.code, raw.shape, slope, inter, mean, std, s0, s1), image_size)
@@ -310,40 +305,3 @@ def _resized(t, image_size):
     if tuple(t.shape[-2:]) != (size, size):
         t = ops.resize_bilinear(t, (size, size))
     return t.contiguous()
-
-
-def load_conditions(paths, half_range, image_size, device, raws=None, norm='percentile', regrid=False, resampled=None, coregister=None,
-                    coreg_reports=None, bias=None, bias_reports=None):
-    """The condition volumes of one subject (paths in MODALITY_ORDERS order; `raws`: the RawVolumes when a prefetch thread has read them
-    already; `norm`: --norm) -> ([three device tensors [n,1,S,S]], shape, affine, header, s0, s1) with the geometry of the first volume.  ValueError when
-    the volumes differ in shape.  With `regrid` (--regrid) a volume that is not on the first one's grid is resampled onto it on the device
-    instead (mudiff_hip.volume_regrid), before it is normalised; its index in `paths` is appended to the list `resampled`.
-    `coregister` (--coregister: the keyword arguments of volume_coreg.coregister, or None) first aligns each such volume to the first one
-    rigidly and resamples it through the transform found; (index, report) goes to the list `coreg_reports`.  `bias` (--bias_correct: the
-    keyword arguments of volume_bias.correct, or None) divides every volume, once on the grid, by its estimated bias field before it is
-    normalised; (index, report, field or None) goes to the list `bias_reports`."""
-    conds, ref = [], None
-    for i, path in enumerate(paths):
-        raw = read_nifti_raw(path) if raws is None else raws[i]
-        if ref is None:
-            ref = raw
-        elif regrid or coregister is not None:
-            from . import volume_regrid as VR
-            world = None
-            if coregister is not None:
-                from . import volume_coreg as VC
-                world, report = VC.coregister(ref, raw, device, **coregister)
-                if coreg_reports is not None:
-                    coreg_reports.append((i, report))
-            on_grid = VR.regrid_to(raw, ref.shape, VR.world_affine_of(ref.affine, ref.header), device, header=ref.header, world=world)
-            if on_grid is not raw and resampled is not None:
-                resampled.append(i)
-            raw = on_grid
-        elif raw.shape != ref.shape:
-            raise ValueError(f'All input volumes must share shape. Got {raw.shape} vs {ref.shape} for {path}')
-        if bias is not None:
-            from . import volume_bias as VB
-            raw = VB.corrected_input(raw, device, bias, i, bias_reports if bias_reports is not None else [])
-        conds.append(condition_from_raw(raw, half_range, image_size, device, name=path, norm=norm))
-    s0, s1 = slab_range(ref.shape[2], half_range)
-    return conds, ref.shape, ref.affine, ref.header, s0, s1

@@ -256,6 +256,26 @@ def score_files(pred_path, gt_path, mask_path=None, std_path=None, slice_half_ra
                         norm=norm)
 
 
+def eval_inputs_on_grid(ref, gt, label, gt_affine, regrid, half_range, device, names, wording=str):
+    """The evaluation inputs of a prediction on the grid ref = (shape, affine, header) of its first input, checked: under `regrid`
+    (--regrid) `gt` and `label` are RawVolumes and what is not on that grid is resampled onto it (volume_regrid.eval_onto_grid);
+    otherwise they are arrays as volume.read_nifti returns them.  `label` may be None; `gt_affine`: the ground truth's own affine.
+    check_shapes' ValueError is raised as ValueError(wording(e)); the affines are compared (warn_affine, with `names` = what to call
+    the first input and the ground truth) unless the ground truth was just resampled.  -> ((gt, label), the names of what was resampled)."""
+    shape, affine, header = ref
+    resampled = []
+    if regrid:
+        from . import volume_regrid as VR
+        gt, label, resampled = VR.eval_onto_grid(shape, VR.world_affine_of(affine, header), gt, label, device)
+    try:
+        check_shapes(shape, gt.shape, None if label is None else label.shape, half_range)
+    except ValueError as e:
+        raise ValueError(wording(e)) from None
+    if 'gt_volume' not in resampled:
+        warn_affine(affine, gt_affine, *names)
+    return (gt, label), resampled
+
+
 def warn_affine(pred_affine, gt_affine, pred_name='the prediction', gt_name='the ground truth'):
     if np.shape(pred_affine) != np.shape(gt_affine) or not np.allclose(np.asarray(pred_affine), np.asarray(gt_affine)):
         warnings.warn(f'the affines of {pred_name} and {gt_name} differ: the volumes are compared voxel by voxel regardless')

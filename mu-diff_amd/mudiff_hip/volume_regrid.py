@@ -123,8 +123,7 @@ def regrid_to(raw, ref_shape, ref_affine, device, mode='linear', header=None, wo
     if not moved and same_grid(raw.shape, src_affine, ref_shape, ref_affine):
         return raw
     M = grid_matrix(src_affine, _affine44(world, 'world transform') @ _affine44(ref_affine, 'reference affine') if moved else ref_affine)
-    slope, inter = (raw.slope, raw.inter) if raw.scaled else (1.0, 0.0)
-    dev = regrid(upload(raw, device), raw.code, raw.shape, slope, inter, M, ref_shape, mode)
+    dev = regrid(upload(raw, device), raw.code, raw.shape, *raw.scaling, M, ref_shape, mode)
     return RegriddedVolume(dev, ref_shape, np.asarray(ref_affine, np.float64), header)
 
 

@@ -33,6 +33,7 @@ for p in (REPO, os.path.join(REPO, 'mu-diff_amd')):
 from bench import bench_config, random_weights_  # noqa: E402
 from mudiff_hip import cohort as Co  # noqa: E402
 from mudiff_hip import volume as V  # noqa: E402
+from mudiff_hip import volume_intake as VI  # noqa: E402
 
 SHAPE = (240, 240, 155)
 
@@ -84,13 +85,13 @@ def make_checkpoints(root):
 
 
 class Timed:
-    """Seconds spent inside chosen functions of mudiff_hip.volume (each call ends in a device synchronise)."""
+    """Seconds spent inside chosen functions of mudiff_hip.volume, or of `mod` (each call ends in a device synchronise)."""
 
     def __init__(self):
         self.t, self.saved = {}, []
 
-    def wrap(self, name, key):
-        fn = getattr(V, name)
+    def wrap(self, name, key, mod=V):
+        fn = getattr(mod, name)
 
         def timed(*a, **k):
             torch.cuda.synchronize()
@@ -99,12 +100,12 @@ class Timed:
             torch.cuda.synchronize()
             self.t[key] = self.t.get(key, 0.0) + time.perf_counter() - t0
             return out
-        self.saved.append((name, fn))
-        setattr(V, name, timed)
+        self.saved.append((mod, name, fn))
+        setattr(mod, name, timed)
 
     def restore(self):
-        for name, fn in self.saved:
-            setattr(V, name, fn)
+        for mod, name, fn in self.saved:
+            setattr(mod, name, fn)
 
 
 def main():
@@ -123,9 +124,10 @@ def main():
 
         # (A) the parent's way
         tm = Timed()
-        for name, key in (('load_generators', 'load_model'), ('load_and_preprocess_volume', 'read_and_intake'), ('predict_slices', 'sample'),
+        for name, key in (('load_generators', 'load_model'), ('host_stacks', 'read_and_intake'), ('predict_slices', 'sample'),
                           ('reconstruct_volume_from_slices', 'assemble'), ('write_nifti', 'write')):
             tm.wrap(name, key)
+        tm.wrap('read_nifti_raw', 'read_and_intake', VI)          # (the host path reads the files as stored, then normalises: one stage)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for s in subjects:

@@ -277,7 +277,12 @@ def runs(tmp_path_factory, head):
         torch.save({'module.' + k: v for k, v in O.make_state_dict(cfg, which, 9).items()}, str(exp / f'{name}.pth'))
     p = {k: str(tmp / f'{k}.nii.gz') for k in ('flair', 't2', 't1')}
     V.write_nifti(p['flair'], head['vol'], np.eye(4))
-    V.write_nifti(p['t2'], B.shaded_head(noise_seed=22)[0][::-1].copy(order='F') * np.float32(0.5), np.eye(4))
+    t2 = B.shaded_head(noise_seed=22)[0][::-1].copy(order='F') * np.float32(0.5)
+    V.write_nifti(p['t2'], t2, np.eye(4))
+    shifted = np.eye(4)
+    shifted[:3, 3] = (1.5, -1.0, 0.5)
+    p['t2_grid'] = str(tmp / 't2_grid.nii.gz')                                     # the same head on another grid: moved, one plane fewer
+    V.write_nifti(p['t2_grid'], t2[:, :, :-1].copy(order='F'), shifted)
     V.write_nifti(p['t1'], B.shaded_head(noise_seed=23)[0][:, ::-1].copy(order='F') * np.float32(2.0), np.eye(4))
     model = ['--target_modality', 'T1CE', '--exp', 'exp0', '--output_path', str(tmp / 'results'), '--image_size', '16', '--num_channels_dae',
              '16', '--ch_mult', '1', '2', '--attn_resolutions', '4', '--num_res_blocks', '1', '--slice_half_range', '2', '--batch_size', '5',
@@ -287,11 +292,25 @@ def runs(tmp_path_factory, head):
             'bias_dev_z': bias + ['--norm', 'zscore', '--device_intake'], 'bias_coreg': bias + ['--coregister', '--coregister_strides', '4'],
             'plain_host': [], 'plain_dev': ['--device_intake'], 'plain_host_z': ['--norm', 'zscore']}
     jobs = {k: model + a + ['--output_dir', str(tmp / k)] for k, a in jobs.items()}
+    every = ['--regrid', '--coregister', '--coregister_strides', '4'] + bias       # the three flags together, T2 on its own grid
+    on_grid = model[:model.index('--input_flair')]
+    jobs.update({k: on_grid + ['--input_flair', p['flair'], '--input_t2', p['t2_grid'], '--input_t1', p['t1']] + every + a +
+                 ['--output_dir', str(tmp / k)] for k, a in (('all_host', []), ('all_dev', ['--device_intake']))})
+    manifest = tmp / 'cohort.tsv'
+    manifest.write_text('id\tt1\tt1ce\tt2\tflair\ns0\t' + '\t'.join([p['t1'], '', p['t2_grid'], p['flair']]) + '\n')
+    cohort = on_grid + every + ['--manifest', str(manifest), '--output_dir', str(tmp / 'all_cohort')]
     log = str(tmp / 'log.json')
     code = f'''
         import contextlib, io, json, warnings
-        from mudiff_hip import volume as V
+        from mudiff_hip import cohort as Co, volume as V
         log = {{}}
+        out = io.StringIO()
+        with contextlib.redirect_stdout(out), warnings.catch_warnings():
+            warnings.simplefilter('ignore', RuntimeWarning)
+            args = Co.build_argparser({cohort!r})
+            failures = Co.run(args, Co.read_manifest(args.manifest))[1]
+        assert not failures, failures
+        log['all_cohort'] = out.getvalue()
         for name, argv in {jobs!r}.items():
             out = io.StringIO()
             with contextlib.redirect_stdout(out), warnings.catch_warnings():
@@ -337,6 +356,24 @@ def test_predict_volume_bias_correct_end_to_end(runs):
     f = V.read_nifti(str(tmp / 'bias_dev' / fields[0]))[0]
     assert f.shape == B.HEAD_SHAPE and np.isfinite(f).all() and f.min() > 0 and f.max() / f.min() > 1.2      # (the shading spans exp(0.6))
     assert not any(f.startswith('bias_field_') for f in os.listdir(tmp / 'bias_host'))
+
+
+def test_the_three_flags_together_agree_on_every_entry_point(runs):
+    """--regrid --coregister --bias_correct with T2 on another grid: the host path, --device_intake and a one-subject cohort write the
+    same prediction and the same reports and print the same [done] line."""
+    import re
+    tmp = runs['tmp']
+    where = {'all_host': tmp / 'all_host', 'all_dev': tmp / 'all_dev', 'all_cohort': tmp / 'all_cohort' / 's0'}
+    payloads = {k: _payload(str(d / 'predicted_t1ce.nii.gz')) for k, d in where.items()}
+    assert payloads['all_host'] == payloads['all_dev'] == payloads['all_cohort']
+    assert payloads['all_host'] != runs['pred']('bias_coreg')                      # (T2 really came from the other grid)
+    for report, keys in (('coreg_t1ce.json', ['T2', 'T1']), ('bias_t1ce.json', ['FLAIR', 'T2', 'T1'])):
+        reps = [json.load(open(d / report)) for d in where.values()]
+        assert reps[0] == reps[1] == reps[2] and list(reps[0]) == keys
+    lines = {k: _done(runs, k).replace(str(d), 'OUT') for k, d in where.items()}
+    print(lines['all_host'])
+    assert lines['all_host'] == lines['all_dev'] == lines['all_cohort']
+    assert re.search(r' \| regrid=T2[^|]* \| coreg=[^|]+ \| bias=FLAIR,T2,T1$', lines['all_host'])
 
 
 def test_without_the_flag_nothing_changes(runs):

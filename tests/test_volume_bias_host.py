@@ -127,14 +127,15 @@ def _argv(*extra):
 
 def test_flags_defaults_and_refusals(capsys):
     from mudiff_hip import volume as V
-    from mudiff_hip import volume_bias as VB
+    from mudiff_hip.volume_prepare import IntakeOptions
+    options = lambda args: IntakeOptions.from_args(args).bias      # noqa: E731
     args = V.build_argparser(_argv())
-    assert args.bias_correct is False and args.bias_field_out is False and VB.options(args) is None
+    assert args.bias_correct is False and args.bias_field_out is False and options(args) is None
     args = V.build_argparser(_argv('--bias_correct'))
-    assert VB.options(args) == dict(shrink=4, levels=4, iters=50, tol=1e-3, bins=200, fwhm=0.15, wiener=0.01, field=False)
+    assert options(args) == dict(shrink=4, levels=4, iters=50, tol=1e-3, bins=200, fwhm=0.15, wiener=0.01, field=False)
     args = V.build_argparser(_argv('--bias_correct', '--bias_shrink', '2', '--bias_levels', '3', '--bias_iters', '7', '--bias_tol', '0.01',
                                    '--bias_bins', '64', '--bias_fwhm', '0.2', '--bias_wiener', '0.1', '--bias_field_out'))
-    assert VB.options(args) == dict(shrink=2, levels=3, iters=7, tol=0.01, bins=64, fwhm=0.2, wiener=0.1, field=True)
+    assert options(args) == dict(shrink=2, levels=3, iters=7, tol=0.01, bins=64, fwhm=0.2, wiener=0.1, field=True)
     for bad, word in ((['--bias_shrink', '0'], 'bias_shrink'), (['--bias_levels', '0'], 'bias_levels'), (['--bias_levels', '6'], 'bias_levels'),
                       (['--bias_iters', '0'], 'bias_iters'), (['--bias_tol', '-1'], 'bias_tol'), (['--bias_tol', 'nan'], 'bias_tol'),
                       (['--bias_bins', '1'], 'bias_bins'), (['--bias_bins', '1025'], 'bias_bins'), (['--bias_fwhm', '0'], 'bias_fwhm'),

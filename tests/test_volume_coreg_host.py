@@ -129,11 +129,13 @@ def test_a_search_that_does_not_improve_returns_the_identity(subject):
 def test_flags_and_the_done_line_suffix():
     from mudiff_hip import volume as V
     from mudiff_hip import volume_coreg as VC
+    from mudiff_hip.volume_prepare import IntakeOptions
+    options = lambda args: IntakeOptions.from_args(args).coreg      # noqa: E731
     base = ['--target_modality', 'T1CE', '--output_dir', 'o', '--exp', 'e']
     args = V.build_argparser(base)
-    assert args.coregister is False and VC.options(args) is None and VC.coreg_suffix([]) == ''
+    assert args.coregister is False and options(args) is None and VC.coreg_suffix([]) == ''
     args = V.build_argparser(base + ['--coregister', '--coregister_strides', '2', '1', '--coregister_max_mm', '10', '--coregister_max_deg', '5'])
-    assert VC.options(args) == dict(strides=(2, 1), max_mm=10.0, max_deg=5.0)
-    assert VC.options(V.build_argparser(base + ['--coregister'])) == dict(strides=(4, 2, 1), max_mm=20.0, max_deg=15.0)
+    assert options(args) == dict(strides=(2, 1), max_mm=10.0, max_deg=5.0)
+    assert options(V.build_argparser(base + ['--coregister'])) == dict(strides=(4, 2, 1), max_mm=20.0, max_deg=15.0)
     reports = [('T2', dict(params=[3.0, 4.0, 0, 0, 0, 2.0], accepted=True)), ('T1', dict(params=[1.0, 0, 0, 0, 0, 0], accepted=False))]
     assert VC.coreg_suffix(reports) == ' | coreg=T2:5.00mm/2.00deg,T1:0.00mm/0.00deg'
