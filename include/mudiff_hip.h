@@ -403,7 +403,23 @@ int mud_ensemble_stats(const float* samples, int n, int N, int64_t hw, float sca
  *     picks k (0 .. 62) so that no sum can overflow (volume_bias.choose_k).  level: 0 .. 4 (a lattice of more than 16 spans does not fit in LDS).
  *   _apply: out (fp32 [Z][Y][X], 16-byte aligned, not vol) = float32(double(v) / exp(F)) at every voxel; a zero stays zero and a
  *     non-finite voxel is passed through.  With field != 0 out is float32(exp(F)) instead.
- *   Integer atomics only: every result is the same bits on every run. */
+ *   Integer atomics only: every result is the same bits on every run.
+ * mud_volume_denoise_* (--denoise; no reference counterpart): 3D non-local means of a stored volume and the
+ *   estimate of its noise level; the host's share is mudiff_hip.volume_denoise.  v = the value of a stored voxel (fp32), valid iff finite.
+ *   _residual (no reference counterpart): keys[i] (device uint32 [Z][Y][X]) = the bits of |eps|, eps = float32(sqrt(6 / 7)) *
+ *     (v - (sum of the six face neighbours in the order -x +x -y +y -z +z, fp32) / 6), for the voxels that are > 0 and whose six face
+ *     neighbours are inside the volume, valid and > 0; 0xFFFFFFFF for every other voxel.
+ *   _select_hist (no reference counterpart): one pass (0 .. 3, most significant byte first) of a radix select over n keys:
+ *     hist (device uint32 [256], cleared first)[byte 3 - pass of key] += 1 over the keys that are not 0xFFFFFFFF and whose `pass` higher
+ *     bytes equal `prefix`.  The host picks the bin that holds the wanted rank and extends the prefix by it.
+ *   _nlm (no reference counterpart): out (fp32 [Z][Y][X], not vol).  For every offset t != 0 with |t|_inf <= search, in z-outermost /
+ *     x-fastest order, q = p + t is a candidate iff it is inside the volume and p and q are valid; d2 = (the fp32 sum over the patch offsets
+ *     |o|_inf <= patch, z outermost and x fastest, of (v(p + o) - v(q + o))^2 where both voxels are inside and valid) / their number; w =
+ *     expf(-(d2 / h)), h = float32(2 * beta * sigma * sigma); in fp64 sw += w, sa += w * a(q), a = double(v), or double(v)^2 with rician.
+ *     m = (sa + wmax a(p)) / (sw + wmax), wmax the largest w, or 1 where that is not > 0 (no candidate); out = float32(m), or with rician
+ *     float32(sqrt(max(m - 2 sigma^2, 0))).  A voxel that is 0 or not valid is passed through.  zeroed (device uint32, cleared first): the
+ *     number of voxels that were not 0 and came out 0.  search: 1 .. 5, patch: 1 .. 2 (the tile and its halo of search + patch voxels per
+ *     side are staged in LDS); sigma, beta: finite and > 0.  A fixed order of accumulation: the same bits on every run. */
 #define MUD_NIFTI_U1 2
 #define MUD_NIFTI_I2 4
 #define MUD_NIFTI_I4 8
@@ -440,6 +456,10 @@ int mud_volume_bias_fit(const float* c, const double* table, int bins, double lo
                         int k, int64_t* sums, void* stream);
 int mud_volume_bias_apply(const void* vol, int datatype, int X, int Y, int Z, float slope, float inter, const double* lattices, int levels,
                           int field, float* out, void* stream);
+int mud_volume_denoise_residual(const void* vol, int datatype, int X, int Y, int Z, float slope, float inter, uint32_t* keys, void* stream);
+int mud_volume_denoise_select_hist(const uint32_t* keys, int64_t n, uint32_t prefix, int pass, uint32_t* hist, void* stream);
+int mud_volume_denoise_nlm(const void* vol, int datatype, int X, int Y, int Z, float slope, float inter, int search, int patch, double sigma,
+                           double beta, int rician, float* out, uint32_t* zeroed, void* stream);
 
 #ifdef __cplusplus
 }

@@ -151,6 +151,9 @@ _SIGNATURES = {
     'mud_volume_bias_hist': (_I, [_P, _L, _D, _D, _I, _P, _P]),
     'mud_volume_bias_fit': (_I, [_P, _P, _I, _D, _D, _I, _I, _I, _I, _I, _I, _P, _P]),
     'mud_volume_bias_apply': (_I, [_P, _I, _I, _I, _I, _F, _F, _P, _I, _I, _P, _P]),
+    'mud_volume_denoise_residual': (_I, [_P, _I, _I, _I, _I, _F, _F, _P, _P]),
+    'mud_volume_denoise_select_hist': (_I, [_P, _L, C.c_uint32, _I, _P, _P]),
+    'mud_volume_denoise_nlm': (_I, [_P, _I, _I, _I, _I, _F, _F, _I, _I, _D, _D, _I, _P, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -25,6 +25,8 @@ With --coregister every input other than the first is f
 on the main thread between the upload and the intake, and coreg_<t>.json goes next to each subject's prediction.
 With --bias_correct every input is divided by its estimated bias field, also on the main thread between the
 upload and the intake; bias_<t>.json goes next to each subject's prediction and the [done] line names the inputs (` | bias=...`).
+With --denoise every input is first replaced by its non-local-means estimate, on the main thread before all
+of the above; denoise_<t>.json goes next to each subject's prediction and the [done] line names the inputs (` | denoise=...`).
 """
 from __future__ import annotations
 

@@ -1039,3 +1039,41 @@ def volume_bias_apply(dev_raw, code, shape, slope, inter, lattices, levels, fiel
     _launch('volume_bias_apply', dev_raw.device, load().mud_volume_bias_apply, ptr(dev_raw), int(code), X, Y, Z, float(slope), float(inter),
             ptr(lattices), int(levels), int(bool(field)), ptr(out), STREAM, nbytes=float(out.numel() * (dev_raw.element_size() + 4)))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# --denoise (csrc/volume_denoise.hip; the host's share is mudiff_hip.volume_denoise)
+# ---------------------------------------------------------------------------------------------------
+def volume_denoise_residual(dev_raw, code, shape, slope, inter):
+    """mud_volume_denoise_residual: the flat device array of a volume's stored voxels -> device int32 [Z, Y, X]: the uint32 bits of the
+    pseudo-residual |eps| of every voxel of the estimation set, all ones elsewhere."""
+    X, Y, Z = _bias_volume('volume_denoise_residual', dev_raw, code, shape)
+    keys = torch.empty(Z, Y, X, device=dev_raw.device, dtype=torch.int32)
+    _launch('volume_denoise_residual', dev_raw.device, load().mud_volume_denoise_residual, ptr(dev_raw), int(code), X, Y, Z, float(slope),
+            float(inter), ptr(keys), STREAM, nbytes=float(keys.numel() * (dev_raw.element_size() + 4)))
+    return keys
+
+
+def volume_denoise_select_hist(keys, prefix, which):
+    """mud_volume_denoise_select_hist -> device int32 [256] (uint32 counts): pass `which` (0 .. 3) of the radix select over the keys
+    whose higher bytes are `prefix`."""
+    require_gpu(keys)
+    if keys.dtype != torch.int32 or not keys.is_contiguous() or keys.numel() == 0:
+        raise MudiffHipError(f'volume_denoise_select_hist: need contiguous 32-bit keys, got {keys.dtype} {tuple(keys.shape)}')
+    hist = torch.empty(256, device=keys.device, dtype=torch.int32)
+    _launch('volume_denoise_select_hist', keys.device, load().mud_volume_denoise_select_hist, ptr(keys), int(keys.numel()), int(prefix),
+            int(which), ptr(hist), STREAM, nbytes=4.0 * keys.numel())
+    return hist
+
+
+def volume_denoise_nlm(dev_raw, code, shape, slope, inter, search, patch, sigma, beta, rician=False):
+    """mud_volume_denoise_nlm -> (device fp32 [Z, Y, X]: the non-local-means estimate of every voxel; device int32 [1]: how many voxels
+    that were not 0 came out 0)."""
+    X, Y, Z = _bias_volume('volume_denoise_nlm', dev_raw, code, shape)
+    out = torch.empty(Z, Y, X, device=dev_raw.device, dtype=torch.float32)
+    zeroed = torch.empty(1, device=dev_raw.device, dtype=torch.int32)
+    side, box = 2 * int(search) + 1, 2 * int(patch) + 1
+    _launch('volume_denoise_nlm', dev_raw.device, load().mud_volume_denoise_nlm, ptr(dev_raw), int(code), X, Y, Z, float(slope), float(inter),
+            int(search), int(patch), float(sigma), float(beta), int(bool(rician)), ptr(out), ptr(zeroed), STREAM,
+            flops=2.0 * out.numel() * (side ** 3 - 1) * box ** 3, nbytes=float(out.numel() * (dev_raw.element_size() + 4)))
+    return out, zeroed

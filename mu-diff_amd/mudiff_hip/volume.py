@@ -12,7 +12,7 @@ Slices are independent, so the only observable difference is the order in which 
 inject the draws per slice (`predict_slices(..., x_inits, zs, noises)`).
 
 Intake: every path reads the three condition files as stored (volume_intake.read_nifti_raw) and hands them to the one preparation
-stage, volume_prepare.prepare_inputs (the first input's grid; --coregister, --regrid, --bias_correct); host_stacks then normalises
+stage, volume_prepare.prepare_inputs (the first input's grid; --denoise, --coregister, --regrid, --bias_correct); host_stacks then normalises
 with numpy, --device_intake with volume_intake.condition_from_raw.  What the stage did travels as args.intake_report to the [done] line.
 
 NIfTI I/O: nibabel is used when importable (it is not in this image); otherwise a minimal built-in reader/writer
@@ -350,8 +350,8 @@ def predict_volume(args):
     there and its std next to it; the return value is then the pair of paths.  --prec_plan holds for the whole prediction.
     With --gt_volume (and --eval_mask) the written prediction is scored afterwards (mudiff_hip.volume_metrics): the lines are printed
     after the [done] line and metrics_<target>.json goes next to the prediction.  Those inputs are checked first, before any GPU or
-    checkpoint work.  --coregister and --bias_correct add coreg_<target>.json and bias_<target>.json (and, with --bias_field_out, the
-    field volumes) next to the prediction (volume_prepare.IntakeReport.write)."""
+    checkpoint work.  --coregister, --bias_correct and --denoise add coreg_<target>.json, bias_<target>.json (and, with --bias_field_out,
+    the field volumes) and denoise_<target>.json next to the prediction (volume_prepare.IntakeReport.write)."""
     from .volume_prepare import IntakeReport
     evaluation, resampled = _load_eval_inputs(args)
     args = copy.copy(args)                               # the run's own copy: it carries the record of what the intake did
@@ -453,7 +453,7 @@ def _predict_volume(args, plan, evaluation=None):
 
 def host_stacks(prepared, options):
     """The host's normalisation of volume_prepare.prepare_inputs' volumes -> one [n,X,Y] condition stack each.  An untouched file gives
-    the float64 array read_nifti returns; a volume --regrid or --bias_correct made on the device is downloaded as the fp32 it is."""
+    the float64 array read_nifti returns; a volume --regrid, --bias_correct or --denoise made on the device is downloaded as the fp32 it is."""
     from .volume_regrid import RegriddedVolume
     stacks = []
     for vol in prepared:
@@ -678,6 +678,18 @@ def make_parser(prog='MU-Diff volume prediction (MI355X)'):
     p.add_argument('--bias_wiener', type=float, default=0.01, help='noise term of the Wiener deconvolution filter')
     p.add_argument('--bias_field_out', action='store_true',
                    help='with --bias_correct: also write bias_field_<name>_<t>.nii.gz, exp(field) of each input on the output grid')
+    p.add_argument('--denoise', action='store_true',
+                   help='replace every input by its 3D non-local-means estimate on its own grid (patch-similarity weighted mean over a '
+                        'search window, on the GPU: mudiff_hip.volume_denoise) before --coregister / --regrid / --bias_correct see it; '
+                        'denoise_<t>.json next to the prediction holds the noise level that was used.  --gt_volume / --eval_mask are '
+                        'not denoised')
+    p.add_argument('--denoise_sigma', type=float, default=None,
+                   help='the noise standard deviation, in stored intensity units (default: estimated per input from pseudo-residuals)')
+    p.add_argument('--denoise_search', type=int, default=2, help='search radius: candidates within this many voxels per axis (1 to 5)')
+    p.add_argument('--denoise_patch', type=int, default=1, help='patch radius: patches of (2 r + 1)^3 voxels are compared (1 to 2)')
+    p.add_argument('--denoise_beta', type=float, default=1.0, help='smoothing strength: the weights fall off with 2 beta sigma^2')
+    p.add_argument('--denoise_rician', action='store_true',
+                   help='with --denoise: average squared intensities and subtract the Rician bias 2 sigma^2 (magnitude images)')
     from .driver import add_calibration_flags
     add_calibration_flags(p)                # (also --prec_plan)
     return p
@@ -700,6 +712,11 @@ def finish_args(p, args):
         p.error(str(e))
     if args.bias_field_out and not args.bias_correct:
         p.error('--bias_field_out needs --bias_correct')
+    from .volume_denoise import check_options as check_denoise
+    try:
+        check_denoise(args.denoise_sigma, args.denoise_search, args.denoise_patch, args.denoise_beta, args.denoise_rician)
+    except ValueError as e:
+        p.error(str(e))
     return args
 
 
@@ -709,8 +726,8 @@ def build_argparser(argv=None):
     (mudiff_hip.precision; the record goes to <output_dir>/prec_calibration.json), --num_samples (ensembles), --gt_volume /
     --eval_mask (scoring of the written prediction, mudiff_hip.volume_metrics), --device_intake (mudiff_hip.volume_intake), --norm
     (the training normalisation), --regrid (inputs on other voxel grids),
-    --coregister (rigid alignment of the inputs to the first one) and --bias_correct (removal of the coil
-    shading of every input)."""
+    --coregister (rigid alignment of the inputs to the first one), --bias_correct (removal of the coil
+    shading of every input) and --denoise (non-local-means denoising of every input)."""
     p = make_parser()
     return finish_args(p, p.parse_args(argv))
 
