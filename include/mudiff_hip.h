@@ -419,7 +419,28 @@ int mud_ensemble_stats(const float* samples, int n, int N, int64_t hw, float sca
  *     m = (sa + wmax a(p)) / (sw + wmax), wmax the largest w, or 1 where that is not > 0 (no candidate); out = float32(m), or with rician
  *     float32(sqrt(max(m - 2 sigma^2, 0))).  A voxel that is 0 or not valid is passed through.  zeroed (device uint32, cleared first): the
  *     number of voxels that were not 0 and came out 0.  search: 1 .. 5, patch: 1 .. 2 (the tile and its halo of search + patch voxels per
- *     side are staged in LDS); sigma, beta: finite and > 0.  A fixed order of accumulation: the same bits on every run. */
+ *     side are staged in LDS); sigma, beta: finite and > 0.  A fixed order of accumulation: the same bits on every run.
+ * mud_volume_fg_* (--foreground; no reference counterpart): a foreground (head or object) mask of a stored volume
+ *   by thresholding and topology - not a brain extraction; the host's share (the Otsu scan) is mudiff_hip.volume_foreground.  v = the value
+ *   of a stored voxel (fp32); a candidate is a voxel whose v is finite and != 0.  Masks are uint8 [Z][Y][X] holding 0 or 1, labels int32.
+ *   _range: range (device uint32 [3], cleared first): with key(v) = bits | 0x80000000 for v >= 0 and ~bits for v < 0, [0] = the largest
+ *     ~key (the smallest candidate), [1] = the largest key, [2] = the number of candidates; all 0 without one.
+ *   _hist: hist (device uint32 [bins], cleared first)[bin(v)] += 1 over the candidates, bin = mud_volume_joint_hist's formula with lo and
+ *     scale.  bins: 16 to 1024; lo finite; scale finite and > 0.
+ *   _mask: mask[i] = 1 iff i is a candidate and bin(v) > k, else 0.  k: 0 .. bins - 2.
+ *   _morph: one erosion (dilate 0: on iff the voxel and its six face neighbours are on, a neighbour outside the volume counts as on) or
+ *     one dilation (dilate 1: on iff any of the seven is on, outside counts as off) from `in` to `out` (not in place).
+ *   _label: the 6-connected components of the voxels whose mask is `value` (1: on, 0: off): labels[i] = the smallest linear index (x
+ *     fastest) of i's component, -1 for every other voxel.  A block-based union-find in three launches (tile-local in LDS, tile faces by a
+ *     lock-free union, path compression); no launch count and no loop depends on the data beyond the depth of a tree.
+ *   _census: census (device uint32 [X*Y*Z], cleared first)[root] = the component's voxel count, with bit 31 set iff one of its voxels lies
+ *     on a face of the volume; summary (device uint64 [2], cleared first): [0] = the largest (count << 32) | (0xFFFFFFFF - root), i.e. the
+ *     largest component, the smallest root on a tie; [1] = the number of components.
+ *   _select: holes 0: mask[i] = (labels[i] == root); holes 1: mask[i] = 1 wherever labels[i] >= 0 and census[labels[i]] has bit 31 clear
+ *     (the rest of the mask stays).  count (device uint32, cleared first): the voxels switched on.
+ *   _apply: out (fp32 [Z][Y][X], not vol)[i] = v where mask[i] != 0 (its bits as they are, a NaN included), +0 elsewhere; removed (device
+ *     uint32, cleared first): the candidates outside the mask.
+ *   X*Y*Z < 2^31.  Integer atomics only: every result is the same bits on every run. */
 #define MUD_NIFTI_U1 2
 #define MUD_NIFTI_I2 4
 #define MUD_NIFTI_I4 8
@@ -460,6 +481,18 @@ int mud_volume_denoise_residual(const void* vol, int datatype, int X, int Y, int
 int mud_volume_denoise_select_hist(const uint32_t* keys, int64_t n, uint32_t prefix, int pass, uint32_t* hist, void* stream);
 int mud_volume_denoise_nlm(const void* vol, int datatype, int X, int Y, int Z, float slope, float inter, int search, int patch, double sigma,
                            double beta, int rician, float* out, uint32_t* zeroed, void* stream);
+int mud_volume_fg_range(const void* vol, int datatype, int X, int Y, int Z, float slope, float inter, uint32_t* range, void* stream);
+int mud_volume_fg_hist(const void* vol, int datatype, int X, int Y, int Z, float slope, float inter, double lo, double scale, int bins,
+                       uint32_t* hist, void* stream);
+int mud_volume_fg_mask(const void* vol, int datatype, int X, int Y, int Z, float slope, float inter, double lo, double scale, int bins, int k,
+                       uint8_t* mask, void* stream);
+int mud_volume_fg_morph(const uint8_t* in, int X, int Y, int Z, int dilate, uint8_t* out, void* stream);
+int mud_volume_fg_label(const uint8_t* mask, int X, int Y, int Z, int value, int32_t* labels, void* stream);
+int mud_volume_fg_census(const int32_t* labels, int X, int Y, int Z, uint32_t* census, uint64_t* summary, void* stream);
+int mud_volume_fg_select(const int32_t* labels, const uint32_t* census, int64_t n, int root, int holes, uint8_t* mask, uint32_t* count,
+                         void* stream);
+int mud_volume_fg_apply(const void* vol, int datatype, int X, int Y, int Z, float slope, float inter, const uint8_t* mask, float* out,
+                        uint32_t* removed, void* stream);
 
 #ifdef __cplusplus
 }

@@ -27,6 +27,8 @@ With --bias_correct every input is divided by its estim
 upload and the intake; bias_<t>.json goes next to each subject's prediction and the [done] line names the inputs (` | bias=...`).
 With --denoise every input is first replaced by its non-local-means estimate, on the main thread before all
 of the above; denoise_<t>.json goes next to each subject's prediction and the [done] line names the inputs (` | denoise=...`).
+With --foreground every input then has the voxels outside its foreground mask set to 0, on the main thread right
+after the denoising; foreground_<t>.json goes next to each subject's prediction and the [done] line names the inputs (` | foreground=...`).
 """
 from __future__ import annotations
 

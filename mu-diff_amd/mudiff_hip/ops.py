@@ -1077,3 +1077,103 @@ def volume_denoise_nlm(dev_raw, code, shape, slope, inter, search, patch, sigma,
             int(search), int(patch), float(sigma), float(beta), int(bool(rician)), ptr(out), ptr(zeroed), STREAM,
             flops=2.0 * out.numel() * (side ** 3 - 1) * box ** 3, nbytes=float(out.numel() * (dev_raw.element_size() + 4)))
     return out, zeroed
+
+
+# ---------------------------------------------------------------------------------------------------
+# --foreground (csrc/volume_foreground.hip; the host's share is mudiff_hip.volume_foreground)
+# ---------------------------------------------------------------------------------------------------
+def _fg_grid(what, t, shape, dtype):
+    require_gpu(t)
+    X, Y, Z = (int(v) for v in shape)
+    if t.dtype != dtype or t.numel() != X * Y * Z or not t.is_contiguous():
+        raise MudiffHipError(f'{what}: need a contiguous {dtype} volume of {X} x {Y} x {Z} voxels, got {t.dtype} {tuple(t.shape)}')
+    return X, Y, Z
+
+
+def volume_fg_range(dev_raw, code, shape, slope, inter):
+    """mud_volume_fg_range -> device int32 [3] (uint32): the largest ~key and the largest key of the candidates (the finite voxels that
+    are != 0) and their number (volume_foreground.range_of decodes them)."""
+    X, Y, Z = _bias_volume('volume_fg_range', dev_raw, code, shape)
+    out = torch.empty(3, device=dev_raw.device, dtype=torch.int32)
+    _launch('volume_fg_range', dev_raw.device, load().mud_volume_fg_range, ptr(dev_raw), int(code), X, Y, Z, float(slope), float(inter), ptr(out),
+            STREAM, nbytes=float(dev_raw.numel() * dev_raw.element_size()))
+    return out
+
+
+def volume_fg_hist(dev_raw, code, shape, slope, inter, lo, scale, bins):
+    """mud_volume_fg_hist -> device int32 [bins] (uint32 counts) of the candidates."""
+    X, Y, Z = _bias_volume('volume_fg_hist', dev_raw, code, shape)
+    hist = torch.empty(max(int(bins), 1), device=dev_raw.device, dtype=torch.int32)
+    _launch('volume_fg_hist', dev_raw.device, load().mud_volume_fg_hist, ptr(dev_raw), int(code), X, Y, Z, float(slope), float(inter), float(lo),
+            float(scale), int(bins), ptr(hist), STREAM, nbytes=float(dev_raw.numel() * dev_raw.element_size()))
+    return hist
+
+
+def volume_fg_mask(dev_raw, code, shape, slope, inter, lo, scale, bins, k):
+    """mud_volume_fg_mask -> device uint8 [Z, Y, X]: 1 for a candidate whose bin is above k."""
+    X, Y, Z = _bias_volume('volume_fg_mask', dev_raw, code, shape)
+    mask = torch.empty(Z, Y, X, device=dev_raw.device, dtype=torch.uint8)
+    _launch('volume_fg_mask', dev_raw.device, load().mud_volume_fg_mask, ptr(dev_raw), int(code), X, Y, Z, float(slope), float(inter), float(lo),
+            float(scale), int(bins), int(k), ptr(mask), STREAM, nbytes=float(dev_raw.numel() * (dev_raw.element_size() + 1)))
+    return mask
+
+
+def volume_fg_morph(mask, shape, dilate):
+    """mud_volume_fg_morph -> device uint8 [Z, Y, X]: one erosion (dilate False) or one dilation of the mask over the 6-neighbourhood."""
+    X, Y, Z = _fg_grid('volume_fg_morph', mask, shape, torch.uint8)
+    out = torch.empty(Z, Y, X, device=mask.device, dtype=torch.uint8)
+    _launch('volume_fg_morph', mask.device, load().mud_volume_fg_morph, ptr(mask), X, Y, Z, int(bool(dilate)), ptr(out), STREAM,
+            nbytes=2.0 * mask.numel())
+    return out
+
+
+def volume_fg_label(mask, shape, value):
+    """mud_volume_fg_label -> device int32 [Z, Y, X]: the smallest linear index of the 6-connected component of every voxel whose mask
+    is `value` (0 or 1), -1 elsewhere."""
+    X, Y, Z = _fg_grid('volume_fg_label', mask, shape, torch.uint8)
+    labels = torch.empty(Z, Y, X, device=mask.device, dtype=torch.int32)
+    _launch('volume_fg_label', mask.device, load().mud_volume_fg_label, ptr(mask), X, Y, Z, int(value), ptr(labels), STREAM,
+            nbytes=14.0 * mask.numel())
+    return labels
+
+
+def volume_fg_census(labels, shape):
+    """mud_volume_fg_census -> (device int32 [X*Y*Z] (uint32): per root the voxel count, bit 31 set for a component on a face of the
+    volume; device int64 [2] (uint64): the winner (count << 32) | (0xFFFFFFFF - root) and the number of components)."""
+    X, Y, Z = _fg_grid('volume_fg_census', labels, shape, torch.int32)
+    census = torch.empty(X * Y * Z, device=labels.device, dtype=torch.int32)
+    summary = torch.empty(2, device=labels.device, dtype=torch.int64)
+    _launch('volume_fg_census', labels.device, load().mud_volume_fg_census, ptr(labels), X, Y, Z, ptr(census), ptr(summary), STREAM,
+            nbytes=16.0 * labels.numel())
+    return census, summary
+
+
+def volume_fg_select(labels, census, root, holes, mask=None):
+    """mud_volume_fg_select -> (mask, device int32 [1]: the voxels switched on).  holes False: a new mask, 1 where the label is `root`;
+    holes True: `mask` itself, with every labelled component that does not touch a face (census) switched on."""
+    require_gpu(labels, census, mask)
+    if labels.dtype != torch.int32 or not labels.is_contiguous() or labels.numel() == 0:
+        raise MudiffHipError(f'volume_fg_select: need contiguous int32 labels, got {labels.dtype} {tuple(labels.shape)}')
+    if holes:
+        if mask is None or mask.dtype != torch.uint8 or mask.numel() != labels.numel() or not mask.is_contiguous():
+            raise MudiffHipError('volume_fg_select: filling the holes needs the uint8 mask the complement was labelled from')
+        if census is None or census.dtype != torch.int32 or census.numel() != labels.numel() or not census.is_contiguous():
+            raise MudiffHipError('volume_fg_select: filling the holes needs the census of the labels')
+    else:
+        mask = torch.empty(labels.shape, device=labels.device, dtype=torch.uint8)
+    count = torch.empty(1, device=labels.device, dtype=torch.int32)
+    _launch('volume_fg_select', labels.device, load().mud_volume_fg_select, ptr(labels), ptr(census), int(labels.numel()), int(root),
+            int(bool(holes)), ptr(mask), ptr(count), STREAM, nbytes=5.0 * labels.numel())
+    return mask, count
+
+
+def volume_fg_apply(dev_raw, code, shape, slope, inter, mask):
+    """mud_volume_fg_apply -> (device fp32 [Z, Y, X]: the voxel inside the mask, +0 outside; device int32 [1]: the candidates outside)."""
+    X, Y, Z = _bias_volume('volume_fg_apply', dev_raw, code, shape)
+    _fg_grid('volume_fg_apply', mask, shape, torch.uint8)
+    require_gpu(dev_raw, mask)
+    out = torch.empty(Z, Y, X, device=dev_raw.device, dtype=torch.float32)
+    removed = torch.empty(1, device=dev_raw.device, dtype=torch.int32)
+    _launch('volume_fg_apply', dev_raw.device, load().mud_volume_fg_apply, ptr(dev_raw), int(code), X, Y, Z, float(slope), float(inter), ptr(mask),
+            ptr(out), ptr(removed), STREAM, nbytes=float(out.numel() * (dev_raw.element_size() + 5)))
+    return out, removed

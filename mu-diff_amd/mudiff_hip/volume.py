@@ -12,7 +12,7 @@ Slices are independent, so the only observable difference is the order in which 
 inject the draws per slice (`predict_slices(..., x_inits, zs, noises)`).
 
 Intake: every path reads the three condition files as stored (volume_intake.read_nifti_raw) and hands them to the one preparation
-stage, volume_prepare.prepare_inputs (the first input's grid; --denoise, --coregister, --regrid, --bias_correct); host_stacks then normalises
+stage, volume_prepare.prepare_inputs (the first input's grid; --denoise, --foreground, --coregister, --regrid, --bias_correct); host_stacks then normalises
 with numpy, --device_intake with volume_intake.condition_from_raw.  What the stage did travels as args.intake_report to the [done] line.
 
 NIfTI I/O: nibabel is used when importable (it is not in this image); otherwise a minimal built-in reader/writer
@@ -350,8 +350,9 @@ def predict_volume(args):
     there and its std next to it; the return value is then the pair of paths.  --prec_plan holds for the whole prediction.
     With --gt_volume (and --eval_mask) the written prediction is scored afterwards (mudiff_hip.volume_metrics): the lines are printed
     after the [done] line and metrics_<target>.json goes next to the prediction.  Those inputs are checked first, before any GPU or
-    checkpoint work.  --coregister, --bias_correct and --denoise add coreg_<target>.json, bias_<target>.json (and, with --bias_field_out,
-    the field volumes) and denoise_<target>.json next to the prediction (volume_prepare.IntakeReport.write)."""
+    checkpoint work.  --coregister, --bias_correct, --denoise and --foreground add coreg_<target>.json, bias_<target>.json (and, with
+    --bias_field_out, the field volumes), denoise_<target>.json and foreground_<target>.json (and, with --foreground_mask_out, the masks)
+    next to the prediction (volume_prepare.IntakeReport.write)."""
     from .volume_prepare import IntakeReport
     evaluation, resampled = _load_eval_inputs(args)
     args = copy.copy(args)                               # the run's own copy: it carries the record of what the intake did
@@ -453,7 +454,7 @@ def _predict_volume(args, plan, evaluation=None):
 
 def host_stacks(prepared, options):
     """The host's normalisation of volume_prepare.prepare_inputs' volumes -> one [n,X,Y] condition stack each.  An untouched file gives
-    the float64 array read_nifti returns; a volume --regrid, --bias_correct or --denoise made on the device is downloaded as the fp32 it is."""
+    the float64 array read_nifti returns; a volume --regrid, --bias_correct, --denoise or --foreground made on the device is downloaded as the fp32 it is."""
     from .volume_regrid import RegriddedVolume
     stacks = []
     for vol in prepared:
@@ -690,6 +691,18 @@ def make_parser(prog='MU-Diff volume prediction (MI355X)'):
     p.add_argument('--denoise_beta', type=float, default=1.0, help='smoothing strength: the weights fall off with 2 beta sigma^2')
     p.add_argument('--denoise_rician', action='store_true',
                    help='with --denoise: average squared intensities and subtract the Rician bias 2 sigma^2 (magnitude images)')
+    p.add_argument('--foreground', action='store_true',
+                   help='set the voxels outside a foreground mask of every input to exactly 0, on its own grid, after --denoise and before '
+                        '--coregister / --regrid / --bias_correct see it (Otsu threshold, largest 6-connected component, holes filled, on '
+                        'the GPU: mudiff_hip.volume_foreground); foreground_<t>.json next to the prediction holds what was found.  This is '
+                        'a head / object mask by thresholding and topology, NOT a brain extraction: the skull stays.  --gt_volume / '
+                        '--eval_mask are not masked')
+    p.add_argument('--foreground_bins', type=int, default=256, help='bins of the histogram the Otsu threshold is taken from (16 to 1024)')
+    p.add_argument('--foreground_open', type=int, default=0,
+                   help='open the thresholded mask first: this many erosions, then as many dilations, over the 6-neighbourhood (0 to 3)')
+    p.add_argument('--foreground_keep_holes', action='store_true', help='with --foreground: do not fill the holes of the kept component')
+    p.add_argument('--foreground_mask_out', action='store_true',
+                   help='with --foreground: also write foreground_<t>_<name>.nii.gz, the uint8 mask of each input on its own grid')
     from .driver import add_calibration_flags
     add_calibration_flags(p)                # (also --prec_plan)
     return p
@@ -717,6 +730,11 @@ def finish_args(p, args):
         check_denoise(args.denoise_sigma, args.denoise_search, args.denoise_patch, args.denoise_beta, args.denoise_rician)
     except ValueError as e:
         p.error(str(e))
+    from .volume_foreground import check_options as check_foreground
+    try:
+        check_foreground(args.foreground_bins, args.foreground_open, args.foreground_keep_holes, args.foreground_mask_out)
+    except ValueError as e:
+        p.error(str(e))
     return args
 
 
@@ -727,7 +745,8 @@ def build_argparser(argv=None):
     --eval_mask (scoring of the written prediction, mudiff_hip.volume_metrics), --device_intake (mudiff_hip.volume_intake), --norm
     (the training normalisation), --regrid (inputs on other voxel grids),
     --coregister (rigid alignment of the inputs to the first one), --bias_correct (removal of the coil
-    shading of every input) and --denoise (non-local-means denoising of every input)."""
+    shading of every input), --denoise (non-local-means denoising of every input) and
+    --foreground (a foreground mask of every input: everything outside becomes 0)."""
     p = make_parser()
     return finish_args(p, p.parse_args(argv))
 

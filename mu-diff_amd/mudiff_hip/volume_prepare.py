@@ -1,9 +1,9 @@
-"""The one input-preparation stage of the volume pipeline (DESIGN.md sections 5.10 - 5.15): every entry point - volume.predict_volume
+"""The one input-preparation stage of the volume pipeline (DESIGN.md sections 5.10 - 5.16): every entry point - volume.predict_volume
 on the host, with --device_intake, and mudiff_hip.cohort - reads a subject's files, hands them to prepare_inputs and normalises what
 comes back, on the host (volume.host_stacks) or on the device (volume_intake.condition_from_raw).
 
-    IntakeOptions.from_args(args)                         what --norm / --regrid / --coregister / --bias_correct / --denoise ask for, built once
-    prepare_inputs(named_raws, options, device)           denoise; first input = the grid; coregister; regrid, or check the shape; bias-correct
+    IntakeOptions.from_args(args)                         what --norm / --regrid / --coregister / --bias_correct / --denoise / --foreground ask for, built once
+    prepare_inputs(named_raws, options, device)           denoise; foreground; first input = the grid; coregister; regrid, or check the shape; bias-correct
     IntakeReport                                          what that did, by modality name: the [done] line's tail and the report files
 """
 from __future__ import annotations
@@ -13,23 +13,25 @@ import collections
 from . import volume_bias as VB
 from . import volume_coreg as VC
 from . import volume_denoise as VD
+from . import volume_foreground as VF
 from . import volume_regrid as VR
 from .volume import regrid_suffix
 from .volume_intake import slab_range
 
 
-class IntakeOptions(collections.namedtuple('IntakeOptions', 'norm regrid coreg bias half_range denoise',
-                                           defaults=('percentile', False, None, None, 80, None))):
-    """norm: --norm; regrid: --regrid; coreg / bias / denoise: the keyword arguments of volume_coreg.coregister / volume_bias.correct /
-    volume_denoise.denoise, or None without --coregister / --bias_correct / --denoise; half_range: --slice_half_range (the slab is part
-    of the reference geometry)."""
+class IntakeOptions(collections.namedtuple('IntakeOptions', 'norm regrid coreg bias half_range foreground denoise',
+                                           defaults=('percentile', False, None, None, 80, None, None))):
+    """norm: --norm; regrid: --regrid; coreg / bias / denoise / foreground: the keyword arguments of volume_coreg.coregister /
+    volume_bias.correct / volume_denoise.denoise / volume_foreground.foreground, or None without --coregister / --bias_correct / --denoise /
+    --foreground; half_range: --slice_half_range (the slab is part of the reference geometry).  `foreground` sits before `denoise`,
+    not at the end: tests/test_volume_denoise_host.py pins `denoise` as the last field, and every positional use stops at half_range."""
     __slots__ = ()
 
     @classmethod
     def from_args(cls, args):
         """The only place that knows the flags' defaults (a namespace that did not come from volume.make_parser may lack any of them)."""
         get = lambda name, default: getattr(args, name, default)      # noqa: E731
-        coreg = bias = denoise = None
+        coreg = bias = denoise = foreground = None
         if get('coregister', False):
             coreg = dict(strides=tuple(int(s) for s in get('coregister_strides', None) or (4, 2, 1)),
                          max_mm=float(get('coregister_max_mm', 20.0)), max_deg=float(get('coregister_max_deg', 15.0)))
@@ -40,30 +42,37 @@ class IntakeOptions(collections.namedtuple('IntakeOptions', 'norm regrid coreg b
             denoise = dict(sigma=None if sigma is None else float(sigma), search=int(get('denoise_search', VD.DEFAULTS['search'])),
                            patch=int(get('denoise_patch', VD.DEFAULTS['patch'])), beta=float(get('denoise_beta', VD.DEFAULTS['beta'])),
                            rician=bool(get('denoise_rician', False)))
-        return cls(get('norm', 'percentile'), bool(get('regrid', False)), coreg, bias, int(get('slice_half_range', 80)), denoise)
+        if get('foreground', False):
+            foreground = dict(bins=int(get('foreground_bins', VF.DEFAULTS['bins'])), open=int(get('foreground_open', VF.DEFAULTS['open'])),
+                              keep_holes=bool(get('foreground_keep_holes', False)), mask_out=bool(get('foreground_mask_out', False)))
+        return cls(get('norm', 'percentile'), bool(get('regrid', False)), coreg, bias, int(get('slice_half_range', 80)), foreground, denoise)
 
 
 class IntakeReport:
     """What the preparation did to one subject, by modality name: `regridded` [name] (a caller appends the evaluation inputs --regrid
     resampled: `report.regridded += names`), `coreg` [(name, report)], `bias` [(name, report, field or None)], `denoise` [(name,
-    report)]."""
+    report)], `foreground` [(name, report, the masked volume or None)]."""
 
     def __init__(self, regridded=()):
-        self.regridded, self.coreg, self.bias, self.denoise = list(regridded), [], [], []
+        self.regridded, self.coreg, self.bias, self.denoise, self.foreground = list(regridded), [], [], [], []
 
     def suffix(self):
-        """What a [done] line gains: ` | regrid=... | coreg=... | bias=... | denoise=...`, each part only when its list is not empty."""
-        return regrid_suffix(self.regridded) + VC.coreg_suffix(self.coreg) + VB.bias_suffix(self.bias) + VD.denoise_suffix(self.denoise)
+        """What a [done] line gains: ` | regrid=... | coreg=... | bias=... | denoise=... | foreground=...`, each part only when its list is
+        not empty."""
+        return (regrid_suffix(self.regridded) + VC.coreg_suffix(self.coreg) + VB.bias_suffix(self.bias) + VD.denoise_suffix(self.denoise) +
+                VF.foreground_suffix(self.foreground))
 
     def write(self, output_dir, target, affine, header):
-        """coreg_<t>.json, bias_<t>.json (and the fields --bias_field_out asked for) and denoise_<t>.json next to the prediction; nothing
-        when empty."""
+        """coreg_<t>.json, bias_<t>.json (and the fields --bias_field_out asked for) , denoise_<t>.json and foreground_<t>.json (and the masks
+        --foreground_mask_out asked for) next to the prediction; nothing when empty."""
         if self.coreg:
             VC.write_reports(self.coreg, output_dir, target)
         if self.bias:
             VB.write_reports(self.bias, output_dir, target, affine, header)
         if self.denoise:
             VD.write_reports(self.denoise, output_dir, target)
+        if self.foreground:
+            VF.write_reports(self.foreground, output_dir, target, affine, header)
 
 
 def prepare_inputs(named_raws, options, device, labels=None):
@@ -73,6 +82,8 @@ def prepare_inputs(named_raws, options, device, labels=None):
 
     Under --denoise every input, the first included, is first replaced by its non-local-means estimate on its own grid
     (volume_denoise.denoise: same shape, affine and header), and everything below sees the denoised list.
+    Under --foreground every input, the first included, then has the voxels outside its foreground mask set to exactly 0, on its own grid
+    (volume_foreground.foreground: same shape, affine and header again), and everything below sees the masked list.
     The first input defines the grid and is never registered or resampled.  Every later one is aligned to it under --coregister
     (volume_coreg.coregister -> world), then resampled under --regrid or --coregister (volume_regrid.regrid_to: untouched when it is on the
     grid already); otherwise it must have the first one's shape.  Under --bias_correct every input, the first included, is then divided by
@@ -89,6 +100,13 @@ def prepare_inputs(named_raws, options, device, labels=None):
             report.denoise.append((name, found))
             cleaned.append((name, vol))
         named_raws = cleaned
+    if options.foreground is not None:
+        masked = []
+        for name, raw in named_raws:
+            vol, found = VF.foreground(raw, device, **options.foreground)
+            report.foreground.append((name, found, vol if options.foreground['mask_out'] and vol is not raw else None))
+            masked.append((name, vol))
+        named_raws = masked
     first = named_raws[0][1]
     ref = (first.shape, first.affine, first.header) + slab_range(first.shape[2], options.half_range)
     ref_world = VR.world_affine_of(first.affine, first.header)
