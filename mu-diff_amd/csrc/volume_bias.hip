@@ -64,33 +64,23 @@ __device__ __forceinline__ double vb_field(const double* lat, int levels, int ix
   return acc;
 }
 
-// order-preserving key of an fp32: unsigned comparison of keys = comparison of values
-__device__ __forceinline__ uint32_t vb_key(float v) {
-  const uint32_t b = __float_as_uint(v);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
 struct vb_grid {                               // the sample points: every shrink-th voxel of X x Y x Z
   int X, Y, Z, shrink, nx, ny;
   int64_t n;
 };
 
 __device__ __forceinline__ void vb_sample(const vb_grid& g, int64_t i, int& xi, int& yj, int& zk) {
-  const uint32_t l = (uint32_t)i;              // n <= X*Y*Z < 2^31: 32-bit divisions
-  const uint32_t row = l / (uint32_t)g.nx;
-  xi = (int)(l - row * (uint32_t)g.nx) * g.shrink;
-  yj = (int)(row % (uint32_t)g.ny) * g.shrink;
-  zk = (int)(row / (uint32_t)g.ny) * g.shrink;
+  vi_xyz(i, g.nx, g.ny, xi, yj, zk);
+  xi *= g.shrink, yj *= g.shrink, zk *= g.shrink;
 }
 
 // ---- 1: u = logf(v) at the sample points, NaN where the sample is masked out (v not finite, or not > 0)
 template <typename T>
-__global__ __launch_bounds__(VI_THREADS) void k_vb_log(const T* __restrict__ vol, int scaled, double slope, double inter, vb_grid g,
-                                                       float* __restrict__ u) {
-  for (int64_t i = (int64_t)blockIdx.x * VI_THREADS + threadIdx.x; i < g.n; i += (int64_t)gridDim.x * VI_THREADS) {
+__global__ __launch_bounds__(VI_THREADS) void k_vb_log(vi_source src, vb_grid g, float* __restrict__ u) {
+  VI_GRID_STRIDE(i, g.n) {
     int xi, yj, zk;
     vb_sample(g, i, xi, yj, zk);
-    const float v = vi_value<T>(vol[((int64_t)zk * g.Y + yj) * g.X + xi], scaled, slope, inter);
+    const float v = vi_at<T>(src, ((int64_t)zk * g.Y + yj) * g.X + xi);
     u[i] = (vc_finite(v) && v > 0.0f) ? logf(v) : __uint_as_float(0x7fc00000u);
   }
 }
@@ -110,7 +100,7 @@ __global__ __launch_bounds__(VI_THREADS) void k_vb_corrected(const float* __rest
   }
   __syncthreads();
   unsigned long long dmax = 0ull, kmax = 0ull, kmin = ~0ull;
-  for (int64_t i = (int64_t)blockIdx.x * VI_THREADS + threadIdx.x; i < g.n; i += (int64_t)gridDim.x * VI_THREADS) {
+  VI_GRID_STRIDE(i, g.n) {
     const float uv = u[i];
     float c = uv;
     if (uv == uv) {
@@ -120,7 +110,7 @@ __global__ __launch_bounds__(VI_THREADS) void k_vb_corrected(const float* __rest
     }
     c_new[i] = c;
     if (vc_finite(c)) {
-      const unsigned long long key = vb_key(c);
+      const unsigned long long key = vc_key(c);
       kmax = key > kmax ? key : kmax;
       kmin = key < kmin ? key : kmin;
     }
@@ -145,17 +135,12 @@ __global__ __launch_bounds__(VI_THREADS) void k_vb_corrected(const float* __rest
 __global__ __launch_bounds__(VI_THREADS) void k_vb_hist(const float* __restrict__ c, int64_t n, double lo, double scale, int bins,
                                                         uint32_t* __restrict__ hist) {
   __shared__ uint32_t h[VB_MAX_BINS];
-  for (int i = threadIdx.x; i < bins; i += VI_THREADS) h[i] = 0;
-  __syncthreads();
-  for (int64_t i = (int64_t)blockIdx.x * VI_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * VI_THREADS) {
+  vc_hist_clear(h, bins);
+  VI_GRID_STRIDE(i, n) {
     const float v = c[i];
     if (vc_finite(v)) atomicAdd(&h[vc_bin(v, lo, scale, bins)], 1u);
   }
-  __syncthreads();
-  for (int i = threadIdx.x; i < bins; i += VI_THREADS) {
-    const uint32_t k = h[i];
-    if (k) atomicAdd(&hist[i], k);
-  }
+  vc_hist_merge(h, bins, hist);
 }
 
 // table(c): linear interpolation between bin centres in fp64, clamped at the ends (bins >= 2)
@@ -188,7 +173,7 @@ __global__ __launch_bounds__(VI_THREADS) void k_vb_fit(const float* __restrict__
   for (int i = threadIdx.x; i < 2 * m3; i += VI_THREADS) acc[i] = 0ull;
   for (int i = threadIdx.x; i < bins; i += VI_THREADS) tab[i] = table[i];
   __syncthreads();
-  for (int64_t i = (int64_t)blockIdx.x * VI_THREADS + threadIdx.x; i < g.n; i += (int64_t)gridDim.x * VI_THREADS) {
+  VI_GRID_STRIDE(i, g.n) {
     const float cv = c[i];
     if (!vc_finite(cv)) continue;
     int xi, yj, zk;
@@ -227,13 +212,12 @@ __global__ __launch_bounds__(VI_THREADS) void k_vb_fit(const float* __restrict__
 }
 
 // ---- 4: every voxel / exp(F) (or exp(F) itself with `field`), four consecutive voxels per thread, one 16-byte store
-__global__ __launch_bounds__(VI_THREADS) void k_vb_apply(const void* __restrict__ vol, int datatype, int scaled, double slope, double inter,
-                                                         const double* __restrict__ lattices, int levels, int nlat, int X, int Y, int Z,
-                                                         int64_t n, int field, float* __restrict__ out) {
+__global__ __launch_bounds__(VI_THREADS) void k_vb_apply(vi_source src, const double* __restrict__ lattices, int levels, int nlat, int X, int Y,
+                                                         int Z, int64_t n, int field, float* __restrict__ out) {
   for (int i = threadIdx.x; i < nlat; i += VI_THREADS) vb_lds[i] = lattices[i];
   __syncthreads();
   const int64_t quads = (n + 3) / 4;
-  for (int64_t q = (int64_t)blockIdx.x * VI_THREADS + threadIdx.x; q < quads; q += (int64_t)gridDim.x * VI_THREADS) {
+  VI_GRID_STRIDE(q, quads) {
     float res[4];
     const int64_t base = q * 4;
 #pragma unroll
@@ -241,10 +225,9 @@ __global__ __launch_bounds__(VI_THREADS) void k_vb_apply(const void* __restrict_
       const int64_t i = base + e;
       res[e] = 0.0f;
       if (i >= n) continue;
-      const uint32_t l = (uint32_t)i;
-      const uint32_t row = l / (uint32_t)X;
-      const int xi = (int)(l - row * (uint32_t)X), yj = (int)(row % (uint32_t)Y), zk = (int)(row / (uint32_t)Y);
-      const float v = vc_stored_value(vol, datatype, i, scaled, slope, inter);
+      int xi, yj, zk;
+      vi_xyz(i, X, Y, xi, yj, zk);
+      const float v = vc_stored_value(src, i);
       if (!field && !(vc_finite(v) && v != 0.0f)) {          // a zero stays zero, a non-finite voxel passes through
         res[e] = v;
         continue;
@@ -263,30 +246,11 @@ __global__ __launch_bounds__(VI_THREADS) void k_vb_apply(const void* __restrict_
 
 // ---- entry points ---------------------------------------------------------------------------------------------------------------------
 static inline int vb_check_grid(const char* who, int X, int Y, int Z, int shrink, vb_grid* g) {
-  MUD_REQUIRE(X > 0 && Y > 0 && Z > 0 && (int64_t)X * Y * Z < ((int64_t)1 << 31), "%s: bad volume size %d x %d x %d", who, X, Y, Z);
+  if (int e = vi_check_size(who, "volume", X, Y, Z)) return e;
   MUD_REQUIRE(shrink > 0, "%s: shrink %d is not positive", who, shrink);
   g->X = X, g->Y = Y, g->Z = Z, g->shrink = shrink;
   g->nx = (int)mud_cdiv(X, shrink), g->ny = (int)mud_cdiv(Y, shrink);
   g->n = (int64_t)g->nx * g->ny * mud_cdiv(Z, shrink);
-  return MUD_OK;
-}
-
-static inline unsigned vb_blocks(int64_t n, int64_t per_block) {
-  int64_t b = mud_cdiv(n, per_block);
-  b = b > VB_MAX_BLOCKS ? VB_MAX_BLOCKS : b;
-  return (unsigned)(b < 1 ? 1 : b);
-}
-
-// dynamic LDS above the default limit of a launch has to be allowed per kernel and device
-static int vb_allow_lds(const char* who, mud_attr_once& once, const void* kernel, int bytes) {
-  if (once.need()) {
-    hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) {
-      mud_set_error("%s: cannot reserve %d B of LDS: %s", who, bytes, hipGetErrorString(e));
-      return MUD_ERR_LAUNCH;
-    }
-    once.ok();
-  }
   return MUD_OK;
 }
 
@@ -299,9 +263,8 @@ extern "C" int mud_volume_bias_log(const void* vol, int datatype, int X, int Y, 
   vb_grid g;
   if (int e = vb_check_grid("mud_volume_bias_log", X, Y, Z, shrink, &g)) return e;
   MUD_REQUIRE(u != nullptr, "mud_volume_bias_log: null pointer");
-  const int scaled = vi_scaled(slope, inter);
-  VI_DISPATCH(datatype, hipLaunchKernelGGL(k_vb_log<T>, dim3(vb_blocks(g.n, VI_THREADS)), dim3(VI_THREADS), 0, (hipStream_t)stream,
-                                           (const T*)vol, scaled, (double)slope, (double)inter, g, u));
+  VI_DISPATCH(datatype, hipLaunchKernelGGL(k_vb_log<T>, dim3(vi_blocks(g.n, VI_THREADS, VB_MAX_BLOCKS)), dim3(VI_THREADS), 0, (hipStream_t)stream,
+                                           vi_source_of(vol, datatype, slope, inter), g, u));
   MUD_CHECK_LAUNCH("mud_volume_bias_log");
   return MUD_OK;
 }
@@ -313,39 +276,28 @@ extern "C" int mud_volume_bias_corrected(const float* u, const float* c_old, flo
   MUD_REQUIRE(u != nullptr && c_old != nullptr && c_new != nullptr && lattices != nullptr && stats != nullptr,
               "mud_volume_bias_corrected: null pointer");
   MUD_REQUIRE(c_old != c_new && u != c_new, "mud_volume_bias_corrected: c_new must be a buffer of its own");
-  MUD_REQUIRE((((uintptr_t)stats) & 7u) == 0 && (((uintptr_t)lattices) & 7u) == 0, "mud_volume_bias_corrected: stats and lattices must be 8-byte aligned");
+  MUD_REQUIRE(vi_aligned(stats, 8) && vi_aligned(lattices, 8), "mud_volume_bias_corrected: stats and lattices must be 8-byte aligned");
   MUD_REQUIRE(levels >= 1 && levels <= VB_MAX_LEVELS, "mud_volume_bias_corrected: 1 to %d levels, got %d", VB_MAX_LEVELS, levels);
   hipStream_t s = (hipStream_t)stream;
   static mud_attr_once once;
-  if (int e = vb_allow_lds("mud_volume_bias_corrected", once, (const void*)k_vb_corrected, VB_FIELD_LDS_MAX)) return e;
-  if (hipMemsetAsync(stats, 0, 16, s) != hipSuccess || hipMemsetAsync(stats + 2, 0xFF, 8, s) != hipSuccess) {
-    mud_set_error("mud_volume_bias_corrected: clearing the statistics failed");
-    return MUD_ERR_LAUNCH;
-  }
+  if (int e = vi_allow_lds("mud_volume_bias_corrected", once, (const void*)k_vb_corrected, VB_FIELD_LDS_MAX)) return e;
+  if (int e = vi_clear("mud_volume_bias_corrected", stats, 16, s)) return e;                  // two maxima from 0,
+  if (int e = vi_clear("mud_volume_bias_corrected", stats + 2, 8, s, 0xFF)) return e;         // the minimum from all ones
   const int nlat = vb_lattice_doubles(levels);
-  hipLaunchKernelGGL(k_vb_corrected, dim3(vb_blocks(g.n, VI_THREADS)), dim3(VI_THREADS), (size_t)nlat * 8, s, u, c_old, c_new, lattices, levels,
+  hipLaunchKernelGGL(k_vb_corrected, dim3(vi_blocks(g.n, VI_THREADS, VB_MAX_BLOCKS)), dim3(VI_THREADS), (size_t)nlat * 8, s, u, c_old, c_new, lattices, levels,
                      nlat, g, (unsigned long long*)stats);
   MUD_CHECK_LAUNCH("mud_volume_bias_corrected");
-  return MUD_OK;
-}
-
-static inline int vb_check_bins(const char* who, double lo, double scale, int bins) {
-  MUD_REQUIRE(bins >= 2 && bins <= VB_MAX_BINS, "%s: 2 to %d bins, got %d", who, VB_MAX_BINS, bins);
-  MUD_REQUIRE(lo - lo == 0.0 && scale - scale == 0.0, "%s: lo / scale must be finite (%g, %g)", who, lo, scale);
   return MUD_OK;
 }
 
 extern "C" int mud_volume_bias_hist(const float* c, int64_t n, double lo, double scale, int bins, uint32_t* hist, void* stream) {
   MUD_REQUIRE(c != nullptr && hist != nullptr, "mud_volume_bias_hist: null pointer");
   MUD_REQUIRE(n > 0 && n < ((int64_t)1 << 31), "mud_volume_bias_hist: bad sample count %lld", (long long)n);
-  if (int e = vb_check_bins("mud_volume_bias_hist", lo, scale, bins)) return e;
-  MUD_REQUIRE((((uintptr_t)hist) & 3u) == 0, "mud_volume_bias_hist: hist must be 4-byte aligned");
+  if (int e = vi_check_bins("mud_volume_bias_hist", lo, scale, bins, 2, VB_MAX_BINS)) return e;
+  MUD_REQUIRE(vi_aligned(hist, 4), "mud_volume_bias_hist: hist must be 4-byte aligned");
   hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync(hist, 0, sizeof(uint32_t) * bins, s) != hipSuccess) {
-    mud_set_error("mud_volume_bias_hist: clearing the histogram failed");
-    return MUD_ERR_LAUNCH;
-  }
-  hipLaunchKernelGGL(k_vb_hist, dim3(vb_blocks(n, VI_THREADS)), dim3(VI_THREADS), 0, s, c, n, lo, scale, bins, hist);
+  if (int e = vi_clear("mud_volume_bias_hist", hist, sizeof(uint32_t) * bins, s)) return e;
+  hipLaunchKernelGGL(k_vb_hist, dim3(vi_blocks(n, VI_THREADS, VB_MAX_BLOCKS)), dim3(VI_THREADS), 0, s, c, n, lo, scale, bins, hist);
   MUD_CHECK_LAUNCH("mud_volume_bias_hist");
   return MUD_OK;
 }
@@ -355,20 +307,17 @@ extern "C" int mud_volume_bias_fit(const float* c, const double* table, int bins
   vb_grid g;
   if (int e = vb_check_grid("mud_volume_bias_fit", X, Y, Z, shrink, &g)) return e;
   MUD_REQUIRE(c != nullptr && table != nullptr && sums != nullptr, "mud_volume_bias_fit: null pointer");
-  if (int e = vb_check_bins("mud_volume_bias_fit", lo, scale, bins)) return e;
-  MUD_REQUIRE((((uintptr_t)sums) & 7u) == 0 && (((uintptr_t)table) & 7u) == 0, "mud_volume_bias_fit: sums and table must be 8-byte aligned");
+  if (int e = vi_check_bins("mud_volume_bias_fit", lo, scale, bins, 2, VB_MAX_BINS)) return e;
+  MUD_REQUIRE(vi_aligned(sums, 8) && vi_aligned(table, 8), "mud_volume_bias_fit: sums and table must be 8-byte aligned");
   MUD_REQUIRE(level >= 0 && level < VB_MAX_LEVELS, "mud_volume_bias_fit: level %d: a lattice of more than %d spans per axis does not fit in LDS",
               level, 1 << (VB_MAX_LEVELS - 1));
   MUD_REQUIRE(k >= 0 && k <= 62, "mud_volume_bias_fit: k = %d is not in [0, 62]", k);
   hipStream_t s = (hipStream_t)stream;
   static mud_attr_once once;
-  if (int e = vb_allow_lds("mud_volume_bias_fit", once, (const void*)k_vb_fit, VB_FIT_LDS_MAX)) return e;
+  if (int e = vi_allow_lds("mud_volume_bias_fit", once, (const void*)k_vb_fit, VB_FIT_LDS_MAX)) return e;
   const int m = (1 << level) + 3, m3 = m * m * m;
-  if (hipMemsetAsync(sums, 0, sizeof(int64_t) * 2 * m3, s) != hipSuccess) {
-    mud_set_error("mud_volume_bias_fit: clearing the sums failed");
-    return MUD_ERR_LAUNCH;
-  }
-  hipLaunchKernelGGL(k_vb_fit, dim3(vb_blocks(g.n, VB_FIT_SAMPLES)), dim3(VI_THREADS), (size_t)(2 * m3 + bins) * 8, s, c, table, bins, lo, scale,
+  if (int e = vi_clear("mud_volume_bias_fit", sums, sizeof(int64_t) * 2 * m3, s)) return e;
+  hipLaunchKernelGGL(k_vb_fit, dim3(vi_blocks(g.n, VB_FIT_SAMPLES, VB_MAX_BLOCKS)), dim3(VI_THREADS), (size_t)(2 * m3 + bins) * 8, s, c, table, bins, lo, scale,
                      level, g, ldexp(1.0, k), (unsigned long long*)sums);
   MUD_CHECK_LAUNCH("mud_volume_bias_fit");
   return MUD_OK;
@@ -378,15 +327,15 @@ extern "C" int mud_volume_bias_apply(const void* vol, int datatype, int X, int Y
                                      int levels, int field, float* out, void* stream) {
   if (int e = vi_check_volume("mud_volume_bias_apply", vol, datatype, X, Y, Z)) return e;
   MUD_REQUIRE(lattices != nullptr && out != nullptr, "mud_volume_bias_apply: null pointer");
-  MUD_REQUIRE(mud_aligned16(out) && (((uintptr_t)lattices) & 7u) == 0, "mud_volume_bias_apply: out must be 16-byte, lattices 8-byte aligned");
+  MUD_REQUIRE(mud_aligned16(out) && vi_aligned(lattices, 8), "mud_volume_bias_apply: out must be 16-byte, lattices 8-byte aligned");
   MUD_REQUIRE((const void*)out != vol, "mud_volume_bias_apply: out must be a buffer of its own");
   MUD_REQUIRE(levels >= 1 && levels <= VB_MAX_LEVELS, "mud_volume_bias_apply: 1 to %d levels, got %d", VB_MAX_LEVELS, levels);
   static mud_attr_once once;
-  if (int e = vb_allow_lds("mud_volume_bias_apply", once, (const void*)k_vb_apply, VB_FIELD_LDS_MAX)) return e;
+  if (int e = vi_allow_lds("mud_volume_bias_apply", once, (const void*)k_vb_apply, VB_FIELD_LDS_MAX)) return e;
   const int64_t n = (int64_t)X * Y * Z;
   const int nlat = vb_lattice_doubles(levels);
-  hipLaunchKernelGGL(k_vb_apply, dim3(vb_blocks(mud_cdiv(n, 4), VI_THREADS)), dim3(VI_THREADS), (size_t)nlat * 8, (hipStream_t)stream, vol, datatype,
-                     vi_scaled(slope, inter), (double)slope, (double)inter, lattices, levels, nlat, X, Y, Z, n, field != 0, out);
+  hipLaunchKernelGGL(k_vb_apply, dim3(vi_blocks(mud_cdiv(n, 4), VI_THREADS, VB_MAX_BLOCKS)), dim3(VI_THREADS), (size_t)nlat * 8, (hipStream_t)stream,
+                     vi_source_of(vol, datatype, slope, inter), lattices, levels, nlat, X, Y, Z, n, field != 0, out);
   MUD_CHECK_LAUNCH("mud_volume_bias_apply");
   return MUD_OK;
 }

@@ -1,11 +1,19 @@
-// What the kernels of the volume pipeline share (volume_intake.hip, volume_coreg.hip, volume_bias.hip): the value of a stored voxel, the trilinear value
-// at a source coordinate, the datatype dispatch and the argument checks of a stored volume.  One definition each, so that a histogram
-// sample of mud_volume_joint_hist is the voxel mud_volume_regrid writes, bit for bit.
+// What the kernels of the volume pipeline share (volume_intake.hip, volume_coreg.hip, volume_bias.hip, volume_denoise.hip,
+// volume_foreground.hip): a stored volume as one kernel argument and the value of its voxels, the trilinear value at a source coordinate,
+// the order-preserving key, the index and loop helpers, the LDS histogram and the per-workgroup count, the launch shapes and the argument
+// checks.  One definition each, so that a histogram sample of mud_volume_joint_hist is the voxel mud_volume_regrid writes and a key decodes
+// to the value that was encoded, bit for bit.  DESIGN.md section 5.17 lists them.
 #pragma once
 #include "mud_common.h"
 
 #define VI_THREADS 256
 #define VI_MAX_BLOCKS 2048
+#define VI_TX 32                               // the tile of the kernels that stage a neighbourhood in LDS (denoise, foreground)
+#define VI_TY 8
+#define VI_TZ 4
+
+// the grid-stride loop of a one-dimensional launch of VI_THREADS threads per workgroup
+#define VI_GRID_STRIDE(i, n) for (int64_t i = (int64_t)blockIdx.x * VI_THREADS + threadIdx.x; i < (n); i += (int64_t)gridDim.x * VI_THREADS)
 
 // ---- the value of a stored voxel ------------------------------------------------------------------------------------------------------
 // float32(double(raw) * slope + inter), the product and the sum rounded separately (numpy: data.astype(float64) * slope + inter, then
@@ -19,6 +27,35 @@ __device__ __forceinline__ float vi_value(T raw, int scaled, double slope, doubl
     d = d + inter;
   }
   return (float)d;
+}
+
+static inline bool vi_scaled(float slope, float inter) {      // volume.read_nifti's condition
+  return slope != 0.0f && slope - slope == 0.0f && (slope != 1.0f || inter != 0.0f);
+}
+
+struct vi_source {                             // a stored volume as a kernel argument: the voxels as the file holds them and how to read them
+  const void* vol;
+  int datatype, scaled;
+  double slope, inter;
+};
+
+static inline vi_source vi_source_of(const void* vol, int datatype, float slope, float inter) {
+  return {vol, datatype, (int)vi_scaled(slope, inter), (double)slope, (double)inter};
+}
+
+template <typename T>                          // voxel i of a volume whose datatype is T (VI_DISPATCH)
+__device__ __forceinline__ float vi_at(const vi_source& s, int64_t i) {
+  return vi_value<T>(((const T*)s.vol)[i], s.scaled, s.slope, s.inter);
+}
+
+__device__ __forceinline__ float vc_stored_value(const vi_source& s, int64_t i) {      // voxel i by the datatype code
+  switch (s.datatype) {                        // uniform over the launch
+    case MUD_NIFTI_U1: return vi_at<uint8_t>(s, i);
+    case MUD_NIFTI_I2: return vi_at<int16_t>(s, i);
+    case MUD_NIFTI_U2: return vi_at<uint16_t>(s, i);
+    case MUD_NIFTI_I4: return vi_at<int32_t>(s, i);
+    default: return vi_at<float>(s, i);
+  }
 }
 
 // m maps a reference voxel index (i, j, k) to a source voxel coordinate p; everything about p is fp64, so that an identity, an integer
@@ -37,8 +74,7 @@ __device__ __forceinline__ bool vi_axis_near(double p, int S) { return p > -1.0 
 
 // the trilinear value at p (vi_axis_near on every axis): the fp64 sum over the 8 neighbours, rounded to fp32 once
 template <typename T>
-__device__ __forceinline__ float vi_trilinear(const T* __restrict__ src, int SX, int SY, int SZ, int scaled, double slope, double inter,
-                                              const double p[3]) {
+__device__ __forceinline__ float vi_trilinear(const vi_source& src, int SX, int SY, int SZ, const double p[3]) {
   const double fx = floor(p[0]), fy = floor(p[1]), fz = floor(p[2]);
   const double wx[2] = {1.0 - (p[0] - fx), p[0] - fx}, wy[2] = {1.0 - (p[1] - fy), p[1] - fy}, wz[2] = {1.0 - (p[2] - fz), p[2] - fz};
   const int x0 = (int)fx, y0 = (int)fy, z0 = (int)fz;
@@ -50,12 +86,23 @@ __device__ __forceinline__ float vi_trilinear(const T* __restrict__ src, int SX,
     const double w = wx[dx] * wy[dy] * wz[dz];
     // a neighbour of weight 0 is not read (an identity next to a NaN stays exact); one outside the grid counts as 0
     if (w != 0.0 && xx >= 0 && xx < SX && yy >= 0 && yy < SY && zz >= 0 && zz < SZ)
-      acc = fma((double)vi_value<T>(src[((int64_t)zz * SY + yy) * SX + xx], scaled, slope, inter), w, acc);
+      acc = fma((double)vi_at<T>(src, ((int64_t)zz * SY + yy) * SX + xx), w, acc);
   }
   return (float)acc;
 }
 
-// ---- shared by the histograms of volume_coreg.hip and volume_bias.hip: the bin of a value, a stored voxel by datatype code, finiteness
+// ---- keys, bins and indices -----------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool vc_finite(float v) { return fabsf(v) <= 3.402823466e38f; }
+
+// order-preserving uint32 image of an fp32 that is not a NaN: unsigned comparison of keys = comparison of values
+__device__ __forceinline__ uint32_t vc_key(float v) {
+  const uint32_t u = __float_as_uint(v);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+// the same with every NaN sorting last (np.sort puts them there), and its inverse
+__device__ __forceinline__ uint32_t vi_key(float v) { return v != v ? 0xFFFFFFFFu : vc_key(v); }
+__device__ __forceinline__ float vi_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
+
 // clamp((int)floor((double(v) - lo) * scale), 0, bins - 1), the subtraction and the product rounded separately (numpy's two steps);
 // clamped before the conversion, so that no product is too large for an int
 __device__ __forceinline__ int vc_bin(float v, double lo, double scale, int bins) {
@@ -69,20 +116,62 @@ __device__ __forceinline__ int vc_bin(float v, double lo, double scale, int bins
   return (int)d;
 }
 
-__device__ __forceinline__ float vc_stored_value(const void* __restrict__ p, int datatype, int64_t i, int scaled, double slope, double inter) {
-  switch (datatype) {                          // uniform over the launch
-    case MUD_NIFTI_U1: return vi_value<uint8_t>(((const uint8_t*)p)[i], scaled, slope, inter);
-    case MUD_NIFTI_I2: return vi_value<int16_t>(((const int16_t*)p)[i], scaled, slope, inter);
-    case MUD_NIFTI_U2: return vi_value<uint16_t>(((const uint16_t*)p)[i], scaled, slope, inter);
-    case MUD_NIFTI_I4: return vi_value<int32_t>(((const int32_t*)p)[i], scaled, slope, inter);
-    default: return vi_value<float>(((const float*)p)[i], scaled, slope, inter);
+// linear index i of a grid with X x Y voxels per plane -> (x, y, z) by two 32-bit divisions: i < 2^31, because every entry point
+// refuses a volume of 2^31 voxels or more (vi_check_size).  A strided sample grid passes (nx, ny) and multiplies by its stride.
+__device__ __forceinline__ void vi_xyz(int64_t i, int X, int Y, int& x, int& y, int& z) {
+  const uint32_t l = (uint32_t)i;
+  const uint32_t row = l / (uint32_t)X;
+  x = (int)(l - row * (uint32_t)X), y = (int)(row % (uint32_t)Y), z = (int)(row / (uint32_t)Y);
+}
+
+// ---- the LDS-privatised histogram: vc_hist_clear, count into h[] with LDS atomics, vc_hist_merge (one global atomic per non-empty bin).
+// A workgroup's count of something is the histogram of one bin: vc_hist_clear(&s, 1), if (mine) atomicAdd(&s, mine), vc_hist_merge(&s, 1, total).
+// Both contain a barrier: every thread of the workgroup must reach them, so no thread may return before the merge.
+__device__ __forceinline__ void vc_hist_clear(uint32_t* h, int nb) {
+  for (int i = threadIdx.x; i < nb; i += VI_THREADS) h[i] = 0;
+  __syncthreads();
+}
+__device__ __forceinline__ void vc_hist_merge(const uint32_t* h, int nb, uint32_t* __restrict__ hist) {
+  __syncthreads();
+  for (int i = threadIdx.x; i < nb; i += VI_THREADS) {
+    const uint32_t c = h[i];
+    if (c) atomicAdd(&hist[i], c);
   }
 }
 
-__device__ __forceinline__ bool vc_finite(float v) { return fabsf(v) <= 3.402823466e38f; }
+// ---- host side: launch shapes and argument checks ---------------------------------------------------------------------------------------
+// the workgroups of a grid-stride launch: clamp(cdiv(n, per_block), 1, cap)
+static inline unsigned vi_blocks(int64_t n, int64_t per_block = VI_THREADS, int64_t cap = VI_MAX_BLOCKS) {
+  const int64_t b = mud_cdiv(n, per_block);
+  return (unsigned)(b < 1 ? 1 : b > cap ? cap : b);
+}
 
-static inline bool vi_scaled(float slope, float inter) {      // volume.read_nifti's condition
-  return slope != 0.0f && slope - slope == 0.0f && (slope != 1.0f || inter != 0.0f);
+static inline dim3 vi_tile_grid(int X, int Y, int Z) {
+  return dim3((unsigned)mud_cdiv(X, VI_TX), (unsigned)mud_cdiv(Y, VI_TY), (unsigned)mud_cdiv(Z, VI_TZ));
+}
+
+static inline bool vi_aligned(const void* p, size_t bytes) { return (((uintptr_t)p) & (uintptr_t)(bytes - 1)) == 0; }      // bytes: a power of two
+
+// fill `bytes` at p on the stream (with zeros unless told otherwise) before the kernels that accumulate into it
+static inline int vi_clear(const char* who, void* p, size_t bytes, hipStream_t s, int fill = 0) {
+  if (hipMemsetAsync(p, fill, bytes, s) != hipSuccess) {
+    mud_set_error("%s: clearing the result failed", who);
+    return MUD_ERR_LAUNCH;
+  }
+  return MUD_OK;
+}
+
+// dynamic LDS above the default limit of a launch has to be allowed per kernel and device
+static inline int vi_allow_lds(const char* who, mud_attr_once& once, const void* kernel, int bytes) {
+  if (once.need()) {
+    hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) {
+      mud_set_error("%s: cannot reserve %d B of LDS: %s", who, bytes, hipGetErrorString(e));
+      return MUD_ERR_LAUNCH;
+    }
+    once.ok();
+  }
+  return MUD_OK;
 }
 
 static inline int vi_esize(int datatype) {
@@ -96,11 +185,29 @@ static inline int vi_esize(int datatype) {
   }
 }
 
+// fewer than 2^31 voxels: what lets every kernel index with 32-bit divisions (vi_xyz) and an int label hold a linear index
+static inline int vi_check_size(const char* who, const char* what, int X, int Y, int Z) {
+  MUD_REQUIRE(X > 0 && Y > 0 && Z > 0 && (int64_t)X * Y * Z < ((int64_t)1 << 31), "%s: bad %s size %d x %d x %d", who, what, X, Y, Z);
+  return MUD_OK;
+}
+
 static inline int vi_check_volume(const char* who, const void* vol, int datatype, int X, int Y, int Z) {
   MUD_REQUIRE(vi_esize(datatype) != 0, "%s: unsupported NIfTI datatype code %d (u1 2, i2 4, i4 8, f4 16, u2 512)", who, datatype);
-  MUD_REQUIRE(X > 0 && Y > 0 && Z > 0 && (int64_t)X * Y * Z < ((int64_t)1 << 31), "%s: bad volume size %d x %d x %d", who, X, Y, Z);
+  if (int e = vi_check_size(who, "volume", X, Y, Z)) return e;
   MUD_REQUIRE(vol != nullptr, "%s: null pointer", who);
   MUD_REQUIRE(mud_aligned16(vol), "%s: the volume must be 16-byte aligned", who);
+  return MUD_OK;
+}
+
+// a grid of VI_TX x VI_TY x VI_TZ tiles (vi_tile_grid) has at most 65535 workgroups along y and z
+static inline int vi_check_tiled(const char* who, int X, int Y, int Z) {
+  MUD_REQUIRE(Y <= VI_TY * 65535 && Z <= VI_TZ * 65535, "%s: bad volume size %d x %d x %d", who, X, Y, Z);
+  return MUD_OK;
+}
+
+static inline int vi_check_bins(const char* who, double lo, double scale, int bins, int min_bins, int max_bins) {
+  MUD_REQUIRE(bins >= min_bins && bins <= max_bins, "%s: %d to %d bins, got %d", who, min_bins, max_bins, bins);
+  MUD_REQUIRE(lo - lo == 0.0 && scale - scale == 0.0, "%s: lo / scale must be finite (%g, %g)", who, lo, scale);
   return MUD_OK;
 }
 

@@ -12,35 +12,29 @@
 // only expf is the math library's.  The estimation's sums are integer counts: two runs give the same bits.
 #include "volume_common.h"
 
-#define VD_TX 32                               // the tile; a thread owns VD_VX consecutive voxels of a row
-#define VD_TY 8
-#define VD_TZ 4
-#define VD_VX 4
+#define VD_VX 4                                // a thread owns VD_VX consecutive voxels of a row of the VI_TX x VI_TY x VI_TZ tile
 #define VD_MAX_SEARCH 5
 #define VD_MAX_PATCH 2
 #define VD_MAX_LDS (160 * 1024)
 #define VD_SKIP 0xFFFFFFFFu                    // the key of a voxel outside the estimation set
 
-static_assert(VD_TX / VD_VX * VD_TY * VD_TZ == VI_THREADS, "one thread per VD_VX voxels of the tile");
+static_assert(VI_TX / VD_VX * VI_TY * VI_TZ == VI_THREADS, "one thread per VD_VX voxels of the tile");
 
 // ---- 1: keys[i] = bits of |eps|, eps = sqrtf(6/7) * (v - (sum of the six face neighbours) / 6), over the voxels that are > 0 with six
 // neighbours inside the volume, valid and > 0; VD_SKIP elsewhere
 template <typename T>
-__global__ __launch_bounds__(VI_THREADS) void k_vd_residual(const T* __restrict__ vol, int scaled, double slope, double inter, int X, int Y,
-                                                            int Z, int64_t n, uint32_t* __restrict__ keys) {
+__global__ __launch_bounds__(VI_THREADS) void k_vd_residual(vi_source src, int X, int Y, int Z, int64_t n, uint32_t* __restrict__ keys) {
 #pragma clang fp contract(off)
   const float K = 0.9258200997725514f;         // float32(sqrt(6 / 7))
-  for (int64_t i = (int64_t)blockIdx.x * VI_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * VI_THREADS) {
-    const uint32_t l = (uint32_t)i;
-    const uint32_t row = l / (uint32_t)X;
-    const int x = (int)(l - row * (uint32_t)X), y = (int)(row % (uint32_t)Y), z = (int)(row / (uint32_t)Y);
+  VI_GRID_STRIDE(i, n) {
+    int x, y, z;
+    vi_xyz(i, X, Y, x, y, z);
     uint32_t key = VD_SKIP;
     if (x > 0 && x < X - 1 && y > 0 && y < Y - 1 && z > 0 && z < Z - 1) {
       const int64_t sy = X, sz = (int64_t)X * Y;
-      const float v = vi_value<T>(vol[i], scaled, slope, inter);
-      const float a = vi_value<T>(vol[i - 1], scaled, slope, inter), b = vi_value<T>(vol[i + 1], scaled, slope, inter);
-      const float c = vi_value<T>(vol[i - sy], scaled, slope, inter), d = vi_value<T>(vol[i + sy], scaled, slope, inter);
-      const float e = vi_value<T>(vol[i - sz], scaled, slope, inter), f = vi_value<T>(vol[i + sz], scaled, slope, inter);
+      const float v = vi_at<T>(src, i);
+      const float a = vi_at<T>(src, i - 1), b = vi_at<T>(src, i + 1), c = vi_at<T>(src, i - sy), d = vi_at<T>(src, i + sy);
+      const float e = vi_at<T>(src, i - sz), f = vi_at<T>(src, i + sz);
       const bool ok = vc_finite(v) && v > 0.0f && vc_finite(a) && a > 0.0f && vc_finite(b) && b > 0.0f && vc_finite(c) && c > 0.0f &&
                       vc_finite(d) && d > 0.0f && vc_finite(e) && e > 0.0f && vc_finite(f) && f > 0.0f;
       if (ok) {
@@ -62,17 +56,16 @@ __global__ __launch_bounds__(VI_THREADS) void k_vd_residual(const T* __restrict_
 __global__ __launch_bounds__(VI_THREADS) void k_vd_select_hist(const uint32_t* __restrict__ keys, int64_t n, uint32_t prefix, int pass,
                                                                uint32_t* __restrict__ hist) {
   __shared__ uint32_t h[256];
-  h[threadIdx.x] = 0;
-  __syncthreads();
+  // 256 bins, VI_THREADS threads: the shared loops run once per thread.  Chosen over h[threadIdx.x] = 0 written out here: the same 9
+  // VGPRs and the same loop over the keys, six scalar / compare instructions more per workgroup outside that loop, one definition fewer
+  vc_hist_clear(h, 256);
   const int shift = 24 - 8 * pass;
-  for (int64_t i = (int64_t)blockIdx.x * VI_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * VI_THREADS) {
+  VI_GRID_STRIDE(i, n) {
     const uint32_t k = keys[i];
     if (k == VD_SKIP) continue;
     if (pass == 0 || ((k >> shift) >> 8) == prefix) atomicAdd(&h[(k >> shift) & 255u], 1u);
   }
-  __syncthreads();
-  const uint32_t c = h[threadIdx.x];
-  if (c) atomicAdd(&hist[threadIdx.x], c);
+  vc_hist_merge(h, 256, hist);
 }
 
 // ---- 3: the estimate
@@ -80,7 +73,7 @@ extern __shared__ __attribute__((aligned(16))) float vd_lds[];
 
 template <int R>
 struct vd_plane {                              // D_t over the tile grown by R per side; rows padded to a multiple of 4 floats
-  static constexpr int DX = VD_TX + 2 * R, DY = VD_TY + 2 * R, DZ = VD_TZ + 2 * R;
+  static constexpr int DX = VI_TX + 2 * R, DY = VI_TY + 2 * R, DZ = VI_TZ + 2 * R;
   static constexpr int DXP = (DX + 3) / 4 * 4;
   static constexpr int COUNT = DX * DY * DZ, FLOATS = DXP * DY * DZ;
   static constexpr int PER_THREAD = (COUNT + VI_THREADS - 1) / VI_THREADS;
@@ -88,30 +81,28 @@ struct vd_plane {                              // D_t over the tile grown by R p
 
 static inline int vd_staged_floats(int s, int r) {
   const int H = s + r;
-  return ((VD_TX + 2 * H) * (VD_TY + 2 * H) * (VD_TZ + 2 * H) + 3) / 4 * 4;
+  return ((VI_TX + 2 * H) * (VI_TY + 2 * H) * (VI_TZ + 2 * H) + 3) / 4 * 4;
 }
 
 template <typename T, int R>
-__global__ __launch_bounds__(VI_THREADS) void k_vd_nlm(const T* __restrict__ vol, int scaled, double slope, double inter, int X, int Y, int Z,
-                                                       int s, int staged, float h, double bias, int rician, float* __restrict__ out,
-                                                       uint32_t* __restrict__ zeroed) {
+__global__ __launch_bounds__(VI_THREADS) void k_vd_nlm(vi_source vol, int X, int Y, int Z, int s, int staged, float h, double bias, int rician,
+                                                       float* __restrict__ out, uint32_t* __restrict__ zeroed) {
 #pragma clang fp contract(off)
   typedef vd_plane<R> P;
   constexpr int W = 2 * R + 1, ROW = VD_VX + 2 * R;
-  __shared__ uint32_t nzeroed;
+  __shared__ uint32_t nzeroed;                 // the workgroup's count: a histogram of one bin
   const int H = s + R;
-  const int SX = VD_TX + 2 * H, SY = VD_TY + 2 * H, SZ = VD_TZ + 2 * H;
+  const int SX = VI_TX + 2 * H, SY = VI_TY + 2 * H, SZ = VI_TZ + 2 * H;
   float* S = vd_lds;
   float* D = vd_lds + staged;
   const int tid = threadIdx.x;
-  const int x0 = blockIdx.x * VD_TX, y0 = blockIdx.y * VD_TY, z0 = blockIdx.z * VD_TZ;
-  if (tid == 0) nzeroed = 0;
+  const int x0 = blockIdx.x * VI_TX, y0 = blockIdx.y * VI_TY, z0 = blockIdx.z * VI_TZ;
   const float nan = __uint_as_float(0x7fc00000u);
   for (int i = tid; i < SX * SY * SZ; i += VI_THREADS) {
     const int row = i / SX, ix = i - row * SX, iz = row / SY, iy = row - iz * SY;
     const int gx = x0 - H + ix, gy = y0 - H + iy, gz = z0 - H + iz;
     float v = nan;
-    if (gx >= 0 && gx < X && gy >= 0 && gy < Y && gz >= 0 && gz < Z) v = vi_value<T>(vol[((int64_t)gz * Y + gy) * X + gx], scaled, slope, inter);
+    if (gx >= 0 && gx < X && gy >= 0 && gy < Y && gz >= 0 && gz < Z) v = vi_at<T>(vol, ((int64_t)gz * Y + gy) * X + gx);
     S[i] = v;
   }
   // this thread's entries of a D plane: where they sit in the plane and in the staged tile (the same for every offset)
@@ -123,13 +114,13 @@ __global__ __launch_bounds__(VI_THREADS) void k_vd_nlm(const T* __restrict__ vol
     d_at[k] = i < P::COUNT ? (dz * P::DY + dy) * P::DXP + dx : -1;
     s_at[k] = i < P::COUNT ? ((dz + s) * SY + (dy + s)) * SX + (dx + s) : 0;
   }
-  const int tx = tid & (VD_TX / VD_VX - 1), ty = (tid / (VD_TX / VD_VX)) & (VD_TY - 1), tz = tid / (VD_TX / VD_VX * VD_TY);
+  const int tx = tid & (VI_TX / VD_VX - 1), ty = (tid / (VI_TX / VD_VX)) & (VI_TY - 1), tz = tid / (VI_TX / VD_VX * VI_TY);
   const int mine = (tz * P::DY + ty) * P::DXP + tx * VD_VX;             // the corner of this thread's first patch in a D plane
   double sw[VD_VX], sa[VD_VX];
   float wmax[VD_VX];
 #pragma unroll
   for (int j = 0; j < VD_VX; ++j) sw[j] = 0.0, sa[j] = 0.0, wmax[j] = 0.0f;
-  __syncthreads();
+  vc_hist_clear(&nzeroed, 1);                  // (its barrier also ends the staging)
   int turn = 0;
   for (int oz = -s; oz <= s; ++oz)
     for (int oy = -s; oy <= s; ++oy)
@@ -212,63 +203,43 @@ __global__ __launch_bounds__(VI_THREADS) void k_vd_nlm(const T* __restrict__ vol
     out[((int64_t)gz * Y + gy) * X + gx] = res;
   }
   if (nz) atomicAdd(&nzeroed, nz);
-  __syncthreads();
-  if (tid == 0 && nzeroed) atomicAdd(zeroed, nzeroed);
+  vc_hist_merge(&nzeroed, 1, zeroed);
 }
 
 // ---- entry points ---------------------------------------------------------------------------------------------------------------------
-static inline unsigned vd_blocks(int64_t n) {
-  int64_t b = mud_cdiv(n, VI_THREADS);
-  b = b > VI_MAX_BLOCKS ? VI_MAX_BLOCKS : b;
-  return (unsigned)(b < 1 ? 1 : b);
-}
-
 extern "C" int mud_volume_denoise_residual(const void* vol, int datatype, int X, int Y, int Z, float slope, float inter, uint32_t* keys,
                                            void* stream) {
   if (int e = vi_check_volume("mud_volume_denoise_residual", vol, datatype, X, Y, Z)) return e;
-  MUD_REQUIRE(keys != nullptr && (((uintptr_t)keys) & 3u) == 0, "mud_volume_denoise_residual: keys must be a 4-byte aligned pointer");
+  MUD_REQUIRE(keys != nullptr && vi_aligned(keys, 4), "mud_volume_denoise_residual: keys must be a 4-byte aligned pointer");
   const int64_t n = (int64_t)X * Y * Z;
-  VI_DISPATCH(datatype, hipLaunchKernelGGL(k_vd_residual<T>, dim3(vd_blocks(n)), dim3(VI_THREADS), 0, (hipStream_t)stream, (const T*)vol,
-                                           (int)vi_scaled(slope, inter), (double)slope, (double)inter, X, Y, Z, n, keys));
+  VI_DISPATCH(datatype, hipLaunchKernelGGL(k_vd_residual<T>, dim3(vi_blocks(n)), dim3(VI_THREADS), 0, (hipStream_t)stream,
+                                           vi_source_of(vol, datatype, slope, inter), X, Y, Z, n, keys));
   MUD_CHECK_LAUNCH("mud_volume_denoise_residual");
   return MUD_OK;
 }
 
 extern "C" int mud_volume_denoise_select_hist(const uint32_t* keys, int64_t n, uint32_t prefix, int pass, uint32_t* hist, void* stream) {
   MUD_REQUIRE(keys != nullptr && hist != nullptr, "mud_volume_denoise_select_hist: null pointer");
-  MUD_REQUIRE((((uintptr_t)keys) & 3u) == 0 && (((uintptr_t)hist) & 3u) == 0, "mud_volume_denoise_select_hist: keys and hist must be 4-byte aligned");
+  MUD_REQUIRE(vi_aligned(keys, 4) && vi_aligned(hist, 4), "mud_volume_denoise_select_hist: keys and hist must be 4-byte aligned");
   MUD_REQUIRE(n > 0 && n < ((int64_t)1 << 31), "mud_volume_denoise_select_hist: bad key count %lld", (long long)n);
   MUD_REQUIRE(pass >= 0 && pass <= 3, "mud_volume_denoise_select_hist: pass %d is not in [0, 3]", pass);
   MUD_REQUIRE(pass == 0 ? prefix == 0 : (prefix >> (8 * pass)) == 0, "mud_volume_denoise_select_hist: prefix 0x%x has more than %d bytes", prefix,
               pass);
   hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync(hist, 0, sizeof(uint32_t) * 256, s) != hipSuccess) {
-    mud_set_error("mud_volume_denoise_select_hist: clearing the histogram failed");
-    return MUD_ERR_LAUNCH;
-  }
-  hipLaunchKernelGGL(k_vd_select_hist, dim3(vd_blocks(n)), dim3(VI_THREADS), 0, s, keys, n, prefix, pass, hist);
+  if (int e = vi_clear("mud_volume_denoise_select_hist", hist, sizeof(uint32_t) * 256, s)) return e;
+  hipLaunchKernelGGL(k_vd_select_hist, dim3(vi_blocks(n)), dim3(VI_THREADS), 0, s, keys, n, prefix, pass, hist);
   MUD_CHECK_LAUNCH("mud_volume_denoise_select_hist");
   return MUD_OK;
 }
 
 template <typename T, int R>
-static int vd_launch_nlm(const void* vol, int scaled, float slope, float inter, int X, int Y, int Z, int s, float h, double bias, int rician,
-                         float* out, uint32_t* zeroed, hipStream_t stream) {
+static int vd_launch_nlm(const vi_source& src, int X, int Y, int Z, int s, float h, double bias, int rician, float* out, uint32_t* zeroed,
+                         hipStream_t stream) {
   static mud_attr_once once;                   // (one per kernel instance)
-  const void* kernel = (const void*)k_vd_nlm<T, R>;
-  if (once.need()) {
-    hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, VD_MAX_LDS - 64);
-    if (e != hipSuccess) {
-      mud_set_error("mud_volume_denoise_nlm: cannot reserve LDS: %s", hipGetErrorString(e));
-      return MUD_ERR_LAUNCH;
-    }
-    once.ok();
-  }
+  if (int e = vi_allow_lds("mud_volume_denoise_nlm", once, (const void*)k_vd_nlm<T, R>, VD_MAX_LDS - 64)) return e;
   const int staged = vd_staged_floats(s, R);
   const size_t bytes = sizeof(float) * ((size_t)staged + 2 * vd_plane<R>::FLOATS);
-  const dim3 grid((unsigned)mud_cdiv(X, VD_TX), (unsigned)mud_cdiv(Y, VD_TY), (unsigned)mud_cdiv(Z, VD_TZ));
-  hipLaunchKernelGGL((k_vd_nlm<T, R>), grid, dim3(VI_THREADS), bytes, stream, (const T*)vol, scaled, (double)slope, (double)inter, X, Y, Z, s,
-                     staged, h, bias, rician, out, zeroed);
+  hipLaunchKernelGGL((k_vd_nlm<T, R>), vi_tile_grid(X, Y, Z), dim3(VI_THREADS), bytes, stream, src, X, Y, Z, s, staged, h, bias, rician, out, zeroed);
   return MUD_OK;
 }
 
@@ -277,12 +248,12 @@ extern "C" int mud_volume_denoise_nlm(const void* vol, int datatype, int X, int 
   if (int e = vi_check_volume("mud_volume_denoise_nlm", vol, datatype, X, Y, Z)) return e;
   MUD_REQUIRE(out != nullptr && zeroed != nullptr, "mud_volume_denoise_nlm: null pointer");
   MUD_REQUIRE((const void*)out != vol, "mud_volume_denoise_nlm: out must be a buffer of its own");
-  MUD_REQUIRE((((uintptr_t)out) & 3u) == 0 && (((uintptr_t)zeroed) & 3u) == 0, "mud_volume_denoise_nlm: out and zeroed must be 4-byte aligned");
+  MUD_REQUIRE(vi_aligned(out, 4) && vi_aligned(zeroed, 4), "mud_volume_denoise_nlm: out and zeroed must be 4-byte aligned");
   MUD_REQUIRE(search >= 1 && search <= VD_MAX_SEARCH, "mud_volume_denoise_nlm: search radius %d is not in [1, %d]", search, VD_MAX_SEARCH);
   MUD_REQUIRE(patch >= 1 && patch <= VD_MAX_PATCH, "mud_volume_denoise_nlm: patch radius %d is not in [1, %d]", patch, VD_MAX_PATCH);
   MUD_REQUIRE(sigma > 0.0 && sigma - sigma == 0.0 && beta > 0.0 && beta - beta == 0.0, "mud_volume_denoise_nlm: sigma and beta must be finite and > 0 (%g, %g)",
               sigma, beta);
-  MUD_REQUIRE(Y <= 8 * 65535 && Z <= 4 * 65535, "mud_volume_denoise_nlm: bad volume size %d x %d x %d", X, Y, Z);
+  if (int e = vi_check_tiled("mud_volume_denoise_nlm", X, Y, Z)) return e;
   const size_t bytes = sizeof(float) * ((size_t)vd_staged_floats(search, patch) +
                                         2 * (size_t)(patch == 1 ? vd_plane<1>::FLOATS : vd_plane<2>::FLOATS));
   MUD_REQUIRE(bytes <= VD_MAX_LDS - 64, "mud_volume_denoise_nlm: a halo of %d + %d voxels needs %zu B of LDS, more than %d", search, patch, bytes,
@@ -295,16 +266,13 @@ extern "C" int mud_volume_denoise_nlm(const void* vol, int datatype, int X, int 
   const float h = (float)hh;
   MUD_REQUIRE(h > 0.0f && h - h == 0.0f, "mud_volume_denoise_nlm: 2 beta sigma^2 = %g is not a positive fp32", hh);
   hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync(zeroed, 0, sizeof(uint32_t), s) != hipSuccess) {
-    mud_set_error("mud_volume_denoise_nlm: clearing the counter failed");
-    return MUD_ERR_LAUNCH;
-  }
-  const int scaled = vi_scaled(slope, inter);
+  if (int e = vi_clear("mud_volume_denoise_nlm", zeroed, sizeof(uint32_t), s)) return e;
+  const vi_source src = vi_source_of(vol, datatype, slope, inter);
   int e = MUD_OK;
   if (patch == 1) {
-    VI_DISPATCH(datatype, e = (vd_launch_nlm<T, 1>(vol, scaled, slope, inter, X, Y, Z, search, h, bias, rician != 0, out, zeroed, s)));
+    VI_DISPATCH(datatype, e = (vd_launch_nlm<T, 1>(src, X, Y, Z, search, h, bias, rician != 0, out, zeroed, s)));
   } else {
-    VI_DISPATCH(datatype, e = (vd_launch_nlm<T, 2>(vol, scaled, slope, inter, X, Y, Z, search, h, bias, rician != 0, out, zeroed, s)));
+    VI_DISPATCH(datatype, e = (vd_launch_nlm<T, 2>(src, X, Y, Z, search, h, bias, rician != 0, out, zeroed, s)));
   }
   if (e) return e;
   MUD_CHECK_LAUNCH("mud_volume_denoise_nlm");

@@ -14,21 +14,13 @@
 // In front of all that, mud_volume_regrid (--regrid) resamples a volume that lies on another voxel grid onto
 // the grid of the first input: a gather through the affines, trilinear or nearest.
 // DESIGN.md section 5.10 has the definitions and why they equal the host's results bit for bit.
-#include "volume_common.h"      // vi_value, vi_trilinear, VI_DISPATCH, vi_check_volume: shared with volume_coreg.hip
+#include "volume_common.h"
 
 typedef uint32_t vi_u32x4 __attribute__((ext_vector_type(4)));
 
 #define VI_TILE 64
 #define VI_NT (2 + 2 * MUD_VI_MAX_RANKS)      // select targets: min, max, and the two ends of every window
 #define VI_BETWEEN 16                         // capacity per window of the keys strictly between its end keys (at most 14 exist)
-
-// order-preserving uint32 image of a float; every NaN sorts last (np.sort puts them there)
-__device__ __forceinline__ uint32_t vi_key(float v) {
-  if (v != v) return 0xFFFFFFFFu;
-  const uint32_t u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float vi_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
 
 // device state of one census (the head of the workspace); zeroed by the entry point
 struct vi_state {
@@ -45,30 +37,29 @@ struct vi_state {
 
 // f(value) for every voxel: 16-byte loads (the base is 16-byte aligned), the tail by the first threads of block 0
 template <typename T, typename F>
-__device__ __forceinline__ void vi_foreach(const T* __restrict__ p, int64_t n, int scaled, double slope, double inter, F f) {
+__device__ __forceinline__ void vi_foreach(const vi_source& src, int64_t n, F f) {
   constexpr int V = 16 / (int)sizeof(T);
   const int64_t nvec = n / V;
-  const vi_u32x4* __restrict__ pv = reinterpret_cast<const vi_u32x4*>(p);
-  for (int64_t i = (int64_t)blockIdx.x * VI_THREADS + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * VI_THREADS) {
+  const vi_u32x4* __restrict__ pv = reinterpret_cast<const vi_u32x4*>(src.vol);
+  VI_GRID_STRIDE(i, nvec) {
     union {
       vi_u32x4 w;
       T e[V];
     } u;
     u.w = pv[i];
 #pragma unroll
-    for (int j = 0; j < V; ++j) f(vi_value<T>(u.e[j], scaled, slope, inter));
+    for (int j = 0; j < V; ++j) f(vi_value<T>(u.e[j], src.scaled, src.slope, src.inter));
   }
   if (blockIdx.x == 0) {
     const int64_t i = nvec * V + threadIdx.x;
-    if (threadIdx.x < V && i < n) f(vi_value<T>(p[i], scaled, slope, inter));
+    if (threadIdx.x < V && i < n) f(vi_at<T>(src, i));
   }
 }
 
 // one histogram pass: pass 0 counts the top digit of every selected key (and the non-finite ones); pass p > 0 counts digit p of the
 // keys that share a target's prefix, once per group of targets with the same prefix
 template <typename T>
-__global__ __launch_bounds__(VI_THREADS) void k_vi_hist(const T* __restrict__ p, int64_t n, int scaled, double slope, double inter, int pass,
-                                                        vi_state* __restrict__ st) {
+__global__ __launch_bounds__(VI_THREADS) void k_vi_hist(vi_source src, int64_t n, int pass, vi_state* __restrict__ st) {
   __shared__ uint32_t h[VI_NT][256];
   __shared__ uint32_t s_prefix[VI_NT];
   __shared__ int s_lead[VI_NT];
@@ -82,12 +73,12 @@ __global__ __launch_bounds__(VI_THREADS) void k_vi_hist(const T* __restrict__ p,
   if (threadIdx.x == 0) s_nonfinite = 0;
   __syncthreads();
   const int hi_shift = 32 - 8 * pass, lo_shift = 24 - 8 * pass;
-  vi_foreach<T>(p, n, scaled, slope, inter, [&](float v) {
+  vi_foreach<T>(src, n, [&](float v) {
     if (!(v != 0.0f)) return;                 // selection: value != 0 (a NaN is selected, like numpy's data != 0)
     const uint32_t k = vi_key(v);
     if (pass == 0) {
       atomicAdd(&h[0][k >> 24], 1u);
-      if (!(fabsf(v) <= 3.402823466e38f)) atomicAdd(&s_nonfinite, 1u);
+      if (!vc_finite(v)) atomicAdd(&s_nonfinite, 1u);
     } else {
 #pragma unroll
       for (int t = 0; t < VI_NT; ++t)
@@ -180,8 +171,7 @@ __global__ __launch_bounds__(64) void k_vi_scan(vi_state* __restrict__ st, int p
 
 // the keys strictly between the end keys of each window (at most 14 per window, by the ranks of the ends)
 template <typename T>
-__global__ __launch_bounds__(VI_THREADS) void k_vi_gather(const T* __restrict__ p, int64_t n, int scaled, double slope, double inter, int nq,
-                                                          vi_state* __restrict__ st) {
+__global__ __launch_bounds__(VI_THREADS) void k_vi_gather(vi_source src, int64_t n, int nq, vi_state* __restrict__ st) {
   __shared__ uint32_t s_lo[MUD_VI_MAX_RANKS], s_hi[MUD_VI_MAX_RANKS];
   if (st->n == 0) return;
   if (threadIdx.x < MUD_VI_MAX_RANKS) {
@@ -189,7 +179,7 @@ __global__ __launch_bounds__(VI_THREADS) void k_vi_gather(const T* __restrict__ 
     s_hi[threadIdx.x] = st->prefix[3 + 2 * threadIdx.x];
   }
   __syncthreads();
-  vi_foreach<T>(p, n, scaled, slope, inter, [&](float v) {
+  vi_foreach<T>(src, n, [&](float v) {
     if (!(v != 0.0f)) return;
     const uint32_t k = vi_key(v);
     for (int i = 0; i < nq; ++i)
@@ -265,31 +255,23 @@ extern "C" int mud_volume_census(const void* vol, int datatype, int X, int Y, in
     qq[i] = q[i];
   }
   MUD_REQUIRE(record != nullptr && ws != nullptr, "mud_volume_census: null pointer");
-  MUD_REQUIRE((((uintptr_t)record) & 7u) == 0 && (((uintptr_t)ws) & 7u) == 0, "mud_volume_census: record and ws must be 8-byte aligned");
+  MUD_REQUIRE(vi_aligned(record, 8) && vi_aligned(ws, 8), "mud_volume_census: record and ws must be 8-byte aligned");
   MUD_REQUIRE(ws_bytes >= mud_volume_census_ws_bytes(), "mud_volume_census: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
               (long long)mud_volume_census_ws_bytes());
   hipStream_t s = (hipStream_t)stream;
   vi_state* st = (vi_state*)ws;
   const int64_t n = (int64_t)X * Y * Z;
-  const int scaled = vi_scaled(slope, inter);
-  const double dslope = (double)slope, dinter = (double)inter;
-  const int esize = vi_esize(datatype);
-  int64_t blocks = mud_cdiv(mud_cdiv(n, 16 / esize), VI_THREADS);
-  blocks = blocks < 1 ? 1 : blocks > VI_MAX_BLOCKS ? VI_MAX_BLOCKS : blocks;
-  if (hipMemsetAsync(st, 0, sizeof(vi_state), s) != hipSuccess) {
-    mud_set_error("mud_volume_census: clearing the workspace failed");
-    return MUD_ERR_LAUNCH;
-  }
+  const vi_source src = vi_source_of(vol, datatype, slope, inter);
+  const unsigned blocks = vi_blocks(mud_cdiv(n, 16 / vi_esize(datatype)), VI_THREADS, VI_MAX_BLOCKS);      // a thread reads 16 bytes at a time
+  if (int e = vi_clear("mud_volume_census", st, sizeof(vi_state), s)) return e;
   for (int pass = 0; pass < 4; ++pass) {
-    VI_DISPATCH(datatype, hipLaunchKernelGGL(k_vi_hist<T>, dim3((unsigned)blocks), dim3(VI_THREADS), 0, s, (const T*)vol, n, scaled, dslope,
-                                             dinter, pass, st));
+    VI_DISPATCH(datatype, hipLaunchKernelGGL(k_vi_hist<T>, dim3(blocks), dim3(VI_THREADS), 0, s, src, n, pass, st));
     MUD_CHECK_LAUNCH("mud_volume_census (histogram)");
     hipLaunchKernelGGL(k_vi_scan, dim3(1), dim3(64), 0, s, st, pass, nq, qq[0], qq[1], qq[2], qq[3]);
     MUD_CHECK_LAUNCH("mud_volume_census (scan)");
   }
   if (nq > 0) {
-    VI_DISPATCH(datatype, hipLaunchKernelGGL(k_vi_gather<T>, dim3((unsigned)blocks), dim3(VI_THREADS), 0, s, (const T*)vol, n, scaled, dslope,
-                                             dinter, nq, st));
+    VI_DISPATCH(datatype, hipLaunchKernelGGL(k_vi_gather<T>, dim3(blocks), dim3(VI_THREADS), 0, s, src, n, nq, st));
     MUD_CHECK_LAUNCH("mud_volume_census (gather)");
   }
   hipLaunchKernelGGL(k_vi_finish, dim3(1), dim3(64), 0, s, st, nq, record);
@@ -310,15 +292,14 @@ __device__ __forceinline__ float vi_normalise(float v, float lo, float den) {
 // the tile both slab kernels share: f(value) of the 64 x 64 voxels at (x0, y0) of stored plane s0 + i goes through LDS, so that the
 // reads run along x and the writes of out[i][x][y] along y (row stride 65 words: a column read touches 64 different banks)
 template <typename T, typename F>
-__device__ __forceinline__ void vi_slab_tile(const T* __restrict__ vol, int X, int Y, int s0, int scaled, double slope, double inter,
-                                             float* __restrict__ out, F f) {
+__device__ __forceinline__ void vi_slab_tile(const vi_source& src, int X, int Y, int s0, float* __restrict__ out, F f) {
   __shared__ float tile[VI_TILE][VI_TILE + 1];
   const int x0 = blockIdx.x * VI_TILE, y0 = blockIdx.y * VI_TILE, i = blockIdx.z;
   const int lx = threadIdx.x & (VI_TILE - 1), r0 = threadIdx.x / VI_TILE;
-  const T* __restrict__ src = vol + (int64_t)(s0 + i) * X * Y;
+  const int64_t plane = (int64_t)(s0 + i) * X * Y;
   for (int r = r0; r < VI_TILE; r += VI_THREADS / VI_TILE) {                 // row r of the tile: y = y0 + r, lanes along x
     const int x = x0 + lx, y = y0 + r;
-    if (x < X && y < Y) tile[r][lx] = f(vi_value<T>(src[(int64_t)y * X + x], scaled, slope, inter));
+    if (x < X && y < Y) tile[r][lx] = f(vi_at<T>(src, plane + (int64_t)y * X + x));
   }
   __syncthreads();
   float* __restrict__ dst = out + (int64_t)i * X * Y;
@@ -329,9 +310,9 @@ __device__ __forceinline__ void vi_slab_tile(const T* __restrict__ vol, int X, i
 }
 
 template <typename T>
-__global__ __launch_bounds__(VI_THREADS) void k_vi_slab(const T* __restrict__ vol, int X, int Y, int s0, int scaled, double slope, double inter,
-                                                        float lo, float den, int degenerate, float* __restrict__ out) {
-  vi_slab_tile<T>(vol, X, Y, s0, scaled, slope, inter, out, [=](float v) { return degenerate ? 0.0f : vi_normalise(v, lo, den); });
+__global__ __launch_bounds__(VI_THREADS) void k_vi_slab(vi_source src, int X, int Y, int s0, float lo, float den, int degenerate,
+                                                        float* __restrict__ out) {
+  vi_slab_tile<T>(src, X, Y, s0, out, [=](float v) { return degenerate ? 0.0f : vi_normalise(v, lo, den); });
 }
 
 extern "C" int mud_volume_slab_normalise(const void* vol, int datatype, int X, int Y, int Z, float slope, float inter, float lo, float den,
@@ -342,9 +323,8 @@ extern "C" int mud_volume_slab_normalise(const void* vol, int datatype, int X, i
   MUD_REQUIRE(degenerate || (den == den && lo == lo), "mud_volume_slab_normalise: lo / den must not be NaN");
   const dim3 grid((unsigned)mud_cdiv(X, VI_TILE), (unsigned)mud_cdiv(Y, VI_TILE), (unsigned)(s1 - s0 + 1));
   MUD_REQUIRE(grid.y <= 65535 && grid.z <= 65535, "mud_volume_slab_normalise: the volume is too large");
-  const int scaled = vi_scaled(slope, inter);
-  VI_DISPATCH(datatype, hipLaunchKernelGGL(k_vi_slab<T>, grid, dim3(VI_THREADS), 0, (hipStream_t)stream, (const T*)vol, X, Y, s0, scaled,
-                                           (double)slope, (double)inter, lo, den, degenerate, out));
+  VI_DISPATCH(datatype, hipLaunchKernelGGL(k_vi_slab<T>, grid, dim3(VI_THREADS), 0, (hipStream_t)stream, vi_source_of(vol, datatype, slope, inter),
+                                           X, Y, s0, lo, den, degenerate, out));
   MUD_CHECK_LAUNCH("mud_volume_slab_normalise");
   return MUD_OK;
 }
@@ -359,9 +339,9 @@ __device__ __forceinline__ float vi_zscore(float v, float mean, float std) {
 }
 
 template <typename T>
-__global__ __launch_bounds__(VI_THREADS) void k_vi_slab_zscore(const T* __restrict__ vol, int X, int Y, int s0, int scaled, double slope,
-                                                               double inter, float mean, float std, float* __restrict__ out) {
-  vi_slab_tile<T>(vol, X, Y, s0, scaled, slope, inter, out, [=](float v) { return vi_zscore(v, mean, std); });
+__global__ __launch_bounds__(VI_THREADS) void k_vi_slab_zscore(vi_source src, int X, int Y, int s0, float mean, float std,
+                                                               float* __restrict__ out) {
+  vi_slab_tile<T>(src, X, Y, s0, out, [=](float v) { return vi_zscore(v, mean, std); });
 }
 
 extern "C" int mud_volume_slab_zscore(const void* vol, int datatype, int X, int Y, int Z, float slope, float inter, float mean, float std,
@@ -372,9 +352,8 @@ extern "C" int mud_volume_slab_zscore(const void* vol, int datatype, int X, int 
   MUD_REQUIRE(std != 0.0f, "mud_volume_slab_zscore: std must not be 0 (a flat volume passes 1)");
   const dim3 grid((unsigned)mud_cdiv(X, VI_TILE), (unsigned)mud_cdiv(Y, VI_TILE), (unsigned)(s1 - s0 + 1));
   MUD_REQUIRE(grid.y <= 65535 && grid.z <= 65535, "mud_volume_slab_zscore: the volume is too large");
-  const int scaled = vi_scaled(slope, inter);
-  VI_DISPATCH(datatype, hipLaunchKernelGGL(k_vi_slab_zscore<T>, grid, dim3(VI_THREADS), 0, (hipStream_t)stream, (const T*)vol, X, Y, s0, scaled,
-                                           (double)slope, (double)inter, mean, std, out));
+  VI_DISPATCH(datatype, hipLaunchKernelGGL(k_vi_slab_zscore<T>, grid, dim3(VI_THREADS), 0, (hipStream_t)stream,
+                                           vi_source_of(vol, datatype, slope, inter), X, Y, s0, mean, std, out));
   MUD_CHECK_LAUNCH("mud_volume_slab_zscore");
   return MUD_OK;
 }
@@ -403,7 +382,7 @@ __global__ __launch_bounds__(VI_THREADS) void k_vi_assemble(const float* __restr
 
 extern "C" int mud_volume_assemble(const float* planes, const float* planes2, int X, int Y, int Z, int s0, int s1, float* vol, float* vol2,
                                    void* stream) {
-  MUD_REQUIRE(X > 0 && Y > 0 && Z > 0 && (int64_t)X * Y * Z < ((int64_t)1 << 31), "mud_volume_assemble: bad volume size %d x %d x %d", X, Y, Z);
+  if (int e = vi_check_size("mud_volume_assemble", "volume", X, Y, Z)) return e;
   MUD_REQUIRE(s0 >= 0 && s1 >= s0 && s1 < Z, "mud_volume_assemble: the slab %d..%d is not inside the %d planes", s0, s1, Z);
   MUD_REQUIRE(planes != nullptr && vol != nullptr, "mud_volume_assemble: null pointer");
   MUD_REQUIRE((planes2 == nullptr) == (vol2 == nullptr), "mud_volume_assemble: the second stack and the second volume go together");
@@ -419,24 +398,21 @@ extern "C" int mud_volume_assemble(const float* planes, const float* planes2, in
 }
 
 // ---- regrid: a volume on another voxel grid -> fp32 [Z][Y][X] on the reference grid ---------------------------------------------------
-// (vi_mat, vi_coordinate, vi_axis_near and vi_trilinear: volume_common.h)
 template <typename T>
-__global__ __launch_bounds__(VI_THREADS) void k_vi_regrid(const T* __restrict__ src, int SX, int SY, int SZ, int scaled, double slope,
-                                                          double inter, vi_mat M, int mode, int X, int Y, int64_t n,
+__global__ __launch_bounds__(VI_THREADS) void k_vi_regrid(vi_source src, int SX, int SY, int SZ, vi_mat M, int mode, int X, int Y, int64_t n,
                                                           float* __restrict__ out) {
-  for (int64_t i = (int64_t)blockIdx.x * VI_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * VI_THREADS) {
-    const uint32_t l = (uint32_t)i;                          // n < 2^31 (the entry point checks it): 32-bit divisions
-    const uint32_t row = l / (uint32_t)X;
-    const double x = (double)(l - row * (uint32_t)X), y = (double)(row % (uint32_t)Y), z = (double)(row / (uint32_t)Y);
+  VI_GRID_STRIDE(i, n) {
+    int x, y, z;
+    vi_xyz(i, X, Y, x, y, z);
     double p[3];
-    vi_coordinate(M, x, y, z, p);
+    vi_coordinate(M, (double)x, (double)y, (double)z, p);
     float r = 0.0f;
     if (mode == 1) {                                         // nearest: floor(p + 0.5) per axis, 0 outside
       const double qx = floor(p[0] + 0.5), qy = floor(p[1] + 0.5), qz = floor(p[2] + 0.5);
       if (qx >= 0.0 && qx < (double)SX && qy >= 0.0 && qy < (double)SY && qz >= 0.0 && qz < (double)SZ)
-        r = vi_value<T>(src[((int64_t)(int)qz * SY + (int)qy) * SX + (int)qx], scaled, slope, inter);
+        r = vi_at<T>(src, ((int64_t)(int)qz * SY + (int)qy) * SX + (int)qx);
     } else if (vi_axis_near(p[0], SX) && vi_axis_near(p[1], SY) && vi_axis_near(p[2], SZ)) {
-      r = vi_trilinear<T>(src, SX, SY, SZ, scaled, slope, inter, p);
+      r = vi_trilinear<T>(src, SX, SY, SZ, p);
     }
     out[i] = r;
   }
@@ -445,7 +421,7 @@ __global__ __launch_bounds__(VI_THREADS) void k_vi_regrid(const T* __restrict__ 
 extern "C" int mud_volume_regrid(const void* src, int datatype, int SX, int SY, int SZ, float slope, float inter, const double* m, int mode,
                                  int X, int Y, int Z, float* out, void* stream) {
   if (int e = vi_check_volume("mud_volume_regrid", src, datatype, SX, SY, SZ)) return e;
-  MUD_REQUIRE(X > 0 && Y > 0 && Z > 0 && (int64_t)X * Y * Z < ((int64_t)1 << 31), "mud_volume_regrid: bad output size %d x %d x %d", X, Y, Z);
+  if (int e = vi_check_size("mud_volume_regrid", "output", X, Y, Z)) return e;
   MUD_REQUIRE(out != nullptr && m != nullptr, "mud_volume_regrid: null pointer");
   MUD_REQUIRE(mode == 0 || mode == 1, "mud_volume_regrid: mode %d is neither 0 (trilinear) nor 1 (nearest)", mode);
   vi_mat M;
@@ -454,11 +430,8 @@ extern "C" int mud_volume_regrid(const void* src, int datatype, int SX, int SY, 
     M.m[i] = m[i];
   }
   const int64_t n = (int64_t)X * Y * Z;
-  int64_t blocks = mud_cdiv(n, VI_THREADS);
-  blocks = blocks > VI_MAX_BLOCKS ? VI_MAX_BLOCKS : blocks;
-  const int scaled = vi_scaled(slope, inter);
-  VI_DISPATCH(datatype, hipLaunchKernelGGL(k_vi_regrid<T>, dim3((unsigned)blocks), dim3(VI_THREADS), 0, (hipStream_t)stream, (const T*)src, SX,
-                                           SY, SZ, scaled, (double)slope, (double)inter, M, mode, X, Y, n, out));
+  VI_DISPATCH(datatype, hipLaunchKernelGGL(k_vi_regrid<T>, dim3(vi_blocks(n)), dim3(VI_THREADS), 0, (hipStream_t)stream,
+                                           vi_source_of(src, datatype, slope, inter), SX, SY, SZ, M, mode, X, Y, n, out));
   MUD_CHECK_LAUNCH("mud_volume_regrid");
   return MUD_OK;
 }

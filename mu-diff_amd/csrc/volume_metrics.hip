@@ -8,7 +8,7 @@
 //  - the SSIM expression is evaluated with contraction off, so identical inputs give exactly 1.0;
 //  - partials go per (plane, region, workgroup) to a workspace and a second kernel adds them per plane in workgroup order.  No float
 //    atomics: the sums are bit-identical run to run.
-#include "mud_common.h"
+#include "volume_common.h"      // vi_aligned
 
 #define VM_TC 64                          // output columns (Y) of a tile: one per lane
 #define VM_TR 8                           // output rows (X) of a tile: one per wave
@@ -196,7 +196,7 @@ extern "C" int mud_volume_metrics(const float* pred, const float* gt, const uint
   MUD_REQUIRE(pred && gt && region && sums && ws, "mud_volume_metrics: null pointer");
   MUD_REQUIRE(ws_bytes >= mud_volume_metrics_ws_bytes(Z, X, Y, nreg), "mud_volume_metrics: ws holds %lld bytes, needs %lld",
               (long long)ws_bytes, (long long)mud_volume_metrics_ws_bytes(Z, X, Y, nreg));
-  MUD_REQUIRE((((uintptr_t)ws) & 7u) == 0 && (((uintptr_t)sums) & 7u) == 0, "mud_volume_metrics: ws and sums must be 8-byte aligned");
+  MUD_REQUIRE(vi_aligned(ws, 8) && vi_aligned(sums, 8), "mud_volume_metrics: ws and sums must be 8-byte aligned");
   int64_t ntx, nty, nzc;
   vm_grid(Z, X, Y, ntx, nty, nzc);
   const int64_t blocks = ntx * nty * nzc, n = (int64_t)Z * nreg * VM_NQ;
