@@ -440,7 +440,21 @@ int mud_ensemble_stats(const float* samples, int n, int N, int64_t hw, float sca
  *     (the rest of the mask stays).  count (device uint32, cleared first): the voxels switched on.
  *   _apply: out (fp32 [Z][Y][X], not vol)[i] = v where mask[i] != 0 (its bits as they are, a NaN included), +0 elsewhere; removed (device
  *     uint32, cleared first): the candidates outside the mask.
- *   X*Y*Z < 2^31.  Integer atomics only: every result is the same bits on every run. */
+ *   X*Y*Z < 2^31.  Integer atomics only: every result is the same bits on every run.
+ * mud_volume_edt* (--brain_extract; no reference counterpart): morphology by a radius in millimetres on an
+ *   anisotropic grid, as a threshold on an exact Euclidean distance transform; the host's share (a morphological estimate of the brain -
+ *   not a learned extraction) is mudiff_hip.volume_brain.  Masks are uint8 [Z][Y][X] holding 0 or 1, as above.
+ *   _edt: d2 (fp64 [Z][Y][X], 16-byte aligned)[p] = the squared distance, in the units of sx, sy, sz, from voxel p to the nearest voxel
+ *     of the volume whose mask equals `value` (0 or 1): 0 at such a voxel, +inf everywhere without one.  Voxels outside the volume do not
+ *     exist: they count as neither on nor off.  Bit for bit: with wx = sx * sx, wy = sy * sy, wz = sz * sz (each rounded once) and the
+ *     integer offsets (dx, dy, dz) to a voxel q, every product and sum rounded separately,
+ *         d2[p] = min over q of ((wx * (dx * dx)) + (wy * (dy * dy))) + (wz * (dz * dz)).
+ *     fp64 addition is monotone, so this is three passes of out(i) = min over j of (in(j) + w * ((i - j) * (i - j))) along x, y and z
+ *     (one kernel, the lines staged in LDS, each scan pruned once w * k^2 is not below the best so far).  sx, sy, sz: finite and > 0; no
+ *     axis longer than 1024 voxels (a line is staged whole).
+ *   _edt_select: out[i] = (above ? d2[i] > r2 : d2[i] <= r2) && (within == NULL || within[i] != 0), over n voxels; count (device uint32,
+ *     cleared first): the voxels switched on.  r2: finite and >= 0; above: 0 or 1; out is not within.
+ *   X*Y*Z < 2^31.  No floating-point atomics: every result is the same bits on every run. */
 #define MUD_NIFTI_U1 2
 #define MUD_NIFTI_I2 4
 #define MUD_NIFTI_I4 8
@@ -493,6 +507,9 @@ int mud_volume_fg_select(const int32_t* labels, const uint32_t* census, int64_t 
                          void* stream);
 int mud_volume_fg_apply(const void* vol, int datatype, int X, int Y, int Z, float slope, float inter, const uint8_t* mask, float* out,
                         uint32_t* removed, void* stream);
+int mud_volume_edt(const uint8_t* mask, int X, int Y, int Z, int value, double sx, double sy, double sz, double* d2, void* stream);
+int mud_volume_edt_select(const double* d2, int64_t n, double r2, int above, const uint8_t* within, uint8_t* out, uint32_t* count,
+                          void* stream);
 
 #ifdef __cplusplus
 }

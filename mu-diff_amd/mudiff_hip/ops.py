@@ -1177,3 +1177,32 @@ def volume_fg_apply(dev_raw, code, shape, slope, inter, mask):
     _launch('volume_fg_apply', dev_raw.device, load().mud_volume_fg_apply, ptr(dev_raw), int(code), X, Y, Z, float(slope), float(inter), ptr(mask),
             ptr(out), ptr(removed), STREAM, nbytes=float(out.numel() * (dev_raw.element_size() + 5)))
     return out, removed
+
+
+# ---------------------------------------------------------------------------------------------------
+# --brain_extract (csrc/volume_brain.hip; the host's share is mudiff_hip.volume_brain)
+# ---------------------------------------------------------------------------------------------------
+def volume_edt(mask, shape, value, spacing):
+    """mud_volume_edt -> device fp64 [Z, Y, X]: the squared distance, in the units of spacing = (sx, sy, sz), from every voxel to the
+    nearest voxel whose mask is `value` (0 or 1); +inf everywhere without one."""
+    X, Y, Z = _fg_grid('volume_edt', mask, shape, torch.uint8)
+    sx, sy, sz = (float(v) for v in spacing)
+    d2 = torch.empty(Z, Y, X, device=mask.device, dtype=torch.float64)
+    _launch('volume_edt', mask.device, load().mud_volume_edt, ptr(mask), X, Y, Z, int(value), sx, sy, sz, ptr(d2), STREAM,
+            nbytes=41.0 * mask.numel())
+    return d2
+
+
+def volume_edt_select(d2, r2, above, within=None):
+    """mud_volume_edt_select -> (device uint8 mask shaped like d2: (d2 > r2 if above else d2 <= r2) and within; device int32 [1]: the
+    voxels switched on)."""
+    require_gpu(d2, within)
+    if d2.dtype != torch.float64 or not d2.is_contiguous() or d2.numel() == 0:
+        raise MudiffHipError(f'volume_edt_select: need contiguous fp64 squared distances, got {d2.dtype} {tuple(d2.shape)}')
+    if within is not None and (within.dtype != torch.uint8 or within.numel() != d2.numel() or not within.is_contiguous()):
+        raise MudiffHipError(f'volume_edt_select: `within` must be a contiguous uint8 mask of {d2.numel()} voxels')
+    out = torch.empty(d2.shape, device=d2.device, dtype=torch.uint8)
+    count = torch.empty(1, device=d2.device, dtype=torch.int32)
+    _launch('volume_edt_select', d2.device, load().mud_volume_edt_select, ptr(d2), int(d2.numel()), float(r2), int(bool(above)), ptr(within),
+            ptr(out), ptr(count), STREAM, nbytes=10.0 * d2.numel())
+    return out, count

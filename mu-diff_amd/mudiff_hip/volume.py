@@ -695,14 +695,31 @@ def make_parser(prog='MU-Diff volume prediction (MI355X)'):
                    help='set the voxels outside a foreground mask of every input to exactly 0, on its own grid, after --denoise and before '
                         '--coregister / --regrid / --bias_correct see it (Otsu threshold, largest 6-connected component, holes filled, on '
                         'the GPU: mudiff_hip.volume_foreground); foreground_<t>.json next to the prediction holds what was found.  This is '
-                        'a head / object mask by thresholding and topology, NOT a brain extraction: the skull stays.  --gt_volume / '
-                        '--eval_mask are not masked')
+                        'a head / object mask by thresholding and topology, NOT a brain extraction: the skull stays (see --brain_extract).  '
+                        '--gt_volume / --eval_mask are not masked')
     p.add_argument('--foreground_bins', type=int, default=256, help='bins of the histogram the Otsu threshold is taken from (16 to 1024)')
     p.add_argument('--foreground_open', type=int, default=0,
                    help='open the thresholded mask first: this many erosions, then as many dilations, over the 6-neighbourhood (0 to 3)')
     p.add_argument('--foreground_keep_holes', action='store_true', help='with --foreground: do not fill the holes of the kept component')
     p.add_argument('--foreground_mask_out', action='store_true',
                    help='with --foreground: also write foreground_<t>_<name>.nii.gz, the uint8 mask of each input on its own grid')
+    p.add_argument('--brain_extract', action='store_true',
+                   help='estimate one brain mask per subject and set the voxels of every input outside it to exactly 0, once the inputs '
+                        'are on the common grid (after --coregister / --regrid) and before --bias_correct and the normalisation see '
+                        'them: the tissue mask of --foreground, eroded by --brain_erode_mm so that the bridges between brain and scalp '
+                        'break, its largest component grown back by --brain_dilate_mm inside the tissue, holes filled (exact Euclidean '
+                        'distance transform with the voxel spacing, on the GPU: mudiff_hip.volume_brain); brain_<t>.json next to the '
+                        'prediction holds what was found.  This is a morphological estimate, not a learned brain extraction.  '
+                        '--gt_volume / --eval_mask are not masked')
+    p.add_argument('--brain_from', type=str, default=None,
+                   help='the input the mask is estimated from (T1, T1CE, T2 or FLAIR; default: T1, else T1CE, else the first input)')
+    p.add_argument('--brain_erode_mm', type=float, default=5.0, help='erosion radius in millimetres (finite, > 0)')
+    p.add_argument('--brain_dilate_mm', type=float, default=6.0,
+                   help='how far the eroded core grows back, in millimetres, inside the thresholded tissue (not below --brain_erode_mm)')
+    p.add_argument('--brain_bins', type=int, default=256, help='bins of the histogram the Otsu threshold is taken from (16 to 1024)')
+    p.add_argument('--brain_keep_holes', action='store_true', help='with --brain_extract: do not fill the holes of the mask')
+    p.add_argument('--brain_mask_out', action='store_true',
+                   help='with --brain_extract: also write brain_<t>_mask.nii.gz, the uint8 mask on the grid of the first input')
     from .driver import add_calibration_flags
     add_calibration_flags(p)                # (also --prec_plan)
     return p
@@ -735,6 +752,11 @@ def finish_args(p, args):
         check_foreground(args.foreground_bins, args.foreground_open, args.foreground_keep_holes, args.foreground_mask_out)
     except ValueError as e:
         p.error(str(e))
+    from .volume_brain import check_options as check_brain
+    try:
+        check_brain(args.brain_bins, args.brain_erode_mm, args.brain_dilate_mm, args.brain_keep_holes)
+    except ValueError as e:
+        p.error(str(e))
     return args
 
 
@@ -746,7 +768,8 @@ def build_argparser(argv=None):
     (the training normalisation), --regrid (inputs on other voxel grids),
     --coregister (rigid alignment of the inputs to the first one), --bias_correct (removal of the coil
     shading of every input), --denoise (non-local-means denoising of every input) and
-    --foreground (a foreground mask of every input: everything outside becomes 0)."""
+    --foreground (a foreground mask of every input: everything outside becomes 0) and --brain_extract (one
+    morphological brain mask per subject, applied to every input)."""
     p = make_parser()
     return finish_args(p, p.parse_args(argv))
 

@@ -12,7 +12,8 @@ replaced by itself with the voxels outside its foreground mask set to exactly 0,
     mud_volume_fg_label(0) / _census / _select --> plus its holes (the components of the complement that touch no face)
     mud_volume_fg_apply --> fp32 [Z,Y,X], a volume like a regridded one, with the source's own geometry
 
-This is a foreground (head or object) mask by thresholding and topology.  It is NOT a brain extraction: the skull and the scalp stay.
+This is a foreground (head or object) mask by thresholding and topology.  It is not a brain extraction: the skull and the scalp stay
+(--brain_extract, mudiff_hip.volume_brain, estimates the brain by morphology on top of the same threshold).
 All per-voxel work is the device's and all of it is integer work: the host sees the counts and a few words per stage, and two runs give
 the same bits.
 """
@@ -89,6 +90,45 @@ def _word(t, dtype=np.uint32):
     return t.cpu().numpy().view(dtype)
 
 
+def threshold_mask(dev, meta, bins, report):
+    """The first half of foreground(), shared with volume_brain.brain_mask: the candidates' range and histogram, the Otsu bin and the
+    raw mask (device uint8 [Z,Y,X]) of the candidates above it.  Fills report's candidates, lo, hi, bin and threshold as far as it gets;
+    None without a candidate, with hi == lo or with fewer than two non-empty bins."""
+    from . import ops
+    found = _word(ops.volume_fg_range(dev, *meta))
+    report['candidates'] = int(found[2])
+    if report['candidates'] == 0:
+        return None
+    lo, hi = unkey(~int(found[0])), unkey(found[1])
+    report['lo'], report['hi'] = lo, hi
+    if hi == lo:
+        return None
+    scale = bins / (hi - lo)
+    k = otsu_bin(_word(ops.volume_fg_hist(dev, *meta, lo, scale, bins)).astype(np.int64))
+    if k is None:
+        return None
+    report['bin'], report['threshold'] = k, lo + (k + 1) / scale
+    return ops.volume_fg_mask(dev, *meta, lo, scale, bins, k)
+
+
+def largest_component(mask, shape):
+    """-> (the largest 6-connected component of a device mask, or None for an empty mask; its voxels; the number of components)."""
+    from . import ops
+    labels = ops.volume_fg_label(mask, shape, 1)
+    winner, components = (int(v) for v in _word(ops.volume_fg_census(labels, shape)[1], np.uint64))
+    if not components:
+        return None, 0, 0
+    return ops.volume_fg_select(labels, None, 0xFFFFFFFF - (winner & 0xFFFFFFFF), False)[0], winner >> 32, components
+
+
+def fill_holes(mask, shape):
+    """Switches on, in `mask` itself, the components of its complement that touch no face of the volume -> (mask, the voxels added)."""
+    from . import ops
+    labels = ops.volume_fg_label(mask, shape, 0)
+    mask, filled = ops.volume_fg_select(labels, ops.volume_fg_census(labels, shape)[0], 0, True, mask)
+    return mask, int(_word(filled)[0])
+
+
 def foreground(raw, device, bins=256, open=0, keep_holes=False, mask_out=False):      # noqa: A002
     """A RawVolume (its voxels on the host, or on the device already) -> (MaskedVolume, report).  report: threshold (fp64, for
     information: the bin is what is compared), bin, bins, lo, hi, candidates, components (of the mask the largest one was taken from),
@@ -103,32 +143,16 @@ def foreground(raw, device, bins=256, open=0, keep_holes=False, mask_out=False):
     shape = meta[1]
     report = dict(threshold=None, bin=None, bins=bins, lo=None, hi=None, candidates=0, components=0, kept=0, filled=0, removed=0,
                   open=steps, keep_holes=bool(keep_holes))
-    found = _word(ops.volume_fg_range(dev, *meta))
-    report['candidates'] = int(found[2])
-    if report['candidates'] == 0:
+    mask = threshold_mask(dev, meta, bins, report)
+    if mask is None:
         return raw, report
-    lo, hi = unkey(~int(found[0])), unkey(found[1])
-    report['lo'], report['hi'] = lo, hi
-    if hi == lo:
-        return raw, report
-    scale = bins / (hi - lo)
-    k = otsu_bin(_word(ops.volume_fg_hist(dev, *meta, lo, scale, bins)).astype(np.int64))
-    if k is None:
-        return raw, report
-    report['bin'], report['threshold'] = k, lo + (k + 1) / scale
-    mask = ops.volume_fg_mask(dev, *meta, lo, scale, bins, k)
     for dilate in (False,) * steps + (True,) * steps:
         mask = ops.volume_fg_morph(mask, shape, dilate)
-    labels = ops.volume_fg_label(mask, shape, 1)
-    winner, components = (int(v) for v in _word(ops.volume_fg_census(labels, shape)[1], np.uint64))
-    report['components'] = components
-    if components:
-        mask = ops.volume_fg_select(labels, None, 0xFFFFFFFF - (winner & 0xFFFFFFFF), False)[0]
-        report['kept'] = winner >> 32
+    kept, report['kept'], report['components'] = largest_component(mask, shape)
+    if kept is not None:
+        mask = kept
         if not keep_holes:
-            labels = ops.volume_fg_label(mask, shape, 0)
-            mask, filled = ops.volume_fg_select(labels, ops.volume_fg_census(labels, shape)[0], 0, True, mask)
-            report['filled'] = int(_word(filled)[0])
+            mask, report['filled'] = fill_holes(mask, shape)
             report['kept'] += report['filled']
     out, removed = ops.volume_fg_apply(dev, *meta, mask)      # (an opening that left nothing: every candidate goes)
     report['removed'] = int(_word(removed)[0])

@@ -1,9 +1,9 @@
-"""The one input-preparation stage of the volume pipeline (DESIGN.md sections 5.10 - 5.16): every entry point - volume.predict_volume
+"""The one input-preparation stage of the volume pipeline (DESIGN.md sections 5.10 - 5.18): every entry point - volume.predict_volume
 on the host, with --device_intake, and mudiff_hip.cohort - reads a subject's files, hands them to prepare_inputs and normalises what
 comes back, on the host (volume.host_stacks) or on the device (volume_intake.condition_from_raw).
 
-    IntakeOptions.from_args(args)                         what --norm / --regrid / --coregister / --bias_correct / --denoise / --foreground ask for, built once
-    prepare_inputs(named_raws, options, device)           denoise; foreground; first input = the grid; coregister; regrid, or check the shape; bias-correct
+    IntakeOptions.from_args(args)                         what --norm / --regrid / --coregister / --bias_correct / --denoise / --foreground / --brain_extract ask for, built once
+    prepare_inputs(named_raws, options, device)           denoise; foreground; first input = the grid; coregister; regrid, or check the shape; brain mask; bias-correct
     IntakeReport                                          what that did, by modality name: the [done] line's tail and the report files
 """
 from __future__ import annotations
@@ -11,6 +11,7 @@ from __future__ import annotations
 import collections
 
 from . import volume_bias as VB
+from . import volume_brain as VBR
 from . import volume_coreg as VC
 from . import volume_denoise as VD
 from . import volume_foreground as VF
@@ -19,19 +20,20 @@ from .volume import regrid_suffix
 from .volume_intake import slab_range
 
 
-class IntakeOptions(collections.namedtuple('IntakeOptions', 'norm regrid coreg bias half_range foreground denoise',
-                                           defaults=('percentile', False, None, None, 80, None, None))):
+class IntakeOptions(collections.namedtuple('IntakeOptions', 'norm regrid coreg bias half_range foreground brain denoise',
+                                           defaults=('percentile', False, None, None, 80, None, None, None))):
     """norm: --norm; regrid: --regrid; coreg / bias / denoise / foreground: the keyword arguments of volume_coreg.coregister /
     volume_bias.correct / volume_denoise.denoise / volume_foreground.foreground, or None without --coregister / --bias_correct / --denoise /
-    --foreground; half_range: --slice_half_range (the slab is part of the reference geometry).  `foreground` sits before `denoise`,
-    not at the end: tests/test_volume_denoise_host.py pins `denoise` as the last field, and every positional use stops at half_range."""
+    --foreground; half_range: --slice_half_range (the slab is part of the reference geometry); brain: the keyword arguments of volume_brain.brain_mask plus
+    `source` (--brain_from or None) and `mask_out`, or None without --brain_extract.  `foreground` and `brain` sit before `denoise`, not
+    at the end: tests/test_volume_denoise_host.py pins `denoise` as the last field, and every positional use stops at half_range."""
     __slots__ = ()
 
     @classmethod
     def from_args(cls, args):
         """The only place that knows the flags' defaults (a namespace that did not come from volume.make_parser may lack any of them)."""
         get = lambda name, default: getattr(args, name, default)      # noqa: E731
-        coreg = bias = denoise = foreground = None
+        coreg = bias = denoise = foreground = brain = None
         if get('coregister', False):
             coreg = dict(strides=tuple(int(s) for s in get('coregister_strides', None) or (4, 2, 1)),
                          max_mm=float(get('coregister_max_mm', 20.0)), max_deg=float(get('coregister_max_deg', 15.0)))
@@ -45,26 +47,34 @@ class IntakeOptions(collections.namedtuple('IntakeOptions', 'norm regrid coreg b
         if get('foreground', False):
             foreground = dict(bins=int(get('foreground_bins', VF.DEFAULTS['bins'])), open=int(get('foreground_open', VF.DEFAULTS['open'])),
                               keep_holes=bool(get('foreground_keep_holes', False)), mask_out=bool(get('foreground_mask_out', False)))
-        return cls(get('norm', 'percentile'), bool(get('regrid', False)), coreg, bias, int(get('slice_half_range', 80)), foreground, denoise)
+        if get('brain_extract', False):
+            source = get('brain_from', None)
+            brain = dict(bins=int(get('brain_bins', VBR.DEFAULTS['bins'])), erode_mm=float(get('brain_erode_mm', VBR.DEFAULTS['erode_mm'])),
+                         dilate_mm=float(get('brain_dilate_mm', VBR.DEFAULTS['dilate_mm'])), keep_holes=bool(get('brain_keep_holes', False)),
+                         source=None if source is None else str(source), mask_out=bool(get('brain_mask_out', False)))
+        return cls(get('norm', 'percentile'), bool(get('regrid', False)), coreg, bias, int(get('slice_half_range', 80)), foreground, brain,
+                   denoise)
 
 
 class IntakeReport:
     """What the preparation did to one subject, by modality name: `regridded` [name] (a caller appends the evaluation inputs --regrid
     resampled: `report.regridded += names`), `coreg` [(name, report)], `bias` [(name, report, field or None)], `denoise` [(name,
-    report)], `foreground` [(name, report, the masked volume or None)]."""
+    report)], `foreground` [(name, report, the masked volume or None)], `brain` [(the source's name, report, the uint8 [X,Y,Z] host mask or
+    None)]: one entry per subject."""
 
     def __init__(self, regridded=()):
-        self.regridded, self.coreg, self.bias, self.denoise, self.foreground = list(regridded), [], [], [], []
+        self.regridded, self.coreg, self.bias, self.denoise, self.foreground, self.brain = list(regridded), [], [], [], [], []
 
     def suffix(self):
-        """What a [done] line gains: ` | regrid=... | coreg=... | bias=... | denoise=... | foreground=...`, each part only when its list is
-        not empty."""
+        """What a [done] line gains: ` | regrid=... | coreg=... | bias=... | denoise=... | foreground=... | brain=...`, each part only when
+        its list is not empty."""
         return (regrid_suffix(self.regridded) + VC.coreg_suffix(self.coreg) + VB.bias_suffix(self.bias) + VD.denoise_suffix(self.denoise) +
-                VF.foreground_suffix(self.foreground))
+                VF.foreground_suffix(self.foreground) + VBR.brain_suffix(self.brain))
 
     def write(self, output_dir, target, affine, header):
         """coreg_<t>.json, bias_<t>.json (and the fields --bias_field_out asked for) , denoise_<t>.json and foreground_<t>.json (and the masks
-        --foreground_mask_out asked for) next to the prediction; nothing when empty."""
+        --foreground_mask_out asked for) and brain_<t>.json (and the mask --brain_mask_out asked for, on the grid of `affine` / `header`)
+        next to the prediction; nothing when empty."""
         if self.coreg:
             VC.write_reports(self.coreg, output_dir, target)
         if self.bias:
@@ -73,6 +83,8 @@ class IntakeReport:
             VD.write_reports(self.denoise, output_dir, target)
         if self.foreground:
             VF.write_reports(self.foreground, output_dir, target, affine, header)
+        if self.brain:
+            VBR.write_reports(self.brain, output_dir, target, affine, header)
 
 
 def prepare_inputs(named_raws, options, device, labels=None):
@@ -86,12 +98,18 @@ def prepare_inputs(named_raws, options, device, labels=None):
     (volume_foreground.foreground: same shape, affine and header again), and everything below sees the masked list.
     The first input defines the grid and is never registered or resampled.  Every later one is aligned to it under --coregister
     (volume_coreg.coregister -> world), then resampled under --regrid or --coregister (volume_regrid.regrid_to: untouched when it is on the
-    grid already); otherwise it must have the first one's shape.  Under --bias_correct every input, the first included, is then divided by
-    its bias field (volume_bias.correct).  ValueError for an input that is not 3D, before any device work."""
+    grid already); otherwise it must have the first one's shape.  Under --brain_extract one brain mask is then estimated from one input
+    on that grid (volume_brain.source_of picks it; volume_brain.brain_mask) and every input has the voxels outside it set to exactly 0; a
+    mask that could not be estimated leaves the inputs as they are (the report's `kept` is 0).  Under --bias_correct every input, the first
+    included, is then divided by its bias field (volume_bias.correct).  ValueError for an input that is not 3D or a --brain_from that is
+    not among the inputs, before any device work."""
     label = lambda name: (labels or {}).get(name, name)      # noqa: E731
     for name, raw in named_raws:
         if len(raw.shape) != 3:
             raise ValueError(f'{label(name)}: expected a 3D volume, got shape {raw.shape}')
+    brain = None if options.brain is None else dict(options.brain)
+    if brain is not None:
+        source, mask_out = VBR.source_of([name for name, _ in named_raws], brain.pop('source', None)), brain.pop('mask_out', False)
     report = IntakeReport()
     if options.denoise is not None:
         cleaned = []
@@ -110,6 +128,12 @@ def prepare_inputs(named_raws, options, device, labels=None):
     first = named_raws[0][1]
     ref = (first.shape, first.affine, first.header) + slab_range(first.shape[2], options.half_range)
     ref_world = VR.world_affine_of(first.affine, first.header)
+    def corrected(name, vol):
+        if options.bias is not None:
+            vol, found = VB.correct(vol, device, **options.bias)
+            report.bias.append((name, found, vol.field if options.bias['field'] else None))
+        return vol
+
     prepared = []
     for k, (name, raw) in enumerate(named_raws):
         vol = raw
@@ -125,8 +149,13 @@ def prepare_inputs(named_raws, options, device, labels=None):
                 report.regridded.append(name)
         elif raw.shape != ref[0]:
             raise ValueError(f'All input volumes must share shape. Got {raw.shape} vs {ref[0]} for {label(name)}')
-        if options.bias is not None:
-            vol, found = VB.correct(vol, device, **options.bias)
-            report.bias.append((name, found, vol.field if options.bias['field'] else None))
-        prepared.append(vol)
+        prepared.append(corrected(name, vol) if brain is None else vol)      # (the mask needs every input on the grid first)
+    if brain is not None:
+        names = [name for name, _ in named_raws]
+        mask, found = VBR.brain_mask(prepared[names.index(source)], device, **brain)
+        found['source'] = source
+        report.brain.append((source, found, VBR.host_mask(mask) if mask_out and mask is not None else None))
+        if mask is not None:
+            prepared = [VBR.apply_mask(vol, mask, device) for vol in prepared]
+        prepared = [corrected(name, vol) for name, vol in zip(names, prepared)]
     return prepared, ref, report
