@@ -372,6 +372,27 @@ int mud_ensemble_stats(const float* samples, int n, int N, int64_t hw, float sca
  *   at the border); one whose weight is exactly 0 is not read, so identities and integer shifts are bit-exact, next to a NaN too.
  *   mode 1, nearest (label volumes): the value at floor(p + 0.5) per axis, 0 outside the source.
  *   Both sizes obey X*Y*Z < 2^31; m must be finite.
+ * mud_volume_bspline_coeffs, mud_volume_regrid_cubic (--regrid_interp cubic; no reference counterpart): mode 0 of
+ *   mud_volume_regrid with a cubic B-spline in place of the trilinear kernel, in two steps.
+ *   _bspline_coeffs: coeffs (device fp64 [SZ][SY][SX], 16-byte aligned, not vol) = the cubic B-spline coefficients of the stored volume
+ *     under mirror (whole-sample symmetric) boundaries.  s = double(the value of a stored voxel), 0 for a non-finite value; nonfinite
+ *     (device uint32, cleared first) counts those.  Every line s[0 .. N-1], along x, then y, then z, is replaced as follows, with
+ *     z = sqrt(3) - 2 formed once on the host and every product and sum rounded separately (no fused multiply-add): for N == 1, c = s;
+ *     else g[i] = 6 * s[i]; a = sum over k = 0 .. 2N-3, in increasing k, of zk * g[m(k)], where zk starts at 1 and is multiplied by z
+ *     after each term and m(k) = k for k <= N-1, else 2N-2-k; c+[0] = a / (1 - zk) with the final zk; c+[i] = g[i] + z * c+[i-1];
+ *     c[N-1] = (z / (z * z - 1)) * (c+[N-1] + z * c+[N-2]); c[i] = z * (c[i+1] - c+[i]) for i = N-2 .. 0.  No axis has a maximum length
+ *     (the x pass moves along its lines in chunks staged in LDS, the y and z passes run one thread per line).
+ *   _regrid_cubic: out, fp32 [Z][Y][X], from coeffs and the stored volume src they were made from (same size, datatype, slope, inter).
+ *     m: the matrix of mud_volume_regrid; p = m * (i, j, k, 1) in fp64, ((m0 * i + m1 * j) + m2 * k) + m3 per axis, every product and sum
+ *     rounded separately.  out = +0 when some axis does not satisfy 0 <= p_a <= S_a - 1 (no extrapolation), and when every in-volume
+ *     neighbour of non-zero weight among the 8 trilinear neighbours of p (mode 0 of mud_volume_regrid) is a voxel whose value is 0: the
+ *     background guard, so that the ringing of the spline creates no non-zero voxel where trilinear resampling leaves exact zeros.
+ *     Otherwise f = floor(p), t = p - f, the weights b0 .. b3 of mud_volume_bias_* at t apply to the coefficient indices f-1 .. f+2 per
+ *     axis, mirrored at each end (i < 0 -> -i, i > S-1 -> 2 (S-1) - i, and once more -i should that be negative; every index is 0 for
+ *     S == 1), and out = float32(clamp(sum, lo, hi)), the fp64 sum running over the 4 x 4 x 4 support, z outermost and x fastest, of
+ *     ((bx * by) * bz) * c.  lo, hi: finite, lo <= 0 <= hi; the caller passes the range of the source's finite values widened to contain
+ *     0 (mud_volume_fg_range yields it), which keeps the overshoot of the spline at an edge inside the values the volume has.
+ *   Both sizes obey X*Y*Z < 2^31; m must be finite.  No atomics on floating-point values: the same bits on every run.
  * mud_volume_joint_hist (--coregister): the joint histogram a rigid registration search evaluates, between a
  *   fixed volume (X x Y x Z stored voxels) and a moving one (SX x SY x SZ) seen through m, the matrix of mud_volume_regrid (fixed voxel
  *   index -> moving voxel coordinate, 12 doubles on the host).  Sample points: the fixed voxels (i, j, k) whose indices are all multiples
@@ -480,6 +501,10 @@ int mud_volume_assemble(const float* planes, const float* planes2, int X, int Y,
                         void* stream);
 int mud_volume_regrid(const void* src, int datatype, int SX, int SY, int SZ, float slope, float inter, const double* m, int mode, int X,
                       int Y, int Z, float* out, void* stream);
+int mud_volume_bspline_coeffs(const void* vol, int datatype, int SX, int SY, int SZ, float slope, float inter, double* coeffs,
+                              uint32_t* nonfinite, void* stream);
+int mud_volume_regrid_cubic(const double* coeffs, int SX, int SY, int SZ, const void* src, int datatype, float slope, float inter,
+                            const double* m, double lo, double hi, int X, int Y, int Z, float* out, void* stream);
 int mud_volume_joint_hist(const void* fix, int fix_dt, int X, int Y, int Z, float fix_slope, float fix_inter, const void* mov, int mov_dt,
                           int SX, int SY, int SZ, float mov_slope, float mov_inter, const double* m, int stride, double fix_lo,
                           double fix_scale, double mov_lo, double mov_scale, int bins, uint32_t* hist, void* stream);

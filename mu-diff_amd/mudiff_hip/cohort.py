@@ -227,11 +227,12 @@ def run(args, subjects, predict=None):
                     sargs = copy.copy(args)
                     sargs.output_dir = os.path.join(args.output_dir, subject.id)
                     gpu = device or torch.device(f'cuda:{args.gpu_chose}')
-                    evaluation, resampled = None, []
+                    evaluation, resampled, found = None, [], {}
                     if ev is not None:                             # the evaluation inputs onto the first input's grid, checked
                         evaluation, resampled = VM.eval_inputs_on_grid((raws[0].shape, raws[0].affine, raws[0].header), *ev, options.regrid,
                                                                        options.half_range, gpu, names=(subject.inputs[needed[0]], subject.gt),
-                                                                       wording=lambda e: f'ground truth / mask: {e}')
+                                                                       wording=lambda e: f'ground truth / mask: {e}',
+                                                                       interp=options.interp, found=found)
                     torch.manual_seed(args.seed)
                     t0 = time.perf_counter()
                     conds, ref, report = prepare_inputs(list(zip(needed, raws)), options, gpu,      # (--coregister and --bias_correct work
@@ -241,6 +242,7 @@ def run(args, subjects, predict=None):
                                  for m, vol in zip(needed, conds)]
                         torch.cuda.synchronize(device)
                     report.regridded += resampled
+                    report.nonfinite += found.get('nonfinite', 0)
                     sargs.intake_report = report                   # (the [done] line names what it lists)
                     timing['intake'] += time.perf_counter() - t0
 

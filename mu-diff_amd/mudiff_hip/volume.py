@@ -354,9 +354,10 @@ def predict_volume(args):
     --bias_field_out, the field volumes), denoise_<target>.json and foreground_<target>.json (and, with --foreground_mask_out, the masks)
     next to the prediction (volume_prepare.IntakeReport.write)."""
     from .volume_prepare import IntakeReport
-    evaluation, resampled = _load_eval_inputs(args)
+    found = {}
+    evaluation, resampled = _load_eval_inputs(args, found)
     args = copy.copy(args)                               # the run's own copy: it carries the record of what the intake did
-    args.intake_report = IntakeReport(resampled)
+    args.intake_report = IntakeReport(resampled, nonfinite=found.get('nonfinite', 0))
     from . import ops
     from .driver import effective_prec_plan
     plan = effective_prec_plan(args)
@@ -380,12 +381,12 @@ def load_eval_inputs(args):
     """--gt_volume / --eval_mask -> None, or (raw GT volume, label volume or None) once the files have been read and their shapes
     checked against the first input volume and the slab (volume_metrics.check_shapes).  A bad evaluation input raises ValueError
     here, so that it cannot cost a sampling run.  With --regrid a ground truth or a label volume on another grid is first resampled
-    onto the first input's (mudiff_hip.volume_regrid: trilinear / nearest neighbour)."""
+    onto the first input's (mudiff_hip.volume_regrid: trilinear, or cubic under --regrid_interp cubic / nearest neighbour)."""
     return _load_eval_inputs(args)[0]
 
 
-def _load_eval_inputs(args):
-    """load_eval_inputs -> (its result, the names of the evaluation inputs --regrid resampled)."""
+def _load_eval_inputs(args, found=None):
+    """load_eval_inputs -> (its result, the names of the evaluation inputs --regrid resampled); `found`: volume_regrid.eval_onto_grid's."""
     if args.gt_volume is None:
         if args.eval_mask is not None:
             raise ValueError('--eval_mask needs --gt_volume')
@@ -406,7 +407,8 @@ def _load_eval_inputs(args):
         label = None if args.eval_mask is None else read_nifti(args.eval_mask)[0]
     return eval_inputs_on_grid(ref, gt, label, gt_aff, args.regrid, args.slice_half_range, torch.device(f'cuda:{args.gpu_chose}'),
                                names=(first, args.gt_volume),
-                               wording=lambda e: f'--gt_volume / --eval_mask: {e} (the prediction has the shape of {first})')
+                               wording=lambda e: f'--gt_volume / --eval_mask: {e} (the prediction has the shape of {first})',
+                               interp=getattr(args, 'regrid_interp', 'linear'), found=found)
 
 
 def _score_prediction(args, evaluation, vol, std_vol, device):
@@ -443,6 +445,7 @@ def _predict_volume(args, plan, evaluation=None):
     prepared, ref, report = prepare_inputs([(m, VI.read_nifti_raw(path)) for m, path in needed], options, device,
                                            labels=dict(needed) if args.device_intake else None)      # (the device path names the file)
     report.regridded += _intake_report(args).regridded       # the inputs first, then the evaluation inputs predict_volume resampled
+    report.nonfinite += _intake_report(args).nonfinite
     args.intake_report = report
     if args.device_intake:
         stacks = [VI.condition_from_raw(vol, options.half_range, args.image_size, device, name=path, norm=options.norm)
@@ -656,6 +659,12 @@ def make_parser(prog='MU-Diff volume prediction (MI355X)'):
                         "input's grid (shape and affine) is resampled onto it on the GPU through the affines before normalisation, "
                         'trilinearly (the label volume: nearest neighbour).  Resampling only: the volumes must already share one '
                         'world space (mudiff_hip.volume_regrid)')
+    p.add_argument('--regrid_interp', type=str, default='linear', choices=['linear', 'cubic'],
+                   help="how --regrid / --coregister resample an input (and --regrid the --gt_volume): 'linear' = trilinearly, which "
+                        "softens the volume by an amount that depends on the sub-voxel offset; 'cubic' = with a cubic B-spline "
+                        '(recursive prefilter + 4 x 4 x 4 gather on the GPU: mudiff_hip.volume_regrid), which keeps the sharpness of the '
+                        'first input; zero background stays exactly zero.  The label volume stays nearest neighbour and the registration '
+                        'search trilinear')
     p.add_argument('--coregister', action='store_true',
                    help='rigidly align every input other than the first to the first input (six parameters, normalised mutual '
                         'information, histogram on the GPU: mudiff_hip.volume_coreg), then resample it onto the first input\'s grid '
@@ -765,7 +774,8 @@ def build_argparser(argv=None):
     the generators read and the reference parser forgot), --batch_size, --resize_back, --calibrate / --calibrate_threshold
     (mudiff_hip.precision; the record goes to <output_dir>/prec_calibration.json), --num_samples (ensembles), --gt_volume /
     --eval_mask (scoring of the written prediction, mudiff_hip.volume_metrics), --device_intake (mudiff_hip.volume_intake), --norm
-    (the training normalisation), --regrid (inputs on other voxel grids),
+    (the training normalisation), --regrid (inputs on other voxel grids; --regrid_interp:
+    trilinear or cubic B-spline resampling),
     --coregister (rigid alignment of the inputs to the first one), --bias_correct (removal of the coil
     shading of every input), --denoise (non-local-means denoising of every input) and
     --foreground (a foreground mask of every input: everything outside becomes 0) and --brain_extract (one

@@ -228,11 +228,11 @@ def score_arrays(pred_vol, gt_raw, label=None, std_vol=None, slice_half_range=80
 
 
 def score_files(pred_path, gt_path, mask_path=None, std_path=None, slice_half_range=80, device='cuda', norm='percentile', regrid=False,
-                resampled=None):
+                resampled=None, interp='linear'):
     """score_arrays on NIfTI files (volume.read_nifti): the prediction, the raw GT, an optional label volume (--eval_mask, e.g. a
     BraTS segmentation) and an optional std volume.  Warns when the prediction's affine differs from the GT's.  With `regrid`
     (--regrid) a GT or a label volume that is not on the prediction's grid is first resampled onto it (mudiff_hip.volume_regrid:
-    trilinear / nearest neighbour); the list `resampled` receives their names."""
+    trilinear, or a cubic B-spline with interp='cubic' (--regrid_interp) / nearest neighbour); the list `resampled` receives their names."""
     from .volume import read_nifti
     pred, pa, ph = read_nifti(pred_path)
     std = None if std_path is None else read_nifti(std_path)[0]
@@ -244,7 +244,7 @@ def score_files(pred_path, gt_path, mask_path=None, std_path=None, slice_half_ra
         ga = gt_raw.affine
         gt, label, done = VR.eval_onto_grid(pred.shape, VR.world_affine_of(pa, ph), gt_raw,
                                             None if mask_path is None else VI.read_nifti_raw(mask_path), torch.device(device),
-                                            names=('gt', 'mask'))
+                                            names=('gt', 'mask'), interp=interp)
         if resampled is not None:
             resampled.extend(done)
     else:
@@ -256,9 +256,10 @@ def score_files(pred_path, gt_path, mask_path=None, std_path=None, slice_half_ra
                         norm=norm)
 
 
-def eval_inputs_on_grid(ref, gt, label, gt_affine, regrid, half_range, device, names, wording=str):
+def eval_inputs_on_grid(ref, gt, label, gt_affine, regrid, half_range, device, names, wording=str, interp='linear', found=None):
     """The evaluation inputs of a prediction on the grid ref = (shape, affine, header) of its first input, checked: under `regrid`
-    (--regrid) `gt` and `label` are RawVolumes and what is not on that grid is resampled onto it (volume_regrid.eval_onto_grid);
+    (--regrid) `gt` and `label` are RawVolumes and what is not on that grid is resampled onto it (volume_regrid.eval_onto_grid, which
+    explains `interp` and `found`);
     otherwise they are arrays as volume.read_nifti returns them.  `label` may be None; `gt_affine`: the ground truth's own affine.
     check_shapes' ValueError is raised as ValueError(wording(e)); the affines are compared (warn_affine, with `names` = what to call
     the first input and the ground truth) unless the ground truth was just resampled.  -> ((gt, label), the names of what was resampled)."""
@@ -266,7 +267,7 @@ def eval_inputs_on_grid(ref, gt, label, gt_affine, regrid, half_range, device, n
     resampled = []
     if regrid:
         from . import volume_regrid as VR
-        gt, label, resampled = VR.eval_onto_grid(shape, VR.world_affine_of(affine, header), gt, label, device)
+        gt, label, resampled = VR.eval_onto_grid(shape, VR.world_affine_of(affine, header), gt, label, device, interp=interp, found=found)
     try:
         check_shapes(shape, gt.shape, None if label is None else label.shape, half_range)
     except ValueError as e:
@@ -295,6 +296,9 @@ def build_parser():
     p.add_argument('--regrid', action='store_true',
                    help="resample a --gt (trilinearly) or a --mask (nearest neighbour) that is not on the prediction's voxel grid onto "
                         'it through the affines before scoring (mudiff_hip.volume_regrid; resampling, not registration)')
+    p.add_argument('--regrid_interp', type=str, default='linear', choices=['linear', 'cubic'],
+                   help="how --regrid resamples the --gt: 'linear' = trilinearly; 'cubic' = with a cubic B-spline, which does not soften "
+                        'it (mudiff_hip.volume_regrid; the --mask stays nearest neighbour)')
     p.add_argument('--json', type=str, default=None, help='write the full report (per-plane curves included) to this file')
     return p
 
@@ -304,12 +308,12 @@ def main(argv=None):
     try:
         resampled = []
         rep = score_files(args.pred, args.gt, args.mask, args.std, args.slice_half_range, norm=args.norm, regrid=args.regrid,
-                          resampled=resampled)
+                          resampled=resampled, interp=args.regrid_interp)
     except ValueError as e:
         print(f'error: {e}', file=sys.stderr)
         return 2
     if resampled:
-        print(f"[metrics] regrid={','.join(resampled)}")
+        print(f"[metrics] regrid={','.join(resampled)}" + ('' if args.regrid_interp == 'linear' else f' | interp={args.regrid_interp}'))
     for ln in format_lines(rep):
         print(ln)
     if args.json:

@@ -20,12 +20,13 @@ from .volume import regrid_suffix
 from .volume_intake import slab_range
 
 
-class IntakeOptions(collections.namedtuple('IntakeOptions', 'norm regrid coreg bias half_range foreground brain denoise',
-                                           defaults=('percentile', False, None, None, 80, None, None, None))):
+class IntakeOptions(collections.namedtuple('IntakeOptions', 'norm regrid coreg bias half_range foreground brain interp denoise',
+                                           defaults=('percentile', False, None, None, 80, None, None, 'linear', None))):
     """norm: --norm; regrid: --regrid; coreg / bias / denoise / foreground: the keyword arguments of volume_coreg.coregister /
     volume_bias.correct / volume_denoise.denoise / volume_foreground.foreground, or None without --coregister / --bias_correct / --denoise /
     --foreground; half_range: --slice_half_range (the slab is part of the reference geometry); brain: the keyword arguments of volume_brain.brain_mask plus
-    `source` (--brain_from or None) and `mask_out`, or None without --brain_extract.  `foreground` and `brain` sit before `denoise`, not
+    `source` (--brain_from or None) and `mask_out`, or None without --brain_extract; interp: --regrid_interp (how --regrid / --coregister
+    resample an image: 'linear' or 'cubic').  `foreground`, `brain` and `interp` sit before `denoise`, not
     at the end: tests/test_volume_denoise_host.py pins `denoise` as the last field, and every positional use stops at half_range."""
     __slots__ = ()
 
@@ -53,22 +54,23 @@ class IntakeOptions(collections.namedtuple('IntakeOptions', 'norm regrid coreg b
                          dilate_mm=float(get('brain_dilate_mm', VBR.DEFAULTS['dilate_mm'])), keep_holes=bool(get('brain_keep_holes', False)),
                          source=None if source is None else str(source), mask_out=bool(get('brain_mask_out', False)))
         return cls(get('norm', 'percentile'), bool(get('regrid', False)), coreg, bias, int(get('slice_half_range', 80)), foreground, brain,
-                   denoise)
+                   str(get('regrid_interp', 'linear')), denoise)
 
 
 class IntakeReport:
     """What the preparation did to one subject, by modality name: `regridded` [name] (a caller appends the evaluation inputs --regrid
     resampled: `report.regridded += names`), `coreg` [(name, report)], `bias` [(name, report, field or None)], `denoise` [(name,
     report)], `foreground` [(name, report, the masked volume or None)], `brain` [(the source's name, report, the uint8 [X,Y,Z] host mask or
-    None)]: one entry per subject."""
+    None)]: one entry per subject; `interp` (--regrid_interp) and `nonfinite`, the non-finite voxels a cubic resampling read as 0."""
 
-    def __init__(self, regridded=()):
+    def __init__(self, regridded=(), interp='linear', nonfinite=0):
         self.regridded, self.coreg, self.bias, self.denoise, self.foreground, self.brain = list(regridded), [], [], [], [], []
+        self.interp, self.nonfinite = interp, int(nonfinite)
 
     def suffix(self):
-        """What a [done] line gains: ` | regrid=... | coreg=... | bias=... | denoise=... | foreground=... | brain=...`, each part only when
+        """What a [done] line gains: ` | regrid=... | interp=cubic | coreg=... | bias=... | denoise=... | foreground=... | brain=...`, each part only when
         its list is not empty."""
-        return (regrid_suffix(self.regridded) + VC.coreg_suffix(self.coreg) + VB.bias_suffix(self.bias) + VD.denoise_suffix(self.denoise) +
+        return (regrid_suffix(self.regridded) + VR.interp_suffix(self.interp, self.nonfinite) + VC.coreg_suffix(self.coreg) + VB.bias_suffix(self.bias) + VD.denoise_suffix(self.denoise) +
                 VF.foreground_suffix(self.foreground) + VBR.brain_suffix(self.brain))
 
     def write(self, output_dir, target, affine, header):
@@ -97,8 +99,8 @@ def prepare_inputs(named_raws, options, device, labels=None):
     Under --foreground every input, the first included, then has the voxels outside its foreground mask set to exactly 0, on its own grid
     (volume_foreground.foreground: same shape, affine and header again), and everything below sees the masked list.
     The first input defines the grid and is never registered or resampled.  Every later one is aligned to it under --coregister
-    (volume_coreg.coregister -> world), then resampled under --regrid or --coregister (volume_regrid.regrid_to: untouched when it is on the
-    grid already); otherwise it must have the first one's shape.  Under --brain_extract one brain mask is then estimated from one input
+    (volume_coreg.coregister -> world; its search stays trilinear), then resampled under --regrid or --coregister (volume_regrid.regrid_to
+    with --regrid_interp: untouched when it is on the grid already); otherwise it must have the first one's shape.  Under --brain_extract one brain mask is then estimated from one input
     on that grid (volume_brain.source_of picks it; volume_brain.brain_mask) and every input has the voxels outside it set to exactly 0; a
     mask that could not be estimated leaves the inputs as they are (the report's `kept` is 0).  Under --bias_correct every input, the first
     included, is then divided by its bias field (volume_bias.correct).  ValueError for an input that is not 3D or a --brain_from that is
@@ -110,7 +112,7 @@ def prepare_inputs(named_raws, options, device, labels=None):
     brain = None if options.brain is None else dict(options.brain)
     if brain is not None:
         source, mask_out = VBR.source_of([name for name, _ in named_raws], brain.pop('source', None)), brain.pop('mask_out', False)
-    report = IntakeReport()
+    report = IntakeReport(interp=options.interp)
     if options.denoise is not None:
         cleaned = []
         for name, raw in named_raws:
@@ -144,7 +146,10 @@ def prepare_inputs(named_raws, options, device, labels=None):
             if options.coreg is not None:
                 world, found = VC.coregister(first, raw, device, **options.coreg)
                 report.coreg.append((name, found))
-            vol = VR.regrid_to(raw, ref[0], ref_world, device, header=ref[2], world=world)
+            seen = {}
+            how = {} if options.interp == 'linear' else dict(mode=options.interp, found=seen)      # (the default call as it ever was)
+            vol = VR.regrid_to(raw, ref[0], ref_world, device, header=ref[2], world=world, **how)
+            report.nonfinite += seen.get('nonfinite', 0)
             if vol is not raw:
                 report.regridded.append(name)
         elif raw.shape != ref[0]:

@@ -6,7 +6,8 @@ is resampled onto the first input's grid through the two affines before anything
 
     stored voxels --upload--> mud_volume_regrid(inv(source affine) @ reference affine) --> fp32 [Z,Y,X] on the reference grid
 
-trilinear for images, nearest neighbour for label volumes, zero outside the source's field of view.  The result is a volume like any
+trilinear for images (or, with --regrid_interp cubic, a cubic B-spline: mud_volume_bspline_coeffs + mud_volume_regrid_cubic, DESIGN.md
+section 5.19), nearest neighbour for label volumes, zero outside the source's field of view.  The result is a volume like any
 other (fp32, NIFTI_F4, the reference geometry): the host path downloads it and normalises it with numpy, the device path hands it to
 the census / slab kernels where it is.  This is resampling between grids whose world coordinates already agree, not registration.
 
@@ -22,7 +23,17 @@ import torch
 from . import NIFTI_F4, MudiffHipError, load, ptr, require_gpu
 from .volume_intake import DEVICE_DTYPES, RawVolume, upload
 
-MODES = {'linear': 0, 'nearest': 1}
+MODES = {'linear': 0, 'nearest': 1}                     # the modes of mud_volume_regrid
+MODES_HIGH = ('cubic',)                                  # the modes that run mud_volume_bspline_coeffs + mud_volume_regrid_cubic
+INTERPS = ('linear',) + MODES_HIGH                       # --regrid_interp: how an image is resampled (a label volume: always nearest)
+
+
+def interp_suffix(interp, nonfinite=0):
+    """What a [done] line gains under a non-default --regrid_interp (nothing by default: the lines as they were); `nonfinite`: the
+    non-finite voxels the spline prefilter read as 0, named when there were any."""
+    if interp == 'linear':
+        return ''
+    return f' | interp={interp}' + (f' nonfinite={int(nonfinite)}' if nonfinite else '')
 
 
 def world_affine_of(affine, header):
@@ -62,12 +73,14 @@ def same_grid(shape_a, aff_a, shape_b, aff_b):
     return a.shape == b.shape and bool(np.array_equal(a.astype(np.float32), b.astype(np.float32)))
 
 
-def regrid(dev_raw, code, shape, slope, inter, M, out_shape, mode='linear'):
+def regrid(dev_raw, code, shape, slope, inter, M, out_shape, mode='linear', found=None):
     """mud_volume_regrid: the flat device array of a volume's stored voxels (datatype `code`, shape [SX,SY,SZ]) -> device fp32
-    [Z,Y,X] on the grid of `out_shape` = (X,Y,Z).  M: grid_matrix(...) (4 x 4 or 3 x 4)."""
+    [Z,Y,X] on the grid of `out_shape` = (X,Y,Z).  M: grid_matrix(...) (4 x 4 or 3 x 4).  mode 'cubic': the value range
+    (mud_volume_fg_range), the spline coefficients (mud_volume_bspline_coeffs: fp64, freed on return) and mud_volume_regrid_cubic; a dict
+    `found` then receives `nonfinite`, the non-finite voxels that were read as 0."""
     require_gpu(dev_raw)
-    if mode not in MODES:
-        raise ValueError(f'mode must be one of {tuple(MODES)}, got {mode!r}')
+    if mode not in MODES and mode not in MODES_HIGH:
+        raise ValueError(f'mode must be one of {tuple(MODES) + MODES_HIGH}, got {mode!r}')
     if int(code) not in DEVICE_DTYPES:
         raise MudiffHipError(f'regrid: unsupported NIfTI datatype code {code}')
     SX, SY, SZ = (int(v) for v in shape)
@@ -80,6 +93,22 @@ def regrid(dev_raw, code, shape, slope, inter, M, out_shape, mode='linear'):
         raise ValueError(f'regrid: need a 3 x 4 or 4 x 4 matrix, got {np.shape(M)}')
     out = torch.empty(max(Z, 0), max(Y, 0), max(X, 0), device=dev_raw.device, dtype=torch.float32)
     from . import ops
+    if mode in MODES_HIGH:
+        from .volume_foreground import unkey
+        rng = ops.volume_fg_range(dev_raw, int(code), (SX, SY, SZ), float(slope), float(inter)).cpu().numpy().view(np.uint32)
+        lo, hi = (unkey(~int(rng[0])), unkey(rng[1])) if int(rng[2]) else (0.0, 0.0)      # the finite values that are != 0 ...
+        lo, hi = min(lo, 0.0), max(hi, 0.0)                                               # ... widened to contain 0
+        coeffs = torch.empty(SZ, SY, SX, device=dev_raw.device, dtype=torch.float64)
+        bad = torch.empty(1, device=dev_raw.device, dtype=torch.int32)
+        ops._launch('volume_bspline_coeffs', dev_raw.device, load().mud_volume_bspline_coeffs, ptr(dev_raw), int(code), SX, SY, SZ, float(slope),
+                    float(inter), ptr(coeffs), ptr(bad), ops.STREAM, nbytes=float(dev_raw.numel() * (3 * dev_raw.element_size() + 80)))
+        ops._launch('volume_regrid_cubic', dev_raw.device, load().mud_volume_regrid_cubic, ptr(coeffs), SX, SY, SZ, ptr(dev_raw), int(code),
+                    float(slope), float(inter), (C.c_double * 12)(*m.reshape(-1).tolist()), lo, hi, X, Y, Z, ptr(out), ops.STREAM,
+                    nbytes=float(8 * coeffs.numel() + dev_raw.numel() * dev_raw.element_size() + 4 * out.numel()))
+        if found is not None:
+            found['nonfinite'] = int(bad.cpu().numpy().view(np.uint32)[0])
+        del coeffs                                            # (stream-ordered: the allocator reuses it after the launch above)
+        return out
     ops._launch('volume_regrid', dev_raw.device, load().mud_volume_regrid, ptr(dev_raw), int(code), SX, SY, SZ, float(slope), float(inter),
                 (C.c_double * 12)(*m.reshape(-1).tolist()), MODES[mode], X, Y, Z, ptr(out), ops.STREAM,
                 nbytes=float(dev_raw.numel() * dev_raw.element_size() + 4 * out.numel()))
@@ -110,12 +139,13 @@ class RegriddedVolume(RawVolume):
         return self.data.reshape(self.shape, order='F')
 
 
-def regrid_to(raw, ref_shape, ref_affine, device, mode='linear', header=None, world=None):
+def regrid_to(raw, ref_shape, ref_affine, device, mode='linear', header=None, world=None, found=None):
     """A RawVolume -> the same volume on the grid (ref_shape, ref_affine): a RegriddedVolume (fp32, NIFTI_F4, slope 1, inter 0, that
     geometry; `header`: the reference's) ready for volume_intake.condition_from_raw.  A volume already on that grid is returned
     untouched.  The source's place in the world is world_affine_of(raw.affine, raw.header).  `world` (--coregister,
     mudiff_hip.volume_coreg): a 4 x 4 matrix W that takes a world point of the reference to the source's world, so that the sampling
-    matrix is inv(source affine) @ W @ reference affine; with a W that is not the identity the volume is resampled even on its own grid."""
+    matrix is inv(source affine) @ W @ reference affine; with a W that is not the identity the volume is resampled even on its own grid.
+    `mode`: 'linear', 'cubic' (an image) or 'nearest' (a label volume); `found`: see regrid."""
     if len(raw.shape) != 3 or len(ref_shape) != 3:
         raise ValueError(f'regrid: expected 3D volumes, got shapes {tuple(raw.shape)} and {tuple(ref_shape)}')
     src_affine = world_affine_of(raw.affine, raw.header)
@@ -123,19 +153,25 @@ def regrid_to(raw, ref_shape, ref_affine, device, mode='linear', header=None, wo
     if not moved and same_grid(raw.shape, src_affine, ref_shape, ref_affine):
         return raw
     M = grid_matrix(src_affine, _affine44(world, 'world transform') @ _affine44(ref_affine, 'reference affine') if moved else ref_affine)
-    dev = regrid(upload(raw, device), raw.code, raw.shape, *raw.scaling, M, ref_shape, mode)
+    dev = regrid(upload(raw, device), raw.code, raw.shape, *raw.scaling, M, ref_shape, mode, found)
     return RegriddedVolume(dev, ref_shape, np.asarray(ref_affine, np.float64), header)
 
 
-def eval_onto_grid(ref_shape, ref_affine, gt_raw, mask_raw, device, names=('gt_volume', 'eval_mask')):
-    """The evaluation inputs on the reference grid: the ground truth trilinearly, the label volume by nearest neighbour.
+def eval_onto_grid(ref_shape, ref_affine, gt_raw, mask_raw, device, names=('gt_volume', 'eval_mask'), interp='linear', found=None):
+    """The evaluation inputs on the reference grid: the ground truth by `interp` (--regrid_interp: trilinearly by default), the label
+    volume by nearest neighbour, always.  A dict `found` has the non-finite voxels a cubic resampling read as 0 added to its `nonfinite`.
     -> (gt [X,Y,Z] float64 as volume.read_nifti returns it, label or None, the names of what was resampled)."""
     out, done = [], []
-    for raw, mode, name in ((gt_raw, 'linear', names[0]), (mask_raw, 'nearest', names[1])):
+    for raw, mode, name in ((gt_raw, interp, names[0]), (mask_raw, 'nearest', names[1])):
         if raw is None:
             out.append(None)
             continue
-        r = regrid_to(raw, ref_shape, ref_affine, device, mode)
+        if mode not in INTERPS and mode != 'nearest':
+            raise ValueError(f'interp must be one of {INTERPS}, got {mode!r}')
+        seen = {}
+        r = regrid_to(raw, ref_shape, ref_affine, device, mode, found=seen)
+        if found is not None:
+            found['nonfinite'] = found.get('nonfinite', 0) + seen.get('nonfinite', 0)
         if r is not raw:
             done.append(name)
             out.append(r.values_float32().astype(np.float64))
