@@ -475,7 +475,17 @@ int mud_ensemble_stats(const float* samples, int n, int N, int64_t hw, float sca
  *     axis longer than 1024 voxels (a line is staged whole).
  *   _edt_select: out[i] = (above ? d2[i] > r2 : d2[i] <= r2) && (within == NULL || within[i] != 0), over n voxels; count (device uint32,
  *     cleared first): the voxels switched on.  r2: finite and >= 0; above: 0 or 1; out is not within.
- *   X*Y*Z < 2^31.  No floating-point atomics: every result is the same bits on every run. */
+ *   X*Y*Z < 2^31.  No floating-point atomics: every result is the same bits on every run.
+ *
+ * mud_volume_reorient (--reorient; replaces nibabel's as_closest_canonical / apply_orientation, which the
+ *   reference does not call: it reads its files unreoriented): a permutation and flips of the storage axes of a volume of
+ *   elem_bytes-wide elements (1, 2, 4 or 8: every stored datatype, fp32 and fp64; the values are moved, never interpreted), x fastest on
+ *   both sides.  With S = (SX, SY, SZ), p = (p0, p1, p2) a permutation of (0, 1, 2) and flip_o = bit o of flip_mask, the destination has
+ *   the extents (S[p0], S[p1], S[p2]) and dst[i0, i1, i2] = src[j], j[p_o] = flip_o ? S[p_o] - 1 - i_o : i_o.  p0 == 0 copies whole
+ *   x-rows (backwards under flip_0); otherwise tiles of the plane (source x, source axis p0) go through LDS, read in runs along source x
+ *   and written in runs along destination x.  MUD_ERR_ARG before any launch for an elem_bytes outside {1, 2, 4, 8}, a p that is not a
+ *   permutation, a flip_mask outside [0, 7], a negative extent, SX*SY*SZ >= 2^31, a null or misaligned pointer and a source that overlaps
+ *   the destination (src == dst included: not an in-place operation).  A volume without voxels launches nothing and succeeds. */
 #define MUD_NIFTI_U1 2
 #define MUD_NIFTI_I2 4
 #define MUD_NIFTI_I4 8
@@ -535,6 +545,8 @@ int mud_volume_fg_apply(const void* vol, int datatype, int X, int Y, int Z, floa
 int mud_volume_edt(const uint8_t* mask, int X, int Y, int Z, int value, double sx, double sy, double sz, double* d2, void* stream);
 int mud_volume_edt_select(const double* d2, int64_t n, double r2, int above, const uint8_t* within, uint8_t* out, uint32_t* count,
                           void* stream);
+int mud_volume_reorient(const void* src, int elem_bytes, int SX, int SY, int SZ, int p0, int p1, int p2, int flip_mask, void* dst,
+                        void* stream);
 
 #ifdef __cplusplus
 }

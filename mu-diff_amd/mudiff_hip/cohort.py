@@ -29,6 +29,9 @@ With --denoise every input is first replaced by its non
 of the above; denoise_<t>.json goes next to each subject's prediction and the [done] line names the inputs (` | denoise=...`).
 With --foreground every input then has the voxels outside its foreground mask set to 0, on the main thread right
 after the denoising; foreground_<t>.json goes next to each subject's prediction and the [done] line names the inputs (` | foreground=...`).
+With --reorient every input, ground truth and mask included, is first brought to the training orientation, on the
+main thread before all of the above; reorient_<t>.json goes next to each subject's prediction and the [done] line names what moved
+(` | reorient=T1:RAS>LPS,...`).  --reorient_back wraps the deferred writer, so the prediction returns to the first input's storage order.
 """
 from __future__ import annotations
 
@@ -129,8 +132,8 @@ def format_lines(agg):
 def _read_subject(subject, needed, score, norm='percentile', regrid=False):
     """(prefetch thread) The subject's three condition volumes as stored (volume_intake.read_nifti_raw) and, with `score`, the
     evaluation inputs of volume.load_eval_inputs.  With norm='zscore' every volume's moments are computed here too, next to the read
-    (RawVolume.moments; their seconds in RawVolume.moments_s).  With `regrid` (--regrid) the evaluation inputs stay as stored, geometry
-    included: the main thread puts them on the first input's grid.  -> (raws, (gt, label or None, the gt's affine) or None, seconds)."""
+    (RawVolume.moments; their seconds in RawVolume.moments_s).  With `regrid` (--regrid, --reorient) the evaluation inputs stay as stored,
+    geometry included: the main thread reorients them and puts them on the first input's grid.  -> (raws, (gt, label or None, the gt's affine) or None, seconds)."""
     from . import volume as V
     from . import volume_intake as VI
     t0 = time.perf_counter()
@@ -172,6 +175,7 @@ def run(args, subjects, predict=None):
     from . import volume as V
     from . import volume_intake as VI
     from . import volume_metrics as VM
+    from . import volume_reorient as VO
     from .driver import effective_prec_plan
     from .volume_prepare import IntakeOptions, prepare_inputs
     target = args.target_modality
@@ -209,7 +213,7 @@ def run(args, subjects, predict=None):
                 s = next(todo, None)
                 if s is None:
                     return
-                reads.append((s, pool.submit(_read_subject, s, needed, args.score, norm, options.regrid)))
+                reads.append((s, pool.submit(_read_subject, s, needed, args.score, norm, options.regrid or options.reorient is not None)))
 
         prefetch()
         calibrated = False
@@ -228,8 +232,12 @@ def run(args, subjects, predict=None):
                     sargs.output_dir = os.path.join(args.output_dir, subject.id)
                     gpu = device or torch.device(f'cuda:{args.gpu_chose}')
                     evaluation, resampled, found = None, [], {}
+                    grid = (raws[0].shape, raws[0].affine, raws[0].header)
+                    if ev is not None and options.reorient is not None:      # (the grid: the first input's once reoriented)
+                        grid = VO.reference_of(raws[0], **options.reorient)[0]
+                        ev = VO.eval_inputs(ev[0], ev[1], gpu, options.reorient['target'], as_arrays=not options.regrid)
                     if ev is not None:                             # the evaluation inputs onto the first input's grid, checked
-                        evaluation, resampled = VM.eval_inputs_on_grid((raws[0].shape, raws[0].affine, raws[0].header), *ev, options.regrid,
+                        evaluation, resampled = VM.eval_inputs_on_grid(grid, *ev, options.regrid,
                                                                        options.half_range, gpu, names=(subject.inputs[needed[0]], subject.gt),
                                                                        wording=lambda e: f'ground truth / mask: {e}',
                                                                        interp=options.interp, found=found)
@@ -249,6 +257,9 @@ def run(args, subjects, predict=None):
                     def write(path, vol, affine, header):
                         drain(QUEUE_DEPTH - 1)                     # subject i-1 is compressed and written while subject i runs
                         pending.append(pool.submit(_timed_write, path, vol, affine, header))
+
+                    if options.reorient is not None and getattr(args, 'reorient_back', False):
+                        write = VO.write_back(write, raws[0], **options.reorient)
 
                     t0 = time.perf_counter()
                     stage = {}

@@ -1206,3 +1206,24 @@ def volume_edt_select(d2, r2, above, within=None):
     _launch('volume_edt_select', d2.device, load().mud_volume_edt_select, ptr(d2), int(d2.numel()), float(r2), int(bool(above)), ptr(within),
             ptr(out), ptr(count), STREAM, nbytes=10.0 * d2.numel())
     return out, count
+
+
+# ---------------------------------------------------------------------------------------------------
+# --reorient (csrc/volume_reorient.hip; the host's share is mudiff_hip.volume_reorient)
+# ---------------------------------------------------------------------------------------------------
+def volume_reorient(dev_flat, elem_bytes, shape, plan):
+    """mud_volume_reorient: the flat device array of a volume's voxels (x fastest, `shape` = (SX, SY, SZ), elements of `elem_bytes`
+    bytes) -> a flat device tensor of the same dtype holding the volume with its storage axes permuted and flipped by `plan`
+    (volume_reorient.ReorientPlan, or anything with `perm` and `flip`): dst[i0, i1, i2] = src[j], j[perm[o]] = S[perm[o]] - 1 - i_o
+    if flip[o] else i_o.  The destination's extents are plan.shape = (S[perm[0]], S[perm[1]], S[perm[2]])."""
+    require_gpu(dev_flat)
+    SX, SY, SZ = (int(v) for v in shape)
+    if dev_flat.dim() != 1 or dev_flat.numel() != SX * SY * SZ or dev_flat.element_size() != int(elem_bytes) or not dev_flat.is_contiguous():
+        raise MudiffHipError(f'volume_reorient: {tuple(dev_flat.shape)} elements of {dev_flat.element_size()} bytes do not hold a flat '
+                             f'{SX} x {SY} x {SZ} volume of {elem_bytes}-byte elements')
+    p0, p1, p2 = (int(v) for v in plan.perm)
+    mask = sum(1 << o for o, f in enumerate(plan.flip) if f)
+    out = torch.empty_like(dev_flat)
+    _launch('volume_reorient', dev_flat.device, load().mud_volume_reorient, ptr(dev_flat), int(elem_bytes), SX, SY, SZ, p0, p1, p2, mask, ptr(out),
+            STREAM, nbytes=2.0 * dev_flat.numel() * dev_flat.element_size())
+    return out

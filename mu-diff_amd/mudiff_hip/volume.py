@@ -12,7 +12,7 @@ Slices are independent, so the only observable difference is the order in which 
 inject the draws per slice (`predict_slices(..., x_inits, zs, noises)`).
 
 Intake: every path reads the three condition files as stored (volume_intake.read_nifti_raw) and hands them to the one preparation
-stage, volume_prepare.prepare_inputs (the first input's grid; --denoise, --foreground, --coregister, --regrid, --bias_correct); host_stacks then normalises
+stage, volume_prepare.prepare_inputs (the first input's grid; --reorient, --denoise, --foreground, --coregister, --regrid, --bias_correct); host_stacks then normalises
 with numpy, --device_intake with volume_intake.condition_from_raw.  What the stage did travels as args.intake_report to the [done] line.
 
 NIfTI I/O: nibabel is used when importable (it is not in this image); otherwise a minimal built-in reader/writer
@@ -352,7 +352,9 @@ def predict_volume(args):
     after the [done] line and metrics_<target>.json goes next to the prediction.  Those inputs are checked first, before any GPU or
     checkpoint work.  --coregister, --bias_correct, --denoise and --foreground add coreg_<target>.json, bias_<target>.json (and, with
     --bias_field_out, the field volumes), denoise_<target>.json and foreground_<target>.json (and, with --foreground_mask_out, the masks)
-    next to the prediction (volume_prepare.IntakeReport.write)."""
+    next to the prediction (volume_prepare.IntakeReport.write).  Under --reorient (mudiff_hip.volume_reorient) everything is written on the
+    reoriented grid, with the affine and header that describe it, and reorient_<target>.json is added; --reorient_back returns the
+    prediction (and its std) to the first input's storage order, after the scoring."""
     from .volume_prepare import IntakeReport
     found = {}
     evaluation, resampled = _load_eval_inputs(args, found)
@@ -381,7 +383,9 @@ def load_eval_inputs(args):
     """--gt_volume / --eval_mask -> None, or (raw GT volume, label volume or None) once the files have been read and their shapes
     checked against the first input volume and the slab (volume_metrics.check_shapes).  A bad evaluation input raises ValueError
     here, so that it cannot cost a sampling run.  With --regrid a ground truth or a label volume on another grid is first resampled
-    onto the first input's (mudiff_hip.volume_regrid: trilinear, or cubic under --regrid_interp cubic / nearest neighbour)."""
+    onto the first input's (mudiff_hip.volume_regrid: trilinear, or cubic under --regrid_interp cubic / nearest neighbour).  With
+    --reorient the grid they are checked against is the first input's once reoriented (its plan's shape, affine and header: no voxel of
+    it is moved for that), and each evaluation input is reoriented by its own affine to the same target first."""
     return _load_eval_inputs(args)[0]
 
 
@@ -394,7 +398,14 @@ def _load_eval_inputs(args, found=None):
     from . import volume_intake as VI
     from .volume_metrics import eval_inputs_on_grid
     _, first = _needed_inputs(args)[0]
-    if args.regrid:
+    device = torch.device(f'cuda:{args.gpu_chose}')
+    if getattr(args, 'reorient', False):
+        from . import volume_reorient as VO
+        target = VO.check_target(getattr(args, 'reorient_to', VO.DEFAULT_TARGET))
+        ref = VO.reference_of(VI.read_nifti_raw(first), target)[0]
+        gt, label, gt_aff = VO.eval_inputs(VI.read_nifti_raw(args.gt_volume), None if args.eval_mask is None else VI.read_nifti_raw(args.eval_mask),
+                                           device, target, as_arrays=not args.regrid)
+    elif args.regrid:
         inp = VI.read_nifti_raw(first)
         ref = (inp.shape, inp.affine, inp.header)
         gt = VI.read_nifti_raw(args.gt_volume)
@@ -405,7 +416,7 @@ def _load_eval_inputs(args, found=None):
         ref = (inp.shape, inp_aff, inp_hdr)
         gt, gt_aff, _ = read_nifti(args.gt_volume)
         label = None if args.eval_mask is None else read_nifti(args.eval_mask)[0]
-    return eval_inputs_on_grid(ref, gt, label, gt_aff, args.regrid, args.slice_half_range, torch.device(f'cuda:{args.gpu_chose}'),
+    return eval_inputs_on_grid(ref, gt, label, gt_aff, args.regrid, args.slice_half_range, device,
                                names=(first, args.gt_volume),
                                wording=lambda e: f'--gt_volume / --eval_mask: {e} (the prediction has the shape of {first})',
                                interp=getattr(args, 'regrid_interp', 'linear'), found=found)
@@ -442,8 +453,13 @@ def _predict_volume(args, plan, evaluation=None):
     from .volume_prepare import IntakeOptions, prepare_inputs
     options = IntakeOptions.from_args(args)
     needed = _needed_inputs(args)
-    prepared, ref, report = prepare_inputs([(m, VI.read_nifti_raw(path)) for m, path in needed], options, device,
+    raws = [VI.read_nifti_raw(path) for _, path in needed]
+    prepared, ref, report = prepare_inputs([(m, raw) for (m, _), raw in zip(needed, raws)], options, device,
                                            labels=dict(needed) if args.device_intake else None)      # (the device path names the file)
+    write = None
+    if options.reorient is not None and getattr(args, 'reorient_back', False):
+        from . import volume_reorient as VO
+        write = VO.write_back(write_nifti, raws[0], **options.reorient)
     report.regridded += _intake_report(args).regridded       # the inputs first, then the evaluation inputs predict_volume resampled
     report.nonfinite += _intake_report(args).nonfinite
     args.intake_report = report
@@ -452,7 +468,7 @@ def _predict_volume(args, plan, evaluation=None):
                   for vol, (_, path) in zip(prepared, needed)]
     else:
         stacks = host_stacks(prepared, options)
-    return predict_from_conditions(args, plan, evaluation, gen1, gen2, device, stacks, ref, on_device=args.device_intake)
+    return predict_from_conditions(args, plan, evaluation, gen1, gen2, device, stacks, ref, on_device=args.device_intake, write=write)
 
 
 def host_stacks(prepared, options):
@@ -729,6 +745,21 @@ def make_parser(prog='MU-Diff volume prediction (MI355X)'):
     p.add_argument('--brain_keep_holes', action='store_true', help='with --brain_extract: do not fill the holes of the mask')
     p.add_argument('--brain_mask_out', action='store_true',
                    help='with --brain_extract: also write brain_<t>_mask.nii.gz, the uint8 mask on the grid of the first input')
+    p.add_argument('--reorient', action='store_true',
+                   help='bring every input (and --gt_volume / --eval_mask), each by its own affine, to the storage orientation the '
+                        'checkpoints were trained on before anything else sees it: a permutation and flips of the storage axes on the GPU '
+                        '(mudiff_hip.volume_reorient), exact, datatype and scaling kept, the affine changed to match.  The slab is then '
+                        'cut along the third axis of that orientation and everything is written on the reoriented grid; '
+                        'reorient_<t>.json next to the prediction holds what was done.  A permutation cannot make tilted slices axial: an '
+                        'input whose axes are tilted by more than 10 degrees (an untuned default, not a measured bar) gets a warning, and '
+                        'de-obliquing by resampling is not done')
+    p.add_argument('--reorient_to', type=str, default='LPS', metavar='CODE',
+                   help="the target orientation of --reorient, one letter of each of R/L, A/P, S/I: the direction every storage axis runs "
+                        "towards.  'LPS' is how BraTS stores its volumes, which the reference reads without reorienting; a checkpoint "
+                        'trained on data stored otherwise needs its own code')
+    p.add_argument('--reorient_back', action='store_true',
+                   help="with --reorient: write predicted_<t>.nii.gz (and predicted_<t>_std.nii.gz) in the first input's own storage order, "
+                        'with its original affine and header (scored first, on the reoriented grid)')
     from .driver import add_calibration_flags
     add_calibration_flags(p)                # (also --prec_plan)
     return p
@@ -766,6 +797,13 @@ def finish_args(p, args):
         check_brain(args.brain_bins, args.brain_erode_mm, args.brain_dilate_mm, args.brain_keep_holes)
     except ValueError as e:
         p.error(str(e))
+    from .volume_reorient import check_target
+    try:
+        args.reorient_to = check_target(args.reorient_to)
+    except ValueError as e:
+        p.error(str(e))
+    if args.reorient_back and not args.reorient:
+        p.error('--reorient_back needs --reorient')
     return args
 
 
@@ -779,7 +817,8 @@ def build_argparser(argv=None):
     --coregister (rigid alignment of the inputs to the first one), --bias_correct (removal of the coil
     shading of every input), --denoise (non-local-means denoising of every input) and
     --foreground (a foreground mask of every input: everything outside becomes 0) and --brain_extract (one
-    morphological brain mask per subject, applied to every input)."""
+    morphological brain mask per subject, applied to every input) and --reorient / --reorient_to / --reorient_back
+    (the inputs brought to the training orientation)."""
     p = make_parser()
     return finish_args(p, p.parse_args(argv))
 

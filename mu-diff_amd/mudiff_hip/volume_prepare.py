@@ -2,8 +2,8 @@
 on the host, with --device_intake, and mudiff_hip.cohort - reads a subject's files, hands them to prepare_inputs and normalises what
 comes back, on the host (volume.host_stacks) or on the device (volume_intake.condition_from_raw).
 
-    IntakeOptions.from_args(args)                         what --norm / --regrid / --coregister / --bias_correct / --denoise / --foreground / --brain_extract ask for, built once
-    prepare_inputs(named_raws, options, device)           denoise; foreground; first input = the grid; coregister; regrid, or check the shape; brain mask; bias-correct
+    IntakeOptions.from_args(args)                         what --norm / --regrid / --coregister / --bias_correct / --denoise / --foreground / --brain_extract / --reorient ask for, built once
+    prepare_inputs(named_raws, options, device)           reorient; denoise; foreground; first input = the grid; coregister; regrid, or check the shape; brain mask; bias-correct
     IntakeReport                                          what that did, by modality name: the [done] line's tail and the report files
 """
 from __future__ import annotations
@@ -16,17 +16,19 @@ from . import volume_coreg as VC
 from . import volume_denoise as VD
 from . import volume_foreground as VF
 from . import volume_regrid as VR
+from . import volume_reorient as VO
 from .volume import regrid_suffix
 from .volume_intake import slab_range
 
 
-class IntakeOptions(collections.namedtuple('IntakeOptions', 'norm regrid coreg bias half_range foreground brain interp denoise',
-                                           defaults=('percentile', False, None, None, 80, None, None, 'linear', None))):
+class IntakeOptions(collections.namedtuple('IntakeOptions', 'norm regrid coreg bias half_range foreground brain interp reorient denoise',
+                                           defaults=('percentile', False, None, None, 80, None, None, 'linear', None, None))):
     """norm: --norm; regrid: --regrid; coreg / bias / denoise / foreground: the keyword arguments of volume_coreg.coregister /
     volume_bias.correct / volume_denoise.denoise / volume_foreground.foreground, or None without --coregister / --bias_correct / --denoise /
     --foreground; half_range: --slice_half_range (the slab is part of the reference geometry); brain: the keyword arguments of volume_brain.brain_mask plus
     `source` (--brain_from or None) and `mask_out`, or None without --brain_extract; interp: --regrid_interp (how --regrid / --coregister
-    resample an image: 'linear' or 'cubic').  `foreground`, `brain` and `interp` sit before `denoise`, not
+    resample an image: 'linear' or 'cubic'); reorient: dict(target=the orientation code of --reorient_to), or None without --reorient.
+    `foreground`, `brain`, `interp` and `reorient` sit before `denoise`, not
     at the end: tests/test_volume_denoise_host.py pins `denoise` as the last field, and every positional use stops at half_range."""
     __slots__ = ()
 
@@ -34,7 +36,7 @@ class IntakeOptions(collections.namedtuple('IntakeOptions', 'norm regrid coreg b
     def from_args(cls, args):
         """The only place that knows the flags' defaults (a namespace that did not come from volume.make_parser may lack any of them)."""
         get = lambda name, default: getattr(args, name, default)      # noqa: E731
-        coreg = bias = denoise = foreground = brain = None
+        coreg = bias = denoise = foreground = brain = reorient = None
         if get('coregister', False):
             coreg = dict(strides=tuple(int(s) for s in get('coregister_strides', None) or (4, 2, 1)),
                          max_mm=float(get('coregister_max_mm', 20.0)), max_deg=float(get('coregister_max_deg', 15.0)))
@@ -53,30 +55,34 @@ class IntakeOptions(collections.namedtuple('IntakeOptions', 'norm regrid coreg b
             brain = dict(bins=int(get('brain_bins', VBR.DEFAULTS['bins'])), erode_mm=float(get('brain_erode_mm', VBR.DEFAULTS['erode_mm'])),
                          dilate_mm=float(get('brain_dilate_mm', VBR.DEFAULTS['dilate_mm'])), keep_holes=bool(get('brain_keep_holes', False)),
                          source=None if source is None else str(source), mask_out=bool(get('brain_mask_out', False)))
+        if get('reorient', False):
+            reorient = dict(target=VO.check_target(get('reorient_to', VO.DEFAULT_TARGET)))
         return cls(get('norm', 'percentile'), bool(get('regrid', False)), coreg, bias, int(get('slice_half_range', 80)), foreground, brain,
-                   str(get('regrid_interp', 'linear')), denoise)
+                   str(get('regrid_interp', 'linear')), reorient, denoise)
 
 
 class IntakeReport:
     """What the preparation did to one subject, by modality name: `regridded` [name] (a caller appends the evaluation inputs --regrid
     resampled: `report.regridded += names`), `coreg` [(name, report)], `bias` [(name, report, field or None)], `denoise` [(name,
     report)], `foreground` [(name, report, the masked volume or None)], `brain` [(the source's name, report, the uint8 [X,Y,Z] host mask or
-    None)]: one entry per subject; `interp` (--regrid_interp) and `nonfinite`, the non-finite voxels a cubic resampling read as 0."""
+    None)]: one entry per subject; `reorient` [(name, entry)] (volume_reorient.ReorientPlan.entry); `interp` (--regrid_interp) and
+    `nonfinite`, the non-finite voxels a cubic resampling read as 0."""
 
     def __init__(self, regridded=(), interp='linear', nonfinite=0):
         self.regridded, self.coreg, self.bias, self.denoise, self.foreground, self.brain = list(regridded), [], [], [], [], []
         self.interp, self.nonfinite = interp, int(nonfinite)
+        self.reorient = []
 
     def suffix(self):
-        """What a [done] line gains: ` | regrid=... | interp=cubic | coreg=... | bias=... | denoise=... | foreground=... | brain=...`, each part only when
+        """What a [done] line gains: ` | regrid=... | interp=cubic | coreg=... | bias=... | denoise=... | foreground=... | brain=... | reorient=...`, each part only when
         its list is not empty."""
         return (regrid_suffix(self.regridded) + VR.interp_suffix(self.interp, self.nonfinite) + VC.coreg_suffix(self.coreg) + VB.bias_suffix(self.bias) + VD.denoise_suffix(self.denoise) +
-                VF.foreground_suffix(self.foreground) + VBR.brain_suffix(self.brain))
+                VF.foreground_suffix(self.foreground) + VBR.brain_suffix(self.brain) + VO.reorient_suffix(self.reorient))
 
     def write(self, output_dir, target, affine, header):
         """coreg_<t>.json, bias_<t>.json (and the fields --bias_field_out asked for) , denoise_<t>.json and foreground_<t>.json (and the masks
         --foreground_mask_out asked for) and brain_<t>.json (and the mask --brain_mask_out asked for, on the grid of `affine` / `header`)
-        next to the prediction; nothing when empty."""
+        and reorient_<t>.json next to the prediction; nothing when empty."""
         if self.coreg:
             VC.write_reports(self.coreg, output_dir, target)
         if self.bias:
@@ -87,6 +93,8 @@ class IntakeReport:
             VF.write_reports(self.foreground, output_dir, target, affine, header)
         if self.brain:
             VBR.write_reports(self.brain, output_dir, target, affine, header)
+        if self.reorient:
+            VO.write_reports(self.reorient, output_dir, target)
 
 
 def prepare_inputs(named_raws, options, device, labels=None):
@@ -94,7 +102,11 @@ def prepare_inputs(named_raws, options, device, labels=None):
     caller has read the files); labels: {name: what an error message calls that input} (the name itself by default; the device paths
     name the file).  -> (volumes on the grid, ref = (shape, affine, header, s0, s1) of the first input, IntakeReport).
 
-    Under --denoise every input, the first included, is first replaced by its non-local-means estimate on its own grid
+    Under --reorient every input, the first included, is first brought to the target orientation on its own grid by its own affine
+    (volume_reorient.reorient: a permutation and flips of the storage axes, the affine and header changed to match; an input stored that
+    way already is left as it is), and everything below sees the reoriented list: the first input's reoriented geometry is `ref`, so that
+    the slab runs along the target's third axis; an input tilted by more than volume_reorient.OBLIQUE_WARN_DEG gets a warning line.
+    Under --denoise every input, the first included, is then replaced by its non-local-means estimate on its own grid
     (volume_denoise.denoise: same shape, affine and header), and everything below sees the denoised list.
     Under --foreground every input, the first included, then has the voxels outside its foreground mask set to exactly 0, on its own grid
     (volume_foreground.foreground: same shape, affine and header again), and everything below sees the masked list.
@@ -113,6 +125,14 @@ def prepare_inputs(named_raws, options, device, labels=None):
     if brain is not None:
         source, mask_out = VBR.source_of([name for name, _ in named_raws], brain.pop('source', None)), brain.pop('mask_out', False)
     report = IntakeReport(interp=options.interp)
+    if options.reorient is not None:
+        turned = []
+        for name, raw in named_raws:
+            vol, found = VO.reorient(raw, device, **options.reorient)
+            report.reorient.append((name, found))
+            VO.warn_oblique(label(name), found)
+            turned.append((name, vol))
+        named_raws = turned
     if options.denoise is not None:
         cleaned = []
         for name, raw in named_raws:
