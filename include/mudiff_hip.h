@@ -485,7 +485,20 @@ int mud_ensemble_stats(const float* samples, int n, int N, int64_t hw, float sca
  *   x-rows (backwards under flip_0); otherwise tiles of the plane (source x, source axis p0) go through LDS, read in runs along source x
  *   and written in runs along destination x.  MUD_ERR_ARG before any launch for an elem_bytes outside {1, 2, 4, 8}, a p that is not a
  *   permutation, a flip_mask outside [0, 7], a negative extent, SX*SY*SZ >= 2^31, a null or misaligned pointer and a source that overlaps
- *   the destination (src == dst included: not an in-place operation).  A volume without voxels launches nothing and succeeds. */
+ *   the destination (src == dst included: not an in-place operation).  A volume without voxels launches nothing and succeeds.
+ * mud_volume_lowpass (--antialias / --conform; what scipy.ndimage.gaussian_filter1d does before a zoom below 1,
+ *   which the reference never performs: it takes its volumes on the training grid): a separable Gaussian low-pass of a stored volume in
+ *   front of a resampling that downsamples.  wx / wy / wz: HOST arrays of 2 r + 1 weights w[t + r], t = -r..r, computed by the caller in
+ *   fp64 (mudiff_hip.volume_conform.weights); a null array skips that axis.  The passes run in x, y, z order; one pass along axis a is
+ *   out[i] = (sum_t w[t] v[i + t]) / (sum_t w[t]), both sums over the t with 0 <= i + t < S_a, t ascending (truncation with
+ *   renormalisation), products and sums in fp64, rounded to fp32 once.  v is the value of the stored voxel (datatype, slope, inter as
+ *   everywhere) on the first pass that runs and the fp32 of the pass before on the later ones; a non-finite value is read as 0, and
+ *   *nonfinite (device, cleared first) counts those of the stored volume.  out: fp32 [Z,Y,X], what mud_volume_regrid reads as an
+ *   MUD_NIFTI_F4 source of slope 1; scratch: a second fp32 [Z,Y,X] volume, needed (and touched) only when two or three axes are
+ *   filtered.  Every global access runs along x: the x pass stages a row segment and its halo in LDS, the y and z passes an x-run times
+ *   a stretch of the filtered axis.  With all three arrays null nothing is launched and nothing is written.  MUD_ERR_ARG before any
+ *   launch for a radius outside [0, 16], a weight that is not finite or negative, a centre weight of 0, an unsupported datatype, a bad
+ *   size, a null or misaligned pointer, and an output that overlaps the source or the scratch volume. */
 #define MUD_NIFTI_U1 2
 #define MUD_NIFTI_I2 4
 #define MUD_NIFTI_I4 8
@@ -547,6 +560,8 @@ int mud_volume_edt_select(const double* d2, int64_t n, double r2, int above, con
                           void* stream);
 int mud_volume_reorient(const void* src, int elem_bytes, int SX, int SY, int SZ, int p0, int p1, int p2, int flip_mask, void* dst,
                         void* stream);
+int mud_volume_lowpass(const void* vol, int datatype, int X, int Y, int Z, float slope, float inter, const double* wx, int rx,
+                       const double* wy, int ry, const double* wz, int rz, float* out, float* scratch, uint32_t* nonfinite, void* stream);
 
 #ifdef __cplusplus
 }

@@ -91,6 +91,18 @@ __device__ __forceinline__ float vi_trilinear(const vi_source& src, int SX, int 
   return (float)acc;
 }
 
+// ---- packed reads of sub-dword voxels (volume_reorient.hip, volume_lowpass.hip) ----------------------------------------------------------
+// a word of sizeof(W) / sizeof(T) elements from an address of unknown alignment (rows of a volume start where they start; gfx950 global
+// memory takes it as one access), and element k of it
+template <typename W, typename T>
+__device__ __forceinline__ W vo_load(const T* p) {
+  W w;
+  __builtin_memcpy(&w, p, sizeof(W));
+  return w;
+}
+template <typename T, typename W>             // element k of a word (little-endian: the element at the lower address first)
+__device__ __forceinline__ T vo_element(W w, int k) { return (T)(w >> (8 * sizeof(T) * k)); }
+
 // ---- keys, bins and indices -----------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool vc_finite(float v) { return fabsf(v) <= 3.402823466e38f; }
 

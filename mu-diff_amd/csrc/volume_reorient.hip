@@ -30,12 +30,6 @@ template <typename T> struct vo_word { typedef uint32_t W; };
 template <> struct vo_word<uint64_t> { typedef uint64_t W; };
 
 template <typename W, typename T>
-__device__ __forceinline__ W vo_load(const T* p) {
-  W w;
-  __builtin_memcpy(&w, p, sizeof(W));
-  return w;
-}
-template <typename W, typename T>
 __device__ __forceinline__ void vo_store(T* p, W w) { __builtin_memcpy(p, &w, sizeof(W)); }
 
 template <typename T, typename W>             // the V elements of a word in reverse order
@@ -44,8 +38,6 @@ __device__ __forceinline__ W vo_reversed(W w) {
   if (sizeof(T) == 2) return (W)(((uint32_t)w >> 16) | ((uint32_t)w << 16));
   return w;
 }
-template <typename T, typename W>             // element k of a word (little-endian: the element at the lower address first)
-__device__ __forceinline__ T vo_element(W w, int k) { return (T)(w >> (8 * sizeof(T) * k)); }
 
 // ---- p0 == 0: rows ------------------------------------------------------------------------------------------------------------------
 struct vo_rows {

@@ -167,6 +167,7 @@ _SIGNATURES = {
     'mud_volume_edt': (_I, [_P, _I, _I, _I, _I, _D, _D, _D, _P, _P]),
     'mud_volume_edt_select': (_I, [_P, _L, _D, _I, _P, _P, _P, _P]),
     'mud_volume_reorient': (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    'mud_volume_lowpass': (_I, [_P, _I, _I, _I, _I, _F, _F, C.POINTER(C.c_double), _I, C.POINTER(C.c_double), _I, C.POINTER(C.c_double), _I, _P, _P, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

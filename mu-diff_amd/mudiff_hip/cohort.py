@@ -32,6 +32,10 @@ after the denoising; foreground_<t>.json goes next to each subject's prediction 
 With --reorient every input, ground truth and mask included, is first brought to the training orientation, on the
 main thread before all of the above; reorient_<t>.json goes next to each subject's prediction and the [done] line names what moved
 (` | reorient=T1:RAS>LPS,...`).  --reorient_back wraps the deferred writer, so the prediction returns to the first input's storage order.
+With --conform every input, ground truth and mask included, is resampled onto the training grid placed in the first
+input's world, behind the anti-aliasing low-pass of --antialias; conform_<t>.json goes next to each subject's prediction and the [done] line
+names the grid and what was resampled (` | conform=240x240x155@1mm:T1,...`).  --conform_back wraps the deferred writer too: the resampling
+onto the first input's own grid runs on the main thread, the compression and the write on the pool.
 """
 from __future__ import annotations
 
@@ -175,6 +179,7 @@ def run(args, subjects, predict=None):
     from . import volume as V
     from . import volume_intake as VI
     from . import volume_metrics as VM
+    from . import volume_conform as VCF
     from . import volume_reorient as VO
     from .driver import effective_prec_plan
     from .volume_prepare import IntakeOptions, prepare_inputs
@@ -213,7 +218,7 @@ def run(args, subjects, predict=None):
                 s = next(todo, None)
                 if s is None:
                     return
-                reads.append((s, pool.submit(_read_subject, s, needed, args.score, norm, options.regrid or options.reorient is not None)))
+                reads.append((s, pool.submit(_read_subject, s, needed, args.score, norm, options.regrid or options.reorient is not None or options.conform is not None)))
 
         prefetch()
         calibrated = False
@@ -235,12 +240,16 @@ def run(args, subjects, predict=None):
                     grid = (raws[0].shape, raws[0].affine, raws[0].header)
                     if ev is not None and options.reorient is not None:      # (the grid: the first input's once reoriented)
                         grid = VO.reference_of(raws[0], **options.reorient)[0]
-                        ev = VO.eval_inputs(ev[0], ev[1], gpu, options.reorient['target'], as_arrays=not options.regrid)
+                        ev = VO.eval_inputs(ev[0], ev[1], gpu, options.reorient['target'],
+                                            as_arrays=not (options.regrid or options.conform is not None))
+                    if ev is not None and options.conform is not None:       # (the grid: the conform grid of that first input)
+                        grid = VCF.reference_of(grid, options.conform)
                     if ev is not None:                             # the evaluation inputs onto the first input's grid, checked
-                        evaluation, resampled = VM.eval_inputs_on_grid(grid, *ev, options.regrid,
+                        evaluation, resampled = VM.eval_inputs_on_grid(grid, *ev, options.regrid or options.conform is not None,
                                                                        options.half_range, gpu, names=(subject.inputs[needed[0]], subject.gt),
                                                                        wording=lambda e: f'ground truth / mask: {e}',
-                                                                       interp=options.interp, found=found)
+                                                                       interp=options.interp, found=found,
+                                                                       **(dict(antialias=True) if options.antialias else {}))
                     torch.manual_seed(args.seed)
                     t0 = time.perf_counter()
                     conds, ref, report = prepare_inputs(list(zip(needed, raws)), options, gpu,      # (--coregister and --bias_correct work
@@ -251,6 +260,7 @@ def run(args, subjects, predict=None):
                         torch.cuda.synchronize(device)
                     report.regridded += resampled
                     report.nonfinite += found.get('nonfinite', 0)
+                    report.lowpass = report.lowpass or bool(found.get('lowpass'))
                     sargs.intake_report = report                   # (the [done] line names what it lists)
                     timing['intake'] += time.perf_counter() - t0
 
@@ -260,6 +270,9 @@ def run(args, subjects, predict=None):
 
                     if options.reorient is not None and getattr(args, 'reorient_back', False):
                         write = VO.write_back(write, raws[0], **options.reorient)
+                    if options.conform is not None and getattr(args, 'conform_back', False):
+                        write = VCF.write_back(write, VCF.first_on_own_grid(raws[0], options), ref[0], ref[1], gpu, options.interp,
+                                               options.antialias)
 
                     t0 = time.perf_counter()
                     stage = {}

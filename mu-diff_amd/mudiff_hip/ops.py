@@ -1227,3 +1227,37 @@ def volume_reorient(dev_flat, elem_bytes, shape, plan):
     _launch('volume_reorient', dev_flat.device, load().mud_volume_reorient, ptr(dev_flat), int(elem_bytes), SX, SY, SZ, p0, p1, p2, mask, ptr(out),
             STREAM, nbytes=2.0 * dev_flat.numel() * dev_flat.element_size())
     return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# --antialias / --conform (csrc/volume_lowpass.hip; the host's share is mudiff_hip.volume_conform)
+# ---------------------------------------------------------------------------------------------------
+def volume_lowpass(dev_raw, code, shape, slope, inter, weights_xyz, out=None, scratch=None):
+    """mud_volume_lowpass: the flat device array of a volume's stored voxels (datatype `code`, shape (X, Y, Z)) -> (device fp32 [Z,Y,X]:
+    the volume after one Gaussian pass along every axis that has weights, the non-finite voxels that were read as 0).  weights_xyz:
+    per axis None (not filtered) or the 2 R + 1 host weights w[t + R] (volume_conform.weights).  Without any weights nothing is launched:
+    (None, 0), and the caller goes on with the stored voxels.  `out` / `scratch`: fp32 volumes to use instead of fresh ones."""
+    X, Y, Z = _bias_volume('volume_lowpass', dev_raw, code, shape)
+    if len(weights_xyz) != 3:
+        raise ValueError(f'volume_lowpass: need the weights of three axes, got {len(weights_xyz)}')
+    arrays, args = [], []
+    for w in weights_xyz:
+        if w is None:
+            args += [None, 0]
+            continue
+        w = np.ascontiguousarray(np.asarray(w, np.float64).reshape(-1))
+        if w.size % 2 != 1:
+            raise ValueError(f'volume_lowpass: 2 R + 1 weights per axis, got {w.size}')
+        arrays.append(w)                                   # (kept alive until the call has returned)
+        args += [w.ctypes.data_as(C.POINTER(C.c_double)), w.size // 2]
+    if not arrays:
+        return None, 0
+    if out is None:
+        out = torch.empty(Z, Y, X, device=dev_raw.device, dtype=torch.float32)
+    if scratch is None and len(arrays) > 1:
+        scratch = torch.empty(Z, Y, X, device=dev_raw.device, dtype=torch.float32)
+    require_gpu(dev_raw, out, scratch)
+    bad = torch.empty(1, device=dev_raw.device, dtype=torch.int32)
+    _launch('volume_lowpass', dev_raw.device, load().mud_volume_lowpass, ptr(dev_raw), int(code), X, Y, Z, float(slope), float(inter), *args,
+            ptr(out), ptr(scratch), ptr(bad), STREAM, nbytes=float(dev_raw.numel() * (dev_raw.element_size() + 4 + 8 * (len(arrays) - 1))))
+    return out, int(bad.cpu().numpy().view(np.uint32)[0])

@@ -12,7 +12,8 @@ Slices are independent, so the only observable difference is the order in which 
 inject the draws per slice (`predict_slices(..., x_inits, zs, noises)`).
 
 Intake: every path reads the three condition files as stored (volume_intake.read_nifti_raw) and hands them to the one preparation
-stage, volume_prepare.prepare_inputs (the first input's grid; --reorient, --denoise, --foreground, --coregister, --regrid, --bias_correct); host_stacks then normalises
+stage, volume_prepare.prepare_inputs (the first input's grid, or under --conform the training grid placed in its world; --reorient, --denoise,
+--foreground, --coregister, --regrid, --bias_correct); host_stacks then normalises
 with numpy, --device_intake with volume_intake.condition_from_raw.  What the stage did travels as args.intake_report to the [done] line.
 
 NIfTI I/O: nibabel is used when importable (it is not in this image); otherwise a minimal built-in reader/writer
@@ -354,12 +355,14 @@ def predict_volume(args):
     --bias_field_out, the field volumes), denoise_<target>.json and foreground_<target>.json (and, with --foreground_mask_out, the masks)
     next to the prediction (volume_prepare.IntakeReport.write).  Under --reorient (mudiff_hip.volume_reorient) everything is written on the
     reoriented grid, with the affine and header that describe it, and reorient_<target>.json is added; --reorient_back returns the
-    prediction (and its std) to the first input's storage order, after the scoring."""
+    prediction (and its std) to the first input's storage order, after the scoring.  Under --conform (mudiff_hip.volume_conform) everything
+    is sampled, scored and written on the conform grid and conform_<target>.json is added; --conform_back resamples the prediction (and its
+    std) onto the first input's own grid as it is written."""
     from .volume_prepare import IntakeReport
     found = {}
     evaluation, resampled = _load_eval_inputs(args, found)
     args = copy.copy(args)                               # the run's own copy: it carries the record of what the intake did
-    args.intake_report = IntakeReport(resampled, nonfinite=found.get('nonfinite', 0))
+    args.intake_report = IntakeReport(resampled, nonfinite=found.get('nonfinite', 0), lowpass=bool(found.get('lowpass')))
     from . import ops
     from .driver import effective_prec_plan
     plan = effective_prec_plan(args)
@@ -385,7 +388,9 @@ def load_eval_inputs(args):
     here, so that it cannot cost a sampling run.  With --regrid a ground truth or a label volume on another grid is first resampled
     onto the first input's (mudiff_hip.volume_regrid: trilinear, or cubic under --regrid_interp cubic / nearest neighbour).  With
     --reorient the grid they are checked against is the first input's once reoriented (its plan's shape, affine and header: no voxel of
-    it is moved for that), and each evaluation input is reoriented by its own affine to the same target first."""
+    it is moved for that), and each evaluation input is reoriented by its own affine to the same target first.  With --conform the grid
+    is the conform grid of that first input (volume_conform.conform_grid: again no voxel of it is moved) and the evaluation inputs are
+    resampled onto it as under --regrid; with --antialias the ground truth is low-passed where that downsamples it."""
     return _load_eval_inputs(args)[0]
 
 
@@ -399,13 +404,16 @@ def _load_eval_inputs(args, found=None):
     from .volume_metrics import eval_inputs_on_grid
     _, first = _needed_inputs(args)[0]
     device = torch.device(f'cuda:{args.gpu_chose}')
+    from .volume_prepare import IntakeOptions
+    options = IntakeOptions.from_args(args)
+    regrid = bool(args.regrid) or options.conform is not None
     if getattr(args, 'reorient', False):
         from . import volume_reorient as VO
-        target = VO.check_target(getattr(args, 'reorient_to', VO.DEFAULT_TARGET))
+        target = VO.check_target(getattr(args, 'reorient_to', None) or VO.DEFAULT_TARGET)
         ref = VO.reference_of(VI.read_nifti_raw(first), target)[0]
         gt, label, gt_aff = VO.eval_inputs(VI.read_nifti_raw(args.gt_volume), None if args.eval_mask is None else VI.read_nifti_raw(args.eval_mask),
-                                           device, target, as_arrays=not args.regrid)
-    elif args.regrid:
+                                           device, target, as_arrays=not regrid)
+    elif regrid:
         inp = VI.read_nifti_raw(first)
         ref = (inp.shape, inp.affine, inp.header)
         gt = VI.read_nifti_raw(args.gt_volume)
@@ -416,10 +424,17 @@ def _load_eval_inputs(args, found=None):
         ref = (inp.shape, inp_aff, inp_hdr)
         gt, gt_aff, _ = read_nifti(args.gt_volume)
         label = None if args.eval_mask is None else read_nifti(args.eval_mask)[0]
-    return eval_inputs_on_grid(ref, gt, label, gt_aff, args.regrid, args.slice_half_range, device,
+    more = {}
+    if options.conform is not None:
+        from . import volume_conform as VCF
+        ref = VCF.reference_of(ref, options.conform)
+    if options.antialias:
+        more = dict(antialias=True)
+        found = {} if found is None else found
+    return eval_inputs_on_grid(ref, gt, label, gt_aff, regrid, args.slice_half_range, device,
                                names=(first, args.gt_volume),
                                wording=lambda e: f'--gt_volume / --eval_mask: {e} (the prediction has the shape of {first})',
-                               interp=getattr(args, 'regrid_interp', 'linear'), found=found)
+                               interp=getattr(args, 'regrid_interp', 'linear'), found=found, **more)
 
 
 def _score_prediction(args, evaluation, vol, std_vol, device):
@@ -460,8 +475,12 @@ def _predict_volume(args, plan, evaluation=None):
     if options.reorient is not None and getattr(args, 'reorient_back', False):
         from . import volume_reorient as VO
         write = VO.write_back(write_nifti, raws[0], **options.reorient)
+    if options.conform is not None and getattr(args, 'conform_back', False):
+        from . import volume_conform as VCF
+        write = VCF.write_back(write or write_nifti, VCF.first_on_own_grid(raws[0], options), ref[0], ref[1], device, options.interp, options.antialias)
     report.regridded += _intake_report(args).regridded       # the inputs first, then the evaluation inputs predict_volume resampled
     report.nonfinite += _intake_report(args).nonfinite
+    report.lowpass = report.lowpass or _intake_report(args).lowpass
     args.intake_report = report
     if args.device_intake:
         stacks = [VI.condition_from_raw(vol, options.half_range, args.image_size, device, name=path, norm=options.norm)
@@ -753,13 +772,34 @@ def make_parser(prog='MU-Diff volume prediction (MI355X)'):
                         'reorient_<t>.json next to the prediction holds what was done.  A permutation cannot make tilted slices axial: an '
                         'input whose axes are tilted by more than 10 degrees (an untuned default, not a measured bar) gets a warning, and '
                         'de-obliquing by resampling is not done')
-    p.add_argument('--reorient_to', type=str, default='LPS', metavar='CODE',
+    p.add_argument('--reorient_to', type=str, default=None, metavar='CODE',
                    help="the target orientation of --reorient, one letter of each of R/L, A/P, S/I: the direction every storage axis runs "
                         "towards.  'LPS' is how BraTS stores its volumes, which the reference reads without reorienting; a checkpoint "
-                        'trained on data stored otherwise needs its own code')
+                        'trained on data stored otherwise needs its own code.  Default: LPS, or under --conform what --conform_to says')
     p.add_argument('--reorient_back', action='store_true',
                    help="with --reorient: write predicted_<t>.nii.gz (and predicted_<t>_std.nii.gz) in the first input's own storage order, "
                         'with its original affine and header (scored first, on the reoriented grid)')
+    p.add_argument('--conform', action='store_true',
+                   help='resample every input, the first included, once onto one axis-aligned grid of the training geometry (240 x 240 x 155 '
+                        "voxels of 1 mm, stored LPS: BraTS), placed so that its centre lies on the centre of the first input's grid "
+                        '(mudiff_hip.volume_conform): another voxel size or field of view reaches the generators at the scale they were '
+                        'trained on and a tilted acquisition is de-obliqued.  Implies the resampling of --regrid for the inputs and for '
+                        '--gt_volume / --eval_mask; everything is sampled, scored and written on that grid; conform_<t>.json next to the '
+                        'prediction holds what was done')
+    p.add_argument('--conform_shape', nargs=3, type=int, default=[240, 240, 155], metavar=('X', 'Y', 'Z'), help='the voxels of the conform grid')
+    p.add_argument('--conform_spacing', nargs='+', type=float, default=[1.0], metavar='MM',
+                   help='the voxel size of the conform grid in mm: one value, or three (one per axis)')
+    p.add_argument('--conform_to', type=str, default='LPS', metavar='CODE',
+                   help='the orientation of the conform grid (as --reorient_to: the direction every storage axis runs towards)')
+    p.add_argument('--conform_back', action='store_true',
+                   help="with --conform: write predicted_<t>.nii.gz (and predicted_<t>_std.nii.gz) resampled onto the first input's own grid "
+                        '(by --regrid_interp), with its affine and header (scored first, on the conform grid)')
+    p.add_argument('--antialias', type=str, default=None, choices=['on', 'off'],
+                   help='low-pass a volume on the GPU before a resampling that downsamples it (--conform, --regrid, --coregister; the '
+                        '--gt_volume too, never the --eval_mask): a separable Gaussian per source axis whose FWHM, added in quadrature to '
+                        'the source voxel, gives the target voxel, sigma = sqrt(f^2 - 1) / 2.355 source voxels for a sampling factor f > 1 '
+                        '(an untuned default, not a measured optimum); an axis that is not downsampled is not filtered, and a resampling '
+                        "that downsamples nothing is bit for bit what it is without the flag.  Default: 'on' under --conform, else 'off'")
     from .driver import add_calibration_flags
     add_calibration_flags(p)                # (also --prec_plan)
     return p
@@ -797,13 +837,26 @@ def finish_args(p, args):
         check_brain(args.brain_bins, args.brain_erode_mm, args.brain_dilate_mm, args.brain_keep_holes)
     except ValueError as e:
         p.error(str(e))
-    from .volume_reorient import check_target
+    from .volume_reorient import DEFAULT_TARGET, check_target
     try:
+        args.conform_to = check_target(args.conform_to)
+        if args.reorient_to is None:                     # not given: it follows --conform_to under --conform
+            args.reorient_to = args.conform_to if args.conform else DEFAULT_TARGET
         args.reorient_to = check_target(args.reorient_to)
     except ValueError as e:
         p.error(str(e))
     if args.reorient_back and not args.reorient:
         p.error('--reorient_back needs --reorient')
+    from . import volume_conform as VCF
+    try:
+        args.conform_shape = list(VCF._shape3(args.conform_shape, '--conform_shape'))
+        args.conform_spacing = list(VCF._spacing3(args.conform_spacing))
+    except ValueError as e:
+        p.error(str(e))
+    if args.conform_back and not args.conform:
+        p.error('--conform_back needs --conform')
+    if args.conform and args.reorient and args.conform_to != args.reorient_to:
+        p.error(f'--conform_to {args.conform_to} differs from --reorient_to {args.reorient_to}: give both the same code')
     return args
 
 
@@ -818,7 +871,9 @@ def build_argparser(argv=None):
     shading of every input), --denoise (non-local-means denoising of every input) and
     --foreground (a foreground mask of every input: everything outside becomes 0) and --brain_extract (one
     morphological brain mask per subject, applied to every input) and --reorient / --reorient_to / --reorient_back
-    (the inputs brought to the training orientation)."""
+    (the inputs brought to the training orientation) and --conform / --conform_shape / --conform_spacing /
+    --conform_to / --conform_back / --antialias (the inputs resampled onto the training grid behind an anti-aliasing low-pass, DESIGN.md
+    section 5.21)."""
     p = make_parser()
     return finish_args(p, p.parse_args(argv))
 

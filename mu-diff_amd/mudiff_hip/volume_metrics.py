@@ -256,10 +256,11 @@ def score_files(pred_path, gt_path, mask_path=None, std_path=None, slice_half_ra
                         norm=norm)
 
 
-def eval_inputs_on_grid(ref, gt, label, gt_affine, regrid, half_range, device, names, wording=str, interp='linear', found=None):
+def eval_inputs_on_grid(ref, gt, label, gt_affine, regrid, half_range, device, names, wording=str, interp='linear', found=None,
+                        antialias=False):
     """The evaluation inputs of a prediction on the grid ref = (shape, affine, header) of its first input, checked: under `regrid`
     (--regrid) `gt` and `label` are RawVolumes and what is not on that grid is resampled onto it (volume_regrid.eval_onto_grid, which
-    explains `interp` and `found`);
+    explains `interp`, `found` and `antialias`);
     otherwise they are arrays as volume.read_nifti returns them.  `label` may be None; `gt_affine`: the ground truth's own affine.
     check_shapes' ValueError is raised as ValueError(wording(e)); the affines are compared (warn_affine, with `names` = what to call
     the first input and the ground truth) unless the ground truth was just resampled.  -> ((gt, label), the names of what was resampled)."""
@@ -267,7 +268,8 @@ def eval_inputs_on_grid(ref, gt, label, gt_affine, regrid, half_range, device, n
     resampled = []
     if regrid:
         from . import volume_regrid as VR
-        gt, label, resampled = VR.eval_onto_grid(shape, VR.world_affine_of(affine, header), gt, label, device, interp=interp, found=found)
+        gt, label, resampled = VR.eval_onto_grid(shape, VR.world_affine_of(affine, header), gt, label, device, interp=interp, found=found,
+                                                  **(dict(antialias=True) if antialias else {}))
     try:
         check_shapes(shape, gt.shape, None if label is None else label.shape, half_range)
     except ValueError as e:

@@ -73,11 +73,15 @@ def same_grid(shape_a, aff_a, shape_b, aff_b):
     return a.shape == b.shape and bool(np.array_equal(a.astype(np.float32), b.astype(np.float32)))
 
 
-def regrid(dev_raw, code, shape, slope, inter, M, out_shape, mode='linear', found=None):
+def regrid(dev_raw, code, shape, slope, inter, M, out_shape, mode='linear', found=None, antialias=False, name=None):
     """mud_volume_regrid: the flat device array of a volume's stored voxels (datatype `code`, shape [SX,SY,SZ]) -> device fp32
     [Z,Y,X] on the grid of `out_shape` = (X,Y,Z).  M: grid_matrix(...) (4 x 4 or 3 x 4).  mode 'cubic': the value range
     (mud_volume_fg_range), the spline coefficients (mud_volume_bspline_coeffs: fp64, freed on return) and mud_volume_regrid_cubic; a dict
-    `found` then receives `nonfinite`, the non-finite voxels that were read as 0."""
+    `found` then receives `nonfinite`, the non-finite voxels that were read as 0.  `antialias` (--antialias; an
+    image only, never mode 'nearest'): where M steps over more than one source voxel the volume first goes through the Gaussian low-pass
+    volume_conform.lowpass_plan(M) asks for (mud_volume_lowpass) and its fp32 output is what is resampled; `found` then receives the plan
+    as `antialias`, `lowpass` (True when a pass ran) and the non-finite voxels the filter read as 0 in `nonfinite`.  Where no axis needs
+    filtering nothing is launched and the stored voxels are resampled as without it.  `name`: what an error calls the volume."""
     require_gpu(dev_raw)
     if mode not in MODES and mode not in MODES_HIGH:
         raise ValueError(f'mode must be one of {tuple(MODES) + MODES_HIGH}, got {mode!r}')
@@ -91,22 +95,30 @@ def regrid(dev_raw, code, shape, slope, inter, M, out_shape, mode='linear', foun
     m = np.ascontiguousarray(np.asarray(M, np.float64)[:3, :4])
     if m.shape != (3, 4):
         raise ValueError(f'regrid: need a 3 x 4 or 4 x 4 matrix, got {np.shape(M)}')
-    out = torch.empty(max(Z, 0), max(Y, 0), max(X, 0), device=dev_raw.device, dtype=torch.float32)
     from . import ops
+    bad = 0
+    if antialias and mode != 'nearest':
+        from . import volume_conform as VCF
+        low, bad, plan = VCF.lowpass(dev_raw, int(code), (SX, SY, SZ), float(slope), float(inter), m, name or 'the volume')
+        if found is not None:
+            found.update(antialias={k: plan[k] for k in ('factors', 'sigmas', 'radii')}, lowpass=low is not None, nonfinite=bad)
+        if low is not None:
+            dev_raw, code, slope, inter = low.reshape(-1), NIFTI_F4, 1.0, 0.0
+    out = torch.empty(max(Z, 0), max(Y, 0), max(X, 0), device=dev_raw.device, dtype=torch.float32)
     if mode in MODES_HIGH:
         from .volume_foreground import unkey
         rng = ops.volume_fg_range(dev_raw, int(code), (SX, SY, SZ), float(slope), float(inter)).cpu().numpy().view(np.uint32)
         lo, hi = (unkey(~int(rng[0])), unkey(rng[1])) if int(rng[2]) else (0.0, 0.0)      # the finite values that are != 0 ...
         lo, hi = min(lo, 0.0), max(hi, 0.0)                                               # ... widened to contain 0
         coeffs = torch.empty(SZ, SY, SX, device=dev_raw.device, dtype=torch.float64)
-        bad = torch.empty(1, device=dev_raw.device, dtype=torch.int32)
+        seen = torch.empty(1, device=dev_raw.device, dtype=torch.int32)
         ops._launch('volume_bspline_coeffs', dev_raw.device, load().mud_volume_bspline_coeffs, ptr(dev_raw), int(code), SX, SY, SZ, float(slope),
-                    float(inter), ptr(coeffs), ptr(bad), ops.STREAM, nbytes=float(dev_raw.numel() * (3 * dev_raw.element_size() + 80)))
+                    float(inter), ptr(coeffs), ptr(seen), ops.STREAM, nbytes=float(dev_raw.numel() * (3 * dev_raw.element_size() + 80)))
         ops._launch('volume_regrid_cubic', dev_raw.device, load().mud_volume_regrid_cubic, ptr(coeffs), SX, SY, SZ, ptr(dev_raw), int(code),
                     float(slope), float(inter), (C.c_double * 12)(*m.reshape(-1).tolist()), lo, hi, X, Y, Z, ptr(out), ops.STREAM,
                     nbytes=float(8 * coeffs.numel() + dev_raw.numel() * dev_raw.element_size() + 4 * out.numel()))
         if found is not None:
-            found['nonfinite'] = int(bad.cpu().numpy().view(np.uint32)[0])
+            found['nonfinite'] = bad + int(seen.cpu().numpy().view(np.uint32)[0])
         del coeffs                                            # (stream-ordered: the allocator reuses it after the launch above)
         return out
     ops._launch('volume_regrid', dev_raw.device, load().mud_volume_regrid, ptr(dev_raw), int(code), SX, SY, SZ, float(slope), float(inter),
@@ -139,13 +151,13 @@ class RegriddedVolume(RawVolume):
         return self.data.reshape(self.shape, order='F')
 
 
-def regrid_to(raw, ref_shape, ref_affine, device, mode='linear', header=None, world=None, found=None):
+def regrid_to(raw, ref_shape, ref_affine, device, mode='linear', header=None, world=None, found=None, antialias=False, name=None):
     """A RawVolume -> the same volume on the grid (ref_shape, ref_affine): a RegriddedVolume (fp32, NIFTI_F4, slope 1, inter 0, that
     geometry; `header`: the reference's) ready for volume_intake.condition_from_raw.  A volume already on that grid is returned
     untouched.  The source's place in the world is world_affine_of(raw.affine, raw.header).  `world` (--coregister,
     mudiff_hip.volume_coreg): a 4 x 4 matrix W that takes a world point of the reference to the source's world, so that the sampling
     matrix is inv(source affine) @ W @ reference affine; with a W that is not the identity the volume is resampled even on its own grid.
-    `mode`: 'linear', 'cubic' (an image) or 'nearest' (a label volume); `found`: see regrid."""
+    `mode`: 'linear', 'cubic' (an image) or 'nearest' (a label volume); `found`, `antialias`, `name`: see regrid."""
     if len(raw.shape) != 3 or len(ref_shape) != 3:
         raise ValueError(f'regrid: expected 3D volumes, got shapes {tuple(raw.shape)} and {tuple(ref_shape)}')
     src_affine = world_affine_of(raw.affine, raw.header)
@@ -153,13 +165,18 @@ def regrid_to(raw, ref_shape, ref_affine, device, mode='linear', header=None, wo
     if not moved and same_grid(raw.shape, src_affine, ref_shape, ref_affine):
         return raw
     M = grid_matrix(src_affine, _affine44(world, 'world transform') @ _affine44(ref_affine, 'reference affine') if moved else ref_affine)
-    dev = regrid(upload(raw, device), raw.code, raw.shape, *raw.scaling, M, ref_shape, mode, found)
+    if antialias:
+        dev = regrid(upload(raw, device), raw.code, raw.shape, *raw.scaling, M, ref_shape, mode, found, antialias=True, name=name)
+    else:
+        dev = regrid(upload(raw, device), raw.code, raw.shape, *raw.scaling, M, ref_shape, mode, found)
     return RegriddedVolume(dev, ref_shape, np.asarray(ref_affine, np.float64), header)
 
 
-def eval_onto_grid(ref_shape, ref_affine, gt_raw, mask_raw, device, names=('gt_volume', 'eval_mask'), interp='linear', found=None):
+def eval_onto_grid(ref_shape, ref_affine, gt_raw, mask_raw, device, names=('gt_volume', 'eval_mask'), interp='linear', found=None,
+                   antialias=False):
     """The evaluation inputs on the reference grid: the ground truth by `interp` (--regrid_interp: trilinearly by default), the label
     volume by nearest neighbour, always.  A dict `found` has the non-finite voxels a cubic resampling read as 0 added to its `nonfinite`.
+    `antialias`: the ground truth goes through regrid's low-pass first (the label volume never); `found` gets `lowpass` when one ran.
     -> (gt [X,Y,Z] float64 as volume.read_nifti returns it, label or None, the names of what was resampled)."""
     out, done = [], []
     for raw, mode, name in ((gt_raw, interp, names[0]), (mask_raw, 'nearest', names[1])):
@@ -169,9 +186,12 @@ def eval_onto_grid(ref_shape, ref_affine, gt_raw, mask_raw, device, names=('gt_v
         if mode not in INTERPS and mode != 'nearest':
             raise ValueError(f'interp must be one of {INTERPS}, got {mode!r}')
         seen = {}
-        r = regrid_to(raw, ref_shape, ref_affine, device, mode, found=seen)
+        more = dict(antialias=True, name=name) if antialias and mode != 'nearest' else {}
+        r = regrid_to(raw, ref_shape, ref_affine, device, mode, found=seen, **more)
         if found is not None:
             found['nonfinite'] = found.get('nonfinite', 0) + seen.get('nonfinite', 0)
+            if seen.get('lowpass'):
+                found['lowpass'] = True
         if r is not raw:
             done.append(name)
             out.append(r.values_float32().astype(np.float64))
