@@ -19,23 +19,12 @@ Outputs: <output_dir>/<id>/predicted_<t>.nii.gz (plus _std and metrics_<t>.json 
 per-subject rows, per region and metric the mean, the population standard deviation (ddof = 0) and the subject count, and the seconds
 of every stage summed over the cohort.  With --norm zscore the moments of every volume are computed on the
 prefetch thread, the [done] lines end in ` | norm=zscore`, and the reports carry "norm": "zscore" (a default run's are unchanged).
-With --regrid a subject's volumes, ground truth and mask included, need not share one voxel grid: what is not
-on the first input's grid is resampled onto it on the device, and the subject's [done] line names it (` | regrid=T2,gt_volume`).
-With --coregister every input other than the first is first aligned to the first one rigidly; the search runs
-on the main thread between the upload and the intake, and coreg_<t>.json goes next to each subject's prediction.
-With --bias_correct every input is divided by its estimated bias field, also on the main thread between the
-upload and the intake; bias_<t>.json goes next to each subject's prediction and the [done] line names the inputs (` | bias=...`).
-With --denoise every input is first replaced by its non-local-means estimate, on the main thread before all
-of the above; denoise_<t>.json goes next to each subject's prediction and the [done] line names the inputs (` | denoise=...`).
-With --foreground every input then has the voxels outside its foreground mask set to 0, on the main thread right
-after the denoising; foreground_<t>.json goes next to each subject's prediction and the [done] line names the inputs (` | foreground=...`).
-With --reorient every input, ground truth and mask included, is first brought to the training orientation, on the
-main thread before all of the above; reorient_<t>.json goes next to each subject's prediction and the [done] line names what moved
-(` | reorient=T1:RAS>LPS,...`).  --reorient_back wraps the deferred writer, so the prediction returns to the first input's storage order.
-With --conform every input, ground truth and mask included, is resampled onto the training grid placed in the first
-input's world, behind the anti-aliasing low-pass of --antialias; conform_<t>.json goes next to each subject's prediction and the [done] line
-names the grid and what was resampled (` | conform=240x240x155@1mm:T1,...`).  --conform_back wraps the deferred writer too: the resampling
-onto the first input's own grid runs on the main thread, the compression and the write on the pool.
+An input stage (volume_prepare.STAGES; each module's header says what it does, volume.make_parser's help what its flags are) works on
+the main thread, between the read and the intake, exactly as in a single run: its report file goes next to each subject's prediction
+and the subject's [done] line names what it did.  The evaluation inputs go onto the grid the prediction will have on the main thread
+too (volume_prepare.evaluation_inputs); the prefetch thread only reads them (volume_prepare.read_for_evaluation).  --reorient_back and
+--conform_back wrap the deferred writer (volume_prepare.output_writer): the resampling onto the first input's own grid runs on the main
+thread, the compression and the write on the pool.
 """
 from __future__ import annotations
 
@@ -133,19 +122,19 @@ def format_lines(agg):
 # ---------------------------------------------------------------------------------------------------
 # one subject
 # ---------------------------------------------------------------------------------------------------
-def _read_subject(subject, needed, score, norm='percentile', regrid=False):
-    """(prefetch thread) The subject's three condition volumes as stored (volume_intake.read_nifti_raw) and, with `score`, the
-    evaluation inputs of volume.load_eval_inputs.  With norm='zscore' every volume's moments are computed here too, next to the read
-    (RawVolume.moments; their seconds in RawVolume.moments_s).  With `regrid` (--regrid, --reorient) the evaluation inputs stay as stored,
-    geometry included: the main thread reorients them and puts them on the first input's grid.  -> (raws, (gt, label or None, the gt's affine) or None, seconds)."""
-    from . import volume as V
+def _read_subject(subject, needed, score, options):
+    """(prefetch thread: no GPU work) The subject's three condition volumes as stored (volume_intake.read_nifti_raw) and, with `score`,
+    the evaluation inputs as volume_prepare.read_for_evaluation reads them under `options`.  With --norm zscore every volume's moments are
+    computed here too, next to the read (RawVolume.moments; their seconds in RawVolume.moments_s).  -> (raws, (gt, label or None) or
+    None, seconds)."""
     from . import volume_intake as VI
+    from .volume_prepare import read_for_evaluation
     t0 = time.perf_counter()
     for m in needed:
         if not subject.inputs.get(m):
             raise ValueError(f'no {m} volume given')
     raws = [VI.read_nifti_raw(subject.inputs[m]) for m in needed]
-    if norm == 'zscore':
+    if options.norm == 'zscore':
         for r in raws:
             t1 = time.perf_counter()
             r.moments = VI.zscore_moments(r)
@@ -154,13 +143,7 @@ def _read_subject(subject, needed, score, norm='percentile', regrid=False):
     if score:
         if not subject.gt:
             raise ValueError('--score needs a ground-truth volume (the manifest\'s gt column)')
-        if regrid:
-            gt = VI.read_nifti_raw(subject.gt)
-            ev = (gt, VI.read_nifti_raw(subject.mask) if subject.mask else None, gt.affine)
-        else:
-            gt, gt_aff, _ = V.read_nifti(subject.gt)
-            label = V.read_nifti(subject.mask)[0] if subject.mask else None
-            ev = (gt, label, gt_aff)
+        ev = (read_for_evaluation(subject.gt, options), read_for_evaluation(subject.mask or None, options))
     return raws, ev, time.perf_counter() - t0
 
 
@@ -178,11 +161,8 @@ def run(args, subjects, predict=None):
     from . import ops
     from . import volume as V
     from . import volume_intake as VI
-    from . import volume_metrics as VM
-    from . import volume_conform as VCF
-    from . import volume_reorient as VO
     from .driver import effective_prec_plan
-    from .volume_prepare import IntakeOptions, prepare_inputs
+    from .volume_prepare import IntakeOptions, evaluation_inputs, output_writer, prepare_inputs
     target = args.target_modality
     needed = V.MODALITY_ORDERS[target]
     plan = effective_prec_plan(args)
@@ -218,7 +198,7 @@ def run(args, subjects, predict=None):
                 s = next(todo, None)
                 if s is None:
                     return
-                reads.append((s, pool.submit(_read_subject, s, needed, args.score, norm, options.regrid or options.reorient is not None or options.conform is not None)))
+                reads.append((s, pool.submit(_read_subject, s, needed, args.score, options)))
 
         prefetch()
         calibrated = False
@@ -237,19 +217,9 @@ def run(args, subjects, predict=None):
                     sargs.output_dir = os.path.join(args.output_dir, subject.id)
                     gpu = device or torch.device(f'cuda:{args.gpu_chose}')
                     evaluation, resampled, found = None, [], {}
-                    grid = (raws[0].shape, raws[0].affine, raws[0].header)
-                    if ev is not None and options.reorient is not None:      # (the grid: the first input's once reoriented)
-                        grid = VO.reference_of(raws[0], **options.reorient)[0]
-                        ev = VO.eval_inputs(ev[0], ev[1], gpu, options.reorient['target'],
-                                            as_arrays=not (options.regrid or options.conform is not None))
-                    if ev is not None and options.conform is not None:       # (the grid: the conform grid of that first input)
-                        grid = VCF.reference_of(grid, options.conform)
-                    if ev is not None:                             # the evaluation inputs onto the first input's grid, checked
-                        evaluation, resampled = VM.eval_inputs_on_grid(grid, *ev, options.regrid or options.conform is not None,
-                                                                       options.half_range, gpu, names=(subject.inputs[needed[0]], subject.gt),
-                                                                       wording=lambda e: f'ground truth / mask: {e}',
-                                                                       interp=options.interp, found=found,
-                                                                       **(dict(antialias=True) if options.antialias else {}))
+                    if ev is not None:                             # the evaluation inputs onto the grid of the prediction, checked
+                        evaluation, resampled, found = evaluation_inputs(raws[0], *ev, options, gpu, names=(subject.inputs[needed[0]], subject.gt),
+                                                                         wording=lambda e: f'ground truth / mask: {e}')
                     torch.manual_seed(args.seed)
                     t0 = time.perf_counter()
                     conds, ref, report = prepare_inputs(list(zip(needed, raws)), options, gpu,      # (--coregister and --bias_correct work
@@ -258,9 +228,7 @@ def run(args, subjects, predict=None):
                         conds = [VI.condition_from_raw(vol, options.half_range, args.image_size, device, name=subject.inputs[m], norm=norm)
                                  for m, vol in zip(needed, conds)]
                         torch.cuda.synchronize(device)
-                    report.regridded += resampled
-                    report.nonfinite += found.get('nonfinite', 0)
-                    report.lowpass = report.lowpass or bool(found.get('lowpass'))
+                    report.add_evaluation(resampled, found)
                     sargs.intake_report = report                   # (the [done] line names what it lists)
                     timing['intake'] += time.perf_counter() - t0
 
@@ -268,11 +236,7 @@ def run(args, subjects, predict=None):
                         drain(QUEUE_DEPTH - 1)                     # subject i-1 is compressed and written while subject i runs
                         pending.append(pool.submit(_timed_write, path, vol, affine, header))
 
-                    if options.reorient is not None and getattr(args, 'reorient_back', False):
-                        write = VO.write_back(write, raws[0], **options.reorient)
-                    if options.conform is not None and getattr(args, 'conform_back', False):
-                        write = VCF.write_back(write, VCF.first_on_own_grid(raws[0], options), ref[0], ref[1], gpu, options.interp,
-                                               options.antialias)
+                    write = output_writer(write, raws[0], options, ref, gpu, getattr(args, 'reorient_back', False), getattr(args, 'conform_back', False))
 
                     t0 = time.perf_counter()
                     stage = {}

@@ -12,9 +12,9 @@ Slices are independent, so the only observable difference is the order in which 
 inject the draws per slice (`predict_slices(..., x_inits, zs, noises)`).
 
 Intake: every path reads the three condition files as stored (volume_intake.read_nifti_raw) and hands them to the one preparation
-stage, volume_prepare.prepare_inputs (the first input's grid, or under --conform the training grid placed in its world; --reorient, --denoise,
---foreground, --coregister, --regrid, --bias_correct); host_stacks then normalises
-with numpy, --device_intake with volume_intake.condition_from_raw.  What the stage did travels as args.intake_report to the [done] line.
+stage, volume_prepare.prepare_inputs; host_stacks then normalises with numpy, --device_intake with volume_intake.condition_from_raw.
+What the stage did travels as args.intake_report to the [done] line.  Each stage's flags, defaults and checks live in its own module
+(volume_prepare.STAGES lists them): make_parser, finish_args and IntakeOptions.from_args loop over that table.
 
 NIfTI I/O: nibabel is used when importable (it is not in this image); otherwise a minimal built-in reader/writer
 handles single-file NIfTI-1 (.nii / .nii.gz, little- or big-endian, scl_slope/inter applied like get_fdata()).
@@ -93,9 +93,9 @@ def norm_suffix(norm):
 
 
 def regrid_suffix(names):
-    """What a [done] line gains when --regrid resampled inputs (nothing otherwise: the lines as they were)."""
-    names = list(names or ())
-    return f" | regrid={','.join(names)}" if names else ''
+    """volume_regrid.regrid_suffix, under the name it first had."""
+    from .volume_regrid import regrid_suffix as suffix
+    return suffix(names)
 
 
 def extract_center_slices(volume, half_range):
@@ -211,14 +211,19 @@ def write_nifti(path, vol, affine, header=None):
         return
     except ImportError:
         pass
-    vol = np.asarray(vol, dtype=np.float32)
+    write_nifti1(path, np.asarray(vol, dtype=np.float32), affine, header, 16, 32)
+
+
+def write_nifti1(path, vol, affine, header, code, bitpix):
+    """The built-in writer behind write_nifti (float32: datatype code 16, bitpix 32) and volume_foreground.write_mask (uint8: 2, 8):
+    `vol` is already of that type.  A little-endian NiftiHeader is reused, geometry fields overwritten; anything else gives a blank one."""
     reuse = isinstance(header, NiftiHeader) and header.endian == '<'
     raw = bytearray(header.raw) if reuse else bytearray(348)
     struct.pack_into('<i', raw, 0, 348)
     dim = [vol.ndim] + list(vol.shape) + [1] * (7 - vol.ndim)
     struct.pack_into('<8h', raw, 40, *dim)
-    struct.pack_into('<h', raw, 70, 16)           # datatype float32
-    struct.pack_into('<h', raw, 72, 32)           # bitpix
+    struct.pack_into('<h', raw, 70, code)         # datatype
+    struct.pack_into('<h', raw, 72, bitpix)
     struct.pack_into('<f', raw, 108, 352.0)       # vox_offset
     struct.pack_into('<2f', raw, 112, 1.0, 0.0)   # scl_slope, scl_inter
     if not reuse:
@@ -351,18 +356,13 @@ def predict_volume(args):
     there and its std next to it; the return value is then the pair of paths.  --prec_plan holds for the whole prediction.
     With --gt_volume (and --eval_mask) the written prediction is scored afterwards (mudiff_hip.volume_metrics): the lines are printed
     after the [done] line and metrics_<target>.json goes next to the prediction.  Those inputs are checked first, before any GPU or
-    checkpoint work.  --coregister, --bias_correct, --denoise and --foreground add coreg_<target>.json, bias_<target>.json (and, with
-    --bias_field_out, the field volumes), denoise_<target>.json and foreground_<target>.json (and, with --foreground_mask_out, the masks)
-    next to the prediction (volume_prepare.IntakeReport.write).  Under --reorient (mudiff_hip.volume_reorient) everything is written on the
-    reoriented grid, with the affine and header that describe it, and reorient_<target>.json is added; --reorient_back returns the
-    prediction (and its std) to the first input's storage order, after the scoring.  Under --conform (mudiff_hip.volume_conform) everything
-    is sampled, scored and written on the conform grid and conform_<target>.json is added; --conform_back resamples the prediction (and its
-    std) onto the first input's own grid as it is written."""
-    from .volume_prepare import IntakeReport
-    found = {}
-    evaluation, resampled = _load_eval_inputs(args, found)
+    checkpoint work.  An input stage (volume_prepare.STAGES; each module's header says what it does) adds its report file, and what its
+    *_out flag asks for, next to the prediction (volume_prepare.IntakeReport.write).  Under --reorient and --conform everything is sampled,
+    scored and written on the reoriented / the conform grid; --reorient_back and --conform_back return the prediction (and its std) to the
+    first input's own grid as it is written, after the scoring (volume_prepare.output_writer)."""
+    evaluation, resampled, found = _load_eval_inputs(args)
     args = copy.copy(args)                               # the run's own copy: it carries the record of what the intake did
-    args.intake_report = IntakeReport(resampled, nonfinite=found.get('nonfinite', 0), lowpass=bool(found.get('lowpass')))
+    args.evaluation_record = (resampled, found)          # (for _predict_volume's report: IntakeReport.add_evaluation)
     from . import ops
     from .driver import effective_prec_plan
     plan = effective_prec_plan(args)
@@ -383,58 +383,26 @@ def _needed_inputs(args):
 
 
 def load_eval_inputs(args):
-    """--gt_volume / --eval_mask -> None, or (raw GT volume, label volume or None) once the files have been read and their shapes
-    checked against the first input volume and the slab (volume_metrics.check_shapes).  A bad evaluation input raises ValueError
-    here, so that it cannot cost a sampling run.  With --regrid a ground truth or a label volume on another grid is first resampled
-    onto the first input's (mudiff_hip.volume_regrid: trilinear, or cubic under --regrid_interp cubic / nearest neighbour).  With
-    --reorient the grid they are checked against is the first input's once reoriented (its plan's shape, affine and header: no voxel of
-    it is moved for that), and each evaluation input is reoriented by its own affine to the same target first.  With --conform the grid
-    is the conform grid of that first input (volume_conform.conform_grid: again no voxel of it is moved) and the evaluation inputs are
-    resampled onto it as under --regrid; with --antialias the ground truth is low-passed where that downsamples it."""
+    """--gt_volume / --eval_mask -> None, or (raw GT volume, label volume or None) once the files have been read and put on the grid the
+    prediction will have and their shapes checked against it and the slab (volume_prepare.evaluation_inputs says which grid that is
+    under which flags; volume_metrics.check_shapes).  A bad evaluation input raises ValueError here, so that it cannot cost a sampling
+    run."""
     return _load_eval_inputs(args)[0]
 
 
-def _load_eval_inputs(args, found=None):
-    """load_eval_inputs -> (its result, the names of the evaluation inputs --regrid resampled); `found`: volume_regrid.eval_onto_grid's."""
+def _load_eval_inputs(args):
+    """load_eval_inputs -> (its result, the names of the evaluation inputs that were resampled, volume_regrid.eval_onto_grid's `found`)."""
     if args.gt_volume is None:
         if args.eval_mask is not None:
             raise ValueError('--eval_mask needs --gt_volume')
-        return None, []
-    from . import volume_intake as VI
-    from .volume_metrics import eval_inputs_on_grid
+        return None, [], {}
+    from . import volume_prepare as VP
     _, first = _needed_inputs(args)[0]
-    device = torch.device(f'cuda:{args.gpu_chose}')
-    from .volume_prepare import IntakeOptions
-    options = IntakeOptions.from_args(args)
-    regrid = bool(args.regrid) or options.conform is not None
-    if getattr(args, 'reorient', False):
-        from . import volume_reorient as VO
-        target = VO.check_target(getattr(args, 'reorient_to', None) or VO.DEFAULT_TARGET)
-        ref = VO.reference_of(VI.read_nifti_raw(first), target)[0]
-        gt, label, gt_aff = VO.eval_inputs(VI.read_nifti_raw(args.gt_volume), None if args.eval_mask is None else VI.read_nifti_raw(args.eval_mask),
-                                           device, target, as_arrays=not regrid)
-    elif regrid:
-        inp = VI.read_nifti_raw(first)
-        ref = (inp.shape, inp.affine, inp.header)
-        gt = VI.read_nifti_raw(args.gt_volume)
-        gt_aff = gt.affine
-        label = None if args.eval_mask is None else VI.read_nifti_raw(args.eval_mask)
-    else:
-        inp, inp_aff, inp_hdr = read_nifti(first)
-        ref = (inp.shape, inp_aff, inp_hdr)
-        gt, gt_aff, _ = read_nifti(args.gt_volume)
-        label = None if args.eval_mask is None else read_nifti(args.eval_mask)[0]
-    more = {}
-    if options.conform is not None:
-        from . import volume_conform as VCF
-        ref = VCF.reference_of(ref, options.conform)
-    if options.antialias:
-        more = dict(antialias=True)
-        found = {} if found is None else found
-    return eval_inputs_on_grid(ref, gt, label, gt_aff, regrid, args.slice_half_range, device,
-                               names=(first, args.gt_volume),
-                               wording=lambda e: f'--gt_volume / --eval_mask: {e} (the prediction has the shape of {first})',
-                               interp=getattr(args, 'regrid_interp', 'linear'), found=found, **more)
+    options = VP.IntakeOptions.from_args(args)
+    read = lambda path: VP.read_for_evaluation(path, options)      # noqa: E731
+    return VP.evaluation_inputs(read(first), read(args.gt_volume), read(args.eval_mask), options, torch.device(f'cuda:{args.gpu_chose}'),
+                                names=(first, args.gt_volume),
+                                wording=lambda e: f'--gt_volume / --eval_mask: {e} (the prediction has the shape of {first})')
 
 
 def _score_prediction(args, evaluation, vol, std_vol, device):
@@ -465,22 +433,14 @@ def _predict_volume(args, plan, evaluation=None):
     device = torch.device(f'cuda:{args.gpu_chose}')
     gen1, gen2 = load_generators(args, device)
     from . import volume_intake as VI
-    from .volume_prepare import IntakeOptions, prepare_inputs
+    from .volume_prepare import IntakeOptions, output_writer, prepare_inputs
     options = IntakeOptions.from_args(args)
     needed = _needed_inputs(args)
     raws = [VI.read_nifti_raw(path) for _, path in needed]
     prepared, ref, report = prepare_inputs([(m, raw) for (m, _), raw in zip(needed, raws)], options, device,
                                            labels=dict(needed) if args.device_intake else None)      # (the device path names the file)
-    write = None
-    if options.reorient is not None and getattr(args, 'reorient_back', False):
-        from . import volume_reorient as VO
-        write = VO.write_back(write_nifti, raws[0], **options.reorient)
-    if options.conform is not None and getattr(args, 'conform_back', False):
-        from . import volume_conform as VCF
-        write = VCF.write_back(write or write_nifti, VCF.first_on_own_grid(raws[0], options), ref[0], ref[1], device, options.interp, options.antialias)
-    report.regridded += _intake_report(args).regridded       # the inputs first, then the evaluation inputs predict_volume resampled
-    report.nonfinite += _intake_report(args).nonfinite
-    report.lowpass = report.lowpass or _intake_report(args).lowpass
+    write = output_writer(write_nifti, raws[0], options, ref, device, getattr(args, 'reorient_back', False), getattr(args, 'conform_back', False))
+    report.add_evaluation(*getattr(args, 'evaluation_record', ([], {})))      # the inputs first, then what predict_volume resampled
     args.intake_report = report
     if args.device_intake:
         stacks = [VI.condition_from_raw(vol, options.half_range, args.image_size, device, name=path, norm=options.norm)
@@ -492,7 +452,7 @@ def _predict_volume(args, plan, evaluation=None):
 
 def host_stacks(prepared, options):
     """The host's normalisation of volume_prepare.prepare_inputs' volumes -> one [n,X,Y] condition stack each.  An untouched file gives
-    the float64 array read_nifti returns; a volume --regrid, --bias_correct, --denoise or --foreground made on the device is downloaded as the fp32 it is."""
+    the float64 array read_nifti returns; a volume that a stage made on the device is downloaded as the fp32 it is."""
     from .volume_regrid import RegriddedVolume
     stacks = []
     for vol in prepared:
@@ -689,117 +649,9 @@ def make_parser(prog='MU-Diff volume prediction (MI355X)'):
                    help="how the input volumes (and --gt_volume) are mapped to [-1, 1]: 'percentile' = 1st / 99th percentile min-max "
                         "(the reference's volume entry point); 'zscore' = z-score over the non-zero voxels, clamped to +-3 sigma and "
                         "divided by 3 (what the reference's training and 2D test data see: use it with such a checkpoint)")
-    p.add_argument('--regrid', action='store_true',
-                   help='accept inputs (and --gt_volume / --eval_mask) on other voxel grids: each volume that is not on the first '
-                        "input's grid (shape and affine) is resampled onto it on the GPU through the affines before normalisation, "
-                        'trilinearly (the label volume: nearest neighbour).  Resampling only: the volumes must already share one '
-                        'world space (mudiff_hip.volume_regrid)')
-    p.add_argument('--regrid_interp', type=str, default='linear', choices=['linear', 'cubic'],
-                   help="how --regrid / --coregister resample an input (and --regrid the --gt_volume): 'linear' = trilinearly, which "
-                        "softens the volume by an amount that depends on the sub-voxel offset; 'cubic' = with a cubic B-spline "
-                        '(recursive prefilter + 4 x 4 x 4 gather on the GPU: mudiff_hip.volume_regrid), which keeps the sharpness of the '
-                        'first input; zero background stays exactly zero.  The label volume stays nearest neighbour and the registration '
-                        'search trilinear')
-    p.add_argument('--coregister', action='store_true',
-                   help='rigidly align every input other than the first to the first input (six parameters, normalised mutual '
-                        'information, histogram on the GPU: mudiff_hip.volume_coreg), then resample it onto the first input\'s grid '
-                        'as --regrid does; coreg_<t>.json next to the prediction holds what was found.  --gt_volume / --eval_mask are '
-                        'not registered')
-    p.add_argument('--coregister_strides', nargs='+', type=int, default=[4, 2, 1],
-                   help='sampling strides of the coarse-to-fine search levels')
-    p.add_argument('--coregister_max_mm', type=float, default=20.0, help='largest translation per axis the search may propose')
-    p.add_argument('--coregister_max_deg', type=float, default=15.0, help='largest rotation per axis the search may propose')
-    p.add_argument('--bias_correct', action='store_true',
-                   help='divide every input by an estimate of its coil-shading (bias) field before it is normalised: an N4-style '
-                        'correction on the GPU (histogram sharpening + multilevel B-spline fit of the log image: '
-                        'mudiff_hip.volume_bias), after --regrid / --coregister; bias_<t>.json next to the prediction holds what was '
-                        'found.  --gt_volume / --eval_mask are not corrected')
-    p.add_argument('--bias_shrink', type=int, default=4, help='the field is estimated from every N-th voxel per axis')
-    p.add_argument('--bias_levels', type=int, default=4, help='B-spline levels: level l has 2^l spans per axis (1 to 5)')
-    p.add_argument('--bias_iters', type=int, default=50, help='most iterations per level')
-    p.add_argument('--bias_tol', type=float, default=1e-3, help='a level ends when no sample of the corrected log image moved by more')
-    p.add_argument('--bias_bins', type=int, default=200, help='bins of the log-intensity histogram (2 to 1024)')
-    p.add_argument('--bias_fwhm', type=float, default=0.15, help='FWHM, in log units, of the Gaussian the histogram is deconvolved by')
-    p.add_argument('--bias_wiener', type=float, default=0.01, help='noise term of the Wiener deconvolution filter')
-    p.add_argument('--bias_field_out', action='store_true',
-                   help='with --bias_correct: also write bias_field_<name>_<t>.nii.gz, exp(field) of each input on the output grid')
-    p.add_argument('--denoise', action='store_true',
-                   help='replace every input by its 3D non-local-means estimate on its own grid (patch-similarity weighted mean over a '
-                        'search window, on the GPU: mudiff_hip.volume_denoise) before --coregister / --regrid / --bias_correct see it; '
-                        'denoise_<t>.json next to the prediction holds the noise level that was used.  --gt_volume / --eval_mask are '
-                        'not denoised')
-    p.add_argument('--denoise_sigma', type=float, default=None,
-                   help='the noise standard deviation, in stored intensity units (default: estimated per input from pseudo-residuals)')
-    p.add_argument('--denoise_search', type=int, default=2, help='search radius: candidates within this many voxels per axis (1 to 5)')
-    p.add_argument('--denoise_patch', type=int, default=1, help='patch radius: patches of (2 r + 1)^3 voxels are compared (1 to 2)')
-    p.add_argument('--denoise_beta', type=float, default=1.0, help='smoothing strength: the weights fall off with 2 beta sigma^2')
-    p.add_argument('--denoise_rician', action='store_true',
-                   help='with --denoise: average squared intensities and subtract the Rician bias 2 sigma^2 (magnitude images)')
-    p.add_argument('--foreground', action='store_true',
-                   help='set the voxels outside a foreground mask of every input to exactly 0, on its own grid, after --denoise and before '
-                        '--coregister / --regrid / --bias_correct see it (Otsu threshold, largest 6-connected component, holes filled, on '
-                        'the GPU: mudiff_hip.volume_foreground); foreground_<t>.json next to the prediction holds what was found.  This is '
-                        'a head / object mask by thresholding and topology, NOT a brain extraction: the skull stays (see --brain_extract).  '
-                        '--gt_volume / --eval_mask are not masked')
-    p.add_argument('--foreground_bins', type=int, default=256, help='bins of the histogram the Otsu threshold is taken from (16 to 1024)')
-    p.add_argument('--foreground_open', type=int, default=0,
-                   help='open the thresholded mask first: this many erosions, then as many dilations, over the 6-neighbourhood (0 to 3)')
-    p.add_argument('--foreground_keep_holes', action='store_true', help='with --foreground: do not fill the holes of the kept component')
-    p.add_argument('--foreground_mask_out', action='store_true',
-                   help='with --foreground: also write foreground_<t>_<name>.nii.gz, the uint8 mask of each input on its own grid')
-    p.add_argument('--brain_extract', action='store_true',
-                   help='estimate one brain mask per subject and set the voxels of every input outside it to exactly 0, once the inputs '
-                        'are on the common grid (after --coregister / --regrid) and before --bias_correct and the normalisation see '
-                        'them: the tissue mask of --foreground, eroded by --brain_erode_mm so that the bridges between brain and scalp '
-                        'break, its largest component grown back by --brain_dilate_mm inside the tissue, holes filled (exact Euclidean '
-                        'distance transform with the voxel spacing, on the GPU: mudiff_hip.volume_brain); brain_<t>.json next to the '
-                        'prediction holds what was found.  This is a morphological estimate, not a learned brain extraction.  '
-                        '--gt_volume / --eval_mask are not masked')
-    p.add_argument('--brain_from', type=str, default=None,
-                   help='the input the mask is estimated from (T1, T1CE, T2 or FLAIR; default: T1, else T1CE, else the first input)')
-    p.add_argument('--brain_erode_mm', type=float, default=5.0, help='erosion radius in millimetres (finite, > 0)')
-    p.add_argument('--brain_dilate_mm', type=float, default=6.0,
-                   help='how far the eroded core grows back, in millimetres, inside the thresholded tissue (not below --brain_erode_mm)')
-    p.add_argument('--brain_bins', type=int, default=256, help='bins of the histogram the Otsu threshold is taken from (16 to 1024)')
-    p.add_argument('--brain_keep_holes', action='store_true', help='with --brain_extract: do not fill the holes of the mask')
-    p.add_argument('--brain_mask_out', action='store_true',
-                   help='with --brain_extract: also write brain_<t>_mask.nii.gz, the uint8 mask on the grid of the first input')
-    p.add_argument('--reorient', action='store_true',
-                   help='bring every input (and --gt_volume / --eval_mask), each by its own affine, to the storage orientation the '
-                        'checkpoints were trained on before anything else sees it: a permutation and flips of the storage axes on the GPU '
-                        '(mudiff_hip.volume_reorient), exact, datatype and scaling kept, the affine changed to match.  The slab is then '
-                        'cut along the third axis of that orientation and everything is written on the reoriented grid; '
-                        'reorient_<t>.json next to the prediction holds what was done.  A permutation cannot make tilted slices axial: an '
-                        'input whose axes are tilted by more than 10 degrees (an untuned default, not a measured bar) gets a warning, and '
-                        'de-obliquing by resampling is not done')
-    p.add_argument('--reorient_to', type=str, default=None, metavar='CODE',
-                   help="the target orientation of --reorient, one letter of each of R/L, A/P, S/I: the direction every storage axis runs "
-                        "towards.  'LPS' is how BraTS stores its volumes, which the reference reads without reorienting; a checkpoint "
-                        'trained on data stored otherwise needs its own code.  Default: LPS, or under --conform what --conform_to says')
-    p.add_argument('--reorient_back', action='store_true',
-                   help="with --reorient: write predicted_<t>.nii.gz (and predicted_<t>_std.nii.gz) in the first input's own storage order, "
-                        'with its original affine and header (scored first, on the reoriented grid)')
-    p.add_argument('--conform', action='store_true',
-                   help='resample every input, the first included, once onto one axis-aligned grid of the training geometry (240 x 240 x 155 '
-                        "voxels of 1 mm, stored LPS: BraTS), placed so that its centre lies on the centre of the first input's grid "
-                        '(mudiff_hip.volume_conform): another voxel size or field of view reaches the generators at the scale they were '
-                        'trained on and a tilted acquisition is de-obliqued.  Implies the resampling of --regrid for the inputs and for '
-                        '--gt_volume / --eval_mask; everything is sampled, scored and written on that grid; conform_<t>.json next to the '
-                        'prediction holds what was done')
-    p.add_argument('--conform_shape', nargs=3, type=int, default=[240, 240, 155], metavar=('X', 'Y', 'Z'), help='the voxels of the conform grid')
-    p.add_argument('--conform_spacing', nargs='+', type=float, default=[1.0], metavar='MM',
-                   help='the voxel size of the conform grid in mm: one value, or three (one per axis)')
-    p.add_argument('--conform_to', type=str, default='LPS', metavar='CODE',
-                   help='the orientation of the conform grid (as --reorient_to: the direction every storage axis runs towards)')
-    p.add_argument('--conform_back', action='store_true',
-                   help="with --conform: write predicted_<t>.nii.gz (and predicted_<t>_std.nii.gz) resampled onto the first input's own grid "
-                        '(by --regrid_interp), with its affine and header (scored first, on the conform grid)')
-    p.add_argument('--antialias', type=str, default=None, choices=['on', 'off'],
-                   help='low-pass a volume on the GPU before a resampling that downsamples it (--conform, --regrid, --coregister; the '
-                        '--gt_volume too, never the --eval_mask): a separable Gaussian per source axis whose FWHM, added in quadrature to '
-                        'the source voxel, gives the target voxel, sigma = sqrt(f^2 - 1) / 2.355 source voxels for a sampling factor f > 1 '
-                        '(an untuned default, not a measured optimum); an axis that is not downsampled is not filtered, and a resampling '
-                        "that downsamples nothing is bit for bit what it is without the flag.  Default: 'on' under --conform, else 'off'")
+    from .volume_prepare import STAGES
+    for stage in STAGES:                    # (each input stage's own flags: <module>.add_flags)
+        stage.module.add_flags(p)
     from .driver import add_calibration_flags
     add_calibration_flags(p)                # (also --prec_plan)
     return p
@@ -813,67 +665,30 @@ def finish_args(p, args):
         p.error(f'--num_samples must be >= 2 (got {args.num_samples})')
     if args.num_samples is not None and not 0 <= args.seed < 1 << 64:
         p.error('--num_samples needs a --seed in [0, 2^64)')
-    if min(args.coregister_strides) < 1 or args.coregister_max_mm < 0 or args.coregister_max_deg < 0:
-        p.error('--coregister_strides must be positive, --coregister_max_mm / --coregister_max_deg not negative')
-    from .volume_bias import check_options
-    try:
-        check_options(args.bias_shrink, args.bias_levels, args.bias_iters, args.bias_tol, args.bias_bins, args.bias_fwhm, args.bias_wiener)
-    except ValueError as e:
-        p.error(str(e))
-    if args.bias_field_out and not args.bias_correct:
-        p.error('--bias_field_out needs --bias_correct')
-    from .volume_denoise import check_options as check_denoise
-    try:
-        check_denoise(args.denoise_sigma, args.denoise_search, args.denoise_patch, args.denoise_beta, args.denoise_rician)
-    except ValueError as e:
-        p.error(str(e))
-    from .volume_foreground import check_options as check_foreground
-    try:
-        check_foreground(args.foreground_bins, args.foreground_open, args.foreground_keep_holes, args.foreground_mask_out)
-    except ValueError as e:
-        p.error(str(e))
-    from .volume_brain import check_options as check_brain
-    try:
-        check_brain(args.brain_bins, args.brain_erode_mm, args.brain_dilate_mm, args.brain_keep_holes)
-    except ValueError as e:
-        p.error(str(e))
-    from .volume_reorient import DEFAULT_TARGET, check_target
-    try:
-        args.conform_to = check_target(args.conform_to)
-        if args.reorient_to is None:                     # not given: it follows --conform_to under --conform
-            args.reorient_to = args.conform_to if args.conform else DEFAULT_TARGET
-        args.reorient_to = check_target(args.reorient_to)
-    except ValueError as e:
-        p.error(str(e))
-    if args.reorient_back and not args.reorient:
-        p.error('--reorient_back needs --reorient')
     from . import volume_conform as VCF
-    try:
-        args.conform_shape = list(VCF._shape3(args.conform_shape, '--conform_shape'))
-        args.conform_spacing = list(VCF._spacing3(args.conform_spacing))
-    except ValueError as e:
-        p.error(str(e))
-    if args.conform_back and not args.conform:
-        p.error('--conform_back needs --conform')
+    from . import volume_reorient as VO
+    from .volume_prepare import STAGES
+    if args.reorient_to is None and args.conform:        # not given: it follows --conform_to under --conform
+        args.reorient_to = args.conform_to
+    for stage in STAGES:
+        try:
+            stage.module.options_from(args)              # (a stage's checks: its ValueError names the flag)
+        except ValueError as e:
+            p.error(str(e))
+    # the namespace keeps the checked spelling: upper-case codes, the default filled in, three integers, three spacings
+    args.conform_to, args.reorient_to = VO.check_target(args.conform_to), VO.check_target(args.reorient_to or VO.DEFAULT_TARGET)
+    args.conform_shape, args.conform_spacing = list(VCF._shape3(args.conform_shape)), list(VCF._spacing3(args.conform_spacing))
     if args.conform and args.reorient and args.conform_to != args.reorient_to:
         p.error(f'--conform_to {args.conform_to} differs from --reorient_to {args.reorient_to}: give both the same code')
     return args
 
 
 def build_argparser(argv=None):
-    """Flags and defaults of the reference parser (:302-357; like it, returns the PARSED namespace), plus --centered (which
-    the generators read and the reference parser forgot), --batch_size, --resize_back, --calibrate / --calibrate_threshold
-    (mudiff_hip.precision; the record goes to <output_dir>/prec_calibration.json), --num_samples (ensembles), --gt_volume /
-    --eval_mask (scoring of the written prediction, mudiff_hip.volume_metrics), --device_intake (mudiff_hip.volume_intake), --norm
-    (the training normalisation), --regrid (inputs on other voxel grids; --regrid_interp:
-    trilinear or cubic B-spline resampling),
-    --coregister (rigid alignment of the inputs to the first one), --bias_correct (removal of the coil
-    shading of every input), --denoise (non-local-means denoising of every input) and
-    --foreground (a foreground mask of every input: everything outside becomes 0) and --brain_extract (one
-    morphological brain mask per subject, applied to every input) and --reorient / --reorient_to / --reorient_back
-    (the inputs brought to the training orientation) and --conform / --conform_shape / --conform_spacing /
-    --conform_to / --conform_back / --antialias (the inputs resampled onto the training grid behind an anti-aliasing low-pass, DESIGN.md
-    section 5.21)."""
+    """Flags and defaults of the reference parser (:302-357; like it, returns the PARSED namespace), plus --centered (which the
+    generators read and the reference parser forgot) and this build's own: the pipeline-wide ones make_parser adds after the
+    reference's (their help texts say what they do and name their modules), --calibrate / --calibrate_threshold / --prec_plan
+    (mudiff_hip.driver), and the flags of every input stage, each added and checked by the stage's own module (volume_prepare.STAGES;
+    DESIGN.md sections 5.12 - 5.21)."""
     p = make_parser()
     return finish_args(p, p.parse_args(argv))
 

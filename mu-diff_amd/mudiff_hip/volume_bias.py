@@ -15,14 +15,13 @@ iteration.  The sums are integers: two runs give the same bits.
 """
 from __future__ import annotations
 
-import json
 import os
 
 import numpy as np
 import torch
 
 from . import MudiffHipError
-from .volume_intake import DEVICE_DTYPES, upload
+from .volume_intake import DEVICE_DTYPES, upload, write_report_json
 from .volume_regrid import RegriddedVolume
 
 MAX_LEVELS, MAX_BINS, MAX_K = 5, 1024, 44
@@ -194,7 +193,7 @@ def correct(raw, device, shrink=4, levels=4, iters=50, tol=1e-3, bins=200, fwhm=
     if len(raw.shape) != 3:
         raise ValueError(f'bias correction: expected a 3D volume, got shape {tuple(raw.shape)}')
     check_options(shrink, levels, iters, tol, bins, fwhm, wiener)
-    eng = DeviceEngine(upload(raw, device), (raw.code, raw.shape) + raw.scaling, shrink)
+    eng = DeviceEngine(upload(raw, device), raw.kernel_meta('bias correction'), shrink)
     lattices, iterations, dmax = loop(eng, levels, iters, tol, bins, fwhm, wiener)
     eng.corrected(lattices)
     u, c = eng.u.cpu().numpy().astype(np.float64), eng.c[0].cpu().numpy().astype(np.float64)
@@ -213,6 +212,34 @@ def correct(raw, device, shrink=4, levels=4, iters=50, tol=1e-3, bins=200, fwhm=
 # ---------------------------------------------------------------------------------------------------
 # the pipeline's side
 # ---------------------------------------------------------------------------------------------------
+def add_flags(p):
+    p.add_argument('--bias_correct', action='store_true',
+                   help='divide every input by an estimate of its coil-shading (bias) field before it is normalised: an N4-style '
+                        'correction on the GPU (histogram sharpening + multilevel B-spline fit of the log image: '
+                        'mudiff_hip.volume_bias), after --regrid / --coregister; bias_<t>.json next to the prediction holds what was '
+                        'found.  --gt_volume / --eval_mask are not corrected')
+    p.add_argument('--bias_shrink', type=int, default=DEFAULTS['shrink'], help='the field is estimated from every N-th voxel per axis')
+    p.add_argument('--bias_levels', type=int, default=DEFAULTS['levels'], help='B-spline levels: level l has 2^l spans per axis (1 to 5)')
+    p.add_argument('--bias_iters', type=int, default=DEFAULTS['iters'], help='most iterations per level')
+    p.add_argument('--bias_tol', type=float, default=DEFAULTS['tol'], help='a level ends when no sample of the corrected log image moved by more')
+    p.add_argument('--bias_bins', type=int, default=DEFAULTS['bins'], help='bins of the log-intensity histogram (2 to 1024)')
+    p.add_argument('--bias_fwhm', type=float, default=DEFAULTS['fwhm'], help='FWHM, in log units, of the Gaussian the histogram is deconvolved by')
+    p.add_argument('--bias_wiener', type=float, default=DEFAULTS['wiener'], help='noise term of the Wiener deconvolution filter')
+    p.add_argument('--bias_field_out', action='store_true',
+                   help='with --bias_correct: also write bias_field_<name>_<t>.nii.gz, exp(field) of each input on the output grid')
+
+
+def options_from(args):
+    """A namespace's --bias_* flags (any may be missing) -> IntakeOptions' `bias`: the keyword arguments of correct, or None without
+    --bias_correct.  ValueError, naming the flag, for a value check_options refuses and for --bias_field_out on its own."""
+    kw = {k: type(v)(getattr(args, 'bias_' + k, v)) for k, v in DEFAULTS.items()}
+    check_options(**kw)
+    on, field = bool(getattr(args, 'bias_correct', False)), bool(getattr(args, 'bias_field_out', False))
+    if field and not on:
+        raise ValueError('--bias_field_out needs --bias_correct')
+    return dict(bias=dict(kw, field=field) if on else None)
+
+
 def bias_suffix(reports):
     """What a [done] line gains under --bias_correct (nothing otherwise): ` | bias=<name>,<name>,...`."""
     if not reports:
@@ -223,10 +250,7 @@ def bias_suffix(reports):
 def write_reports(reports, output_dir, target, affine=None, header=None):
     """bias_<t>.json next to the prediction: {input name: report}; with --bias_field_out also bias_field_<name>_<t>.nii.gz, exp(F) on
     the output grid.  -> the json's path."""
-    os.makedirs(output_dir, exist_ok=True)
-    path = os.path.join(output_dir, f'bias_{target.lower()}.json')
-    with open(path, 'w') as f:
-        json.dump({r[0]: r[1] for r in reports}, f, indent=1)
+    path = write_report_json('bias', {r[0]: r[1] for r in reports}, output_dir, target)
     for r in reports:
         if len(r) > 2 and r[2] is not None:
             from .volume import write_nifti

@@ -19,14 +19,13 @@ available to tune.  All per-voxel work is the device's; two runs give the same b
 """
 from __future__ import annotations
 
-import json
 import math
 import os
 
 import numpy as np
 
 from . import volume_foreground as VF
-from .volume_intake import upload
+from .volume_intake import upload, write_report_json
 from .volume_regrid import world_affine_of
 
 MIN_BINS, MAX_BINS = VF.MIN_BINS, VF.MAX_BINS
@@ -79,7 +78,7 @@ def brain_mask(vol, device, bins=256, erode_mm=5.0, dilate_mm=6.0, keep_holes=Fa
     check_options(bins, erode_mm, dilate_mm, keep_holes)
     bins, erode_mm, dilate_mm = int(bins), float(erode_mm), float(dilate_mm)
     spacing = spacing_of(vol)
-    dev, meta = upload(vol, device), VF._meta(vol)
+    dev, meta = upload(vol, device), vol.kernel_meta('foreground')
     shape = meta[1]
     report = dict(threshold=None, bin=None, bins=bins, lo=None, hi=None, candidates=0, spacing=list(spacing), erode_mm=erode_mm,
                   dilate_mm=dilate_mm, tissue=0, eroded=0, components=0, core=0, kept=0, filled=0, source=None)
@@ -104,7 +103,7 @@ def brain_mask(vol, device, bins=256, erode_mm=5.0, dilate_mm=6.0, keep_holes=Fa
 def apply_mask(vol, mask, device):
     """The volume with every voxel outside the device mask set to exactly 0: a MaskedVolume with the volume's own geometry."""
     from . import ops
-    out = ops.volume_fg_apply(upload(vol, device), *VF._meta(vol), mask)[0]
+    out = ops.volume_fg_apply(upload(vol, device), *vol.kernel_meta('foreground'), mask)[0]
     return VF.MaskedVolume(out, vol.shape, vol.affine, vol.header)
 
 
@@ -116,6 +115,37 @@ def host_mask(mask):
 # ---------------------------------------------------------------------------------------------------
 # the pipeline's side
 # ---------------------------------------------------------------------------------------------------
+def add_flags(p):
+    p.add_argument('--brain_extract', action='store_true',
+                   help='estimate one brain mask per subject and set the voxels of every input outside it to exactly 0, once the inputs '
+                        'are on the common grid (after --coregister / --regrid) and before --bias_correct and the normalisation see '
+                        'them: the tissue mask of --foreground, eroded by --brain_erode_mm so that the bridges between brain and scalp '
+                        'break, its largest component grown back by --brain_dilate_mm inside the tissue, holes filled (exact Euclidean '
+                        'distance transform with the voxel spacing, on the GPU: mudiff_hip.volume_brain); brain_<t>.json next to the '
+                        'prediction holds what was found.  This is a morphological estimate, not a learned brain extraction.  '
+                        '--gt_volume / --eval_mask are not masked')
+    p.add_argument('--brain_from', type=str, default=None,
+                   help='the input the mask is estimated from (T1, T1CE, T2 or FLAIR; default: T1, else T1CE, else the first input)')
+    p.add_argument('--brain_erode_mm', type=float, default=DEFAULTS['erode_mm'], help='erosion radius in millimetres (finite, > 0)')
+    p.add_argument('--brain_dilate_mm', type=float, default=DEFAULTS['dilate_mm'],
+                   help='how far the eroded core grows back, in millimetres, inside the thresholded tissue (not below --brain_erode_mm)')
+    p.add_argument('--brain_bins', type=int, default=DEFAULTS['bins'], help='bins of the histogram the Otsu threshold is taken from (16 to 1024)')
+    p.add_argument('--brain_keep_holes', action='store_true', help='with --brain_extract: do not fill the holes of the mask')
+    p.add_argument('--brain_mask_out', action='store_true',
+                   help='with --brain_extract: also write brain_<t>_mask.nii.gz, the uint8 mask on the grid of the first input')
+
+
+def options_from(args):
+    """A namespace's --brain_* flags (any may be missing) -> IntakeOptions' `brain`: the keyword arguments of brain_mask plus `source`
+    (--brain_from or None) and `mask_out`, or None without --brain_extract.  ValueError, naming the flag, for a value check_options refuses."""
+    kw = {k: getattr(args, 'brain_' + k, v) for k, v in DEFAULTS.items()}
+    check_options(**kw)
+    source = getattr(args, 'brain_from', None)
+    kw = dict({k: type(v)(kw[k]) for k, v in DEFAULTS.items()}, source=None if source is None else str(source),
+              mask_out=bool(getattr(args, 'brain_mask_out', False)))
+    return dict(brain=kw if getattr(args, 'brain_extract', False) else None)
+
+
 def brain_suffix(reports):
     """What a [done] line gains under --brain_extract (nothing otherwise): ` | brain=<source>`."""
     if not reports:
@@ -127,10 +157,7 @@ def write_reports(reports, output_dir, target, affine=None, header=None):
     """brain_<t>.json next to the prediction: the report of the subject's mask; with --brain_mask_out also brain_<t>_mask.nii.gz, the
     uint8 mask on the common grid (affine / header: that grid's).  reports: [(source name, report, host mask or None)].  -> the json's
     path."""
-    os.makedirs(output_dir, exist_ok=True)
-    path = os.path.join(output_dir, f'brain_{target.lower()}.json')
-    with open(path, 'w') as f:
-        json.dump(reports[0][1], f, indent=1)
+    path = write_report_json('brain', reports[0][1], output_dir, target)
     mask = reports[0][2] if len(reports[0]) > 2 else None
     if mask is not None:
         VF.write_mask(os.path.join(output_dir, f'brain_{target.lower()}_mask.nii.gz'), mask, np.eye(4) if affine is None else affine, header)

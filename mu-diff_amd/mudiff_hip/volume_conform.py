@@ -26,13 +26,13 @@ conform_suffix, antialias_suffix, write_reports.  On the device: lowpass (ops.vo
 """
 from __future__ import annotations
 
-import json
 import math
 import os
 import struct
 
 import numpy as np
 
+from .volume_intake import write_report_json
 from .volume_reorient import DEFAULT_TARGET, NEGATIVE, POSITIVE, check_target, obliquity_deg
 
 DEFAULT_SHAPE = (240, 240, 155)                          # BraTS
@@ -172,6 +172,44 @@ def lowpass(dev_raw, code, shape, slope, inter, M, name='the volume'):
 # ---------------------------------------------------------------------------------------------------
 # the pipeline's side
 # ---------------------------------------------------------------------------------------------------
+def add_flags(p):
+    p.add_argument('--conform', action='store_true',
+                   help='resample every input, the first included, once onto one axis-aligned grid of the training geometry (240 x 240 x 155 '
+                        "voxels of 1 mm, stored LPS: BraTS), placed so that its centre lies on the centre of the first input's grid "
+                        '(mudiff_hip.volume_conform): another voxel size or field of view reaches the generators at the scale they were '
+                        'trained on and a tilted acquisition is de-obliqued.  Implies the resampling of --regrid for the inputs and for '
+                        '--gt_volume / --eval_mask; everything is sampled, scored and written on that grid; conform_<t>.json next to the '
+                        'prediction holds what was done')
+    p.add_argument('--conform_shape', nargs=3, type=int, default=list(DEFAULT_SHAPE), metavar=('X', 'Y', 'Z'), help='the voxels of the conform grid')
+    p.add_argument('--conform_spacing', nargs='+', type=float, default=list(DEFAULT_SPACING[:1]), metavar='MM',
+                   help='the voxel size of the conform grid in mm: one value, or three (one per axis)')
+    p.add_argument('--conform_to', type=str, default=DEFAULT_TARGET, metavar='CODE',
+                   help='the orientation of the conform grid (as --reorient_to: the direction every storage axis runs towards)')
+    p.add_argument('--conform_back', action='store_true',
+                   help="with --conform: write predicted_<t>.nii.gz (and predicted_<t>_std.nii.gz) resampled onto the first input's own grid "
+                        '(by --regrid_interp), with its affine and header (scored first, on the conform grid)')
+    p.add_argument('--antialias', type=str, default=None, choices=['on', 'off'],
+                   help='low-pass a volume on the GPU before a resampling that downsamples it (--conform, --regrid, --coregister; the '
+                        '--gt_volume too, never the --eval_mask): a separable Gaussian per source axis whose FWHM, added in quadrature to '
+                        'the source voxel, gives the target voxel, sigma = sqrt(f^2 - 1) / 2.355 source voxels for a sampling factor f > 1 '
+                        '(an untuned default, not a measured optimum); an axis that is not downsampled is not filtered, and a resampling '
+                        "that downsamples nothing is bit for bit what it is without the flag.  Default: 'on' under --conform, else 'off'")
+
+
+def options_from(args):
+    """A namespace's --conform flags and --antialias (any may be missing) -> IntakeOptions' `conform`: the keyword arguments of
+    conform_grid, or None without --conform; and `antialias`: --antialias as a bool, on by default under --conform and off otherwise.
+    ValueError, naming the flag, for a bad shape, spacing or code and for --conform_back on its own."""
+    spacing = getattr(args, 'conform_spacing', None)
+    grid = dict(shape=_shape3(getattr(args, 'conform_shape', None) or DEFAULT_SHAPE, '--conform_shape'),
+                spacing=_spacing3(DEFAULT_SPACING if spacing is None else spacing), target=check_target(getattr(args, 'conform_to', DEFAULT_TARGET)))
+    on = bool(getattr(args, 'conform', False))
+    if getattr(args, 'conform_back', False) and not on:
+        raise ValueError('--conform_back needs --conform')
+    antialias = getattr(args, 'antialias', None)
+    return dict(conform=grid if on else None, antialias=on if antialias is None else antialias in (True, 'on'))
+
+
 def entry(raw, M, resampled, nonfinite=0, antialias=True):
     """What conform_<t>.json holds for one input: where it came from, what the sampling matrix M covers per source axis and what the
     anti-aliasing rule made of it (sigmas and radii all 0 with `antialias` off)."""
@@ -226,11 +264,7 @@ def antialias_suffix(ran):
 
 def write_reports(entries, output_dir, target, grid=None):
     """conform_<t>.json next to the prediction: {'grid': name, 'inputs': {input name: entry}}.  -> its path."""
-    os.makedirs(output_dir, exist_ok=True)
-    path = os.path.join(output_dir, f'conform_{target.lower()}.json')
-    with open(path, 'w') as f:
-        json.dump({'grid': grid, 'inputs': {name: e for name, e in entries}}, f, indent=1)
-    return path
+    return write_report_json('conform', {'grid': grid, 'inputs': {name: e for name, e in entries}}, output_dir, target)
 
 
 def write_back(write, first_raw, grid_shape, grid_affine, device, interp='linear', antialias=True):

@@ -14,18 +14,18 @@ histogram is the device's work (one launch and a copy of bins^2 counts per evalu
 from __future__ import annotations
 
 import ctypes as C
-import json
 import warnings
 
 import numpy as np
 import torch
 
 from . import MudiffHipError, load, ptr, require_gpu
-from .volume_intake import DEVICE_DTYPES, upload
+from .volume_intake import DEVICE_DTYPES, upload, write_report_json
 from .volume_regrid import _affine44, grid_matrix, world_affine_of
 
 PARAM_NAMES = ('tx_mm', 'ty_mm', 'tz_mm', 'rx_deg', 'ry_deg', 'rz_deg')
 MAX_BINS = 64
+DEFAULTS = dict(strides=(4, 2, 1), max_mm=20.0, max_deg=15.0)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -283,7 +283,7 @@ def coregister(fixed_raw, moving_raw, device, strides=(4, 2, 1), bins=32, max_mm
     a_fix, a_mov = world_affine_of(fixed_raw.affine, fixed_raw.header), world_affine_of(moving_raw.affine, moving_raw.header)
     centre = grid_centre(fixed_raw.shape, a_fix)
     ranges = bin_ranges(fixed_raw, moving_raw, bins)
-    metas = [(r.code, r.shape) + r.scaling for r in (fixed_raw, moving_raw)]
+    metas = [r.kernel_meta('joint_hist') for r in (fixed_raw, moving_raw)]
     fix_dev, mov_dev = upload(fixed_raw, device), upload(moving_raw, device)
 
     def cost_at(params, stride):
@@ -311,6 +311,29 @@ def finish(cost_at, centre, strides, bins, max_mm, max_deg):
 # ---------------------------------------------------------------------------------------------------
 # the pipeline's side
 # ---------------------------------------------------------------------------------------------------
+def add_flags(p):
+    p.add_argument('--coregister', action='store_true',
+                   help='rigidly align every input other than the first to the first input (six parameters, normalised mutual '
+                        'information, histogram on the GPU: mudiff_hip.volume_coreg), then resample it onto the first input\'s grid '
+                        'as --regrid does; coreg_<t>.json next to the prediction holds what was found.  --gt_volume / --eval_mask are '
+                        'not registered')
+    p.add_argument('--coregister_strides', nargs='+', type=int, default=list(DEFAULTS['strides']),
+                   help='sampling strides of the coarse-to-fine search levels')
+    p.add_argument('--coregister_max_mm', type=float, default=DEFAULTS['max_mm'], help='largest translation per axis the search may propose')
+    p.add_argument('--coregister_max_deg', type=float, default=DEFAULTS['max_deg'], help='largest rotation per axis the search may propose')
+
+
+def options_from(args):
+    """A namespace's --coregister flags (any may be missing) -> IntakeOptions' `coreg`: the keyword arguments of coregister, or None
+    without --coregister.  ValueError, naming the flags, for values the search cannot run with."""
+    get = lambda name: getattr(args, 'coregister_' + name, None)      # noqa: E731
+    kw = dict(strides=tuple(int(s) for s in get('strides') or DEFAULTS['strides']),
+              **{k: float(DEFAULTS[k] if get(k) is None else get(k)) for k in ('max_mm', 'max_deg')})
+    if min(kw['strides']) < 1 or kw['max_mm'] < 0 or kw['max_deg'] < 0:
+        raise ValueError('--coregister_strides must be positive, --coregister_max_mm / --coregister_max_deg not negative')
+    return dict(coreg=kw if getattr(args, 'coregister', False) else None)
+
+
 def coreg_suffix(reports):
     """What a [done] line gains under --coregister (nothing otherwise): ` | coreg=<name>:<mm>mm/<deg>deg,...`, the lengths of the
     translation and of the rotation vector of each registered input."""
@@ -325,9 +348,4 @@ def coreg_suffix(reports):
 
 def write_reports(reports, output_dir, target):
     """coreg_<t>.json next to the prediction: {input name: report}.  -> its path."""
-    import os
-    os.makedirs(output_dir, exist_ok=True)
-    path = os.path.join(output_dir, f'coreg_{target.lower()}.json')
-    with open(path, 'w') as f:
-        json.dump({name: rep for name, rep in reports}, f, indent=1)
-    return path
+    return write_report_json('coreg', {name: rep for name, rep in reports}, output_dir, target)

@@ -14,13 +14,10 @@ two runs give the same bits.
 """
 from __future__ import annotations
 
-import json
-import os
-
 import numpy as np
 
 from . import MudiffHipError
-from .volume_intake import DEVICE_DTYPES, upload
+from .volume_intake import upload, write_report_json
 from .volume_regrid import RegriddedVolume
 
 MAX_SEARCH, MAX_PATCH = 5, 2
@@ -72,19 +69,13 @@ def sigma_of_key(key):
     return MAD_TO_SIGMA * float(np.array([int(key)], np.uint32).view(np.float32)[0])
 
 
-def _meta(raw):
-    if int(raw.code) not in DEVICE_DTYPES:
-        raise MudiffHipError(f'denoise: unsupported NIfTI datatype code {raw.code}')
-    return (int(raw.code), tuple(int(v) for v in raw.shape)) + tuple(float(v) for v in raw.scaling)
-
-
 def estimate_sigma(raw, device, dev=None):
     """The noise level of a RawVolume from its pseudo-residuals -> (sigma, samples): 1.4826 x the lower median of |eps| over the voxels
     that are > 0 with six face neighbours inside the volume, valid and > 0; (0.0, 0) without such a voxel."""
     from . import ops
     if len(raw.shape) != 3:
         raise ValueError(f'denoise: expected a 3D volume, got shape {tuple(raw.shape)}')
-    keys = ops.volume_denoise_residual(upload(raw, device) if dev is None else dev, *_meta(raw))
+    keys = ops.volume_denoise_residual(upload(raw, device) if dev is None else dev, *raw.kernel_meta('denoise'))
     key, n = select_lower_median(lambda prefix, which: ops.volume_denoise_select_hist(keys, prefix, which).cpu().numpy().view(np.uint32))
     return (0.0, 0) if key is None else (sigma_of_key(key), n)
 
@@ -97,7 +88,7 @@ def denoise(raw, device, sigma=None, search=2, patch=1, beta=1.0, rician=False):
     if len(raw.shape) != 3:
         raise ValueError(f'denoise: expected a 3D volume, got shape {tuple(raw.shape)}')
     check_options(sigma, search, patch, beta, rician)
-    dev, meta = upload(raw, device), _meta(raw)
+    dev, meta = upload(raw, device), raw.kernel_meta('denoise')
     report = dict(sigma=0.0, estimated=sigma is None, samples=0, zeroed=0, search=int(search), patch=int(patch), beta=float(beta),
                   rician=bool(rician))
     if sigma is None:
@@ -113,6 +104,31 @@ def denoise(raw, device, sigma=None, search=2, patch=1, beta=1.0, rician=False):
 # ---------------------------------------------------------------------------------------------------
 # the pipeline's side
 # ---------------------------------------------------------------------------------------------------
+def add_flags(p):
+    p.add_argument('--denoise', action='store_true',
+                   help='replace every input by its 3D non-local-means estimate on its own grid (patch-similarity weighted mean over a '
+                        'search window, on the GPU: mudiff_hip.volume_denoise) before --coregister / --regrid / --bias_correct see it; '
+                        'denoise_<t>.json next to the prediction holds the noise level that was used.  --gt_volume / --eval_mask are '
+                        'not denoised')
+    p.add_argument('--denoise_sigma', type=float, default=DEFAULTS['sigma'],
+                   help='the noise standard deviation, in stored intensity units (default: estimated per input from pseudo-residuals)')
+    p.add_argument('--denoise_search', type=int, default=DEFAULTS['search'], help='search radius: candidates within this many voxels per axis (1 to 5)')
+    p.add_argument('--denoise_patch', type=int, default=DEFAULTS['patch'], help='patch radius: patches of (2 r + 1)^3 voxels are compared (1 to 2)')
+    p.add_argument('--denoise_beta', type=float, default=DEFAULTS['beta'], help='smoothing strength: the weights fall off with 2 beta sigma^2')
+    p.add_argument('--denoise_rician', action='store_true',
+                   help='with --denoise: average squared intensities and subtract the Rician bias 2 sigma^2 (magnitude images)')
+
+
+def options_from(args):
+    """A namespace's --denoise_* flags (any may be missing) -> IntakeOptions' `denoise`: the keyword arguments of denoise, or None
+    without --denoise.  ValueError, naming the flag, for a value check_options refuses."""
+    get = lambda k: getattr(args, 'denoise_' + k, DEFAULTS[k])      # noqa: E731
+    kw = dict(sigma=None if get('sigma') is None else float(get('sigma')), search=int(get('search')), patch=int(get('patch')),
+              beta=float(get('beta')), rician=bool(get('rician')))
+    check_options(**kw)
+    return dict(denoise=kw if getattr(args, 'denoise', False) else None)
+
+
 def denoise_suffix(reports):
     """What a [done] line gains under --denoise (nothing otherwise): ` | denoise=<name>,<name>,...`."""
     if not reports:
@@ -122,8 +138,4 @@ def denoise_suffix(reports):
 
 def write_reports(reports, output_dir, target):
     """denoise_<t>.json next to the prediction: {input name: report}.  -> its path."""
-    os.makedirs(output_dir, exist_ok=True)
-    path = os.path.join(output_dir, f'denoise_{target.lower()}.json')
-    with open(path, 'w') as f:
-        json.dump({r[0]: r[1] for r in reports}, f, indent=1)
-    return path
+    return write_report_json('denoise', {r[0]: r[1] for r in reports}, output_dir, target)

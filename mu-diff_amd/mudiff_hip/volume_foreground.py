@@ -19,14 +19,12 @@ the same bits.
 """
 from __future__ import annotations
 
-import json
 import os
-import struct
 
 import numpy as np
 
 from . import MudiffHipError
-from .volume_intake import DEVICE_DTYPES, upload
+from .volume_intake import upload, write_report_json
 from .volume_regrid import RegriddedVolume
 
 MIN_BINS, MAX_BINS, MAX_OPEN = 16, 1024, 3
@@ -78,12 +76,6 @@ def unkey(key):
     key = int(key) & 0xFFFFFFFF
     bits = key ^ 0x80000000 if key & 0x80000000 else ~key & 0xFFFFFFFF
     return float(np.array([bits], np.uint32).view(np.float32)[0])
-
-
-def _meta(raw):
-    if int(raw.code) not in DEVICE_DTYPES:
-        raise MudiffHipError(f'foreground: unsupported NIfTI datatype code {raw.code}')
-    return (int(raw.code), tuple(int(v) for v in raw.shape)) + tuple(float(v) for v in raw.scaling)
 
 
 def _word(t, dtype=np.uint32):
@@ -139,7 +131,7 @@ def foreground(raw, device, bins=256, open=0, keep_holes=False, mask_out=False):
         raise ValueError(f'foreground: expected a 3D volume, got shape {tuple(raw.shape)}')
     check_options(bins, open, keep_holes, mask_out)
     bins, steps = int(bins), int(open)
-    dev, meta = upload(raw, device), _meta(raw)
+    dev, meta = upload(raw, device), raw.kernel_meta('foreground')
     shape = meta[1]
     report = dict(threshold=None, bin=None, bins=bins, lo=None, hi=None, candidates=0, components=0, kept=0, filled=0, removed=0,
                   open=steps, keep_holes=bool(keep_holes))
@@ -165,6 +157,29 @@ def foreground(raw, device, bins=256, open=0, keep_holes=False, mask_out=False):
 # ---------------------------------------------------------------------------------------------------
 # the pipeline's side
 # ---------------------------------------------------------------------------------------------------
+def add_flags(p):
+    p.add_argument('--foreground', action='store_true',
+                   help='set the voxels outside a foreground mask of every input to exactly 0, on its own grid, after --denoise and before '
+                        '--coregister / --regrid / --bias_correct see it (Otsu threshold, largest 6-connected component, holes filled, on '
+                        'the GPU: mudiff_hip.volume_foreground); foreground_<t>.json next to the prediction holds what was found.  This is '
+                        'a head / object mask by thresholding and topology, NOT a brain extraction: the skull stays (see --brain_extract).  '
+                        '--gt_volume / --eval_mask are not masked')
+    p.add_argument('--foreground_bins', type=int, default=DEFAULTS['bins'], help='bins of the histogram the Otsu threshold is taken from (16 to 1024)')
+    p.add_argument('--foreground_open', type=int, default=DEFAULTS['open'],
+                   help='open the thresholded mask first: this many erosions, then as many dilations, over the 6-neighbourhood (0 to 3)')
+    p.add_argument('--foreground_keep_holes', action='store_true', help='with --foreground: do not fill the holes of the kept component')
+    p.add_argument('--foreground_mask_out', action='store_true',
+                   help='with --foreground: also write foreground_<t>_<name>.nii.gz, the uint8 mask of each input on its own grid')
+
+
+def options_from(args):
+    """A namespace's --foreground_* flags (any may be missing) -> IntakeOptions' `foreground`: the keyword arguments of foreground, or
+    None without --foreground.  ValueError, naming the flag, for a value check_options refuses."""
+    kw = {k: getattr(args, 'foreground_' + k, v) for k, v in DEFAULTS.items()}
+    check_options(**kw)
+    return dict(foreground={k: type(v)(kw[k]) for k, v in DEFAULTS.items()} if getattr(args, 'foreground', False) else None)
+
+
 def foreground_suffix(reports):
     """What a [done] line gains under --foreground (nothing otherwise): ` | foreground=<name>,<name>,...`."""
     if not reports:
@@ -174,8 +189,7 @@ def foreground_suffix(reports):
 
 def write_mask(path, mask, affine, header=None):
     """A uint8 [X,Y,Z] mask with a volume's geometry -> .nii / .nii.gz (datatype 2)."""
-    import gzip
-    from .volume import NiftiHeader
+    from .volume import write_nifti1
     mask = np.asarray(mask, dtype=np.uint8)
     try:
         import nibabel as nib
@@ -183,32 +197,14 @@ def write_mask(path, mask, affine, header=None):
         return
     except ImportError:
         pass
-    reuse = isinstance(header, NiftiHeader) and header.endian == '<'
-    raw = bytearray(header.raw) if reuse else bytearray(348)
-    struct.pack_into('<i', raw, 0, 348)
-    struct.pack_into('<8h', raw, 40, mask.ndim, *mask.shape, *([1] * (7 - mask.ndim)))
-    struct.pack_into('<h', raw, 70, 2)            # datatype uint8
-    struct.pack_into('<h', raw, 72, 8)            # bitpix
-    struct.pack_into('<f', raw, 108, 352.0)       # vox_offset
-    struct.pack_into('<2f', raw, 112, 1.0, 0.0)   # scl_slope, scl_inter
-    if not reuse:
-        struct.pack_into('<8f', raw, 76, 1.0, *[float(np.linalg.norm(np.asarray(affine)[:3, i])) for i in range(3)], 1.0, 1.0, 1.0, 1.0)
-    struct.pack_into('<h', raw, 254, 1)           # sform_code: scanner
-    for r in range(3):
-        struct.pack_into('<4f', raw, 280 + 16 * r, *[float(v) for v in np.asarray(affine)[r]])
-    raw[344:348] = b'n+1\0'
-    with (gzip.open if path.endswith('.gz') else open)(path, 'wb') as f:
-        f.write(bytes(raw) + b'\0\0\0\0' + mask.tobytes(order='F'))
+    write_nifti1(path, mask, affine, header, 2, 8)
 
 
 def write_reports(reports, output_dir, target, affine=None, header=None):
     """foreground_<t>.json next to the prediction: {input name: report}; with --foreground_mask_out also foreground_<t>_<name>.nii.gz,
     each input's uint8 mask on that input's own grid.  reports: [(name, report, masked volume or None)]; affine / header: the geometry
     for a mask whose volume carries none.  -> the json's path."""
-    os.makedirs(output_dir, exist_ok=True)
-    path = os.path.join(output_dir, f'foreground_{target.lower()}.json')
-    with open(path, 'w') as f:
-        json.dump({r[0]: r[1] for r in reports}, f, indent=1)
+    path = write_report_json('foreground', {r[0]: r[1] for r in reports}, output_dir, target)
     for r in reports:
         vol = r[2] if len(r) > 2 else None
         if vol is not None and getattr(vol, 'mask', None) is not None:

@@ -57,6 +57,13 @@ class RawVolume:
         """(slope, inter) as the kernels take them: the file's where read_nifti applies them, else (1, 0)."""
         return (self.slope, self.inter) if self.scaled else (1.0, 0.0)
 
+    def kernel_meta(self, stage):
+        """(datatype code, shape [X,Y,Z], slope, inter) as the volume kernels take them; `stage` is what the refusal of a datatype they do
+        not read calls the caller."""
+        if self.code not in DEVICE_DTYPES:
+            raise MudiffHipError(f'{stage}: unsupported NIfTI datatype code {self.code}')
+        return (self.code, self.shape) + self.scaling
+
     def values_float64(self):
         """The [X,Y,Z] float64 array volume.read_nifti returns for this file (the reference conversion)."""
         data = np.asarray(self.data).reshape(self.shape, order='F').astype(np.float64)
@@ -92,6 +99,17 @@ def read_nifti_raw(path):
     n = int(np.prod(shape))
     data = np.frombuffer(buf, dtype=np.dtype('<' + DEVICE_DTYPES[code]), count=n, offset=offset)
     return RawVolume(data, code, hdr.endian, slope, inter, shape, hdr.affine, hdr)
+
+
+def write_report_json(kind, payload, output_dir, target):
+    """<kind>_<target>.json next to the prediction (every stage's write_reports).  -> its path."""
+    import json
+    import os
+    os.makedirs(output_dir, exist_ok=True)
+    path = os.path.join(output_dir, f'{kind}_{target.lower()}.json')
+    with open(path, 'w') as f:
+        json.dump(payload, f, indent=1)
+    return path
 
 
 # ---------------------------------------------------------------------------------------------------

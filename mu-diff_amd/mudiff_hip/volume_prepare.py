@@ -1,10 +1,15 @@
-"""The one input-preparation stage of the volume pipeline (DESIGN.md sections 5.10 - 5.18): every entry point - volume.predict_volume
-on the host, with --device_intake, and mudiff_hip.cohort - reads a subject's files, hands them to prepare_inputs and normalises what
-comes back, on the host (volume.host_stacks) or on the device (volume_intake.condition_from_raw).
+"""The one input-preparation stage of the volume pipeline (DESIGN.md sections 5.10 - 5.21) and the subject-level plan around it: every
+entry point - volume.predict_volume on the host, with --device_intake, and mudiff_hip.cohort - reads a subject's files, hands them to
+prepare_inputs and normalises what comes back, on the host (volume.host_stacks) or on the device (volume_intake.condition_from_raw).
 
-    IntakeOptions.from_args(args)                         what --norm / --regrid / --coregister / --bias_correct / --denoise / --foreground / --brain_extract / --reorient ask for, built once
+    STAGES                                                one line per stage: its module (add_flags, options_from, the suffixes, write_reports)
+    IntakeOptions.from_args(args)                         what --norm, --slice_half_range and every stage's flags ask for, built once
     prepare_inputs(named_raws, options, device)           reorient; denoise; foreground; first input = the grid; coregister; regrid, or check the shape; brain mask; bias-correct
     IntakeReport                                          what that did, by modality name: the [done] line's tail and the report files
+    read_for_evaluation, evaluation_inputs                --gt_volume / --eval_mask on the grid the prediction will have
+    output_writer                                         --reorient_back / --conform_back around a writer
+
+A stage's flags, their defaults and their checks live in the stage's own module (add_flags, options_from): nothing here lists them.
 """
 from __future__ import annotations
 
@@ -18,69 +23,61 @@ from . import volume_conform as VCF
 from . import volume_coreg as VC
 from . import volume_denoise as VD
 from . import volume_foreground as VF
+from . import volume_intake as VI
 from . import volume_regrid as VR
 from . import volume_reorient as VO
-from .volume import regrid_suffix
 from .volume_intake import slab_range
+
+# One line per stage, in the order of the flags, of the [done] line's parts and of the report files.  `parts`: (the module's suffix
+# function, the IntakeReport attributes it takes); `written`: the attributes (and `affine` / `header`, the prediction's) that its
+# write_reports takes after (entries, output_dir, target), the first of them being the entries; None for a stage without a report file.
+# Functions are looked up in the module when they are called: a test may replace them there.
+Stage = collections.namedtuple('Stage', 'module parts written')
+STAGES = (
+    Stage(VR, (('regrid_suffix', 'regridded'), ('interp_suffix', 'interp nonfinite')), None),
+    Stage(VC, (('coreg_suffix', 'coreg'),), 'coreg'),
+    Stage(VB, (('bias_suffix', 'bias'),), 'bias affine header'),
+    Stage(VD, (('denoise_suffix', 'denoise'),), 'denoise'),
+    Stage(VF, (('foreground_suffix', 'foreground'),), 'foreground affine header'),
+    Stage(VBR, (('brain_suffix', 'brain'),), 'brain affine header'),
+    Stage(VO, (('reorient_suffix', 'reorient'),), 'reorient'),
+    Stage(VCF, (('conform_suffix', 'conform conform_grid'), ('antialias_suffix', 'lowpass')), 'conform conform_grid'),
+)
 
 
 class IntakeOptions(collections.namedtuple('IntakeOptions', 'norm regrid coreg bias half_range foreground brain interp reorient conform antialias denoise',
                                            defaults=('percentile', False, None, None, 80, None, None, 'linear', None, None, False, None))):
-    """norm: --norm; regrid: --regrid; coreg / bias / denoise / foreground: the keyword arguments of volume_coreg.coregister /
-    volume_bias.correct / volume_denoise.denoise / volume_foreground.foreground, or None without --coregister / --bias_correct / --denoise /
-    --foreground; half_range: --slice_half_range (the slab is part of the reference geometry); brain: the keyword arguments of volume_brain.brain_mask plus
-    `source` (--brain_from or None) and `mask_out`, or None without --brain_extract; interp: --regrid_interp (how --regrid / --coregister
-    resample an image: 'linear' or 'cubic'); reorient: dict(target=the orientation code of --reorient_to), or None without --reorient;
-    conform: dict(shape, spacing, target) of --conform_shape / --conform_spacing / --conform_to (the keyword arguments of
-    volume_conform.conform_grid), or None without --conform; antialias: --antialias as a bool (on by default under --conform, off otherwise).
-    `foreground`, `brain`, `interp`, `reorient`, `conform` and `antialias` sit before `denoise`, not
-    at the end: tests/test_volume_denoise_host.py pins `denoise` as the last field, and every positional use stops at half_range."""
+    """norm: --norm; half_range: --slice_half_range (the slab is part of the reference geometry); every other field is what one stage's
+    options_from made of that stage's flags (its docstring says what): regrid and interp (volume_regrid), coreg, bias, denoise,
+    foreground, brain, reorient, conform and antialias (volume_conform).  `foreground`, `brain`, `interp`, `reorient`, `conform` and
+    `antialias` sit before `denoise`, not at the end: tests/test_volume_denoise_host.py pins `denoise` as the last field, and every
+    positional use stops at half_range."""
     __slots__ = ()
 
     @classmethod
     def from_args(cls, args):
-        """The only place that knows the flags' defaults (a namespace that did not come from volume.make_parser may lack any of them)."""
-        get = lambda name, default: getattr(args, name, default)      # noqa: E731
-        coreg = bias = denoise = foreground = brain = reorient = None
-        if get('coregister', False):
-            coreg = dict(strides=tuple(int(s) for s in get('coregister_strides', None) or (4, 2, 1)),
-                         max_mm=float(get('coregister_max_mm', 20.0)), max_deg=float(get('coregister_max_deg', 15.0)))
-        if get('bias_correct', False):
-            bias = dict({k: type(v)(get('bias_' + k, v)) for k, v in VB.DEFAULTS.items()}, field=bool(get('bias_field_out', False)))
-        if get('denoise', False):
-            sigma = get('denoise_sigma', None)
-            denoise = dict(sigma=None if sigma is None else float(sigma), search=int(get('denoise_search', VD.DEFAULTS['search'])),
-                           patch=int(get('denoise_patch', VD.DEFAULTS['patch'])), beta=float(get('denoise_beta', VD.DEFAULTS['beta'])),
-                           rician=bool(get('denoise_rician', False)))
-        if get('foreground', False):
-            foreground = dict(bins=int(get('foreground_bins', VF.DEFAULTS['bins'])), open=int(get('foreground_open', VF.DEFAULTS['open'])),
-                              keep_holes=bool(get('foreground_keep_holes', False)), mask_out=bool(get('foreground_mask_out', False)))
-        if get('brain_extract', False):
-            source = get('brain_from', None)
-            brain = dict(bins=int(get('brain_bins', VBR.DEFAULTS['bins'])), erode_mm=float(get('brain_erode_mm', VBR.DEFAULTS['erode_mm'])),
-                         dilate_mm=float(get('brain_dilate_mm', VBR.DEFAULTS['dilate_mm'])), keep_holes=bool(get('brain_keep_holes', False)),
-                         source=None if source is None else str(source), mask_out=bool(get('brain_mask_out', False)))
-        if get('reorient', False):
-            reorient = dict(target=VO.check_target(get('reorient_to', None) or VO.DEFAULT_TARGET))
-        conform = None
-        if get('conform', False):
-            spacing = get('conform_spacing', None)
-            conform = dict(shape=VCF._shape3(get('conform_shape', None) or VCF.DEFAULT_SHAPE),
-                           spacing=VCF._spacing3(VCF.DEFAULT_SPACING if spacing is None else spacing),
-                           target=VO.check_target(get('conform_to', VCF.DEFAULT_TARGET)))
-        antialias = get('antialias', None)
-        antialias = conform is not None if antialias is None else antialias in (True, 'on')
-        return cls(get('norm', 'percentile'), bool(get('regrid', False)), coreg, bias, int(get('slice_half_range', 80)), foreground, brain,
-                   str(get('regrid_interp', 'linear')), reorient, conform, antialias, denoise)
+        """A namespace that did not come from volume.make_parser may lack any flag: a stage's options_from knows its defaults.
+        ValueError, naming the flag, for a value a stage refuses."""
+        fields = dict(norm=getattr(args, 'norm', cls._field_defaults['norm']),
+                      half_range=int(getattr(args, 'slice_half_range', cls._field_defaults['half_range'])))
+        for stage in STAGES:
+            fields.update(stage.module.options_from(args))
+        return cls(**fields)
+
+    @property
+    def eval_as_stored(self):
+        """The evaluation inputs are read as stored (volume_intake.read_nifti_raw), geometry included, because the device reorients or
+        resamples them; otherwise they are read as arrays (volume.read_nifti) and only compared."""
+        return self.regrid or self.reorient is not None or self.conform is not None
 
 
 class IntakeReport:
-    """What the preparation did to one subject, by modality name: `regridded` [name] (a caller appends the evaluation inputs --regrid
-    resampled: `report.regridded += names`), `coreg` [(name, report)], `bias` [(name, report, field or None)], `denoise` [(name,
-    report)], `foreground` [(name, report, the masked volume or None)], `brain` [(the source's name, report, the uint8 [X,Y,Z] host mask or
-    None)]: one entry per subject; `reorient` [(name, entry)] (volume_reorient.ReorientPlan.entry); `interp` (--regrid_interp) and
-    `nonfinite`, the non-finite voxels a cubic resampling or the anti-aliasing low-pass read as 0; `conform` [(name, entry)]
-    (volume_conform.entry) with `conform_grid`, the grid's name ('240x240x155@1mm'); `lowpass`: a low-pass actually ran (--antialias)."""
+    """What the preparation did to one subject, by modality name: `regridded` [name], `coreg` [(name, report)], `bias` [(name, report,
+    field or None)], `denoise` [(name, report)], `foreground` [(name, report, the masked volume or None)], `brain` [(the source's name,
+    report, the uint8 [X,Y,Z] host mask or None)]: one entry per subject; `reorient` [(name, entry)] (volume_reorient.ReorientPlan.entry);
+    `interp` (--regrid_interp) and `nonfinite`, the non-finite voxels a cubic resampling or the anti-aliasing low-pass read as 0; `conform`
+    [(name, entry)] (volume_conform.entry) with `conform_grid`, the grid's name ('240x240x155@1mm'); `lowpass`: a low-pass actually ran
+    (--antialias)."""
 
     def __init__(self, regridded=(), interp='linear', nonfinite=0, lowpass=False):
         self.regridded, self.coreg, self.bias, self.denoise, self.foreground, self.brain = list(regridded), [], [], [], [], []
@@ -88,31 +85,72 @@ class IntakeReport:
         self.reorient = []
         self.conform, self.conform_grid, self.lowpass = [], None, bool(lowpass)
 
+    def add_evaluation(self, resampled, found):
+        """What evaluation_inputs did, after the inputs' own: the names it resampled, and its `found`."""
+        self.regridded += resampled
+        self.nonfinite += found.get('nonfinite', 0)
+        self.lowpass = self.lowpass or bool(found.get('lowpass'))
+
     def suffix(self):
-        """What a [done] line gains: ` | regrid=... | interp=cubic | coreg=... | bias=... | denoise=... | foreground=... | brain=... | reorient=... | conform=... | antialias=on`, each part only when
-        its list is not empty."""
-        return (regrid_suffix(self.regridded) + VR.interp_suffix(self.interp, self.nonfinite) + VC.coreg_suffix(self.coreg) + VB.bias_suffix(self.bias) + VD.denoise_suffix(self.denoise) +
-                VF.foreground_suffix(self.foreground) + VBR.brain_suffix(self.brain) + VO.reorient_suffix(self.reorient) +
-                VCF.conform_suffix(self.conform, self.conform_grid) + VCF.antialias_suffix(self.lowpass))
+        """What a [done] line gains: ` | regrid=... | interp=cubic | coreg=... | bias=... | denoise=... | foreground=... | brain=... |
+        reorient=... | conform=... | antialias=on`, each part only when there is something to say (STAGES' order)."""
+        return ''.join(getattr(stage.module, name)(*(getattr(self, k) for k in takes.split())) for stage in STAGES for name, takes in stage.parts)
 
     def write(self, output_dir, target, affine, header):
-        """coreg_<t>.json, bias_<t>.json (and the fields --bias_field_out asked for) , denoise_<t>.json and foreground_<t>.json (and the masks
-        --foreground_mask_out asked for) and brain_<t>.json (and the mask --brain_mask_out asked for, on the grid of `affine` / `header`)
-        and reorient_<t>.json and conform_<t>.json next to the prediction; nothing when empty."""
-        if self.coreg:
-            VC.write_reports(self.coreg, output_dir, target)
-        if self.bias:
-            VB.write_reports(self.bias, output_dir, target, affine, header)
-        if self.denoise:
-            VD.write_reports(self.denoise, output_dir, target)
-        if self.foreground:
-            VF.write_reports(self.foreground, output_dir, target, affine, header)
-        if self.brain:
-            VBR.write_reports(self.brain, output_dir, target, affine, header)
-        if self.reorient:
-            VO.write_reports(self.reorient, output_dir, target)
-        if self.conform:
-            VCF.write_reports(self.conform, output_dir, target, self.conform_grid)
+        """Every stage's report file (and the volumes its *_out flag asked for, on the grid of `affine` / `header` where they carry none)
+        next to the prediction, in STAGES' order; a stage with nothing to report writes nothing, not even the directory."""
+        have = dict(vars(self), affine=affine, header=header)
+        for stage in STAGES:
+            takes = (stage.written or '').split()
+            if takes and have[takes[0]]:
+                stage.module.write_reports(have[takes[0]], output_dir, target, *(have[k] for k in takes[1:]))
+
+
+def read_for_evaluation(path, options):
+    """One file the evaluation needs (the first input, --gt_volume, --eval_mask; None stays None) for evaluation_inputs: a RawVolume as
+    stored under options.eval_as_stored, else volume.read_nifti's (array, affine, header).  Host work only: a cohort calls it on its
+    prefetch thread."""
+    from . import volume as V
+    if path is None:
+        return None
+    return VI.read_nifti_raw(path) if options.eval_as_stored else V.read_nifti(path)
+
+
+def evaluation_inputs(first, gt, label, options, device, names, wording):
+    """The evaluation inputs on the grid the prediction will have, checked (volume_metrics.eval_inputs_on_grid: `names`, `wording`).
+    first, gt, label (or None): read_for_evaluation's, or for `first` the RawVolume a caller has read anyway.  The grid is the first
+    input's own; under --reorient that input's once reoriented (volume_reorient.reference_of: no voxel of it is moved), each evaluation
+    input being reoriented by its own affine first; under --conform the conform grid of that (volume_conform.reference_of).  Under
+    --regrid or --conform what is not on the grid is resampled onto it (--regrid_interp; the label volume by nearest neighbour), the
+    ground truth behind the low-pass of --antialias.  -> ((gt, label), the names of what was resampled, `found` of
+    volume_regrid.eval_onto_grid): IntakeReport.add_evaluation takes the last two."""
+    from . import volume_metrics as VM
+    geometry = lambda v: (v.shape, v.affine, v.header) if hasattr(v, 'header') else (v[0].shape, v[1], v[2])      # noqa: E731
+    grid, gt_affine = geometry(first), geometry(gt)[1]
+    if not options.eval_as_stored:
+        gt, label = gt[0], None if label is None else label[0]
+    resample = options.regrid or options.conform is not None
+    if options.reorient is not None:
+        grid = VO.reference_of(first, **options.reorient)[0]
+        gt, label, gt_affine = VO.eval_inputs(gt, label, device, options.reorient['target'], as_arrays=not resample)
+    if options.conform is not None:
+        grid = VCF.reference_of(grid, options.conform)
+    found = {}
+    evaluation, resampled = VM.eval_inputs_on_grid(grid, gt, label, gt_affine, resample, options.half_range, device, names=names, wording=wording,
+                                                   interp=options.interp, found=found, **(dict(antialias=True) if options.antialias else {}))
+    return evaluation, resampled, found
+
+
+def output_writer(write, first_raw, options, ref, device, reorient_back=False, conform_back=False):
+    """`write(path, vol, affine, header)` (volume.write_nifti, or a cohort's deferred writer) wrapped for --reorient_back and
+    --conform_back: the prediction arrives on the grid `ref` it was sampled on; --conform_back, outermost, resamples it onto the first
+    input's own grid (under --reorient: that grid reoriented), and --reorient_back, innermost, returns it to the storage order of
+    `first_raw`, the first input as read."""
+    if options.reorient is not None and reorient_back:
+        write = VO.write_back(write, first_raw, **options.reorient)
+    if options.conform is not None and conform_back:
+        write = VCF.write_back(write, VCF.first_on_own_grid(first_raw, options), ref[0], ref[1], device, options.interp, options.antialias)
+    return write
 
 
 def prepare_inputs(named_raws, options, device, labels=None):

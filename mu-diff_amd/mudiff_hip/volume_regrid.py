@@ -28,6 +28,31 @@ MODES_HIGH = ('cubic',)                                  # the modes that run mu
 INTERPS = ('linear',) + MODES_HIGH                       # --regrid_interp: how an image is resampled (a label volume: always nearest)
 
 
+def add_flags(p):
+    p.add_argument('--regrid', action='store_true',
+                   help='accept inputs (and --gt_volume / --eval_mask) on other voxel grids: each volume that is not on the first '
+                        "input's grid (shape and affine) is resampled onto it on the GPU through the affines before normalisation, "
+                        'trilinearly (the label volume: nearest neighbour).  Resampling only: the volumes must already share one '
+                        'world space (mudiff_hip.volume_regrid)')
+    p.add_argument('--regrid_interp', type=str, default=INTERPS[0], choices=list(INTERPS),
+                   help="how --regrid / --coregister resample an input (and --regrid the --gt_volume): 'linear' = trilinearly, which "
+                        "softens the volume by an amount that depends on the sub-voxel offset; 'cubic' = with a cubic B-spline "
+                        '(recursive prefilter + 4 x 4 x 4 gather on the GPU: mudiff_hip.volume_regrid), which keeps the sharpness of the '
+                        'first input; zero background stays exactly zero.  The label volume stays nearest neighbour and the registration '
+                        'search trilinear')
+
+
+def options_from(args):
+    """A namespace's --regrid / --regrid_interp (either may be missing) -> IntakeOptions' `regrid` and `interp`."""
+    return dict(regrid=bool(getattr(args, 'regrid', False)), interp=str(getattr(args, 'regrid_interp', INTERPS[0])))
+
+
+def regrid_suffix(names):
+    """What a [done] line gains when --regrid resampled inputs (nothing otherwise: the lines as they were)."""
+    names = list(names or ())
+    return f" | regrid={','.join(names)}" if names else ''
+
+
 def interp_suffix(interp, nonfinite=0):
     """What a [done] line gains under a non-default --regrid_interp (nothing by default: the lines as they were); `nonfinite`: the
     non-finite voxels the spline prefilter read as 0, named when there were any."""

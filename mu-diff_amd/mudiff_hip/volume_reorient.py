@@ -22,13 +22,11 @@ write_reports.  On the device: reorient -> ReorientedVolume.
 from __future__ import annotations
 
 import itertools
-import json
-import os
 import struct
 
 import numpy as np
 
-from .volume_intake import DEVICE_DTYPES, RawVolume, upload
+from .volume_intake import DEVICE_DTYPES, RawVolume, upload, write_report_json
 
 POSITIVE, NEGATIVE = 'RAS', 'LPI'                        # NIfTI world is RAS+: the letter of world axis w by the sign along it
 TARGETS = tuple(''.join(POSITIVE[w] if s else NEGATIVE[w] for w, s in zip(order, signs))
@@ -215,6 +213,34 @@ def reorient(raw, device, target=DEFAULT_TARGET):
 # ---------------------------------------------------------------------------------------------------
 # the pipeline's side
 # ---------------------------------------------------------------------------------------------------
+def add_flags(p):
+    p.add_argument('--reorient', action='store_true',
+                   help='bring every input (and --gt_volume / --eval_mask), each by its own affine, to the storage orientation the '
+                        'checkpoints were trained on before anything else sees it: a permutation and flips of the storage axes on the GPU '
+                        '(mudiff_hip.volume_reorient), exact, datatype and scaling kept, the affine changed to match.  The slab is then '
+                        'cut along the third axis of that orientation and everything is written on the reoriented grid; '
+                        'reorient_<t>.json next to the prediction holds what was done.  A permutation cannot make tilted slices axial: an '
+                        'input whose axes are tilted by more than 10 degrees (an untuned default, not a measured bar) gets a warning, and '
+                        'de-obliquing by resampling is not done')
+    p.add_argument('--reorient_to', type=str, default=None, metavar='CODE',
+                   help="the target orientation of --reorient, one letter of each of R/L, A/P, S/I: the direction every storage axis runs "
+                        "towards.  'LPS' is how BraTS stores its volumes, which the reference reads without reorienting; a checkpoint "
+                        'trained on data stored otherwise needs its own code.  Default: LPS, or under --conform what --conform_to says')
+    p.add_argument('--reorient_back', action='store_true',
+                   help="with --reorient: write predicted_<t>.nii.gz (and predicted_<t>_std.nii.gz) in the first input's own storage order, "
+                        'with its original affine and header (scored first, on the reoriented grid)')
+
+
+def options_from(args):
+    """A namespace's --reorient flags (any may be missing) -> IntakeOptions' `reorient`: dict(target=the code of --reorient_to, LPS
+    when there is none), or None without --reorient.  ValueError for a bad code and for --reorient_back on its own."""
+    target = check_target(getattr(args, 'reorient_to', None) or DEFAULT_TARGET)
+    on = bool(getattr(args, 'reorient', False))
+    if getattr(args, 'reorient_back', False) and not on:
+        raise ValueError('--reorient_back needs --reorient')
+    return dict(reorient=dict(target=target) if on else None)
+
+
 def reference_of(raw, target=DEFAULT_TARGET):
     """(shape, affine, header) of a volume once reoriented, and the plan: the geometry a prediction from it has.  No voxel is moved."""
     from .volume_regrid import world_affine_of
@@ -262,8 +288,4 @@ def reorient_suffix(entries):
 
 def write_reports(entries, output_dir, target):
     """reorient_<t>.json next to the prediction: {input name: entry}.  -> its path."""
-    os.makedirs(output_dir, exist_ok=True)
-    path = os.path.join(output_dir, f'reorient_{target.lower()}.json')
-    with open(path, 'w') as f:
-        json.dump({name: e for name, e in entries}, f, indent=1)
-    return path
+    return write_report_json('reorient', {name: e for name, e in entries}, output_dir, target)

@@ -347,6 +347,7 @@ def _payload(path):
 
 
 CONFORM = ['--conform', '--conform_shape', '24', '24', '16', '--conform_spacing', '2']
+NESTED = ['--reorient', '--reorient_back'] + CONFORM + ['--conform_back']      # both writers, --reorient_back inside --conform_back
 
 
 @pytest.fixture(scope='module')
@@ -376,12 +377,17 @@ def runs(tmp_path_factory):
     back = CONFORM + ['--conform_back']
     jobs = {'a_plain': inputs('A'), 'a_conform': inputs('A') + CONFORM, 'b_host': inputs('B') + back + ['--gt_volume', files['B', 'gt']],
             'c_host': inputs('C') + back, 'b_plain': inputs('B'), 'b_dev': inputs('B') + back + ['--device_intake'],
-            'c_dev': inputs('C') + back + ['--device_intake']}
+            'c_dev': inputs('C') + back + ['--device_intake'],
+            'b_nested': inputs('B') + NESTED + ['--gt_volume', files['B', 'gt']],
+            'b_nested_dev': inputs('B') + NESTED + ['--gt_volume', files['B', 'gt'], '--device_intake']}
     jobs = {k: model + a + ['--output_dir', str(tmp / k)] for k, a in jobs.items()}
     manifest = tmp / 'cohort.tsv'
     manifest.write_text('id\tt1\tt1ce\tt2\tflair\n' + ''.join(f's_{n.lower()}\t' + '\t'.join([files[n, 't1'], '', files[n, 't2'], files[n, 'flair']]) + '\n'
                                                               for n in 'BC'))
-    cohort = model + back + ['--manifest', str(manifest), '--output_dir', str(tmp / 'cohort')]
+    scored = tmp / 'cohort_nested.tsv'
+    scored.write_text('id\tt1\tt1ce\tt2\tflair\tgt\n' + 's_b\t' + '\t'.join([files['B', 't1'], '', files['B', 't2'], files['B', 'flair'], files['B', 'gt']]) + '\n')
+    cohorts = {'cohort': model + back + ['--manifest', str(manifest), '--output_dir', str(tmp / 'cohort')],
+               'cohort_nested': model + NESTED + ['--score', '--manifest', str(scored), '--output_dir', str(tmp / 'cohort_nested')]}
     log = str(tmp / 'log.json')
     code = f'''
         import contextlib, io, json, warnings
@@ -402,13 +408,14 @@ def runs(tmp_path_factory):
                 V.predict_volume(V.build_argparser(argv))
             log[name] = out.getvalue()
         current[0] = None
-        out = io.StringIO()
-        with contextlib.redirect_stdout(out), warnings.catch_warnings():
-            warnings.simplefilter('ignore')
-            args = Co.build_argparser({cohort!r})
-            failures = Co.run(args, Co.read_manifest(args.manifest))[1]
-        assert not failures, failures
-        log['cohort'] = out.getvalue()
+        for name, argv in {cohorts!r}.items():
+            out = io.StringIO()
+            with contextlib.redirect_stdout(out), warnings.catch_warnings():
+                warnings.simplefilter('ignore')
+                args = Co.build_argparser(argv)
+                failures = Co.run(args, Co.read_manifest(args.manifest))[1]
+            assert not failures, failures
+            log[name] = out.getvalue()
         json.dump(log, open({log!r}, 'w'))
     '''
     env = dict(os.environ, PYTHONPATH=os.pathsep.join([REPO, PKG, os.environ.get('PYTHONPATH', '')]), MUD_DETERMINISTIC='1')
@@ -488,3 +495,37 @@ def test_cohort_writes_the_single_runs_files(runs):
         assert _payload(str(tmp / 'cohort' / f's_{n}' / 'predicted_t1ce.nii.gz')) == _payload(str(tmp / f'{n}_dev' / 'predicted_t1ce.nii.gz'))
         assert open(tmp / 'cohort' / f's_{n}' / 'conform_t1ce.json').read() == open(tmp / f'{n}_dev' / 'conform_t1ce.json').read()
         assert line.endswith(' | conform=24x24x16@2mm:FLAIR,T2,T1 | antialias=on')
+
+
+def test_nested_writers_and_evaluation_grid_through_both_entry_points(runs):
+    """Subject B (stored RAS, 12 degrees oblique) under --reorient --reorient_back --conform --conform_back with a ground truth: the
+    evaluation inputs go reoriented onto the conform grid of the reoriented first input, the prediction is scored there and both writers
+    take it back to the first input's own storage grid.  predict_volume (host and device intake) and the cohort with --score write the
+    same bytes, the same metrics and the same [done] tail.  24 x 24 x 16 with a slab of 7 planes is the smallest grid the 7 x 7 x 7 SSIM
+    window accepts."""
+    import json
+    from mudiff_hip import volume as V
+    tmp = runs['tmp']
+    single, cohort = tmp / 'b_nested', tmp / 'cohort_nested' / 's_b'
+    tail = lambda line: line.split(' | ', 1)[1]                       # noqa: E731  (what follows the path, which differs)
+    want = _done(runs, 'b_nested')[0]
+    assert tail(want) == ('shape=(24, 24, 16) | slices=5..11 | regrid=gt_volume | reorient=FLAIR:RAS>LPS,T2:RAS>LPS,T1:RAS>LPS | '
+                          'conform=24x24x16@2mm:FLAIR,T2,T1 | antialias=on')
+    for other, line in ((tmp / 'b_nested_dev', _done(runs, 'b_nested_dev')[0]), (cohort, _done(runs, 'cohort_nested')[0])):
+        assert _payload(str(other / 'predicted_t1ce.nii.gz')) == _payload(str(single / 'predicted_t1ce.nii.gz'))
+        for report in ('metrics_t1ce.json', 'reorient_t1ce.json', 'conform_t1ce.json'):
+            assert open(other / report).read() == open(single / report).read(), report
+        assert tail(line) == tail(want)
+    assert sorted(p.name for p in cohort.iterdir()) == sorted(p.name for p in single.iterdir()) == [
+        'conform_t1ce.json', 'metrics_t1ce.json', 'predicted_t1ce.nii.gz', 'reorient_t1ce.json']
+    # the written file: the first input's own shape, affine and header
+    _, hdr, code = V.open_nifti1(str(single / 'predicted_t1ce.nii.gz'))
+    _, first, _ = V.open_nifti1(runs['files']['B', 'flair'])
+    assert code == 16 and hdr.shape == B_SHAPE and np.array_equal(hdr.world_affine, first.world_affine) and np.array_equal(hdr.world_affine, B_AFFINE)
+    assert hdr._get('8f', 76) == first._get('8f', 76) and hdr.raw[252:256] == first.raw[252:256]
+    pred = V.read_nifti(str(single / 'predicted_t1ce.nii.gz'))[0]
+    assert float(pred.max()) > 0.05 and np.isfinite(pred).all()
+    metrics = json.load(open(single / 'metrics_t1ce.json'))
+    assert metrics['regions'] == ['slab', 'brain'] and metrics['metrics']['slab']['voxels'] == 24 * 24 * 7
+    row = json.load(open(tmp / 'cohort_nested' / 'cohort_t1ce.json'))['subjects'][0]
+    assert row['id'] == 's_b' and row['metrics']['slab']['psnr'] == metrics['metrics']['slab']['psnr']
