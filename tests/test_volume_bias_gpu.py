@@ -3,21 +3,16 @@
 1 to 3 levels: the log image within 2 ulp, the corrected log image, its extremes, its largest change, its histogram and the integer sums
 of the fit equal to the restatement's; the applied correction within 1 ulp; the whole loop equal to the restatement driven from the
 device's log image; the recovery of a known field; the C ABI's argument checks; `predict_volume --bias_correct` end to end."""
-import gzip
 import json
 import os
-import subprocess
-import sys
-import textwrap
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import PKG, REPO
 import volume_bias_ref as B
 import volume_intake_ref as R
-from oracle import mudiff_oracle as O
+import volume_support as VS
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -25,22 +20,11 @@ SHAPE = (37, 29, 23)
 SHRINKS, LEVELS = (1, 2, 3), (1, 2, 3)
 
 
-def _raw(vol, scale=(1.0, 0.0), affine=None):
-    from mudiff_hip import volume_intake as VI
-    return VI.RawVolume(np.ascontiguousarray(vol.reshape(-1, order='F')), R.CODES[vol.dtype.str[1:]], '<', float(np.float32(scale[0])),
-                        float(np.float32(scale[1])), vol.shape, np.eye(4) if affine is None else affine, None)
-
-
 def _engine(vol, shrink, scale=(1.0, 0.0)):
     from mudiff_hip import volume_bias as VB
     from mudiff_hip import volume_intake as VI
-    raw = _raw(vol, scale)
+    raw = VS.raw_volume(vol, scale)
     return VB.DeviceEngine(VI.upload(raw, DEV), (raw.code, raw.shape) + ((raw.slope, raw.inter) if raw.scaled else (1.0, 0.0)), shrink)
-
-
-def _host(t):
-    """A device log image [nz,ny,nx] -> the restatement's [nx,ny,nz]."""
-    return t.cpu().numpy().transpose(2, 1, 0)
 
 
 def _lattices(levels, seed, amp=0.2):
@@ -64,7 +48,7 @@ def test_log_image(dtype, scale):
     values = R.values_float32(vol, *scale)
     for shrink in SHRINKS:
         want = B.log_image(values, shrink)
-        got = _host(_engine(vol, shrink, scale).u)
+        got = VS.to_host_xyz(_engine(vol, shrink, scale).u)
         assert got.shape == want.shape and got.dtype == np.float32
         assert np.array_equal(np.isnan(got), np.isnan(want))
         ok = ~np.isnan(want)
@@ -79,18 +63,18 @@ def test_corrected_histogram_and_fit_are_the_restatement(tissue, shrink):
     from mudiff_hip import volume_bias as VB
     for levels in LEVELS:
         eng = _engine(tissue, shrink)
-        u = _host(eng.u)
+        u = VS.to_host_xyz(eng.u)
         lat = _lattices(levels, 100 + levels)
         lo, hi, dmax = eng.corrected(lat)
         c, wlo, whi, wdmax = B.corrected(u, lat, SHAPE, shrink)
-        got_c = _host(eng.c[0])
+        got_c = VS.to_host_xyz(eng.c[0])
         assert np.array_equal(got_c, c, equal_nan=True) and np.isfinite(c).sum() > 100
         assert (lo, hi, dmax) == (wlo, whi, wdmax) and dmax > 0
         # a second pass against the first: dmax is measured from the previous corrected image
         lat2 = _lattices(levels, 200 + levels, amp=0.05)
         lo2, hi2, dmax2 = eng.corrected(lat2)
         c2, wlo2, whi2, wdmax2 = B.corrected(u, lat2, SHAPE, shrink, c)
-        assert np.array_equal(_host(eng.c[0]), c2, equal_nan=True) and (lo2, hi2, dmax2) == (wlo2, whi2, wdmax2)
+        assert np.array_equal(VS.to_host_xyz(eng.c[0]), c2, equal_nan=True) and (lo2, hi2, dmax2) == (wlo2, whi2, wdmax2)
         for bins in (200, 64):
             scale = bins / (hi2 - lo2)
             h = eng.hist(lo2, scale, bins)
@@ -111,8 +95,8 @@ def test_corner_cases():
     from mudiff_hip import volume_bias as VB
     # nothing masked in: NaN everywhere, no extremes, zero sums, no fault
     eng = _engine(np.zeros(SHAPE, np.int16, order='F'), 2)
-    assert np.isnan(_host(eng.u)).all()
-    assert eng.corrected(_lattices(2, 5)) == (None, None, 0.0) and np.isnan(_host(eng.c[0])).all()
+    assert np.isnan(VS.to_host_xyz(eng.u)).all()
+    assert eng.corrected(_lattices(2, 5)) == (None, None, 0.0) and np.isnan(VS.to_host_xyz(eng.c[0])).all()
     assert not eng.hist(0.0, 0.0, 200).any()
     delta, omega = eng.fit(1, VB.bin_centres(0.0, 0.0, 200), 0.0, 0.0, 30)
     assert delta.shape == (5, 5, 5) and not delta.any() and not omega.any()
@@ -125,8 +109,8 @@ def test_corner_cases():
         eng = _engine(vol, shrink)
         lat = _lattices(3, 6)
         lo, hi, dmax = eng.corrected(lat)
-        c, wlo, whi, wdmax = B.corrected(_host(eng.u), lat, vol.shape, shrink)
-        assert np.array_equal(_host(eng.c[0]), c) and (lo, hi, dmax) == (wlo, whi, wdmax)
+        c, wlo, whi, wdmax = B.corrected(VS.to_host_xyz(eng.u), lat, vol.shape, shrink)
+        assert np.array_equal(VS.to_host_xyz(eng.c[0]), c) and (lo, hi, dmax) == (wlo, whi, wdmax)
         scale = 200 / (hi - lo)
         table = VB.sharpen(eng.hist(lo, scale, 200), lo, hi)
         delta, omega = eng.fit(2, table, lo, scale, 40)
@@ -175,7 +159,7 @@ def test_whole_loop_equals_the_restatement_driven_from_the_device_log_image(head
     eng = _engine(head['vol'], 2)
     opts = dict(levels=3, iters=8, tol=1e-3, bins=200, fwhm=0.15, wiener=0.01)
     lattices, iterations, dmax = VB.loop(eng, **opts)
-    want, want_iterations, want_dmax = VB.loop(B.Engine(_host(eng.u), B.HEAD_SHAPE, 2), **opts)
+    want, want_iterations, want_dmax = VB.loop(B.Engine(VS.to_host_xyz(eng.u), B.HEAD_SHAPE, 2), **opts)
     print('iterations', iterations, want_iterations, 'dmax', dmax, want_dmax)
     assert iterations == want_iterations and dmax == want_dmax and sum(iterations) >= 3
     for a, b in zip(lattices, want):
@@ -188,7 +172,7 @@ def test_device_recovery_meets_the_bar(head):
     """The bar is 1.5 x the ratio the restatement alone reaches (volume_bias_ref.RECORDED_RATIO)."""
     from mudiff_hip import volume_bias as VB
     from mudiff_hip import volume_regrid as VR
-    out, rep = VB.correct(_raw(head['vol']), DEV, **B.RECOVERY, field=True)
+    out, rep = VB.correct(VS.raw_volume(head['vol']), DEV, **B.RECOVERY, field=True)
     ratio = B.recovery_ratio(out.lattices, head['field'], head['mask'])
     print('device recovery', ratio, 'bar', B.BAR, rep)
     assert ratio < 0.5 and ratio <= B.BAR
@@ -261,20 +245,11 @@ def test_c_abi_rejects_bad_arguments_without_launching():
 # ---------------------------------------------------------------------------------------------------
 # end to end: the tiny model of the other volume tests, three shaded inputs on one grid
 # ---------------------------------------------------------------------------------------------------
-def _payload(path):
-    with gzip.open(path, 'rb') as f:
-        return f.read()
-
-
 @pytest.fixture(scope='module')
 def runs(tmp_path_factory, head):
     from mudiff_hip import volume as V
     tmp = tmp_path_factory.mktemp('shaded')
-    cfg = O.default_config(image_size=16, num_channels_dae=16, ch_mult=[1, 2], attn_resolutions=(4,), num_res_blocks=1)
-    exp = tmp / 'results' / 'exp0'
-    exp.mkdir(parents=True)
-    for which, name in (('g1', 'gen_diffusive_1'), ('g2', 'gen_diffusive_2')):
-        torch.save({'module.' + k: v for k, v in O.make_state_dict(cfg, which, 9).items()}, str(exp / f'{name}.pth'))
+    VS.write_tiny_model(tmp)
     p = {k: str(tmp / f'{k}.nii.gz') for k in ('flair', 't2', 't1')}
     V.write_nifti(p['flair'], head['vol'], np.eye(4))
     t2 = B.shaded_head(noise_seed=22)[0][::-1].copy(order='F') * np.float32(0.5)
@@ -284,9 +259,7 @@ def runs(tmp_path_factory, head):
     p['t2_grid'] = str(tmp / 't2_grid.nii.gz')                                     # the same head on another grid: moved, one plane fewer
     V.write_nifti(p['t2_grid'], t2[:, :, :-1].copy(order='F'), shifted)
     V.write_nifti(p['t1'], B.shaded_head(noise_seed=23)[0][:, ::-1].copy(order='F') * np.float32(2.0), np.eye(4))
-    model = ['--target_modality', 'T1CE', '--exp', 'exp0', '--output_path', str(tmp / 'results'), '--image_size', '16', '--num_channels_dae',
-             '16', '--ch_mult', '1', '2', '--attn_resolutions', '4', '--num_res_blocks', '1', '--slice_half_range', '2', '--batch_size', '5',
-             '--seed', '31', '--resize_back', '--input_flair', p['flair'], '--input_t2', p['t2'], '--input_t1', p['t1']]
+    model = VS.model_argv(tmp, 2, 5, '--resize_back', '--input_flair', p['flair'], '--input_t2', p['t2'], '--input_t1', p['t1'])
     bias = ['--bias_correct', '--bias_shrink', '2', '--bias_levels', '3']
     jobs = {'bias_host': bias, 'bias_dev': bias + ['--device_intake', '--bias_field_out'], 'bias_host_z': bias + ['--norm', 'zscore'],
             'bias_dev_z': bias + ['--norm', 'zscore', '--device_intake'], 'bias_coreg': bias + ['--coregister', '--coregister_strides', '4'],
@@ -299,39 +272,9 @@ def runs(tmp_path_factory, head):
     manifest = tmp / 'cohort.tsv'
     manifest.write_text('id\tt1\tt1ce\tt2\tflair\ns0\t' + '\t'.join([p['t1'], '', p['t2_grid'], p['flair']]) + '\n')
     cohort = on_grid + every + ['--manifest', str(manifest), '--output_dir', str(tmp / 'all_cohort')]
-    log = str(tmp / 'log.json')
-    code = f'''
-        import contextlib, io, json, warnings
-        from mudiff_hip import cohort as Co, volume as V
-        log = {{}}
-        out = io.StringIO()
-        with contextlib.redirect_stdout(out), warnings.catch_warnings():
-            warnings.simplefilter('ignore', RuntimeWarning)
-            args = Co.build_argparser({cohort!r})
-            failures = Co.run(args, Co.read_manifest(args.manifest))[1]
-        assert not failures, failures
-        log['all_cohort'] = out.getvalue()
-        for name, argv in {jobs!r}.items():
-            out = io.StringIO()
-            with contextlib.redirect_stdout(out), warnings.catch_warnings():
-                warnings.simplefilter('ignore', RuntimeWarning)
-                V.predict_volume(V.build_argparser(argv))
-            log[name] = out.getvalue()
-        json.dump(log, open({log!r}, 'w'))
-    '''
-    env = dict(os.environ, PYTHONPATH=os.pathsep.join([REPO, PKG, os.environ.get('PYTHONPATH', '')]), MUD_DETERMINISTIC='1')
-    for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE'):
-        env.pop(k, None)
-    c = subprocess.run([sys.executable, '-c', textwrap.dedent(code)], cwd=REPO, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                       timeout=900)
-    assert c.returncode == 0, c.stdout[-3000:] + c.stderr[-3000:]
-    return dict(tmp=tmp, log=json.load(open(log)), pred=lambda k: _payload(str(tmp / k / 'predicted_t1ce.nii.gz')))
-
-
-def _done(runs, name):
-    lines = [ln for ln in runs['log'][name].splitlines() if ln.startswith('[done]')]
-    assert len(lines) == 1
-    return lines[0]
+    steps = [VS.cohort_step('all_cohort', cohort)] + [VS.volume_step(k, argv) for k, argv in jobs.items()]
+    log = VS.run_plan(tmp, steps, 900, ignore='RuntimeWarning')
+    return dict(tmp=tmp, log=log, pred=lambda k: VS.payload(str(tmp / k / 'predicted_t1ce.nii.gz')))
 
 
 def test_predict_volume_bias_correct_end_to_end(runs):
@@ -343,13 +286,13 @@ def test_predict_volume_bias_correct_end_to_end(runs):
         for r in rep.values():
             assert len(r['iterations']) == 3 and all(1 <= i <= 50 for i in r['iterations']) and r['shrink'] == 2
             assert r['field_min'] < r['field_mean'] < r['field_max'] and r['field_max'] - r['field_min'] > 0.2      # (the shading is +-0.3)
-        assert _done(runs, name).endswith(' | bias=FLAIR,T2,T1')
+        assert VS.done_line(runs['log'][name]).endswith(' | bias=FLAIR,T2,T1')
     assert reports['bias_host'] == reports['bias_dev'] == reports['bias_host_z'] == reports['bias_dev_z']
     assert runs['pred']('bias_host') == runs['pred']('bias_dev')                   # host file == device file, byte for byte
     assert runs['pred']('bias_host_z') == runs['pred']('bias_dev_z')               # in both --norm modes
     assert runs['pred']('bias_host') != runs['pred']('plain_host')                 # and the correction reached the sampler
     assert runs['pred']('bias_host_z') != runs['pred']('plain_host_z')
-    assert ' | coreg=T2:' in _done(runs, 'bias_coreg') and os.path.exists(tmp / 'bias_coreg' / 'coreg_t1ce.json')
+    assert ' | coreg=T2:' in VS.done_line(runs['log']['bias_coreg']) and os.path.exists(tmp / 'bias_coreg' / 'coreg_t1ce.json')
     fields = sorted(f for f in os.listdir(tmp / 'bias_dev') if f.startswith('bias_field_'))
     assert fields == ['bias_field_flair_t1ce.nii.gz', 'bias_field_t1_t1ce.nii.gz', 'bias_field_t2_t1ce.nii.gz']
     from mudiff_hip import volume as V
@@ -364,13 +307,13 @@ def test_the_three_flags_together_agree_on_every_entry_point(runs):
     import re
     tmp = runs['tmp']
     where = {'all_host': tmp / 'all_host', 'all_dev': tmp / 'all_dev', 'all_cohort': tmp / 'all_cohort' / 's0'}
-    payloads = {k: _payload(str(d / 'predicted_t1ce.nii.gz')) for k, d in where.items()}
+    payloads = {k: VS.payload(str(d / 'predicted_t1ce.nii.gz')) for k, d in where.items()}
     assert payloads['all_host'] == payloads['all_dev'] == payloads['all_cohort']
     assert payloads['all_host'] != runs['pred']('bias_coreg')                      # (T2 really came from the other grid)
     for report, keys in (('coreg_t1ce.json', ['T2', 'T1']), ('bias_t1ce.json', ['FLAIR', 'T2', 'T1'])):
         reps = [json.load(open(d / report)) for d in where.values()]
         assert reps[0] == reps[1] == reps[2] and list(reps[0]) == keys
-    lines = {k: _done(runs, k).replace(str(d), 'OUT') for k, d in where.items()}
+    lines = {k: VS.done_line(runs['log'][k]).replace(str(d), 'OUT') for k, d in where.items()}
     print(lines['all_host'])
     assert lines['all_host'] == lines['all_dev'] == lines['all_cohort']
     assert re.search(r' \| regrid=T2[^|]* \| coreg=[^|]+ \| bias=FLAIR,T2,T1$', lines['all_host'])
@@ -380,7 +323,7 @@ def test_without_the_flag_nothing_changes(runs):
     tmp = runs['tmp']
     assert runs['pred']('plain_dev') == runs['pred']('plain_host')
     for name in ('plain_host', 'plain_dev', 'plain_host_z'):
-        assert ' | bias=' not in _done(runs, name) and ' | regrid=' not in _done(runs, name) and 'bias' not in runs['log'][name]
+        assert ' | bias=' not in VS.done_line(runs['log'][name]) and ' | regrid=' not in VS.done_line(runs['log'][name]) and 'bias' not in runs['log'][name]
         assert sorted(os.listdir(tmp / name)) == ['predicted_t1ce.nii.gz']
-    assert _done(runs, 'plain_host').endswith('| slices=16..20')
-    assert _done(runs, 'plain_host_z').endswith('| slices=16..20 | norm=zscore')
+    assert VS.done_line(runs['log']['plain_host']).endswith('| slices=16..20')
+    assert VS.done_line(runs['log']['plain_host_z']).endswith('| slices=16..20 | norm=zscore')

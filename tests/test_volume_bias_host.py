@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import volume_bias_ref as B
+from volume_support import cli_argv
 
 
 def _two_classes(n=60000, seed=3):
@@ -121,19 +122,15 @@ def test_integer_fit_is_the_floating_point_fit():
     assert np.abs(got - want).max() <= 1e-6 and np.abs(want).max() > 1e-3
 
 
-def _argv(*extra):
-    return ['--target_modality', 'T1CE', '--output_dir', 'out', '--exp', 'e'] + list(extra)
-
-
 def test_flags_defaults_and_refusals(capsys):
     from mudiff_hip import volume as V
     from mudiff_hip.volume_prepare import IntakeOptions
     options = lambda args: IntakeOptions.from_args(args).bias      # noqa: E731
-    args = V.build_argparser(_argv())
+    args = V.build_argparser(cli_argv())
     assert args.bias_correct is False and args.bias_field_out is False and options(args) is None
-    args = V.build_argparser(_argv('--bias_correct'))
+    args = V.build_argparser(cli_argv('--bias_correct'))
     assert options(args) == dict(shrink=4, levels=4, iters=50, tol=1e-3, bins=200, fwhm=0.15, wiener=0.01, field=False)
-    args = V.build_argparser(_argv('--bias_correct', '--bias_shrink', '2', '--bias_levels', '3', '--bias_iters', '7', '--bias_tol', '0.01',
+    args = V.build_argparser(cli_argv('--bias_correct', '--bias_shrink', '2', '--bias_levels', '3', '--bias_iters', '7', '--bias_tol', '0.01',
                                    '--bias_bins', '64', '--bias_fwhm', '0.2', '--bias_wiener', '0.1', '--bias_field_out'))
     assert options(args) == dict(shrink=2, levels=3, iters=7, tol=0.01, bins=64, fwhm=0.2, wiener=0.1, field=True)
     for bad, word in ((['--bias_shrink', '0'], 'bias_shrink'), (['--bias_levels', '0'], 'bias_levels'), (['--bias_levels', '6'], 'bias_levels'),
@@ -142,10 +139,10 @@ def test_flags_defaults_and_refusals(capsys):
                       (['--bias_fwhm', 'inf'], 'bias_fwhm'), (['--bias_wiener', '0'], 'bias_wiener'), (['--bias_wiener', '-0.01'], 'bias_wiener'),
                       (['--bias_field_out'], 'bias_correct')):
         with pytest.raises(SystemExit):
-            V.build_argparser(_argv('--bias_correct', *bad) if bad != ['--bias_field_out'] else _argv(*bad))
+            V.build_argparser(cli_argv('--bias_correct', *bad) if bad != ['--bias_field_out'] else cli_argv(*bad))
         assert word in capsys.readouterr().err
     from mudiff_hip import cohort
-    assert cohort.build_argparser(_argv('--manifest', 'm.tsv', '--bias_correct', '--bias_shrink', '3')).bias_shrink == 3
+    assert cohort.build_argparser(cli_argv('--manifest', 'm.tsv', '--bias_correct', '--bias_shrink', '3')).bias_shrink == 3
 
 
 def test_bias_suffix_and_reports(tmp_path):

@@ -3,22 +3,17 @@
 of the labelling tests, at four shapes (one with a line longer than a workgroup), three spacings and both values; mud_volume_edt_select
 with the > / <= edge; the whole brain_mask() on the head phantom stored as int16 with slope / inter and as fp32 with a NaN and an inf, at
 1 mm and at 1 x 1 x 2 mm; degenerate inputs; the C ABI's refusals; `predict_volume --brain_extract` end to end."""
-import gzip
 import json
 import os
-import subprocess
-import sys
-import textwrap
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import PKG, REPO
 import volume_brain_ref as B
 import volume_foreground_ref as F
 import volume_intake_ref as R
-from oracle import mudiff_oracle as O
+import volume_support as VS
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -26,21 +21,6 @@ EDT_SHAPES = ((37, 29, 23), (5, 4, 3), (70, 19, 11), (300, 5, 3))
 EDT_SPACINGS = ((1.0, 1.0, 1.0), (0.9375, 0.9375, 3.0), (0.7, 1.3, 2.1))
 I2_SCALE = (0.25, -3.0)
 RADII = B.PHANTOM_RADII
-
-
-def _raw(vol, scale=(1.0, 0.0), affine=None):
-    from mudiff_hip import volume_intake as VI
-    return VI.RawVolume(np.ascontiguousarray(vol.reshape(-1, order='F')), R.CODES[vol.dtype.str[1:]], '<', float(np.float32(scale[0])),
-                        float(np.float32(scale[1])), vol.shape, np.eye(4) if affine is None else affine, None)
-
-
-def _device(a, dtype=None):
-    """[X,Y,Z] host array -> [Z,Y,X] device tensor."""
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype).transpose(2, 1, 0))).to(DEV)
-
-
-def _host(t):
-    return t.cpu().numpy().transpose(2, 1, 0)
 
 
 def _edt_masks(shape):
@@ -60,9 +40,9 @@ def test_edt_is_the_restatement_bit_for_bit(shape, spacing, value):
     assert list(masks) == ['on', 'off', 'comb', 'random0.5', 'random0.7', 'corner', 'middle']
     for name, mask in masks.items():
         want = B.edt2(mask, value, spacing)
-        dev = _device(mask)
+        dev = VS.to_device_zyx(mask)
         d2 = ops.volume_edt(dev, shape, value, spacing)
-        got = _host(d2)
+        got = VS.to_host_xyz(d2)
         assert got.dtype == np.float64 and got.shape == shape
         same = got.view(np.int64) == want.view(np.int64)
         assert same.all(), (name, int((~same).sum()), got[~same][:3], want[~same][:3])
@@ -78,20 +58,20 @@ def test_edt_select_is_exact():
     shape, spacing = (37, 29, 23), (0.9375, 0.9375, 3.0)
     mask = F.label_masks(shape)['random0.7']
     within = F.label_masks(shape)['comb']
-    d2 = ops.volume_edt(_device(mask), shape, 0, spacing)
-    host = _host(d2)
+    d2 = ops.volume_edt(VS.to_device_zyx(mask), shape, 0, spacing)
+    host = VS.to_host_xyz(d2)
     present = np.unique(host[host > 0])
     assert present.size >= 3
     for r2 in (0.0, float(present[0]), float(present[1]), float(np.nextafter(present[1], 0.0)), 7.25, 1e300):
         for above in (1, 0):
             for inside in (None, within):
-                got, count = ops.volume_edt_select(d2, r2, above, None if inside is None else _device(inside))
+                got, count = ops.volume_edt_select(d2, r2, above, None if inside is None else VS.to_device_zyx(inside))
                 want = (host > r2) if above else (host <= r2)
                 if inside is not None:
                     want = want & (inside != 0)
-                assert got.dtype == torch.uint8 and got.shape == d2.shape and np.array_equal(_host(got), want.astype(np.uint8)), (r2, above)
+                assert got.dtype == torch.uint8 and got.shape == d2.shape and np.array_equal(VS.to_host_xyz(got), want.astype(np.uint8)), (r2, above)
                 assert int(count[0]) == int(want.sum())
-    inf = ops.volume_edt(_device(np.ones(shape, np.uint8)), shape, 0, spacing)          # +inf everywhere: above any radius, within none
+    inf = ops.volume_edt(VS.to_device_zyx(np.ones(shape, np.uint8)), shape, 0, spacing)          # +inf everywhere: above any radius, within none
     assert int(ops.volume_edt_select(inf, 1e300, 1)[1][0]) == int(np.prod(shape)) and int(ops.volume_edt_select(inf, 1e300, 0)[1][0]) == 0
 
 
@@ -115,16 +95,16 @@ def _stored(kind, spacing):
 def test_brain_mask_is_the_restatement(kind, spacing):
     from mudiff_hip import volume_brain as VBR
     vol, scale, labels, affine = _stored(kind, spacing)
-    raw, values = _raw(vol, scale, affine), R.values_float32(vol, *scale)
+    raw, values = VS.raw_volume(vol, scale, affine), R.values_float32(vol, *scale)
     for options in (dict(), dict(keep_holes=True), dict(bins=64)):
         want, want_report, _ = B.brain_mask(values, spacing=spacing, **RADII, **options)
         mask, report = VBR.brain_mask(raw, DEV, **RADII, **options)
         print(kind, spacing, options, report)
         assert mask.dtype == torch.uint8 and tuple(mask.shape) == vol.shape[::-1]
-        assert np.array_equal(_host(mask), want.astype(np.uint8))
+        assert np.array_equal(VS.to_host_xyz(mask), want.astype(np.uint8))
         assert report == want_report and report['threshold'] is not None and report['spacing'] == list(spacing)
         if not options.get('keep_holes'):
-            assert B.properties(_host(mask), labels, spacing, RADII['dilate_mm']) == dict(no_scalp=True, no_air=True, ventricle=True, bridge_cut=True,
+            assert B.properties(VS.to_host_xyz(mask), labels, spacing, RADII['dilate_mm']) == dict(no_scalp=True, no_air=True, ventricle=True, bridge_cut=True,
                                                                                          short_of_scalp=True, brain=True)
     if kind == 'f4':
         assert report['candidates'] == int((labels != B.AIR).sum())                    # the NaN and the inf are no candidates
@@ -133,7 +113,7 @@ def test_brain_mask_is_the_restatement(kind, spacing):
     stripped = VBR.apply_mask(raw, mask, DEV)                                          # applying it: the volume's own geometry
     got = stripped.values_float32()
     assert got.shape == raw.shape and stripped.affine is raw.affine and stripped.header is raw.header
-    keep = _host(mask) != 0
+    keep = VS.to_host_xyz(mask) != 0
     assert np.array_equal(got[keep].view(np.uint32), values[keep].view(np.uint32)) and not got[~keep].any()
 
 
@@ -144,17 +124,17 @@ def test_degenerate_inputs_come_back_untouched():
     two = np.full((9, 8, 7), 7.0, '<f4', order='F')
     two[4:, 4:, 4:], two[0, 0, 0] = 0.0, np.nan
     for vol in (np.zeros((9, 8, 7), np.int16, order='F'), np.full((9, 8, 7), 5, np.int16, order='F'), two):
-        mask, report = VBR.brain_mask(_raw(vol), DEV)
+        mask, report = VBR.brain_mask(VS.raw_volume(vol), DEV)
         assert mask is None and report['threshold'] is None and report['kept'] == 0
         assert report == B.brain_mask(R.values_float32(vol))[1]
     assert (report['lo'], report['hi'], report['candidates']) == (7.0, 7.0, 9 * 8 * 7 - 5 * 4 * 3 - 1)
     block = np.zeros((20, 18, 16), np.int16, order='F')
     block[:] = 10
     block[6:13, 6:12, 5:11] = 900
-    mask, report = VBR.brain_mask(_raw(block), DEV, erode_mm=4.0, dilate_mm=5.0)
+    mask, report = VBR.brain_mask(VS.raw_volume(block), DEV, erode_mm=4.0, dilate_mm=5.0)
     assert mask is None and report['threshold'] is not None and (report['tissue'], report['eroded'], report['core'], report['kept']) == (7 * 6 * 6, 0, 0, 0)
     assert report == B.brain_mask(R.values_float32(block), erode_mm=4.0, dilate_mm=5.0)[1]
-    mask, report = VBR.brain_mask(_raw(block), DEV, erode_mm=2.0, dilate_mm=2.0)        # (one voxel less and something is left)
+    mask, report = VBR.brain_mask(VS.raw_volume(block), DEV, erode_mm=2.0, dilate_mm=2.0)        # (one voxel less and something is left)
     assert mask is not None and report == B.brain_mask(R.values_float32(block), erode_mm=2.0, dilate_mm=2.0)[1] and report['eroded'] > 0
 
 
@@ -211,63 +191,25 @@ def _on_shifted_grid(vol):
     return out
 
 
-def _payload(path):
-    with gzip.open(path, 'rb') as f:
-        return f.read()
-
-
 @pytest.fixture(scope='module')
 def runs(tmp_path_factory):
     from mudiff_hip import volume as V
     tmp = tmp_path_factory.mktemp('stripped')
-    cfg = O.default_config(image_size=16, num_channels_dae=16, ch_mult=[1, 2], attn_resolutions=(4,), num_res_blocks=1)
-    exp = tmp / 'results' / 'exp0'
-    exp.mkdir(parents=True)
-    for which, name in (('g1', 'gen_diffusive_1'), ('g2', 'gen_diffusive_2')):
-        torch.save({'module.' + k: v for k, v in O.make_state_dict(cfg, which, 9).items()}, str(exp / f'{name}.pth'))
+    VS.write_tiny_model(tmp)
     p = {k: str(tmp / f'{k}.nii.gz') for k in ('flair', 't2', 't1')}
     grid = np.eye(4)
     grid[:3, 3] = SHIFT
     V.write_nifti(p['t1'], np.asfortranarray(B.phantom()[0]), np.eye(4))
     for seed, k in ((12, 'flair'), (13, 't2')):
         V.write_nifti(p[k], np.asfortranarray(_on_shifted_grid(B.phantom(seed=seed)[0])), grid)
-    model = ['--target_modality', 'T1CE', '--exp', 'exp0', '--output_path', str(tmp / 'results'), '--image_size', '16', '--num_channels_dae',
-             '16', '--ch_mult', '1', '2', '--attn_resolutions', '4', '--num_res_blocks', '1', '--slice_half_range', '2', '--batch_size', '5',
-             '--seed', '31', '--resize_back', '--regrid']
+    model = VS.model_argv(tmp, 2, 5, '--resize_back', '--regrid')
     inputs = ['--input_flair', p['flair'], '--input_t2', p['t2'], '--input_t1', p['t1']]
     brain = ['--brain_extract', '--brain_mask_out', '--brain_erode_mm', str(RADII['erode_mm']), '--brain_dilate_mm', str(RADII['dilate_mm'])]
     jobs = {'brain_host': brain, 'brain_dev': brain + ['--device_intake'], 'plain': [], 'unparsed': []}
     jobs = {k: model + inputs + a + ['--output_dir', str(tmp / k)] for k, a in jobs.items()}
-    log = str(tmp / 'log.json')
-    code = f'''
-        import contextlib, io, json, warnings
-        from mudiff_hip import volume as V
-        log = {{}}
-        for name, argv in {jobs!r}.items():
-            out = io.StringIO()
-            args = V.build_argparser(argv)
-            if name == 'unparsed':                 # the options as a parser without the new flags leaves them
-                for k in [k for k in vars(args) if k.startswith('brain_')]:
-                    delattr(args, k)
-            with contextlib.redirect_stdout(out), warnings.catch_warnings():
-                warnings.simplefilter('ignore', RuntimeWarning)
-                V.predict_volume(args)
-            log[name] = out.getvalue()
-        json.dump(log, open({log!r}, 'w'))
-    '''
-    env = dict(os.environ, PYTHONPATH=os.pathsep.join([REPO, PKG, os.environ.get('PYTHONPATH', '')]), MUD_DETERMINISTIC='1')
-    for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE'):
-        env.pop(k, None)
-    c = subprocess.run([sys.executable, '-c', textwrap.dedent(code)], cwd=REPO, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                       timeout=600)
-    assert c.returncode == 0, c.stdout[-3000:] + c.stderr[-3000:]
-    return dict(tmp=tmp, log=json.load(open(log)), pred=lambda k: _payload(str(tmp / k / 'predicted_t1ce.nii.gz')))
-
-
-def _done(runs, name):
-    lines = [ln for ln in runs['log'][name].splitlines() if ln.startswith('[done]')]
-    assert len(lines) == 1
-    return lines[0]
+    strip = {'unparsed': ['brain_']}                                               # the options as a parser without the new flags leaves them
+    log = VS.run_plan(tmp, [VS.volume_step(k, argv, strip=strip.get(k, [])) for k, argv in jobs.items()], 600, ignore='RuntimeWarning')
+    return dict(tmp=tmp, log=log, pred=lambda k: VS.payload(str(tmp / k / 'predicted_t1ce.nii.gz')))
 
 
 def test_predict_volume_brain_extract_end_to_end(runs):
@@ -277,20 +219,20 @@ def test_predict_volume_brain_extract_end_to_end(runs):
     want, want_report, _ = B.brain_mask(t1_on_grid, **RADII)
     assert B.properties(want, _on_shifted_grid(B.phantom()[1]), (1.0, 1.0, 1.0), RADII['dilate_mm'])['no_scalp']
     for name in ('brain_host', 'brain_dev'):
-        assert _done(runs, name).endswith(' | brain=T1') and ' | regrid=T1' in _done(runs, name)
+        assert VS.done_line(runs['log'][name]).endswith(' | brain=T1') and ' | regrid=T1' in VS.done_line(runs['log'][name])
         assert sorted(os.listdir(tmp / name)) == ['brain_t1ce.json', 'brain_t1ce_mask.nii.gz', 'predicted_t1ce.nii.gz']
         assert json.load(open(tmp / name / 'brain_t1ce.json')) == dict(want_report, source='T1')
         mask, affine, _ = V.read_nifti(str(tmp / name / 'brain_t1ce_mask.nii.gz'))
         assert np.array_equal(np.asarray(mask), want.astype(np.uint8)) and np.array_equal(np.asarray(affine)[:3, 3], SHIFT)
     assert runs['pred']('brain_host') == runs['pred']('brain_dev')                     # host file == device file
-    assert _payload(str(tmp / 'brain_host' / 'brain_t1ce_mask.nii.gz')) == _payload(str(tmp / 'brain_dev' / 'brain_t1ce_mask.nii.gz'))
+    assert VS.payload(str(tmp / 'brain_host' / 'brain_t1ce_mask.nii.gz')) == VS.payload(str(tmp / 'brain_dev' / 'brain_t1ce_mask.nii.gz'))
     assert runs['pred']('brain_host') != runs['pred']('plain')
 
 
 def test_without_the_flag_nothing_changes(runs):
     tmp = runs['tmp']
     assert runs['pred']('plain') == runs['pred']('unparsed')
-    assert _done(runs, 'plain').replace(str(tmp / 'plain'), 'OUT') == _done(runs, 'unparsed').replace(str(tmp / 'unparsed'), 'OUT')
+    assert VS.done_line(runs['log']['plain']).replace(str(tmp / 'plain'), 'OUT') == VS.done_line(runs['log']['unparsed']).replace(str(tmp / 'unparsed'), 'OUT')
     for name in ('plain', 'unparsed'):
-        assert 'brain' not in runs['log'][name] and _done(runs, name).endswith(' | regrid=T1')
+        assert 'brain' not in runs['log'][name] and VS.done_line(runs['log'][name]).endswith(' | regrid=T1')
         assert sorted(os.listdir(tmp / name)) == ['predicted_t1ce.nii.gz']

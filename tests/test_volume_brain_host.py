@@ -9,6 +9,7 @@ import pytest
 
 import volume_brain_ref as B
 import volume_intake_ref as R
+from volume_support import cli_argv
 
 
 @pytest.mark.parametrize('spacing', [(1.0, 1.0, 1.0), (0.7, 1.3, 2.1)])
@@ -64,15 +65,11 @@ def test_the_restatement_strips_the_phantom(head):
     assert nothing is None and report['eroded'] == 0 and report['tissue'] > 0 and report['threshold'] is not None
 
 
-def _argv(*extra):
-    return ['--target_modality', 'T1CE', '--output_dir', 'out', '--exp', 'e'] + list(extra)
-
-
 def test_flags_defaults_and_refusals(capsys):
     from mudiff_hip import volume as V
     from mudiff_hip import volume_brain as VBR
     from mudiff_hip.volume_prepare import IntakeOptions
-    args = V.build_argparser(_argv())
+    args = V.build_argparser(cli_argv())
     assert args.brain_extract is False and args.brain_from is None and (args.brain_erode_mm, args.brain_dilate_mm, args.brain_bins) == (5.0, 6.0, 256)
     assert args.brain_keep_holes is False and args.brain_mask_out is False
     assert VBR.DEFAULTS == dict(bins=256, erode_mm=5.0, dilate_mm=6.0, keep_holes=False)
@@ -80,17 +77,17 @@ def test_flags_defaults_and_refusals(capsys):
     assert IntakeOptions.from_args(args).brain is None and IntakeOptions.from_args(args) == IntakeOptions('percentile', False, None, None, 80)
     assert IntakeOptions._fields[-1] == 'denoise' and IntakeOptions._fields.index('foreground') + 1 == IntakeOptions._fields.index('brain')
     assert IntakeOptions().brain is None
-    assert IntakeOptions.from_args(V.build_argparser(_argv('--brain_extract'))).brain == dict(VBR.DEFAULTS, source=None, mask_out=False)
-    args = V.build_argparser(_argv('--brain_extract', '--brain_from', 'T2', '--brain_erode_mm', '3', '--brain_dilate_mm', '4.5', '--brain_bins', '64',
+    assert IntakeOptions.from_args(V.build_argparser(cli_argv('--brain_extract'))).brain == dict(VBR.DEFAULTS, source=None, mask_out=False)
+    args = V.build_argparser(cli_argv('--brain_extract', '--brain_from', 'T2', '--brain_erode_mm', '3', '--brain_dilate_mm', '4.5', '--brain_bins', '64',
                                    '--brain_keep_holes', '--brain_mask_out', '--foreground'))
     options = IntakeOptions.from_args(args)
     assert options.brain == dict(bins=64, erode_mm=3.0, dilate_mm=4.5, keep_holes=True, source='T2', mask_out=True) and options.foreground is not None
-    assert IntakeOptions.from_args(V.build_argparser(_argv('--brain_erode_mm', '3'))).brain is None      # (the flag itself is missing)
+    assert IntakeOptions.from_args(V.build_argparser(cli_argv('--brain_erode_mm', '3'))).brain is None      # (the flag itself is missing)
     for bad, word in ((['--brain_bins', '15'], 'brain_bins'), (['--brain_bins', '1025'], 'brain_bins'), (['--brain_erode_mm', '0'], 'brain_erode_mm'),
                       (['--brain_erode_mm', 'nan'], 'brain_erode_mm'), (['--brain_dilate_mm', '4'], 'brain_dilate_mm'),
                       (['--brain_dilate_mm', 'inf'], 'brain_dilate_mm')):
         with pytest.raises(SystemExit):
-            V.build_argparser(_argv('--brain_extract', *bad))
+            V.build_argparser(cli_argv('--brain_extract', *bad))
         assert word in capsys.readouterr().err
     nan, inf = float('nan'), float('inf')
     for kw, word in ((dict(bins=8), '--brain_bins'), (dict(bins=2048), '--brain_bins'), (dict(bins=64.5), '--brain_bins'),
@@ -104,7 +101,7 @@ def test_flags_defaults_and_refusals(capsys):
     help_text = ' '.join(V.make_parser().format_help().split())
     assert 'morphological estimate, not a learned brain extraction' in help_text and '--brain_mask_out' in help_text
     from mudiff_hip import cohort
-    assert cohort.build_argparser(_argv('--manifest', 'm.tsv', '--brain_extract', '--brain_erode_mm', '4')).brain_erode_mm == 4.0
+    assert cohort.build_argparser(cli_argv('--manifest', 'm.tsv', '--brain_extract', '--brain_erode_mm', '4')).brain_erode_mm == 4.0
 
 
 def test_the_source_input():

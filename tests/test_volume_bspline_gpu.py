@@ -4,22 +4,16 @@ axes longer than a tile of the x pass and than a workgroup of the y and z passes
 clamp; the C ABI's argument checks; volume_regrid.regrid_to(mode='cubic'); then `predict_volume --regrid --regrid_interp cubic` against
 the same run on inputs resampled beforehand, byte for byte, --coregister with the flag, and the flag's default."""
 import ctypes as C
-import gzip
-import json
 import os
-import subprocess
-import sys
-import textwrap
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import PKG, REPO
 import volume_bspline_ref as S
 import volume_intake_ref as R
 import volume_regrid_ref as G
-from oracle import mudiff_oracle as O
+import volume_support as VS
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -30,16 +24,10 @@ def _bits(a):
     return np.ascontiguousarray(a).view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
 
 
-def _raw(vol, scale=(1.0, 0.0), affine=None):
-    from mudiff_hip import volume_intake as VI
-    return VI.RawVolume(np.ascontiguousarray(vol.reshape(-1, order='F')), R.CODES[vol.dtype.str[1:]], '<', float(np.float32(scale[0])),
-                        float(np.float32(scale[1])), vol.shape, np.eye(4) if affine is None else affine, None)
-
-
 def _stored(vol, scale=(1.0, 0.0)):
     """-> (the device array of the stored voxels, datatype code, slope, inter, the fp32 values the pipeline sees)."""
     from mudiff_hip import volume_intake as VI
-    raw = _raw(vol, scale)
+    raw = VS.raw_volume(vol, scale)
     slope, inter = (raw.slope, raw.inter) if raw.scaled else (1.0, 0.0)
     return VI.upload(raw, DEV), raw.code, slope, inter, np.asfortranarray(R.values_float32(vol, *scale))
 
@@ -195,7 +183,7 @@ def test_c_abi_rejects_bad_arguments_without_launching():
 def test_regrid_to_cubic(prepared):
     from mudiff_hip import volume_regrid as VR
     vol, scale = _sources()['i2']
-    raw = _raw(vol, scale)
+    raw = VS.raw_volume(vol, scale)
     assert VR.regrid_to(raw, vol.shape, np.eye(4), DEV, 'cubic') is raw             # on the grid already: untouched
     aff = _matrix('oblique')                                                       # the reference's affine, the source's being the identity
     found = {}
@@ -208,7 +196,7 @@ def test_regrid_to_cubic(prepared):
     assert not np.array_equal(linear, want) and (linear == 0).any() and not want[linear == 0].any()      # another interpolant, no new tissue
     nan = np.asfortranarray(vol.astype('f4'))
     nan[3, 3, 3] = np.nan
-    VR.regrid_to(_raw(nan), OUT_SHAPE, aff, DEV, 'cubic', found=found)
+    VR.regrid_to(VS.raw_volume(nan), OUT_SHAPE, aff, DEV, 'cubic', found=found)
     assert found == {'nonfinite': 1}
     with pytest.raises(ValueError, match='mode must be one of'):
         VR.regrid_to(raw, OUT_SHAPE, aff, DEV, 'sinc')
@@ -217,11 +205,6 @@ def test_regrid_to_cubic(prepared):
 # ---------------------------------------------------------------------------------------------------
 # end to end: the tiny model of tests/test_volume_regrid_gpu.py, inputs on three grids
 # ---------------------------------------------------------------------------------------------------
-def _payload(path):
-    with gzip.open(path, 'rb') as f:
-        return f.read()
-
-
 def _affine(lin, centre_of):
     a = np.eye(4)
     a[:3, :3] = lin
@@ -234,11 +217,7 @@ def runs(tmp_path_factory):
     """One child process for every sampling run of this module: the log of each run."""
     from mudiff_hip import volume as V
     tmp = tmp_path_factory.mktemp('bspline')
-    cfg = O.default_config(image_size=16, num_channels_dae=16, ch_mult=[1, 2], attn_resolutions=(4,), num_res_blocks=1)
-    exp = tmp / 'results' / 'exp0'
-    exp.mkdir(parents=True)
-    for which, name in (('g1', 'gen_diffusive_1'), ('g2', 'gen_diffusive_2')):
-        torch.save({'module.' + k: v for k, v in O.make_state_dict(cfg, which, 9).items()}, str(exp / f'{name}.pth'))
+    VS.write_tiny_model(tmp)
     rng = np.random.default_rng(7)
     ref_shape, obl_shape = (16, 16, 9), (18, 14, 11)
     ref_aff = _affine(np.diag([1.0, 1.0, 2.5]), ref_shape)
@@ -253,9 +232,7 @@ def runs(tmp_path_factory):
     V.write_nifti(p['flair'], volume(ref_shape, 'f4'), ref_aff)
     R.write_nifti_typed(p['t2'], volume(obl_shape, 'i2'), affine=obl_aff)
     R.write_nifti_typed(p['t1'], volume(ref_shape, 'i2'), '<', 0.5, 3.0, affine=shift_aff)
-    model = ['--target_modality', 'T1CE', '--exp', 'exp0', '--output_path', str(tmp / 'results'), '--image_size', '16', '--num_channels_dae',
-             '16', '--ch_mult', '1', '2', '--attn_resolutions', '4', '--num_res_blocks', '1', '--slice_half_range', '3', '--batch_size', '4',
-             '--seed', '31']
+    model = VS.model_argv(tmp, 3, 4)
     raw_in = ['--input_flair', p['flair'], '--input_t2', p['t2'], '--input_t1', p['t1']]
     pre_in = ['--input_flair', p['flair'], '--input_t2', p['t2_pre'], '--input_t1', p['t1_pre']]
     jobs = {'cubic_host': raw_in + ['--regrid', '--regrid_interp', 'cubic'],
@@ -263,38 +240,14 @@ def runs(tmp_path_factory):
             'coreg': raw_in + ['--coregister', '--coregister_strides', '4', '--regrid_interp', 'cubic'],
             'linear_flag': raw_in + ['--regrid', '--regrid_interp', 'linear'], 'no_flag': raw_in + ['--regrid']}
     jobs = {k: model + a + ['--output_dir', str(tmp / k)] for k, a in jobs.items()}
-    log = str(tmp / 'log.json')
-    code = f'''
-        import contextlib, io, json
-        from mudiff_hip import volume as V, volume_intake as VI, volume_regrid as VR
-        p, dev = {p!r}, 'cuda:0'
-        ref = VI.read_nifti_raw(p['flair'])
-        world = VR.world_affine_of(ref.affine, ref.header)
-        for k in ('t2', 't1'):                                                     # the offline resampling
-            r = VR.regrid_to(VI.read_nifti_raw(p[k]), ref.shape, world, dev, 'cubic')
-            assert isinstance(r, VR.RegriddedVolume) and r.code == 16 and r.shape == ref.shape
-            V.write_nifti(p[k + '_pre'], r.values_float32(), ref.affine)
-        log = {{}}
-        for name, argv in {jobs!r}.items():
-            out = io.StringIO()
-            with contextlib.redirect_stdout(out):
-                V.predict_volume(V.build_argparser(argv))
-            log[name] = out.getvalue()
-        json.dump(log, open({log!r}, 'w'))
-    '''
-    env = dict(os.environ, PYTHONPATH=os.pathsep.join([REPO, PKG, os.environ.get('PYTHONPATH', '')]), MUD_DETERMINISTIC='1')
-    for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE'):
-        env.pop(k, None)
-    c = subprocess.run([sys.executable, '-c', textwrap.dedent(code)], cwd=REPO, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                       timeout=900)
-    assert c.returncode == 0, c.stdout[-3000:] + c.stderr[-3000:]
-    return dict(tmp=tmp, paths=p, log=json.load(open(log)), pred=lambda k: _payload(str(tmp / k / 'predicted_t1ce.nii.gz')))
+    offline = [VS.regrid_step(p[k], p['flair'], p[k + '_pre'], 'cubic') for k in ('t2', 't1')]
+    log = VS.run_plan(tmp, offline + [VS.volume_step(k, argv) for k, argv in jobs.items()], 900)
+    return dict(tmp=tmp, paths=p, log=log, pred=lambda k: VS.payload(str(tmp / k / 'predicted_t1ce.nii.gz')))
 
 
-def _done(runs, name):
-    lines = [ln for ln in runs['log'][name].splitlines() if ln.startswith('[done]')]
-    assert len(lines) == 1
-    return lines[0].replace(os.path.join(str(runs['tmp']), name), 'OUT')
+def _done_out(runs, name):
+    """The run's [done] line with its own output directory replaced."""
+    return VS.done_line(runs['log'][name]).replace(os.path.join(str(runs['tmp']), name), 'OUT')
 
 
 def test_cubic_run_writes_the_file_of_the_run_on_resampled_inputs(runs):
@@ -302,16 +255,16 @@ def test_cubic_run_writes_the_file_of_the_run_on_resampled_inputs(runs):
     assert runs['pred']('cubic_host') == want and runs['pred']('cubic_dev') == want
     assert want != runs['pred']('no_flag')                                         # (the interpolant reaches the prediction)
     for name in ('cubic_host', 'cubic_dev'):
-        assert _done(runs, name).endswith(' | regrid=T2,T1 | interp=cubic')
-    assert ' | interp=' not in _done(runs, 'pre') and ' | regrid=' not in _done(runs, 'pre')
+        assert _done_out(runs, name).endswith(' | regrid=T2,T1 | interp=cubic')
+    assert ' | interp=' not in _done_out(runs, 'pre') and ' | regrid=' not in _done_out(runs, 'pre')
 
 
 def test_coregister_with_the_flag(runs):
-    line = _done(runs, 'coreg')
+    line = _done_out(runs, 'coreg')
     assert ' | regrid=T2,T1 | interp=cubic | coreg=' in line
     assert os.path.exists(runs['tmp'] / 'coreg' / 'coreg_t1ce.json') and len(runs['pred']('coreg')) > 0
 
 
 def test_linear_is_the_default(runs):
     assert runs['pred']('linear_flag') == runs['pred']('no_flag')
-    assert _done(runs, 'linear_flag') == _done(runs, 'no_flag') and _done(runs, 'no_flag').endswith(' | regrid=T2,T1')
+    assert _done_out(runs, 'linear_flag') == _done_out(runs, 'no_flag') and _done_out(runs, 'no_flag').endswith(' | regrid=T2,T1')

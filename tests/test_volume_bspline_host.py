@@ -6,6 +6,7 @@ import pytest
 
 import volume_bspline_ref as S
 import volume_regrid_ref as G
+from volume_support import cli_argv
 
 SCIPY_BOUND = 1e-12                                      # of max |v|: about 100 x what the recursion differs from scipy's by (8e-15, 9 x 7 x 5)
 
@@ -99,10 +100,6 @@ def test_it_is_sharper_than_trilinear():
     assert inside.sum() >= 0.5 * inside.size and cubic < linear
 
 
-def _argv(*extra):
-    return ['--target_modality', 'T1CE', '--output_dir', 'out', '--exp', 'e'] + list(extra)
-
-
 def test_the_flag_the_options_and_the_done_line(capsys):
     from mudiff_hip import cohort
     from mudiff_hip import volume as V
@@ -110,18 +107,18 @@ def test_the_flag_the_options_and_the_done_line(capsys):
     from mudiff_hip import volume_regrid as VR
     from mudiff_hip.volume_prepare import IntakeOptions, IntakeReport
     assert VR.MODES == {'linear': 0, 'nearest': 1} and VR.MODES_HIGH == ('cubic',) and VR.INTERPS == ('linear', 'cubic')
-    args = V.build_argparser(_argv())
+    args = V.build_argparser(cli_argv())
     assert args.regrid_interp == 'linear'
     assert IntakeOptions.from_args(args).interp == 'linear' and IntakeOptions.from_args(args) == IntakeOptions('percentile', False, None, None, 80)
     assert IntakeOptions._fields[-1] == 'denoise' and IntakeOptions._fields.index('half_range') == 4 and IntakeOptions().interp == 'linear'
-    options = IntakeOptions.from_args(V.build_argparser(_argv('--regrid', '--regrid_interp', 'cubic')))
+    options = IntakeOptions.from_args(V.build_argparser(cli_argv('--regrid', '--regrid_interp', 'cubic')))
     assert options.interp == 'cubic' and options.regrid is True and options.coreg is None
-    assert cohort.build_argparser(_argv('--manifest', 'm.tsv', '--coregister', '--regrid_interp', 'cubic')).regrid_interp == 'cubic'
-    assert cohort.build_argparser(_argv('--manifest', 'm.tsv')).regrid_interp == 'linear'
+    assert cohort.build_argparser(cli_argv('--manifest', 'm.tsv', '--coregister', '--regrid_interp', 'cubic')).regrid_interp == 'cubic'
+    assert cohort.build_argparser(cli_argv('--manifest', 'm.tsv')).regrid_interp == 'linear'
     metrics = VM.build_parser()
     assert metrics.parse_args(['--pred', 'p', '--gt', 'g']).regrid_interp == 'linear'
     assert metrics.parse_args(['--pred', 'p', '--gt', 'g', '--regrid', '--regrid_interp', 'cubic']).regrid_interp == 'cubic'
-    for build in (lambda: V.build_argparser(_argv('--regrid_interp', 'sinc')), lambda: metrics.parse_args(['--pred', 'p', '--gt', 'g', '--regrid_interp', 'nearest'])):
+    for build in (lambda: V.build_argparser(cli_argv('--regrid_interp', 'sinc')), lambda: metrics.parse_args(['--pred', 'p', '--gt', 'g', '--regrid_interp', 'nearest'])):
         with pytest.raises(SystemExit):
             build()
         assert 'regrid_interp' in capsys.readouterr().err

@@ -16,6 +16,7 @@ import volume_conform_ref as CR
 import volume_intake_ref as I
 import volume_regrid_ref as G
 import volume_reorient_ref as R
+import volume_support as VS
 
 pytestmark = pytest.mark.gpu
 
@@ -24,7 +25,6 @@ W1, W3, W11 = (CR.weights(CR.sigma(f)) for f in (1.25, 2.0, 8.0))          # R =
 SIGMA_SETS = {'x': [W3, None, None], 'y': [None, W3, None], 'z': [None, None, W3], 'xyz': [W1, W3, W11], 'zyx': [W11, W1, W3],
               'none': [None, None, None]}
 KINDS = {'u1': ('<u1', 0.0, 0.0), 'i2_scaled': ('<i2', 0.5, -3.0), 'u2': ('<u2', 0.0, 0.0), 'i4': ('<i4', 0.0, 0.0), 'f4': ('<f4', 0.0, 0.0)}
-CODES = {'u1': 2, 'i2': 4, 'i4': 8, 'f4': 16, 'u2': 512}
 SIGNED = {'u1': np.uint8, 'i2': np.int16, 'u2': np.int16, 'i4': np.int32, 'f4': np.float32}      # torch has no wide unsigned dtypes
 SENTINEL = 0xA5
 
@@ -62,7 +62,7 @@ def test_kernel_against_the_restatement(shape):
         dev = _device(vol)
         scaling = (slope, inter) if I.is_scaled(slope, inter) else (1.0, 0.0)
         for name, ws in SIGMA_SETS.items():
-            out, bad = ops.volume_lowpass(dev, CODES[dtype[1:]], shape, *scaling, ws)
+            out, bad = ops.volume_lowpass(dev, I.CODES[dtype[1:]], shape, *scaling, ws)
             if name == 'none':                           # nothing to filter: nothing launched, the caller keeps the stored voxels
                 assert out is None and bad == 0
                 continue
@@ -71,7 +71,7 @@ def test_kernel_against_the_restatement(shape):
             assert out.dtype == torch.float32 and tuple(out.shape) == shape[::-1] and bad == 0
             assert _within_one_ulp(got, want), (kind, name, float(np.abs(got - want).max()))
             assert got.min() >= values.min() and got.max() <= values.max(), (kind, name)          # a weighted mean stays inside the range
-            again, _ = ops.volume_lowpass(dev, CODES[dtype[1:]], shape, *scaling, ws)
+            again, _ = ops.volume_lowpass(dev, I.CODES[dtype[1:]], shape, *scaling, ws)
             assert torch.equal(again, out), (kind, name)                                           # two runs: the same bits
 
 
@@ -135,7 +135,7 @@ def test_nothing_is_written_out_of_range(shape):
             out = torch.full((band + 4 * n + band,), SENTINEL, dtype=torch.uint8, device='cuda')
             scratch = torch.full((band + 4 * n + band,), SENTINEL, dtype=torch.uint8, device='cuda')
             count = torch.full((3,), -1, dtype=torch.int32, device='cuda')
-            assert _call(src.data_ptr() + band, CODES[dtype[1:]], shape, (1.0, 0.0), ws, out.data_ptr() + band, scratch.data_ptr() + band,
+            assert _call(src.data_ptr() + band, I.CODES[dtype[1:]], shape, (1.0, 0.0), ws, out.data_ptr() + band, scratch.data_ptr() + band,
                          count.data_ptr() + 4) == 0
             for buf in (out, scratch):
                 assert bool((buf[:band] == SENTINEL).all()) and bool((buf[band + 4 * n:] == SENTINEL).all()), (dtype, len(ws))
@@ -213,11 +213,6 @@ def regrid_case(tilt=12.0, spacing=(0.5, 0.5, 2.0)):
     return vol, src, REF_SHAPE, ref
 
 
-def _raw(vol, affine):
-    from mudiff_hip.volume_intake import RawVolume
-    return RawVolume(np.ascontiguousarray(vol.reshape(-1, order='F')), CODES[vol.dtype.kind + str(vol.dtype.itemsize)], '<', 1.0, 0.0, vol.shape, np.asarray(affine, np.float64), None)
-
-
 def test_regrid_to_antialiased():
     """The bar is the restatement's own: on this case the chain with fp32 between the passes (what the kernels do) and the chain with
     fp64 throughout differ by 1.052e-4 at most (measured on the CPU, at values up to 1071: the fp32 roundings, 6.1e-5 each at that size, of
@@ -234,26 +229,26 @@ def test_regrid_to_antialiased():
     print(f'restatement fp32 vs fp64 intermediates: {own:.3e}')
     assert own <= REGRID_BAR / 4
     found = {}
-    out = VR.regrid_to(_raw(vol, src), ref_shape, ref, device, antialias=True, found=found, name='case')
+    out = VR.regrid_to(VS.raw_volume(vol, affine=src), ref_shape, ref, device, antialias=True, found=found, name='case')
     got = out.values_float32()
     err = float(np.abs(got - want).max())
     print(f'device vs restatement: {err:.3e}')
     assert err <= REGRID_BAR
     assert found['lowpass'] is True and found['nonfinite'] == 0 and found['antialias']['radii'] == [3, 3, 0]
-    plain = VR.regrid_to(_raw(vol, src), ref_shape, ref, device)
+    plain = VR.regrid_to(VS.raw_volume(vol, affine=src), ref_shape, ref, device)
     assert float(np.abs(plain.values_float32() - got).max()) > 10                                  # the filter does something here
-    off = VR.regrid_to(_raw(vol, src), ref_shape, ref, device, antialias=False)
+    off = VR.regrid_to(VS.raw_volume(vol, affine=src), ref_shape, ref, device, antialias=False)
     assert torch.equal(off.dev, plain.dev)
     # a pure 12 degree rotation at equal spacing: nothing is filtered, the result is today's bit for bit (linear and cubic)
     vol, src, ref_shape, ref = regrid_case(spacing=(1.0, 1.0, 1.0))
     for mode in ('linear', 'cubic'):
         found = {}
-        a = VR.regrid_to(_raw(vol, src), ref_shape, ref, device, mode=mode, antialias=True, found=found)
-        b = VR.regrid_to(_raw(vol, src), ref_shape, ref, device, mode=mode)
+        a = VR.regrid_to(VS.raw_volume(vol, affine=src), ref_shape, ref, device, mode=mode, antialias=True, found=found)
+        b = VR.regrid_to(VS.raw_volume(vol, affine=src), ref_shape, ref, device, mode=mode)
         assert torch.equal(a.dev, b.dev) and found['lowpass'] is False and found['antialias']['radii'] == [0, 0, 0]
     # a label volume is never filtered
-    a = VR.regrid_to(_raw(vol, src * np.array([2.0, 2.0, 2.0, 1.0])), ref_shape, ref, device, mode='nearest', antialias=True)
-    b = VR.regrid_to(_raw(vol, src * np.array([2.0, 2.0, 2.0, 1.0])), ref_shape, ref, device, mode='nearest')
+    a = VR.regrid_to(VS.raw_volume(vol, affine=src * np.array([2.0, 2.0, 2.0, 1.0])), ref_shape, ref, device, mode='nearest', antialias=True)
+    b = VR.regrid_to(VS.raw_volume(vol, affine=src * np.array([2.0, 2.0, 2.0, 1.0])), ref_shape, ref, device, mode='nearest')
     assert torch.equal(a.dev, b.dev)
 
 
@@ -265,9 +260,9 @@ def test_stripes_on_the_device():
     vol = np.asfortranarray(CR.stripes(shape).astype('<i2'))
     src, ref, ref_shape = np.diag([0.5, 1.0, 1.0, 1.0]), np.eye(4), (32, 6, 5)
     device = torch.device('cuda:0')
-    plain = VR.regrid_to(_raw(vol, src), ref_shape, ref, device).values_float32()
+    plain = VR.regrid_to(VS.raw_volume(vol, affine=src), ref_shape, ref, device).values_float32()
     assert np.array_equal(plain, np.zeros(ref_shape, np.float32))
-    got = VR.regrid_to(_raw(vol, src), ref_shape, ref, device, antialias=True).values_float32()
+    got = VR.regrid_to(VS.raw_volume(vol, affine=src), ref_shape, ref, device, antialias=True).values_float32()
     assert float(np.abs(got[2:-2] - 100.0).max()) <= 13.86 and float(got[2:-2].min()) > 86.0
     want = G.trilinear(CR.lowpass(vol.astype(np.float32), [W3, None, None])[0], G.matrix(src, ref), ref_shape)
     assert _within_one_ulp(got, want)
@@ -340,39 +335,20 @@ def _write(path, vol, affine, spacing):
     return str(path)
 
 
-def _payload(path):
-    import gzip
-    with gzip.open(path, 'rb') as f:
-        return f.read()
-
-
 CONFORM = ['--conform', '--conform_shape', '24', '24', '16', '--conform_spacing', '2']
 NESTED = ['--reorient', '--reorient_back'] + CONFORM + ['--conform_back']      # both writers, --reorient_back inside --conform_back
 
 
 @pytest.fixture(scope='module')
 def runs(tmp_path_factory):
-    import json
-    import os
-    import subprocess
-    import sys
-    import textwrap
-    from conftest import PKG, REPO
-    from oracle import mudiff_oracle as O
     tmp = tmp_path_factory.mktemp('conform')
-    cfg = O.default_config(image_size=16, num_channels_dae=16, ch_mult=[1, 2], attn_resolutions=(4,), num_res_blocks=1)
-    exp = tmp / 'results' / 'exp0'
-    exp.mkdir(parents=True)
-    for which, name in (('g1', 'gen_diffusive_1'), ('g2', 'gen_diffusive_2')):
-        torch.save({'module.' + k: v for k, v in O.make_state_dict(cfg, which, 9).items()}, str(exp / f'{name}.pth'))
+    VS.write_tiny_model(tmp)
     files = {}
     for name in 'ABC':
         for which in FIELDS:
             shape, affine = geometry(name, which)
             files[name, which] = _write(tmp / f'{name}_{which}.nii', phantom(which, shape, affine), affine, float(np.linalg.norm(affine[:3, 0])))
-    model = ['--target_modality', 'T1CE', '--exp', 'exp0', '--output_path', str(tmp / 'results'), '--image_size', '16', '--num_channels_dae',
-             '16', '--ch_mult', '1', '2', '--attn_resolutions', '4', '--num_res_blocks', '1', '--slice_half_range', '3', '--batch_size', '7',
-             '--seed', '31', '--resize_back']
+    model = VS.model_argv(tmp, 3, 7, '--resize_back')
     inputs = lambda n: ['--input_flair', files[n, 'flair'], '--input_t2', files[n, 't2'], '--input_t1', files[n, 't1']]      # noqa: E731
     back = CONFORM + ['--conform_back']
     jobs = {'a_plain': inputs('A'), 'a_conform': inputs('A') + CONFORM, 'b_host': inputs('B') + back + ['--gt_volume', files['B', 'gt']],
@@ -388,50 +364,9 @@ def runs(tmp_path_factory):
     scored.write_text('id\tt1\tt1ce\tt2\tflair\tgt\n' + 's_b\t' + '\t'.join([files['B', 't1'], '', files['B', 't2'], files['B', 'flair'], files['B', 'gt']]) + '\n')
     cohorts = {'cohort': model + back + ['--manifest', str(manifest), '--output_dir', str(tmp / 'cohort')],
                'cohort_nested': model + NESTED + ['--score', '--manifest', str(scored), '--output_dir', str(tmp / 'cohort_nested')]}
-    log = str(tmp / 'log.json')
-    code = f'''
-        import contextlib, io, json, warnings
-        import numpy as np, torch
-        from mudiff_hip import cohort as Co, volume as V
-        log, current = {{}}, [None]
-        sample = V.predict_from_conditions
-        def spy(args, plan, evaluation, gen1, gen2, device, stacks, ref, **kw):
-            if current[0] is not None:
-                np.savez({str(tmp)!r} + '/stacks_' + current[0] + '.npz', *[s.cpu().numpy() if torch.is_tensor(s) else np.asarray(s) for s in stacks])
-            return sample(args, plan, evaluation, gen1, gen2, device, stacks, ref, **kw)
-        V.predict_from_conditions = spy
-        for name, argv in {jobs!r}.items():
-            out = io.StringIO()
-            current[0] = name
-            with contextlib.redirect_stdout(out), warnings.catch_warnings():
-                warnings.simplefilter('ignore')
-                V.predict_volume(V.build_argparser(argv))
-            log[name] = out.getvalue()
-        current[0] = None
-        for name, argv in {cohorts!r}.items():
-            out = io.StringIO()
-            with contextlib.redirect_stdout(out), warnings.catch_warnings():
-                warnings.simplefilter('ignore')
-                args = Co.build_argparser(argv)
-                failures = Co.run(args, Co.read_manifest(args.manifest))[1]
-            assert not failures, failures
-            log[name] = out.getvalue()
-        json.dump(log, open({log!r}, 'w'))
-    '''
-    env = dict(os.environ, PYTHONPATH=os.pathsep.join([REPO, PKG, os.environ.get('PYTHONPATH', '')]), MUD_DETERMINISTIC='1')
-    for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE'):
-        env.pop(k, None)
-    c = subprocess.run([sys.executable, '-c', textwrap.dedent(code)], cwd=REPO, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                       timeout=600)
-    assert c.returncode == 0, c.stdout[-3000:] + c.stderr[-3000:]
-    stacks = {k: [v for _, v in sorted(np.load(str(tmp / f'stacks_{k}.npz')).items(), key=lambda kv: int(kv[0].split('_')[1]))] for k in jobs}
-    return dict(tmp=tmp, log=json.load(open(log)), stacks=stacks, files=files)
-
-
-def _done(runs, name, count=1):
-    lines = [ln for ln in runs['log'][name].splitlines() if ln.startswith('[done]')]
-    assert len(lines) == count
-    return lines
+    steps = [VS.volume_step(k, argv, stacks=True) for k, argv in jobs.items()] + [VS.cohort_step(k, argv) for k, argv in cohorts.items()]
+    log = VS.run_plan(tmp, steps, 600, ignore='all')
+    return dict(tmp=tmp, log=log, stacks={k: VS.load_stacks(tmp, k) for k in jobs}, files=files)
 
 
 def test_conform_end_to_end(runs):
@@ -445,9 +380,9 @@ def test_conform_end_to_end(runs):
     from mudiff_hip import volume as V
     tmp = runs['tmp']
     # A: on the conform grid already - no input is resampled and the file is the plain run's, header included
-    assert _payload(str(tmp / 'a_conform' / 'predicted_t1ce.nii.gz')) == _payload(str(tmp / 'a_plain' / 'predicted_t1ce.nii.gz'))
+    assert VS.payload(str(tmp / 'a_conform' / 'predicted_t1ce.nii.gz')) == VS.payload(str(tmp / 'a_plain' / 'predicted_t1ce.nii.gz'))
     assert all(np.array_equal(g, w) for g, w in zip(runs['stacks']['a_conform'], runs['stacks']['a_plain']))
-    assert _done(runs, 'a_conform')[0].endswith(' | conform=24x24x16@2mm:') and 'conform' not in _done(runs, 'a_plain')[0].replace(str(tmp), 'TMP')
+    assert VS.done_line(runs['log']['a_conform']).endswith(' | conform=24x24x16@2mm:') and 'conform' not in VS.done_line(runs['log']['a_plain']).replace(str(tmp), 'TMP')
     entries = json.load(open(tmp / 'a_conform' / 'conform_t1ce.json'))
     assert entries['grid'] == '24x24x16@2mm' and all(not e['resampled'] and e['radii'] == [0, 0, 0] for e in entries['inputs'].values())
     assert sorted(os.listdir(tmp / 'a_plain')) == ['predicted_t1ce.nii.gz']
@@ -479,20 +414,20 @@ def test_conform_end_to_end(runs):
             assert e['resampled'] is True and e['nonfinite'] == 0 and e['shape_from'] == list(C_SHAPE if third else B_SHAPE)
             assert e['radii'] == ([2, 2, 2] if third else [3, 3, 3]) and e['factors'] == pytest.approx([1.6] * 3 if third else [2.0] * 3, abs=1e-6)
             assert e['obliquity_deg'] == pytest.approx(0.0 if third else 12.0, abs=1e-4) and e['spacing_from'] == pytest.approx([1.25 if third else 1.0] * 3, abs=1e-6)
-    assert _done(runs, 'c_host')[0].endswith(' | conform=24x24x16@2mm:FLAIR,T2,T1 | antialias=on')
-    assert _done(runs, 'b_host')[0].endswith(' | regrid=gt_volume | conform=24x24x16@2mm:FLAIR,T2,T1 | antialias=on')      # the ground truth too
-    assert 'shape=(24, 24, 16)' in _done(runs, 'b_host')[0] and 'slices=5..11' in _done(runs, 'b_host')[0]
+    assert VS.done_line(runs['log']['c_host']).endswith(' | conform=24x24x16@2mm:FLAIR,T2,T1 | antialias=on')
+    assert VS.done_line(runs['log']['b_host']).endswith(' | regrid=gt_volume | conform=24x24x16@2mm:FLAIR,T2,T1 | antialias=on')      # the ground truth too
+    assert 'shape=(24, 24, 16)' in VS.done_line(runs['log']['b_host']) and 'slices=5..11' in VS.done_line(runs['log']['b_host'])
     assert sorted(os.listdir(tmp / 'b_host')) == ['conform_t1ce.json', 'metrics_t1ce.json', 'predicted_t1ce.nii.gz']
     # B without the flag: nothing fails (--resize_back), but the generators see other stacks
     plain = runs['stacks']['b_plain']
-    assert plain[0].shape == (7, 60, 60) and 'conform' not in _done(runs, 'b_plain')[0].replace(str(tmp), 'TMP')
+    assert plain[0].shape == (7, 60, 60) and 'conform' not in VS.done_line(runs['log']['b_plain']).replace(str(tmp), 'TMP')
 
 
 def test_cohort_writes_the_single_runs_files(runs):
     tmp = runs['tmp']
-    lines = _done(runs, 'cohort', 2)
+    lines = VS.done_lines(runs['log']['cohort'], 2)
     for n, line in zip('bc', lines):
-        assert _payload(str(tmp / 'cohort' / f's_{n}' / 'predicted_t1ce.nii.gz')) == _payload(str(tmp / f'{n}_dev' / 'predicted_t1ce.nii.gz'))
+        assert VS.payload(str(tmp / 'cohort' / f's_{n}' / 'predicted_t1ce.nii.gz')) == VS.payload(str(tmp / f'{n}_dev' / 'predicted_t1ce.nii.gz'))
         assert open(tmp / 'cohort' / f's_{n}' / 'conform_t1ce.json').read() == open(tmp / f'{n}_dev' / 'conform_t1ce.json').read()
         assert line.endswith(' | conform=24x24x16@2mm:FLAIR,T2,T1 | antialias=on')
 
@@ -508,11 +443,11 @@ def test_nested_writers_and_evaluation_grid_through_both_entry_points(runs):
     tmp = runs['tmp']
     single, cohort = tmp / 'b_nested', tmp / 'cohort_nested' / 's_b'
     tail = lambda line: line.split(' | ', 1)[1]                       # noqa: E731  (what follows the path, which differs)
-    want = _done(runs, 'b_nested')[0]
+    want = VS.done_line(runs['log']['b_nested'])
     assert tail(want) == ('shape=(24, 24, 16) | slices=5..11 | regrid=gt_volume | reorient=FLAIR:RAS>LPS,T2:RAS>LPS,T1:RAS>LPS | '
                           'conform=24x24x16@2mm:FLAIR,T2,T1 | antialias=on')
-    for other, line in ((tmp / 'b_nested_dev', _done(runs, 'b_nested_dev')[0]), (cohort, _done(runs, 'cohort_nested')[0])):
-        assert _payload(str(other / 'predicted_t1ce.nii.gz')) == _payload(str(single / 'predicted_t1ce.nii.gz'))
+    for other, line in ((tmp / 'b_nested_dev', VS.done_line(runs['log']['b_nested_dev'])), (cohort, VS.done_line(runs['log']['cohort_nested']))):
+        assert VS.payload(str(other / 'predicted_t1ce.nii.gz')) == VS.payload(str(single / 'predicted_t1ce.nii.gz'))
         for report in ('metrics_t1ce.json', 'reorient_t1ce.json', 'conform_t1ce.json'):
             assert open(other / report).read() == open(single / report).read(), report
         assert tail(line) == tail(want)

@@ -10,6 +10,7 @@ import pytest
 import volume_conform_ref as CR
 import volume_intake_ref as I
 import volume_reorient_ref as R
+from volume_support import raw_volume
 
 BASE = ['--target_modality', 'T1CE', '--output_dir', 'o', '--exp', 'e']
 
@@ -188,10 +189,7 @@ def test_flags_and_options(capsys):
 # prepare_inputs with the device stages replaced
 # ---------------------------------------------------------------------------------------------------
 def _raw(vol, affine):
-    from mudiff_hip import NIFTI_I2
-    from mudiff_hip.volume_intake import RawVolume
-    vol = np.asarray(vol, np.int16)
-    return RawVolume(np.ascontiguousarray(vol.reshape(-1, order='F')), NIFTI_I2, '<', 1.0, 0.0, vol.shape, np.asarray(affine, np.float64), None)
+    return raw_volume(np.asarray(vol, np.int16), affine=np.asarray(affine, np.float64))
 
 
 GRID = dict(shape=(6, 5, 8), spacing=(2.0, 2.0, 2.0), target='LPS')

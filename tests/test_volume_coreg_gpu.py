@@ -4,33 +4,22 @@ on a bin edge for an oblique matrix; equality with a histogram of mud_volume_reg
 NaN voxels; an empty overlap; two runs; the C ABI's argument checks; then the recovery of a known rigid motion on the device against
 the same search on the host, and `predict_volume --coregister` end to end through the host path and --device_intake."""
 import ctypes as C
-import gzip
 import json
 import os
-import subprocess
-import sys
-import textwrap
 import warnings
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import PKG, REPO
 import volume_coreg_ref as K
 import volume_intake_ref as R
 import volume_regrid_ref as G
-from oracle import mudiff_oracle as O
+import volume_support as VS
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
 STRIDES, BINS = (1, 2, 3), (32, 64)
-
-
-def _raw(vol, affine=None, scale=(1.0, 0.0)):
-    from mudiff_hip import volume_intake as VI
-    return VI.RawVolume(np.ascontiguousarray(vol.reshape(-1, order='F')), R.CODES[vol.dtype.str[1:]], '<', float(np.float32(scale[0])),
-                        float(np.float32(scale[1])), vol.shape, np.eye(4) if affine is None else affine, None)
 
 
 def _device_hist(fix, mov, M, stride, ranges, bins, fix_scale=(1.0, 0.0), mov_scale=(1.0, 0.0)):
@@ -39,7 +28,7 @@ def _device_hist(fix, mov, M, stride, ranges, bins, fix_scale=(1.0, 0.0), mov_sc
     from mudiff_hip import volume_intake as VI
     sides = []
     for vol, scale in ((fix, fix_scale), (mov, mov_scale)):
-        raw = _raw(vol, scale=scale)
+        raw = VS.raw_volume(vol, scale)
         sides += [VI.upload(raw, DEV), (raw.code, vol.shape) + ((raw.slope, raw.inter) if raw.scaled else (1.0, 0.0))]
     out = VC.joint_hist(*sides, M, stride, ranges, bins)
     assert out.dtype == np.int64 and out.shape == (bins, bins)
@@ -81,7 +70,7 @@ def test_histogram_equals_the_histogram_of_the_regrid_kernel(source, name):
     from mudiff_hip import volume_regrid as VR
     _, sa, rs, ra = G.case(name)
     M, fix = G.matrix(sa, ra), _fixed(rs)
-    out = VR.regrid(VI.upload(_raw(source), DEV), 16, source.shape, 1.0, 0.0, M, rs).cpu().numpy().transpose(2, 1, 0)
+    out = VR.regrid(VI.upload(VS.raw_volume(source), DEV), 16, source.shape, 1.0, 0.0, M, rs).cpu().numpy().transpose(2, 1, 0)
     for stride in (1, 3):
         ranges = K.ranges_of(fix, source, 32)
         _, info = K.joint_hist(fix, source, M, stride, ranges, 32, details=True)
@@ -193,7 +182,7 @@ def test_device_recovery_meets_the_bar_and_agrees_with_the_host_search(subject):
     from mudiff_hip import volume_coreg as VC
     from mudiff_hip import volume_regrid as VR
     s = subject
-    fixed_raw, moving_raw = _raw(s['fix'], s['A']), _raw(s['mov'], s['A'])
+    fixed_raw, moving_raw = VS.raw_volume(s['fix'], affine=s['A']), VS.raw_volume(s['mov'], affine=s['A'])
     with warnings.catch_warnings():
         warnings.simplefilter('error')
         W, rep = VC.coregister(fixed_raw, moving_raw, DEV)
@@ -219,7 +208,7 @@ def test_device_recovery_meets_the_bar_and_agrees_with_the_host_search(subject):
     assert int(np.abs(got - want).sum()) <= 2 * ne and int(got.sum()) == info['counted']
     # regrid_to(world=W) against plain regrid of the same voxels whose header carries the true motion
     by_search = VR.regrid_to(moving_raw, K.HEAD_SHAPE, s['A'], DEV, world=W)
-    by_header = VR.regrid_to(_raw(s['mov'], np.linalg.inv(VC.rigid_world(K.TRUE_PARAMS, s['centre'])) @ s['A']), K.HEAD_SHAPE, s['A'], DEV)
+    by_header = VR.regrid_to(VS.raw_volume(s['mov'], affine=np.linalg.inv(VC.rigid_world(K.TRUE_PARAMS, s['centre'])) @ s['A']), K.HEAD_SHAPE, s['A'], DEV)
     assert isinstance(by_search, VR.RegriddedVolume) and isinstance(by_header, VR.RegriddedVolume)
     a, b = by_search.values_float32().astype(np.float64), by_header.values_float32().astype(np.float64)
     step = max(float(np.abs(np.diff(s['mov'].astype(np.float64), axis=ax)).max()) for ax in range(3))
@@ -234,7 +223,7 @@ def test_a_moving_volume_that_does_not_overlap_is_left_alone(subject):
     far = subject['A'].copy()
     far[0, 3] = 1000.0
     with pytest.warns(RuntimeWarning, match='did not improve'):
-        W, rep = VC.coregister(_raw(subject['fix'], subject['A']), _raw(subject['mov'], far), DEV, strides=(4,))
+        W, rep = VC.coregister(VS.raw_volume(subject['fix'], affine=subject['A']), VS.raw_volume(subject['mov'], affine=far), DEV, strides=(4,))
     assert np.array_equal(W, np.eye(4)) and not rep['accepted'] and rep['nmi_identity'] == 0.0 and rep['nmi_result'] == 0.0
 
 
@@ -244,59 +233,25 @@ def test_a_moving_volume_that_does_not_overlap_is_left_alone(subject):
 PARAMS_T1 = (-1.5, 2.0, 0.8, -2.5, 3.0, 1.5)
 
 
-def _payload(path):
-    with gzip.open(path, 'rb') as f:
-        return f.read()
-
-
 @pytest.fixture(scope='module')
 def runs(tmp_path_factory, subject):
     from mudiff_hip import volume as V
     from mudiff_hip import volume_coreg as VC
     s = subject
     tmp = tmp_path_factory.mktemp('coreg')
-    cfg = O.default_config(image_size=16, num_channels_dae=16, ch_mult=[1, 2], attn_resolutions=(4,), num_res_blocks=1)
-    exp = tmp / 'results' / 'exp0'
-    exp.mkdir(parents=True)
-    for which, name in (('g1', 'gen_diffusive_1'), ('g2', 'gen_diffusive_2')):
-        torch.save({'module.' + k: v for k, v in O.make_state_dict(cfg, which, 9).items()}, str(exp / f'{name}.pth'))
+    VS.write_tiny_model(tmp)
     M_t1 = VC.sampling_matrix(s['A'], VC.rigid_world(PARAMS_T1, s['centre']), s['A'])
     t1 = K.moved(np.asfortranarray(((500.0 + 300.0 * np.cos(5.0 * s['t'])) * s['mask']).astype(np.float32)), M_t1, seed=13, mask=s['mask'])
     p = {k: str(tmp / f'{k}.nii.gz') for k in ('flair', 't2', 't1')}
     V.write_nifti(p['flair'], s['fix'], s['A'])
     V.write_nifti(p['t2'], s['mov'], s['A'])
     V.write_nifti(p['t1'], t1, s['A'])
-    model = ['--target_modality', 'T1CE', '--exp', 'exp0', '--output_path', str(tmp / 'results'), '--image_size', '16', '--num_channels_dae',
-             '16', '--ch_mult', '1', '2', '--attn_resolutions', '4', '--num_res_blocks', '1', '--slice_half_range', '2', '--batch_size', '5',
-             '--seed', '31', '--resize_back', '--input_flair', p['flair'], '--input_t2', p['t2'], '--input_t1', p['t1']]
+    model = VS.model_argv(tmp, 2, 5, '--resize_back', '--input_flair', p['flair'], '--input_t2', p['t2'], '--input_t1', p['t1'])
     jobs = {'coreg_host': ['--coregister'], 'coreg_dev': ['--coregister', '--device_intake'], 'plain_host': [], 'plain_dev': ['--device_intake'],
             'regrid_host': ['--regrid']}
     jobs = {k: model + a + ['--output_dir', str(tmp / k)] for k, a in jobs.items()}
-    log = str(tmp / 'log.json')
-    code = f'''
-        import contextlib, io, json
-        from mudiff_hip import volume as V
-        log = {{}}
-        for name, argv in {jobs!r}.items():
-            out = io.StringIO()
-            with contextlib.redirect_stdout(out):
-                V.predict_volume(V.build_argparser(argv))
-            log[name] = out.getvalue()
-        json.dump(log, open({log!r}, 'w'))
-    '''
-    env = dict(os.environ, PYTHONPATH=os.pathsep.join([REPO, PKG, os.environ.get('PYTHONPATH', '')]), MUD_DETERMINISTIC='1')
-    for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE'):
-        env.pop(k, None)
-    c = subprocess.run([sys.executable, '-c', textwrap.dedent(code)], cwd=REPO, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                       timeout=900)
-    assert c.returncode == 0, c.stdout[-3000:] + c.stderr[-3000:]
-    return dict(tmp=tmp, log=json.load(open(log)), M_t1=M_t1, pred=lambda k: _payload(str(tmp / k / 'predicted_t1ce.nii.gz')))
-
-
-def _done(runs, name):
-    lines = [ln for ln in runs['log'][name].splitlines() if ln.startswith('[done]')]
-    assert len(lines) == 1
-    return lines[0]
+    log = VS.run_plan(tmp, [VS.volume_step(k, argv) for k, argv in jobs.items()], 900)
+    return dict(tmp=tmp, log=log, M_t1=M_t1, pred=lambda k: VS.payload(str(tmp / k / 'predicted_t1ce.nii.gz')))
 
 
 def test_predict_volume_coregister_end_to_end(runs, subject):
@@ -310,7 +265,7 @@ def test_predict_volume_coregister_end_to_end(runs, subject):
             mean, worst = K.displacement_error(M, truth, s['mask'])
             print(name, key, rep[key]['params'], (mean, worst), rep[key]['evaluations'])
             assert rep[key]['accepted'] and mean <= K.BAR_MEAN and worst <= K.BAR_MAX
-        assert ' | regrid=T2,T1 | coreg=T2:' in _done(runs, name) and 'mm/' in _done(runs, name) and _done(runs, name).count('deg') == 2
+        assert ' | regrid=T2,T1 | coreg=T2:' in VS.done_line(runs['log'][name]) and 'mm/' in VS.done_line(runs['log'][name]) and VS.done_line(runs['log'][name]).count('deg') == 2
     assert json.load(open(tmp / 'coreg_host' / 'coreg_t1ce.json')) == json.load(open(tmp / 'coreg_dev' / 'coreg_t1ce.json'))
     assert runs['pred']('coreg_host') == runs['pred']('coreg_dev')                 # host file == device file, byte for byte
     assert runs['pred']('coreg_host') != runs['pred']('plain_host')                # and the alignment reached the sampler
@@ -321,6 +276,6 @@ def test_without_the_flag_nothing_changes(runs):
     want = runs['pred']('plain_host')
     assert runs['pred']('plain_dev') == want and runs['pred']('regrid_host') == want       # (the inputs share a grid: --regrid is a no-op)
     for name in ('plain_host', 'plain_dev', 'regrid_host'):
-        assert ' | coreg=' not in _done(runs, name) and ' | regrid=' not in _done(runs, name)
+        assert ' | coreg=' not in VS.done_line(runs['log'][name]) and ' | regrid=' not in VS.done_line(runs['log'][name])
         assert not os.path.exists(tmp / name / 'coreg_t1ce.json')
-    assert _done(runs, 'plain_host').endswith('| slices=16..20')
+    assert VS.done_line(runs['log']['plain_host']).endswith('| slices=16..20')

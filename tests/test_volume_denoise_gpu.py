@@ -4,33 +4,22 @@ that cross the volume's faces) and a 5 x 4 x 3 one (smaller than the search wind
 and as fp32 with a NaN, an inf and a block of zeros: the keys of the pseudo-residuals, the four radix-select histograms and the
 estimated sigma equal to the restatement's; the estimate within the derived bound at every voxel in both modes; the recovery of a
 noisy slab; the C ABI's refusals; `predict_volume --denoise` end to end."""
-import gzip
 import json
 import os
-import subprocess
-import sys
-import textwrap
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import PKG, REPO
 import volume_denoise_ref as D
 import volume_intake_ref as R
-from oracle import mudiff_oracle as O
+import volume_support as VS
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
 SHAPES = ((37, 29, 23), (5, 4, 3))
 WINDOWS = ((2, 1), (1, 1), (3, 2))
 I2_SCALE = (0.25, -3.0)
-
-
-def _raw(vol, scale=(1.0, 0.0)):
-    from mudiff_hip import volume_intake as VI
-    return VI.RawVolume(np.ascontiguousarray(vol.reshape(-1, order='F')), R.CODES[vol.dtype.str[1:]], '<', float(np.float32(scale[0])),
-                        float(np.float32(scale[1])), vol.shape, np.eye(4), None)
 
 
 def _stored(shape, kind):
@@ -62,7 +51,7 @@ def volumes():
     for shape, kind in CASES:
         vol, scale = _stored(shape, kind)
         values = np.asfortranarray(R.values_float32(vol, *scale))
-        out[shape, kind] = (_raw(vol, scale), values) + D.sigma_by_sorting(values)
+        out[shape, kind] = (VS.raw_volume(vol, scale), values) + D.sigma_by_sorting(values)
     return out
 
 
@@ -77,17 +66,13 @@ def references(volumes):
     return ref
 
 
-def _host(t):
-    return t.cpu().numpy().transpose(2, 1, 0)
-
-
 @pytest.mark.parametrize('shape,kind', CASES)
 def test_keys_histograms_and_sigma_are_the_restatement(volumes, shape, kind):
     from mudiff_hip import ops, volume_denoise as VD, volume_intake as VI
     raw, values, want_sigma, want_n = volumes[shape, kind]
     assert (values == 0).any()
     keys = ops.volume_denoise_residual(VI.upload(raw, DEV), raw.code, raw.shape, *raw.scaling)
-    got = _host(keys).view(np.uint32)
+    got = VS.to_host_xyz(keys).view(np.uint32)
     want = D.residual_keys(values)
     assert got.shape == want.shape and np.array_equal(got, want)
     assert int((want != D.SKIP).sum()) == want_n and want_n >= 2
@@ -157,15 +142,15 @@ def test_estimated_sigma_flat_input_and_geometry(volumes):
     assert out.affine is raw.affine and out.header == 'the header' and out.code == 16 and not out.scaled and out.dev.shape == (23, 29, 37)
     # nothing to estimate from (no voxel with six positive neighbours) and a noise-free volume: returned untouched
     for vol in (np.zeros((9, 8, 7), np.int16, order='F'), np.full((9, 8, 7), 5, np.int16, order='F')):
-        flat = _raw(vol)
+        flat = VS.raw_volume(vol)
         same, rep = VD.denoise(flat, DEV)
         assert same is flat and rep['sigma'] == 0.0 and rep['estimated'] is True and rep['samples'] == (0 if not vol.any() else 7 * 6 * 5)
     # a constant volume and a single valid voxel come back unchanged for a given sigma
-    const = VD.denoise(_raw(np.full((9, 8, 7), 5, np.int16, order='F')), DEV, sigma=3.0)[0].values_float32()
+    const = VD.denoise(VS.raw_volume(np.full((9, 8, 7), 5, np.int16, order='F')), DEV, sigma=3.0)[0].values_float32()
     assert np.array_equal(const, np.full((9, 8, 7), 5, np.float32))
     lone = np.full((9, 8, 7), np.nan, '<f4', order='F')
     lone[4, 4, 3] = 123.5
-    got = VD.denoise(_raw(lone), DEV, sigma=3.0)[0].values_float32()
+    got = VD.denoise(VS.raw_volume(lone), DEV, sigma=3.0)[0].values_float32()
     assert np.array_equal(got.view(np.uint32), lone.view(np.uint32))
 
 
@@ -174,9 +159,9 @@ def test_device_recovery_meets_the_bar():
     section 5.15) and below the host test's bar of 1.5 x it."""
     from mudiff_hip import volume_denoise as VD
     noisy, clean = D.slab()
-    out, rep = VD.denoise(_raw(noisy), DEV, sigma=D.SLAB_SIGMA)
+    out, rep = VD.denoise(VS.raw_volume(noisy), DEV, sigma=D.SLAB_SIGMA)
     ratio = D.recovery_ratio(out.values_float32(), noisy, clean)
-    sigma = VD.estimate_sigma(_raw(noisy), DEV)[0]
+    sigma = VD.estimate_sigma(VS.raw_volume(noisy), DEV)[0]
     print('device recovery', ratio, 'recorded', D.RECORDED_RATIO, 'bar', D.BAR, 'estimated sigma', sigma)
     assert abs(ratio - D.RECORDED_RATIO) <= 1e-3 * D.RECORDED_RATIO and ratio <= D.BAR
     assert abs(sigma - D.RECORDED_SIGMA) <= 1e-3 * D.RECORDED_SIGMA and abs(sigma - D.SLAB_SIGMA) <= 0.2 * D.SLAB_SIGMA
@@ -221,26 +206,15 @@ def test_c_abi_rejects_bad_arguments_without_launching():
 # ---------------------------------------------------------------------------------------------------
 # end to end: the tiny model of the other volume tests, three noisy inputs on one grid
 # ---------------------------------------------------------------------------------------------------
-def _payload(path):
-    with gzip.open(path, 'rb') as f:
-        return f.read()
-
-
 @pytest.fixture(scope='module')
 def runs(tmp_path_factory):
     from mudiff_hip import volume as V
     tmp = tmp_path_factory.mktemp('noisy')
-    cfg = O.default_config(image_size=16, num_channels_dae=16, ch_mult=[1, 2], attn_resolutions=(4,), num_res_blocks=1)
-    exp = tmp / 'results' / 'exp0'
-    exp.mkdir(parents=True)
-    for which, name in (('g1', 'gen_diffusive_1'), ('g2', 'gen_diffusive_2')):
-        torch.save({'module.' + k: v for k, v in O.make_state_dict(cfg, which, 9).items()}, str(exp / f'{name}.pth'))
+    VS.write_tiny_model(tmp)
     p = {k: str(tmp / f'{k}.nii.gz') for k in ('flair', 't2', 't1')}
     for seed, k in enumerate(p):
         V.write_nifti(p[k], np.asfortranarray(D.phantom(SHAPES[0], 91 + seed).astype(np.float32)), np.eye(4))
-    model = ['--target_modality', 'T1CE', '--exp', 'exp0', '--output_path', str(tmp / 'results'), '--image_size', '16', '--num_channels_dae',
-             '16', '--ch_mult', '1', '2', '--attn_resolutions', '4', '--num_res_blocks', '1', '--slice_half_range', '2', '--batch_size', '5',
-             '--seed', '31', '--resize_back']
+    model = VS.model_argv(tmp, 2, 5, '--resize_back')
     inputs = ['--input_flair', p['flair'], '--input_t2', p['t2'], '--input_t1', p['t1']]
     jobs = {'den_host': ['--denoise'], 'den_dev': ['--denoise', '--device_intake'], 'den_host_z': ['--denoise', '--norm', 'zscore'],
             'den_dev_z': ['--denoise', '--norm', 'zscore', '--device_intake'], 'plain_host': [], 'plain_dev': ['--device_intake']}
@@ -248,39 +222,9 @@ def runs(tmp_path_factory):
     manifest = tmp / 'cohort.tsv'
     manifest.write_text('id\tt1\tt1ce\tt2\tflair\ns0\t' + '\t'.join([p['t1'], '', p['t2'], p['flair']]) + '\n')
     cohort = model + ['--denoise', '--manifest', str(manifest), '--output_dir', str(tmp / 'den_cohort')]
-    log = str(tmp / 'log.json')
-    code = f'''
-        import contextlib, io, json, warnings
-        from mudiff_hip import cohort as Co, volume as V
-        log = {{}}
-        out = io.StringIO()
-        with contextlib.redirect_stdout(out), warnings.catch_warnings():
-            warnings.simplefilter('ignore', RuntimeWarning)
-            args = Co.build_argparser({cohort!r})
-            failures = Co.run(args, Co.read_manifest(args.manifest))[1]
-        assert not failures, failures
-        log['den_cohort'] = out.getvalue()
-        for name, argv in {jobs!r}.items():
-            out = io.StringIO()
-            with contextlib.redirect_stdout(out), warnings.catch_warnings():
-                warnings.simplefilter('ignore', RuntimeWarning)
-                V.predict_volume(V.build_argparser(argv))
-            log[name] = out.getvalue()
-        json.dump(log, open({log!r}, 'w'))
-    '''
-    env = dict(os.environ, PYTHONPATH=os.pathsep.join([REPO, PKG, os.environ.get('PYTHONPATH', '')]), MUD_DETERMINISTIC='1')
-    for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE'):
-        env.pop(k, None)
-    c = subprocess.run([sys.executable, '-c', textwrap.dedent(code)], cwd=REPO, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                       timeout=900)
-    assert c.returncode == 0, c.stdout[-3000:] + c.stderr[-3000:]
-    return dict(tmp=tmp, log=json.load(open(log)), pred=lambda k: _payload(str(tmp / k / 'predicted_t1ce.nii.gz')))
-
-
-def _done(runs, name):
-    lines = [ln for ln in runs['log'][name].splitlines() if ln.startswith('[done]')]
-    assert len(lines) == 1
-    return lines[0]
+    steps = [VS.cohort_step('den_cohort', cohort)] + [VS.volume_step(k, argv) for k, argv in jobs.items()]
+    log = VS.run_plan(tmp, steps, 900, ignore='RuntimeWarning')
+    return dict(tmp=tmp, log=log, pred=lambda k: VS.payload(str(tmp / k / 'predicted_t1ce.nii.gz')))
 
 
 def test_predict_volume_denoise_end_to_end(runs):
@@ -294,17 +238,17 @@ def test_predict_volume_denoise_end_to_end(runs):
         for r in rep.values():
             assert r['estimated'] is True and 15.0 < r['sigma'] < 60.0 and r['samples'] > 1000 and r['zeroed'] == 0      # (noise of sigma 30)
             assert (r['search'], r['patch'], r['beta'], r['rician']) == (2, 1, 1.0, False)
-        assert _done(runs, name).endswith(' | denoise=FLAIR,T2,T1')
+        assert VS.done_line(runs['log'][name]).endswith(' | denoise=FLAIR,T2,T1')
     assert all(r == reports['den_host'] for r in reports.values())
-    assert runs['pred']('den_host') == runs['pred']('den_dev') == _payload(str(where['den_cohort'] / 'predicted_t1ce.nii.gz'))
+    assert runs['pred']('den_host') == runs['pred']('den_dev') == VS.payload(str(where['den_cohort'] / 'predicted_t1ce.nii.gz'))
     assert runs['pred']('den_host_z') == runs['pred']('den_dev_z')                 # host file == device file in both --norm modes
     assert runs['pred']('den_host') != runs['pred']('plain_host')                  # and the denoised inputs reached the sampler
-    assert _done(runs, 'den_host').replace(str(where['den_host']), 'OUT') == _done(runs, 'den_dev').replace(str(where['den_dev']), 'OUT')
+    assert VS.done_line(runs['log']['den_host']).replace(str(where['den_host']), 'OUT') == VS.done_line(runs['log']['den_dev']).replace(str(where['den_dev']), 'OUT')
 
 
 def test_without_the_flag_nothing_changes(runs):
     tmp = runs['tmp']
     assert runs['pred']('plain_dev') == runs['pred']('plain_host')
     for name in ('plain_host', 'plain_dev'):
-        assert 'denoise' not in runs['log'][name] and _done(runs, name).endswith('| slices=9..13')
+        assert 'denoise' not in runs['log'][name] and VS.done_line(runs['log'][name]).endswith('| slices=9..13')
         assert sorted(os.listdir(tmp / name)) == ['predicted_t1ce.nii.gz']

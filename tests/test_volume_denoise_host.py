@@ -9,6 +9,7 @@ import pytest
 
 import volume_denoise_ref as D
 import volume_intake_ref as R
+from volume_support import cli_argv
 
 SHAPE = (13, 11, 9)
 
@@ -83,33 +84,29 @@ def test_residual_keys_cover_the_interior_positive_voxels_only():
     assert D.sigma_by_sorting(np.zeros(SHAPE, np.float32)) == (0.0, 0) and D.sigma_by_sorting(np.ones((5, 2, 5), np.float32)) == (0.0, 0)
 
 
-def _argv(*extra):
-    return ['--target_modality', 'T1CE', '--output_dir', 'out', '--exp', 'e'] + list(extra)
-
-
 def test_flags_defaults_and_refusals(capsys):
     from mudiff_hip import volume as V
     from mudiff_hip import volume_denoise as VD
     from mudiff_hip.volume_prepare import IntakeOptions
-    args = V.build_argparser(_argv())
+    args = V.build_argparser(cli_argv())
     assert args.denoise is False and args.denoise_sigma is None and args.denoise_rician is False
     assert IntakeOptions.from_args(args).denoise is None and IntakeOptions.from_args(args) == IntakeOptions('percentile', False, None, None, 80)
     assert IntakeOptions._fields[-1] == 'denoise' and IntakeOptions().denoise is None
-    assert IntakeOptions.from_args(V.build_argparser(_argv('--denoise'))).denoise == VD.DEFAULTS == dict(sigma=None, search=2, patch=1, beta=1.0,
+    assert IntakeOptions.from_args(V.build_argparser(cli_argv('--denoise'))).denoise == VD.DEFAULTS == dict(sigma=None, search=2, patch=1, beta=1.0,
                                                                                                          rician=False)
-    args = V.build_argparser(_argv('--denoise', '--denoise_sigma', '12.5', '--denoise_search', '3', '--denoise_patch', '2', '--denoise_beta', '0.5',
+    args = V.build_argparser(cli_argv('--denoise', '--denoise_sigma', '12.5', '--denoise_search', '3', '--denoise_patch', '2', '--denoise_beta', '0.5',
                                    '--denoise_rician'))
     assert IntakeOptions.from_args(args).denoise == dict(sigma=12.5, search=3, patch=2, beta=0.5, rician=True)
     for bad, word in ((['--denoise_sigma', '0'], 'denoise_sigma'), (['--denoise_sigma', 'nan'], 'denoise_sigma'), (['--denoise_sigma', '-1'], 'denoise_sigma'),
                       (['--denoise_search', '0'], 'denoise_search'), (['--denoise_search', '6'], 'denoise_search'), (['--denoise_patch', '0'], 'denoise_patch'),
                       (['--denoise_patch', '3'], 'denoise_patch'), (['--denoise_beta', '0'], 'denoise_beta'), (['--denoise_beta', 'inf'], 'denoise_beta')):
         with pytest.raises(SystemExit):
-            V.build_argparser(_argv('--denoise', *bad))
+            V.build_argparser(cli_argv('--denoise', *bad))
         assert word in capsys.readouterr().err
     with pytest.raises(ValueError, match='--denoise_search'):
         VD.check_options(search=9)
     from mudiff_hip import cohort
-    assert cohort.build_argparser(_argv('--manifest', 'm.tsv', '--denoise', '--denoise_search', '3')).denoise_search == 3
+    assert cohort.build_argparser(cli_argv('--manifest', 'm.tsv', '--denoise', '--denoise_search', '3')).denoise_search == 3
 
 
 def test_denoise_suffix_and_reports(tmp_path):

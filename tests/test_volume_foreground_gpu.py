@@ -3,41 +3,21 @@
 23, 5 x 4 x 3 and 70 x 19 x 11 (three 32 x 8 x 4 tiles along every axis and a multiple of none), with the census and the winner; the
 morphology against scipy; the whole foreground() on the phantom stored as int16 with slope / inter and as fp32 with a NaN, an inf and a
 block of zeros; degenerate inputs; the C ABI's refusals; `predict_volume --foreground` end to end."""
-import gzip
 import json
 import os
-import subprocess
-import sys
-import textwrap
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import PKG, REPO
 import volume_foreground_ref as F
 import volume_intake_ref as R
-from oracle import mudiff_oracle as O
+import volume_support as VS
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
 LABEL_SHAPES = ((37, 29, 23), (5, 4, 3), (70, 19, 11))
 I2_SCALE = (0.25, -3.0)
-
-
-def _raw(vol, scale=(1.0, 0.0)):
-    from mudiff_hip import volume_intake as VI
-    return VI.RawVolume(np.ascontiguousarray(vol.reshape(-1, order='F')), R.CODES[vol.dtype.str[1:]], '<', float(np.float32(scale[0])),
-                        float(np.float32(scale[1])), vol.shape, np.eye(4), None)
-
-
-def _device(a, dtype=None):
-    """[X,Y,Z] host array -> [Z,Y,X] device tensor."""
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype).transpose(2, 1, 0))).to(DEV)
-
-
-def _host(t):
-    return t.cpu().numpy().transpose(2, 1, 0)
 
 
 @pytest.fixture(scope='module')
@@ -59,8 +39,8 @@ def test_labels_census_and_winner_are_the_restatement(label_references, shape, v
     n = int(np.prod(shape))
     for name in F.label_masks(shape):
         mask, want, counts, face, winner, components = label_references[shape, name, value]
-        labels = ops.volume_fg_label(_device(mask), shape, value)
-        got = _host(labels)
+        labels = ops.volume_fg_label(VS.to_device_zyx(mask), shape, value)
+        got = VS.to_host_xyz(labels)
         assert got.dtype == np.int32 and np.array_equal(got, want), (name, int((got != want).sum()))
         census, summary = ops.volume_fg_census(labels, shape)
         census = census.cpu().numpy().view(np.uint32)
@@ -71,11 +51,11 @@ def test_labels_census_and_winner_are_the_restatement(label_references, shape, v
             assert (best >> 32, 0xFFFFFFFF - (best & 0xFFFFFFFF)) == (int(counts[winner]), winner), name
         else:
             assert best == 0
-        again = ops.volume_fg_label(_device(mask), shape, value)
+        again = ops.volume_fg_label(VS.to_device_zyx(mask), shape, value)
         assert torch.equal(again, labels)                                              # two runs: identical bits
         if components:                                                                 # keeping the winner
             kept, count = ops.volume_fg_select(labels, None, winner, False)
-            assert np.array_equal(_host(kept), (want == winner).astype(np.uint8)) and int(count[0]) == int(counts[winner])
+            assert np.array_equal(VS.to_host_xyz(kept), (want == winner).astype(np.uint8)) and int(count[0]) == int(counts[winner])
     if value == 1:
         checker = label_references[shape, 'checker', 1]
         assert checker[4] == 0 and checker[5] == (n + 1) // 2                          # the tie goes to index 0
@@ -87,11 +67,11 @@ def test_filling_the_holes_is_the_restatement(label_references, shape):
     from mudiff_hip import ops
     for name in ('random0.7', 'random0.5', 'comb', 'on', 'off'):
         mask = label_references[shape, name, 1][0]
-        dev = _device(mask)
+        dev = VS.to_device_zyx(mask)
         labels = ops.volume_fg_label(dev, shape, 0)
         filled, count = ops.volume_fg_select(labels, ops.volume_fg_census(labels, shape)[0], 0, True, dev)
         want = F.fill_holes(mask)
-        assert filled is dev and np.array_equal(_host(filled), want.astype(np.uint8)), name
+        assert filled is dev and np.array_equal(VS.to_host_xyz(filled), want.astype(np.uint8)), name
         assert int(count[0]) == int(want.sum()) - int((mask != 0).sum())
 
 
@@ -104,12 +84,12 @@ def test_morphology_is_scipys(steps):
         for name, mask in F.label_masks(shape).items():
             if name not in ('on', 'single', 'random0.7', 'random0.5', 'comb'):
                 continue
-            eroded = dilated = _device(mask)
+            eroded = dilated = VS.to_device_zyx(mask)
             for _ in range(steps):
                 eroded, dilated = ops.volume_fg_morph(eroded, shape, False), ops.volume_fg_morph(dilated, shape, True)
-            assert np.array_equal(_host(eroded) != 0, ndimage.binary_erosion(mask != 0, six, iterations=steps, border_value=1)), (shape, name)
-            assert np.array_equal(_host(dilated) != 0, ndimage.binary_dilation(mask != 0, six, iterations=steps, border_value=0)), (shape, name)
-            assert set(np.unique(_host(eroded))) <= {0, 1} and set(np.unique(_host(dilated))) <= {0, 1}
+            assert np.array_equal(VS.to_host_xyz(eroded) != 0, ndimage.binary_erosion(mask != 0, six, iterations=steps, border_value=1)), (shape, name)
+            assert np.array_equal(VS.to_host_xyz(dilated) != 0, ndimage.binary_dilation(mask != 0, six, iterations=steps, border_value=0)), (shape, name)
+            assert set(np.unique(VS.to_host_xyz(eroded))) <= {0, 1} and set(np.unique(VS.to_host_xyz(dilated))) <= {0, 1}
 
 
 def _stored(kind):
@@ -130,7 +110,7 @@ def phantoms():
     out = {}
     for kind in ('i2', 'f4'):
         vol, scale = _stored(kind)
-        out[kind] = (_raw(vol, scale), np.asfortranarray(R.values_float32(vol, *scale)))
+        out[kind] = (VS.raw_volume(vol, scale), np.asfortranarray(R.values_float32(vol, *scale)))
     return out
 
 
@@ -170,7 +150,7 @@ def test_degenerate_inputs_come_back_untouched():
     two[1:3, 1:3, 1:3], two[4:, 4:, 4:], two[0, 0, 0] = np.inf, 0.0, np.nan
     for vol, candidates in ((np.zeros((9, 8, 7), np.int16, order='F'), 0), (np.full((9, 8, 7), 5, np.int16, order='F'), 9 * 8 * 7),
                             (two, 9 * 8 * 7 - 8 - 5 * 4 * 3 - 1)):
-        flat = _raw(vol)
+        flat = VS.raw_volume(vol)
         same, report = VF.foreground(flat, DEV)
         assert same is flat and report['threshold'] is None and report['bin'] is None and report['candidates'] == candidates
         assert report == F.foreground(R.values_float32(vol))[2]
@@ -255,26 +235,15 @@ def test_c_abi_rejects_bad_arguments_without_launching():
 # ---------------------------------------------------------------------------------------------------
 # end to end: the tiny model of the other volume tests, three phantom inputs with Rician air
 # ---------------------------------------------------------------------------------------------------
-def _payload(path):
-    with gzip.open(path, 'rb') as f:
-        return f.read()
-
-
 @pytest.fixture(scope='module')
 def runs(tmp_path_factory):
     from mudiff_hip import volume as V
     tmp = tmp_path_factory.mktemp('heads')
-    cfg = O.default_config(image_size=16, num_channels_dae=16, ch_mult=[1, 2], attn_resolutions=(4,), num_res_blocks=1)
-    exp = tmp / 'results' / 'exp0'
-    exp.mkdir(parents=True)
-    for which, name in (('g1', 'gen_diffusive_1'), ('g2', 'gen_diffusive_2')):
-        torch.save({'module.' + k: v for k, v in O.make_state_dict(cfg, which, 9).items()}, str(exp / f'{name}.pth'))
+    VS.write_tiny_model(tmp)
     p = {k: str(tmp / f'{k}.nii.gz') for k in ('flair', 't2', 't1')}
     for seed, k in enumerate(p):
         V.write_nifti(p[k], np.asfortranarray(F.phantom(seed=5 + seed)[0]), np.eye(4))
-    model = ['--target_modality', 'T1CE', '--exp', 'exp0', '--output_path', str(tmp / 'results'), '--image_size', '16', '--num_channels_dae',
-             '16', '--ch_mult', '1', '2', '--attn_resolutions', '4', '--num_res_blocks', '1', '--slice_half_range', '2', '--batch_size', '5',
-             '--seed', '31', '--resize_back']
+    model = VS.model_argv(tmp, 2, 5, '--resize_back')
     inputs = ['--input_flair', p['flair'], '--input_t2', p['t2'], '--input_t1', p['t1']]
     jobs = {'fg_host': ['--foreground'], 'fg_dev': ['--foreground', '--device_intake'], 'fg_host_z': ['--foreground', '--norm', 'zscore'],
             'fg_dev_z': ['--foreground', '--norm', 'zscore', '--device_intake'],
@@ -284,39 +253,9 @@ def runs(tmp_path_factory):
     manifest = tmp / 'cohort.tsv'
     manifest.write_text('id\tt1\tt1ce\tt2\tflair\ns0\t' + '\t'.join([p['t1'], '', p['t2'], p['flair']]) + '\n')
     cohort = model + ['--foreground', '--manifest', str(manifest), '--output_dir', str(tmp / 'fg_cohort')]
-    log = str(tmp / 'log.json')
-    code = f'''
-        import contextlib, io, json, warnings
-        from mudiff_hip import cohort as Co, volume as V
-        log = {{}}
-        out = io.StringIO()
-        with contextlib.redirect_stdout(out), warnings.catch_warnings():
-            warnings.simplefilter('ignore', RuntimeWarning)
-            args = Co.build_argparser({cohort!r})
-            failures = Co.run(args, Co.read_manifest(args.manifest))[1]
-        assert not failures, failures
-        log['fg_cohort'] = out.getvalue()
-        for name, argv in {jobs!r}.items():
-            out = io.StringIO()
-            with contextlib.redirect_stdout(out), warnings.catch_warnings():
-                warnings.simplefilter('ignore', RuntimeWarning)
-                V.predict_volume(V.build_argparser(argv))
-            log[name] = out.getvalue()
-        json.dump(log, open({log!r}, 'w'))
-    '''
-    env = dict(os.environ, PYTHONPATH=os.pathsep.join([REPO, PKG, os.environ.get('PYTHONPATH', '')]), MUD_DETERMINISTIC='1')
-    for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE'):
-        env.pop(k, None)
-    c = subprocess.run([sys.executable, '-c', textwrap.dedent(code)], cwd=REPO, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                       timeout=900)
-    assert c.returncode == 0, c.stdout[-3000:] + c.stderr[-3000:]
-    return dict(tmp=tmp, log=json.load(open(log)), pred=lambda k: _payload(str(tmp / k / 'predicted_t1ce.nii.gz')))
-
-
-def _done(runs, name):
-    lines = [ln for ln in runs['log'][name].splitlines() if ln.startswith('[done]')]
-    assert len(lines) == 1
-    return lines[0]
+    steps = [VS.cohort_step('fg_cohort', cohort)] + [VS.volume_step(k, argv) for k, argv in jobs.items()]
+    log = VS.run_plan(tmp, steps, 900, ignore='RuntimeWarning')
+    return dict(tmp=tmp, log=log, pred=lambda k: VS.payload(str(tmp / k / 'predicted_t1ce.nii.gz')))
 
 
 def test_predict_volume_foreground_end_to_end(runs):
@@ -330,19 +269,19 @@ def test_predict_volume_foreground_end_to_end(runs):
         for seed, r in enumerate(rep.values()):
             assert r == F.foreground(F.phantom(seed=5 + seed)[0])[2]                   # the report is the restatement's
             assert r['components'] >= 2 and r['filled'] >= 81 and r['removed'] > 15000 and (r['bins'], r['open'], r['keep_holes']) == (256, 0, False)
-        assert _done(runs, name).endswith(' | foreground=FLAIR,T2,T1')
+        assert VS.done_line(runs['log'][name]).endswith(' | foreground=FLAIR,T2,T1')
         assert sorted(os.listdir(d)) == ['foreground_t1ce.json', 'predicted_t1ce.nii.gz']
     assert all(r == reports['fg_host'] for r in reports.values())
-    assert runs['pred']('fg_host') == runs['pred']('fg_dev') == _payload(str(where['fg_cohort'] / 'predicted_t1ce.nii.gz'))
+    assert runs['pred']('fg_host') == runs['pred']('fg_dev') == VS.payload(str(where['fg_cohort'] / 'predicted_t1ce.nii.gz'))
     assert runs['pred']('fg_host_z') == runs['pred']('fg_dev_z')                       # host file == device file in both --norm modes
     assert runs['pred']('fg_host') != runs['pred']('plain_host') and runs['pred']('fg_host_z') != runs['pred']('plain_host_z')
-    assert _done(runs, 'fg_host').replace(str(where['fg_host']), 'OUT') == _done(runs, 'fg_dev').replace(str(where['fg_dev']), 'OUT')
+    assert VS.done_line(runs['log']['fg_host']).replace(str(where['fg_host']), 'OUT') == VS.done_line(runs['log']['fg_dev']).replace(str(where['fg_dev']), 'OUT')
 
 
 def test_all_three_stages_together_and_the_masks(runs):
     from mudiff_hip import volume as V
     tmp = runs['tmp']
-    assert _done(runs, 'fg_all').endswith(' | bias=FLAIR,T2,T1 | denoise=FLAIR,T2,T1 | foreground=FLAIR,T2,T1')
+    assert VS.done_line(runs['log']['fg_all']).endswith(' | bias=FLAIR,T2,T1 | denoise=FLAIR,T2,T1 | foreground=FLAIR,T2,T1')
     assert sorted(os.listdir(tmp / 'fg_all')) == ['bias_t1ce.json', 'denoise_t1ce.json', 'foreground_t1ce.json', 'foreground_t1ce_flair.nii.gz',
                                                   'foreground_t1ce_t1.nii.gz', 'foreground_t1ce_t2.nii.gz', 'predicted_t1ce.nii.gz']
     head = F.phantom()[1]
@@ -356,5 +295,5 @@ def test_without_the_flag_nothing_changes(runs):
     tmp = runs['tmp']
     assert runs['pred']('plain_dev') == runs['pred']('plain_host')
     for name in ('plain_host', 'plain_dev', 'plain_host_z'):
-        assert 'foreground' not in runs['log'][name] and _done(runs, name).endswith('| slices=9..13' + (' | norm=zscore' if name.endswith('_z') else ''))
+        assert 'foreground' not in runs['log'][name] and VS.done_line(runs['log'][name]).endswith('| slices=9..13' + (' | norm=zscore' if name.endswith('_z') else ''))
         assert sorted(os.listdir(tmp / name)) == ['predicted_t1ce.nii.gz']

@@ -10,6 +10,7 @@ import pytest
 
 import volume_foreground_ref as F
 import volume_intake_ref as R
+from volume_support import cli_argv
 
 LABEL_SHAPES = ((37, 29, 23), (5, 4, 3), (70, 19, 11))
 
@@ -45,31 +46,27 @@ def test_otsu_bin_is_the_brute_force_scan():
         assert VF.unkey(key) == float(np.float32(v)) and VF.unkey(~(~key & 0xFFFFFFFF)) == float(np.float32(v))
 
 
-def _argv(*extra):
-    return ['--target_modality', 'T1CE', '--output_dir', 'out', '--exp', 'e'] + list(extra)
-
-
 def test_flags_defaults_and_refusals(capsys):
     from mudiff_hip import volume as V
     from mudiff_hip import volume_foreground as VF
     from mudiff_hip.volume_prepare import IntakeOptions
-    args = V.build_argparser(_argv())
+    args = V.build_argparser(cli_argv())
     assert args.foreground is False and args.foreground_bins == 256 and args.foreground_open == 0
     assert args.foreground_keep_holes is False and args.foreground_mask_out is False
     assert VF.DEFAULTS == dict(bins=256, open=0, keep_holes=False, mask_out=False)
     # without the flag: the tuple it is today
     assert IntakeOptions.from_args(args).foreground is None and IntakeOptions.from_args(args) == IntakeOptions('percentile', False, None, None, 80)
     assert 'foreground' in IntakeOptions._fields and IntakeOptions().foreground is None and IntakeOptions().denoise is None
-    assert IntakeOptions.from_args(V.build_argparser(_argv('--foreground'))).foreground == VF.DEFAULTS
-    args = V.build_argparser(_argv('--foreground', '--foreground_bins', '64', '--foreground_open', '2', '--foreground_keep_holes',
+    assert IntakeOptions.from_args(V.build_argparser(cli_argv('--foreground'))).foreground == VF.DEFAULTS
+    args = V.build_argparser(cli_argv('--foreground', '--foreground_bins', '64', '--foreground_open', '2', '--foreground_keep_holes',
                                    '--foreground_mask_out', '--denoise'))
     options = IntakeOptions.from_args(args)
     assert options.foreground == dict(bins=64, open=2, keep_holes=True, mask_out=True) and options.denoise is not None
-    assert IntakeOptions.from_args(V.build_argparser(_argv('--foreground_bins', '64'))).foreground is None      # (the flag itself is missing)
+    assert IntakeOptions.from_args(V.build_argparser(cli_argv('--foreground_bins', '64'))).foreground is None      # (the flag itself is missing)
     for bad, word in ((['--foreground_bins', '15'], 'foreground_bins'), (['--foreground_bins', '1025'], 'foreground_bins'),
                       (['--foreground_open', '-1'], 'foreground_open'), (['--foreground_open', '4'], 'foreground_open')):
         with pytest.raises(SystemExit):
-            V.build_argparser(_argv('--foreground', *bad))
+            V.build_argparser(cli_argv('--foreground', *bad))
         assert word in capsys.readouterr().err
     for kw, word in ((dict(bins=8), '--foreground_bins'), (dict(bins=2048), '--foreground_bins'), (dict(bins=64.5), '--foreground_bins'),
                      (dict(open=4), '--foreground_open'), (dict(open=-1), '--foreground_open')):
@@ -80,7 +77,7 @@ def test_flags_defaults_and_refusals(capsys):
     help_text = ' '.join(V.make_parser().format_help().split())
     assert 'NOT a brain extraction' in help_text
     from mudiff_hip import cohort
-    assert cohort.build_argparser(_argv('--manifest', 'm.tsv', '--foreground', '--foreground_open', '1')).foreground_open == 1
+    assert cohort.build_argparser(cli_argv('--manifest', 'm.tsv', '--foreground', '--foreground_open', '1')).foreground_open == 1
 
 
 def test_foreground_suffix_and_reports(tmp_path):

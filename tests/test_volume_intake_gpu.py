@@ -5,16 +5,13 @@ import ctypes
 import gzip
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import PKG, REPO
 import volume_intake_ref as R
-from oracle import mudiff_oracle as O
+import volume_support as VS
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -23,8 +20,7 @@ FRACTIONS = (0.01, 0.99, 0.5, 0.999)
 
 def _dev_raw(vol):
     from mudiff_hip import volume_intake as VI
-    return VI.upload(VI.RawVolume(np.ascontiguousarray(vol.reshape(-1, order='F')), R.CODES[vol.dtype.str[1:]], '<', 1.0, 0.0, vol.shape,
-                                  np.eye(4), None), DEV)
+    return VI.upload(VS.raw_volume(vol), DEV)
 
 
 def _census(vol, slope, inter, fractions=FRACTIONS):
@@ -170,21 +166,6 @@ def test_c_abi_rejects_bad_arguments_without_launching():
 # ---------------------------------------------------------------------------------------------------
 # end to end: the volume CLI with and without --device_intake, then the cohort
 # ---------------------------------------------------------------------------------------------------
-def _run(module, argv, expect=0, timeout=900):
-    env = dict(os.environ, PYTHONPATH=os.pathsep.join([REPO, PKG, os.environ.get('PYTHONPATH', '')]), MUD_DETERMINISTIC='1')
-    for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE'):
-        env.pop(k, None)
-    p = subprocess.run([sys.executable, '-m', module] + argv, cwd=REPO, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                       timeout=timeout)
-    assert p.returncode == expect, (p.returncode, p.stdout[-3000:], p.stderr[-3000:])
-    return p
-
-
-def _payload(path):
-    with gzip.open(path, 'rb') as f:
-        return f.read()
-
-
 def _subject(root, sid, shape, seed, dtype='i2', scale=(0.0, 0.0)):
     rng = np.random.default_rng(seed)
     os.makedirs(root / sid)
@@ -199,14 +180,8 @@ def _subject(root, sid, shape, seed, dtype='i2', scale=(0.0, 0.0)):
 
 
 def test_device_intake_and_cohort_write_the_host_path_files(tmp_path):
-    cfg = O.default_config(image_size=16, num_channels_dae=16, ch_mult=[1, 2], attn_resolutions=(4,), num_res_blocks=1)
-    exp = tmp_path / 'results' / 'exp0'
-    exp.mkdir(parents=True)
-    for which, name in (('g1', 'gen_diffusive_1'), ('g2', 'gen_diffusive_2')):
-        torch.save({'module.' + k: v for k, v in O.make_state_dict(cfg, which, 9).items()}, str(exp / f'{name}.pth'))
-    model = ['--target_modality', 'T1CE', '--exp', 'exp0', '--output_path', str(tmp_path / 'results'), '--image_size', '16',
-             '--num_channels_dae', '16', '--ch_mult', '1', '2', '--attn_resolutions', '4', '--num_res_blocks', '1', '--slice_half_range', '3',
-             '--batch_size', '4', '--seed', '31', '--resize_back']
+    VS.write_tiny_model(tmp_path)
+    model = VS.model_argv(tmp_path, 3, 4, '--resize_back')
     data = tmp_path / 'brats'
     subjects = {'s_a': _subject(data, 's_a', (16, 16, 9), 1), 's_b': _subject(data, 's_b', (20, 12, 11), 2, scale=(0.5, 3.0)),
                 's_c': _subject(data, 's_c', (16, 16, 9), 3)}
@@ -217,26 +192,26 @@ def test_device_intake_and_cohort_write_the_host_path_files(tmp_path):
         p = subjects[sid]
         inputs = ['--input_flair', p['flair'], '--input_t2', p['t2'], '--input_t1', p['t1'], '--gt_volume', p['t1ce'], '--eval_mask', p['seg']]
         host, dev = str(tmp_path / f'{sid}_host'), str(tmp_path / f'{sid}_dev')
-        a = _run('mudiff_hip.volume', model + inputs + ['--output_dir', host])
-        b = _run('mudiff_hip.volume', model + inputs + ['--output_dir', dev, '--device_intake'])
-        assert _payload(host + '/predicted_t1ce.nii.gz') == _payload(dev + '/predicted_t1ce.nii.gz')
+        a = VS.run_module('mudiff_hip.volume', model + inputs + ['--output_dir', host])
+        b = VS.run_module('mudiff_hip.volume', model + inputs + ['--output_dir', dev, '--device_intake'])
+        assert VS.payload(host + '/predicted_t1ce.nii.gz') == VS.payload(dev + '/predicted_t1ce.nii.gz')
         assert json.load(open(host + '/metrics_t1ce.json')) == json.load(open(dev + '/metrics_t1ce.json'))
         assert a.stdout.replace(host, 'OUT') == b.stdout.replace(dev, 'OUT')      # the same lines, too
         single[sid] = host
     # an ensemble through both paths (mean and std volumes)
     p = subjects['s_b']
     inputs = ['--input_flair', p['flair'], '--input_t2', p['t2'], '--input_t1', p['t1'], '--num_samples', '2']
-    _run('mudiff_hip.volume', model + inputs + ['--output_dir', str(tmp_path / 'ens_host')])
-    _run('mudiff_hip.volume', model + inputs + ['--output_dir', str(tmp_path / 'ens_dev'), '--device_intake'])
+    VS.run_module('mudiff_hip.volume', model + inputs + ['--output_dir', str(tmp_path / 'ens_host')])
+    VS.run_module('mudiff_hip.volume', model + inputs + ['--output_dir', str(tmp_path / 'ens_dev'), '--device_intake'])
     for name in ('predicted_t1ce.nii.gz', 'predicted_t1ce_std.nii.gz'):
-        assert _payload(str(tmp_path / 'ens_host' / name)) == _payload(str(tmp_path / 'ens_dev' / name))
+        assert VS.payload(str(tmp_path / 'ens_host' / name)) == VS.payload(str(tmp_path / 'ens_dev' / name))
     # the cohort: three subjects, one of them broken
     out = tmp_path / 'cohort'
-    c = _run('mudiff_hip.cohort', model + ['--brats_root', str(data), '--subjects', str(tmp_path / 'test.list'), '--score', '--output_dir',
+    c = VS.run_module('mudiff_hip.cohort', model + ['--brats_root', str(data), '--subjects', str(tmp_path / 'test.list'), '--score', '--output_dir',
                                            str(out), '--io_threads', '2'], expect=1)
     assert '[cohort] skipped s_c' in c.stderr and 'FAILED s_c' in c.stderr and '[cohort] brain: PSNR ' in c.stdout
     for sid in ('s_a', 's_b'):
-        assert _payload(str(out / sid / 'predicted_t1ce.nii.gz')) == _payload(single[sid] + '/predicted_t1ce.nii.gz')
+        assert VS.payload(str(out / sid / 'predicted_t1ce.nii.gz')) == VS.payload(single[sid] + '/predicted_t1ce.nii.gz')
         assert json.load(open(out / sid / 'metrics_t1ce.json')) == json.load(open(single[sid] + '/metrics_t1ce.json'))
     assert not (out / 's_c' / 'predicted_t1ce.nii.gz').exists()
     from mudiff_hip import cohort as Co

@@ -5,7 +5,6 @@ import math
 import os
 import subprocess
 import sys
-import textwrap
 
 import numpy as np
 import pytest
@@ -13,7 +12,7 @@ import torch
 
 from conftest import PKG, REPO
 import volume_metrics_ref as R
-from oracle import mudiff_oracle as O
+import volume_support as VS
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -151,24 +150,9 @@ def test_bad_inputs_raise_value_error():
 # ---------------------------------------------------------------------------------------------------
 # the volume pipeline and the CLI
 # ---------------------------------------------------------------------------------------------------
-def _child(code, timeout=900):
-    env = dict(os.environ, PYTHONPATH=os.pathsep.join([REPO, PKG, os.path.join(REPO, 'tests'), os.environ.get('PYTHONPATH', '')]),
-               MUD_DETERMINISTIC='1')
-    for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE'):
-        env.pop(k, None)
-    p = subprocess.run([sys.executable, '-c', textwrap.dedent(code)], cwd=REPO, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                       text=True, timeout=timeout)
-    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
-    return p
-
-
 def _synthetic_case(tmp_path):
     from mudiff_hip import volume as V
-    cfg = O.default_config(image_size=16, num_channels_dae=16, ch_mult=[1, 2], attn_resolutions=(4,), num_res_blocks=1)
-    exp = tmp_path / 'results' / 'exp0'
-    exp.mkdir(parents=True)
-    for which, name in (('g1', 'gen_diffusive_1'), ('g2', 'gen_diffusive_2')):
-        torch.save({'module.' + k: v for k, v in O.make_state_dict(cfg, which, 9).items()}, str(exp / f'{name}.pth'))
+    VS.write_tiny_model(tmp_path)
     rng = np.random.default_rng(0)
     aff = np.diag([1.0, 1.0, 2.5, 1.0])
     aff[:3, 3] = (-8, -8, 3)
@@ -179,9 +163,7 @@ def _synthetic_case(tmp_path):
         V.write_nifti(paths[m], v.astype(np.float32), aff)
     paths['seg'] = str(tmp_path / 'seg.nii.gz')
     V.write_nifti(paths['seg'], (rng.random((16, 16, 9)) < 0.3).astype(np.float32) * 4, aff)
-    argv = ['--target_modality', 'T1CE', '--exp', 'exp0', '--output_path', str(tmp_path / 'results'), '--image_size', '16',
-            '--num_channels_dae', '16', '--ch_mult', '1', '2', '--attn_resolutions', '4', '--num_res_blocks', '1', '--slice_half_range', '3',
-            '--batch_size', '4', '--input_flair', paths['flair'], '--input_t2', paths['t2'], '--input_t1', paths['t1'], '--seed', '31']
+    argv = VS.model_argv(tmp_path, 3, 4, '--input_flair', paths['flair'], '--input_t2', paths['t2'], '--input_t1', paths['t1'])
     return paths, argv
 
 
@@ -189,26 +171,22 @@ def test_predict_volume_scores_what_it_wrote(tmp_path):
     paths, argv = _synthetic_case(tmp_path)
     ev = ['--gt_volume', paths['t1ce'], '--eval_mask', paths['seg']]
     out = {k: str(tmp_path / k) for k in ('plain', 'eval', 'ens')}
-    res = str(tmp_path / 'rescored.json')
-    p = _child(f'''
-        import json
-        from mudiff_hip import volume as V, volume_metrics as VM
-        V.predict_volume(V.build_argparser({argv + ['--output_dir', out['plain']]!r}))
-        V.predict_volume(V.build_argparser({argv + ev + ['--output_dir', out['eval']]!r}))
-        V.predict_volume(V.build_argparser({argv + ev + ['--num_samples', '3', '--output_dir', out['ens']]!r}))
-        a = VM.score_files({out['eval'] + '/predicted_t1ce.nii.gz'!r}, {paths['t1ce']!r}, {paths['seg']!r}, slice_half_range=3)
-        b = VM.score_files({out['ens'] + '/predicted_t1ce.nii.gz'!r}, {paths['t1ce']!r}, {paths['seg']!r},
-                           {out['ens'] + '/predicted_t1ce_std.nii.gz'!r}, slice_half_range=3)
-        json.dump(dict(eval=a, ens=b), open({res!r}, 'w'))
-    ''')
-    assert '[metrics] brain: PSNR ' in p.stdout and '[metrics] slice2d (8-bit, 7 planes)' in p.stdout
-    lines = p.stdout.splitlines()
+    jobs = {'plain': argv, 'eval': argv + ev, 'ens': argv + ev + ['--num_samples', '3']}
+    log = VS.run_plan(tmp_path, [VS.volume_step(k, a + ['--output_dir', out[k]]) for k, a in jobs.items()], 900)
+    stdout = ''.join(log[k] for k in jobs)
+    # the files scored once more, here (the scoring kernels need no MUD_DETERMINISTIC); through JSON like the reports they are compared with
+    from mudiff_hip import volume_metrics as VM
+    rescored = json.loads(json.dumps(dict(
+        eval=VM.score_files(out['eval'] + '/predicted_t1ce.nii.gz', paths['t1ce'], paths['seg'], slice_half_range=3),
+        ens=VM.score_files(out['ens'] + '/predicted_t1ce.nii.gz', paths['t1ce'], paths['seg'], out['ens'] + '/predicted_t1ce_std.nii.gz',
+                           slice_half_range=3))))
+    assert '[metrics] brain: PSNR ' in stdout and '[metrics] slice2d (8-bit, 7 planes)' in stdout
+    lines = stdout.splitlines()
     done = [i for i, ln in enumerate(lines) if ln.startswith('[done] saved:')]
     assert len(done) == 3 and lines[done[1] + 1].startswith('[metrics] slab: ')
     with open(os.path.join(out['plain'], 'predicted_t1ce.nii.gz'), 'rb') as f1, open(os.path.join(out['eval'], 'predicted_t1ce.nii.gz'), 'rb') as f2:
         assert f1.read() == f2.read()                                          # scoring does not change the prediction
     assert not os.path.exists(os.path.join(out['plain'], 'metrics_t1ce.json'))
-    rescored = json.load(open(res))
     got = json.load(open(os.path.join(out['eval'], 'metrics_t1ce.json')))
     assert got == rescored['eval']                                              # bit-identical: the same array, the same kernels
     assert got['slab'] == [1, 7] and got['regions'] == list(NAMES) and 'uncertainty' not in got
@@ -217,7 +195,6 @@ def test_predict_volume_scores_what_it_wrote(tmp_path):
     # against the restatement, from the written file
     from mudiff_hip import ops
     from mudiff_hip import volume as V
-    from mudiff_hip import volume_metrics as VM
     for which, rep, std_name in (('eval', got, None), ('ens', ens, 'predicted_t1ce_std.nii.gz')):
         pred = VM.slab_planes(V.read_nifti(os.path.join(out[which], 'predicted_t1ce.nii.gz'))[0], 1, 7)
         raw = V.read_nifti(paths['t1ce'])[0]

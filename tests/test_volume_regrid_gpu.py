@@ -4,21 +4,16 @@ neighbour on a label volume; the C ABI's argument checks; then `predict_volume -
 against the same run on inputs resampled beforehand, byte for byte, through the host path and --device_intake, and the scoring of a
 ground truth and a mask on other grids."""
 import ctypes as C
-import gzip
 import json
 import os
-import subprocess
-import sys
-import textwrap
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import PKG, REPO
 import volume_intake_ref as R
 import volume_regrid_ref as G
-from oracle import mudiff_oracle as O
+import volume_support as VS
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -30,8 +25,7 @@ def _device_regrid(vol, name, mode='linear', scale=(1.0, 0.0), shapes=()):
     from mudiff_hip import volume_intake as VI
     from mudiff_hip import volume_regrid as VR
     _, sa, rs, ra = G.case(name, vol.shape, *shapes)
-    raw = VI.RawVolume(np.ascontiguousarray(vol.reshape(-1, order='F')), R.CODES[vol.dtype.str[1:]], '<', float(np.float32(scale[0])),
-                       float(np.float32(scale[1])), vol.shape, sa, None)
+    raw = VS.raw_volume(vol, scale, sa)
     M = VR.grid_matrix(sa, ra)
     slope, inter = (raw.slope, raw.inter) if raw.scaled else (1.0, 0.0)
     out = VR.regrid(VI.upload(raw, DEV), raw.code, vol.shape, slope, inter, M, rs, mode)
@@ -142,11 +136,6 @@ def test_c_abi_rejects_bad_arguments_without_launching():
 # ---------------------------------------------------------------------------------------------------
 # end to end: the tiny model of the other volume tests, inputs on three grids
 # ---------------------------------------------------------------------------------------------------
-def _payload(path):
-    with gzip.open(path, 'rb') as f:
-        return f.read()
-
-
 def _affine(lin, centre_of):
     a = np.eye(4)
     a[:3, :3] = lin
@@ -160,11 +149,7 @@ def runs(tmp_path_factory):
     each run, and the exceptions of the runs that must fail."""
     from mudiff_hip import volume as V
     tmp = tmp_path_factory.mktemp('regrid')
-    cfg = O.default_config(image_size=16, num_channels_dae=16, ch_mult=[1, 2], attn_resolutions=(4,), num_res_blocks=1)
-    exp = tmp / 'results' / 'exp0'
-    exp.mkdir(parents=True)
-    for which, name in (('g1', 'gen_diffusive_1'), ('g2', 'gen_diffusive_2')):
-        torch.save({'module.' + k: v for k, v in O.make_state_dict(cfg, which, 9).items()}, str(exp / f'{name}.pth'))
+    VS.write_tiny_model(tmp)
     rng = np.random.default_rng(7)
     ref_shape, obl_shape = (16, 16, 9), (18, 14, 11)
     ref_aff = _affine(np.diag([1.0, 1.0, 2.5]), ref_shape)
@@ -181,9 +166,7 @@ def runs(tmp_path_factory):
     R.write_nifti_typed(p['t1'], volume(ref_shape, 'i2'), '<', 0.5, 3.0, affine=shift_aff)
     R.write_nifti_typed(p['t1ce'], volume(obl_shape, 'i2'), affine=obl_aff)         # the ground truth, oblique
     R.write_nifti_typed(p['seg'], np.asfortranarray(((rng.random(ref_shape) < 0.3) * 4).astype('u1')), affine=shift_aff)
-    model = ['--target_modality', 'T1CE', '--exp', 'exp0', '--output_path', str(tmp / 'results'), '--image_size', '16', '--num_channels_dae',
-             '16', '--ch_mult', '1', '2', '--attn_resolutions', '4', '--num_res_blocks', '1', '--slice_half_range', '3', '--batch_size', '4',
-             '--seed', '31']
+    model = VS.model_argv(tmp, 3, 4)
     raw_in = ['--input_flair', p['flair'], '--input_t2', p['t2'], '--input_t1', p['t1']]
     pre_in = ['--input_flair', p['flair'], '--input_t2', p['t2_pre'], '--input_t1', p['t1_pre']]
     raw_ev, pre_ev = ['--gt_volume', p['t1ce'], '--eval_mask', p['seg']], ['--gt_volume', p['t1ce_pre'], '--eval_mask', p['seg_pre']]
@@ -197,44 +180,9 @@ def runs(tmp_path_factory):
         'score_regrid': (pre_in + raw_ev + ['--regrid'], False), 'score_pre': (pre_in + pre_ev, False), 'score_noflag': (pre_in + raw_ev, True),
     }
     jobs = {k: (model + a + ['--output_dir', str(tmp / k)], bad) for k, (a, bad) in jobs.items()}
-    log = str(tmp / 'log.json')
-    code = f'''
-        import contextlib, io, json
-        import numpy as np
-        from mudiff_hip import volume as V, volume_intake as VI, volume_regrid as VR
-        p, dev = {p!r}, 'cuda:0'
-        ref = VI.read_nifti_raw(p['flair'])
-        world = VR.world_affine_of(ref.affine, ref.header)
-        for k, mode in (('t2', 'linear'), ('t1', 'linear'), ('t1ce', 'linear'), ('seg', 'nearest')):      # the offline resampling
-            r = VR.regrid_to(VI.read_nifti_raw(p[k]), ref.shape, world, dev, mode)
-            assert isinstance(r, VR.RegriddedVolume) and r.code == 16 and r.shape == ref.shape
-            V.write_nifti(p[k + '_pre'], r.values_float32(), ref.affine)
-        log = {{}}
-        for name, (argv, bad) in {jobs!r}.items():
-            out = io.StringIO()
-            try:
-                with contextlib.redirect_stdout(out):
-                    V.predict_volume(V.build_argparser(argv))
-                err = None
-            except ValueError as e:
-                err = str(e)
-            assert (err is not None) == bad, (name, err)
-            log[name] = dict(stdout=out.getvalue(), error=err)
-        json.dump(log, open({log!r}, 'w'))
-    '''
-    env = dict(os.environ, PYTHONPATH=os.pathsep.join([REPO, PKG, os.environ.get('PYTHONPATH', '')]), MUD_DETERMINISTIC='1')
-    for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE'):
-        env.pop(k, None)
-    c = subprocess.run([sys.executable, '-c', textwrap.dedent(code)], cwd=REPO, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                       timeout=900)
-    assert c.returncode == 0, c.stdout[-3000:] + c.stderr[-3000:]
-    return dict(tmp=tmp, paths=p, log=json.load(open(log)), pred=lambda k: _payload(str(tmp / k / 'predicted_t1ce.nii.gz')))
-
-
-def _done(runs, name):
-    lines = [ln for ln in runs['log'][name]['stdout'].splitlines() if ln.startswith('[done]')]
-    assert len(lines) == 1
-    return lines[0]
+    offline = [VS.regrid_step(p[k], p['flair'], p[k + '_pre'], mode) for k, mode in (('t2', 'linear'), ('t1', 'linear'), ('t1ce', 'linear'), ('seg', 'nearest'))]
+    log = VS.run_plan(tmp, offline + [VS.volume_step(k, argv, raises=bad) for k, (argv, bad) in jobs.items()], 900)
+    return dict(tmp=tmp, paths=p, log=log, pred=lambda k: VS.payload(str(tmp / k / 'predicted_t1ce.nii.gz')))
 
 
 def test_regrid_run_writes_the_file_of_the_run_on_resampled_inputs(runs):
@@ -243,9 +191,9 @@ def test_regrid_run_writes_the_file_of_the_run_on_resampled_inputs(runs):
     want_z = runs['pred']('pre_host_z')
     assert runs['pred']('regrid_host_z') == want_z and runs['pred']('regrid_dev_z') == want_z and want_z != want
     for name in ('regrid_host', 'regrid_dev'):
-        assert _done(runs, name).endswith(' | regrid=T2,T1')
+        assert VS.done_line(runs['log'][name]['stdout']).endswith(' | regrid=T2,T1')
     for name in ('regrid_host_z', 'regrid_dev_z'):
-        assert _done(runs, name).endswith(' | norm=zscore | regrid=T2,T1')
+        assert VS.done_line(runs['log'][name]['stdout']).endswith(' | norm=zscore | regrid=T2,T1')
     # the inputs really were on other grids: the resampled T1 differs from the stored one although the shapes agree
     from mudiff_hip import volume as V
     t1, t1_pre = V.read_nifti(runs['paths']['t1'])[0], V.read_nifti(runs['paths']['t1_pre'])[0]
@@ -258,14 +206,14 @@ def test_without_the_flag_nothing_changes(runs):
     p = runs['paths']
     assert runs['log']['noflag_host']['error'] == 'All input volumes must share shape. Got (18, 14, 11) vs (16, 16, 9) for T2'
     assert runs['log']['noflag_dev']['error'] == f"All input volumes must share shape. Got (18, 14, 11) vs (16, 16, 9) for {p['t2']}"
-    assert ' | regrid=' not in _done(runs, 'pre_host')
+    assert ' | regrid=' not in VS.done_line(runs['log']['pre_host']['stdout'])
 
 
 def test_the_flag_on_inputs_that_share_a_grid_changes_nothing(runs):
     want = runs['pred']('pre_host')
     assert runs['pred']('pre_flag_host') == want and runs['pred']('pre_flag_dev') == want
     tmp = str(runs['tmp'])
-    lines = {k: _done(runs, k).replace(os.path.join(tmp, k), 'OUT') for k in ('pre_host', 'pre_flag_host', 'pre_flag_dev')}
+    lines = {k: VS.done_line(runs['log'][k]['stdout']).replace(os.path.join(tmp, k), 'OUT') for k in ('pre_host', 'pre_flag_host', 'pre_flag_dev')}
     assert lines['pre_flag_host'] == lines['pre_host'] and lines['pre_flag_dev'] == lines['pre_host']
 
 
@@ -274,7 +222,7 @@ def test_scoring_a_ground_truth_and_a_mask_on_other_grids(runs):
     got, want = (json.load(open(tmp / k / 'metrics_t1ce.json')) for k in ('score_regrid', 'score_pre'))
     assert got == want and got['regions'] == ['slab', 'brain', 'tumor', 'healthy'] and got['metrics']['tumor']['voxels'] > 0
     assert runs['pred']('score_regrid') == runs['pred']('pre_host')                # scoring does not change the prediction
-    assert _done(runs, 'score_regrid').endswith(' | regrid=gt_volume,eval_mask') and ' | regrid=' not in _done(runs, 'score_pre')
+    assert VS.done_line(runs['log']['score_regrid']['stdout']).endswith(' | regrid=gt_volume,eval_mask') and ' | regrid=' not in VS.done_line(runs['log']['score_pre']['stdout'])
     assert runs['log']['score_noflag']['error'].startswith('--gt_volume / --eval_mask: prediction (16, 16, 9) and ground truth (18, 14, 11) '
                                                           'differ in shape')
     assert not os.path.exists(tmp / 'score_noflag' / 'predicted_t1ce.nii.gz')      # refused before any sampling

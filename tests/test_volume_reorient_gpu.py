@@ -9,9 +9,6 @@ import ctypes as C
 import itertools
 import json
 import os
-import subprocess
-import sys
-import textwrap
 import types
 
 import numpy as np
@@ -20,8 +17,7 @@ import torch
 
 import volume_intake_ref as I
 import volume_reorient_ref as R
-from conftest import PKG, REPO
-from oracle import mudiff_oracle as O
+import volume_support as VS
 
 pytestmark = pytest.mark.gpu
 
@@ -194,11 +190,7 @@ def _read(path):
 @pytest.fixture(scope='module')
 def runs(tmp_path_factory):
     tmp = tmp_path_factory.mktemp('reorient')
-    cfg = O.default_config(image_size=16, num_channels_dae=16, ch_mult=[1, 2], attn_resolutions=(4,), num_res_blocks=1)
-    exp = tmp / 'results' / 'exp0'
-    exp.mkdir(parents=True)
-    for which, name in (('g1', 'gen_diffusive_1'), ('g2', 'gen_diffusive_2')):
-        torch.save({'module.' + k: v for k, v in O.make_state_dict(cfg, which, 9).items()}, str(exp / f'{name}.pth'))
+    VS.write_tiny_model(tmp)
     vols = {'flair': _phantom(21), 't2': _phantom(22), 't1': _phantom(23), 'gt': _phantom(24)}
     vols['mask'] = np.asfortranarray((vols['gt'] > 1200).astype(np.uint8))
     files = {}
@@ -206,9 +198,7 @@ def runs(tmp_path_factory):
         for k, vol in vols.items():
             stored, affine = R.stored_as(vol, LPS_AFFINE, code)
             files[code, k] = I.write_nifti_typed(tmp / f'{code}_{k}.nii.gz', stored, affine=affine)
-    model = ['--target_modality', 'T1CE', '--exp', 'exp0', '--output_path', str(tmp / 'results'), '--image_size', '16', '--num_channels_dae',
-             '16', '--ch_mult', '1', '2', '--attn_resolutions', '4', '--num_res_blocks', '1', '--slice_half_range', '3', '--batch_size', '7',
-             '--seed', '31']
+    model = VS.model_argv(tmp, 3, 7)
     inputs = lambda code: ['--input_flair', files[code, 'flair'], '--input_t2', files[code, 't2'], '--input_t1', files[code, 't1']]      # noqa: E731
     ev = lambda code: ['--gt_volume', files[code, 'gt'], '--eval_mask', files[code, 'mask']]      # noqa: E731
     back = ['--reorient', '--reorient_back']
@@ -217,40 +207,8 @@ def runs(tmp_path_factory):
             'sag_host': inputs(SAGITTAL) + back, 'sag_dev': inputs(SAGITTAL) + back + ['--device_intake'],
             'ras_plain': inputs('RAS')}
     jobs = {k: model + a + ['--output_dir', str(tmp / k)] for k, a in jobs.items()}
-    log = str(tmp / 'log.json')
-    code = f'''
-        import contextlib, io, json, warnings
-        import numpy as np, torch
-        from mudiff_hip import volume as V
-        log, current = {{}}, [None]
-        sample = V.predict_from_conditions
-        def spy(args, plan, evaluation, gen1, gen2, device, stacks, ref, **kw):
-            np.savez({str(tmp)!r} + '/stacks_' + current[0] + '.npz', *[s.cpu().numpy() if torch.is_tensor(s) else np.asarray(s) for s in stacks])
-            return sample(args, plan, evaluation, gen1, gen2, device, stacks, ref, **kw)
-        V.predict_from_conditions = spy
-        for name, argv in {jobs!r}.items():
-            out = io.StringIO()
-            current[0] = name
-            with contextlib.redirect_stdout(out), warnings.catch_warnings():
-                warnings.simplefilter('ignore', RuntimeWarning)
-                V.predict_volume(V.build_argparser(argv))
-            log[name] = out.getvalue()
-        json.dump(log, open({log!r}, 'w'))
-    '''
-    env = dict(os.environ, PYTHONPATH=os.pathsep.join([REPO, PKG, os.environ.get('PYTHONPATH', '')]), MUD_DETERMINISTIC='1')
-    for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE'):
-        env.pop(k, None)
-    c = subprocess.run([sys.executable, '-c', textwrap.dedent(code)], cwd=REPO, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                       timeout=600)
-    assert c.returncode == 0, c.stdout[-3000:] + c.stderr[-3000:]
-    stacks = {k: [v for _, v in sorted(np.load(str(tmp / f'stacks_{k}.npz')).items(), key=lambda kv: int(kv[0].split('_')[1]))] for k in jobs}
-    return dict(tmp=tmp, log=json.load(open(log)), stacks=stacks, files=files)
-
-
-def _done(runs, name):
-    lines = [ln for ln in runs['log'][name].splitlines() if ln.startswith('[done]')]
-    assert len(lines) == 1
-    return lines[0]
+    log = VS.run_plan(tmp, [VS.volume_step(k, argv, stacks=True) for k, argv in jobs.items()], 600, ignore='RuntimeWarning')
+    return dict(tmp=tmp, log=log, stacks={k: VS.load_stacks(tmp, k) for k in jobs}, files=files)
 
 
 def test_equivariance_end_to_end(runs):
@@ -272,7 +230,7 @@ def test_equivariance_end_to_end(runs):
             assert np.array_equal(affine.astype(np.float32), want_affine.astype(np.float32)), name
             assert np.array_equal(affine, _read(runs['files'][code, 'flair'])[1])       # the first input's original affine
             flips = f'FLAIR:{code}>LPS,T2:{code}>LPS,T1:{code}>LPS'
-            assert _done(runs, name).endswith(f' | reorient={flips}') and f'shape={SHAPE}' in _done(runs, name)
+            assert VS.done_line(runs['log'][name]).endswith(f' | reorient={flips}') and f'shape={SHAPE}' in VS.done_line(runs['log'][name])
             entries = json.load(open(tmp / name / 'reorient_t1ce.json'))
             assert list(entries) == ['FLAIR', 'T2', 'T1'] and all(e['moved'] and e['shape_to'] == list(SHAPE) for e in entries.values())
     # the flag does something: the same RAS files without it give another prediction, and nothing of the feature shows

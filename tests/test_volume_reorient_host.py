@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import volume_reorient_ref as R
+from volume_support import raw_volume
 
 BASE = ['--target_modality', 'T1CE', '--output_dir', 'o', '--exp', 'e']
 SAGITTAL, CORONAL = 'PSL', 'LSP'                    # storage axes of a sagittal / a coronal acquisition
@@ -185,10 +186,7 @@ def test_suffix_and_reports(tmp_path):
 
 
 def _raw(vol, affine):
-    from mudiff_hip import NIFTI_I2
-    from mudiff_hip.volume_intake import RawVolume
-    vol = np.asarray(vol, np.int16)
-    return RawVolume(np.ascontiguousarray(vol.reshape(-1, order='F')), NIFTI_I2, '<', 1.0, 0.0, vol.shape, np.asarray(affine, np.float64), None)
+    return raw_volume(np.asarray(vol, np.int16), affine=np.asarray(affine, np.float64))
 
 
 def _host_reorient(raw, device, target='LPS'):

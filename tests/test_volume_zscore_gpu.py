@@ -1,29 +1,18 @@
 """GPU: --norm zscore.  mud_volume_slab_zscore against the host function, `python -m mudiff_hip.volume --norm
 zscore` with and without --device_intake, `python -m mudiff_hip.cohort --norm zscore`, and the scoring of a ground truth mapped by
 the same rule.  Every comparison is exact."""
-import gzip
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import PKG, REPO
 import volume_intake_ref as R
-from oracle import mudiff_oracle as O
+import volume_support as VS
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
-
-
-def _raw(vol, scale=(1.0, 0.0)):
-    from mudiff_hip import volume_intake as VI
-    slope, inter = float(np.float32(scale[0])), float(np.float32(scale[1]))            # what a header holds
-    return VI.RawVolume(np.ascontiguousarray(vol.reshape(-1, order='F')), R.CODES[vol.dtype.str[1:]], '<', slope, inter, vol.shape, np.eye(4),
-                        None)
 
 
 def _host_stack(vol, scale, half):
@@ -46,7 +35,7 @@ def _same(got, want):
 def _check_slab(vol, scale, half):
     from mudiff_hip import volume_intake as VI
     want, s0, s1 = _host_stack(vol, scale, half)
-    raw = _raw(vol, scale)
+    raw = VS.raw_volume(vol, scale)
     slope, inter = (raw.slope, raw.inter) if raw.scaled else (1.0, 0.0)
     with np.errstate(invalid='ignore'):
         mean, std = VI.zscore_moments(raw)
@@ -95,7 +84,7 @@ def test_slab_zscore_keeps_nan():
     mean, std, want = _check_slab(vol, (1.0, 0.0), 4)
     assert np.isnan(mean) and np.isnan(std) and bool(torch.isnan(want).all())
     m, s = np.float32(12.5), np.float32(800.0)
-    t = VI.slab_zscore(VI.upload(_raw(vol), DEV), R.CODES['f4'], vol.shape, 1.0, 0.0, m, s, 1, 9).cpu()
+    t = VI.slab_zscore(VI.upload(VS.raw_volume(vol), DEV), R.CODES['f4'], vol.shape, 1.0, 0.0, m, s, 1, 9).cpu()
     ref = torch.clamp(torch.from_numpy(np.ascontiguousarray(np.moveaxis((vol - m) / s, 2, 0)[1:10])), -3.0, 3.0) / 3.0
     assert _same(t[:, 0], ref) and int(torch.isnan(t).sum()) == 1 and bool(torch.isnan(t[4, 0, 3, 4]))
 
@@ -151,21 +140,6 @@ def test_a_prediction_equal_to_the_mapped_ground_truth_scores_perfectly_only_in_
 # ---------------------------------------------------------------------------------------------------
 # end to end: the volume CLI with and without --device_intake, then the cohort
 # ---------------------------------------------------------------------------------------------------
-def _run(module, argv, expect=0, timeout=900):
-    env = dict(os.environ, PYTHONPATH=os.pathsep.join([REPO, PKG, os.environ.get('PYTHONPATH', '')]), MUD_DETERMINISTIC='1')
-    for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE'):
-        env.pop(k, None)
-    p = subprocess.run([sys.executable, '-m', module] + argv, cwd=REPO, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                       timeout=timeout)
-    assert p.returncode == expect, (p.returncode, p.stdout[-3000:], p.stderr[-3000:])
-    return p
-
-
-def _payload(path):
-    with gzip.open(path, 'rb') as f:
-        return f.read()
-
-
 def _subject(root, sid, shape, seed, dtype='i2', scale=(0.0, 0.0)):
     rng = np.random.default_rng(seed)
     os.makedirs(root / sid)
@@ -180,14 +154,8 @@ def _subject(root, sid, shape, seed, dtype='i2', scale=(0.0, 0.0)):
 
 
 def test_zscore_runs_write_the_same_files_through_every_path(tmp_path):
-    cfg = O.default_config(image_size=16, num_channels_dae=16, ch_mult=[1, 2], attn_resolutions=(4,), num_res_blocks=1)
-    exp = tmp_path / 'results' / 'exp0'
-    exp.mkdir(parents=True)
-    for which, name in (('g1', 'gen_diffusive_1'), ('g2', 'gen_diffusive_2')):
-        torch.save({'module.' + k: v for k, v in O.make_state_dict(cfg, which, 9).items()}, str(exp / f'{name}.pth'))
-    model = ['--target_modality', 'T1CE', '--exp', 'exp0', '--output_path', str(tmp_path / 'results'), '--image_size', '16',
-             '--num_channels_dae', '16', '--ch_mult', '1', '2', '--attn_resolutions', '4', '--num_res_blocks', '1', '--slice_half_range', '3',
-             '--batch_size', '4', '--seed', '31', '--resize_back', '--norm', 'zscore']
+    VS.write_tiny_model(tmp_path)
+    model = VS.model_argv(tmp_path, 3, 4, '--resize_back', '--norm', 'zscore')
     data = tmp_path / 'brats'
     subjects = {'s_a': _subject(data, 's_a', (16, 16, 9), 1), 's_b': _subject(data, 's_b', (20, 12, 11), 2, scale=(0.5, 3.0))}
     (tmp_path / 'test.list').write_text('s_a\ns_b\n')
@@ -196,9 +164,9 @@ def test_zscore_runs_write_the_same_files_through_every_path(tmp_path):
         p = subjects[sid]
         inputs = ['--input_flair', p['flair'], '--input_t2', p['t2'], '--input_t1', p['t1'], '--gt_volume', p['t1ce'], '--eval_mask', p['seg']]
         host, dev = str(tmp_path / f'{sid}_host'), str(tmp_path / f'{sid}_dev')
-        a = _run('mudiff_hip.volume', model + inputs + ['--output_dir', host])
-        b = _run('mudiff_hip.volume', model + inputs + ['--output_dir', dev, '--device_intake'])
-        assert _payload(host + '/predicted_t1ce.nii.gz') == _payload(dev + '/predicted_t1ce.nii.gz')
+        a = VS.run_module('mudiff_hip.volume', model + inputs + ['--output_dir', host])
+        b = VS.run_module('mudiff_hip.volume', model + inputs + ['--output_dir', dev, '--device_intake'])
+        assert VS.payload(host + '/predicted_t1ce.nii.gz') == VS.payload(dev + '/predicted_t1ce.nii.gz')
         rep = json.load(open(host + '/metrics_t1ce.json'))
         assert rep == json.load(open(dev + '/metrics_t1ce.json')) and rep['norm'] == 'zscore'
         assert a.stdout.replace(host, 'OUT') == b.stdout.replace(dev, 'OUT')      # the same lines, too
@@ -207,25 +175,25 @@ def test_zscore_runs_write_the_same_files_through_every_path(tmp_path):
         single[sid] = host
     # the mode changes the prediction: the default run of the same subject writes another file, and says nothing about a mode
     p = subjects['s_a']
-    d = _run('mudiff_hip.volume', [m for m in model if m not in ('--norm', 'zscore')] +
+    d = VS.run_module('mudiff_hip.volume', [m for m in model if m not in ('--norm', 'zscore')] +
              ['--input_flair', p['flair'], '--input_t2', p['t2'], '--input_t1', p['t1'], '--output_dir', str(tmp_path / 'default')])
-    assert _payload(str(tmp_path / 'default' / 'predicted_t1ce.nii.gz')) != _payload(single['s_a'] + '/predicted_t1ce.nii.gz')
+    assert VS.payload(str(tmp_path / 'default' / 'predicted_t1ce.nii.gz')) != VS.payload(single['s_a'] + '/predicted_t1ce.nii.gz')
     assert 'norm=' not in d.stdout
     # an ensemble through both paths (mean and std volumes)
     p = subjects['s_b']
     inputs = ['--input_flair', p['flair'], '--input_t2', p['t2'], '--input_t1', p['t1'], '--num_samples', '2']
-    e = _run('mudiff_hip.volume', model + inputs + ['--output_dir', str(tmp_path / 'ens_host')])
-    _run('mudiff_hip.volume', model + inputs + ['--output_dir', str(tmp_path / 'ens_dev'), '--device_intake'])
+    e = VS.run_module('mudiff_hip.volume', model + inputs + ['--output_dir', str(tmp_path / 'ens_host')])
+    VS.run_module('mudiff_hip.volume', model + inputs + ['--output_dir', str(tmp_path / 'ens_dev'), '--device_intake'])
     for name in ('predicted_t1ce.nii.gz', 'predicted_t1ce_std.nii.gz'):
-        assert _payload(str(tmp_path / 'ens_host' / name)) == _payload(str(tmp_path / 'ens_dev' / name))
+        assert VS.payload(str(tmp_path / 'ens_host' / name)) == VS.payload(str(tmp_path / 'ens_dev' / name))
     assert [ln for ln in e.stdout.splitlines() if ln.startswith('[done]')][0].endswith(' | norm=zscore')
     # the cohort: both subjects, moments on the prefetch thread
     out = tmp_path / 'cohort'
-    c = _run('mudiff_hip.cohort', model + ['--brats_root', str(data), '--subjects', str(tmp_path / 'test.list'), '--score', '--output_dir',
+    c = VS.run_module('mudiff_hip.cohort', model + ['--brats_root', str(data), '--subjects', str(tmp_path / 'test.list'), '--score', '--output_dir',
                                            str(out), '--io_threads', '2'])
     assert c.stdout.count(' | norm=zscore') == 2
     for sid in ('s_a', 's_b'):
-        assert _payload(str(out / sid / 'predicted_t1ce.nii.gz')) == _payload(single[sid] + '/predicted_t1ce.nii.gz')
+        assert VS.payload(str(out / sid / 'predicted_t1ce.nii.gz')) == VS.payload(single[sid] + '/predicted_t1ce.nii.gz')
         assert json.load(open(out / sid / 'metrics_t1ce.json')) == json.load(open(single[sid] + '/metrics_t1ce.json'))
     rep = json.load(open(out / 'cohort_t1ce.json'))
     assert rep['norm'] == 'zscore' and [r['id'] for r in rep['subjects']] == ['s_a', 's_b'] and rep['timing']['moments'] > 0
