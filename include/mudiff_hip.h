@@ -402,6 +402,18 @@ int mud_ensemble_stats(const float* samples, int n, int N, int64_t hw, float sca
  *   subtraction and the product rounded separately; hist[bin_fix][bin_mov] += 1.  hist: device, uint32 [bins][bins], cleared first
  *   (stream-ordered).  Counts are integers (LDS atomics per workgroup, one global atomic per non-empty bin): the result does not depend
  *   on the order of arrival and is the same bits on every run.  bins: 2 to 64; stride > 0; m, lo and scale finite.
+ * mud_volume_mirror_moments (--align; no reference counterpart): what the search for a head's mid-sagittal plane
+ *   evaluates: the moments of a stored volume (X x Y x Z) against its own mirror image through K candidate planes, in one launch.  mats:
+ *   device, K x 12 doubles, 8-byte aligned; candidate k's 3 x 4 matrix (the matrix of mud_volume_regrid) maps a voxel index to the voxel
+ *   coordinate p of its mirror image.  Sample points and the overlap rule are mud_volume_joint_hist's: the voxels whose indices are all
+ *   multiples of `stride`; a pair is counted iff 0 <= p_a <= S_a - 1 on every axis and both values are finite; a = bin of the stored
+ *   voxel's value, b = bin of mode 0 of mud_volume_regrid at p, both by mud_volume_joint_hist's formula with the one (lo, scale).
+ *   sums: device, uint64 [K][6], 8-byte aligned, cleared first (stream-ordered): n, sum a, sum b, sum a^2, sum b^2, sum a b over the
+ *   counted pairs of candidate k.  A candidate whose matrix holds a value that is not finite counts nothing (its p fails the overlap
+ *   rule); the matrices are device memory and are not inspected on the host (mudiff_hip.ops.volume_mirror_moments refuses them before
+ *   it uploads them).  Integer sums (registers, wave shuffles, LDS, then one 64-bit atomic add per workgroup, candidate and non-zero sum):
+ *   the result does not depend on the order of arrival, nor on which other candidates share the launch, and is the same bits on every
+ *   run.  bins: 2 to 256; stride > 0; 1 <= K <= 1048560; lo and scale finite.
  * mud_volume_bias_* (--bias_correct): the device's share of an N4-style bias-field correction; the loop around
  *   them is mudiff_hip.volume_bias.loop.  Sample points: the voxels whose indices are all multiples of `shrink`, nx x ny x nz of them (nx =
  *   ceil(X / shrink), ...), flat with x fastest.  The field F is a sum of uniform cubic B-spline lattices: level l = 0 .. levels - 1 (at
@@ -531,6 +543,8 @@ int mud_volume_regrid_cubic(const double* coeffs, int SX, int SY, int SZ, const 
 int mud_volume_joint_hist(const void* fix, int fix_dt, int X, int Y, int Z, float fix_slope, float fix_inter, const void* mov, int mov_dt,
                           int SX, int SY, int SZ, float mov_slope, float mov_inter, const double* m, int stride, double fix_lo,
                           double fix_scale, double mov_lo, double mov_scale, int bins, uint32_t* hist, void* stream);
+int mud_volume_mirror_moments(const void* vol, int datatype, int X, int Y, int Z, float slope, float inter, const double* mats, int K,
+                              int stride, double lo, double scale, int bins, uint64_t* sums, void* stream);
 int mud_volume_bias_log(const void* vol, int datatype, int X, int Y, int Z, float slope, float inter, int shrink, float* u, void* stream);
 int mud_volume_bias_corrected(const float* u, const float* c_old, float* c_new, const double* lattices, int levels, int X, int Y, int Z,
                               int shrink, uint64_t* stats, void* stream);

@@ -148,6 +148,7 @@ _SIGNATURES = {
     'mud_volume_bspline_coeffs': (_I, [_P, _I, _I, _I, _I, _F, _F, _P, _P, _P]),
     'mud_volume_regrid_cubic': (_I, [_P, _I, _I, _I, _P, _I, _F, _F, C.POINTER(C.c_double), _D, _D, _I, _I, _I, _P, _P]),
     'mud_volume_joint_hist': (_I, [_P, _I, _I, _I, _I, _F, _F, _P, _I, _I, _I, _I, _F, _F, C.POINTER(C.c_double), _I, _D, _D, _D, _D, _I, _P, _P]),
+    'mud_volume_mirror_moments': (_I, [_P, _I, _I, _I, _I, _F, _F, _P, _I, _I, _D, _D, _I, _P, _P]),
     'mud_volume_bias_log': (_I, [_P, _I, _I, _I, _I, _F, _F, _I, _P, _P]),
     'mud_volume_bias_corrected': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     'mud_volume_bias_hist': (_I, [_P, _L, _D, _D, _I, _P, _P]),

@@ -223,7 +223,8 @@ def run(args, subjects, predict=None):
                     torch.manual_seed(args.seed)
                     t0 = time.perf_counter()
                     conds, ref, report = prepare_inputs(list(zip(needed, raws)), options, gpu,      # (--coregister and --bias_correct work
-                                                        labels=None if device is None else subject.inputs)      # here: they need the GPU)
+                                                        labels=None if device is None else subject.inputs,      # here: they need the GPU)
+                                                        align=found.get('align'))
                     if device is not None:
                         conds = [VI.condition_from_raw(vol, options.half_range, args.image_size, device, name=subject.inputs[m], norm=norm)
                                  for m, vol in zip(needed, conds)]

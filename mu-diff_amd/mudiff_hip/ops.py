@@ -1261,3 +1261,24 @@ def volume_lowpass(dev_raw, code, shape, slope, inter, weights_xyz, out=None, sc
     _launch('volume_lowpass', dev_raw.device, load().mud_volume_lowpass, ptr(dev_raw), int(code), X, Y, Z, float(slope), float(inter), *args,
             ptr(out), ptr(scratch), ptr(bad), STREAM, nbytes=float(dev_raw.numel() * (dev_raw.element_size() + 4 + 8 * (len(arrays) - 1))))
     return out, int(bad.cpu().numpy().view(np.uint32)[0])
+
+
+# ---------------------------------------------------------------------------------------------------
+# --align (csrc/volume_align.hip; the host's share is mudiff_hip.volume_align)
+# ---------------------------------------------------------------------------------------------------
+def volume_mirror_moments(dev_raw, code, shape, slope, inter, mats, stride, lo, scale, bins):
+    """mud_volume_mirror_moments: the flat device array of a volume's stored voxels and K candidate matrices (host, [K, 3, 4] or [K, 12]
+    fp64: voxel index -> the voxel coordinate of its mirror image) -> device int64 [K, 6] (uint64 sums): n, sum a, sum b, sum a^2, sum b^2,
+    sum a b of the bin indices over the overlap, one launch for all K.  ValueError, before anything is uploaded or launched, for matrices
+    that are not finite."""
+    X, Y, Z = _bias_volume('volume_mirror_moments', dev_raw, code, shape)
+    m = np.ascontiguousarray(np.asarray(mats, np.float64).reshape(-1, 12))
+    if m.shape[0] < 1 or not np.isfinite(m).all():
+        raise ValueError(f'volume_mirror_moments: need at least one candidate and finite matrices, got {m.shape[0]} candidates')
+    K = int(m.shape[0])
+    dev_m = torch.from_numpy(m).to(dev_raw.device)
+    sums = torch.empty(K, 6, device=dev_raw.device, dtype=torch.int64)
+    _launch('volume_mirror_moments', dev_raw.device, load().mud_volume_mirror_moments, ptr(dev_raw), int(code), X, Y, Z, float(slope), float(inter),
+            ptr(dev_m), K, int(stride), float(lo), float(scale), int(bins), ptr(sums), STREAM,
+            nbytes=float(dev_raw.numel() * dev_raw.element_size()) / max(int(stride), 1) ** 3 * 9.0 * K)
+    return sums

@@ -438,7 +438,8 @@ def _predict_volume(args, plan, evaluation=None):
     needed = _needed_inputs(args)
     raws = [VI.read_nifti_raw(path) for _, path in needed]
     prepared, ref, report = prepare_inputs([(m, raw) for (m, _), raw in zip(needed, raws)], options, device,
-                                           labels=dict(needed) if args.device_intake else None)      # (the device path names the file)
+                                           labels=dict(needed) if args.device_intake else None,      # (the device path names the file)
+                                           align=getattr(args, 'evaluation_record', ([], {}))[1].get('align'))      # (--gt_volume: estimated already)
     write = output_writer(write_nifti, raws[0], options, ref, device, getattr(args, 'reorient_back', False), getattr(args, 'conform_back', False))
     report.add_evaluation(*getattr(args, 'evaluation_record', ([], {})))      # the inputs first, then what predict_volume resampled
     args.intake_report = report
@@ -591,9 +592,30 @@ def _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref, evaluation=N
     return tuple(paths)
 
 
+class VolumeParser(argparse.ArgumentParser):
+    """The volume pipeline's parser: an ArgumentParser whose option list is the one tests/test_volume_cli_host.py pins, and `late`, a
+    second parser for the flags of the stages that came after that list was pinned (a stage's add_flags puts them there:
+    volume_align).  parse_args hands `late` what the main parser did not know, into the same namespace, and refuses what neither
+    knows; the help lists both."""
+
+    def __init__(self, prog):
+        super().__init__(prog)
+        self.late = argparse.ArgumentParser(prog, add_help=False, usage=argparse.SUPPRESS)
+
+    def parse_args(self, args=None, namespace=None):
+        namespace, rest = self.parse_known_args(args, namespace)
+        namespace, rest = self.late.parse_known_args(rest, namespace)
+        if rest:
+            self.error('unrecognized arguments: ' + ' '.join(rest))
+        return namespace
+
+    def format_help(self):
+        return super().format_help() + '\n' + self.late.format_help()
+
+
 def make_parser(prog='MU-Diff volume prediction (MI355X)'):
     """The volume pipeline's parser, unparsed (mudiff_hip.cohort adds its own flags to it; finish_args checks the result)."""
-    p = argparse.ArgumentParser(prog)
+    p = VolumeParser(prog)
     for m in ('t1ce', 't1', 't2', 'flair'):
         p.add_argument(f'--input_{m}', type=str, help=f'Path to {m.upper()} NIfTI')
     p.add_argument('--target_modality', type=str, required=True, choices=['T1CE', 'FLAIR', 'T2', 'T1'])
@@ -688,7 +710,7 @@ def build_argparser(argv=None):
     generators read and the reference parser forgot) and this build's own: the pipeline-wide ones make_parser adds after the
     reference's (their help texts say what they do and name their modules), --calibrate / --calibrate_threshold / --prec_plan
     (mudiff_hip.driver), and the flags of every input stage, each added and checked by the stage's own module (volume_prepare.STAGES;
-    DESIGN.md sections 5.12 - 5.21)."""
+    DESIGN.md sections 5.12 - 5.22; --align's flags sit in VolumeParser.late)."""
     p = make_parser()
     return finish_args(p, p.parse_args(argv))
 

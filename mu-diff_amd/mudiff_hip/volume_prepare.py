@@ -1,10 +1,10 @@
-"""The one input-preparation stage of the volume pipeline (DESIGN.md sections 5.10 - 5.21) and the subject-level plan around it: every
+"""The one input-preparation stage of the volume pipeline (DESIGN.md sections 5.10 - 5.22) and the subject-level plan around it: every
 entry point - volume.predict_volume on the host, with --device_intake, and mudiff_hip.cohort - reads a subject's files, hands them to
 prepare_inputs and normalises what comes back, on the host (volume.host_stacks) or on the device (volume_intake.condition_from_raw).
 
     STAGES                                                one line per stage: its module (add_flags, options_from, the suffixes, write_reports)
     IntakeOptions.from_args(args)                         what --norm, --slice_half_range and every stage's flags ask for, built once
-    prepare_inputs(named_raws, options, device)           reorient; denoise; foreground; first input = the grid; coregister; regrid, or check the shape; brain mask; bias-correct
+    prepare_inputs(named_raws, options, device)           reorient; denoise; foreground; first input = the grid [conformed, aligned]; coregister; regrid, or check the shape; brain mask; bias-correct
     IntakeReport                                          what that did, by modality name: the [done] line's tail and the report files
     read_for_evaluation, evaluation_inputs                --gt_volume / --eval_mask on the grid the prediction will have
     output_writer                                         --reorient_back / --conform_back around a writer
@@ -17,6 +17,7 @@ import collections
 
 import numpy as np
 
+from . import volume_align as VA
 from . import volume_bias as VB
 from . import volume_brain as VBR
 from . import volume_conform as VCF
@@ -42,15 +43,16 @@ STAGES = (
     Stage(VBR, (('brain_suffix', 'brain'),), 'brain affine header'),
     Stage(VO, (('reorient_suffix', 'reorient'),), 'reorient'),
     Stage(VCF, (('conform_suffix', 'conform conform_grid'), ('antialias_suffix', 'lowpass')), 'conform conform_grid'),
+    Stage(VA, (('align_suffix', 'align'),), 'align'),
 )
 
 
-class IntakeOptions(collections.namedtuple('IntakeOptions', 'norm regrid coreg bias half_range foreground brain interp reorient conform antialias denoise',
-                                           defaults=('percentile', False, None, None, 80, None, None, 'linear', None, None, False, None))):
+class IntakeOptions(collections.namedtuple('IntakeOptions', 'norm regrid coreg bias half_range foreground brain interp reorient conform antialias align denoise',
+                                           defaults=('percentile', False, None, None, 80, None, None, 'linear', None, None, False, None, None))):
     """norm: --norm; half_range: --slice_half_range (the slab is part of the reference geometry); every other field is what one stage's
     options_from made of that stage's flags (its docstring says what): regrid and interp (volume_regrid), coreg, bias, denoise,
-    foreground, brain, reorient, conform and antialias (volume_conform).  `foreground`, `brain`, `interp`, `reorient`, `conform` and
-    `antialias` sit before `denoise`, not at the end: tests/test_volume_denoise_host.py pins `denoise` as the last field, and every
+    foreground, brain, reorient, conform and antialias (volume_conform), align.  `foreground`, `brain`, `interp`, `reorient`, `conform`,
+    `antialias` and `align` sit before `denoise`, not at the end: tests/test_volume_denoise_host.py pins `denoise` as the last field, and every
     positional use stops at half_range."""
     __slots__ = ()
 
@@ -77,13 +79,14 @@ class IntakeReport:
     report, the uint8 [X,Y,Z] host mask or None)]: one entry per subject; `reorient` [(name, entry)] (volume_reorient.ReorientPlan.entry);
     `interp` (--regrid_interp) and `nonfinite`, the non-finite voxels a cubic resampling or the anti-aliasing low-pass read as 0; `conform`
     [(name, entry)] (volume_conform.entry) with `conform_grid`, the grid's name ('240x240x155@1mm'); `lowpass`: a low-pass actually ran
-    (--antialias)."""
+    (--antialias); `align` [(the first input's name, report)] (volume_align.estimate)."""
 
     def __init__(self, regridded=(), interp='linear', nonfinite=0, lowpass=False):
         self.regridded, self.coreg, self.bias, self.denoise, self.foreground, self.brain = list(regridded), [], [], [], [], []
         self.interp, self.nonfinite = interp, int(nonfinite)
         self.reorient = []
         self.conform, self.conform_grid, self.lowpass = [], None, bool(lowpass)
+        self.align = []
 
     def add_evaluation(self, resampled, found):
         """What evaluation_inputs did, after the inputs' own: the names it resampled, and its `found`."""
@@ -93,7 +96,7 @@ class IntakeReport:
 
     def suffix(self):
         """What a [done] line gains: ` | regrid=... | interp=cubic | coreg=... | bias=... | denoise=... | foreground=... | brain=... |
-        reorient=... | conform=... | antialias=on`, each part only when there is something to say (STAGES' order)."""
+        reorient=... | conform=... | antialias=on | align=...`, each part only when there is something to say (STAGES' order)."""
         return ''.join(getattr(stage.module, name)(*(getattr(self, k) for k in takes.split())) for stage in STAGES for name, takes in stage.parts)
 
     def write(self, output_dir, target, affine, header):
@@ -116,13 +119,15 @@ def read_for_evaluation(path, options):
     return VI.read_nifti_raw(path) if options.eval_as_stored else V.read_nifti(path)
 
 
-def evaluation_inputs(first, gt, label, options, device, names, wording):
+def evaluation_inputs(first, gt, label, options, device, names, wording, align=None):
     """The evaluation inputs on the grid the prediction will have, checked (volume_metrics.eval_inputs_on_grid: `names`, `wording`).
     first, gt, label (or None): read_for_evaluation's, or for `first` the RawVolume a caller has read anyway.  The grid is the first
     input's own; under --reorient that input's once reoriented (volume_reorient.reference_of: no voxel of it is moved), each evaluation
     input being reoriented by its own affine first; under --conform the conform grid of that (volume_conform.reference_of).  Under
     --regrid or --conform what is not on the grid is resampled onto it (--regrid_interp; the label volume by nearest neighbour), the
-    ground truth behind the low-pass of --antialias.  -> ((gt, label), the names of what was resampled, `found` of
+    ground truth behind the low-pass of --antialias.  Under --align the conform grid is the turned one, T @ its affine: `align` is
+    estimate_alignment's result when the caller has it; otherwise the plane is estimated here, from `first`, and left in found['align']
+    for the caller to hand to prepare_inputs, so that a subject's plane is estimated once.  -> ((gt, label), the names of what was resampled, `found` of
     volume_regrid.eval_onto_grid): IntakeReport.add_evaluation takes the last two."""
     from . import volume_metrics as VM
     geometry = lambda v: (v.shape, v.affine, v.header) if hasattr(v, 'header') else (v[0].shape, v[1], v[2])      # noqa: E731
@@ -136,6 +141,9 @@ def evaluation_inputs(first, gt, label, options, device, names, wording):
     if options.conform is not None:
         grid = VCF.reference_of(grid, options.conform)
     found = {}
+    if options.align is not None:
+        found['align'] = align = align or estimate_alignment(first, options, device)
+        grid = (grid[0], aligned_affine(align[0], grid[1]), None)
     evaluation, resampled = VM.eval_inputs_on_grid(grid, gt, label, gt_affine, resample, options.half_range, device, names=names, wording=wording,
                                                    interp=options.interp, found=found, **(dict(antialias=True) if options.antialias else {}))
     return evaluation, resampled, found
@@ -153,7 +161,60 @@ def output_writer(write, first_raw, options, ref, device, reorient_back=False, c
     return write
 
 
-def prepare_inputs(named_raws, options, device, labels=None):
+def _on_own_grid(named_raws, options, device, report, label):
+    """--reorient, --denoise and --foreground: every input on its own grid (prepare_inputs says what each does) -> the new list.
+    label: name -> what a warning line calls the input; None prints no warning line (the caller prints it: warn_first)."""
+    if options.reorient is not None:
+        turned = []
+        for name, raw in named_raws:
+            vol, found = VO.reorient(raw, device, **options.reorient)
+            report.reorient.append((name, found))
+            if label is not None:
+                VO.warn_oblique(label(name), found)
+            turned.append((name, vol))
+        named_raws = turned
+    if options.denoise is not None:
+        cleaned = []
+        for name, raw in named_raws:
+            vol, found = VD.denoise(raw, device, **options.denoise)
+            report.denoise.append((name, found))
+            cleaned.append((name, vol))
+        named_raws = cleaned
+    if options.foreground is not None:
+        masked = []
+        for name, raw in named_raws:
+            vol, found = VF.foreground(raw, device, **options.foreground)
+            report.foreground.append((name, found, vol if options.foreground['mask_out'] and vol is not raw else None))
+            masked.append((name, vol))
+        named_raws = masked
+    return named_raws
+
+
+class Alignment(collections.namedtuple('Alignment', 'T report first stages')):
+    """estimate_alignment's result: T and report (volume_align.estimate's), `first` - the first input as the plane was estimated from it,
+    after --reorient / --denoise / --foreground - and `stages`, the IntakeReport of those three stages for it, so that prepare_inputs
+    takes the first input from here and runs none of them on it again."""
+    __slots__ = ()
+
+
+def estimate_alignment(first_raw, options, device):
+    """--align for a caller that needs the plane before prepare_inputs runs (the evaluation inputs): the first input as read, taken through
+    --reorient / --denoise / --foreground as prepare_inputs takes it (no warning line: prepare_inputs prints it, with the input's name),
+    then volume_align.estimate -> an Alignment, for prepare_inputs' and evaluation_inputs' `align`."""
+    stages = IntakeReport()
+    (_, first), = _on_own_grid([(None, first_raw)], options, device, stages, None)
+    T, report = VA.estimate(first, device, **options.align)
+    return Alignment(T, report, first, stages)
+
+
+def aligned_affine(T, conform_affine):
+    """T @ the conform grid's affine: the grid's centre column on the plane found, its left-right axis along the plane's normal; the
+    affine itself, untouched, for T = I (the fallback)."""
+    T = np.asarray(T, np.float64)
+    return conform_affine if np.array_equal(T, np.eye(4)) else T @ np.asarray(conform_affine, np.float64)
+
+
+def prepare_inputs(named_raws, options, device, labels=None, align=None):
     """A subject's inputs on the first input's grid, corrected.  named_raws: [(modality name, RawVolume)] in MODALITY_ORDERS order (the
     caller has read the files); labels: {name: what an error message calls that input} (the name itself by default; the device paths
     name the file).  -> (volumes on the grid, ref = (shape, affine, header, s0, s1) of the first input, IntakeReport).
@@ -175,7 +236,10 @@ def prepare_inputs(named_raws, options, device, labels=None):
     `ref` holds that grid's shape, affine, volume_conform.conformed_header and slab.  The later inputs are still coregistered against the
     unresampled first input, and then every input, the first included, goes through one regrid_to onto the conform grid (one
     interpolation per input; an input that is on that grid already is left untouched); the brain mask and the bias correction follow on
-    the conform grid.  With options.antialias every such resampling (--regrid's and --coregister's too) low-passes what it downsamples.  Under --bias_correct every input, the first
+    the conform grid.  Under --align (options.align) the mid-sagittal plane of the first input, as it is at this
+    point, is estimated (volume_align.estimate; with `align`, estimate_alignment's result, the plane and the first input as it is at this
+    point are taken from there: neither the estimate nor the three stages above run on the first input twice) and the
+    conform grid's affine becomes T @ itself: still one regrid_to per input, now onto the turned grid.  With options.antialias every such resampling (--regrid's and --coregister's too) low-passes what it downsamples.  Under --bias_correct every input, the first
     included, is then divided by its bias field (volume_bias.correct).  ValueError for an input that is not 3D or a --brain_from that is
     not among the inputs, before any device work."""
     label = lambda name: (labels or {}).get(name, name)      # noqa: E731
@@ -186,33 +250,24 @@ def prepare_inputs(named_raws, options, device, labels=None):
     if brain is not None:
         source, mask_out = VBR.source_of([name for name, _ in named_raws], brain.pop('source', None)), brain.pop('mask_out', False)
     report = IntakeReport(interp=options.interp)
-    if options.reorient is not None:
-        turned = []
-        for name, raw in named_raws:
-            vol, found = VO.reorient(raw, device, **options.reorient)
-            report.reorient.append((name, found))
+    if isinstance(align, Alignment):                     # the first input has been through these stages: its entries and its warning line first
+        name = named_raws[0][0]
+        for stage in ('reorient', 'denoise', 'foreground'):
+            getattr(report, stage).extend((name,) + tuple(entry[1:]) for entry in getattr(align.stages, stage))
+        for _, found in report.reorient:
             VO.warn_oblique(label(name), found)
-            turned.append((name, vol))
-        named_raws = turned
-    if options.denoise is not None:
-        cleaned = []
-        for name, raw in named_raws:
-            vol, found = VD.denoise(raw, device, **options.denoise)
-            report.denoise.append((name, found))
-            cleaned.append((name, vol))
-        named_raws = cleaned
-    if options.foreground is not None:
-        masked = []
-        for name, raw in named_raws:
-            vol, found = VF.foreground(raw, device, **options.foreground)
-            report.foreground.append((name, found, vol if options.foreground['mask_out'] and vol is not raw else None))
-            masked.append((name, vol))
-        named_raws = masked
+        named_raws = [(name, align.first)] + _on_own_grid(named_raws[1:], options, device, report, label)
+    else:
+        named_raws = _on_own_grid(named_raws, options, device, report, label)
     first = named_raws[0][1]
     ref = (first.shape, first.affine, first.header) + slab_range(first.shape[2], options.half_range)
     ref_world = VR.world_affine_of(first.affine, first.header)
     if options.conform is not None:
         grid_shape, ref_world = VCF.conform_grid(first.shape, ref_world, **options.conform)
+        if options.align is not None:
+            T, found = align[:2] if align else VA.estimate(first, device, **options.align)
+            report.align.append((named_raws[0][0], found))
+            ref_world = aligned_affine(T, ref_world)
         ref = (grid_shape, ref_world, VCF.conformed_header(grid_shape, ref_world, first.header)) + slab_range(grid_shape[2], options.half_range)
         report.conform_grid = VCF.grid_name(grid_shape, options.conform['spacing'])
     def corrected(name, vol):
