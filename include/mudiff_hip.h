@@ -168,6 +168,13 @@ typedef struct mud_conv_args {
   /* mud_conv2d_mfma - arithmetic plan of this launch (MUD_PREC_*; 0 = the default) and, for MUD_PREC_FP8X, the power-of-two         */
   /* exponent the weights' e4m3 image was packed with (mud_pack_weights_prec: the largest e with max|w| * 2^e <= 448).               */
   int prec; int w_exp;
+  /* mud_conv2d_mfma, ks 3, pro_mode AFFINE_SILU, no sub2 / skip_w, even H and W, a grid that is not split over K - the residual */
+  /* up-sampled on load:                                                                                                        */
+  /* with res_up2 != 0 `res` is the LOW-resolution view [B, H/2, W/2, Cout] and the residual of output (2i+a, 2j+b) is its x2 FIR */
+  /* up-sampling by the separable 4x4 filter res_k (x) res_k (1-D taps, gain included; mud_fir_nhwc up = 2, pad (2, 1)):          */
+  /* a = 0 takes rows i-1 (tap 3) and i (tap 1), a = 1 rows i (tap 2) and i+1 (tap 0), columns alike, outside the image = 0.     */
+  /* Any other launch that sets it is refused (mud_conv2d_mfma_res_up2_supported tells beforehand); mud_conv2d_direct refuses it. */
+  int res_up2; float res_k[4];
 } mud_conv_args;
 
 /* Exact fp32 direct convolution (FMA chain per output), any ks/stride/pad/Cin/Cout.
@@ -198,6 +205,8 @@ int mud_conv2d_mfma(const mud_conv_args* a, void* stream);
 int mud_conv2d_mfma_prec_supported(const mud_conv_args* a, int prec);
 /* Bytes of split-K workspace mud_conv2d_mfma would use for this call (0: the launch is not split). */
 int64_t mud_conv2d_mfma_splitk_bytes(const mud_conv_args* a);
+/* 1 when mud_conv2d_mfma takes res_up2 for this launch (ks, sub2, skip_w, sizes and the split-K policy are looked at), else 0. */
+int mud_conv2d_mfma_res_up2_supported(const mud_conv_args* a);
 
 /* ---- e4m3 range census of a convolution input (the precision guard of MUD_PREC_FP8X: mudiff_hip.precision).
  * MUD_PREC_FP8X converts every prologued activation a (and its fp16 remainder a - fp16(a)) to e4m3 at CONSTANT power-of-two

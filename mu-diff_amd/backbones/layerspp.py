@@ -372,7 +372,10 @@ class ResnetBlockBigGANpp_Adagn(nn.Module, _Prepared):
         if self.up:
             kk, up, down, pad = up_or_down_sampling.fir_params('up' if self.fir else 'naive_up', self.fir_kernel)
             h_in, _ = ops.fir_nhwc(x, kk, up, down, pad, pro=(sc0, sh0, PRO_AFFINE_SILU), want_h=True, want_x=False)
-            x_skip, _ = ops.fir_nhwc(p['c2'](x), kk, up, down, pad)          # = Conv_2(FIR(x)) minus its bias (see _prepare)
+            x_skip = p['c2'](x)          # LOW resolution: Conv_2(FIR(x)) = FIR(Conv_2(x)) minus its bias (see _prepare)
+            taps = ops.up2_taps(kk, up, down, pad) if p['c1'].mfma and ops.res_up2_ok(x.B, h_in.H, h_in.W, self.out_ch, self.out_ch) else None
+            if taps is None:             # (else Conv_1 up-samples it while loading its residual: the full-resolution tensor is never written)
+                x_skip, _ = ops.fir_nhwc(x_skip, kk, up, down, pad)
             h = p['c0'](h_in, bias2=tbias, arena=arena)
         elif self.down:
             kk, up, down, pad = up_or_down_sampling.fir_params('down' if self.fir else 'naive_down', self.fir_kernel)
@@ -390,7 +393,8 @@ class ResnetBlockBigGANpp_Adagn(nn.Module, _Prepared):
         sc1, sh1 = (gn1, None) if isinstance(gn1, ops.LazyGN) else gn1
         if 'c2' in p and not self.up and not fused:
             x_skip = p['c2'](x_skip)
-        return p['c1'](h, pro=(sc1, sh1, PRO_AFFINE_SILU), res=x_skip, out_scale=INV_SQRT2 if self.skip_rescale else 1.0, out=out)
+        kw = dict(res_up2=taps) if self.up and taps is not None else {}
+        return p['c1'](h, pro=(sc1, sh1, PRO_AFFINE_SILU), res=x_skip, out_scale=INV_SQRT2 if self.skip_rescale else 1.0, out=out, **kw)
 
     def forward(self, x, temb=None, zemb=None):
         st0 = ops.dense(zemb, self.GroupNorm_0.style.weight.detach(), self.GroupNorm_0.style.bias.detach())

@@ -460,7 +460,67 @@ __global__ __launch_bounds__(64 * WM * WN, (MT == 1 && WM * WN == 8) ? 4 : 2) vo
   // wave), behind the first staging loads: the sums come out as res + sum(products), no registers are held and nothing is
   // left for the epilogue.  (Not with sub2 / split-K slabs / the fused skip conv, which has no residual.)
   const bool res_in_acc = !DUAL && KS == 3 && a.res != nullptr && !a.sub2 && nsplit == 1;
-  if (res_in_acc) {
+  // res_up2: `res` is the low-resolution tensor and every accumulator register starts as its x2 FIR up-sampling instead (the
+  // polyphase sums of k_fir_up2_quad, fir.hip, term for term in its order: rows, then columns).  A register quad is 4 output
+  // pixels in a row = 2 low-resolution rows x 4 columns: 8 masked loads per 4 elements, then 4 multiply-adds each.
+  // Built into the AdaGN + SiLU instantiations only (the residual blocks' Conv_1): the other prologues keep their registers.
+  constexpr bool UP2 = KS == 3 && !DUAL && PRO == MUD_PRO_AFFINE_SILU;
+  bool res_up2 = false;
+  if constexpr (UP2) res_up2 = res_in_acc && a.res_up2 != 0;                   // workgroup-uniform
+  if (res_up2) {
+    if constexpr (UP2) {
+      // No lane mask stays live across a load (64 loads x an SGPR pair each would not fit): addresses are clamped into the image,
+      // rows outside it (and channels past Cout) get a zero row weight, columns outside it are cleared after the load from one
+      // bit mask per lane (opaque to the compiler, or it would fold the bit tests back into the 64 compares).
+      const int Hl = a.H >> 1, Wl = a.W >> 1;
+      const float* rb = a.res + (int64_t)b * Hl * Wl * a.ldr;
+      const int jq = ((tx0 + 4 * hh) >> 1) - 1;                        // first low-resolution column of register quad 0 (quad g4: + 4 g4)
+      unsigned cmask = 0;                                               // bit 4 g4 + cx: column jq + 4 g4 + cx lies inside the image
+#pragma unroll
+      for (int i = 0; i < 16; ++i) cmask |= (jq + i >= 0 && jq + i < Wl ? 1u : 0u) << i;
+      const int co0 = (nt * WN + wn) * CM_BN + r;                      // this lane's channel of accumulator half n: co0 + 32 n
+      const float* rc = rb + (co0 < a.Cout ? co0 : 0);
+      const int dn = co0 + 32 < a.Cout ? 32 : 0;
+      unsigned cm[2] = {co0 < a.Cout ? cmask : 0u, co0 + 32 < a.Cout ? cmask : 0u};
+      asm volatile("" : "+v"(cm[0]), "+v"(cm[1]));
+#pragma unroll
+      for (int m = 0; m < MT; ++m) {
+        const int gy = ty0 + __builtin_amdgcn_readfirstlane(wm) * MT + m;      // wave-uniform: the row weights and offsets stay scalar
+        const int ay = gy & 1, y0 = (gy >> 1) - 1 + ay;                // rows (i-1, i) for a = 0, (i, i+1) for a = 1
+        const float ky[2] = {(y0 >= 0 && y0 < Hl) ? (ay ? a.res_k[2] : a.res_k[3]) : 0.f, (y0 + 1 < Hl) ? (ay ? a.res_k[0] : a.res_k[1]) : 0.f};
+        const int yo[2] = {min(max(y0, 0), Hl - 1) * Wl, min(y0 + 1, Hl - 1) * Wl};
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) {
+          float v[2][2][4];                                            // [n][row][column]; the two channel halves share their offsets
+#pragma unroll
+          for (int ry = 0; ry < 2; ++ry)
+#pragma unroll
+            for (int cx = 0; cx < 4; ++cx) {
+              const float* pp = rc + (yo[ry] + min(max(jq + 4 * g4 + cx, 0), Wl - 1)) * a.ldr;      // (int: the host checks the image size)
+              v[0][ry][cx] = pp[0];
+              v[1][ry][cx] = pp[dn];
+            }
+#pragma unroll
+          for (int n = 0; n < 2; ++n) {
+#pragma unroll
+            for (int ry = 0; ry < 2; ++ry)
+#pragma unroll
+              for (int cx = 0; cx < 4; ++cx) v[n][ry][cx] = (cm[n] & (1u << (4 * g4 + cx))) ? v[n][ry][cx] : 0.f;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {                                // outputs 2j, 2j+1, 2j+2, 2j+3 read columns (j-1, j), (j, j+1), (j, j+1), (j+1, j+2)
+              const int ca = (e + 1) >> 1;
+              const float kx0 = (e & 1) ? a.res_k[2] : a.res_k[3], kx1 = (e & 1) ? a.res_k[0] : a.res_k[1];
+              float t = (ky[0] * kx0) * v[n][0][ca];                     // k_fir_up2_quad's chain, term for term (the 2-D weights are scalar products)
+              t = __builtin_fmaf(ky[0] * kx1, v[n][0][ca + 1], t);
+              t = __builtin_fmaf(ky[1] * kx0, v[n][1][ca], t);
+              t = __builtin_fmaf(ky[1] * kx1, v[n][1][ca + 1], t);
+              acc[m][n][g4 * 4 + e] = t;
+            }
+          }
+        }
+      }
+    }
+  } else if (res_in_acc) {
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
       const int co = (nt * WN + wn) * CM_BN + n * 32 + r;
@@ -1422,6 +1482,7 @@ static int cm_launch_pro(const mud_conv_args& a, hipStream_t s) {
     // (the fused skip conv has two accumulator sets: only the in-launch reduction handles it)
     if ((!DUAL || in_launch) && a.splitk_ws && mud_aligned16(a.splitk_ws) && cm_split_eligible(a)) ns = cm_splits(nblocks, k16s);
     if (ns > 1 && a.splitk_ws_bytes < cm_slab_bytes(ns, nblocks, 64 * WM * WN * 32 * MT * (DUAL ? 2 : 1))) ns = 1;      // workspace too small: run unsplit
+    MUD_REQUIRE(ns == 1 || !a.res_up2, "mud_conv2d_mfma: res_up2 is not built for a launch split over K (ask mud_conv2d_mfma_res_up2_supported first)");
     if (ns > 1) {
       mud_conv_args p = a;                       // raw partial sums: no epilogue terms, output = slab ksi of the workspace
       p.out = (float*)a.splitk_ws;
@@ -1519,6 +1580,16 @@ extern "C" int64_t mud_conv2d_mfma_splitk_bytes(const mud_conv_args* ap) {
   return ns > 1 ? cm_slab_bytes(ns, blocks, tile_words) : 0;
 }
 
+// res_up2 lives where the residual is loaded into the accumulators (the 3x3 kernel, no sub2, no fused skip conv, no split-K), in the
+// instantiations of the AdaGN + SiLU prologue: the residual blocks' Conv_1
+extern "C" int mud_conv2d_mfma_res_up2_supported(const mud_conv_args* ap) {
+  if (!ap || ap->ks != 3 || ap->stride != 1 || ap->pad != 1 || ap->sub2 || ap->skip_w || ap->pro_mode != MUD_PRO_AFFINE_SILU) return 0;
+  if (ap->B <= 0 || ap->H <= 0 || ap->W <= 0 || ap->Cin <= 0 || ap->Cout <= 0 || (ap->H & 1) || (ap->W & 1)) return 0;
+  int64_t blocks = 0;
+  cm_variant3(*ap, &blocks);
+  return cm_splits(blocks, (int)mud_cdiv(ap->Cin, 16)) == 1;      // (whatever workspace the caller has: a launch that may split is left alone)
+}
+
 // MUD_PREC_FP8X is built for the 8-wave tiles (8 x 32 px x 128 ch, 16 x 32 px x 64 ch, and the one-row 8 x 32 px x 64 ch tile of the
 // 64 -> 64 layers), i.e. for launches that fill the chip, with the prologues the generators use there (none: G2's gate / fusion
 // convolutions; AdaGN + SiLU: the residual blocks, with or without the fused skip conv - whose own centre-tap products stay 16-bit x 3).
@@ -1577,6 +1648,12 @@ extern "C" int mud_conv2d_mfma(const mud_conv_args* ap, void* stream) {
     MUD_REQUIRE(a.skip_out && a.Cin <= 512 && a.Cout % 4 == 0 && a.skip_ldo >= a.Cout && a.skip_ldo % 4 == 0 && a.ldo % 4 == 0 &&
                 mud_aligned16(a.skip_w) && mud_aligned16(a.skip_out) && mud_aligned16(a.out),
                 "mud_conv2d_mfma: fused skip conv needs Cin <= 512, Cout %% 4 == 0 and aligned float4 output rows (Cin=%d Cout=%d)", a.Cin, a.Cout);
+  }
+  if (a.res_up2) {
+    MUD_REQUIRE(a.ks == 3 && a.res && !a.sub2 && !a.skip_w && (a.H & 1) == 0 && (a.W & 1) == 0 && a.pro_mode == MUD_PRO_AFFINE_SILU,
+                "mud_conv2d_mfma: res_up2 needs ks == 3, the AFFINE_SILU prologue, a residual, no sub2 / fused skip conv and even H, W (ks=%d H=%d W=%d sub2=%d pro_mode=%d)",
+                a.ks, a.H, a.W, a.sub2, a.pro_mode);
+    MUD_REQUIRE((int64_t)(a.H / 2) * (a.W / 2) * a.ldr < 0x7fffffffLL, "mud_conv2d_mfma: res_up2: one low-resolution image must stay below 2^31 elements");
   }
   MUD_REQUIRE(a.prec == MUD_PREC_16X3 || a.prec == MUD_PREC_FP8X || a.prec == MUD_PREC_16X1, "mud_conv2d_mfma: unknown arithmetic plan prec=%d", a.prec);
   MUD_REQUIRE(a.prec != MUD_PREC_16X1 || a.ks == 3, "mud_conv2d_mfma: MUD_PREC_16X1 is built for ks == 3 only (got ks=%d)", a.ks);

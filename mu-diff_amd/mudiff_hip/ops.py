@@ -394,6 +394,29 @@ def fused_skip_ok(x: View, cout, pro_mode):
             and (FUSE_SKIP_SPLIT or not conv3x3_would_split_k(x, cout)))
 
 
+RES_UP2 = os.environ.get('MUD_RES_UP2', '1') != '0'     # A/B knob: 0 = the up blocks' skip path is up-sampled by a FIR launch of its own
+
+
+def up2_taps(kernel2d, up, down, pad):
+    """The four 1-D taps t (gain included) of an x2 up-sampling FIR whose 4x4 kernel is exactly t (x) t with pad (2, 1) - the form
+    mud_conv_args.res_up2 takes - or None for any other filter."""
+    k = np.asarray(kernel2d, dtype=np.float32)
+    if k.shape != (4, 4) or (up, down, tuple(pad)) != (2, 1, (2, 1)) or not float(k.sum()) > 0.0:
+        return None
+    t = (k.sum(axis=1) / np.sqrt(k.sum())).astype(np.float32)
+    return tuple(float(v) for v in t) if np.array_equal(np.outer(t, t).astype(np.float32), k) else None
+
+
+def res_up2_ok(B, H, W, cin, cout):
+    """Does a 3x3 mud_conv2d_mfma launch of these sizes ([B,H,W,cin] -> cout) take its residual up-sampled on load
+    (mud_conv2d_mfma_res_up2_supported: the AdaGN + SiLU prologue, even H and W, a grid that is not split over K)?"""
+    if not RES_UP2 or cin % 4 or cout % 4:
+        return False
+    a = ConvArgs()
+    a.B, a.H, a.W, a.Cin, a.ldx, a.ks, a.stride, a.pad, a.Cout, a.ldo, a.pro_mode = B, H, W, cin, cin, 3, 1, 1, cout, cout, PRO_AFFINE_SILU
+    return bool(load().mud_conv2d_mfma_res_up2_supported(C.byref(a)))
+
+
 def resolve_pro(pro):
     """(scale, shift, mode) with the arrays materialised (for consumers that cannot fold the GroupNorm finalisation)."""
     if pro is not None and isinstance(pro[0], LazyGN):
@@ -521,11 +544,14 @@ RECORD = None         # the active precision.launch_record() list, or None: ever
 
 def conv(x: View, w, ks, Cout, *, mfma, stride=1, pad=None, pro=None, bias=None, bias2=None, res: View = None,
          out_scale=1.0, act=ACT_NONE, out: View = None, w_bstride=0, arena=None, sub2=False, emul: View = None, gate=None, emul_cout=0,
-         skip=None, prec=PREC_16X3, w_exp=0, layer=None):
+         skip=None, prec=PREC_16X3, w_exp=0, layer=None, res_up2=None, split_k=True):
     """One fused convolution launch.  pro = (scale [B,Cin], shift [B,Cin], mode).
     skip = (packed 1x1 weights, bias or None, out View): the same launch also writes the 1x1 convolution of the RAW input
     (the residual block's Conv_2) - see fused_skip_ok().  prec / w_exp: the arithmetic plan `w` was packed for.
-    layer: the launch's layer name in a launch record (precision.launch_record)."""
+    layer: the launch's layer name in a launch record (precision.launch_record).
+    res_up2 = the four 1-D taps of a separable 4x4 x2 up-sampling filter (up2_taps): `res` is then the LOW-resolution view
+    [B,Ho/2,Wo/2,Cout] and the launch up-samples it while loading it (mud_conv_args.res_up2; see res_up2_ok).
+    split_k=False: hand the launch no split-K workspace, so a small grid runs unsplit (a res_up2 launch never gets one)."""
     if RECORD is not None:
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError('precision.launch_record() is eager only: the launch is being captured into a graph')
@@ -569,7 +595,11 @@ def conv(x: View, w, ks, Cout, *, mfma, stride=1, pad=None, pro=None, bias=None,
         assert bias2.shape == (x.B, Cout) and bias2.stride(1) == 1
         a.bias2, a.bias2_ld = ptr(bias2), bias2.stride(0)
     if res is not None:
-        assert (res.B, res.H, res.W, res.C) == (x.B, Ho, Wo, Cout)
+        if res_up2 is not None:
+            assert mfma and Ho % 2 == 0 and Wo % 2 == 0 and (res.B, res.H, res.W, res.C) == (x.B, Ho // 2, Wo // 2, Cout) and len(res_up2) == 4
+            a.res_up2, a.res_k = 1, (C.c_float * 4)(*res_up2)
+        else:
+            assert (res.B, res.H, res.W, res.C) == (x.B, Ho, Wo, Cout)
         a.res, a.ldr = res.ptr, res.ld
     a.out_scale, a.act = out_scale, act
     a.sub2 = 1 if sub2 else 0
@@ -590,7 +620,8 @@ def conv(x: View, w, ks, Cout, *, mfma, stride=1, pad=None, pro=None, bias=None,
         assert mfma and ks == 3 and res is None and (so.B, so.H, so.W, so.C) == (x.B, Ho, Wo, Cout)
         a.skip_w, a.skip_bias, a.skip_out, a.skip_ldo = ptr(sw), ptr(sb), so.ptr, so.ld
         skip_flops = 2.0 * x.B * Ho * Wo * Cout * x.C
-    if mfma and ks == 3:          # small grids (one slice at a time): split-K slabs, stream-ordered scratch (graph-capture safe)
+    if mfma and ks == 3 and split_k and res_up2 is None:      # small grids (one slice at a time): split-K slabs, stream-ordered scratch (graph-capture safe);
+                                                   # a launch that up-samples its residual is never split (no workspace: it runs unsplit)
         cnt = splitk_counters(x.device)
         a.splitk_counters, a.splitk_ncounters = ptr(cnt), cnt.numel()
         nws = lib.mud_conv2d_mfma_splitk_bytes(C.byref(a))
