@@ -350,6 +350,43 @@ int mud_randn_keyed(float* out, int rows, int64_t row_len, const int64_t* keys, 
 int mud_ensemble_stats(const float* samples, int n, int N, int64_t hw, float scale, float shift, float lo, float hi, float* mean,
                        float* std, void* stream);
 
+/* ---- slice-coupled sampling noise (mudiff_hip.slice_coupling; the volume pipeline's --slice_coupling).
+ * mud_randn_keyed_coupled: the keyed draws of neighbouring slices filtered along z.  With eta(s)[e] the fp32 value mud_randn_keyed gives
+ * element e of a row keyed (slice s, sample m) under the same seed, step and kind,
+ *   out[r*row_len + e] = (float) sum_{j=-R..R} w_|j| * eta(s_r + j)[e],
+ * the products and the sum in fp64 in tap order j = -R..R, each rounded once (no contraction).  s_r + j wraps modulo 2^64 as the Philox
+ * counter word, so the noise is stationary at a volume's first slices; the keys themselves obey mud_randn_keyed's rules.
+ * half_taps: HOST array of radius + 1 finite fp64 weights w_0..w_R, read at call time and passed as a kernel argument (no device
+ * allocation); radius in [0, MUD_COUPLING_MAX_RADIUS].  With sum_j w_|j|^2 = 1 (the caller's business: mudiff_hip.slice_coupling.
+ * coupling_taps) every element stays N(0, 1) and rows d slices apart correlate by sum_j w_|j| w_|j+d|.  radius 0 with w_0 = 1 gives
+ * mud_randn_keyed's bits. */
+#define MUD_COUPLING_MAX_RADIUS 32
+int mud_randn_keyed_coupled(float* out, int rows, int64_t row_len, const int64_t* keys, uint64_t seed, int step, int kind,
+                            const double* half_taps, int radius, void* stream);
+
+/* ---- through-plane roughness of a volume (mudiff_hip.volume_through_plane; the volume pipeline's --through_plane).
+ * vol (fp32) and the optional mask (uint8, may be NULL: every voxel is inside; else non-zero is inside) are [Z, X, Y] with planes
+ * contiguous, X*Y*Z < 2^31.  For the planes z0 <= z <= z1 (0 <= z0 <= z1 < Z; planes outside are never read),
+ * sums[(z - z0) * MUD_TP_NQ + q] are the counts and fp64 sums, over the voxels v of plane z that are inside, of
+ *   MUD_TP_N_DZ / _S_DZ    |V[z+1] - V[z]|               where z < z1 and the voxel above is inside
+ *   MUD_TP_N_DZZ / _S_DZZ  |(V[z+1] - 2 V[z]) + V[z-1]|  where z0 < z < z1 and the voxels above and below are inside
+ *   MUD_TP_N_DX / _S_DX    |V[x+1] - V[x]|               where x + 1 < X and that neighbour is inside
+ *   MUD_TP_N_DY / _S_DY    |V[y+1] - V[y]|               where y + 1 < Y and that neighbour is inside
+ * with every difference taken in fp64 from the fp32 values.  Partials per (plane, workgroup) are added in a fixed order, no atomics:
+ * bit-identical run to run.  ws: (z1 - z0 + 1) * MUD_TP_PARTS * MUD_TP_NQ * 8 bytes, 8-byte aligned. */
+#define MUD_TP_NQ 8
+#define MUD_TP_PARTS 16
+#define MUD_TP_N_DZ 0
+#define MUD_TP_S_DZ 1
+#define MUD_TP_N_DZZ 2
+#define MUD_TP_S_DZZ 3
+#define MUD_TP_N_DX 4
+#define MUD_TP_S_DX 5
+#define MUD_TP_N_DY 6
+#define MUD_TP_S_DY 7
+int mud_volume_through_plane(const float* vol, const uint8_t* mask, int Z, int X, int Y, int z0, int z1, double* sums, void* ws,
+                             int64_t ws_bytes, void* stream);
+
 /* ---- on-device NIfTI intake and re-assembly of the volume pipeline (mudiff_hip.volume_intake; --device_intake, mudiff_hip.cohort).
  * A volume is passed exactly as the file stores it: X x Y x Z voxels, x fastest ([Z][Y][X] in C terms), 16-byte aligned, X*Y*Z < 2^31,
  * in the NIfTI datatype MUD_NIFTI_* (little-endian), with the header's scl_slope / scl_inter.  A voxel's value is

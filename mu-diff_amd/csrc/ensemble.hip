@@ -89,6 +89,75 @@ extern "C" int mud_randn_keyed(float* out, int rows, int64_t row_len, const int6
   return MUD_OK;
 }
 
+// ---- slice-coupled keyed draws (mudiff_hip.slice_coupling) --------------------------------------------------
+// out[r, e] = fp32(sum_{j=-R..R} w_|j| * eta(seed, s + j, m, step, kind)[e]) with eta the fp32 value of k_randn_keyed for that key: the
+// white noise of the slices around s, filtered along z.  With sum w^2 = 1 every row stays N(0, 1) per element, and two rows d slices apart
+// correlate by sum_j w_j w_{j+d}.  s + j wraps modulo 2^64 (the Philox counter word), so the first slices of a volume see the same
+// statistics as the others.  The half taps travel as a kernel argument: nothing is allocated and nothing read from the device but the keys.
+#define ES_MAX_RADIUS MUD_COUPLING_MAX_RADIUS
+struct es_taps {
+  double w[ES_MAX_RADIUS + 1];
+};
+
+// the thread mapping and the two store paths of k_randn_keyed; per tap one Philox block and its two Box-Muller pairs, the products and
+// the sums in fp64 in tap order j = -R..R, each rounded once (no contraction), the result rounded to fp32 once
+__global__ __launch_bounds__(ES_THREADS) void k_randn_keyed_coupled(float* __restrict__ out, int rows, int64_t row_len, int64_t blocks_per_row,
+                                                                    const int64_t* __restrict__ keys, uint64_t seed, uint64_t word2, int vec,
+                                                                    es_taps taps, int radius) {
+#pragma clang fp contract(off)
+  const int64_t t = (int64_t)blockIdx.x * ES_THREADS + threadIdx.x;
+  if (t >= (int64_t)rows * blocks_per_row) return;
+  const int64_t r = t / blocks_per_row, b = t - r * blocks_per_row;
+  const uint64_t slice = (uint64_t)keys[2 * r], sample = (uint64_t)keys[2 * r + 1];
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int j = -radius; j <= radius; ++j) {                // uniform over the launch
+    const double w = taps.w[j < 0 ? -j : j];
+    uint64_t c0 = (uint64_t)b, c1 = slice + (uint64_t)(int64_t)j, c2 = (sample << 32) | word2, c3 = 0;
+    es_philox(c0, c1, c2, c3, seed, ES_KEY_HI);
+    float e0, e1, e2, e3;
+    es_box_muller(c0, c1, e0, e1);
+    es_box_muller(c2, c3, e2, e3);
+    acc[0] = acc[0] + w * (double)e0;
+    acc[1] = acc[1] + w * (double)e1;
+    acc[2] = acc[2] + w * (double)e2;
+    acc[3] = acc[3] + w * (double)e3;
+  }
+  f32x4 v;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] = (float)acc[e];
+  float* dst = out + r * row_len + 4 * b;
+  if (vec) {
+    *reinterpret_cast<f32x4*>(dst) = v;
+  } else {
+    const int64_t n = row_len - 4 * b < 4 ? row_len - 4 * b : 4;
+    for (int e = 0; e < n; ++e) dst[e] = v[e];
+  }
+}
+
+extern "C" int mud_randn_keyed_coupled(float* out, int rows, int64_t row_len, const int64_t* keys, uint64_t seed, int step, int kind,
+                                       const double* half_taps, int radius, void* stream) {
+  MUD_REQUIRE(rows >= 0 && row_len > 0, "mud_randn_keyed_coupled: bad sizes (rows %d, row_len %lld)", rows, (long long)row_len);
+  MUD_REQUIRE(kind >= 0 && kind <= 2, "mud_randn_keyed_coupled: kind must be 0 (x_init), 1 (z) or 2 (posterior noise), got %d", kind);
+  MUD_REQUIRE(step >= 0 && step < (1 << 24), "mud_randn_keyed_coupled: step must be in [0, 2^24), got %d", step);
+  MUD_REQUIRE(radius >= 0 && radius <= ES_MAX_RADIUS, "mud_randn_keyed_coupled: radius must be in [0, %d], got %d", ES_MAX_RADIUS, radius);
+  MUD_REQUIRE(out && keys && half_taps, "mud_randn_keyed_coupled: null pointer");
+  es_taps taps;
+  for (int j = 0; j <= ES_MAX_RADIUS; ++j) {
+    taps.w[j] = j <= radius ? half_taps[j] : 0.0;
+    MUD_REQUIRE(taps.w[j] - taps.w[j] == 0.0, "mud_randn_keyed_coupled: tap %d is not finite", j);
+  }
+  if (rows == 0) return MUD_OK;
+  const int64_t bpr = mud_cdiv(row_len, 4);
+  const int64_t threads = (int64_t)rows * bpr;
+  MUD_REQUIRE(mud_cdiv(threads, ES_THREADS) <= 0x7fffffff, "mud_randn_keyed_coupled: too many elements");
+  const int vec = (row_len % 4 == 0) && mud_aligned16(out);
+  const uint64_t word2 = ((uint64_t)step << 8) | (uint64_t)kind;
+  hipLaunchKernelGGL(k_randn_keyed_coupled, dim3((unsigned)mud_cdiv(threads, ES_THREADS)), dim3(ES_THREADS), 0, (hipStream_t)stream, out, rows,
+                     row_len, bpr, keys, seed, word2, vec, taps, radius);
+  MUD_CHECK_LAUNCH("mud_randn_keyed_coupled");
+  return MUD_OK;
+}
+
 // ---- per-pixel ensemble statistics --------------------------------------------------------------------------------------------------
 // y = clamp(x*scale + shift, lo, hi) with the fp32 steps of mud_affine_clamp, each rounded once (no contraction); unlike fminf / fmaxf
 // alone, a NaN stays NaN (np.clip semantics) so that it reaches both outputs

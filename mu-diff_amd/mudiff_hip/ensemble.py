@@ -32,14 +32,16 @@ def premap(map_0_1):
 
 
 def sample_ensemble(args, gen1, gen2, conds, num_samples, seed, batch_size=32, slice_offset=0, chunk=None, sampler=None, map_0_1=False,
-                    return_samples=False):
+                    return_samples=False, coupling=None):
     """conds: three device tensors [n,1,S,S] (S = args.image_size) -> (mean, std) device fp32 [n,S,S] over `num_samples` (>= 2) samples
     per slice, plus the raw samples [n,N,S,S] with `return_samples`.  `map_0_1`: the statistics are those of the samples mapped to
     [0,1] (ops.to_range_0_1); the returned samples are never mapped.
 
     Items (slice i, sample j) run slice-major in batches of the sampler's B (`sampler`, a sampling.GraphSampler for these generators
     and this image size, else one is captured at `batch_size`); the last batch of a chunk is padded by repeating its last item.  At most
-    `chunk` slices' samples are held at a time (default: a buffer of at most 1 GiB).  Slice i is keyed as slice_offset + i."""
+    `chunk` slices' samples are held at a time (default: a buffer of at most 1 GiB).  Slice i is keyed as slice_offset + i.
+    `coupling`: GraphSampler.sample_keyed's (mudiff_hip.slice_coupling): sample j of neighbouring slices then shares part of its draws;
+    the keys stay global, so shards and chunks still draw what a single run would."""
     from . import sampling as S
     N = int(num_samples)
     if N < 2:
@@ -82,7 +84,7 @@ def sample_ensemble(args, gen1, gen2, conds, num_samples, seed, batch_size=32, s
             sl = items // N
             keys = torch.stack([sl + int(slice_offset), items % N], 1)
             idx = sl.to(device)
-            res = sampler.sample_keyed(c1.index_select(0, idx), c2.index_select(0, idx), c3.index_select(0, idx), keys, seed, T)
+            res = sampler.sample_keyed(c1.index_select(0, idx), c2.index_select(0, idx), c3.index_select(0, idx), keys, seed, T, coupling=coupling)
             flat[b0 - q0:b0 - q0 + m] = res[:m, 0]
         mean[s0:s1], std[s0:s1] = ops.ensemble_stats(out, scale, shift, lo, hi)
     return (mean, std, every) if return_samples else (mean, std)

@@ -957,6 +957,76 @@ def randn_keyed(rows_keys, row_len, seed, step, kind, out=None):
     return out
 
 
+COUPLING_MAX_RADIUS = 32      # include/mudiff_hip.h: MUD_COUPLING_MAX_RADIUS
+
+
+def coupling_taps_arg(half_taps, radius):
+    """(half_taps, R) -> (the ctypes fp64 array mud_randn_keyed_coupled reads on the host at call time, R), checked."""
+    from .slice_coupling import check_coupling
+    try:
+        half, R = check_coupling((half_taps, radius))
+    except ValueError as e:
+        raise MudiffHipError(f'randn_keyed_coupled: {e}') from None
+    return (C.c_double * (R + 1))(*half.tolist()), R
+
+
+def randn_keyed_coupled_into(out, keys_dev, seed, step, kind, taps, radius):
+    """Unchecked launch of ops.randn_keyed_coupled into `out`, as randn_keyed_into; (taps, radius) from coupling_taps_arg."""
+    rows = keys_dev.shape[0]
+    _launch('randn_keyed_coupled', out.device, load().mud_randn_keyed_coupled, ptr(out), rows, out.numel() // max(rows, 1), ptr(keys_dev),
+            C.c_uint64(seed), int(step), int(kind), taps, int(radius), STREAM)
+    return out
+
+
+def randn_keyed_coupled(rows_keys, row_len, seed, step, kind, half_taps, radius, out=None):
+    """Slice-coupled keyed normals (mud_randn_keyed_coupled; mudiff_hip.slice_coupling): row r with key (slice s, sample m) is
+    fp32(sum_{j=-R..R} half_taps[|j|] * eta(s + j)) with eta(.) the row ops.randn_keyed gives (slice, m) under the same seed, step and
+    kind, summed in fp64 in tap order; s + j wraps modulo 2^64.  Everything else as ops.randn_keyed."""
+    k = check_keys(rows_keys)
+    seed = _seed64(seed)
+    taps, R = coupling_taps_arg(half_taps, radius)
+    rows, row_len = k.shape[0], int(row_len)
+    if out is None:
+        dev = rows_keys.device if isinstance(rows_keys, torch.Tensor) and rows_keys.is_cuda else torch.device('cuda', torch.cuda.current_device())
+        out = torch.empty(rows, row_len, device=dev, dtype=torch.float32)
+    require_gpu(out)
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != rows * row_len:
+        raise MudiffHipError(f'randn_keyed_coupled: out must be a contiguous fp32 tensor of {rows} x {row_len} elements, got {out.dtype} '
+                             f'{tuple(out.shape)}')
+    _launch('randn_keyed_coupled', out.device, load().mud_randn_keyed_coupled, ptr(out), rows, row_len, ptr(k.to(out.device)), C.c_uint64(seed),
+            int(step), int(kind), taps, R, STREAM)
+    return out
+
+
+# columns of volume_through_plane's sums (include/mudiff_hip.h: MUD_TP_*)
+TP_N_DZ, TP_S_DZ, TP_N_DZZ, TP_S_DZZ, TP_N_DX, TP_S_DX, TP_N_DY, TP_S_DY = range(8)
+TP_NQ, TP_PARTS = 8, 16
+
+
+def volume_through_plane(vol, mask=None, z0=0, z1=None):
+    """Per-plane counts and fp64 sums of the absolute differences of a [Z, X, Y] fp32 volume (planes contiguous) along z, x and y and of
+    its second difference along z, over the voxels inside the uint8 `mask` (non-zero; None: every voxel), for the planes z0..z1 clipped to
+    the volume (z1 None: the last plane); planes outside that range are never read -> (device fp64 [planes, TP_NQ], first plane, last
+    plane).  mud_volume_through_plane defines the columns.  Bit-identical run to run.  No synchronisation."""
+    require_gpu(vol, mask)
+    if vol.dtype != torch.float32 or vol.dim() != 3 or (mask is not None and (mask.dtype != torch.uint8 or mask.shape != vol.shape)):
+        raise MudiffHipError(f'volume_through_plane: need an fp32 [Z, X, Y] volume and a uint8 mask of its shape (got {vol.dtype} '
+                             f'{tuple(vol.shape)}' + ('' if mask is None else f', {mask.dtype} {tuple(mask.shape)}') + ')')
+    Z, X, Y = vol.shape
+    if min(Z, X, Y) < 1:
+        raise MudiffHipError(f'volume_through_plane: empty volume {tuple(vol.shape)}')
+    z0, z1 = max(0, int(z0)), Z - 1 if z1 is None else min(Z - 1, int(z1))
+    if z0 > z1:
+        raise MudiffHipError(f'volume_through_plane: no plane of the {Z} lies in {z0}..{z1}')
+    vin, min_ = vol.contiguous(), None if mask is None else mask.contiguous()
+    planes = z1 - z0 + 1
+    sums = torch.empty(planes, TP_NQ, device=vol.device, dtype=torch.float64)
+    ws = torch.empty(planes * TP_PARTS * TP_NQ, device=vol.device, dtype=torch.float64)
+    _launch('volume_through_plane', vol.device, load().mud_volume_through_plane, ptr(vin), ptr(min_), Z, X, Y, z0, z1, ptr(sums), ptr(ws),
+            ws.numel() * 8, STREAM, nbytes=float(planes) * X * Y * (5 if mask is None else 6))
+    return sums, z0, z1
+
+
 def ensemble_stats(samples, scale=1.0, shift=0.0, lo=-math.inf, hi=math.inf):
     """Per-pixel mean and standard deviation (N - 1) over the samples of each slice: samples [n, N, ...] (N >= 2, fp32) -> (mean, std),
     fp32 [n, ...], of y = clamp(samples*scale + shift, lo, hi); fp64 sums in sample order, so a fixed function of the samples

@@ -246,21 +246,34 @@ class GraphSampler:
         out = self.x.clone()
         return (out, steps) if return_steps else out
 
-    def sample_keyed(self, cond1, cond2, cond3, keys, seed, n_time):
+    def sample_keyed(self, cond1, cond2, cond3, keys, seed, n_time, coupling=None):
         """sample() with keyed draws (DESIGN.md section 5.7): row r of the batch is sample keys[r] = (slice, sample) of an ensemble;
         x_init (kind 0, step 0) and every executed step k's z (kind 1) and posterior noise (kind 2) are drawn with ops.randn_keyed
-        on this device's current stream, so each row's result depends on (seed, its key) alone.  keys: int64 [B, 2] (host or device)."""
+        on this device's current stream, so each row's result depends on (seed, its key) alone.  keys: int64 [B, 2] (host or device).
+        `coupling` (mudiff_hip.slice_coupling): None; 'shared' = every row draws with slice key 0, so rows of one
+        sample index get identical draws; (half_taps, R) = every draw is ops.randn_keyed_coupled's, the white noise of the slices
+        slice-R..slice+R under those weights."""
+        from .slice_coupling import SHARED, check_coupling
+        coupling = check_coupling(coupling)
         k = ops.check_keys(keys)
         if k.shape[0] != self.B:
             raise ValueError(f'GraphSampler.sample_keyed: {k.shape[0]} keys for a batch of {self.B}')
         seed = ops._seed64(seed)
+        if coupling == SHARED:
+            k = k.clone()
+            k[:, 0] = 0
         kd = k.to(self.x.device)
+        if coupling is None or coupling == SHARED:
+            draw = lambda out, step, kind: ops.randn_keyed_into(out, kd, seed, step, kind)      # noqa: E731
+        else:
+            taps, radius = ops.coupling_taps_arg(*coupling)
+            draw = lambda out, step, kind: ops.randn_keyed_coupled_into(out, kd, seed, step, kind, taps, radius)      # noqa: E731
         self.c1.copy_(cond1); self.c2.copy_(cond2); self.c3.copy_(cond3)
-        ops.randn_keyed_into(self.x, kd, seed, 0, ops.KIND_X_INIT)
+        draw(self.x, 0, ops.KIND_X_INIT)
         for k_, i in enumerate(reversed(range(n_time))):
             self.t.fill_(i)
-            ops.randn_keyed_into(self.z, kd, seed, k_, ops.KIND_Z)
-            ops.randn_keyed_into(self.noise, kd, seed, k_, ops.KIND_NOISE)
+            draw(self.z, k_, ops.KIND_Z)
+            draw(self.noise, k_, ops.KIND_NOISE)
             if k_ == 0:
                 self.graph.replay()
                 x_new = self._first_out[2]

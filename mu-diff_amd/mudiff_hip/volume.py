@@ -9,7 +9,9 @@ What is different is the schedule, not the result: the reference pushes ONE slic
 (`for i in range(n)`, :266); here all <= 2*half_range+1 slices of the volume are uploaded once, resized by a HIP
 kernel, and sampled in batches of `--batch_size` through one captured hipGraph per reverse step (sampling.GraphSampler).
 Slices are independent, so the only observable difference is the order in which Gaussian draws are consumed; parity runs
-inject the draws per slice (`predict_slices(..., x_inits, zs, noises)`).
+inject the draws per slice (`predict_slices(..., x_inits, zs, noises)`).  --slice_coupling gives that independence up on purpose
+(mudiff_hip.slice_coupling): neighbouring slices then share part of their noise, and the single-sample path draws with the keyed
+generator of the ensembles instead of the torch generator.  --through_plane measures what it did (mudiff_hip.volume_through_plane).
 
 Intake: every path reads the three condition files as stored (volume_intake.read_nifti_raw) and hands them to the one preparation
 stage, volume_prepare.prepare_inputs; host_stacks then normalises with numpy, --device_intake with volume_intake.condition_from_raw.
@@ -289,7 +291,7 @@ def calibrate_volume(args, gen1, gen2, cond_stacks, device, batch_size=32):
 
 
 def predict_slices(args, gen1, gen2, cond_stacks, device, batch_size=32, x_inits=None, zs=None, noises=None, seed=None,
-                   use_graph=True, progress=None, sampler=None, return_device=False):
+                   use_graph=True, progress=None, sampler=None, return_device=False, coupling=None):
     """cond_stacks: three float arrays [n,X,Y] in [-1,1] (the condition contrasts, already normalised and sliced), or three device
     tensors [n,1,S,S] (volume_intake.condition_from_raw).  -> [n,S,S] float32 numpy in [0,1], S = args.image_size; with `return_device`
     the device tensor instead (no copy to the host).
@@ -298,9 +300,21 @@ def predict_slices(args, gen1, gen2, cond_stacks, device, batch_size=32, x_inits
     volumes - warm-up and the two hipGraph captures are then paid once per process instead of once per volume.
 
     x_inits [n,1,S,S] / zs (per step [n,nz]) / noises (per step [n,1,S,S]) inject the Gaussian draws per slice for
-    parity runs; otherwise they are drawn on the device (seeded by `seed` when given)."""
+    parity runs; otherwise they are drawn on the device (seeded by `seed` when given).
+
+    `coupling` (--slice_coupling; mudiff_hip.slice_coupling): None, 'shared' or (half_taps, R).  With one the
+    draws no longer come from the torch generator: every batch is sampled through GraphSampler.sample_keyed with the keys (global slice,
+    sample 0) and `seed` (required, in [0, 2^64)), so neighbouring slices share part of their noise and the result still does not depend
+    on the batch size.  Injected draws together with a coupling raise ValueError."""
     from . import ops
     from . import sampling as S
+    from .slice_coupling import check_coupling
+    coupling = check_coupling(coupling)
+    if coupling is not None:
+        if x_inits is not None or zs is not None or noises is not None:
+            raise ValueError('predict_slices: injected x_inits / zs / noises cannot be combined with a coupling (its draws are keyed)')
+        if seed is None or not use_graph:
+            raise ValueError('predict_slices: a coupling needs a seed and the captured sampler (use_graph=True)')
     n = int(cond_stacks[0].shape[0])
     size = int(args.image_size)
     if n == 0:
@@ -308,7 +322,7 @@ def predict_slices(args, gen1, gen2, cond_stacks, device, batch_size=32, x_inits
     conds = upload_conds(cond_stacks, size, device)
     coef = S.Posterior_Coefficients(args, device)
     gen = None
-    if seed is not None:
+    if seed is not None and coupling is None:
         gen = torch.Generator(device=device).manual_seed(int(seed))
     T = int(args.num_timesteps)
     bs = min(int(batch_size), n)
@@ -337,6 +351,12 @@ def predict_slices(args, gen1, gen2, cond_stacks, device, batch_size=32, x_inits
     for lo in range(0, n, bs):
         hi = min(lo + bs, n)
         c1, c2, c3 = (padded(c, lo, hi) for c in conds)
+        if coupling is not None:
+            keys = torch.stack([torch.arange(lo, lo + bs).clamp_(max=hi - 1), torch.zeros(bs, dtype=torch.int64)], 1)
+            out[lo:hi] = ops.to_range_0_1(sampler.sample_keyed(c1, c2, c3, keys, seed, T, coupling=coupling))[:hi - lo, 0]
+            if progress:
+                progress(hi, n)
+            continue
         x0 = padded(x_inits, lo, hi) if x_inits is not None else torch.randn(bs, 1, size, size, device=device)
         kw = {}
         if zs is not None:
@@ -359,7 +379,9 @@ def predict_volume(args):
     checkpoint work.  An input stage (volume_prepare.STAGES; each module's header says what it does) adds its report file, and what its
     *_out flag asks for, next to the prediction (volume_prepare.IntakeReport.write).  Under --reorient and --conform everything is sampled,
     scored and written on the reoriented / the conform grid; --reorient_back and --conform_back return the prediction (and its std) to the
-    first input's own grid as it is written, after the scoring (volume_prepare.output_writer)."""
+    first input's own grid as it is written, after the scoring (volume_prepare.output_writer).  --slice_coupling couples the draws of
+    neighbouring slices (predict_slices' `coupling`); --through_plane adds through_plane_<target>.json and one [through-plane] line
+    after the scores (mudiff_hip.volume_through_plane)."""
     evaluation, resampled, found = _load_eval_inputs(args)
     args = copy.copy(args)                               # the run's own copy: it carries the record of what the intake did
     args.evaluation_record = (resampled, found)          # (for _predict_volume's report: IntakeReport.add_evaluation)
@@ -469,8 +491,11 @@ def _intake_report(args):
 
 
 def _done_tail(args, plan):
-    """What a [done] line ends in: the arithmetic plan, --norm and what the intake did, each only when it is not the default."""
-    return ('' if plan == 'auto' else f' | prec_plan={plan}') + norm_suffix(args.norm) + _intake_report(args).suffix()
+    """What a [done] line ends in: the arithmetic plan, --norm, what the intake did and --slice_coupling, each only when it is not the
+    default."""
+    from .slice_coupling import suffix
+    return (('' if plan == 'auto' else f' | prec_plan={plan}') + norm_suffix(args.norm) + _intake_report(args).suffix() +
+            suffix(getattr(args, 'slice_coupling', None)))
 
 
 class _Stages:
@@ -519,7 +544,7 @@ def predict_from_conditions(args, plan, evaluation, gen1, gen2, device, stacks, 
     sampler = _cached_sampler(args, gen1, gen2, device, samplers, min(int(args.batch_size), n)) if n else None
     pred = stages.run('sample', lambda: predict_slices(args, gen1, gen2, stacks, device, batch_size=args.batch_size, seed=args.seed,
                                                        progress=lambda d, n: print(f'[infer] processed {d}/{n} slices'), sampler=sampler,
-                                                       return_device=on_device))
+                                                       return_device=on_device, coupling=_coupling(args)))
     if on_device:
         def put_together():
             from . import ops
@@ -539,7 +564,28 @@ def predict_from_conditions(args, plan, evaluation, gen1, gen2, device, stacks, 
     print(f'[done] saved: {out_path} | shape={tuple(vol_pred.shape)} | slices={s0}..{s1}' + _done_tail(args, plan))
     if evaluation is not None:
         _score_prediction(args, evaluation, vol_pred, None, device)
+    _through_plane(args, evaluation, vol_pred, device)
     return out_path
+
+
+def _coupling(args):
+    """--slice_coupling as the samplers take it (slice_coupling.coupling_from_flag; a namespace without the flag: None)."""
+    from .slice_coupling import coupling_from_flag
+    return coupling_from_flag(getattr(args, 'slice_coupling', None))
+
+
+def _through_plane(args, evaluation, vol, device):
+    """--through_plane: the roughness of the prediction exactly as written (and of --gt_volume when given) -> one printed line and
+    <output_dir>/through_plane_<target>.json (its path; None without the flag).  metrics_<t>.json is not touched."""
+    if not getattr(args, 'through_plane', False):
+        return None
+    from . import volume_through_plane as TP
+    gt = None if evaluation is None else evaluation[0]
+    rep = TP.measure_arrays(vol, gt, None, args.slice_half_range, device, norm=args.norm)
+    print(TP.format_line(rep))
+    path = TP.write_json(rep, os.path.join(args.output_dir, f'through_plane_{args.target_modality.lower()}.json'))
+    print(f'[through-plane] wrote {path}')
+    return path
 
 
 def _cached_sampler(args, gen1, gen2, device, samplers, batch):
@@ -570,7 +616,8 @@ def _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref, evaluation=N
     stages = stages or _Stages(None, device)
     sampler = _cached_sampler(args, gen1, gen2, device, samplers, args.batch_size)
     mean, std = stages.run('sample', lambda: ensemble.sample_ensemble(args, gen1, gen2, conds, args.num_samples, args.seed,
-                                                                      batch_size=args.batch_size, map_0_1=True, sampler=sampler))
+                                                                      batch_size=args.batch_size, map_0_1=True, sampler=sampler,
+                                                                      coupling=_coupling(args)))
     os.makedirs(args.output_dir, exist_ok=True)
     if tuple(shp[:2]) != tuple(mean.shape[1:]):
         mean, std = (stages.run('assemble', lambda t=t: ops.resize_bilinear(t, shp[:2])) for t in (mean, std))
@@ -589,28 +636,37 @@ def _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref, evaluation=N
           _done_tail(args, effective_prec_plan(args)))
     if evaluation is not None:
         _score_prediction(args, evaluation, vols[0], vols[1], device)
+    _through_plane(args, evaluation, vols[0], device)
     return tuple(paths)
 
 
 class VolumeParser(argparse.ArgumentParser):
     """The volume pipeline's parser: an ArgumentParser whose option list is the one tests/test_volume_cli_host.py pins, and `late`, a
     second parser for the flags of the stages that came after that list was pinned (a stage's add_flags puts them there:
-    volume_align).  parse_args hands `late` what the main parser did not know, into the same namespace, and refuses what neither
-    knows; the help lists both."""
+    volume_align).  `late`'s own list is pinned by now as well (tests/test_volume_align_host.py), so `later()` opens one more parser of
+    the same kind for what came after it (slice_coupling).  parse_args hands each of them what the parsers before it did not know, into
+    the same namespace, and refuses what none knows; the help lists them all."""
 
     def __init__(self, prog):
         super().__init__(prog)
         self.late = argparse.ArgumentParser(prog, add_help=False, usage=argparse.SUPPRESS)
+        self.lates = [self.late]
+
+    def later(self):
+        """A further late parser, consulted after the ones before it."""
+        self.lates.append(argparse.ArgumentParser(self.prog, add_help=False, usage=argparse.SUPPRESS))
+        return self.lates[-1]
 
     def parse_args(self, args=None, namespace=None):
         namespace, rest = self.parse_known_args(args, namespace)
-        namespace, rest = self.late.parse_known_args(rest, namespace)
+        for late in self.lates:
+            namespace, rest = late.parse_known_args(rest, namespace)
         if rest:
             self.error('unrecognized arguments: ' + ' '.join(rest))
         return namespace
 
     def format_help(self):
-        return super().format_help() + '\n' + self.late.format_help()
+        return super().format_help() + ''.join('\n' + late.format_help() for late in self.lates)
 
 
 def make_parser(prog='MU-Diff volume prediction (MI355X)'):
@@ -676,6 +732,8 @@ def make_parser(prog='MU-Diff volume prediction (MI355X)'):
         stage.module.add_flags(p)
     from .driver import add_calibration_flags
     add_calibration_flags(p)                # (also --prec_plan)
+    from . import slice_coupling
+    slice_coupling.add_flags(p)             # (--slice_coupling, --through_plane: in a late parser, VolumeParser.later())
     return p
 
 
@@ -687,6 +745,12 @@ def finish_args(p, args):
         p.error(f'--num_samples must be >= 2 (got {args.num_samples})')
     if args.num_samples is not None and not 0 <= args.seed < 1 << 64:
         p.error('--num_samples needs a --seed in [0, 2^64)')
+    from . import slice_coupling
+    try:
+        if slice_coupling.parse_flag(getattr(args, 'slice_coupling', None)) is not None and not 0 <= args.seed < 1 << 64:
+            p.error('--slice_coupling needs a --seed in [0, 2^64)')
+    except ValueError as e:
+        p.error(str(e))
     from . import volume_conform as VCF
     from . import volume_reorient as VO
     from .volume_prepare import STAGES
@@ -710,7 +774,8 @@ def build_argparser(argv=None):
     generators read and the reference parser forgot) and this build's own: the pipeline-wide ones make_parser adds after the
     reference's (their help texts say what they do and name their modules), --calibrate / --calibrate_threshold / --prec_plan
     (mudiff_hip.driver), and the flags of every input stage, each added and checked by the stage's own module (volume_prepare.STAGES;
-    DESIGN.md sections 5.12 - 5.22; --align's flags sit in VolumeParser.late)."""
+    DESIGN.md sections 5.12 - 5.22; --align's flags sit in VolumeParser.late), and --slice_coupling / --through_plane (mudiff_hip.slice_coupling,
+    DESIGN.md section 5.23; in a further late parser)."""
     p = make_parser()
     return finish_args(p, p.parse_args(argv))
 
