@@ -350,6 +350,44 @@ int mud_randn_keyed(float* out, int rows, int64_t row_len, const int64_t* keys, 
 int mud_ensemble_stats(const float* samples, int n, int N, int64_t hw, float scale, float shift, float lo, float hi, float* mean,
                        float* std, void* stream);
 
+/* ---- per-pixel order statistics of an ensemble (mudiff_hip.ensemble.sample_ensemble(quantiles=); the volume pipeline's
+ *      --ensemble_quantiles, --ensemble_center median and --coverage).
+ * mud_ensemble_quantiles: samples [n][N][hw] -> out [K][n][hw] (2 <= N <= MUD_ENSEMBLE_QUANTILES_MAX_N, 1 <= K <=
+ * MUD_ENSEMBLE_MAX_QUANTILES, hw > 0).  With y_(0) <= ... <= y_(N-1) a pixel's samples after mud_ensemble_stats' pre-map
+ * y = clamp(x*scale + shift, lo, hi) in ascending order and q[k] in [0, 1]:
+ *   h = (N - 1) * q[k],  i = min(floor(h), N - 2),  g = h - i,  out = (float)(y_(i) + g * (y_(i+1) - y_(i)))
+ * in fp64 from h on, each operation rounded once (no contraction): q = 0.5 is the median for odd and even N, q = 0 the minimum.  A pixel
+ * with a NaN sample gives NaN for every q; the sign of a zero is not specified.  q: HOST array of K finite fractions, read at call time
+ * and passed as a kernel argument (no device allocation).  A sorting network in registers, no LDS, no atomics: a fixed function of the
+ * samples. */
+#define MUD_ENSEMBLE_MAX_QUANTILES 8
+#define MUD_ENSEMBLE_QUANTILES_MAX_N 64
+int mud_ensemble_quantiles(const float* samples, int n, int N, int64_t hw, float scale, float shift, float lo, float hi, const double* q,
+                           int K, float* out, void* stream);
+
+/* ---- interval coverage against a ground truth (mudiff_hip.volume_coverage; the volume pipeline's --coverage).
+ * lo, hi, gt (fp32) and the optional region (uint8, bit k = region k as for mud_volume_metrics; may be NULL: every voxel is in every
+ * region) are [Z, X, Y] with planes contiguous, X*Y*Z < 2^31; 1 <= nreg <= MUD_VM_MAX_REGIONS.  For the planes z0 <= z <= z1
+ * (0 <= z0 <= z1 < Z; planes outside are never read) and the voxels v of plane z in region k,
+ *   counts[((z - z0) * nreg + k) * MUD_VC_NC + c]:  MUD_VC_N        voxels where none of lo, hi, gt is a NaN (the five below are over these)
+ *                                                   MUD_VC_BELOW    gt < lo            MUD_VC_ABOVE  gt > hi
+ *                                                   MUD_VC_INSIDE   neither            MUD_VC_NONFINITE  voxels where one of the three is a NaN
+ *   sums[((z - z0) * nreg + k) * MUD_VC_NS + s]:    MUD_VC_WIDTH    sum of (double)hi - (double)lo     MUD_VC_WIDTH_INSIDE  the same over `inside`
+ * A voxel with a NaN is counted in MUD_VC_NONFINITE and in nothing else.  Partials per (plane, workgroup) are added in a fixed order, no
+ * atomics: bit-identical run to run.  ws: (z1 - z0 + 1) * MUD_VC_PARTS * nreg * (MUD_VC_NC + MUD_VC_NS) * 8 bytes, 8-byte aligned. */
+#define MUD_VC_NC 5
+#define MUD_VC_NS 2
+#define MUD_VC_PARTS 16
+#define MUD_VC_N 0
+#define MUD_VC_BELOW 1
+#define MUD_VC_ABOVE 2
+#define MUD_VC_INSIDE 3
+#define MUD_VC_NONFINITE 4
+#define MUD_VC_WIDTH 0
+#define MUD_VC_WIDTH_INSIDE 1
+int mud_volume_interval_coverage(const float* lo, const float* hi, const float* gt, const uint8_t* region, int Z, int X, int Y, int nreg,
+                                 int z0, int z1, int64_t* counts, double* sums, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- slice-coupled sampling noise (mudiff_hip.slice_coupling; the volume pipeline's --slice_coupling).
  * mud_randn_keyed_coupled: the keyed draws of neighbouring slices filtered along z.  With eta(s)[e] the fp32 value mud_randn_keyed gives
  * element e of a row keyed (slice s, sample m) under the same seed, step and kind,

@@ -1,4 +1,4 @@
-// N-sample ensemble inference (include/mudiff_hip.h: mud_randn_keyed, mud_ensemble_stats).
+// N-sample ensemble inference (include/mudiff_hip.h: mud_randn_keyed, mud_ensemble_stats, mud_ensemble_quantiles).
 //
 // The sampler is stochastic: x_init, every step's latent z and every step's posterior noise are Gaussian draws.  Sampling a slice N
 // times and reporting the per-pixel mean and spread shows where a synthesis is unsure of itself.  Two kernels serve it:
@@ -6,7 +6,9 @@
 //    Philox4x64-10 (Random123; the algorithm and word order of numpy.random.Philox), so an ensemble does not depend on batch size,
 //    chunking or rank count, and nothing is pre-drawn;
 //  - statistics: per pixel, the fp64 mean and unbiased standard deviation over the N samples, summed in sample order with no
-//    atomics and no contraction: a fixed function of the samples.
+//    atomics and no contraction: a fixed function of the samples;
+//  - order statistics: per pixel, up to 8 quantiles of the N samples (the median, an interval's bounds) from a sorting network in
+//    registers: the same one read of the samples, a fixed function of them as well.
 // DESIGN.md section 5.7 has the definitions and the order arguments.
 #include "mud_common.h"
 
@@ -283,5 +285,157 @@ extern "C" int mud_ensemble_stats(const float* samples, int n, int N, int64_t hw
   else
     hipLaunchKernelGGL(k_ensemble_stats1, grid, dim3(ES_THREADS), 0, s, samples, n, N, hw, scale, shift, lo, hi, mean, std);
   MUD_CHECK_LAUNCH("mud_ensemble_stats");
+  return MUD_OK;
+}
+
+// ---- per-pixel quantiles --------------------------------------------------------------------------------------------------------------
+// With y_(0) <= ... <= y_(N-1) the pre-mapped (es_premap) samples of a pixel in ascending order and q a fraction in [0, 1]:
+//   h = (N - 1) * q,  i = min(floor(h), N - 2),  g = h - i,  out = fp32(y_(i) + g * (y_(i+1) - y_(i))),
+// everything from h on in fp64, each operation rounded once (no contraction).  A pixel with a NaN sample gives NaN for every q
+// (np.quantile's rule): v_min_f32 / v_max_f32 drop a NaN, so it is replaced by +inf for the sort and remembered beside it.
+// One thread sorts the samples of W pixels in registers: N is padded to NP, a power of two, with +inf (which sorts behind every sample,
+// ties included: only y_(0..N-1) are ever read), and a bitonic network of NP/2 * log2(NP) * (log2(NP) + 1) / 2 min / max pairs, fully
+// unrolled, does the rest.  Every index of y[][] is a compile-time constant, so the array lives in VGPRs; the order statistic of a
+// fraction is picked by NP selects on the (launch-uniform) index.  The fractions travel as a kernel argument.
+#define EQ_MAX_K MUD_ENSEMBLE_MAX_QUANTILES
+#define EQ_MAX_N MUD_ENSEMBLE_QUANTILES_MAX_N
+struct eq_fracs {
+  double q[EQ_MAX_K];
+};
+
+template <int NP, int W>
+__device__ __forceinline__ void eq_sort(float (&y)[NP][W]) {
+#pragma unroll
+  for (int lk = 1; (1 << lk) <= NP; ++lk) {               // merge sorted runs of 2^(lk-1) into runs of 2^lk, alternately up and down
+#pragma unroll
+    for (int lj = lk - 1; lj >= 0; --lj) {
+#pragma unroll
+      for (int a = 0; a < NP; ++a) {
+        const int b = a ^ (1 << lj);
+        if (b > a) {
+          const bool up = (a & (1 << lk)) == 0;
+#pragma unroll
+          for (int w = 0; w < W; ++w) {
+            const float mn = fminf(y[a][w], y[b][w]), mx = fmaxf(y[a][w], y[b][w]);
+            y[a][w] = up ? mn : mx;
+            y[b][w] = up ? mx : mn;
+          }
+        }
+      }
+    }
+  }
+}
+
+// one thread = W consecutive pixels of one slice; W == 4 under k_ensemble_stats4's condition (hw % 4 == 0, every pointer 16-byte aligned)
+template <int NP, int W>
+__global__ __launch_bounds__(ES_THREADS) void k_ensemble_quantiles(const float* __restrict__ x, int n, int N, int64_t hw, float scale, float shift,
+                                                                   float lo, float hi, eq_fracs fr, int K, float* __restrict__ out) {
+#pragma clang fp contract(off)
+  const int64_t per = hw / W;
+  const int64_t t = (int64_t)blockIdx.x * ES_THREADS + threadIdx.x;
+  if (t >= (int64_t)n * per) return;
+  const int64_t i = t / per, p = W * (t - i * per);
+  const float* src = x + (int64_t)i * N * hw + p;
+  const float inf = __builtin_inff();
+  float y[NP][W];
+  bool bad[W];
+#pragma unroll
+  for (int w = 0; w < W; ++w) bad[w] = false;
+#pragma unroll
+  for (int j = 0; j < NP; ++j) {
+    if (j < N) {                                            // uniform over the launch
+      float v[W];
+      es_load<W>(src + (int64_t)j * hw, v);
+#pragma unroll
+      for (int w = 0; w < W; ++w) {
+        const float m = es_premap(v[w], scale, shift, lo, hi);
+        bad[w] = bad[w] || m != m;
+        y[j][w] = m != m ? inf : m;
+      }
+    } else {
+#pragma unroll
+      for (int w = 0; w < W; ++w) y[j][w] = inf;
+    }
+  }
+  eq_sort<NP, W>(y);
+  float* dst = out + i * hw + p;
+#pragma unroll
+  for (int k = 0; k < EQ_MAX_K; ++k) {
+    if (k < K) {                                            // uniform over the launch, like idx and g
+      const double h = (double)(N - 1) * fr.q[k];
+      int idx = (int)floor(h);
+      idx = idx > N - 2 ? N - 2 : idx;
+      const double g = h - (double)idx;
+      float r[W];
+#pragma unroll
+      for (int w = 0; w < W; ++w) {
+        float a = y[0][w], b = y[1][w];
+#pragma unroll
+        for (int j = 1; j < NP - 1; ++j) {
+          a = j == idx ? y[j][w] : a;
+          b = j == idx ? y[j + 1][w] : b;
+        }
+        const double d = (double)b - (double)a;
+        const double e = g * d;
+        r[w] = bad[w] ? __builtin_nanf("") : (float)((double)a + e);
+      }
+      float* o = dst + (int64_t)k * n * hw;
+      if constexpr (W == 4) {
+        f32x4 ov;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) ov[w] = r[w];
+        *reinterpret_cast<f32x4*>(o) = ov;
+      } else {
+#pragma unroll
+        for (int w = 0; w < W; ++w) o[w] = r[w];
+      }
+    }
+  }
+}
+
+template <int NP, int W>
+static void eq_launch(dim3 grid, hipStream_t s, const float* samples, int n, int N, int64_t hw, float scale, float shift, float lo, float hi,
+                      const eq_fracs& fr, int K, float* out) {
+  hipLaunchKernelGGL((k_ensemble_quantiles<NP, W>), grid, dim3(ES_THREADS), 0, s, samples, n, N, hw, scale, shift, lo, hi, fr, K, out);
+}
+
+// NP <= EQ_VEC_NP sorts 4 pixels per thread on the aligned path (NP = 32: 196 VGPRs, 2 waves per SIMD); the 256 values of NP = 64 do
+// not fit the register file without scratch, so that size sorts one pixel per thread on both paths (scripts/kernel_resources.py;
+// DESIGN.md section 5.24)
+#define EQ_VEC_NP 32
+template <int NP>
+static void eq_dispatch(bool vec, int64_t blocks1, int64_t blocks4, hipStream_t s, const float* samples, int n, int N, int64_t hw, float scale,
+                        float shift, float lo, float hi, const eq_fracs& fr, int K, float* out) {
+  if constexpr (NP <= EQ_VEC_NP) {
+    if (vec) return eq_launch<NP, 4>(dim3((unsigned)blocks4), s, samples, n, N, hw, scale, shift, lo, hi, fr, K, out);
+  }
+  eq_launch<NP, 1>(dim3((unsigned)blocks1), s, samples, n, N, hw, scale, shift, lo, hi, fr, K, out);
+}
+
+extern "C" int mud_ensemble_quantiles(const float* samples, int n, int N, int64_t hw, float scale, float shift, float lo, float hi,
+                                      const double* q, int K, float* out, void* stream) {
+  MUD_REQUIRE(n >= 0 && hw > 0, "mud_ensemble_quantiles: bad sizes (n %d, hw %lld)", n, (long long)hw);
+  MUD_REQUIRE(N >= 2 && N <= EQ_MAX_N, "mud_ensemble_quantiles: N must be in [2, %d], got %d", EQ_MAX_N, N);
+  MUD_REQUIRE(K >= 1 && K <= EQ_MAX_K, "mud_ensemble_quantiles: 1 to %d quantiles, got %d", EQ_MAX_K, K);
+  MUD_REQUIRE(samples && q && out, "mud_ensemble_quantiles: null pointer");
+  eq_fracs fr;
+  for (int k = 0; k < EQ_MAX_K; ++k) {
+    fr.q[k] = k < K ? q[k] : 0.0;
+    MUD_REQUIRE(fr.q[k] >= 0.0 && fr.q[k] <= 1.0, "mud_ensemble_quantiles: quantile %d (%g) is not in [0, 1]", k, fr.q[k]);      // (a NaN fails it)
+  }
+  if (n == 0) return MUD_OK;
+  const bool vec = hw % 4 == 0 && mud_aligned16(samples) && mud_aligned16(out);
+  const int64_t blocks1 = mud_cdiv((int64_t)n * hw, ES_THREADS), blocks4 = mud_cdiv((int64_t)n * (hw / 4), ES_THREADS);
+  MUD_REQUIRE(blocks1 <= 0x7fffffff, "mud_ensemble_quantiles: too many pixels");
+  hipStream_t s = (hipStream_t)stream;
+#define EQ_CASE(NP) eq_dispatch<NP>(vec, blocks1, blocks4, s, samples, n, N, hw, scale, shift, lo, hi, fr, K, out)
+  if (N <= 2) EQ_CASE(2);
+  else if (N <= 4) EQ_CASE(4);
+  else if (N <= 8) EQ_CASE(8);
+  else if (N <= 16) EQ_CASE(16);
+  else if (N <= 32) EQ_CASE(32);
+  else EQ_CASE(64);
+#undef EQ_CASE
+  MUD_CHECK_LAUNCH("mud_ensemble_quantiles");
   return MUD_OK;
 }

@@ -15,7 +15,9 @@ is that run's file, bit for bit.  (--calibrate is the exception it has to be: it
 A bad subject - a missing or unreadable file, volumes of different shapes, an in-plane size the flags cannot write back - is reported
 and skipped; the run goes on and exits non-zero at the end.  A GPU error is not caught: it ends the run.
 
-Outputs: <output_dir>/<id>/predicted_<t>.nii.gz (plus _std and metrics_<t>.json when applicable) and <output_dir>/cohort_<t>.json: the
+Outputs: <output_dir>/<id>/predicted_<t>.nii.gz (plus _std, the _q<PPP> quantile maps, metrics_<t>.json and coverage_<t>.json when
+applicable; under --coverage the report gains a `coverage` block: mean and std over subjects of each region's empirical coverage and
+mean interval width) and <output_dir>/cohort_<t>.json: the
 per-subject rows, per region and metric the mean, the population standard deviation (ddof = 0) and the subject count, and the seconds
 of every stage summed over the cohort.  With --norm zscore the moments of every volume are computed on the
 prefetch thread, the [done] lines end in ` | norm=zscore`, and the reports carry "norm": "zscore" (a default run's are unchanged).
@@ -92,8 +94,8 @@ def subject_row(sid, report):
     return dict(id=sid, metrics={name: {k: report['metrics'][name][k] for k in METRICS + ('voxels',)} for name in report['regions']})
 
 
-def aggregate(rows):
-    """Per region and metric over the subjects that have a finite value: mean, std (population, ddof = 0) and count, summed in fp64 in
+def aggregate(rows, keys=METRICS):
+    """Per region and metric (`keys`) over the subjects that have a finite value: mean, std (population, ddof = 0) and count, summed in fp64 in
     row order.  A region no subject has (or only with null / infinite scores) reports null."""
     regions = []
     for r in rows:
@@ -101,7 +103,7 @@ def aggregate(rows):
     out = {}
     for name in regions:
         out[name] = {}
-        for k in METRICS:
+        for k in keys:
             vals = [r['metrics'][name][k] for r in rows if name in r['metrics']]
             vals = [float(v) for v in vals if v is not None and math.isfinite(v)]
             if not vals:
@@ -110,6 +112,19 @@ def aggregate(rows):
             mean = math.fsum(vals) / len(vals)
             out[name][k] = dict(mean=mean, std=math.sqrt(math.fsum((v - mean) ** 2 for v in vals) / len(vals)), count=len(vals))
     return out
+
+
+COVERAGE_KEYS = ('empirical', 'mean_width')
+
+
+def coverage_row(report):
+    """A subject's coverage block from its coverage_<t>.json report: {region: {empirical, mean_width}}."""
+    return {name: {k: report['coverage'][name][k] for k in COVERAGE_KEYS} for name in report['regions']}
+
+
+def aggregate_coverage(rows):
+    """aggregate's mean, std and count per region over the subjects' `coverage` blocks (--coverage), for empirical and mean_width."""
+    return aggregate([dict(metrics=r['coverage']) for r in rows if 'coverage' in r], COVERAGE_KEYS)
 
 
 def format_lines(agg):
@@ -251,6 +266,9 @@ def run(args, subjects, predict=None):
                     if evaluation is not None:
                         with open(os.path.join(sargs.output_dir, f'metrics_{target.lower()}.json')) as f:
                             row = subject_row(subject.id, json.load(f))
+                        if getattr(args, 'coverage', None) is not None:
+                            with open(os.path.join(sargs.output_dir, f'coverage_{target.lower()}.json')) as f:
+                                row['coverage'] = coverage_row(json.load(f))
                     rows.append(row)
                 except (OSError, ValueError, EOFError, zlib.error, struct.error) as e:       # (what reading a damaged file raises)
                     failures.append((subject.id, f'{type(e).__name__}: {e}'))
@@ -262,6 +280,8 @@ def run(args, subjects, predict=None):
     agg = aggregate(rows)
     report = dict(target=target, **({} if norm == 'percentile' else dict(norm=norm)), subjects=rows, failed=[dict(id=i, error=e) for i, e in failures], aggregate=agg,
                   std_definition='population standard deviation over subjects (ddof = 0)', timing=timing)
+    if getattr(args, 'coverage', None) is not None:      # (--coverage: mean +- std over subjects of empirical and mean_width per region)
+        report['coverage'] = aggregate_coverage(rows)
     os.makedirs(args.output_dir, exist_ok=True)
     path = os.path.join(args.output_dir, f'cohort_{target.lower()}.json')
     with open(path, 'w') as f:

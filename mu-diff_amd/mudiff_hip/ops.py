@@ -1048,6 +1048,78 @@ def ensemble_stats(samples, scale=1.0, shift=0.0, lo=-math.inf, hi=math.inf):
     return mean, std
 
 
+QUANTILES_MAX_K, QUANTILES_MAX_N = 8, 64      # include/mudiff_hip.h: MUD_ENSEMBLE_MAX_QUANTILES, MUD_ENSEMBLE_QUANTILES_MAX_N
+
+
+def ensemble_quantiles(samples, qs, scale=1.0, shift=0.0, lo=-math.inf, hi=math.inf, out=None):
+    """Per-pixel quantiles over the samples of each slice: samples [n, N, ...] (2 <= N <= 64, fp32) and 1 to 8 fractions `qs` in [0, 1]
+    -> fp32 [K, n, ...] of y = clamp(samples*scale + shift, lo, hi) (ops.ensemble_stats' pre-map): with y sorted ascending,
+    h = (N - 1) q, i = min(floor(h), N - 2), out = fp32(y[i] + (h - i) * (y[i+1] - y[i])) in fp64; q = 0.5 is the median.  A pixel with
+    a NaN sample gives NaN for every q.  A sorting network in registers: a fixed function of the samples (mud_ensemble_quantiles).
+    `out`: a contiguous fp32 device tensor of K * n * ... elements to fill instead of a new one."""
+    require_gpu(samples)
+    if samples.dim() < 3:
+        raise MudiffHipError(f'ensemble_quantiles: samples must be [n, N, ...], got {tuple(samples.shape)}')
+    n, N = samples.shape[0], samples.shape[1]
+    q = [float(v) for v in qs]
+    K = len(q)
+    x = _f32(samples.contiguous())
+    hw = math.prod(x.shape[2:])
+    shape = (K, n, *x.shape[2:])
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=torch.float32)
+    else:
+        require_gpu(x, out)
+        if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != math.prod(shape):
+            raise MudiffHipError(f'ensemble_quantiles: out must be a contiguous fp32 tensor of {math.prod(shape)} elements, got {out.dtype} '
+                                 f'{tuple(out.shape)}')
+        out = out.view(shape)
+    if n == 0 or hw == 0:                      # nothing to launch: the entry point's own range checks, then the empty result
+        if not (2 <= N <= QUANTILES_MAX_N and 1 <= K <= QUANTILES_MAX_K):
+            raise MudiffHipError(f'ensemble_quantiles: need 2 to {QUANTILES_MAX_N} samples and 1 to {QUANTILES_MAX_K} quantiles, got {N} and {K}')
+        return out
+    _launch('ensemble_quantiles', x.device, load().mud_ensemble_quantiles, ptr(x), n, N, hw, float(scale), float(shift), float(lo),
+            float(hi), (C.c_double * max(K, 1))(*q), K, ptr(out), STREAM, nbytes=4.0 * n * hw * (N + K))
+    return out
+
+
+# columns of volume_interval_coverage's counts and sums (include/mudiff_hip.h: MUD_VC_*)
+VC_N, VC_BELOW, VC_ABOVE, VC_INSIDE, VC_NONFINITE = range(5)
+VC_WIDTH, VC_WIDTH_INSIDE = range(2)
+VC_NC, VC_NS, VC_PARTS = 5, 2, 16
+
+
+def volume_interval_coverage(lo, hi, gt, region=None, nreg=1, z0=0, z1=None):
+    """Per plane and region, how the ground truth `gt` lies to the interval [lo, hi]: three fp32 [Z, X, Y] volumes (planes contiguous)
+    and the uint8 region bits of volume_metrics.region_mask (None: every voxel is in every region), for the planes z0..z1 clipped to
+    the volume (z1 None: the last plane); planes outside that range are never read -> (device int64 counts [planes, nreg, VC_NC], device
+    fp64 width sums [planes, nreg, VC_NS], first plane, last plane).  mud_volume_interval_coverage defines the columns: a voxel with a
+    NaN in any of the three counts as VC_NONFINITE and nothing else.  Bit-identical run to run.  No synchronisation."""
+    require_gpu(lo, hi, gt, region)
+    vols = (lo, hi, gt)
+    if any(v.dtype != torch.float32 or v.dim() != 3 or v.shape != lo.shape for v in vols) or (
+            region is not None and (region.dtype != torch.uint8 or region.shape != lo.shape)):
+        raise MudiffHipError('volume_interval_coverage: need three fp32 [Z, X, Y] volumes of one shape and a uint8 region volume of that '
+                             'shape (got ' + ', '.join(f'{v.dtype} {tuple(v.shape)}' for v in vols + (() if region is None else (region,))) + ')')
+    Z, X, Y = lo.shape
+    if min(Z, X, Y) < 1:
+        raise MudiffHipError(f'volume_interval_coverage: empty volume {tuple(lo.shape)}')
+    nreg = int(nreg)
+    if not 1 <= nreg <= VM_MAX_REGIONS:
+        raise MudiffHipError(f'volume_interval_coverage: nreg must be in [1, {VM_MAX_REGIONS}], got {nreg}')
+    z0, z1 = max(0, int(z0)), Z - 1 if z1 is None else min(Z - 1, int(z1))
+    if z0 > z1:
+        raise MudiffHipError(f'volume_interval_coverage: no plane of the {Z} lies in {z0}..{z1}')
+    lo_, hi_, gt_, reg_ = lo.contiguous(), hi.contiguous(), gt.contiguous(), None if region is None else region.contiguous()
+    planes = z1 - z0 + 1
+    counts = torch.empty(planes, nreg, VC_NC, device=lo.device, dtype=torch.int64)
+    sums = torch.empty(planes, nreg, VC_NS, device=lo.device, dtype=torch.float64)
+    ws = torch.empty(planes * VC_PARTS * nreg * (VC_NC + VC_NS), device=lo.device, dtype=torch.float64)
+    _launch('volume_interval_coverage', lo.device, load().mud_volume_interval_coverage, ptr(lo_), ptr(hi_), ptr(gt_), ptr(reg_), Z, X, Y, nreg,
+            z0, z1, ptr(counts), ptr(sums), ptr(ws), ws.numel() * 8, STREAM, nbytes=float(planes) * X * Y * (12 if region is None else 13))
+    return counts, sums, z0, z1
+
+
 # ---------------------------------------------------------------------------------------------------
 # --bias_correct (csrc/volume_bias.hip; the loop around these is mudiff_hip.volume_bias)
 # ---------------------------------------------------------------------------------------------------

@@ -381,7 +381,9 @@ def predict_volume(args):
     scored and written on the reoriented / the conform grid; --reorient_back and --conform_back return the prediction (and its std) to the
     first input's own grid as it is written, after the scoring (volume_prepare.output_writer).  --slice_coupling couples the draws of
     neighbouring slices (predict_slices' `coupling`); --through_plane adds through_plane_<target>.json and one [through-plane] line
-    after the scores (mudiff_hip.volume_through_plane)."""
+    after the scores (mudiff_hip.volume_through_plane).  With --num_samples, --ensemble_quantiles writes per-voxel quantile maps of the
+    samples next to the mean and the std, --ensemble_center median makes the median the written and scored prediction, and --coverage
+    counts how often the ground truth lies between two of the maps (mudiff_hip.ensemble, mudiff_hip.volume_coverage)."""
     evaluation, resampled, found = _load_eval_inputs(args)
     args = copy.copy(args)                               # the run's own copy: it carries the record of what the intake did
     args.evaluation_record = (resampled, found)          # (for _predict_volume's report: IntakeReport.add_evaluation)
@@ -491,11 +493,12 @@ def _intake_report(args):
 
 
 def _done_tail(args, plan):
-    """What a [done] line ends in: the arithmetic plan, --norm, what the intake did and --slice_coupling, each only when it is not the
-    default."""
+    """What a [done] line ends in: the arithmetic plan, --norm, what the intake did, --slice_coupling and the ensemble's centre and
+    quantiles, each only when it is not the default."""
+    from .ensemble import done_suffix
     from .slice_coupling import suffix
     return (('' if plan == 'auto' else f' | prec_plan={plan}') + norm_suffix(args.norm) + _intake_report(args).suffix() +
-            suffix(getattr(args, 'slice_coupling', None)))
+            suffix(getattr(args, 'slice_coupling', None)) + done_suffix(args))
 
 
 class _Stages:
@@ -605,7 +608,10 @@ def _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref, evaluation=N
                              stages=None):
     """--num_samples: every slice sampled N times with draws keyed by (--seed, slice, sample) (mudiff_hip.ensemble); the mean and
     the std of the [0,1]-mapped samples, resized back and re-assembled like the single prediction, go to predicted_<t>.nii.gz and
-    predicted_<t>_std.nii.gz.  With `evaluation` the mean is scored, the std feeding the uncertainty block.  -> (mean path, std path)."""
+    predicted_<t>_std.nii.gz.  With `evaluation` the mean is scored, the std feeding the uncertainty block.  -> (mean path, std path).
+    Under --ensemble_quantiles / --ensemble_center median / --coverage (ensemble.quantile_plan) the per-voxel
+    quantile maps take the same road to predicted_<t>_q<PPP>.nii.gz, the median replaces the mean as the centre, and coverage_<t>.json
+    follows the scores."""
     from . import ensemble, ops
     from .driver import effective_prec_plan
     shp, aff, hdr, s0, s1 = ref
@@ -615,19 +621,28 @@ def _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref, evaluation=N
     write = write or write_nifti
     stages = stages or _Stages(None, device)
     sampler = _cached_sampler(args, gen1, gen2, device, samplers, args.batch_size)
-    mean, std = stages.run('sample', lambda: ensemble.sample_ensemble(args, gen1, gen2, conds, args.num_samples, args.seed,
-                                                                      batch_size=args.batch_size, map_0_1=True, sampler=sampler,
-                                                                      coupling=_coupling(args)))
+    qplan = ensemble.quantile_plan(args)
+    res = stages.run('sample', lambda: ensemble.sample_ensemble(args, gen1, gen2, conds, args.num_samples, args.seed,
+                                                                batch_size=args.batch_size, map_0_1=True, sampler=sampler,
+                                                                coupling=_coupling(args), quantiles=qplan and qplan.computed))
+    mean, std = res[:2]
+    qmaps = list(res[2]) if qplan is not None else []                # one [n,S,S] map per computed fraction
     os.makedirs(args.output_dir, exist_ok=True)
     if tuple(shp[:2]) != tuple(mean.shape[1:]):
         mean, std = (stages.run('assemble', lambda t=t: ops.resize_bilinear(t, shp[:2])) for t in (mean, std))
+        qmaps = [stages.run('assemble', lambda t=t: ops.resize_bilinear(t.contiguous(), shp[:2])) for t in qmaps]
     if on_device:
         from . import volume_intake as VI
         vols = stages.run('assemble', lambda: [VI.to_host_volume(v) for v in VI.assemble(mean, shp, s0, s1, std)])
+        qvols = [stages.run('assemble', lambda t=t: VI.to_host_volume(VI.assemble(t.contiguous(), shp, s0, s1))) for t in qmaps]
     else:
         vols = [reconstruct_volume_from_slices(list(t.cpu().numpy()), shp, s0, s1) for t in (mean, std)]
+        qvols = [reconstruct_volume_from_slices(list(t.cpu().numpy()), shp, s0, s1) for t in qmaps]
+    quantile_vols = {} if qplan is None else dict(zip(qplan.computed, qvols))
+    if qplan is not None and qplan.center == 'median':
+        vols[0] = quantile_vols[0.5]                                 # the centre: what is written, scored and measured from here on
     paths = []
-    for suffix, vol in (('', vols[0]), ('_std', vols[1])):
+    for suffix, vol in (('', vols[0]), ('_std', vols[1])) + tuple((ensemble.quantile_suffix(q), quantile_vols[q]) for q in (qplan.written if qplan else ())):
         path = os.path.join(args.output_dir, f'predicted_{args.target_modality.lower()}{suffix}.nii.gz')
         stages.run('write', lambda: write(path, vol, aff, hdr))
         paths.append(path)
@@ -636,8 +651,24 @@ def _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref, evaluation=N
           _done_tail(args, effective_prec_plan(args)))
     if evaluation is not None:
         _score_prediction(args, evaluation, vols[0], vols[1], device)
+        if qplan is not None and qplan.coverage is not None:
+            _coverage(args, evaluation, quantile_vols[qplan.coverage[0]], quantile_vols[qplan.coverage[1]], qplan.coverage, device)
     _through_plane(args, evaluation, vols[0], device)
-    return tuple(paths)
+    return tuple(paths[:2])
+
+
+def _coverage(args, evaluation, lo_vol, hi_vol, fractions, device):
+    """--coverage: how often the ground truth lies between the two quantile volumes exactly as written -> one printed line per region and
+    <output_dir>/coverage_<target>.json (its path).  metrics_<t>.json is not touched."""
+    from . import volume_coverage as VC
+    gt, label = evaluation
+    rep = VC.measure_arrays(lo_vol, hi_vol, gt, label, args.slice_half_range, device, norm=args.norm, nominal=fractions[1] - fractions[0])
+    rep['quantiles'] = [float(fractions[0]), float(fractions[1])]
+    for ln in VC.format_lines(rep):
+        print(ln)
+    path = VC.write_json(rep, os.path.join(args.output_dir, f'coverage_{args.target_modality.lower()}.json'))
+    print(f'[coverage] wrote {path}')
+    return path
 
 
 class VolumeParser(argparse.ArgumentParser):
@@ -734,6 +765,8 @@ def make_parser(prog='MU-Diff volume prediction (MI355X)'):
     add_calibration_flags(p)                # (also --prec_plan)
     from . import slice_coupling
     slice_coupling.add_flags(p)             # (--slice_coupling, --through_plane: in a late parser, VolumeParser.later())
+    from . import ensemble
+    ensemble.add_flags(p)                   # (--ensemble_quantiles, --ensemble_center, --coverage: in a further one)
     return p
 
 
@@ -749,6 +782,11 @@ def finish_args(p, args):
     try:
         if slice_coupling.parse_flag(getattr(args, 'slice_coupling', None)) is not None and not 0 <= args.seed < 1 << 64:
             p.error('--slice_coupling needs a --seed in [0, 2^64)')
+    except ValueError as e:
+        p.error(str(e))
+    from . import ensemble
+    try:
+        ensemble.quantile_plan(args)                     # (its ValueError names the flag)
     except ValueError as e:
         p.error(str(e))
     from . import volume_conform as VCF
@@ -775,7 +813,8 @@ def build_argparser(argv=None):
     reference's (their help texts say what they do and name their modules), --calibrate / --calibrate_threshold / --prec_plan
     (mudiff_hip.driver), and the flags of every input stage, each added and checked by the stage's own module (volume_prepare.STAGES;
     DESIGN.md sections 5.12 - 5.22; --align's flags sit in VolumeParser.late), and --slice_coupling / --through_plane (mudiff_hip.slice_coupling,
-    DESIGN.md section 5.23; in a further late parser)."""
+    DESIGN.md section 5.23; in a further late parser), and --ensemble_quantiles / --ensemble_center / --coverage (mudiff_hip.ensemble,
+    mudiff_hip.volume_coverage; in one more)."""
     p = make_parser()
     return finish_args(p, p.parse_args(argv))
 
