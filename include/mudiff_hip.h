@@ -402,6 +402,29 @@ int mud_volume_interval_coverage(const float* lo, const float* hi, const float* 
 int mud_randn_keyed_coupled(float* out, int rows, int64_t row_len, const int64_t* keys, uint64_t seed, int step, int kind,
                             const double* half_taps, int radius, void* stream);
 
+/* ---- sampling with a partly acquired target (mudiff_hip.known_region; GraphSampler.sample_keyed(known=)).
+ * mud_known_constrain: re-imposes the known voxels on a reverse step's result at that step's noise level (RePaint, Lugmayr et al. 2022).
+ * Rows are the slices of a batch, row_len contiguous fp32 values each.  With c = clamp(t[r] + toff, 0, ntab - 1) (mud_q_sample's rule),
+ *   out[r][e] = mask[r][e] ? (clean ? known[r][e] : a_tab[c] * known[r][e] + s_tab[c] * eta[r][e]) : x_new[r][e],
+ * the two products and the sum in fp32, each rounded once, in mud_q_sample's order: with the same eta the known part has mud_q_sample's
+ * bits.  It is a select: whatever `known` holds where the mask is 0 (a NaN, an inf) never reaches out.  eta is `noise` [rows][row_len] when
+ * that is given, else the value mud_randn_keyed gives element e of a row keyed keys[2r..2r+1] under (seed, step, kind): the same
+ * counter, key and Box-Muller, drawn in the kernel, and only by the threads (4 consecutive elements each) that have a known element.
+ * kind in [0, 15] (mud_randn_keyed itself accepts 0..2: 3 and 4 are this entry's, mudiff_hip.ops.KIND_KNOWN / KIND_RENOISE); step in
+ * [0, 2^24).  mask: uint8 [rows][row_len], non-zero = known; NULL = known everywhere, x_new may then be NULL as well and the call is a
+ * keyed q_sample of `known`.  out may be x_new or known.  With clean != 0 nothing is drawn: t, the tables, noise and keys may be NULL.
+ * 16-byte loads and stores when row_len % 4 == 0 and every pointer is 16-byte (the mask: 4-byte) aligned, else element by element.
+ * MUD_ERR_ARG before any launch for rows <= 0, row_len <= 0, ntab <= 0, a kind or step out of range, a null pointer that is needed, and
+ * neither noise nor keys.
+ * mud_known_coverage: out (uint8 [Z][Y][X]) = 1 where the destination voxel (i, j, k) of a resampling by the matrix m of
+ * mud_volume_regrid (12 doubles on the host, finite) has a source coordinate p with 0 <= p_a <= S_a - 1 on all three axes, else 0;
+ * p in fp64 as mud_volume_regrid_cubic forms it.  There the trilinear and the cubic footprint need no zero padding: the voxel was
+ * interpolated from acquired voxels alone.  Both sizes positive, X*Y*Z < 2^31. */
+int mud_known_constrain(const float* x_new, const float* known, const uint8_t* mask, const float* noise, const int64_t* keys, uint64_t seed,
+                        int step, int kind, const int64_t* t, int toff, const float* a_tab, const float* s_tab, int ntab, int clean,
+                        float* out, int rows, int64_t row_len, void* stream);
+int mud_known_coverage(const double* m, int SX, int SY, int SZ, int X, int Y, int Z, uint8_t* out, void* stream);
+
 /* ---- through-plane roughness of a volume (mudiff_hip.volume_through_plane; the volume pipeline's --through_plane).
  * vol (fp32) and the optional mask (uint8, may be NULL: every voxel is inside; else non-zero is inside) are [Z, X, Y] with planes
  * contiguous, X*Y*Z < 2^31.  For the planes z0 <= z <= z1 (0 <= z0 <= z1 < Z; planes outside are never read),

@@ -10,43 +10,9 @@
 //  - order statistics: per pixel, up to 8 quantiles of the N samples (the median, an interval's bounds) from a sorting network in
 //    registers: the same one read of the samples, a fixed function of them as well.
 // DESIGN.md section 5.7 has the definitions and the order arguments.
-#include "mud_common.h"
+#include "keyed_normal.h"      // es_philox, es_box_muller, es_block_normals (shared with known_region.hip)
 
 #define ES_THREADS 256
-#define ES_KEY_HI 0x4D55444946460001ull
-
-// ---- Philox4x64-10 ----------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void es_philox_round(uint64_t& c0, uint64_t& c1, uint64_t& c2, uint64_t& c3, uint64_t k0, uint64_t k1) {
-  const uint64_t lo0 = 0xD2E7470EE14C6C93ull * c0, hi0 = __umul64hi(0xD2E7470EE14C6C93ull, c0);
-  const uint64_t lo1 = 0xCA5A826395121157ull * c2, hi1 = __umul64hi(0xCA5A826395121157ull, c2);
-  const uint64_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-  c0 = n0;
-  c1 = lo1;
-  c2 = n2;
-  c3 = lo0;
-}
-
-__device__ __forceinline__ void es_philox(uint64_t& c0, uint64_t& c1, uint64_t& c2, uint64_t& c3, uint64_t k0, uint64_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    if (r) {
-      k0 += 0x9E3779B97F4A7C15ull;
-      k1 += 0xBB67AE8584CAA73Bull;
-    }
-    es_philox_round(c0, c1, c2, c3, k0, k1);
-  }
-}
-
-// Box-Muller on one word pair, all in fp64: u1 in (0, 1], u2 in [0, 1)
-__device__ __forceinline__ void es_box_muller(uint64_t wa, uint64_t wb, float& a, float& b) {
-  const double u1 = (double)((wa >> 11) + 1) * 0x1.0p-53;
-  const double u2 = (double)(wb >> 11) * 0x1.0p-53;
-  const double r = sqrt(-2.0 * log(u1));
-  double s, c;
-  sincos(6.283185307179586 * u2, &s, &c);
-  a = (float)(r * c);
-  b = (float)(r * s);
-}
 
 // one thread = one Philox block = 4 consecutive elements of one row
 __global__ __launch_bounds__(ES_THREADS) void k_randn_keyed(float* __restrict__ out, int rows, int64_t row_len, int64_t blocks_per_row,
@@ -55,16 +21,7 @@ __global__ __launch_bounds__(ES_THREADS) void k_randn_keyed(float* __restrict__ 
   if (t >= (int64_t)rows * blocks_per_row) return;
   const int64_t r = t / blocks_per_row, b = t - r * blocks_per_row;
   const uint64_t slice = (uint64_t)keys[2 * r], sample = (uint64_t)keys[2 * r + 1];
-  uint64_t c0 = (uint64_t)b, c1 = slice, c2 = (sample << 32) | word2, c3 = 0;
-  es_philox(c0, c1, c2, c3, seed, ES_KEY_HI);
-  f32x4 v;
-  float a, bb;
-  es_box_muller(c0, c1, a, bb);
-  v[0] = a;
-  v[1] = bb;
-  es_box_muller(c2, c3, a, bb);
-  v[2] = a;
-  v[3] = bb;
+  const f32x4 v = es_block_normals((uint64_t)b, slice, sample, seed, word2);
   float* dst = out + r * row_len + 4 * b;
   if (vec) {                       // row_len % 4 == 0 and out 16-byte aligned: every block is whole and aligned
     *reinterpret_cast<f32x4*>(dst) = v;

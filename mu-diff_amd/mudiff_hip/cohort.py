@@ -26,7 +26,9 @@ the main thread, between the read and the intake, exactly as in a single run: it
 and the subject's [done] line names what it did.  The evaluation inputs go onto the grid the prediction will have on the main thread
 too (volume_prepare.evaluation_inputs); the prefetch thread only reads them (volume_prepare.read_for_evaluation).  --reorient_back and
 --conform_back wrap the deferred writer (volume_prepare.output_writer): the resampling onto the first input's own grid runs on the main
-thread, the compression and the write on the pool.
+thread, the compression and the write on the pool.  A subject whose manifest row has a `known` (and `known_mask`) cell is sampled with
+that subject's --known_volume / --known_mask (mudiff_hip.known_region; --known_drop_slices and --known_resample
+come from the command line): known_<t>.json goes next to its prediction and the regions known / synthesised join the aggregate.
 """
 from __future__ import annotations
 
@@ -45,15 +47,15 @@ import zlib
 METRICS = ('psnr', 'ssim3d', 'mae')
 MODALITIES = ('t1', 't1ce', 't2', 'flair')
 QUEUE_DEPTH = 2                    # subjects read ahead, and written volumes in flight: memory stays flat whatever the cohort's size
-Subject = collections.namedtuple('Subject', 'id inputs gt mask')       # inputs: {'T1': path, ...}; gt / mask: path or None
+Subject = collections.namedtuple('Subject', 'id inputs gt mask known known_mask', defaults=(None, None))      # inputs: {'T1': path, ...}; the rest: path or None
 
 
 # ---------------------------------------------------------------------------------------------------
 # which subjects
 # ---------------------------------------------------------------------------------------------------
 def read_manifest(path):
-    """TSV with a header row: id, t1, t1ce, t2, flair and optionally gt, mask (an empty cell is `not given`).  Relative paths are
-    relative to the manifest."""
+    """TSV with a header row: id, t1, t1ce, t2, flair and optionally gt, mask, known, known_mask (an empty cell is `not given`; the last
+    two: the subject's --known_volume / --known_mask, mudiff_hip.known_region).  Relative paths are relative to the manifest."""
     base = os.path.dirname(os.path.abspath(path))
     with open(path, newline='') as f:
         rows = list(csv.DictReader(f, delimiter='\t'))
@@ -69,7 +71,10 @@ def read_manifest(path):
         if not sid:
             raise ValueError(f'{path}: a row without an id')
         out.append(Subject(sid, {m.upper(): where((r[m] or '').strip()) for m in MODALITIES}, where((r.get('gt') or '').strip()),
-                           where((r.get('mask') or '').strip())))
+                           where((r.get('mask') or '').strip()), where((r.get('known') or '').strip()),
+                           where((r.get('known_mask') or '').strip())))
+        if out[-1].known_mask and not out[-1].known:
+            raise ValueError(f'{path}: {sid} has a known_mask without a known volume')
     if len({s.id for s in out}) != len(out):
         raise ValueError(f'{path}: subject ids must be unique')
     return out
@@ -245,6 +250,13 @@ def run(args, subjects, predict=None):
                                  for m, vol in zip(needed, conds)]
                         torch.cuda.synchronize(device)
                     report.add_evaluation(resampled, found)
+                    sargs.known_inputs = None
+                    if subject.known:                              # (the subject's --known_volume: mudiff_hip.known_region)
+                        from . import known_region as KR
+                        sargs.known_volume, sargs.known_mask = subject.known, subject.known_mask
+                        known = KR.options_from(sargs)
+                        sargs.known_inputs = KR.on_grid(raws[0], KR.read_inputs(known, options), known, options, gpu, align=found.get('align'))
+                        report.add_evaluation(list(sargs.known_inputs.resampled), {})
                     sargs.intake_report = report                   # (the [done] line names what it lists)
                     timing['intake'] += time.perf_counter() - t0
 
@@ -309,7 +321,7 @@ def build_argparser(argv=None):
         p.error('--brats_root needs --subjects LIST')
     if args.io_threads < 1:
         p.error('--io_threads must be >= 1')
-    for flag in ('gt_volume', 'eval_mask') + tuple(f'input_{m}' for m in MODALITIES):
+    for flag in ('gt_volume', 'eval_mask', 'known_volume', 'known_mask') + tuple(f'input_{m}' for m in MODALITIES):
         if getattr(args, flag) is not None:
             p.error(f'--{flag} names one subject\'s file: a cohort takes its files from the manifest or the BraTS layout')
     return args

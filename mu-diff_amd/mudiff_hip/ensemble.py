@@ -45,7 +45,7 @@ def premap(map_0_1):
 
 
 def sample_ensemble(args, gen1, gen2, conds, num_samples, seed, batch_size=32, slice_offset=0, chunk=None, sampler=None, map_0_1=False,
-                    return_samples=False, coupling=None, quantiles=None):
+                    return_samples=False, coupling=None, quantiles=None, known=None, resample=1):
     """conds: three device tensors [n,1,S,S] (S = args.image_size) -> (mean, std) device fp32 [n,S,S] over `num_samples` (>= 2) samples
     per slice, plus the raw samples [n,N,S,S] with `return_samples`.  `map_0_1`: the statistics are those of the samples mapped to
     [0,1] (ops.to_range_0_1); the returned samples are never mapped.
@@ -57,7 +57,9 @@ def sample_ensemble(args, gen1, gen2, conds, num_samples, seed, batch_size=32, s
     the keys stay global, so shards and chunks still draw what a single run would.
     `quantiles`: a tuple of 1 to 8 fractions in [0, 1] (num_samples <= MAX_QUANTILE_SAMPLES): the per-pixel quantiles of each slice's
     samples under the same pre-map (ops.ensemble_quantiles; 0.5 is the median), taken from the chunk buffer right
-    after the statistics, are returned as one more tensor [K,n,S,S] at the end of the tuple.  None returns exactly what it did before."""
+    after the statistics, are returned as one more tensor [K,n,S,S] at the end of the tuple.  None returns exactly what it did before.
+    `known`, `resample` (mudiff_hip.known_region): None, or (known [n,1,S,S], mask uint8 [n,1,S,S]) per slice on the
+    device: every sample of slice i is drawn with that slice's known region re-imposed (GraphSampler.sample_keyed's known / known_mask)."""
     from . import sampling as S
     N = int(num_samples)
     if N < 2:
@@ -106,7 +108,9 @@ def sample_ensemble(args, gen1, gen2, conds, num_samples, seed, batch_size=32, s
             sl = items // N
             keys = torch.stack([sl + int(slice_offset), items % N], 1)
             idx = sl.to(device)
-            res = sampler.sample_keyed(c1.index_select(0, idx), c2.index_select(0, idx), c3.index_select(0, idx), keys, seed, T, coupling=coupling)
+            more = {} if known is None else dict(known=known[0].index_select(0, idx), known_mask=known[1].index_select(0, idx), resample=resample)
+            res = sampler.sample_keyed(c1.index_select(0, idx), c2.index_select(0, idx), c3.index_select(0, idx), keys, seed, T, coupling=coupling,
+                                       **more)
             flat[b0 - q0:b0 - q0 + m] = res[:m, 0]
         mean[s0:s1], std[s0:s1] = ops.ensemble_stats(out, scale, shift, lo, hi)
         if qmaps is not None:

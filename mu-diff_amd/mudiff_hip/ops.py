@@ -998,6 +998,74 @@ def randn_keyed_coupled(rows_keys, row_len, seed, step, kind, half_taps, radius,
     return out
 
 
+# ---------------------------------------------------------------------------------------------------
+# sampling with a partly acquired target (csrc/known_region.hip, mudiff_hip.known_region)
+KIND_KNOWN, KIND_RENOISE = 3, 4      # the draws of mud_known_constrain: the known region's forward noise, RePaint's one-level re-noising
+
+
+def known_constrain_into(out, x_new, known, mask, keys_dev, seed, step, kind, t, toff, a_tab, s_tab, clean=False, noise=None):
+    """Unchecked launch of mud_known_constrain into `out` (fp32, contiguous, [rows, ...]; may be x_new or known): GraphSampler.sample_keyed
+    checks its operands once per batch, not once per step.  keys_dev: through check_keys and on out's device (None with `noise`)."""
+    rows = out.shape[0]
+    _launch('known_constrain', out.device, load().mud_known_constrain, ptr(x_new), ptr(known), ptr(mask), ptr(noise), ptr(keys_dev), C.c_uint64(seed),
+            int(step), int(kind), ptr(t), int(toff), ptr(a_tab), ptr(s_tab), 1 if a_tab is None else a_tab.numel(), int(bool(clean)), ptr(out), rows,
+            out.numel() // max(rows, 1), STREAM, nbytes=float(out.numel() * (13 if mask is not None else 8)))
+    return out
+
+
+def known_constrain(x_new, known, mask, t, toff, a_tab, s_tab, *, noise=None, keys=None, seed=0, step=0, kind=KIND_KNOWN, clean=False, out=None):
+    """out = mask ? (clean ? known : a_tab[c] * known + s_tab[c] * eta) : x_new per element, c = clamp(t[row] + toff, 0, len(a_tab) - 1)
+    (mud_known_constrain): the known part is ops.q_sample's arithmetic bit for bit, the rest x_new's bits; a select, so a NaN of `known`
+    outside the mask stays out.  x_new, known: fp32 [rows, ...] of one shape; mask: uint8 of that shape, or None = known everywhere
+    (x_new may then be None: a keyed q_sample).  eta: `noise` (fp32, that shape) when given, else the keyed normal ops.randn_keyed gives
+    keys[r] = (slice, sample) under (seed, step, kind), drawn in the kernel; kind in [0, 15].  t: int64 [rows]; with `clean` it, the
+    tables and the draw are not needed.  out: None (a new tensor), x_new or known (in place) or any contiguous fp32 tensor of the shape."""
+    require_gpu(x_new, known, mask, noise, t, a_tab, s_tab, out)
+    if known.dtype != torch.float32 or known.dim() < 1 or known.shape[0] < 1 or known[0].numel() < 1:
+        raise MudiffHipError(f'known_constrain: known must be a non-empty fp32 [rows, ...] tensor, got {known.dtype} {tuple(known.shape)}')
+    rows = known.shape[0]
+    for name, v, dt in (('x_new', x_new, torch.float32), ('mask', mask, torch.uint8), ('noise', noise, torch.float32), ('out', out, torch.float32)):
+        if v is not None and (v.dtype != dt or v.shape != known.shape):
+            raise MudiffHipError(f'known_constrain: {name} must be {dt} of shape {tuple(known.shape)}, got {v.dtype} {tuple(v.shape)}')
+    if mask is not None and x_new is None:
+        raise MudiffHipError('known_constrain: x_new may be None only without a mask')
+    if out is not None and not out.is_contiguous():
+        raise MudiffHipError('known_constrain: out must be contiguous')
+    known = known if known.is_contiguous() or out is known else known.contiguous()
+    x_new = x_new if x_new is None or x_new.is_contiguous() or out is x_new else x_new.contiguous()
+    mask, noise = (None if v is None else v.contiguous() for v in (mask, noise))
+    kd = None
+    if not clean:
+        if t is None or a_tab is None or s_tab is None or t.dtype != torch.int64 or t.numel() != rows or a_tab.numel() != s_tab.numel():
+            raise MudiffHipError('known_constrain: need t (int64 [rows]) and two tables of one length')
+        t, a_tab, s_tab = t.contiguous(), _f32(a_tab.contiguous()), _f32(s_tab.contiguous())
+        if noise is None:
+            if keys is None:
+                raise MudiffHipError('known_constrain: pass noise or keys')
+            k = check_keys(keys)
+            if k.shape[0] != rows:
+                raise MudiffHipError(f'known_constrain: {k.shape[0]} keys for {rows} rows')
+            kd = k.to(known.device)
+    out = torch.empty(known.shape, device=known.device, dtype=torch.float32) if out is None else out
+    return known_constrain_into(out, x_new, known, mask, kd, _seed64(seed), step, kind, t, toff, a_tab, s_tab, clean, noise)
+
+
+def known_coverage(M, src_shape, out_shape, device=None):
+    """uint8 [Z, Y, X] on `device`: 1 where the voxel of the grid `out_shape` = (X, Y, Z) maps through M (volume_regrid.grid_matrix: 3 x 4
+    or 4 x 4) to a source coordinate inside [0, S - 1] on all three axes of `src_shape` = (SX, SY, SZ): interpolated from acquired voxels
+    alone (mud_known_coverage)."""
+    m = np.ascontiguousarray(np.asarray(M, np.float64)[:3, :4])
+    if m.shape != (3, 4):
+        raise ValueError(f'known_coverage: need a 3 x 4 or 4 x 4 matrix, got {np.shape(M)}')
+    SX, SY, SZ = (int(v) for v in src_shape)
+    X, Y, Z = (int(v) for v in out_shape)
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    out = torch.empty(max(Z, 0), max(Y, 0), max(X, 0), device=dev, dtype=torch.uint8)
+    _launch('known_coverage', dev, load().mud_known_coverage, (C.c_double * 12)(*m.reshape(-1).tolist()), SX, SY, SZ, X, Y, Z, ptr(out), STREAM,
+            nbytes=float(out.numel()))
+    return out
+
+
 # columns of volume_through_plane's sums (include/mudiff_hip.h: MUD_TP_*)
 TP_N_DZ, TP_S_DZ, TP_N_DZZ, TP_S_DZZ, TP_N_DX, TP_S_DX, TP_N_DY, TP_S_DY = range(8)
 TP_NQ, TP_PARTS = 8, 16

@@ -246,19 +246,44 @@ class GraphSampler:
         out = self.x.clone()
         return (out, steps) if return_steps else out
 
-    def sample_keyed(self, cond1, cond2, cond3, keys, seed, n_time, coupling=None):
+    def sample_keyed(self, cond1, cond2, cond3, keys, seed, n_time, coupling=None, known=None, known_mask=None, resample=1):
         """sample() with keyed draws (DESIGN.md section 5.7): row r of the batch is sample keys[r] = (slice, sample) of an ensemble;
         x_init (kind 0, step 0) and every executed step k's z (kind 1) and posterior noise (kind 2) are drawn with ops.randn_keyed
         on this device's current stream, so each row's result depends on (seed, its key) alone.  keys: int64 [B, 2] (host or device).
         `coupling` (mudiff_hip.slice_coupling): None; 'shared' = every row draws with slice key 0, so rows of one
         sample index get identical draws; (half_taps, R) = every draw is ops.randn_keyed_coupled's, the white noise of the slices
-        slice-R..slice+R under those weights."""
+        slice-R..slice+R under those weights.
+        `known`, `known_mask`: the target where it was acquired, [B,1,H,W] in [-1,1], and uint8 [B,1,H,W], non-zero =
+        known.  After the step executed with t = i the result is at the level of q_sample(., t=i), so the known voxels are replaced by
+        a_s_cum[i] * known + sigmas_cum[i] * eta (ops.known_constrain, kind KIND_KNOWN) for i > 0 and by `known` itself for i = 0, where the
+        posterior adds no noise: the known voxels of the result are the known values bit for bit, and the free region was sampled
+        conditioned on them.  The captured graphs are the same; the constraint runs between replays, in place of the copy into x.
+        `resample` = R > 1 (RePaint's resampling with jump length 1): every step is executed R times; after each of the first R - 1 the
+        constrained x is taken back one level, x <- a_s[i+1] * x + sigmas[i+1] * eta' (kind KIND_RENOISE), and the step runs again with fresh
+        z and posterior noise.  The step word of every draw is the running count of executed steps, so no two draws share a key.  The
+        KIND_KNOWN and KIND_RENOISE draws always use the row's true (slice, sample) key and are never slice-coupled: `coupling` acts on
+        kinds 0..2 only.  Without `known` the result is what it was before these arguments existed."""
         from .slice_coupling import SHARED, check_coupling
         coupling = check_coupling(coupling)
         k = ops.check_keys(keys)
         if k.shape[0] != self.B:
             raise ValueError(f'GraphSampler.sample_keyed: {k.shape[0]} keys for a batch of {self.B}')
         seed = ops._seed64(seed)
+        resample = int(resample)
+        if resample < 1:
+            raise ValueError(f'GraphSampler.sample_keyed: resample must be >= 1, got {resample}')
+        if known is None and (known_mask is not None or resample != 1):
+            raise ValueError('GraphSampler.sample_keyed: known_mask and resample need known')
+        if known is not None:
+            if known_mask is None:
+                raise ValueError('GraphSampler.sample_keyed: known needs known_mask')
+            if tuple(known.shape) != tuple(self.x.shape) or tuple(known_mask.shape) != tuple(self.x.shape) or known_mask.dtype != torch.uint8:
+                raise ValueError(f'GraphSampler.sample_keyed: known (fp32) and known_mask (uint8) must be {tuple(self.x.shape)}, got '
+                                 f'{tuple(known.shape)} and {known_mask.dtype} {tuple(known_mask.shape)}')
+            known = known.to(self.x.device, torch.float32).contiguous()
+            known_mask = known_mask.to(self.x.device).contiguous()
+            dc = self._diffusion_tables()
+            k_true = k.to(self.x.device)
         if coupling == SHARED:
             k = k.clone()
             k[:, 0] = 0
@@ -270,15 +295,31 @@ class GraphSampler:
             draw = lambda out, step, kind: ops.randn_keyed_coupled_into(out, kd, seed, step, kind, taps, radius)      # noqa: E731
         self.c1.copy_(cond1); self.c2.copy_(cond2); self.c3.copy_(cond3)
         draw(self.x, 0, ops.KIND_X_INIT)
-        for k_, i in enumerate(reversed(range(n_time))):
+        step = 0                                      # the running count of executed steps: the step word of every draw
+        for i in reversed(range(n_time)):
             self.t.fill_(i)
-            draw(self.z, k_, ops.KIND_Z)
-            draw(self.noise, k_, ops.KIND_NOISE)
-            if k_ == 0:
-                self.graph.replay()
-                x_new = self._first_out[2]
-            else:
-                self.graph_rest.replay()
-                x_new = self._rest_out[2]
-            self.x.copy_(x_new)
+            for j in range(resample):
+                draw(self.z, step, ops.KIND_Z)
+                draw(self.noise, step, ops.KIND_NOISE)
+                if step == 0:
+                    self.graph.replay()
+                    x_new = self._first_out[2]
+                else:
+                    self.graph_rest.replay()
+                    x_new = self._rest_out[2]
+                if known is None:
+                    self.x.copy_(x_new)
+                else:
+                    ops.known_constrain_into(self.x, x_new, known, known_mask, k_true, seed, step, ops.KIND_KNOWN, self.t, 0, dc[0], dc[1],
+                                             clean=i == 0)
+                    if j < resample - 1:              # back one level, everywhere (mask None), then the same step again
+                        ops.known_constrain_into(self.x, None, self.x, None, k_true, seed, step, ops.KIND_RENOISE, self.t, 1, dc[2], dc[3])
+                step += 1
         return self.x.clone()
+
+    def _diffusion_tables(self):
+        """(a_s_cum, sigmas_cum, a_s, sigmas) of Diffusion_Coefficients(opt) as fp32 on this sampler's device, built once."""
+        if getattr(self, '_diff', None) is None:
+            d = Diffusion_Coefficients(self.opt, self.x.device)
+            self._diff = tuple(v.float().contiguous() for v in (d.a_s_cum, d.sigmas_cum, d.a_s, d.sigmas))
+        return self._diff

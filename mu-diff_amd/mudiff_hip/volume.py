@@ -291,7 +291,7 @@ def calibrate_volume(args, gen1, gen2, cond_stacks, device, batch_size=32):
 
 
 def predict_slices(args, gen1, gen2, cond_stacks, device, batch_size=32, x_inits=None, zs=None, noises=None, seed=None,
-                   use_graph=True, progress=None, sampler=None, return_device=False, coupling=None):
+                   use_graph=True, progress=None, sampler=None, return_device=False, coupling=None, known=None, resample=1):
     """cond_stacks: three float arrays [n,X,Y] in [-1,1] (the condition contrasts, already normalised and sliced), or three device
     tensors [n,1,S,S] (volume_intake.condition_from_raw).  -> [n,S,S] float32 numpy in [0,1], S = args.image_size; with `return_device`
     the device tensor instead (no copy to the host).
@@ -305,7 +305,10 @@ def predict_slices(args, gen1, gen2, cond_stacks, device, batch_size=32, x_inits
     `coupling` (--slice_coupling; mudiff_hip.slice_coupling): None, 'shared' or (half_taps, R).  With one the
     draws no longer come from the torch generator: every batch is sampled through GraphSampler.sample_keyed with the keys (global slice,
     sample 0) and `seed` (required, in [0, 2^64)), so neighbouring slices share part of their noise and the result still does not depend
-    on the batch size.  Injected draws together with a coupling raise ValueError."""
+    on the batch size.  Injected draws together with a coupling raise ValueError.
+    `known` (--known_volume; mudiff_hip.known_region): None, or (known [n,1,S,S] in [-1,1], mask uint8 [n,1,S,S])
+    on the device, with `resample` what GraphSampler.sample_keyed takes: the same keyed road, a padded row repeating the last slice's
+    known stack and mask; it needs a seed and the captured sampler as a coupling does (ValueError otherwise)."""
     from . import ops
     from . import sampling as S
     from .slice_coupling import check_coupling
@@ -315,6 +318,12 @@ def predict_slices(args, gen1, gen2, cond_stacks, device, batch_size=32, x_inits
             raise ValueError('predict_slices: injected x_inits / zs / noises cannot be combined with a coupling (its draws are keyed)')
         if seed is None or not use_graph:
             raise ValueError('predict_slices: a coupling needs a seed and the captured sampler (use_graph=True)')
+    if known is not None:
+        if x_inits is not None or zs is not None or noises is not None:
+            raise ValueError('predict_slices: injected x_inits / zs / noises cannot be combined with a known region (its draws are keyed)')
+        if seed is None or not use_graph:
+            raise ValueError('predict_slices: a known region needs a seed and the captured sampler (use_graph=True)')
+    keyed = coupling is not None or known is not None
     n = int(cond_stacks[0].shape[0])
     size = int(args.image_size)
     if n == 0:
@@ -322,7 +331,7 @@ def predict_slices(args, gen1, gen2, cond_stacks, device, batch_size=32, x_inits
     conds = upload_conds(cond_stacks, size, device)
     coef = S.Posterior_Coefficients(args, device)
     gen = None
-    if seed is not None and coupling is None:
+    if seed is not None and not keyed:
         gen = torch.Generator(device=device).manual_seed(int(seed))
     T = int(args.num_timesteps)
     bs = min(int(batch_size), n)
@@ -351,9 +360,10 @@ def predict_slices(args, gen1, gen2, cond_stacks, device, batch_size=32, x_inits
     for lo in range(0, n, bs):
         hi = min(lo + bs, n)
         c1, c2, c3 = (padded(c, lo, hi) for c in conds)
-        if coupling is not None:
+        if keyed:
             keys = torch.stack([torch.arange(lo, lo + bs).clamp_(max=hi - 1), torch.zeros(bs, dtype=torch.int64)], 1)
-            out[lo:hi] = ops.to_range_0_1(sampler.sample_keyed(c1, c2, c3, keys, seed, T, coupling=coupling))[:hi - lo, 0]
+            more = {} if known is None else dict(known=padded(known[0], lo, hi), known_mask=padded(known[1], lo, hi), resample=resample)
+            out[lo:hi] = ops.to_range_0_1(sampler.sample_keyed(c1, c2, c3, keys, seed, T, coupling=coupling, **more))[:hi - lo, 0]
             if progress:
                 progress(hi, n)
             continue
@@ -383,10 +393,15 @@ def predict_volume(args):
     neighbouring slices (predict_slices' `coupling`); --through_plane adds through_plane_<target>.json and one [through-plane] line
     after the scores (mudiff_hip.volume_through_plane).  With --num_samples, --ensemble_quantiles writes per-voxel quantile maps of the
     samples next to the mean and the std, --ensemble_center median makes the median the written and scored prediction, and --coverage
-    counts how often the ground truth lies between two of the maps (mudiff_hip.ensemble, mudiff_hip.volume_coverage)."""
+    counts how often the ground truth lies between two of the maps (mudiff_hip.ensemble, mudiff_hip.volume_coverage).  --known_volume keeps
+    the acquired part of the target: it conditions the sampling and is pasted into every written map, known_<target>.json goes next to the
+    prediction and the scores gain the regions known / synthesised (mudiff_hip.known_region)."""
     evaluation, resampled, found = _load_eval_inputs(args)
     args = copy.copy(args)                               # the run's own copy: it carries the record of what the intake did
     args.evaluation_record = (resampled, found)          # (for _predict_volume's report: IntakeReport.add_evaluation)
+    args.known_inputs = _load_known_inputs(args, found)  # (--known_volume: K and M on the prediction's grid, checked, or None)
+    if args.known_inputs is not None:
+        args.evaluation_record = (resampled + list(args.known_inputs.resampled), found)
     from . import ops
     from .driver import effective_prec_plan
     plan = effective_prec_plan(args)
@@ -429,11 +444,29 @@ def _load_eval_inputs(args):
                                 wording=lambda e: f'--gt_volume / --eval_mask: {e} (the prediction has the shape of {first})')
 
 
+def _load_known_inputs(args, found):
+    """--known_volume / --known_mask -> None, or known_region.KnownInputs: the files read and put on the grid the prediction will have
+    (known_region.on_grid), before any checkpoint work.  A bad flag or shape raises ValueError here.  `found`: _load_eval_inputs' (its
+    alignment, when it has one, is used)."""
+    from . import known_region as KR
+    known = KR.options_from(args)
+    if known is None:
+        return None
+    from . import volume_prepare as VP
+    _, first = _needed_inputs(args)[0]
+    options = VP.IntakeOptions.from_args(args)
+    return KR.on_grid(VP.read_for_evaluation(first, options), KR.read_inputs(known, options), known, options,
+                      torch.device(f'cuda:{args.gpu_chose}'), align=found.get('align'))
+
+
 def _score_prediction(args, evaluation, vol, std_vol, device):
     """Scores of the prediction exactly as written -> printed lines and <output_dir>/metrics_<target>.json (its path)."""
     from . import volume_metrics as VM
     gt, label = evaluation
-    rep = VM.score_arrays(vol, gt, label, std_vol, args.slice_half_range, device, norm=args.norm)
+    region = getattr(args, 'known_region', None)         # (--known_volume: the regions `known` and `synthesised` as well)
+    from . import known_region as KR
+    more = {} if region is None else dict(more_regions=lambda s0, s1, bit: (KR.region_bits(region, s0, s1, bit), KR.REGION_NAMES))
+    rep = VM.score_arrays(vol, gt, label, std_vol, args.slice_half_range, device, norm=args.norm, **more)
     for ln in VM.format_lines(rep):
         print(ln)
     path = VM.write_json(rep, os.path.join(args.output_dir, f'metrics_{args.target_modality.lower()}.json'))
@@ -496,9 +529,10 @@ def _done_tail(args, plan):
     """What a [done] line ends in: the arithmetic plan, --norm, what the intake did, --slice_coupling and the ensemble's centre and
     quantiles, each only when it is not the default."""
     from .ensemble import done_suffix
+    from .known_region import suffix as known_suffix
     from .slice_coupling import suffix
     return (('' if plan == 'auto' else f' | prec_plan={plan}') + norm_suffix(args.norm) + _intake_report(args).suffix() +
-            suffix(getattr(args, 'slice_coupling', None)) + done_suffix(args))
+            suffix(getattr(args, 'slice_coupling', None)) + done_suffix(args) + known_suffix(getattr(args, 'known_region', None)))
 
 
 class _Stages:
@@ -541,13 +575,14 @@ def predict_from_conditions(args, plan, evaluation, gen1, gen2, device, stacks, 
             from .driver import write_calibration
             print(f'[calibrate] {cal.summary()}')
             print(f'[calibrate] wrote {write_calibration(cal, args.output_dir)}')
+    region, known = _known_region(args, ref, device)
     if args.num_samples is not None:
-        return _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref, evaluation, on_device, samplers, write, stages)
+        return _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref, evaluation, on_device, samplers, write, stages, region, known)
     n = int(stacks[0].shape[0])
     sampler = _cached_sampler(args, gen1, gen2, device, samplers, min(int(args.batch_size), n)) if n else None
     pred = stages.run('sample', lambda: predict_slices(args, gen1, gen2, stacks, device, batch_size=args.batch_size, seed=args.seed,
                                                        progress=lambda d, n: print(f'[infer] processed {d}/{n} slices'), sampler=sampler,
-                                                       return_device=on_device, coupling=_coupling(args)))
+                                                       return_device=on_device, coupling=_coupling(args), **known))
     if on_device:
         def put_together():
             from . import ops
@@ -562,6 +597,10 @@ def predict_from_conditions(args, plan, evaluation, gen1, gen2, device, stacks, 
         vol_pred = reconstruct_volume_from_slices(list(pred), shp, s0, s1)
     os.makedirs(args.output_dir, exist_ok=True)
     out_path = os.path.join(args.output_dir, f'predicted_{args.target_modality.lower()}.nii.gz')
+    if region is not None:
+        from . import known_region as KR
+        vol_pred = stages.run('assemble', lambda: KR.paste(vol_pred, region, device))      # the acquired voxels, exactly, in what is written
+        KR.write_json(region, args.output_dir, args.target_modality)
     stages.run('write', lambda: write(out_path, vol_pred, aff, hdr))
     _intake_report(args).write(args.output_dir, args.target_modality, aff, hdr)
     print(f'[done] saved: {out_path} | shape={tuple(vol_pred.shape)} | slices={s0}..{s1}' + _done_tail(args, plan))
@@ -569,6 +608,18 @@ def predict_from_conditions(args, plan, evaluation, gen1, gen2, device, stacks, 
         _score_prediction(args, evaluation, vol_pred, None, device)
     _through_plane(args, evaluation, vol_pred, device)
     return out_path
+
+
+def _known_region(args, ref, device):
+    """--known_volume: (the run's known_region.KnownRegion, also left in args.known_region for the [done] line and the scores; what
+    predict_slices and sample_ensemble take for it) - or (None, {}) without the flag."""
+    inputs = getattr(args, 'known_inputs', None)
+    args.known_region = None
+    if inputs is None:
+        return None, {}
+    from . import known_region as KR
+    region = args.known_region = KR.compose(inputs, ref, args.norm, device)
+    return region, dict(known=KR.sampler_inputs(region, ref[3], ref[4], int(args.image_size), device), resample=region.resample)
 
 
 def _coupling(args):
@@ -605,13 +656,14 @@ def _cached_sampler(args, gen1, gen2, device, samplers, batch):
 
 
 def _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref, evaluation=None, on_device=False, samplers=None, write=None,
-                             stages=None):
+                             stages=None, region=None, known=None):
     """--num_samples: every slice sampled N times with draws keyed by (--seed, slice, sample) (mudiff_hip.ensemble); the mean and
     the std of the [0,1]-mapped samples, resized back and re-assembled like the single prediction, go to predicted_<t>.nii.gz and
     predicted_<t>_std.nii.gz.  With `evaluation` the mean is scored, the std feeding the uncertainty block.  -> (mean path, std path).
     Under --ensemble_quantiles / --ensemble_center median / --coverage (ensemble.quantile_plan) the per-voxel
     quantile maps take the same road to predicted_<t>_q<PPP>.nii.gz, the median replaces the mean as the centre, and coverage_<t>.json
-    follows the scores."""
+    follows the scores.  `region`, `known` (--known_volume): _known_region's pair; every written map then carries the acquired voxels
+    (the std: 0 there)."""
     from . import ensemble, ops
     from .driver import effective_prec_plan
     shp, aff, hdr, s0, s1 = ref
@@ -622,9 +674,10 @@ def _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref, evaluation=N
     stages = stages or _Stages(None, device)
     sampler = _cached_sampler(args, gen1, gen2, device, samplers, args.batch_size)
     qplan = ensemble.quantile_plan(args)
+    known = known or {}                                              # (--known_volume: predict_from_conditions' region and sampler inputs)
     res = stages.run('sample', lambda: ensemble.sample_ensemble(args, gen1, gen2, conds, args.num_samples, args.seed,
                                                                 batch_size=args.batch_size, map_0_1=True, sampler=sampler,
-                                                                coupling=_coupling(args), quantiles=qplan and qplan.computed))
+                                                                coupling=_coupling(args), quantiles=qplan and qplan.computed, **known))
     mean, std = res[:2]
     qmaps = list(res[2]) if qplan is not None else []                # one [n,S,S] map per computed fraction
     os.makedirs(args.output_dir, exist_ok=True)
@@ -639,6 +692,11 @@ def _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref, evaluation=N
         vols = [reconstruct_volume_from_slices(list(t.cpu().numpy()), shp, s0, s1) for t in (mean, std)]
         qvols = [reconstruct_volume_from_slices(list(t.cpu().numpy()), shp, s0, s1) for t in qmaps]
     quantile_vols = {} if qplan is None else dict(zip(qplan.computed, qvols))
+    if region is not None:                                           # the acquired voxels, exactly, in every map that is written; std 0 there
+        from . import known_region as KR
+        vols = [stages.run('assemble', lambda v=v, k=k: KR.paste(v, region, device, std=k == 1)) for k, v in enumerate(vols)]
+        quantile_vols = {q: stages.run('assemble', lambda v=v: KR.paste(v, region, device)) for q, v in quantile_vols.items()}
+        KR.write_json(region, args.output_dir, args.target_modality)
     if qplan is not None and qplan.center == 'median':
         vols[0] = quantile_vols[0.5]                                 # the centre: what is written, scored and measured from here on
     paths = []
@@ -765,6 +823,8 @@ def make_parser(prog='MU-Diff volume prediction (MI355X)'):
     add_calibration_flags(p)                # (also --prec_plan)
     from . import slice_coupling
     slice_coupling.add_flags(p)             # (--slice_coupling, --through_plane: in a late parser, VolumeParser.later())
+    from . import known_region
+    known_region.add_flags(p)               # (--known_volume and its three: in one of their own, before the last)
     from . import ensemble
     ensemble.add_flags(p)                   # (--ensemble_quantiles, --ensemble_center, --coverage: in a further one)
     return p
@@ -787,6 +847,11 @@ def finish_args(p, args):
     from . import ensemble
     try:
         ensemble.quantile_plan(args)                     # (its ValueError names the flag)
+    except ValueError as e:
+        p.error(str(e))
+    from . import known_region
+    try:
+        known_region.options_from(args)                  # (its ValueError names the flag)
     except ValueError as e:
         p.error(str(e))
     from . import volume_conform as VCF
@@ -814,7 +879,8 @@ def build_argparser(argv=None):
     (mudiff_hip.driver), and the flags of every input stage, each added and checked by the stage's own module (volume_prepare.STAGES;
     DESIGN.md sections 5.12 - 5.22; --align's flags sit in VolumeParser.late), and --slice_coupling / --through_plane (mudiff_hip.slice_coupling,
     DESIGN.md section 5.23; in a further late parser), and --ensemble_quantiles / --ensemble_center / --coverage (mudiff_hip.ensemble,
-    mudiff_hip.volume_coverage; in one more)."""
+    mudiff_hip.volume_coverage; in one more), and --known_volume / --known_mask / --known_drop_slices /
+    --known_resample (mudiff_hip.known_region; in a parser of their own before that last one)."""
     p = make_parser()
     return finish_args(p, p.parse_args(argv))
 

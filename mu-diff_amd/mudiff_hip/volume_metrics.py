@@ -208,10 +208,12 @@ def score_volume(pred, gt, region, std=None, names=REGIONS, first_plane=0):
     return rep
 
 
-def score_arrays(pred_vol, gt_raw, label=None, std_vol=None, slice_half_range=80, device='cuda', norm='percentile'):
+def score_arrays(pred_vol, gt_raw, label=None, std_vol=None, slice_half_range=80, device='cuda', norm='percentile', more_regions=None):
     """Scores of a prediction as written (host [X, Y, Z] array in [0, 1]) against the raw GT volume, with an optional label volume
     (regions tumor / healthy) and std volume.  `norm`: how the GT is mapped to [-1, 1] (volume.NORMS; the mode the prediction's inputs
-    were normalised with).  -> score_volume's report plus shape and slab [s0, s1], and the key norm when it is not the default."""
+    were normalised with).  `more_regions(s0, s1, first_bit)` -> (uint8 [planes, X, Y] bits from first_bit on, their names): further regions
+    next to region_mask's (mudiff_hip.known_region: known, synthesised).  -> score_volume's report plus shape and slab [s0, s1], and the
+    key norm when it is not the default."""
     from . import ops
     from .volume import normalise_volume
     s0, s1 = check_shapes(np.shape(pred_vol), np.shape(gt_raw), None if label is None else np.shape(label), slice_half_range,
@@ -222,6 +224,9 @@ def score_arrays(pred_vol, gt_raw, label=None, std_vol=None, slice_half_range=80
     pred = torch.from_numpy(slab_planes(pred_vol, s0, s1)).to(device)
     std = None if std_vol is None else torch.from_numpy(slab_planes(std_vol, s0, s1)).to(device)
     m, names = region_mask(slab_planes(gt_raw, s0, s1, np.float64), None if label is None else slab_planes(label, s0, s1, np.float64))
+    if more_regions is not None:
+        bits, more = more_regions(s0, s1, len(names))
+        m, names = m | np.asarray(bits, np.uint8), tuple(names) + tuple(more)
     rep = score_volume(pred, gt, torch.from_numpy(m).to(device), std, names, first_plane=s0)
     extra = {} if norm == 'percentile' else dict(norm=norm)
     return dict(shape=[int(v) for v in np.shape(gt_raw)], slab=[s0, s1], **extra, **rep)

@@ -130,6 +130,16 @@ def evaluation_inputs(first, gt, label, options, device, names, wording, align=N
     for the caller to hand to prepare_inputs, so that a subject's plane is estimated once.  -> ((gt, label), the names of what was resampled, `found` of
     volume_regrid.eval_onto_grid): IntakeReport.add_evaluation takes the last two."""
     from . import volume_metrics as VM
+    grid, gt, label, gt_affine, resample, found = evaluation_grid(first, gt, label, options, device, align)
+    evaluation, resampled = VM.eval_inputs_on_grid(grid, gt, label, gt_affine, resample, options.half_range, device, names=names, wording=wording,
+                                                   interp=options.interp, found=found, **(dict(antialias=True) if options.antialias else {}))
+    return evaluation, resampled, found
+
+
+def evaluation_grid(first, gt, label, options, device, align=None):
+    """The first half of evaluation_inputs, for a caller that resamples by itself (mudiff_hip.known_region): -> (grid = (shape, affine,
+    header) the prediction will have, gt and label reoriented where --reorient asks for it, the ground truth's affine, whether what is
+    not on the grid is to be resampled onto it, `found` with the alignment under --align)."""
     geometry = lambda v: (v.shape, v.affine, v.header) if hasattr(v, 'header') else (v[0].shape, v[1], v[2])      # noqa: E731
     grid, gt_affine = geometry(first), geometry(gt)[1]
     if not options.eval_as_stored:
@@ -144,9 +154,7 @@ def evaluation_inputs(first, gt, label, options, device, names, wording, align=N
     if options.align is not None:
         found['align'] = align = align or estimate_alignment(first, options, device)
         grid = (grid[0], aligned_affine(align[0], grid[1]), None)
-    evaluation, resampled = VM.eval_inputs_on_grid(grid, gt, label, gt_affine, resample, options.half_range, device, names=names, wording=wording,
-                                                   interp=options.interp, found=found, **(dict(antialias=True) if options.antialias else {}))
-    return evaluation, resampled, found
+    return grid, gt, label, gt_affine, resample, found
 
 
 def output_writer(write, first_raw, options, ref, device, reorient_back=False, conform_back=False):
