@@ -342,7 +342,8 @@ int mud_lpips_u8(const uint8_t* pred, const uint8_t* gt, int n, int H, int W, co
  * Philox4x64-10 (numpy.random.Philox's algorithm and word order) with key (seed, 0x4D55444946460001) and counter
  * (e/4, s, (j << 32) | (step << 8) | kind, 0); lane l = e % 4 takes the word pair (w[2(l/2)], w[2(l/2)+1]) = (wa, wb),
  * u1 = ((wa >> 11) + 1) 2^-53, u2 = (wb >> 11) 2^-53, r = sqrt(-2 log u1), theta = 2 pi u2: r cos theta (even l), r sin theta (odd l),
- * in fp64, rounded once to fp32.  kind: 0 x_init, 1 z, 2 posterior noise; step in [0, 2^24); row_len > 0.
+ * in fp64, rounded once to fp32.  kind: 0 x_init, 1 z, 2 posterior noise, or 5: the draw of mud_kspace_constrain, so that a caller can
+ * inject what that entry draws (3 and 4, mud_known_constrain's, stay refused); step in [0, 2^24); row_len > 0.
  * mud_ensemble_stats: samples [n][N][hw] -> mean, std [n][hw] (N >= 2, hw > 0): y = clamp(x*scale + shift, lo, hi) in fp32 (each step
  * rounded once, NaN kept), m = (sum_j y_j) / N and v = sum_j (y_j - m)^2 / (N - 1) in fp64 in sample order j = 0..N-1,
  * mean = (float)m, std = (float)sqrt(v); a NaN sample gives NaN in both.  No atomics: a fixed function of the samples. */
@@ -424,6 +425,32 @@ int mud_known_constrain(const float* x_new, const float* known, const uint8_t* m
                         int step, int kind, const int64_t* t, int toff, const float* a_tab, const float* s_tab, int ntab, int clean,
                         float* out, int rows, int64_t row_len, void* stream);
 int mud_known_coverage(const double* m, int SX, int SY, int SZ, int X, int Y, int Z, uint8_t* out, void* stream);
+
+/* ---- sampling a target acquired undersampled in k-space (mudiff_hip.kspace; GraphSampler.sample_keyed(kspace=)).
+ * F is the unitary 2D DFT of an S x S slice: F(x)[u][v] = (1/S) sum_{j,k} x[j][k] exp(-2 pi i (u j + v k) / S), DC at [0][0], S a power of
+ * two in [16, 512]; the scale 1/S is an exact power of two.  Complex data is interleaved (re, im) fp32, the layout of torch.complex64.
+ * Radix-4 passes (and one radix-2 layer when log2 S is odd) in LDS with twiddles correctly rounded from fp64; every product and sum is
+ * rounded once (no contraction); no atomics; a slice's result depends on that slice's operands alone, not on the batch around it.
+ * mud_fft2_c2c: out[r] = F(in[r]) (inverse != 0: F^H) for rows slices [rows][S][S]; in place (out == in) is allowed.  Two launches.
+ * mud_fft2_r2c: the same with `in` real fp32 [rows][S][S]: the bits of mud_fft2_c2c on (in, 0).  Not in place.
+ * mud_kspace_constrain: the data-consistency step for measurements y = mask .* F(k).  With c = clamp(t[r] + toff, 0, ntab - 1),
+ *   out[r] = x_new[r] - Re F^H[ mask ? F(x_new[r] - s_tab[c] * eta[r]) - a_tab[c] * y[r] : 0 ]
+ * and with clean != 0  out[r] = x_new[r] - Re F^H[ mask ? F(x_new[r]) - y[r] : 0 ]  (nothing drawn: t, the tables, noise and keys may be
+ * NULL).  Where the mask is 0 the residual is an exact 0, and a correction that is 0 leaves x_new's bits: an all-zero mask returns x_new
+ * bit for bit.  y: complex [rows][S][S]; mask: uint8 [mask_rows][S][S], non-zero = measured, mask_rows 1 (shared) or rows; work: a
+ * complex workspace [rows][S][S] of the caller's, overwritten.  eta is `noise` [rows][S][S] when given, else the value mud_randn_keyed
+ * gives element e of a row of S * S elements keyed keys[2r..2r+1] under (seed, step, kind) - counter words (e / 4, slice, sample << 32 |
+ * step << 8 | kind, 0), drawn in the kernel by the thread that loads elements 4b..4b+3; kind in [0, 15] (mudiff_hip.ops.KIND_KSPACE =
+ * 5 is this entry's), step in [0, 2^24).  out may be x_new.  Three launches: rows forward (d = x_new - s * eta fused into the load),
+ * columns forward -> residual -> columns inverse inside LDS, rows inverse (out = x_new - Re(.) fused into the store).
+ * MUD_ERR_ARG before any launch for an S that is not a power of two in [16, 512], rows <= 0 or rows * S * S >= 2^31, mask_rows outside
+ * {1, rows}, ntab <= 0, a kind or step out of range, a null pointer that is needed, neither noise nor keys, x_new / out / noise not
+ * 16-byte aligned, and a work that is one of the other operands. */
+int mud_fft2_c2c(const float* in, float* out, int rows, int S, int inverse, void* stream);
+int mud_fft2_r2c(const float* in, float* out, int rows, int S, int inverse, void* stream);
+int mud_kspace_constrain(const float* x_new, const float* y, const uint8_t* mask, int mask_rows, const float* noise, const int64_t* keys,
+                         uint64_t seed, int step, int kind, const int64_t* t, int toff, const float* a_tab, const float* s_tab, int ntab,
+                         int clean, float* out, float* work, int rows, int S, void* stream);
 
 /* ---- through-plane roughness of a volume (mudiff_hip.volume_through_plane; the volume pipeline's --through_plane).
  * vol (fp32) and the optional mask (uint8, may be NULL: every voxel is inside; else non-zero is inside) are [Z, X, Y] with planes

@@ -45,7 +45,7 @@ def premap(map_0_1):
 
 
 def sample_ensemble(args, gen1, gen2, conds, num_samples, seed, batch_size=32, slice_offset=0, chunk=None, sampler=None, map_0_1=False,
-                    return_samples=False, coupling=None, quantiles=None, known=None, resample=1):
+                    return_samples=False, coupling=None, quantiles=None, known=None, resample=1, kspace=None):
     """conds: three device tensors [n,1,S,S] (S = args.image_size) -> (mean, std) device fp32 [n,S,S] over `num_samples` (>= 2) samples
     per slice, plus the raw samples [n,N,S,S] with `return_samples`.  `map_0_1`: the statistics are those of the samples mapped to
     [0,1] (ops.to_range_0_1); the returned samples are never mapped.
@@ -59,8 +59,12 @@ def sample_ensemble(args, gen1, gen2, conds, num_samples, seed, batch_size=32, s
     samples under the same pre-map (ops.ensemble_quantiles; 0.5 is the median), taken from the chunk buffer right
     after the statistics, are returned as one more tensor [K,n,S,S] at the end of the tuple.  None returns exactly what it did before.
     `known`, `resample` (mudiff_hip.known_region): None, or (known [n,1,S,S], mask uint8 [n,1,S,S]) per slice on the
-    device: every sample of slice i is drawn with that slice's known region re-imposed (GraphSampler.sample_keyed's known / known_mask)."""
+    device: every sample of slice i is drawn with that slice's known region re-imposed (GraphSampler.sample_keyed's known / known_mask).
+    `kspace` (mudiff_hip.kspace): None, or a kspace.KSpaceMeasurement for these n slices (exclusive with `known`):
+    every sample of slice i keeps that slice's measured coefficients, and each is handed to the measurement's `record`."""
     from . import sampling as S
+    if known is not None and kspace is not None:
+        raise ValueError('sample_ensemble: known and kspace are mutually exclusive')
     N = int(num_samples)
     if N < 2:
         raise ValueError(f'sample_ensemble: num_samples must be >= 2, got {N}')
@@ -109,8 +113,12 @@ def sample_ensemble(args, gen1, gen2, conds, num_samples, seed, batch_size=32, s
             keys = torch.stack([sl + int(slice_offset), items % N], 1)
             idx = sl.to(device)
             more = {} if known is None else dict(known=known[0].index_select(0, idx), known_mask=known[1].index_select(0, idx), resample=resample)
+            if kspace is not None:
+                more = dict(kspace=(kspace.y.index_select(0, idx), kspace.mask.index_select(0, idx)), resample=resample)
             res = sampler.sample_keyed(c1.index_select(0, idx), c2.index_select(0, idx), c3.index_select(0, idx), keys, seed, T, coupling=coupling,
                                        **more)
+            if kspace is not None:
+                kspace.record(idx[:m], res[:m])
             flat[b0 - q0:b0 - q0 + m] = res[:m, 0]
         mean[s0:s1], std[s0:s1] = ops.ensemble_stats(out, scale, shift, lo, hi)
         if qmaps is not None:

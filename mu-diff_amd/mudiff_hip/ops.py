@@ -941,7 +941,8 @@ def randn_keyed(rows_keys, row_len, seed, step, kind, out=None):
     """Keyed standard normals: row r of the fp32 result [rows, row_len] is a pure function of (seed, slice, sample, step, kind) with
     rows_keys[r] = (slice, sample) (int64 [rows, 2], host or device): Philox4x64-10 + Box-Muller in fp64 (mud_randn_keyed).  `out`:
     a contiguous fp32 device tensor of rows * row_len elements to fill (any shape); without it the result lands on rows_keys's device
-    (or the current one for host keys).  kind: KIND_X_INIT, KIND_Z or KIND_NOISE."""
+    (or the current one for host keys).  kind: KIND_X_INIT, KIND_Z or KIND_NOISE (or KIND_KSPACE, to inject what ops.kspace_constrain
+    draws)."""
     k = check_keys(rows_keys)
     seed = _seed64(seed)
     rows, row_len = k.shape[0], int(row_len)
@@ -1064,6 +1065,97 @@ def known_coverage(M, src_shape, out_shape, device=None):
     _launch('known_coverage', dev, load().mud_known_coverage, (C.c_double * 12)(*m.reshape(-1).tolist()), SX, SY, SZ, X, Y, Z, ptr(out), STREAM,
             nbytes=float(out.numel()))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# sampling a target acquired undersampled in k-space (csrc/kspace.hip, mudiff_hip.kspace)
+KIND_KSPACE = 5                      # the draw of mud_kspace_constrain: the measured coefficients' forward noise
+KSPACE_SIZES = (16, 32, 64, 128, 256, 512)
+
+
+def kspace_size_ok(S):
+    """S x S is a grid the k-space kernels take: a power of two in [16, 512]."""
+    return int(S) in KSPACE_SIZES
+
+
+def fft2(x, inverse=False, out=None):
+    """The unitary 2D DFT of every slice of x [rows, S, S] (mud_fft2_c2c / mud_fft2_r2c): DC at [0, 0], scale 1/S; `inverse`: its adjoint.
+    x: complex64, or real fp32 (the bits of the complex transform of (x, 0)).  out: None (a new complex64 tensor), a contiguous complex64
+    tensor of the shape, or x itself for a complex x (in place).  S: a power of two in [16, 512]."""
+    require_gpu(x, out)
+    if x.dtype not in (torch.float32, torch.complex64) or x.dim() != 3 or x.shape[0] < 1 or x.shape[1] != x.shape[2]:
+        raise MudiffHipError(f'fft2: x must be fp32 or complex64 [rows, S, S], got {x.dtype} {tuple(x.shape)}')
+    rows, S = int(x.shape[0]), int(x.shape[1])
+    if not kspace_size_ok(S):
+        raise MudiffHipError(f'fft2: S must be a power of two in [16, 512], got {S}')
+    real = x.dtype == torch.float32
+    if out is not None and (out.dtype != torch.complex64 or out.shape != x.shape or not out.is_contiguous()):
+        raise MudiffHipError(f'fft2: out must be a contiguous complex64 tensor of shape {tuple(x.shape)}, got {out.dtype} {tuple(out.shape)}')
+    x = x if x.is_contiguous() else x.contiguous()
+    out = torch.empty(x.shape, device=x.device, dtype=torch.complex64) if out is None else out
+    fn = load().mud_fft2_r2c if real else load().mud_fft2_c2c
+    _launch('fft2', x.device, fn, ptr(x), ptr(out), rows, S, int(bool(inverse)), STREAM, nbytes=float(x.numel() * (28 if real else 32)))
+    return out
+
+
+def kspace_constrain_into(out, x_new, y, mask, work, keys_dev, seed, step, kind, t, toff, a_tab, s_tab, clean=False, noise=None):
+    """Unchecked launch of mud_kspace_constrain into `out` (fp32, contiguous, [rows, ..., S, S]; may be x_new): GraphSampler.sample_keyed
+    checks its operands once per batch, not once per step.  y, work: complex64 [rows, S, S]; mask: uint8 [1 or rows, S, S]; keys_dev:
+    through check_keys and on out's device (None with `noise` or `clean`)."""
+    rows, S = out.shape[0], out.shape[-1]
+    _launch('kspace_constrain', out.device, load().mud_kspace_constrain, ptr(x_new), ptr(y), ptr(mask), int(mask.shape[0]), ptr(noise), ptr(keys_dev),
+            C.c_uint64(seed), int(step), int(kind), ptr(t), int(toff), ptr(a_tab), ptr(s_tab), 1 if a_tab is None else a_tab.numel(), int(bool(clean)),
+            ptr(out), ptr(work), rows, S, STREAM, nbytes=float(out.numel() * 44))
+    return out
+
+
+def kspace_constrain(x_new, y, mask, t, toff, a_tab, s_tab, *, noise=None, keys=None, seed=0, step=0, kind=KIND_KSPACE, clean=False, out=None,
+                     work=None):
+    """out = x_new - Re F^H[ mask ? F(x_new - s_tab[c] * eta) - a_tab[c] * y : 0 ] per slice, c = clamp(t[row] + toff, 0, len(a_tab) - 1);
+    with `clean`, out = x_new - Re F^H[ mask ? F(x_new) - y : 0 ] (mud_kspace_constrain; F: ops.fft2).  F is unitary, so the measured
+    coefficients of x_new become those of q_sample(k, c) for y = mask * F(k) and the others stay.  x_new: fp32 [rows, S, S] or
+    [rows, 1, S, S]; y: complex64 [rows, S, S]; mask: uint8 [1 or rows, S, S], non-zero = measured (pass a Hermitian-symmetric one, or the
+    real part taken at the end halves the unpaired coefficients' correction).  eta: `noise` (fp32, x_new's shape) when given, else the keyed normal
+    ops.randn_keyed gives keys[r] = (slice, sample) under (seed, step, kind), drawn in the kernel.  t: int64 [rows]; with `clean` it, the
+    tables and the draw are not needed.  out: None (a new tensor), x_new (in place) or a contiguous fp32 tensor of the shape.  work: None
+    or a contiguous complex64 [rows, S, S] workspace (overwritten)."""
+    require_gpu(x_new, y, mask, noise, t, a_tab, s_tab, out, work)
+    if x_new.dtype != torch.float32 or x_new.dim() not in (3, 4) or x_new.shape[0] < 1 or x_new.shape[-1] != x_new.shape[-2] or \
+            (x_new.dim() == 4 and x_new.shape[1] != 1):
+        raise MudiffHipError(f'kspace_constrain: x_new must be fp32 [rows, S, S] or [rows, 1, S, S], got {x_new.dtype} {tuple(x_new.shape)}')
+    rows, S = int(x_new.shape[0]), int(x_new.shape[-1])
+    if not kspace_size_ok(S):
+        raise MudiffHipError(f'kspace_constrain: S must be a power of two in [16, 512], got {S}')
+    if y is None or y.dtype != torch.complex64 or tuple(y.shape) != (rows, S, S):
+        raise MudiffHipError(f'kspace_constrain: y must be complex64 {(rows, S, S)}, got {None if y is None else (y.dtype, tuple(y.shape))}')
+    if mask is None or mask.dtype != torch.uint8 or mask.dim() != 3 or mask.shape[0] not in (1, rows) or tuple(mask.shape[1:]) != (S, S):
+        raise MudiffHipError(f'kspace_constrain: mask must be uint8 [1 or {rows}, {S}, {S}], got '
+                             f'{None if mask is None else (mask.dtype, tuple(mask.shape))}')
+    for name, v in (('noise', noise), ('out', out)):
+        if v is not None and (v.dtype != torch.float32 or v.shape != x_new.shape):
+            raise MudiffHipError(f'kspace_constrain: {name} must be fp32 of shape {tuple(x_new.shape)}, got {v.dtype} {tuple(v.shape)}')
+    if out is not None and not out.is_contiguous():
+        raise MudiffHipError('kspace_constrain: out must be contiguous')
+    if work is not None and (work.dtype != torch.complex64 or tuple(work.shape) != (rows, S, S) or not work.is_contiguous()):
+        raise MudiffHipError(f'kspace_constrain: work must be a contiguous complex64 {(rows, S, S)}, got {work.dtype} {tuple(work.shape)}')
+    x_new = x_new if x_new.is_contiguous() else x_new.contiguous()
+    y, mask = y.contiguous(), mask.contiguous()
+    noise = None if noise is None else noise.contiguous()
+    kd = None
+    if not clean:
+        if t is None or a_tab is None or s_tab is None or t.dtype != torch.int64 or t.numel() != rows or a_tab.numel() != s_tab.numel():
+            raise MudiffHipError('kspace_constrain: need t (int64 [rows]) and two tables of one length')
+        t, a_tab, s_tab = t.contiguous(), _f32(a_tab.contiguous()), _f32(s_tab.contiguous())
+        if noise is None:
+            if keys is None:
+                raise MudiffHipError('kspace_constrain: pass noise or keys')
+            k = check_keys(keys)
+            if k.shape[0] != rows:
+                raise MudiffHipError(f'kspace_constrain: {k.shape[0]} keys for {rows} rows')
+            kd = k.to(x_new.device)
+    out = torch.empty(x_new.shape, device=x_new.device, dtype=torch.float32) if out is None else out
+    work = torch.empty(rows, S, S, device=x_new.device, dtype=torch.complex64) if work is None else work
+    return kspace_constrain_into(out, x_new, y, mask, work, kd, _seed64(seed), step, kind, t, toff, a_tab, s_tab, clean, noise)
 
 
 # columns of volume_through_plane's sums (include/mudiff_hip.h: MUD_TP_*)

@@ -246,7 +246,7 @@ class GraphSampler:
         out = self.x.clone()
         return (out, steps) if return_steps else out
 
-    def sample_keyed(self, cond1, cond2, cond3, keys, seed, n_time, coupling=None, known=None, known_mask=None, resample=1):
+    def sample_keyed(self, cond1, cond2, cond3, keys, seed, n_time, coupling=None, known=None, known_mask=None, resample=1, kspace=None):
         """sample() with keyed draws (DESIGN.md section 5.7): row r of the batch is sample keys[r] = (slice, sample) of an ensemble;
         x_init (kind 0, step 0) and every executed step k's z (kind 1) and posterior noise (kind 2) are drawn with ops.randn_keyed
         on this device's current stream, so each row's result depends on (seed, its key) alone.  keys: int64 [B, 2] (host or device).
@@ -262,7 +262,13 @@ class GraphSampler:
         constrained x is taken back one level, x <- a_s[i+1] * x + sigmas[i+1] * eta' (kind KIND_RENOISE), and the step runs again with fresh
         z and posterior noise.  The step word of every draw is the running count of executed steps, so no two draws share a key.  The
         KIND_KNOWN and KIND_RENOISE draws always use the row's true (slice, sample) key and are never slice-coupled: `coupling` acts on
-        kinds 0..2 only.  Without `known` the result is what it was before these arguments existed."""
+        kinds 0..2 only.  Without `known` the result is what it was before these arguments existed.
+        `kspace` (mudiff_hip.kspace): None, or (y complex64 [B,S,S], mask uint8 [1 or B,S,S]): the target was measured
+        in k-space, y = mask * F(k) with F = ops.fft2.  After the step executed with t = i the measured coefficients of the result are
+        replaced by those of q_sample(k, i): x <- x_new - Re F^H[mask * (F(x_new - sigmas_cum[i] * eta) - a_s_cum[i] * y)] with eta of kind
+        KIND_KSPACE (the row's true key, never slice-coupled), and for i = 0 by y itself (ops.kspace_constrain).  Exclusive with `known`;
+        `resample` and `coupling` act as they do with `known`.  ValueError unless H == W is a size ops.fft2 takes.  The complex workspace
+        is allocated once per sampler."""
         from .slice_coupling import SHARED, check_coupling
         coupling = check_coupling(coupling)
         k = ops.check_keys(keys)
@@ -272,8 +278,25 @@ class GraphSampler:
         resample = int(resample)
         if resample < 1:
             raise ValueError(f'GraphSampler.sample_keyed: resample must be >= 1, got {resample}')
-        if known is None and (known_mask is not None or resample != 1):
-            raise ValueError('GraphSampler.sample_keyed: known_mask and resample need known')
+        if known is not None and kspace is not None:
+            raise ValueError('GraphSampler.sample_keyed: known and kspace are mutually exclusive')
+        if known is None and (known_mask is not None or (resample != 1 and kspace is None)):
+            raise ValueError('GraphSampler.sample_keyed: known_mask and resample need known (resample: or kspace)')
+        if kspace is not None:
+            if self.H != self.W or not ops.kspace_size_ok(self.H):
+                raise ValueError(f'GraphSampler.sample_keyed: kspace needs a square grid whose size is a power of two in [16, 512], got '
+                                 f'{self.H} x {self.W}')
+            ks_y, ks_mask = kspace
+            want = (self.B, self.H, self.W)
+            if ks_y.dtype != torch.complex64 or tuple(ks_y.shape) != want or ks_mask.dtype != torch.uint8 or \
+                    tuple(ks_mask.shape) not in (want, (1,) + want[1:]):
+                raise ValueError(f'GraphSampler.sample_keyed: kspace = (y complex64 {want}, mask uint8 [1 or {self.B}, {self.H}, {self.W}]), got '
+                                 f'{ks_y.dtype} {tuple(ks_y.shape)} and {ks_mask.dtype} {tuple(ks_mask.shape)}')
+            ks_y, ks_mask = ks_y.to(self.x.device).contiguous(), ks_mask.to(self.x.device).contiguous()
+            if getattr(self, '_ks_work', None) is None:
+                self._ks_work = torch.empty(want, device=self.x.device, dtype=torch.complex64)
+            dc = self._diffusion_tables()
+            k_true = k.to(self.x.device)
         if known is not None:
             if known_mask is None:
                 raise ValueError('GraphSampler.sample_keyed: known needs known_mask')
@@ -307,7 +330,12 @@ class GraphSampler:
                 else:
                     self.graph_rest.replay()
                     x_new = self._rest_out[2]
-                if known is None:
+                if kspace is not None:
+                    ops.kspace_constrain_into(self.x, x_new, ks_y, ks_mask, self._ks_work, k_true, seed, step, ops.KIND_KSPACE, self.t, 0, dc[0],
+                                              dc[1], clean=i == 0)
+                    if j < resample - 1:
+                        ops.known_constrain_into(self.x, None, self.x, None, k_true, seed, step, ops.KIND_RENOISE, self.t, 1, dc[2], dc[3])
+                elif known is None:
                     self.x.copy_(x_new)
                 else:
                     ops.known_constrain_into(self.x, x_new, known, known_mask, k_true, seed, step, ops.KIND_KNOWN, self.t, 0, dc[0], dc[1],

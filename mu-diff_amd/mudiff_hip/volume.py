@@ -291,7 +291,7 @@ def calibrate_volume(args, gen1, gen2, cond_stacks, device, batch_size=32):
 
 
 def predict_slices(args, gen1, gen2, cond_stacks, device, batch_size=32, x_inits=None, zs=None, noises=None, seed=None,
-                   use_graph=True, progress=None, sampler=None, return_device=False, coupling=None, known=None, resample=1):
+                   use_graph=True, progress=None, sampler=None, return_device=False, coupling=None, known=None, resample=1, kspace=None):
     """cond_stacks: three float arrays [n,X,Y] in [-1,1] (the condition contrasts, already normalised and sliced), or three device
     tensors [n,1,S,S] (volume_intake.condition_from_raw).  -> [n,S,S] float32 numpy in [0,1], S = args.image_size; with `return_device`
     the device tensor instead (no copy to the host).
@@ -308,11 +308,21 @@ def predict_slices(args, gen1, gen2, cond_stacks, device, batch_size=32, x_inits
     on the batch size.  Injected draws together with a coupling raise ValueError.
     `known` (--known_volume; mudiff_hip.known_region): None, or (known [n,1,S,S] in [-1,1], mask uint8 [n,1,S,S])
     on the device, with `resample` what GraphSampler.sample_keyed takes: the same keyed road, a padded row repeating the last slice's
-    known stack and mask; it needs a seed and the captured sampler as a coupling does (ValueError otherwise)."""
+    known stack and mask; it needs a seed and the captured sampler as a coupling does (ValueError otherwise).
+    `kspace` (--known_kspace; mudiff_hip.kspace): None, or a kspace.KSpaceMeasurement for these n slices: the same
+    keyed road with GraphSampler.sample_keyed's `kspace`; what the sampler returns is handed to its `record` before the [0,1] map.
+    Exclusive with `known`; `resample` serves either."""
     from . import ops
     from . import sampling as S
     from .slice_coupling import check_coupling
     coupling = check_coupling(coupling)
+    if kspace is not None:
+        if known is not None:
+            raise ValueError('predict_slices: known and kspace are mutually exclusive')
+        if x_inits is not None or zs is not None or noises is not None:
+            raise ValueError('predict_slices: injected x_inits / zs / noises cannot be combined with k-space measurements (their draws are keyed)')
+        if seed is None or not use_graph:
+            raise ValueError('predict_slices: k-space measurements need a seed and the captured sampler (use_graph=True)')
     if coupling is not None:
         if x_inits is not None or zs is not None or noises is not None:
             raise ValueError('predict_slices: injected x_inits / zs / noises cannot be combined with a coupling (its draws are keyed)')
@@ -323,7 +333,7 @@ def predict_slices(args, gen1, gen2, cond_stacks, device, batch_size=32, x_inits
             raise ValueError('predict_slices: injected x_inits / zs / noises cannot be combined with a known region (its draws are keyed)')
         if seed is None or not use_graph:
             raise ValueError('predict_slices: a known region needs a seed and the captured sampler (use_graph=True)')
-    keyed = coupling is not None or known is not None
+    keyed = coupling is not None or known is not None or kspace is not None
     n = int(cond_stacks[0].shape[0])
     size = int(args.image_size)
     if n == 0:
@@ -363,7 +373,12 @@ def predict_slices(args, gen1, gen2, cond_stacks, device, batch_size=32, x_inits
         if keyed:
             keys = torch.stack([torch.arange(lo, lo + bs).clamp_(max=hi - 1), torch.zeros(bs, dtype=torch.int64)], 1)
             more = {} if known is None else dict(known=padded(known[0], lo, hi), known_mask=padded(known[1], lo, hi), resample=resample)
-            out[lo:hi] = ops.to_range_0_1(sampler.sample_keyed(c1, c2, c3, keys, seed, T, coupling=coupling, **more))[:hi - lo, 0]
+            if kspace is not None:
+                more = dict(kspace=(padded(kspace.y, lo, hi), padded(kspace.mask, lo, hi)), resample=resample)
+            fake = sampler.sample_keyed(c1, c2, c3, keys, seed, T, coupling=coupling, **more)
+            if kspace is not None:
+                kspace.record(torch.arange(lo, hi, device=device), fake[:hi - lo])
+            out[lo:hi] = ops.to_range_0_1(fake)[:hi - lo, 0]
             if progress:
                 progress(hi, n)
             continue
@@ -395,7 +410,10 @@ def predict_volume(args):
     samples next to the mean and the std, --ensemble_center median makes the median the written and scored prediction, and --coverage
     counts how often the ground truth lies between two of the maps (mudiff_hip.ensemble, mudiff_hip.volume_coverage).  --known_volume keeps
     the acquired part of the target: it conditions the sampling and is pasted into every written map, known_<target>.json goes next to the
-    prediction and the scores gain the regions known / synthesised (mudiff_hip.known_region)."""
+    prediction and the scores gain the regions known / synthesised (mudiff_hip.known_region).  With --known_kspace
+    that volume was acquired undersampled in k-space instead: its measured Fourier coefficients condition the sampling, nothing is pasted,
+    and kspace_<target>.json (under --kspace_zero_filled also zero_filled_<target>.nii.gz) goes next to the prediction (mudiff_hip.kspace,
+    DESIGN.md section 5.26)."""
     evaluation, resampled, found = _load_eval_inputs(args)
     args = copy.copy(args)                               # the run's own copy: it carries the record of what the intake did
     args.evaluation_record = (resampled, found)          # (for _predict_volume's report: IntakeReport.add_evaluation)
@@ -530,9 +548,11 @@ def _done_tail(args, plan):
     quantiles, each only when it is not the default."""
     from .ensemble import done_suffix
     from .known_region import suffix as known_suffix
+    from .kspace import suffix as kspace_suffix
     from .slice_coupling import suffix
     return (('' if plan == 'auto' else f' | prec_plan={plan}') + norm_suffix(args.norm) + _intake_report(args).suffix() +
-            suffix(getattr(args, 'slice_coupling', None)) + done_suffix(args) + known_suffix(getattr(args, 'known_region', None)))
+            suffix(getattr(args, 'slice_coupling', None)) + done_suffix(args) + known_suffix(getattr(args, 'known_region', None)) +
+            kspace_suffix(getattr(args, 'kspace', None)))
 
 
 class _Stages:
@@ -602,6 +622,7 @@ def predict_from_conditions(args, plan, evaluation, gen1, gen2, device, stacks, 
         vol_pred = stages.run('assemble', lambda: KR.paste(vol_pred, region, device))      # the acquired voxels, exactly, in what is written
         KR.write_json(region, args.output_dir, args.target_modality)
     stages.run('write', lambda: write(out_path, vol_pred, aff, hdr))
+    _kspace_outputs(args, write, lambda p: _assemble_map(p, shp, s0, s1, on_device), aff, hdr, evaluation, device)
     _intake_report(args).write(args.output_dir, args.target_modality, aff, hdr)
     print(f'[done] saved: {out_path} | shape={tuple(vol_pred.shape)} | slices={s0}..{s1}' + _done_tail(args, plan))
     if evaluation is not None:
@@ -614,12 +635,53 @@ def _known_region(args, ref, device):
     """--known_volume: (the run's known_region.KnownRegion, also left in args.known_region for the [done] line and the scores; what
     predict_slices and sample_ensemble take for it) - or (None, {}) without the flag."""
     inputs = getattr(args, 'known_inputs', None)
-    args.known_region = None
+    args.known_region = args.kspace = None
     if inputs is None:
         return None, {}
     from . import known_region as KR
-    region = args.known_region = KR.compose(inputs, ref, args.norm, device)
+    from . import kspace as KS
+    region = KR.compose(inputs, ref, args.norm, device)
+    options = KS.options_from(args)
+    if options is not None:       # --known_kspace: K is measured in k-space instead; no known region, no paste (mudiff_hip.kspace)
+        args.kspace = KS.measure(region, ref[3], ref[4], int(args.image_size), options, args.seed, device)
+        return None, dict(kspace=args.kspace, resample=region.resample)
+    args.known_region = region
     return region, dict(known=KR.sampler_inputs(region, ref[3], ref[4], int(args.image_size), device), resample=region.resample)
+
+
+def _assemble_map(p, shp, s0, s1, on_device):
+    """A device map [n,S,S] -> the host volume [X,Y,Z] the prediction's road gives it: resized back, the slab's planes put in place."""
+    from . import ops
+    p = p if tuple(shp[:2]) == tuple(p.shape[1:]) else ops.resize_bilinear(p.contiguous(), shp[:2])
+    if on_device:
+        from . import volume_intake as VI
+        return VI.to_host_volume(VI.assemble(p, shp, s0, s1))
+    return reconstruct_volume_from_slices(list(p.cpu().numpy()), shp, s0, s1)
+
+
+def _kspace_outputs(args, write, put_together, aff, hdr, evaluation, device):
+    """--known_kspace: kspace_<t>.json next to the prediction, and under --kspace_zero_filled zero_filled_<t>.nii.gz = Re F^H y mapped to
+    [0,1], through the prediction's own road (`put_together`: a device [n,S,S] map -> the host volume as written) and, with an
+    evaluation, scored into metrics_zero_filled_<t>.json.  Nothing without the flag."""
+    meas = getattr(args, 'kspace', None)
+    if meas is None:
+        return
+    from . import kspace as KS
+    from . import ops
+    target = args.target_modality.lower()
+    print(f'[kspace] wrote {KS.write_json(meas, args.output_dir, args.target_modality)}')
+    if not meas.options['zero_filled']:
+        return
+    vol = put_together(ops.to_range_0_1(meas.zero_filled()))
+    path = os.path.join(args.output_dir, f'zero_filled_{target}.nii.gz')
+    write(path, vol, aff, hdr)
+    print(f'[kspace] wrote {path}')
+    if evaluation is not None:
+        from . import volume_metrics as VM
+        rep = VM.score_arrays(vol, evaluation[0], evaluation[1], None, args.slice_half_range, device, norm=args.norm)
+        for ln in VM.format_lines(rep):
+            print('[zero-filled] ' + ln)
+        print(f"[metrics] wrote {VM.write_json(rep, os.path.join(args.output_dir, f'metrics_zero_filled_{target}.json'))}")
 
 
 def _coupling(args):
@@ -704,6 +766,7 @@ def _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref, evaluation=N
         path = os.path.join(args.output_dir, f'predicted_{args.target_modality.lower()}{suffix}.nii.gz')
         stages.run('write', lambda: write(path, vol, aff, hdr))
         paths.append(path)
+    _kspace_outputs(args, write, lambda p: _assemble_map(p, shp, s0, s1, on_device), aff, hdr, evaluation, device)
     _intake_report(args).write(args.output_dir, args.target_modality, aff, hdr)
     print(f'[done] saved: {paths[0]} and {paths[1]} | shape={tuple(shp)} | slices={s0}..{s1} | {args.num_samples} samples per slice' +
           _done_tail(args, effective_prec_plan(args)))
@@ -823,6 +886,8 @@ def make_parser(prog='MU-Diff volume prediction (MI355X)'):
     add_calibration_flags(p)                # (also --prec_plan)
     from . import slice_coupling
     slice_coupling.add_flags(p)             # (--slice_coupling, --through_plane: in a late parser, VolumeParser.later())
+    from . import kspace
+    kspace.add_flags(p)                     # (--known_kspace and the --kspace_* flags: in one of their own, before the last two, whose places are pinned)
     from . import known_region
     known_region.add_flags(p)               # (--known_volume and its three: in one of their own, before the last)
     from . import ensemble
@@ -854,6 +919,11 @@ def finish_args(p, args):
         known_region.options_from(args)                  # (its ValueError names the flag)
     except ValueError as e:
         p.error(str(e))
+    from . import kspace
+    try:
+        kspace.options_from(args)                        # (its ValueError names the flag)
+    except ValueError as e:
+        p.error(str(e))
     from . import volume_conform as VCF
     from . import volume_reorient as VO
     from .volume_prepare import STAGES
@@ -880,7 +950,8 @@ def build_argparser(argv=None):
     DESIGN.md sections 5.12 - 5.22; --align's flags sit in VolumeParser.late), and --slice_coupling / --through_plane (mudiff_hip.slice_coupling,
     DESIGN.md section 5.23; in a further late parser), and --ensemble_quantiles / --ensemble_center / --coverage (mudiff_hip.ensemble,
     mudiff_hip.volume_coverage; in one more), and --known_volume / --known_mask / --known_drop_slices /
-    --known_resample (mudiff_hip.known_region; in a parser of their own before that last one)."""
+    --known_resample (mudiff_hip.known_region; in a parser of their own before that last one), and --known_kspace
+    with the --kspace_* flags (mudiff_hip.kspace; in one more parser, before those two)."""
     p = make_parser()
     return finish_args(p, p.parse_args(argv))
 
