@@ -342,8 +342,9 @@ int mud_lpips_u8(const uint8_t* pred, const uint8_t* gt, int n, int H, int W, co
  * Philox4x64-10 (numpy.random.Philox's algorithm and word order) with key (seed, 0x4D55444946460001) and counter
  * (e/4, s, (j << 32) | (step << 8) | kind, 0); lane l = e % 4 takes the word pair (w[2(l/2)], w[2(l/2)+1]) = (wa, wb),
  * u1 = ((wa >> 11) + 1) 2^-53, u2 = (wb >> 11) 2^-53, r = sqrt(-2 log u1), theta = 2 pi u2: r cos theta (even l), r sin theta (odd l),
- * in fp64, rounded once to fp32.  kind: 0 x_init, 1 z, 2 posterior noise, or 5: the draw of mud_kspace_constrain, so that a caller can
- * inject what that entry draws (3 and 4, mud_known_constrain's, stay refused); step in [0, 2^24); row_len > 0.
+ * in fp64, rounded once to fp32.  kind: 0 x_init, 1 z, 2 posterior noise, or 5 / 6: the draws of mud_kspace_constrain /
+ * mud_slab_constrain, so that a caller can inject what those entries draw (3 and 4, mud_known_constrain's, stay refused); step in
+ * [0, 2^24); row_len > 0.
  * mud_ensemble_stats: samples [n][N][hw] -> mean, std [n][hw] (N >= 2, hw > 0): y = clamp(x*scale + shift, lo, hi) in fp32 (each step
  * rounded once, NaN kept), m = (sum_j y_j) / N and v = sum_j (y_j - m)^2 / (N - 1) in fp64 in sample order j = 0..N-1,
  * mean = (float)m, std = (float)sqrt(v); a NaN sample gives NaN in both.  No atomics: a fixed function of the samples. */
@@ -451,6 +452,35 @@ int mud_fft2_r2c(const float* in, float* out, int rows, int S, int inverse, void
 int mud_kspace_constrain(const float* x_new, const float* y, const uint8_t* mask, int mask_rows, const float* noise, const int64_t* keys,
                          uint64_t seed, int step, int kind, const int64_t* t, int toff, const float* a_tab, const float* s_tab, int ntab,
                          int clean, float* out, float* work, int rows, int S, void* stream);
+
+/* ---- sampling a target acquired with thick slices (mudiff_hip.thick; GraphSampler.sample_keyed(thick=)).
+ * A group (a slab) names up to L rows of the batch, its thin slices, with weights w_l > 0 (the slice profile) and gains
+ * g_l = w_l / sum_m w_m^2, formed by the caller in fp64 and rounded once; its measurement y[g] is sum_l w_l k_l per element.  The host
+ * tables, read at call time (they travel as kernel arguments): members int32 [groups][L], a row index or -1 = unused; weights and gains
+ * fp32 [groups][L].  No row is in two groups or twice in one, so the groups' rows are orthogonal and the step is an exact projection.
+ * mud_slab_constrain: with c = clamp(t[first member of g] + toff, 0, ntab - 1), for every group g and element e
+ *   r = sum_l w_l (x_new[m_l][e] - s_tab[c] * eta[m_l][e]) - a_tab[c] * y[g][e]      (clean != 0:  r = sum_l w_l x_new[m_l][e] - y[g][e])
+ *   out[m_l][e] = x_new[m_l][e] - g_l * r                                            for every member l,
+ * in fp32, every product and sum rounded once (no contraction), the sum over l from 0 in the table's order whatever the rows' positions:
+ * a group's result depends on its own rows, table and keys alone, not on where its rows sit or on what else is in the batch.  A
+ * correction g_l * r that compares equal to 0 leaves x_new's bits, and a row of no group is copied bit for bit (nothing when out is
+ * x_new, which is allowed).  eta is `noise` [rows][row_len] when given, else the value mud_randn_keyed gives element e of a row keyed
+ * keys[2r..2r+1] under (seed, step, kind), drawn by the thread that owns elements 4b..4b+3 of the group (Philox block b of each member
+ * row); kind in [0, 15] (mudiff_hip.ops.KIND_THICK = 6 is this entry's), step in [0, 2^24).  With clean != 0 nothing is drawn: t, the
+ * tables, noise and keys may be NULL.  One thread owns 4 consecutive elements of one group and walks its members twice (accumulate,
+ * then store); 16-byte loads and stores when row_len % 4 == 0 and x_new, y, noise and out are 16-byte aligned, else element by element.
+ * One launch per 32 groups or 128 members; no atomics, no LDS, no allocation on the device.
+ * mud_slab_average: avg[g][e] = sum_l w_l x[m_l][e] under the same tables, order and rounding (avg: fp32 [groups][row_len]).
+ * MUD_ERR_ARG before any launch or copy, naming the argument, for a member outside [0, rows) (other than -1), a row named twice, a group
+ * with no member, a weight or gain that is not finite and positive, L outside [1, MUD_SLAB_MAX_MEMBERS], groups outside [0, rows]
+ * (average: [1, rows]), rows * row_len >= 2^31, ntab <= 0, a kind or step out of range, a null pointer that is needed, and neither noise
+ * nor keys. */
+#define MUD_SLAB_MAX_MEMBERS 16
+int mud_slab_constrain(const float* x_new, const float* y, const int32_t* members, const float* weights, const float* gains, int groups, int L,
+                       const float* noise, const int64_t* keys, uint64_t seed, int step, int kind, const int64_t* t, int toff,
+                       const float* a_tab, const float* s_tab, int ntab, int clean, float* out, int rows, int64_t row_len, void* stream);
+int mud_slab_average(const float* x, const int32_t* members, const float* weights, int groups, int L, float* avg, int rows, int64_t row_len,
+                     void* stream);
 
 /* ---- through-plane roughness of a volume (mudiff_hip.volume_through_plane; the volume pipeline's --through_plane).
  * vol (fp32) and the optional mask (uint8, may be NULL: every voxel is inside; else non-zero is inside) are [Z, X, Y] with planes

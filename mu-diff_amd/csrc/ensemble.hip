@@ -33,8 +33,8 @@ __global__ __launch_bounds__(ES_THREADS) void k_randn_keyed(float* __restrict__ 
 
 extern "C" int mud_randn_keyed(float* out, int rows, int64_t row_len, const int64_t* keys, uint64_t seed, int step, int kind, void* stream) {
   MUD_REQUIRE(rows >= 0 && row_len > 0, "mud_randn_keyed: bad sizes (rows %d, row_len %lld)", rows, (long long)row_len);
-  MUD_REQUIRE((kind >= 0 && kind <= 2) || kind == 5, "mud_randn_keyed: kind must be 0 (x_init), 1 (z), 2 (posterior noise) or 5 (k-space), got %d",
-              kind);
+  MUD_REQUIRE((kind >= 0 && kind <= 2) || kind == 5 || kind == 6,
+              "mud_randn_keyed: kind must be 0 (x_init), 1 (z), 2 (posterior noise), 5 (k-space) or 6 (thick slices), got %d", kind);
   MUD_REQUIRE(step >= 0 && step < (1 << 24), "mud_randn_keyed: step must be in [0, 2^24), got %d", step);
   MUD_REQUIRE(out && keys, "mud_randn_keyed: null pointer");
   if (rows == 0) return MUD_OK;

@@ -1,0 +1,240 @@
+// Sampling a target acquired with thick slices (include/mudiff_hip.h: mud_slab_constrain, mud_slab_average; mudiff_hip.thick, DESIGN.md
+// section 5.27).  A thick slice (a slab) is a weighted average of L thin slices, y = sum_l w_l k_l per pixel; slabs do not overlap, so
+// A A^T is diagonal and the data-consistency step is an exact orthogonal projection along the profile:
+//  - constrain: r = sum_l w_l (x_l - s eta_l) - a y, x_l <- x_l - g_l r for every member row l of a group, g_l = w_l / sum_m w_m^2;
+//  - average:   avg = sum_l w_l x_l, the measurement of k and the residual's A x.
+// This is the first constraint that couples the rows of a batch.  The sum over a group's members runs in the table's order whatever the
+// rows' positions, one thread owns 4 consecutive elements of one group (all its members), and the draw is keyed (keyed_normal.h): a
+// group's result is a function of its own rows, its table and its keys alone.  No LDS, no atomics, no contraction.
+#include <vector>
+#include "keyed_normal.h"
+
+#define SL_THREADS 256
+#define SL_GROUPS 32             // groups per launch
+#define SL_SLOTS 128             // member slots per launch (>= MUD_SLAB_MAX_MEMBERS): 32 rows of L = 5 or 16 are one launch
+
+// the tables of one launch, passed by value like es_taps: the unused tails (-1) are squeezed out, the order is the table's
+struct sl_tables {
+  int start[SL_GROUPS + 1];      // group q of the launch owns slots start[q] .. start[q + 1] - 1
+  int member[SL_SLOTS];          // row index
+  float w[SL_SLOTS];
+  float g[SL_SLOTS];
+};
+
+template <bool VEC>
+__device__ __forceinline__ f32x4 sl_load(const float* p, int n) {
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (VEC) {
+    v = *reinterpret_cast<const f32x4*>(p);
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (e < n) v[e] = p[e];
+  }
+  return v;
+}
+
+template <bool VEC>
+__device__ __forceinline__ void sl_store(float* p, f32x4 v, int n) {
+  if constexpr (VEC) {
+    *reinterpret_cast<f32x4*>(p) = v;
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (e < n) p[e] = v[e];
+  }
+}
+
+// grid (blocks over the row's quads, groups of this launch).  AVERAGE: out = avg [groups][row_len], nothing else is written.  Else out may
+// alias x_new: a thread reads its 4 elements of a member row before it writes them, and no other thread touches them (a row is in one
+// group once: validated on the host).  VEC: row_len % 4 == 0 and every pointer 16-byte aligned; else element by element, the last quad cut.
+template <bool VEC, bool AVERAGE>
+__global__ __launch_bounds__(SL_THREADS) void k_slab(const float* x_new, const float* __restrict__ y, sl_tables tab, int group0,
+                                                     const float* __restrict__ noise, const int64_t* __restrict__ keys, uint64_t seed, uint64_t word2,
+                                                     const int64_t* __restrict__ t, int toff, const float* __restrict__ at,
+                                                     const float* __restrict__ st, int ntab, int clean, float* out, int64_t row_len,
+                                                     int64_t blocks_per_row) {
+#pragma clang fp contract(off)   // s * eta, x - ., w * ., acc + .: each rounded once
+  const int64_t b = (int64_t)blockIdx.x * SL_THREADS + threadIdx.x;
+  if (b >= blocks_per_row) return;
+  const int q = blockIdx.y;
+  const int s0 = tab.start[q], s1 = tab.start[q + 1];
+  const int64_t col = 4 * b;
+  const int n = VEC ? 4 : (int)(row_len - col < 4 ? row_len - col : 4);
+  const bool noisy = !AVERAGE && !clean;
+  float a = 1.f, sg = 0.f;
+  if (noisy) {
+    int64_t ti = t[tab.member[s0]] + toff;              // the level of the group's first member
+    ti = ti < 0 ? 0 : (ti >= ntab ? ntab - 1 : ti);
+    a = at[ti];
+    sg = st[ti];
+  }
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  for (int s = s0; s < s1; ++s) {                       // table order
+    const int64_t base = (int64_t)tab.member[s] * row_len + col;
+    f32x4 d = sl_load<VEC>(x_new + base, n);
+    if (noisy) {
+      const int64_t r = tab.member[s];
+      const f32x4 eta = noise ? sl_load<VEC>(noise + base, n)
+                              : es_block_normals((uint64_t)b, (uint64_t)keys[2 * r], (uint64_t)keys[2 * r + 1], seed, word2);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float p = sg * eta[e];
+        d[e] = d[e] - p;
+      }
+    }
+    const float w = tab.w[s];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float p = w * d[e];
+      acc[e] = acc[e] + p;
+    }
+  }
+  const int64_t gbase = (int64_t)(group0 + q) * row_len + col;
+  if constexpr (AVERAGE) {
+    sl_store<VEC>(out + gbase, acc, n);
+  } else {
+    const f32x4 yv = sl_load<VEC>(y + gbase, n);
+    f32x4 r;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float ay = noisy ? a * yv[e] : yv[e];
+      r[e] = acc[e] - ay;
+    }
+    for (int s = s0; s < s1; ++s) {
+      const int64_t base = (int64_t)tab.member[s] * row_len + col;
+      const f32x4 x = sl_load<VEC>(x_new + base, n);
+      const float g = tab.g[s];
+      f32x4 o;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float c = g * r[e];
+        const float v = x[e] - c;
+        o[e] = c == 0.f ? x[e] : v;                     // a correction that is 0 leaves x_new's bits (a -0 included)
+      }
+      sl_store<VEC>(out + base, o, n);
+    }
+  }
+}
+
+// members / weights / gains [groups][L] -> the launches' tables; every refusal before any launch.  owner[r] = 1 for a row in a group.
+static int sl_pack(const char* who, const int32_t* members, const float* weights, const float* gains, int groups, int L, int rows,
+                   std::vector<sl_tables>& launches, std::vector<int>& first_group, std::vector<int>& n_groups, std::vector<uint8_t>& owner) {
+  owner.assign((size_t)rows, 0);
+  sl_tables cur = {};
+  int ng = 0, ns = 0;
+  for (int g = 0; g < groups; ++g) {
+    int cnt = 0;
+    for (int l = 0; l < L; ++l) cnt += members[(size_t)g * L + l] >= 0 ? 1 : 0;
+    MUD_REQUIRE(cnt > 0, "%s: members: group %d has no member", who, g);
+    if (ng == SL_GROUPS || ns + cnt > SL_SLOTS) {
+      cur.start[ng] = ns;
+      launches.push_back(cur);
+      n_groups.push_back(ng);
+      ng = ns = 0;
+    }
+    if (ng == 0) first_group.push_back(g);
+    cur.start[ng] = ns;
+    for (int l = 0; l < L; ++l) {
+      const int32_t m = members[(size_t)g * L + l];
+      if (m == -1) continue;
+      MUD_REQUIRE(m >= 0 && m < rows, "%s: members: group %d names row %d outside [0, %d)", who, g, (int)m, rows);
+      MUD_REQUIRE(!owner[m], "%s: members: row %d is named twice", who, (int)m);
+      owner[m] = 1;
+      const float w = weights[(size_t)g * L + l];
+      MUD_REQUIRE(w > 0.f && w - w == 0.f, "%s: weights: group %d, member %d is not a finite positive number", who, g, l);
+      cur.member[ns] = m;
+      cur.w[ns] = w;
+      cur.g[ns] = 0.f;
+      if (gains) {
+        const float gn = gains[(size_t)g * L + l];
+        MUD_REQUIRE(gn > 0.f && gn - gn == 0.f, "%s: gains: group %d, member %d is not a finite positive number", who, g, l);
+        cur.g[ns] = gn;
+      }
+      ++ns;
+    }
+    ++ng;
+  }
+  if (ng) {
+    cur.start[ng] = ns;
+    launches.push_back(cur);
+    n_groups.push_back(ng);
+  }
+  return MUD_OK;
+}
+
+#define SL_LAUNCH(VEC, AVG, ...) hipLaunchKernelGGL((k_slab<VEC, AVG>), grid, dim3(SL_THREADS), 0, (hipStream_t)stream, __VA_ARGS__)
+
+extern "C" int mud_slab_constrain(const float* x_new, const float* y, const int32_t* members, const float* weights, const float* gains, int groups,
+                                  int L, const float* noise, const int64_t* keys, uint64_t seed, int step, int kind, const int64_t* t, int toff,
+                                  const float* a_tab, const float* s_tab, int ntab, int clean, float* out, int rows, int64_t row_len, void* stream) {
+  MUD_REQUIRE(rows > 0 && row_len > 0, "mud_slab_constrain: bad sizes (rows %d, row_len %lld)", rows, (long long)row_len);
+  MUD_REQUIRE((int64_t)rows * row_len < (1ll << 31), "mud_slab_constrain: rows * row_len must be < 2^31, got %d x %lld", rows, (long long)row_len);
+  MUD_REQUIRE(groups >= 0 && groups <= rows, "mud_slab_constrain: groups must be in [0, rows = %d], got %d", rows, groups);
+  MUD_REQUIRE(L >= 1 && L <= MUD_SLAB_MAX_MEMBERS, "mud_slab_constrain: L must be in [1, %d], got %d", MUD_SLAB_MAX_MEMBERS, L);
+  MUD_REQUIRE(ntab > 0, "mud_slab_constrain: ntab must be > 0, got %d", ntab);
+  MUD_REQUIRE(kind >= 0 && kind <= 15, "mud_slab_constrain: kind must be in [0, 15], got %d", kind);
+  MUD_REQUIRE(step >= 0 && step < (1 << 24), "mud_slab_constrain: step must be in [0, 2^24), got %d", step);
+  MUD_REQUIRE(x_new && out, "mud_slab_constrain: null pointer (x_new, out)");
+  MUD_REQUIRE(groups == 0 || (y && members && weights && gains), "mud_slab_constrain: null pointer (y, members, weights, gains)");
+  MUD_REQUIRE(groups == 0 || clean || (t && a_tab && s_tab), "mud_slab_constrain: null pointer (t, a_tab, s_tab)");
+  MUD_REQUIRE(groups == 0 || clean || noise || keys, "mud_slab_constrain: without injected noise the draw needs keys");
+  std::vector<sl_tables> launches;
+  std::vector<int> first, count;
+  std::vector<uint8_t> owner;
+  const int rc = sl_pack("mud_slab_constrain", members, weights, gains, groups, L, rows, launches, first, count, owner);
+  if (rc != MUD_OK) return rc;
+  if (out != x_new) {                                   // the rows of no group: copied, bit for bit, run by run
+    for (int r = 0; r < rows;) {
+      if (owner[r]) {
+        ++r;
+        continue;
+      }
+      int e = r;
+      while (e < rows && !owner[e]) ++e;
+      if (hipMemcpyAsync(out + (int64_t)r * row_len, x_new + (int64_t)r * row_len, (size_t)(e - r) * row_len * sizeof(float), hipMemcpyDeviceToDevice,
+                         (hipStream_t)stream) != hipSuccess) {
+        mud_set_error("mud_slab_constrain: copying the free rows failed");
+        return MUD_ERR_LAUNCH;
+      }
+      r = e;
+    }
+  }
+  const int64_t bpr = mud_cdiv(row_len, 4);
+  const bool vec = row_len % 4 == 0 && mud_aligned16(x_new) && mud_aligned16(out) && mud_aligned16(y) && (!noise || mud_aligned16(noise));
+  const uint64_t word2 = ((uint64_t)step << 8) | (uint64_t)kind;
+  for (size_t i = 0; i < launches.size(); ++i) {
+    const dim3 grid((unsigned)mud_cdiv(bpr, SL_THREADS), (unsigned)count[i]);
+    if (vec)
+      SL_LAUNCH(true, false, x_new, y, launches[i], first[i], noise, keys, seed, word2, t, toff, a_tab, s_tab, ntab, clean, out, row_len, bpr);
+    else
+      SL_LAUNCH(false, false, x_new, y, launches[i], first[i], noise, keys, seed, word2, t, toff, a_tab, s_tab, ntab, clean, out, row_len, bpr);
+    MUD_CHECK_LAUNCH("mud_slab_constrain");
+  }
+  return MUD_OK;
+}
+
+extern "C" int mud_slab_average(const float* x, const int32_t* members, const float* weights, int groups, int L, float* avg, int rows,
+                                int64_t row_len, void* stream) {
+  MUD_REQUIRE(rows > 0 && row_len > 0, "mud_slab_average: bad sizes (rows %d, row_len %lld)", rows, (long long)row_len);
+  MUD_REQUIRE((int64_t)rows * row_len < (1ll << 31), "mud_slab_average: rows * row_len must be < 2^31, got %d x %lld", rows, (long long)row_len);
+  MUD_REQUIRE(groups >= 1 && groups <= rows, "mud_slab_average: groups must be in [1, rows = %d], got %d", rows, groups);
+  MUD_REQUIRE(L >= 1 && L <= MUD_SLAB_MAX_MEMBERS, "mud_slab_average: L must be in [1, %d], got %d", MUD_SLAB_MAX_MEMBERS, L);
+  MUD_REQUIRE(x && members && weights && avg, "mud_slab_average: null pointer");
+  std::vector<sl_tables> launches;
+  std::vector<int> first, count;
+  std::vector<uint8_t> owner;
+  const int rc = sl_pack("mud_slab_average", members, weights, nullptr, groups, L, rows, launches, first, count, owner);
+  if (rc != MUD_OK) return rc;
+  const int64_t bpr = mud_cdiv(row_len, 4);
+  const bool vec = row_len % 4 == 0 && mud_aligned16(x) && mud_aligned16(avg);
+  for (size_t i = 0; i < launches.size(); ++i) {
+    const dim3 grid((unsigned)mud_cdiv(bpr, SL_THREADS), (unsigned)count[i]);
+    if (vec)
+      SL_LAUNCH(true, true, x, nullptr, launches[i], first[i], nullptr, nullptr, 0ull, 0ull, nullptr, 0, nullptr, nullptr, 1, 1, avg, row_len, bpr);
+    else
+      SL_LAUNCH(false, true, x, nullptr, launches[i], first[i], nullptr, nullptr, 0ull, 0ull, nullptr, 0, nullptr, nullptr, 1, 1, avg, row_len, bpr);
+    MUD_CHECK_LAUNCH("mud_slab_average");
+  }
+  return MUD_OK;
+}

@@ -941,8 +941,8 @@ def randn_keyed(rows_keys, row_len, seed, step, kind, out=None):
     """Keyed standard normals: row r of the fp32 result [rows, row_len] is a pure function of (seed, slice, sample, step, kind) with
     rows_keys[r] = (slice, sample) (int64 [rows, 2], host or device): Philox4x64-10 + Box-Muller in fp64 (mud_randn_keyed).  `out`:
     a contiguous fp32 device tensor of rows * row_len elements to fill (any shape); without it the result lands on rows_keys's device
-    (or the current one for host keys).  kind: KIND_X_INIT, KIND_Z or KIND_NOISE (or KIND_KSPACE, to inject what ops.kspace_constrain
-    draws)."""
+    (or the current one for host keys).  kind: KIND_X_INIT, KIND_Z or KIND_NOISE (or KIND_KSPACE / KIND_THICK, to inject what
+    ops.kspace_constrain / ops.slab_constrain draw)."""
     k = check_keys(rows_keys)
     seed = _seed64(seed)
     rows, row_len = k.shape[0], int(row_len)
@@ -1156,6 +1156,120 @@ def kspace_constrain(x_new, y, mask, t, toff, a_tab, s_tab, *, noise=None, keys=
     out = torch.empty(x_new.shape, device=x_new.device, dtype=torch.float32) if out is None else out
     work = torch.empty(rows, S, S, device=x_new.device, dtype=torch.complex64) if work is None else work
     return kspace_constrain_into(out, x_new, y, mask, work, kd, _seed64(seed), step, kind, t, toff, a_tab, s_tab, clean, noise)
+
+
+# ---------------------------------------------------------------------------------------------------
+# sampling a target acquired with thick slices (csrc/slab.hip, mudiff_hip.thick)
+KIND_THICK = 6                       # the draw of mud_slab_constrain: the slab averages' forward noise
+SLAB_MAX_MEMBERS = 16                # include/mudiff_hip.h: MUD_SLAB_MAX_MEMBERS
+
+
+def slab_gains(weights):
+    """g_l = w_l / sum_m w_m^2 per group (an unused slot's weight counts as it stands: pass 0 there), in fp64, rounded once to fp32."""
+    w = np.asarray(weights, dtype=np.float32).astype(np.float64)
+    w = w.reshape(1, -1) if w.ndim == 1 else w
+    return (w / (w * w).sum(1, keepdims=True)).astype(np.float32)
+
+
+def slab_tables(members, weights, gains=None):
+    """The host tables of mud_slab_constrain / mud_slab_average, read at call time: (members int32 [groups, L], weights fp32 [groups, L],
+    gains fp32 [groups, L]) as contiguous numpy arrays.  members: row indices, -1 = an unused tail; weights [L] serves every group;
+    gains None: slab_gains of the weights with the unused slots' weights taken as 0.  Only shapes are checked here: the entry refuses a
+    bad index, a row named twice, an empty group and a bad weight before it launches anything."""
+    m = np.ascontiguousarray(np.asarray(members, dtype=np.int32))
+    m = m.reshape(1, -1) if m.ndim == 1 else m
+    if m.ndim != 2 or m.shape[1] < 1:
+        raise MudiffHipError(f'slab_tables: members must be [groups, L] with L >= 1, got {m.shape}')
+    w = np.asarray(weights, dtype=np.float32)
+    w = np.ascontiguousarray(np.broadcast_to(w, m.shape)) if w.ndim == 1 and w.shape[0] == m.shape[1] else np.ascontiguousarray(w)
+    if w.shape != m.shape:
+        raise MudiffHipError(f'slab_tables: weights must be [L] or {m.shape}, got {w.shape}')
+    g = slab_gains(np.where(m >= 0, w, np.float32(0))) if gains is None else np.ascontiguousarray(np.asarray(gains, dtype=np.float32))
+    g = np.ascontiguousarray(np.broadcast_to(g, m.shape)) if g.ndim == 1 and g.shape[0] == m.shape[1] else g
+    if g.shape != m.shape:
+        raise MudiffHipError(f'slab_tables: gains must be [L] or {m.shape}, got {g.shape}')
+    return m, w, g
+
+
+def _host(a):
+    return C.c_void_p(a.ctypes.data)
+
+
+def slab_constrain_into(out, x_new, y, tables, keys_dev, seed, step, kind, t, toff, a_tab, s_tab, clean=False, noise=None):
+    """Unchecked launch of mud_slab_constrain into `out` (fp32, contiguous, [rows, ...]; may be x_new): GraphSampler.sample_keyed checks
+    its operands once per batch, not once per step.  y: fp32 [groups, row_len]; tables: slab_tables'; keys_dev: through check_keys and on
+    out's device (None with `noise` or `clean`)."""
+    rows = out.shape[0]
+    m, w, g = tables
+    groups, L = m.shape
+    row_len = out.numel() // max(rows, 1)
+    _launch('slab_constrain', out.device, load().mud_slab_constrain, ptr(x_new), ptr(y), _host(m), _host(w), _host(g), groups, L, ptr(noise),
+            ptr(keys_dev), C.c_uint64(seed), int(step), int(kind), ptr(t), int(toff), ptr(a_tab), ptr(s_tab), 1 if a_tab is None else a_tab.numel(),
+            int(bool(clean)), ptr(out), rows, row_len, STREAM, nbytes=float(row_len * 4 * (3 * int((m >= 0).sum()) + groups)))
+    return out
+
+
+def slab_constrain(x_new, y, members, weights, t, toff, a_tab, s_tab, *, gains=None, noise=None, keys=None, seed=0, step=0, kind=KIND_THICK,
+                   clean=False, out=None):
+    """The data-consistency step of thick-slice measurements (mud_slab_constrain).  Group j names the rows members[j] (its thin slices,
+    -1 = unused) with weights w and gains g (slab_tables); with c = clamp(t[first member] + toff, 0, len(a_tab) - 1), per element
+        r = sum_l w_l (x_new[m_l] - s_tab[c] * eta[m_l]) - a_tab[c] * y[j]        (clean: r = sum_l w_l x_new[m_l] - y[j])
+        out[m_l] = x_new[m_l] - g_l * r,
+    summed in the table's order, so that the slab average of the result is that of q_sample(k, c) for y = sum_l w_l k_l and everything
+    orthogonal to the profile is untouched.  A row of no group is copied bit for bit.  x_new: fp32 [rows, ...]; y: fp32 [groups, ...] with
+    x_new's row shape.  eta: `noise` (fp32, x_new's shape) when given, else the keyed normal ops.randn_keyed gives keys[r] = (slice, sample)
+    under (seed, step, kind), drawn in the kernel.  t: int64 [rows]; with `clean` it, the tables and the draw are not needed.  out: None (a
+    new tensor), x_new (in place) or a contiguous fp32 tensor of the shape."""
+    require_gpu(x_new, y, noise, t, a_tab, s_tab, out)
+    if x_new.dtype != torch.float32 or x_new.dim() < 1 or x_new.shape[0] < 1 or x_new[0].numel() < 1:
+        raise MudiffHipError(f'slab_constrain: x_new must be a non-empty fp32 [rows, ...] tensor, got {x_new.dtype} {tuple(x_new.shape)}')
+    rows = x_new.shape[0]
+    tables = slab_tables(members, weights, gains)
+    groups = tables[0].shape[0]
+    if y is None or y.dtype != torch.float32 or y.dim() < 1 or y.shape[0] != groups or y.numel() != groups * x_new[0].numel():
+        raise MudiffHipError(f'slab_constrain: y must be fp32 [{groups}, {x_new[0].numel()}], got '
+                             f'{None if y is None else (y.dtype, tuple(y.shape))}')
+    for name, v in (('noise', noise), ('out', out)):
+        if v is not None and (v.dtype != torch.float32 or v.shape != x_new.shape):
+            raise MudiffHipError(f'slab_constrain: {name} must be fp32 of shape {tuple(x_new.shape)}, got {v.dtype} {tuple(v.shape)}')
+    if out is not None and not out.is_contiguous():
+        raise MudiffHipError('slab_constrain: out must be contiguous')
+    x_new = x_new if x_new.is_contiguous() or out is x_new else x_new.contiguous()
+    y = y.contiguous()
+    noise = None if noise is None else noise.contiguous()
+    kd = None
+    if not clean:
+        if t is None or a_tab is None or s_tab is None or t.dtype != torch.int64 or t.numel() != rows or a_tab.numel() != s_tab.numel():
+            raise MudiffHipError('slab_constrain: need t (int64 [rows]) and two tables of one length')
+        t, a_tab, s_tab = t.contiguous(), _f32(a_tab.contiguous()), _f32(s_tab.contiguous())
+        if noise is None:
+            if keys is None:
+                raise MudiffHipError('slab_constrain: pass noise or keys')
+            k = check_keys(keys)
+            if k.shape[0] != rows:
+                raise MudiffHipError(f'slab_constrain: {k.shape[0]} keys for {rows} rows')
+            kd = k.to(x_new.device)
+    out = torch.empty(x_new.shape, device=x_new.device, dtype=torch.float32) if out is None else out
+    return slab_constrain_into(out, x_new, y, tables, kd, _seed64(seed), step, kind, t, toff, a_tab, s_tab, clean, noise)
+
+
+def slab_average(x, members, weights, out=None):
+    """avg[j] = sum_l w_l x[members[j][l]] per element, in mud_slab_constrain's order and rounding (mud_slab_average): the measurement y of
+    k, and A x of the residual.  x: fp32 [rows, ...] -> fp32 [groups, ...]."""
+    require_gpu(x, out)
+    if x.dtype != torch.float32 or x.dim() < 1 or x.shape[0] < 1 or x[0].numel() < 1:
+        raise MudiffHipError(f'slab_average: x must be a non-empty fp32 [rows, ...] tensor, got {x.dtype} {tuple(x.shape)}')
+    m, w, _ = slab_tables(members, weights, weights)
+    groups, L = m.shape
+    shape = (groups,) + tuple(x.shape[1:])
+    if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous()):
+        raise MudiffHipError(f'slab_average: out must be a contiguous fp32 tensor of shape {shape}, got {out.dtype} {tuple(out.shape)}')
+    x = x if x.is_contiguous() else x.contiguous()
+    out = torch.empty(shape, device=x.device, dtype=torch.float32) if out is None else out
+    row_len = x[0].numel()
+    _launch('slab_average', x.device, load().mud_slab_average, ptr(x), _host(m), _host(w), groups, L, ptr(out), int(x.shape[0]), row_len, STREAM,
+            nbytes=float(row_len * 4 * (int((m >= 0).sum()) + groups)))
+    return out
 
 
 # columns of volume_through_plane's sums (include/mudiff_hip.h: MUD_TP_*)

@@ -246,7 +246,8 @@ class GraphSampler:
         out = self.x.clone()
         return (out, steps) if return_steps else out
 
-    def sample_keyed(self, cond1, cond2, cond3, keys, seed, n_time, coupling=None, known=None, known_mask=None, resample=1, kspace=None):
+    def sample_keyed(self, cond1, cond2, cond3, keys, seed, n_time, coupling=None, known=None, known_mask=None, resample=1, kspace=None,
+                     thick=None):
         """sample() with keyed draws (DESIGN.md section 5.7): row r of the batch is sample keys[r] = (slice, sample) of an ensemble;
         x_init (kind 0, step 0) and every executed step k's z (kind 1) and posterior noise (kind 2) are drawn with ops.randn_keyed
         on this device's current stream, so each row's result depends on (seed, its key) alone.  keys: int64 [B, 2] (host or device).
@@ -268,7 +269,17 @@ class GraphSampler:
         replaced by those of q_sample(k, i): x <- x_new - Re F^H[mask * (F(x_new - sigmas_cum[i] * eta) - a_s_cum[i] * y)] with eta of kind
         KIND_KSPACE (the row's true key, never slice-coupled), and for i = 0 by y itself (ops.kspace_constrain).  Exclusive with `known`;
         `resample` and `coupling` act as they do with `known`.  ValueError unless H == W is a size ops.fft2 takes.  The complex workspace
-        is allocated once per sampler."""
+        is allocated once per sampler.
+        `thick` (mudiff_hip.thick): None, or (y fp32 [groups,H,W], members, weights, gains) - a tuple, or an object
+        with those attributes - for this batch: the target was acquired with thick slices, group j being the rows members[j] of the
+        batch (its thin slices, -1 = unused) and y[j] = sum_l w_l k_l their measured average (ops.slab_tables has the tables' form;
+        gains None = w_l / sum w^2).  After the step executed with t = i the slab average of the result is replaced by that of
+        q_sample(k, i): r = sum_l w_l (x_new_l - sigmas_cum[i] * eta_l) - a_s_cum[i] * y, x_l <- x_new_l - g_l r with eta of kind KIND_THICK
+        (the row's true key, never slice-coupled), and for i = 0 by y itself (ops.slab_constrain).  This couples the rows of a group: the
+        caller keeps a group inside one batch.  A row of no group is sampled freely.  Exclusive with `known` and `kspace`; `resample` and
+        `coupling` act as they do with `known`.  `thick_x_new` is then the last step's result as the constraint received it (the graph's
+        own buffer, valid until the next replay: the scale of the residual's rounding).  Without `thick` the result is what it was before
+        the argument existed."""
         from .slice_coupling import SHARED, check_coupling
         coupling = check_coupling(coupling)
         k = ops.check_keys(keys)
@@ -280,8 +291,22 @@ class GraphSampler:
             raise ValueError(f'GraphSampler.sample_keyed: resample must be >= 1, got {resample}')
         if known is not None and kspace is not None:
             raise ValueError('GraphSampler.sample_keyed: known and kspace are mutually exclusive')
-        if known is None and (known_mask is not None or (resample != 1 and kspace is None)):
-            raise ValueError('GraphSampler.sample_keyed: known_mask and resample need known (resample: or kspace)')
+        if thick is not None and (known is not None or kspace is not None):
+            raise ValueError('GraphSampler.sample_keyed: thick is exclusive with known and kspace')
+        if known is None and (known_mask is not None or (resample != 1 and kspace is None and thick is None)):
+            raise ValueError('GraphSampler.sample_keyed: known_mask and resample need known (resample: or kspace, or thick)')
+        if thick is not None:
+            th_y, th_m, th_w, th_g = thick if isinstance(thick, (tuple, list)) else (thick.y, thick.members, thick.weights, thick.gains)
+            th_tab = ops.slab_tables(th_m, th_w, th_g)
+            want = (th_tab[0].shape[0], self.H, self.W)
+            if th_y.dtype != torch.float32 or tuple(th_y.shape) != want:
+                raise ValueError(f'GraphSampler.sample_keyed: thick y must be fp32 {want}, got {th_y.dtype} {tuple(th_y.shape)}')
+            if want[0] > self.B or th_tab[0].shape[1] > ops.SLAB_MAX_MEMBERS or int(th_tab[0].max(initial=-1)) >= self.B:
+                raise ValueError(f'GraphSampler.sample_keyed: thick names {want[0]} groups of {th_tab[0].shape[1]} rows up to row '
+                                 f'{int(th_tab[0].max(initial=-1))} for a batch of {self.B} (at most {ops.SLAB_MAX_MEMBERS} rows a group)')
+            th_y = th_y.to(self.x.device).contiguous()
+            dc = self._diffusion_tables()
+            k_true = k.to(self.x.device)
         if kspace is not None:
             if self.H != self.W or not ops.kspace_size_ok(self.H):
                 raise ValueError(f'GraphSampler.sample_keyed: kspace needs a square grid whose size is a power of two in [16, 512], got '
@@ -335,6 +360,11 @@ class GraphSampler:
                                               dc[1], clean=i == 0)
                     if j < resample - 1:
                         ops.known_constrain_into(self.x, None, self.x, None, k_true, seed, step, ops.KIND_RENOISE, self.t, 1, dc[2], dc[3])
+                elif thick is not None:
+                    ops.slab_constrain_into(self.x, x_new, th_y, th_tab, k_true, seed, step, ops.KIND_THICK, self.t, 0, dc[0], dc[1], clean=i == 0)
+                    if j < resample - 1:
+                        ops.known_constrain_into(self.x, None, self.x, None, k_true, seed, step, ops.KIND_RENOISE, self.t, 1, dc[2], dc[3])
+                    self.thick_x_new = x_new          # what the last constraint was given (the graph's own buffer, until the next replay)
                 elif known is None:
                     self.x.copy_(x_new)
                 else:

@@ -1,0 +1,294 @@
+"""Sample a target that was acquired with thick slices (--known_thick; csrc/slab.hip: mud_slab_constrain, mud_slab_average; DESIGN.md
+section 5.27).
+
+--known_volume keeps acquired voxels and --known_kspace acquired Fourier coefficients of each slice.  The most common way a contrast is
+partly there is a third one: the target is a 2D multi-slice scan with thick slices (5 mm, perhaps with a gap) while the conditioning
+contrasts are 3D at 1 mm, so every thick slice is a weighted average of several thin slices of the grid that is predicted.  A synthesis
+model guided by such a measurement is through-plane super-resolution.  With --known_thick L the thin slices of --known_volume K are
+measured retrospectively and the sampler keeps the measured averages:
+
+    K --known_region's road--> the prediction's grid --norm, resize--> k [n,S,S] --ops.slab_average--> y_j = sum_l w_l k_{z_j + l} --> sampler
+
+A slab j is L consecutive thin slices from z_j = O + j (L + G) of the *volume* (--thick_offset O, --thick_gap G: unmeasured thin slices
+between slabs), so --slice_half_range, shards and chunks do not move the slabs.  The weights w_l > 0 sum to 1 (--thick_profile: box, or
+gauss with FWHM = L slices).  Slabs do not overlap, so A A^T is diagonal and the constraint is an exact orthogonal projection: after the
+reverse step executed with t = i the slab average of x is replaced by that of q_sample(k, i), after the last by y itself, and everything
+orthogonal to the profile is left as the model made it (GraphSampler.sample_keyed's `thick`; the draw is kind ops.KIND_THICK, keyed by
+the true (slice, sample), never slice-coupled).  --known_resample R works as it does with --known_volume.
+
+A slab is measured when every one of its slices lies in the sampled range, K is known on every pixel of every one of them (finite and
+fully covered after resampling: known_region's sense) and --known_drop_slices names none of them: the flag then means `this thick slice
+was not acquired`.  The slices of an unmeasured slab, the gap slices and a partial last slab are sampled freely.  --known_mask and
+--known_kspace are refused.
+
+The constraint couples the rows of a batch, so the batching keeps a measured (slab, sample) group inside one batch (`batches`): a batch
+is closed early before a group that would not fit and padded as the last batch is.  The kernel sums in the table's order and the draws
+are keyed, so the written bytes do not depend on --batch_size.
+
+There is no final paste.  Consistency holds on the sampler's grid: thick_<t>.json lists, per slab, |A x - y| / |y| of the sampler's
+result before it is mapped to [0,1] (the largest over an ensemble's samples).  It does not survive clipping, --resize_back, the median
+or the quantile maps.  --thick_interp also writes thick_interp_<t>.nii.gz, what one would have without the model: piecewise linear along
+z through (slab centre, y_j) over the measured slabs, constant beyond the first and last centre.
+
+Scope: the retrospective model with non-overlapping profiles, K given on (or resampled onto) the thin grid and measured here - the
+protocol section 5.26 uses for k-space.  A NIfTI that is itself thick (its own slice spacing, slabs that cut thin slices in fractions,
+overlapping profiles: a banded A A^T) is out of scope, and so is in-plane undersampling combined with thick slices.  A later intake
+only has to fill the same ThickMeasurement.
+"""
+from __future__ import annotations
+
+import json
+import math
+import os
+
+import numpy as np
+import torch
+
+PROFILES = ('box', 'gauss')
+MAX_L = 16                           # ops.SLAB_MAX_MEMBERS
+
+
+def add_flags(p):
+    p = p.later() if hasattr(p, 'later') else p          # volume.VolumeParser: the lists of the parsers before this one are pinned
+    p.add_argument('--known_thick', type=int, default=None, metavar='L',
+                   help=f'with --known_volume K: K was acquired with thick slices.  Every L (1..{MAX_L}) consecutive thin slices of K are '
+                        'averaged under the slice profile and the sampler re-imposes those averages after every reverse step '
+                        '(mudiff_hip.thick, DESIGN.md section 5.27); --known_drop_slices then means `this thick slice was not acquired`')
+    p.add_argument('--thick_gap', type=int, default=None, metavar='G', help='with --known_thick: unmeasured thin slices between slabs (default 0)')
+    p.add_argument('--thick_offset', type=int, default=None, metavar='O',
+                   help='with --known_thick: the thin slice of the volume where the first slab starts (default 0)')
+    p.add_argument('--thick_profile', type=str, default=None, choices=list(PROFILES),
+                   help='with --known_thick: the slice profile, box (equal weights, the default) or gauss (FWHM = L slices)')
+    p.add_argument('--thick_interp', action='store_true',
+                   help='with --known_thick: also write thick_interp_<t>.nii.gz, the thick slices interpolated linearly along z (what one '
+                        'would have without the model; scored too under --gt_volume)')
+
+
+def options_from(args):
+    """A namespace's --known_thick / --thick_* flags (any may be missing) -> None without --known_thick, else dict(L, gap, offset,
+    profile, interp).  ValueError, naming the flag, for a dependent flag without --known_thick, --known_thick without --known_volume (a
+    cohort's namespace excepted: its K is the manifest's `known` column) or with --known_kspace or --known_mask, and a bad value."""
+    L = getattr(args, 'known_thick', None)
+    gap, offset, profile = (getattr(args, f, None) for f in ('thick_gap', 'thick_offset', 'thick_profile'))
+    interp = bool(getattr(args, 'thick_interp', False))
+    if L is None:
+        for flag, given in (('--thick_gap', gap is not None), ('--thick_offset', offset is not None), ('--thick_profile', profile is not None),
+                            ('--thick_interp', interp)):
+            if given:
+                raise ValueError(f'{flag} needs --known_thick')
+        return None
+    if int(L) != L or not 1 <= L <= MAX_L:
+        raise ValueError(f'--known_thick must be an integer in [1, {MAX_L}] (thin slices per slab), got {L}')
+    cohort = getattr(args, 'manifest', None) is not None or getattr(args, 'brats_root', None) is not None
+    if getattr(args, 'known_volume', None) is None and not cohort:
+        raise ValueError('--known_thick needs --known_volume')
+    if getattr(args, 'known_kspace', None) is not None:
+        raise ValueError('--known_thick cannot be combined with --known_kspace (in-plane undersampling of thick slices is out of scope)')
+    if getattr(args, 'known_mask', None) is not None:
+        raise ValueError('--known_thick cannot be combined with --known_mask (a thick slice is measured whole; use --known_drop_slices '
+                         'for thick slices that were not acquired)')
+    gap, offset = 0 if gap is None else gap, 0 if offset is None else offset
+    if int(gap) != gap or gap < 0:
+        raise ValueError(f'--thick_gap must be an integer >= 0, got {gap}')
+    if int(offset) != offset or offset < 0:
+        raise ValueError(f'--thick_offset must be an integer >= 0, got {offset}')
+    profile = 'box' if profile is None else profile
+    if profile not in PROFILES:
+        raise ValueError(f'--thick_profile must be one of {PROFILES}, got {profile!r}')
+    seed = getattr(args, 'seed', 0)
+    if not 0 <= int(seed) < 1 << 64:
+        raise ValueError('--known_thick needs a --seed in [0, 2^64) (its draws are keyed)')
+    return dict(L=int(L), gap=int(gap), offset=int(offset), profile=profile, interp=interp)
+
+
+# ---------------------------------------------------------------------------------------------------
+# the profile and the layout: numpy, functions of the flags alone
+# ---------------------------------------------------------------------------------------------------
+def profile_weights(L, profile='box'):
+    """fp64 [L], w_l > 0, sum 1.  box: 1 / L; gauss: w_l ~ exp(-4 ln 2 (l - (L - 1) / 2)^2 / L^2), a Gaussian of FWHM = L slices."""
+    L = int(L)
+    if not 1 <= L <= MAX_L:
+        raise ValueError(f'profile_weights: L must be in [1, {MAX_L}], got {L}')
+    if profile == 'box':
+        w = np.ones(L, np.float64)
+    elif profile == 'gauss':
+        d = np.arange(L, dtype=np.float64) - (L - 1) / 2.0
+        w = np.exp(-4.0 * math.log(2.0) * d * d / float(L * L))
+        w = 0.5 * (w + w[::-1])                          # symmetric to the bit
+    else:
+        raise ValueError(f'profile_weights: profile must be one of {PROFILES}, got {profile!r}')
+    return w / w.sum()
+
+
+def layout(Z, L, gap=0, offset=0):
+    """The slabs of a volume of Z thin slices: [(first, last, complete)] with first = offset + j (L + gap) < Z; a last slab that the volume
+    cuts short has last = Z - 1 and complete False (it is never measured)."""
+    Z, L, gap, offset = int(Z), int(L), int(gap), int(offset)
+    if L < 1 or gap < 0 or offset < 0:
+        raise ValueError(f'layout: need L >= 1, gap >= 0 and offset >= 0, got {L}, {gap}, {offset}')
+    return [(z, min(z + L, Z) - 1, z + L <= Z) for z in range(offset, Z, L + gap)]
+
+
+def batches(units, B, flag='--batch_size'):
+    """units: the run's items in order, grouped: a list of lists, each inner list the items that must share a batch (a measured slab's
+    thin slices; one item for a free slice).  -> [(items of the batch, in order)] of at most B items each: a batch is closed early before
+    a unit that would not fit.  ValueError naming `flag` for a unit longer than B."""
+    out, cur = [], []
+    for u in units:
+        if len(u) > B:
+            raise ValueError(f'{flag} {B} is smaller than a slab of {len(u)} thin slices: a measured slab must travel in one batch')
+        if len(cur) + len(u) > B:
+            out.append(cur)
+            cur = []
+        cur = cur + list(u)
+    if cur:
+        out.append(cur)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# the measurement of one prediction
+# ---------------------------------------------------------------------------------------------------
+class ThickMeasurement:
+    """What the samplers take for one prediction of n thin slices (the sampled range s0..s1; local index i = slice s0 + i): `y` fp32
+    [G,S,S] on the device, the measured slabs' averages; `starts` [G], each measured slab's first local index; `group_of` int [n], the
+    measured slab of a slice or -1; `weights`, `gains` fp32 [L] (numpy: the host tables of ops.slab_constrain); `report`: thick_<t>.json;
+    `resample`: --known_resample.  A later intake of really thick data only has to fill the same fields."""
+
+    def __init__(self, y, starts, n, weights, report, resample, options):
+        from . import ops
+        self.y, self.starts, self.n, self.report, self.resample, self.options = y, [int(s) for s in starts], int(n), report, int(resample), options
+        self.weights = np.ascontiguousarray(weights, dtype=np.float32)
+        self.gains = ops.slab_gains(self.weights)[0]
+        self.L = int(self.weights.shape[0])
+        self.group_of = np.full(self.n, -1, np.int64)
+        for g, s in enumerate(self.starts):
+            self.group_of[s:s + self.L] = g
+        self.y_norm = torch.linalg.vector_norm(y.flatten(1), dim=1) if y.shape[0] else torch.zeros(0, device=y.device)
+        self.residual = torch.zeros(y.shape[0], device=y.device, dtype=torch.float32)
+        self.x_norm = torch.zeros_like(self.residual)
+
+    def units(self, lo=0, hi=None):
+        """The local slices lo..hi-1 in order as batches() takes them: a measured slab's L slices together, every other slice alone.
+        ValueError when the range cuts a measured slab."""
+        hi = self.n if hi is None else hi
+        out, i = [], lo
+        while i < hi:
+            g = int(self.group_of[i])
+            if g < 0:
+                out.append([i])
+                i += 1
+                continue
+            s = self.starts[g]
+            if s < lo or s + self.L > hi or i != s:
+                raise ValueError(f'thick slices: the range {lo}..{hi - 1} cuts the measured slab {s}..{s + self.L - 1}')
+            out.append(list(range(s, s + self.L)))
+            i = s + self.L
+        return out
+
+    def for_rows(self, slices, samples=None):
+        """The batch whose row r holds local slice slices[r] (-1: a padded row, in no group) of sample samples[r] (None: all 0) ->
+        (GraphSampler.sample_keyed's `thick` tuple (y, members, weights, gains), the measured slab of each group).  Every measured slab
+        that a row touches must be in the batch whole, per sample; its rows enter the table in slice order."""
+        samples = [0] * len(slices) if samples is None else [int(s) for s in samples]
+        found = {}
+        for r, (i, j) in enumerate(zip(slices, samples)):
+            g = int(self.group_of[i]) if i >= 0 else -1
+            if g >= 0:
+                found.setdefault((g, j), {})[int(i) - self.starts[g]] = r
+        members, gids = [], []
+        for (g, j), rows in found.items():
+            if sorted(rows) != list(range(self.L)):
+                raise ValueError(f'thick slices: the batch holds {len(rows)} of the {self.L} thin slices of a measured slab (sample {j})')
+            members.append([rows[l] for l in range(self.L)])
+            gids.append(g)
+        m = np.asarray(members, np.int32).reshape(len(members), self.L)
+        idx = torch.as_tensor(gids, dtype=torch.int64, device=self.y.device)
+        return (self.y.index_select(0, idx), m, self.weights, self.gains), idx
+
+    def record(self, thick, gids, x, x_new=None):
+        """x [B,1,S,S]: what the sampler returned (in [-1,1], before any map) for the batch that for_rows described: keeps, per slab,
+        the largest |A x - y| / |y| seen (an ensemble records every sample), and the largest |A |x_new|| of what the last constraint was
+        given (GraphSampler.thick_x_new; x itself without it): with |y|, what the residual's rounding scales with."""
+        from . import ops
+        if gids.numel() == 0:
+            return
+        x_new = x if x_new is None else x_new
+        ax = ops.slab_average(x_new[:, 0].abs().contiguous(), thick[1], thick[2])
+        self.x_norm.scatter_reduce_(0, gids, torch.linalg.vector_norm(ax.flatten(1), dim=1), 'amax')
+        d = ops.slab_average(x[:, 0].contiguous(), thick[1], thick[2]) - thick[0]
+        den = self.y_norm.index_select(0, gids)
+        r = torch.where(den > 0, torch.linalg.vector_norm(d.flatten(1), dim=1) / den.clamp_min(1e-30), torch.zeros_like(den))
+        self.residual.scatter_reduce_(0, gids, r, 'amax')
+
+    def interpolated(self):
+        """[n,S,S] in [-1,1] terms: piecewise linear along z through (slab centre, y_j) over the measured slabs, constant beyond the first
+        and the last centre - the thick slices as one would resample them without the model.  Without a measured slab: -1 everywhere."""
+        G, S = self.y.shape[0], self.y.shape[-1]
+        if G == 0:
+            return torch.full((self.n, S, S), -1.0, device=self.y.device)
+        centres = np.asarray(self.starts, np.float64) + (self.L - 1) / 2.0
+        z = np.arange(self.n, dtype=np.float64)
+        hi = np.clip(np.searchsorted(centres, z, side='right'), 1, max(G - 1, 1))
+        lo = hi - 1
+        hi = np.minimum(hi, G - 1)
+        span = np.where(hi > lo, centres[hi] - centres[lo], 1.0)
+        f = np.clip((z - centres[lo]) / span, 0.0, 1.0)
+        f = torch.from_numpy(f.astype(np.float32)).to(self.y.device)[:, None, None]
+        ya = self.y.index_select(0, torch.from_numpy(lo).to(self.y.device))
+        yb = self.y.index_select(0, torch.from_numpy(hi).to(self.y.device))
+        return ((1.0 - f) * ya + f * yb).contiguous()
+
+    def finish(self):
+        """The report with the residuals put in (None for a slab that was not measured)."""
+        res, yn, xn = self.residual.cpu().tolist(), self.y_norm.cpu().tolist(), self.x_norm.cpu().tolist()
+        g = 0
+        for s in self.report['slabs']:
+            s['residual'], s['y_norm'], s['x_norm'] = (res[g], yn[g], xn[g]) if s['measured'] else (None, None, None)
+            g += 1 if s['measured'] else 0
+        self.report['max_residual'] = max(res, default=None)
+        return self.report
+
+
+def measure(region, s0, s1, size, options, device):
+    """known_region.KnownRegion (K on the prediction's grid: --norm applied, its known mask = coverage AND finite AND not dropped AND
+    sampled range) -> ThickMeasurement for the thin slices s0..s1 on the S x S sampler grid."""
+    from . import known_region as KR
+    from . import ops
+    S, L = int(size), options['L']
+    s0, s1 = int(s0), int(s1)
+    k, vmask = KR.sampler_inputs(region, s0, s1, S, device)                      # [n,1,S,S] each, resized like the conditions
+    n = int(k.shape[0])
+    whole = [bool(v) for v in (vmask.flatten(1).min(1).values != 0).cpu().tolist()]      # every pixel of the slice known
+    w = profile_weights(L, options['profile'])
+    slabs, starts = [], []
+    for first, last, complete in layout(region.mask.shape[2], L, options['gap'], options['offset']):
+        measured = complete and first >= s0 and last <= s1 and all(whole[first - s0:last - s0 + 1])
+        slabs.append(dict(first=first, last=last, measured=bool(measured)))
+        if measured:
+            starts.append(first - s0)
+    w32 = w.astype(np.float32)
+    if starts:
+        members = np.asarray([list(range(s, s + L)) for s in starts], np.int32)
+        y = ops.slab_average(k[:, 0].contiguous(), members, w32)
+    else:
+        y = torch.zeros(0, S, S, device=device, dtype=torch.float32)
+    report = dict(L=L, gap=options['gap'], offset=options['offset'], profile=options['profile'], weights=[float(v) for v in w32],
+                  sum_w2=float((w32.astype(np.float64) ** 2).sum()), image_size=S, slab=[s0, s1], slabs=slabs, measured_slabs=len(starts),
+                  drop_slices=region.report['drop_slices'], resample=region.resample, resampled=region.report['resampled'])
+    return ThickMeasurement(y, starts, n, w32, report, region.resample, options)
+
+
+def suffix(measurement):
+    """What a [done] line gains (nothing without --known_thick)."""
+    if measurement is None:
+        return ''
+    r = measurement.report
+    return f" | thick={r['L']}+{r['gap']} {r['profile']} ({r['measured_slabs']}/{len(r['slabs'])} slabs)"
+
+
+def write_json(measurement, output_dir, target):
+    path = os.path.join(output_dir, f'thick_{target.lower()}.json')
+    with open(path, 'w') as f:
+        json.dump(measurement.finish(), f, indent=1)
+    return path

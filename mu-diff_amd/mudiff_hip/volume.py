@@ -291,7 +291,8 @@ def calibrate_volume(args, gen1, gen2, cond_stacks, device, batch_size=32):
 
 
 def predict_slices(args, gen1, gen2, cond_stacks, device, batch_size=32, x_inits=None, zs=None, noises=None, seed=None,
-                   use_graph=True, progress=None, sampler=None, return_device=False, coupling=None, known=None, resample=1, kspace=None):
+                   use_graph=True, progress=None, sampler=None, return_device=False, coupling=None, known=None, resample=1, kspace=None,
+                   thick=None):
     """cond_stacks: three float arrays [n,X,Y] in [-1,1] (the condition contrasts, already normalised and sliced), or three device
     tensors [n,1,S,S] (volume_intake.condition_from_raw).  -> [n,S,S] float32 numpy in [0,1], S = args.image_size; with `return_device`
     the device tensor instead (no copy to the host).
@@ -311,7 +312,11 @@ def predict_slices(args, gen1, gen2, cond_stacks, device, batch_size=32, x_inits
     known stack and mask; it needs a seed and the captured sampler as a coupling does (ValueError otherwise).
     `kspace` (--known_kspace; mudiff_hip.kspace): None, or a kspace.KSpaceMeasurement for these n slices: the same
     keyed road with GraphSampler.sample_keyed's `kspace`; what the sampler returns is handed to its `record` before the [0,1] map.
-    Exclusive with `known`; `resample` serves either."""
+    Exclusive with `known`; `resample` serves either.
+    `thick` (--known_thick; mudiff_hip.thick): None, or a thick.ThickMeasurement for these n slices: the same keyed
+    road with GraphSampler.sample_keyed's `thick`.  The constraint couples the thin slices of a measured slab, so the batches are formed
+    by thick.batches: a batch is closed early before a slab that would not fit and padded like the last one (a padded row is in no
+    group); a slab longer than the captured batch is a ValueError naming --batch_size.  Exclusive with `known` and `kspace`."""
     from . import ops
     from . import sampling as S
     from .slice_coupling import check_coupling
@@ -323,6 +328,13 @@ def predict_slices(args, gen1, gen2, cond_stacks, device, batch_size=32, x_inits
             raise ValueError('predict_slices: injected x_inits / zs / noises cannot be combined with k-space measurements (their draws are keyed)')
         if seed is None or not use_graph:
             raise ValueError('predict_slices: k-space measurements need a seed and the captured sampler (use_graph=True)')
+    if thick is not None:
+        if known is not None or kspace is not None:
+            raise ValueError('predict_slices: thick is exclusive with known and kspace')
+        if x_inits is not None or zs is not None or noises is not None:
+            raise ValueError('predict_slices: injected x_inits / zs / noises cannot be combined with thick-slice measurements (their draws are keyed)')
+        if seed is None or not use_graph:
+            raise ValueError('predict_slices: thick-slice measurements need a seed and the captured sampler (use_graph=True)')
     if coupling is not None:
         if x_inits is not None or zs is not None or noises is not None:
             raise ValueError('predict_slices: injected x_inits / zs / noises cannot be combined with a coupling (its draws are keyed)')
@@ -333,7 +345,7 @@ def predict_slices(args, gen1, gen2, cond_stacks, device, batch_size=32, x_inits
             raise ValueError('predict_slices: injected x_inits / zs / noises cannot be combined with a known region (its draws are keyed)')
         if seed is None or not use_graph:
             raise ValueError('predict_slices: a known region needs a seed and the captured sampler (use_graph=True)')
-    keyed = coupling is not None or known is not None or kspace is not None
+    keyed = coupling is not None or known is not None or kspace is not None or thick is not None
     n = int(cond_stacks[0].shape[0])
     size = int(args.image_size)
     if n == 0:
@@ -367,6 +379,23 @@ def predict_slices(args, gen1, gen2, cond_stacks, device, batch_size=32, x_inits
             x_inits = torch.randn(n, 1, size, size, device=device, generator=gen)
         zs = [torch.randn(n, args.nz, device=device, generator=gen) for _ in range(T)]
         noises = [torch.randn(n, 1, size, size, device=device, generator=gen) for _ in range(T)]
+    if thick is not None:                    # batches that keep a measured slab whole; row r of a batch is slice items[r], padded by the last
+        from .thick import batches
+        if thick.n != n:
+            raise ValueError(f'predict_slices: the thick-slice measurement is of {thick.n} slices, the conditions of {n}')
+        done = 0
+        for items in batches(thick.units(), bs):
+            idx = torch.as_tensor(items + [items[-1]] * (bs - len(items)), dtype=torch.int64)
+            keys = torch.stack([idx, torch.zeros(bs, dtype=torch.int64)], 1)
+            th, gids = thick.for_rows(items + [-1] * (bs - len(items)))
+            idx = idx.to(device)
+            fake = sampler.sample_keyed(*(c.index_select(0, idx) for c in conds), keys, seed, T, coupling=coupling, thick=th, resample=resample)
+            thick.record(th, gids, fake, sampler.thick_x_new)
+            out[idx[:len(items)]] = ops.to_range_0_1(fake)[:len(items), 0]
+            done += len(items)
+            if progress:
+                progress(done, n)
+        return out if return_device else out.cpu().numpy()
     for lo in range(0, n, bs):
         hi = min(lo + bs, n)
         c1, c2, c3 = (padded(c, lo, hi) for c in conds)
@@ -413,7 +442,9 @@ def predict_volume(args):
     prediction and the scores gain the regions known / synthesised (mudiff_hip.known_region).  With --known_kspace
     that volume was acquired undersampled in k-space instead: its measured Fourier coefficients condition the sampling, nothing is pasted,
     and kspace_<target>.json (under --kspace_zero_filled also zero_filled_<target>.nii.gz) goes next to the prediction (mudiff_hip.kspace,
-    DESIGN.md section 5.26)."""
+    DESIGN.md section 5.26).  With --known_thick it was acquired with thick slices: the slab averages condition the sampling, nothing is
+    pasted, and thick_<target>.json (under --thick_interp also thick_interp_<target>.nii.gz) goes next to the prediction (mudiff_hip.thick,
+    DESIGN.md section 5.27)."""
     evaluation, resampled, found = _load_eval_inputs(args)
     args = copy.copy(args)                               # the run's own copy: it carries the record of what the intake did
     args.evaluation_record = (resampled, found)          # (for _predict_volume's report: IntakeReport.add_evaluation)
@@ -550,9 +581,10 @@ def _done_tail(args, plan):
     from .known_region import suffix as known_suffix
     from .kspace import suffix as kspace_suffix
     from .slice_coupling import suffix
+    from .thick import suffix as thick_suffix
     return (('' if plan == 'auto' else f' | prec_plan={plan}') + norm_suffix(args.norm) + _intake_report(args).suffix() +
             suffix(getattr(args, 'slice_coupling', None)) + done_suffix(args) + known_suffix(getattr(args, 'known_region', None)) +
-            kspace_suffix(getattr(args, 'kspace', None)))
+            kspace_suffix(getattr(args, 'kspace', None)) + thick_suffix(getattr(args, 'thick', None)))
 
 
 class _Stages:
@@ -623,6 +655,7 @@ def predict_from_conditions(args, plan, evaluation, gen1, gen2, device, stacks, 
         KR.write_json(region, args.output_dir, args.target_modality)
     stages.run('write', lambda: write(out_path, vol_pred, aff, hdr))
     _kspace_outputs(args, write, lambda p: _assemble_map(p, shp, s0, s1, on_device), aff, hdr, evaluation, device)
+    _thick_outputs(args, write, lambda p: _assemble_map(p, shp, s0, s1, on_device), aff, hdr, evaluation, device)
     _intake_report(args).write(args.output_dir, args.target_modality, aff, hdr)
     print(f'[done] saved: {out_path} | shape={tuple(vol_pred.shape)} | slices={s0}..{s1}' + _done_tail(args, plan))
     if evaluation is not None:
@@ -635,12 +668,17 @@ def _known_region(args, ref, device):
     """--known_volume: (the run's known_region.KnownRegion, also left in args.known_region for the [done] line and the scores; what
     predict_slices and sample_ensemble take for it) - or (None, {}) without the flag."""
     inputs = getattr(args, 'known_inputs', None)
-    args.known_region = args.kspace = None
+    args.known_region = args.kspace = args.thick = None
     if inputs is None:
         return None, {}
     from . import known_region as KR
     from . import kspace as KS
+    from . import thick as TK
     region = KR.compose(inputs, ref, args.norm, device)
+    options = TK.options_from(args)
+    if options is not None:       # --known_thick: K is measured in thick slices instead; no known region, no paste (mudiff_hip.thick)
+        args.thick = TK.measure(region, ref[3], ref[4], int(args.image_size), options, device)
+        return None, dict(thick=args.thick, resample=region.resample)
     options = KS.options_from(args)
     if options is not None:       # --known_kspace: K is measured in k-space instead; no known region, no paste (mudiff_hip.kspace)
         args.kspace = KS.measure(region, ref[3], ref[4], int(args.image_size), options, args.seed, device)
@@ -682,6 +720,37 @@ def _kspace_outputs(args, write, put_together, aff, hdr, evaluation, device):
         for ln in VM.format_lines(rep):
             print('[zero-filled] ' + ln)
         print(f"[metrics] wrote {VM.write_json(rep, os.path.join(args.output_dir, f'metrics_zero_filled_{target}.json'))}")
+
+
+def _thick_outputs(args, write, put_together, aff, hdr, evaluation, device):
+    """--known_thick: thick_<t>.json next to the prediction, and under --thick_interp thick_interp_<t>.nii.gz = the thick slices
+    interpolated linearly along z, mapped to [0,1], through the prediction's own road (`put_together`: a device [n,S,S] map -> the host
+    volume as written); with an evaluation it is scored into metrics_thick_interp_<t>.json, and under --through_plane its roughness goes
+    to through_plane_thick_interp_<t>.json, beside the prediction's.  Nothing without the flag."""
+    meas = getattr(args, 'thick', None)
+    if meas is None:
+        return
+    from . import ops
+    from . import thick as TK
+    target = args.target_modality.lower()
+    print(f'[thick] wrote {TK.write_json(meas, args.output_dir, args.target_modality)}')
+    if not meas.options['interp']:
+        return
+    vol = put_together(ops.to_range_0_1(meas.interpolated()))
+    path = os.path.join(args.output_dir, f'thick_interp_{target}.nii.gz')
+    write(path, vol, aff, hdr)
+    print(f'[thick] wrote {path}')
+    if evaluation is not None:
+        from . import volume_metrics as VM
+        rep = VM.score_arrays(vol, evaluation[0], evaluation[1], None, args.slice_half_range, device, norm=args.norm)
+        for ln in VM.format_lines(rep):
+            print('[thick-interp] ' + ln)
+        print(f"[metrics] wrote {VM.write_json(rep, os.path.join(args.output_dir, f'metrics_thick_interp_{target}.json'))}")
+    if getattr(args, 'through_plane', False):
+        from . import volume_through_plane as TP
+        rep = TP.measure_arrays(vol, None if evaluation is None else evaluation[0], None, args.slice_half_range, device, norm=args.norm)
+        print('[thick-interp] ' + TP.format_line(rep))
+        print(f"[through-plane] wrote {TP.write_json(rep, os.path.join(args.output_dir, f'through_plane_thick_interp_{target}.json'))}")
 
 
 def _coupling(args):
@@ -767,6 +836,7 @@ def _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref, evaluation=N
         stages.run('write', lambda: write(path, vol, aff, hdr))
         paths.append(path)
     _kspace_outputs(args, write, lambda p: _assemble_map(p, shp, s0, s1, on_device), aff, hdr, evaluation, device)
+    _thick_outputs(args, write, lambda p: _assemble_map(p, shp, s0, s1, on_device), aff, hdr, evaluation, device)
     _intake_report(args).write(args.output_dir, args.target_modality, aff, hdr)
     print(f'[done] saved: {paths[0]} and {paths[1]} | shape={tuple(shp)} | slices={s0}..{s1} | {args.num_samples} samples per slice' +
           _done_tail(args, effective_prec_plan(args)))
@@ -888,6 +958,8 @@ def make_parser(prog='MU-Diff volume prediction (MI355X)'):
     slice_coupling.add_flags(p)             # (--slice_coupling, --through_plane: in a late parser, VolumeParser.later())
     from . import kspace
     kspace.add_flags(p)                     # (--known_kspace and the --kspace_* flags: in one of their own, before the last two, whose places are pinned)
+    from . import thick
+    thick.add_flags(p)                      # (--known_thick and the --thick_* flags: in one more parser, before the last three)
     from . import known_region
     known_region.add_flags(p)               # (--known_volume and its three: in one of their own, before the last)
     from . import ensemble
@@ -924,6 +996,11 @@ def finish_args(p, args):
         kspace.options_from(args)                        # (its ValueError names the flag)
     except ValueError as e:
         p.error(str(e))
+    from . import thick
+    try:
+        thick.options_from(args)                         # (its ValueError names the flag)
+    except ValueError as e:
+        p.error(str(e))
     from . import volume_conform as VCF
     from . import volume_reorient as VO
     from .volume_prepare import STAGES
@@ -951,7 +1028,8 @@ def build_argparser(argv=None):
     DESIGN.md section 5.23; in a further late parser), and --ensemble_quantiles / --ensemble_center / --coverage (mudiff_hip.ensemble,
     mudiff_hip.volume_coverage; in one more), and --known_volume / --known_mask / --known_drop_slices /
     --known_resample (mudiff_hip.known_region; in a parser of their own before that last one), and --known_kspace
-    with the --kspace_* flags (mudiff_hip.kspace; in one more parser, before those two)."""
+    with the --kspace_* flags (mudiff_hip.kspace; in one more parser, before those two), and --known_thick with
+    the --thick_* flags (mudiff_hip.thick; in one more, after that one)."""
     p = make_parser()
     return finish_args(p, p.parse_args(argv))
 
