@@ -29,10 +29,9 @@ too (volume_prepare.evaluation_inputs); the prefetch thread only reads them (vol
 thread, the compression and the write on the pool.  A subject whose manifest row has a `known` (and `known_mask`) cell is sampled with
 that subject's --known_volume / --known_mask (mudiff_hip.known_region; --known_drop_slices and --known_resample
 come from the command line): known_<t>.json goes next to its prediction and the regions known / synthesised join the aggregate.  Under
---known_kspace (and the --kspace_* flags, all from the command line) that `known` volume was acquired undersampled in k-space instead
-(mudiff_hip.kspace): kspace_<t>.json goes next to the prediction, and a `known_mask` cell fails that subject.
-Under --known_thick (and the --thick_* flags, from the command line too) it was acquired with thick slices (mudiff_hip.thick, DESIGN.md
-section 5.27): thick_<t>.json goes next to the prediction, and a `known_mask` cell fails that subject.
+--known_kspace or --known_thick (and the --kspace_* / --thick_* flags, all from the command line) that `known` volume was acquired
+undersampled in k-space or with thick slices instead (mudiff_hip.kspace, mudiff_hip.thick; DESIGN.md sections 5.26, 5.27):
+kspace_<t>.json or thick_<t>.json goes next to the prediction, and a `known_mask` cell fails that subject.
 """
 from __future__ import annotations
 
@@ -258,11 +257,7 @@ def run(args, subjects, predict=None):
                     if subject.known:                              # (the subject's --known_volume: mudiff_hip.known_region)
                         from . import known_region as KR
                         sargs.known_volume, sargs.known_mask = subject.known, subject.known_mask
-                        known = KR.options_from(sargs)
-                        from . import kspace as KS
-                        KS.options_from(sargs)                     # (--known_kspace: K is measured in k-space; a known_mask cell is refused)
-                        from . import thick as TK
-                        TK.options_from(sargs)                     # (--known_thick: K was acquired with thick slices; the same refusal)
+                        known = [module.options_from(sargs) for module in V.known_modes()][0]      # (each mode's own refusals)
                         sargs.known_inputs = KR.on_grid(raws[0], KR.read_inputs(known, options), known, options, gpu, align=found.get('align'))
                         report.add_evaluation(list(sargs.known_inputs.resampled), {})
                     sargs.intake_report = report                   # (the [done] line names what it lists)

@@ -1,0 +1,172 @@
+"""What the three ways of sampling a partly acquired target share (--known_volume, --known_kspace, --known_thick; DESIGN.md section
+5.24a): after every reverse step the result is projected onto what was measured, at that step's noise level, with a keyed draw.
+
+A *prediction-level* constraint (Constraint: KnownVoxels here, kspace.KSpaceMeasurement, thick.ThickMeasurement) describes the n slices
+one prediction samples; volume.predict_slices and ensemble.sample_ensemble form their batches from it and know nothing else of it.
+Its for_rows gives the *batch-level* constraint of one captured batch (KnownRows, KSpaceRows, SlabRows): `check(sampler)`, once, and
+`apply(sampler, x_new, keys_dev, seed, step, clean)`, one unchecked launch into sampler.x per executed step, for GraphSampler.sample_keyed."""
+from __future__ import annotations
+
+import collections
+import json
+import os
+
+import torch
+
+from . import ops
+
+
+def batches(units, B, flag='--batch_size'):
+    """units: the run's items in order, grouped: a list of lists, each inner list the items that must share a batch (a measured slab's
+    thin slices; one item for a free slice).  -> [(items of the batch, in order)] of at most B items each: a batch is closed early before
+    a unit that would not fit.  ValueError naming `flag` for a unit longer than B."""
+    out, cur = [], []
+    for u in units:
+        if len(u) > B:
+            raise ValueError(f'{flag} {B} is smaller than a slab of {len(u)} thin slices: a measured slab must travel in one batch')
+        if len(cur) + len(u) > B:
+            out.append(cur)
+            cur = []
+        cur = cur + list(u)
+    if cur:
+        out.append(cur)
+    return out
+
+
+class Constraint:
+    """A prediction-level constraint over the local slices 0..n-1, and its defaults: no constraint at all (FREE).
+    `for_rows(slices, samples, m)` -> the batch-level constraint of the batch whose row r holds local slice slices[r] of sample samples[r]
+    (None: all 0); the first m rows are real, the others padding that repeats the last item.  `record(bound, x, x_new)` takes what the
+    sampler returned for that batch, x [B,1,S,S], and the sampler's thick_x_new.  A measurement with a report of its own
+    (volume._measurement_outputs) also declares `tag` (its log tag and its report's file name; `finish()` is the report), `baseline()`
+    (None, or (file name stem, [n,S,S] map in [-1,1] terms): what one would have without the model) and `baseline_through_plane`."""
+    n, resample, tag, baseline_through_plane = None, 1, None, False
+
+    def done_suffix(self):
+        return ''                            # what a [done] line gains
+
+    def over(self, n, who):
+        if self.n not in (None, n):
+            raise ValueError(f'{who}: the constraint is of {self.n} slices, the conditions of {n}')
+
+    def units(self, lo, hi):
+        return [[i] for i in range(lo, hi)]  # the local slices lo..hi-1 in order, grouped into the lists that must share a batch
+
+    def chunk_end(self, s0, s1):
+        return s1                            # where an ensemble's chunk that starts at s0 and would end before s1 may end
+
+    def for_rows(self, slices, samples, m):
+        return None
+
+    def record(self, bound, x, x_new):
+        return None
+
+    def write_json(self, output_dir, target):
+        path = os.path.join(output_dir, f'{self.tag}_{target.lower()}.json')
+        with open(path, 'w') as f:
+            json.dump(self.finish(), f, indent=1)
+        return path
+
+
+FREE = Constraint()
+
+
+class KnownVoxels(Constraint):
+    """--known_volume for the samplers: known_region.sampler_inputs' pair.  A padded row repeats the last item's stack and mask."""
+
+    def __init__(self, known, mask, resample=1):
+        self.known, self.mask, self.resample = known, mask, int(resample)
+        self.n = None if known is None else int(known.shape[0])
+
+    def for_rows(self, slices, samples, m):
+        idx = torch.as_tensor(slices, dtype=torch.int64, device=self.known.device)
+        return KnownRows(self.known.index_select(0, idx), self.mask.index_select(0, idx))
+
+
+def of_prediction(who, constraint, known, kspace, thick, resample):
+    """The keywords of volume.predict_slices / ensemble.sample_ensemble, `known` = (known, mask) -> (the one prediction-level constraint
+    or FREE, resample: a `constraint`'s own, else the keyword).  ValueError for more than one."""
+    given = [v for v in (constraint, known, kspace, thick) if v is not None]
+    if len(given) > 1:
+        raise ValueError(f'{who}: known, kspace and thick are mutually exclusive')
+    if not given:
+        return FREE, 1
+    con = given[0] if known is None else KnownVoxels(known[0], known[1], resample)
+    return con, con.resample if constraint is not None else resample
+
+
+class KnownRows(collections.namedtuple('KnownRows', 'known mask')):
+    """GraphSampler.sample_keyed's `known`, `known_mask`: [B,1,H,W] fp32 and uint8."""
+
+    def check(self, sampler):
+        (known, mask), shape = self, tuple(sampler.x.shape)
+        if mask is None:
+            raise ValueError('GraphSampler.sample_keyed: known needs known_mask')
+        if tuple(known.shape) != shape or tuple(mask.shape) != shape or mask.dtype != torch.uint8:
+            raise ValueError(f'GraphSampler.sample_keyed: known (fp32) and known_mask (uint8) must be {shape}, got '
+                             f'{tuple(known.shape)} and {mask.dtype} {tuple(mask.shape)}')
+        self.dev = known.to(sampler.x.device, torch.float32).contiguous(), mask.to(sampler.x.device).contiguous()
+
+    def apply(self, sampler, x_new, keys_dev, seed, step, clean):
+        dc = sampler._diffusion_tables()
+        ops.known_constrain_into(sampler.x, x_new, *self.dev, keys_dev, seed, step, ops.KIND_KNOWN, sampler.t, 0, dc[0], dc[1], clean=clean)
+
+
+class KSpaceRows(collections.namedtuple('KSpaceRows', 'y mask idx', defaults=(None,))):
+    """GraphSampler.sample_keyed's `kspace`: y complex64 [B,S,S], mask uint8 [1 or B,S,S].  `idx`: the local slices of the real rows
+    (KSpaceMeasurement.for_rows; None from the keyword)."""
+
+    def check(self, sampler):
+        B, H, W = sampler.B, sampler.H, sampler.W
+        if H != W or not ops.kspace_size_ok(H):
+            raise ValueError(f'GraphSampler.sample_keyed: kspace needs a square grid whose size is a power of two in [16, 512], got {H} x {W}')
+        (y, mask, _), want = self, (B, H, W)
+        if y.dtype != torch.complex64 or tuple(y.shape) != want or mask.dtype != torch.uint8 or tuple(mask.shape) not in (want, (1,) + want[1:]):
+            raise ValueError(f'GraphSampler.sample_keyed: kspace = (y complex64 {want}, mask uint8 [1 or {B}, {H}, {W}]), got '
+                             f'{y.dtype} {tuple(y.shape)} and {mask.dtype} {tuple(mask.shape)}')
+        self.dev = y.to(sampler.x.device).contiguous(), mask.to(sampler.x.device).contiguous()
+        if getattr(sampler, '_ks_work', None) is None:          # the complex workspace: one per sampler
+            sampler._ks_work = torch.empty(want, device=sampler.x.device, dtype=torch.complex64)
+
+    def apply(self, sampler, x_new, keys_dev, seed, step, clean):
+        dc = sampler._diffusion_tables()
+        ops.kspace_constrain_into(sampler.x, x_new, *self.dev, sampler._ks_work, keys_dev, seed, step, ops.KIND_KSPACE, sampler.t, 0, dc[0],
+                                  dc[1], clean=clean)
+
+
+class SlabRows(collections.namedtuple('SlabRows', 'thick gids')):
+    """GraphSampler.sample_keyed's `thick` = (y fp32 [groups,H,W], members, weights, gains), and `gids`: the measured slab of each group
+    (ThickMeasurement.for_rows; None from the keyword)."""
+
+    def check(self, sampler):
+        y, members, weights, gains = self.thick
+        tab = ops.slab_tables(members, weights, gains)
+        B, want, top = sampler.B, (tab[0].shape[0], sampler.H, sampler.W), int(tab[0].max(initial=-1))
+        if y.dtype != torch.float32 or tuple(y.shape) != want:
+            raise ValueError(f'GraphSampler.sample_keyed: thick y must be fp32 {want}, got {y.dtype} {tuple(y.shape)}')
+        if want[0] > B or tab[0].shape[1] > ops.SLAB_MAX_MEMBERS or top >= B:
+            raise ValueError(f'GraphSampler.sample_keyed: thick names {want[0]} groups of {tab[0].shape[1]} rows up to row {top} for a batch '
+                             f'of {B} (at most {ops.SLAB_MAX_MEMBERS} rows a group)')
+        self.dev = y.to(sampler.x.device).contiguous(), tab
+
+    def apply(self, sampler, x_new, keys_dev, seed, step, clean):
+        dc = sampler._diffusion_tables()
+        ops.slab_constrain_into(sampler.x, x_new, *self.dev, keys_dev, seed, step, ops.KIND_THICK, sampler.t, 0, dc[0], dc[1], clean=clean)
+        sampler.thick_x_new = x_new          # what the last constraint was given (the graph's own buffer, until the next replay)
+
+
+def of_batch(constraint, known, known_mask, kspace, thick, resample):
+    """The keywords of GraphSampler.sample_keyed (`thick`: a tuple, or an object with its attributes) -> the one batch-level constraint
+    or None.  ValueError for more than one, for known_mask without known, and for resample != 1 with none."""
+    given = [v for v in (constraint, known, kspace, thick) if v is not None]
+    if len(given) > 1:
+        raise ValueError('GraphSampler.sample_keyed: known, kspace and thick are mutually exclusive')
+    if known is None and known_mask is not None or not given and resample != 1:
+        raise ValueError('GraphSampler.sample_keyed: known_mask and resample need known (resample: or kspace, or thick)')
+    if known is not None:
+        return KnownRows(known, known_mask)
+    if kspace is not None:
+        return KSpaceRows(*kspace)
+    if thick is not None:
+        return SlabRows(tuple(thick) if isinstance(thick, (tuple, list)) else (thick.y, thick.members, thick.weights, thick.gains), None)
+    return constraint

@@ -45,7 +45,8 @@ def premap(map_0_1):
 
 
 def sample_ensemble(args, gen1, gen2, conds, num_samples, seed, batch_size=32, slice_offset=0, chunk=None, sampler=None, map_0_1=False,
-                    return_samples=False, coupling=None, quantiles=None, known=None, resample=1, kspace=None, thick=None):
+                    return_samples=False, coupling=None, quantiles=None, known=None, resample=1, kspace=None, thick=None,
+                    constraint=None):
     """conds: three device tensors [n,1,S,S] (S = args.image_size) -> (mean, std) device fp32 [n,S,S] over `num_samples` (>= 2) samples
     per slice, plus the raw samples [n,N,S,S] with `return_samples`.  `map_0_1`: the statistics are those of the samples mapped to
     [0,1] (ops.to_range_0_1); the returned samples are never mapped.
@@ -58,19 +59,15 @@ def sample_ensemble(args, gen1, gen2, conds, num_samples, seed, batch_size=32, s
     `quantiles`: a tuple of 1 to 8 fractions in [0, 1] (num_samples <= MAX_QUANTILE_SAMPLES): the per-pixel quantiles of each slice's
     samples under the same pre-map (ops.ensemble_quantiles; 0.5 is the median), taken from the chunk buffer right
     after the statistics, are returned as one more tensor [K,n,S,S] at the end of the tuple.  None returns exactly what it did before.
-    `known`, `resample` (mudiff_hip.known_region): None, or (known [n,1,S,S], mask uint8 [n,1,S,S]) per slice on the
-    device: every sample of slice i is drawn with that slice's known region re-imposed (GraphSampler.sample_keyed's known / known_mask).
-    `kspace` (mudiff_hip.kspace): None, or a kspace.KSpaceMeasurement for these n slices (exclusive with `known`):
-    every sample of slice i keeps that slice's measured coefficients, and each is handed to the measurement's `record`.
-    `thick` (mudiff_hip.thick): None, or a thick.ThickMeasurement for these n slices (exclusive with both): every
-    sample keeps the measured slabs' averages.  The constraint couples the L thin slices of a (slab, sample), so a measured slab's items
-    run sample-major - each sample's L slices together - in batches that thick.batches closes early before a group that would not fit
-    (a padded row is in no group), and a chunk ends before a slab it would cut.  The other paths keep their item order."""
+    `known`, `kspace`, `thick` (at most one): what of the target was acquired - (known [n,1,S,S], mask uint8
+    [n,1,S,S]) per slice on the device, a kspace.KSpaceMeasurement or a thick.ThickMeasurement for these n slices, with `resample` what
+    GraphSampler.sample_keyed takes; or `constraint`, any of them as one object of mudiff_hip.constraints (its own `resample` counts).
+    Every sample of slice i is drawn under it and handed to its `record`.  Thick slices couple the L thin slices of a (slab, sample), so
+    a measured slab's items run sample-major - each sample's L slices together, never split over two batches (constraints.batches) -
+    and a chunk ends before a slab it would cut (the constraint's `chunk_end`).  Free slices keep their item order."""
     from . import sampling as S
-    if known is not None and kspace is not None:
-        raise ValueError('sample_ensemble: known and kspace are mutually exclusive')
-    if thick is not None and (known is not None or kspace is not None):
-        raise ValueError('sample_ensemble: thick is exclusive with known and kspace')
+    from .constraints import batches, of_prediction
+    constraint, resample = of_prediction('sample_ensemble', constraint, known, kspace, thick, resample)
     N = int(num_samples)
     if N < 2:
         raise ValueError(f'sample_ensemble: num_samples must be >= 2, got {N}')
@@ -102,19 +99,12 @@ def sample_ensemble(args, gen1, gen2, conds, num_samples, seed, batch_size=32, s
     every = torch.empty(n, N, size, size, device=device, dtype=torch.float32) if return_samples else None
     qmaps = None if quantiles is None else torch.empty(len(quantiles), n, size, size, device=device, dtype=torch.float32)
     buf = None
-    chunks = [(s0, min(s0 + chunk, n)) for s0 in range(0, n, chunk)]
-    if thick is not None:
-        if thick.n != n:
-            raise ValueError(f'sample_ensemble: the thick-slice measurement is of {thick.n} slices, the conditions of {n}')
-        chunks, s0 = [], 0
-        while s0 < n:                                   # a chunk ends before a measured slab that it would cut
-            s1 = min(s0 + chunk, n)
-            if s1 < n and thick.group_of[s1] >= 0 and thick.group_of[s1] == thick.group_of[s1 - 1]:
-                s1 = thick.starts[int(thick.group_of[s1])]
-            if s1 <= s0:
-                raise ValueError(f'sample_ensemble: a chunk of {chunk} slices is smaller than a slab of {thick.L} thin slices')
-            chunks.append((s0, s1))
-            s0 = s1
+    constraint.over(n, 'sample_ensemble')
+    chunks, s0 = [], 0
+    while s0 < n:
+        s1 = constraint.chunk_end(s0, min(s0 + chunk, n))
+        chunks.append((s0, s1))
+        s0 = s1
     for s0, s1 in chunks:
         if every is not None:
             out = every[s0:s1]
@@ -123,41 +113,20 @@ def sample_ensemble(args, gen1, gen2, conds, num_samples, seed, batch_size=32, s
                 buf = torch.empty(min(chunk, n), N, size, size, device=device, dtype=torch.float32)
             out = buf[:s1 - s0]
         flat = out.view(-1, size, size)
-        if thick is not None:
-            from .thick import batches
-            units = []
-            for u in thick.units(s0, s1):                # a slab: sample-major, each sample's slices one unit; a free slice: slice-major
-                units += [[(i, j) for i in u] for j in range(N)]
-            for items in batches(units, B):
-                m = len(items)
-                sl = torch.as_tensor([i for i, _ in items] + [items[-1][0]] * (B - m), dtype=torch.int64)
-                sm = torch.as_tensor([j for _, j in items] + [items[-1][1]] * (B - m), dtype=torch.int64)
-                keys = torch.stack([sl + int(slice_offset), sm], 1)
-                th, gids = thick.for_rows([i for i, _ in items] + [-1] * (B - m), [j for _, j in items] + [0] * (B - m))
-                idx = sl.to(device)
-                res = sampler.sample_keyed(c1.index_select(0, idx), c2.index_select(0, idx), c3.index_select(0, idx), keys, seed, T,
-                                           coupling=coupling, thick=th, resample=resample)
-                thick.record(th, gids, res, sampler.thick_x_new)
-                flat[((sl[:m] - s0) * N + sm[:m]).to(device)] = res[:m, 0]
-            mean[s0:s1], std[s0:s1] = ops.ensemble_stats(out, scale, shift, lo, hi)
-            if qmaps is not None:
-                qmaps[:, s0:s1] = ops.ensemble_quantiles(out, quantiles, scale, shift, lo, hi)
-            continue
-        q0, q1 = s0 * N, s1 * N                                  # items of this chunk, slice-major
-        for b0 in range(q0, q1, B):
-            m = min(B, q1 - b0)
-            items = torch.arange(b0, b0 + B).clamp_(max=b0 + m - 1)          # padding repeats the last item
-            sl = items // N
-            keys = torch.stack([sl + int(slice_offset), items % N], 1)
+        units = []
+        for u in constraint.units(s0, s1):
+            units += [[(i, j) for i in u] for j in range(N)]      # a free slice: slice-major; a slab: sample-major, each sample's slices one unit
+        for items in batches(units, B):
+            m = len(items)
+            items = items + [items[-1]] * (B - m)                    # padding repeats the last item
+            sl, sm = (torch.as_tensor(v, dtype=torch.int64) for v in zip(*items))
+            keys = torch.stack([sl + int(slice_offset), sm], 1)
+            bound = constraint.for_rows([i for i, _ in items], [j for _, j in items], m)
             idx = sl.to(device)
-            more = {} if known is None else dict(known=known[0].index_select(0, idx), known_mask=known[1].index_select(0, idx), resample=resample)
-            if kspace is not None:
-                more = dict(kspace=(kspace.y.index_select(0, idx), kspace.mask.index_select(0, idx)), resample=resample)
             res = sampler.sample_keyed(c1.index_select(0, idx), c2.index_select(0, idx), c3.index_select(0, idx), keys, seed, T, coupling=coupling,
-                                       **more)
-            if kspace is not None:
-                kspace.record(idx[:m], res[:m])
-            flat[b0 - q0:b0 - q0 + m] = res[:m, 0]
+                                       constraint=bound, resample=resample)
+            constraint.record(bound, res, sampler.thick_x_new)
+            flat[((sl[:m] - s0) * N + sm[:m]).to(device)] = res[:m, 0]
         mean[s0:s1], std[s0:s1] = ops.ensemble_stats(out, scale, shift, lo, hi)
         if qmaps is not None:
             qmaps[:, s0:s1] = ops.ensemble_quantiles(out, quantiles, scale, shift, lo, hi)

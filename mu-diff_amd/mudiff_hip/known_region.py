@@ -205,6 +205,18 @@ def sampler_inputs(region, s0, s1, size, device):
     return known.contiguous(), mask.contiguous()
 
 
+def constraint_for(region, s0, s1, size, args, device):
+    """What the samplers take for the run's K (mudiff_hip.constraints): under --known_thick or --known_kspace K is measured that way
+    instead (thick.measure, kspace.measure), else its known voxels themselves (constraints.KnownVoxels of sampler_inputs)."""
+    from . import kspace, thick
+    from .constraints import KnownVoxels
+    for module, more in ((thick, ()), (kspace, (args.seed,))):
+        options = module.options_from(args)
+        if options is not None:
+            return module.measure(region, s0, s1, size, options, *more, device)
+    return KnownVoxels(*sampler_inputs(region, s0, s1, size, device), region.resample)
+
+
 def paste(vol, region, device, std=False):
     """A map as it is about to be written (host [X,Y,Z], fp32) with the known voxels put in (mud_known_constrain, clean): region.k01, or 0
     for an ensemble's std -> a new host array of the same shape."""

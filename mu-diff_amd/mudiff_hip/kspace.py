@@ -12,8 +12,7 @@ F is the unitary 2D DFT on the sampler's S x S grid (S = --image_size, a power o
 per volume, numpy, a function of the flags and --seed alone.  k is real, so F(k) is Hermitian and a measured coefficient gives its
 mirror: the sampler works with M_eff[u,v] = M[u,v] | M[-u mod S, -v mod S], and the report holds both sampling fractions.  After the
 reverse step executed with t = i the measured coefficients of x are replaced by those of q_sample(k, i), after the last by y itself
-(GraphSampler.sample_keyed's `kspace`; the draw is kind ops.KIND_KSPACE, keyed by the true (slice, sample), never slice-coupled).
---known_resample R works as it does with --known_volume.
+(GraphSampler.sample_keyed's `kspace`, kind ops.KIND_KSPACE; the draw and --known_resample: mudiff_hip.constraints, section 5.24a).
 
 A slice is measured when K is finite and fully covered on it after resampling (known_region's coverage) and --known_drop_slices does
 not name it: `this slice was not measured` is a zero mask row, and the slice is sampled freely.  --known_mask is refused: a voxel mask
@@ -28,11 +27,12 @@ data is out of scope.
 """
 from __future__ import annotations
 
-import json
 import os
 
 import numpy as np
 import torch
+
+from .constraints import Constraint, KSpaceRows
 
 PATTERNS = ('equispaced', 'random', 'lowres', 'file')
 DEFAULT_ACCEL, DEFAULT_CENTER, DEFAULT_AXIS = 4, 0.08, 0
@@ -153,21 +153,33 @@ def symmetrise(mask):
 # ---------------------------------------------------------------------------------------------------
 # the measurement of one prediction
 # ---------------------------------------------------------------------------------------------------
-class KSpaceMeasurement:
+class KSpaceMeasurement(Constraint):
     """What the samplers take for one prediction: `y` complex64 [n,S,S] = M_eff * F(k) and `mask` uint8 [n,S,S] (M_eff on a measured
     slice, zeros on one that is not) on the device, n the slab's slices; `report`: kspace_<t>.json; `resample`: --known_resample.
     `record` collects the data-consistency residual of what the sampler returned."""
 
     def __init__(self, y, mask, report, resample, options):
         self.y, self.mask, self.report, self.resample, self.options = y, mask, report, int(resample), options
+        self.n = int(y.shape[0])
         self.y_norm = torch.linalg.vector_norm(y.flatten(1), dim=1)
         self.residual = torch.zeros(y.shape[0], device=y.device, dtype=torch.float32)
         self.x_norm = torch.zeros_like(self.residual)
 
-    def record(self, idx, x):
-        """x [m,1,S,S]: the sampler's results (in [-1,1], before any map) for the slab's slices idx (int64 [m], device): keeps, per
-        slice, the largest |M_eff * (F(x) - y)| / |y| seen (an ensemble records every sample)."""
+    tag = 'kspace'
+    done_suffix = lambda self: suffix(self)      # noqa: E731
+    baseline = lambda self: ('zero_filled', self.zero_filled()) if self.options['zero_filled'] else None      # noqa: E731
+
+    def for_rows(self, slices, samples, m):
+        """A padded row (from m on) repeats the last item's coefficients and mask; only the first m rows are recorded."""
+        idx = torch.as_tensor(slices, dtype=torch.int64, device=self.y.device)
+        return KSpaceRows(self.y.index_select(0, idx), self.mask.index_select(0, idx), idx[:m])
+
+    def record(self, bound, x, x_new=None):
+        """x [B,1,S,S]: what the sampler returned (in [-1,1], before any map) for the batch that for_rows bound: keeps, per slice, the
+        largest |M_eff * (F(x) - y)| / |y| seen over its real rows (an ensemble records every sample)."""
         from . import ops
+        idx = bound.idx
+        x = x[:idx.shape[0]]
         F = ops.fft2(x[:, 0].contiguous())
         d = torch.where(self.mask.index_select(0, idx) != 0, F - self.y.index_select(0, idx), torch.zeros((), device=F.device, dtype=F.dtype))
         den = self.y_norm.index_select(0, idx)
@@ -219,9 +231,3 @@ def suffix(measurement):
     r = measurement.report
     return f" | kspace={r['pattern']} x{r['accel']} ({r['effective_fraction']:.3f})"
 
-
-def write_json(measurement, output_dir, target):
-    path = os.path.join(output_dir, f'kspace_{target.lower()}.json')
-    with open(path, 'w') as f:
-        json.dump(measurement.finish(), f, indent=1)
-    return path

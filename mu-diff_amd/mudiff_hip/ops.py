@@ -1004,6 +1004,24 @@ def randn_keyed_coupled(rows_keys, row_len, seed, step, kind, half_taps, radius,
 KIND_KNOWN, KIND_RENOISE = 3, 4      # the draws of mud_known_constrain: the known region's forward noise, RePaint's one-level re-noising
 
 
+def _level_and_keys(name, clean, t, a_tab, s_tab, noise, keys, rows, device):
+    """What the checked wrappers of the three constraints share -> (t, a_tab, s_tab, the keys on `device` or None): without `clean`, t
+    (int64 [rows]) and two fp32 tables of one length, contiguous, and then either `noise` or keys for every row (check_keys)."""
+    if clean:
+        return t, a_tab, s_tab, None
+    if t is None or a_tab is None or s_tab is None or t.dtype != torch.int64 or t.numel() != rows or a_tab.numel() != s_tab.numel():
+        raise MudiffHipError(f'{name}: need t (int64 [rows]) and two tables of one length')
+    kd = None
+    if noise is None:
+        if keys is None:
+            raise MudiffHipError(f'{name}: pass noise or keys')
+        k = check_keys(keys)
+        if k.shape[0] != rows:
+            raise MudiffHipError(f'{name}: {k.shape[0]} keys for {rows} rows')
+        kd = k.to(device)
+    return t.contiguous(), _f32(a_tab.contiguous()), _f32(s_tab.contiguous()), kd
+
+
 def known_constrain_into(out, x_new, known, mask, keys_dev, seed, step, kind, t, toff, a_tab, s_tab, clean=False, noise=None):
     """Unchecked launch of mud_known_constrain into `out` (fp32, contiguous, [rows, ...]; may be x_new or known): GraphSampler.sample_keyed
     checks its operands once per batch, not once per step.  keys_dev: through check_keys and on out's device (None with `noise`)."""
@@ -1035,18 +1053,7 @@ def known_constrain(x_new, known, mask, t, toff, a_tab, s_tab, *, noise=None, ke
     known = known if known.is_contiguous() or out is known else known.contiguous()
     x_new = x_new if x_new is None or x_new.is_contiguous() or out is x_new else x_new.contiguous()
     mask, noise = (None if v is None else v.contiguous() for v in (mask, noise))
-    kd = None
-    if not clean:
-        if t is None or a_tab is None or s_tab is None or t.dtype != torch.int64 or t.numel() != rows or a_tab.numel() != s_tab.numel():
-            raise MudiffHipError('known_constrain: need t (int64 [rows]) and two tables of one length')
-        t, a_tab, s_tab = t.contiguous(), _f32(a_tab.contiguous()), _f32(s_tab.contiguous())
-        if noise is None:
-            if keys is None:
-                raise MudiffHipError('known_constrain: pass noise or keys')
-            k = check_keys(keys)
-            if k.shape[0] != rows:
-                raise MudiffHipError(f'known_constrain: {k.shape[0]} keys for {rows} rows')
-            kd = k.to(known.device)
+    t, a_tab, s_tab, kd = _level_and_keys('known_constrain', clean, t, a_tab, s_tab, noise, keys, rows, known.device)
     out = torch.empty(known.shape, device=known.device, dtype=torch.float32) if out is None else out
     return known_constrain_into(out, x_new, known, mask, kd, _seed64(seed), step, kind, t, toff, a_tab, s_tab, clean, noise)
 
@@ -1141,18 +1148,7 @@ def kspace_constrain(x_new, y, mask, t, toff, a_tab, s_tab, *, noise=None, keys=
     x_new = x_new if x_new.is_contiguous() else x_new.contiguous()
     y, mask = y.contiguous(), mask.contiguous()
     noise = None if noise is None else noise.contiguous()
-    kd = None
-    if not clean:
-        if t is None or a_tab is None or s_tab is None or t.dtype != torch.int64 or t.numel() != rows or a_tab.numel() != s_tab.numel():
-            raise MudiffHipError('kspace_constrain: need t (int64 [rows]) and two tables of one length')
-        t, a_tab, s_tab = t.contiguous(), _f32(a_tab.contiguous()), _f32(s_tab.contiguous())
-        if noise is None:
-            if keys is None:
-                raise MudiffHipError('kspace_constrain: pass noise or keys')
-            k = check_keys(keys)
-            if k.shape[0] != rows:
-                raise MudiffHipError(f'kspace_constrain: {k.shape[0]} keys for {rows} rows')
-            kd = k.to(x_new.device)
+    t, a_tab, s_tab, kd = _level_and_keys('kspace_constrain', clean, t, a_tab, s_tab, noise, keys, rows, x_new.device)
     out = torch.empty(x_new.shape, device=x_new.device, dtype=torch.float32) if out is None else out
     work = torch.empty(rows, S, S, device=x_new.device, dtype=torch.complex64) if work is None else work
     return kspace_constrain_into(out, x_new, y, mask, work, kd, _seed64(seed), step, kind, t, toff, a_tab, s_tab, clean, noise)
@@ -1237,18 +1233,7 @@ def slab_constrain(x_new, y, members, weights, t, toff, a_tab, s_tab, *, gains=N
     x_new = x_new if x_new.is_contiguous() or out is x_new else x_new.contiguous()
     y = y.contiguous()
     noise = None if noise is None else noise.contiguous()
-    kd = None
-    if not clean:
-        if t is None or a_tab is None or s_tab is None or t.dtype != torch.int64 or t.numel() != rows or a_tab.numel() != s_tab.numel():
-            raise MudiffHipError('slab_constrain: need t (int64 [rows]) and two tables of one length')
-        t, a_tab, s_tab = t.contiguous(), _f32(a_tab.contiguous()), _f32(s_tab.contiguous())
-        if noise is None:
-            if keys is None:
-                raise MudiffHipError('slab_constrain: pass noise or keys')
-            k = check_keys(keys)
-            if k.shape[0] != rows:
-                raise MudiffHipError(f'slab_constrain: {k.shape[0]} keys for {rows} rows')
-            kd = k.to(x_new.device)
+    t, a_tab, s_tab, kd = _level_and_keys('slab_constrain', clean, t, a_tab, s_tab, noise, keys, rows, x_new.device)
     out = torch.empty(x_new.shape, device=x_new.device, dtype=torch.float32) if out is None else out
     return slab_constrain_into(out, x_new, y, tables, kd, _seed64(seed), step, kind, t, toff, a_tab, s_tab, clean, noise)
 

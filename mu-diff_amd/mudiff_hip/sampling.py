@@ -246,40 +246,33 @@ class GraphSampler:
         out = self.x.clone()
         return (out, steps) if return_steps else out
 
+    thick_x_new = None      # after sample_keyed with `thick`: the last step's result as the constraint received it (the graph's own buffer)
+
     def sample_keyed(self, cond1, cond2, cond3, keys, seed, n_time, coupling=None, known=None, known_mask=None, resample=1, kspace=None,
-                     thick=None):
+                     thick=None, constraint=None):
         """sample() with keyed draws (DESIGN.md section 5.7): row r of the batch is sample keys[r] = (slice, sample) of an ensemble;
         x_init (kind 0, step 0) and every executed step k's z (kind 1) and posterior noise (kind 2) are drawn with ops.randn_keyed
         on this device's current stream, so each row's result depends on (seed, its key) alone.  keys: int64 [B, 2] (host or device).
         `coupling` (mudiff_hip.slice_coupling): None; 'shared' = every row draws with slice key 0, so rows of one
         sample index get identical draws; (half_taps, R) = every draw is ops.randn_keyed_coupled's, the white noise of the slices
         slice-R..slice+R under those weights.
-        `known`, `known_mask`: the target where it was acquired, [B,1,H,W] in [-1,1], and uint8 [B,1,H,W], non-zero =
-        known.  After the step executed with t = i the result is at the level of q_sample(., t=i), so the known voxels are replaced by
-        a_s_cum[i] * known + sigmas_cum[i] * eta (ops.known_constrain, kind KIND_KNOWN) for i > 0 and by `known` itself for i = 0, where the
-        posterior adds no noise: the known voxels of the result are the known values bit for bit, and the free region was sampled
-        conditioned on them.  The captured graphs are the same; the constraint runs between replays, in place of the copy into x.
-        `resample` = R > 1 (RePaint's resampling with jump length 1): every step is executed R times; after each of the first R - 1 the
-        constrained x is taken back one level, x <- a_s[i+1] * x + sigmas[i+1] * eta' (kind KIND_RENOISE), and the step runs again with fresh
-        z and posterior noise.  The step word of every draw is the running count of executed steps, so no two draws share a key.  The
-        KIND_KNOWN and KIND_RENOISE draws always use the row's true (slice, sample) key and are never slice-coupled: `coupling` acts on
-        kinds 0..2 only.  Without `known` the result is what it was before these arguments existed.
-        `kspace` (mudiff_hip.kspace): None, or (y complex64 [B,S,S], mask uint8 [1 or B,S,S]): the target was measured
-        in k-space, y = mask * F(k) with F = ops.fft2.  After the step executed with t = i the measured coefficients of the result are
-        replaced by those of q_sample(k, i): x <- x_new - Re F^H[mask * (F(x_new - sigmas_cum[i] * eta) - a_s_cum[i] * y)] with eta of kind
-        KIND_KSPACE (the row's true key, never slice-coupled), and for i = 0 by y itself (ops.kspace_constrain).  Exclusive with `known`;
-        `resample` and `coupling` act as they do with `known`.  ValueError unless H == W is a size ops.fft2 takes.  The complex workspace
-        is allocated once per sampler.
-        `thick` (mudiff_hip.thick): None, or (y fp32 [groups,H,W], members, weights, gains) - a tuple, or an object
-        with those attributes - for this batch: the target was acquired with thick slices, group j being the rows members[j] of the
-        batch (its thin slices, -1 = unused) and y[j] = sum_l w_l k_l their measured average (ops.slab_tables has the tables' form;
-        gains None = w_l / sum w^2).  After the step executed with t = i the slab average of the result is replaced by that of
-        q_sample(k, i): r = sum_l w_l (x_new_l - sigmas_cum[i] * eta_l) - a_s_cum[i] * y, x_l <- x_new_l - g_l r with eta of kind KIND_THICK
-        (the row's true key, never slice-coupled), and for i = 0 by y itself (ops.slab_constrain).  This couples the rows of a group: the
-        caller keeps a group inside one batch.  A row of no group is sampled freely.  Exclusive with `known` and `kspace`; `resample` and
-        `coupling` act as they do with `known`.  `thick_x_new` is then the last step's result as the constraint received it (the graph's
-        own buffer, valid until the next replay: the scale of the residual's rounding).  Without `thick` the result is what it was before
-        the argument existed."""
+
+        At most one of `known`, `kspace`, `thick` (or `constraint`, a batch-level object of mudiff_hip.constraints) says what of the
+        target was acquired.  After the step executed with t = i the result is at the level of q_sample(., t=i),
+        so what was measured of it is replaced by that of q_sample(k, i), with a draw eta of the mode's own kind, and for i = 0, where the
+        posterior adds no noise, by the measurement itself (`clean`).  The captured graphs are the same; the constraint runs between
+        replays, in place of the copy into x.  `resample` = R > 1 (RePaint's resampling with jump length 1) needs one of them: every step
+        is executed R times; after each of the first R - 1 the constrained x is taken back one level, x <- a_s[i+1] * x + sigmas[i+1] *
+        eta' (kind KIND_RENOISE), and the step runs again with fresh z and posterior noise.  The step word of every draw is the running
+        count of executed steps.  These draws use the row's true (slice, sample) key: `coupling` acts on kinds 0..2 only.
+        `known`, `known_mask` (section 5.25): the target where it was acquired, [B,1,H,W] in [-1,1], and uint8 [B,1,H,W], non-zero = known:
+        those voxels of the result are the known values bit for bit (ops.known_constrain, kind KIND_KNOWN).
+        `kspace` (section 5.26): (y complex64 [B,S,S], mask uint8 [1 or B,S,S]), y = mask * F(k) with F = ops.fft2: the measured coefficients
+        are kept (ops.kspace_constrain, kind KIND_KSPACE).  ValueError unless H == W is a size ops.fft2 takes.
+        `thick` (section 5.27): (y fp32 [groups,H,W], members, weights, gains) - a tuple, or an object with those attributes - in
+        ops.slab_tables' form: group j is the rows members[j] of the batch, whose weighted average y[j] is kept (ops.slab_constrain, kind
+        KIND_THICK); the caller keeps a group inside one batch, and a row of no group is sampled freely (`thick_x_new`: see above)."""
+        from .constraints import of_batch
         from .slice_coupling import SHARED, check_coupling
         coupling = check_coupling(coupling)
         k = ops.check_keys(keys)
@@ -289,47 +282,9 @@ class GraphSampler:
         resample = int(resample)
         if resample < 1:
             raise ValueError(f'GraphSampler.sample_keyed: resample must be >= 1, got {resample}')
-        if known is not None and kspace is not None:
-            raise ValueError('GraphSampler.sample_keyed: known and kspace are mutually exclusive')
-        if thick is not None and (known is not None or kspace is not None):
-            raise ValueError('GraphSampler.sample_keyed: thick is exclusive with known and kspace')
-        if known is None and (known_mask is not None or (resample != 1 and kspace is None and thick is None)):
-            raise ValueError('GraphSampler.sample_keyed: known_mask and resample need known (resample: or kspace, or thick)')
-        if thick is not None:
-            th_y, th_m, th_w, th_g = thick if isinstance(thick, (tuple, list)) else (thick.y, thick.members, thick.weights, thick.gains)
-            th_tab = ops.slab_tables(th_m, th_w, th_g)
-            want = (th_tab[0].shape[0], self.H, self.W)
-            if th_y.dtype != torch.float32 or tuple(th_y.shape) != want:
-                raise ValueError(f'GraphSampler.sample_keyed: thick y must be fp32 {want}, got {th_y.dtype} {tuple(th_y.shape)}')
-            if want[0] > self.B or th_tab[0].shape[1] > ops.SLAB_MAX_MEMBERS or int(th_tab[0].max(initial=-1)) >= self.B:
-                raise ValueError(f'GraphSampler.sample_keyed: thick names {want[0]} groups of {th_tab[0].shape[1]} rows up to row '
-                                 f'{int(th_tab[0].max(initial=-1))} for a batch of {self.B} (at most {ops.SLAB_MAX_MEMBERS} rows a group)')
-            th_y = th_y.to(self.x.device).contiguous()
-            dc = self._diffusion_tables()
-            k_true = k.to(self.x.device)
-        if kspace is not None:
-            if self.H != self.W or not ops.kspace_size_ok(self.H):
-                raise ValueError(f'GraphSampler.sample_keyed: kspace needs a square grid whose size is a power of two in [16, 512], got '
-                                 f'{self.H} x {self.W}')
-            ks_y, ks_mask = kspace
-            want = (self.B, self.H, self.W)
-            if ks_y.dtype != torch.complex64 or tuple(ks_y.shape) != want or ks_mask.dtype != torch.uint8 or \
-                    tuple(ks_mask.shape) not in (want, (1,) + want[1:]):
-                raise ValueError(f'GraphSampler.sample_keyed: kspace = (y complex64 {want}, mask uint8 [1 or {self.B}, {self.H}, {self.W}]), got '
-                                 f'{ks_y.dtype} {tuple(ks_y.shape)} and {ks_mask.dtype} {tuple(ks_mask.shape)}')
-            ks_y, ks_mask = ks_y.to(self.x.device).contiguous(), ks_mask.to(self.x.device).contiguous()
-            if getattr(self, '_ks_work', None) is None:
-                self._ks_work = torch.empty(want, device=self.x.device, dtype=torch.complex64)
-            dc = self._diffusion_tables()
-            k_true = k.to(self.x.device)
-        if known is not None:
-            if known_mask is None:
-                raise ValueError('GraphSampler.sample_keyed: known needs known_mask')
-            if tuple(known.shape) != tuple(self.x.shape) or tuple(known_mask.shape) != tuple(self.x.shape) or known_mask.dtype != torch.uint8:
-                raise ValueError(f'GraphSampler.sample_keyed: known (fp32) and known_mask (uint8) must be {tuple(self.x.shape)}, got '
-                                 f'{tuple(known.shape)} and {known_mask.dtype} {tuple(known_mask.shape)}')
-            known = known.to(self.x.device, torch.float32).contiguous()
-            known_mask = known_mask.to(self.x.device).contiguous()
+        constraint = of_batch(constraint, known, known_mask, kspace, thick, resample)
+        if constraint is not None:
+            constraint.check(self)
             dc = self._diffusion_tables()
             k_true = k.to(self.x.device)
         if coupling == SHARED:
@@ -355,23 +310,12 @@ class GraphSampler:
                 else:
                     self.graph_rest.replay()
                     x_new = self._rest_out[2]
-                if kspace is not None:
-                    ops.kspace_constrain_into(self.x, x_new, ks_y, ks_mask, self._ks_work, k_true, seed, step, ops.KIND_KSPACE, self.t, 0, dc[0],
-                                              dc[1], clean=i == 0)
-                    if j < resample - 1:
-                        ops.known_constrain_into(self.x, None, self.x, None, k_true, seed, step, ops.KIND_RENOISE, self.t, 1, dc[2], dc[3])
-                elif thick is not None:
-                    ops.slab_constrain_into(self.x, x_new, th_y, th_tab, k_true, seed, step, ops.KIND_THICK, self.t, 0, dc[0], dc[1], clean=i == 0)
-                    if j < resample - 1:
-                        ops.known_constrain_into(self.x, None, self.x, None, k_true, seed, step, ops.KIND_RENOISE, self.t, 1, dc[2], dc[3])
-                    self.thick_x_new = x_new          # what the last constraint was given (the graph's own buffer, until the next replay)
-                elif known is None:
+                if constraint is None:
                     self.x.copy_(x_new)
                 else:
-                    ops.known_constrain_into(self.x, x_new, known, known_mask, k_true, seed, step, ops.KIND_KNOWN, self.t, 0, dc[0], dc[1],
-                                             clean=i == 0)
-                    if j < resample - 1:              # back one level, everywhere (mask None), then the same step again
-                        ops.known_constrain_into(self.x, None, self.x, None, k_true, seed, step, ops.KIND_RENOISE, self.t, 1, dc[2], dc[3])
+                    constraint.apply(self, x_new, k_true, seed, step, i == 0)
+                if j < resample - 1:                  # back one level, everywhere (mask None), then the same step again
+                    ops.known_constrain_into(self.x, None, self.x, None, k_true, seed, step, ops.KIND_RENOISE, self.t, 1, dc[2], dc[3])
                 step += 1
         return self.x.clone()
 

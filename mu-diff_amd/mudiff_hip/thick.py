@@ -13,8 +13,8 @@ A slab j is L consecutive thin slices from z_j = O + j (L + G) of the *volume* (
 between slabs), so --slice_half_range, shards and chunks do not move the slabs.  The weights w_l > 0 sum to 1 (--thick_profile: box, or
 gauss with FWHM = L slices).  Slabs do not overlap, so A A^T is diagonal and the constraint is an exact orthogonal projection: after the
 reverse step executed with t = i the slab average of x is replaced by that of q_sample(k, i), after the last by y itself, and everything
-orthogonal to the profile is left as the model made it (GraphSampler.sample_keyed's `thick`; the draw is kind ops.KIND_THICK, keyed by
-the true (slice, sample), never slice-coupled).  --known_resample R works as it does with --known_volume.
+orthogonal to the profile is left as the model made it (GraphSampler.sample_keyed's `thick`, kind ops.KIND_THICK; the draw and
+--known_resample: mudiff_hip.constraints, section 5.24a).
 
 A slab is measured when every one of its slices lies in the sampled range, K is known on every pixel of every one of them (finite and
 fully covered after resampling: known_region's sense) and --known_drop_slices names none of them: the flag then means `this thick slice
@@ -37,12 +37,12 @@ only has to fill the same ThickMeasurement.
 """
 from __future__ import annotations
 
-import json
 import math
-import os
 
 import numpy as np
 import torch
+
+from .constraints import Constraint, SlabRows, batches      # noqa: F401  (batches: the batching that keeps a slab whole)
 
 PROFILES = ('box', 'gauss')
 MAX_L = 16                           # ops.SLAB_MAX_MEMBERS
@@ -129,27 +129,10 @@ def layout(Z, L, gap=0, offset=0):
     return [(z, min(z + L, Z) - 1, z + L <= Z) for z in range(offset, Z, L + gap)]
 
 
-def batches(units, B, flag='--batch_size'):
-    """units: the run's items in order, grouped: a list of lists, each inner list the items that must share a batch (a measured slab's
-    thin slices; one item for a free slice).  -> [(items of the batch, in order)] of at most B items each: a batch is closed early before
-    a unit that would not fit.  ValueError naming `flag` for a unit longer than B."""
-    out, cur = [], []
-    for u in units:
-        if len(u) > B:
-            raise ValueError(f'{flag} {B} is smaller than a slab of {len(u)} thin slices: a measured slab must travel in one batch')
-        if len(cur) + len(u) > B:
-            out.append(cur)
-            cur = []
-        cur = cur + list(u)
-    if cur:
-        out.append(cur)
-    return out
-
-
 # ---------------------------------------------------------------------------------------------------
 # the measurement of one prediction
 # ---------------------------------------------------------------------------------------------------
-class ThickMeasurement:
+class ThickMeasurement(Constraint):
     """What the samplers take for one prediction of n thin slices (the sampled range s0..s1; local index i = slice s0 + i): `y` fp32
     [G,S,S] on the device, the measured slabs' averages; `starts` [G], each measured slab's first local index; `group_of` int [n], the
     measured slab of a slice or -1; `weights`, `gains` fp32 [L] (numpy: the host tables of ops.slab_constrain); `report`: thick_<t>.json;
@@ -167,6 +150,10 @@ class ThickMeasurement:
         self.y_norm = torch.linalg.vector_norm(y.flatten(1), dim=1) if y.shape[0] else torch.zeros(0, device=y.device)
         self.residual = torch.zeros(y.shape[0], device=y.device, dtype=torch.float32)
         self.x_norm = torch.zeros_like(self.residual)
+
+    tag, baseline_through_plane = 'thick', True
+    done_suffix = lambda self: suffix(self)      # noqa: E731
+    baseline = lambda self: ('thick_interp', self.interpolated()) if self.options['interp'] else None      # noqa: E731
 
     def units(self, lo=0, hi=None):
         """The local slices lo..hi-1 in order as batches() takes them: a measured slab's L slices together, every other slice alone.
@@ -186,13 +173,22 @@ class ThickMeasurement:
             i = s + self.L
         return out
 
-    def for_rows(self, slices, samples=None):
-        """The batch whose row r holds local slice slices[r] (-1: a padded row, in no group) of sample samples[r] (None: all 0) ->
-        (GraphSampler.sample_keyed's `thick` tuple (y, members, weights, gains), the measured slab of each group).  Every measured slab
-        that a row touches must be in the batch whole, per sample; its rows enter the table in slice order."""
+    def chunk_end(self, s0, s1):
+        """An ensemble's chunk ends before a measured slab that it would cut."""
+        chunk = s1 - s0
+        if s1 < self.n and self.group_of[s1] >= 0 and self.group_of[s1] == self.group_of[s1 - 1]:
+            s1 = self.starts[int(self.group_of[s1])]
+        if s1 <= s0:
+            raise ValueError(f'sample_ensemble: a chunk of {chunk} slices is smaller than a slab of {self.L} thin slices')
+        return s1
+
+    def for_rows(self, slices, samples=None, m=None):
+        """The batch whose row r holds local slice slices[r] of sample samples[r] (None: all 0); a row from m on, or with slice -1, is
+        padding, in no group -> constraints.SlabRows = (GraphSampler.sample_keyed's `thick` tuple, the measured slab of each group).
+        Every measured slab that a row touches must be in the batch whole, per sample; its rows enter the table in slice order."""
         samples = [0] * len(slices) if samples is None else [int(s) for s in samples]
         found = {}
-        for r, (i, j) in enumerate(zip(slices, samples)):
+        for r, (i, j) in enumerate(zip(slices[:m], samples)):
             g = int(self.group_of[i]) if i >= 0 else -1
             if g >= 0:
                 found.setdefault((g, j), {})[int(i) - self.starts[g]] = r
@@ -202,15 +198,16 @@ class ThickMeasurement:
                 raise ValueError(f'thick slices: the batch holds {len(rows)} of the {self.L} thin slices of a measured slab (sample {j})')
             members.append([rows[l] for l in range(self.L)])
             gids.append(g)
-        m = np.asarray(members, np.int32).reshape(len(members), self.L)
+        members = np.asarray(members, np.int32).reshape(len(members), self.L)
         idx = torch.as_tensor(gids, dtype=torch.int64, device=self.y.device)
-        return (self.y.index_select(0, idx), m, self.weights, self.gains), idx
+        return SlabRows((self.y.index_select(0, idx), members, self.weights, self.gains), idx)
 
-    def record(self, thick, gids, x, x_new=None):
-        """x [B,1,S,S]: what the sampler returned (in [-1,1], before any map) for the batch that for_rows described: keeps, per slab,
+    def record(self, bound, x, x_new=None):
+        """x [B,1,S,S]: what the sampler returned (in [-1,1], before any map) for the batch that for_rows bound: keeps, per slab,
         the largest |A x - y| / |y| seen (an ensemble records every sample), and the largest |A |x_new|| of what the last constraint was
         given (GraphSampler.thick_x_new; x itself without it): with |y|, what the residual's rounding scales with."""
         from . import ops
+        thick, gids = bound
         if gids.numel() == 0:
             return
         x_new = x if x_new is None else x_new
@@ -286,9 +283,3 @@ def suffix(measurement):
     r = measurement.report
     return f" | thick={r['L']}+{r['gap']} {r['profile']} ({r['measured_slabs']}/{len(r['slabs'])} slabs)"
 
-
-def write_json(measurement, output_dir, target):
-    path = os.path.join(output_dir, f'thick_{target.lower()}.json')
-    with open(path, 'w') as f:
-        json.dump(measurement.finish(), f, indent=1)
-    return path

@@ -292,7 +292,7 @@ def calibrate_volume(args, gen1, gen2, cond_stacks, device, batch_size=32):
 
 def predict_slices(args, gen1, gen2, cond_stacks, device, batch_size=32, x_inits=None, zs=None, noises=None, seed=None,
                    use_graph=True, progress=None, sampler=None, return_device=False, coupling=None, known=None, resample=1, kspace=None,
-                   thick=None):
+                   thick=None, constraint=None):
     """cond_stacks: three float arrays [n,X,Y] in [-1,1] (the condition contrasts, already normalised and sliced), or three device
     tensors [n,1,S,S] (volume_intake.condition_from_raw).  -> [n,S,S] float32 numpy in [0,1], S = args.image_size; with `return_device`
     the device tensor instead (no copy to the host).
@@ -307,45 +307,25 @@ def predict_slices(args, gen1, gen2, cond_stacks, device, batch_size=32, x_inits
     draws no longer come from the torch generator: every batch is sampled through GraphSampler.sample_keyed with the keys (global slice,
     sample 0) and `seed` (required, in [0, 2^64)), so neighbouring slices share part of their noise and the result still does not depend
     on the batch size.  Injected draws together with a coupling raise ValueError.
-    `known` (--known_volume; mudiff_hip.known_region): None, or (known [n,1,S,S] in [-1,1], mask uint8 [n,1,S,S])
-    on the device, with `resample` what GraphSampler.sample_keyed takes: the same keyed road, a padded row repeating the last slice's
-    known stack and mask; it needs a seed and the captured sampler as a coupling does (ValueError otherwise).
-    `kspace` (--known_kspace; mudiff_hip.kspace): None, or a kspace.KSpaceMeasurement for these n slices: the same
-    keyed road with GraphSampler.sample_keyed's `kspace`; what the sampler returns is handed to its `record` before the [0,1] map.
-    Exclusive with `known`; `resample` serves either.
-    `thick` (--known_thick; mudiff_hip.thick): None, or a thick.ThickMeasurement for these n slices: the same keyed
-    road with GraphSampler.sample_keyed's `thick`.  The constraint couples the thin slices of a measured slab, so the batches are formed
-    by thick.batches: a batch is closed early before a slab that would not fit and padded like the last one (a padded row is in no
-    group); a slab longer than the captured batch is a ValueError naming --batch_size.  Exclusive with `known` and `kspace`."""
+    `known`, `kspace`, `thick` (at most one): what of the target was acquired - (known [n,1,S,S] in [-1,1], mask
+    uint8 [n,1,S,S]) on the device (--known_volume), a kspace.KSpaceMeasurement (--known_kspace) or a thick.ThickMeasurement
+    (--known_thick) for these n slices, with `resample` what GraphSampler.sample_keyed takes; or `constraint`, any of them as one object
+    of mudiff_hip.constraints (its own `resample` counts).  The same keyed road, with the same two refusals; the batches are
+    constraints.batches of the constraint's units (a slab longer than the captured batch is a ValueError naming --batch_size), and what
+    the sampler returns is handed to the constraint's `record` before the [0,1] map."""
     from . import ops
     from . import sampling as S
+    from .constraints import FREE, batches, of_prediction
     from .slice_coupling import check_coupling
     coupling = check_coupling(coupling)
-    if kspace is not None:
-        if known is not None:
-            raise ValueError('predict_slices: known and kspace are mutually exclusive')
+    constraint, resample = of_prediction('predict_slices', constraint, known, kspace, thick, resample)
+    keyed = coupling is not None or constraint is not FREE
+    if keyed:
+        what = 'a coupling' if constraint is FREE else 'a constraint (known region, k-space or thick-slice measurements)'
         if x_inits is not None or zs is not None or noises is not None:
-            raise ValueError('predict_slices: injected x_inits / zs / noises cannot be combined with k-space measurements (their draws are keyed)')
+            raise ValueError(f'predict_slices: injected x_inits / zs / noises cannot be combined with {what} (its draws are keyed)')
         if seed is None or not use_graph:
-            raise ValueError('predict_slices: k-space measurements need a seed and the captured sampler (use_graph=True)')
-    if thick is not None:
-        if known is not None or kspace is not None:
-            raise ValueError('predict_slices: thick is exclusive with known and kspace')
-        if x_inits is not None or zs is not None or noises is not None:
-            raise ValueError('predict_slices: injected x_inits / zs / noises cannot be combined with thick-slice measurements (their draws are keyed)')
-        if seed is None or not use_graph:
-            raise ValueError('predict_slices: thick-slice measurements need a seed and the captured sampler (use_graph=True)')
-    if coupling is not None:
-        if x_inits is not None or zs is not None or noises is not None:
-            raise ValueError('predict_slices: injected x_inits / zs / noises cannot be combined with a coupling (its draws are keyed)')
-        if seed is None or not use_graph:
-            raise ValueError('predict_slices: a coupling needs a seed and the captured sampler (use_graph=True)')
-    if known is not None:
-        if x_inits is not None or zs is not None or noises is not None:
-            raise ValueError('predict_slices: injected x_inits / zs / noises cannot be combined with a known region (its draws are keyed)')
-        if seed is None or not use_graph:
-            raise ValueError('predict_slices: a known region needs a seed and the captured sampler (use_graph=True)')
-    keyed = coupling is not None or known is not None or kspace is not None or thick is not None
+            raise ValueError(f'predict_slices: {what} needs a seed and the captured sampler (use_graph=True)')
     n = int(cond_stacks[0].shape[0])
     size = int(args.image_size)
     if n == 0:
@@ -379,38 +359,27 @@ def predict_slices(args, gen1, gen2, cond_stacks, device, batch_size=32, x_inits
             x_inits = torch.randn(n, 1, size, size, device=device, generator=gen)
         zs = [torch.randn(n, args.nz, device=device, generator=gen) for _ in range(T)]
         noises = [torch.randn(n, 1, size, size, device=device, generator=gen) for _ in range(T)]
-    if thick is not None:                    # batches that keep a measured slab whole; row r of a batch is slice items[r], padded by the last
-        from .thick import batches
-        if thick.n != n:
-            raise ValueError(f'predict_slices: the thick-slice measurement is of {thick.n} slices, the conditions of {n}')
+    if keyed:                                # row r of a batch is slice items[r]; a short batch is padded by its last slice
+        constraint.over(n, 'predict_slices')
         done = 0
-        for items in batches(thick.units(), bs):
-            idx = torch.as_tensor(items + [items[-1]] * (bs - len(items)), dtype=torch.int64)
+        for items in batches(constraint.units(0, n), bs):
+            m = len(items)
+            rows = items + [items[-1]] * (bs - m)
+            idx = torch.as_tensor(rows, dtype=torch.int64)
             keys = torch.stack([idx, torch.zeros(bs, dtype=torch.int64)], 1)
-            th, gids = thick.for_rows(items + [-1] * (bs - len(items)))
+            bound = constraint.for_rows(rows, None, m)
             idx = idx.to(device)
-            fake = sampler.sample_keyed(*(c.index_select(0, idx) for c in conds), keys, seed, T, coupling=coupling, thick=th, resample=resample)
-            thick.record(th, gids, fake, sampler.thick_x_new)
-            out[idx[:len(items)]] = ops.to_range_0_1(fake)[:len(items), 0]
-            done += len(items)
+            fake = sampler.sample_keyed(*(c.index_select(0, idx) for c in conds), keys, seed, T, coupling=coupling, constraint=bound,
+                                        resample=resample)
+            constraint.record(bound, fake, sampler.thick_x_new)
+            out[items[0]:items[0] + m] = ops.to_range_0_1(fake)[:m, 0]
+            done += m
             if progress:
                 progress(done, n)
         return out if return_device else out.cpu().numpy()
     for lo in range(0, n, bs):
         hi = min(lo + bs, n)
         c1, c2, c3 = (padded(c, lo, hi) for c in conds)
-        if keyed:
-            keys = torch.stack([torch.arange(lo, lo + bs).clamp_(max=hi - 1), torch.zeros(bs, dtype=torch.int64)], 1)
-            more = {} if known is None else dict(known=padded(known[0], lo, hi), known_mask=padded(known[1], lo, hi), resample=resample)
-            if kspace is not None:
-                more = dict(kspace=(padded(kspace.y, lo, hi), padded(kspace.mask, lo, hi)), resample=resample)
-            fake = sampler.sample_keyed(c1, c2, c3, keys, seed, T, coupling=coupling, **more)
-            if kspace is not None:
-                kspace.record(torch.arange(lo, hi, device=device), fake[:hi - lo])
-            out[lo:hi] = ops.to_range_0_1(fake)[:hi - lo, 0]
-            if progress:
-                progress(hi, n)
-            continue
         x0 = padded(x_inits, lo, hi) if x_inits is not None else torch.randn(bs, 1, size, size, device=device)
         kw = {}
         if zs is not None:
@@ -440,11 +409,9 @@ def predict_volume(args):
     counts how often the ground truth lies between two of the maps (mudiff_hip.ensemble, mudiff_hip.volume_coverage).  --known_volume keeps
     the acquired part of the target: it conditions the sampling and is pasted into every written map, known_<target>.json goes next to the
     prediction and the scores gain the regions known / synthesised (mudiff_hip.known_region).  With --known_kspace
-    that volume was acquired undersampled in k-space instead: its measured Fourier coefficients condition the sampling, nothing is pasted,
-    and kspace_<target>.json (under --kspace_zero_filled also zero_filled_<target>.nii.gz) goes next to the prediction (mudiff_hip.kspace,
-    DESIGN.md section 5.26).  With --known_thick it was acquired with thick slices: the slab averages condition the sampling, nothing is
-    pasted, and thick_<target>.json (under --thick_interp also thick_interp_<target>.nii.gz) goes next to the prediction (mudiff_hip.thick,
-    DESIGN.md section 5.27)."""
+    (mudiff_hip.kspace, section 5.26) or --known_thick (mudiff_hip.thick, section 5.27) that volume's measured Fourier coefficients or slab
+    averages condition the sampling instead, nothing is pasted, and kspace_<target>.json or thick_<target>.json (and under
+    --kspace_zero_filled / --thick_interp the baseline volume) goes next to the prediction."""
     evaluation, resampled, found = _load_eval_inputs(args)
     args = copy.copy(args)                               # the run's own copy: it carries the record of what the intake did
     args.evaluation_record = (resampled, found)          # (for _predict_volume's report: IntakeReport.add_evaluation)
@@ -579,12 +546,11 @@ def _done_tail(args, plan):
     quantiles, each only when it is not the default."""
     from .ensemble import done_suffix
     from .known_region import suffix as known_suffix
-    from .kspace import suffix as kspace_suffix
     from .slice_coupling import suffix
-    from .thick import suffix as thick_suffix
+    constraint = getattr(args, 'constraint', None)
     return (('' if plan == 'auto' else f' | prec_plan={plan}') + norm_suffix(args.norm) + _intake_report(args).suffix() +
             suffix(getattr(args, 'slice_coupling', None)) + done_suffix(args) + known_suffix(getattr(args, 'known_region', None)) +
-            kspace_suffix(getattr(args, 'kspace', None)) + thick_suffix(getattr(args, 'thick', None)))
+            ('' if constraint is None else constraint.done_suffix()))
 
 
 class _Stages:
@@ -627,14 +593,14 @@ def predict_from_conditions(args, plan, evaluation, gen1, gen2, device, stacks, 
             from .driver import write_calibration
             print(f'[calibrate] {cal.summary()}')
             print(f'[calibrate] wrote {write_calibration(cal, args.output_dir)}')
-    region, known = _known_region(args, ref, device)
+    region, constraint = _known_region(args, ref, device)
     if args.num_samples is not None:
-        return _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref, evaluation, on_device, samplers, write, stages, region, known)
+        return _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref, evaluation, on_device, samplers, write, stages, region, constraint)
     n = int(stacks[0].shape[0])
     sampler = _cached_sampler(args, gen1, gen2, device, samplers, min(int(args.batch_size), n)) if n else None
     pred = stages.run('sample', lambda: predict_slices(args, gen1, gen2, stacks, device, batch_size=args.batch_size, seed=args.seed,
                                                        progress=lambda d, n: print(f'[infer] processed {d}/{n} slices'), sampler=sampler,
-                                                       return_device=on_device, coupling=_coupling(args), **known))
+                                                       return_device=on_device, coupling=_coupling(args), constraint=constraint))
     if on_device:
         def put_together():
             from . import ops
@@ -654,8 +620,7 @@ def predict_from_conditions(args, plan, evaluation, gen1, gen2, device, stacks, 
         vol_pred = stages.run('assemble', lambda: KR.paste(vol_pred, region, device))      # the acquired voxels, exactly, in what is written
         KR.write_json(region, args.output_dir, args.target_modality)
     stages.run('write', lambda: write(out_path, vol_pred, aff, hdr))
-    _kspace_outputs(args, write, lambda p: _assemble_map(p, shp, s0, s1, on_device), aff, hdr, evaluation, device)
-    _thick_outputs(args, write, lambda p: _assemble_map(p, shp, s0, s1, on_device), aff, hdr, evaluation, device)
+    _measurement_outputs(args, write, lambda p: _assemble_map(p, shp, s0, s1, on_device), aff, hdr, evaluation, device)
     _intake_report(args).write(args.output_dir, args.target_modality, aff, hdr)
     print(f'[done] saved: {out_path} | shape={tuple(vol_pred.shape)} | slices={s0}..{s1}' + _done_tail(args, plan))
     if evaluation is not None:
@@ -664,27 +629,25 @@ def predict_from_conditions(args, plan, evaluation, gen1, gen2, device, stacks, 
     return out_path
 
 
+def known_modes():
+    """The modules of the three ways a target can be partly acquired, in the order their flags are checked."""
+    from . import known_region, kspace, thick
+    return known_region, kspace, thick
+
+
 def _known_region(args, ref, device):
-    """--known_volume: (the run's known_region.KnownRegion, also left in args.known_region for the [done] line and the scores; what
-    predict_slices and sample_ensemble take for it) - or (None, {}) without the flag."""
+    """--known_volume: (the run's known_region.KnownRegion, or None when K is measured in k-space or in thick slices instead: nothing
+    is pasted; the one constraint that predict_slices and sample_ensemble take, or None), also left in args.known_region and
+    args.constraint for the [done] line, the scores and the measurement's outputs."""
     inputs = getattr(args, 'known_inputs', None)
-    args.known_region = args.kspace = args.thick = None
+    args.known_region = args.constraint = None
     if inputs is None:
-        return None, {}
+        return None, None
     from . import known_region as KR
-    from . import kspace as KS
-    from . import thick as TK
     region = KR.compose(inputs, ref, args.norm, device)
-    options = TK.options_from(args)
-    if options is not None:       # --known_thick: K is measured in thick slices instead; no known region, no paste (mudiff_hip.thick)
-        args.thick = TK.measure(region, ref[3], ref[4], int(args.image_size), options, device)
-        return None, dict(thick=args.thick, resample=region.resample)
-    options = KS.options_from(args)
-    if options is not None:       # --known_kspace: K is measured in k-space instead; no known region, no paste (mudiff_hip.kspace)
-        args.kspace = KS.measure(region, ref[3], ref[4], int(args.image_size), options, args.seed, device)
-        return None, dict(kspace=args.kspace, resample=region.resample)
-    args.known_region = region
-    return region, dict(known=KR.sampler_inputs(region, ref[3], ref[4], int(args.image_size), device), resample=region.resample)
+    args.constraint = KR.constraint_for(region, ref[3], ref[4], int(args.image_size), args, device)
+    args.known_region = region if args.constraint.tag is None else None      # the known voxels themselves: pasted, and scored as regions
+    return args.known_region, args.constraint
 
 
 def _assemble_map(p, shp, s0, s1, on_device):
@@ -697,60 +660,37 @@ def _assemble_map(p, shp, s0, s1, on_device):
     return reconstruct_volume_from_slices(list(p.cpu().numpy()), shp, s0, s1)
 
 
-def _kspace_outputs(args, write, put_together, aff, hdr, evaluation, device):
-    """--known_kspace: kspace_<t>.json next to the prediction, and under --kspace_zero_filled zero_filled_<t>.nii.gz = Re F^H y mapped to
-    [0,1], through the prediction's own road (`put_together`: a device [n,S,S] map -> the host volume as written) and, with an
-    evaluation, scored into metrics_zero_filled_<t>.json.  Nothing without the flag."""
-    meas = getattr(args, 'kspace', None)
-    if meas is None:
+def _measurement_outputs(args, write, put_together, aff, hdr, evaluation, device):
+    """--known_kspace / --known_thick: the measurement's report (kspace_<t>.json, thick_<t>.json) next to the prediction, and under its
+    flag its baseline (zero_filled_<t>.nii.gz, thick_interp_<t>.nii.gz), mapped to [0,1], through the prediction's own road
+    (`put_together`: a device [n,S,S] map -> the host volume as written); with an evaluation it is scored into metrics_<name>_<t>.json,
+    and where the measurement says so --through_plane measures it into through_plane_<name>_<t>.json.  Nothing without the flags."""
+    meas = getattr(args, 'constraint', None)
+    if meas is None or meas.tag is None:
         return
-    from . import kspace as KS
     from . import ops
     target = args.target_modality.lower()
-    print(f'[kspace] wrote {KS.write_json(meas, args.output_dir, args.target_modality)}')
-    if not meas.options['zero_filled']:
+    print(f'[{meas.tag}] wrote {meas.write_json(args.output_dir, args.target_modality)}')
+    baseline = meas.baseline()
+    if baseline is None:
         return
-    vol = put_together(ops.to_range_0_1(meas.zero_filled()))
-    path = os.path.join(args.output_dir, f'zero_filled_{target}.nii.gz')
+    name, volume = baseline
+    line = '[' + name.replace('_', '-') + '] '
+    vol = put_together(ops.to_range_0_1(volume))
+    path = os.path.join(args.output_dir, f'{name}_{target}.nii.gz')
     write(path, vol, aff, hdr)
-    print(f'[kspace] wrote {path}')
+    print(f'[{meas.tag}] wrote {path}')
     if evaluation is not None:
         from . import volume_metrics as VM
         rep = VM.score_arrays(vol, evaluation[0], evaluation[1], None, args.slice_half_range, device, norm=args.norm)
         for ln in VM.format_lines(rep):
-            print('[zero-filled] ' + ln)
-        print(f"[metrics] wrote {VM.write_json(rep, os.path.join(args.output_dir, f'metrics_zero_filled_{target}.json'))}")
-
-
-def _thick_outputs(args, write, put_together, aff, hdr, evaluation, device):
-    """--known_thick: thick_<t>.json next to the prediction, and under --thick_interp thick_interp_<t>.nii.gz = the thick slices
-    interpolated linearly along z, mapped to [0,1], through the prediction's own road (`put_together`: a device [n,S,S] map -> the host
-    volume as written); with an evaluation it is scored into metrics_thick_interp_<t>.json, and under --through_plane its roughness goes
-    to through_plane_thick_interp_<t>.json, beside the prediction's.  Nothing without the flag."""
-    meas = getattr(args, 'thick', None)
-    if meas is None:
-        return
-    from . import ops
-    from . import thick as TK
-    target = args.target_modality.lower()
-    print(f'[thick] wrote {TK.write_json(meas, args.output_dir, args.target_modality)}')
-    if not meas.options['interp']:
-        return
-    vol = put_together(ops.to_range_0_1(meas.interpolated()))
-    path = os.path.join(args.output_dir, f'thick_interp_{target}.nii.gz')
-    write(path, vol, aff, hdr)
-    print(f'[thick] wrote {path}')
-    if evaluation is not None:
-        from . import volume_metrics as VM
-        rep = VM.score_arrays(vol, evaluation[0], evaluation[1], None, args.slice_half_range, device, norm=args.norm)
-        for ln in VM.format_lines(rep):
-            print('[thick-interp] ' + ln)
-        print(f"[metrics] wrote {VM.write_json(rep, os.path.join(args.output_dir, f'metrics_thick_interp_{target}.json'))}")
-    if getattr(args, 'through_plane', False):
+            print(line + ln)
+        print(f"[metrics] wrote {VM.write_json(rep, os.path.join(args.output_dir, f'metrics_{name}_{target}.json'))}")
+    if meas.baseline_through_plane and getattr(args, 'through_plane', False):
         from . import volume_through_plane as TP
         rep = TP.measure_arrays(vol, None if evaluation is None else evaluation[0], None, args.slice_half_range, device, norm=args.norm)
-        print('[thick-interp] ' + TP.format_line(rep))
-        print(f"[through-plane] wrote {TP.write_json(rep, os.path.join(args.output_dir, f'through_plane_thick_interp_{target}.json'))}")
+        print(line + TP.format_line(rep))
+        print(f"[through-plane] wrote {TP.write_json(rep, os.path.join(args.output_dir, f'through_plane_{name}_{target}.json'))}")
 
 
 def _coupling(args):
@@ -787,13 +727,13 @@ def _cached_sampler(args, gen1, gen2, device, samplers, batch):
 
 
 def _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref, evaluation=None, on_device=False, samplers=None, write=None,
-                             stages=None, region=None, known=None):
+                             stages=None, region=None, constraint=None):
     """--num_samples: every slice sampled N times with draws keyed by (--seed, slice, sample) (mudiff_hip.ensemble); the mean and
     the std of the [0,1]-mapped samples, resized back and re-assembled like the single prediction, go to predicted_<t>.nii.gz and
     predicted_<t>_std.nii.gz.  With `evaluation` the mean is scored, the std feeding the uncertainty block.  -> (mean path, std path).
     Under --ensemble_quantiles / --ensemble_center median / --coverage (ensemble.quantile_plan) the per-voxel
     quantile maps take the same road to predicted_<t>_q<PPP>.nii.gz, the median replaces the mean as the centre, and coverage_<t>.json
-    follows the scores.  `region`, `known` (--known_volume): _known_region's pair; every written map then carries the acquired voxels
+    follows the scores.  `region`, `constraint` (--known_volume): _known_region's pair; every written map then carries the acquired voxels
     (the std: 0 there)."""
     from . import ensemble, ops
     from .driver import effective_prec_plan
@@ -805,10 +745,10 @@ def _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref, evaluation=N
     stages = stages or _Stages(None, device)
     sampler = _cached_sampler(args, gen1, gen2, device, samplers, args.batch_size)
     qplan = ensemble.quantile_plan(args)
-    known = known or {}                                              # (--known_volume: predict_from_conditions' region and sampler inputs)
     res = stages.run('sample', lambda: ensemble.sample_ensemble(args, gen1, gen2, conds, args.num_samples, args.seed,
                                                                 batch_size=args.batch_size, map_0_1=True, sampler=sampler,
-                                                                coupling=_coupling(args), quantiles=qplan and qplan.computed, **known))
+                                                                coupling=_coupling(args), quantiles=qplan and qplan.computed,
+                                                                constraint=constraint))
     mean, std = res[:2]
     qmaps = list(res[2]) if qplan is not None else []                # one [n,S,S] map per computed fraction
     os.makedirs(args.output_dir, exist_ok=True)
@@ -835,8 +775,7 @@ def _predict_volume_ensemble(args, gen1, gen2, stacks, device, ref, evaluation=N
         path = os.path.join(args.output_dir, f'predicted_{args.target_modality.lower()}{suffix}.nii.gz')
         stages.run('write', lambda: write(path, vol, aff, hdr))
         paths.append(path)
-    _kspace_outputs(args, write, lambda p: _assemble_map(p, shp, s0, s1, on_device), aff, hdr, evaluation, device)
-    _thick_outputs(args, write, lambda p: _assemble_map(p, shp, s0, s1, on_device), aff, hdr, evaluation, device)
+    _measurement_outputs(args, write, lambda p: _assemble_map(p, shp, s0, s1, on_device), aff, hdr, evaluation, device)
     _intake_report(args).write(args.output_dir, args.target_modality, aff, hdr)
     print(f'[done] saved: {paths[0]} and {paths[1]} | shape={tuple(shp)} | slices={s0}..{s1} | {args.num_samples} samples per slice' +
           _done_tail(args, effective_prec_plan(args)))
@@ -956,12 +895,8 @@ def make_parser(prog='MU-Diff volume prediction (MI355X)'):
     add_calibration_flags(p)                # (also --prec_plan)
     from . import slice_coupling
     slice_coupling.add_flags(p)             # (--slice_coupling, --through_plane: in a late parser, VolumeParser.later())
-    from . import kspace
-    kspace.add_flags(p)                     # (--known_kspace and the --kspace_* flags: in one of their own, before the last two, whose places are pinned)
-    from . import thick
-    thick.add_flags(p)                      # (--known_thick and the --thick_* flags: in one more parser, before the last three)
-    from . import known_region
-    known_region.add_flags(p)               # (--known_volume and its three: in one of their own, before the last)
+    for module in known_modes()[1:] + known_modes()[:1]:      # (each mode's flags in a late parser of its own; --known_volume's place,
+        module.add_flags(p)                                   # before the last, is pinned, so the two later modes' came before it)
     from . import ensemble
     ensemble.add_flags(p)                   # (--ensemble_quantiles, --ensemble_center, --coverage: in a further one)
     return p
@@ -986,21 +921,11 @@ def finish_args(p, args):
         ensemble.quantile_plan(args)                     # (its ValueError names the flag)
     except ValueError as e:
         p.error(str(e))
-    from . import known_region
-    try:
-        known_region.options_from(args)                  # (its ValueError names the flag)
-    except ValueError as e:
-        p.error(str(e))
-    from . import kspace
-    try:
-        kspace.options_from(args)                        # (its ValueError names the flag)
-    except ValueError as e:
-        p.error(str(e))
-    from . import thick
-    try:
-        thick.options_from(args)                         # (its ValueError names the flag)
-    except ValueError as e:
-        p.error(str(e))
+    for module in known_modes():
+        try:
+            module.options_from(args)                    # (its ValueError names the flag)
+        except ValueError as e:
+            p.error(str(e))
     from . import volume_conform as VCF
     from . import volume_reorient as VO
     from .volume_prepare import STAGES
@@ -1027,9 +952,8 @@ def build_argparser(argv=None):
     DESIGN.md sections 5.12 - 5.22; --align's flags sit in VolumeParser.late), and --slice_coupling / --through_plane (mudiff_hip.slice_coupling,
     DESIGN.md section 5.23; in a further late parser), and --ensemble_quantiles / --ensemble_center / --coverage (mudiff_hip.ensemble,
     mudiff_hip.volume_coverage; in one more), and --known_volume / --known_mask / --known_drop_slices /
-    --known_resample (mudiff_hip.known_region; in a parser of their own before that last one), and --known_kspace
-    with the --kspace_* flags (mudiff_hip.kspace; in one more parser, before those two), and --known_thick with
-    the --thick_* flags (mudiff_hip.thick; in one more, after that one)."""
+    --known_resample, --known_kspace with the --kspace_* flags and --known_thick with the --thick_* flags (known_modes(); DESIGN.md sections
+    5.24a - 5.27; each in a parser of its own before that last one)."""
     p = make_parser()
     return finish_args(p, p.parse_args(argv))
 

@@ -424,3 +424,15 @@ def test_a_resampled_partial_field_of_view(runs):
     assert VS.done_line(runs['log']['regrid']).endswith(' | regrid=known_volume | known=0.444')
     pred = runs['pred']('regrid')
     assert np.isfinite(pred).all() and pred[:, :, :3].any() and pred[:, :, 7:].any()
+
+
+def test_with_the_flags_the_bytes_are_those_of_the_separate_code_paths(runs):
+    """The three modes share one constraint path (mudiff_hip.constraints): the runs with the flags write the bytes, and report the
+    residuals, that the commit before it wrote (recorded there: tests/golden/constraint_parent_payloads.json)."""
+    import hashlib
+    from conftest import REPO
+    with open(os.path.join(REPO, 'tests', 'golden', 'constraint_parent_payloads.json')) as f:
+        recorded = json.load(f)['known']
+    for job, suffix in (('known', ''), ('ens', ''), ('ens', '_std'), ('r2', '')):
+        got = VS.payload(str(runs['tmp'] / job / f'predicted_t1ce{suffix}.nii.gz'))
+        assert hashlib.sha256(got).hexdigest() == recorded[job + suffix], job + suffix

@@ -133,3 +133,17 @@ def test_ensemble_and_zero_filled(runs):
     assert np.abs(np.moveaxis(zf, 2, 0) - want).max() <= 1e-5
     both = [json.load(open(tmp / 'zf' / f)) for f in ('metrics_t1ce.json', 'metrics_zero_filled_t1ce.json')]
     assert both[0].keys() == both[1].keys()
+
+
+def test_with_the_flags_the_bytes_are_those_of_the_separate_code_paths(runs):
+    """The three modes share one constraint path (mudiff_hip.constraints): the runs with the flags write the bytes, and report the
+    residuals, that the commit before it wrote (recorded there: tests/golden/constraint_parent_payloads.json)."""
+    import hashlib
+    from conftest import REPO
+    with open(os.path.join(REPO, 'tests', 'golden', 'constraint_parent_payloads.json')) as f:
+        recorded = json.load(f)['kspace']
+    for job, suffix in (('ks', ''), ('ens', ''), ('ens', '_std')):
+        got = VS.payload(str(runs['tmp'] / job / f'predicted_t1ce{suffix}.nii.gz'))
+        assert hashlib.sha256(got).hexdigest() == recorded[job + suffix], job + suffix
+    for job in ('ks', 'ens'):
+        assert runs['report'](job)['max_residual'] == recorded[job + '_max_residual'], job

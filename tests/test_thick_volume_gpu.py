@@ -156,3 +156,17 @@ def test_the_interpolated_baseline(runs):
     both = [json.load(open(tmp / 'interp' / f)) for f in ('through_plane_t1ce.json', 'through_plane_thick_interp_t1ce.json')]
     assert both[0].keys() == both[1].keys()
     assert '[thick-interp] ' in runs['log']['interp']
+
+
+def test_with_the_flags_the_bytes_are_those_of_the_separate_code_paths(runs):
+    """The three modes share one constraint path (mudiff_hip.constraints): the runs with the flags write the bytes, and report the
+    residuals, that the commit before it wrote (recorded there: tests/golden/constraint_parent_payloads.json)."""
+    import hashlib
+    from conftest import REPO
+    with open(os.path.join(REPO, 'tests', 'golden', 'constraint_parent_payloads.json')) as f:
+        recorded = json.load(f)['thick']
+    for job, suffix in (('th', ''), ('ens', ''), ('ens', '_std')):
+        got = VS.payload(str(runs['tmp'] / job / f'predicted_t1ce{suffix}.nii.gz'))
+        assert hashlib.sha256(got).hexdigest() == recorded[job + suffix], job + suffix
+    for job in ('th', 'ens'):
+        assert runs['report'](job)['max_residual'] == recorded[job + '_max_residual'], job
