@@ -21,8 +21,7 @@ __global__ __launch_bounds__(256) void k_posterior(const float* __restrict__ x01
                                                    int ntab, float* __restrict__ out, int64_t per_sample) {
 #pragma clang fp contract(off)   // every * and + below rounds separately, like the reference's chain of torch ops
   const int b = blockIdx.y;
-  int64_t ti = t[b];
-  ti = ti < 0 ? 0 : (ti >= ntab ? ntab - 1 : ti);
+  const int64_t ti = mud_level_index(t, b, 0, ntab);
   const float c1 = c1t[ti], c2 = c2t[ti];
   const float sd = (ti == 0) ? 0.0f : sdt[ti];   // nonzero_mask * exp(0.5*log_var)
   const int64_t base = (int64_t)b * per_sample;
@@ -82,8 +81,7 @@ __global__ __launch_bounds__(256) void k_q_sample(const float* __restrict__ x, c
                                                   int64_t per_sample) {
 #pragma clang fp contract(off)
   const int b = blockIdx.y;
-  int64_t ti = t[b] + toff;
-  ti = ti < 0 ? 0 : (ti >= ntab ? ntab - 1 : ti);
+  const int64_t ti = mud_level_index(t, b, toff, ntab);
   const float a = at[ti], sg = st[ti];
   const int64_t base = (int64_t)b * per_sample;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < per_sample; i += (int64_t)gridDim.x * blockDim.x)

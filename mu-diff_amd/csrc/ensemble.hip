@@ -10,41 +10,34 @@
 //  - order statistics: per pixel, up to 8 quantiles of the N samples (the median, an interval's bounds) from a sorting network in
 //    registers: the same one read of the samples, a fixed function of them as well.
 // DESIGN.md section 5.7 has the definitions and the order arguments.
-#include "keyed_normal.h"      // es_philox, es_box_muller, es_block_normals (shared with known_region.hip)
+#include "keyed_rows.h"        // the quad mapping and store, and keyed_normal.h: es_philox, es_box_muller, es_block_normals
 
 #define ES_THREADS 256
 
-// one thread = one Philox block = 4 consecutive elements of one row
+// one thread = one Philox block = one quad of one row.  VEC: row_len % 4 == 0 and out 16-byte aligned: every block is whole and aligned
+template <bool VEC>
 __global__ __launch_bounds__(ES_THREADS) void k_randn_keyed(float* __restrict__ out, int rows, int64_t row_len, int64_t blocks_per_row,
-                                                            const int64_t* __restrict__ keys, uint64_t seed, uint64_t word2, int vec) {
-  const int64_t t = (int64_t)blockIdx.x * ES_THREADS + threadIdx.x;
-  if (t >= (int64_t)rows * blocks_per_row) return;
-  const int64_t r = t / blocks_per_row, b = t - r * blocks_per_row;
-  const uint64_t slice = (uint64_t)keys[2 * r], sample = (uint64_t)keys[2 * r + 1];
-  const f32x4 v = es_block_normals((uint64_t)b, slice, sample, seed, word2);
-  float* dst = out + r * row_len + 4 * b;
-  if (vec) {                       // row_len % 4 == 0 and out 16-byte aligned: every block is whole and aligned
-    *reinterpret_cast<f32x4*>(dst) = v;
-  } else {
-    const int64_t n = row_len - 4 * b < 4 ? row_len - 4 * b : 4;
-    for (int e = 0; e < n; ++e) dst[e] = v[e];
-  }
+                                                            const int64_t* __restrict__ keys, uint64_t seed, uint64_t word2) {
+  row_quad q;
+  if (!row_quad_of<VEC>((int64_t)blockIdx.x * ES_THREADS + threadIdx.x, rows, row_len, blocks_per_row, q)) return;
+  quad_store<VEC>(out + q.base, es_block_normals((uint64_t)q.b, (uint64_t)keys[2 * q.r], (uint64_t)keys[2 * q.r + 1], seed, word2), q.n);
 }
 
 extern "C" int mud_randn_keyed(float* out, int rows, int64_t row_len, const int64_t* keys, uint64_t seed, int step, int kind, void* stream) {
   MUD_REQUIRE(rows >= 0 && row_len > 0, "mud_randn_keyed: bad sizes (rows %d, row_len %lld)", rows, (long long)row_len);
   MUD_REQUIRE((kind >= 0 && kind <= 2) || kind == 5 || kind == 6,
               "mud_randn_keyed: kind must be 0 (x_init), 1 (z), 2 (posterior noise), 5 (k-space) or 6 (thick slices), got %d", kind);
-  MUD_REQUIRE(step >= 0 && step < (1 << 24), "mud_randn_keyed: step must be in [0, 2^24), got %d", step);
+  uint64_t word2;
+  MUD_TRY(keyed_step_word2("mud_randn_keyed", step, kind, word2));
   MUD_REQUIRE(out && keys, "mud_randn_keyed: null pointer");
   if (rows == 0) return MUD_OK;
   const int64_t bpr = mud_cdiv(row_len, 4);
   const int64_t threads = (int64_t)rows * bpr;
   MUD_REQUIRE(mud_cdiv(threads, ES_THREADS) <= 0x7fffffff, "mud_randn_keyed: too many elements");
-  const int vec = (row_len % 4 == 0) && mud_aligned16(out);
-  const uint64_t word2 = ((uint64_t)step << 8) | (uint64_t)kind;
-  hipLaunchKernelGGL(k_randn_keyed, dim3((unsigned)mud_cdiv(threads, ES_THREADS)), dim3(ES_THREADS), 0, (hipStream_t)stream, out, rows,
-                     row_len, bpr, keys, seed, word2, vec);
+  vec_dispatch(row_len % 4 == 0 && mud_aligned16(out), [&](auto v) {
+    hipLaunchKernelGGL(k_randn_keyed<VEC_OF(v)>, dim3((unsigned)mud_cdiv(threads, ES_THREADS)), dim3(ES_THREADS), 0, (hipStream_t)stream, out, rows,
+                       row_len, bpr, keys, seed, word2);
+  });
   MUD_CHECK_LAUNCH("mud_randn_keyed");
   return MUD_OK;
 }
@@ -59,20 +52,20 @@ struct es_taps {
   double w[ES_MAX_RADIUS + 1];
 };
 
-// the thread mapping and the two store paths of k_randn_keyed; per tap one Philox block and its two Box-Muller pairs, the products and
+// the thread mapping and the store of k_randn_keyed; per tap one Philox block and its two Box-Muller pairs, the products and
 // the sums in fp64 in tap order j = -R..R, each rounded once (no contraction), the result rounded to fp32 once
+template <bool VEC>
 __global__ __launch_bounds__(ES_THREADS) void k_randn_keyed_coupled(float* __restrict__ out, int rows, int64_t row_len, int64_t blocks_per_row,
-                                                                    const int64_t* __restrict__ keys, uint64_t seed, uint64_t word2, int vec,
-                                                                    es_taps taps, int radius) {
+                                                                    const int64_t* __restrict__ keys, uint64_t seed, uint64_t word2, es_taps taps,
+                                                                    int radius) {
 #pragma clang fp contract(off)
-  const int64_t t = (int64_t)blockIdx.x * ES_THREADS + threadIdx.x;
-  if (t >= (int64_t)rows * blocks_per_row) return;
-  const int64_t r = t / blocks_per_row, b = t - r * blocks_per_row;
-  const uint64_t slice = (uint64_t)keys[2 * r], sample = (uint64_t)keys[2 * r + 1];
+  row_quad q;
+  if (!row_quad_of<VEC>((int64_t)blockIdx.x * ES_THREADS + threadIdx.x, rows, row_len, blocks_per_row, q)) return;
+  const uint64_t slice = (uint64_t)keys[2 * q.r], sample = (uint64_t)keys[2 * q.r + 1];
   double acc[4] = {0.0, 0.0, 0.0, 0.0};
   for (int j = -radius; j <= radius; ++j) {                // uniform over the launch
     const double w = taps.w[j < 0 ? -j : j];
-    uint64_t c0 = (uint64_t)b, c1 = slice + (uint64_t)(int64_t)j, c2 = (sample << 32) | word2, c3 = 0;
+    uint64_t c0 = (uint64_t)q.b, c1 = slice + (uint64_t)(int64_t)j, c2 = (sample << 32) | word2, c3 = 0;
     es_philox(c0, c1, c2, c3, seed, ES_KEY_HI);
     float e0, e1, e2, e3;
     es_box_muller(c0, c1, e0, e1);
@@ -85,20 +78,15 @@ __global__ __launch_bounds__(ES_THREADS) void k_randn_keyed_coupled(float* __res
   f32x4 v;
 #pragma unroll
   for (int e = 0; e < 4; ++e) v[e] = (float)acc[e];
-  float* dst = out + r * row_len + 4 * b;
-  if (vec) {
-    *reinterpret_cast<f32x4*>(dst) = v;
-  } else {
-    const int64_t n = row_len - 4 * b < 4 ? row_len - 4 * b : 4;
-    for (int e = 0; e < n; ++e) dst[e] = v[e];
-  }
+  quad_store<VEC>(out + q.base, v, q.n);
 }
 
 extern "C" int mud_randn_keyed_coupled(float* out, int rows, int64_t row_len, const int64_t* keys, uint64_t seed, int step, int kind,
                                        const double* half_taps, int radius, void* stream) {
   MUD_REQUIRE(rows >= 0 && row_len > 0, "mud_randn_keyed_coupled: bad sizes (rows %d, row_len %lld)", rows, (long long)row_len);
   MUD_REQUIRE(kind >= 0 && kind <= 2, "mud_randn_keyed_coupled: kind must be 0 (x_init), 1 (z) or 2 (posterior noise), got %d", kind);
-  MUD_REQUIRE(step >= 0 && step < (1 << 24), "mud_randn_keyed_coupled: step must be in [0, 2^24), got %d", step);
+  uint64_t word2;
+  MUD_TRY(keyed_step_word2("mud_randn_keyed_coupled", step, kind, word2));
   MUD_REQUIRE(radius >= 0 && radius <= ES_MAX_RADIUS, "mud_randn_keyed_coupled: radius must be in [0, %d], got %d", ES_MAX_RADIUS, radius);
   MUD_REQUIRE(out && keys && half_taps, "mud_randn_keyed_coupled: null pointer");
   es_taps taps;
@@ -110,10 +98,10 @@ extern "C" int mud_randn_keyed_coupled(float* out, int rows, int64_t row_len, co
   const int64_t bpr = mud_cdiv(row_len, 4);
   const int64_t threads = (int64_t)rows * bpr;
   MUD_REQUIRE(mud_cdiv(threads, ES_THREADS) <= 0x7fffffff, "mud_randn_keyed_coupled: too many elements");
-  const int vec = (row_len % 4 == 0) && mud_aligned16(out);
-  const uint64_t word2 = ((uint64_t)step << 8) | (uint64_t)kind;
-  hipLaunchKernelGGL(k_randn_keyed_coupled, dim3((unsigned)mud_cdiv(threads, ES_THREADS)), dim3(ES_THREADS), 0, (hipStream_t)stream, out, rows,
-                     row_len, bpr, keys, seed, word2, vec, taps, radius);
+  vec_dispatch(row_len % 4 == 0 && mud_aligned16(out), [&](auto v) {
+    hipLaunchKernelGGL(k_randn_keyed_coupled<VEC_OF(v)>, dim3((unsigned)mud_cdiv(threads, ES_THREADS)), dim3(ES_THREADS), 0, (hipStream_t)stream, out,
+                       rows, row_len, bpr, keys, seed, word2, taps, radius);
+  });
   MUD_CHECK_LAUNCH("mud_randn_keyed_coupled");
   return MUD_OK;
 }

@@ -1,4 +1,4 @@
-// The keyed Gaussian draw shared by ensemble.hip (mud_randn_keyed, mud_randn_keyed_coupled) and known_region.hip (mud_known_constrain):
+// The keyed Gaussian draw shared by ensemble.hip, known_region.hip, kspace.hip and slab.hip (through keyed_rows.h, the row toolkit on top):
 // counter-based Philox4x64-10 (Random123; the algorithm and word order of numpy.random.Philox) and Box-Muller in fp64.  One Philox block
 // gives 4 consecutive elements of one row; include/mudiff_hip.h (mud_randn_keyed) has the counter layout.
 #pragma once

@@ -5,116 +5,62 @@
 //    keyed Philox draw (keyed_normal.h), so nothing is pre-drawn and a row's result depends on (seed, its key) alone;
 //  - coverage: which voxels of a resampled known volume were interpolated from acquired voxels only.
 // No LDS, no atomics: both are fixed functions of their inputs.
-#include "keyed_normal.h"
+#include "keyed_rows.h"
 
 #define KR_THREADS 256
 
-// one thread = one Philox block = 4 consecutive elements of one row (k_randn_keyed's mapping).  out may alias x_new or known: a thread
-// reads its 4 elements of each before it writes them, and no other thread touches them.  VEC: row_len % 4 == 0 and every pointer aligned
-// for a 16-byte (mask: 4-byte) access; else element by element, the last block of a row cut to the row.
+// one thread = one quad (keyed_rows.h: row_quad_of).  out may alias x_new or known: a thread reads its 4 elements of each before it
+// writes them, and no other thread touches them.  VEC: row_len % 4 == 0 and every pointer aligned for a 16-byte (mask: 4-byte) access.
 template <bool VEC>
-__global__ __launch_bounds__(KR_THREADS) void k_known_constrain(const float* x_new, const float* known, const uint8_t* __restrict__ mask,
-                                                                const float* __restrict__ noise, const int64_t* __restrict__ keys, uint64_t seed,
-                                                                uint64_t word2, const int64_t* __restrict__ t, int toff,
-                                                                const float* __restrict__ at, const float* __restrict__ st, int ntab, int clean,
+__global__ __launch_bounds__(KR_THREADS) void k_known_constrain(const float* x_new, const float* known, const uint8_t* __restrict__ mask, keyed_level d,
                                                                 float* out, int rows, int64_t row_len, int64_t blocks_per_row) {
 #pragma clang fp contract(off)   // a * known + sg * eta: mul, mul, add, each rounded once, in k_q_sample's order
-  const int64_t tid = (int64_t)blockIdx.x * KR_THREADS + threadIdx.x;
-  if (tid >= (int64_t)rows * blocks_per_row) return;
-  const int64_t r = tid / blocks_per_row, b = tid - r * blocks_per_row;
-  const int64_t base = r * row_len + 4 * b;
-  const int n = VEC ? 4 : (int)(row_len - 4 * b < 4 ? row_len - 4 * b : 4);
-  bool m[4] = {false, false, false, false};
-  f32x4 x = {0.f, 0.f, 0.f, 0.f}, k = {0.f, 0.f, 0.f, 0.f};
+  row_quad q;
+  if (!row_quad_of<VEC>((int64_t)blockIdx.x * KR_THREADS + threadIdx.x, rows, row_len, blocks_per_row, q)) return;
+  bool m[4] = {q.n > 0, q.n > 1, q.n > 2, q.n > 3};             // no mask: known everywhere
+  f32x4 x = {0.f, 0.f, 0.f, 0.f};
   if (mask) {
-    if constexpr (VEC) {
-      const uchar4 mv = *reinterpret_cast<const uchar4*>(mask + base);
-      m[0] = mv.x != 0;
-      m[1] = mv.y != 0;
-      m[2] = mv.z != 0;
-      m[3] = mv.w != 0;
-      x = *reinterpret_cast<const f32x4*>(x_new + base);
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        if (e < n) {
-          m[e] = mask[base + e] != 0;
-          x[e] = x_new[base + e];
-        }
-      }
-    }
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) m[e] = e < n;
+    quad_load_mask<VEC>(mask + q.base, q.n, m);
+    x = quad_load<VEC>(x_new + q.base, q.n);
   }
   f32x4 o = x;
   if (m[0] || m[1] || m[2] || m[3]) {            // a thread with nothing known skips the loads of `known` and the draw
-    if constexpr (VEC) {
-      k = *reinterpret_cast<const f32x4*>(known + base);
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (e < n) k[e] = known[base + e];
-    }
-    f32x4 q = k;
-    if (!clean) {
-      int64_t ti = t[r] + toff;
-      ti = ti < 0 ? 0 : (ti >= ntab ? ntab - 1 : ti);
-      const float a = at[ti], sg = st[ti];
-      f32x4 eta = {0.f, 0.f, 0.f, 0.f};
-      if (noise) {
-        if constexpr (VEC) {
-          eta = *reinterpret_cast<const f32x4*>(noise + base);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (e < n) eta[e] = noise[base + e];
-        }
-      } else {
-        eta = es_block_normals((uint64_t)b, (uint64_t)keys[2 * r], (uint64_t)keys[2 * r + 1], seed, word2);
-      }
+    const f32x4 k = quad_load<VEC>(known + q.base, q.n);
+    f32x4 ks = k;
+    if (!d.clean) {
+      const int64_t ti = mud_level_index(d.t, q.r, d.toff, d.ntab);
+      const float a = d.at[ti], sg = d.st[ti];
+      const f32x4 eta = quad_eta<VEC>(d, q.r, (uint64_t)q.b, q.base, q.n);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float p0 = a * k[e], p1 = sg * eta[e];
-        q[e] = p0 + p1;
+        ks[e] = p0 + p1;
       }
     }
 #pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = m[e] ? q[e] : x[e];      // a select: what `known` holds where the mask is 0 never reaches out
+    for (int e = 0; e < 4; ++e) o[e] = m[e] ? ks[e] : x[e];     // a select: what `known` holds where the mask is 0 never reaches out
   }
-  if constexpr (VEC) {
-    *reinterpret_cast<f32x4*>(out + base) = o;
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (e < n) out[base + e] = o[e];
-  }
+  quad_store<VEC>(out + q.base, o, q.n);
 }
 
 extern "C" int mud_known_constrain(const float* x_new, const float* known, const uint8_t* mask, const float* noise, const int64_t* keys,
                                    uint64_t seed, int step, int kind, const int64_t* t, int toff, const float* a_tab, const float* s_tab,
                                    int ntab, int clean, float* out, int rows, int64_t row_len, void* stream) {
+  keyed_level d = {noise, keys, seed, 0, t, toff, a_tab, s_tab, ntab, clean};
   MUD_REQUIRE(rows > 0 && row_len > 0, "mud_known_constrain: bad sizes (rows %d, row_len %lld)", rows, (long long)row_len);
-  MUD_REQUIRE(ntab > 0, "mud_known_constrain: ntab must be > 0, got %d", ntab);
-  MUD_REQUIRE(kind >= 0 && kind <= 15, "mud_known_constrain: kind must be in [0, 15], got %d", kind);
-  MUD_REQUIRE(step >= 0 && step < (1 << 24), "mud_known_constrain: step must be in [0, 2^24), got %d", step);
+  MUD_TRY(keyed_level_word2("mud_known_constrain", ntab, kind, step, d.word2));
   MUD_REQUIRE(known && out, "mud_known_constrain: null pointer (known, out)");
   MUD_REQUIRE(!mask || x_new, "mud_known_constrain: null pointer (x_new may be NULL only when mask is)");
-  MUD_REQUIRE(clean || (t && a_tab && s_tab), "mud_known_constrain: null pointer (t, a_tab, s_tab)");
-  MUD_REQUIRE(clean || noise || keys, "mud_known_constrain: without injected noise the draw needs keys");
+  MUD_TRY(keyed_level_operands("mud_known_constrain", true, d));
   const int64_t bpr = mud_cdiv(row_len, 4);
   const int64_t threads = (int64_t)rows * bpr;
   MUD_REQUIRE(mud_cdiv(threads, KR_THREADS) <= 0x7fffffff, "mud_known_constrain: too many elements");
   const bool vec = row_len % 4 == 0 && mud_aligned16(known) && mud_aligned16(out) && (!mask || (mud_aligned16(x_new) && (((uintptr_t)mask) & 3u) == 0)) &&
                    (!noise || mud_aligned16(noise));
-  const uint64_t word2 = ((uint64_t)step << 8) | (uint64_t)kind;
-  const dim3 grid((unsigned)mud_cdiv(threads, KR_THREADS));
-  if (vec)
-    hipLaunchKernelGGL(k_known_constrain<true>, grid, dim3(KR_THREADS), 0, (hipStream_t)stream, x_new, known, mask, noise, keys, seed, word2, t, toff,
-                       a_tab, s_tab, ntab, clean, out, rows, row_len, bpr);
-  else
-    hipLaunchKernelGGL(k_known_constrain<false>, grid, dim3(KR_THREADS), 0, (hipStream_t)stream, x_new, known, mask, noise, keys, seed, word2, t, toff,
-                       a_tab, s_tab, ntab, clean, out, rows, row_len, bpr);
+  vec_dispatch(vec, [&](auto v) {
+    hipLaunchKernelGGL(k_known_constrain<VEC_OF(v)>, dim3((unsigned)mud_cdiv(threads, KR_THREADS)), dim3(KR_THREADS), 0, (hipStream_t)stream, x_new, known,
+                       mask, d, out, rows, row_len, bpr);
+  });
   MUD_CHECK_LAUNCH("mud_known_constrain");
   return MUD_OK;
 }

@@ -6,7 +6,7 @@
 //    the load), columns forward -> residual -> columns inverse without leaving LDS, rows inverse (the epilogue fused into the store).
 // A workgroup owns KS_LINES(S) whole lines from load to store, so in place is allowed; no atomics, and a slice's result is a function of
 // that slice's operands alone.  Twiddles: fp64 sincospi rounded to fp32, S/2 of them per workgroup into LDS.
-#include "keyed_normal.h"
+#include "keyed_rows.h"
 #include "kspace_fft.h"
 
 #pragma clang fp contract(off)   // s * eta, x - p, a * y, D - ay: each rounded once, as tests/kspace_ref.py states them
@@ -59,13 +59,7 @@ __device__ __forceinline__ void ks_lines_dit(float2* x, int P, int logL, int log
 // what the constraint's row passes need beside the lines
 struct ks_con {
   const float* x_new;
-  const float* noise;
-  const int64_t* keys;
-  uint64_t seed, word2;
-  const int64_t* t;
-  int toff;
-  const float* st;
-  int ntab, clean;
+  keyed_level d;
   float* out;
 };
 
@@ -100,13 +94,10 @@ __global__ __launch_bounds__(KS_THREADS) void k_ks_rows(const void* in, float2* 
       const int l = i >> (logS - 2), c4 = i & ((S >> 2) - 1);
       const int64_t line = line0 + l, r = line >> logS, u = line & (S - 1);
       const int64_t g = (line << logS) + 4 * c4;
-      f32x4 d = *reinterpret_cast<const f32x4*>(c.x_new + g);
-      if (!c.clean) {
-        int64_t ti = c.t[r] + c.toff;
-        ti = ti < 0 ? 0 : (ti >= c.ntab ? c.ntab - 1 : ti);
-        const float s = c.st[ti];
-        const f32x4 eta = c.noise ? *reinterpret_cast<const f32x4*>(c.noise + g)
-                                  : es_block_normals((uint64_t)((u << (logS - 2)) + c4), (uint64_t)c.keys[2 * r], (uint64_t)c.keys[2 * r + 1], c.seed, c.word2);
+      f32x4 d = quad_load<true>(c.x_new + g, 4);
+      if (!c.d.clean) {
+        const float s = c.d.st[mud_level_index(c.d.t, r, c.d.toff, c.d.ntab)];
+        const f32x4 eta = quad_eta<true>(c.d, r, (uint64_t)((u << (logS - 2)) + c4), g, 4);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const float p = s * eta[e];
@@ -165,11 +156,7 @@ __global__ __launch_bounds__(KS_THREADS) void k_ks_cols(float2* data, const floa
   ks_lines_dif(x, P, logL, logS, tw, CON ? false : inverse != 0);
   if constexpr (CON) {
     float a = 1.0f;
-    if (!clean) {
-      int64_t ti = t[r] + toff;
-      ti = ti < 0 ? 0 : (ti >= ntab ? ntab - 1 : ti);
-      a = at[ti];
-    }
+    if (!clean) a = at[mud_level_index(t, r, toff, ntab)];
     const uint8_t* m = mask + (mask_rows == 1 ? 0 : (r << (2 * logS)));
     const float2* ys = y + (r << (2 * logS));
     for (int i = threadIdx.x; i < L * S; i += KS_THREADS) {
@@ -232,16 +219,14 @@ extern "C" int mud_fft2_r2c(const float* in, float* out, int rows, int S, int in
 extern "C" int mud_kspace_constrain(const float* x_new, const float* y, const uint8_t* mask, int mask_rows, const float* noise, const int64_t* keys,
                                     uint64_t seed, int step, int kind, const int64_t* t, int toff, const float* a_tab, const float* s_tab, int ntab,
                                     int clean, float* out, float* work, int rows, int S, void* stream) {
+  ks_con c = {x_new, {noise, keys, seed, 0, t, toff, a_tab, s_tab, ntab, clean}, out};
   const int logS = ks_log2(S);
   MUD_REQUIRE(logS > 0, "mud_kspace_constrain: S must be a power of two in [%d, %d], got %d", KS_MIN_S, KS_MAX_S, S);
   MUD_REQUIRE(rows > 0 && (int64_t)rows * S * S < (1ll << 31), "mud_kspace_constrain: rows must be > 0 with rows * S * S < 2^31, got %d", rows);
   MUD_REQUIRE(mask_rows == 1 || mask_rows == rows, "mud_kspace_constrain: mask_rows must be 1 or rows (%d), got %d", rows, mask_rows);
-  MUD_REQUIRE(ntab > 0, "mud_kspace_constrain: ntab must be > 0, got %d", ntab);
-  MUD_REQUIRE(kind >= 0 && kind <= 15, "mud_kspace_constrain: kind must be in [0, 15], got %d", kind);
-  MUD_REQUIRE(step >= 0 && step < (1 << 24), "mud_kspace_constrain: step must be in [0, 2^24), got %d", step);
+  MUD_TRY(keyed_level_word2("mud_kspace_constrain", ntab, kind, step, c.d.word2));
   MUD_REQUIRE(x_new && y && mask && out && work, "mud_kspace_constrain: null pointer (x_new, y, mask, out, work)");
-  MUD_REQUIRE(clean || (t && a_tab && s_tab), "mud_kspace_constrain: null pointer (t, a_tab, s_tab)");
-  MUD_REQUIRE(clean || noise || keys, "mud_kspace_constrain: without injected noise the draw needs keys");
+  MUD_TRY(keyed_level_operands("mud_kspace_constrain", true, c.d));
   MUD_REQUIRE(mud_aligned16(x_new) && mud_aligned16(out) && (!noise || mud_aligned16(noise)) && (((uintptr_t)y | (uintptr_t)work) & 7u) == 0,
               "mud_kspace_constrain: x_new, out and noise must be 16-byte aligned, y and work 8-byte");
   MUD_REQUIRE((const void*)work != (const void*)x_new && (const void*)work != (const void*)out && (const void*)work != (const void*)y,
@@ -251,18 +236,6 @@ extern "C" int mud_kspace_constrain(const float* x_new, const float* y, const ui
   const size_t lds = ks_lds_bytes(S);
   hipStream_t st = (hipStream_t)stream;
   float2* w = reinterpret_cast<float2*>(work);
-  ks_con c;
-  c.x_new = x_new;
-  c.noise = noise;
-  c.keys = keys;
-  c.seed = seed;
-  c.word2 = ((uint64_t)step << 8) | (uint64_t)kind;
-  c.t = t;
-  c.toff = toff;
-  c.st = s_tab;
-  c.ntab = ntab;
-  c.clean = clean;
-  c.out = out;
   hipLaunchKernelGGL((k_ks_rows<KS_ROW_FWD, false>), grid_rows, dim3(KS_THREADS), lds, st, (const void*)nullptr, w, c, logS, logL, 0);
   MUD_CHECK_LAUNCH("mud_kspace_constrain");
   hipLaunchKernelGGL(k_ks_cols<true>, grid_cols, dim3(KS_THREADS), lds, st, w, reinterpret_cast<const float2*>(y), mask, mask_rows, t, toff, a_tab, ntab,

@@ -58,6 +58,13 @@ struct mud_attr_once {
 static inline bool mud_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 static inline int64_t mud_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// the noise-level index of row r: t[r] + toff clamped into the tables' [0, ntab).  The one clamp of the posterior, q_sample and the
+// constraints (keyed_rows.h): integers only
+__device__ __forceinline__ int64_t mud_level_index(const int64_t* __restrict__ t, int64_t r, int toff, int ntab) {
+  const int64_t ti = t[r] + toff;
+  return ti < 0 ? 0 : (ti >= ntab ? ntab - 1 : ti);
+}
+
 __device__ __forceinline__ float mud_silu(float v) { return v / (1.0f + expf(-v)); }
 __device__ __forceinline__ float mud_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
 

@@ -7,7 +7,7 @@
 // rows' positions, one thread owns 4 consecutive elements of one group (all its members), and the draw is keyed (keyed_normal.h): a
 // group's result is a function of its own rows, its table and its keys alone.  No LDS, no atomics, no contraction.
 #include <vector>
-#include "keyed_normal.h"
+#include "keyed_rows.h"
 
 #define SL_THREADS 256
 #define SL_GROUPS 32             // groups per launch
@@ -21,39 +21,12 @@ struct sl_tables {
   float g[SL_SLOTS];
 };
 
-template <bool VEC>
-__device__ __forceinline__ f32x4 sl_load(const float* p, int n) {
-  f32x4 v = {0.f, 0.f, 0.f, 0.f};
-  if constexpr (VEC) {
-    v = *reinterpret_cast<const f32x4*>(p);
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (e < n) v[e] = p[e];
-  }
-  return v;
-}
-
-template <bool VEC>
-__device__ __forceinline__ void sl_store(float* p, f32x4 v, int n) {
-  if constexpr (VEC) {
-    *reinterpret_cast<f32x4*>(p) = v;
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (e < n) p[e] = v[e];
-  }
-}
-
 // grid (blocks over the row's quads, groups of this launch).  AVERAGE: out = avg [groups][row_len], nothing else is written.  Else out may
 // alias x_new: a thread reads its 4 elements of a member row before it writes them, and no other thread touches them (a row is in one
 // group once: validated on the host).  VEC: row_len % 4 == 0 and every pointer 16-byte aligned; else element by element, the last quad cut.
 template <bool VEC, bool AVERAGE>
-__global__ __launch_bounds__(SL_THREADS) void k_slab(const float* x_new, const float* __restrict__ y, sl_tables tab, int group0,
-                                                     const float* __restrict__ noise, const int64_t* __restrict__ keys, uint64_t seed, uint64_t word2,
-                                                     const int64_t* __restrict__ t, int toff, const float* __restrict__ at,
-                                                     const float* __restrict__ st, int ntab, int clean, float* out, int64_t row_len,
-                                                     int64_t blocks_per_row) {
+__global__ __launch_bounds__(SL_THREADS) void k_slab(const float* x_new, const float* __restrict__ y, sl_tables tab, int group0, keyed_level lv, float* out,
+                                                     int64_t row_len, int64_t blocks_per_row) {
 #pragma clang fp contract(off)   // s * eta, x - ., w * ., acc + .: each rounded once
   const int64_t b = (int64_t)blockIdx.x * SL_THREADS + threadIdx.x;
   if (b >= blocks_per_row) return;
@@ -61,22 +34,19 @@ __global__ __launch_bounds__(SL_THREADS) void k_slab(const float* x_new, const f
   const int s0 = tab.start[q], s1 = tab.start[q + 1];
   const int64_t col = 4 * b;
   const int n = VEC ? 4 : (int)(row_len - col < 4 ? row_len - col : 4);
-  const bool noisy = !AVERAGE && !clean;
+  const bool noisy = !AVERAGE && !lv.clean;
   float a = 1.f, sg = 0.f;
   if (noisy) {
-    int64_t ti = t[tab.member[s0]] + toff;              // the level of the group's first member
-    ti = ti < 0 ? 0 : (ti >= ntab ? ntab - 1 : ti);
-    a = at[ti];
-    sg = st[ti];
+    const int64_t ti = mud_level_index(lv.t, tab.member[s0], lv.toff, lv.ntab);      // the level of the group's first member
+    a = lv.at[ti];
+    sg = lv.st[ti];
   }
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   for (int s = s0; s < s1; ++s) {                       // table order
     const int64_t base = (int64_t)tab.member[s] * row_len + col;
-    f32x4 d = sl_load<VEC>(x_new + base, n);
+    f32x4 d = quad_load<VEC>(x_new + base, n);
     if (noisy) {
-      const int64_t r = tab.member[s];
-      const f32x4 eta = noise ? sl_load<VEC>(noise + base, n)
-                              : es_block_normals((uint64_t)b, (uint64_t)keys[2 * r], (uint64_t)keys[2 * r + 1], seed, word2);
+      const f32x4 eta = quad_eta<VEC>(lv, tab.member[s], (uint64_t)b, base, n);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float p = sg * eta[e];
@@ -92,9 +62,9 @@ __global__ __launch_bounds__(SL_THREADS) void k_slab(const float* x_new, const f
   }
   const int64_t gbase = (int64_t)(group0 + q) * row_len + col;
   if constexpr (AVERAGE) {
-    sl_store<VEC>(out + gbase, acc, n);
+    quad_store<VEC>(out + gbase, acc, n);
   } else {
-    const f32x4 yv = sl_load<VEC>(y + gbase, n);
+    const f32x4 yv = quad_load<VEC>(y + gbase, n);
     f32x4 r;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -103,7 +73,7 @@ __global__ __launch_bounds__(SL_THREADS) void k_slab(const float* x_new, const f
     }
     for (int s = s0; s < s1; ++s) {
       const int64_t base = (int64_t)tab.member[s] * row_len + col;
-      const f32x4 x = sl_load<VEC>(x_new + base, n);
+      const f32x4 x = quad_load<VEC>(x_new + base, n);
       const float g = tab.g[s];
       f32x4 o;
 #pragma unroll
@@ -112,7 +82,7 @@ __global__ __launch_bounds__(SL_THREADS) void k_slab(const float* x_new, const f
         const float v = x[e] - c;
         o[e] = c == 0.f ? x[e] : v;                     // a correction that is 0 leaves x_new's bits (a -0 included)
       }
-      sl_store<VEC>(out + base, o, n);
+      quad_store<VEC>(out + base, o, n);
     }
   }
 }
@@ -163,27 +133,37 @@ static int sl_pack(const char* who, const int32_t* members, const float* weights
   return MUD_OK;
 }
 
-#define SL_LAUNCH(VEC, AVG, ...) hipLaunchKernelGGL((k_slab<VEC, AVG>), grid, dim3(SL_THREADS), 0, (hipStream_t)stream, __VA_ARGS__)
+// the launches of one call
+template <bool AVERAGE>
+static int sl_run(const char* who, bool vec, const float* x, const float* y, const std::vector<sl_tables>& launches, const std::vector<int>& first_group,
+                  const std::vector<int>& n_groups, const keyed_level& d, float* out, int64_t row_len, void* stream) {
+  const int64_t bpr = mud_cdiv(row_len, 4);
+  for (size_t i = 0; i < launches.size(); ++i) {
+    vec_dispatch(vec, [&](auto v) {
+      hipLaunchKernelGGL((k_slab<VEC_OF(v), AVERAGE>), dim3((unsigned)mud_cdiv(bpr, SL_THREADS), (unsigned)n_groups[i]), dim3(SL_THREADS), 0,
+                         (hipStream_t)stream, x, y, launches[i], first_group[i], d, out, row_len, bpr);
+    });
+    MUD_CHECK_LAUNCH(who);
+  }
+  return MUD_OK;
+}
 
 extern "C" int mud_slab_constrain(const float* x_new, const float* y, const int32_t* members, const float* weights, const float* gains, int groups,
                                   int L, const float* noise, const int64_t* keys, uint64_t seed, int step, int kind, const int64_t* t, int toff,
                                   const float* a_tab, const float* s_tab, int ntab, int clean, float* out, int rows, int64_t row_len, void* stream) {
+  keyed_level d = {noise, keys, seed, 0, t, toff, a_tab, s_tab, ntab, clean};
   MUD_REQUIRE(rows > 0 && row_len > 0, "mud_slab_constrain: bad sizes (rows %d, row_len %lld)", rows, (long long)row_len);
   MUD_REQUIRE((int64_t)rows * row_len < (1ll << 31), "mud_slab_constrain: rows * row_len must be < 2^31, got %d x %lld", rows, (long long)row_len);
   MUD_REQUIRE(groups >= 0 && groups <= rows, "mud_slab_constrain: groups must be in [0, rows = %d], got %d", rows, groups);
   MUD_REQUIRE(L >= 1 && L <= MUD_SLAB_MAX_MEMBERS, "mud_slab_constrain: L must be in [1, %d], got %d", MUD_SLAB_MAX_MEMBERS, L);
-  MUD_REQUIRE(ntab > 0, "mud_slab_constrain: ntab must be > 0, got %d", ntab);
-  MUD_REQUIRE(kind >= 0 && kind <= 15, "mud_slab_constrain: kind must be in [0, 15], got %d", kind);
-  MUD_REQUIRE(step >= 0 && step < (1 << 24), "mud_slab_constrain: step must be in [0, 2^24), got %d", step);
+  MUD_TRY(keyed_level_word2("mud_slab_constrain", ntab, kind, step, d.word2));
   MUD_REQUIRE(x_new && out, "mud_slab_constrain: null pointer (x_new, out)");
   MUD_REQUIRE(groups == 0 || (y && members && weights && gains), "mud_slab_constrain: null pointer (y, members, weights, gains)");
-  MUD_REQUIRE(groups == 0 || clean || (t && a_tab && s_tab), "mud_slab_constrain: null pointer (t, a_tab, s_tab)");
-  MUD_REQUIRE(groups == 0 || clean || noise || keys, "mud_slab_constrain: without injected noise the draw needs keys");
+  MUD_TRY(keyed_level_operands("mud_slab_constrain", groups != 0, d));
   std::vector<sl_tables> launches;
   std::vector<int> first, count;
   std::vector<uint8_t> owner;
-  const int rc = sl_pack("mud_slab_constrain", members, weights, gains, groups, L, rows, launches, first, count, owner);
-  if (rc != MUD_OK) return rc;
+  MUD_TRY(sl_pack("mud_slab_constrain", members, weights, gains, groups, L, rows, launches, first, count, owner));
   if (out != x_new) {                                   // the rows of no group: copied, bit for bit, run by run
     for (int r = 0; r < rows;) {
       if (owner[r]) {
@@ -200,18 +180,8 @@ extern "C" int mud_slab_constrain(const float* x_new, const float* y, const int3
       r = e;
     }
   }
-  const int64_t bpr = mud_cdiv(row_len, 4);
   const bool vec = row_len % 4 == 0 && mud_aligned16(x_new) && mud_aligned16(out) && mud_aligned16(y) && (!noise || mud_aligned16(noise));
-  const uint64_t word2 = ((uint64_t)step << 8) | (uint64_t)kind;
-  for (size_t i = 0; i < launches.size(); ++i) {
-    const dim3 grid((unsigned)mud_cdiv(bpr, SL_THREADS), (unsigned)count[i]);
-    if (vec)
-      SL_LAUNCH(true, false, x_new, y, launches[i], first[i], noise, keys, seed, word2, t, toff, a_tab, s_tab, ntab, clean, out, row_len, bpr);
-    else
-      SL_LAUNCH(false, false, x_new, y, launches[i], first[i], noise, keys, seed, word2, t, toff, a_tab, s_tab, ntab, clean, out, row_len, bpr);
-    MUD_CHECK_LAUNCH("mud_slab_constrain");
-  }
-  return MUD_OK;
+  return sl_run<false>("mud_slab_constrain", vec, x_new, y, launches, first, count, d, out, row_len, stream);
 }
 
 extern "C" int mud_slab_average(const float* x, const int32_t* members, const float* weights, int groups, int L, float* avg, int rows,
@@ -224,17 +194,8 @@ extern "C" int mud_slab_average(const float* x, const int32_t* members, const fl
   std::vector<sl_tables> launches;
   std::vector<int> first, count;
   std::vector<uint8_t> owner;
-  const int rc = sl_pack("mud_slab_average", members, weights, nullptr, groups, L, rows, launches, first, count, owner);
-  if (rc != MUD_OK) return rc;
-  const int64_t bpr = mud_cdiv(row_len, 4);
+  MUD_TRY(sl_pack("mud_slab_average", members, weights, nullptr, groups, L, rows, launches, first, count, owner));
   const bool vec = row_len % 4 == 0 && mud_aligned16(x) && mud_aligned16(avg);
-  for (size_t i = 0; i < launches.size(); ++i) {
-    const dim3 grid((unsigned)mud_cdiv(bpr, SL_THREADS), (unsigned)count[i]);
-    if (vec)
-      SL_LAUNCH(true, true, x, nullptr, launches[i], first[i], nullptr, nullptr, 0ull, 0ull, nullptr, 0, nullptr, nullptr, 1, 1, avg, row_len, bpr);
-    else
-      SL_LAUNCH(false, true, x, nullptr, launches[i], first[i], nullptr, nullptr, 0ull, 0ull, nullptr, 0, nullptr, nullptr, 1, 1, avg, row_len, bpr);
-    MUD_CHECK_LAUNCH("mud_slab_average");
-  }
-  return MUD_OK;
+  const keyed_level none = {nullptr, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, 1, 1};
+  return sl_run<true>("mud_slab_average", vec, x, nullptr, launches, first, count, none, avg, row_len, stream);
 }

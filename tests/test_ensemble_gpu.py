@@ -82,6 +82,25 @@ def test_keyed_normals_do_not_depend_on_row_order_or_batching():
     assert torch.equal(torch.cat(parts, 0), full)
 
 
+def parent_bit_cases():
+    """(name, output) of ops.randn_keyed over the row lengths and row counts of tests/parent_bits.py, and into an output 4 bytes off a
+    16-byte boundary (row_len 8: the element path although the rows are whole quads)."""
+    import parent_bits as P
+    from mudiff_hip import ops
+    for rows in P.ROWS:
+        keys = torch.stack([torch.arange(rows) * 5 + 2, torch.arange(rows) % 3], 1)
+        for row_len in P.ROW_LENS:
+            yield f'{rows}x{row_len}', ops.randn_keyed(keys, row_len, 1024 + row_len, rows, ops.KIND_Z)
+        out = P.off_by_one_float(torch.zeros(rows, 8, device=DEV))
+        assert out.is_contiguous() and out.data_ptr() % 16 == 4
+        yield f'{rows}x8 unaligned', ops.randn_keyed(keys, 8, 7, 3, ops.KIND_NOISE, out=out)
+
+
+def test_the_bits_are_those_of_the_parent_commit():
+    import parent_bits as P
+    P.check('test_ensemble_gpu', parent_bit_cases())
+
+
 def test_keyed_normals_moments():
     from mudiff_hip import ops
     keys = torch.stack([torch.arange(256) // 4, torch.arange(256) % 4], 1)

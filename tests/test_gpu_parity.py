@@ -80,6 +80,28 @@ def test_posterior_and_q_sample_bit_exact():
         assert torch.equal(out.cpu(), ref)
 
 
+def parent_bit_cases():
+    """(name, output) of ops.posterior_sample (one and two predictions) and ops.q_sample with t at 0, at the table's last entry and out
+    of range on both sides, at a row length that takes the 16-byte path and at one that does not.  The tables are literals and the
+    inputs numpy's: the schedule's own tables go through the host's exp and log, whose last bit is the CPU's."""
+    ops = _imports()[0]
+    c1, c2, sd, a, s = (g(torch.tensor(v, dtype=torch.float32)) for v in ([0.9, 0.5, 0.3, 0.11], [0.05, 0.4, 0.6, 0.85], [0.3, 0.2, 0.1, 0.05],
+                                                                          [0.97, 0.81, 0.5, 0.12], [0.25, 0.59, 0.87, 0.99]))
+    t = torch.tensor([0, 3, -3, 6], device=DEV)
+    for shape in ((1, 8, 8), (1, 7, 9)):
+        gen = np.random.default_rng(shape[1])
+        x01, x02, xt, nz = (g(torch.from_numpy(gen.standard_normal((4,) + shape).astype(np.float32))) for _ in range(4))
+        yield f'posterior {shape}', ops.posterior_sample(x01, None, xt, nz, t, c1, c2, sd)
+        yield f'posterior of two {shape}', ops.posterior_sample(x01, x02, xt, nz, t, c1, c2, sd)
+        for toff in (-1, 0, 1):
+            yield f'q_sample {shape} toff {toff}', ops.q_sample(x01, nz, t, toff, a, s)
+
+
+def test_the_bits_are_those_of_the_parent_commit():
+    import parent_bits as P
+    P.check('test_gpu_parity', parent_bit_cases())
+
+
 def test_embeddings_and_dense():
     ops, *_ = _imports()
     t = torch.tensor([0, 1, 2, 3, 7, 999])

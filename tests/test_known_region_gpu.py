@@ -159,6 +159,46 @@ def test_constrain_refuses_bad_arguments():
         ops.randn_keyed(torch.tensor([[0, 0]]), 8, 1, 0, ops.KIND_KNOWN)
 
 
+def parent_bit_cases():
+    """(name, output) of ops.known_constrain over the shapes and paths of tests/parent_bits.py: every row length and row count with
+    injected noise, the keyed draw and `clean`, out of place and in place, toff -1 / 0 / +1 against levels at both ends of the table;
+    then the unaligned form, no mask, a quad with nothing known beside a mixed one, and `out is known`."""
+    import parent_bits as P
+    from mudiff_hip import ops
+    at, st = (_dev(v) for v in _tables())
+    for rows in P.ROWS:
+        keys = torch.stack([torch.arange(rows) * 3 + 1, torch.arange(rows) % 4], 1)
+        for row_len in P.ROW_LENS:
+            x, k, m, eta, _ = (_dev(v) for v in _case(rows, row_len))
+            draws = dict(noise=dict(noise=eta), keyed=dict(keys=keys, seed=2024, step=3), clean=dict(clean=True))
+            for mode, kw in draws.items():
+                for toff in ((0,) if mode == 'clean' else (-1, 0, 1)):
+                    t = P.level_t(rows, toff).to(DEV)
+                    yield f'{rows}x{row_len} {mode} toff {toff}', ops.known_constrain(x, k, m, t, toff, at, st, **kw)
+                xd = x.clone()
+                yield f'{rows}x{row_len} {mode} in place', ops.known_constrain(xd, k, m, P.level_t(rows, 0).to(DEV), 0, at, st, out=xd, **kw)
+    rows, row_len = 5, 8
+    x, k, m, eta, _ = (_dev(v) for v in _case(rows, row_len))
+    t, keys = P.level_t(rows, 0).to(DEV), torch.stack([torch.arange(rows) + 7, torch.arange(rows) % 2], 1)
+    for mode, kw in dict(noise=dict(noise=eta), keyed=dict(keys=keys, seed=9, step=1), clean=dict(clean=True)).items():
+        ku = P.off_by_one_float(k)
+        assert ku.is_contiguous() and ku.data_ptr() % 16 == 4
+        yield f'unaligned known {mode}', ops.known_constrain(x, ku, m, t, 0, at, st, **kw)
+        yield f'unaligned out {mode}', ops.known_constrain(x, k, m, t, 0, at, st, out=P.off_by_one_float(x), **kw)
+        yield f'no mask {mode}', ops.known_constrain(None, k, None, t, 1, at, st, **kw)
+        quads = m.clone()
+        quads[:, :4] = 0
+        quads[:, 4:] = torch.tensor([1, 0, 0, 1], dtype=torch.uint8)
+        yield f'empty quad {mode}', ops.known_constrain(x, k, quads, t, 0, at, st, **kw)
+        kd = k.clone()
+        yield f'out is known {mode}', ops.known_constrain(x, kd, m, t, 0, at, st, out=kd, **kw)
+
+
+def test_the_bits_are_those_of_the_parent_commit():
+    import parent_bits as P
+    P.check('test_known_region_gpu', parent_bit_cases())
+
+
 # ---------------------------------------------------------------------------------------------------
 SRC, DST = (7, 9, 11), (8, 8, 8)
 DYADIC = {

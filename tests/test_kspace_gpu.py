@@ -217,6 +217,43 @@ def test_clean_step_with_a_hermitian_mask_meets_the_measurements(S):
     assert 0 < int(m.sum()) < m.size
 
 
+def parent_bit_cases():
+    """(name, output) of ops.kspace_constrain and ops.fft2 at S = 16 and 512 (the two ends; 512 runs 8 lines per workgroup), rows 1 and
+    3: a mask shared by the rows and one per row, of zeros and of ones; noise injected at toff -1 / 0 / +1 against levels at both ends
+    of the table, the keyed draw out of place and in place, `clean`; fft2 of a real and a complex input, forward and inverse."""
+    import parent_bits as P
+    from mudiff_hip import ops
+    at, st = (_dev(v) for v in _tables())
+    for S in (16, 512):
+        for rows in (1, 3):
+            x, _, eta, t, masks, ys = _con_case(S, rows)
+            x, eta, t = _dev(x), _dev(eta), _dev(t)
+            keys = torch.stack([torch.arange(rows) + 11, torch.arange(rows) % 2], 1)
+            for mr in sorted(masks):
+                m, y = _dev(masks[mr]), _dev(ys[mr])
+                tag = f'S{S} rows {rows} mask {mr}'
+                for toff in (-1, 0, 1):
+                    yield f'{tag} noise toff {toff}', ops.kspace_constrain(x, y, m, P.level_t(rows, toff).to(DEV), toff, at, st, noise=eta)
+                yield f'{tag} keyed', ops.kspace_constrain(x, y, m, t, 0, at, st, keys=keys, seed=2024, step=3)
+                xd = x.clone()
+                yield f'{tag} keyed in place', ops.kspace_constrain(xd, y, m, t, 0, at, st, keys=keys, seed=2024, step=3, out=xd)
+                yield f'{tag} clean', ops.kspace_constrain(x, y, m, None, 0, None, None, clean=True)
+            y = _dev(ys[rows])
+            for name, fill in (('zeros', 0), ('ones', 1)):
+                m = torch.full((1, S, S), fill, device=DEV, dtype=torch.uint8)
+                yield f'S{S} rows {rows} mask of {name} noise', ops.kspace_constrain(x, y, m, t, 0, at, st, noise=eta)
+                yield f'S{S} rows {rows} mask of {name} clean', ops.kspace_constrain(x, y, m, None, 0, None, None, clean=True)
+            z = _dev(_fft_case(S, rows)[0])
+            for inverse in (False, True):
+                yield f'S{S} rows {rows} fft2 complex inverse {inverse}', ops.fft2(z, inverse=inverse)
+                yield f'S{S} rows {rows} fft2 real inverse {inverse}', ops.fft2(x, inverse=inverse)
+
+
+def test_the_bits_are_those_of_the_parent_commit():
+    import parent_bits as P
+    P.check('test_kspace_gpu', parent_bit_cases())
+
+
 def test_bad_arguments_are_refused_before_a_launch():
     import mudiff_hip
     from mudiff_hip import MudiffHipError, ops

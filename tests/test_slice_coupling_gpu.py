@@ -81,6 +81,27 @@ def test_coupled_normals_do_not_depend_on_row_order_or_batching():
     assert torch.equal(torch.cat(parts, 0), full)
 
 
+def parent_bit_cases():
+    """(name, output) of ops.randn_keyed_coupled at radius 0, 3 and 32 over the row lengths and row counts of tests/parent_bits.py, and
+    into an output 4 bytes off a 16-byte boundary (row_len 8: the element path although the rows are whole quads)."""
+    import parent_bits as P
+    from mudiff_hip import ops
+    for radius in (0, 3, 32):
+        half = _half(radius)
+        for rows in P.ROWS:
+            keys = torch.stack([torch.arange(rows) * 5, torch.arange(rows) % 3], 1)         # slice 0: taps below it wrap
+            for row_len in P.ROW_LENS:
+                yield f'R{radius} {rows}x{row_len}', ops.randn_keyed_coupled(keys, row_len, 77 + row_len, rows, ops.KIND_NOISE, half, radius)
+            out = P.off_by_one_float(torch.zeros(rows, 8, device=DEV))
+            assert out.is_contiguous() and out.data_ptr() % 16 == 4
+            yield f'R{radius} {rows}x8 unaligned', ops.randn_keyed_coupled(keys, 8, 7, 3, ops.KIND_Z, half, radius, out=out)
+
+
+def test_the_bits_are_those_of_the_parent_commit():
+    import parent_bits as P
+    P.check('test_slice_coupling_gpu', parent_bit_cases())
+
+
 def test_coupled_normals_moments_on_the_device():
     """64 consecutive slices x 65536 elements at sigma = 2 (R = 6): every row's mean within 6 / sqrt(L), its variance within
     6 sqrt(2 / L), and every pair's lag-d correlation within 6 / sqrt(L) of coupling_correlation, d = 1..2R + 2."""

@@ -204,6 +204,54 @@ def test_many_groups_take_more_than_one_launch():
     assert (np.abs(avg.cpu().numpy().astype(np.float64) - R.average(x, members, w)) <= (L + 4) * R.EPS * R.average(np.abs(x), members, w)).all()
 
 
+def parent_bit_cases():
+    """(name, output) of ops.slab_constrain and ops.slab_average over the row lengths of tests/parent_bits.py and L = 1, 5, 16 with three
+    interleaved groups (free rows with a -0, an unused tail for L > 1): injected noise at toff -1 / 0 / +1 against first-member levels
+    at both ends of the table, the keyed draw out of place and in place, `clean`, an operand 4 bytes off a 16-byte boundary; then one row
+    alone, 33 groups of one member in 37 rows (two launches) and 9 groups of 16 (144 slots: the launch splits on slots)."""
+    import parent_bits as P
+    from mudiff_hip import ops
+    at, st = (_dev(v) for v in _tables())
+    for row_len in P.ROW_LENS:
+        for L in (1, 5, 16):
+            c = _case(row_len, L, 3)
+            x, y, eta, keys = (_dev(c[n]) for n in ('x', 'y', 'eta', 'keys'))
+            tab = dict(gains=c['g'])
+            for toff in (-1, 0, 1):
+                t = torch.full((c['rows'],), 2)
+                t[c['members'][0][0]], t[c['members'][1][0]] = 0, NTAB - 1
+                yield f'{row_len} L{L} noise toff {toff}', ops.slab_constrain(x, y, c['members'], c['w'], t.to(DEV), toff, at, st, noise=eta, **tab)
+            t = _dev(c['t'])
+            yield f'{row_len} L{L} keyed', ops.slab_constrain(x, y, c['members'], c['w'], t, 0, at, st, keys=keys, seed=SEED, step=7, **tab)
+            xd = x.clone()
+            yield f'{row_len} L{L} keyed in place', ops.slab_constrain(xd, y, c['members'], c['w'], t, 0, at, st, keys=keys, seed=SEED, step=7, out=xd, **tab)
+            yield f'{row_len} L{L} clean', ops.slab_constrain(x, y, c['members'], c['w'], None, 0, None, None, clean=True, **tab)
+            yield f'{row_len} L{L} average', ops.slab_average(x, c['members'], c['w'])
+    c = _case(8, 5, 3)
+    x, y, eta, t = P.off_by_one_float(_dev(c['x'])), _dev(c['y']), _dev(c['eta']), _dev(c['t'])
+    assert x.is_contiguous() and x.data_ptr() % 16 == 4
+    yield 'unaligned noise', ops.slab_constrain(x, y, c['members'], c['w'], t, 0, at, st, noise=eta, gains=c['g'])
+    yield 'unaligned keyed', ops.slab_constrain(x, y, c['members'], c['w'], t, 0, at, st, keys=_dev(c['keys']), seed=SEED, step=7, gains=c['g'])
+    yield 'unaligned average', ops.slab_average(x, c['members'], c['w'])
+    g = np.random.default_rng(5)
+    for name, rows, members in (('one row', 1, [[0]]), ('33 groups', 37, [[r] for r in range(36, 3, -1)]),
+                                ('144 slots', 144, g.permutation(144).reshape(9, 16))):
+        members = np.array(members, np.int32)
+        w = R.profile(members.shape[1], 'gauss').astype(np.float32)
+        x, eta = (_dev(g.standard_normal((rows, 33)).astype(np.float32)) for _ in range(2))
+        y = _dev(g.standard_normal((len(members), 33)).astype(np.float32))
+        t, keys = P.level_t(rows, 0).to(DEV), torch.stack([torch.arange(rows) + 2, torch.arange(rows) % 3], 1)
+        yield f'{name} noise', ops.slab_constrain(x, y, members, w, t, 0, at, st, noise=eta)
+        yield f'{name} keyed', ops.slab_constrain(x, y, members, w, t, 0, at, st, keys=keys, seed=SEED, step=1)
+        yield f'{name} clean', ops.slab_constrain(x, y, members, w, None, 0, None, None, clean=True)
+        yield f'{name} average', ops.slab_average(x, members, w)
+
+
+def test_the_bits_are_those_of_the_parent_commit():
+    import parent_bits as P
+    P.check('test_thick_gpu', parent_bit_cases())
+
+
 def test_bad_arguments_are_refused_before_a_launch():
     import mudiff_hip
     from mudiff_hip import MudiffHipError, ops
