@@ -342,8 +342,9 @@ int mud_lpips_u8(const uint8_t* pred, const uint8_t* gt, int n, int H, int W, co
  * Philox4x64-10 (numpy.random.Philox's algorithm and word order) with key (seed, 0x4D55444946460001) and counter
  * (e/4, s, (j << 32) | (step << 8) | kind, 0); lane l = e % 4 takes the word pair (w[2(l/2)], w[2(l/2)+1]) = (wa, wb),
  * u1 = ((wa >> 11) + 1) 2^-53, u2 = (wb >> 11) 2^-53, r = sqrt(-2 log u1), theta = 2 pi u2: r cos theta (even l), r sin theta (odd l),
- * in fp64, rounded once to fp32.  kind: 0 x_init, 1 z, 2 posterior noise, or 5 / 6: the draws of mud_kspace_constrain /
- * mud_slab_constrain, so that a caller can inject what those entries draw (3 and 4, mud_known_constrain's, stay refused); step in
+ * in fp64, rounded once to fp32.  kind: 0 x_init, 1 z, 2 posterior noise, or 5 / 6 / 7: the draws of mud_kspace_constrain /
+ * mud_slab_constrain / mud_slab_kspace_constrain, so that a caller can inject what those entries draw (3 and 4, mud_known_constrain's,
+ * stay refused); step in
  * [0, 2^24); row_len > 0.
  * mud_ensemble_stats: samples [n][N][hw] -> mean, std [n][hw] (N >= 2, hw > 0): y = clamp(x*scale + shift, lo, hi) in fp32 (each step
  * rounded once, NaN kept), m = (sum_j y_j) / N and v = sum_j (y_j - m)^2 / (N - 1) in fp64 in sample order j = 0..N-1,
@@ -481,6 +482,31 @@ int mud_slab_constrain(const float* x_new, const float* y, const int32_t* member
                        const float* a_tab, const float* s_tab, int ntab, int clean, float* out, int rows, int64_t row_len, void* stream);
 int mud_slab_average(const float* x, const int32_t* members, const float* weights, int groups, int L, float* avg, int rows, int64_t row_len,
                      void* stream);
+
+/* ---- sampling a target acquired as accelerated thick slices (mudiff_hip.multislice; GraphSampler.sample_keyed(constraint=
+ *      SlabKSpaceRows)).  The composite of the two models above: a group (a slab) of up to L rows with weights w_l
+ * and gains g_l = w_l / sum_m w_m^2 (the tables of mud_slab_constrain), whose average was measured in k-space on a mask:
+ * y[g] = mask .* F(sum_l w_l k_l).  A A^H = (sum w^2) mask, so the step is still an exact projection.
+ * mud_slab_kspace_constrain: with c = clamp(t[first member of g] + toff, 0, ntab - 1), for every group g
+ *   d = sum_l w_l (x_new[m_l] - s_tab[c] * eta[m_l])                                  (clean != 0:  d = sum_l w_l x_new[m_l])
+ *   C = Re F^H[ mask ? F(d) - a_tab[c] * y[g] : 0 ]                                   (clean != 0:  ... - y[g])
+ *   out[m_l] = x_new[m_l] - g_l * C                                                   for every member l,
+ * in fp32, every product and sum rounded once (no contraction), the sum over l from 0 in the table's order whatever the rows'
+ * positions, the transforms those of mud_kspace_constrain: a group's result depends on its own rows, table and keys alone, and with
+ * L = 1, w = g = 1 it has mud_kspace_constrain's bits.  A correction g_l * C that compares equal to 0 leaves x_new's bits (an all-zero
+ * mask returns x_new bit for bit), and a row of no group is copied bit for bit (nothing when out is x_new, which is allowed).
+ * y: complex [groups][S][S]; mask: uint8 [mask_rows][S][S], mask_rows 1 (shared) or groups; work: a complex workspace [groups][S][S]
+ * of the caller's, overwritten.  eta is `noise` [rows][S][S] when given, else the value mud_randn_keyed gives element e of a row keyed
+ * keys[2r..2r+1] under (seed, step, kind), drawn by the thread that loads elements 4b..4b+3 of that row; kind in [0, 15]
+ * (mudiff_hip.ops.KIND_MULTISLICE = 7 is this entry's), step in [0, 2^24).  Three launches per 32 groups or 128 members: rows forward
+ * (the members' sum fused into the load), mud_kspace_constrain's column pass by group, rows inverse (the members' correction fused
+ * into the store).  No atomics, no allocation on the device.
+ * MUD_ERR_ARG before any launch or copy for every refusal of mud_kspace_constrain (S, rows * S * S, alignment, work, kind, step, null
+ * pointers, neither noise nor keys; mask_rows outside {1, groups}) and of mud_slab_constrain (members, weights, gains, L, groups). */
+int mud_slab_kspace_constrain(const float* x_new, const float* y, const uint8_t* mask, int mask_rows, const int32_t* members,
+                              const float* weights, const float* gains, int groups, int L, const float* noise, const int64_t* keys,
+                              uint64_t seed, int step, int kind, const int64_t* t, int toff, const float* a_tab, const float* s_tab,
+                              int ntab, int clean, float* out, float* work, int rows, int S, void* stream);
 
 /* ---- through-plane roughness of a volume (mudiff_hip.volume_through_plane; the volume pipeline's --through_plane).
  * vol (fp32) and the optional mask (uint8, may be NULL: every voxel is inside; else non-zero is inside) are [Z, X, Y] with planes

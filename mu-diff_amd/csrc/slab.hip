@@ -6,21 +6,10 @@
 // This is the first constraint that couples the rows of a batch.  The sum over a group's members runs in the table's order whatever the
 // rows' positions, one thread owns 4 consecutive elements of one group (all its members), and the draw is keyed (keyed_normal.h): a
 // group's result is a function of its own rows, its table and its keys alone.  No LDS, no atomics, no contraction.
-#include <vector>
 #include "keyed_rows.h"
+#include "slab_tables.h"          // sl_tables, sl_pack, sl_copy_free_rows: shared with slab_kspace.hip
 
 #define SL_THREADS 256
-#define SL_GROUPS 32             // groups per launch
-#define SL_SLOTS 128             // member slots per launch (>= MUD_SLAB_MAX_MEMBERS): 32 rows of L = 5 or 16 are one launch
-
-// the tables of one launch, passed by value like es_taps: the unused tails (-1) are squeezed out, the order is the table's
-struct sl_tables {
-  int start[SL_GROUPS + 1];      // group q of the launch owns slots start[q] .. start[q + 1] - 1
-  int member[SL_SLOTS];          // row index
-  float w[SL_SLOTS];
-  float g[SL_SLOTS];
-};
-
 // grid (blocks over the row's quads, groups of this launch).  AVERAGE: out = avg [groups][row_len], nothing else is written.  Else out may
 // alias x_new: a thread reads its 4 elements of a member row before it writes them, and no other thread touches them (a row is in one
 // group once: validated on the host).  VEC: row_len % 4 == 0 and every pointer 16-byte aligned; else element by element, the last quad cut.
@@ -87,52 +76,6 @@ __global__ __launch_bounds__(SL_THREADS) void k_slab(const float* x_new, const f
   }
 }
 
-// members / weights / gains [groups][L] -> the launches' tables; every refusal before any launch.  owner[r] = 1 for a row in a group.
-static int sl_pack(const char* who, const int32_t* members, const float* weights, const float* gains, int groups, int L, int rows,
-                   std::vector<sl_tables>& launches, std::vector<int>& first_group, std::vector<int>& n_groups, std::vector<uint8_t>& owner) {
-  owner.assign((size_t)rows, 0);
-  sl_tables cur = {};
-  int ng = 0, ns = 0;
-  for (int g = 0; g < groups; ++g) {
-    int cnt = 0;
-    for (int l = 0; l < L; ++l) cnt += members[(size_t)g * L + l] >= 0 ? 1 : 0;
-    MUD_REQUIRE(cnt > 0, "%s: members: group %d has no member", who, g);
-    if (ng == SL_GROUPS || ns + cnt > SL_SLOTS) {
-      cur.start[ng] = ns;
-      launches.push_back(cur);
-      n_groups.push_back(ng);
-      ng = ns = 0;
-    }
-    if (ng == 0) first_group.push_back(g);
-    cur.start[ng] = ns;
-    for (int l = 0; l < L; ++l) {
-      const int32_t m = members[(size_t)g * L + l];
-      if (m == -1) continue;
-      MUD_REQUIRE(m >= 0 && m < rows, "%s: members: group %d names row %d outside [0, %d)", who, g, (int)m, rows);
-      MUD_REQUIRE(!owner[m], "%s: members: row %d is named twice", who, (int)m);
-      owner[m] = 1;
-      const float w = weights[(size_t)g * L + l];
-      MUD_REQUIRE(w > 0.f && w - w == 0.f, "%s: weights: group %d, member %d is not a finite positive number", who, g, l);
-      cur.member[ns] = m;
-      cur.w[ns] = w;
-      cur.g[ns] = 0.f;
-      if (gains) {
-        const float gn = gains[(size_t)g * L + l];
-        MUD_REQUIRE(gn > 0.f && gn - gn == 0.f, "%s: gains: group %d, member %d is not a finite positive number", who, g, l);
-        cur.g[ns] = gn;
-      }
-      ++ns;
-    }
-    ++ng;
-  }
-  if (ng) {
-    cur.start[ng] = ns;
-    launches.push_back(cur);
-    n_groups.push_back(ng);
-  }
-  return MUD_OK;
-}
-
 // the launches of one call
 template <bool AVERAGE>
 static int sl_run(const char* who, bool vec, const float* x, const float* y, const std::vector<sl_tables>& launches, const std::vector<int>& first_group,
@@ -164,22 +107,7 @@ extern "C" int mud_slab_constrain(const float* x_new, const float* y, const int3
   std::vector<int> first, count;
   std::vector<uint8_t> owner;
   MUD_TRY(sl_pack("mud_slab_constrain", members, weights, gains, groups, L, rows, launches, first, count, owner));
-  if (out != x_new) {                                   // the rows of no group: copied, bit for bit, run by run
-    for (int r = 0; r < rows;) {
-      if (owner[r]) {
-        ++r;
-        continue;
-      }
-      int e = r;
-      while (e < rows && !owner[e]) ++e;
-      if (hipMemcpyAsync(out + (int64_t)r * row_len, x_new + (int64_t)r * row_len, (size_t)(e - r) * row_len * sizeof(float), hipMemcpyDeviceToDevice,
-                         (hipStream_t)stream) != hipSuccess) {
-        mud_set_error("mud_slab_constrain: copying the free rows failed");
-        return MUD_ERR_LAUNCH;
-      }
-      r = e;
-    }
-  }
+  if (out != x_new) MUD_TRY(sl_copy_free_rows("mud_slab_constrain", x_new, out, owner, rows, row_len, stream));
   const bool vec = row_len % 4 == 0 && mud_aligned16(x_new) && mud_aligned16(out) && mud_aligned16(y) && (!noise || mud_aligned16(noise));
   return sl_run<false>("mud_slab_constrain", vec, x_new, y, launches, first, count, d, out, row_len, stream);
 }

@@ -151,6 +151,8 @@ _SIGNATURES = {
     'mud_kspace_constrain': (_I, [_P, _P, _P, _I, _P, _P, C.c_uint64, _I, _I, _P, _I, _P, _P, _I, _I, _P, _P, _I, _I, _P]),
     'mud_slab_constrain': (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, C.c_uint64, _I, _I, _P, _I, _P, _P, _I, _I, _P, _I, _L, _P]),
     'mud_slab_average': (_I, [_P, _P, _P, _I, _I, _P, _I, _L, _P]),
+    'mud_slab_kspace_constrain': (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _P, _P, C.c_uint64, _I, _I, _P, _I, _P, _P, _I, _I, _P, _P, _I, _I,
+                                        _P]),
     'mud_volume_through_plane': (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _L, _P]),
     'mud_volume_census_ws_bytes': (_L, []),
     'mud_volume_census': (_I, [_P, _I, _I, _I, _I, _F, _F, C.POINTER(C.c_double), _I, _P, _P, _L, _P]),

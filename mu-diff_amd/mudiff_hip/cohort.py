@@ -29,9 +29,10 @@ too (volume_prepare.evaluation_inputs); the prefetch thread only reads them (vol
 thread, the compression and the write on the pool.  A subject whose manifest row has a `known` (and `known_mask`) cell is sampled with
 that subject's --known_volume / --known_mask (mudiff_hip.known_region; --known_drop_slices and --known_resample
 come from the command line): known_<t>.json goes next to its prediction and the regions known / synthesised join the aggregate.  Under
---known_kspace or --known_thick (and the --kspace_* / --thick_* flags, all from the command line) that `known` volume was acquired
-undersampled in k-space or with thick slices instead (mudiff_hip.kspace, mudiff_hip.thick; DESIGN.md sections 5.26, 5.27):
-kspace_<t>.json or thick_<t>.json goes next to the prediction, and a `known_mask` cell fails that subject.
+--known_kspace, --known_thick or --known_multislice (and the --kspace_* / --thick_* / --multislice_* flags, all from the command line)
+that `known` volume was acquired undersampled in k-space, with thick slices or both instead (mudiff_hip.kspace, mudiff_hip.thick,
+mudiff_hip.multislice; DESIGN.md sections 5.26 - 5.28): kspace_<t>.json, thick_<t>.json or multislice_<t>.json goes next to the
+prediction, and a `known_mask` cell fails that subject.
 """
 from __future__ import annotations
 
@@ -257,7 +258,8 @@ def run(args, subjects, predict=None):
                     if subject.known:                              # (the subject's --known_volume: mudiff_hip.known_region)
                         from . import known_region as KR
                         sargs.known_volume, sargs.known_mask = subject.known, subject.known_mask
-                        known = [module.options_from(sargs) for module in V.known_modes()][0]      # (each mode's own refusals)
+                        known = {module: module.options_from(sargs) for module in V.known_modes()}[KR]      # (each mode's own refusals;
+                                                                                                            #  K's options: known_region's)
                         sargs.known_inputs = KR.on_grid(raws[0], KR.read_inputs(known, options), known, options, gpu, align=found.get('align'))
                         report.add_evaluation(list(sargs.known_inputs.resampled), {})
                     sargs.intake_report = report                   # (the [done] line names what it lists)

@@ -1,10 +1,12 @@
-"""What the three ways of sampling a partly acquired target share (--known_volume, --known_kspace, --known_thick; DESIGN.md section
-5.24a): after every reverse step the result is projected onto what was measured, at that step's noise level, with a keyed draw.
+"""What the four ways of sampling a partly acquired target share (--known_volume, --known_kspace, --known_thick, --known_multislice;
+DESIGN.md section 5.24a): after every reverse step the result is projected onto what was measured, at that step's noise level, with a
+keyed draw.
 
-A *prediction-level* constraint (Constraint: KnownVoxels here, kspace.KSpaceMeasurement, thick.ThickMeasurement) describes the n slices
-one prediction samples; volume.predict_slices and ensemble.sample_ensemble form their batches from it and know nothing else of it.
-Its for_rows gives the *batch-level* constraint of one captured batch (KnownRows, KSpaceRows, SlabRows): `check(sampler)`, once, and
-`apply(sampler, x_new, keys_dev, seed, step, clean)`, one unchecked launch into sampler.x per executed step, for GraphSampler.sample_keyed."""
+A *prediction-level* constraint (Constraint: KnownVoxels here, kspace.KSpaceMeasurement, thick.ThickMeasurement,
+multislice.MultisliceMeasurement) describes the n slices one prediction samples; volume.predict_slices and ensemble.sample_ensemble form
+their batches from it and know nothing else of it.  Its for_rows gives the *batch-level* constraint of one captured batch (KnownRows,
+KSpaceRows, SlabRows, SlabKSpaceRows): `check(sampler)`, once, and `apply(sampler, x_new, keys_dev, seed, step, clean)`, one unchecked
+launch into sampler.x per executed step, for GraphSampler.sample_keyed."""
 from __future__ import annotations
 
 import collections
@@ -152,6 +154,35 @@ class SlabRows(collections.namedtuple('SlabRows', 'thick gids')):
     def apply(self, sampler, x_new, keys_dev, seed, step, clean):
         dc = sampler._diffusion_tables()
         ops.slab_constrain_into(sampler.x, x_new, *self.dev, keys_dev, seed, step, ops.KIND_THICK, sampler.t, 0, dc[0], dc[1], clean=clean)
+        sampler.thick_x_new = x_new          # what the last constraint was given (the graph's own buffer, until the next replay)
+
+
+class SlabKSpaceRows(collections.namedtuple('SlabKSpaceRows', 'multislice gids', defaults=(None,))):
+    """The batch-level constraint of accelerated thick slices, for GraphSampler.sample_keyed(constraint=):
+    `multislice` = (y complex64 [groups,S,S], mask uint8 [1 or groups,S,S], members, weights, gains), the tables as SlabRows', and `gids`:
+    the measured slab of each group (multislice.MultisliceMeasurement.for_rows; None from a caller's own tuple)."""
+
+    def check(self, sampler):
+        B, H, W = sampler.B, sampler.H, sampler.W
+        if H != W or not ops.kspace_size_ok(H):
+            raise ValueError(f'GraphSampler.sample_keyed: multislice needs a square grid whose size is a power of two in [16, 512], got {H} x {W}')
+        y, mask, members, weights, gains = self.multislice
+        tab = ops.slab_tables(members, weights, gains)
+        want, top = (tab[0].shape[0], H, W), int(tab[0].max(initial=-1))
+        if y.dtype != torch.complex64 or tuple(y.shape) != want or mask.dtype != torch.uint8 or tuple(mask.shape) not in (want, (1,) + want[1:]):
+            raise ValueError(f'GraphSampler.sample_keyed: multislice = (y complex64 {want}, mask uint8 [1 or {want[0]}, {H}, {W}], ...), got '
+                             f'{y.dtype} {tuple(y.shape)} and {mask.dtype} {tuple(mask.shape)}')
+        if want[0] > B or tab[0].shape[1] > ops.SLAB_MAX_MEMBERS or top >= B:
+            raise ValueError(f'GraphSampler.sample_keyed: multislice names {want[0]} groups of {tab[0].shape[1]} rows up to row {top} for a '
+                             f'batch of {B} (at most {ops.SLAB_MAX_MEMBERS} rows a group)')
+        self.dev = y.to(sampler.x.device).contiguous(), mask.to(sampler.x.device).contiguous(), tab
+        if getattr(sampler, '_ks_work', None) is None:          # the complex workspace: one per sampler, KSpaceRows' (groups <= B)
+            sampler._ks_work = torch.empty((B, H, W), device=sampler.x.device, dtype=torch.complex64)
+
+    def apply(self, sampler, x_new, keys_dev, seed, step, clean):
+        dc = sampler._diffusion_tables()
+        ops.slab_kspace_constrain_into(sampler.x, x_new, *self.dev, sampler._ks_work, keys_dev, seed, step, ops.KIND_MULTISLICE, sampler.t, 0,
+                                       dc[0], dc[1], clean=clean)
         sampler.thick_x_new = x_new          # what the last constraint was given (the graph's own buffer, until the next replay)
 
 

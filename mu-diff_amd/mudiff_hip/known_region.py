@@ -206,11 +206,12 @@ def sampler_inputs(region, s0, s1, size, device):
 
 
 def constraint_for(region, s0, s1, size, args, device):
-    """What the samplers take for the run's K (mudiff_hip.constraints): under --known_thick or --known_kspace K is measured that way
-    instead (thick.measure, kspace.measure), else its known voxels themselves (constraints.KnownVoxels of sampler_inputs)."""
-    from . import kspace, thick
+    """What the samplers take for the run's K (mudiff_hip.constraints): under --known_thick, --known_kspace or --known_multislice K is
+    measured that way instead (thick.measure, kspace.measure, multislice.measure), else its known voxels themselves
+    (constraints.KnownVoxels of sampler_inputs)."""
+    from . import kspace, multislice, thick
     from .constraints import KnownVoxels
-    for module, more in ((thick, ()), (kspace, (args.seed,))):
+    for module, more in ((thick, ()), (kspace, (args.seed,)), (multislice, (args.seed,))):
         options = module.options_from(args)
         if options is not None:
             return module.measure(region, s0, s1, size, options, *more, device)

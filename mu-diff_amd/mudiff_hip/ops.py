@@ -941,8 +941,8 @@ def randn_keyed(rows_keys, row_len, seed, step, kind, out=None):
     """Keyed standard normals: row r of the fp32 result [rows, row_len] is a pure function of (seed, slice, sample, step, kind) with
     rows_keys[r] = (slice, sample) (int64 [rows, 2], host or device): Philox4x64-10 + Box-Muller in fp64 (mud_randn_keyed).  `out`:
     a contiguous fp32 device tensor of rows * row_len elements to fill (any shape); without it the result lands on rows_keys's device
-    (or the current one for host keys).  kind: KIND_X_INIT, KIND_Z or KIND_NOISE (or KIND_KSPACE / KIND_THICK, to inject what
-    ops.kspace_constrain / ops.slab_constrain draw)."""
+    (or the current one for host keys).  kind: KIND_X_INIT, KIND_Z or KIND_NOISE (or KIND_KSPACE / KIND_THICK / KIND_MULTISLICE, to
+    inject what ops.kspace_constrain / ops.slab_constrain / ops.slab_kspace_constrain draw)."""
     k = check_keys(rows_keys)
     seed = _seed64(seed)
     rows, row_len = k.shape[0], int(row_len)
@@ -1005,7 +1005,7 @@ KIND_KNOWN, KIND_RENOISE = 3, 4      # the draws of mud_known_constrain: the kno
 
 
 def _level_and_keys(name, clean, t, a_tab, s_tab, noise, keys, rows, device):
-    """What the checked wrappers of the three constraints share -> (t, a_tab, s_tab, the keys on `device` or None): without `clean`, t
+    """What the checked wrappers of the four constraints share -> (t, a_tab, s_tab, the keys on `device` or None): without `clean`, t
     (int64 [rows]) and two fp32 tables of one length, contiguous, and then either `noise` or keys for every row (check_keys)."""
     if clean:
         return t, a_tab, s_tab, None
@@ -1255,6 +1255,70 @@ def slab_average(x, members, weights, out=None):
     _launch('slab_average', x.device, load().mud_slab_average, ptr(x), _host(m), _host(w), groups, L, ptr(out), int(x.shape[0]), row_len, STREAM,
             nbytes=float(row_len * 4 * (int((m >= 0).sum()) + groups)))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# sampling a target acquired as accelerated thick slices (csrc/slab_kspace.hip, mudiff_hip.multislice)
+KIND_MULTISLICE = 7                  # the draw of mud_slab_kspace_constrain: the slab averages' measured coefficients' forward noise
+
+
+def slab_kspace_constrain_into(out, x_new, y, mask, tables, work, keys_dev, seed, step, kind, t, toff, a_tab, s_tab, clean=False, noise=None):
+    """Unchecked launch of mud_slab_kspace_constrain into `out` (fp32, contiguous, [rows, ..., S, S]; may be x_new): GraphSampler.
+    sample_keyed checks its operands once per batch, not once per step.  y, work: complex64 [groups, S, S]; mask: uint8 [1 or groups, S, S];
+    tables: slab_tables'; keys_dev: through check_keys and on out's device (None with `noise` or `clean`)."""
+    rows, S = out.shape[0], out.shape[-1]
+    m, w, g = tables
+    groups, L = m.shape
+    _launch('slab_kspace_constrain', out.device, load().mud_slab_kspace_constrain, ptr(x_new), ptr(y), ptr(mask), int(mask.shape[0]), _host(m), _host(w),
+            _host(g), groups, L, ptr(noise), ptr(keys_dev), C.c_uint64(seed), int(step), int(kind), ptr(t), int(toff), ptr(a_tab), ptr(s_tab),
+            1 if a_tab is None else a_tab.numel(), int(bool(clean)), ptr(out), ptr(work), rows, S, STREAM,
+            nbytes=float(S * S * (12 * int((m >= 0).sum()) + 41 * groups)))
+    return out
+
+
+def slab_kspace_constrain(x_new, y, mask, members, weights, t, toff, a_tab, s_tab, *, gains=None, noise=None, keys=None, seed=0, step=0,
+                          kind=KIND_MULTISLICE, clean=False, out=None, work=None):
+    """The data-consistency step of accelerated thick-slice measurements (mud_slab_kspace_constrain).  Group j names the rows members[j]
+    (its thin slices, -1 = unused) with weights w and gains g (slab_tables); with c = clamp(t[first member] + toff, 0, len(a_tab) - 1)
+        d = sum_l w_l (x_new[m_l] - s_tab[c] * eta[m_l])                         (clean: d = sum_l w_l x_new[m_l])
+        out[m_l] = x_new[m_l] - g_l * Re F^H[ mask ? F(d) - a_tab[c] * y[j] : 0 ]     (clean: ... - y[j]),
+    summed in the table's order (F: ops.fft2), so that the measured coefficients of the slab average of the result are those of
+    q_sample(k, c) for y = mask * F(sum_l w_l k_l); the other coefficients and everything orthogonal to the profile are untouched.  A row
+    of no group is copied bit for bit.  x_new: fp32 [rows, S, S] or [rows, 1, S, S]; y: complex64 [groups, S, S]; mask: uint8
+    [1 or groups, S, S], non-zero = measured (pass a Hermitian-symmetric one).  eta: `noise` (fp32, x_new's shape) when given, else the keyed
+    normal ops.randn_keyed gives keys[r] = (slice, sample) under (seed, step, kind), drawn in the kernel.  t: int64 [rows]; with `clean`
+    it, the tables and the draw are not needed.  out: None (a new tensor), x_new (in place) or a contiguous fp32 tensor of the shape.
+    work: None or a contiguous complex64 [groups, S, S] workspace (overwritten)."""
+    require_gpu(x_new, y, mask, noise, t, a_tab, s_tab, out, work)
+    if x_new.dtype != torch.float32 or x_new.dim() not in (3, 4) or x_new.shape[0] < 1 or x_new.shape[-1] != x_new.shape[-2] or \
+            (x_new.dim() == 4 and x_new.shape[1] != 1):
+        raise MudiffHipError(f'slab_kspace_constrain: x_new must be fp32 [rows, S, S] or [rows, 1, S, S], got {x_new.dtype} {tuple(x_new.shape)}')
+    rows, S = int(x_new.shape[0]), int(x_new.shape[-1])
+    if not kspace_size_ok(S):
+        raise MudiffHipError(f'slab_kspace_constrain: S must be a power of two in [16, 512], got {S}')
+    tables = slab_tables(members, weights, gains)
+    groups = tables[0].shape[0]
+    if y is None or y.dtype != torch.complex64 or tuple(y.shape) != (groups, S, S):
+        raise MudiffHipError(f'slab_kspace_constrain: y must be complex64 {(groups, S, S)}, got '
+                             f'{None if y is None else (y.dtype, tuple(y.shape))}')
+    if mask is None or mask.dtype != torch.uint8 or mask.dim() != 3 or mask.shape[0] not in (1, groups) or tuple(mask.shape[1:]) != (S, S):
+        raise MudiffHipError(f'slab_kspace_constrain: mask must be uint8 [1 or {groups}, {S}, {S}], got '
+                             f'{None if mask is None else (mask.dtype, tuple(mask.shape))}')
+    for name, v in (('noise', noise), ('out', out)):
+        if v is not None and (v.dtype != torch.float32 or v.shape != x_new.shape):
+            raise MudiffHipError(f'slab_kspace_constrain: {name} must be fp32 of shape {tuple(x_new.shape)}, got {v.dtype} {tuple(v.shape)}')
+    if out is not None and not out.is_contiguous():
+        raise MudiffHipError('slab_kspace_constrain: out must be contiguous')
+    if work is not None and (work.dtype != torch.complex64 or tuple(work.shape) != (groups, S, S) or not work.is_contiguous()):
+        raise MudiffHipError(f'slab_kspace_constrain: work must be a contiguous complex64 {(groups, S, S)}, got {work.dtype} '
+                             f'{tuple(work.shape)}')
+    x_new = x_new if x_new.is_contiguous() or out is x_new else x_new.contiguous()
+    y, mask = y.contiguous(), mask.contiguous()
+    noise = None if noise is None else noise.contiguous()
+    t, a_tab, s_tab, kd = _level_and_keys('slab_kspace_constrain', clean, t, a_tab, s_tab, noise, keys, rows, x_new.device)
+    out = torch.empty(x_new.shape, device=x_new.device, dtype=torch.float32) if out is None else out
+    work = torch.empty(groups, S, S, device=x_new.device, dtype=torch.complex64) if work is None else work
+    return slab_kspace_constrain_into(out, x_new, y, mask, tables, work, kd, _seed64(seed), step, kind, t, toff, a_tab, s_tab, clean, noise)
 
 
 # columns of volume_through_plane's sums (include/mudiff_hip.h: MUD_TP_*)

@@ -32,8 +32,8 @@ z through (slab centre, y_j) over the measured slabs, constant beyond the first 
 
 Scope: the retrospective model with non-overlapping profiles, K given on (or resampled onto) the thin grid and measured here - the
 protocol section 5.26 uses for k-space.  A NIfTI that is itself thick (its own slice spacing, slabs that cut thin slices in fractions,
-overlapping profiles: a banded A A^T) is out of scope, and so is in-plane undersampling combined with thick slices.  A later intake
-only has to fill the same ThickMeasurement.
+overlapping profiles: a banded A A^T) is out of scope.  Thick slices that are also undersampled in-plane are --known_multislice's
+(mudiff_hip.multislice, section 5.28), not this flag's with --known_kspace.  A later intake only has to fill the same ThickMeasurement.
 """
 from __future__ import annotations
 
@@ -132,28 +132,20 @@ def layout(Z, L, gap=0, offset=0):
 # ---------------------------------------------------------------------------------------------------
 # the measurement of one prediction
 # ---------------------------------------------------------------------------------------------------
-class ThickMeasurement(Constraint):
-    """What the samplers take for one prediction of n thin slices (the sampled range s0..s1; local index i = slice s0 + i): `y` fp32
-    [G,S,S] on the device, the measured slabs' averages; `starts` [G], each measured slab's first local index; `group_of` int [n], the
-    measured slab of a slice or -1; `weights`, `gains` fp32 [L] (numpy: the host tables of ops.slab_constrain); `report`: thick_<t>.json;
-    `resample`: --known_resample.  A later intake of really thick data only has to fill the same fields."""
+class SlabbedMeasurement(Constraint):
+    """What the measurements of slabs share (ThickMeasurement; multislice.MultisliceMeasurement): the measured slabs of the n local
+    slices - `starts` [G], `group_of` int [n], `weights`, `gains` fp32 [L], `L` - and what follows from them alone: the units that must
+    share a batch, where an ensemble's chunk may end, and the member rows of a batch's groups."""
 
-    def __init__(self, y, starts, n, weights, report, resample, options):
+    def _slabs(self, starts, n, weights):
         from . import ops
-        self.y, self.starts, self.n, self.report, self.resample, self.options = y, [int(s) for s in starts], int(n), report, int(resample), options
+        self.starts, self.n = [int(s) for s in starts], int(n)
         self.weights = np.ascontiguousarray(weights, dtype=np.float32)
         self.gains = ops.slab_gains(self.weights)[0]
         self.L = int(self.weights.shape[0])
         self.group_of = np.full(self.n, -1, np.int64)
         for g, s in enumerate(self.starts):
             self.group_of[s:s + self.L] = g
-        self.y_norm = torch.linalg.vector_norm(y.flatten(1), dim=1) if y.shape[0] else torch.zeros(0, device=y.device)
-        self.residual = torch.zeros(y.shape[0], device=y.device, dtype=torch.float32)
-        self.x_norm = torch.zeros_like(self.residual)
-
-    tag, baseline_through_plane = 'thick', True
-    done_suffix = lambda self: suffix(self)      # noqa: E731
-    baseline = lambda self: ('thick_interp', self.interpolated()) if self.options['interp'] else None      # noqa: E731
 
     def units(self, lo=0, hi=None):
         """The local slices lo..hi-1 in order as batches() takes them: a measured slab's L slices together, every other slice alone.
@@ -182,10 +174,10 @@ class ThickMeasurement(Constraint):
             raise ValueError(f'sample_ensemble: a chunk of {chunk} slices is smaller than a slab of {self.L} thin slices')
         return s1
 
-    def for_rows(self, slices, samples=None, m=None):
+    def group_rows(self, slices, samples=None, m=None):
         """The batch whose row r holds local slice slices[r] of sample samples[r] (None: all 0); a row from m on, or with slice -1, is
-        padding, in no group -> constraints.SlabRows = (GraphSampler.sample_keyed's `thick` tuple, the measured slab of each group).
-        Every measured slab that a row touches must be in the batch whole, per sample; its rows enter the table in slice order."""
+        padding, in no group -> (members int32 [groups, L], the measured slab of each group).  Every measured slab that a row touches
+        must be in the batch whole, per sample; its rows enter the table in slice order."""
         samples = [0] * len(slices) if samples is None else [int(s) for s in samples]
         found = {}
         for r, (i, j) in enumerate(zip(slices[:m], samples)):
@@ -198,7 +190,29 @@ class ThickMeasurement(Constraint):
                 raise ValueError(f'thick slices: the batch holds {len(rows)} of the {self.L} thin slices of a measured slab (sample {j})')
             members.append([rows[l] for l in range(self.L)])
             gids.append(g)
-        members = np.asarray(members, np.int32).reshape(len(members), self.L)
+        return np.asarray(members, np.int32).reshape(len(members), self.L), gids
+
+
+class ThickMeasurement(SlabbedMeasurement):
+    """What the samplers take for one prediction of n thin slices (the sampled range s0..s1; local index i = slice s0 + i): `y` fp32
+    [G,S,S] on the device, the measured slabs' averages; `starts` [G], each measured slab's first local index; `group_of` int [n], the
+    measured slab of a slice or -1; `weights`, `gains` fp32 [L] (numpy: the host tables of ops.slab_constrain); `report`: thick_<t>.json;
+    `resample`: --known_resample.  A later intake of really thick data only has to fill the same fields."""
+
+    def __init__(self, y, starts, n, weights, report, resample, options):
+        self.y, self.report, self.resample, self.options = y, report, int(resample), options
+        self._slabs(starts, n, weights)
+        self.y_norm = torch.linalg.vector_norm(y.flatten(1), dim=1) if y.shape[0] else torch.zeros(0, device=y.device)
+        self.residual = torch.zeros(y.shape[0], device=y.device, dtype=torch.float32)
+        self.x_norm = torch.zeros_like(self.residual)
+
+    tag, baseline_through_plane = 'thick', True
+    done_suffix = lambda self: suffix(self)      # noqa: E731
+    baseline = lambda self: ('thick_interp', self.interpolated()) if self.options['interp'] else None      # noqa: E731
+
+    def for_rows(self, slices, samples=None, m=None):
+        """group_rows' batch -> constraints.SlabRows = (GraphSampler.sample_keyed's `thick` tuple, the measured slab of each group)."""
+        members, gids = self.group_rows(slices, samples, m)
         idx = torch.as_tensor(gids, dtype=torch.int64, device=self.y.device)
         return SlabRows((self.y.index_select(0, idx), members, self.weights, self.gains), idx)
 
@@ -219,22 +233,8 @@ class ThickMeasurement(Constraint):
         self.residual.scatter_reduce_(0, gids, r, 'amax')
 
     def interpolated(self):
-        """[n,S,S] in [-1,1] terms: piecewise linear along z through (slab centre, y_j) over the measured slabs, constant beyond the first
-        and the last centre - the thick slices as one would resample them without the model.  Without a measured slab: -1 everywhere."""
-        G, S = self.y.shape[0], self.y.shape[-1]
-        if G == 0:
-            return torch.full((self.n, S, S), -1.0, device=self.y.device)
-        centres = np.asarray(self.starts, np.float64) + (self.L - 1) / 2.0
-        z = np.arange(self.n, dtype=np.float64)
-        hi = np.clip(np.searchsorted(centres, z, side='right'), 1, max(G - 1, 1))
-        lo = hi - 1
-        hi = np.minimum(hi, G - 1)
-        span = np.where(hi > lo, centres[hi] - centres[lo], 1.0)
-        f = np.clip((z - centres[lo]) / span, 0.0, 1.0)
-        f = torch.from_numpy(f.astype(np.float32)).to(self.y.device)[:, None, None]
-        ya = self.y.index_select(0, torch.from_numpy(lo).to(self.y.device))
-        yb = self.y.index_select(0, torch.from_numpy(hi).to(self.y.device))
-        return ((1.0 - f) * ya + f * yb).contiguous()
+        """interpolate_slabs of the slab averages."""
+        return interpolate_slabs(self.y, self.starts, self.L, self.n)
 
     def finish(self):
         """The report with the residuals put in (None for a slab that was not measured)."""
@@ -245,6 +245,26 @@ class ThickMeasurement(Constraint):
             g += 1 if s['measured'] else 0
         self.report['max_residual'] = max(res, default=None)
         return self.report
+
+
+def interpolate_slabs(y, starts, L, n):
+    """y fp32 [G,S,S], one image per measured slab -> [n,S,S] in [-1,1] terms: piecewise linear along z through (slab centre, y_j),
+    constant beyond the first and the last centre - the thick slices as one would resample them without the model.  Without a measured
+    slab: -1 everywhere."""
+    G, S = y.shape[0], y.shape[-1]
+    if G == 0:
+        return torch.full((n, S, S), -1.0, device=y.device)
+    centres = np.asarray(starts, np.float64) + (L - 1) / 2.0
+    z = np.arange(n, dtype=np.float64)
+    hi = np.clip(np.searchsorted(centres, z, side='right'), 1, max(G - 1, 1))
+    lo = hi - 1
+    hi = np.minimum(hi, G - 1)
+    span = np.where(hi > lo, centres[hi] - centres[lo], 1.0)
+    f = np.clip((z - centres[lo]) / span, 0.0, 1.0)
+    f = torch.from_numpy(f.astype(np.float32)).to(y.device)[:, None, None]
+    ya = y.index_select(0, torch.from_numpy(lo).to(y.device))
+    yb = y.index_select(0, torch.from_numpy(hi).to(y.device))
+    return ((1.0 - f) * ya + f * yb).contiguous()
 
 
 def measure(region, s0, s1, size, options, device):

@@ -411,7 +411,8 @@ def predict_volume(args):
     prediction and the scores gain the regions known / synthesised (mudiff_hip.known_region).  With --known_kspace
     (mudiff_hip.kspace, section 5.26) or --known_thick (mudiff_hip.thick, section 5.27) that volume's measured Fourier coefficients or slab
     averages condition the sampling instead, nothing is pasted, and kspace_<target>.json or thick_<target>.json (and under
-    --kspace_zero_filled / --thick_interp the baseline volume) goes next to the prediction."""
+    --kspace_zero_filled / --thick_interp the baseline volume) goes next to the prediction; --known_multislice (mudiff_hip.multislice,
+    section 5.28) is both at once, with multislice_<target>.json and --multislice_baseline."""
     evaluation, resampled, found = _load_eval_inputs(args)
     args = copy.copy(args)                               # the run's own copy: it carries the record of what the intake did
     args.evaluation_record = (resampled, found)          # (for _predict_volume's report: IntakeReport.add_evaluation)
@@ -630,9 +631,9 @@ def predict_from_conditions(args, plan, evaluation, gen1, gen2, device, stacks, 
 
 
 def known_modes():
-    """The modules of the three ways a target can be partly acquired, in the order their flags are checked."""
-    from . import known_region, kspace, thick
-    return known_region, kspace, thick
+    """The modules of the four ways a target can be partly acquired, in the order their flags are checked."""
+    from . import known_region, kspace, multislice, thick
+    return known_region, kspace, thick, multislice
 
 
 def _known_region(args, ref, device):
@@ -661,8 +662,9 @@ def _assemble_map(p, shp, s0, s1, on_device):
 
 
 def _measurement_outputs(args, write, put_together, aff, hdr, evaluation, device):
-    """--known_kspace / --known_thick: the measurement's report (kspace_<t>.json, thick_<t>.json) next to the prediction, and under its
-    flag its baseline (zero_filled_<t>.nii.gz, thick_interp_<t>.nii.gz), mapped to [0,1], through the prediction's own road
+    """--known_kspace / --known_thick / --known_multislice: the measurement's report (kspace_<t>.json, thick_<t>.json, multislice_<t>.json)
+    next to the prediction, and under its flag its baseline (zero_filled_<t>.nii.gz, thick_interp_<t>.nii.gz,
+    multislice_baseline_<t>.nii.gz), mapped to [0,1], through the prediction's own road
     (`put_together`: a device [n,S,S] map -> the host volume as written); with an evaluation it is scored into metrics_<name>_<t>.json,
     and where the measurement says so --through_plane measures it into through_plane_<name>_<t>.json.  Nothing without the flags."""
     meas = getattr(args, 'constraint', None)
@@ -896,7 +898,7 @@ def make_parser(prog='MU-Diff volume prediction (MI355X)'):
     from . import slice_coupling
     slice_coupling.add_flags(p)             # (--slice_coupling, --through_plane: in a late parser, VolumeParser.later())
     for module in known_modes()[1:] + known_modes()[:1]:      # (each mode's flags in a late parser of its own; --known_volume's place,
-        module.add_flags(p)                                   # before the last, is pinned, so the two later modes' came before it)
+        module.add_flags(p)                                   # before the last, is pinned, so the later modes' came before it)
     from . import ensemble
     ensemble.add_flags(p)                   # (--ensemble_quantiles, --ensemble_center, --coverage: in a further one)
     return p
@@ -952,8 +954,8 @@ def build_argparser(argv=None):
     DESIGN.md sections 5.12 - 5.22; --align's flags sit in VolumeParser.late), and --slice_coupling / --through_plane (mudiff_hip.slice_coupling,
     DESIGN.md section 5.23; in a further late parser), and --ensemble_quantiles / --ensemble_center / --coverage (mudiff_hip.ensemble,
     mudiff_hip.volume_coverage; in one more), and --known_volume / --known_mask / --known_drop_slices /
-    --known_resample, --known_kspace with the --kspace_* flags and --known_thick with the --thick_* flags (known_modes(); DESIGN.md sections
-    5.24a - 5.27; each in a parser of its own before that last one)."""
+    --known_resample, --known_kspace with the --kspace_* flags, --known_thick with the --thick_* flags and --known_multislice with the
+    --multislice_* flags (known_modes(); DESIGN.md sections 5.24a - 5.28; each in a parser of its own before that last one)."""
     p = make_parser()
     return finish_args(p, p.parse_args(argv))
 
