@@ -41,6 +41,9 @@ extern "C" {
 #define MUD_PRO_AFFINE 1       /* a[b,c]*x + s[b,c]            (GroupNorm, AttnBlockpp)      */
 #define MUD_PRO_AFFINE_SILU 2  /* silu(a[b,c]*x + s[b,c])      (AdaGN + SiLU of the ResBlock) */
 #define MUD_PRO_LRELU 3        /* lrelu_0.2(x), no affine      (DownConvBlock of the critic)  */
+/* Not a value of pro_mode: the form of the 3x3 matrix-core kernel that a launch with pro_mode AFFINE_SILU and             */
+/* mud_conv_args.in_up2 runs - FIR x2 up-sampling of silu(a*x + s), formed from the LOW-resolution x while it is staged. */
+#define MUD_PRO_UP2_AFFINE_SILU 4
 
 /* arithmetic plan of one mud_conv2d_mfma launch (mud_conv_args.prec); the weights must have been packed for the same plan */
 #define MUD_PREC_16X3 0        /* every product as hi*hi + hi*lo + lo*hi on the 16-bit MFMA (fp16 pieces): ~2^-22 per product */
@@ -175,6 +178,14 @@ typedef struct mud_conv_args {
   /* a = 0 takes rows i-1 (tap 3) and i (tap 1), a = 1 rows i (tap 2) and i+1 (tap 0), columns alike, outside the image = 0.     */
   /* Any other launch that sets it is refused (mud_conv2d_mfma_res_up2_supported tells beforehand); mud_conv2d_direct refuses it. */
   int res_up2; float res_k[4];
+  /* mud_conv2d_mfma, ks 3, pro_mode AFFINE_SILU, no sub2 / skip_w / res_up2, even H and W, a grid that is not split over K - the  */
+  /* INPUT up-sampled while it is staged (the up-sampling residual blocks' Conv_0): with in_up2 != 0 `x` is the LOW-resolution     */
+  /* view [B, H/2, W/2, Cin] (H, W stay the output size; the folded GroupNorm's gn_count is that of the low-resolution tensor) and */
+  /* the launch computes conv3x3(FIR x2 (silu(a*x + s))) - what mud_fir_nhwc(up = 2, pad (2, 1), the prologue) followed by a       */
+  /* MUD_PRO_NONE launch computes, term for term - with the separable 4x4 filter in_k (x) in_k (1-D taps, gain included; rows and  */
+  /* columns as for res_k).  Built for some tiles and plans only: mud_conv2d_mfma_in_up2_supported tells beforehand, any other      */
+  /* launch that sets it is refused; mud_conv2d_direct refuses it.                                                                  */
+  int in_up2; float in_k[4];
 } mud_conv_args;
 
 /* Exact fp32 direct convolution (FMA chain per output), any ks/stride/pad/Cin/Cout.
@@ -207,6 +218,9 @@ int mud_conv2d_mfma_prec_supported(const mud_conv_args* a, int prec);
 int64_t mud_conv2d_mfma_splitk_bytes(const mud_conv_args* a);
 /* 1 when mud_conv2d_mfma takes res_up2 for this launch (ks, sub2, skip_w, sizes and the split-K policy are looked at), else 0. */
 int mud_conv2d_mfma_res_up2_supported(const mud_conv_args* a);
+/* 1 when mud_conv2d_mfma takes in_up2 for this launch (ks, sub2, skip_w, res_up2, pro_mode, the output size H x W, the tile that  */
+/* size takes, a.prec and the split-K policy are looked at), else 0. */
+int mud_conv2d_mfma_in_up2_supported(const mud_conv_args* a);
 
 /* ---- e4m3 range census of a convolution input (the precision guard of MUD_PREC_FP8X: mudiff_hip.precision).
  * MUD_PREC_FP8X converts every prologued activation a (and its fp16 remainder a - fp16(a)) to e4m3 at CONSTANT power-of-two

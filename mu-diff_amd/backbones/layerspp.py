@@ -159,8 +159,17 @@ class ConvParam:
             return ops.PREC_16X3
         return ops.choose_prec(x, self.cout, pro[2] if pro is not None else ops.PRO_NONE, skip=skip is not None, sub2=sub2)
 
+    def in_up2_ok(self, x):
+        """Does this 3x3 conv, run on the x2 FIR up-sampling of silu(AdaGN(x)), take the LOW-resolution x itself and up-sample it
+        while staging it (ops.conv(in_up2=...))?  Asked for the plan the launch would run with, at the size it runs at."""
+        if not (ops.IN_UP2 and self.mfma and self.ks == 3):
+            return False
+        full = x.up2_shape()
+        return ops.in_up2_ok(full.B, full.H, full.W, self.cin, self.cout, self.plan(full, (None, None, ops.PRO_AFFINE_SILU)))
+
     def __call__(self, x, **kw):
-        plan = self.plan(x, kw.get('pro'), kw.get('skip'), kw.get('sub2', False))
+        # (a launch that up-samples its input is planned at its own size, twice that of x)
+        plan = self.plan(x if kw.get('in_up2') is None else x.up2_shape(), kw.get('pro'), kw.get('skip'), kw.get('sub2', False))
         if plan == ops.PREC_FP8X:
             if precision.CENSUS:          # inside precision.census(): the e4m3 range census of this input first (eager only)
                 precision.record(self, x, kw.get('pro'))
@@ -371,12 +380,22 @@ class ResnetBlockBigGANpp_Adagn(nn.Module, _Prepared):
         sc0, sh0 = (gn0, None) if isinstance(gn0, ops.LazyGN) else gn0
         if self.up:
             kk, up, down, pad = up_or_down_sampling.fir_params('up' if self.fir else 'naive_up', self.fir_kernel)
-            h_in, _ = ops.fir_nhwc(x, kk, up, down, pad, pro=(sc0, sh0, PRO_AFFINE_SILU), want_h=True, want_x=False)
+            taps_all = ops.up2_taps(kk, up, down, pad)
+            # Conv_0 up-samples silu(AdaGN(x)) while staging it where the kernel has that form for the launch: h_in is never written
+            taps_in = taps_all if taps_all is not None and p['c0'].in_up2_ok(x) else None
+            if taps_in is None:
+                h_in, _ = ops.fir_nhwc(x, kk, up, down, pad, pro=(sc0, sh0, PRO_AFFINE_SILU), want_h=True, want_x=False)
+                Hf, Wf = h_in.H, h_in.W
+            else:
+                Hf, Wf = 2 * x.H, 2 * x.W
             x_skip = p['c2'](x)          # LOW resolution: Conv_2(FIR(x)) = FIR(Conv_2(x)) minus its bias (see _prepare)
-            taps = ops.up2_taps(kk, up, down, pad) if p['c1'].mfma and ops.res_up2_ok(x.B, h_in.H, h_in.W, self.out_ch, self.out_ch) else None
+            taps = taps_all if p['c1'].mfma and ops.res_up2_ok(x.B, Hf, Wf, self.out_ch, self.out_ch) else None
             if taps is None:             # (else Conv_1 up-samples it while loading its residual: the full-resolution tensor is never written)
                 x_skip, _ = ops.fir_nhwc(x_skip, kk, up, down, pad)
-            h = p['c0'](h_in, bias2=tbias, arena=arena)
+            if taps_in is None:
+                h = p['c0'](h_in, bias2=tbias, arena=arena)
+            else:
+                h = p['c0'](x, pro=(sc0, sh0, PRO_AFFINE_SILU), bias2=tbias, arena=arena, in_up2=taps_in)
         elif self.down:
             kk, up, down, pad = up_or_down_sampling.fir_params('down' if self.fir else 'naive_down', self.fir_kernel)
             h_in, x_skip = ops.fir_nhwc(x, kk, up, down, pad, pro=(sc0, sh0, PRO_AFFINE_SILU), want_h=True, want_x=True)

@@ -269,6 +269,7 @@ extern "C" int mud_conv2d_direct(const mud_conv_args* ap, void* stream) {
   MUD_REQUIRE(a.pro_mode == MUD_PRO_NONE || a.pro_mode == MUD_PRO_LRELU || (a.pro_scale && a.pro_shift && a.pro_ld >= a.Cin), "mud_conv2d_direct: prologue arrays missing");
   MUD_REQUIRE(!a.res || a.ldr >= a.Cout, "mud_conv2d_direct: bad residual view");
   MUD_REQUIRE(!a.res_up2, "mud_conv2d_direct: res_up2 (a residual up-sampled on load) is built for mud_conv2d_mfma's 3x3 kernel only");
+  MUD_REQUIRE(!a.in_up2, "mud_conv2d_direct: in_up2 (an input up-sampled while it is staged) is built for mud_conv2d_mfma's 3x3 kernel only");
   const int Ho = (a.H + 2 * a.pad - a.ks) / a.stride + 1, Wo = (a.W + 2 * a.pad - a.ks) / a.stride + 1;
   MUD_REQUIRE(Ho > 0 && Wo > 0, "mud_conv2d_direct: empty output");
   if (a.B == 0) return MUD_OK;

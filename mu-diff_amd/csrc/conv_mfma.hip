@@ -116,6 +116,13 @@ struct CmGeo {
   }
   static_assert(LDS_MAX <= 160 * 1024, "LDS budget");
   static_assert(NT % Q == 0, "staging split");
+  // MUD_PRO_UP2_AFFINE_SILU (3x3 only): the LOW-resolution halo of the tile - full-resolution rows ty0 - 1 .. ty0 + ROWS read the
+  // low-resolution rows ty0 / 2 - 1 .. (ty0 + ROWS) / 2, columns alike - one 16-channel chunk of it, activated, as fp32 in LDS
+  // (64-B pixel records).  That scratch sits at GN_OFF and pushes the GroupNorm arrays behind it.
+  static constexpr int UP_ROWS = ROWS / 2 + 2, UP_COLS = 32 / 2 + 2;
+  static constexpr int UP_ITEMS = UP_ROWS * UP_COLS * 4;            // float4 per chunk
+  static constexpr int UP_NLOAD = (UP_ITEMS + NT - 1) / NT;
+  static constexpr int UP_BYTES = UP_ROWS * UP_COLS * 64;
 };
 
 
@@ -227,6 +234,16 @@ __global__ __launch_bounds__(64 * WM * WN, (MT == 1 && WM * WN == 8) ? 4 : 2) vo
   constexpr bool H1 = G::H1;                            // one pass: fp16 hi.hi only (3x3 only)
   static_assert(!X8 || KS == 3, "the fp8 cross-term plan is built for the 3x3 kernel");
   static_assert(!H1 || KS == 3, "the single-pass fp16 plan is built for the 3x3 kernel");
+  // IUP (MUD_PRO_UP2_AFFINE_SILU, mud_conv_args.in_up2): a.x is the LOW-resolution tensor [B, H/2, W/2, Cin] and the A tile is the x2 FIR
+  // up-sampling of silu(scale * x + shift) - what k_fir_up2_quad<true, false> (fir.hip) writes and a MUD_PRO_NONE launch reads back -
+  // formed while it is staged, in two passes per chunk: the low-resolution halo is loaded, activated ONCE per element and kept as fp32
+  // in an LDS scratch (up_pass1); behind a barrier every staged float4 is the polyphase sum of its 2 x 2 low-resolution neighbours
+  // (up_pass2), then split like any MUD_PRO_NONE value.
+  constexpr bool IUP = PRO == MUD_PRO_UP2_AFFINE_SILU;
+  constexpr bool AFF = PRO == MUD_PRO_AFFINE || PRO == MUD_PRO_AFFINE_SILU || IUP;      // prologue with per-channel scale / shift
+  static_assert(!IUP || (KS == 3 && !DUAL && G::ROWS % 2 == 0 && G::LDS_MAX + G::UP_BYTES <= 160 * 1024), "in_up2: 3x3, no fused skip conv, even tile rows, LDS budget");
+  constexpr int GN_OFF = G::GN_OFF + (IUP ? G::UP_BYTES : 0);     // (the scratch sits where the GroupNorm arrays start otherwise)
+  constexpr int NRAW = IUP ? G::UP_NLOAD : G::NLOAD;               // activation loads per thread and chunk
   using HV4 = h16x4;
   using HV8 = h16x8;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -256,7 +273,7 @@ __global__ __launch_bounds__(64 * WM * WN, (MT == 1 && WM * WN == 8) ? 4 : 2) vo
   } else {
     flat0 = (int64_t)tile * G::P;
   }
-  const float* xb = a.x + (int64_t)b * HW * a.ldx;
+  const float* xb = a.x + (int64_t)b * (IUP ? (int64_t)(a.H >> 1) * (a.W >> 1) : HW) * a.ldx;
   const int64_t tile_bytes = (int64_t)k16s * (G::TAPS * G::BSTEP);          // packed bytes of one 64-channel tile
   const char* wb = (const char*)a.w + (int64_t)b * a.w_bstride + (int64_t)nt * WN * tile_bytes;
   const float* psc = a.pro_scale + (int64_t)b * a.pro_ld;
@@ -271,9 +288,27 @@ __global__ __launch_bounds__(64 * WM * WN, (MT == 1 && WM * WN == 8) ? 4 : 2) vo
   // Everything below is branch-free: padding pixels load a clamped (valid) address and are zeroed by a 0/1
   // mask; slots past the tile wrap around and redo another thread's item (identical value, same address).
   const int q = tid % G::Q;                     // this thread's float4 (4 channels) inside a chunk
-  int goff[G::NLOAD], loff[G::NLOAD];
+  int goff[NRAW], loff[G::NLOAD];
   int loff2[DUAL ? G::NLOAD : 1];               // DUAL: byte offset of the slot's hi half in the raw centre image, or -1 (halo pixel)
   unsigned vmask = 0;                           // bit j: slot j is a real (non-padding) pixel
+  // IUP: the thread's low-resolution slots (goff, scratch byte offset, bit j of lmask: inside the low-resolution image) and, per
+  // full-resolution slot, the scratch offset of its first neighbour (row y0, column x0; the others sit one record / one scratch row
+  // further) and the parities of its row and column, which pick the polyphase taps
+  int slo[IUP ? G::UP_NLOAD : 1], soff[IUP ? G::NLOAD : 1];
+  unsigned lmask = 0, ymask = 0, xmask = 0;
+  if constexpr (IUP) {
+    const int Hl = a.H >> 1, Wl = a.W >> 1;
+#pragma unroll
+    for (int j = 0; j < G::UP_NLOAD; ++j) {
+      const int item = (tid + j * G::NT) % G::UP_ITEMS;     // (NT % 4 == 0 and UP_ITEMS % 4 == 0: q is preserved; wrapped slots redo an item)
+      const int p = item >> 2, py = p / G::UP_COLS, px = p - py * G::UP_COLS;
+      const int ly = (ty0 >> 1) - 1 + py, lx = (tx0 >> 1) - 1 + px;
+      const bool valid = ly >= 0 && ly < Hl && lx >= 0 && lx < Wl;
+      goff[j] = valid ? (ly * Wl + lx) * a.ldx : 0;          // (int: the host checks the image size)
+      lmask |= (valid ? 1u : 0u) << j;
+      slo[j] = p * 64 + q * 16;
+    }
+  }
 #pragma unroll
   for (int j = 0; j < G::NLOAD; ++j) {
     const int item = (tid + j * G::NT) % G::ITEMS;   // NT % Q == 0 and ITEMS % Q == 0: q is preserved
@@ -295,12 +330,21 @@ __global__ __launch_bounds__(64 * WM * WN, (MT == 1 && WM * WN == 8) ? 4 : 2) vo
       valid = fp < HW;
       g = fp * a.ldx;
     }
-    goff[j] = valid ? (int)g : 0;
+    if constexpr (IUP) {
+      // output row gy = 2 i + ay reads the low-resolution rows y0 = i - 1 + ay and y0 + 1 (k_fir_up2_quad; the res_up2 block below),
+      // columns alike; relative to the scratch's first row ty0 / 2 - 1 that is (gy >> 1) + ay - ty0 / 2 in [0, UP_ROWS - 2]
+      const int py = p / G::PW, px = p - py * G::PW;
+      const int gy = ty0 + py - 1, gx = tx0 + px - 1, ay = gy & 1, ax = gx & 1;
+      soff[j] = ((((gy >> 1) + ay - (ty0 >> 1)) * G::UP_COLS + (gx >> 1) + ax - (tx0 >> 1)) * 16 + q * 4) * 4;
+      ymask |= (unsigned)ay << j;
+      xmask |= (unsigned)ax << j;
+    } else
+      goff[j] = valid ? (int)g : 0;
     vmask |= (valid ? 1u : 0u) << j;
     loff[j] = (q >> 2) * G::PLANE + p * G::PIX + (q & 3) * 8;
   }
 
-  f32x4 raw[G::NLOAD];
+  f32x4 raw[NRAW];
   // CNT: the activation loads of chunk k+1 (issued at the head of chunk k's group 0, consumed from group 1 on) stay IN FLIGHT across
   // group 0's barrier.  hipcc cannot do that by itself: with LDS-DMA and ordinary loads both pending its wait-count pass assumes they
   // return out of order and waits for vmcnt(0) at the first use - i.e. also for the weight DMA it issued a moment ago - and
@@ -313,24 +357,24 @@ __global__ __launch_bounds__(64 * WM * WN, (MT == 1 && WM * WN == 8) ? 4 : 2) vo
   do {                                                                          \
     if constexpr (CNT) {                                                        \
       asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");                 \
-      _Pragma("unroll") for (int j_ = 0; j_ < G::NLOAD; ++j_) asm volatile("" : "+v"(raw[j_])); \
+      _Pragma("unroll") for (int j_ = 0; j_ < NRAW; ++j_) asm volatile("" : "+v"(raw[j_])); \
     }                                                                           \
   } while (0)
   f32x4 psc_r = {1.f, 1.f, 1.f, 1.f}, psh_r = {0.f, 0.f, 0.f, 0.f};   // prologue scale/shift of the chunk in `raw`
-  const bool gn_fold = (PRO == MUD_PRO_AFFINE || PRO == MUD_PRO_AFFINE_SILU) && a.gn_sums != nullptr;   // workgroup-uniform
-  const float* const gn_sc = (const float*)(smem + G::GN_OFF);
+  const bool gn_fold = AFF && a.gn_sums != nullptr;   // workgroup-uniform
+  const float* const gn_sc = (const float*)(smem + GN_OFF);
   const int gn_c = (a.Cin + 3) & ~3;            // shift array follows the scale array
   auto fetch_raw = [&](int chunk) {
     int c = chunk * G::KCH + q * 4;
     c = c < a.Cin ? c : 0;                      // clamped; zeroed in store_a
 #pragma unroll
-    for (int j = 0; j < G::NLOAD; ++j) {
+    for (int j = 0; j < NRAW; ++j) {
       if constexpr (CNT) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(raw[j]) : "v"(xb + goff[j] + c) : "memory");
       else raw[j] = *(const f32x4*)(xb + goff[j] + c);
     }
   };
   auto fetch_ss = [&](int chunk) {
-    if (PRO == MUD_PRO_AFFINE || PRO == MUD_PRO_AFFINE_SILU) {
+    if (AFF) {
       int c = chunk * G::KCH + q * 4;
       c = c < a.Cin ? c : 0;
       // always from LDS (the caller's arrays are copied there by the prologue when the GroupNorm finalisation is not folded in): as a
@@ -341,7 +385,7 @@ __global__ __launch_bounds__(64 * WM * WN, (MT == 1 && WM * WN == 8) ? 4 : 2) vo
   };
   auto fetch_a = [&](int chunk) {
     fetch_ss(chunk);
-    fetch_raw(chunk);                           // LAST: the NLOAD youngest loads of the wave at group 0's barrier (counted wait there)
+    fetch_raw(chunk);                           // LAST: the NRAW youngest loads of the wave at group 0's barrier (counted wait there)
   };
   auto store_a_slots = [&](int chunk, char* buf, int j0, int j1) {
     const bool cvalid = chunk * G::KCH + q * 4 < a.Cin;
@@ -371,6 +415,58 @@ __global__ __launch_bounds__(64 * WM * WN, (MT == 1 && WM * WN == 8) ? 4 : 2) vo
     }
   };
   auto store_a = [&](int chunk, char* buf) { store_a_slots(chunk, buf, 0, G::NLOAD); };
+  // IUP, pass 1: the chunk's low-resolution halo -> silu(scale * x + shift), once per element (k_fir_up2_quad's prologue, the same
+  // instructions), zero outside the low-resolution image and past Cin -> the scratch
+  char* const scr = smem + G::GN_OFF;
+  auto up_pass1 = [&](int chunk) {
+    if constexpr (IUP) {
+      const bool cvalid = chunk * G::KCH + q * 4 < a.Cin;
+#pragma unroll
+      for (int j = 0; j < G::UP_NLOAD; ++j) {
+        const float keep = (cvalid && ((lmask >> j) & 1u)) ? 1.0f : 0.0f;
+        f32x4 v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = cm_fast_silu(__builtin_fmaf(raw[j][e], psc_r[e], psh_r[e])) * keep;
+        *(f32x4*)(scr + slo[j]) = v;
+      }
+    }
+  };
+  // IUP, pass 2: slots [j0, j1) of the full-resolution tile from the scratch.  Polyphase weights and term order of k_fir_up2_quad
+  // (rows, then columns; the 2-D weights are the products of the 1-D taps, as in the res_up2 block below); pixels outside the
+  // image are the convolution's own zero padding (vmask); then the MUD_PRO_NONE split
+  auto up_pass2 = [&](char* buf, int j0, int j1) {
+    if constexpr (IUP) {
+#pragma unroll
+      for (int j = 0; j < G::NLOAD; ++j) {
+        if (j < j0 || j >= j1) continue;
+        const bool ay = (ymask >> j) & 1u, ax = (xmask >> j) & 1u;
+        const float ky0 = ay ? a.in_k[2] : a.in_k[3], ky1 = ay ? a.in_k[0] : a.in_k[1];
+        const float kx0 = ax ? a.in_k[2] : a.in_k[3], kx1 = ax ? a.in_k[0] : a.in_k[1];
+        const float w00 = ky0 * kx0, w01 = ky0 * kx1, w10 = ky1 * kx0, w11 = ky1 * kx1;
+        const char* sp = scr + soff[j];
+        const f32x4 v00 = *(const f32x4*)sp, v01 = *(const f32x4*)(sp + 64);
+        const f32x4 v10 = *(const f32x4*)(sp + G::UP_COLS * 64), v11 = *(const f32x4*)(sp + G::UP_COLS * 64 + 64);
+        f32x4 t;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float u = w00 * v00[e];
+          u = __builtin_fmaf(w01, v01[e], u);
+          u = __builtin_fmaf(w10, v10[e], u);
+          t[e] = __builtin_fmaf(w11, v11[e], u);
+        }
+        HV4 hi, lo;
+        int a8 = 0, al8 = 0;
+        cm_stage4<MUD_PRO_NONE, X8, H1>(t, psc_r, psh_r, ((vmask >> j) & 1u) ? 1.0f : 0.0f, hi, lo, a8, al8);
+        *(HV4*)(buf + loff[j]) = hi;
+        if constexpr (X8) {                     // (as store_a_slots)
+          *(int*)(buf + loff[j] + 32 - q * 4) = a8;
+          *(int*)(buf + loff[j] + 48 - q * 4) = al8;
+        } else if constexpr (!H1) {
+          *(HV4*)(buf + loff[j] + 32) = lo;
+        }
+      }
+    }
+  };
 
   // ---- B operand: groups of GS steps are copied global -> LDS by direct-to-LDS loads (no VGPRs) into a 2-slot ring, one group
   // ahead of its use.  The packed layout already is the LDS image (16-B halves pre-swizzled for conflict-free ds_read_b128).
@@ -538,10 +634,10 @@ __global__ __launch_bounds__(64 * WM * WN, (MT == 1 && WM * WN == 8) ? 4 : 2) vo
   }
 
   if (gn_fold) {                                // scale / shift of this sample -> LDS while the first loads are in flight
-    cm_gn_to_lds(a, b, tid, G::NT, (float*)(smem + G::GN_OFF), gn_c);
+    cm_gn_to_lds(a, b, tid, G::NT, (float*)(smem + GN_OFF), gn_c);
     __syncthreads();
-  } else if (PRO == MUD_PRO_AFFINE || PRO == MUD_PRO_AFFINE_SILU) {
-    float* sc_lds = (float*)(smem + G::GN_OFF);
+  } else if (AFF) {
+    float* sc_lds = (float*)(smem + GN_OFF);
     for (int c = tid; c < a.Cin; c += G::NT) {
       sc_lds[c] = psc[c];
       sc_lds[gn_c + c] = psh[c];
@@ -550,7 +646,12 @@ __global__ __launch_bounds__(64 * WM * WN, (MT == 1 && WM * WN == 8) ? 4 : 2) vo
   }
   fetch_ss(kc0);
   CM_RAW_WAIT(0);
-  store_a(kc0, smem + (kc0 & 1) * G::BUF);
+  if constexpr (IUP) {
+    up_pass1(kc0);
+    __syncthreads();
+    up_pass2(smem + (kc0 & 1) * G::BUF, 0, G::NLOAD);
+  } else
+    store_a(kc0, smem + (kc0 & 1) * G::BUF);
   __syncthreads();
 
   // One chunk of the reduction.  `more` (a further chunk follows: its tile is fetched and staged under this one's MFMAs) is a
@@ -696,16 +797,25 @@ __global__ __launch_bounds__(64 * WM * WN, (MT == 1 && WM * WN == 8) ? 4 : 2) vo
             return i >= SPAN ? G::NLOAD : ((i > 0 ? i - 1 : 0) * G::NLOAD + G::NLOAD - 1) / SPAN;
           };
           const int j0 = jb(st - G::GS), j1 = jb(st - G::GS + 1);
-          store_a_slots(kc + 1, nxt, j0, j1);
+          if constexpr (IUP) {
+            // group 1's first step takes the low-resolution halo to the scratch, the group's barrier (the one that is there anyway)
+            // publishes it, and the three steps of group 2 stage the tile from it.  One scratch is enough: it is read in group 2
+            // and written again in group 1 of the next chunk, two barriers later.
+            static_assert(G::NG == 3 && G::GS == 3, "in_up2: the scratch in group 1, the staging in group 2");
+            if (st == G::GS) up_pass1(kc + 1);
+            if (st >= 2 * G::GS) up_pass2(nxt, ((st - 2 * G::GS) * G::NLOAD) / G::GS, ((st - 2 * G::GS + 1) * G::NLOAD) / G::GS);
+          } else
+            store_a_slots(kc + 1, nxt, j0, j1);
         }
       }
       if (G::NG == 1 && more) store_a(kc + 1, nxt);
       if constexpr (g == 0 && more && CNT) {
-        // group 0 issued, in this order, the DMA of group gg+1 and then the NLOAD activation loads of chunk kc+1 (not needed before
-        // group 1).  Memory operations of a wave retire in order: waiting until only NLOAD are outstanding guarantees the DMA has
+        // group 0 issued, in this order, the DMA of group gg+1 and then the NRAW activation loads of chunk kc+1 (NLOAD of them; in_up2:
+        // the UP_NLOAD of the low-resolution halo; not needed before group 1).  Memory operations of a wave retire in order: waiting
+        // until only NRAW are outstanding guarantees the DMA has
         // landed and leaves the activation loads IN FLIGHT across the barrier - __syncthreads() would drain them (HBM latency, ~1-2 us
         // under load, inside a ~1 us group: with the loads removed the bench line gains 7.6 %).
-        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(G::NLOAD) : "memory");
+        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(NRAW) : "memory");
       } else
         __syncthreads();                          // DMA of group gg+1 landed (vmcnt drained by the fence) and is visible to all waves
     });
@@ -1453,16 +1563,18 @@ static int cm_launch_pro(const mud_conv_args& a, hipStream_t s) {
   if constexpr (KS == 3) kfn = (const void*)k_conv_mfma<KS, MT, WM, WN, PRO, DUAL, PREC>;      // only the variant that is launched is instantiated
   else kfn = (const void*)k_conv_mfma_regb<KS, MT, PRO>;
   static mud_attr_once attr_once;
+  int up_bytes = 0;                             // in_up2: the low-resolution scratch, in front of the GroupNorm arrays
+  if constexpr (PRO == MUD_PRO_UP2_AFFINE_SILU) up_bytes = G::UP_BYTES;
   if (attr_once.need()) {
-    hipError_t e = hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_MAX);
+    hipError_t e = hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_MAX + up_bytes);
     if (e != hipSuccess) {
-      mud_set_error("mud_conv2d_mfma: cannot reserve %d B of LDS: %s", G::LDS_MAX, hipGetErrorString(e));
+      mud_set_error("mud_conv2d_mfma: cannot reserve %d B of LDS: %s", G::LDS_MAX + up_bytes, hipGetErrorString(e));
       return MUD_ERR_LAUNCH;
     }
     attr_once.ok();
   }
   const int k16s = (int)mud_cdiv(a.Cin, 16), ntiles = (int)mud_cdiv(a.Cout, CM_BN * WN);
-  const int lds = G::lds_bytes((PRO == MUD_PRO_AFFINE || PRO == MUD_PRO_AFFINE_SILU) ? a.Cin : 0);   // scale | shift arrays of the sample: always in LDS
+  const int lds = G::lds_bytes((PRO == MUD_PRO_AFFINE || PRO == MUD_PRO_AFFINE_SILU || PRO == MUD_PRO_UP2_AFFINE_SILU) ? a.Cin : 0) + up_bytes;   // scale | shift arrays of the sample: always in LDS
   int tiles_x = 1;
   int64_t tiles;
   if (KS == 3) {
@@ -1483,6 +1595,7 @@ static int cm_launch_pro(const mud_conv_args& a, hipStream_t s) {
     if ((!DUAL || in_launch) && a.splitk_ws && mud_aligned16(a.splitk_ws) && cm_split_eligible(a)) ns = cm_splits(nblocks, k16s);
     if (ns > 1 && a.splitk_ws_bytes < cm_slab_bytes(ns, nblocks, 64 * WM * WN * 32 * MT * (DUAL ? 2 : 1))) ns = 1;      // workspace too small: run unsplit
     MUD_REQUIRE(ns == 1 || !a.res_up2, "mud_conv2d_mfma: res_up2 is not built for a launch split over K (ask mud_conv2d_mfma_res_up2_supported first)");
+    MUD_REQUIRE(ns == 1 || !a.in_up2, "mud_conv2d_mfma: in_up2 is not built for a launch split over K (ask mud_conv2d_mfma_in_up2_supported first)");
     if (ns > 1) {
       mud_conv_args p = a;                       // raw partial sums: no epilogue terms, output = slab ksi of the workspace
       p.out = (float*)a.splitk_ws;
@@ -1590,6 +1703,24 @@ extern "C" int mud_conv2d_mfma_res_up2_supported(const mud_conv_args* ap) {
   return cm_splits(blocks, (int)mud_cdiv(ap->Cin, 16)) == 1;      // (whatever workspace the caller has: a launch that may split is left alone)
 }
 
+// in_up2 (MUD_PRO_UP2_AFFINE_SILU) is built for two tiles: 8 x 32 px x 128 ch on eight waves under every plan (the up-sampling
+// residual blocks' Conv_0 at 256x256 / 128x128 once the batch fills the chip) and 4 x 32 px x 64 ch on four waves under the two
+// fp16 plans (small grids; MUD_PREC_FP8X has no such tile).  Any other tile keeps the FIR launch in front of the convolution.
+static bool cm_in_up2_built(int variant, int prec) {
+  if (variant == CMV_8X2) return prec == MUD_PREC_16X3 || prec == MUD_PREC_FP8X || prec == MUD_PREC_16X1;
+  return variant == CMV_MT1 && (prec == MUD_PREC_16X3 || prec == MUD_PREC_16X1);
+}
+// H, W: the OUTPUT size (twice the size of x).  Like res_up2: the 3x3 kernel, no sub2, no fused skip conv, no split-K.
+extern "C" int mud_conv2d_mfma_in_up2_supported(const mud_conv_args* ap) {
+  if (!ap || ap->ks != 3 || ap->stride != 1 || ap->pad != 1 || ap->sub2 || ap->skip_w || ap->res_up2 || ap->pro_mode != MUD_PRO_AFFINE_SILU) return 0;
+  if (ap->B <= 0 || ap->H <= 0 || ap->W <= 0 || ap->Cin <= 0 || ap->Cout <= 0 || (ap->H & 1) || (ap->W & 1)) return 0;
+  static const bool forced_tile = getenv("MUD_CONV_MT") != nullptr;             // (the tuning knob picks tiles this form may not have)
+  if (forced_tile) return 0;
+  int64_t blocks = 0;
+  const int v = cm_variant3(*ap, &blocks);
+  return cm_in_up2_built(v, ap->prec) && cm_splits(blocks, (int)mud_cdiv(ap->Cin, 16)) == 1;
+}
+
 // MUD_PREC_FP8X is built for the 8-wave tiles (8 x 32 px x 128 ch, 16 x 32 px x 64 ch, and the one-row 8 x 32 px x 64 ch tile of the
 // 64 -> 64 layers), i.e. for launches that fill the chip, with the prologues the generators use there (none: G2's gate / fusion
 // convolutions; AdaGN + SiLU: the residual blocks, with or without the fused skip conv - whose own centre-tap products stay 16-bit x 3).
@@ -1656,11 +1787,26 @@ extern "C" int mud_conv2d_mfma(const mud_conv_args* ap, void* stream) {
     MUD_REQUIRE((int64_t)(a.H / 2) * (a.W / 2) * a.ldr < 0x7fffffffLL, "mud_conv2d_mfma: res_up2: one low-resolution image must stay below 2^31 elements");
   }
   MUD_REQUIRE(a.prec == MUD_PREC_16X3 || a.prec == MUD_PREC_FP8X || a.prec == MUD_PREC_16X1, "mud_conv2d_mfma: unknown arithmetic plan prec=%d", a.prec);
+  if (a.in_up2) {
+    MUD_REQUIRE(a.ks == 3 && !a.sub2 && !a.skip_w && !a.res_up2 && (a.H & 1) == 0 && (a.W & 1) == 0 && a.pro_mode == MUD_PRO_AFFINE_SILU,
+                "mud_conv2d_mfma: in_up2 needs ks == 3, the AFFINE_SILU prologue, no sub2 / fused skip conv / res_up2 and even H, W (ks=%d H=%d W=%d sub2=%d pro_mode=%d)",
+                a.ks, a.H, a.W, a.sub2, a.pro_mode);
+    MUD_REQUIRE(cm_in_up2_built(cm_variant3(a, nullptr), a.prec),
+                "mud_conv2d_mfma: in_up2 is not built for the tile / arithmetic plan of this launch (prec=%d; ask mud_conv2d_mfma_in_up2_supported first)", a.prec);
+  }
   MUD_REQUIRE(a.prec != MUD_PREC_16X1 || a.ks == 3, "mud_conv2d_mfma: MUD_PREC_16X1 is built for ks == 3 only (got ks=%d)", a.ks);
   MUD_REQUIRE(a.prec != MUD_PREC_FP8X || (cm_fp8x_built(a) && a.w_exp >= -100 && a.w_exp <= 100),
               "mud_conv2d_mfma: MUD_PREC_FP8X is not built for this launch (ask mud_conv2d_mfma_prec_supported first; the weights were packed for it and cannot be read by another plan)");
   if (a.B == 0) return MUD_OK;
   hipStream_t s = (hipStream_t)stream;
+  if (a.in_up2) {                                // (tile and plan checked above: cm_in_up2_built)
+    constexpr int PU = MUD_PRO_UP2_AFFINE_SILU;
+    if (cm_variant3(a, nullptr) == CMV_8X2)
+      return a.prec == MUD_PREC_FP8X   ? cm_launch_pro<3, 2, 4, 2, PU, false, MUD_PREC_FP8X>(a, s)
+             : a.prec == MUD_PREC_16X1 ? cm_launch_pro<3, 2, 4, 2, PU, false, MUD_PREC_16X1>(a, s)
+                                       : cm_launch_pro<3, 2, 4, 2, PU>(a, s);
+    return a.prec == MUD_PREC_16X1 ? cm_launch_pro<3, 1, 4, 1, PU, false, MUD_PREC_16X1>(a, s) : cm_launch_pro<3, 1, 4, 1, PU>(a, s);
+  }
 #ifdef MUD_EXPERIMENT_WS      // scripts/build_variants.py ws:-DMUD_EXPERIMENT_WS (csrc/experiments/conv_ws.inc); never in the shipped build
   if (cm_ws_wanted(a)) return cm_ws_dispatch(a, s);
 #endif

@@ -83,6 +83,11 @@ class View:
         """The viewed region as a (possibly non-contiguous) torch tensor [B,H,W,C]."""
         return self.base.reshape(self.B, self.H, self.W, self.ld)[..., self.c0:self.c0 + self.C]
 
+    def up2_shape(self):
+        """This view with H and W doubled, for size queries only: the shape a launch that up-samples it on the way in runs at
+        (conv(in_up2=...))."""
+        return View(self.base, self.B, 2 * self.H, 2 * self.W, self.C, self.ld, self.c0)
+
     def slice(self, c0, C_):
         assert 0 <= c0 and c0 + C_ <= self.C
         return View(self.base, self.B, self.H, self.W, C_, self.ld, self.c0 + c0, self.stats)
@@ -417,6 +422,20 @@ def res_up2_ok(B, H, W, cin, cout):
     return bool(load().mud_conv2d_mfma_res_up2_supported(C.byref(a)))
 
 
+IN_UP2 = os.environ.get('MUD_IN_UP2', '1') != '0'       # A/B knob: 0 = the up blocks' Conv_0 reads a tensor that a FIR launch of its own up-sampled
+
+
+def in_up2_ok(B, H, W, cin, cout, prec=PREC_16X3):
+    """Does a 3x3 mud_conv2d_mfma launch with OUTPUT size [B,H,W,cout] under plan `prec` take its input [B,H/2,W/2,cin] up-sampled
+    while it is staged (mud_conv2d_mfma_in_up2_supported: the AdaGN + SiLU prologue, even H and W, a tile and plan the form is built
+    for, a grid that is not split over K)?  Independent of RES_UP2."""
+    if not IN_UP2 or cin % 4 or cout % 4:
+        return False
+    a = ConvArgs()
+    a.B, a.H, a.W, a.Cin, a.ldx, a.ks, a.stride, a.pad, a.Cout, a.ldo, a.pro_mode, a.prec = B, H, W, cin, cin, 3, 1, 1, cout, cout, PRO_AFFINE_SILU, prec
+    return bool(load().mud_conv2d_mfma_in_up2_supported(C.byref(a)))
+
+
 def resolve_pro(pro):
     """(scale, shift, mode) with the arrays materialised (for consumers that cannot fold the GroupNorm finalisation)."""
     if pro is not None and isinstance(pro[0], LazyGN):
@@ -544,14 +563,21 @@ RECORD = None         # the active precision.launch_record() list, or None: ever
 
 def conv(x: View, w, ks, Cout, *, mfma, stride=1, pad=None, pro=None, bias=None, bias2=None, res: View = None,
          out_scale=1.0, act=ACT_NONE, out: View = None, w_bstride=0, arena=None, sub2=False, emul: View = None, gate=None, emul_cout=0,
-         skip=None, prec=PREC_16X3, w_exp=0, layer=None, res_up2=None, split_k=True):
+         skip=None, prec=PREC_16X3, w_exp=0, layer=None, res_up2=None, split_k=True, in_up2=None):
     """One fused convolution launch.  pro = (scale [B,Cin], shift [B,Cin], mode).
     skip = (packed 1x1 weights, bias or None, out View): the same launch also writes the 1x1 convolution of the RAW input
     (the residual block's Conv_2) - see fused_skip_ok().  prec / w_exp: the arithmetic plan `w` was packed for.
     layer: the launch's layer name in a launch record (precision.launch_record).
     res_up2 = the four 1-D taps of a separable 4x4 x2 up-sampling filter (up2_taps): `res` is then the LOW-resolution view
     [B,Ho/2,Wo/2,Cout] and the launch up-samples it while loading it (mud_conv_args.res_up2; see res_up2_ok).
-    split_k=False: hand the launch no split-K workspace, so a small grid runs unsplit (a res_up2 launch never gets one)."""
+    split_k=False: hand the launch no split-K workspace, so a small grid runs unsplit (a res_up2 launch never gets one).
+    in_up2 = the four 1-D taps of such a filter: `x` is then the LOW-resolution view [B,Ho/2,Wo/2,Cin], `pro` the AdaGN + SiLU
+    prologue of that view, and the launch convolves FIR x2 (silu(affine(x))), formed while x is staged (mud_conv_args.in_up2; see
+    in_up2_ok).  The launch is recorded, and its plan chosen, at the size it runs at: [B,Ho,Wo,Cin]."""
+    if in_up2 is not None:
+        assert mfma and ks == 3 and stride == 1 and not sub2 and skip is None and res_up2 is None and len(in_up2) == 4
+        assert pro is not None and pro[2] == PRO_AFFINE_SILU
+        x_lo, x = x, x.up2_shape()                # (sizes below are the launch's; the pointer and the statistics are the low-resolution view's)
     if RECORD is not None:
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError('precision.launch_record() is eager only: the launch is being captured into a graph')
@@ -601,6 +627,8 @@ def conv(x: View, w, ks, Cout, *, mfma, stride=1, pad=None, pro=None, bias=None,
         else:
             assert (res.B, res.H, res.W, res.C) == (x.B, Ho, Wo, Cout)
         a.res, a.ldr = res.ptr, res.ld
+    if in_up2 is not None:
+        a.in_up2, a.in_k = 1, (C.c_float * 4)(*in_up2)
     a.out_scale, a.act = out_scale, act
     a.sub2 = 1 if sub2 else 0
     if emul is not None:          # v *= emul (on the first emul_cout output channels only, when given)
@@ -620,8 +648,8 @@ def conv(x: View, w, ks, Cout, *, mfma, stride=1, pad=None, pro=None, bias=None,
         assert mfma and ks == 3 and res is None and (so.B, so.H, so.W, so.C) == (x.B, Ho, Wo, Cout)
         a.skip_w, a.skip_bias, a.skip_out, a.skip_ldo = ptr(sw), ptr(sb), so.ptr, so.ld
         skip_flops = 2.0 * x.B * Ho * Wo * Cout * x.C
-    if mfma and ks == 3 and split_k and res_up2 is None:      # small grids (one slice at a time): split-K slabs, stream-ordered scratch (graph-capture safe);
-                                                   # a launch that up-samples its residual is never split (no workspace: it runs unsplit)
+    if mfma and ks == 3 and split_k and res_up2 is None and in_up2 is None:      # small grids (one slice at a time): split-K slabs, stream-ordered scratch (graph-capture safe);
+                                                   # a launch that up-samples its residual or its input is never split (no workspace: it runs unsplit)
         cnt = splitk_counters(x.device)
         a.splitk_counters, a.splitk_ncounters = ptr(cnt), cnt.numel()
         nws = lib.mud_conv2d_mfma_splitk_bytes(C.byref(a))
@@ -631,7 +659,7 @@ def conv(x: View, w, ks, Cout, *, mfma, stride=1, pad=None, pro=None, bias=None,
     fn = lib.mud_conv2d_mfma if mfma else lib.mud_conv2d_direct
     name = (f'conv_mfma_k{ks}' if mfma else f'conv_direct_k{ks}') + {PREC_FP8X: '_fp8x', PREC_16X1: '_fp16'}.get(prec, '')
     flops = 2.0 * x.B * Ho * Wo * Cout * x.C * ks * ks + skip_flops     # algorithmic (sub2 issues 4x this)
-    nbytes = 4.0 * (x.npix * x.C + out.npix * Cout * ((2 if res is not None else 1) + (1 if skip is not None else 0))) + (w.numel() * w.element_size() if w_bstride == 0 else x.B * w_bstride)
+    nbytes = 4.0 * ((x_lo if in_up2 is not None else x).npix * x.C + out.npix * Cout * ((2 if res is not None else 1) + (1 if skip is not None else 0))) + (w.numel() * w.element_size() if w_bstride == 0 else x.B * w_bstride)
     _launch(name, x.device, fn, C.byref(a), STREAM, flops=flops, nbytes=nbytes)
     return out
 
