@@ -356,8 +356,8 @@ int mud_lpips_u8(const uint8_t* pred, const uint8_t* gt, int n, int H, int W, co
  * Philox4x64-10 (numpy.random.Philox's algorithm and word order) with key (seed, 0x4D55444946460001) and counter
  * (e/4, s, (j << 32) | (step << 8) | kind, 0); lane l = e % 4 takes the word pair (w[2(l/2)], w[2(l/2)+1]) = (wa, wb),
  * u1 = ((wa >> 11) + 1) 2^-53, u2 = (wb >> 11) 2^-53, r = sqrt(-2 log u1), theta = 2 pi u2: r cos theta (even l), r sin theta (odd l),
- * in fp64, rounded once to fp32.  kind: 0 x_init, 1 z, 2 posterior noise, or 5 / 6 / 7: the draws of mud_kspace_constrain /
- * mud_slab_constrain / mud_slab_kspace_constrain, so that a caller can inject what those entries draw (3 and 4, mud_known_constrain's,
+ * in fp64, rounded once to fp32.  kind: 0 x_init, 1 z, 2 posterior noise, or 5 / 6 / 7 / 8: the draws of mud_kspace_constrain /
+ * mud_slab_constrain / mud_slab_kspace_constrain / mud_band_constrain, so that a caller can inject what those entries draw (3 and 4, mud_known_constrain's,
  * stay refused); step in
  * [0, 2^24); row_len > 0.
  * mud_ensemble_stats: samples [n][N][hw] -> mean, std [n][hw] (N >= 2, hw > 0): y = clamp(x*scale + shift, lo, hi) in fp32 (each step
@@ -521,6 +521,53 @@ int mud_slab_kspace_constrain(const float* x_new, const float* y, const uint8_t*
                               const float* weights, const float* gains, int groups, int L, const float* noise, const int64_t* keys,
                               uint64_t seed, int step, int kind, const int64_t* t, int toff, const float* a_tab, const float* s_tab,
                               int ntab, int clean, float* out, float* work, int rows, int S, void* stream);
+
+/* ---- sampling a target given as a thick-slice volume of its own geometry (mudiff_hip.thick_volume; GraphSampler.sample_lockstep,
+ *      DESIGN.md section 5.29).  Thick slice j of m is a weighted average of thin slices of a stack of n, y_j = sum_i A_ji k_i per
+ * element; thick slices may cut thin slices in fractions and overlap, so G = A A^T is banded (bandwidth bw) and symmetric positive
+ * definite.  The tables (struct mud_band_tables) are built by the caller in fp64, rounded once and kept in DEVICE memory: the CSR of A
+ * by thick slice (start int32 [m + 1], member int32 [nnz] = thin index, w fp32 [nnz]), the CSR of A^T by thin slice (tstart int32
+ * [n + 1], tmember int32 [nnz] = thick index ascending, tw fp32 [nnz]) and the banded Cholesky factor of G, lc fp32 [m][bw + 1] with
+ * lc[j][0] = 1 / L[j][j] and lc[j][k] = L[j][j - k].  A set is one sample's whole stack: x, noise, out are [sets][n][row_len], keys
+ * [sets * n][2], t [sets * n], y [m][row_len] (shared by the sets), work [sets][m][row_len] (the caller's, overwritten).
+ * mud_band_constrain: with c = clamp(t[first row of the set] + toff, 0, ntab - 1), a = a_tab[c], s = s_tab[c] (clean != 0: a = 1, s = 0,
+ * nothing drawn), per element of a set
+ *   forward,  j = 0..m-1:  r_j = sum_s w_js (x[member_js] - s * eta[member_js]) - a * y_j,   v_j = (r_j - sum_{k=1..bw} lc[j][k] v_{j-k}) * lc[j][0]
+ *   backward, j = m-1..0:  u_j = (v_j - sum_{k=1..bw} lc[j+k][k] u_{j+k}) * lc[j][0]
+ *   scatter,  every i:     c = sum_j tw_ji u_j,   out_i = (c == 0 ? x_i : x_i - c)
+ * in fp32, every product and sum rounded once (no contraction), every sum from 0 in the table's order (k ascending): the orthogonal
+ * projection x - A^T G^-1 (A (x - s eta) - a y).  A thin slice under no thick slice is copied bit for bit (nothing when out is x, which
+ * is allowed).  eta is `noise` when given, else the value mud_randn_keyed gives element e of the row keyed keys[2r..2r+1] under (seed,
+ * step, kind), drawn by the thread that owns elements 4b..4b+3 of the set's column (Philox block b of each row); kind in [0, 15]
+ * (mudiff_hip.ops.KIND_BAND = 8 is this entry's), step in [0, 2^24).  One thread owns 4 consecutive elements of one set's whole column;
+ * grid (ceil(row_len / 4 / 256), sets); 16-byte accesses when row_len % 4 == 0 and x, y, noise, out, work are 16-byte aligned, else
+ * element by element.  One launch; no atomics, no LDS, no allocation: a set's result depends on its own rows, keys and the tables alone.
+ * mud_band_measure: ax[set][j] = sum_s w_js x[set][member_js] in the same order and rounding (ax: fp32 [sets][m][row_len]).
+ * MUD_ERR_ARG before the launch for m outside [1, MUD_BAND_MAX_M], n outside [1, MUD_BAND_MAX_N], bw outside [0, min(MUD_BAND_MAX_BW,
+ * m - 1)], nnz outside [m, m * MUD_BAND_MAX_MEMBERS], sets outside [1, 65535], sets * max(m, n) * row_len >= 2^31, ntab <= 0, a kind or
+ * step out of range, a null pointer that is needed, neither noise nor keys, and a work or out that overlaps another operand (out == x
+ * excepted).  The tables' contents cannot be read on the host: the kernel skips an index outside [0, n) or [0, m).
+ * Replaces nothing in the reference (it has no measurement model); new with section 5.29. */
+#define MUD_BAND_MAX_MEMBERS 32
+#define MUD_BAND_MAX_BW 8
+#define MUD_BAND_MAX_M 256
+#define MUD_BAND_MAX_N 512
+typedef struct mud_band_tables {
+  int m, n, bw, nnz;
+  const int32_t* start;
+  const int32_t* member;
+  const float* w;
+  const int32_t* tstart;
+  const int32_t* tmember;
+  const float* tw;
+  const float* lc;
+} mud_band_tables;
+/* mud_band_constrain: new (no counterpart in the reference) */
+int mud_band_constrain(const float* x, const float* y, const mud_band_tables* tab, const float* noise, const int64_t* keys, uint64_t seed, int step,
+                       int kind, const int64_t* t, int toff, const float* a_tab, const float* s_tab, int ntab, int clean, float* out, float* work,
+                       int sets, int64_t row_len, void* stream);
+/* mud_band_measure: new (no counterpart in the reference) */
+int mud_band_measure(const float* x, const mud_band_tables* tab, float* ax, int sets, int64_t row_len, void* stream);
 
 /* ---- through-plane roughness of a volume (mudiff_hip.volume_through_plane; the volume pipeline's --through_plane).
  * vol (fp32) and the optional mask (uint8, may be NULL: every voxel is inside; else non-zero is inside) are [Z, X, Y] with planes

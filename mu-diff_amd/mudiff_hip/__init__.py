@@ -91,6 +91,13 @@ class VolumeCensusRecord(C.Structure):
                 ('window', (C.c_float * VI_WINDOW) * VI_MAX_RANKS)]
 
 
+class BandTables(C.Structure):
+    """struct mud_band_tables (include/mudiff_hip.h): the pointers are device addresses."""
+    _fields_ = [('m', C.c_int), ('n', C.c_int), ('bw', C.c_int), ('nnz', C.c_int),
+                ('start', C.c_void_p), ('member', C.c_void_p), ('w', C.c_void_p),
+                ('tstart', C.c_void_p), ('tmember', C.c_void_p), ('tw', C.c_void_p), ('lc', C.c_void_p)]
+
+
 _P, _I, _L, _F, _D = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 _SIGNATURES = {
     'mud_version': (C.c_int, []),
@@ -155,6 +162,8 @@ _SIGNATURES = {
     'mud_slab_average': (_I, [_P, _P, _P, _I, _I, _P, _I, _L, _P]),
     'mud_slab_kspace_constrain': (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _P, _P, C.c_uint64, _I, _I, _P, _I, _P, _P, _I, _I, _P, _P, _I, _I,
                                         _P]),
+    'mud_band_constrain': (_I, [_P, _P, C.POINTER(BandTables), _P, _P, C.c_uint64, _I, _I, _P, _I, _P, _P, _I, _I, _P, _P, _I, _L, _P]),
+    'mud_band_measure': (_I, [_P, C.POINTER(BandTables), _P, _I, _L, _P]),
     'mud_volume_through_plane': (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _L, _P]),
     'mud_volume_census_ws_bytes': (_L, []),
     'mud_volume_census': (_I, [_P, _I, _I, _I, _I, _F, _F, C.POINTER(C.c_double), _I, _P, _P, _L, _P]),

@@ -254,8 +254,15 @@ def run(args, subjects, predict=None):
                                  for m, vol in zip(needed, conds)]
                         torch.cuda.synchronize(device)
                     report.add_evaluation(resampled, found)
-                    sargs.known_inputs = None
-                    if subject.known:                              # (the subject's --known_volume: mudiff_hip.known_region)
+                    sargs.known_inputs = sargs.thick_inputs = None
+                    if getattr(args, 'known_thick_volume', None) is not None:      # (the subject's Y: mudiff_hip.thick_volume)
+                        from . import thick_volume as TV
+                        sargs.known_thick_volume = subject.known if args.known_thick_volume == TV.MANIFEST else args.known_thick_volume
+                        if not sargs.known_thick_volume:
+                            raise ValueError(f'--known_thick_volume {TV.MANIFEST}: the manifest names no `known` file for this subject')
+                        thick = TV.options_from(sargs)
+                        sargs.thick_inputs = TV.on_grid(raws[0], TV.read_input(thick, options), thick, options, gpu, align=found.get('align'))
+                    elif subject.known:                            # (the subject's --known_volume: mudiff_hip.known_region)
                         from . import known_region as KR
                         sargs.known_volume, sargs.known_mask = subject.known, subject.known_mask
                         known = {module: module.options_from(sargs) for module in V.known_modes()}[KR]      # (each mode's own refusals;

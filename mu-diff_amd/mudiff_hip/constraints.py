@@ -6,7 +6,11 @@ A *prediction-level* constraint (Constraint: KnownVoxels here, kspace.KSpaceMeas
 multislice.MultisliceMeasurement) describes the n slices one prediction samples; volume.predict_slices and ensemble.sample_ensemble form
 their batches from it and know nothing else of it.  Its for_rows gives the *batch-level* constraint of one captured batch (KnownRows,
 KSpaceRows, SlabRows, SlabKSpaceRows): `check(sampler)`, once, and `apply(sampler, x_new, keys_dev, seed, step, clean)`, one unchecked
-launch into sampler.x per executed step, for GraphSampler.sample_keyed."""
+launch into sampler.x per executed step, for GraphSampler.sample_keyed.
+
+A constraint that couples the whole stack along z (thick_volume.BandMeasurement, --known_thick_volume; section 5.29) has no batch-level
+form: it declares `lockstep` and the samplers hand it the whole state of the prediction after every step
+(GraphSampler.sample_lockstep)."""
 from __future__ import annotations
 
 import collections
@@ -43,6 +47,12 @@ class Constraint:
     (volume._measurement_outputs) also declares `tag` (its log tag and its report's file name; `finish()` is the report), `baseline()`
     (None, or (file name stem, [n,S,S] map in [-1,1] terms): what one would have without the model) and `baseline_through_plane`."""
     n, resample, tag, baseline_through_plane = None, 1, None, False
+    # True: the constraint couples the whole stack along z, so no batch can hold what it couples.  The samplers then advance every
+    # (slice, sample) of the prediction one reverse step and constrain them all at once (GraphSampler.sample_lockstep, DESIGN.md
+    # section 5.29) through `check_volume(sampler, rows)`, once, `apply_volume(sampler, x_new, x, keys_dev, seed, step, clean)`, one
+    # launch over the [rows,1,S,S] state x_new -> x per executed step (rows sample-major: row j n + i is slice i of sample j; the
+    # rows' levels: sampler.t_rows), and `record_volume(x, x_new)` for what the sampler returned.
+    lockstep = False
 
     def done_suffix(self):
         return ''                            # what a [done] line gains

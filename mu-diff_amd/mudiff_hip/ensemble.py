@@ -64,7 +64,9 @@ def sample_ensemble(args, gen1, gen2, conds, num_samples, seed, batch_size=32, s
     GraphSampler.sample_keyed takes; or `constraint`, any of them as one object of mudiff_hip.constraints (its own `resample` counts).
     Every sample of slice i is drawn under it and handed to its `record`.  Thick slices couple the L thin slices of a (slab, sample), so
     a measured slab's items run sample-major - each sample's L slices together, never split over two batches (constraints.batches) -
-    and a chunk ends before a slab it would cut (the constraint's `chunk_end`).  Free slices keep their item order."""
+    and a chunk ends before a slab it would cut (the constraint's `chunk_end`).  Free slices keep their item order.  A constraint that couples the whole stack
+    (`lockstep`: thick_volume.BandMeasurement, section 5.29) makes the whole n one chunk and every item advance together
+    (GraphSampler.sample_lockstep): ValueError naming --num_samples when 2 N n S^2 x 4 bytes exceed the free device memory."""
     from . import sampling as S
     from .constraints import batches, of_prediction
     constraint, resample = of_prediction('sample_ensemble', constraint, known, kspace, thick, resample)
@@ -100,6 +102,13 @@ def sample_ensemble(args, gen1, gen2, conds, num_samples, seed, batch_size=32, s
     qmaps = None if quantiles is None else torch.empty(len(quantiles), n, size, size, device=device, dtype=torch.float32)
     buf = None
     constraint.over(n, 'sample_ensemble')
+    if constraint.lockstep:                  # the constraint couples the whole stack: all N n items advance together (section 5.29)
+        out = _sample_lockstep(sampler, conds, constraint, N, n, size, seed, T, int(slice_offset), coupling, resample, every)
+        mean[:], std[:] = ops.ensemble_stats(out, scale, shift, lo, hi)
+        if qmaps is not None:
+            qmaps[:] = ops.ensemble_quantiles(out, quantiles, scale, shift, lo, hi)
+        res = (mean, std, every) if return_samples else (mean, std)
+        return res if qmaps is None else res + (qmaps,)
     chunks, s0 = [], 0
     while s0 < n:
         s1 = constraint.chunk_end(s0, min(s0 + chunk, n))
@@ -132,6 +141,31 @@ def sample_ensemble(args, gen1, gen2, conds, num_samples, seed, batch_size=32, s
             qmaps[:, s0:s1] = ops.ensemble_quantiles(out, quantiles, scale, shift, lo, hi)
     res = (mean, std, every) if return_samples else (mean, std)
     return res if qmaps is None else res + (qmaps,)
+
+
+def lockstep_bytes(N, n, size, m=0):
+    """What GraphSampler.sample_lockstep holds for N samples of n slices: the state and the steps' results, 2 N n S^2 x 4 bytes, and the
+    constraint's workspace of m rows per sample."""
+    return (2 * N * n + N * m) * size * size * 4
+
+
+def _sample_lockstep(sampler, conds, constraint, N, n, size, seed, T, slice_offset, coupling, resample, every):
+    """sample_ensemble under a constraint that couples the whole stack: rows sample-major (row j n + i: slice i of sample j), one
+    GraphSampler.sample_lockstep over them, -> the samples [n,N,S,S] (into `every` when given).  The memory is counted first."""
+    device = conds[0].device
+    need = lockstep_bytes(N, n, size, getattr(constraint, 'm', 0))
+    free = torch.cuda.mem_get_info(device)[0]
+    if need > free:
+        raise ValueError(f'sample_ensemble: a constraint over the whole stack keeps all {N} x {n} samples on the device, {need / 2 ** 30:.2f} GiB '
+                         f'with {free / 2 ** 30:.2f} GiB free: lower --num_samples')
+    sl = torch.arange(n, dtype=torch.int64).repeat(N)
+    sm = torch.arange(N, dtype=torch.int64).repeat_interleave(n)
+    keys = torch.stack([sl + slice_offset, sm], 1)
+    X = sampler.sample_lockstep(conds, keys, seed, T, constraint=constraint, coupling=coupling, resample=resample, cond_index=sl)
+    constraint.record_volume(X, sampler.lockstep_x_new)
+    out = every if every is not None else torch.empty(n, N, size, size, device=device, dtype=torch.float32)
+    out.copy_(X.view(N, n, size, size).transpose(0, 1))
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------

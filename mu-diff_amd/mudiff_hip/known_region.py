@@ -79,7 +79,9 @@ def options_from(args):
     if volume is None:
         if getattr(args, 'manifest', None) is not None or getattr(args, 'brats_root', None) is not None:
             return None                                   # a cohort: K comes from the manifest, per subject; the other flags from here
-        for flag, given in (('--known_mask', mask is not None), ('--known_drop_slices', drop is not None), ('--known_resample', resample != 1)):
+        thick_volume = getattr(args, 'known_thick_volume', None) is not None      # (mudiff_hip.thick_volume takes --known_resample too)
+        for flag, given in (('--known_mask', mask is not None), ('--known_drop_slices', drop is not None),
+                            ('--known_resample', resample != 1 and not thick_volume)):
             if given:
                 raise ValueError(f'{flag} needs --known_volume')
         return None

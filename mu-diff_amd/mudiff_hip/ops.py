@@ -969,8 +969,8 @@ def randn_keyed(rows_keys, row_len, seed, step, kind, out=None):
     """Keyed standard normals: row r of the fp32 result [rows, row_len] is a pure function of (seed, slice, sample, step, kind) with
     rows_keys[r] = (slice, sample) (int64 [rows, 2], host or device): Philox4x64-10 + Box-Muller in fp64 (mud_randn_keyed).  `out`:
     a contiguous fp32 device tensor of rows * row_len elements to fill (any shape); without it the result lands on rows_keys's device
-    (or the current one for host keys).  kind: KIND_X_INIT, KIND_Z or KIND_NOISE (or KIND_KSPACE / KIND_THICK / KIND_MULTISLICE, to
-    inject what ops.kspace_constrain / ops.slab_constrain / ops.slab_kspace_constrain draw)."""
+    (or the current one for host keys).  kind: KIND_X_INIT, KIND_Z or KIND_NOISE (or KIND_KSPACE / KIND_THICK / KIND_MULTISLICE /
+    KIND_BAND, to inject what ops.kspace_constrain / ops.slab_constrain / ops.slab_kspace_constrain / ops.band_constrain draw)."""
     k = check_keys(rows_keys)
     seed = _seed64(seed)
     rows, row_len = k.shape[0], int(row_len)
@@ -1347,6 +1347,161 @@ def slab_kspace_constrain(x_new, y, mask, members, weights, t, toff, a_tab, s_ta
     out = torch.empty(x_new.shape, device=x_new.device, dtype=torch.float32) if out is None else out
     work = torch.empty(groups, S, S, device=x_new.device, dtype=torch.complex64) if work is None else work
     return slab_kspace_constrain_into(out, x_new, y, mask, tables, work, kd, _seed64(seed), step, kind, t, toff, a_tab, s_tab, clean, noise)
+
+
+# ---------------------------------------------------------------------------------------------------
+# sampling a target given as a thick-slice volume of its own geometry (csrc/band.hip, mudiff_hip.thick_volume)
+KIND_BAND = 8                        # the draw of mud_band_constrain: the thick slices' forward noise
+BAND_MAX_MEMBERS, BAND_MAX_BW, BAND_MAX_M, BAND_MAX_N = 32, 8, 256, 512      # include/mudiff_hip.h: MUD_BAND_MAX_*
+BAND_MAX_COND = 1e4                  # cond(A A^T) <= 1e4: 1e4 * 2^-24 ~ 6e-4 keeps the fp32 solve inside the 1e-3 parity bar
+
+
+class BandTables:
+    """The tables of mud_band_constrain / mud_band_measure for a measurement matrix A [m, n] (band_tables): numpy arrays `start`,
+    `member`, `w` (the CSR of A by thick slice), `tstart`, `tmember`, `tw` (of A^T by thin slice), `lc` [m, bw + 1] (the banded Cholesky
+    factor of G = A A^T, lc[j, 0] = 1 / L[j, j], lc[j, k] = L[j, j - k]), and m, n, bw, nnz, cond (of G, fp64).  `A32` is A as the kernel
+    sees it, the fp32 weights in fp64.  `on(device)` uploads them once per device -> the struct the entries take."""
+
+    def __init__(self, m, n, bw, start, member, w, tstart, tmember, tw, lc, cond, A32):
+        self.m, self.n, self.bw, self.nnz, self.cond, self.A32 = int(m), int(n), int(bw), int(member.shape[0]), float(cond), A32
+        self.start, self.member, self.w, self.tstart, self.tmember, self.tw, self.lc = start, member, w, tstart, tmember, tw, lc
+        self._dev = {}
+
+    def on(self, device):
+        device = torch.device(device)
+        key = (device.type, torch.cuda.current_device() if device.index is None else device.index)
+        if key not in self._dev:
+            from . import BandTables as Struct
+            t = [torch.from_numpy(a).to(device) for a in (self.start, self.member, self.w, self.tstart, self.tmember, self.tw, self.lc.reshape(-1))]
+            self._dev[key] = (Struct(self.m, self.n, self.bw, self.nnz, *(v.data_ptr() for v in t)), t)      # t: keeps the memory alive
+        return self._dev[key][0]
+
+
+def band_tables(A):
+    """A: the measurement matrix of thick slices, dense fp64 [m, n] or CSR as (start [m + 1], member [nnz], w [nnz], n) -> BandTables.
+    Row j's non-zeros become its members in thin-slice order; the weights are rounded once to fp32, and G = A A^T, its bandwidth, its
+    fp64 eigenvalues and its Cholesky factor are those of the rounded weights.  ValueError for m > 256, n > 512, a row with no member or
+    more than 32, a bandwidth above 8, a weight that is not finite, and for cond(G) > 1e4 (or a G that is not positive definite: two
+    coincident thick slices)."""
+    if isinstance(A, (tuple, list)) and len(A) == 4:
+        st, mem, ww, n = A
+        st, mem, ww = np.asarray(st, np.int64), np.asarray(mem, np.int64), np.asarray(ww, np.float64)
+        if st.ndim != 1 or st.shape[0] < 2 or st[0] != 0 or st[-1] != mem.shape[0] or mem.shape != ww.shape or np.any(np.diff(st) < 0):
+            raise ValueError('band_tables: CSR must be (start [m + 1] from 0 to nnz, member [nnz], w [nnz], n)')
+        if mem.size and (mem.min() < 0 or mem.max() >= int(n)):
+            raise ValueError(f'band_tables: a member lies outside [0, {int(n)})')
+        dense = np.zeros((st.shape[0] - 1, int(n)), np.float64)
+        for j in range(st.shape[0] - 1):
+            np.add.at(dense[j], mem[st[j]:st[j + 1]], ww[st[j]:st[j + 1]])
+        A = dense
+    A = np.asarray(A, np.float64)
+    if A.ndim != 2 or A.shape[0] < 1 or A.shape[1] < 1:
+        raise ValueError(f'band_tables: A must be [m, n], got {A.shape}')
+    m, n = A.shape
+    if m > BAND_MAX_M or n > BAND_MAX_N:
+        raise ValueError(f'band_tables: at most {BAND_MAX_M} thick and {BAND_MAX_N} thin slices, got {m} and {n}')
+    if not np.all(np.isfinite(A)):
+        raise ValueError('band_tables: A holds a weight that is not finite')
+    A32 = A.astype(np.float32).astype(np.float64)
+    counts = (A32 != 0).sum(1)
+    if counts.min() < 1 or counts.max() > BAND_MAX_MEMBERS:
+        raise ValueError(f'band_tables: a thick slice must have 1 to {BAND_MAX_MEMBERS} members, got {int(counts.min())} to {int(counts.max())}')
+    G = A32 @ A32.T
+    jj, kk = np.nonzero(G)
+    bw = int(np.abs(jj - kk).max())
+    if bw > BAND_MAX_BW:
+        raise ValueError(f'band_tables: A A^T has bandwidth {bw}, at most {BAND_MAX_BW} is supported')
+    ev = np.linalg.eigvalsh(G)
+    cond = float(ev[-1] / ev[0]) if ev[0] > 0 else math.inf
+    if not cond <= BAND_MAX_COND:
+        raise ValueError(f'band_tables: cond(A A^T) = {cond:.3g} exceeds {BAND_MAX_COND:g}: the thick slices are (nearly) dependent and the '
+                         'fp32 solve would leave the 1e-3 parity bar')
+    L = np.linalg.cholesky(G)
+    lc = np.zeros((m, bw + 1), np.float64)
+    lc[:, 0] = 1.0 / np.diag(L)
+    for k in range(1, bw + 1):
+        lc[k:, k] = np.diag(L, -k)
+    start = np.zeros(m + 1, np.int32)
+    start[1:] = np.cumsum(counts)
+    rows, cols = np.nonzero(A32)                             # row-major: thin index ascending within a thick slice
+    tcols, trows = np.nonzero(A32.T)                         # thick index ascending within a thin slice
+    tstart = np.zeros(n + 1, np.int32)
+    tstart[1:] = np.cumsum((A32 != 0).sum(0))
+    c = np.ascontiguousarray
+    return BandTables(m, n, bw, start, c(cols.astype(np.int32)), c(A32[rows, cols].astype(np.float32)), tstart, c(trows.astype(np.int32)),
+                      c(A32[trows, tcols].astype(np.float32)), c(lc.astype(np.float32)), cond, A32)
+
+
+def band_constrain_into(out, x, y, tables, work, keys_dev, seed, step, kind, t, toff, a_tab, s_tab, clean=False, noise=None):
+    """Unchecked launch of mud_band_constrain into `out` (fp32, contiguous, sets * n rows; may be x): GraphSampler.sample_lockstep checks
+    its operands once, not once per step.  y: fp32 [m, row_len]; tables: band_tables'; work: fp32, sets * m rows; keys_dev: through
+    check_keys and on out's device (None with `noise` or `clean`)."""
+    row_len = y.numel() // tables.m
+    sets = out.numel() // (tables.n * row_len)
+    _launch('band_constrain', out.device, load().mud_band_constrain, ptr(x), ptr(y), C.byref(tables.on(out.device)), ptr(noise), ptr(keys_dev),
+            C.c_uint64(seed), int(step), int(kind), ptr(t), int(toff), ptr(a_tab), ptr(s_tab), 1 if a_tab is None else a_tab.numel(),
+            int(bool(clean)), ptr(out), ptr(work), sets, row_len, STREAM,
+            nbytes=float(row_len * 4 * (sets * (2 * tables.nnz + 2 * tables.n + 4 * tables.m) + tables.m)))
+    return out
+
+
+def _band_shapes(name, x, tables):
+    """x: fp32 [sets, n, ...] -> (sets, row_len)."""
+    if not isinstance(tables, BandTables):
+        raise MudiffHipError(f'{name}: tables must come from ops.band_tables')
+    if x.dtype != torch.float32 or x.dim() < 3 or x.numel() < 1 or x.shape[1] != tables.n:
+        raise MudiffHipError(f'{name}: x must be a non-empty fp32 [sets, {tables.n}, ...] tensor, got {x.dtype} {tuple(x.shape)}')
+    sets, row_len = int(x.shape[0]), x[0, 0].numel()
+    if sets * max(tables.n, tables.m) * row_len >= 1 << 31 or sets > 65535:
+        raise MudiffHipError(f'{name}: sets * max(m, n) * row_len must be < 2^31 and sets <= 65535, got {sets} x {max(tables.n, tables.m)} x {row_len}')
+    return sets, row_len
+
+
+def band_constrain(x, y, tables, t, toff, a_tab, s_tab, *, noise=None, keys=None, seed=0, step=0, kind=KIND_BAND, clean=False, out=None,
+                   work=None):
+    """The data-consistency step of thick slices with a geometry of their own (mud_band_constrain).  With A = tables.A32 [m, n],
+    G = A A^T and c = clamp(t[first row of the set] + toff, 0, len(a_tab) - 1), per element of every set
+        out = x - A^T G^-1 (A (x - s_tab[c] * eta) - a_tab[c] * y)                  (clean: out = x - A^T G^-1 (A x - y)),
+    the solve by the banded Cholesky factor of the tables, so that A out is A q_sample(k, c) for y = A k and everything orthogonal to
+    the rows of A is untouched.  A thin slice under no thick slice is copied bit for bit.  x: fp32 [sets, n, ...] (a set: one sample's
+    whole stack); y: fp32 [m, ...] with x's row shape, shared by the sets.  eta: `noise` (fp32, x's shape) when given, else the keyed normal
+    ops.randn_keyed gives keys[r] = (slice, sample) of row r = set * n + i under (seed, step, kind), drawn in the kernel.  t: int64
+    [sets * n]; with `clean` it, the tables and the draw are not needed.  out: None (a new tensor), x (in place) or a contiguous fp32
+    tensor of the shape.  work: None or a contiguous fp32 workspace of sets * m rows (overwritten)."""
+    require_gpu(x, y, noise, t, a_tab, s_tab, out, work)
+    sets, row_len = _band_shapes('band_constrain', x, tables)
+    rows = sets * tables.n
+    if y is None or y.dtype != torch.float32 or y.dim() < 1 or y.shape[0] != tables.m or y.numel() != tables.m * row_len:
+        raise MudiffHipError(f'band_constrain: y must be fp32 [{tables.m}, {row_len}], got {None if y is None else (y.dtype, tuple(y.shape))}')
+    for name, v in (('noise', noise), ('out', out)):
+        if v is not None and (v.dtype != torch.float32 or v.shape != x.shape):
+            raise MudiffHipError(f'band_constrain: {name} must be fp32 of shape {tuple(x.shape)}, got {v.dtype} {tuple(v.shape)}')
+    if out is not None and not out.is_contiguous():
+        raise MudiffHipError('band_constrain: out must be contiguous')
+    if work is not None and (work.dtype != torch.float32 or work.numel() != sets * tables.m * row_len or not work.is_contiguous()):
+        raise MudiffHipError(f'band_constrain: work must be a contiguous fp32 tensor of {sets * tables.m} x {row_len} elements')
+    x = x if x.is_contiguous() or out is x else x.contiguous()
+    y = y.contiguous()
+    noise = None if noise is None else noise.contiguous()
+    t, a_tab, s_tab, kd = _level_and_keys('band_constrain', clean, t, a_tab, s_tab, noise, keys, rows, x.device)
+    out = torch.empty(x.shape, device=x.device, dtype=torch.float32) if out is None else out
+    work = torch.empty(sets * tables.m, row_len, device=x.device, dtype=torch.float32) if work is None else work
+    return band_constrain_into(out, x, y, tables, work, kd, _seed64(seed), step, kind, t, toff, a_tab, s_tab, clean, noise)
+
+
+def band_measure(x, tables, out=None):
+    """ax[set, j] = sum_s w_js x[set, member_js] per element, in mud_band_constrain's order and rounding (mud_band_measure): the
+    measurement y of k, and A x of the residual.  x: fp32 [sets, n, ...] -> fp32 [sets, m, ...]."""
+    require_gpu(x, out)
+    sets, row_len = _band_shapes('band_measure', x, tables)
+    shape = (sets, tables.m) + tuple(x.shape[2:])
+    if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous()):
+        raise MudiffHipError(f'band_measure: out must be a contiguous fp32 tensor of shape {shape}, got {out.dtype} {tuple(out.shape)}')
+    x = x if x.is_contiguous() else x.contiguous()
+    out = torch.empty(shape, device=x.device, dtype=torch.float32) if out is None else out
+    _launch('band_measure', x.device, load().mud_band_measure, ptr(x), C.byref(tables.on(x.device)), ptr(out), sets, row_len, STREAM,
+            nbytes=float(row_len * 4 * sets * (tables.nnz + tables.m)))
+    return out
 
 
 # columns of volume_through_plane's sums (include/mudiff_hip.h: MUD_TP_*)

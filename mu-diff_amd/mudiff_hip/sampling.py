@@ -319,6 +319,92 @@ class GraphSampler:
                 step += 1
         return self.x.clone()
 
+    lockstep_x_new = None   # after sample_lockstep: the last step's result [R,1,H,W] as the constraint received it
+    t_rows = None           # during sample_lockstep: the level of every row, int64 [R] (what a volume constraint's launch takes for t)
+
+    def sample_lockstep(self, conds, keys_all, seed, n_time, constraint=None, coupling=None, resample=1, cond_index=None):
+        """sample_keyed for a constraint that couples the whole stack (constraints.Constraint.lockstep): every
+        row of the prediction is advanced one reverse step, batch after batch, then the whole state is constrained at once, then the
+        next step follows.  conds: three device tensors [R,1,H,W]; keys_all: int64 [R,2], every (slice, sample) item of the prediction,
+        sample-major.  `cond_index` (int64 [R]): row r takes its conditions from conds[.][cond_index[r]] instead, so that an ensemble
+        need not repeat them per sample.  The state X and the steps' results Xnew stay on the device as [R,1,H,W].
+
+        For each executed step, for each batch of <= B rows (the last one padded by repeating its last row): the conditions and X[rows]
+        go into the static buffers (at step 0 x is drawn, kind KIND_X_INIT), z and the posterior noise are drawn with the batch's keys
+        exactly as sample_keyed draws them (`coupling` included), and the FIRST-step graph is replayed - every time: the generators'
+        loop caches hold what depends on one batch's conditions, and the later-step graph would read another batch's.  Then one
+        `constraint.apply_volume(self, Xnew, X, keys, seed, step, clean)` launch, clean at i == 0 (None: a plain copy), and under
+        `resample` > 1 sample_keyed's re-noising over the whole of X.  -> X (also kept: `lockstep_x_new`, the last Xnew)."""
+        from .slice_coupling import SHARED, check_coupling
+        coupling = check_coupling(coupling)
+        k = ops.check_keys(keys_all)
+        R, B, dev = int(k.shape[0]), self.B, self.x.device
+        if R < 1:
+            raise ValueError('GraphSampler.sample_lockstep: no rows')
+        seed = ops._seed64(seed)
+        resample = int(resample)
+        if resample < 1 or (constraint is None and resample != 1):
+            raise ValueError(f'GraphSampler.sample_lockstep: resample must be >= 1 and needs a constraint, got {resample}')
+        cidx = torch.arange(R, dtype=torch.int64) if cond_index is None else torch.as_tensor(cond_index).detach().to('cpu', torch.int64)
+        rows_c = int(conds[0].shape[0])
+        if cidx.shape != (R,) or int(cidx.min()) < 0 or int(cidx.max()) >= rows_c:
+            raise ValueError(f'GraphSampler.sample_lockstep: cond_index must be {R} rows of the conditions, each in [0, {rows_c})')
+        for c in conds:
+            if tuple(c.shape) != (rows_c, 1, self.H, self.W) or c.device != dev or c.dtype != torch.float32:
+                raise ValueError(f'GraphSampler.sample_lockstep: conditions must be fp32 [{rows_c}, 1, {self.H}, {self.W}] on {dev}, got '
+                                 f'{c.dtype} {tuple(c.shape)} on {c.device}')
+        k_true = k.to(dev)
+        if coupling == SHARED:
+            k = k.clone()
+            k[:, 0] = 0
+        kd_all = k.to(dev)
+        taps = None if coupling is None or coupling == SHARED else ops.coupling_taps_arg(*coupling)
+
+        def draw(out, kd, step, kind):
+            if taps is None:
+                ops.randn_keyed_into(out, kd, seed, step, kind)
+            else:
+                ops.randn_keyed_coupled_into(out, kd, seed, step, kind, *taps)
+
+        batches = []
+        for lo in range(0, R, B):
+            m = min(B, R - lo)
+            rows = torch.arange(lo, lo + m, dtype=torch.int64)
+            padded = torch.cat([rows, rows[-1:].expand(B - m)]) if m < B else rows
+            batches.append((rows.to(dev), padded.to(dev), cidx[padded].to(dev), kd_all.index_select(0, padded.to(dev)).contiguous(), m))
+        X = torch.empty(R, 1, self.H, self.W, device=dev, dtype=torch.float32)
+        Xnew = torch.empty_like(X)
+        self.t_rows = torch.zeros(R, dtype=torch.int64, device=dev)
+        if constraint is not None:
+            constraint.check_volume(self, R)
+            dc = self._diffusion_tables()
+        x_new = self._first_out[2]
+        step = 0                                      # the running count of executed steps: the step word of every draw
+        for i in reversed(range(n_time)):
+            self.t.fill_(i)
+            self.t_rows.fill_(i)
+            for j in range(resample):
+                for rows, padded, crow, kd, m in batches:
+                    self.c1.copy_(conds[0].index_select(0, crow)); self.c2.copy_(conds[1].index_select(0, crow))
+                    self.c3.copy_(conds[2].index_select(0, crow))
+                    if step == 0:
+                        draw(self.x, kd, 0, ops.KIND_X_INIT)
+                    else:
+                        self.x.copy_(X.index_select(0, padded))
+                    draw(self.z, kd, step, ops.KIND_Z)
+                    draw(self.noise, kd, step, ops.KIND_NOISE)
+                    self.graph.replay()
+                    Xnew.index_copy_(0, rows, x_new[:m])
+                if constraint is None:
+                    X.copy_(Xnew)
+                else:
+                    constraint.apply_volume(self, Xnew, X, k_true, seed, step, i == 0)
+                if j < resample - 1:                  # back one level, everywhere (mask None), then the same step again
+                    ops.known_constrain_into(X, None, X, None, k_true, seed, step, ops.KIND_RENOISE, self.t_rows, 1, dc[2], dc[3])
+                step += 1
+        self.lockstep_x_new = Xnew
+        return X
+
     def _diffusion_tables(self):
         """(a_s_cum, sigmas_cum, a_s, sigmas) of Diffusion_Coefficients(opt) as fp32 on this sampler's device, built once."""
         if getattr(self, '_diff', None) is None:

@@ -32,8 +32,9 @@ z through (slab centre, y_j) over the measured slabs, constant beyond the first 
 
 Scope: the retrospective model with non-overlapping profiles, K given on (or resampled onto) the thin grid and measured here - the
 protocol section 5.26 uses for k-space.  A NIfTI that is itself thick (its own slice spacing, slabs that cut thin slices in fractions,
-overlapping profiles: a banded A A^T) is out of scope.  Thick slices that are also undersampled in-plane are --known_multislice's
-(mudiff_hip.multislice, section 5.28), not this flag's with --known_kspace.  A later intake only has to fill the same ThickMeasurement.
+overlapping profiles: a banded A A^T) is --known_thick_volume's (mudiff_hip.thick_volume, section 5.29: a constraint of its own, over
+the whole stack).  Thick slices that are also undersampled in-plane are --known_multislice's (mudiff_hip.multislice, section 5.28), not
+this flag's with --known_kspace.
 """
 from __future__ import annotations
 

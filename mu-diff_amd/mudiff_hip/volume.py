@@ -312,7 +312,9 @@ def predict_slices(args, gen1, gen2, cond_stacks, device, batch_size=32, x_inits
     (--known_thick) for these n slices, with `resample` what GraphSampler.sample_keyed takes; or `constraint`, any of them as one object
     of mudiff_hip.constraints (its own `resample` counts).  The same keyed road, with the same two refusals; the batches are
     constraints.batches of the constraint's units (a slab longer than the captured batch is a ValueError naming --batch_size), and what
-    the sampler returns is handed to the constraint's `record` before the [0,1] map."""
+    the sampler returns is handed to the constraint's `record` before the [0,1] map.  A constraint that couples the whole stack
+    (`lockstep`: thick_volume.BandMeasurement, section 5.29) goes through GraphSampler.sample_lockstep instead: the same keys, the whole
+    state on the device, `record_volume` at the end."""
     from . import ops
     from . import sampling as S
     from .constraints import FREE, batches, of_prediction
@@ -359,6 +361,15 @@ def predict_slices(args, gen1, gen2, cond_stacks, device, batch_size=32, x_inits
             x_inits = torch.randn(n, 1, size, size, device=device, generator=gen)
         zs = [torch.randn(n, args.nz, device=device, generator=gen) for _ in range(T)]
         noises = [torch.randn(n, 1, size, size, device=device, generator=gen) for _ in range(T)]
+    if keyed and constraint.lockstep:        # the constraint couples the whole stack: every slice one step, then all constrained at once
+        constraint.over(n, 'predict_slices')
+        keys = torch.stack([torch.arange(n, dtype=torch.int64), torch.zeros(n, dtype=torch.int64)], 1)
+        fake = sampler.sample_lockstep(conds, keys, seed, T, constraint=constraint, coupling=coupling, resample=resample)
+        constraint.record_volume(fake, sampler.lockstep_x_new)
+        out.copy_(ops.to_range_0_1(fake)[:, 0])
+        if progress:
+            progress(n, n)
+        return out if return_device else out.cpu().numpy()
     if keyed:                                # row r of a batch is slice items[r]; a short batch is padded by its last slice
         constraint.over(n, 'predict_slices')
         done = 0
@@ -412,13 +423,16 @@ def predict_volume(args):
     (mudiff_hip.kspace, section 5.26) or --known_thick (mudiff_hip.thick, section 5.27) that volume's measured Fourier coefficients or slab
     averages condition the sampling instead, nothing is pasted, and kspace_<target>.json or thick_<target>.json (and under
     --kspace_zero_filled / --thick_interp the baseline volume) goes next to the prediction; --known_multislice (mudiff_hip.multislice,
-    section 5.28) is both at once, with multislice_<target>.json and --multislice_baseline."""
+    section 5.28) is both at once, with multislice_<target>.json and --multislice_baseline.  --known_thick_volume (mudiff_hip.thick_volume,
+    section 5.29) takes the measurement from a thick-slice file of its own geometry instead of --known_volume: the whole stack is sampled in
+    lockstep, with thick_volume_<target>.json and --thick_volume_baseline."""
     evaluation, resampled, found = _load_eval_inputs(args)
     args = copy.copy(args)                               # the run's own copy: it carries the record of what the intake did
     args.evaluation_record = (resampled, found)          # (for _predict_volume's report: IntakeReport.add_evaluation)
     args.known_inputs = _load_known_inputs(args, found)  # (--known_volume: K and M on the prediction's grid, checked, or None)
     if args.known_inputs is not None:
         args.evaluation_record = (resampled + list(args.known_inputs.resampled), found)
+    args.thick_inputs = _load_thick_inputs(args, found)  # (--known_thick_volume: Y checked against the prediction's grid, or None)
     from . import ops
     from .driver import effective_prec_plan
     plan = effective_prec_plan(args)
@@ -473,6 +487,20 @@ def _load_known_inputs(args, found):
     _, first = _needed_inputs(args)[0]
     options = VP.IntakeOptions.from_args(args)
     return KR.on_grid(VP.read_for_evaluation(first, options), KR.read_inputs(known, options), known, options,
+                      torch.device(f'cuda:{args.gpu_chose}'), align=found.get('align'))
+
+
+def _load_thick_inputs(args, found):
+    """--known_thick_volume -> None, or thick_volume.ThickInputs: the file read and its geometry checked against the grid the prediction
+    will have (thick_volume.on_grid), before any checkpoint work.  A bad flag or geometry raises ValueError here."""
+    from . import thick_volume as TV
+    options = TV.options_from(args)
+    if options is None:
+        return None
+    from . import volume_prepare as VP
+    _, first = _needed_inputs(args)[0]
+    intake = VP.IntakeOptions.from_args(args)
+    return TV.on_grid(VP.read_for_evaluation(first, intake), TV.read_input(options, intake), options, intake,
                       torch.device(f'cuda:{args.gpu_chose}'), align=found.get('align'))
 
 
@@ -636,12 +664,24 @@ def known_modes():
     return known_region, kspace, thick, multislice
 
 
+def measurement_modes():
+    """known_modes() and, after them, the mode whose measurement is a file of its own and not --known_volume measured retrospectively:
+    --known_thick_volume (mudiff_hip.thick_volume)."""
+    from . import thick_volume
+    return known_modes() + (thick_volume,)
+
+
 def _known_region(args, ref, device):
     """--known_volume: (the run's known_region.KnownRegion, or None when K is measured in k-space or in thick slices instead: nothing
     is pasted; the one constraint that predict_slices and sample_ensemble take, or None), also left in args.known_region and
     args.constraint for the [done] line, the scores and the measurement's outputs."""
     inputs = getattr(args, 'known_inputs', None)
     args.known_region = args.constraint = None
+    thick = getattr(args, 'thick_inputs', None)
+    if thick is not None:                                # --known_thick_volume: the measurement itself, nothing pasted (section 5.29)
+        from . import thick_volume as TV
+        args.constraint = TV.measure(thick, ref, int(args.image_size), args.norm, device)
+        return None, args.constraint
     if inputs is None:
         return None, None
     from . import known_region as KR
@@ -897,8 +937,8 @@ def make_parser(prog='MU-Diff volume prediction (MI355X)'):
     add_calibration_flags(p)                # (also --prec_plan)
     from . import slice_coupling
     slice_coupling.add_flags(p)             # (--slice_coupling, --through_plane: in a late parser, VolumeParser.later())
-    for module in known_modes()[1:] + known_modes()[:1]:      # (each mode's flags in a late parser of its own; --known_volume's place,
-        module.add_flags(p)                                   # before the last, is pinned, so the later modes' came before it)
+    for module in measurement_modes()[1:] + known_modes()[:1]:      # (each mode's flags in a late parser of its own; --known_volume's
+        module.add_flags(p)                                         # place, before the last, is pinned, so the later modes' came before it)
     from . import ensemble
     ensemble.add_flags(p)                   # (--ensemble_quantiles, --ensemble_center, --coverage: in a further one)
     return p
@@ -923,7 +963,7 @@ def finish_args(p, args):
         ensemble.quantile_plan(args)                     # (its ValueError names the flag)
     except ValueError as e:
         p.error(str(e))
-    for module in known_modes():
+    for module in measurement_modes():
         try:
             module.options_from(args)                    # (its ValueError names the flag)
         except ValueError as e:
@@ -955,7 +995,8 @@ def build_argparser(argv=None):
     DESIGN.md section 5.23; in a further late parser), and --ensemble_quantiles / --ensemble_center / --coverage (mudiff_hip.ensemble,
     mudiff_hip.volume_coverage; in one more), and --known_volume / --known_mask / --known_drop_slices /
     --known_resample, --known_kspace with the --kspace_* flags, --known_thick with the --thick_* flags and --known_multislice with the
-    --multislice_* flags (known_modes(); DESIGN.md sections 5.24a - 5.28; each in a parser of its own before that last one)."""
+    --multislice_* flags (known_modes(); DESIGN.md sections 5.24a - 5.28; each in a parser of its own before that last one), and
+    --known_thick_volume with the --thick_volume_* flags (measurement_modes(); section 5.29; likewise)."""
     p = make_parser()
     return finish_args(p, p.parse_args(argv))
 
