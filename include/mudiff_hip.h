@@ -44,6 +44,9 @@ extern "C" {
 /* Not a value of pro_mode: the form of the 3x3 matrix-core kernel that a launch with pro_mode AFFINE_SILU and             */
 /* mud_conv_args.in_up2 runs - FIR x2 up-sampling of silu(a*x + s), formed from the LOW-resolution x while it is staged. */
 #define MUD_PRO_UP2_AFFINE_SILU 4
+/* Not a value of pro_mode either: the form of the 3x3 matrix-core kernel that a launch with pro_mode NONE and mud_conv_args.in_s2d */
+/* runs - the 2x2 space-to-depth view of x, gathered from the full-resolution tensor while it is staged.                          */
+#define MUD_PRO_S2D 5
 
 /* arithmetic plan of one mud_conv2d_mfma launch (mud_conv_args.prec); the weights must have been packed for the same plan */
 #define MUD_PREC_16X3 0        /* every product as hi*hi + hi*lo + lo*hi on the 16-bit MFMA (fp16 pieces): ~2^-22 per product */
@@ -186,6 +189,16 @@ typedef struct mud_conv_args {
   /* columns as for res_k).  Built for some tiles and plans only: mud_conv2d_mfma_in_up2_supported tells beforehand, any other      */
   /* launch that sets it is refused; mud_conv2d_direct refuses it.                                                                  */
   int in_up2; float in_k[4];
+  /* mud_conv2d_mfma, ks 3, pro_mode NONE, no sub2 / skip_w / res_up2 / in_up2, a grid that is not split over K - the 2x2              */
+  /* space-to-depth view of the input, gathered while it is staged (the input pyramid's FIR + stride-2 conv as ONE stride-1 launch:   */
+  /* DESIGN 5.2c): with in_s2d != 0 `x` is the FULL-resolution tensor [B, 2H, 2W, Cin/4] with its own ldx, and H, W, Cin describe     */
+  /* the folded view [B, H, W, Cin] the launch convolves: view channel (py*2 + px)*C + c, C = Cin/4, of view pixel (y, x) is element  */
+  /* c of pixel (2y + py, 2x + px); the zero padding is the view's.  C must be a multiple of 16 (a 16-channel chunk never straddles    */
+  /* two parities).  w_exp: the packed weights are W * 2^w_exp, and the launch takes the power of two back out of the accumulated sum   */
+  /* before bias, residual and out_scale apply (exact; the composed weights' small taps stay normal fp16 numbers that way).            */
+  /* Built for some tiles and plans only: mud_conv2d_mfma_in_s2d_supported tells beforehand, any other launch that    */
+  /* sets it is refused; mud_conv2d_direct refuses it.                                                                                 */
+  int in_s2d;
 } mud_conv_args;
 
 /* Exact fp32 direct convolution (FMA chain per output), any ks/stride/pad/Cin/Cout.
@@ -221,6 +234,9 @@ int mud_conv2d_mfma_res_up2_supported(const mud_conv_args* a);
 /* 1 when mud_conv2d_mfma takes in_up2 for this launch (ks, sub2, skip_w, res_up2, pro_mode, the output size H x W, the tile that  */
 /* size takes, a.prec and the split-K policy are looked at), else 0. */
 int mud_conv2d_mfma_in_up2_supported(const mud_conv_args* a);
+/* 1 when mud_conv2d_mfma takes in_s2d for this launch (ks, pro_mode, sub2, skip_w, res_up2, in_up2, Cin, the tile the view's size  */
+/* takes, a.prec and the split-K policy are looked at), else 0. */
+int mud_conv2d_mfma_in_s2d_supported(const mud_conv_args* a);
 
 /* ---- e4m3 range census of a convolution input (the precision guard of MUD_PREC_FP8X: mudiff_hip.precision).
  * MUD_PREC_FP8X converts every prologued activation a (and its fp16 remainder a - fp16(a)) to e4m3 at CONSTANT power-of-two

@@ -265,6 +265,7 @@ extern "C" int mud_conv2d_direct(const mud_conv_args* ap, void* stream) {
   MUD_REQUIRE(a.x && a.w && a.out, "mud_conv2d_direct: null pointer");
   MUD_REQUIRE(a.B >= 0 && a.H > 0 && a.W > 0 && a.Cin > 0 && a.Cout > 0 && a.ks >= 1 && a.stride >= 1 && a.pad >= 0,
               "mud_conv2d_direct: bad sizes");
+  MUD_REQUIRE(!a.in_s2d, "mud_conv2d_direct: in_s2d (the space-to-depth view gathered while it is staged) is built for mud_conv2d_mfma's 3x3 kernel only");      // (first: with it ldx is that of Cin / 4 channels)
   MUD_REQUIRE(a.ldx >= a.Cin && a.ldo >= a.Cout, "mud_conv2d_direct: ld smaller than C");
   MUD_REQUIRE(a.pro_mode == MUD_PRO_NONE || a.pro_mode == MUD_PRO_LRELU || (a.pro_scale && a.pro_shift && a.pro_ld >= a.Cin), "mud_conv2d_direct: prologue arrays missing");
   MUD_REQUIRE(!a.res || a.ldr >= a.Cout, "mud_conv2d_direct: bad residual view");

@@ -244,6 +244,13 @@ __global__ __launch_bounds__(64 * WM * WN, (MT == 1 && WM * WN == 8) ? 4 : 2) vo
   static_assert(!IUP || (KS == 3 && !DUAL && G::ROWS % 2 == 0 && G::LDS_MAX + G::UP_BYTES <= 160 * 1024), "in_up2: 3x3, no fused skip conv, even tile rows, LDS budget");
   constexpr int GN_OFF = G::GN_OFF + (IUP ? G::UP_BYTES : 0);     // (the scratch sits where the GroupNorm arrays start otherwise)
   constexpr int NRAW = IUP ? G::UP_NLOAD : G::NLOAD;               // activation loads per thread and chunk
+  // S2D (MUD_PRO_S2D, mud_conv_args.in_s2d): a.x is the FULL-resolution tensor [B, 2H, 2W, C], C = Cin / 4, and the launch convolves its
+  // 2x2 space-to-depth view [B, H, W, 4C] - view channel (py * 2 + px) * C + c of view pixel (y, x) = element c of pixel (2y + py, 2x + px).
+  // Only the staging ADDRESSES differ from a MUD_PRO_NONE launch: a slot's pixel offset is that of pixel (2y, 2x), and a chunk's channel
+  // offset is that of its parity's pixel plus its 16 channels inside C (C % 16 == 0: one parity per chunk, wave-uniform).
+  constexpr bool S2D = PRO == MUD_PRO_S2D;
+  constexpr int PROX = S2D ? MUD_PRO_NONE : PRO;                   // the prologue arithmetic of the staged values
+  static_assert(!S2D || (KS == 3 && !DUAL), "in_s2d: 3x3, no fused skip conv");
   using HV4 = h16x4;
   using HV8 = h16x8;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -273,7 +280,7 @@ __global__ __launch_bounds__(64 * WM * WN, (MT == 1 && WM * WN == 8) ? 4 : 2) vo
   } else {
     flat0 = (int64_t)tile * G::P;
   }
-  const float* xb = a.x + (int64_t)b * (IUP ? (int64_t)(a.H >> 1) * (a.W >> 1) : HW) * a.ldx;
+  const float* xb = a.x + (int64_t)b * (IUP ? (int64_t)(a.H >> 1) * (a.W >> 1) : S2D ? 4 * HW : HW) * a.ldx;
   const int64_t tile_bytes = (int64_t)k16s * (G::TAPS * G::BSTEP);          // packed bytes of one 64-channel tile
   const char* wb = (const char*)a.w + (int64_t)b * a.w_bstride + (int64_t)nt * WN * tile_bytes;
   const float* psc = a.pro_scale + (int64_t)b * a.pro_ld;
@@ -319,7 +326,8 @@ __global__ __launch_bounds__(64 * WM * WN, (MT == 1 && WM * WN == 8) ? 4 : 2) vo
       const int py = p / G::PW, px = p - py * G::PW;
       const int gy = ty0 + py - 1, gx = tx0 + px - 1;
       valid = gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
-      g = ((int64_t)gy * a.W + gx) * a.ldx;
+      if constexpr (S2D) g = ((int64_t)(2 * gy) * (2 * a.W) + 2 * gx) * a.ldx;      // pixel (2y, 2x) of the full-resolution image (the mask: view coordinates)
+      else g = ((int64_t)gy * a.W + gx) * a.ldx;
       if (DUAL) {
         const bool centre = py >= 1 && py <= G::ROWS && px >= 1 && px <= 32 && tid + j * G::NT < G::ITEMS;   // (wrapped slots redo an item: skip)
         const int col = px - 1, sw = (col >> 2) & 3;
@@ -367,6 +375,12 @@ __global__ __launch_bounds__(64 * WM * WN, (MT == 1 && WM * WN == 8) ? 4 : 2) vo
   auto fetch_raw = [&](int chunk) {
     int c = chunk * G::KCH + q * 4;
     c = c < a.Cin ? c : 0;                      // clamped; zeroed in store_a
+    if constexpr (S2D) {
+      // chunk -> (parity, 16 channels inside C): scalar compares, no division; one value per chunk and wave.  (Cin % 64 == 0: the host)
+      const int cpp = a.Cin >> 6, kc_ = chunk < k16s ? chunk : k16s - 1;                 // chunks per parity = C / 16
+      const int par = (kc_ >= cpp ? 1 : 0) + (kc_ >= 2 * cpp ? 1 : 0) + (kc_ >= 3 * cpp ? 1 : 0);
+      c = ((par >> 1) * 2 * a.W + (par & 1)) * a.ldx + (kc_ - par * cpp) * 16 + q * 4;
+    }
 #pragma unroll
     for (int j = 0; j < NRAW; ++j) {
       if constexpr (CNT) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(raw[j]) : "v"(xb + goff[j] + c) : "memory");
@@ -395,7 +409,7 @@ __global__ __launch_bounds__(64 * WM * WN, (MT == 1 && WM * WN == 8) ? 4 : 2) vo
       const float keep = (cvalid && ((vmask >> j) & 1u)) ? 1.0f : 0.0f;   // zero padding stays zero
       HV4 hi, lo;
       int a8 = 0, al8 = 0;
-      cm_stage4<PRO, X8, H1>(raw[j], psc_r, psh_r, keep, hi, lo, a8, al8);
+      cm_stage4<PROX, X8, H1>(raw[j], psc_r, psh_r, keep, hi, lo, a8, al8);
       *(HV4*)(buf + loff[j]) = hi;
       if constexpr (X8) {                       // (loff holds record + 8 q)
         *(int*)(buf + loff[j] + 32 - q * 4) = a8;          // record + 32 + 4 q
@@ -628,6 +642,7 @@ __global__ __launch_bounds__(64 * WM * WN, (MT == 1 && WM * WN == 8) ? 4 : 2) vo
           const int gx = tx0 + (reg & 3) + 8 * (reg >> 2) + 4 * hh;
           const bool ok = gy < a.H && gx < a.W && co < a.Cout;
           acc[m][n][reg] = ok ? a.res[(((int64_t)b * a.H + gy) * a.W + gx) * a.ldr + co] : 0.f;
+          if constexpr (S2D) acc[m][n][reg] *= __builtin_ldexpf(1.0f, a.w_exp);      // (exact: the sums below carry the weights' 2^w_exp)
         }
       }
     }
@@ -793,7 +808,7 @@ __global__ __launch_bounds__(64 * WM * WN, (MT == 1 && WM * WN == 8) ? 4 : 2) vo
           // placing the slices one step LATER (3 slots: steps 5, 7, 8 instead of 4, 6, 8) gives the loads more time: 2-5 % on those launches;
           // with the AdaGN + SiLU prologue the later placement crowds the end of the group (+0.5-1.5 %: profiles/r03_q_staging_one_step_later.txt)
           auto jb = [](int i) {
-            if (PRO != MUD_PRO_NONE) return (i * G::NLOAD) / SPAN;
+            if (PROX != MUD_PRO_NONE) return (i * G::NLOAD) / SPAN;
             return i >= SPAN ? G::NLOAD : ((i > 0 ? i - 1 : 0) * G::NLOAD + G::NLOAD - 1) / SPAN;
           };
           const int j0 = jb(st - G::GS), j1 = jb(st - G::GS + 1);
@@ -822,6 +837,17 @@ __global__ __launch_bounds__(64 * WM * WN, (MT == 1 && WM * WN == 8) ? 4 : 2) vo
   };
   for (int kc = kc0; kc + 1 < nchunks; ++kc) chunk_body(kc, std::true_type{});
   if (kc0 < nchunks) chunk_body(nchunks - 1, std::false_type{});
+  if constexpr (S2D) {
+    // the composed weights were packed as W * 2^w_exp (their small taps would otherwise be fp16 subnormals with no lo piece left): the
+    // power of two comes back out here, exactly, before anything of the epilogue is added (the residual went in times 2^w_exp)
+    const float unscale = __builtin_ldexpf(1.0f, -a.w_exp);
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+      for (int n = 0; n < 2; ++n)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[m][n][i] *= unscale;
+  }
 
   if constexpr (KS == 3) {
     if (slab_mode) {
@@ -1596,6 +1622,7 @@ static int cm_launch_pro(const mud_conv_args& a, hipStream_t s) {
     if (ns > 1 && a.splitk_ws_bytes < cm_slab_bytes(ns, nblocks, 64 * WM * WN * 32 * MT * (DUAL ? 2 : 1))) ns = 1;      // workspace too small: run unsplit
     MUD_REQUIRE(ns == 1 || !a.res_up2, "mud_conv2d_mfma: res_up2 is not built for a launch split over K (ask mud_conv2d_mfma_res_up2_supported first)");
     MUD_REQUIRE(ns == 1 || !a.in_up2, "mud_conv2d_mfma: in_up2 is not built for a launch split over K (ask mud_conv2d_mfma_in_up2_supported first)");
+    MUD_REQUIRE(ns == 1 || !a.in_s2d, "mud_conv2d_mfma: in_s2d is not built for a launch split over K (ask mud_conv2d_mfma_in_s2d_supported first)");
     if (ns > 1) {
       mud_conv_args p = a;                       // raw partial sums: no epilogue terms, output = slab ksi of the workspace
       p.out = (float*)a.splitk_ws;
@@ -1721,6 +1748,24 @@ extern "C" int mud_conv2d_mfma_in_up2_supported(const mud_conv_args* ap) {
   return cm_in_up2_built(v, ap->prec) && cm_splits(blocks, (int)mud_cdiv(ap->Cin, 16)) == 1;
 }
 
+// in_s2d (MUD_PRO_S2D) is built for the same two tiles under the two fp16 plans: 8 x 32 px x 128 ch on eight waves (the input pyramid's
+// 64 -> 128 down-sampler at 128x128 once the batch fills the chip) and 4 x 32 px x 64 ch on four waves (small models, one slice at a time).
+static bool cm_in_s2d_built(int variant, int prec) {
+  return (variant == CMV_8X2 || variant == CMV_MT1) && (prec == MUD_PREC_16X3 || prec == MUD_PREC_16X1);
+}
+// H, W, Cin: the folded view's.  The 3x3 kernel without prologue, sub2, fused skip conv, res_up2, in_up2; whole 16-channel chunks per parity.
+static bool cm_in_s2d_form(const mud_conv_args& a) {
+  return a.ks == 3 && a.stride == 1 && a.pad == 1 && !a.sub2 && !a.skip_w && !a.res_up2 && !a.in_up2 && a.pro_mode == MUD_PRO_NONE && a.Cin > 0 && a.Cin % 64 == 0;
+}
+extern "C" int mud_conv2d_mfma_in_s2d_supported(const mud_conv_args* ap) {
+  if (!ap || !cm_in_s2d_form(*ap) || ap->B <= 0 || ap->H <= 0 || ap->W <= 0 || ap->Cout <= 0) return 0;
+  static const bool forced_tile = getenv("MUD_CONV_MT") != nullptr;             // (the tuning knob picks tiles this form may not have)
+  if (forced_tile) return 0;
+  int64_t blocks = 0;
+  const int v = cm_variant3(*ap, &blocks);
+  return cm_in_s2d_built(v, ap->prec) && cm_splits(blocks, (int)mud_cdiv(ap->Cin, 16)) == 1;
+}
+
 // MUD_PREC_FP8X is built for the 8-wave tiles (8 x 32 px x 128 ch, 16 x 32 px x 64 ch, and the one-row 8 x 32 px x 64 ch tile of the
 // 64 -> 64 layers), i.e. for launches that fill the chip, with the prologues the generators use there (none: G2's gate / fusion
 // convolutions; AdaGN + SiLU: the residual blocks, with or without the fused skip conv - whose own centre-tap products stay 16-bit x 3).
@@ -1748,8 +1793,21 @@ extern "C" int mud_conv2d_mfma(const mud_conv_args* ap, void* stream) {
   MUD_REQUIRE(a.x && a.w && a.out, "mud_conv2d_mfma: null pointer");
   MUD_REQUIRE((a.ks == 1 || a.ks == 3) && a.stride == 1 && a.pad == a.ks / 2, "mud_conv2d_mfma: only ks in {1,3}, stride 1, pad ks/2 (got ks=%d stride=%d pad=%d)", a.ks, a.stride, a.pad);
   MUD_REQUIRE(a.B >= 0 && a.H > 0 && a.W > 0 && a.Cin > 0 && a.Cout > 0, "mud_conv2d_mfma: bad sizes");
-  MUD_REQUIRE(a.Cin % 4 == 0 && a.ldx % 4 == 0 && a.ldx >= a.Cin && mud_aligned16(a.x), "mud_conv2d_mfma: needs Cin%%4==0 (Cin=%d), ldx%%4==0 (ldx=%d), 16-byte aligned x", a.Cin, a.ldx);
-  MUD_REQUIRE((int64_t)a.H * a.W * a.ldx < 0x7fffffffLL, "mud_conv2d_mfma: one image must stay below 2^31 elements");
+  if (a.in_s2d) {                                // (before the plain size checks: x is [B, 2H, 2W, Cin / 4] with its own ldx)
+    MUD_REQUIRE(cm_in_s2d_form(a),
+                "mud_conv2d_mfma: in_s2d needs ks == 3, no prologue, no sub2 / fused skip conv / res_up2 / in_up2 and Cin %% 64 == 0 (ks=%d sub2=%d pro_mode=%d Cin=%d)",
+                a.ks, a.sub2, a.pro_mode, a.Cin);
+    MUD_REQUIRE(a.ldx % 4 == 0 && a.ldx >= a.Cin / 4 && mud_aligned16(a.x), "mud_conv2d_mfma: in_s2d needs ldx%%4==0, ldx >= Cin/4 (Cin=%d ldx=%d), 16-byte aligned x", a.Cin, a.ldx);
+    MUD_REQUIRE(4 * (int64_t)a.H * a.W * a.ldx < 0x7fffffffLL, "mud_conv2d_mfma: in_s2d: one full-resolution image must stay below 2^31 elements");
+    MUD_REQUIRE(a.prec == MUD_PREC_16X3 || a.prec == MUD_PREC_16X1, "mud_conv2d_mfma: in_s2d is built for the two fp16 plans only (prec=%d)", a.prec);
+    MUD_REQUIRE(a.w_exp >= -100 && a.w_exp <= 100, "mud_conv2d_mfma: in_s2d: w_exp (the weights' power-of-two pre-scale) out of range (%d)", a.w_exp);
+    static const bool forced_tile = getenv("MUD_CONV_MT") != nullptr;
+    MUD_REQUIRE(!forced_tile && cm_in_s2d_built(cm_variant3(a, nullptr), a.prec),
+                "mud_conv2d_mfma: in_s2d is not built for the tile of this launch (ask mud_conv2d_mfma_in_s2d_supported first)");
+  } else {
+    MUD_REQUIRE(a.Cin % 4 == 0 && a.ldx % 4 == 0 && a.ldx >= a.Cin && mud_aligned16(a.x), "mud_conv2d_mfma: needs Cin%%4==0 (Cin=%d), ldx%%4==0 (ldx=%d), 16-byte aligned x", a.Cin, a.ldx);
+    MUD_REQUIRE((int64_t)a.H * a.W * a.ldx < 0x7fffffffLL, "mud_conv2d_mfma: one image must stay below 2^31 elements");
+  }
   MUD_REQUIRE(mud_aligned16(a.w) && a.w_bstride % 16 == 0, "mud_conv2d_mfma: packed weights must be 16-byte aligned");
   MUD_REQUIRE(a.ldo >= a.Cout && (!a.res || a.ldr >= a.Cout), "mud_conv2d_mfma: bad output/residual view");
   MUD_REQUIRE(!a.stats || a.stats_ld >= a.Cout, "mud_conv2d_mfma: bad stats view");
@@ -1806,6 +1864,12 @@ extern "C" int mud_conv2d_mfma(const mud_conv_args* ap, void* stream) {
              : a.prec == MUD_PREC_16X1 ? cm_launch_pro<3, 2, 4, 2, PU, false, MUD_PREC_16X1>(a, s)
                                        : cm_launch_pro<3, 2, 4, 2, PU>(a, s);
     return a.prec == MUD_PREC_16X1 ? cm_launch_pro<3, 1, 4, 1, PU, false, MUD_PREC_16X1>(a, s) : cm_launch_pro<3, 1, 4, 1, PU>(a, s);
+  }
+  if (a.in_s2d) {                                // (form, tile and plan checked above: cm_in_s2d_form, cm_in_s2d_built)
+    constexpr int PS = MUD_PRO_S2D;
+    if (cm_variant3(a, nullptr) == CMV_8X2)
+      return a.prec == MUD_PREC_16X1 ? cm_launch_pro<3, 2, 4, 2, PS, false, MUD_PREC_16X1>(a, s) : cm_launch_pro<3, 2, 4, 2, PS>(a, s);
+    return a.prec == MUD_PREC_16X1 ? cm_launch_pro<3, 1, 4, 1, PS, false, MUD_PREC_16X1>(a, s) : cm_launch_pro<3, 1, 4, 1, PS>(a, s);
   }
 #ifdef MUD_EXPERIMENT_WS      // scripts/build_variants.py ws:-DMUD_EXPERIMENT_WS (csrc/experiments/conv_ws.inc); never in the shipped build
   if (cm_ws_wanted(a)) return cm_ws_dispatch(a, s);

@@ -50,6 +50,7 @@ class ConvArgs(C.Structure):
         ('prec', C.c_int), ('w_exp', C.c_int),
         ('res_up2', C.c_int), ('res_k', C.c_float * 4),
         ('in_up2', C.c_int), ('in_k', C.c_float * 4),
+        ('in_s2d', C.c_int),
     ]
 
 
@@ -124,6 +125,7 @@ _SIGNATURES = {
     'mud_conv2d_mfma_splitk_bytes': (_L, [C.POINTER(ConvArgs)]),
     'mud_conv2d_mfma_res_up2_supported': (_I, [C.POINTER(ConvArgs)]),
     'mud_conv2d_mfma_in_up2_supported': (_I, [C.POINTER(ConvArgs)]),
+    'mud_conv2d_mfma_in_s2d_supported': (_I, [C.POINTER(ConvArgs)]),
     'mud_upfirdn2d': (_I, [_P, _L, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     'mud_fir_nhwc': (_I, [_P, _I, _I, _I, _I, _I, C.POINTER(C.c_float), _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P, _I, _P, _I, _P]),
     'mud_minibatch_stddev': (_I, [_P, _I, _L, _I, _I, _I, _P, _P]),

@@ -88,6 +88,11 @@ class View:
         (conv(in_up2=...))."""
         return View(self.base, self.B, 2 * self.H, 2 * self.W, self.C, self.ld, self.c0)
 
+    def s2d_shape(self):
+        """The 2x2 space-to-depth view of this view, for size queries only: [B, H/2, W/2, 4C], the shape a launch that folds it on
+        the way in runs at (conv(in_s2d=True)).  The pointer, ld and c0 stay the full-resolution view's."""
+        return View(self.base, self.B, self.H // 2, self.W // 2, 4 * self.C, self.ld, self.c0)
+
     def slice(self, c0, C_):
         assert 0 <= c0 and c0 + C_ <= self.C
         return View(self.base, self.B, self.H, self.W, C_, self.ld, self.c0 + c0, self.stats)
@@ -436,6 +441,28 @@ def in_up2_ok(B, H, W, cin, cout, prec=PREC_16X3):
     return bool(load().mud_conv2d_mfma_in_up2_supported(C.byref(a)))
 
 
+PYR_S2D = os.environ.get('MUD_PYR_S2D', '1') != '0'     # A/B knob: 0 = the input pyramid's down-sampler runs its FIR launch and the sub2 conv launch
+
+
+def in_s2d_ok(B, H, W, c, cout, prec=PREC_16X3):
+    """Does a 3x3 mud_conv2d_mfma launch under plan `prec` take the FULL-resolution input [B,H,W,c] as its 2x2 space-to-depth view
+    [B,H/2,W/2,4c], gathered while it is staged (mud_conv2d_mfma_in_s2d_supported: no prologue, c % 16 == 0, a tile and plan the form
+    is built for, a grid that is not split over K)?  The PYR_S2D knob is the dispatcher's (up_or_down_sampling.padded_strided_conv)."""
+    if H % 2 or W % 2 or c % 16 or cout % 4:
+        return False
+    a = ConvArgs()
+    a.B, a.H, a.W, a.Cin, a.ldx, a.ks, a.stride, a.pad, a.Cout, a.ldo, a.pro_mode, a.prec = B, H // 2, W // 2, 4 * c, c, 3, 1, 1, cout, cout, PRO_NONE, prec
+    a.in_s2d = 1
+    return bool(load().mud_conv2d_mfma_in_s2d_supported(C.byref(a)))
+
+
+def s2d_fold(t):
+    """[B,H,W,C] -> the materialised 2x2 space-to-depth tensor [B,H/2,W/2,4C] in mud_conv_args.in_s2d's channel order
+    ((py*2 + px)*C + c); a reference for tests and tools - the launches gather it themselves."""
+    B, H, W, Cc = t.shape
+    return t.reshape(B, H // 2, 2, W // 2, 2, Cc).permute(0, 1, 3, 2, 4, 5).reshape(B, H // 2, W // 2, 4 * Cc).contiguous()
+
+
 def resolve_pro(pro):
     """(scale, shift, mode) with the arrays materialised (for consumers that cannot fold the GroupNorm finalisation)."""
     if pro is not None and isinstance(pro[0], LazyGN):
@@ -555,7 +582,10 @@ def choose_prec(x: View, cout, pro_mode, *, skip=False, sub2=False, w_bstride=0)
 
 # One entry of a launch record (precision.launch_record): layer name (None where no ConvParam names the launch), kernel size,
 # matrix-core kernel or not, arithmetic plan, (B, H, W, Cin, Cout), sub2 form, fused skip conv, prologue mode.
-Launch = collections.namedtuple('Launch', 'layer ks mfma prec shape sub2 skip pro')
+# sub2: the launch computes a stride-2 pad-0 convolution on the stride-1 kernel - by the sub2 epilogue (shape: the padded image's) or
+# as the folded space-to-depth launch (shape: the folded view's).  Neither is planned by choose_prec: fp16 x 3, or single-pass.
+# s2d tells the two apart: True for the folded launch (mud_conv_args.in_s2d), which has no sub2 epilogue.
+Launch = collections.namedtuple('Launch', 'layer ks mfma prec shape sub2 skip pro s2d', defaults=(False,))
 
 
 RECORD = None         # the active precision.launch_record() list, or None: every ops.conv call appends a Launch to it
@@ -563,7 +593,7 @@ RECORD = None         # the active precision.launch_record() list, or None: ever
 
 def conv(x: View, w, ks, Cout, *, mfma, stride=1, pad=None, pro=None, bias=None, bias2=None, res: View = None,
          out_scale=1.0, act=ACT_NONE, out: View = None, w_bstride=0, arena=None, sub2=False, emul: View = None, gate=None, emul_cout=0,
-         skip=None, prec=PREC_16X3, w_exp=0, layer=None, res_up2=None, split_k=True, in_up2=None):
+         skip=None, prec=PREC_16X3, w_exp=0, layer=None, res_up2=None, split_k=True, in_up2=None, in_s2d=False, flops=None):
     """One fused convolution launch.  pro = (scale [B,Cin], shift [B,Cin], mode).
     skip = (packed 1x1 weights, bias or None, out View): the same launch also writes the 1x1 convolution of the RAW input
     (the residual block's Conv_2) - see fused_skip_ok().  prec / w_exp: the arithmetic plan `w` was packed for.
@@ -573,7 +603,16 @@ def conv(x: View, w, ks, Cout, *, mfma, stride=1, pad=None, pro=None, bias=None,
     split_k=False: hand the launch no split-K workspace, so a small grid runs unsplit (a res_up2 launch never gets one).
     in_up2 = the four 1-D taps of such a filter: `x` is then the LOW-resolution view [B,Ho/2,Wo/2,Cin], `pro` the AdaGN + SiLU
     prologue of that view, and the launch convolves FIR x2 (silu(affine(x))), formed while x is staged (mud_conv_args.in_up2; see
-    in_up2_ok).  The launch is recorded, and its plan chosen, at the size it runs at: [B,Ho,Wo,Cin]."""
+    in_up2_ok).  The launch is recorded, and its plan chosen, at the size it runs at: [B,Ho,Wo,Cin].
+    in_s2d=True: `x` is the FULL-resolution view [B,2Ho,2Wo,Cin/4] and the launch convolves its 2x2 space-to-depth view
+    [B,Ho,Wo,Cin] (channel (py*2 + px)*C + c), gathered while x is staged; `w` is packed for that view (mud_conv_args.in_s2d; see
+    in_s2d_ok).  Recorded at the size it runs at.  flops: the algorithmic count to book instead of the launch's own (a launch that
+    stands for another operator, e.g. a folded stride-2 convolution)."""
+    if in_s2d:
+        assert mfma and ks == 3 and stride == 1 and not sub2 and skip is None and res_up2 is None and in_up2 is None and pro is None
+        if x.H % 2 or x.W % 2 or x.C % 16:
+            raise MudiffHipError(f'conv: in_s2d needs even H, W and C % 16 == 0 (got {x.H}x{x.W}, C={x.C})')
+        x = x.s2d_shape()                         # (sizes below are the launch's; the pointer and ld are the full-resolution view's)
     if in_up2 is not None:
         assert mfma and ks == 3 and stride == 1 and not sub2 and skip is None and res_up2 is None and len(in_up2) == 4
         assert pro is not None and pro[2] == PRO_AFFINE_SILU
@@ -581,8 +620,8 @@ def conv(x: View, w, ks, Cout, *, mfma, stride=1, pad=None, pro=None, bias=None,
     if RECORD is not None:
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError('precision.launch_record() is eager only: the launch is being captured into a graph')
-        RECORD.append(Launch(layer, ks, bool(mfma), prec, (x.B, x.H, x.W, x.C, Cout), bool(sub2), skip is not None,
-                             PRO_NONE if pro is None else pro[2]))
+        RECORD.append(Launch(layer, ks, bool(mfma), prec, (x.B, x.H, x.W, x.C, Cout), bool(sub2 or in_s2d), skip is not None,
+                             PRO_NONE if pro is None else pro[2], bool(in_s2d)))
     lib = load()
     pad = ks // 2 if pad is None else pad
     Ho = (x.H + 2 * pad - ks) // stride + 1
@@ -629,6 +668,8 @@ def conv(x: View, w, ks, Cout, *, mfma, stride=1, pad=None, pro=None, bias=None,
         a.res, a.ldr = res.ptr, res.ld
     if in_up2 is not None:
         a.in_up2, a.in_k = 1, (C.c_float * 4)(*in_up2)
+    if in_s2d:
+        a.in_s2d = 1
     a.out_scale, a.act = out_scale, act
     a.sub2 = 1 if sub2 else 0
     if emul is not None:          # v *= emul (on the first emul_cout output channels only, when given)
@@ -648,7 +689,7 @@ def conv(x: View, w, ks, Cout, *, mfma, stride=1, pad=None, pro=None, bias=None,
         assert mfma and ks == 3 and res is None and (so.B, so.H, so.W, so.C) == (x.B, Ho, Wo, Cout)
         a.skip_w, a.skip_bias, a.skip_out, a.skip_ldo = ptr(sw), ptr(sb), so.ptr, so.ld
         skip_flops = 2.0 * x.B * Ho * Wo * Cout * x.C
-    if mfma and ks == 3 and split_k and res_up2 is None and in_up2 is None:      # small grids (one slice at a time): split-K slabs, stream-ordered scratch (graph-capture safe);
+    if mfma and ks == 3 and split_k and res_up2 is None and in_up2 is None and not in_s2d:      # small grids (one slice at a time): split-K slabs, stream-ordered scratch (graph-capture safe);
                                                    # a launch that up-samples its residual or its input is never split (no workspace: it runs unsplit)
         cnt = splitk_counters(x.device)
         a.splitk_counters, a.splitk_ncounters = ptr(cnt), cnt.numel()
@@ -658,7 +699,8 @@ def conv(x: View, w, ks, Cout, *, mfma, stride=1, pad=None, pro=None, bias=None,
             a.splitk_ws, a.splitk_ws_bytes = ptr(keep[1]), nws
     fn = lib.mud_conv2d_mfma if mfma else lib.mud_conv2d_direct
     name = (f'conv_mfma_k{ks}' if mfma else f'conv_direct_k{ks}') + {PREC_FP8X: '_fp8x', PREC_16X1: '_fp16'}.get(prec, '')
-    flops = 2.0 * x.B * Ho * Wo * Cout * x.C * ks * ks + skip_flops     # algorithmic (sub2 issues 4x this)
+    if flops is None:
+        flops = 2.0 * x.B * Ho * Wo * Cout * x.C * ks * ks + skip_flops     # algorithmic (sub2 issues 4x this)
     nbytes = 4.0 * ((x_lo if in_up2 is not None else x).npix * x.C + out.npix * Cout * ((2 if res is not None else 1) + (1 if skip is not None else 0))) + (w.numel() * w.element_size() if w_bstride == 0 else x.B * w_bstride)
     _launch(name, x.device, fn, C.byref(a), STREAM, flops=flops, nbytes=nbytes)
     return out
