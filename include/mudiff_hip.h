@@ -237,6 +237,18 @@ int mud_conv2d_mfma_in_up2_supported(const mud_conv_args* a);
 /* 1 when mud_conv2d_mfma takes in_s2d for this launch (ks, pro_mode, sub2, skip_w, res_up2, in_up2, Cin, the tile the view's size  */
 /* takes, a.prec and the split-K policy are looked at), else 0. */
 int mud_conv2d_mfma_in_s2d_supported(const mud_conv_args* a);
+/* The workgroup tile mud_conv2d_mfma launches for a ks == 3 argument block (rows x 32 px x output channels, waves): it follows from  */
+/* the workgroup count alone (B, H, W, Cout; Cin <= 64 for the one-row tile), never from the layer.  skip_w set: the fused skip conv  */
+/* is built for 8X2, 16X1 and MT1 only, so its small grids take MT1.  in_up2 / in_s2d: H, W, Cin as the launch takes them; -1 where   */
+/* the form is not built for the tile and a.prec.  -1 for ks != 3 or sizes <= 0.  Sizes, skip_w, in_up2, in_s2d and prec are looked   */
+/* at, no pointer is dereferenced.  (The A/B knobs MUD_CONV_NO16 / MUD_CONV_NO8X1R are honoured; MUD_CONV_MT, which forces a tile on   */
+/* plain launches, is not.)                                                                                                            */
+#define MUD_TILE_8X2 0         /*  8 rows x 128 channels, 8 waves                     (an even number of 64-channel tiles) */
+#define MUD_TILE_16X1 1        /* 16 rows x  64 channels, 8 waves                                                         */
+#define MUD_TILE_MT2 2         /*  8 rows x  64 channels, 4 waves                                                         */
+#define MUD_TILE_MT1 3         /*  4 rows x  64 channels, 4 waves                     (every grid too small for the others) */
+#define MUD_TILE_8X1R 4        /*  8 rows x  64 channels, 8 waves of one row each     (Cout <= 64 and Cin <= 64)           */
+int mud_conv2d_mfma_tile(const mud_conv_args* a);
 
 /* ---- e4m3 range census of a convolution input (the precision guard of MUD_PREC_FP8X: mudiff_hip.precision).
  * MUD_PREC_FP8X converts every prologued activation a (and its fp16 remainder a - fp16(a)) to e4m3 at CONSTANT power-of-two

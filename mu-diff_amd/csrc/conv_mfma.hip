@@ -1676,7 +1676,7 @@ static int cm_launch(const mud_conv_args& a, hipStream_t s) {
 // 3x3 tile variant by problem size: big tiles (more MFMA work per weight byte) once they still fill the 256 CUs.
 // Measured on MI355X (scripts/bench_conv.py): MT=2 (two workgroups co-resident per CU, one wave of each per SIMD)
 // beats MT=4 (one workgroup per CU) by 15-40 % on every layer shape; MT=1 only when MT=2 cannot give 2 blocks/CU.
-enum { CMV_8X2, CMV_16X1, CMV_MT2, CMV_MT1, CMV_8X1R };
+enum { CMV_8X2 = MUD_TILE_8X2, CMV_16X1 = MUD_TILE_16X1, CMV_MT2 = MUD_TILE_MT2, CMV_MT1 = MUD_TILE_MT1, CMV_8X1R = MUD_TILE_8X1R };
 static int cm_variant3(const mud_conv_args& a, int64_t* blocks) {
   const int64_t ntiles = mud_cdiv(a.Cout, CM_BN);
   int64_t nb;
@@ -1703,18 +1703,25 @@ static int cm_variant3(const mud_conv_args& a, int64_t* blocks) {
   if (blocks) *blocks = nb;
   return v;
 }
+// The tile of a 3x3 launch, for the dispatcher and every query: cm_variant3's, except that the fused 1x1 skip conv (DUAL) is built
+// for three tiles - the 8-row 4-wave tile would drop to one workgroup per CU with the second image, so its small grids take the
+// 4-row tile (the one-row tile is never chosen for it)
+static int cm_tile3(const mud_conv_args& a, int64_t* blocks) {
+  int64_t nb;
+  int v = cm_variant3(a, &nb);
+  if (a.skip_w && v != CMV_8X2 && v != CMV_16X1) {
+    v = CMV_MT1;
+    nb = mud_cdiv(a.W, 32) * mud_cdiv(a.H, 4) * mud_cdiv(a.Cout, CM_BN) * a.B;
+  }
+  if (blocks) *blocks = nb;
+  return v;
+}
 
 extern "C" int64_t mud_conv2d_mfma_splitk_bytes(const mud_conv_args* ap) {
   if (!ap || ap->ks != 3 || ap->B <= 0 || ap->H <= 0 || ap->W <= 0 || ap->Cin <= 0 || ap->Cout <= 0 || !cm_split_eligible(*ap)) return 0;
+  if (ap->skip_w && !ap->splitk_counters) return 0;   // the fused skip conv: two accumulator sets, the in-launch reduction only
   int64_t blocks = 0;
-  int v = cm_variant3(*ap, &blocks);
-  if (ap->skip_w) {                              // the fused skip conv: two accumulator sets, the in-launch reduction only, and
-    if (!ap->splitk_counters) return 0;          // mud_conv2d_mfma's tile choice (small grids take the 4-row tile)
-    if (v != CMV_8X2 && v != CMV_16X1) {
-      v = CMV_MT1;
-      blocks = mud_cdiv(ap->W, 32) * mud_cdiv(ap->H, 4) * mud_cdiv(ap->Cout, CM_BN) * ap->B;
-    }
-  }
+  const int v = cm_tile3(*ap, &blocks);
   const int ns = cm_splits(blocks, (int)mud_cdiv(ap->Cin, 16));
   const int tile_words = ((v == CMV_8X2 || v == CMV_16X1) ? 512 * 64 : v == CMV_MT2 ? 256 * 64 : v == CMV_8X1R ? 512 * 32 : 256 * 32) * (ap->skip_w ? 2 : 1);   // threads x accumulators
   return ns > 1 ? cm_slab_bytes(ns, blocks, tile_words) : 0;
@@ -1726,7 +1733,7 @@ extern "C" int mud_conv2d_mfma_res_up2_supported(const mud_conv_args* ap) {
   if (!ap || ap->ks != 3 || ap->stride != 1 || ap->pad != 1 || ap->sub2 || ap->skip_w || ap->pro_mode != MUD_PRO_AFFINE_SILU) return 0;
   if (ap->B <= 0 || ap->H <= 0 || ap->W <= 0 || ap->Cin <= 0 || ap->Cout <= 0 || (ap->H & 1) || (ap->W & 1)) return 0;
   int64_t blocks = 0;
-  cm_variant3(*ap, &blocks);
+  cm_tile3(*ap, &blocks);
   return cm_splits(blocks, (int)mud_cdiv(ap->Cin, 16)) == 1;      // (whatever workspace the caller has: a launch that may split is left alone)
 }
 
@@ -1744,7 +1751,7 @@ extern "C" int mud_conv2d_mfma_in_up2_supported(const mud_conv_args* ap) {
   static const bool forced_tile = getenv("MUD_CONV_MT") != nullptr;             // (the tuning knob picks tiles this form may not have)
   if (forced_tile) return 0;
   int64_t blocks = 0;
-  const int v = cm_variant3(*ap, &blocks);
+  const int v = cm_tile3(*ap, &blocks);
   return cm_in_up2_built(v, ap->prec) && cm_splits(blocks, (int)mud_cdiv(ap->Cin, 16)) == 1;
 }
 
@@ -1762,7 +1769,7 @@ extern "C" int mud_conv2d_mfma_in_s2d_supported(const mud_conv_args* ap) {
   static const bool forced_tile = getenv("MUD_CONV_MT") != nullptr;             // (the tuning knob picks tiles this form may not have)
   if (forced_tile) return 0;
   int64_t blocks = 0;
-  const int v = cm_variant3(*ap, &blocks);
+  const int v = cm_tile3(*ap, &blocks);
   return cm_in_s2d_built(v, ap->prec) && cm_splits(blocks, (int)mud_cdiv(ap->Cin, 16)) == 1;
 }
 
@@ -1772,9 +1779,18 @@ extern "C" int mud_conv2d_mfma_in_s2d_supported(const mud_conv_args* ap) {
 static bool cm_fp8x_built(const mud_conv_args& a) {
   if (a.ks != 3 || a.sub2 || (a.pro_mode != MUD_PRO_NONE && a.pro_mode != MUD_PRO_AFFINE_SILU)) return false;
   if (a.skip_w && a.pro_mode != MUD_PRO_AFFINE_SILU) return false;
-  const int v = cm_variant3(a, nullptr);
+  const int v = cm_tile3(a, nullptr);
   return v == CMV_8X2 || v == CMV_16X1 || v == CMV_8X1R;
 }
+// The tile the dispatcher below launches (mudiff_hip.h): cm_tile3's; -1 where a form is not built for it.  Host only.
+extern "C" int mud_conv2d_mfma_tile(const mud_conv_args* ap) {
+  if (!ap || ap->ks != 3 || ap->B <= 0 || ap->H <= 0 || ap->W <= 0 || ap->Cin <= 0 || ap->Cout <= 0) return -1;
+  const int v = cm_tile3(*ap, nullptr);
+  if (ap->in_up2 && !cm_in_up2_built(v, ap->prec)) return -1;
+  if (ap->in_s2d && !cm_in_s2d_built(v, ap->prec)) return -1;
+  return v;
+}
+
 // MUD_PREC_16X1 is built for every 3x3 launch: every tile, every prologue, the fused skip conv (AdaGN + SiLU prologue, as always),
 // split-K and sub2.  No 1x1 form.
 extern "C" int mud_conv2d_mfma_prec_supported(const mud_conv_args* ap, int prec) {
@@ -1802,7 +1818,7 @@ extern "C" int mud_conv2d_mfma(const mud_conv_args* ap, void* stream) {
     MUD_REQUIRE(a.prec == MUD_PREC_16X3 || a.prec == MUD_PREC_16X1, "mud_conv2d_mfma: in_s2d is built for the two fp16 plans only (prec=%d)", a.prec);
     MUD_REQUIRE(a.w_exp >= -100 && a.w_exp <= 100, "mud_conv2d_mfma: in_s2d: w_exp (the weights' power-of-two pre-scale) out of range (%d)", a.w_exp);
     static const bool forced_tile = getenv("MUD_CONV_MT") != nullptr;
-    MUD_REQUIRE(!forced_tile && cm_in_s2d_built(cm_variant3(a, nullptr), a.prec),
+    MUD_REQUIRE(!forced_tile && cm_in_s2d_built(cm_tile3(a, nullptr), a.prec),
                 "mud_conv2d_mfma: in_s2d is not built for the tile of this launch (ask mud_conv2d_mfma_in_s2d_supported first)");
   } else {
     MUD_REQUIRE(a.Cin % 4 == 0 && a.ldx % 4 == 0 && a.ldx >= a.Cin && mud_aligned16(a.x), "mud_conv2d_mfma: needs Cin%%4==0 (Cin=%d), ldx%%4==0 (ldx=%d), 16-byte aligned x", a.Cin, a.ldx);
@@ -1849,7 +1865,7 @@ extern "C" int mud_conv2d_mfma(const mud_conv_args* ap, void* stream) {
     MUD_REQUIRE(a.ks == 3 && !a.sub2 && !a.skip_w && !a.res_up2 && (a.H & 1) == 0 && (a.W & 1) == 0 && a.pro_mode == MUD_PRO_AFFINE_SILU,
                 "mud_conv2d_mfma: in_up2 needs ks == 3, the AFFINE_SILU prologue, no sub2 / fused skip conv / res_up2 and even H, W (ks=%d H=%d W=%d sub2=%d pro_mode=%d)",
                 a.ks, a.H, a.W, a.sub2, a.pro_mode);
-    MUD_REQUIRE(cm_in_up2_built(cm_variant3(a, nullptr), a.prec),
+    MUD_REQUIRE(cm_in_up2_built(cm_tile3(a, nullptr), a.prec),
                 "mud_conv2d_mfma: in_up2 is not built for the tile / arithmetic plan of this launch (prec=%d; ask mud_conv2d_mfma_in_up2_supported first)", a.prec);
   }
   MUD_REQUIRE(a.prec != MUD_PREC_16X1 || a.ks == 3, "mud_conv2d_mfma: MUD_PREC_16X1 is built for ks == 3 only (got ks=%d)", a.ks);
@@ -1859,7 +1875,7 @@ extern "C" int mud_conv2d_mfma(const mud_conv_args* ap, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   if (a.in_up2) {                                // (tile and plan checked above: cm_in_up2_built)
     constexpr int PU = MUD_PRO_UP2_AFFINE_SILU;
-    if (cm_variant3(a, nullptr) == CMV_8X2)
+    if (cm_tile3(a, nullptr) == CMV_8X2)
       return a.prec == MUD_PREC_FP8X   ? cm_launch_pro<3, 2, 4, 2, PU, false, MUD_PREC_FP8X>(a, s)
              : a.prec == MUD_PREC_16X1 ? cm_launch_pro<3, 2, 4, 2, PU, false, MUD_PREC_16X1>(a, s)
                                        : cm_launch_pro<3, 2, 4, 2, PU>(a, s);
@@ -1867,7 +1883,7 @@ extern "C" int mud_conv2d_mfma(const mud_conv_args* ap, void* stream) {
   }
   if (a.in_s2d) {                                // (form, tile and plan checked above: cm_in_s2d_form, cm_in_s2d_built)
     constexpr int PS = MUD_PRO_S2D;
-    if (cm_variant3(a, nullptr) == CMV_8X2)
+    if (cm_tile3(a, nullptr) == CMV_8X2)
       return a.prec == MUD_PREC_16X1 ? cm_launch_pro<3, 2, 4, 2, PS, false, MUD_PREC_16X1>(a, s) : cm_launch_pro<3, 2, 4, 2, PS>(a, s);
     return a.prec == MUD_PREC_16X1 ? cm_launch_pro<3, 1, 4, 1, PS, false, MUD_PREC_16X1>(a, s) : cm_launch_pro<3, 1, 4, 1, PS>(a, s);
   }
@@ -1875,7 +1891,7 @@ extern "C" int mud_conv2d_mfma(const mud_conv_args* ap, void* stream) {
   if (cm_ws_wanted(a)) return cm_ws_dispatch(a, s);
 #endif
   if (a.prec == MUD_PREC_FP8X) {
-    const int v8 = cm_variant3(a, nullptr);
+    const int v8 = cm_tile3(a, nullptr);
     if (v8 == CMV_8X1R) return a.pro_mode == MUD_PRO_NONE ? cm_launch_pro<3, 1, 8, 1, MUD_PRO_NONE, false, MUD_PREC_FP8X>(a, s) : cm_launch_pro<3, 1, 8, 1, MUD_PRO_AFFINE_SILU, false, MUD_PREC_FP8X>(a, s);
     const bool x2 = v8 == CMV_8X2;
     if (a.skip_w) return x2 ? cm_launch_pro<3, 2, 4, 2, MUD_PRO_AFFINE_SILU, true, MUD_PREC_FP8X>(a, s) : cm_launch_pro<3, 2, 8, 1, MUD_PRO_AFFINE_SILU, true, MUD_PREC_FP8X>(a, s);
@@ -1883,16 +1899,16 @@ extern "C" int mud_conv2d_mfma(const mud_conv_args* ap, void* stream) {
     return x2 ? cm_launch_pro<3, 2, 4, 2, MUD_PRO_AFFINE_SILU, false, MUD_PREC_FP8X>(a, s) : cm_launch_pro<3, 2, 8, 1, MUD_PRO_AFFINE_SILU, false, MUD_PREC_FP8X>(a, s);
   }
   if (a.prec == MUD_PREC_16X1) {
-    // the single-pass plan on the same tile choice as 16x3 (cm_variant3; the fused skip conv: its three tiles)
+    // the single-pass plan on the same tile choice as 16x3 (cm_tile3; the fused skip conv: its three tiles)
     constexpr int P1 = MUD_PREC_16X1;
     if (a.skip_w) {
-      switch (cm_variant3(a, nullptr)) {
+      switch (cm_tile3(a, nullptr)) {
         case CMV_8X2: return cm_launch_pro<3, 2, 4, 2, MUD_PRO_AFFINE_SILU, true, P1>(a, s);
         case CMV_16X1: return cm_launch_pro<3, 2, 8, 1, MUD_PRO_AFFINE_SILU, true, P1>(a, s);
-        default: return cm_launch_pro<3, 1, 4, 1, MUD_PRO_AFFINE_SILU, true, P1>(a, s);
+        default: return cm_launch_pro<3, 1, 4, 1, MUD_PRO_AFFINE_SILU, true, P1>(a, s);      // CMV_MT1 (cm_tile3)
       }
     }
-    switch (cm_variant3(a, nullptr)) {
+    switch (cm_tile3(a, nullptr)) {
       case CMV_8X2: return cm_launch<3, 2, 4, 2, P1>(a, s);
       case CMV_16X1: return cm_launch<3, 2, 8, 1, P1>(a, s);
       case CMV_MT2: return cm_launch<3, 2, 4, 1, P1>(a, s);
@@ -1908,16 +1924,15 @@ extern "C" int mud_conv2d_mfma(const mud_conv_args* ap, void* stream) {
     return cm_launch<1, 1>(a, s);      // (256- and 512-pixel 1x1 tiles were measured 5-8 % slower and are no longer built)
   }
   if (a.ks == 3 && a.skip_w) {
-    // fused 1x1 skip conv (DUAL): built for the AdaGN + SiLU prologue of the residual blocks only; the 8-row 4-wave tile would
-    // drop to one workgroup per CU with the second image, so small grids take the 4-row tile
-    switch (cm_variant3(a, nullptr)) {
+    // fused 1x1 skip conv (DUAL): built for the AdaGN + SiLU prologue of the residual blocks only, on its three tiles (cm_tile3)
+    switch (cm_tile3(a, nullptr)) {
       case CMV_8X2: return cm_launch_pro<3, 2, 4, 2, MUD_PRO_AFFINE_SILU, true>(a, s);
       case CMV_16X1: return cm_launch_pro<3, 2, 8, 1, MUD_PRO_AFFINE_SILU, true>(a, s);
-      default: return cm_launch_pro<3, 1, 4, 1, MUD_PRO_AFFINE_SILU, true>(a, s);
+      default: return cm_launch_pro<3, 1, 4, 1, MUD_PRO_AFFINE_SILU, true>(a, s);      // CMV_MT1
     }
   }
   if (a.ks == 3) {
-    switch (cm_variant3(a, nullptr)) {
+    switch (cm_tile3(a, nullptr)) {
       case CMV_8X2: return cm_launch<3, 2, 4, 2>(a, s);
       case CMV_16X1: return cm_launch<3, 2, 8, 1>(a, s);
       case CMV_MT2: return cm_launch<3, 2>(a, s);

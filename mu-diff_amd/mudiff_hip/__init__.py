@@ -20,6 +20,7 @@ PREC_16X3, PREC_FP8X, PREC_16X1 = 0, 1, 2
 
 ACT_NONE, ACT_SIGMOID, ACT_TANH, ACT_SILU, ACT_LRELU = 0, 1, 2, 3, 4
 PRO_NONE, PRO_AFFINE, PRO_AFFINE_SILU, PRO_LRELU = 0, 1, 2, 3
+TILE_8X2, TILE_16X1, TILE_MT2, TILE_MT1, TILE_8X1R = 0, 1, 2, 3, 4      # MUD_TILE_* (mud_conv2d_mfma_tile)
 
 
 class MudiffHipError(RuntimeError):
@@ -126,6 +127,7 @@ _SIGNATURES = {
     'mud_conv2d_mfma_res_up2_supported': (_I, [C.POINTER(ConvArgs)]),
     'mud_conv2d_mfma_in_up2_supported': (_I, [C.POINTER(ConvArgs)]),
     'mud_conv2d_mfma_in_s2d_supported': (_I, [C.POINTER(ConvArgs)]),
+    'mud_conv2d_mfma_tile': (_I, [C.POINTER(ConvArgs)]),
     'mud_upfirdn2d': (_I, [_P, _L, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     'mud_fir_nhwc': (_I, [_P, _I, _I, _I, _I, _I, C.POINTER(C.c_float), _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P, _I, _P, _I, _P]),
     'mud_minibatch_stddev': (_I, [_P, _I, _L, _I, _I, _I, _P, _P]),

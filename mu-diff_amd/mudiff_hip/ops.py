@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import (ACT_LRELU, ACT_NONE, ACT_SIGMOID, ACT_SILU, ACT_TANH, PREC_16X1, PREC_16X3, PREC_FP8X, PRO_AFFINE, PRO_AFFINE_SILU, PRO_LRELU,  # noqa: F401
-               PRO_NONE, ConvArgs, MudiffHipError, check, load, ptr, require_gpu)
+               PRO_NONE, TILE_8X1R, TILE_8X2, TILE_16X1, TILE_MT1, TILE_MT2, ConvArgs, MudiffHipError, check, load, ptr, require_gpu)
 
 
 # MUD_DETERMINISTIC=1: bit-stable outputs run to run.  The only order-dependent arithmetic of the path is the fp64 atomic
@@ -567,6 +567,25 @@ def conv_prec_supported(x: View, cout, pro_mode, prec, skip=False, sub2=False):
     if skip:
         a.skip_w = x.ptr
     return bool(load().mud_conv2d_mfma_prec_supported(C.byref(a), prec))
+
+
+TILE_NAMES = {TILE_8X2: '8X2', TILE_16X1: '16X1', TILE_MT2: 'MT2', TILE_MT1: 'MT1', TILE_8X1R: '8X1R'}
+
+
+def conv_tile(x: View, cout, *, skip=False, in_up2=False, in_s2d=False, pro_mode=PRO_NONE, prec=PREC_16X3):
+    """The workgroup tile (TILE_*) a 3x3 mud_conv2d_mfma launch of this shape runs on (mud_conv2d_mfma_tile: it follows from the
+    workgroup count, not from the layer), or -1 where in_up2 / in_s2d is not built for that tile and plan.  `x`: the view the launch
+    reads, as ops.conv takes it (in_up2: the low-resolution view; in_s2d: the full-resolution view).  Only sizes are looked at."""
+    if in_up2:
+        x = x.up2_shape()
+    if in_s2d:
+        x = x.s2d_shape()
+    a = ConvArgs()
+    a.x, a.B, a.H, a.W, a.Cin, a.ldx, a.ks, a.stride, a.pad = x.ptr, x.B, x.H, x.W, x.C, x.ld, 3, 1, 1
+    a.out, a.Cout, a.ldo, a.pro_mode, a.prec, a.in_up2, a.in_s2d = x.ptr, cout, (cout + 3) & ~3, pro_mode, prec, int(in_up2), int(in_s2d)
+    if skip:
+        a.skip_w = x.ptr
+    return load().mud_conv2d_mfma_tile(C.byref(a))
 
 
 def choose_prec(x: View, cout, pro_mode, *, skip=False, sub2=False, w_bstride=0):

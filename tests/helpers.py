@@ -77,6 +77,49 @@ def wide_cfg3_case(cfg, copies=2):
                 refs=refs, targets=torch.cat(tgt, 0), groups=list(CFG3_ORDERS))
 
 
+def h16(t):
+    """fp16 round-to-nearest-even, saturating at +-65504 (the matrix-core kernels' staging and packing), back in fp64."""
+    return t.float().clamp(-65504.0, 65504.0).half().double()
+
+
+def pro_host(x, sc, sh, mode):
+    """A conv launch's prologue in fp32 (x*sc + sh, SiLU) as the kernel computes it before its one rounding to fp16."""
+    import torch.nn.functional as F
+    from mudiff_hip import ops
+    if mode == ops.PRO_NONE:
+        return x
+    if mode == ops.PRO_LRELU:
+        return torch.where(x > 0, x, 0.2 * x)
+    a = x * sc[:, :, None, None] + sh[:, :, None, None]
+    return F.silu(a) if mode == ops.PRO_AFFINE_SILU else a
+
+
+def check_fp16_definition(y, a16, w16, extra_abs=None, mult=1.0, bias=None, res=None, tag='', bias2=None, pick=None, scale=1.0):
+    """The single-pass fp16 plan (MUD_PREC_16X1) against its definition: max |y - conv(a16, w16) (+ bias + res)| against
+    mult * K * 2^-24 * sum|a w| per output (+ the magnitude of what the epilogue adds): the products are exact in fp32, only the
+    accumulation order differs.  bias2: a per-sample bias [B, Cout]; pick: the outputs the launch keeps (sub2: the odd positions),
+    applied before the residual; scale: the launch's out_scale, applied to the sum (and to the bound)."""
+    import torch.nn.functional as F
+    K = a16.shape[1] * 9
+    ref = F.conv2d(a16, w16, padding=1)
+    mag = F.conv2d(a16.abs(), w16.abs(), padding=1)
+    if bias is not None:
+        ref, mag = ref + bias.double()[None, :, None, None], mag + bias.double().abs()[None, :, None, None]
+    if bias2 is not None:
+        ref, mag = ref + bias2.double()[:, :, None, None], mag + bias2.double().abs()[:, :, None, None]
+    if pick is not None:
+        ref, mag = pick(ref), pick(mag)
+    if res is not None:
+        ref, mag = ref + res.double(), mag + res.double().abs()
+    ref, mag = ref * scale, mag * abs(scale)
+    err = (y.cpu().double() - ref).abs()
+    bound = mult * K * 2.0 ** -24 * mag + 1e-30
+    worst = float((err / bound).max())
+    print(f'{tag}: max-abs {float(err.max()):.2e}, worst err / (K 2^-24 sum|aw|) = {worst * mult:.3f} (bar {mult:g})')
+    assert torch.isfinite(y).all() and worst <= 1.0
+    return ref
+
+
 SMALL_CFGS = {
     's32': dict(image_size=32, num_channels_dae=32, ch_mult=[1, 2, 4], attn_resolutions=(16,)),
     's32na': dict(image_size=32, num_channels_dae=16, ch_mult=[1, 2], attn_resolutions=(), num_res_blocks=1),

@@ -13,7 +13,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import PKG, REPO
-from helpers import SMALL_CFGS, demo_conds, load_golden, sampler_inputs
+from helpers import SMALL_CFGS, check_fp16_definition as _check, demo_conds, h16 as _h16, load_golden, pro_host as _pro_host, sampler_inputs
 from oracle import mudiff_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -23,40 +23,6 @@ DEV = 'cuda:0'
 
 def g(t):
     return t.to(DEV)
-
-
-def _h16(t):
-    """fp16 round-to-nearest-even, saturating at +-65504 (the kernel's staging and packing), back in fp64."""
-    return t.float().clamp(-65504.0, 65504.0).half().double()
-
-
-def _check(y, a16, w16, extra_abs=None, mult=1.0, bias=None, res=None, tag=''):
-    """max |y - conv(a16, w16) (+ bias + res)| against mult * K * 2^-24 * sum|a w| per output (+ the magnitude of what the epilogue
-    adds): the products are exact in fp32, only the accumulation order differs."""
-    K = a16.shape[1] * 9
-    ref = F.conv2d(a16, w16, padding=1)
-    mag = F.conv2d(a16.abs(), w16.abs(), padding=1)
-    if bias is not None:
-        ref, mag = ref + bias.double()[None, :, None, None], mag + bias.double().abs()[None, :, None, None]
-    if res is not None:
-        ref, mag = ref + res.double(), mag + res.double().abs()
-    err = (y.cpu().double() - ref).abs()
-    bound = mult * K * 2.0 ** -24 * mag + 1e-30
-    worst = float((err / bound).max())
-    print(f'{tag}: max-abs {float(err.max()):.2e}, worst err / (K 2^-24 sum|aw|) = {worst * mult:.3f} (bar {mult:g})')
-    assert torch.isfinite(y).all() and worst <= 1.0
-    return ref
-
-
-def _pro_host(x, sc, sh, mode):
-    """The prologue in fp32 (x*sc + sh, SiLU) as the kernel computes it before its one rounding to fp16."""
-    from mudiff_hip import ops
-    if mode == ops.PRO_NONE:
-        return x
-    if mode == ops.PRO_LRELU:
-        return torch.where(x > 0, x, 0.2 * x)
-    a = x * sc[:, :, None, None] + sh[:, :, None, None]
-    return F.silu(a) if mode == ops.PRO_AFFINE_SILU else a
 
 
 # (B, H, W, Cin, Cout, prologue, tile cm_variant3 picks): one shape per tile variant and prologue mode
@@ -75,6 +41,7 @@ def test_plain_launch_exact_against_its_definition(B, H, W, Cin, Cout, pro, tile
     bias = torch.randn(Cout, generator=gen)
     sc, sh = torch.rand(B, Cin, generator=gen) + 0.5, torch.randn(B, Cin, generator=gen)
     xv = ops.View.from_nchw(g(x))
+    assert ops.TILE_NAMES[ops.conv_tile(xv, Cout)] == tile          # the label is the tile that runs (mud_conv2d_mfma_tile)
     assert ops.conv_prec_supported(xv, Cout, mode, ops.PREC_16X1)
     prol = None if mode == ops.PRO_NONE else (g(sc), g(sh), mode) if mode != ops.PRO_LRELU else (None, None, mode)
     y = ops.conv(xv, ops.pack_conv_weight(g(w), prec=ops.PREC_16X1), 3, Cout, mfma=True, pro=prol, bias=g(bias), prec=ops.PREC_16X1).to_nchw()
@@ -112,6 +79,7 @@ def test_fused_skip_launch(B, H, W, Cin, Cout, tile):
     bias, bias_s = torch.randn(Cout, generator=gen), torch.randn(Cout, generator=gen)
     sc, sh = torch.rand(B, Cin, generator=gen) + 0.5, torch.randn(B, Cin, generator=gen)
     xv, w2p = ops.View.from_nchw(g(x)), ops.pack_conv_weight(g(w2))
+    assert ops.TILE_NAMES[ops.conv_tile(xv, Cout, skip=True)] == tile.split()[0]
     assert ops.fused_skip_ok(xv, Cout, ops.PRO_AFFINE_SILU) and ops.conv_prec_supported(xv, Cout, ops.PRO_AFFINE_SILU, ops.PREC_16X1, skip=True)
     assert _fused_launch_splits(xv, Cout) == ('split-K' in tile)         # the split-K case really is one
     pro = (g(sc), g(sh), ops.PRO_AFFINE_SILU)

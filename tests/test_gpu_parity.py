@@ -427,6 +427,8 @@ def test_conv_with_fused_skip_conv(B, H, W, Cin, Cout):
     bias, bias_s, b2 = torch.randn(Cout, generator=gen), torch.randn(Cout, generator=gen), torch.randn(B, Cout, generator=gen)
     sc, sh = torch.rand(B, Cin, generator=gen) + 0.5, torch.randn(B, Cin, generator=gen)
     xv, wp, w2p = ops.View.from_nchw(g(x)), ops.pack_conv_weight(g(w)), ops.pack_conv_weight(g(w2))
+    # the three tile variants the docstring names, through the query (mud_conv2d_mfma_tile); every other shape of the table: 4-row
+    assert ops.TILE_NAMES[ops.conv_tile(xv, Cout, skip=True)] == {(16, 64, 64, 384, 256): '8X2', (8, 128, 128, 192, 64): '16X1'}.get((B, H, W, Cin, Cout), 'MT1')
     assert ops.fused_skip_ok(xv, Cout, ops.PRO_AFFINE_SILU)       # (also where the launch is split over K: both accumulator sets go through the slabs)
     arena = ops.StatsArena(torch.device(DEV))
     out, skip = ops.View.empty(B, H, W, Cout, DEV, arena), ops.View.empty(B, H, W, Cout + 8, DEV).slice(4, Cout)
