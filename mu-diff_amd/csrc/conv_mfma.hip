@@ -1582,233 +1582,295 @@ static int cm_splits(int64_t blocks, int nchunks) {
   return ns;
 }
 
-template <int KS, int MT, int WM, int WN, int PRO, bool DUAL = false, int PREC = MUD_PREC_16X3>
-static int cm_launch_pro(const mud_conv_args& a, hipStream_t s) {
-  using G = typename std::conditional<KS == 3, CmGeo<KS, MT, WM, WN, DUAL, PREC>, CmGeoRegB<KS, MT>>::type;
-  const void* kfn;
-  if constexpr (KS == 3) kfn = (const void*)k_conv_mfma<KS, MT, WM, WN, PRO, DUAL, PREC>;      // only the variant that is launched is instantiated
-  else kfn = (const void*)k_conv_mfma_regb<KS, MT, PRO>;
-  static mud_attr_once attr_once;
-  int up_bytes = 0;                             // in_up2: the low-resolution scratch, in front of the GroupNorm arrays
-  if constexpr (PRO == MUD_PRO_UP2_AFFINE_SILU) up_bytes = G::UP_BYTES;
-  if (attr_once.need()) {
-    hipError_t e = hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_MAX + up_bytes);
+// ---- Host side.  A kernel is registered in ONE place, kCmRows below: the dispatcher launches what it finds there, and every query
+// (mud_conv2d_mfma_tile, *_supported, mud_conv2d_mfma_prec_supported) asks the same lookup, so neither can name a kernel that the
+// other does not have.  A tile's geometry is written once too (kCmTile).
+// The workgroup tiles by MUD_TILE_* (mudiff_hip.h), then the 1x1 kernel's: the kernels' template arguments MT (32-pixel rows per wave;
+// 1x1: 128-pixel groups per workgroup) and WM x WN (waves along the rows x along the 64-channel tiles), and what follows from them.
+struct CmTile {
+  int mt, wm, wn;
+  constexpr int threads() const { return 64 * wm * wn; }
+  constexpr int rows() const { return wm * mt; }                    // 3x3: image rows per workgroup (x 32 pixels)
+  constexpr int cols() const { return CM_BN * wn; }                 // output channels per workgroup
+  constexpr int acc_words(bool dual) const { return threads() * 32 * mt * (dual ? 2 : 1); }   // fp32 accumulators per workgroup = one split-K slab tile
+};
+enum { CM_TILE_1X1 = MUD_TILE_8X1R + 1, CM_NTILE };
+static_assert(MUD_TILE_8X2 == 0 && MUD_TILE_16X1 == 1 && MUD_TILE_MT2 == 2 && MUD_TILE_MT1 == 3 && MUD_TILE_8X1R == 4, "kCmTile's order");
+constexpr CmTile kCmTile[CM_NTILE] = {{2, 4, 2}, {2, 8, 1}, {2, 4, 1}, {1, 4, 1}, {1, 8, 1}, {1, 4, 1}};
+
+static int cm_reserve_lds(mud_attr_once& once, const void* kfn, int bytes) {
+  if (once.need()) {
+    hipError_t e = hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     if (e != hipSuccess) {
-      mud_set_error("mud_conv2d_mfma: cannot reserve %d B of LDS: %s", G::LDS_MAX + up_bytes, hipGetErrorString(e));
+      mud_set_error("mud_conv2d_mfma: cannot reserve %d B of LDS: %s", bytes, hipGetErrorString(e));
       return MUD_ERR_LAUNCH;
     }
-    attr_once.ok();
+    once.ok();
   }
-  const int k16s = (int)mud_cdiv(a.Cin, 16), ntiles = (int)mud_cdiv(a.Cout, CM_BN * WN);
-  const int lds = G::lds_bytes((PRO == MUD_PRO_AFFINE || PRO == MUD_PRO_AFFINE_SILU || PRO == MUD_PRO_UP2_AFFINE_SILU) ? a.Cin : 0) + up_bytes;   // scale | shift arrays of the sample: always in LDS
-  int tiles_x = 1;
-  int64_t tiles;
-  if (KS == 3) {
-    tiles_x = (int)mud_cdiv(a.W, 32);
-    tiles = (int64_t)tiles_x * mud_cdiv(a.H, WM * MT);
-  } else {
-    tiles = mud_cdiv((int64_t)a.H * a.W, G::P);
-  }
-  int64_t nblocks = tiles * ntiles * a.B;
+  return MUD_OK;
+}
+// the prologues whose scale | shift arrays of the sample sit in LDS
+constexpr bool cm_pro_affine(int pro) { return pro == MUD_PRO_AFFINE || pro == MUD_PRO_AFFINE_SILU || pro == MUD_PRO_UP2_AFFINE_SILU; }
+
+// split-K of one 3x3 launch (small grids): ns K slices (1 = unsplit), reduced by the last workgroup of each tile (in_launch: arrival
+// counters, one per output tile, zero between launches) or by k_splitk_epilogue.  Needs the caller's slab workspace, a plain epilogue
+// and whole float4 channel columns; the fused skip conv has two accumulator sets, which only the in-launch reduction handles.
+struct CmSplit { int ns; bool in_launch; };
+static CmSplit cm_plan_split(const mud_conv_args& a, int64_t nblocks, int k16s, bool dual, int acc_words) {
+  static const bool two_launches = getenv("MUD_CONV_SPLITK_2LAUNCH") != nullptr;   // A/B knob
+  CmSplit sp = {1, !two_launches && a.splitk_counters && nblocks <= a.splitk_ncounters};
+  if ((!dual || sp.in_launch) && a.splitk_ws && mud_aligned16(a.splitk_ws) && cm_split_eligible(a)) sp.ns = cm_splits(nblocks, k16s);
+  if (sp.ns > 1 && a.splitk_ws_bytes < cm_slab_bytes(sp.ns, nblocks, acc_words)) sp.ns = 1;      // workspace too small: run unsplit
+  return sp;
+}
+
+template <int TILE, int PRO, bool DUAL, int PREC>
+static int cm_launch3(const mud_conv_args& a, hipStream_t s) {
+  constexpr CmTile T = kCmTile[TILE];
+  constexpr auto kfn = k_conv_mfma<3, T.mt, T.wm, T.wn, PRO, DUAL, PREC>;      // only the rows of kCmRows are instantiated
+  using G = CmGeo<3, T.mt, T.wm, T.wn, DUAL, PREC>;
+  constexpr int up_bytes = PRO == MUD_PRO_UP2_AFFINE_SILU ? G::UP_BYTES : 0;   // in_up2: the low-resolution scratch, in front of the GroupNorm arrays
+  static mud_attr_once attr_once;
+  if (const int rc = cm_reserve_lds(attr_once, (const void*)kfn, G::LDS_MAX + up_bytes)) return rc;
+  const int k16s = (int)mud_cdiv(a.Cin, 16), ntiles = (int)mud_cdiv(a.Cout, T.cols());
+  const int lds = G::lds_bytes(cm_pro_affine(PRO) ? a.Cin : 0) + up_bytes;
+  const int tiles_x = (int)mud_cdiv(a.W, 32);
+  const int64_t tiles = (int64_t)tiles_x * mud_cdiv(a.H, T.rows());
+  const int64_t nblocks = tiles * ntiles * a.B;
   MUD_REQUIRE(nblocks <= 0x7fffffff, "mud_conv2d_mfma: grid too large");
-  if constexpr (KS == 3) {
-    // split-K (small grids): needs the caller's slab workspace, a plain epilogue and whole float4 channel columns
-    const int64_t npix = (int64_t)a.B * a.H * a.W;
-    int ns = 1;
-    static const bool two_launches = getenv("MUD_CONV_SPLITK_2LAUNCH") != nullptr;   // A/B knob
-    const bool in_launch = !two_launches && a.splitk_counters && nblocks <= a.splitk_ncounters;
-    // (the fused skip conv has two accumulator sets: only the in-launch reduction handles it)
-    if ((!DUAL || in_launch) && a.splitk_ws && mud_aligned16(a.splitk_ws) && cm_split_eligible(a)) ns = cm_splits(nblocks, k16s);
-    if (ns > 1 && a.splitk_ws_bytes < cm_slab_bytes(ns, nblocks, 64 * WM * WN * 32 * MT * (DUAL ? 2 : 1))) ns = 1;      // workspace too small: run unsplit
-    MUD_REQUIRE(ns == 1 || !a.res_up2, "mud_conv2d_mfma: res_up2 is not built for a launch split over K (ask mud_conv2d_mfma_res_up2_supported first)");
-    MUD_REQUIRE(ns == 1 || !a.in_up2, "mud_conv2d_mfma: in_up2 is not built for a launch split over K (ask mud_conv2d_mfma_in_up2_supported first)");
-    MUD_REQUIRE(ns == 1 || !a.in_s2d, "mud_conv2d_mfma: in_s2d is not built for a launch split over K (ask mud_conv2d_mfma_in_s2d_supported first)");
-    if (ns > 1) {
-      mud_conv_args p = a;                       // raw partial sums: no epilogue terms, output = slab ksi of the workspace
-      p.out = (float*)a.splitk_ws;
-      p.ldo = a.Cout;
-      p.bias = p.bias2 = p.res = nullptr;
-      p.out_scale = 1.0f;
-      p.act = MUD_ACT_NONE;
-      p.stats = nullptr;
-      const int64_t stride = npix * a.Cout;
-      // with arrival counters (one per output tile, zero between launches) the last workgroup of each tile reduces the slabs itself
-      if (in_launch) {
-        hipLaunchKernelGGL((k_conv_mfma<KS, MT, WM, WN, PRO, DUAL, PREC>), dim3((unsigned)(nblocks * ns)), dim3(64 * WM * WN), lds, s, a, tiles_x,
-                           (int)tiles, ntiles, k16s, (unsigned)(nblocks * ns), ns, (int64_t)0, CmFin{(float*)a.splitk_ws, a.splitk_counters});
-        MUD_CHECK_LAUNCH("mud_conv2d_mfma(split-K, reduced in the launch)");
-        return MUD_OK;
-      }
-      hipLaunchKernelGGL((k_conv_mfma<KS, MT, WM, WN, PRO, DUAL, PREC>), dim3((unsigned)(nblocks * ns)), dim3(64 * WM * WN), lds, s, p, tiles_x,
-                         (int)tiles, ntiles, k16s, (unsigned)(nblocks * ns), ns, stride, CmFin{nullptr, nullptr});
-      MUD_CHECK_LAUNCH("mud_conv2d_mfma(split-K)");
-      const int64_t HW = (int64_t)a.H * a.W;
-      int ppb = 32;                              // pixels per block of the reduce: a divisor of H*W (one sample per block)
-      while (ppb > 1 && HW % ppb) ppb >>= 1;
-      hipLaunchKernelGGL(k_splitk_epilogue, dim3((unsigned)mud_cdiv(npix, ppb)), dim3(256), 0, s, a, (const float*)a.splitk_ws, ns, stride, a.Cout,
-                         npix, ppb);
-      MUD_CHECK_LAUNCH("mud_conv2d_mfma(split-K epilogue)");
-      return MUD_OK;
-    }
-    hipLaunchKernelGGL((k_conv_mfma<KS, MT, WM, WN, PRO, DUAL, PREC>), dim3((unsigned)nblocks), dim3(64 * WM * WN), lds, s, a, tiles_x, (int)tiles,
-                       ntiles, k16s, (unsigned)nblocks, 1, (int64_t)0, CmFin{nullptr, nullptr});
-  } else
-    hipLaunchKernelGGL((k_conv_mfma_regb<KS, MT, PRO>), dim3((unsigned)nblocks), dim3(256), lds, s, a, tiles_x, (int)tiles, ntiles, k16s,
-                       (unsigned)nblocks);
+  const CmSplit sp = cm_plan_split(a, nblocks, k16s, DUAL, T.acc_words(DUAL));
+  const int ns = sp.ns;
+  const dim3 grid((unsigned)(nblocks * ns)), block(T.threads());
+  MUD_REQUIRE(ns == 1 || !a.res_up2, "mud_conv2d_mfma: res_up2 is not built for a launch split over K (ask mud_conv2d_mfma_res_up2_supported first)");
+  MUD_REQUIRE(ns == 1 || !a.in_up2, "mud_conv2d_mfma: in_up2 is not built for a launch split over K (ask mud_conv2d_mfma_in_up2_supported first)");
+  MUD_REQUIRE(ns == 1 || !a.in_s2d, "mud_conv2d_mfma: in_s2d is not built for a launch split over K (ask mud_conv2d_mfma_in_s2d_supported first)");
+  if (ns == 1 || sp.in_launch) {                 // unsplit, or split with the slabs reduced by the last workgroup of each tile
+    const CmFin fin = ns > 1 ? CmFin{(float*)a.splitk_ws, a.splitk_counters} : CmFin{nullptr, nullptr};
+    hipLaunchKernelGGL(kfn, grid, block, lds, s, a, tiles_x, (int)tiles, ntiles, k16s, grid.x, ns, (int64_t)0, fin);
+    MUD_CHECK_LAUNCH(ns > 1 ? "mud_conv2d_mfma(split-K, reduced in the launch)" : "mud_conv2d_mfma");
+    return MUD_OK;
+  }
+  mud_conv_args p = a;                           // raw partial sums: no epilogue terms, output = slab ksi of the workspace
+  p.out = (float*)a.splitk_ws;
+  p.ldo = a.Cout;
+  p.bias = p.bias2 = p.res = nullptr;
+  p.out_scale = 1.0f;
+  p.act = MUD_ACT_NONE;
+  p.stats = nullptr;
+  const int64_t npix = (int64_t)a.B * a.H * a.W, stride = npix * a.Cout;
+  hipLaunchKernelGGL(kfn, grid, block, lds, s, p, tiles_x, (int)tiles, ntiles, k16s, grid.x, ns, stride, CmFin{nullptr, nullptr});
+  MUD_CHECK_LAUNCH("mud_conv2d_mfma(split-K)");
+  const int64_t HW = (int64_t)a.H * a.W;
+  int ppb = 32;                                  // pixels per block of the reduce: a divisor of H*W (one sample per block)
+  while (ppb > 1 && HW % ppb) ppb >>= 1;
+  hipLaunchKernelGGL(k_splitk_epilogue, dim3((unsigned)mud_cdiv(npix, ppb)), dim3(256), 0, s, a, (const float*)a.splitk_ws, ns, stride, a.Cout, npix, ppb);
+  MUD_CHECK_LAUNCH("mud_conv2d_mfma(split-K epilogue)");
+  return MUD_OK;
+}
+
+// 1x1 GEMMs: 128-pixel tiles (MT = 1) beat 256-pixel tiles (MT = 2) by 5-8 % on every skip-conv / NIN shape at batch 16
+// (scripts/bench_conv.py) - these launches are HBM-bound and the smaller tile keeps more of them in flight; the larger are no longer built
+template <int PRO>
+static int cm_launch1(const mud_conv_args& a, hipStream_t s) {
+  constexpr CmTile T = kCmTile[CM_TILE_1X1];
+  constexpr auto kfn = k_conv_mfma_regb<1, T.mt, PRO>;
+  using G = CmGeoRegB<1, T.mt>;
+  static mud_attr_once attr_once;
+  if (const int rc = cm_reserve_lds(attr_once, (const void*)kfn, G::LDS_MAX)) return rc;
+  const int k16s = (int)mud_cdiv(a.Cin, 16), ntiles = (int)mud_cdiv(a.Cout, T.cols());
+  const int64_t tiles = mud_cdiv((int64_t)a.H * a.W, G::P), nblocks = tiles * ntiles * a.B;
+  MUD_REQUIRE(nblocks <= 0x7fffffff, "mud_conv2d_mfma: grid too large");
+  hipLaunchKernelGGL(kfn, dim3((unsigned)nblocks), dim3(T.threads()), G::lds_bytes(cm_pro_affine(PRO) ? a.Cin : 0), s, a, 1, (int)tiles, ntiles, k16s,
+                     (unsigned)nblocks);
   MUD_CHECK_LAUNCH("mud_conv2d_mfma");
   return MUD_OK;
 }
 
-template <int KS, int MT, int WM = 4, int WN = 1, int PREC = MUD_PREC_16X3>
-static int cm_launch(const mud_conv_args& a, hipStream_t s) {
-  switch (a.pro_mode) {
-    case MUD_PRO_NONE: return cm_launch_pro<KS, MT, WM, WN, MUD_PRO_NONE, false, PREC>(a, s);
-    case MUD_PRO_AFFINE: return cm_launch_pro<KS, MT, WM, WN, MUD_PRO_AFFINE, false, PREC>(a, s);
-    case MUD_PRO_LRELU: return cm_launch_pro<KS, MT, WM, WN, MUD_PRO_LRELU, false, PREC>(a, s);
-    default: return cm_launch_pro<KS, MT, WM, WN, MUD_PRO_AFFINE_SILU, false, PREC>(a, s);
-  }
-}
-
-#ifdef MUD_EXPERIMENT_WS
-#include "experiments/conv_ws.inc"
+#ifdef MUD_EXPERIMENT_WS      // scripts/build_variants.py ws:-DMUD_EXPERIMENT_WS (scripts/experiments/conv_ws.inc); never in the shipped build
+#include "conv_ws.inc"
 #endif
 
-// 3x3 tile variant by problem size: big tiles (more MFMA work per weight byte) once they still fill the 256 CUs.
+// ---- the built kernels: one row each.  Key: (tile, prologue - in_up2 and in_s2d are prologues here -, fused skip conv, plan); the
+// launcher's template arguments are the key's own tokens.  A new kernel is one more row and nothing else.
+typedef int (*CmLaunchFn)(const mud_conv_args&, hipStream_t);
+struct CmRow { int tile, pro, dual, prec; CmLaunchFn launch; };
+#define CM_ROW(T, PRO, DUAL, PREC) \
+  {MUD_TILE_##T, MUD_PRO_##PRO, DUAL, MUD_PREC_##PREC, cm_launch3<MUD_TILE_##T, MUD_PRO_##PRO, DUAL, MUD_PREC_##PREC>}
+#define CM_ROWS4(T, PREC) CM_ROW(T, NONE, false, PREC), CM_ROW(T, AFFINE, false, PREC), CM_ROW(T, LRELU, false, PREC), CM_ROW(T, AFFINE_SILU, false, PREC)
+#define CM_SKIP(T, PREC) CM_ROW(T, AFFINE_SILU, true, PREC)
+#define CM_ROW1(PRO) {CM_TILE_1X1, MUD_PRO_##PRO, false, MUD_PREC_16X3, cm_launch1<MUD_PRO_##PRO>}
+constexpr CmRow kCmRows[] = {
+    // (The kernels are emitted in the order of their rows.  These keep the order the code object had before the table existed, so its
+    // device code is the one every figure in DESIGN.md was measured on: another order moved the bench line by 0.2 %.  New rows: at the end.)
+    // in_up2: 8 x 32 px x 128 ch on eight waves under every plan (the up-sampling residual blocks' Conv_0 at 256x256 / 128x128 once the
+    // batch fills the chip) and 4 x 32 px x 64 ch on four waves under the two fp16 plans (small grids).  Any other tile keeps the FIR
+    // launch in front of the convolution.
+    CM_ROW(8X2, UP2_AFFINE_SILU, false, FP8X), CM_ROW(8X2, UP2_AFFINE_SILU, false, 16X1), CM_ROW(8X2, UP2_AFFINE_SILU, false, 16X3),
+    CM_ROW(MT1, UP2_AFFINE_SILU, false, 16X1), CM_ROW(MT1, UP2_AFFINE_SILU, false, 16X3),
+    // in_s2d: the same two tiles under the two fp16 plans (the input pyramid's 64 -> 128 down-sampler at 128x128 once the batch fills the
+    // chip; small models, one slice at a time)
+    CM_ROW(8X2, S2D, false, 16X1), CM_ROW(8X2, S2D, false, 16X3), CM_ROW(MT1, S2D, false, 16X1), CM_ROW(MT1, S2D, false, 16X3),
+    // MUD_PREC_FP8X: the 8-wave tiles (8 x 32 px x 128 ch, 16 x 32 px x 64 ch and the one-row tile of the 64 -> 64 layers), i.e. launches
+    // that fill the chip, with the prologues the generators use there (none: G2's gate / fusion convolutions; AdaGN + SiLU: the residual
+    // blocks, with or without the fused skip conv - whose own centre-tap products stay 16-bit x 3)
+    CM_ROW(8X1R, NONE, false, FP8X), CM_ROW(8X1R, AFFINE_SILU, false, FP8X), CM_SKIP(8X2, FP8X), CM_SKIP(16X1, FP8X),
+    CM_ROW(8X2, NONE, false, FP8X), CM_ROW(16X1, NONE, false, FP8X), CM_ROW(8X2, AFFINE_SILU, false, FP8X), CM_ROW(16X1, AFFINE_SILU, false, FP8X),
+    // the single-pass fp16 plan: the fused 1x1 skip conv (DUAL; the AdaGN + SiLU prologue of the residual blocks, on the three tiles
+    // cm_tile3 gives it), then every tile with every prologue
+    CM_SKIP(8X2, 16X1), CM_SKIP(16X1, 16X1), CM_SKIP(MT1, 16X1),
+    CM_ROWS4(8X2, 16X1), CM_ROWS4(16X1, 16X1), CM_ROWS4(MT2, 16X1), CM_ROWS4(8X1R, 16X1), CM_ROWS4(MT1, 16X1),
+    // fp16 x 3, the default plan: every tile with every prologue, the 1x1 kernel (this plan only), the fused skip conv
+    CM_ROWS4(8X2, 16X3), CM_ROWS4(16X1, 16X3), CM_ROWS4(MT1, 16X3), CM_ROWS4(MT2, 16X3),
+    CM_ROW1(NONE), CM_ROW1(AFFINE), CM_ROW1(LRELU), CM_ROW1(AFFINE_SILU),
+    CM_SKIP(8X2, 16X3), CM_SKIP(16X1, 16X3), CM_SKIP(MT1, 16X3),
+    CM_ROWS4(8X1R, 16X3),
+};
+
+// the rows by key, filled at compile time: a lookup is one indexed load
+enum { CM_NPRO = MUD_PRO_S2D + 1, CM_NPREC = MUD_PREC_16X1 + 1 };
+struct CmIndex { CmLaunchFn at[CM_NPREC][CM_NTILE][CM_NPRO][2]; int rows; bool twice; };
+constexpr CmIndex cm_index() {
+  CmIndex ix = {};
+  for (const CmRow& r : kCmRows) {
+    CmLaunchFn& slot = ix.at[r.prec][r.tile][r.pro][r.dual];
+    if (slot) ix.twice = true;
+    slot = r.launch;
+    ++ix.rows;
+  }
+  return ix;
+}
+constexpr CmIndex kCmIndex = cm_index();
+static_assert(kCmIndex.rows == 67 && !kCmIndex.twice, "67 kernels, each registered once (update DESIGN.md section 5.1 with the count)");
+
+// the launcher of a key, nullptr where no such kernel is built
+static CmLaunchFn cm_find(int tile, int pro, bool dual, int prec) {
+  if (tile < 0 || tile >= CM_NTILE || pro < 0 || pro >= CM_NPRO || prec < 0 || prec >= CM_NPREC) return nullptr;
+  return kCmIndex.at[prec][tile][pro][dual];
+}
+
+// 3x3 tile by problem size: big tiles (more MFMA work per weight byte) once they still fill the 256 CUs.
 // Measured on MI355X (scripts/bench_conv.py): MT=2 (two workgroups co-resident per CU, one wave of each per SIMD)
 // beats MT=4 (one workgroup per CU) by 15-40 % on every layer shape; MT=1 only when MT=2 cannot give 2 blocks/CU.
-enum { CMV_8X2 = MUD_TILE_8X2, CMV_16X1 = MUD_TILE_16X1, CMV_MT2 = MUD_TILE_MT2, CMV_MT1 = MUD_TILE_MT1, CMV_8X1R = MUD_TILE_8X1R };
-static int cm_variant3(const mud_conv_args& a, int64_t* blocks) {
-  const int64_t ntiles = mud_cdiv(a.Cout, CM_BN);
-  int64_t nb;
-  int v;
-  // 8-wave variant (8 rows x 32 px x 128 channels per workgroup, 4 x 2 waves): the staged input tile (GroupNorm +
-  // SiLU + split, the main non-MFMA cost) is shared by twice as many MFMAs; used when the layer has an even number
-  // of 64-channel tiles and still fills the chip
-  const int64_t blocks8 = mud_cdiv(a.W, 32) * mud_cdiv(a.H, 8) * (ntiles / 2) * a.B;
-  // other layers (64 or an odd number of 64-channel tiles): 8 waves stacked along the rows (16 x 32 px x 64 channels):
-  // less halo per staged pixel and the weight ring is shared by twice as many waves (+4-7 % measured)
-  const int64_t blocks16 = mud_cdiv(a.W, 32) * mud_cdiv(a.H, 16) * ntiles * a.B;
-  const int64_t blocks2 = mud_cdiv(a.W, 32) * mud_cdiv(a.H, 8) * ntiles * a.B;
-  static const bool no16 = getenv("MUD_CONV_NO16") != nullptr;   // A/B knob
+static int64_t cm_blocks(int tile, const mud_conv_args& a) {
+  return mud_cdiv(a.W, 32) * mud_cdiv(a.H, kCmTile[tile].rows()) * mud_cdiv(a.Cout, kCmTile[tile].cols()) * a.B;
+}
+static int cm_variant3(const mud_conv_args& a) {
+  const int64_t ntiles = mud_cdiv(a.Cout, CM_BN), blocks2 = cm_blocks(MUD_TILE_MT2, a);
+  static const bool no16 = getenv("MUD_CONV_NO16") != nullptr;       // A/B knob
+  static const bool no8x1r = getenv("MUD_CONV_NO8X1R") != nullptr;   // A/B knob
   // 64 -> 64 layers (four K chunks: a quarter of a workgroup's life is first fetch + epilogue): 8 waves x ONE row x 64 channels,
   // 79 KiB of LDS and 110 VGPRs, so two workgroups share a CU (four waves per SIMD) and one's residual / store phase runs
   // under the other's K loop.  Measured against the 16-row tile (profiles/r02_j_ab_8x1row.txt): with a residual 330 -> 305 us,
   // without 307 -> 303 us; deeper reductions (128 / 192 / 256 -> 64) are equal, so they keep the tile with less halo.
-  static const bool no8x1r = getenv("MUD_CONV_NO8X1R") != nullptr;   // A/B knob
-  if (!no8x1r && !a.skip_w && ntiles == 1 && a.Cin <= 64 && a.H >= 8 && blocks2 >= 512) v = CMV_8X1R, nb = blocks2;
-  else if (ntiles % 2 == 0 && a.H >= 8 && blocks8 >= 256) v = CMV_8X2, nb = blocks8;
-  else if (!no16 && a.H >= 16 && blocks16 >= 256) v = CMV_16X1, nb = blocks16;
-  else if (blocks2 >= 512 && a.H >= 8) v = CMV_MT2, nb = blocks2;
-  else v = CMV_MT1, nb = mud_cdiv(a.W, 32) * mud_cdiv(a.H, 4) * ntiles * a.B;
-  if (blocks) *blocks = nb;
-  return v;
+  if (!no8x1r && !a.skip_w && ntiles == 1 && a.Cin <= 64 && a.H >= 8 && blocks2 >= 512) return MUD_TILE_8X1R;      // (as many workgroups as MT2)
+  // 8-wave variant (8 rows x 32 px x 128 channels per workgroup, 4 x 2 waves): the staged input tile (GroupNorm +
+  // SiLU + split, the main non-MFMA cost) is shared by twice as many MFMAs; used when the layer has an even number
+  // of 64-channel tiles and still fills the chip
+  if (ntiles % 2 == 0 && a.H >= 8 && cm_blocks(MUD_TILE_8X2, a) >= 256) return MUD_TILE_8X2;
+  // other layers (64 or an odd number of 64-channel tiles): 8 waves stacked along the rows (16 x 32 px x 64 channels):
+  // less halo per staged pixel and the weight ring is shared by twice as many waves (+4-7 % measured)
+  if (!no16 && a.H >= 16 && cm_blocks(MUD_TILE_16X1, a) >= 256) return MUD_TILE_16X1;
+  return (blocks2 >= 512 && a.H >= 8) ? MUD_TILE_MT2 : MUD_TILE_MT1;
 }
 // The tile of a 3x3 launch, for the dispatcher and every query: cm_variant3's, except that the fused 1x1 skip conv (DUAL) is built
 // for three tiles - the 8-row 4-wave tile would drop to one workgroup per CU with the second image, so its small grids take the
 // 4-row tile (the one-row tile is never chosen for it)
-static int cm_tile3(const mud_conv_args& a, int64_t* blocks) {
-  int64_t nb;
-  int v = cm_variant3(a, &nb);
-  if (a.skip_w && v != CMV_8X2 && v != CMV_16X1) {
-    v = CMV_MT1;
-    nb = mud_cdiv(a.W, 32) * mud_cdiv(a.H, 4) * mud_cdiv(a.Cout, CM_BN) * a.B;
-  }
-  if (blocks) *blocks = nb;
-  return v;
+static int cm_tile3(const mud_conv_args& a) {
+  const int v = cm_variant3(a);
+  return (a.skip_w && v != MUD_TILE_8X2 && v != MUD_TILE_16X1) ? MUD_TILE_MT1 : v;
+}
+
+// MUD_CONV_MT, read once.  set: the variable exists - in_up2 / in_s2d are refused, since the knob picks tiles they may not have;
+// mt: its value - non-zero forces a tile on the plain fp16 x 3 launches (cm_launch_tile)
+struct CmKnobMT { bool set; int mt; };
+static CmKnobMT cm_knob_mt() {
+  static const char* const e = getenv("MUD_CONV_MT");
+  static const CmKnobMT k = {e != nullptr, e ? atoi(e) : 0};
+  return k;
+}
+// The tile mud_conv2d_mfma launches: cm_tile3's (the queries' answer), except where the tuning knob applies - plain 3x3 launches under
+// the default plan; the fused skip conv, the other plans and in_up2 / in_s2d keep their own tiles
+static int cm_launch_tile(const mud_conv_args& a) {
+  if (a.ks != 3) return CM_TILE_1X1;
+  const int mt = cm_knob_mt().mt;
+  if (!mt || a.skip_w || a.prec != MUD_PREC_16X3 || a.in_up2 || a.in_s2d) return cm_tile3(a);
+  return (mt == 8 && mud_cdiv(a.Cout, CM_BN) % 2 == 0) ? MUD_TILE_8X2 : mt == 16 ? MUD_TILE_16X1 : mt == 1 ? MUD_TILE_MT1 : MUD_TILE_MT2;
+}
+// the prologue of a launch as the table keys it
+static int cm_pro_key(const mud_conv_args& a) { return a.in_up2 ? MUD_PRO_UP2_AFFINE_SILU : a.in_s2d ? MUD_PRO_S2D : a.pro_mode; }
+
+static bool cm_sizes_ok(const mud_conv_args* ap) { return ap && ap->B > 0 && ap->H > 0 && ap->W > 0 && ap->Cin > 0 && ap->Cout > 0; }
+// would this 3x3 launch be cut over K, whatever workspace the caller has?  (res_up2 / in_up2 / in_s2d leave such a launch alone)
+static bool cm_may_split(const mud_conv_args& a, int* tile) {
+  *tile = cm_tile3(a);
+  return cm_splits(cm_blocks(*tile, a), (int)mud_cdiv(a.Cin, 16)) > 1;
 }
 
 extern "C" int64_t mud_conv2d_mfma_splitk_bytes(const mud_conv_args* ap) {
-  if (!ap || ap->ks != 3 || ap->B <= 0 || ap->H <= 0 || ap->W <= 0 || ap->Cin <= 0 || ap->Cout <= 0 || !cm_split_eligible(*ap)) return 0;
+  if (!cm_sizes_ok(ap) || ap->ks != 3 || !cm_split_eligible(*ap)) return 0;
   if (ap->skip_w && !ap->splitk_counters) return 0;   // the fused skip conv: two accumulator sets, the in-launch reduction only
-  int64_t blocks = 0;
-  const int v = cm_tile3(*ap, &blocks);
+  const int v = cm_tile3(*ap);
+  const int64_t blocks = cm_blocks(v, *ap);
   const int ns = cm_splits(blocks, (int)mud_cdiv(ap->Cin, 16));
-  const int tile_words = ((v == CMV_8X2 || v == CMV_16X1) ? 512 * 64 : v == CMV_MT2 ? 256 * 64 : v == CMV_8X1R ? 512 * 32 : 256 * 32) * (ap->skip_w ? 2 : 1);   // threads x accumulators
-  return ns > 1 ? cm_slab_bytes(ns, blocks, tile_words) : 0;
+  return ns > 1 ? cm_slab_bytes(ns, blocks, kCmTile[v].acc_words(ap->skip_w != nullptr)) : 0;
 }
 
-// res_up2 lives where the residual is loaded into the accumulators (the 3x3 kernel, no sub2, no fused skip conv, no split-K), in the
-// instantiations of the AdaGN + SiLU prologue: the residual blocks' Conv_1
+// res_up2 lives where the residual is loaded into the accumulators (the 3x3 kernel, no sub2, no fused skip conv, no split-K), in every
+// row with the AdaGN + SiLU prologue: the residual blocks' Conv_1
 extern "C" int mud_conv2d_mfma_res_up2_supported(const mud_conv_args* ap) {
-  if (!ap || ap->ks != 3 || ap->stride != 1 || ap->pad != 1 || ap->sub2 || ap->skip_w || ap->pro_mode != MUD_PRO_AFFINE_SILU) return 0;
-  if (ap->B <= 0 || ap->H <= 0 || ap->W <= 0 || ap->Cin <= 0 || ap->Cout <= 0 || (ap->H & 1) || (ap->W & 1)) return 0;
-  int64_t blocks = 0;
-  cm_tile3(*ap, &blocks);
-  return cm_splits(blocks, (int)mud_cdiv(ap->Cin, 16)) == 1;      // (whatever workspace the caller has: a launch that may split is left alone)
+  if (!cm_sizes_ok(ap) || ap->ks != 3 || ap->stride != 1 || ap->pad != 1 || ap->sub2 || ap->skip_w || ap->pro_mode != MUD_PRO_AFFINE_SILU) return 0;
+  int v;
+  return !(ap->H & 1) && !(ap->W & 1) && !cm_may_split(*ap, &v);
 }
 
-// in_up2 (MUD_PRO_UP2_AFFINE_SILU) is built for two tiles: 8 x 32 px x 128 ch on eight waves under every plan (the up-sampling
-// residual blocks' Conv_0 at 256x256 / 128x128 once the batch fills the chip) and 4 x 32 px x 64 ch on four waves under the two
-// fp16 plans (small grids; MUD_PREC_FP8X has no such tile).  Any other tile keeps the FIR launch in front of the convolution.
-static bool cm_in_up2_built(int variant, int prec) {
-  if (variant == CMV_8X2) return prec == MUD_PREC_16X3 || prec == MUD_PREC_FP8X || prec == MUD_PREC_16X1;
-  return variant == CMV_MT1 && (prec == MUD_PREC_16X3 || prec == MUD_PREC_16X1);
-}
 // H, W: the OUTPUT size (twice the size of x).  Like res_up2: the 3x3 kernel, no sub2, no fused skip conv, no split-K.
 extern "C" int mud_conv2d_mfma_in_up2_supported(const mud_conv_args* ap) {
-  if (!ap || ap->ks != 3 || ap->stride != 1 || ap->pad != 1 || ap->sub2 || ap->skip_w || ap->res_up2 || ap->pro_mode != MUD_PRO_AFFINE_SILU) return 0;
-  if (ap->B <= 0 || ap->H <= 0 || ap->W <= 0 || ap->Cin <= 0 || ap->Cout <= 0 || (ap->H & 1) || (ap->W & 1)) return 0;
-  static const bool forced_tile = getenv("MUD_CONV_MT") != nullptr;             // (the tuning knob picks tiles this form may not have)
-  if (forced_tile) return 0;
-  int64_t blocks = 0;
-  const int v = cm_tile3(*ap, &blocks);
-  return cm_in_up2_built(v, ap->prec) && cm_splits(blocks, (int)mud_cdiv(ap->Cin, 16)) == 1;
+  if (!cm_sizes_ok(ap) || ap->ks != 3 || ap->stride != 1 || ap->pad != 1 || ap->sub2 || ap->skip_w || ap->res_up2 || ap->pro_mode != MUD_PRO_AFFINE_SILU) return 0;
+  if ((ap->H & 1) || (ap->W & 1) || cm_knob_mt().set) return 0;
+  int v;
+  return !cm_may_split(*ap, &v) && cm_find(v, MUD_PRO_UP2_AFFINE_SILU, false, ap->prec);
 }
 
-// in_s2d (MUD_PRO_S2D) is built for the same two tiles under the two fp16 plans: 8 x 32 px x 128 ch on eight waves (the input pyramid's
-// 64 -> 128 down-sampler at 128x128 once the batch fills the chip) and 4 x 32 px x 64 ch on four waves (small models, one slice at a time).
-static bool cm_in_s2d_built(int variant, int prec) {
-  return (variant == CMV_8X2 || variant == CMV_MT1) && (prec == MUD_PREC_16X3 || prec == MUD_PREC_16X1);
-}
 // H, W, Cin: the folded view's.  The 3x3 kernel without prologue, sub2, fused skip conv, res_up2, in_up2; whole 16-channel chunks per parity.
 static bool cm_in_s2d_form(const mud_conv_args& a) {
   return a.ks == 3 && a.stride == 1 && a.pad == 1 && !a.sub2 && !a.skip_w && !a.res_up2 && !a.in_up2 && a.pro_mode == MUD_PRO_NONE && a.Cin > 0 && a.Cin % 64 == 0;
 }
 extern "C" int mud_conv2d_mfma_in_s2d_supported(const mud_conv_args* ap) {
-  if (!ap || !cm_in_s2d_form(*ap) || ap->B <= 0 || ap->H <= 0 || ap->W <= 0 || ap->Cout <= 0) return 0;
-  static const bool forced_tile = getenv("MUD_CONV_MT") != nullptr;             // (the tuning knob picks tiles this form may not have)
-  if (forced_tile) return 0;
-  int64_t blocks = 0;
-  const int v = cm_tile3(*ap, &blocks);
-  return cm_in_s2d_built(v, ap->prec) && cm_splits(blocks, (int)mud_cdiv(ap->Cin, 16)) == 1;
+  if (!cm_sizes_ok(ap) || !cm_in_s2d_form(*ap) || cm_knob_mt().set) return 0;
+  int v;
+  return !cm_may_split(*ap, &v) && cm_find(v, MUD_PRO_S2D, false, ap->prec);
 }
 
-// MUD_PREC_FP8X is built for the 8-wave tiles (8 x 32 px x 128 ch, 16 x 32 px x 64 ch, and the one-row 8 x 32 px x 64 ch tile of the
-// 64 -> 64 layers), i.e. for launches that fill the chip, with the prologues the generators use there (none: G2's gate / fusion
-// convolutions; AdaGN + SiLU: the residual blocks, with or without the fused skip conv - whose own centre-tap products stay 16-bit x 3).
-static bool cm_fp8x_built(const mud_conv_args& a) {
-  if (a.ks != 3 || a.sub2 || (a.pro_mode != MUD_PRO_NONE && a.pro_mode != MUD_PRO_AFFINE_SILU)) return false;
-  if (a.skip_w && a.pro_mode != MUD_PRO_AFFINE_SILU) return false;
-  const int v = cm_tile3(a, nullptr);
-  return v == CMV_8X2 || v == CMV_16X1 || v == CMV_8X1R;
-}
 // The tile the dispatcher below launches (mudiff_hip.h): cm_tile3's; -1 where a form is not built for it.  Host only.
 extern "C" int mud_conv2d_mfma_tile(const mud_conv_args* ap) {
-  if (!ap || ap->ks != 3 || ap->B <= 0 || ap->H <= 0 || ap->W <= 0 || ap->Cin <= 0 || ap->Cout <= 0) return -1;
-  const int v = cm_tile3(*ap, nullptr);
-  if (ap->in_up2 && !cm_in_up2_built(v, ap->prec)) return -1;
-  if (ap->in_s2d && !cm_in_s2d_built(v, ap->prec)) return -1;
+  if (!cm_sizes_ok(ap) || ap->ks != 3) return -1;
+  const int v = cm_tile3(*ap);
+  if (ap->in_up2 && !cm_find(v, MUD_PRO_UP2_AFFINE_SILU, false, ap->prec)) return -1;
+  if (ap->in_s2d && !cm_find(v, MUD_PRO_S2D, false, ap->prec)) return -1;
   return v;
 }
 
-// MUD_PREC_16X1 is built for every 3x3 launch: every tile, every prologue, the fused skip conv (AdaGN + SiLU prologue, as always),
-// split-K and sub2.  No 1x1 form.
+// MUD_PREC_16X3 is the plan of every launch; the other two have the rows of kCmRows: MUD_PREC_16X1 every 3x3 launch (sub2 and split-K
+// included), MUD_PREC_FP8X the 3x3 launches on its tiles and prologues, without sub2.  Neither has a 1x1 form.  (pro_mode is one of the
+// four modes a caller may set: the in_up2 / in_s2d keys are not values of it, as in the dispatcher.)
+static bool cm_prec_built(const mud_conv_args& a, int prec) {
+  return a.ks == 3 && a.pro_mode >= MUD_PRO_NONE && a.pro_mode <= MUD_PRO_LRELU && !(a.sub2 && prec == MUD_PREC_FP8X) &&
+         cm_find(cm_tile3(a), a.pro_mode, a.skip_w != nullptr, prec);
+}
 extern "C" int mud_conv2d_mfma_prec_supported(const mud_conv_args* ap, int prec) {
-  if (!ap || ap->B <= 0 || ap->H <= 0 || ap->W <= 0 || ap->Cin <= 0 || ap->Cout <= 0) return 0;
+  if (!cm_sizes_ok(ap)) return 0;
   if (prec == MUD_PREC_16X3) return ap->ks == 1 || ap->ks == 3;
-  if (prec == MUD_PREC_16X1)
-    return ap->ks == 3 && ap->pro_mode >= MUD_PRO_NONE && ap->pro_mode <= MUD_PRO_LRELU && (!ap->skip_w || ap->pro_mode == MUD_PRO_AFFINE_SILU);
-  mud_conv_args a = *ap;
-  a.prec = prec;                                 // (the tile choice looks at it)
-  return prec == MUD_PREC_FP8X && cm_fp8x_built(a);
+  return (prec == MUD_PREC_16X1 || prec == MUD_PREC_FP8X) && cm_prec_built(*ap, prec);
 }
 
+// Validate, choose the tile (cm_launch_tile), look the kernel up (cm_find), launch it - or say which form or plan has no such kernel.
 extern "C" int mud_conv2d_mfma(const mud_conv_args* ap, void* stream) {
   MUD_REQUIRE(ap, "mud_conv2d_mfma: null args");
   mud_conv_args a = *ap;
   MUD_REQUIRE(a.x && a.w && a.out, "mud_conv2d_mfma: null pointer");
   MUD_REQUIRE((a.ks == 1 || a.ks == 3) && a.stride == 1 && a.pad == a.ks / 2, "mud_conv2d_mfma: only ks in {1,3}, stride 1, pad ks/2 (got ks=%d stride=%d pad=%d)", a.ks, a.stride, a.pad);
   MUD_REQUIRE(a.B >= 0 && a.H > 0 && a.W > 0 && a.Cin > 0 && a.Cout > 0, "mud_conv2d_mfma: bad sizes");
+  const CmLaunchFn launch = cm_find(cm_launch_tile(a), cm_pro_key(a), a.skip_w != nullptr, a.prec);      // (nullptr: refused below, by form, then by plan)
   if (a.in_s2d) {                                // (before the plain size checks: x is [B, 2H, 2W, Cin / 4] with its own ldx)
     MUD_REQUIRE(cm_in_s2d_form(a),
                 "mud_conv2d_mfma: in_s2d needs ks == 3, no prologue, no sub2 / fused skip conv / res_up2 / in_up2 and Cin %% 64 == 0 (ks=%d sub2=%d pro_mode=%d Cin=%d)",
@@ -1817,9 +1879,7 @@ extern "C" int mud_conv2d_mfma(const mud_conv_args* ap, void* stream) {
     MUD_REQUIRE(4 * (int64_t)a.H * a.W * a.ldx < 0x7fffffffLL, "mud_conv2d_mfma: in_s2d: one full-resolution image must stay below 2^31 elements");
     MUD_REQUIRE(a.prec == MUD_PREC_16X3 || a.prec == MUD_PREC_16X1, "mud_conv2d_mfma: in_s2d is built for the two fp16 plans only (prec=%d)", a.prec);
     MUD_REQUIRE(a.w_exp >= -100 && a.w_exp <= 100, "mud_conv2d_mfma: in_s2d: w_exp (the weights' power-of-two pre-scale) out of range (%d)", a.w_exp);
-    static const bool forced_tile = getenv("MUD_CONV_MT") != nullptr;
-    MUD_REQUIRE(!forced_tile && cm_in_s2d_built(cm_tile3(a, nullptr), a.prec),
-                "mud_conv2d_mfma: in_s2d is not built for the tile of this launch (ask mud_conv2d_mfma_in_s2d_supported first)");
+    MUD_REQUIRE(!cm_knob_mt().set && launch, "mud_conv2d_mfma: in_s2d is not built for the tile of this launch (ask mud_conv2d_mfma_in_s2d_supported first)");
   } else {
     MUD_REQUIRE(a.Cin % 4 == 0 && a.ldx % 4 == 0 && a.ldx >= a.Cin && mud_aligned16(a.x), "mud_conv2d_mfma: needs Cin%%4==0 (Cin=%d), ldx%%4==0 (ldx=%d), 16-byte aligned x", a.Cin, a.ldx);
     MUD_REQUIRE((int64_t)a.H * a.W * a.ldx < 0x7fffffffLL, "mud_conv2d_mfma: one image must stay below 2^31 elements");
@@ -1865,82 +1925,15 @@ extern "C" int mud_conv2d_mfma(const mud_conv_args* ap, void* stream) {
     MUD_REQUIRE(a.ks == 3 && !a.sub2 && !a.skip_w && !a.res_up2 && (a.H & 1) == 0 && (a.W & 1) == 0 && a.pro_mode == MUD_PRO_AFFINE_SILU,
                 "mud_conv2d_mfma: in_up2 needs ks == 3, the AFFINE_SILU prologue, no sub2 / fused skip conv / res_up2 and even H, W (ks=%d H=%d W=%d sub2=%d pro_mode=%d)",
                 a.ks, a.H, a.W, a.sub2, a.pro_mode);
-    MUD_REQUIRE(cm_in_up2_built(cm_tile3(a, nullptr), a.prec),
-                "mud_conv2d_mfma: in_up2 is not built for the tile / arithmetic plan of this launch (prec=%d; ask mud_conv2d_mfma_in_up2_supported first)", a.prec);
+    MUD_REQUIRE(launch, "mud_conv2d_mfma: in_up2 is not built for the tile / arithmetic plan of this launch (prec=%d; ask mud_conv2d_mfma_in_up2_supported first)", a.prec);
   }
-  MUD_REQUIRE(a.prec != MUD_PREC_16X1 || a.ks == 3, "mud_conv2d_mfma: MUD_PREC_16X1 is built for ks == 3 only (got ks=%d)", a.ks);
-  MUD_REQUIRE(a.prec != MUD_PREC_FP8X || (cm_fp8x_built(a) && a.w_exp >= -100 && a.w_exp <= 100),
+  MUD_REQUIRE(a.prec != MUD_PREC_16X1 || launch, "mud_conv2d_mfma: MUD_PREC_16X1 is not built for this launch (no 1x1 form; ks=%d pro_mode=%d)", a.ks, a.pro_mode);
+  MUD_REQUIRE(a.prec != MUD_PREC_FP8X || (launch && !a.sub2 && a.w_exp >= -100 && a.w_exp <= 100),
               "mud_conv2d_mfma: MUD_PREC_FP8X is not built for this launch (ask mud_conv2d_mfma_prec_supported first; the weights were packed for it and cannot be read by another plan)");
+  MUD_REQUIRE(launch, "mud_conv2d_mfma: no kernel is built for this launch (ks=%d pro_mode=%d prec=%d)", a.ks, a.pro_mode, a.prec);
   if (a.B == 0) return MUD_OK;
-  hipStream_t s = (hipStream_t)stream;
-  if (a.in_up2) {                                // (tile and plan checked above: cm_in_up2_built)
-    constexpr int PU = MUD_PRO_UP2_AFFINE_SILU;
-    if (cm_tile3(a, nullptr) == CMV_8X2)
-      return a.prec == MUD_PREC_FP8X   ? cm_launch_pro<3, 2, 4, 2, PU, false, MUD_PREC_FP8X>(a, s)
-             : a.prec == MUD_PREC_16X1 ? cm_launch_pro<3, 2, 4, 2, PU, false, MUD_PREC_16X1>(a, s)
-                                       : cm_launch_pro<3, 2, 4, 2, PU>(a, s);
-    return a.prec == MUD_PREC_16X1 ? cm_launch_pro<3, 1, 4, 1, PU, false, MUD_PREC_16X1>(a, s) : cm_launch_pro<3, 1, 4, 1, PU>(a, s);
-  }
-  if (a.in_s2d) {                                // (form, tile and plan checked above: cm_in_s2d_form, cm_in_s2d_built)
-    constexpr int PS = MUD_PRO_S2D;
-    if (cm_tile3(a, nullptr) == CMV_8X2)
-      return a.prec == MUD_PREC_16X1 ? cm_launch_pro<3, 2, 4, 2, PS, false, MUD_PREC_16X1>(a, s) : cm_launch_pro<3, 2, 4, 2, PS>(a, s);
-    return a.prec == MUD_PREC_16X1 ? cm_launch_pro<3, 1, 4, 1, PS, false, MUD_PREC_16X1>(a, s) : cm_launch_pro<3, 1, 4, 1, PS>(a, s);
-  }
-#ifdef MUD_EXPERIMENT_WS      // scripts/build_variants.py ws:-DMUD_EXPERIMENT_WS (csrc/experiments/conv_ws.inc); never in the shipped build
-  if (cm_ws_wanted(a)) return cm_ws_dispatch(a, s);
+#ifdef MUD_EXPERIMENT_WS
+  if (cm_ws_wanted(a)) return cm_ws_dispatch(a, (hipStream_t)stream);
 #endif
-  if (a.prec == MUD_PREC_FP8X) {
-    const int v8 = cm_tile3(a, nullptr);
-    if (v8 == CMV_8X1R) return a.pro_mode == MUD_PRO_NONE ? cm_launch_pro<3, 1, 8, 1, MUD_PRO_NONE, false, MUD_PREC_FP8X>(a, s) : cm_launch_pro<3, 1, 8, 1, MUD_PRO_AFFINE_SILU, false, MUD_PREC_FP8X>(a, s);
-    const bool x2 = v8 == CMV_8X2;
-    if (a.skip_w) return x2 ? cm_launch_pro<3, 2, 4, 2, MUD_PRO_AFFINE_SILU, true, MUD_PREC_FP8X>(a, s) : cm_launch_pro<3, 2, 8, 1, MUD_PRO_AFFINE_SILU, true, MUD_PREC_FP8X>(a, s);
-    if (a.pro_mode == MUD_PRO_NONE) return x2 ? cm_launch_pro<3, 2, 4, 2, MUD_PRO_NONE, false, MUD_PREC_FP8X>(a, s) : cm_launch_pro<3, 2, 8, 1, MUD_PRO_NONE, false, MUD_PREC_FP8X>(a, s);
-    return x2 ? cm_launch_pro<3, 2, 4, 2, MUD_PRO_AFFINE_SILU, false, MUD_PREC_FP8X>(a, s) : cm_launch_pro<3, 2, 8, 1, MUD_PRO_AFFINE_SILU, false, MUD_PREC_FP8X>(a, s);
-  }
-  if (a.prec == MUD_PREC_16X1) {
-    // the single-pass plan on the same tile choice as 16x3 (cm_tile3; the fused skip conv: its three tiles)
-    constexpr int P1 = MUD_PREC_16X1;
-    if (a.skip_w) {
-      switch (cm_tile3(a, nullptr)) {
-        case CMV_8X2: return cm_launch_pro<3, 2, 4, 2, MUD_PRO_AFFINE_SILU, true, P1>(a, s);
-        case CMV_16X1: return cm_launch_pro<3, 2, 8, 1, MUD_PRO_AFFINE_SILU, true, P1>(a, s);
-        default: return cm_launch_pro<3, 1, 4, 1, MUD_PRO_AFFINE_SILU, true, P1>(a, s);      // CMV_MT1 (cm_tile3)
-      }
-    }
-    switch (cm_tile3(a, nullptr)) {
-      case CMV_8X2: return cm_launch<3, 2, 4, 2, P1>(a, s);
-      case CMV_16X1: return cm_launch<3, 2, 8, 1, P1>(a, s);
-      case CMV_MT2: return cm_launch<3, 2, 4, 1, P1>(a, s);
-      case CMV_8X1R: return cm_launch<3, 1, 8, 1, P1>(a, s);
-      default: return cm_launch<3, 1, 4, 1, P1>(a, s);
-    }
-  }
-  // tile height by problem size: big tiles (more MFMA work per weight byte) once they still fill the 256 CUs
-  const int64_t ntiles = mud_cdiv(a.Cout, CM_BN);
-  static const int force_mt = getenv("MUD_CONV_MT") ? atoi(getenv("MUD_CONV_MT")) : 0;   // tuning knob (plain launches only: the fused skip conv keeps its own tiles)
-  if (force_mt && !a.skip_w) {
-    if (a.ks == 3) return (force_mt == 8 && ntiles % 2 == 0) ? cm_launch<3, 2, 4, 2>(a, s) : force_mt == 16 ? cm_launch<3, 2, 8, 1>(a, s) : force_mt == 1 ? cm_launch<3, 1>(a, s) : cm_launch<3, 2>(a, s);
-    return cm_launch<1, 1>(a, s);      // (256- and 512-pixel 1x1 tiles were measured 5-8 % slower and are no longer built)
-  }
-  if (a.ks == 3 && a.skip_w) {
-    // fused 1x1 skip conv (DUAL): built for the AdaGN + SiLU prologue of the residual blocks only, on its three tiles (cm_tile3)
-    switch (cm_tile3(a, nullptr)) {
-      case CMV_8X2: return cm_launch_pro<3, 2, 4, 2, MUD_PRO_AFFINE_SILU, true>(a, s);
-      case CMV_16X1: return cm_launch_pro<3, 2, 8, 1, MUD_PRO_AFFINE_SILU, true>(a, s);
-      default: return cm_launch_pro<3, 1, 4, 1, MUD_PRO_AFFINE_SILU, true>(a, s);      // CMV_MT1
-    }
-  }
-  if (a.ks == 3) {
-    switch (cm_tile3(a, nullptr)) {
-      case CMV_8X2: return cm_launch<3, 2, 4, 2>(a, s);
-      case CMV_16X1: return cm_launch<3, 2, 8, 1>(a, s);
-      case CMV_MT2: return cm_launch<3, 2>(a, s);
-      case CMV_8X1R: return cm_launch<3, 1, 8, 1>(a, s);
-      default: return cm_launch<3, 1>(a, s);
-    }
-  }
-  // 1x1 GEMMs: 128-pixel tiles (MT = 1) beat 256-pixel tiles (MT = 2) by 5-8 % on every skip-conv / NIN shape at batch 16
-  // (scripts/bench_conv.py with MUD_CONV_MT=1/2) - these launches are HBM-bound and the smaller tile keeps more of them in flight
-  return cm_launch<1, 1>(a, s);
+  return launch(a, (hipStream_t)stream);
 }

@@ -385,12 +385,22 @@ def splitk_counters(device):
     return buf
 
 
+def _query_args(B, H, W, cin, ld, cout, at=None, skip=False, **fields):
+    """The ConvArgs of a 3x3 launch [B,H,W,cin] (row stride ld) -> cout for the library's host-side queries (mud_conv2d_mfma_tile,
+    *_supported, _splitk_bytes): only sizes and alignment are looked at, so `at` (a device pointer or None) stands for every operand."""
+    a = ConvArgs()
+    a.x, a.B, a.H, a.W, a.Cin, a.ldx, a.ks, a.stride, a.pad = at, B, H, W, cin, ld, 3, 1, 1
+    a.out, a.Cout, a.ldo = at, cout, (cout + 3) & ~3
+    if skip:
+        a.skip_w = at
+    for name, value in fields.items():
+        setattr(a, name, value)
+    return C.byref(a)
+
+
 def conv3x3_would_split_k(x: View, cout):
     """Would mud_conv2d_mfma deal the K chunks of this 3x3 launch to several workgroups (small grid, long reduction)?"""
-    a = ConvArgs()
-    a.x, a.B, a.H, a.W, a.Cin, a.ldx, a.ks, a.stride, a.pad = x.ptr, x.B, x.H, x.W, x.C, x.ld, 3, 1, 1
-    a.out, a.Cout, a.ldo = x.ptr, cout, (cout + 3) & ~3          # (only sizes and alignment are looked at)
-    return load().mud_conv2d_mfma_splitk_bytes(C.byref(a)) > 0
+    return load().mud_conv2d_mfma_splitk_bytes(_query_args(x.B, x.H, x.W, x.C, x.ld, cout, x.ptr)) > 0
 
 
 FUSE_SKIP_SPLIT = os.environ.get('MUD_FUSE_SKIP_SPLIT', '1') != '0'       # A/B knob: keep the skip conv fused where the launch is split over K
@@ -422,9 +432,7 @@ def res_up2_ok(B, H, W, cin, cout):
     (mud_conv2d_mfma_res_up2_supported: the AdaGN + SiLU prologue, even H and W, a grid that is not split over K)?"""
     if not RES_UP2 or cin % 4 or cout % 4:
         return False
-    a = ConvArgs()
-    a.B, a.H, a.W, a.Cin, a.ldx, a.ks, a.stride, a.pad, a.Cout, a.ldo, a.pro_mode = B, H, W, cin, cin, 3, 1, 1, cout, cout, PRO_AFFINE_SILU
-    return bool(load().mud_conv2d_mfma_res_up2_supported(C.byref(a)))
+    return bool(load().mud_conv2d_mfma_res_up2_supported(_query_args(B, H, W, cin, cin, cout, pro_mode=PRO_AFFINE_SILU)))
 
 
 IN_UP2 = os.environ.get('MUD_IN_UP2', '1') != '0'       # A/B knob: 0 = the up blocks' Conv_0 reads a tensor that a FIR launch of its own up-sampled
@@ -436,9 +444,7 @@ def in_up2_ok(B, H, W, cin, cout, prec=PREC_16X3):
     for, a grid that is not split over K)?  Independent of RES_UP2."""
     if not IN_UP2 or cin % 4 or cout % 4:
         return False
-    a = ConvArgs()
-    a.B, a.H, a.W, a.Cin, a.ldx, a.ks, a.stride, a.pad, a.Cout, a.ldo, a.pro_mode, a.prec = B, H, W, cin, cin, 3, 1, 1, cout, cout, PRO_AFFINE_SILU, prec
-    return bool(load().mud_conv2d_mfma_in_up2_supported(C.byref(a)))
+    return bool(load().mud_conv2d_mfma_in_up2_supported(_query_args(B, H, W, cin, cin, cout, pro_mode=PRO_AFFINE_SILU, prec=prec)))
 
 
 PYR_S2D = os.environ.get('MUD_PYR_S2D', '1') != '0'     # A/B knob: 0 = the input pyramid's down-sampler runs its FIR launch and the sub2 conv launch
@@ -450,10 +456,7 @@ def in_s2d_ok(B, H, W, c, cout, prec=PREC_16X3):
     is built for, a grid that is not split over K)?  The PYR_S2D knob is the dispatcher's (up_or_down_sampling.padded_strided_conv)."""
     if H % 2 or W % 2 or c % 16 or cout % 4:
         return False
-    a = ConvArgs()
-    a.B, a.H, a.W, a.Cin, a.ldx, a.ks, a.stride, a.pad, a.Cout, a.ldo, a.pro_mode, a.prec = B, H // 2, W // 2, 4 * c, c, 3, 1, 1, cout, cout, PRO_NONE, prec
-    a.in_s2d = 1
-    return bool(load().mud_conv2d_mfma_in_s2d_supported(C.byref(a)))
+    return bool(load().mud_conv2d_mfma_in_s2d_supported(_query_args(B, H // 2, W // 2, 4 * c, c, cout, pro_mode=PRO_NONE, prec=prec, in_s2d=1)))
 
 
 def s2d_fold(t):
@@ -561,12 +564,8 @@ class prec_plan:
 
 
 def conv_prec_supported(x: View, cout, pro_mode, prec, skip=False, sub2=False):
-    a = ConvArgs()
-    a.x, a.B, a.H, a.W, a.Cin, a.ldx, a.ks, a.stride, a.pad = x.ptr, x.B, x.H, x.W, x.C, x.ld, 3, 1, 1
-    a.out, a.Cout, a.ldo, a.pro_mode, a.sub2 = x.ptr, cout, (cout + 3) & ~3, pro_mode, int(sub2)
-    if skip:
-        a.skip_w = x.ptr
-    return bool(load().mud_conv2d_mfma_prec_supported(C.byref(a), prec))
+    """Does mud_conv2d_mfma have plan `prec` for this 3x3 launch (mud_conv2d_mfma_prec_supported)?"""
+    return bool(load().mud_conv2d_mfma_prec_supported(_query_args(x.B, x.H, x.W, x.C, x.ld, cout, x.ptr, skip, pro_mode=pro_mode, sub2=int(sub2)), prec))
 
 
 TILE_NAMES = {TILE_8X2: '8X2', TILE_16X1: '16X1', TILE_MT2: 'MT2', TILE_MT1: 'MT1', TILE_8X1R: '8X1R'}
@@ -580,12 +579,8 @@ def conv_tile(x: View, cout, *, skip=False, in_up2=False, in_s2d=False, pro_mode
         x = x.up2_shape()
     if in_s2d:
         x = x.s2d_shape()
-    a = ConvArgs()
-    a.x, a.B, a.H, a.W, a.Cin, a.ldx, a.ks, a.stride, a.pad = x.ptr, x.B, x.H, x.W, x.C, x.ld, 3, 1, 1
-    a.out, a.Cout, a.ldo, a.pro_mode, a.prec, a.in_up2, a.in_s2d = x.ptr, cout, (cout + 3) & ~3, pro_mode, prec, int(in_up2), int(in_s2d)
-    if skip:
-        a.skip_w = x.ptr
-    return load().mud_conv2d_mfma_tile(C.byref(a))
+    return load().mud_conv2d_mfma_tile(_query_args(x.B, x.H, x.W, x.C, x.ld, cout, x.ptr, skip, pro_mode=pro_mode, prec=prec, in_up2=int(in_up2),
+                                                   in_s2d=int(in_s2d)))
 
 
 def choose_prec(x: View, cout, pro_mode, *, skip=False, sub2=False, w_bstride=0):

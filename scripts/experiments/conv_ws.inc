@@ -408,7 +408,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_ws(mud_conv_args a, int tiles_x
 
 // the warp-specialised kernel: plain 3x3 launches that fill the chip, vector epilogue (whole aligned float4 channel columns)
 static bool cm_ws_eligible(const mud_conv_args& a) {
-  if (a.ks != 3 || a.skip_w || a.sub2 || (a.pro_mode != MUD_PRO_NONE && a.pro_mode != MUD_PRO_AFFINE_SILU)) return false;
+  if (a.ks != 3 || a.skip_w || a.sub2 || a.in_up2 || a.in_s2d || (a.pro_mode != MUD_PRO_NONE && a.pro_mode != MUD_PRO_AFFINE_SILU)) return false;
   const int emul_lim = a.emul_cout > 0 ? a.emul_cout : a.Cout;
   if (((a.Cout | a.ldo | emul_lim | (a.emul ? a.ld_emul : 0) | (a.egate ? (a.ld_egate | a.ld_eother) : 0)) & 3) != 0) return false;
   if (!mud_aligned16(a.out) || (a.emul && !mud_aligned16(a.emul)) || (a.egate && (!mud_aligned16(a.egate) || !mud_aligned16(a.eother)))) return false;
@@ -422,14 +422,7 @@ template <int CWM, int CWN, int PRO, int PREC>
 static int cm_launch_ws(const mud_conv_args& a, hipStream_t s) {
   using G = CwGeo<CWM, CWN>;
   static mud_attr_once attr_once;
-  if (attr_once.need()) {
-    hipError_t e = hipFuncSetAttribute((const void*)k_conv_ws<CWM, CWN, PRO, PREC>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_MAX);
-    if (e != hipSuccess) {
-      mud_set_error("mud_conv2d_mfma: cannot reserve %d B of LDS: %s", G::LDS_MAX, hipGetErrorString(e));
-      return MUD_ERR_LAUNCH;
-    }
-    attr_once.ok();
-  }
+  if (const int rc = cm_reserve_lds(attr_once, (const void*)k_conv_ws<CWM, CWN, PRO, PREC>, G::LDS_MAX)) return rc;
   const int k16s = (int)mud_cdiv(a.Cin, 16), ntiles = (int)mud_cdiv(a.Cout, CM_BN * CWN);
   const int tiles_x = (int)mud_cdiv(a.W, 32);
   const int64_t tiles = (int64_t)tiles_x * mud_cdiv(a.H, G::ROWS);

@@ -1,10 +1,20 @@
-"""Register / spill / LDS / occupancy table of every k_conv_mfma instantiation, from hipcc's kernel-resource-usage remarks
-(no GPU needed):  python scripts/kernel_resources.py [file.hip] [extra hipcc flags]"""
-import re, subprocess, sys, os
+"""Register / spill / LDS / occupancy table of every kernel of one unit (default: every k_conv_mfma instantiation), from hipcc's
+kernel-resource-usage remarks (no GPU needed), compiled with the flags csrc/Makefile gives that unit:
+    python scripts/kernel_resources.py [file.hip] [extra hipcc flags]"""
+import re, subprocess, sys, os, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-src = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, 'mu-diff_amd', 'csrc', 'conv_mfma.hip')
-p = subprocess.run(['/opt/rocm/bin/hipcc', '-O3', '-fPIC', '-std=c++17', '--offload-arch=gfx950', '-Wno-unused-function', '-Wno-pass-failed',
-                    '-Rpass-analysis=kernel-resource-usage', *sys.argv[2:], '-c', src, '-o', '/tmp/_kres.o'], stderr=subprocess.PIPE, text=True)
+CSRC = os.path.join(ROOT, 'mu-diff_amd', 'csrc')
+src = sys.argv[1] if len(sys.argv) > 1 else os.path.join(CSRC, 'conv_mfma.hip')
+
+
+def from_makefile(what):
+    return subprocess.check_output(['make', '-C', CSRC, '-s', '--no-print-directory', 'print-' + what], text=True).split()
+
+
+unit = os.path.splitext(os.path.basename(src))[0]
+with tempfile.TemporaryDirectory(prefix='mud_kres_') as tmp:      # the object is not wanted, only the remarks
+    p = subprocess.run([*from_makefile('hipcc'), *from_makefile('flags-' + unit), '-Wno-pass-failed', f'-I{CSRC}', '-Rpass-analysis=kernel-resource-usage',
+                        *sys.argv[2:], '-c', src, '-o', os.path.join(tmp, unit + '.o')], stderr=subprocess.PIPE, text=True)
 t = p.stderr
 if p.returncode:
     sys.exit(t[-3000:])

@@ -202,3 +202,16 @@ def test_split_k_workspace_is_sized_for_the_tile_the_query_names():
     assert lib.mud_conv2d_mfma_splitk_bytes(C.byref(a)) == 0                     # no arrival counters: the fused launch is not split
     a.splitk_counters, a.splitk_ncounters = C.c_void_p(buf.data_ptr()), 16
     assert lib.mud_conv2d_mfma_splitk_bytes(C.byref(a)) == 2 * 4 * blocks * 256 * 32 * 4
+
+
+def test_the_in_up2_and_in_s2d_keys_are_no_prologue_modes():
+    """MUD_PRO_UP2_AFFINE_SILU (4) and MUD_PRO_S2D (5) key kernels inside the library and are no values of mud_conv_args.pro_mode: the
+    plan query says no to them, as to any other unknown mode, on the tiles those kernels exist for (8X2, MT1) and on one they do not."""
+    import mudiff_hip
+    from mudiff_hip import ops
+    lib = _lib()
+    for (B, H, W, Cin, Cout), tile in (((4, 128, 128, 96, 128), T8X2), ((1, 20, 37, 48, 96), MT1), ((128, 11, 35, 20, 60), T8X1R)):
+        assert ops.conv_tile(_view(B, H, W, Cin), Cout) == _code(tile)
+        for mode in (-7, 4, 5, 6, 1 << 30):
+            for prec in (mudiff_hip.PREC_16X1, mudiff_hip.PREC_FP8X):
+                assert lib.mud_conv2d_mfma_prec_supported(ops._query_args(B, H, W, Cin, Cin, Cout, pro_mode=mode), prec) == 0, (tile, mode, prec)
