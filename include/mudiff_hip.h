@@ -732,6 +732,22 @@ int mud_volume_through_plane(const float* vol, const uint8_t* mask, int Z, int X
  *     float32(sqrt(max(m - 2 sigma^2, 0))).  A voxel that is 0 or not valid is passed through.  zeroed (device uint32, cleared first): the
  *     number of voxels that were not 0 and came out 0.  search: 1 .. 5, patch: 1 .. 2 (the tile and its halo of search + patch voxels per
  *     side are staged in LDS); sigma, beta: finite and > 0.  A fixed order of accumulation: the same bits on every run.
+ * mud_volume_unring_* (--unring, DESIGN.md section 5.30, which holds the definition; no reference counterpart): removal of truncation (Gibbs)
+ *   ringing by local sub-voxel shifts; the host's share (the tables) is mudiff_hip.volume_unring.  Axes are storage axes (0 = x, the
+ *   fastest); every in-plane axis has at most 512 voxels; volumes are [Z][Y][X].
+ *   _filter ("2D"): v = the value of a stored voxel, a non-finite one read as 0; nonfinite (device uint32, cleared first) counts
+ *     them.  Per slice normal to the third axis, ix (fp32) = v circularly filtered by Gx(kx, ky) = cy / (cx + cy), c = 1 + cos(2 pi k / n)
+ *     along axis_x and axis_y (1/2 at the bin 2 kx = nx, 2 ky = ny), and iy = v - ix.  twiddle: fp64 [nx][2] = (cos, -sin)(2 pi m / nx);
+ *     kernel: fp64 [nx / 2 + 1][ny], row kx the inverse transform along ky of Gx(kx, .) (real).  ix and iy are also the workspace (the half
+ *     spectrum along axis_x, fp32): buffers of their own.  Sums are fp64 chains in index order: the same bits on every run.
+ *   _lines ("U(x)"): every line of `in` (fp32) along `axis`, circular: for the shifts s_j, j = 0 .. 2 shifts, y_s = the line
+ *     convolved with row j of table (fp32 [2 shifts + 1][n], D_s of the definition; row 0 is not read: y_0 is the line), TV_s[l] = the
+ *     smaller of the sums of |y_s[i] - y_s[i-1]| over the b - a + 1 differences that end a .. b voxels to the left of l and that begin a ..
+ *     b voxels to its right; j* = the first j of the smallest TV_s[l]; the result is y_s[l] + |s| (y_s[l -+ 1] - y_s[l]) for s >< 0 and
+ *     in[l] for j* = 0.  out = the result, or out + the result with accumulate != 0; out may be `in`.  jmap (int8, or NULL) = j*.  counters
+ *     (device uint64 [2], cleared first): the voxels with j* != 0 and the sum of |s_j*| (2 shifts + 1).  `normal`, the slices' normal, only
+ *     has to differ from `axis`: the lines of every slice are all the lines of the volume.  shifts: 1 .. 32; 1 <= a <= b <= 8; 2 b + 2
+ *     <= n <= 512.  Fixed-order fp32 sums and integer counters: the same bits on every run.
  * mud_volume_fg_* (--foreground; no reference counterpart): a foreground (head or object) mask of a stored volume
  *   by thresholding and topology - not a brain extraction; the host's share (the Otsu scan) is mudiff_hip.volume_foreground.  v = the value
  *   of a stored voxel (fp32); a candidate is a voxel whose v is finite and != 0.  Masks are uint8 [Z][Y][X] holding 0 or 1, labels int32.
@@ -836,6 +852,10 @@ int mud_volume_denoise_residual(const void* vol, int datatype, int X, int Y, int
 int mud_volume_denoise_select_hist(const uint32_t* keys, int64_t n, uint32_t prefix, int pass, uint32_t* hist, void* stream);
 int mud_volume_denoise_nlm(const void* vol, int datatype, int X, int Y, int Z, float slope, float inter, int search, int patch, double sigma,
                            double beta, int rician, float* out, uint32_t* zeroed, void* stream);
+int mud_volume_unring_filter(const void* vol, int datatype, int X, int Y, int Z, float slope, float inter, int axis_x, int axis_y,
+                             const double* twiddle, const double* kernel, float* ix, float* iy, uint32_t* nonfinite, void* stream);
+int mud_volume_unring_lines(const float* in, int X, int Y, int Z, int axis, int normal, int shifts, int a, int b, const float* table,
+                            float* out, int accumulate, int8_t* jmap, uint64_t* counters, void* stream);
 int mud_volume_fg_range(const void* vol, int datatype, int X, int Y, int Z, float slope, float inter, uint32_t* range, void* stream);
 int mud_volume_fg_hist(const void* vol, int datatype, int X, int Y, int Z, float slope, float inter, double lo, double scale, int bins,
                        uint32_t* hist, void* stream);

@@ -187,6 +187,8 @@ _SIGNATURES = {
     'mud_volume_denoise_residual': (_I, [_P, _I, _I, _I, _I, _F, _F, _P, _P]),
     'mud_volume_denoise_select_hist': (_I, [_P, _L, C.c_uint32, _I, _P, _P]),
     'mud_volume_denoise_nlm': (_I, [_P, _I, _I, _I, _I, _F, _F, _I, _I, _D, _D, _I, _P, _P, _P]),
+    'mud_volume_unring_filter': (_I, [_P, _I, _I, _I, _I, _F, _F, _I, _I, _P, _P, _P, _P, _P, _P]),
+    'mud_volume_unring_lines': (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P]),
     'mud_volume_fg_range': (_I, [_P, _I, _I, _I, _I, _F, _F, _P, _P]),
     'mud_volume_fg_hist': (_I, [_P, _I, _I, _I, _I, _F, _F, _D, _D, _I, _P, _P]),
     'mud_volume_fg_mask': (_I, [_P, _I, _I, _I, _I, _F, _F, _D, _D, _I, _I, _P, _P]),

@@ -1815,6 +1815,51 @@ def volume_denoise_nlm(dev_raw, code, shape, slope, inter, search, patch, sigma,
 
 
 # ---------------------------------------------------------------------------------------------------
+# --unring (csrc/volume_unring.hip; the host's share, the tables, is mudiff_hip.volume_unring)
+# ---------------------------------------------------------------------------------------------------
+def volume_unring_filter(dev_raw, code, shape, slope, inter, axes, twiddle, kernel):
+    """mud_volume_unring_filter -> (ix, iy: device fp32 [Z, Y, X], ix + iy = the volume with its non-finite voxels read as 0; device int32
+    [1] (uint32): how many those were).  twiddle, kernel: the device tables of volume_unring.filter_tables(nx, ny)."""
+    X, Y, Z = _bias_volume('volume_unring_filter', dev_raw, code, shape)
+    require_gpu(dev_raw, twiddle, kernel)
+    ax, ay = (int(a) for a in axes)
+    if not (0 <= ax <= 2 and 0 <= ay <= 2 and ax != ay):
+        raise MudiffHipError(f'volume_unring_filter: two distinct storage axes in [0, 2], got {ax} and {ay}')
+    nx, ny = (X, Y, Z)[ax], (X, Y, Z)[ay]
+    for t, count, what in ((twiddle, 2 * nx, 'twiddle'), (kernel, (nx // 2 + 1) * ny, 'kernel')):
+        if t.dtype != torch.float64 or t.numel() != count or not t.is_contiguous():
+            raise MudiffHipError(f'volume_unring_filter: need {count} contiguous fp64 entries of the {what} table, got {t.dtype} {tuple(t.shape)}')
+    ix = torch.empty(Z, Y, X, device=dev_raw.device, dtype=torch.float32)
+    iy = torch.empty_like(ix)
+    nonfinite = torch.empty(1, device=dev_raw.device, dtype=torch.int32)
+    _launch('volume_unring_filter', dev_raw.device, load().mud_volume_unring_filter, ptr(dev_raw), int(code), X, Y, Z, float(slope), float(inter),
+            ax, ay, ptr(twiddle), ptr(kernel), ptr(ix), ptr(iy), ptr(nonfinite), STREAM,
+            flops=2.0 * ix.numel() * (3.0 * nx + 2.0 * ny), nbytes=float(ix.numel() * (2 * dev_raw.element_size() + 32)))
+    return ix, iy, nonfinite
+
+
+def volume_unring_lines(vol, shape, axis, normal, shifts, window, table, out=None, accumulate=False, jmap=False):
+    """mud_volume_unring_lines on the fp32 [Z, Y, X] device volume `vol` -> (out, jmap or None, device int64 [2]: the voxels that moved and
+    the sum of their |shift| in units of 1 / (2 shifts + 1)).  out: where the result goes (`vol` itself by default: in place), added to
+    what it holds with `accumulate`; jmap=True also returns the int8 [Z, Y, X] map of the chosen shifts."""
+    require_gpu(vol, table)
+    X, Y, Z = _fg_grid('volume_unring_lines', vol, shape, torch.float32)
+    out = vol if out is None else out
+    _fg_grid('volume_unring_lines', out, shape, torch.float32)
+    n = (X, Y, Z)[int(axis)] if 0 <= int(axis) <= 2 else 0
+    a, b = (int(w) for w in window)
+    if table.dtype != torch.float32 or table.numel() != (2 * int(shifts) + 1) * n or not table.is_contiguous():
+        raise MudiffHipError(f'volume_unring_lines: need the contiguous fp32 table of {2 * int(shifts) + 1} shifts of {n} voxels, got {table.dtype} '
+                             f'{tuple(table.shape)}')
+    chosen = torch.empty(Z, Y, X, device=vol.device, dtype=torch.int8) if jmap else None
+    counters = torch.empty(2, device=vol.device, dtype=torch.int64)
+    _launch('volume_unring_lines', vol.device, load().mud_volume_unring_lines, ptr(vol), X, Y, Z, int(axis), int(normal), int(shifts), a, b, ptr(table),
+            ptr(out), int(bool(accumulate)), ptr(chosen) if jmap else None, ptr(counters), STREAM,
+            flops=2.0 * vol.numel() * n * 2 * int(shifts), nbytes=8.0 * vol.numel())
+    return out, chosen, counters
+
+
+# ---------------------------------------------------------------------------------------------------
 # --foreground (csrc/volume_foreground.hip; the host's share is mudiff_hip.volume_foreground)
 # ---------------------------------------------------------------------------------------------------
 def _fg_grid(what, t, shape, dtype):

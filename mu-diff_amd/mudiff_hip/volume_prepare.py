@@ -4,7 +4,7 @@ prepare_inputs and normalises what comes back, on the host (volume.host_stacks) 
 
     STAGES                                                one line per stage: its module (add_flags, options_from, the suffixes, write_reports)
     IntakeOptions.from_args(args)                         what --norm, --slice_half_range and every stage's flags ask for, built once
-    prepare_inputs(named_raws, options, device)           reorient; denoise; foreground; first input = the grid [conformed, aligned]; coregister; regrid, or check the shape; brain mask; bias-correct
+    prepare_inputs(named_raws, options, device)           reorient; denoise; unring; foreground; first input = the grid [conformed, aligned]; coregister; regrid, or check the shape; brain mask; bias-correct
     IntakeReport                                          what that did, by modality name: the [done] line's tail and the report files
     read_for_evaluation, evaluation_inputs                --gt_volume / --eval_mask on the grid the prediction will have
     output_writer                                         --reorient_back / --conform_back around a writer
@@ -27,6 +27,7 @@ from . import volume_foreground as VF
 from . import volume_intake as VI
 from . import volume_regrid as VR
 from . import volume_reorient as VO
+from . import volume_unring as VU
 from .volume_intake import slab_range
 
 # One line per stage, in the order of the flags, of the [done] line's parts and of the report files.  `parts`: (the module's suffix
@@ -43,16 +44,17 @@ STAGES = (
     Stage(VBR, (('brain_suffix', 'brain'),), 'brain affine header'),
     Stage(VO, (('reorient_suffix', 'reorient'),), 'reorient'),
     Stage(VCF, (('conform_suffix', 'conform conform_grid'), ('antialias_suffix', 'lowpass')), 'conform conform_grid'),
+    Stage(VU, (('unring_suffix', 'unring'),), 'unring'),
     Stage(VA, (('align_suffix', 'align'),), 'align'),
 )
 
 
-class IntakeOptions(collections.namedtuple('IntakeOptions', 'norm regrid coreg bias half_range foreground brain interp reorient conform antialias align denoise',
-                                           defaults=('percentile', False, None, None, 80, None, None, 'linear', None, None, False, None, None))):
+class IntakeOptions(collections.namedtuple('IntakeOptions', 'norm regrid coreg bias half_range foreground brain interp reorient conform antialias unring align denoise',
+                                           defaults=('percentile', False, None, None, 80, None, None, 'linear', None, None, False, None, None, None))):
     """norm: --norm; half_range: --slice_half_range (the slab is part of the reference geometry); every other field is what one stage's
     options_from made of that stage's flags (its docstring says what): regrid and interp (volume_regrid), coreg, bias, denoise,
-    foreground, brain, reorient, conform and antialias (volume_conform), align.  `foreground`, `brain`, `interp`, `reorient`, `conform`,
-    `antialias` and `align` sit before `denoise`, not at the end: tests/test_volume_denoise_host.py pins `denoise` as the last field, and every
+    foreground, brain, reorient, conform and antialias (volume_conform), unring, align.  `foreground`, `brain`, `interp`, `reorient`, `conform`,
+    `antialias`, `unring` and `align` sit before `denoise`, not at the end: tests/test_volume_denoise_host.py pins `denoise` as the last field, and every
     positional use stops at half_range."""
     __slots__ = ()
 
@@ -79,7 +81,8 @@ class IntakeReport:
     report, the uint8 [X,Y,Z] host mask or None)]: one entry per subject; `reorient` [(name, entry)] (volume_reorient.ReorientPlan.entry);
     `interp` (--regrid_interp) and `nonfinite`, the non-finite voxels a cubic resampling or the anti-aliasing low-pass read as 0; `conform`
     [(name, entry)] (volume_conform.entry) with `conform_grid`, the grid's name ('240x240x155@1mm'); `lowpass`: a low-pass actually ran
-    (--antialias); `align` [(the first input's name, report)] (volume_align.estimate)."""
+    (--antialias); `align` [(the first input's name, report)] (volume_align.estimate); `unring` [(name, report)]
+    (volume_unring.unring)."""
 
     def __init__(self, regridded=(), interp='linear', nonfinite=0, lowpass=False):
         self.regridded, self.coreg, self.bias, self.denoise, self.foreground, self.brain = list(regridded), [], [], [], [], []
@@ -87,6 +90,7 @@ class IntakeReport:
         self.reorient = []
         self.conform, self.conform_grid, self.lowpass = [], None, bool(lowpass)
         self.align = []
+        self.unring = []
 
     def add_evaluation(self, resampled, found):
         """What evaluation_inputs did, after the inputs' own: the names it resampled, and its `found`."""
@@ -96,7 +100,7 @@ class IntakeReport:
 
     def suffix(self):
         """What a [done] line gains: ` | regrid=... | interp=cubic | coreg=... | bias=... | denoise=... | foreground=... | brain=... |
-        reorient=... | conform=... | antialias=on | align=...`, each part only when there is something to say (STAGES' order)."""
+        reorient=... | conform=... | antialias=on | unring=... | align=...`, each part only when there is something to say (STAGES' order)."""
         return ''.join(getattr(stage.module, name)(*(getattr(self, k) for k in takes.split())) for stage in STAGES for name, takes in stage.parts)
 
     def write(self, output_dir, target, affine, header):
@@ -170,7 +174,7 @@ def output_writer(write, first_raw, options, ref, device, reorient_back=False, c
 
 
 def _on_own_grid(named_raws, options, device, report, label):
-    """--reorient, --denoise and --foreground: every input on its own grid (prepare_inputs says what each does) -> the new list.
+    """--reorient, --denoise, --unring and --foreground: every input on its own grid (prepare_inputs says what each does) -> the new list.
     label: name -> what a warning line calls the input; None prints no warning line (the caller prints it: warn_first)."""
     if options.reorient is not None:
         turned = []
@@ -188,6 +192,13 @@ def _on_own_grid(named_raws, options, device, report, label):
             report.denoise.append((name, found))
             cleaned.append((name, vol))
         named_raws = cleaned
+    if options.unring is not None:                       # on the input's own grid: a resampling moves the ripples off the lattice the method relies on
+        unrung = []
+        for name, raw in named_raws:
+            vol, found = VU.unring(raw, device, name='the first input' if label is None else label(name), **options.unring)
+            report.unring.append((name, found))
+            unrung.append((name, vol))
+        named_raws = unrung
     if options.foreground is not None:
         masked = []
         for name, raw in named_raws:
@@ -200,14 +211,14 @@ def _on_own_grid(named_raws, options, device, report, label):
 
 class Alignment(collections.namedtuple('Alignment', 'T report first stages')):
     """estimate_alignment's result: T and report (volume_align.estimate's), `first` - the first input as the plane was estimated from it,
-    after --reorient / --denoise / --foreground - and `stages`, the IntakeReport of those three stages for it, so that prepare_inputs
+    after --reorient / --denoise / --unring / --foreground - and `stages`, the IntakeReport of those four stages for it, so that prepare_inputs
     takes the first input from here and runs none of them on it again."""
     __slots__ = ()
 
 
 def estimate_alignment(first_raw, options, device):
     """--align for a caller that needs the plane before prepare_inputs runs (the evaluation inputs): the first input as read, taken through
-    --reorient / --denoise / --foreground as prepare_inputs takes it (no warning line: prepare_inputs prints it, with the input's name),
+    --reorient / --denoise / --unring / --foreground as prepare_inputs takes it (no warning line: prepare_inputs prints it, with the input's name),
     then volume_align.estimate -> an Alignment, for prepare_inputs' and evaluation_inputs' `align`."""
     stages = IntakeReport()
     (_, first), = _on_own_grid([(None, first_raw)], options, device, stages, None)
@@ -233,6 +244,8 @@ def prepare_inputs(named_raws, options, device, labels=None, align=None):
     the slab runs along the target's third axis; an input tilted by more than volume_reorient.OBLIQUE_WARN_DEG gets a warning line.
     Under --denoise every input, the first included, is then replaced by its non-local-means estimate on its own grid
     (volume_denoise.denoise: same shape, affine and header), and everything below sees the denoised list.
+    Under --unring every input, the first included, then has its truncation ringing removed on its own grid (volume_unring.unring: same
+    shape, affine and header; before --foreground, whose mask re-zeroes what the correction's sinc tails put into the background).
     Under --foreground every input, the first included, then has the voxels outside its foreground mask set to exactly 0, on its own grid
     (volume_foreground.foreground: same shape, affine and header again), and everything below sees the masked list.
     The first input defines the grid and is never registered or resampled.  Every later one is aligned to it under --coregister
@@ -246,7 +259,7 @@ def prepare_inputs(named_raws, options, device, labels=None, align=None):
     interpolation per input; an input that is on that grid already is left untouched); the brain mask and the bias correction follow on
     the conform grid.  Under --align (options.align) the mid-sagittal plane of the first input, as it is at this
     point, is estimated (volume_align.estimate; with `align`, estimate_alignment's result, the plane and the first input as it is at this
-    point are taken from there: neither the estimate nor the three stages above run on the first input twice) and the
+    point are taken from there: neither the estimate nor the four stages above run on the first input twice) and the
     conform grid's affine becomes T @ itself: still one regrid_to per input, now onto the turned grid.  With options.antialias every such resampling (--regrid's and --coregister's too) low-passes what it downsamples.  Under --bias_correct every input, the first
     included, is then divided by its bias field (volume_bias.correct).  ValueError for an input that is not 3D or a --brain_from that is
     not among the inputs, before any device work."""
@@ -260,7 +273,7 @@ def prepare_inputs(named_raws, options, device, labels=None, align=None):
     report = IntakeReport(interp=options.interp)
     if isinstance(align, Alignment):                     # the first input has been through these stages: its entries and its warning line first
         name = named_raws[0][0]
-        for stage in ('reorient', 'denoise', 'foreground'):
+        for stage in ('reorient', 'denoise', 'unring', 'foreground'):
             getattr(report, stage).extend((name,) + tuple(entry[1:]) for entry in getattr(align.stages, stage))
         for _, found in report.reorient:
             VO.warn_oblique(label(name), found)
