@@ -1,5 +1,5 @@
-// What the row kernels of the sampler share (known_region.hip, kspace.hip, slab.hip and the keyed draws of ensemble.hip; DESIGN.md
-// section 5.24b): a thread owns a quad, 4 consecutive floats of one row = one Philox block of keyed_normal.h.  The helpers here only
+// What the row kernels of the sampler share (known_region.hip, kspace.hip, slab.hip, slab_kspace.hip, band.hip and the keyed draws of
+// ensemble.hip): a thread owns a quad, 4 consecutive floats of one row = one Philox block of keyed_normal.h.  The helpers here only
 // index, load, store and draw: none holds a contractible floating-point expression, so every product and sum stays in the kernels, under
 // their own `#pragma clang fp contract(off)` (which would not reach into a helper).  The level clamp itself is mud_level_index
 // (mud_common.h), shared with elementwise.hip.

@@ -10,7 +10,13 @@ launch into sampler.x per executed step, for GraphSampler.sample_keyed.
 
 A constraint that couples the whole stack along z (thick_volume.BandMeasurement, --known_thick_volume; section 5.29) has no batch-level
 form: it declares `lockstep` and the samplers hand it the whole state of the prediction after every step
-(GraphSampler.sample_lockstep)."""
+(GraphSampler.sample_lockstep).
+
+The pieces a mode takes from here instead of writing them again: level_tables (what every apply hands its launch), _kspace_batch and
+_slab_tables_fit (the checks of a batch measured in k-space, and of slab tables against a batch), relative_residual (the |d| / |y| of
+every report), and for the flags need_known_volume and need_keyed_seed.  Next to them: thick.SlabbedMeasurement, thick.select_slabs and
+thick.slab_options for anything measured in slabs, kspace.pattern_options for a sampling pattern, thick_volume.interpolate for the
+through-plane baseline."""
 from __future__ import annotations
 
 import collections
@@ -95,6 +101,25 @@ class KnownVoxels(Constraint):
         return KnownRows(self.known.index_select(0, idx), self.mask.index_select(0, idx))
 
 
+def relative_residual(d, den):
+    """|d| / den over d's last axis, 0 where den is 0: the data-consistency residual of every measurement's report (d [..., k, len]
+    against den [k], the measurements' norms)."""
+    r = torch.linalg.vector_norm(d, dim=-1)
+    return torch.where(den > 0, r / den.clamp_min(1e-30), torch.zeros_like(r))
+
+
+def need_known_volume(args, flag):
+    """`flag` measures --known_volume K; a cohort's namespace is excepted: its K is the manifest's `known` column."""
+    cohort = getattr(args, 'manifest', None) is not None or getattr(args, 'brats_root', None) is not None
+    if getattr(args, 'known_volume', None) is None and not cohort:
+        raise ValueError(f'{flag} needs --known_volume')
+
+
+def need_keyed_seed(args, flag, why='its draws are keyed'):
+    if not 0 <= int(getattr(args, 'seed', 0)) < 1 << 64:
+        raise ValueError(f'{flag} needs a --seed in [0, 2^64) ({why})')
+
+
 def of_prediction(who, constraint, known, kspace, thick, resample):
     """The keywords of volume.predict_slices / ensemble.sample_ensemble, `known` = (known, mask) -> (the one prediction-level constraint
     or FREE, resample: a `constraint`'s own, else the keyword).  ValueError for more than one."""
@@ -105,6 +130,39 @@ def of_prediction(who, constraint, known, kspace, thick, resample):
         return FREE, 1
     con = given[0] if known is None else KnownVoxels(known[0], known[1], resample)
     return con, con.resample if constraint is not None else resample
+
+
+# ---------------------------------------------------------------------------------------------------
+# what the batch-level constraints share: `sampler` is the GraphSampler (its B, H, W, x, t and level tables)
+# ---------------------------------------------------------------------------------------------------
+def level_tables(sampler):
+    """(a_s_cum, sigmas_cum): the two tables every constraint launch takes after its t and offset."""
+    return sampler._diffusion_tables()[:2]
+
+
+def _kspace_batch(word, sampler, y, mask, slab=None):
+    """A batch measured in k-space: the sampler's grid is square and one the transform takes, y is complex64 [count,S,S] and mask uint8
+    [1 or count,S,S] -> (y, mask on the sampler's device, the slab tables or None).  count: B, or with `slab` = (members, weights, gains)
+    the groups of ops.slab_tables of it.  Leaves the complex workspace on the sampler: one per sampler, [B,S,S] (groups <= B)."""
+    B, H, W = sampler.B, sampler.H, sampler.W
+    if H != W or not ops.kspace_size_ok(H):
+        raise ValueError(f'GraphSampler.sample_keyed: {word} needs a square grid whose size is a power of two in [16, 512], got {H} x {W}')
+    tab = None if slab is None else ops.slab_tables(*slab)
+    want = (B if tab is None else tab[0].shape[0], H, W)
+    if y.dtype != torch.complex64 or tuple(y.shape) != want or mask.dtype != torch.uint8 or tuple(mask.shape) not in (want, (1,) + want[1:]):
+        raise ValueError(f'GraphSampler.sample_keyed: {word} = (y complex64 {want}, mask uint8 [1 or {want[0]}, {H}, {W}]'
+                         f'{"" if tab is None else ", ..."}), got {y.dtype} {tuple(y.shape)} and {mask.dtype} {tuple(mask.shape)}')
+    if getattr(sampler, '_ks_work', None) is None:
+        sampler._ks_work = torch.empty((B, H, W), device=sampler.x.device, dtype=torch.complex64)
+    return y.to(sampler.x.device).contiguous(), mask.to(sampler.x.device).contiguous(), tab
+
+
+def _slab_tables_fit(word, sampler, tab):
+    """Slab tables against the batch: at most B groups, of at most ops.SLAB_MAX_MEMBERS rows each, all of them rows of the batch."""
+    (groups, L), B, top = tab[0].shape, sampler.B, int(tab[0].max(initial=-1))
+    if groups > B or L > ops.SLAB_MAX_MEMBERS or top >= B:
+        raise ValueError(f'GraphSampler.sample_keyed: {word} names {groups} groups of {L} rows up to row {top} for a batch of {B} (at most '
+                         f'{ops.SLAB_MAX_MEMBERS} rows a group)')
 
 
 class KnownRows(collections.namedtuple('KnownRows', 'known mask')):
@@ -120,8 +178,7 @@ class KnownRows(collections.namedtuple('KnownRows', 'known mask')):
         self.dev = known.to(sampler.x.device, torch.float32).contiguous(), mask.to(sampler.x.device).contiguous()
 
     def apply(self, sampler, x_new, keys_dev, seed, step, clean):
-        dc = sampler._diffusion_tables()
-        ops.known_constrain_into(sampler.x, x_new, *self.dev, keys_dev, seed, step, ops.KIND_KNOWN, sampler.t, 0, dc[0], dc[1], clean=clean)
+        ops.known_constrain_into(sampler.x, x_new, *self.dev, keys_dev, seed, step, ops.KIND_KNOWN, sampler.t, 0, *level_tables(sampler), clean=clean)
 
 
 class KSpaceRows(collections.namedtuple('KSpaceRows', 'y mask idx', defaults=(None,))):
@@ -129,21 +186,11 @@ class KSpaceRows(collections.namedtuple('KSpaceRows', 'y mask idx', defaults=(No
     (KSpaceMeasurement.for_rows; None from the keyword)."""
 
     def check(self, sampler):
-        B, H, W = sampler.B, sampler.H, sampler.W
-        if H != W or not ops.kspace_size_ok(H):
-            raise ValueError(f'GraphSampler.sample_keyed: kspace needs a square grid whose size is a power of two in [16, 512], got {H} x {W}')
-        (y, mask, _), want = self, (B, H, W)
-        if y.dtype != torch.complex64 or tuple(y.shape) != want or mask.dtype != torch.uint8 or tuple(mask.shape) not in (want, (1,) + want[1:]):
-            raise ValueError(f'GraphSampler.sample_keyed: kspace = (y complex64 {want}, mask uint8 [1 or {B}, {H}, {W}]), got '
-                             f'{y.dtype} {tuple(y.shape)} and {mask.dtype} {tuple(mask.shape)}')
-        self.dev = y.to(sampler.x.device).contiguous(), mask.to(sampler.x.device).contiguous()
-        if getattr(sampler, '_ks_work', None) is None:          # the complex workspace: one per sampler
-            sampler._ks_work = torch.empty(want, device=sampler.x.device, dtype=torch.complex64)
+        self.dev = _kspace_batch('kspace', sampler, self.y, self.mask)[:2]
 
     def apply(self, sampler, x_new, keys_dev, seed, step, clean):
-        dc = sampler._diffusion_tables()
-        ops.kspace_constrain_into(sampler.x, x_new, *self.dev, sampler._ks_work, keys_dev, seed, step, ops.KIND_KSPACE, sampler.t, 0, dc[0],
-                                  dc[1], clean=clean)
+        ops.kspace_constrain_into(sampler.x, x_new, *self.dev, sampler._ks_work, keys_dev, seed, step, ops.KIND_KSPACE, sampler.t, 0,
+                                  *level_tables(sampler), clean=clean)
 
 
 class SlabRows(collections.namedtuple('SlabRows', 'thick gids')):
@@ -153,17 +200,14 @@ class SlabRows(collections.namedtuple('SlabRows', 'thick gids')):
     def check(self, sampler):
         y, members, weights, gains = self.thick
         tab = ops.slab_tables(members, weights, gains)
-        B, want, top = sampler.B, (tab[0].shape[0], sampler.H, sampler.W), int(tab[0].max(initial=-1))
+        want = (tab[0].shape[0], sampler.H, sampler.W)
         if y.dtype != torch.float32 or tuple(y.shape) != want:
             raise ValueError(f'GraphSampler.sample_keyed: thick y must be fp32 {want}, got {y.dtype} {tuple(y.shape)}')
-        if want[0] > B or tab[0].shape[1] > ops.SLAB_MAX_MEMBERS or top >= B:
-            raise ValueError(f'GraphSampler.sample_keyed: thick names {want[0]} groups of {tab[0].shape[1]} rows up to row {top} for a batch '
-                             f'of {B} (at most {ops.SLAB_MAX_MEMBERS} rows a group)')
+        _slab_tables_fit('thick', sampler, tab)
         self.dev = y.to(sampler.x.device).contiguous(), tab
 
     def apply(self, sampler, x_new, keys_dev, seed, step, clean):
-        dc = sampler._diffusion_tables()
-        ops.slab_constrain_into(sampler.x, x_new, *self.dev, keys_dev, seed, step, ops.KIND_THICK, sampler.t, 0, dc[0], dc[1], clean=clean)
+        ops.slab_constrain_into(sampler.x, x_new, *self.dev, keys_dev, seed, step, ops.KIND_THICK, sampler.t, 0, *level_tables(sampler), clean=clean)
         sampler.thick_x_new = x_new          # what the last constraint was given (the graph's own buffer, until the next replay)
 
 
@@ -173,26 +217,14 @@ class SlabKSpaceRows(collections.namedtuple('SlabKSpaceRows', 'multislice gids',
     the measured slab of each group (multislice.MultisliceMeasurement.for_rows; None from a caller's own tuple)."""
 
     def check(self, sampler):
-        B, H, W = sampler.B, sampler.H, sampler.W
-        if H != W or not ops.kspace_size_ok(H):
-            raise ValueError(f'GraphSampler.sample_keyed: multislice needs a square grid whose size is a power of two in [16, 512], got {H} x {W}')
-        y, mask, members, weights, gains = self.multislice
-        tab = ops.slab_tables(members, weights, gains)
-        want, top = (tab[0].shape[0], H, W), int(tab[0].max(initial=-1))
-        if y.dtype != torch.complex64 or tuple(y.shape) != want or mask.dtype != torch.uint8 or tuple(mask.shape) not in (want, (1,) + want[1:]):
-            raise ValueError(f'GraphSampler.sample_keyed: multislice = (y complex64 {want}, mask uint8 [1 or {want[0]}, {H}, {W}], ...), got '
-                             f'{y.dtype} {tuple(y.shape)} and {mask.dtype} {tuple(mask.shape)}')
-        if want[0] > B or tab[0].shape[1] > ops.SLAB_MAX_MEMBERS or top >= B:
-            raise ValueError(f'GraphSampler.sample_keyed: multislice names {want[0]} groups of {tab[0].shape[1]} rows up to row {top} for a '
-                             f'batch of {B} (at most {ops.SLAB_MAX_MEMBERS} rows a group)')
-        self.dev = y.to(sampler.x.device).contiguous(), mask.to(sampler.x.device).contiguous(), tab
-        if getattr(sampler, '_ks_work', None) is None:          # the complex workspace: one per sampler, KSpaceRows' (groups <= B)
-            sampler._ks_work = torch.empty((B, H, W), device=sampler.x.device, dtype=torch.complex64)
+        y, mask, *slab = self.multislice
+        dev = _kspace_batch('multislice', sampler, y, mask, slab)
+        _slab_tables_fit('multislice', sampler, dev[2])
+        self.dev = dev
 
     def apply(self, sampler, x_new, keys_dev, seed, step, clean):
-        dc = sampler._diffusion_tables()
         ops.slab_kspace_constrain_into(sampler.x, x_new, *self.dev, sampler._ks_work, keys_dev, seed, step, ops.KIND_MULTISLICE, sampler.t, 0,
-                                       dc[0], dc[1], clean=clean)
+                                       *level_tables(sampler), clean=clean)
         sampler.thick_x_new = x_new          # what the last constraint was given (the graph's own buffer, until the next replay)
 
 

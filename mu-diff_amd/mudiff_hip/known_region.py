@@ -87,9 +87,8 @@ def options_from(args):
         return None
     if int(resample) != resample or resample < 1:
         raise ValueError(f'--known_resample must be an integer >= 1, got {resample}')
-    seed = getattr(args, 'seed', 0)
-    if not 0 <= int(seed) < 1 << 64:
-        raise ValueError('--known_volume needs a --seed in [0, 2^64) (its draws are keyed)')
+    from .constraints import need_keyed_seed
+    need_keyed_seed(args, '--known_volume')
     return dict(volume=volume, mask=mask, drop=parse_drop_slices(drop), resample=int(resample))
 
 

@@ -32,7 +32,7 @@ import os
 import numpy as np
 import torch
 
-from .constraints import Constraint, KSpaceRows
+from .constraints import Constraint, KSpaceRows, need_keyed_seed, need_known_volume, relative_residual
 
 PATTERNS = ('equispaced', 'random', 'lowres', 'file')
 DEFAULT_ACCEL, DEFAULT_CENTER, DEFAULT_AXIS = 4, 0.08, 0
@@ -56,6 +56,24 @@ def add_flags(p):
                    help='also write zero_filled_<t>.nii.gz = Re F^H y, the reconstruction without the model (scored too under --gt_volume)')
 
 
+def pattern_options(flag, prefix, pattern, accel, center, axis, mask_file, axis_checked=True):
+    """The sampling pattern of --known_kspace or --known_multislice (`flag`; its dependents are `prefix`accel, ...) as given (None: the
+    default) -> dict(accel, center, axis, mask_file).  ValueError naming the flag for a bad value.  --known_kspace has never refused an
+    axis (`axis_checked` False): build_mask takes every axis but 0 as 1."""
+    accel = DEFAULT_ACCEL if accel is None else accel
+    center = DEFAULT_CENTER if center is None else float(center)
+    axis = DEFAULT_AXIS if axis is None else axis
+    if int(accel) != accel or accel < 1:
+        raise ValueError(f'{prefix}accel must be an integer >= 1, got {accel}')
+    if not 0.0 <= center <= 1.0:
+        raise ValueError(f'{prefix}center must lie in [0, 1], got {center}')
+    if axis_checked and axis not in (0, 1):
+        raise ValueError(f'{prefix}axis must be 0 or 1, got {axis}')
+    if (pattern == 'file') != (mask_file is not None):
+        raise ValueError(f'{prefix}mask_file goes with {flag} file, and that pattern needs it')
+    return dict(accel=int(accel), center=center, axis=int(axis), mask_file=mask_file)
+
+
 def options_from(args):
     """A namespace's --known_kspace / --kspace_* flags (any may be missing) -> None without --known_kspace, else dict(pattern, accel,
     center, axis, mask_file, zero_filled).  ValueError, naming the flag, for a dependent flag without --known_kspace, --known_kspace
@@ -72,9 +90,7 @@ def options_from(args):
         return None
     if pattern not in PATTERNS:
         raise ValueError(f'--known_kspace must be one of {PATTERNS}, got {pattern!r}')
-    cohort = getattr(args, 'manifest', None) is not None or getattr(args, 'brats_root', None) is not None
-    if getattr(args, 'known_volume', None) is None and not cohort:
-        raise ValueError('--known_kspace needs --known_volume')
+    need_known_volume(args, '--known_kspace')
     if getattr(args, 'known_mask', None) is not None:
         raise ValueError('--known_kspace cannot be combined with --known_mask (a voxel mask has no meaning in k-space; '
                          'use --known_drop_slices for slices that were not measured)')
@@ -82,19 +98,9 @@ def options_from(args):
     size = getattr(args, 'image_size', None)
     if size is not None and not kspace_size_ok(size):
         raise ValueError(f'--known_kspace needs an --image_size that is a power of two in [16, 512], got {size}')
-    accel = DEFAULT_ACCEL if accel is None else accel
-    center = DEFAULT_CENTER if center is None else float(center)
-    if int(accel) != accel or accel < 1:
-        raise ValueError(f'--kspace_accel must be an integer >= 1, got {accel}')
-    if not 0.0 <= center <= 1.0:
-        raise ValueError(f'--kspace_center must lie in [0, 1], got {center}')
-    if (pattern == 'file') != (mask_file is not None):
-        raise ValueError('--kspace_mask_file goes with --known_kspace file, and that pattern needs it')
-    seed = getattr(args, 'seed', 0)
-    if not 0 <= int(seed) < 1 << 64:
-        raise ValueError('--known_kspace needs a --seed in [0, 2^64) (its draws are keyed)')
-    return dict(pattern=pattern, accel=int(accel), center=center, axis=DEFAULT_AXIS if axis is None else int(axis), mask_file=mask_file,
-                zero_filled=zero_filled)
+    sampling = pattern_options('--known_kspace', '--kspace_', pattern, accel, center, axis, mask_file, axis_checked=False)
+    need_keyed_seed(args, '--known_kspace')
+    return dict(pattern=pattern, **sampling, zero_filled=zero_filled)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -182,9 +188,7 @@ class KSpaceMeasurement(Constraint):
         x = x[:idx.shape[0]]
         F = ops.fft2(x[:, 0].contiguous())
         d = torch.where(self.mask.index_select(0, idx) != 0, F - self.y.index_select(0, idx), torch.zeros((), device=F.device, dtype=F.dtype))
-        den = self.y_norm.index_select(0, idx)
-        r = torch.where(den > 0, torch.linalg.vector_norm(d.flatten(1), dim=1) / den.clamp_min(1e-30), torch.zeros_like(den))
-        self.residual.scatter_reduce_(0, idx, r, 'amax')
+        self.residual.scatter_reduce_(0, idx, relative_residual(d.flatten(1), self.y_norm.index_select(0, idx)), 'amax')
         self.x_norm.scatter_reduce_(0, idx, torch.linalg.vector_norm(x.flatten(1), dim=1), 'amax')
 
     def zero_filled(self):

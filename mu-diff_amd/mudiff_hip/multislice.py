@@ -36,7 +36,7 @@ import torch
 
 from . import kspace as KS
 from . import thick as TH
-from .constraints import SlabKSpaceRows
+from .constraints import SlabKSpaceRows, need_keyed_seed, need_known_volume
 
 PATTERNS = KS.PATTERNS
 _DEPENDENT = ('thick', 'gap', 'offset', 'profile', 'accel', 'center', 'axis', 'mask_file')
@@ -85,9 +85,7 @@ def options_from(args):
         return None
     if pattern not in PATTERNS:
         raise ValueError(f'--known_multislice must be one of {PATTERNS}, got {pattern!r}')
-    cohort = getattr(args, 'manifest', None) is not None or getattr(args, 'brats_root', None) is not None
-    if getattr(args, 'known_volume', None) is None and not cohort:
-        raise ValueError('--known_multislice needs --known_volume')
+    need_known_volume(args, '--known_multislice')
     if getattr(args, 'known_mask', None) is not None:
         raise ValueError('--known_multislice cannot be combined with --known_mask (a thick slice is measured in k-space; use '
                          '--known_drop_slices for thick slices that were not acquired)')
@@ -98,36 +96,15 @@ def options_from(args):
     L = v['thick']
     if L is None:
         raise ValueError('--known_multislice needs --multislice_thick L (thin slices per thick slice)')
-    if int(L) != L or not 1 <= L <= TH.MAX_L:
-        raise ValueError(f'--multislice_thick must be an integer in [1, {TH.MAX_L}] (thin slices per slab), got {L}')
+    TH.thickness('--multislice_thick', L)                 # (a bad L is named before a bad --image_size)
     from .ops import kspace_size_ok
     size = getattr(args, 'image_size', None)
     if size is not None and not kspace_size_ok(size):
         raise ValueError(f'--known_multislice needs an --image_size that is a power of two in [16, 512], got {size}')
-    gap, offset = (0 if v[f] is None else v[f] for f in ('gap', 'offset'))
-    if int(gap) != gap or gap < 0:
-        raise ValueError(f'--multislice_gap must be an integer >= 0, got {gap}')
-    if int(offset) != offset or offset < 0:
-        raise ValueError(f'--multislice_offset must be an integer >= 0, got {offset}')
-    profile = 'box' if v['profile'] is None else v['profile']
-    if profile not in TH.PROFILES:
-        raise ValueError(f'--multislice_profile must be one of {TH.PROFILES}, got {profile!r}')
-    accel = KS.DEFAULT_ACCEL if v['accel'] is None else v['accel']
-    center = KS.DEFAULT_CENTER if v['center'] is None else float(v['center'])
-    axis = KS.DEFAULT_AXIS if v['axis'] is None else v['axis']
-    if int(accel) != accel or accel < 1:
-        raise ValueError(f'--multislice_accel must be an integer >= 1, got {accel}')
-    if not 0.0 <= center <= 1.0:
-        raise ValueError(f'--multislice_center must lie in [0, 1], got {center}')
-    if axis not in (0, 1):
-        raise ValueError(f'--multislice_axis must be 0 or 1, got {axis}')
-    if (pattern == 'file') != (v['mask_file'] is not None):
-        raise ValueError('--multislice_mask_file goes with --known_multislice file, and that pattern needs it')
-    seed = getattr(args, 'seed', 0)
-    if not 0 <= int(seed) < 1 << 64:
-        raise ValueError('--known_multislice needs a --seed in [0, 2^64) (its draws and its mask are keyed)')
-    return dict(pattern=pattern, L=int(L), gap=int(gap), offset=int(offset), profile=profile, accel=int(accel), center=center, axis=int(axis),
-                mask_file=v['mask_file'], baseline=baseline)
+    slab = TH.slab_options('--multislice_thick', '--multislice_', L, v['gap'], v['offset'], v['profile'])
+    sampling = KS.pattern_options('--known_multislice', '--multislice_', pattern, v['accel'], v['center'], v['axis'], v['mask_file'])
+    need_keyed_seed(args, '--known_multislice', 'its draws and its mask are keyed')
+    return dict(pattern=pattern, **slab, **sampling, baseline=baseline)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -139,11 +116,8 @@ class MultisliceMeasurement(TH.SlabbedMeasurement):
     as thick.ThickMeasurement's; `report`: multislice_<t>.json; `resample`: --known_resample."""
 
     def __init__(self, y, mask, starts, n, weights, report, resample, options):
-        self.y, self.mask, self.report, self.resample, self.options = y, mask, report, int(resample), options
-        self._slabs(starts, n, weights)
-        self.y_norm = torch.linalg.vector_norm(y.flatten(1), dim=1) if y.shape[0] else torch.zeros(0, device=y.device)
-        self.residual = torch.zeros(y.shape[0], device=y.device, dtype=torch.float32)
-        self.x_norm = torch.zeros_like(self.residual)
+        super().__init__(y, starts, n, weights, report, resample, options)
+        self.mask = mask
 
     tag, baseline_through_plane = 'multislice', True
     done_suffix = lambda self: suffix(self)      # noqa: E731
@@ -156,22 +130,11 @@ class MultisliceMeasurement(TH.SlabbedMeasurement):
         idx = torch.as_tensor(gids, dtype=torch.int64, device=self.y.device)
         return SlabKSpaceRows((self.y.index_select(0, idx), self.mask, members, self.weights, self.gains), idx)
 
-    def record(self, bound, x, x_new=None):
-        """x [B,1,S,S]: what the sampler returned (in [-1,1], before any map) for the batch that for_rows bound: keeps, per slab, the
-        largest |M_eff (F(sum_l w_l x_l) - y)| / |y| seen (an ensemble records every sample), and the largest |sum_l w_l |x_new_l|| of
-        what the last constraint was given: with |y|, what the residual's rounding scales with."""
+    def difference(self, operands, ax):
+        """M_eff (F(A x) - y) of the batch's groups: `record` keeps |M_eff (F(sum_l w_l x_l) - y)| / |y|."""
         from . import ops
-        (y, mask, members, weights, _), gids = bound
-        if gids.numel() == 0:
-            return
-        x_new = x if x_new is None else x_new
-        ax = ops.slab_average(x_new[:, 0].abs().contiguous(), members, weights)
-        self.x_norm.scatter_reduce_(0, gids, torch.linalg.vector_norm(ax.flatten(1), dim=1), 'amax')
-        F = ops.fft2(ops.slab_average(x[:, 0].contiguous(), members, weights))
-        d = torch.where(mask != 0, F - y, torch.zeros((), device=F.device, dtype=F.dtype))
-        den = self.y_norm.index_select(0, gids)
-        r = torch.where(den > 0, torch.linalg.vector_norm(d.flatten(1), dim=1) / den.clamp_min(1e-30), torch.zeros_like(den))
-        self.residual.scatter_reduce_(0, gids, r, 'amax')
+        F = ops.fft2(ax)
+        return torch.where(operands[1] != 0, F - operands[0], torch.zeros((), device=F.device, dtype=F.dtype))
 
     def zero_filled_interpolated(self):
         """[n,S,S] in [-1,1] terms: Re F^H y_j per measured slab, interpolated along z as thick.interpolate_slabs does."""
@@ -180,35 +143,13 @@ class MultisliceMeasurement(TH.SlabbedMeasurement):
         z = ops.fft2(self.y, inverse=True).real.contiguous() if self.y.shape[0] else torch.zeros(0, S, S, device=self.y.device)
         return TH.interpolate_slabs(z, self.starts, self.L, self.n)
 
-    def finish(self):
-        """The report with the residuals put in (None for a slab that was not measured)."""
-        res, yn, xn = self.residual.cpu().tolist(), self.y_norm.cpu().tolist(), self.x_norm.cpu().tolist()
-        g = 0
-        for s in self.report['slabs']:
-            s['residual'], s['y_norm'], s['x_norm'] = (res[g], yn[g], xn[g]) if s['measured'] else (None, None, None)
-            g += 1 if s['measured'] else 0
-        self.report['max_residual'] = max(res, default=None)
-        return self.report
-
 
 def measure(region, s0, s1, size, options, seed, device):
     """known_region.KnownRegion (K on the prediction's grid: --norm applied, its known mask = coverage AND finite AND not dropped AND
     sampled range) -> MultisliceMeasurement for the thin slices s0..s1 on the S x S sampler grid."""
-    from . import known_region as KR
     from . import ops
     S, L = int(size), options['L']
-    s0, s1 = int(s0), int(s1)
-    k, vmask = KR.sampler_inputs(region, s0, s1, S, device)                      # [n,1,S,S] each, resized like the conditions
-    n = int(k.shape[0])
-    whole = [bool(v) for v in (vmask.flatten(1).min(1).values != 0).cpu().tolist()]      # every pixel of the slice known
-    w = TH.profile_weights(L, options['profile'])
-    slabs, starts = [], []
-    for first, last, complete in TH.layout(region.mask.shape[2], L, options['gap'], options['offset']):
-        measured = complete and first >= s0 and last <= s1 and all(whole[first - s0:last - s0 + 1])
-        slabs.append(dict(first=first, last=last, measured=bool(measured)))
-        if measured:
-            starts.append(first - s0)
-    w32 = w.astype(np.float32)
+    k, starts, slabs, w32, head, tail = TH.select_slabs(region, int(s0), int(s1), S, options, device)
     M = KS.build_mask(S, options['pattern'], options['accel'], options['center'], options['axis'], seed, options['mask_file'])
     M_eff = KS.symmetrise(M)
     mask = torch.from_numpy(M_eff).to(device)[None].contiguous()
@@ -219,11 +160,9 @@ def measure(region, s0, s1, size, options, seed, device):
     else:
         y = torch.zeros(0, S, S, device=device, dtype=torch.complex64)
     report = dict(pattern=options['pattern'], accel=options['accel'], center=options['center'], axis=options['axis'],
-                  mask_file=options['mask_file'], L=L, gap=options['gap'], offset=options['offset'], profile=options['profile'],
-                  weights=[float(v) for v in w32], sum_w2=float((w32.astype(np.float64) ** 2).sum()), image_size=S, slab=[s0, s1],
-                  given_fraction=float(M.mean()), effective_fraction=float(M_eff.mean()), slabs=slabs, measured_slabs=len(starts),
-                  drop_slices=region.report['drop_slices'], resample=region.resample, resampled=region.report['resampled'])
-    return MultisliceMeasurement(y, mask, starts, n, w32, report, region.resample, options)
+                  mask_file=options['mask_file'], **head, given_fraction=float(M.mean()), effective_fraction=float(M_eff.mean()), slabs=slabs,
+                  **tail)
+    return MultisliceMeasurement(y, mask, starts, int(k.shape[0]), w32, report, region.resample, options)
 
 
 def suffix(measurement):

@@ -1012,12 +1012,17 @@ def _seed64(seed):
     return seed
 
 
+def _draw_args(keys_dev, seed, step, kind):
+    """The four arguments that name a keyed draw, in the order every entry takes them."""
+    return ptr(keys_dev), C.c_uint64(seed), int(step), int(kind)
+
+
 def randn_keyed_into(out, keys_dev, seed, step, kind):
     """Unchecked launch of ops.randn_keyed into `out` (fp32, contiguous, [rows, ...]) with keys already through check_keys and on
     out's device (GraphSampler.sample_keyed checks its keys once per batch, not once per draw)."""
     rows = keys_dev.shape[0]
-    _launch('randn_keyed', out.device, load().mud_randn_keyed, ptr(out), rows, out.numel() // max(rows, 1), ptr(keys_dev), C.c_uint64(seed),
-            int(step), int(kind), STREAM)
+    _launch('randn_keyed', out.device, load().mud_randn_keyed, ptr(out), rows, out.numel() // max(rows, 1), *_draw_args(keys_dev, seed, step, kind),
+            STREAM)
     return out
 
 
@@ -1037,8 +1042,7 @@ def randn_keyed(rows_keys, row_len, seed, step, kind, out=None):
     if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != rows * row_len:
         raise MudiffHipError(f'randn_keyed: out must be a contiguous fp32 tensor of {rows} x {row_len} elements, got {out.dtype} '
                              f'{tuple(out.shape)}')
-    _launch('randn_keyed', out.device, load().mud_randn_keyed, ptr(out), rows, row_len, ptr(k.to(out.device)), C.c_uint64(seed), int(step),
-            int(kind), STREAM)
+    _launch('randn_keyed', out.device, load().mud_randn_keyed, ptr(out), rows, row_len, *_draw_args(k.to(out.device), seed, step, kind), STREAM)
     return out
 
 
@@ -1058,8 +1062,8 @@ def coupling_taps_arg(half_taps, radius):
 def randn_keyed_coupled_into(out, keys_dev, seed, step, kind, taps, radius):
     """Unchecked launch of ops.randn_keyed_coupled into `out`, as randn_keyed_into; (taps, radius) from coupling_taps_arg."""
     rows = keys_dev.shape[0]
-    _launch('randn_keyed_coupled', out.device, load().mud_randn_keyed_coupled, ptr(out), rows, out.numel() // max(rows, 1), ptr(keys_dev),
-            C.c_uint64(seed), int(step), int(kind), taps, int(radius), STREAM)
+    _launch('randn_keyed_coupled', out.device, load().mud_randn_keyed_coupled, ptr(out), rows, out.numel() // max(rows, 1),
+            *_draw_args(keys_dev, seed, step, kind), taps, int(radius), STREAM)
     return out
 
 
@@ -1078,8 +1082,8 @@ def randn_keyed_coupled(rows_keys, row_len, seed, step, kind, half_taps, radius,
     if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != rows * row_len:
         raise MudiffHipError(f'randn_keyed_coupled: out must be a contiguous fp32 tensor of {rows} x {row_len} elements, got {out.dtype} '
                              f'{tuple(out.shape)}')
-    _launch('randn_keyed_coupled', out.device, load().mud_randn_keyed_coupled, ptr(out), rows, row_len, ptr(k.to(out.device)), C.c_uint64(seed),
-            int(step), int(kind), taps, R, STREAM)
+    _launch('randn_keyed_coupled', out.device, load().mud_randn_keyed_coupled, ptr(out), rows, row_len, *_draw_args(k.to(out.device), seed, step, kind),
+            taps, R, STREAM)
     return out
 
 
@@ -1106,13 +1110,38 @@ def _level_and_keys(name, clean, t, a_tab, s_tab, noise, keys, rows, device):
     return t.contiguous(), _f32(a_tab.contiguous()), _f32(s_tab.contiguous()), kd
 
 
+def _level_args(noise, keys_dev, seed, step, kind, t, toff, a_tab, s_tab, clean):
+    """The eleven arguments of every constraint entry that say at which level, and with which draw (_draw_args' four, spelt out: this
+    runs once per launch), the measurement is imposed."""
+    return (ptr(noise), ptr(keys_dev), C.c_uint64(seed), int(step), int(kind), ptr(t), int(toff), ptr(a_tab), ptr(s_tab),
+            1 if a_tab is None else a_tab.numel(), int(bool(clean)))
+
+
+def _contiguous_into(name, x, noise, out):
+    """`out` must be contiguous -> (x and noise made contiguous, out or a new fp32 tensor of x's shape).  An `out` that is x has passed
+    as contiguous, so x is then handed on as it is."""
+    if out is not None and not out.is_contiguous():
+        raise MudiffHipError(f'{name}: out must be contiguous')
+    out = torch.empty(x.shape, device=x.device, dtype=torch.float32) if out is None else out
+    return x.contiguous(), None if noise is None else noise.contiguous(), out
+
+
+def _noise_and_out(name, x, noise, out):
+    """What the checked wrappers share for the state x (fp32 [rows, ...]): `noise` and `out`, where given, are fp32 of x's shape, and
+    _contiguous_into's rule and result."""
+    for what, v in (('noise', noise), ('out', out)):
+        if v is not None and (v.dtype != torch.float32 or v.shape != x.shape):
+            raise MudiffHipError(f'{name}: {what} must be fp32 of shape {tuple(x.shape)}, got {v.dtype} {tuple(v.shape)}')
+    return _contiguous_into(name, x, noise, out)
+
+
 def known_constrain_into(out, x_new, known, mask, keys_dev, seed, step, kind, t, toff, a_tab, s_tab, clean=False, noise=None):
     """Unchecked launch of mud_known_constrain into `out` (fp32, contiguous, [rows, ...]; may be x_new or known): GraphSampler.sample_keyed
     checks its operands once per batch, not once per step.  keys_dev: through check_keys and on out's device (None with `noise`)."""
     rows = out.shape[0]
-    _launch('known_constrain', out.device, load().mud_known_constrain, ptr(x_new), ptr(known), ptr(mask), ptr(noise), ptr(keys_dev), C.c_uint64(seed),
-            int(step), int(kind), ptr(t), int(toff), ptr(a_tab), ptr(s_tab), 1 if a_tab is None else a_tab.numel(), int(bool(clean)), ptr(out), rows,
-            out.numel() // max(rows, 1), STREAM, nbytes=float(out.numel() * (13 if mask is not None else 8)))
+    _launch('known_constrain', out.device, load().mud_known_constrain, ptr(x_new), ptr(known), ptr(mask),
+            *_level_args(noise, keys_dev, seed, step, kind, t, toff, a_tab, s_tab, clean), ptr(out), rows, out.numel() // max(rows, 1), STREAM,
+            nbytes=float(out.numel() * (13 if mask is not None else 8)))
     return out
 
 
@@ -1132,13 +1161,9 @@ def known_constrain(x_new, known, mask, t, toff, a_tab, s_tab, *, noise=None, ke
             raise MudiffHipError(f'known_constrain: {name} must be {dt} of shape {tuple(known.shape)}, got {v.dtype} {tuple(v.shape)}')
     if mask is not None and x_new is None:
         raise MudiffHipError('known_constrain: x_new may be None only without a mask')
-    if out is not None and not out.is_contiguous():
-        raise MudiffHipError('known_constrain: out must be contiguous')
-    known = known if known.is_contiguous() or out is known else known.contiguous()
-    x_new = x_new if x_new is None or x_new.is_contiguous() or out is x_new else x_new.contiguous()
-    mask, noise = (None if v is None else v.contiguous() for v in (mask, noise))
+    known, noise, out = _contiguous_into('known_constrain', known, noise, out)
+    x_new, mask = (None if v is None else v.contiguous() for v in (x_new, mask))
     t, a_tab, s_tab, kd = _level_and_keys('known_constrain', clean, t, a_tab, s_tab, noise, keys, rows, known.device)
-    out = torch.empty(known.shape, device=known.device, dtype=torch.float32) if out is None else out
     return known_constrain_into(out, x_new, known, mask, kd, _seed64(seed), step, kind, t, toff, a_tab, s_tab, clean, noise)
 
 
@@ -1189,14 +1214,42 @@ def fft2(x, inverse=False, out=None):
     return out
 
 
+def _kspace_grid(name, x_new):
+    """x_new: fp32 [rows, S, S] or [rows, 1, S, S] on a grid the transform takes -> (rows, S)."""
+    if x_new.dtype != torch.float32 or x_new.dim() not in (3, 4) or x_new.shape[0] < 1 or x_new.shape[-1] != x_new.shape[-2] or \
+            (x_new.dim() == 4 and x_new.shape[1] != 1):
+        raise MudiffHipError(f'{name}: x_new must be fp32 [rows, S, S] or [rows, 1, S, S], got {x_new.dtype} {tuple(x_new.shape)}')
+    if not kspace_size_ok(x_new.shape[-1]):
+        raise MudiffHipError(f'{name}: S must be a power of two in [16, 512], got {int(x_new.shape[-1])}')
+    return int(x_new.shape[0]), int(x_new.shape[-1])
+
+
+def _kspace_operands(name, x_new, count, y, mask, noise, out, work):
+    """What the two k-space wrappers share once _kspace_grid has passed x_new: y complex64 [count, S, S], mask uint8 [1 or count, S, S],
+    _noise_and_out, and `work`, None or a contiguous complex64 [count, S, S] -> (x_new, y, mask, noise, out, work), contiguous, out and
+    work allocated where they were not given.  count: the rows, or the groups of a slab measurement (its tables are built between the
+    two checks, so a doubly bad call is refused as it always was)."""
+    want = (count,) + tuple(x_new.shape[-2:])
+    if y is None or y.dtype != torch.complex64 or tuple(y.shape) != want:
+        raise MudiffHipError(f'{name}: y must be complex64 {want}, got {None if y is None else (y.dtype, tuple(y.shape))}')
+    if mask is None or mask.dtype != torch.uint8 or mask.dim() != 3 or mask.shape[0] not in (1, count) or tuple(mask.shape[1:]) != want[1:]:
+        raise MudiffHipError(f'{name}: mask must be uint8 [1 or {count}, {want[1]}, {want[2]}], got '
+                             f'{None if mask is None else (mask.dtype, tuple(mask.shape))}')
+    x_new, noise, out = _noise_and_out(name, x_new, noise, out)
+    if work is not None and (work.dtype != torch.complex64 or tuple(work.shape) != want or not work.is_contiguous()):
+        raise MudiffHipError(f'{name}: work must be a contiguous complex64 {want}, got {work.dtype} {tuple(work.shape)}')
+    work = torch.empty(want, device=x_new.device, dtype=torch.complex64) if work is None else work
+    return x_new, y.contiguous(), mask.contiguous(), noise, out, work
+
+
 def kspace_constrain_into(out, x_new, y, mask, work, keys_dev, seed, step, kind, t, toff, a_tab, s_tab, clean=False, noise=None):
     """Unchecked launch of mud_kspace_constrain into `out` (fp32, contiguous, [rows, ..., S, S]; may be x_new): GraphSampler.sample_keyed
     checks its operands once per batch, not once per step.  y, work: complex64 [rows, S, S]; mask: uint8 [1 or rows, S, S]; keys_dev:
     through check_keys and on out's device (None with `noise` or `clean`)."""
     rows, S = out.shape[0], out.shape[-1]
-    _launch('kspace_constrain', out.device, load().mud_kspace_constrain, ptr(x_new), ptr(y), ptr(mask), int(mask.shape[0]), ptr(noise), ptr(keys_dev),
-            C.c_uint64(seed), int(step), int(kind), ptr(t), int(toff), ptr(a_tab), ptr(s_tab), 1 if a_tab is None else a_tab.numel(), int(bool(clean)),
-            ptr(out), ptr(work), rows, S, STREAM, nbytes=float(out.numel() * 44))
+    _launch('kspace_constrain', out.device, load().mud_kspace_constrain, ptr(x_new), ptr(y), ptr(mask), int(mask.shape[0]),
+            *_level_args(noise, keys_dev, seed, step, kind, t, toff, a_tab, s_tab, clean), ptr(out), ptr(work), rows, S, STREAM,
+            nbytes=float(out.numel() * 44))
     return out
 
 
@@ -1211,30 +1264,9 @@ def kspace_constrain(x_new, y, mask, t, toff, a_tab, s_tab, *, noise=None, keys=
     tables and the draw are not needed.  out: None (a new tensor), x_new (in place) or a contiguous fp32 tensor of the shape.  work: None
     or a contiguous complex64 [rows, S, S] workspace (overwritten)."""
     require_gpu(x_new, y, mask, noise, t, a_tab, s_tab, out, work)
-    if x_new.dtype != torch.float32 or x_new.dim() not in (3, 4) or x_new.shape[0] < 1 or x_new.shape[-1] != x_new.shape[-2] or \
-            (x_new.dim() == 4 and x_new.shape[1] != 1):
-        raise MudiffHipError(f'kspace_constrain: x_new must be fp32 [rows, S, S] or [rows, 1, S, S], got {x_new.dtype} {tuple(x_new.shape)}')
-    rows, S = int(x_new.shape[0]), int(x_new.shape[-1])
-    if not kspace_size_ok(S):
-        raise MudiffHipError(f'kspace_constrain: S must be a power of two in [16, 512], got {S}')
-    if y is None or y.dtype != torch.complex64 or tuple(y.shape) != (rows, S, S):
-        raise MudiffHipError(f'kspace_constrain: y must be complex64 {(rows, S, S)}, got {None if y is None else (y.dtype, tuple(y.shape))}')
-    if mask is None or mask.dtype != torch.uint8 or mask.dim() != 3 or mask.shape[0] not in (1, rows) or tuple(mask.shape[1:]) != (S, S):
-        raise MudiffHipError(f'kspace_constrain: mask must be uint8 [1 or {rows}, {S}, {S}], got '
-                             f'{None if mask is None else (mask.dtype, tuple(mask.shape))}')
-    for name, v in (('noise', noise), ('out', out)):
-        if v is not None and (v.dtype != torch.float32 or v.shape != x_new.shape):
-            raise MudiffHipError(f'kspace_constrain: {name} must be fp32 of shape {tuple(x_new.shape)}, got {v.dtype} {tuple(v.shape)}')
-    if out is not None and not out.is_contiguous():
-        raise MudiffHipError('kspace_constrain: out must be contiguous')
-    if work is not None and (work.dtype != torch.complex64 or tuple(work.shape) != (rows, S, S) or not work.is_contiguous()):
-        raise MudiffHipError(f'kspace_constrain: work must be a contiguous complex64 {(rows, S, S)}, got {work.dtype} {tuple(work.shape)}')
-    x_new = x_new if x_new.is_contiguous() else x_new.contiguous()
-    y, mask = y.contiguous(), mask.contiguous()
-    noise = None if noise is None else noise.contiguous()
+    rows, _ = _kspace_grid('kspace_constrain', x_new)
+    x_new, y, mask, noise, out, work = _kspace_operands('kspace_constrain', x_new, rows, y, mask, noise, out, work)
     t, a_tab, s_tab, kd = _level_and_keys('kspace_constrain', clean, t, a_tab, s_tab, noise, keys, rows, x_new.device)
-    out = torch.empty(x_new.shape, device=x_new.device, dtype=torch.float32) if out is None else out
-    work = torch.empty(rows, S, S, device=x_new.device, dtype=torch.complex64) if work is None else work
     return kspace_constrain_into(out, x_new, y, mask, work, kd, _seed64(seed), step, kind, t, toff, a_tab, s_tab, clean, noise)
 
 
@@ -1283,9 +1315,9 @@ def slab_constrain_into(out, x_new, y, tables, keys_dev, seed, step, kind, t, to
     m, w, g = tables
     groups, L = m.shape
     row_len = out.numel() // max(rows, 1)
-    _launch('slab_constrain', out.device, load().mud_slab_constrain, ptr(x_new), ptr(y), _host(m), _host(w), _host(g), groups, L, ptr(noise),
-            ptr(keys_dev), C.c_uint64(seed), int(step), int(kind), ptr(t), int(toff), ptr(a_tab), ptr(s_tab), 1 if a_tab is None else a_tab.numel(),
-            int(bool(clean)), ptr(out), rows, row_len, STREAM, nbytes=float(row_len * 4 * (3 * int((m >= 0).sum()) + groups)))
+    _launch('slab_constrain', out.device, load().mud_slab_constrain, ptr(x_new), ptr(y), _host(m), _host(w), _host(g), groups, L,
+            *_level_args(noise, keys_dev, seed, step, kind, t, toff, a_tab, s_tab, clean), ptr(out), rows, row_len, STREAM,
+            nbytes=float(row_len * 4 * (3 * int((m >= 0).sum()) + groups)))
     return out
 
 
@@ -1309,17 +1341,9 @@ def slab_constrain(x_new, y, members, weights, t, toff, a_tab, s_tab, *, gains=N
     if y is None or y.dtype != torch.float32 or y.dim() < 1 or y.shape[0] != groups or y.numel() != groups * x_new[0].numel():
         raise MudiffHipError(f'slab_constrain: y must be fp32 [{groups}, {x_new[0].numel()}], got '
                              f'{None if y is None else (y.dtype, tuple(y.shape))}')
-    for name, v in (('noise', noise), ('out', out)):
-        if v is not None and (v.dtype != torch.float32 or v.shape != x_new.shape):
-            raise MudiffHipError(f'slab_constrain: {name} must be fp32 of shape {tuple(x_new.shape)}, got {v.dtype} {tuple(v.shape)}')
-    if out is not None and not out.is_contiguous():
-        raise MudiffHipError('slab_constrain: out must be contiguous')
-    x_new = x_new if x_new.is_contiguous() or out is x_new else x_new.contiguous()
-    y = y.contiguous()
-    noise = None if noise is None else noise.contiguous()
+    x_new, noise, out = _noise_and_out('slab_constrain', x_new, noise, out)
     t, a_tab, s_tab, kd = _level_and_keys('slab_constrain', clean, t, a_tab, s_tab, noise, keys, rows, x_new.device)
-    out = torch.empty(x_new.shape, device=x_new.device, dtype=torch.float32) if out is None else out
-    return slab_constrain_into(out, x_new, y, tables, kd, _seed64(seed), step, kind, t, toff, a_tab, s_tab, clean, noise)
+    return slab_constrain_into(out, x_new, y.contiguous(), tables, kd, _seed64(seed), step, kind, t, toff, a_tab, s_tab, clean, noise)
 
 
 def slab_average(x, members, weights, out=None):
@@ -1354,8 +1378,7 @@ def slab_kspace_constrain_into(out, x_new, y, mask, tables, work, keys_dev, seed
     m, w, g = tables
     groups, L = m.shape
     _launch('slab_kspace_constrain', out.device, load().mud_slab_kspace_constrain, ptr(x_new), ptr(y), ptr(mask), int(mask.shape[0]), _host(m), _host(w),
-            _host(g), groups, L, ptr(noise), ptr(keys_dev), C.c_uint64(seed), int(step), int(kind), ptr(t), int(toff), ptr(a_tab), ptr(s_tab),
-            1 if a_tab is None else a_tab.numel(), int(bool(clean)), ptr(out), ptr(work), rows, S, STREAM,
+            _host(g), groups, L, *_level_args(noise, keys_dev, seed, step, kind, t, toff, a_tab, s_tab, clean), ptr(out), ptr(work), rows, S, STREAM,
             nbytes=float(S * S * (12 * int((m >= 0).sum()) + 41 * groups)))
     return out
 
@@ -1374,34 +1397,10 @@ def slab_kspace_constrain(x_new, y, mask, members, weights, t, toff, a_tab, s_ta
     it, the tables and the draw are not needed.  out: None (a new tensor), x_new (in place) or a contiguous fp32 tensor of the shape.
     work: None or a contiguous complex64 [groups, S, S] workspace (overwritten)."""
     require_gpu(x_new, y, mask, noise, t, a_tab, s_tab, out, work)
-    if x_new.dtype != torch.float32 or x_new.dim() not in (3, 4) or x_new.shape[0] < 1 or x_new.shape[-1] != x_new.shape[-2] or \
-            (x_new.dim() == 4 and x_new.shape[1] != 1):
-        raise MudiffHipError(f'slab_kspace_constrain: x_new must be fp32 [rows, S, S] or [rows, 1, S, S], got {x_new.dtype} {tuple(x_new.shape)}')
-    rows, S = int(x_new.shape[0]), int(x_new.shape[-1])
-    if not kspace_size_ok(S):
-        raise MudiffHipError(f'slab_kspace_constrain: S must be a power of two in [16, 512], got {S}')
+    rows, _ = _kspace_grid('slab_kspace_constrain', x_new)
     tables = slab_tables(members, weights, gains)
-    groups = tables[0].shape[0]
-    if y is None or y.dtype != torch.complex64 or tuple(y.shape) != (groups, S, S):
-        raise MudiffHipError(f'slab_kspace_constrain: y must be complex64 {(groups, S, S)}, got '
-                             f'{None if y is None else (y.dtype, tuple(y.shape))}')
-    if mask is None or mask.dtype != torch.uint8 or mask.dim() != 3 or mask.shape[0] not in (1, groups) or tuple(mask.shape[1:]) != (S, S):
-        raise MudiffHipError(f'slab_kspace_constrain: mask must be uint8 [1 or {groups}, {S}, {S}], got '
-                             f'{None if mask is None else (mask.dtype, tuple(mask.shape))}')
-    for name, v in (('noise', noise), ('out', out)):
-        if v is not None and (v.dtype != torch.float32 or v.shape != x_new.shape):
-            raise MudiffHipError(f'slab_kspace_constrain: {name} must be fp32 of shape {tuple(x_new.shape)}, got {v.dtype} {tuple(v.shape)}')
-    if out is not None and not out.is_contiguous():
-        raise MudiffHipError('slab_kspace_constrain: out must be contiguous')
-    if work is not None and (work.dtype != torch.complex64 or tuple(work.shape) != (groups, S, S) or not work.is_contiguous()):
-        raise MudiffHipError(f'slab_kspace_constrain: work must be a contiguous complex64 {(groups, S, S)}, got {work.dtype} '
-                             f'{tuple(work.shape)}')
-    x_new = x_new if x_new.is_contiguous() or out is x_new else x_new.contiguous()
-    y, mask = y.contiguous(), mask.contiguous()
-    noise = None if noise is None else noise.contiguous()
+    x_new, y, mask, noise, out, work = _kspace_operands('slab_kspace_constrain', x_new, tables[0].shape[0], y, mask, noise, out, work)
     t, a_tab, s_tab, kd = _level_and_keys('slab_kspace_constrain', clean, t, a_tab, s_tab, noise, keys, rows, x_new.device)
-    out = torch.empty(x_new.shape, device=x_new.device, dtype=torch.float32) if out is None else out
-    work = torch.empty(groups, S, S, device=x_new.device, dtype=torch.complex64) if work is None else work
     return slab_kspace_constrain_into(out, x_new, y, mask, tables, work, kd, _seed64(seed), step, kind, t, toff, a_tab, s_tab, clean, noise)
 
 
@@ -1494,9 +1493,8 @@ def band_constrain_into(out, x, y, tables, work, keys_dev, seed, step, kind, t, 
     check_keys and on out's device (None with `noise` or `clean`)."""
     row_len = y.numel() // tables.m
     sets = out.numel() // (tables.n * row_len)
-    _launch('band_constrain', out.device, load().mud_band_constrain, ptr(x), ptr(y), C.byref(tables.on(out.device)), ptr(noise), ptr(keys_dev),
-            C.c_uint64(seed), int(step), int(kind), ptr(t), int(toff), ptr(a_tab), ptr(s_tab), 1 if a_tab is None else a_tab.numel(),
-            int(bool(clean)), ptr(out), ptr(work), sets, row_len, STREAM,
+    _launch('band_constrain', out.device, load().mud_band_constrain, ptr(x), ptr(y), C.byref(tables.on(out.device)),
+            *_level_args(noise, keys_dev, seed, step, kind, t, toff, a_tab, s_tab, clean), ptr(out), ptr(work), sets, row_len, STREAM,
             nbytes=float(row_len * 4 * (sets * (2 * tables.nnz + 2 * tables.n + 4 * tables.m) + tables.m)))
     return out
 
@@ -1529,20 +1527,12 @@ def band_constrain(x, y, tables, t, toff, a_tab, s_tab, *, noise=None, keys=None
     rows = sets * tables.n
     if y is None or y.dtype != torch.float32 or y.dim() < 1 or y.shape[0] != tables.m or y.numel() != tables.m * row_len:
         raise MudiffHipError(f'band_constrain: y must be fp32 [{tables.m}, {row_len}], got {None if y is None else (y.dtype, tuple(y.shape))}')
-    for name, v in (('noise', noise), ('out', out)):
-        if v is not None and (v.dtype != torch.float32 or v.shape != x.shape):
-            raise MudiffHipError(f'band_constrain: {name} must be fp32 of shape {tuple(x.shape)}, got {v.dtype} {tuple(v.shape)}')
-    if out is not None and not out.is_contiguous():
-        raise MudiffHipError('band_constrain: out must be contiguous')
+    x, noise, out = _noise_and_out('band_constrain', x, noise, out)
     if work is not None and (work.dtype != torch.float32 or work.numel() != sets * tables.m * row_len or not work.is_contiguous()):
         raise MudiffHipError(f'band_constrain: work must be a contiguous fp32 tensor of {sets * tables.m} x {row_len} elements')
-    x = x if x.is_contiguous() or out is x else x.contiguous()
-    y = y.contiguous()
-    noise = None if noise is None else noise.contiguous()
     t, a_tab, s_tab, kd = _level_and_keys('band_constrain', clean, t, a_tab, s_tab, noise, keys, rows, x.device)
-    out = torch.empty(x.shape, device=x.device, dtype=torch.float32) if out is None else out
     work = torch.empty(sets * tables.m, row_len, device=x.device, dtype=torch.float32) if work is None else work
-    return band_constrain_into(out, x, y, tables, work, kd, _seed64(seed), step, kind, t, toff, a_tab, s_tab, clean, noise)
+    return band_constrain_into(out, x, y.contiguous(), tables, work, kd, _seed64(seed), step, kind, t, toff, a_tab, s_tab, clean, noise)
 
 
 def band_measure(x, tables, out=None):

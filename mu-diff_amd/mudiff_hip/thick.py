@@ -43,7 +43,9 @@ import math
 import numpy as np
 import torch
 
-from .constraints import Constraint, SlabRows, batches      # noqa: F401  (batches: the batching that keeps a slab whole)
+from .constraints import batches      # noqa: F401  (the batching that keeps a slab whole)
+from .constraints import Constraint, SlabRows, need_keyed_seed, need_known_volume, relative_residual
+from .thick_volume import interpolate
 
 PROFILES = ('box', 'gauss')
 MAX_L = 16                           # ops.SLAB_MAX_MEMBERS
@@ -65,6 +67,28 @@ def add_flags(p):
                         'would have without the model; scored too under --gt_volume)')
 
 
+def thickness(flag, L):
+    """--known_thick's / --multislice_thick's L, refused first of all of slab_options' checks."""
+    if int(L) != L or not 1 <= L <= MAX_L:
+        raise ValueError(f'{flag} must be an integer in [1, {MAX_L}] (thin slices per slab), got {L}')
+    return int(L)
+
+
+def slab_options(flag, prefix, L, gap, offset, profile):
+    """The slab layout of --known_thick (`flag`; its dependents are `prefix`gap, ...) or --multislice_thick as given (None: the default)
+    -> dict(L, gap, offset, profile).  ValueError naming the flag for a bad value."""
+    L = thickness(flag, L)
+    gap, offset = 0 if gap is None else gap, 0 if offset is None else offset
+    if int(gap) != gap or gap < 0:
+        raise ValueError(f'{prefix}gap must be an integer >= 0, got {gap}')
+    if int(offset) != offset or offset < 0:
+        raise ValueError(f'{prefix}offset must be an integer >= 0, got {offset}')
+    profile = 'box' if profile is None else profile
+    if profile not in PROFILES:
+        raise ValueError(f'{prefix}profile must be one of {PROFILES}, got {profile!r}')
+    return dict(L=L, gap=int(gap), offset=int(offset), profile=profile)
+
+
 def options_from(args):
     """A namespace's --known_thick / --thick_* flags (any may be missing) -> None without --known_thick, else dict(L, gap, offset,
     profile, interp).  ValueError, naming the flag, for a dependent flag without --known_thick, --known_thick without --known_volume (a
@@ -78,28 +102,16 @@ def options_from(args):
             if given:
                 raise ValueError(f'{flag} needs --known_thick')
         return None
-    if int(L) != L or not 1 <= L <= MAX_L:
-        raise ValueError(f'--known_thick must be an integer in [1, {MAX_L}] (thin slices per slab), got {L}')
-    cohort = getattr(args, 'manifest', None) is not None or getattr(args, 'brats_root', None) is not None
-    if getattr(args, 'known_volume', None) is None and not cohort:
-        raise ValueError('--known_thick needs --known_volume')
+    thickness('--known_thick', L)                         # (a bad L is named before a missing --known_volume)
+    need_known_volume(args, '--known_thick')
     if getattr(args, 'known_kspace', None) is not None:
         raise ValueError('--known_thick cannot be combined with --known_kspace (in-plane undersampling of thick slices is out of scope)')
     if getattr(args, 'known_mask', None) is not None:
         raise ValueError('--known_thick cannot be combined with --known_mask (a thick slice is measured whole; use --known_drop_slices '
                          'for thick slices that were not acquired)')
-    gap, offset = 0 if gap is None else gap, 0 if offset is None else offset
-    if int(gap) != gap or gap < 0:
-        raise ValueError(f'--thick_gap must be an integer >= 0, got {gap}')
-    if int(offset) != offset or offset < 0:
-        raise ValueError(f'--thick_offset must be an integer >= 0, got {offset}')
-    profile = 'box' if profile is None else profile
-    if profile not in PROFILES:
-        raise ValueError(f'--thick_profile must be one of {PROFILES}, got {profile!r}')
-    seed = getattr(args, 'seed', 0)
-    if not 0 <= int(seed) < 1 << 64:
-        raise ValueError('--known_thick needs a --seed in [0, 2^64) (its draws are keyed)')
-    return dict(L=int(L), gap=int(gap), offset=int(offset), profile=profile, interp=interp)
+    slab = slab_options('--known_thick', '--thick_', L, gap, offset, profile)
+    need_keyed_seed(args, '--known_thick')
+    return dict(slab, interp=interp)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -134,12 +146,18 @@ def layout(Z, L, gap=0, offset=0):
 # the measurement of one prediction
 # ---------------------------------------------------------------------------------------------------
 class SlabbedMeasurement(Constraint):
-    """What the measurements of slabs share (ThickMeasurement; multislice.MultisliceMeasurement): the measured slabs of the n local
-    slices - `starts` [G], `group_of` int [n], `weights`, `gains` fp32 [L], `L` - and what follows from them alone: the units that must
-    share a batch, where an ensemble's chunk may end, and the member rows of a batch's groups."""
+    """What the measurements of slabs share (ThickMeasurement; multislice.MultisliceMeasurement): `y` [G,S,S] on the device, one
+    measurement per measured slab of the n local slices; the slabs - `starts` [G], `group_of` int [n], `weights`, `gains` fp32 [L], `L` -
+    and what follows from them alone: the units that must share a batch, where an ensemble's chunk may end, and the member rows of a
+    batch's groups; `report`, `resample` (--known_resample), `options`; and the residuals that `record` collects and `finish` reports.
+    A measurement says what it compares in `difference`."""
 
-    def _slabs(self, starts, n, weights):
+    def __init__(self, y, starts, n, weights, report, resample, options):
         from . import ops
+        self.y, self.report, self.resample, self.options = y, report, int(resample), options
+        self.y_norm = torch.linalg.vector_norm(y.flatten(1), dim=1) if y.shape[0] else torch.zeros(0, device=y.device)
+        self.residual = torch.zeros(y.shape[0], device=y.device, dtype=torch.float32)
+        self.x_norm = torch.zeros_like(self.residual)
         self.starts, self.n = [int(s) for s in starts], int(n)
         self.weights = np.ascontiguousarray(weights, dtype=np.float32)
         self.gains = ops.slab_gains(self.weights)[0]
@@ -193,49 +211,21 @@ class SlabbedMeasurement(Constraint):
             gids.append(g)
         return np.asarray(members, np.int32).reshape(len(members), self.L), gids
 
-
-class ThickMeasurement(SlabbedMeasurement):
-    """What the samplers take for one prediction of n thin slices (the sampled range s0..s1; local index i = slice s0 + i): `y` fp32
-    [G,S,S] on the device, the measured slabs' averages; `starts` [G], each measured slab's first local index; `group_of` int [n], the
-    measured slab of a slice or -1; `weights`, `gains` fp32 [L] (numpy: the host tables of ops.slab_constrain); `report`: thick_<t>.json;
-    `resample`: --known_resample.  A later intake of really thick data only has to fill the same fields."""
-
-    def __init__(self, y, starts, n, weights, report, resample, options):
-        self.y, self.report, self.resample, self.options = y, report, int(resample), options
-        self._slabs(starts, n, weights)
-        self.y_norm = torch.linalg.vector_norm(y.flatten(1), dim=1) if y.shape[0] else torch.zeros(0, device=y.device)
-        self.residual = torch.zeros(y.shape[0], device=y.device, dtype=torch.float32)
-        self.x_norm = torch.zeros_like(self.residual)
-
-    tag, baseline_through_plane = 'thick', True
-    done_suffix = lambda self: suffix(self)      # noqa: E731
-    baseline = lambda self: ('thick_interp', self.interpolated()) if self.options['interp'] else None      # noqa: E731
-
-    def for_rows(self, slices, samples=None, m=None):
-        """group_rows' batch -> constraints.SlabRows = (GraphSampler.sample_keyed's `thick` tuple, the measured slab of each group)."""
-        members, gids = self.group_rows(slices, samples, m)
-        idx = torch.as_tensor(gids, dtype=torch.int64, device=self.y.device)
-        return SlabRows((self.y.index_select(0, idx), members, self.weights, self.gains), idx)
-
     def record(self, bound, x, x_new=None):
-        """x [B,1,S,S]: what the sampler returned (in [-1,1], before any map) for the batch that for_rows bound: keeps, per slab,
-        the largest |A x - y| / |y| seen (an ensemble records every sample), and the largest |A |x_new|| of what the last constraint was
-        given (GraphSampler.thick_x_new; x itself without it): with |y|, what the residual's rounding scales with."""
+        """x [B,1,S,S]: what the sampler returned (in [-1,1], before any map) for the batch that for_rows bound = (the operands, which
+        end in members, weights, gains; the measured slab of each group): keeps, per slab, the largest |difference| / |y| seen (an
+        ensemble records every sample), and the largest |A |x_new|| of what the last constraint was given (GraphSampler.thick_x_new; x
+        itself without it): with |y|, what the residual's rounding scales with."""
         from . import ops
-        thick, gids = bound
+        operands, gids = bound
         if gids.numel() == 0:
             return
+        members, weights = operands[-3], operands[-2]
         x_new = x if x_new is None else x_new
-        ax = ops.slab_average(x_new[:, 0].abs().contiguous(), thick[1], thick[2])
+        ax = ops.slab_average(x_new[:, 0].abs().contiguous(), members, weights)
         self.x_norm.scatter_reduce_(0, gids, torch.linalg.vector_norm(ax.flatten(1), dim=1), 'amax')
-        d = ops.slab_average(x[:, 0].contiguous(), thick[1], thick[2]) - thick[0]
-        den = self.y_norm.index_select(0, gids)
-        r = torch.where(den > 0, torch.linalg.vector_norm(d.flatten(1), dim=1) / den.clamp_min(1e-30), torch.zeros_like(den))
-        self.residual.scatter_reduce_(0, gids, r, 'amax')
-
-    def interpolated(self):
-        """interpolate_slabs of the slab averages."""
-        return interpolate_slabs(self.y, self.starts, self.L, self.n)
+        d = self.difference(operands, ops.slab_average(x[:, 0].contiguous(), members, weights))
+        self.residual.scatter_reduce_(0, gids, relative_residual(d.flatten(1), self.y_norm.index_select(0, gids)), 'amax')
 
     def finish(self):
         """The report with the residuals put in (None for a slab that was not measured)."""
@@ -248,35 +238,46 @@ class ThickMeasurement(SlabbedMeasurement):
         return self.report
 
 
+class ThickMeasurement(SlabbedMeasurement):
+    """What the samplers take for one prediction of n thin slices (the sampled range s0..s1; local index i = slice s0 + i): `y` fp32
+    [G,S,S] on the device, the measured slabs' averages; `starts` [G], each measured slab's first local index; `group_of` int [n], the
+    measured slab of a slice or -1; `weights`, `gains` fp32 [L] (numpy: the host tables of ops.slab_constrain); `report`: thick_<t>.json;
+    `resample`: --known_resample.  A later intake of really thick data only has to fill the same fields."""
+
+    tag, baseline_through_plane = 'thick', True
+    done_suffix = lambda self: suffix(self)      # noqa: E731
+    baseline = lambda self: ('thick_interp', self.interpolated()) if self.options['interp'] else None      # noqa: E731
+
+    def for_rows(self, slices, samples=None, m=None):
+        """group_rows' batch -> constraints.SlabRows = (GraphSampler.sample_keyed's `thick` tuple, the measured slab of each group)."""
+        members, gids = self.group_rows(slices, samples, m)
+        idx = torch.as_tensor(gids, dtype=torch.int64, device=self.y.device)
+        return SlabRows((self.y.index_select(0, idx), members, self.weights, self.gains), idx)
+
+    def difference(self, operands, ax):
+        """A x - y of the batch's groups: `record` keeps |A x - y| / |y|."""
+        return ax - operands[0]
+
+    def interpolated(self):
+        """interpolate_slabs of the slab averages."""
+        return interpolate_slabs(self.y, self.starts, self.L, self.n)
+
+
 def interpolate_slabs(y, starts, L, n):
-    """y fp32 [G,S,S], one image per measured slab -> [n,S,S] in [-1,1] terms: piecewise linear along z through (slab centre, y_j),
-    constant beyond the first and the last centre - the thick slices as one would resample them without the model.  Without a measured
-    slab: -1 everywhere."""
-    G, S = y.shape[0], y.shape[-1]
-    if G == 0:
-        return torch.full((n, S, S), -1.0, device=y.device)
-    centres = np.asarray(starts, np.float64) + (L - 1) / 2.0
-    z = np.arange(n, dtype=np.float64)
-    hi = np.clip(np.searchsorted(centres, z, side='right'), 1, max(G - 1, 1))
-    lo = hi - 1
-    hi = np.minimum(hi, G - 1)
-    span = np.where(hi > lo, centres[hi] - centres[lo], 1.0)
-    f = np.clip((z - centres[lo]) / span, 0.0, 1.0)
-    f = torch.from_numpy(f.astype(np.float32)).to(y.device)[:, None, None]
-    ya = y.index_select(0, torch.from_numpy(lo).to(y.device))
-    yb = y.index_select(0, torch.from_numpy(hi).to(y.device))
-    return ((1.0 - f) * ya + f * yb).contiguous()
+    """y fp32 [G,S,S], one image per measured slab of L slices from local index starts[j] -> [n,S,S] in [-1,1] terms:
+    thick_volume.interpolate through the slab centres - the thick slices as one would resample them without the model."""
+    return interpolate(y, np.asarray(starts, np.float64) + (L - 1) / 2.0, n)
 
 
-def measure(region, s0, s1, size, options, device):
-    """known_region.KnownRegion (K on the prediction's grid: --norm applied, its known mask = coverage AND finite AND not dropped AND
-    sampled range) -> ThickMeasurement for the thin slices s0..s1 on the S x S sampler grid."""
+def select_slabs(region, s0, s1, S, options, device):
+    """known_region.KnownRegion and the slab layout of `options` (L, gap, offset, profile) for the thin slices s0..s1 on the S x S grid
+    -> (k [n,1,S,S]: K as the sampler sees it; starts: the measured slabs' first local index; slabs: every slab of the volume as the
+    report lists it; w32: the profile, fp32 [L]; and the fields every report of slabs holds, in two dicts: those before `slabs` and
+    those after it).  A slab is measured when it is complete, inside the range, and K is known on every
+    pixel of every one of its slices."""
     from . import known_region as KR
-    from . import ops
-    S, L = int(size), options['L']
-    s0, s1 = int(s0), int(s1)
+    L = options['L']
     k, vmask = KR.sampler_inputs(region, s0, s1, S, device)                      # [n,1,S,S] each, resized like the conditions
-    n = int(k.shape[0])
     whole = [bool(v) for v in (vmask.flatten(1).min(1).values != 0).cpu().tolist()]      # every pixel of the slice known
     w = profile_weights(L, options['profile'])
     slabs, starts = [], []
@@ -286,15 +287,25 @@ def measure(region, s0, s1, size, options, device):
         if measured:
             starts.append(first - s0)
     w32 = w.astype(np.float32)
+    head = dict(L=L, gap=options['gap'], offset=options['offset'], profile=options['profile'], weights=[float(v) for v in w32],
+                sum_w2=float((w32.astype(np.float64) ** 2).sum()), image_size=S, slab=[s0, s1])
+    tail = dict(measured_slabs=len(starts), drop_slices=region.report['drop_slices'], resample=region.resample,
+                resampled=region.report['resampled'])
+    return k, starts, slabs, w32, head, tail
+
+
+def measure(region, s0, s1, size, options, device):
+    """known_region.KnownRegion (K on the prediction's grid: --norm applied, its known mask = coverage AND finite AND not dropped AND
+    sampled range) -> ThickMeasurement for the thin slices s0..s1 on the S x S sampler grid."""
+    from . import ops
+    S, L = int(size), options['L']
+    k, starts, slabs, w32, head, tail = select_slabs(region, int(s0), int(s1), S, options, device)
     if starts:
         members = np.asarray([list(range(s, s + L)) for s in starts], np.int32)
         y = ops.slab_average(k[:, 0].contiguous(), members, w32)
     else:
         y = torch.zeros(0, S, S, device=device, dtype=torch.float32)
-    report = dict(L=L, gap=options['gap'], offset=options['offset'], profile=options['profile'], weights=[float(v) for v in w32],
-                  sum_w2=float((w32.astype(np.float64) ** 2).sum()), image_size=S, slab=[s0, s1], slabs=slabs, measured_slabs=len(starts),
-                  drop_slices=region.report['drop_slices'], resample=region.resample, resampled=region.report['resampled'])
-    return ThickMeasurement(y, starts, n, w32, report, region.resample, options)
+    return ThickMeasurement(y, starts, int(k.shape[0]), w32, dict(head, slabs=slabs, **tail), region.resample, options)
 
 
 def suffix(measurement):

@@ -49,7 +49,7 @@ import math
 import numpy as np
 import torch
 
-from .constraints import Constraint
+from .constraints import Constraint, level_tables, need_keyed_seed, relative_residual
 
 PROFILES = ('box', 'gauss')
 MANIFEST = 'manifest'
@@ -120,9 +120,7 @@ def options_from(args):
     resample = 1 if resample is None else resample
     if int(resample) != resample or resample < 1:
         raise ValueError(f'--known_resample must be an integer >= 1, got {resample}')
-    seed = getattr(args, 'seed', 0)
-    if not 0 <= int(seed) < 1 << 64:
-        raise ValueError('--known_thick_volume needs a --seed in [0, 2^64) (its draws are keyed)')
+    need_keyed_seed(args, '--known_thick_volume')
     return dict(volume=volume, thickness=None if T is None else float(T), profile=profile, drop=_drop_ranges(drop), baseline=baseline,
                 resample=int(resample))
 
@@ -234,9 +232,8 @@ class BandMeasurement(Constraint):
         if not self.m:
             x.copy_(x_new)
             return
-        dc = sampler._diffusion_tables()
-        ops.band_constrain_into(x, x_new, self._y, self.tables, self._work, keys_dev, seed, step, ops.KIND_BAND, sampler.t_rows, 0, dc[0], dc[1],
-                                clean=clean)
+        ops.band_constrain_into(x, x_new, self._y, self.tables, self._work, keys_dev, seed, step, ops.KIND_BAND, sampler.t_rows, 0,
+                                *level_tables(sampler), clean=clean)
 
     def record_volume(self, x, x_new=None):
         """x [sets * n,1,S,S]: what the sampler returned (in [-1,1], before any map): keeps, per thick slice, the largest
@@ -248,9 +245,7 @@ class BandMeasurement(Constraint):
         sets = x.shape[0] // self.n
         xs = x.reshape(sets, self.n, -1)
         d = ops.band_measure(xs.contiguous(), self.tables) - self.y.reshape(1, self.m, -1)
-        r = torch.linalg.vector_norm(d, dim=2)
-        r = torch.where(self.y_norm > 0, r / self.y_norm.clamp_min(1e-30), torch.zeros_like(r))
-        self.residual = torch.maximum(self.residual, r.amax(0))
+        self.residual = torch.maximum(self.residual, relative_residual(d, self.y_norm).amax(0))
         xn = xs if x_new is None else x_new.reshape(sets, self.n, -1)
         self.x_new_norm = torch.maximum(self.x_new_norm, torch.linalg.vector_norm(xn, dim=2).amax(0))
 
