@@ -384,9 +384,9 @@ int mud_lpips_u8(const uint8_t* pred, const uint8_t* gt, int n, int H, int W, co
  * Philox4x64-10 (numpy.random.Philox's algorithm and word order) with key (seed, 0x4D55444946460001) and counter
  * (e/4, s, (j << 32) | (step << 8) | kind, 0); lane l = e % 4 takes the word pair (w[2(l/2)], w[2(l/2)+1]) = (wa, wb),
  * u1 = ((wa >> 11) + 1) 2^-53, u2 = (wb >> 11) 2^-53, r = sqrt(-2 log u1), theta = 2 pi u2: r cos theta (even l), r sin theta (odd l),
- * in fp64, rounded once to fp32.  kind: 0 x_init, 1 z, 2 posterior noise, or 5 / 6 / 7 / 8: the draws of mud_kspace_constrain /
- * mud_slab_constrain / mud_slab_kspace_constrain / mud_band_constrain, so that a caller can inject what those entries draw (3 and 4, mud_known_constrain's,
- * stay refused); step in
+ * in fp64, rounded once to fp32.  kind: 0 x_init, 1 z, 2 posterior noise, or 5 / 6 / 7 / 8 / 9: the draws of mud_kspace_constrain /
+ * mud_slab_constrain / mud_slab_kspace_constrain / mud_band_constrain / mud_lowres_constrain, so that a caller can inject what those entries
+ * draw (3 and 4, mud_known_constrain's, stay refused); step in
  * [0, 2^24); row_len > 0.
  * mud_ensemble_stats: samples [n][N][hw] -> mean, std [n][hw] (N >= 2, hw > 0): y = clamp(x*scale + shift, lo, hi) in fp32 (each step
  * rounded once, NaN kept), m = (sum_j y_j) / N and v = sum_j (y_j - m)^2 / (N - 1) in fp64 in sample order j = 0..N-1,
@@ -596,6 +596,41 @@ int mud_band_constrain(const float* x, const float* y, const mud_band_tables* ta
                        int sets, int64_t row_len, void* stream);
 /* mud_band_measure: new (no counterpart in the reference) */
 int mud_band_measure(const float* x, const mud_band_tables* tab, float* ax, int sets, int64_t row_len, void* stream);
+
+/* ---- sampling a target given as a volume coarser than the stack in all three axes (mudiff_hip.lowres_volume; GraphSampler.
+ *      sample_lockstep).  Coarse voxel (jz, jy, jx) is a separable weighted average of fine voxels,
+ * y = (A_z (x) A_y (x) A_x) k, with one struct mud_band_tables per axis: tab_z over the n = tab_z.n thin slices of a set, tab_y over
+ * the H image rows (tab_y.n == H), tab_x over the W image columns (tab_x.n == W).  A A^T = G_z (x) G_y (x) G_x, so the orthogonal
+ * projection x - A^T (A A^T)^-1 (A (x - s eta) - a y) is one banded Cholesky solve per axis.  x, noise, out are [rows][H][W] with
+ * rows = sets * n, sample-major as for mud_band_constrain (keys [rows][2], t [rows]); y is [m_z][m_y][m_x], shared by the sets; work
+ * is the caller's, mud_lowres_ws_floats(sets, n, m_z, m_y, m_x) floats (P [rows][m_y][m_x], then U [sets][m_z][m_y][m_x]), overwritten.
+ * mud_lowres_constrain, four launches, with a, s of the level of the set's first row as in mud_band_constrain (clean: a = 1, s = 0):
+ *   1. P[r][jy][jx] = sum_sx wx (sum_sy wy (x - s * eta)[r][yy][xx]): per column the image rows of coarse row jy in tab_y's order, then
+ *      the columns of jx in tab_x's order.  eta: `noise`, else mud_randn_keyed's value for element yy * W + xx of the row keyed
+ *      keys[2r..2r+1] under (seed, step, kind) (mudiff_hip.ops.KIND_LOWRES = 9 is this entry's); drawn once per coarse row that covers it
+ *   2. per set and coarse column: R_j = sum_s wz P[member] - a * y_j in tab_z's order, then mud_band_constrain's forward and backward
+ *      pass with tab_z.lc
+ *   3. per set and coarse slice: the same two passes with tab_y.lc along jy, then with tab_x.lc along jx -> U
+ *   4. c = sum_jz twz (sum_jy twy (sum_jx twx U[jz][jy][jx])) with the transposed tables, each index ascending; out = (c == 0 ? x : x - c)
+ * in fp32, every product and sum rounded once, every sum from 0.  out may be x; then an element under no coarse voxel (a thin slice, an
+ * image row or a column outside every support) is not written.  16-byte accesses when W % 4 == 0 and x, noise, out are 16-byte aligned,
+ * else element by element.  No atomics, no allocation: a set's result depends on its own rows, keys and the tables alone.
+ * mud_lowres_measure: ax [sets][m_z][m_y][m_x] = A x by passes 1 and 2's sums alone (no eta, no y, no solve); work: rows * m_y * m_x floats.
+ * mud_lowres_ws_floats: the floats of work; -1 for a size < 1.
+ * MUD_ERR_ARG before any launch for a null pointer that is needed, per axis the limits of mud_band_constrain (m of an axis 0 among
+ * them), tab_y.n != H, tab_x.n != W, tab_z.n not dividing rows, rows > 65535, rows * H * W >= 2^31, ntab <= 0, a kind or step out of
+ * range, neither noise nor keys, and a work or out that overlaps another operand (out == x excepted).  The kernels skip a table index
+ * outside its axis.  Replaces nothing in the reference (it has no measurement model); new with section 5.31. */
+/* mud_lowres_constrain: new (no counterpart in the reference) */
+int mud_lowres_constrain(const float* x, const float* y, const mud_band_tables* tab_z, const mud_band_tables* tab_y,
+                         const mud_band_tables* tab_x, int H, int W, int rows, float* work, const float* noise, const int64_t* keys,
+                         uint64_t seed, int step, int kind, const int64_t* t, int toff, const float* a_tab, const float* s_tab, int ntab,
+                         int clean, float* out, void* stream);
+/* mud_lowres_measure: new (no counterpart in the reference) */
+int mud_lowres_measure(const float* x, const mud_band_tables* tab_z, const mud_band_tables* tab_y, const mud_band_tables* tab_x, int H,
+                       int W, int rows, float* work, float* ax, void* stream);
+/* mud_lowres_ws_floats: new (no counterpart in the reference) */
+int64_t mud_lowres_ws_floats(int sets, int n, int m_z, int m_y, int m_x);
 
 /* ---- through-plane roughness of a volume (mudiff_hip.volume_through_plane; the volume pipeline's --through_plane).
  * vol (fp32) and the optional mask (uint8, may be NULL: every voxel is inside; else non-zero is inside) are [Z, X, Y] with planes

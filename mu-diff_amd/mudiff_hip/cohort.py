@@ -254,7 +254,7 @@ def run(args, subjects, predict=None):
                                  for m, vol in zip(needed, conds)]
                         torch.cuda.synchronize(device)
                     report.add_evaluation(resampled, found)
-                    sargs.known_inputs = sargs.thick_inputs = None
+                    sargs.known_inputs = sargs.thick_inputs = sargs.lowres_inputs = None
                     if getattr(args, 'known_thick_volume', None) is not None:      # (the subject's Y: mudiff_hip.thick_volume)
                         from . import thick_volume as TV
                         sargs.known_thick_volume = subject.known if args.known_thick_volume == TV.MANIFEST else args.known_thick_volume
@@ -262,6 +262,13 @@ def run(args, subjects, predict=None):
                             raise ValueError(f'--known_thick_volume {TV.MANIFEST}: the manifest names no `known` file for this subject')
                         thick = TV.options_from(sargs)
                         sargs.thick_inputs = TV.on_grid(raws[0], TV.read_input(thick, options), thick, options, gpu, align=found.get('align'))
+                    elif getattr(args, 'known_lowres_volume', None) is not None:   # (the subject's Y: mudiff_hip.lowres_volume)
+                        from . import lowres_volume as LV
+                        sargs.known_lowres_volume = subject.known if args.known_lowres_volume == LV.MANIFEST else args.known_lowres_volume
+                        if not sargs.known_lowres_volume:
+                            raise ValueError(f'--known_lowres_volume {LV.MANIFEST}: the manifest names no `known` file for this subject')
+                        lowres = LV.options_from(sargs)
+                        sargs.lowres_inputs = LV.on_grid(raws[0], LV.read_input(lowres, options), lowres, options, gpu, align=found.get('align'))
                     elif subject.known:                            # (the subject's --known_volume: mudiff_hip.known_region)
                         from . import known_region as KR
                         sargs.known_volume, sargs.known_mask = subject.known, subject.known_mask

@@ -79,9 +79,10 @@ def options_from(args):
     if volume is None:
         if getattr(args, 'manifest', None) is not None or getattr(args, 'brats_root', None) is not None:
             return None                                   # a cohort: K comes from the manifest, per subject; the other flags from here
-        thick_volume = getattr(args, 'known_thick_volume', None) is not None      # (mudiff_hip.thick_volume takes --known_resample too)
+        own_grid = (getattr(args, 'known_thick_volume', None) is not None or          # (mudiff_hip.thick_volume and mudiff_hip.lowres_volume
+                    getattr(args, 'known_lowres_volume', None) is not None)           #  take --known_resample too)
         for flag, given in (('--known_mask', mask is not None), ('--known_drop_slices', drop is not None),
-                            ('--known_resample', resample != 1 and not thick_volume)):
+                            ('--known_resample', resample != 1 and not own_grid)):
             if given:
                 raise ValueError(f'{flag} needs --known_volume')
         return None

@@ -1031,7 +1031,8 @@ def randn_keyed(rows_keys, row_len, seed, step, kind, out=None):
     rows_keys[r] = (slice, sample) (int64 [rows, 2], host or device): Philox4x64-10 + Box-Muller in fp64 (mud_randn_keyed).  `out`:
     a contiguous fp32 device tensor of rows * row_len elements to fill (any shape); without it the result lands on rows_keys's device
     (or the current one for host keys).  kind: KIND_X_INIT, KIND_Z or KIND_NOISE (or KIND_KSPACE / KIND_THICK / KIND_MULTISLICE /
-    KIND_BAND, to inject what ops.kspace_constrain / ops.slab_constrain / ops.slab_kspace_constrain / ops.band_constrain draw)."""
+    KIND_BAND / KIND_LOWRES, to inject what ops.kspace_constrain / ops.slab_constrain / ops.slab_kspace_constrain / ops.band_constrain /
+    ops.lowres_constrain draw)."""
     k = check_keys(rows_keys)
     seed = _seed64(seed)
     rows, row_len = k.shape[0], int(row_len)
@@ -1547,6 +1548,112 @@ def band_measure(x, tables, out=None):
     out = torch.empty(shape, device=x.device, dtype=torch.float32) if out is None else out
     _launch('band_measure', x.device, load().mud_band_measure, ptr(x), C.byref(tables.on(x.device)), ptr(out), sets, row_len, STREAM,
             nbytes=float(row_len * 4 * sets * (tables.nnz + tables.m)))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# sampling a target given as a volume coarser than the stack in all three axes (csrc/lowres.hip, mudiff_hip.lowres_volume; DESIGN.md
+# section 5.31)
+KIND_LOWRES = 9                      # the draw of mud_lowres_constrain: the coarse voxels' forward noise
+
+
+class LowresTables:
+    """The three BandTables of mud_lowres_constrain / mud_lowres_measure (lowres_tables): `z` over the thin slices, `y` over the image
+    rows, `x` over the image columns, and `cond` = cond(G_z) cond(G_y) cond(G_x), the condition number of A A^T for A = A_z (x) A_y (x) A_x."""
+
+    def __init__(self, z, y, x):
+        self.z, self.y, self.x = z, y, x
+        self.cond = z.cond * y.cond * x.cond
+        self.shape = (z.m, y.m, x.m)
+
+    def on(self, device):
+        return tuple(C.byref(t.on(device)) for t in (self.z, self.y, self.x))
+
+
+def lowres_tables(A_z, A_y, A_x):
+    """A_z [m_z, n], A_y [m_y, H], A_x [m_x, W] (each as band_tables takes it) -> LowresTables.  Every axis keeps band_tables' own limits;
+    ValueError in addition when cond(G_z) cond(G_y) cond(G_x) > 1e4: the Kronecker product's condition number is the product, and the
+    fp32 solves run one after the other."""
+    tabs = LowresTables(band_tables(A_z), band_tables(A_y), band_tables(A_x))
+    if not tabs.cond <= BAND_MAX_COND:
+        raise ValueError(f'lowres_tables: cond(A A^T) = {tabs.z.cond:.3g} x {tabs.y.cond:.3g} x {tabs.x.cond:.3g} = {tabs.cond:.3g} exceeds '
+                         f'{BAND_MAX_COND:g}: the coarse voxels are (nearly) dependent and the fp32 solve would leave the 1e-3 parity bar')
+    return tabs
+
+
+def lowres_ws_floats(sets, tables):
+    """The floats of the workspace of lowres_constrain / lowres_measure for `sets` sets (mud_lowres_ws_floats)."""
+    return int(load().mud_lowres_ws_floats(int(sets), tables.z.n, *tables.shape))
+
+
+def lowres_constrain_into(out, x, y, tables, work, keys_dev, seed, step, kind, t, toff, a_tab, s_tab, clean=False, noise=None):
+    """Unchecked launch of mud_lowres_constrain into `out` (fp32, contiguous, [sets * n, H, W]; may be x): GraphSampler.sample_lockstep
+    checks its operands once, not once per step.  y: fp32 [m_z, m_y, m_x]; tables: lowres_tables'; work: fp32, lowres_ws_floats
+    elements; keys_dev: through check_keys and on out's device (None with `noise` or `clean`)."""
+    H, W = tables.y.n, tables.x.n
+    rows = out.numel() // (H * W)
+    mz, my, mx = tables.shape
+    _launch('lowres_constrain', out.device, load().mud_lowres_constrain, ptr(x), ptr(y), *tables.on(out.device), H, W, rows, ptr(work),
+            *_level_args(noise, keys_dev, seed, step, kind, t, toff, a_tab, s_tab, clean), ptr(out), STREAM,
+            nbytes=float(4 * (rows * (tables.y.nnz * W + 2 * H * W + my * mx * (1 + tables.z.nnz / tables.z.n)) + 8 * (rows // tables.z.n) * mz * my * mx)))
+    return out
+
+
+def _lowres_shapes(name, x, tables):
+    """x: fp32 [sets, n, H, W] -> sets."""
+    if not isinstance(tables, LowresTables):
+        raise MudiffHipError(f'{name}: tables must come from ops.lowres_tables')
+    want = (tables.z.n, tables.y.n, tables.x.n)
+    if x.dtype != torch.float32 or x.dim() != 4 or x.shape[0] < 1 or tuple(x.shape[1:]) != want:
+        raise MudiffHipError(f'{name}: x must be a non-empty fp32 [sets, {want[0]}, {want[1]}, {want[2]}] tensor, got {x.dtype} {tuple(x.shape)}')
+    sets = int(x.shape[0])
+    if x.numel() >= 1 << 31 or sets * want[0] > 65535:
+        raise MudiffHipError(f'{name}: sets * n * H * W must be < 2^31 and sets * n <= 65535, got {tuple(x.shape)}')
+    return sets
+
+
+def lowres_constrain(x, y, tables, t, toff, a_tab, s_tab, *, noise=None, keys=None, seed=0, step=0, kind=KIND_LOWRES, clean=False, out=None,
+                     work=None):
+    """The data-consistency step of a target measured on a coarser grid in all three axes (mud_lowres_constrain).  With A = A_z (x) A_y
+    (x) A_x of tables' three axes and c = clamp(t[first row of the set] + toff, 0, len(a_tab) - 1), per set
+        out = x - A^T (A A^T)^-1 (A (x - s_tab[c] * eta) - a_tab[c] * y)             (clean: out = x - A^T (A A^T)^-1 (A x - y)),
+    one banded Cholesky solve per axis, so that A out is A q_sample(k, c) for y = A k and everything orthogonal to the rows of A is
+    untouched.  A pixel under no coarse voxel is copied bit for bit.  x: fp32 [sets, n, H, W] (a set: one sample's whole stack); y: fp32
+    [m_z, m_y, m_x], shared by the sets.  eta: `noise` (fp32, x's shape) when given, else the keyed normal ops.randn_keyed gives
+    keys[r] = (slice, sample) of row r = set * n + i under (seed, step, kind), drawn in the kernel.  t: int64 [sets * n]; with `clean`
+    it, the level tables and the draw are not needed.  out: None (a new tensor), x (in place) or a contiguous fp32 tensor of the shape.
+    work: None or a contiguous fp32 workspace of lowres_ws_floats(sets, tables) elements (overwritten)."""
+    require_gpu(x, y, noise, t, a_tab, s_tab, out, work)
+    sets = _lowres_shapes('lowres_constrain', x, tables)
+    rows = sets * tables.z.n
+    if y is None or y.dtype != torch.float32 or tuple(y.shape) != tables.shape:
+        raise MudiffHipError(f'lowres_constrain: y must be fp32 {list(tables.shape)}, got {None if y is None else (y.dtype, tuple(y.shape))}')
+    x, noise, out = _noise_and_out('lowres_constrain', x, noise, out)
+    need = lowres_ws_floats(sets, tables)
+    if work is not None and (work.dtype != torch.float32 or work.numel() != need or not work.is_contiguous()):
+        raise MudiffHipError(f'lowres_constrain: work must be a contiguous fp32 tensor of {need} elements')
+    t, a_tab, s_tab, kd = _level_and_keys('lowres_constrain', clean, t, a_tab, s_tab, noise, keys, rows, x.device)
+    work = torch.empty(need, device=x.device, dtype=torch.float32) if work is None else work
+    return lowres_constrain_into(out, x, y.contiguous(), tables, work, kd, _seed64(seed), step, kind, t, toff, a_tab, s_tab, clean, noise)
+
+
+def lowres_measure(x, tables, out=None, work=None):
+    """ax[set] = A x[set] on the coarse lattice, in mud_lowres_constrain's order and rounding (mud_lowres_measure): the measurement y
+    of k, and A x of the residual.  x: fp32 [sets, n, H, W] -> fp32 [sets, m_z, m_y, m_x].  work: None or a contiguous fp32 workspace of
+    at least sets * n * m_y * m_x elements (overwritten)."""
+    require_gpu(x, out, work)
+    sets = _lowres_shapes('lowres_measure', x, tables)
+    shape = (sets,) + tables.shape
+    if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous()):
+        raise MudiffHipError(f'lowres_measure: out must be a contiguous fp32 tensor of shape {shape}, got {out.dtype} {tuple(out.shape)}')
+    need = sets * tables.z.n * tables.y.m * tables.x.m
+    if work is not None and (work.dtype != torch.float32 or work.numel() < need or not work.is_contiguous()):
+        raise MudiffHipError(f'lowres_measure: work must be a contiguous fp32 tensor of at least {need} elements')
+    x = x if x.is_contiguous() else x.contiguous()
+    out = torch.empty(shape, device=x.device, dtype=torch.float32) if out is None else out
+    work = torch.empty(need, device=x.device, dtype=torch.float32) if work is None else work
+    _launch('lowres_measure', x.device, load().mud_lowres_measure, ptr(x), *tables.on(x.device), tables.y.n, tables.x.n, sets * tables.z.n, ptr(work),
+            ptr(out), STREAM, nbytes=float(4 * sets * tables.z.n * (tables.y.nnz * tables.x.n + 2 * tables.y.m * tables.x.m)))
     return out
 
 

@@ -39,7 +39,8 @@ centre, whether it was measured and |A x - y| / |y| of the sampler's result (the
 takes each subject's Y from the manifest's `known` column under `--known_thick_volume manifest`.
 
 Out of scope: in-plane resampling or registration of Y; multi-coil or in-plane-undersampled thick volumes; a profile per slice; the
-uncaptured (use_graph=False) path; the 2D driver.
+uncaptured (use_graph=False) path; the 2D driver.  A Y that is coarser in-plane as well goes to --known_lowres_volume
+(mudiff_hip.lowres_volume, section 5.31), which measures it on its own grid in all three axes.
 """
 from __future__ import annotations
 
@@ -309,6 +310,13 @@ def on_grid(first, y_file, options, intake_options, device, align=None):
     """Y (read_input's) against the grid the prediction will have (volume_prepare.evaluation_grid: `first` is the first input as
     read_for_evaluation reads it, or its RawVolume) -> ThickInputs.  Y is reoriented by its own affine under --reorient and never
     resampled: slice_geometry's ValueError when it does not share the grid's in-plane geometry."""
+    shape, grid_world, values, y_world = own_grid_volume(first, y_file, intake_options, device, align)
+    return ThickInputs(values, slice_geometry(shape, grid_world, values.shape, y_world), shape, options)
+
+
+def own_grid_volume(first, y_file, intake_options, device, align=None):
+    """What on_grid (and lowres_volume.on_grid) compares: -> (the prediction grid's shape and world affine, Y's values [X,Y,Z] float as
+    read - reoriented under --reorient, never resampled - and Y's world affine)."""
     from . import volume_prepare as VP
     from . import volume_regrid as VR
     grid, Y, _, y_affine, _, _ = VP.evaluation_grid(first, y_file, None, intake_options, device, align)
@@ -318,9 +326,7 @@ def on_grid(first, y_file, options, intake_options, device, align=None):
         y_world, values = VR.world_affine_of(y_file[1], y_file[2]), np.asarray(Y)
     else:
         y_world, values = np.asarray(y_affine, np.float64), np.asarray(Y)
-    shape = tuple(int(v) for v in grid[0])
-    geometry = slice_geometry(shape, VR.world_affine_of(grid[1], grid[2]), values.shape, y_world)
-    return ThickInputs(values, geometry, shape, options)
+    return tuple(int(v) for v in grid[0]), VR.world_affine_of(grid[1], grid[2]), values, y_world
 
 
 def measure(inputs, ref, size, norm, device):

@@ -425,14 +425,17 @@ def predict_volume(args):
     --kspace_zero_filled / --thick_interp the baseline volume) goes next to the prediction; --known_multislice (mudiff_hip.multislice,
     section 5.28) is both at once, with multislice_<target>.json and --multislice_baseline.  --known_thick_volume (mudiff_hip.thick_volume,
     section 5.29) takes the measurement from a thick-slice file of its own geometry instead of --known_volume: the whole stack is sampled in
-    lockstep, with thick_volume_<target>.json and --thick_volume_baseline."""
+    lockstep, with thick_volume_<target>.json and --thick_volume_baseline.  --known_lowres_volume (mudiff_hip.lowres_volume, section 5.31) does
+    the same for a file that is coarser in all three axes, with lowres_volume_<target>.json and --lowres_volume_baseline."""
     evaluation, resampled, found = _load_eval_inputs(args)
     args = copy.copy(args)                               # the run's own copy: it carries the record of what the intake did
     args.evaluation_record = (resampled, found)          # (for _predict_volume's report: IntakeReport.add_evaluation)
     args.known_inputs = _load_known_inputs(args, found)  # (--known_volume: K and M on the prediction's grid, checked, or None)
     if args.known_inputs is not None:
         args.evaluation_record = (resampled + list(args.known_inputs.resampled), found)
-    args.thick_inputs = _load_thick_inputs(args, found)  # (--known_thick_volume: Y checked against the prediction's grid, or None)
+    from . import lowres_volume, thick_volume
+    args.thick_inputs = _load_own_grid_inputs(args, found, thick_volume)       # (--known_thick_volume: Y checked against the prediction's grid, or None)
+    args.lowres_inputs = _load_own_grid_inputs(args, found, lowres_volume)     # (--known_lowres_volume: likewise)
     from . import ops
     from .driver import effective_prec_plan
     plan = effective_prec_plan(args)
@@ -490,10 +493,10 @@ def _load_known_inputs(args, found):
                       torch.device(f'cuda:{args.gpu_chose}'), align=found.get('align'))
 
 
-def _load_thick_inputs(args, found):
-    """--known_thick_volume -> None, or thick_volume.ThickInputs: the file read and its geometry checked against the grid the prediction
-    will have (thick_volume.on_grid), before any checkpoint work.  A bad flag or geometry raises ValueError here."""
-    from . import thick_volume as TV
+def _load_own_grid_inputs(args, found, TV):
+    """A measurement given as a file on a grid of its own, TV = thick_volume (--known_thick_volume) or lowres_volume
+    (--known_lowres_volume) -> None, or TV's ThickInputs / LowresInputs: the file read and its geometry checked against the grid the
+    prediction will have (TV.on_grid), before any checkpoint work.  A bad flag or geometry raises ValueError here."""
     options = TV.options_from(args)
     if options is None:
         return None
@@ -671,6 +674,14 @@ def measurement_modes():
     return known_modes() + (thick_volume,)
 
 
+def sampling_modes():
+    """measurement_modes() and, after them, the mode whose file is coarser than the prediction in all three axes: --known_lowres_volume
+    (mudiff_hip.lowres_volume).  Every module that can put a constraint on the sampler, in the order their flags
+    are checked."""
+    from . import lowres_volume
+    return measurement_modes() + (lowres_volume,)
+
+
 def _known_region(args, ref, device):
     """--known_volume: (the run's known_region.KnownRegion, or None when K is measured in k-space or in thick slices instead: nothing
     is pasted; the one constraint that predict_slices and sample_ensemble take, or None), also left in args.known_region and
@@ -681,6 +692,11 @@ def _known_region(args, ref, device):
     if thick is not None:                                # --known_thick_volume: the measurement itself, nothing pasted (section 5.29)
         from . import thick_volume as TV
         args.constraint = TV.measure(thick, ref, int(args.image_size), args.norm, device)
+        return None, args.constraint
+    lowres = getattr(args, 'lowres_inputs', None)
+    if lowres is not None:                               # --known_lowres_volume: likewise, coarse in all three axes (section 5.31)
+        from . import lowres_volume as LV
+        args.constraint = LV.measure(lowres, ref, int(args.image_size), args.norm, device)
         return None, args.constraint
     if inputs is None:
         return None, None
@@ -705,7 +721,8 @@ def _measurement_outputs(args, write, put_together, aff, hdr, evaluation, device
     """--known_kspace / --known_thick / --known_multislice: the measurement's report (kspace_<t>.json, thick_<t>.json, multislice_<t>.json)
     next to the prediction, and under its flag its baseline (zero_filled_<t>.nii.gz, thick_interp_<t>.nii.gz,
     multislice_baseline_<t>.nii.gz), mapped to [0,1], through the prediction's own road
-    (`put_together`: a device [n,S,S] map -> the host volume as written); with an evaluation it is scored into metrics_<name>_<t>.json,
+    (`put_together`: a device [n,S,S] map -> the host volume as written; a baseline that is a host [X,Y,Z] array already, lowres_volume's,
+    is written as it is and scored once normalised by --norm as the ground truth is); with an evaluation it is scored into metrics_<name>_<t>.json,
     and where the measurement says so --through_plane measures it into through_plane_<name>_<t>.json.  Nothing without the flags."""
     meas = getattr(args, 'constraint', None)
     if meas is None or meas.tag is None:
@@ -718,19 +735,24 @@ def _measurement_outputs(args, write, put_together, aff, hdr, evaluation, device
         return
     name, volume = baseline
     line = '[' + name.replace('_', '-') + '] '
-    vol = put_together(ops.to_range_0_1(volume))
+    if isinstance(volume, np.ndarray):
+        vol = volume
+        scored = np.ascontiguousarray(normalise_volume(volume, args.norm), dtype=np.float32)
+        scored = ops.to_range_0_1(torch.from_numpy(scored).to(device)).cpu().numpy()
+    else:
+        vol = scored = put_together(ops.to_range_0_1(volume))
     path = os.path.join(args.output_dir, f'{name}_{target}.nii.gz')
     write(path, vol, aff, hdr)
     print(f'[{meas.tag}] wrote {path}')
     if evaluation is not None:
         from . import volume_metrics as VM
-        rep = VM.score_arrays(vol, evaluation[0], evaluation[1], None, args.slice_half_range, device, norm=args.norm)
+        rep = VM.score_arrays(scored, evaluation[0], evaluation[1], None, args.slice_half_range, device, norm=args.norm)
         for ln in VM.format_lines(rep):
             print(line + ln)
         print(f"[metrics] wrote {VM.write_json(rep, os.path.join(args.output_dir, f'metrics_{name}_{target}.json'))}")
     if meas.baseline_through_plane and getattr(args, 'through_plane', False):
         from . import volume_through_plane as TP
-        rep = TP.measure_arrays(vol, None if evaluation is None else evaluation[0], None, args.slice_half_range, device, norm=args.norm)
+        rep = TP.measure_arrays(scored, None if evaluation is None else evaluation[0], None, args.slice_half_range, device, norm=args.norm)
         print(line + TP.format_line(rep))
         print(f"[through-plane] wrote {TP.write_json(rep, os.path.join(args.output_dir, f'through_plane_{name}_{target}.json'))}")
 
@@ -937,8 +959,8 @@ def make_parser(prog='MU-Diff volume prediction (MI355X)'):
     add_calibration_flags(p)                # (also --prec_plan)
     from . import slice_coupling
     slice_coupling.add_flags(p)             # (--slice_coupling, --through_plane: in a late parser, VolumeParser.later())
-    for module in measurement_modes()[1:] + known_modes()[:1]:      # (each mode's flags in a late parser of its own; --known_volume's
-        module.add_flags(p)                                         # place, before the last, is pinned, so the later modes' came before it)
+    for module in sampling_modes()[-1:] + measurement_modes()[1:] + known_modes()[:1]:      # (each mode's flags in a late parser of its
+        module.add_flags(p)                 # own; the places of --known_volume's and --known_thick_volume's, the last two, are pinned, so the later modes' came before them)
     from . import ensemble
     ensemble.add_flags(p)                   # (--ensemble_quantiles, --ensemble_center, --coverage: in a further one)
     return p
@@ -963,7 +985,7 @@ def finish_args(p, args):
         ensemble.quantile_plan(args)                     # (its ValueError names the flag)
     except ValueError as e:
         p.error(str(e))
-    for module in measurement_modes():
+    for module in sampling_modes()[-1:] + measurement_modes():      # (--known_lowres_volume first: it refuses every other mode by its own name)
         try:
             module.options_from(args)                    # (its ValueError names the flag)
         except ValueError as e:
@@ -996,7 +1018,8 @@ def build_argparser(argv=None):
     mudiff_hip.volume_coverage; in one more), and --known_volume / --known_mask / --known_drop_slices /
     --known_resample, --known_kspace with the --kspace_* flags, --known_thick with the --thick_* flags and --known_multislice with the
     --multislice_* flags (known_modes(); DESIGN.md sections 5.24a - 5.28; each in a parser of its own before that last one), and
-    --known_thick_volume with the --thick_volume_* flags (measurement_modes(); section 5.29; likewise)."""
+    --known_thick_volume with the --thick_volume_* flags (measurement_modes(); section 5.29; likewise), and --known_lowres_volume with the
+    --lowres_volume_* flags (sampling_modes(); section 5.31; likewise)."""
     p = make_parser()
     return finish_args(p, p.parse_args(argv))
 
