@@ -384,9 +384,9 @@ int mud_lpips_u8(const uint8_t* pred, const uint8_t* gt, int n, int H, int W, co
  * Philox4x64-10 (numpy.random.Philox's algorithm and word order) with key (seed, 0x4D55444946460001) and counter
  * (e/4, s, (j << 32) | (step << 8) | kind, 0); lane l = e % 4 takes the word pair (w[2(l/2)], w[2(l/2)+1]) = (wa, wb),
  * u1 = ((wa >> 11) + 1) 2^-53, u2 = (wb >> 11) 2^-53, r = sqrt(-2 log u1), theta = 2 pi u2: r cos theta (even l), r sin theta (odd l),
- * in fp64, rounded once to fp32.  kind: 0 x_init, 1 z, 2 posterior noise, or 5 / 6 / 7 / 8 / 9: the draws of mud_kspace_constrain /
- * mud_slab_constrain / mud_slab_kspace_constrain / mud_band_constrain / mud_lowres_constrain, so that a caller can inject what those entries
- * draw (3 and 4, mud_known_constrain's, stay refused); step in
+ * in fp64, rounded once to fp32.  kind: 0 x_init, 1 z, 2 posterior noise, or 5 / 6 / 7 / 8 / 9 / 10: the draws of mud_kspace_constrain /
+ * mud_slab_constrain / mud_slab_kspace_constrain / mud_band_constrain / mud_lowres_constrain / mud_sense_constrain, so that a caller can
+ * inject what those entries draw, or 11: the measurement noise of mudiff_hip.sense (3 and 4, mud_known_constrain's, stay refused); step in
  * [0, 2^24); row_len > 0.
  * mud_ensemble_stats: samples [n][N][hw] -> mean, std [n][hw] (N >= 2, hw > 0): y = clamp(x*scale + shift, lo, hi) in fp32 (each step
  * rounded once, NaN kept), m = (sum_j y_j) / N and v = sum_j (y_j - m)^2 / (N - 1) in fp64 in sample order j = 0..N-1,
@@ -631,6 +631,46 @@ int mud_lowres_measure(const float* x, const mud_band_tables* tab_z, const mud_b
                        int W, int rows, float* work, float* ax, void* stream);
 /* mud_lowres_ws_floats: new (no counterpart in the reference) */
 int64_t mud_lowres_ws_floats(int sets, int n, int m_z, int m_y, int m_x);
+
+/* ---- sampling a target acquired accelerated on several coils (mudiff_hip.sense; GraphSampler.sample_keyed).
+ * S a power of two in [16, 512], F the unitary 2D DFT of mud_fft2_c2c.  maps: complex64 [map_rows][coils][S][S], the coil sensitivities
+ * C_c (map_rows 1: one set for every row, else rows); mask: uint8 [mask_rows][S][S], non-zero = measured, taken as it is (C_c x is
+ * complex: pass the pattern, not its Hermitian symmetrisation).  A x = (mask .* F(C_c x))_c, A^H z = Re sum_c conj(C_c) F^H z_c and
+ * N = A^H A.
+ * mud_sense_measure: y [rows][coils][S][S] complex64 = A x for x fp32 [rows][S][S]: rows forward with the multiply by C_c fused into the
+ *   load, then columns forward, the mask applied in the store.
+ * mud_sense_adjoint: out fp32 [rows][S][S] = A^H y (no mask: y is what mud_sense_measure gave, zero where nothing was measured).  y is
+ *   the transform's workspace and is OVERWRITTEN.  Columns inverse in place, then rows inverse with the coil sum in registers, coil 0 first.
+ * mud_sense_constrain: with a, s = a_tab[c], s_tab[c] at c = clamp(t[r] + toff, 0, ntab - 1) (clean: a = 1, s = 0, no draw) and eta as
+ *   for mud_kspace_constrain (mudiff_hip.ops.KIND_SENSE = 10 is this entry's kind),
+ *       b = N (x_new - s eta) - a ahy,    (I + lambda N) e = b by exactly `iters` conjugate-gradient steps from e = 0,    out = x_new - lambda e:
+ *   the minimiser of |x - x_new|^2 + lambda |A (x - s eta) - a y|^2 for ahy = A^H y (fp32 [rows][S][S]).  One application of N is three
+ *   launches (rows forward: the vector's formation fused into the load; columns forward, mask, inverse in LDS; rows inverse: the coil sum
+ *   in registers, q = p + lambda N p or b = N v - a ahy and the workgroup's partial of p.q or b.b fused into the store), one more per
+ *   iteration for e += alpha p, r -= alpha q and the partial of r.r, p = r + beta p being fused into the next rows-forward load.  Every
+ *   scalar is per row, summed in fp64 from the fp32 partials [row][tile] in tile order by each workgroup: no atomics, no host read, a
+ *   fixed sequence of 4 + 4 iters launches; a row's result depends on its own operands alone.  A row whose b is exactly 0, whose r.r
+ *   reaches exactly 0 or whose p.q is 0 is frozen from then on.  out = x_new's bits where lambda e compares equal to 0 (a zero mask,
+ *   zero maps, lambda = 0; a -0 included); out may be x_new.  cg_res[rows] = |r_iters| / |b|, 0 for a frozen row.  work:
+ *   mud_sense_ws_floats(rows, coils, S) floats of the caller's, overwritten (the spectra [rows][coils][S][S], r, p, q, e, the partials).
+ * mud_sense_ws_floats: the floats of work; -1 for a size that is refused.
+ * MUD_ERR_ARG before any launch for every refusal of mud_kspace_constrain, coils outside [1, MUD_SENSE_MAX_COILS], map_rows outside
+ * {1, rows}, iters outside [1, 64], a lambda that is negative or not finite, rows * coils * S * S >= 2^31, a null pointer that is needed,
+ * a misaligned operand (x_new, ahy, out, noise, work: 16 bytes; maps, y: 8) and a work that overlaps an operand.  Replaces nothing in
+ * the reference (it has no measurement model); new with section 5.32. */
+#define MUD_SENSE_MAX_COILS 32
+/* mud_sense_constrain: new (no counterpart in the reference) */
+int mud_sense_constrain(const float* x_new, const float* ahy, const uint8_t* mask, int mask_rows, const float* maps, int map_rows, int coils,
+                        float lambda, int iters, const float* noise, const int64_t* keys, uint64_t seed, int step, int kind, const int64_t* t,
+                        int toff, const float* a_tab, const float* s_tab, int ntab, int clean, float* out, float* cg_res, float* work, int rows,
+                        int S, void* stream);
+/* mud_sense_measure: new (no counterpart in the reference) */
+int mud_sense_measure(const float* x, const float* maps, int map_rows, int coils, const uint8_t* mask, int mask_rows, float* y, int rows, int S,
+                      void* stream);
+/* mud_sense_adjoint: new (no counterpart in the reference) */
+int mud_sense_adjoint(float* y, const float* maps, int map_rows, int coils, float* out, int rows, int S, void* stream);
+/* mud_sense_ws_floats: new (no counterpart in the reference) */
+int64_t mud_sense_ws_floats(int rows, int coils, int S);
 
 /* ---- through-plane roughness of a volume (mudiff_hip.volume_through_plane; the volume pipeline's --through_plane).
  * vol (fp32) and the optional mask (uint8, may be NULL: every voxel is inside; else non-zero is inside) are [Z, X, Y] with planes

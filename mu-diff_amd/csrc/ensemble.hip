@@ -25,9 +25,9 @@ __global__ __launch_bounds__(ES_THREADS) void k_randn_keyed(float* __restrict__ 
 
 extern "C" int mud_randn_keyed(float* out, int rows, int64_t row_len, const int64_t* keys, uint64_t seed, int step, int kind, void* stream) {
   MUD_REQUIRE(rows >= 0 && row_len > 0, "mud_randn_keyed: bad sizes (rows %d, row_len %lld)", rows, (long long)row_len);
-  MUD_REQUIRE((kind >= 0 && kind <= 2) || (kind >= 5 && kind <= 9),
+  MUD_REQUIRE((kind >= 0 && kind <= 2) || (kind >= 5 && kind <= 11),
               "mud_randn_keyed: kind must be 0 (x_init), 1 (z), 2 (posterior noise), 5 (k-space), 6 (thick slices), 7 (multislice), 8 (thick "
-              "volume) or 9 (low-resolution volume), got %d", kind);
+              "volume), 9 (low-resolution volume), 10 (multi-coil) or 11 (multi-coil measurement noise), got %d", kind);
   uint64_t word2;
   MUD_TRY(keyed_step_word2("mud_randn_keyed", step, kind, word2));
   MUD_REQUIRE(out && keys, "mud_randn_keyed: null pointer");

@@ -172,6 +172,10 @@ _SIGNATURES = {
                                    _I, _P, _I, _P, _P, _I, _I, _P, _P]),
     'mud_lowres_measure': (_I, [_P, C.POINTER(BandTables), C.POINTER(BandTables), C.POINTER(BandTables), _I, _I, _I, _P, _P, _P]),
     'mud_lowres_ws_floats': (_L, [_I, _I, _I, _I, _I]),
+    'mud_sense_constrain': (_I, [_P, _P, _P, _I, _P, _I, _I, _F, _I, _P, _P, C.c_uint64, _I, _I, _P, _I, _P, _P, _I, _I, _P, _P, _P, _I, _I, _P]),
+    'mud_sense_measure': (_I, [_P, _P, _I, _I, _P, _I, _P, _I, _I, _P]),
+    'mud_sense_adjoint': (_I, [_P, _P, _I, _I, _P, _I, _I, _P]),
+    'mud_sense_ws_floats': (_L, [_I, _I, _I]),
     'mud_volume_through_plane': (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _L, _P]),
     'mud_volume_census_ws_bytes': (_L, []),
     'mud_volume_census': (_I, [_P, _I, _I, _I, _I, _F, _F, C.POINTER(C.c_double), _I, _P, _P, _L, _P]),

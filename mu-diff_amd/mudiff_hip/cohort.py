@@ -32,7 +32,8 @@ come from the command line): known_<t>.json goes next to its prediction and the 
 --known_kspace, --known_thick or --known_multislice (and the --kspace_* / --thick_* / --multislice_* flags, all from the command line)
 that `known` volume was acquired undersampled in k-space, with thick slices or both instead (mudiff_hip.kspace, mudiff_hip.thick,
 mudiff_hip.multislice; DESIGN.md sections 5.26 - 5.28): kspace_<t>.json, thick_<t>.json or multislice_<t>.json goes next to the
-prediction, and a `known_mask` cell fails that subject.
+prediction, and a `known_mask` cell fails that subject.  --known_sense (and the --sense_* flags; mudiff_hip.sense, section 5.32) measures
+it through several coils instead, with sense_<t>.json.
 """
 from __future__ import annotations
 
@@ -272,7 +273,7 @@ def run(args, subjects, predict=None):
                     elif subject.known:                            # (the subject's --known_volume: mudiff_hip.known_region)
                         from . import known_region as KR
                         sargs.known_volume, sargs.known_mask = subject.known, subject.known_mask
-                        known = {module: module.options_from(sargs) for module in V.known_modes()}[KR]      # (each mode's own refusals;
+                        known = {module: module.options_from(sargs) for module in V.known_modes() + V.constraint_modes()[-1:]}[KR]      # (each mode's own refusals;
                                                                                                             #  K's options: known_region's)
                         sargs.known_inputs = KR.on_grid(raws[0], KR.read_inputs(known, options), known, options, gpu, align=found.get('align'))
                         report.add_evaluation(list(sargs.known_inputs.resampled), {})

@@ -1,11 +1,11 @@
-"""What the four ways of sampling a partly acquired target share (--known_volume, --known_kspace, --known_thick, --known_multislice;
-DESIGN.md section 5.24a): after every reverse step the result is projected onto what was measured, at that step's noise level, with a
+"""What the ways of sampling a partly acquired target share (--known_volume, --known_kspace, --known_thick, --known_multislice,
+--known_sense): after every reverse step the result is projected onto what was measured, at that step's noise level, with a
 keyed draw.
 
 A *prediction-level* constraint (Constraint: KnownVoxels here, kspace.KSpaceMeasurement, thick.ThickMeasurement,
-multislice.MultisliceMeasurement) describes the n slices one prediction samples; volume.predict_slices and ensemble.sample_ensemble form
+multislice.MultisliceMeasurement, sense.SenseMeasurement) describes the n slices one prediction samples; volume.predict_slices and ensemble.sample_ensemble form
 their batches from it and know nothing else of it.  Its for_rows gives the *batch-level* constraint of one captured batch (KnownRows,
-KSpaceRows, SlabRows, SlabKSpaceRows): `check(sampler)`, once, and `apply(sampler, x_new, keys_dev, seed, step, clean)`, one unchecked
+KSpaceRows, SlabRows, SlabKSpaceRows, SenseRows): `check(sampler)`, once, and `apply(sampler, x_new, keys_dev, seed, step, clean)`, one unchecked
 launch into sampler.x per executed step, for GraphSampler.sample_keyed.
 
 A constraint that couples the whole stack along z (thick_volume.BandMeasurement, --known_thick_volume; section 5.29) has no batch-level
@@ -226,6 +226,42 @@ class SlabKSpaceRows(collections.namedtuple('SlabKSpaceRows', 'multislice gids',
         ops.slab_kspace_constrain_into(sampler.x, x_new, *self.dev, sampler._ks_work, keys_dev, seed, step, ops.KIND_MULTISLICE, sampler.t, 0,
                                        *level_tables(sampler), clean=clean)
         sampler.thick_x_new = x_new          # what the last constraint was given (the graph's own buffer, until the next replay)
+
+
+class SenseRows(collections.namedtuple('SenseRows', 'ahy mask maps lam iters idx', defaults=(None,))):
+    """The batch-level constraint of a target acquired accelerated on several coils, for GraphSampler.
+    sample_keyed(constraint=): `ahy` fp32 [B,S,S] = A^H y, `mask` uint8 [1 or B,S,S] (as given: not symmetrised), `maps` complex64
+    [Nc,S,S] or [1 or B,Nc,S,S], `lam` and `iters` of the proximal step; `idx`: the local slices of the real rows
+    (sense.SenseMeasurement.for_rows; None from a caller's own tuple).  Leaves the workspace on the sampler (one per sampler and coil
+    count) and, after every step, sampler.sense_x_new and sampler.sense_cg_res [B] (on itself: `x_new`, and `cg_max`, the largest
+    sense_cg_res of the batch's steps so far)."""
+
+    def check(self, sampler):
+        B, H, W = sampler.B, sampler.H, sampler.W
+        if H != W or not ops.kspace_size_ok(H):
+            raise ValueError(f'GraphSampler.sample_keyed: sense needs a square grid whose size is a power of two in [16, 512], got {H} x {W}')
+        ahy, mask, maps, lam, iters = self[:5]
+        maps = maps[None] if maps.dim() == 3 else maps
+        if ahy.dtype != torch.float32 or tuple(ahy.shape) != (B, H, W) or mask.dtype != torch.uint8 or tuple(mask.shape) not in ((B, H, W), (1, H, W)) or \
+                maps.dtype != torch.complex64 or maps.dim() != 4 or maps.shape[0] not in (1, B) or tuple(maps.shape[2:]) != (H, W) or \
+                not 1 <= maps.shape[1] <= ops.SENSE_MAX_COILS:
+            raise ValueError(f'GraphSampler.sample_keyed: sense = (ahy fp32 {(B, H, W)}, mask uint8 [1 or {B}, {H}, {W}], maps complex64 '
+                             f'[1 or {B}, 1..{ops.SENSE_MAX_COILS}, {H}, {W}], ...), got {ahy.dtype} {tuple(ahy.shape)}, {mask.dtype} '
+                             f'{tuple(mask.shape)} and {maps.dtype} {tuple(maps.shape)}')
+        if not (float(lam) >= 0.0 and float(lam) < float('inf')) or not 1 <= int(iters) <= ops.SENSE_MAX_ITERS:
+            raise ValueError(f'GraphSampler.sample_keyed: sense needs a finite lambda >= 0 and iters in [1, {ops.SENSE_MAX_ITERS}], got {lam} and {iters}')
+        need = ops.sense_ws_floats(B, maps.shape[1], H)
+        if getattr(sampler, '_sense_work', None) is None or sampler._sense_work.numel() < need:
+            sampler._sense_work = torch.empty(need, device=sampler.x.device, dtype=torch.float32)
+            sampler.sense_cg_res = torch.zeros(B, device=sampler.x.device, dtype=torch.float32)
+        dev = sampler.x.device
+        self.dev = ahy.to(dev).contiguous(), mask.to(dev).contiguous(), maps.to(dev).contiguous(), float(lam), int(iters)
+
+    def apply(self, sampler, x_new, keys_dev, seed, step, clean):
+        ops.sense_constrain_into(sampler.x, x_new, *self.dev, sampler.sense_cg_res, sampler._sense_work, keys_dev, seed, step, ops.KIND_SENSE, sampler.t,
+                                 0, *level_tables(sampler), clean=clean)
+        sampler.sense_x_new = self.x_new = x_new      # what the last constraint was given (the graph's own buffer, until the next replay)
+        self.cg_max = sampler.sense_cg_res.clone() if step == 0 else torch.maximum(self.cg_max, sampler.sense_cg_res)      # over all steps
 
 
 def of_batch(constraint, known, known_mask, kspace, thick, resample):

@@ -208,12 +208,12 @@ def sampler_inputs(region, s0, s1, size, device):
 
 
 def constraint_for(region, s0, s1, size, args, device):
-    """What the samplers take for the run's K (mudiff_hip.constraints): under --known_thick, --known_kspace or --known_multislice K is
-    measured that way instead (thick.measure, kspace.measure, multislice.measure), else its known voxels themselves
+    """What the samplers take for the run's K (mudiff_hip.constraints): under --known_thick, --known_kspace, --known_multislice or
+    --known_sense K is measured that way instead (thick.measure, kspace.measure, multislice.measure, sense.measure), else its known voxels themselves
     (constraints.KnownVoxels of sampler_inputs)."""
-    from . import kspace, multislice, thick
+    from . import kspace, multislice, sense, thick
     from .constraints import KnownVoxels
-    for module, more in ((thick, ()), (kspace, (args.seed,)), (multislice, (args.seed,))):
+    for module, more in ((thick, ()), (kspace, (args.seed,)), (multislice, (args.seed,)), (sense, (args.seed,))):
         options = module.options_from(args)
         if options is not None:
             return module.measure(region, s0, s1, size, options, *more, device)

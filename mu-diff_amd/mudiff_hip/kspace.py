@@ -22,8 +22,8 @@ There is no final paste.  Consistency holds on the sampler's grid: kspace_<t>.js
 sampler's result before it is mapped to [0,1].  It survives the affine [0,1] map (away from the clip) and an ensemble's mean; it does
 not survive clipping, --resize_back, the median or the quantile maps.
 
-This is the single-coil, real-image, retrospective model of the research on guided accelerated acquisition.  Multi-coil complex raw
-data is out of scope.
+This is the single-coil, real-image, retrospective model of the research on guided accelerated acquisition.  A multi-coil
+acquisition is --known_sense (mudiff_hip.sense, section 5.32); complex raw data is out of scope.
 """
 from __future__ import annotations
 

@@ -1031,8 +1031,8 @@ def randn_keyed(rows_keys, row_len, seed, step, kind, out=None):
     rows_keys[r] = (slice, sample) (int64 [rows, 2], host or device): Philox4x64-10 + Box-Muller in fp64 (mud_randn_keyed).  `out`:
     a contiguous fp32 device tensor of rows * row_len elements to fill (any shape); without it the result lands on rows_keys's device
     (or the current one for host keys).  kind: KIND_X_INIT, KIND_Z or KIND_NOISE (or KIND_KSPACE / KIND_THICK / KIND_MULTISLICE /
-    KIND_BAND / KIND_LOWRES, to inject what ops.kspace_constrain / ops.slab_constrain / ops.slab_kspace_constrain / ops.band_constrain /
-    ops.lowres_constrain draw)."""
+    KIND_BAND / KIND_LOWRES / KIND_SENSE, to inject what ops.kspace_constrain / ops.slab_constrain / ops.slab_kspace_constrain /
+    ops.band_constrain / ops.lowres_constrain / ops.sense_constrain draw; KIND_SENSE_MEAS: the measurement noise of mudiff_hip.sense)."""
     k = check_keys(rows_keys)
     seed = _seed64(seed)
     rows, row_len = k.shape[0], int(row_len)
@@ -1655,6 +1655,121 @@ def lowres_measure(x, tables, out=None, work=None):
     _launch('lowres_measure', x.device, load().mud_lowres_measure, ptr(x), *tables.on(x.device), tables.y.n, tables.x.n, sets * tables.z.n, ptr(work),
             ptr(out), STREAM, nbytes=float(4 * sets * tables.z.n * (tables.y.nnz * tables.x.n + 2 * tables.y.m * tables.x.m)))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# sampling a target acquired accelerated on several coils (csrc/sense.hip, mudiff_hip.sense)
+KIND_SENSE = 10                      # the draw of mud_sense_constrain: the measurement's forward noise, in the image domain
+KIND_SENSE_MEAS = 11                 # the measurement noise of mudiff_hip.sense (--sense_noise): key (slice, coil), row length 2 S^2
+SENSE_MAX_COILS, SENSE_MAX_ITERS = 32, 64      # include/mudiff_hip.h: MUD_SENSE_MAX_COILS, the largest `iters`
+
+
+def sense_ws_floats(rows, coils, S):
+    """The floats of the workspace of sense_constrain for a batch of `rows` slices (mud_sense_ws_floats)."""
+    n = int(load().mud_sense_ws_floats(int(rows), int(coils), int(S)))
+    if n < 0:
+        raise MudiffHipError(f'sense_ws_floats: rows >= 1, coils in [1, {SENSE_MAX_COILS}] and S a power of two in [16, 512], got {rows}, {coils}, {S}')
+    return n
+
+
+def _sense_maps(name, maps, rows, S, mask=None):
+    """maps: complex64 [coils, S, S] (one set for every row) or [rows, coils, S, S]; mask: None or uint8 [1 or rows, S, S] -> (maps as
+    [map_rows, coils, S, S], mask), contiguous."""
+    if maps is None or maps.dtype != torch.complex64 or maps.dim() not in (3, 4) or tuple(maps.shape[-2:]) != (S, S) or \
+            (maps.dim() == 4 and maps.shape[0] not in (1, rows)) or not 1 <= maps.shape[-3] <= SENSE_MAX_COILS:
+        raise MudiffHipError(f'{name}: maps must be complex64 [coils, {S}, {S}] or [1 or {rows}, coils, {S}, {S}] with coils in [1, {SENSE_MAX_COILS}], '
+                             f'got {None if maps is None else (maps.dtype, tuple(maps.shape))}')
+    maps = (maps[None] if maps.dim() == 3 else maps).contiguous()
+    if maps.numel() // maps.shape[0] * rows >= 1 << 31:
+        raise MudiffHipError(f'{name}: rows * coils * S * S must be < 2^31, got {rows} x {tuple(maps.shape[1:])}')
+    if mask is not None and (mask.dtype != torch.uint8 or mask.dim() != 3 or mask.shape[0] not in (1, rows) or tuple(mask.shape[1:]) != (S, S)):
+        raise MudiffHipError(f'{name}: mask must be uint8 [1 or {rows}, {S}, {S}], got {mask.dtype} {tuple(mask.shape)}')
+    return maps, None if mask is None else mask.contiguous()
+
+
+def sense_measure(x, maps, mask, out=None):
+    """y = mask .* F(C_c x) per coil (mud_sense_measure; F: ops.fft2): x fp32 [rows, S, S], maps complex64 [coils, S, S] or [1 or rows,
+    coils, S, S], mask uint8 [1 or rows, S, S] (non-zero = measured; not symmetrised: C_c x is complex) -> complex64 [rows, coils, S, S]."""
+    require_gpu(x, maps, mask, out)
+    if x.dim() != 3:
+        raise MudiffHipError(f'sense_measure: x must be fp32 [rows, S, S], got {x.dtype} {tuple(x.shape)}')
+    rows, S = _kspace_grid('sense_measure', x)
+    if mask is None:
+        raise MudiffHipError('sense_measure: mask is needed')
+    maps, mask = _sense_maps('sense_measure', maps, rows, S, mask)
+    shape = (rows, maps.shape[1], S, S)
+    if out is not None and (out.dtype != torch.complex64 or tuple(out.shape) != shape or not out.is_contiguous()):
+        raise MudiffHipError(f'sense_measure: out must be a contiguous complex64 tensor of shape {shape}, got {out.dtype} {tuple(out.shape)}')
+    out = torch.empty(shape, device=x.device, dtype=torch.complex64) if out is None else out
+    _launch('sense_measure', x.device, load().mud_sense_measure, ptr(x.contiguous()), ptr(maps), int(maps.shape[0]), int(maps.shape[1]), ptr(mask),
+            int(mask.shape[0]), ptr(out), rows, S, STREAM, nbytes=float(out.numel() * 32))
+    return out
+
+
+def sense_adjoint(y, maps, out=None):
+    """Re sum_c conj(C_c) F^H y_c (mud_sense_adjoint): y complex64 [rows, coils, S, S] (kept: the launch works on a copy) -> fp32
+    [rows, S, S].  No mask: y is zero where nothing was measured."""
+    require_gpu(y, maps, out)
+    if y.dtype != torch.complex64 or y.dim() != 4 or y.shape[0] < 1 or y.shape[-1] != y.shape[-2] or not kspace_size_ok(y.shape[-1]):
+        raise MudiffHipError(f'sense_adjoint: y must be complex64 [rows, coils, S, S], S a power of two in [16, 512], got {y.dtype} {tuple(y.shape)}')
+    rows, coils, S = int(y.shape[0]), int(y.shape[1]), int(y.shape[-1])
+    maps, _ = _sense_maps('sense_adjoint', maps, rows, S)
+    if maps.shape[1] != coils:
+        raise MudiffHipError(f'sense_adjoint: y has {coils} coils, maps {int(maps.shape[1])}')
+    if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != (rows, S, S) or not out.is_contiguous()):
+        raise MudiffHipError(f'sense_adjoint: out must be a contiguous fp32 tensor of shape {(rows, S, S)}, got {out.dtype} {tuple(out.shape)}')
+    out = torch.empty((rows, S, S), device=y.device, dtype=torch.float32) if out is None else out
+    _launch('sense_adjoint', y.device, load().mud_sense_adjoint, ptr(y.clone(memory_format=torch.contiguous_format)), ptr(maps), int(maps.shape[0]), coils,
+            ptr(out), rows, S, STREAM, nbytes=float(y.numel() * 40))
+    return out
+
+
+def sense_constrain_into(out, x_new, ahy, mask, maps, lam, iters, cg_res, work, keys_dev, seed, step, kind, t, toff, a_tab, s_tab, clean=False,
+                         noise=None):
+    """Unchecked launch of mud_sense_constrain into `out` (fp32, contiguous, [rows, ..., S, S]; may be x_new): GraphSampler.sample_keyed
+    checks its operands once per batch, not once per step.  ahy: fp32 [rows, S, S]; mask: uint8 [1 or rows, S, S]; maps: complex64
+    [1 or rows, coils, S, S]; cg_res: fp32 [rows]; work: fp32, sense_ws_floats elements; keys_dev: through check_keys and on out's device
+    (None with `noise` or `clean`)."""
+    rows, S, coils = out.shape[0], out.shape[-1], maps.shape[1]
+    _launch('sense_constrain', out.device, load().mud_sense_constrain, ptr(x_new), ptr(ahy), ptr(mask), int(mask.shape[0]), ptr(maps), int(maps.shape[0]),
+            int(coils), float(lam), int(iters), *_level_args(noise, keys_dev, seed, step, kind, t, toff, a_tab, s_tab, clean), ptr(out), ptr(cg_res),
+            ptr(work), rows, S, STREAM, nbytes=float(out.numel() * (1 + int(iters)) * (40 * coils + 24)))
+    return out
+
+
+def sense_constrain(x_new, ahy, mask, maps, lam, iters, t, toff, a_tab, s_tab, *, noise=None, keys=None, seed=0, step=0, kind=KIND_SENSE,
+                    clean=False, out=None, work=None, cg_res=None):
+    """The data-consistency step of a multi-coil measurement (mud_sense_constrain).  With A x = (mask .* F(C_c x))_c, N = A^H A and
+    c = clamp(t[row] + toff, 0, len(a_tab) - 1), per slice
+        b = N (x_new - s_tab[c] * eta) - a_tab[c] * ahy,   (I + lam N) e = b by exactly `iters` CG steps from 0,   out = x_new - lam e
+    (clean: a = 1, s = 0): the minimiser of |x - x_new|^2 + lam |A (x - s eta) - a y|^2 for ahy = sense_adjoint(y).  x_new: fp32
+    [rows, S, S] or [rows, 1, S, S]; ahy: fp32 [rows, S, S]; mask, maps: as sense_measure takes them.  eta: `noise` (fp32, x_new's shape)
+    when given, else the keyed normal ops.randn_keyed gives keys[r] = (slice, sample) under (seed, step, kind), drawn in the kernel.
+    out: None (a new tensor), x_new (in place) or a contiguous fp32 tensor of the shape.  work: None or a contiguous fp32 workspace of
+    sense_ws_floats(rows, coils, S) elements (overwritten).  cg_res: None or a contiguous fp32 [rows] tensor that receives |r_iters| / |b|
+    (0 for a row whose iteration stopped early at an exact 0).  -> out, or (out, cg_res) where cg_res was given."""
+    require_gpu(x_new, ahy, mask, maps, noise, t, a_tab, s_tab, out, work, cg_res)
+    rows, S = _kspace_grid('sense_constrain', x_new)
+    if ahy is None or ahy.dtype != torch.float32 or tuple(ahy.shape) != (rows, S, S):
+        raise MudiffHipError(f'sense_constrain: ahy must be fp32 {(rows, S, S)}, got {None if ahy is None else (ahy.dtype, tuple(ahy.shape))}')
+    if mask is None:
+        raise MudiffHipError('sense_constrain: mask is needed')
+    maps, mask = _sense_maps('sense_constrain', maps, rows, S, mask)
+    lam, iters = float(lam), int(iters)
+    if not (lam >= 0.0 and math.isfinite(lam)) or not 1 <= iters <= SENSE_MAX_ITERS:
+        raise MudiffHipError(f'sense_constrain: lam must be finite and >= 0 and iters in [1, {SENSE_MAX_ITERS}], got {lam} and {iters}')
+    x_new, noise, out = _noise_and_out('sense_constrain', x_new, noise, out)
+    need = sense_ws_floats(rows, maps.shape[1], S)
+    if work is not None and (work.dtype != torch.float32 or work.numel() != need or not work.is_contiguous()):
+        raise MudiffHipError(f'sense_constrain: work must be a contiguous fp32 tensor of {need} elements')
+    if cg_res is not None and (cg_res.dtype != torch.float32 or tuple(cg_res.shape) != (rows,) or not cg_res.is_contiguous()):
+        raise MudiffHipError(f'sense_constrain: cg_res must be a contiguous fp32 [{rows}] tensor')
+    t, a_tab, s_tab, kd = _level_and_keys('sense_constrain', clean, t, a_tab, s_tab, noise, keys, rows, x_new.device)
+    work = torch.empty(need, device=x_new.device, dtype=torch.float32) if work is None else work
+    res = torch.empty(rows, device=x_new.device, dtype=torch.float32) if cg_res is None else cg_res
+    sense_constrain_into(out, x_new, ahy.contiguous(), mask, maps, lam, iters, res, work, kd, _seed64(seed), step, kind, t, toff, a_tab, s_tab, clean,
+                         noise)
+    return out if cg_res is None else (out, cg_res)
 
 
 # columns of volume_through_plane's sums (include/mudiff_hip.h: MUD_TP_*)

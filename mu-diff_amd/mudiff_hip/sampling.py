@@ -247,6 +247,8 @@ class GraphSampler:
         return (out, steps) if return_steps else out
 
     thick_x_new = None      # after sample_keyed with `thick`: the last step's result as the constraint received it (the graph's own buffer)
+    sense_x_new = None      # likewise after a constraints.SenseRows; sense_cg_res [B]: |r| / |b| of its last conjugate gradients
+    sense_cg_res = None
 
     def sample_keyed(self, cond1, cond2, cond3, keys, seed, n_time, coupling=None, known=None, known_mask=None, resample=1, kspace=None,
                      thick=None, constraint=None):

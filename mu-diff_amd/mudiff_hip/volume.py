@@ -426,7 +426,9 @@ def predict_volume(args):
     section 5.28) is both at once, with multislice_<target>.json and --multislice_baseline.  --known_thick_volume (mudiff_hip.thick_volume,
     section 5.29) takes the measurement from a thick-slice file of its own geometry instead of --known_volume: the whole stack is sampled in
     lockstep, with thick_volume_<target>.json and --thick_volume_baseline.  --known_lowres_volume (mudiff_hip.lowres_volume, section 5.31) does
-    the same for a file that is coarser in all three axes, with lowres_volume_<target>.json and --lowres_volume_baseline."""
+    the same for a file that is coarser in all three axes, with lowres_volume_<target>.json and --lowres_volume_baseline.  --known_sense
+    (mudiff_hip.sense, section 5.32) measures --known_volume through several coils and pulls every step towards that measurement by a
+    regularised conjugate-gradient step, with sense_<target>.json and --sense_baseline."""
     evaluation, resampled, found = _load_eval_inputs(args)
     args = copy.copy(args)                               # the run's own copy: it carries the record of what the intake did
     args.evaluation_record = (resampled, found)          # (for _predict_volume's report: IntakeReport.add_evaluation)
@@ -682,6 +684,14 @@ def sampling_modes():
     return measurement_modes() + (lowres_volume,)
 
 
+def constraint_modes():
+    """sampling_modes() and, after them, the mode that measures --known_volume through several coils: --known_sense (mudiff_hip.sense,
+    DESIGN.md section 5.32).  The functions before this one keep the contents the tests of their modes pin; this one is what the parser,
+    the refusals and the cohort visit."""
+    from . import sense
+    return sampling_modes() + (sense,)
+
+
 def _known_region(args, ref, device):
     """--known_volume: (the run's known_region.KnownRegion, or None when K is measured in k-space or in thick slices instead: nothing
     is pasted; the one constraint that predict_slices and sample_ensemble take, or None), also left in args.known_region and
@@ -718,9 +728,9 @@ def _assemble_map(p, shp, s0, s1, on_device):
 
 
 def _measurement_outputs(args, write, put_together, aff, hdr, evaluation, device):
-    """--known_kspace / --known_thick / --known_multislice: the measurement's report (kspace_<t>.json, thick_<t>.json, multislice_<t>.json)
-    next to the prediction, and under its flag its baseline (zero_filled_<t>.nii.gz, thick_interp_<t>.nii.gz,
-    multislice_baseline_<t>.nii.gz), mapped to [0,1], through the prediction's own road
+    """--known_kspace / --known_thick / --known_multislice / --known_sense: the measurement's report (kspace_<t>.json, thick_<t>.json,
+    multislice_<t>.json, sense_<t>.json) next to the prediction, and under its flag its baseline (zero_filled_<t>.nii.gz,
+    thick_interp_<t>.nii.gz, multislice_baseline_<t>.nii.gz, sense_baseline_<t>.nii.gz), mapped to [0,1], through the prediction's own road
     (`put_together`: a device [n,S,S] map -> the host volume as written; a baseline that is a host [X,Y,Z] array already, lowres_volume's,
     is written as it is and scored once normalised by --norm as the ground truth is); with an evaluation it is scored into metrics_<name>_<t>.json,
     and where the measurement says so --through_plane measures it into through_plane_<name>_<t>.json.  Nothing without the flags."""
@@ -959,8 +969,9 @@ def make_parser(prog='MU-Diff volume prediction (MI355X)'):
     add_calibration_flags(p)                # (also --prec_plan)
     from . import slice_coupling
     slice_coupling.add_flags(p)             # (--slice_coupling, --through_plane: in a late parser, VolumeParser.later())
-    for module in sampling_modes()[-1:] + measurement_modes()[1:] + known_modes()[:1]:      # (each mode's flags in a late parser of its
-        module.add_flags(p)                 # own; the places of --known_volume's and --known_thick_volume's, the last two, are pinned, so the later modes' came before them)
+    for module in sampling_modes()[-1:] + known_modes()[1:] + constraint_modes()[-1:] + measurement_modes()[-1:] + known_modes()[:1]:
+        module.add_flags(p)                 # (each mode's flags in a late parser of its own; the places of --known_volume's and
+                                            #  --known_thick_volume's, the last two, are pinned, so the later modes' came before them)
     from . import ensemble
     ensemble.add_flags(p)                   # (--ensemble_quantiles, --ensemble_center, --coverage: in a further one)
     return p
@@ -985,7 +996,8 @@ def finish_args(p, args):
         ensemble.quantile_plan(args)                     # (its ValueError names the flag)
     except ValueError as e:
         p.error(str(e))
-    for module in sampling_modes()[-1:] + measurement_modes():      # (--known_lowres_volume first: it refuses every other mode by its own name)
+    for module in constraint_modes()[:-3:-1] + measurement_modes():      # (--known_sense, then --known_lowres_volume: each refuses every mode
+                                                                         #  before it by its own name)
         try:
             module.options_from(args)                    # (its ValueError names the flag)
         except ValueError as e:
@@ -1019,7 +1031,8 @@ def build_argparser(argv=None):
     --known_resample, --known_kspace with the --kspace_* flags, --known_thick with the --thick_* flags and --known_multislice with the
     --multislice_* flags (known_modes(); DESIGN.md sections 5.24a - 5.28; each in a parser of its own before that last one), and
     --known_thick_volume with the --thick_volume_* flags (measurement_modes(); section 5.29; likewise), and --known_lowres_volume with the
-    --lowres_volume_* flags (sampling_modes(); section 5.31; likewise)."""
+    --lowres_volume_* flags (sampling_modes(); section 5.31; likewise), and --known_sense with the --sense_* flags (constraint_modes();
+    section 5.32; likewise)."""
     p = make_parser()
     return finish_args(p, p.parse_args(argv))
 
